@@ -27,6 +27,9 @@ tokens/s (prefill).
 --gpus N > 1 (launched through torch.distributed.run, one rank per GPU, RCCL): weight ROWS are sharded over the ranks
 (tile-aligned), the integer path needs no reduction, and the only exchange step is an all-gather of each produced activation
 block before the next LUT build; total work is fixed, so "scaling" is "strong".
+
+A plain run sets up, warms up, times --steps steps and prints the line; --full adds everything measured or checked beside the headline
+figure (oracle check, CPU baseline, per-kernel roofline figures, the dependent chain, the prefill twin, the other decode workloads).
 """
 from __future__ import annotations
 
@@ -71,6 +74,22 @@ def algorithmic_bytes(Mw, K, bits, gs, ags, zp, mg, N=1):
     return Mw * K * bits // 8 + sc + N * (K // 4) * 16 + N * g * 4 + N * Mw * 2
 
 
+DUMP_BYTES = 64_000_000
+
+
+def dump_outputs(dirname, arrays):
+    """--dump-outputs: every array as dirname/<name>.npy in float32.  Above DUMP_BYTES in all, each array is cut down to the same share of
+    its elements, drawn without replacement by np.random.default_rng(0) from the flattened array and kept in index order."""
+    os.makedirs(dirname, exist_ok=True)
+    total = sum(a.size for a in arrays.values()) * 4
+    for name, a in arrays.items():
+        a = np.ascontiguousarray(a, dtype=np.float32)
+        if total > DUMP_BYTES:
+            k = max(1, a.size * (DUMP_BYTES - 4096 * len(arrays)) // total)
+            a = a.reshape(-1)[np.sort(np.random.default_rng(0).choice(a.size, size=k, replace=False))]
+        np.save(os.path.join(dirname, name + ".npy"), a)
+
+
 def parse():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -88,12 +107,12 @@ def parse():
                     help="independent: SURVEY 8(d)'s measurement -- the token's GEMVs back to back over distinct weights, every call reading a vector "
                          "that is resident before the launch (LUT builds included): the timed workload of a decode line since round 6; chained: "
                          "the calls linked by real data (x1 = q, x2 = o, x3 = gate, next x0 = down: every call waits for its predecessor inside one "
-                         "persistent launch) -- rounds 1-5 timed this stricter form, a default run still measures it and reports it as "
-                         "`dependent_chain`; auto (default): independent + the extras of the default line; "
+                         "persistent launch) -- rounds 1-5 timed this stricter form, --full still measures it and reports it as "
+                         "`dependent_chain`; auto (default): independent (with --full, plus the extra measurements beside it); "
                          "decoder: the calls as a decoder issues them -- residual add + RMSNorm and silu(gate) * up inside the chain "
                          "(tmac_hip_chain_xform), one launch per segment o -> gate/up -> down -> next q/k/v, an outside kernel (stand-in for "
                          "attention) between the segments; hipGraph replay of the token's launches")
-    ap.add_argument("--no-decoder-pattern", action="store_true", help="skip the decoder-pattern measurement of the default line")
+    ap.add_argument("--no-decoder-pattern", action="store_true", help="--full: skip the decoder-pattern measurement beside the timed workload")
     ap.add_argument("--stream-calls", type=int, default=96, help="independent GEMVs per launch of roofline.stream_core / stream_by_shape (distinct weight sets)")
     ap.add_argument("--clock-ramp-ms", type=float, default=100.0, help="decode workloads: GPU milliseconds of the step run untimed in front of the warm-up steps (0: off)")
     ap.add_argument("--no-stream-core", action="store_true", help="skip roofline.stream_core (profiling passes: keeps the kernel's statistics to the timed launches)")
@@ -114,6 +133,15 @@ def parse():
                          "N > 1 orchestration (row shards, recorded exchange steps, IPC export / connect, trial launches) on a one-GPU box.  Times mean nothing.")
     ap.add_argument("--gemm-kernel", type=int, default=0, choices=[0, 1, 2, 3],
                     help="prefill A/B: tmac_hip_debug_gemm_kernel (0 auto, 1 k_gemm_onehot, 2 / 3 k_gemm_planes with eight- / four-wave workgroups)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check everything beside the headline figure: the oracle check of the timed path, the CPU baseline, "
+                         "per-kernel roofline figures (headline GEMV, stream core, independent / decoder patterns, dense fp16), the dependent chain, "
+                         "the prefill twin and the other decode workloads.  Without it a run sets up, warms up, times the steps and prints the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the timed path computed in its last step as DIR/<name>.npy (float32; per output "
+                         "group, stacked over the layers that have buffers of their own; a fixed seeded sample where the total exceeds 64 MB).  "
+                         "A chained step reads its predecessor's output: on one GPU the W + K steps start again from the seeded input after the "
+                         "clock ramp.  With several ranks, rank 0 writes its row shard; the measurements --full adds write nothing")
     a = ap.parse_args()
     wl = WORKLOADS[a.workload]
     if a.steps is None:
@@ -707,7 +735,7 @@ def run(args, env):
     ops_per_step *= args.layers
     lvl = (2 ** BITS - 1) / 2.0 - 2 ** (BITS - 1)                # mean weight level minus the offset 2^(b-1)
     wvar = (4 ** BITS - 1) / 12.0                                 # variance of a uniform b-bit level
-    keep_host = not args.no_verify and world == 1
+    keep_host = args.full and not args.no_verify and world == 1
     def new_weights(Mloc, K, cfg, keep=None):
         """one synthetic matrix in the reference layout, registered (re-tiled on the GPU); keep: list that receives the host copy"""
         A = torch.randint(0, 256, (Mloc * BITS // BM, K // 4, BM // 2), dtype=torch.uint8, device=dev, generator=gen)
@@ -759,6 +787,7 @@ def run(args, env):
     xdim = {slot: K for name, Mw, K, cnt, slot in MATS}
     shp = (lambda k: (k,)) if decode else (lambda k: (N, k))
     x = {s: torch.randn(shp(xdim[s]), device=dev, generator=gen).half() for s in xdim}
+    x_seed = x[MATS[0][4]].clone()       # the chained patterns' first input as seeded (a step overwrites it with its last output)
     outs = {name: [torch.empty(shp(shard_rows[name]), dtype=torch.float16, device=dev) for _ in range(cnt)]
             for name, Mw, K, cnt, slot in MATS}
     gathered = {name: torch.empty((world,) + shp(shard_rows[name]), dtype=torch.float16, device=dev) for name, *_ in MATS}
@@ -1066,6 +1095,10 @@ def run(args, env):
                 break
         clock_ramp = {"untimed_steps": n_ramp, "untimed_ms": round(cr0.elapsed_time(cr2), 1), "first_%d_steps_after_idle_ms_per_step" % args.steps: round(first_ms / args.steps, 4),
                       "what": "the step run untimed until the GPU's clocks reach their steady state under this load, in front of the W warm-up and K timed steps"}
+        if args.pattern == "chained" and dpat is None and world == 1:
+            # a chained step reads the previous step's output, and the ramp's step count follows the clock: the W + K steps start from the
+            # seeded input again, so that the last step computes the same thing in every run with the same arguments
+            step_in[0].copy_(x_seed)
     for _ in range(args.warmup):
         run_step()
     barrier()
@@ -1104,6 +1137,16 @@ def run(args, env):
         dt = float(t.item())
     ms_per_step = dt / args.steps * 1e3
     finite = bool(torch.isfinite((dpat["keep"][3][-1]["down"][0] if dpat is not None else outs["down"][0]).float()).all().item())     # the chained activations stayed finite
+    if args.dump_outputs and rank == 0:
+        if dpat is not None:
+            # decoder pattern: every segment's outputs and the residual stream after every layer (bo[0] holds only the first q/k/v)
+            bo, hs = dpat["keep"][3], dpat["keep"][1]
+            groups = {name: [bo[li][name] for li in range(len(bo)) if li > 0 or name == "qkv"] for name in outs}
+            groups["hidden"] = [[h] for h in hs]
+        else:
+            # independent pattern: every layer writes buffers of its own; chained: all layers share one set, which holds the last layer's
+            groups = {name: [ol[name] for ol in (outs_l if args.pattern == "independent" else [outs])] for name in outs}
+        dump_outputs(args.dump_outputs, {name: np.stack([np.stack([t.float().cpu().numpy() for t in ts]) for ts in g]) for name, g in groups.items()})
 
     def time_headline_launches(graph_ok):
         """back-to-back stand-alone launches of the GEMV on the headline shape (the down projection of every layer: distinct
@@ -1164,7 +1207,7 @@ def run(args, env):
         roof["dense_equivalent"] = {"TFLOPs": round(dense_flop / (ev_ms_per_step * 1e-3) / 1e12, 1), "peak": 2500.0,
                                     "frac": round(dense_flop / (ev_ms_per_step * 1e-3) / 1e12 / 2500.0, 4),
                                     "what": "2 x rows x K x N per matrix over the same time, against the dense bf16 MFMA peak (MI355X_MICROARCH.md)"}
-        if not dist_on:
+        if not dist_on and args.full:
             measure_dense_fp16(ctx, roof, ev_ms_per_step)
     elif args.path == "chain":
         ach = bytes_per_step / (ev_ms_per_step * 1e-3) / 1e9
@@ -1183,17 +1226,18 @@ def run(args, env):
         # BASELINE.json's target shape as a kernel of its own (outside the timed region): the down projection of every layer,
         # LUT build fused, back-to-back launches over distinct weights replayed from a hipGraph
         name, Mw, K, cnt, slot = MATS[3]
-        hdurs, _ = time_headline_launches(True)
-        hb = algorithmic_bytes(Mw, K, BITS, GS, ags_of(K), ZP, MG)
-        hus = float(np.mean(hdurs)) * 1e6
-        roof["headline_gemv"] = {"shape": f"{Mw}x{K} N=1 (k_gemv_quad, LUT build fused, one launch per GEMV)", "us": round(hus, 3),
-                                 "min_us": round(float(np.min(hdurs)) * 1e6, 3), "algorithmic_bytes": hb,
-                                 "GBps": round(hb / hus * 1e-3, 1), "frac": round(hb / hus * 1e-3 / HBM_PEAK_GBS, 4),
-                                 "timing": "hipEvent pair around %d back-to-back launches (distinct weights, hipGraph replay), mean of 10" % args.layers}
+        if args.full:
+            hdurs, _ = time_headline_launches(True)
+            hb = algorithmic_bytes(Mw, K, BITS, GS, ags_of(K), ZP, MG)
+            hus = float(np.mean(hdurs)) * 1e6
+            roof["headline_gemv"] = {"shape": f"{Mw}x{K} N=1 (k_gemv_quad, LUT build fused, one launch per GEMV)", "us": round(hus, 3),
+                                     "min_us": round(float(np.min(hdurs)) * 1e6, 3), "algorithmic_bytes": hb,
+                                     "GBps": round(hb / hus * 1e-3, 1), "frac": round(hb / hus * 1e-3 / HBM_PEAK_GBS, 4),
+                                     "timing": "hipEvent pair around %d back-to-back launches (distinct weights, hipGraph replay), mean of 10" % args.layers}
         # The streaming core alone: ONE persistent launch over the headline GEMV of every layer (distinct weights >
         # MALL), every call fed by the same external vector -- no hand-off anywhere, so what is left is activation fetch, LUT build,
         # lookups, reduction and publish of a workgroup, call after call.  Separates "issue / structure bound" from "latency bound".
-        if not dist_on and not args.no_stream_core:
+        if args.full and not dist_on and not args.no_stream_core:
             # SURVEY 8(d)'s headline measurement: back-to-back INDEPENDENT GEMVs of the target shape over rotating distinct weights (> MALL in
             # total), a distinct activation vector per call.  Nothing is handed over, so the recording runs in stream mode: tables once per
             # call by k_lut_images (the reference's llama_cpp_init), lookups by k_gemv_stream (its llama_cpp_compute); both launches timed.
@@ -1202,10 +1246,10 @@ def run(args, env):
         # With several ranks: every rank streams ITS row shard of every matrix, nothing is exchanged (rows split, K whole, vectors resident on
         # every rank) -- the decode-side workload that scales by construction, reported beside the dependent chain's value as
         # roofline.independent_pattern (n_gpus ranks, aggregate bytes over the slowest rank's time)
-        if (not args.no_stream_core) and decode and args.path == "chain" and dpat is None and args.pattern != "independent":
+        if args.full and (not args.no_stream_core) and decode and args.path == "chain" and dpat is None and args.pattern != "independent":
             measure_independent_pattern(ctx, roof)
         # the same matrices as a decoder issues them (outside the timed region; --pattern decoder makes it the timed workload)
-        if not dist_on and dpat is None and args.pattern == "chained" and not args.no_decoder_pattern:
+        if args.full and not dist_on and dpat is None and args.pattern == "chained" and not args.no_decoder_pattern:
             try:
                 dms, dok, dn, dgraphed, dout = time_decoder_pattern(ctx)
                 roof["decoder_pattern"] = {"what": "one launch per segment (o -> gate/up -> down -> next q/k/v; residual add + RMSNorm and silu(gate) * up inside the "
@@ -1240,7 +1284,7 @@ def run(args, env):
             roof["per_call_from_stamps"] = per
             roof["headline_gemv_inside_chain"] = {"shape": f"{Mw}x{K} (the down projection inside the launch)", "us": per["down"]["us"],
                                                   "GBps": round(hb / (per["down"]["us"] * 1e-6) / 1e9, 1), "frac": round(hb / (per["down"]["us"] * 1e-6) / 1e9 / HBM_PEAK_GBS, 4)}
-    else:
+    elif args.full:
         # per-launch paths: the headline GEMV is the dominant kernel
         name, Mw, K, cnt, slot = MATS[3]
         durs, reps = time_headline_launches(use_graph)
@@ -1302,7 +1346,7 @@ def run(args, env):
                        "gemm_per_step": 7 * args.layers,
                        "launches_per_step": (len(dpat["chains"]) if dpat is not None else (2 if is_stream else 1)) if args.path == "chain" else (4 if fused_calls else 11) * args.layers + (0 if decode else 4 * args.layers), "path": args.path,
                        "pattern": args.pattern,
-                       **({"outside_ms": (lambda v: None if v is None else round(v, 4))(time_outside_ops(ctx, dpat["dstep"]))} if dpat is not None else {}),
+                       **({"outside_ms": (lambda v: None if v is None else round(v, 4))(time_outside_ops(ctx, dpat["dstep"]) if args.full else None)} if dpat is not None else {}),
                        "autotune": tuned,
                        "algorithmic_bytes_per_step": bytes_per_step, "weights": wl["weights"],
                        "parallelism": f"row-shard x{world}" if world > 1 else "single GPU",
@@ -1319,12 +1363,12 @@ def run(args, env):
             "event_ms_per_step": round(ev_ms_per_step, 4),
             "cpu_baseline": None,
         }
-        if world == 1 and not args.no_cpu_baseline and decode:
+        if args.full and world == 1 and not args.no_cpu_baseline and decode:
             try:
                 res["cpu_baseline"] = cpu_baseline(args.workload)
             except Exception as e:  # the baseline is a reported extra, never a reason to lose the GPU number
                 res["cpu_baseline"] = {"error": repr(e)}
-        elif world == 1 and not args.no_cpu_baseline:
+        elif args.full and world == 1 and not args.no_cpu_baseline:
             try:
                 res["cpu_baseline"] = cpu_baseline_prefill(args.workload)
             except Exception as e:
@@ -1343,6 +1387,15 @@ def run(args, env):
     except Exception:
         pass
     return res
+
+
+def extra_run_args(args):
+    """arguments of a measurement that --full adds beside the timed run: a copy that dumps nothing (--dump-outputs holds the timed path's
+    outputs alone)"""
+    import copy
+    a2 = copy.copy(args)
+    a2.dump_outputs = None
+    return a2
 
 
 PREFILL_TWIN = {"llama2-7b-w2": "llama2-7b-w2-prefill", "llama2-7b-w4": "llama2-7b-w4-prefill", "bitnet-3b": "bitnet-3b-prefill"}
@@ -1385,9 +1438,8 @@ def main():
     # LUT build per call and CU; with ranks: hand-off granules stored into every rank's IPC-mapped arena).  Measured in the same run, same
     # matrices' shapes and bytes, verified against the oracle, reported as `dependent_chain`; the decoder pattern (one launch per segment
     # between two attentions) rides in that run.
-    if auto and decode_wl and args.path in ("auto", "chain") and args.variant == 0 and not args.stamps:
-        import copy
-        a2 = copy.copy(args)
+    if args.full and auto and decode_wl and args.path in ("auto", "chain") and args.variant == 0 and not args.stamps:
+        a2 = extra_run_args(args)
         a2.pattern, a2.path = "chained", "chain"
         a2.steps, a2.warmup, a2.no_cpu_baseline, a2.no_stream_core = max(args.steps // 3, 50), 10, True, True
         try:
@@ -1409,9 +1461,8 @@ def main():
     # Scaling headline.  Decode is a chain of dependent GEMVs whose hand-off and LUT build do not shrink with the number of GPUs (DESIGN 6:
     # 1.3 / 1.6 / 1.9 x at 2 / 4 / 8 by the model); the prefill GEMM of the same matrices (N = 256, BASELINE config 5) is compute-bound and
     # splits by rows with one all-gather per call -- so a multi-GPU run also measures it, on the same ranks, and rank 0 reports both.
-    if world > 1 and WORKLOADS[args.workload]["N"] == 1 and args.workload in PREFILL_TWIN and not args.no_prefill_headline:
-        import copy
-        a2 = copy.copy(args)
+    if args.full and world > 1 and WORKLOADS[args.workload]["N"] == 1 and args.workload in PREFILL_TWIN and not args.no_prefill_headline:
+        a2 = extra_run_args(args)
         a2.workload, a2.path, a2.pattern = PREFILL_TWIN[args.workload], "auto", "chained"
         a2.steps, a2.warmup, a2.no_cpu_baseline, a2.no_verify, a2.stamps = 10, 2, True, True, False
         a2.layers = min(args.layers, WORKLOADS[a2.workload]["layers"])
@@ -1426,12 +1477,11 @@ def main():
             head = {"error": repr(e)}
         if res is not None:
             res["prefill_scaling_headline"] = head
-    # One GPU: the prefill twin rides along in the default line too (N = 256 over the same matrices, with its graph-replayed dense fp16 baseline),
-    # so that the driver's own run carries a prefill number, not only the builder's.  Outside the timed region.
-    if (world == 1 and not dist_on and res is not None and WORKLOADS[args.workload]["N"] == 1 and args.workload in PREFILL_TWIN
+    # One GPU, --full: the prefill twin rides along in the decode line (N = 256 over the same matrices, with its graph-replayed dense fp16 baseline),
+    # so that a decode run carries a prefill number too.  Outside the timed region.
+    if (args.full and world == 1 and not dist_on and res is not None and WORKLOADS[args.workload]["N"] == 1 and args.workload in PREFILL_TWIN
             and not args.no_prefill_headline and auto and not args.stamps):
-        import copy
-        a2 = copy.copy(args)
+        a2 = extra_run_args(args)
         a2.workload, a2.path, a2.pattern = PREFILL_TWIN[args.workload], "auto", "chained"
         a2.steps, a2.warmup, a2.no_cpu_baseline, a2.no_verify = 30, 5, True, True
         a2.layers = min(args.layers, WORKLOADS[a2.workload]["layers"])
@@ -1443,16 +1493,15 @@ def main():
                                    "dense_fp16_baseline": r2r.get("dense_fp16_baseline")}
         except BaseException as e:      # the decode number is never lost to the extra measurement
             res["prefill_twin"] = {"error": repr(e)}
-    # ... and so do the other two decode configurations of BASELINE.json (W4 GPTQ-style, BitNet-b1.58-3B): the same two measurements (the token's
-    # calls as independent calls; as one dependent chain), 200 launches each, outside the timed region, so that the driver's run carries them
-    if (world == 1 and not dist_on and res is not None and args.workload == "llama2-7b-w2" and auto and args.path in ("auto", "chain")
+    # ... and so, with --full, do the other two decode configurations of BASELINE.json (W4 GPTQ-style, BitNet-b1.58-3B): the same two measurements (the token's
+    # calls as independent calls; as one dependent chain), 200 launches each, outside the timed region, so that a --full run carries them
+    if (args.full and world == 1 and not dist_on and res is not None and args.workload == "llama2-7b-w2" and auto and args.path in ("auto", "chain")
             and not args.no_prefill_headline and not args.stamps and args.layers == WORKLOADS[args.workload]["layers"]):
-        import copy
         res["other_decode_workloads"] = {}
         for w2 in ("llama2-7b-w4", "bitnet-3b"):
             ent = {}
             for pat in ("independent", "chained"):
-                a2 = copy.copy(args)
+                a2 = extra_run_args(args)
                 a2.workload, a2.pattern, a2.path, a2.steps, a2.warmup, a2.no_cpu_baseline, a2.no_verify = w2, pat, "chain", 200, 10, True, True
                 a2.no_stream_core, a2.no_decoder_pattern, a2.layers = True, True, WORKLOADS[w2]["layers"]
                 try:

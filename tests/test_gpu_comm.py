@@ -196,7 +196,7 @@ def test_bench_ranks_share_the_device(tm, workload, extra, nranks):
     port = 29600 + (os.getpid() % 300)
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", str(nranks), "--master-addr", "127.0.0.1", "--master-port", str(port),
            os.path.join(ROOT, "bench.py"), "--gpus", str(nranks), "--share-device", "--workload", workload, "--layers", "2", "--steps", "5", "--warmup", "2",
-           "--no-cpu-baseline"] + extra
+           "--full", "--no-cpu-baseline"] + extra
     r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, (r.stdout[-2000:] + "\n" + r.stderr[-4000:])
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]

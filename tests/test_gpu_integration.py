@@ -158,13 +158,13 @@ def test_cmake_consumer_computes_a_gemv(tm, tmp_path):
 @pytest.mark.parametrize("extra,path", [([], "chain"), (["--force-dist"], "chain"), (["--path", "fused"], "fused"),
                                         (["--workload", "bitnet-3b"], "chain")])
 def test_bench_runs_and_verifies(tm, extra, path):
-    """bench.py end to end on two layers: ONE JSON line on stdout with the contract's keys, the timed path verified against the oracle
+    """bench.py --full end to end on two layers: ONE JSON line on stdout with the contract's keys, the timed path verified against the oracle
     inside the run; --force-dist takes the multi-GPU code path (recorded exchange steps, blob exchange, trial launches) with one rank"""
     import json
     import sys
     env = {k: v for k, v in os.environ.items() if k not in ("MASTER_ADDR", "RANK", "WORLD_SIZE", "LOCAL_RANK")}
     env["MASTER_PORT"] = "29577"
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--layers", "2", "--steps", "3", "--warmup", "1", "--no-cpu-baseline"] + extra,
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--layers", "2", "--steps", "3", "--warmup", "1", "--no-cpu-baseline"] + extra,
                        capture_output=True, timeout=600, env=env)
     assert r.returncode == 0, r.stderr.decode()[-2000:]
     lines = [l for l in r.stdout.decode().splitlines() if l.strip()]
@@ -189,6 +189,70 @@ def test_bench_runs_and_verifies(tm, extra, path):
         assert "error" not in tw and tw["value"] > 0 and tw["dense_fp16_baseline"]["ms_per_step"] > 0, tw
     if path == "chain":
         assert d["roofline"]["headline_gemv"]["us"] > 0
+
+
+def run_bench_dump(out_dir, args):
+    """bench.py on two layers with --dump-outputs out_dir; returns (result line, {file name: array})"""
+    import json
+    import sys
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--layers", "2", "--steps", "3", "--warmup", "1",
+                        "--dump-outputs", str(out_dir)] + args, capture_output=True, timeout=600)
+    assert r.returncode == 0, r.stderr.decode()[-2000:]
+    lines = [l for l in r.stdout.decode().splitlines() if l.strip()]
+    assert len(lines) == 1, lines
+    files = sorted(p.name for p in out_dir.iterdir())
+    assert files == ["down.npy", "gate_up.npy", "o.npy", "qkv.npy"], files
+    return json.loads(lines[0]), {f: np.load(out_dir / f) for f in files}
+
+
+@pytest.mark.parametrize("extra", [[], ["--workload", "llama2-7b-w2-prefill"], ["--pattern", "chained"]])
+def test_bench_plain_run_dumps_outputs(tm, tmp_path, extra):
+    """a plain bench.py run (no --full): the headline line alone, none of the extra measurements; --dump-outputs writes the timed
+    path's outputs of its last step, and a second run with the same arguments writes the same arrays.  --pattern chained: every
+    step reads its predecessor's output and the clock ramp's step count follows the clocks, so equal dumps need the timed steps to
+    start again from the seeded input"""
+    dumps = []
+    for i in range(2):
+        d, dump = run_bench_dump(tmp_path / f"run{i}", extra)
+        for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"):
+            assert k in d, k
+        assert d["steps"] == 3 and d["value"] > 0 and d["ms_per_step"] > 0 and d["activations_finite"]
+        assert d["cpu_baseline"] is None and d["verified"] is None
+        for k in ("dependent_chain", "prefill_twin", "other_decode_workloads"):
+            assert k not in d, k
+        for k in ("headline_gemv", "stream_core", "dense_fp16_baseline"):
+            assert k not in (d["roofline"] or {}), k
+        if "--pattern" in extra:
+            assert d["config"]["pattern"] == "chained" and d["clock_ramp"]["untimed_steps"] > 0, d["config"]
+        dumps.append(dump)
+    for f, a in dumps[0].items():
+        assert a.dtype == np.float32 and np.isfinite(a).all() and np.abs(a).max() > 0, f
+        assert np.array_equal(a, dumps[1][f]), f
+    # independent calls: every layer's outputs; chained: the last layer's (all layers share one set of buffers); prefill rows: N = 256
+    want = {0: (2, 2, 11008), 1: (1, 2, 256, 11008), 2: (1, 2, 11008)}[[[], ["--workload", "llama2-7b-w2-prefill"], ["--pattern", "chained"]].index(extra)]
+    assert dumps[0]["gate_up.npy"].shape == want
+
+
+def test_bench_dump_is_the_headline_path(tm, tmp_path):
+    """what --dump-outputs writes is the headline path's outputs: (a) --full --dump-outputs writes the same arrays as the plain run --
+    the measurements --full adds (dependent chain and prefill twin among them, other shapes) write nothing over them -- and that run's
+    oracle check of the timed path passes; (b) the same calls through the other launch path (one fused launch per call replayed from a
+    hipGraph instead of k_lut_images + k_gemv_stream) give the same outputs within the stream form's tolerance, slice by slice, while
+    distinct layers / matrices differ, so a dump of another buffer would not pass"""
+    dp, plain = run_bench_dump(tmp_path / "plain", [])
+    dfull, full = run_bench_dump(tmp_path / "full", ["--full", "--no-cpu-baseline"])
+    assert "error" not in dfull["dependent_chain"] and "error" not in dfull["prefill_twin"], dfull
+    assert dfull["verified"]["ok"], dfull["verified"]
+    for f in plain:
+        assert full[f].shape == plain[f].shape and np.array_equal(full[f], plain[f]), f
+    dfu, fused = run_bench_dump(tmp_path / "fused", ["--path", "fused"])
+    assert dp["config"]["path"] == "chain" and dfu["config"]["path"] == "fused" and dfu["config"]["pattern"] == "independent"
+    for f in plain:
+        a, b = plain[f].reshape(-1, plain[f].shape[-1]), fused[f].reshape(-1, fused[f].shape[-1])
+        assert a.shape == b.shape, f
+        for s in range(a.shape[0]):
+            assert np.abs(a[s] - b[s]).max() <= 2e-3 * np.abs(b[s]).max(), (f, s)
+        assert np.abs(a[0] - a[-1]).max() > 0.1 * np.abs(a[0]).max(), f
 
 
 def test_ggml_glue_decoder_segments(tm, tmp_path):
