@@ -7,7 +7,10 @@
 //   tmac_workspace.cpp   LUT workspace + the preprocessor entry point
 //   tmac_dispatch.cpp    qgemm_lut dispatch, the fused entry point, parity taps
 //   tmac_tuner.cpp       launch-configuration tuner of the decode kernel
-//   tmac_chain_host.cpp  recording / building / launching the persistent decode chain
+//   tmac_chain_host.cpp  recording and building the persistent decode chain (chain_build and its stages, the stream schedule)
+//   tmac_chain_launch.cpp  launching a built chain, IPC export / connect, status, info, taps, stamps
+//   tmac_defer.cpp       the deferred queue (tmac_hip_defer / tmac_hip_flush)
+//                        (the three share tmac_chain_host.h: struct tmac_hip_chain, the noted calls, chain_build)
 //   tmac_hostptr.cpp     the reference-named host-pointer entry points (struct HostRoute)
 //   tmac_comm.cpp        multi-GPU exchange step (RCCL)
 #pragma once
@@ -142,7 +145,7 @@ void release_fused_workspaces();   // caller holds g_mu
 // ---- tuner (tmac_tuner.cpp) -----------------------------------------------------------------------
 void tuned_config(const FusedArgs& fa, int total_q, int& ft, int& wpq);   // leaves ft / wpq alone when nothing is recorded
 
-// ---- decode chain (tmac_chain_host.cpp) -----------------------------------------------------------
+// ---- decode chain (tmac_chain_host.cpp) and deferred queue (tmac_defer.cpp) -----------------------------------------------------------
 bool chain_recording();            // is the calling thread between tmac_hip_chain_begin and tmac_hip_chain_end?
 void chain_clear_xform();          // drops a transform declared for the next recorded call (the call was rejected before it could be recorded)
 int32_t chain_record(const tmac_hip_weights* const* wl, int nmat, const void* B_dev, tmac_dtype_t act_dtype, void* const* C_list,
