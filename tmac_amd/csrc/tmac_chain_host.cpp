@@ -388,7 +388,7 @@ static int32_t describe_ops(const std::vector<ChainRecOp>& rec, const ChainFlow&
         for (size_t m = 0; m < r.w.size(); ++m) {
             const tmac_hip_weights* w = r.w[m];
             const Shape& a = w->s;
-            if (a.lay != 2 || !w->lo_ok || w->fa) return fail(TMAC_HIP_E_NOMATCH, "op %zu matrix %zu is not registered in the QUAD layout", i, m);
+            if (layout_of(a) != L_QUAD || !w->tiled_ok || w->fa) return fail(TMAC_HIP_E_NOMATCH, "op %zu matrix %zu is not registered in the QUAD layout", i, m);
             if (a.K != s0.K || a.bits != c.bits || a.gs != s0.gs || a.ags != s0.ags || a.zero_point != c.zp || a.m_groups != s0.m_groups ||
                 (w->sc_dtype == F16) != (c.sc_f16 != 0))
                 return fail(TMAC_HIP_E_ARG, "op %zu: the matrices of a chain share bits, zero points and scale dtype; those of an op also K and group size", i);

@@ -1,22 +1,53 @@
 // tmac_dispatch.cpp — qgemm_lut dispatch: which kernel serves a call (decode GEMV variants, the N > 1 GEMMs, the fused
-// LUT-build + GEMV entry point and its prefill route) and the parity taps around them.
+// LUT-build + GEMV entry point and its prefill route) and the parity taps around them.  A call is planned (plan_split /
+// plan_fused name the kernel: enum Route), then launched.
 #include "tmac_host.h"
 
 using namespace tmac_host;
 
+// ---- the plan: what runs -------------------------------------------------------------------------------------------------
+enum Route {
+    R_GEMM_PLANES,   // k_gemm_planes / k_gemm_planes_us on the workspace's LUT image
+    R_GEMM_ONEHOT,   // k_gemm_onehot on the half-table image
+    R_GEMV_QUAD,     // k_gemv_quad (QUAD layout)
+    R_GEMV_FUSED,    // k_gemv_fused (row-block layout)
+    R_GEMV_LO,       // k_gemv_lo (two-kernel path; v_mqsad or SDWA accumulate by the variant knob)
+    R_REF_LAYOUT,    // k_gemv_ref_layout on the reference blobs
+    R_ROW_LOOP       // fused entry point's last resort: one LUT build, then tmac_hip_qgemm_dev (plan_split) per matrix
+};
+// the LUT the fused entry point builds before the planned kernel (the split entry points find theirs in the workspace)
+enum LutBuild {
+    LB_NONE,         // none: the GEMV kernel builds its own
+    LB_IMAGE,        // k_gemm_planes' LUT image alone
+    LB_HALF_TABLES,  // the half-table image (qlut_lds) alone, two tables per lane: all that k_gemm_onehot and k_gemv_quad read
+    LB_ALL           // tmac_hip_preprocessor_dev: every layout of the workspace
+};
+struct Plan {
+    Route route;
+    LutBuild lut;
+    int32_t err;       // TMAC_HIP_OK, or the call is refused: fail(err, msg, mat)
+    const char* msg;   // (may name the offending matrix: %d)
+    int mat;
+};
+static Plan planned(Route r, LutBuild lut = LB_NONE) { return Plan{r, lut, TMAC_HIP_OK, nullptr, 0}; }
+static Plan refused(int32_t code, const char* msg, int mat = 0) { return Plan{R_ROW_LOOP, LB_NONE, code, msg, mat}; }
+
+// ---- predicates of the plan ------------------------------------------------------------------------------------------------
+// matrices that can be served from one LUT | by one kernel instantiation
+static bool same_lut(const tmac_hip_weights* a, const tmac_hip_weights* b) { return a->s.K == b->s.K && a->s.ags == b->s.ags; }
+static bool same_quant(const tmac_hip_weights* a, const tmac_hip_weights* b) {
+    return a->s.bits == b->s.bits && a->s.gs == b->s.gs && a->s.zero_point == b->s.zero_point && a->s.m_groups == b->s.m_groups &&
+           a->sc_dtype == b->sc_dtype;
+}
 // GEMM or row loop for N activation rows on matrices with total_Mw output rows?  An explicitly set threshold
 // (tmac_hip_set_gemm_min_n) is taken literally.  Otherwise: the measured crossover per launch where k_gemm_planes covers the
 // configuration (planes_pays), and k_gemm_onehot only from 32 rows on with a grid that fills the chip (onehot_pays: with fewer
 // than 128 workgroups of 128 bit-plane rows the row loop is faster up to 64 rows: 4096 x 11008 at N = 32: 88 us against 152 us).
-static bool planes_covers(const Shape& s) { return g_knobs.gemm_kernel != 1 && s.lay == 2 && s.ts == 8 && gemm_planes_supported(s); }
+static bool planes_covers(const Shape& s) { return g_knobs.gemm_kernel != 1 && layout_of(s) == L_QUAD && gemm_planes_supported(s); }
 static bool onehot_pays(const Shape& s, long total_Mw, int N) {
-    if (g_knobs.gemm_min_n <= 0) return false;
-    if (g_knobs.gemm_min_n != 32) return N >= g_knobs.gemm_min_n;
-    return N >= 32 && (N >= 64 || (total_Mw * s.bits + 127) / 128 >= 128);
+    return N >= gemm_min_rows(32) && (g_knobs.gemm_min_n != 32 || N >= 64 || (total_Mw * s.bits + 127) / 128 >= 128);
 }
-static bool planes_pays(const Shape& s, long total_Mw, int N) {
-    if (g_knobs.gemm_min_n <= 0) return false;
-    if (g_knobs.gemm_min_n != 32) return N >= g_knobs.gemm_min_n;
+static int planes_crossover(const Shape& s, long total_Mw, int N) {
     // From how many activation rows on k_gemm_planes beats the GEMV kernel looped over the rows: measured on MI355X, llama-2-7B shapes,
     // 1- to 4-bit weights (tools/bench_small_n.py, profiles/r03_small_n.txt).  The row loop costs ~3 us + N x (0.7 us + 0.155 us per MB
     // of weights + 0.2 us per 1000 of K beyond 4096); the GEMM (6 + 14 K / 4096) us per wave of 64 x 64 tiles (x 1.18 for 3- / 4-bit
@@ -26,20 +57,124 @@ static bool planes_pays(const Shape& s, long total_Mw, int N) {
     const double waves = tiles <= 256.0 ? 1.0 : s.bits == 4 ? (double)(((long)tiles + 255) / 256) : (s.bits == 3 ? 0.45 : 0.25) + tiles / 256.0;
     const double tp = (6.0 + 14.0 * s.K / 4096.0) * waves * (s.bits >= 3 ? 1.18 : 1.0);
     const double c1 = 0.7 + 0.155 * mb + 0.2 * (s.K > 4096 ? (s.K - 4096) / 1000.0 : 0.0);
-    int nmin = (int)((1.05 * tp - 3.0) / c1 + 0.999);
-    nmin = nmin < 4 ? 4 : nmin > 16 ? 16 : nmin;
-    return N >= nmin;
+    const int nmin = (int)((1.05 * tp - 3.0) / c1 + 0.999);
+    return nmin < 4 ? 4 : nmin > 16 ? 16 : nmin;
 }
+static bool planes_pays(const Shape& s, long total_Mw, int N) { return N >= gemm_min_rows(planes_crossover(s, total_Mw, N)); }
 // the fused entry point builds whatever LUT form the chosen kernel wants, so one question decides
 static bool gemm_pays(const Shape& s, long total_Mw, int N) { return planes_covers(s) ? planes_pays(s, total_Mw, N) : onehot_pays(s, total_Mw, N); }
-// one-hot MFMA GEMM over 1..4 matrices that share K, the quantisation config (checked by the callers) and the LUT in ws
+static bool planes_ok(const tmac_hip_weights* w) {
+    return planes_covers(w->s) && w->tiled_ok && !w->fa && w->w_bytes < ((size_t)1 << 31);
+}
+static bool planes_image_fits(const tmac_hip_workspace* ws, int K) { return ws->gimg && (size_t)2 * K * ws->gNpad < ((size_t)1 << 31); }
+
+// ---- the two planners ------------------------------------------------------------------------------------------------------
+// They read g_knobs and their arguments, take no lock, allocate nothing and launch nothing.  Today's routing, quirks included
+// (none of them is this file's to fix):
+//  * Split entry points (tmac_hip_qgemm_dev, the host-pointer C-ABI, the row loop below).  The weights' device layout decides which
+//    tiled kernel can run; the variant knob only picks V_REF_LAYOUT and the accumulate of k_gemv_lo.  Weights without a tiled kernel
+//    go to the reference layout whatever the knob says.  k_gemm_planes only when the workspace holds a valid LUT image of the kind
+//    the shape wants: tmac_hip_preprocessor_dev builds it from PLANES_MIN_N rows on (it does not know the matrix), while the
+//    crossover applied here is the measured one of the matrix -- between the two the image is built and not used, or wanted and not
+//    there.  Without the image only k_gemm_onehot's own, later crossover counts: below it the row loop is the faster kernel.  The
+//    image's K and N are not checked against the LUT the workspace holds (only gimg_valid and its kind are).
+//  * A tap bypasses k_gemm_planes on the split entry point, but not k_gemm_onehot, which has a per-plane tap of its own.  On the
+//    fused entry point a tap (dump / lut_tap) bypasses both GEMMs -- and, in fused_impl, recording and the deferred queue.
+//  * Fast-aggregation weights are accepted on V_REF_LAYOUT, V_LO_MQSAD and V_LO_SDWA only (registration puts them in the LO layout,
+//    so the refusal cannot be reached with weights this library registered).
+//  * Fused entry point, N >= 2.  The GEMM family is entered when every matrix is covered by one of the two GEMMs and gemm_pays says
+//    so for the FIRST matrix's shape over the rows of all: the planes crossover whenever that shape is coverable, even when
+//    planes_ok then fails for the weights (fast aggregation, 2 GB) or the matrices differ, and k_gemm_onehot runs below its own
+//    crossover.  1- and 3-bit matrices that k_gemm_planes cannot take, a mix of configurations and V_REF_LAYOUT go to the row loop,
+//    where each matrix is planned again from the workspace's state: after LB_ALL that may be a GEMM after all, after
+//    LB_HALF_TABLES k_gemv_quad or k_gemm_onehot (gimg_valid is left as an earlier call on the stream set it).
+//  * The K > PAIRS_ROW_MAX_K limit applies to the row-wise image: unified-scale matrices beyond it get k_gemm_onehot on the LUT of
+//    the one-workgroup-per-act-group build.
+//  * image_fits: the LUT image of the stream's workspace, which has the row stride of the largest N the stream has seen, stays below
+//    2 GB.  fused_impl plans before the workspace exists and assumes it does; fused_prefill plans again where it does not.
+//  * N = 1, a tap, or a GEMM that does not pay: one fused GEMV launch; the matrices must share layout, K and quantisation config.
+static Plan plan_split(const tmac_hip_weights* w, const tmac_hip_workspace* ws, int N, bool tap) {
+    Route r = R_REF_LAYOUT;
+    if (g_knobs.variant != V_REF_LAYOUT && w->tiled_ok)
+        r = layout_of(w->s) == L_QUAD ? R_GEMV_QUAD : layout_of(w->s) == L_ROWBLOCK ? R_GEMV_FUSED : R_GEMV_LO;
+    if (w->fa && r != R_REF_LAYOUT && r != R_GEMV_LO) return refused(TMAC_HIP_E_NOMATCH, "fast-aggregation weights run on the two-kernel path only");
+    if (r == R_REF_LAYOUT && !w->A_ref)
+        return refused(TMAC_HIP_E_NOMATCH, "reference-layout blobs were not kept for these weights (register them with variant 3 selected)");
+    if (r != R_GEMV_QUAD && r != R_GEMV_FUSED) return planned(r);
+    if (!tap && ws->gimg_valid && ws->gimg_kind == gimg_kind_for(w->s) && planes_ok(w) && planes_image_fits(ws, w->s.K) && planes_pays(w->s, w->s.Mw, N))
+        return planned(R_GEMM_PLANES);
+    if (onehot_pays(w->s, w->s.Mw, N) && gemm_onehot_supported(w->s)) return planned(R_GEMM_ONEHOT);
+    return planned(r);
+}
+
+static Plan plan_fused(const tmac_hip_weights* const* wl, void* const* C_list, int nmat, int N, bool tap, bool image_fits = true) {
+    if (g_knobs.gemm_min_n > 0 && N >= 2 && !tap) {       // (gemm_pays applies the threshold: a set one, or the measured crossover)
+        bool ok = true, quant = true, all_planes = true, all_onehot = true, all_quad = true;
+        long rows = 0;
+        for (int i = 0; i < nmat && ok; ++i) {
+            const tmac_hip_weights* w = wl[i];
+            ok = w && C_list[i] && (gemm_onehot_supported(w->s) || planes_ok(w)) && same_lut(w, wl[0]);
+            if (!ok) break;
+            rows += w->s.Mw;
+            quant = quant && same_quant(w, wl[0]);
+            all_planes = all_planes && planes_ok(w);
+            all_onehot = all_onehot && gemm_onehot_supported(w->s);
+            all_quad = all_quad && layout_of(w->s) == L_QUAD && w->tiled_ok && !w->fa;
+        }
+        if (ok && gemm_pays(wl[0]->s, rows, N)) {
+            const Shape& s0 = wl[0]->s;
+            const bool tiled = g_knobs.variant != V_REF_LAYOUT;
+            // the plane-combined GEMM reads its own LUT image only: one build, one launch for all matrices
+            if (tiled && image_fits && all_planes && quant && !(s0.m_groups >= 1 && s0.K > PAIRS_ROW_MAX_K)) return planned(R_GEMM_PLANES, LB_IMAGE);
+            const LutBuild lut = tiled && all_onehot && (s0.ags == 64 || (s0.ags == s0.K && s0.K <= PAIRS_ROW_MAX_K)) ? LB_HALF_TABLES : LB_ALL;
+            if (tiled && all_onehot && quant && all_quad) return planned(R_GEMM_ONEHOT, lut);   // q/k/v or gate/up: one launch fills the chip
+            return planned(R_ROW_LOOP, lut);
+        }
+    }
+    for (int i = 0; i < nmat; ++i) {
+        const tmac_hip_weights* w = wl[i];
+        if (!w || !C_list[i]) return refused(TMAC_HIP_E_ARG, "null matrix or output");
+        if (layout_of(w->s) == L_LO || !w->tiled_ok || layout_of(w->s) != layout_of(wl[0]->s))
+            return refused(TMAC_HIP_E_NOMATCH, "matrix %d is not registered in the fused layout", i);
+        if (!same_lut(w, wl[0]) || !same_quant(w, wl[0]))
+            return refused(TMAC_HIP_E_ARG, "matrices fused in one launch must share K, bits and quantisation config");
+    }
+    return planned(layout_of(wl[0]->s) == L_QUAD ? R_GEMV_QUAD : R_GEMV_FUSED);
+}
+
+// ---- argument blocks of the planned kernels --------------------------------------------------------------------------------
+static void fill_gemm_mats(GemmMat* m, const tmac_hip_weights* const* wl, void* const* C_list, int nmat) {
+    for (int i = 0; i < nmat; ++i) { m[i].W = wl[i]->W; m[i].SC = wl[i]->SC; m[i].C = C_list[i]; m[i].Mw = wl[i]->s.Mw; }
+}
+// what the two GEMV sites share; returns the launch's row blocks (row quads in the QUAD layout) over all matrices
+static int fill_fused_args(FusedArgs& fa, const tmac_hip_weights* const* wl, void* const* C_list, int nmat, tmac_dtype_t out_dtype, int32_t* dump) {
+    memset(&fa, 0, sizeof(fa));
+    fa.nmat = nmat; fa.s = wl[0]->s;
+    const bool quad = layout_of(fa.s) == L_QUAD;
+    int nb = 0;
+    for (int i = 0; i < nmat; ++i) {
+        const Shape& a = wl[i]->s;
+        nb += quad ? a.nquads() : a.nb();
+        fa.m[i].W = (const uint4*)wl[i]->W; fa.m[i].SC = wl[i]->SC; fa.m[i].C = C_list[i]; fa.m[i].Mw = a.Mw; fa.m[i].nb_end = nb;
+    }
+    fa.sc_f16 = wl[0]->sc_dtype == F16; fa.out_f16 = out_dtype == TMAC_F16; fa.dump = dump;
+    fa.acc_mfma = quad ? (g_knobs.variant != V_QUAD_MQSAD) : (g_knobs.variant == V_FUSED_MFMA);
+    return nb;
+}
+static int32_t fused_gemv_rc(hipError_t e) {
+    if (e == hipErrorInvalidValue) return fail(TMAC_HIP_E_NOMATCH, "no fused GEMV kernel for this configuration");
+    if (e != hipSuccess) return fail(TMAC_HIP_E_RUNTIME, "fused gemv launch: %s", hipGetErrorString(e));
+    return TMAC_HIP_OK;
+}
+
+// one-hot MFMA GEMM over 1..4 matrices that share K, the quantisation config (checked by the planners) and the LUT in ws
 static int32_t gemm_multi(const tmac_hip_weights* const* wl, int nmat, const tmac_hip_workspace* ws, void* const* C_list,
                           tmac_dtype_t out_dtype, int N, int32_t* dump, hipStream_t st) {
     GemmArgs ga;
     memset(&ga, 0, sizeof(ga));
     const tmac_hip_weights* w0 = wl[0];
     ga.s = w0->s; ga.nmat = nmat;
-    for (int i = 0; i < nmat; ++i) { ga.m[i].W = wl[i]->W; ga.m[i].SC = wl[i]->SC; ga.m[i].C = C_list[i]; ga.m[i].Mw = wl[i]->s.Mw; }
+    fill_gemm_mats(ga.m, wl, C_list, nmat);
     ga.sc_f16 = w0->sc_dtype == F16; ga.out_f16 = out_dtype == TMAC_F16;
     ga.qlut_lds = ws->qlut_lds; ga.tstride = (((w0->s.K / 32) + 15) & ~15) + 1; ga.lut_scales = ws->lut_scales; ga.lut_biases = ws->lut_biases;
     ga.dump = dump; ga.N = N;
@@ -48,13 +183,6 @@ static int32_t gemm_multi(const tmac_hip_weights* const* wl, int nmat, const tma
     return TMAC_HIP_OK;
 }
 
-
-static bool planes_ok(const tmac_hip_weights* w) {
-    return g_knobs.gemm_kernel != 1 && w->s.lay == 2 && w->lo_ok && w->s.ts == 8 && !w->fa && gemm_planes_supported(w->s) &&
-           w->w_bytes < ((size_t)1 << 31);
-}
-static bool planes_image_fits(const tmac_hip_workspace* ws, int K) { return ws->gimg && (size_t)2 * K * ws->gNpad < ((size_t)1 << 31); }
-
 // k_gemm_planes over up to 4 matrices that share K and the quantisation config; the workspace holds the LUT image
 static int32_t planes_multi(const tmac_hip_weights* const* wl, int nmat, const tmac_hip_workspace* ws, void* const* C_list,
                             tmac_dtype_t out_dtype, int N, int32_t* comb_dump, hipStream_t st) {
@@ -62,7 +190,7 @@ static int32_t planes_multi(const tmac_hip_weights* const* wl, int nmat, const t
     memset(&ga, 0, sizeof(ga));
     const tmac_hip_weights* w0 = wl[0];
     ga.s = w0->s; ga.nmat = nmat;
-    for (int i = 0; i < nmat; ++i) { ga.m[i].W = wl[i]->W; ga.m[i].SC = wl[i]->SC; ga.m[i].C = C_list[i]; ga.m[i].Mw = wl[i]->s.Mw; }
+    fill_gemm_mats(ga.m, wl, C_list, nmat);
     ga.sc_f16 = w0->sc_dtype == F16; ga.out_f16 = out_dtype == TMAC_F16;
     ga.bimg = (const uint4*)ws->gimg; ga.colv = ws->gcol; ga.Npad = ws->gNpad; ga.N = N; ga.dump = comb_dump;
     ga.stamps = g_knobs.gemm_stamps;
@@ -73,6 +201,7 @@ static int32_t planes_multi(const tmac_hip_weights* const* wl, int nmat, const t
     return TMAC_HIP_OK;
 }
 
+// ---- split entry point -----------------------------------------------------------------------------------------------------
 int32_t tmac_host::qgemm_impl(const tmac_hip_weights* w, const tmac_hip_workspace* ws, void* C_dev, tmac_dtype_t out_dtype,
                           int N, int32_t* dump, hipStream_t st) {
     bind_thread_device();
@@ -80,50 +209,33 @@ int32_t tmac_host::qgemm_impl(const tmac_hip_weights* w, const tmac_hip_workspac
     if (ws->K != w->s.K || ws->ags != w->s.ags)
         return fail(TMAC_HIP_E_ARG, "workspace LUT (K=%d, ags=%d) does not match the weights (K=%d, ags=%d)", ws->K, ws->ags, w->s.K, w->s.ags);
     if (N <= 0 || N > ws->N) return fail(TMAC_HIP_E_ARG, "N=%d but the workspace LUT holds %d rows", N, ws->N);
-    Variant v = (Variant)g_knobs.variant;
-    if (v != V_REF_LAYOUT) {   // the weights' device layout decides which tiled kernel can run
-        if (!w->lo_ok) v = V_REF_LAYOUT;
-        else if (w->s.ts == 8) v = V_FUSED;
-        else if (v != V_LO_SDWA) v = V_LO_MQSAD;
-    }
-    if (w->fa && v != V_REF_LAYOUT && v != V_LO_MQSAD && v != V_LO_SDWA)
-        return fail(TMAC_HIP_E_NOMATCH, "fast-aggregation weights run on the two-kernel path only");
-    // split entry points: tmac_hip_preprocessor_dev builds k_gemm_planes' LUT image from PLANES_MIN_N rows on (it does not know the
-    // matrix); without the image only k_gemm_onehot's own, later crossover counts -- below it the row loop is the faster kernel
-    if (v == V_FUSED && !dump && ws->gimg_valid && ws->gimg_kind == (w->s.m_groups >= 1 ? 1 : 2) && planes_ok(w) && planes_image_fits(ws, w->s.K) && planes_pays(w->s, w->s.Mw, N)) {
-        void* cl[1] = {C_dev};
-        return planes_multi(&w, 1, ws, cl, out_dtype, N, nullptr, st);
-    }
-    if (v == V_FUSED && onehot_pays(w->s, w->s.Mw, N) && gemm_onehot_supported(w->s)) {
-        void* cl[1] = {C_dev};
-        return gemm_multi(&w, 1, ws, cl, out_dtype, N, dump, st);
-    }
-    if (v == V_FUSED) {
+    const Plan p = plan_split(w, ws, N, dump != nullptr);
+    if (p.err) return fail(p.err, p.msg, p.mat);
+    void* cl[1] = {C_dev};
+    switch (p.route) {
+    case R_GEMM_PLANES: return planes_multi(&w, 1, ws, cl, out_dtype, N, nullptr, st);
+    case R_GEMM_ONEHOT: return gemm_multi(&w, 1, ws, cl, out_dtype, N, dump, st);
+    case R_GEMV_QUAD:
+    case R_GEMV_FUSED: {
         FusedArgs fa;
-        memset(&fa, 0, sizeof(fa));
-        fa.nmat = 1; fa.s = w->s;
-        fa.m[0].W = (const uint4*)w->W; fa.m[0].SC = w->SC; fa.m[0].C = C_dev; fa.m[0].Mw = w->s.Mw; fa.m[0].nb_end = w->s.nb();
+        fill_fused_args(fa, &w, cl, 1, out_dtype, dump);
         fa.qlut_lds = ws->qlut_lds; fa.lut_scales = ws->lut_scales; fa.lut_biases = ws->lut_biases;
-        fa.sc_f16 = w->sc_dtype == F16; fa.out_f16 = out_dtype == TMAC_F16; fa.dump = dump;
-        fa.acc_mfma = (w->s.lay == 2) ? (g_knobs.variant != V_QUAD_MQSAD) : (g_knobs.variant == V_FUSED_MFMA);
-        if (w->s.lay == 2) fa.m[0].nb_end = w->s.nquads();
-        hipError_t e = (w->s.lay == 2) ? launch_gemv_quad(fa, N, false, g_knobs.force_ft, g_knobs.force_wpq, st) : launch_gemv_fused(fa, N, false, st);
-        if (e == hipErrorInvalidValue) return fail(TMAC_HIP_E_NOMATCH, "no fused GEMV kernel for this configuration");
-        if (e != hipSuccess) return fail(TMAC_HIP_E_RUNTIME, "fused gemv launch: %s", hipGetErrorString(e));
-        return TMAC_HIP_OK;
+        return fused_gemv_rc(p.route == R_GEMV_QUAD ? launch_gemv_quad(fa, N, false, g_knobs.force_ft, g_knobs.force_wpq, st)
+                                                    : launch_gemv_fused(fa, N, false, st));
+    }
+    default: break;
     }
     GemvArgs a;
     a.s = w->s; a.N = N; a.qlut_dev = ws->qlut_dev; a.qlut_ref = ws->qlut_ref;
     a.lut_scales = ws->lut_scales; a.lut_biases = ws->lut_biases; a.C = C_dev; a.out_dtype = (Dtype)out_dtype;
     a.ps_dump = dump;
     a.fa_mode = w->fa;
-    if (v == V_REF_LAYOUT) {
-        if (!w->A_ref) return fail(TMAC_HIP_E_NOMATCH, "reference-layout blobs were not kept for these weights (register them with variant 3 selected)");
+    if (p.route == R_REF_LAYOUT) {
         a.W = w->A_ref; a.SC = w->S_ref; a.sc_dtype = w->ref_dtype;
     } else {
         a.W = w->W; a.SC = w->SC; a.sc_dtype = w->sc_dtype;
     }
-    hipError_t e = launch_gemv(a, v, st);
+    hipError_t e = launch_gemv(a, p.route == R_REF_LAYOUT ? V_REF_LAYOUT : g_knobs.variant == V_LO_SDWA ? V_LO_SDWA : V_LO_MQSAD, st);
     if (e == hipErrorInvalidValue) return fail(TMAC_HIP_E_NOMATCH, "no GEMV kernel for this configuration");
     if (e != hipSuccess) return fail(TMAC_HIP_E_RUNTIME, "gemv launch: %s", hipGetErrorString(e));
     return TMAC_HIP_OK;
@@ -134,30 +246,42 @@ extern "C" int32_t tmac_hip_qgemm_dev(const tmac_hip_weights* w, const tmac_hip_
     return qgemm_impl(w, ws, C_dev, out_dtype, N, nullptr, (hipStream_t)stream);
 }
 
+// ---- parity taps -----------------------------------------------------------------------------------------------------------
+// One tap round trip: tap (cap elements; grown when too small, the pointer nulled first so that a failed allocation leaves nothing
+// dangling) is filled with 0x7f bytes, launch(tap) runs, elems integers come back to host.  Once anything was enqueued the stream
+// is synchronised -- or, after a failure, drained -- before the return: nothing of the call may still use the scratch that the
+// caller frees next.
+template <class Launch>
+static int32_t run_tap(int32_t*& tap, size_t& cap, size_t elems, int32_t* host, hipStream_t st, const char* what, Launch launch) {
+    if (cap < elems) {
+        if (tap) (void)hipFree(tap);
+        tap = nullptr; cap = 0;
+        HIP_TRY(hipMalloc((void**)&tap, elems * sizeof(int32_t)));
+        cap = elems;
+    }
+    hipError_t e = hipMemsetAsync(tap, 0x7f, elems * sizeof(int32_t), st);
+    int32_t rc = e == hipSuccess ? launch(tap) : fail(TMAC_HIP_E_RUNTIME, "%s fill: %s", what, hipGetErrorString(e));
+    if (rc == TMAC_HIP_OK) {
+        e = hipMemcpyAsync(host, tap, elems * sizeof(int32_t), hipMemcpyDeviceToHost, st);
+        if (e == hipSuccess) e = hipStreamSynchronize(st);
+        if (e != hipSuccess) rc = fail(TMAC_HIP_E_RUNTIME, "%s readback: %s", what, hipGetErrorString(e));
+    } else {
+        (void)hipStreamSynchronize(st);
+    }
+    return rc;
+}
+// elements of the per-plane integer tap of the GEMV kernels and k_gemm_onehot
+static size_t ps_elems(const Shape& s, int N) { return (size_t)N * s.M() * ((s.m_groups >= 1 && s.ags == s.K) ? 1 : (size_t)s.ngroups()); }
+
 extern "C" int32_t tmac_hip_qgemm_partial_sums(const tmac_hip_weights* w, const tmac_hip_workspace* ws_c, int32_t* PS_host,
                                                int N, void* stream) {
     if (!w || !ws_c || !PS_host) return fail(TMAC_HIP_E_ARG, "null argument");
     auto* ws = const_cast<tmac_hip_workspace*>(ws_c);
     hipStream_t st = (hipStream_t)stream;
-    const size_t G = (w->s.m_groups >= 1 && w->s.ags == w->s.K) ? 1 : (size_t)w->s.ngroups();
-    const size_t elems = (size_t)N * w->s.M() * G;
-    if (ws->dump_elems < elems) {
-        if (ws->dump) (void)hipFree(ws->dump);
-        HIP_TRY(hipMalloc((void**)&ws->dump, elems * sizeof(int32_t)));
-        ws->dump_elems = elems;
-    }
-    HIP_TRY(hipMemsetAsync(ws->dump, 0x7f, elems * sizeof(int32_t), st));
     DevBuf Ctmp;
     HIP_TRY(Ctmp.alloc(sizeof(float) * (size_t)N * w->s.Mw));
-    int32_t rc = qgemm_impl(w, ws, Ctmp.p, TMAC_F32, N, ws->dump, st);
-    if (rc == TMAC_HIP_OK) {
-        hipError_t e = hipMemcpyAsync(PS_host, ws->dump, elems * sizeof(int32_t), hipMemcpyDeviceToHost, st);
-        if (e == hipSuccess) e = hipStreamSynchronize(st);
-        if (e != hipSuccess) rc = fail(TMAC_HIP_E_RUNTIME, "partial-sum readback: %s", hipGetErrorString(e));
-    } else {
-        (void)hipStreamSynchronize(st);      // nothing of this call may still use the scratch that is freed on return
-    }
-    return rc;
+    return run_tap(ws->dump, ws->dump_elems, ps_elems(w->s, N), PS_host, st, "partial-sum",
+                   [&](int32_t* tap) { return qgemm_impl(w, ws, Ctmp.p, TMAC_F32, N, tap, st); });
 }
 
 extern "C" int32_t tmac_hip_debug_gemm_stamps(unsigned long long* dev_buffer) {
@@ -178,28 +302,14 @@ extern "C" int32_t tmac_hip_debug_gemm_comb_sums(const tmac_hip_weights* w, cons
     if (!w || !ws_c || !comb_host) return fail(TMAC_HIP_E_ARG, "null argument");
     auto* ws = const_cast<tmac_hip_workspace*>(ws_c);
     hipStream_t st = (hipStream_t)stream;
-    if (!ws->gimg_valid || ws->gimg_kind != (w->s.m_groups >= 1 ? 1 : 2) || ws->K != w->s.K || N <= 0 || N > ws->N) return fail(TMAC_HIP_E_ARG, "the workspace holds no LUT image for K=%d, N=%d", w->s.K, N);
+    if (!ws->gimg_valid || ws->gimg_kind != gimg_kind_for(w->s) || ws->K != w->s.K || N <= 0 || N > ws->N) return fail(TMAC_HIP_E_ARG, "the workspace holds no LUT image for K=%d, N=%d", w->s.K, N);
     if (!planes_ok(w)) return fail(TMAC_HIP_E_NOMATCH, "k_gemm_planes does not cover this configuration");
     const size_t elems = (size_t)N * w->s.Mw * (w->s.m_groups >= 1 ? 1 : w->s.K / 64);
-    if (ws->dump_elems < elems) {
-        if (ws->dump) (void)hipFree(ws->dump);
-        ws->dump = nullptr; ws->dump_elems = 0;
-        HIP_TRY(hipMalloc((void**)&ws->dump, elems * sizeof(int32_t)));
-        ws->dump_elems = elems;
-    }
-    HIP_TRY(hipMemsetAsync(ws->dump, 0x7f, elems * sizeof(int32_t), st));
     DevBuf Ctmp;
     HIP_TRY(Ctmp.alloc(sizeof(float) * (size_t)N * w->s.Mw));
     void* cl[1] = {Ctmp.p};
-    int32_t rc = planes_multi(&w, 1, ws, cl, TMAC_F32, N, ws->dump, st);
-    if (rc == TMAC_HIP_OK) {
-        hipError_t e = hipMemcpyAsync(comb_host, ws->dump, elems * sizeof(int32_t), hipMemcpyDeviceToHost, st);
-        if (e == hipSuccess) e = hipStreamSynchronize(st);
-        if (e != hipSuccess) rc = fail(TMAC_HIP_E_RUNTIME, "comb-sum readback: %s", hipGetErrorString(e));
-    } else {
-        (void)hipStreamSynchronize(st);
-    }
-    return rc;
+    return run_tap(ws->dump, ws->dump_elems, elems, comb_host, st, "comb-sum",
+                   [&](int32_t* tap) { return planes_multi(&w, 1, ws, cl, TMAC_F32, N, tap, st); });
 }
 
 // The LUT image of the workspace in plain layouts: half tables int8 [N][K/4][8], then lut_scales, lut_biases and the
@@ -241,13 +351,13 @@ extern "C" int32_t tmac_hip_debug_gemm_image_read(const tmac_hip_workspace* ws, 
     return TMAC_HIP_OK;
 }
 
-
+// ---- fused entry point -----------------------------------------------------------------------------------------------------
 // Prefill through the fused entry point: one LUT build (k_preprocess) into a workspace owned by the library, one
 // one-hot MFMA GEMM per matrix.  The workspace is per stream (launches on one stream are ordered; two streams must not
 // share LUT buffers) and grows on demand; tmac_hip_cache_clear() releases them.
 static std::map<std::pair<int, hipStream_t>, tmac_hip_workspace*> g_fused_ws;   // per (device, stream): the null stream exists on every device
 
-static int32_t fused_prefill(const tmac_hip_weights* const* wl, int nmat, const void* B_dev, tmac_dtype_t act_dtype,
+static int32_t fused_prefill(Plan p, const tmac_hip_weights* const* wl, int nmat, const void* B_dev, tmac_dtype_t act_dtype,
                              void* const* C_list, tmac_dtype_t out_dtype, int N, hipStream_t st) {
     const Shape& s0 = wl[0]->s;
     tmac_hip_workspace* ws = nullptr;
@@ -271,49 +381,29 @@ static int32_t fused_prefill(const tmac_hip_weights* const* wl, int nmat, const 
         }
         ws = slot;
     }
-    int32_t rc;
-    bool planes = g_knobs.variant != V_REF_LAYOUT && planes_image_fits(ws, s0.K);
-    for (int i = 0; i < nmat && planes; ++i) {
-        const Shape &x = wl[i]->s, &y = s0;
-        planes = planes_ok(wl[i]) && x.bits == y.bits && x.gs == y.gs && x.zero_point == y.zero_point && x.ags == y.ags &&
-                 x.m_groups == y.m_groups && wl[i]->sc_dtype == wl[0]->sc_dtype;
-    }
-    if (planes && s0.m_groups >= 1 && s0.K > 12288) planes = false;   // (the row-wise LUT build's limit)
-    if (planes) {
-        // the plane-combined GEMM reads its own LUT image only: one build, one launch for all matrices
-        rc = check_lut_shape(ws, s0.K, N, s0.ags);
-        if (rc) return rc;
+    if (p.route == R_GEMM_PLANES && !planes_image_fits(ws, s0.K)) p = plan_fused(wl, C_list, nmat, N, false, false);   // (see image_fits at the planners)
+    int32_t rc = p.lut == LB_ALL ? TMAC_HIP_OK : check_lut_shape(ws, s0.K, N, s0.ags);
+    if (rc) return rc;
+    const int f16 = act_dtype == TMAC_F16;
+    hipError_t e = hipSuccess;
+    if (p.lut == LB_IMAGE) {
         ws->K = 0; ws->N = 0; ws->gimg_valid = false;      // the other layouts of this workspace are not built
-        hipError_t e = s0.m_groups >= 1
-            ? launch_preprocess_pairs_row(B_dev, act_dtype == TMAC_F16, ws->qlut_lds, ws->lut_scales, ws->lut_biases, s0.K, N, nullptr, nullptr, 0,
-                                          ws->gimg, ws->gcol, ws->gNpad, st)
-            : launch_lut_image(B_dev, act_dtype == TMAC_F16, ws->gimg, ws->gcol, s0.K, N, ws->gNpad, st);
+        e = s0.m_groups >= 1
+            ? launch_preprocess_pairs_row(B_dev, f16, ws->qlut_lds, ws->lut_scales, ws->lut_biases, s0.K, N, nullptr, nullptr, 0, ws->gimg, ws->gcol, ws->gNpad, st)
+            : launch_lut_image(B_dev, f16, ws->gimg, ws->gcol, s0.K, N, ws->gNpad, st);
         if (e != hipSuccess) return fail(TMAC_HIP_E_RUNTIME, "LUT image launch: %s", hipGetErrorString(e));
-        return planes_multi(wl, nmat, ws, C_list, out_dtype, N, nullptr, st);
-    }
-    bool onehot_all = true;       // (1- / 3-bit weights reach this point only when k_gemm_planes cannot take them: they go to the row loop)
-    for (int i = 0; i < nmat; ++i) onehot_all = onehot_all && gemm_onehot_supported(wl[i]->s);
-    if (onehot_all && (s0.ags == 64 || (s0.ags == s0.K && s0.K <= 12288)) && g_knobs.variant != V_REF_LAYOUT) {
-        // only the one-hot GEMM reads this workspace: build the half-table image alone, two tables per lane
-        rc = check_lut_shape(ws, s0.K, N, s0.ags);
-        if (rc) return rc;
+    } else if (p.lut == LB_HALF_TABLES) {
         ws->K = s0.K; ws->N = N; ws->ags = s0.ags; ws->qdev_u4_per_row = qdev_u4_for_K(s0.K);
-        hipError_t e = s0.ags == 64
-            ? launch_preprocess_pairs(B_dev, act_dtype == TMAC_F16, ws->qlut_lds, ws->lut_scales, ws->lut_biases, s0.K, N, nullptr, nullptr, 0, st)
-            : launch_preprocess_pairs_row(B_dev, act_dtype == TMAC_F16, ws->qlut_lds, ws->lut_scales, ws->lut_biases, s0.K, N, nullptr, nullptr, 0,
-                                          nullptr, nullptr, 0, st);
+        e = s0.ags == 64
+            ? launch_preprocess_pairs(B_dev, f16, ws->qlut_lds, ws->lut_scales, ws->lut_biases, s0.K, N, nullptr, nullptr, 0, st)
+            : launch_preprocess_pairs_row(B_dev, f16, ws->qlut_lds, ws->lut_scales, ws->lut_biases, s0.K, N, nullptr, nullptr, 0, nullptr, nullptr, 0, st);
         if (e != hipSuccess) return fail(TMAC_HIP_E_RUNTIME, "preprocess launch: %s", hipGetErrorString(e));
     } else {
         rc = tmac_hip_preprocessor_dev(ws, B_dev, act_dtype, s0.K, N, s0.ags, st);
+        if (rc) return rc;
     }
-    if (rc) return rc;
-    bool same = onehot_all && g_knobs.variant != V_REF_LAYOUT;      // (the caller has established that the GEMM pays for these matrices)
-    for (int i = 0; i < nmat && same; ++i) {
-        const Shape &x = wl[i]->s, &y = s0;
-        same = x.lay == 2 && wl[i]->lo_ok && x.ts == 8 && x.bits == y.bits && x.gs == y.gs && x.zero_point == y.zero_point &&
-               x.m_groups == y.m_groups && wl[i]->sc_dtype == wl[0]->sc_dtype && !wl[i]->fa;
-    }
-    if (same) return gemm_multi(wl, nmat, ws, C_list, out_dtype, N, nullptr, st);   // q/k/v or gate/up: one launch fills the chip
+    if (p.route == R_GEMM_PLANES) return planes_multi(wl, nmat, ws, C_list, out_dtype, N, nullptr, st);
+    if (p.route == R_GEMM_ONEHOT) return gemm_multi(wl, nmat, ws, C_list, out_dtype, N, nullptr, st);
     for (int i = 0; i < nmat && rc == TMAC_HIP_OK; ++i) rc = tmac_hip_qgemm_dev(wl[i], ws, C_list[i], out_dtype, N, st);
     return rc;
 }
@@ -324,49 +414,25 @@ int32_t tmac_host::fused_impl(const tmac_hip_weights* const* wl, int nmat, const
         if (chain_recording()) chain_clear_xform();      // a rejected call must not leave its transform pending for the next recorded call
         return fail(TMAC_HIP_E_ARG, "bad fused arguments (1..4 matrices)");
     }
-    if (chain_recording() && !dump && !lut_tap) return chain_record(wl, nmat, B_dev, act_dtype, C_list, out_dtype, N);
-    if (!dump && !lut_tap) {           // deferred launches: queued until tmac_hip_flush (or a call that depends on a queued one)
+    const bool tap = dump || lut_tap;
+    if (chain_recording() && !tap) return chain_record(wl, nmat, B_dev, act_dtype, C_list, out_dtype, N);
+    if (!tap) {           // deferred launches: queued until tmac_hip_flush (or a call that depends on a queued one)
         int32_t drc;
         if (defer_if_on(wl, nmat, B_dev, act_dtype, C_list, out_dtype, N, st, &drc)) return drc;
     }
-    if (g_knobs.gemm_min_n > 0 && N >= 2 && !dump && !lut_tap) {       // (gemm_pays applies the threshold: a set one, or the measured crossover)
-        bool ok = true;
-        long rows = 0;
-        for (int i = 0; i < nmat; ++i) {
-            ok = ok && wl[i] && C_list[i] && (gemm_onehot_supported(wl[i]->s) || planes_ok(wl[i])) && wl[i]->s.K == wl[0]->s.K &&
-                 wl[i]->s.ags == wl[0]->s.ags;
-            if (ok) rows += wl[i]->s.Mw;
-        }
-        if (ok && gemm_pays(wl[0]->s, rows, N)) return fused_prefill(wl, nmat, B_dev, act_dtype, C_list, out_dtype, N, st);
-    }
+    const Plan p = plan_fused(wl, C_list, nmat, N, tap);
+    if (p.err) return fail(p.err, p.msg, p.mat);
+    if (p.route != R_GEMV_QUAD && p.route != R_GEMV_FUSED) return fused_prefill(p, wl, nmat, B_dev, act_dtype, C_list, out_dtype, N, st);
     FusedArgs fa;
-    memset(&fa, 0, sizeof(fa));
-    fa.nmat = nmat;
-    int nb = 0;
-    for (int i = 0; i < nmat; ++i) {
-        const tmac_hip_weights* w = wl[i];
-        if (!w || !C_list[i]) return fail(TMAC_HIP_E_ARG, "null matrix or output");
-        if (w->s.ts != 8 || !w->lo_ok || w->s.lay != wl[0]->s.lay) return fail(TMAC_HIP_E_NOMATCH, "matrix %d is not registered in the fused layout", i);
-        const Shape &a = w->s, &b = wl[0]->s;
-        if (a.K != b.K || a.bits != b.bits || a.gs != b.gs || a.ags != b.ags || a.zero_point != b.zero_point ||
-            a.m_groups != b.m_groups || w->sc_dtype != wl[0]->sc_dtype)
-            return fail(TMAC_HIP_E_ARG, "matrices fused in one launch must share K, bits and quantisation config");
-        nb += (a.lay == 2) ? a.nquads() : a.nb();
-        fa.m[i].W = (const uint4*)w->W; fa.m[i].SC = w->SC; fa.m[i].C = C_list[i]; fa.m[i].Mw = a.Mw; fa.m[i].nb_end = nb;
-    }
-    fa.s = wl[0]->s;
+    const int nb = fill_fused_args(fa, wl, C_list, nmat, out_dtype, dump);
     fa.B = B_dev; fa.act_f16 = act_dtype == TMAC_F16;
-    fa.sc_f16 = wl[0]->sc_dtype == F16; fa.out_f16 = out_dtype == TMAC_F16; fa.dump = dump;
     fa.stamps = g_knobs.stamps;
     if (g_knobs.stamps && !fa.dump) fa.dump = g_knobs.stamp_dump;   // the stamps live in the tap (DUMP) instantiation of the kernel
     fa.lut_tap = lut_tap;
-    fa.acc_mfma = (fa.s.lay == 2) ? (g_knobs.variant != V_QUAD_MQSAD) : (g_knobs.variant == V_FUSED_MFMA);
+    if (p.route == R_GEMV_FUSED) return fused_gemv_rc(launch_gemv_fused(fa, N, true, st));
     int ft = g_knobs.force_ft, wpq = g_knobs.force_wpq;
-    if (fa.s.lay == 2 && !ft && !wpq && !fa.dump && N == 1) tuned_config(fa, nb, ft, wpq);
-    hipError_t e = (fa.s.lay == 2) ? launch_gemv_quad(fa, N, true, ft, wpq, st) : launch_gemv_fused(fa, N, true, st);
-    if (e == hipErrorInvalidValue) return fail(TMAC_HIP_E_NOMATCH, "no fused GEMV kernel for this configuration");
-    if (e != hipSuccess) return fail(TMAC_HIP_E_RUNTIME, "fused gemv launch: %s", hipGetErrorString(e));
-    return TMAC_HIP_OK;
+    if (!ft && !wpq && !fa.dump && N == 1) tuned_config(fa, nb, ft, wpq);
+    return fused_gemv_rc(launch_gemv_quad(fa, N, true, ft, wpq, st));
 }
 extern "C" int32_t tmac_hip_qgemm_fused_dev(const tmac_hip_weights* const* weights, int nmat, const void* B_dev,
                                             tmac_dtype_t act_dtype, void* const* C_dev, tmac_dtype_t out_dtype, int N,
@@ -378,26 +444,20 @@ extern "C" int32_t tmac_hip_qgemm_fused_partial_sums(const tmac_hip_weights* w, 
                                                      int32_t* PS_host, float* C_host, float* lut_host, int N, void* stream) {
     if (!w || !PS_host) return fail(TMAC_HIP_E_ARG, "null argument");
     hipStream_t st = (hipStream_t)stream;
-    const size_t G = (w->s.m_groups >= 1 && w->s.ags == w->s.K) ? 1 : (size_t)w->s.ngroups();
-    const size_t elems = (size_t)N * w->s.M() * G;
-    DevBuf dump, Ctmp, ltap;
+    DevBuf Ctmp, ltap;
     const size_t lt = (size_t)N * 2 * w->s.ngroups();
     HIP_TRY(ltap.alloc(lt * sizeof(float)));
-    HIP_TRY(dump.alloc(elems * sizeof(int32_t)));
     HIP_TRY(Ctmp.alloc(sizeof(float) * (size_t)N * w->s.Mw));
-    HIP_TRY(hipMemsetAsync(dump.p, 0x7f, elems * sizeof(int32_t), st));
     void* cl[1] = {Ctmp.p};
-    int32_t rc = fused_impl(&w, 1, B_dev, act_dtype, cl, TMAC_F32, N, dump.as<int32_t>(), ltap.as<float>(), st);
-    if (rc == TMAC_HIP_OK) {
-        hipError_t e = hipMemcpyAsync(PS_host, dump.p, elems * sizeof(int32_t), hipMemcpyDeviceToHost, st);
-        if (e == hipSuccess && C_host) e = hipMemcpyAsync(C_host, Ctmp.p, sizeof(float) * (size_t)N * w->s.Mw, hipMemcpyDeviceToHost, st);
-        if (e == hipSuccess && lut_host) e = hipMemcpyAsync(lut_host, ltap.p, lt * sizeof(float), hipMemcpyDeviceToHost, st);
-        if (e == hipSuccess) e = hipStreamSynchronize(st);
-        if (e != hipSuccess) rc = fail(TMAC_HIP_E_RUNTIME, "fused tap readback: %s", hipGetErrorString(e));
-    } else {
-        (void)hipStreamSynchronize(st);
-    }
-    return rc;
+    int32_t* tap = nullptr;      // scratch of this call, unlike the workspace's tap of the two entry points above
+    size_t cap = 0;
+    int32_t rc = run_tap(tap, cap, ps_elems(w->s, N), PS_host, st, "fused tap",
+                         [&](int32_t* t) { return fused_impl(&w, 1, B_dev, act_dtype, cl, TMAC_F32, N, t, ltap.as<float>(), st); });
+    if (tap) (void)hipFree(tap);
+    if (rc) return rc;
+    if (C_host) HIP_TRY(hipMemcpy(C_host, Ctmp.p, sizeof(float) * (size_t)N * w->s.Mw, hipMemcpyDeviceToHost));
+    if (lut_host) HIP_TRY(hipMemcpy(lut_host, ltap.p, lt * sizeof(float), hipMemcpyDeviceToHost));
+    return TMAC_HIP_OK;
 }
 
 // the per-stream workspaces of the fused entry point's prefill route (tmac_hip_cache_clear; caller holds g_mu)

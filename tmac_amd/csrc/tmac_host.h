@@ -5,7 +5,7 @@
 //   tmac_kcfg.cpp        the kcfg.ini table and its lookups
 //   tmac_weights.cpp     weight registration (reference layout -> device layout)
 //   tmac_workspace.cpp   LUT workspace + the preprocessor entry point
-//   tmac_dispatch.cpp    qgemm_lut dispatch, the fused entry point, parity taps
+//   tmac_dispatch.cpp    qgemm_lut dispatch (a call is planned -- enum Route -- then launched), the fused entry point, parity taps
 //   tmac_tuner.cpp       launch-configuration tuner of the decode kernel
 //   tmac_chain_host.cpp  recording and building the persistent decode chain (chain_build and its stages, the stream schedule)
 //   tmac_chain_launch.cpp  launching a built chain, IPC export / connect, status, info, taps, stamps
@@ -18,6 +18,7 @@
 
 #include <array>
 #include <chrono>
+#include <climits>
 #include <cstdarg>
 #include <cstdio>
 #include <cstdlib>
@@ -43,7 +44,7 @@ struct tmac_hip_weights {
     void* A_ref = nullptr;  // reference blobs kept on the device only when the generic kernel needs them
     void* S_ref = nullptr;
     tmac::Dtype ref_dtype = tmac::F32;
-    bool lo_ok = false;
+    bool tiled_ok = false;  // W / SC hold the device layout s names (layout_of) and its tiled kernel covers the configuration; else only the reference blobs serve
     int fa = 0;             // fast-aggregation mode these weights were registered under (0 = exact)
     size_t w_bytes = 0, sc_bytes = 0;
 };
@@ -117,6 +118,17 @@ void bind_thread_device();
 int32_t ensure_device();
 
 constexpr int PLANES_MIN_N = 12;   // default GEMM threshold where k_gemm_planes covers the configuration (tmac_dispatch.cpp)
+constexpr int PAIRS_ROW_MAX_K = 12288;   // largest K of the row-wise pair build (k_preprocess_pairs_row) and so of the row-wise LUT image
+// Fewest activation rows that go to a GEMM instead of the row loop: none when switched off (tmac_hip_set_gemm_min_n(0)), an explicitly
+// set threshold literally, else `fitted`, the caller's own default (setting 32, the knob's initial value, counts as "not set").
+inline int gemm_min_rows(int fitted) { return g_knobs.gemm_min_n <= 0 ? INT_MAX : g_knobs.gemm_min_n != 32 ? g_knobs.gemm_min_n : fitted; }
+// the LUT-image kind (tmac_hip_workspace::gimg_kind) k_gemm_planes wants for this shape: row-wise for unified scales, else chunk-major
+inline int gimg_kind_for(const Shape& s) { return s.m_groups >= 1 ? 1 : 2; }
+// The device layout of registered weights, which Shape spells as the pair (ts, lay): 16-table segments for the two-kernel path
+// (k_gemv_lo), 8-table units in 16-row blocks (k_gemv_fused), or 8-table units in row quads (k_gemv_quad and the GEMMs).
+enum Layout { L_LO, L_ROWBLOCK, L_QUAD };
+inline Layout layout_of(const Shape& s) { return s.lay == 2 ? L_QUAD : s.ts == 8 ? L_ROWBLOCK : L_LO; }
+inline void set_layout(Shape& s, Layout l) { s.ts = l == L_LO ? 16 : 8; s.lay = l == L_QUAD ? 2 : 0; }
 inline size_t qdev_u4_for_K(int K) { return (size_t)((K / (4 * TS) + KL - 1) / KL) * 8 * KL; }
 
 // ---- kcfg (tmac_kcfg.cpp; callers hold g_mu) -----------------------------------------------------
@@ -150,12 +162,12 @@ bool chain_recording();            // is the calling thread between tmac_hip_cha
 void chain_clear_xform();          // drops a transform declared for the next recorded call (the call was rejected before it could be recorded)
 int32_t chain_record(const tmac_hip_weights* const* wl, int nmat, const void* B_dev, tmac_dtype_t act_dtype, void* const* C_list,
                      tmac_dtype_t out_dtype, int N);
-// true (and *rc set) when the calling thread is recording: the exchange step was noted, not executed
 // deferred launches (tmac_hip_defer): true (and *rc set) when the call was queued instead of launched
 bool defer_if_on(const tmac_hip_weights* const* wl, int nmat, const void* B_dev, tmac_dtype_t act_dtype, void* const* C_list, tmac_dtype_t out_dtype,
                  int N, hipStream_t st, int32_t* rc);
 void defer_release_thread();       // frees the calling thread's cached recordings (tmac_hip_cache_clear)
 void defer_forget_all();           // weights were freed / the library was reset: cached recordings of every thread are stale from now on
+// true (and *rc set) when the calling thread is recording: the exchange step was noted, not executed
 bool chain_record_gather_if_recording(const void* send_dev, void* recv_dev, size_t bytes_per_rank, int rank, int world, int32_t* rc);
 
 // ---- host-pointer layer (tmac_hostptr.cpp) --------------------------------------------------------

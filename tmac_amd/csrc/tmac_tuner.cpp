@@ -97,7 +97,7 @@ extern "C" int32_t tmac_hip_autotune_fused(const tmac_hip_weights* const* wl, in
     if (rc) return rc;
     size_t bytes = 0;
     for (int i = 0; i < nmat; ++i) {
-        if (!wl[i] || wl[i]->s.lay != 2 || !wl[i]->lo_ok) return fail(TMAC_HIP_E_NOMATCH, "matrix %d is not registered in the QUAD layout", i);
+        if (!wl[i] || layout_of(wl[i]->s) != L_QUAD || !wl[i]->tiled_ok) return fail(TMAC_HIP_E_NOMATCH, "matrix %d is not registered in the QUAD layout", i);
         bytes += wl[i]->w_bytes + wl[i]->sc_bytes;
     }
     int R = (int)(((size_t)768 << 20) / (bytes ? bytes : 1)) + 1;

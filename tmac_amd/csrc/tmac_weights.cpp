@@ -22,19 +22,18 @@ int32_t tmac_host::make_shape(Shape& s, int Mw, int K, int bits, const tmac_kcfg
         return fail(TMAC_HIP_E_NOMATCH, "act_group_size=%d must divide 4*kfactor=%d (qgemm.py:113-115)", s.ags, 4 * s.kfactor);
     if (s.m_groups < 0 && s.gs % (4 * s.kfactor)) return fail(TMAC_HIP_E_NOMATCH, "group_size %% (4*kfactor) != 0");
     // device layout: 8-table units for the fused kernel, 16-table segments for the two-kernel path
-    s.ts = 8;
-    s.lay = 0;
+    set_layout(s, L_ROWBLOCK);
     const bool fused_ok = gemv_fused_supported(s), quad_ok = gemv_quad_supported(s);
     if (g_knobs.fa_mode) {
         // the reference has no fast aggregation on the int32 / unified-scale path (tbl.cc:534) and the halving tree
         // needs a power-of-two number of tables per act group
         if (s.m_groups >= 1) return fail(TMAC_HIP_E_NOMATCH, "fast aggregation is defined for per-group scales only");
         if (s.ags != 32 && s.ags != 64) return fail(TMAC_HIP_E_NOMATCH, "fast aggregation needs act_group_size 32 or 64");
-        s.ts = 16;   // one act group's 16 (or 2 x 8) tables per lane: the tree stays inside a thread (k_gemv_lo)
+        set_layout(s, L_LO);   // one act group's 16 (or 2 x 8) tables per lane: the tree stays inside a thread (k_gemv_lo)
         return TMAC_HIP_OK;
     }
-    if ((g_knobs.variant == V_AUTO || g_knobs.variant == V_QUAD || g_knobs.variant == V_QUAD_MQSAD) && quad_ok) s.lay = 2;
-    else if (g_knobs.variant == V_LO_MQSAD || g_knobs.variant == V_LO_SDWA || !fused_ok) s.ts = 16;
+    if ((g_knobs.variant == V_AUTO || g_knobs.variant == V_QUAD || g_knobs.variant == V_QUAD_MQSAD) && quad_ok) set_layout(s, L_QUAD);
+    else if (g_knobs.variant == V_LO_MQSAD || g_knobs.variant == V_LO_SDWA || !fused_ok) set_layout(s, L_LO);
     return TMAC_HIP_OK;
 }
 
@@ -59,9 +58,9 @@ int32_t tmac_host::register_impl(tmac_hip_weights** out, const void* A_ref, cons
     w->sc_dtype = (Dtype)dev_float;
     w->ref_dtype = (Dtype)host_float;
     w->fa = g_knobs.fa_mode;
-    w->lo_ok = (s.lay == 2) ? gemv_quad_supported(s) : (s.ts == 8) ? gemv_fused_supported(s) : gemv_lo_supported(s);
+    w->tiled_ok = layout_of(s) == L_QUAD ? gemv_quad_supported(s) : layout_of(s) == L_ROWBLOCK ? gemv_fused_supported(s) : gemv_lo_supported(s);
     const size_t ab = ref_weight_bytes(s), se = ref_scale_elems(s), sb = se * dt_size((Dtype)host_float);
-    const bool keep_ref = !w->lo_ok || g_knobs.variant == V_REF_LAYOUT;
+    const bool keep_ref = !w->tiled_ok || g_knobs.variant == V_REF_LAYOUT;
     void *dA = nullptr, *dS = nullptr;
     auto cleanup = [&](int32_t code) {  // error path: drop everything this call allocated
         if (!(src_on_device && !keep_ref)) { if (dA) (void)hipFree(dA); if (dS) (void)hipFree(dS); }
@@ -83,7 +82,7 @@ int32_t tmac_host::register_impl(tmac_hip_weights** out, const void* A_ref, cons
         REG_TRY(hipMemcpyAsync(dA, A_ref, ab, kind, st));
         REG_TRY(hipMemcpyAsync(dS, scales_ref, sb, kind, st));
     }
-    if (w->lo_ok) {
+    if (w->tiled_ok) {
         w->w_bytes = s.weight_u4() * 16;
         REG_TRY(hipMalloc(&w->W, w->w_bytes));
         hipError_t e = launch_retile_weights((const uint8_t*)dA, w->W, s, st);

@@ -65,15 +65,18 @@ extern "C" int32_t tmac_hip_preprocessor_dev(tmac_hip_workspace* ws, const void*
     if (rc) return rc;
     if (!B_dev) return fail(TMAC_HIP_E_ARG, "null activations");
     ws->K = K; ws->N = N; ws->ags = act_group_size; ws->qdev_u4_per_row = qdev_u4_for_K(K);
-    const int gmin = g_knobs.gemm_min_n <= 0 ? 0x7fffffff : (g_knobs.gemm_min_n != 32 ? (g_knobs.gemm_min_n > 2 ? g_knobs.gemm_min_n : 2) : PLANES_MIN_N);
+    // k_gemm_planes' LUT image is built when tmac_hip_qgemm_dev may pick that kernel: not for one row, and not below the GEMM threshold
+    // (PLANES_MIN_N by default: the matrix, and with it the measured crossover plan_split applies, is not known here)
+    const bool want_img = N >= 2 && N >= gemm_min_rows(PLANES_MIN_N) && ws->gimg && g_knobs.gemm_kernel != 1;
+    const bool pairs_row = act_group_size == K && K <= PAIRS_ROW_MAX_K && N >= g_knobs.pairs_min_n;
     // one act group per row: the row-wise pair build also writes the LUT image of the plane-combined GEMM when that may be chosen
-    const bool row_img = act_group_size == K && K <= 12288 && N >= g_knobs.pairs_min_n && N >= gmin && ws->gimg && g_knobs.gemm_kernel != 1;
+    const bool row_img = pairs_row && want_img;
     // several activation rows with 64-activation groups: the pair-wise build (two tables per lane, all three layouts);
     // otherwise one workgroup per act group (any act_group_size, and cheaper than it looks for a single row)
     hipError_t e = (act_group_size == 64 && N >= g_knobs.pairs_min_n)
         ? launch_preprocess_pairs(B_dev, act_dtype == TMAC_F16, ws->qlut_lds, ws->lut_scales, ws->lut_biases, K, N, ws->qlut_ref,
                                   ws->qlut_dev, ws->qdev_u4_per_row, (hipStream_t)stream)
-        : (act_group_size == K && K <= 12288 && N >= g_knobs.pairs_min_n)
+        : pairs_row
         ? launch_preprocess_pairs_row(B_dev, act_dtype == TMAC_F16, ws->qlut_lds, ws->lut_scales, ws->lut_biases, K, N, ws->qlut_ref,
                                       ws->qlut_dev, ws->qdev_u4_per_row, row_img ? ws->gimg : nullptr, row_img ? ws->gcol : nullptr, ws->gNpad,
                                       (hipStream_t)stream)
@@ -81,7 +84,7 @@ extern "C" int32_t tmac_hip_preprocessor_dev(tmac_hip_workspace* ws, const void*
                             K, N, act_group_size, ws->qdev_u4_per_row, (hipStream_t)stream);
     if (e != hipSuccess) return fail(TMAC_HIP_E_RUNTIME, "preprocess launch: %s", hipGetErrorString(e));
     ws->gimg_valid = row_img; ws->gimg_kind = row_img ? 1 : 0;
-    if (act_group_size == 64 && N >= gmin && ws->gimg && g_knobs.gemm_kernel != 1) {   // what k_gemm_planes streams (tmac_hip_qgemm_dev may pick it)
+    if (act_group_size == 64 && want_img) {   // what k_gemm_planes streams (tmac_hip_qgemm_dev may pick it)
         e = launch_lut_image(B_dev, act_dtype == TMAC_F16, ws->gimg, ws->gcol, K, N, ws->gNpad, (hipStream_t)stream);
         if (e != hipSuccess) return fail(TMAC_HIP_E_RUNTIME, "LUT image launch: %s", hipGetErrorString(e));
         ws->gimg_valid = true; ws->gimg_kind = 2;      // (K == 64 with one act group per row: this image wins, the unified-scale GEMM is not offered it)
