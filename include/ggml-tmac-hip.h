@@ -55,7 +55,10 @@ const char* ggml_tmac_hip_last_error(void);
  * ggml_tmac_hip_stream() and returns at once.  With ggml_tmac_hip_set_deferred(1) such calls are QUEUED and ggml_tmac_hip_flush() launches
  * the queue as one stream-mode launch (tmac_hip.h: tmac_hip_defer / tmac_hip_flush): the calls between two synchronisation points that do
  * not depend on each other -- q, k, v issued one by one; the projections of several sequences -- run at 0.6-0.75 of the HBM peak instead
- * of 0.25.  A call that depends on a queued one flushes the queue by itself; ggml_tmac_hip_synchronize() flushes, then waits. */
+ * of 0.25.  A call that depends on a queued one flushes the queue by itself, and so does every other call into the library that launches
+ * work or touches device memory (ggml_tmac_hip_mul_mat, ggml_tmac_hip_free); ggml_tmac_hip_synchronize() flushes, then waits.  A call that
+ * would be refused is refused when it is issued, not at the flush; a flush launches every queued call and returns the first error; outputs
+ * of a batch match in-order launches to the stream kernel's tolerance (tmac_hip.h). */
 int ggml_tmac_hip_mul_mat_dev(const struct tmac_ggml_tensor* const* w, int nw, const void* x_dev, int x_is_f32, void* const* dst_dev, int dst_is_f32);
 int ggml_tmac_hip_set_deferred(int on);
 int ggml_tmac_hip_flush(void);

@@ -81,7 +81,8 @@ int32_t tmac_hip_load_kcfg_ex(const char* path, int replace);
 int32_t tmac_hip_clear_kcfg(void);
 /* Puts every piece of process-global state back to that of a freshly loaded library: kcfg table, tuning table, all
  * tmac_hip_set_* / tmac_hip_debug_* knobs, the host-pointer layer's caches, LUT workspace and staging buffers, the fused
- * entry point's per-stream workspaces.  Registered weights, workspaces and chains the caller holds stay valid.
+ * entry point's per-stream workspaces, the calling thread's deferred mode (left, its queue launched first) and tmac_hip_defer_stats
+ * counters.  Registered weights, workspaces and chains the caller holds stay valid.
  * Synchronises the library's own streams.  (tests/conftest.py calls it before every GPU test.) */
 int32_t tmac_hip_reset_state(void);
 /* M here is the number of WEIGHT rows (as in TMACGeMMWrapper::get_kcfg); fills zero_point /
@@ -145,7 +146,22 @@ int32_t tmac_hip_qgemm_fused_dev(const tmac_hip_weights* const* weights, int nma
  * tmac_hip_qgemm_fused_dev calls are QUEUED instead of launched; tmac_hip_flush launches what is queued as ONE stream-mode launch
  * (k_lut_images + k_gemv_stream: the independent-call path, 0.6-0.75 of the HBM peak instead of 0.25 for stand-alone launches).  The
  * queue never holds a dependence: a call that reads, or overwrites, anything a queued call writes (or overwrites what one reads), a call on
- * another stream, an N > 1 call and tmac_hip_defer(0) flush it first -- results are those of launching the calls in order.  The recording
+ * another stream, an N > 1 call and tmac_hip_defer(0) flush it first -- results are those of launching the calls in order (per-group-scale
+ * outputs of a batch to the tolerance of the stream kernel, not bit for bit: k_gemv_stream's default quarter-walk form adds a row's fp32
+ * partial sums in another order than a stand-alone launch, see tmac_hip_chain_is_stream; integers and unified-scale outputs are the same).
+ * EVERY other entry point that launches work or touches device memory for the caller is ordered behind the calling thread's queue too: it
+ * flushes the queue first, unconditionally (no overlap analysis: none of them is a hot path) -- tmac_hip_preprocessor_dev,
+ * tmac_hip_qgemm_dev, tmac_hip_qgemm_partial_sums, tmac_hip_qgemm_fused_partial_sums, tmac_hip_chain_launch, tmac_hip_workspace_read /
+ * _write, tmac_hip_debug_gemm_comb_sums / _gemm_image_read, tmac_hip_autotune_fused, and tmac_hip_free_weights, tmac_hip_chain_free and
+ * tmac_hip_cache_clear (a queued call may name what they release).  When that flush fails the entry point returns its status and launches
+ * nothing of its own (the three that release still release: the handle is dead either way).  A queue belongs to a thread: freeing, from
+ * another thread, weights that this thread has queued is the caller's error.
+ * A call is checked when it is queued: one that would be refused with deferral off is refused at once with the same code and message, is
+ * not queued and leaves the queue alone.  A flush launches EVERY queued call whatever fails on the way -- after a failed stream launch
+ * that group's calls one by one, after a failed call the rest -- returns the first error of a call that could not be launched, and leaves
+ * the queue empty.  An N > 1 call whose flush fails returns that error and is not launched.  tmac_hip_defer(0) leaves deferred mode
+ * whatever its flush returns; tmac_hip_reset_state ends with the mode off and the queue empty.
+ * tmac_hip_flush launches the queue on the stream its calls were ISSUED on, whatever its argument.  The recording
  * built from a batch is cached by the batch's signature (matrices, pointers, dtypes; invalidated when weights are freed): a decode loop
  * pays for it once.  A batch that mixes configurations (bits, zero points, per-group / unified scales, scale or output dtype) becomes one
  * stream launch per configuration -- its calls are independent of each other; calls the persistent kernels do not cover, and configurations
@@ -402,6 +418,10 @@ int32_t tmac_hip_debug_host_runs(int on);
 /* test knob: 0 skips the synchronisation that orders tmac_hip_workspace_create's null-stream fills before the workspace's
  * first user on another stream -- the round-2 defect (all-zero LUT image), kept reproducible for tests/test_gpu_hostptr.py */
 int32_t tmac_hip_debug_ws_fill_sync(int on);
+/* Test hook of the deferred queue: the nth launch attempted by the following flushes (1-based; a flush issues its stream launches first,
+ * then its single calls) returns TMAC_HIP_E_RUNTIME before anything is enqueued on the GPU -- a host-side `if`, the device is not touched.
+ * One-shot; 0 clears it, tmac_hip_reset_state clears it. */
+int32_t tmac_hip_debug_defer_fail(int nth);
 /* Launch-configuration tuner of the fused decode kernel (the role autotvm's grid search over
  * (bm, kfactor, bn) plays for the reference's CPU kernels, python/t_mac/ops/base.py:84-127, qgemm.py:98-116).
  * tmac_hip_autotune_fused times every (threads per workgroup, waves per row quad) configuration of k_gemv_quad on the

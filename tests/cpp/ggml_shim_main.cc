@@ -4,7 +4,9 @@
 // with "batch" (N = 1): THREE uploads of the blob stand for q / k / v; a hook without a view of the graph issues them as three separate
 // device-resident calls (ggml_tmac_hip_mul_mat_dev) in deferred mode, then synchronises: the calls must have run as ONE stream-mode launch
 // (tmac_hip_defer_stats), the recording cached from the second token on, every output equal to the reference; a fourth call that READS the
-// first output must flush the queue by itself.
+// first output must flush the queue by itself.  Last, a deferred N = 1 call writes row 0 of a two-row activation matrix and an N = 2
+// ggml_tmac_hip_mul_mat on that matrix follows with no flush in between: the N = 2 call goes behind the queue -- its row 0 equals what the
+// fourth call above computed in order from the same vector, its row 1 the reference.
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
@@ -62,9 +64,31 @@ int main(int argc, char** argv) {
         }
         uint64_t fl = 0, hits = 0, st = 0, single = 0;
         tmac_hip_defer_stats(&fl, &hits, &st, &single);
+        // still deferred: x2 = [poison; x], a queued N = 1 call writes q = W x over the poison, an N = 2 call reads x2
+        void *x2 = nullptr, *y2 = nullptr;
+        std::vector<float> poison((size_t)K, 1.0f), y4h((size_t)M), y2h((size_t)2 * M);
+        if (hipMalloc(&x2, 2 * by) || hipMalloc(&y2, 2 * by) || hipMemcpy(x2, poison.data(), by, 1) || hipMemcpy((char*)x2 + by, xb.data(), by, 1) ||
+            hipMemcpy(y4h.data(), y4, by, 2)) return 7;
+        void* ox2[1] = {x2};
+        tmac_ggml_tensor x2t{{K, 2, 1, 1}, x2, nullptr}, y2t{{M, 2, 1, 1}, y2, nullptr};
+        if (ggml_tmac_hip_mul_mat_dev(wq, 1, xd, 1, ox2, 1) || ggml_tmac_hip_mul_mat(&w2, &x2t, &y2t) || ggml_tmac_hip_synchronize()) {
+            fprintf(stderr, "N = 2 behind the queue: %s\n", ggml_tmac_hip_last_error()); return 6;
+        }
+        uint64_t fl2 = 0, single2 = 0;
+        tmac_hip_defer_stats(&fl2, nullptr, nullptr, &single2);
+        if (hipMemcpy(y2h.data(), y2, 2 * by, 2)) return 9;
+        double worst2 = 0;
+        for (int n = 0; n < 2; ++n) {                       // row 0 against W (W x) computed in order above, row 1 against the reference
+            const float* want = n == 0 ? y4h.data() : ref;
+            double mx = 0, err = 0;
+            for (int i = 0; i < M; ++i) { mx = std::fmax(mx, std::fabs(want[i])); err = std::fmax(err, std::fabs(y2h[(size_t)n * M + i] - want[i])); }
+            worst2 = std::fmax(worst2, err / mx);
+        }
         ggml_tmac_hip_set_deferred(0);
-        printf("RESULT worst_rel_err %.3g flushes %llu cache_hits %llu stream_launches %llu single_calls %llu\n", worst, (unsigned long long)fl,
-               (unsigned long long)hits, (unsigned long long)st, (unsigned long long)single);
+        printf("RESULT worst_rel_err %.3g flushes %llu cache_hits %llu stream_launches %llu single_calls %llu n2_rel_err %.3g n2_flushes %llu n2_single_calls %llu\n",
+               worst, (unsigned long long)fl, (unsigned long long)hits, (unsigned long long)st, (unsigned long long)single, worst2,
+               (unsigned long long)(fl2 - fl), (unsigned long long)(single2 - single));
+        if (!(worst2 <= 2e-5 && fl2 == fl + 1 && single2 == single + 1)) return 1;
         ggml_tmac_hip_free(&w); ggml_tmac_hip_free(&w2); ggml_tmac_hip_free(&w3);
         // tokens 0..2: one stream-mode launch each (the recording cached after the first), + the dependent call of token 2 on its own
         return (worst <= 2e-5 && st == 3 && hits == 2 && single == 1 && fl == 4) ? 0 : 1;

@@ -128,7 +128,8 @@ def test_ggml_op_hook_glue(tm, tmp_path, N, where):
 def test_ggml_hook_without_recording_reaches_stream_mode(tm, tmp_path):
     """a hook that is called mat-mul by mat-mul (no chain_begin / segment) issues q / k / v as three separate device-resident
     calls; in deferred mode they run as ONE stream-mode launch (k_lut_images + k_gemv_stream), the recording is cached from the second token
-    on, a call that reads a queued output flushes the queue by itself, and every output equals the reference (tests/cpp/ggml_shim_main.cc)"""
+    on, a call that reads a queued output flushes the queue by itself -- an N = 1 call and an N = 2 ggml_tmac_hip_mul_mat alike -- and every
+    output equals the reference (tests/cpp/ggml_shim_main.cc)"""
     Mw, K, bits, bm = 4096, 4096, 2, 128
     d = fixtures(tmp_path, Mw, K, bits, bm, N=1)
     exe = os.path.join(d, "ggml_shim_main")
@@ -138,6 +139,11 @@ def test_ggml_hook_without_recording_reaches_stream_mode(tm, tmp_path):
     r = subprocess.run([exe, d, str(Mw), str(K), str(bits), "1", "batch"], capture_output=True, text=True, timeout=300, env=env)
     assert r.returncode == 0, r.stdout + r.stderr
     assert "stream_launches 3" in r.stdout and "cache_hits 2" in r.stdout, r.stdout
+    # ... and an N = 2 call that reads a queued call's output goes behind the queue: one more flush (the queued call, on its own), both rows
+    # equal to what the shim computed in order
+    line = [x for x in r.stdout.splitlines() if x.startswith("RESULT")][0].split()
+    n2 = dict(zip(line[11::2], line[12::2]))
+    assert float(n2["n2_rel_err"]) <= 2e-5 and int(n2["n2_flushes"]) == 1 and int(n2["n2_single_calls"]) == 1, r.stdout
 
 
 @pytest.mark.skipif(shutil.which("cmake") is None, reason="cmake not installed")

@@ -118,6 +118,7 @@ def load_library() -> C.CDLL:
         "tmac_hip_comm_last_error": ([], C.c_char_p),
         "tmac_hip_defer": ([C.c_int], i32),
         "tmac_hip_flush": ([vp], i32),
+        "tmac_hip_debug_defer_fail": ([C.c_int], i32),
         "tmac_hip_defer_stats": ([C.POINTER(C.c_uint64)] * 4, i32),
         "tmac_hip_chain_begin": ([], i32),
         "tmac_hip_chain_end": ([C.POINTER(vp)], i32),

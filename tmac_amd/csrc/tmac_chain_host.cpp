@@ -111,6 +111,7 @@ static int chain_pick_wpq(int total_q, int nst, int grid, int nwv = CHAIN_NWV) {
 
 extern "C" int32_t tmac_hip_chain_free(tmac_hip_chain* c) {
     if (!c) return TMAC_HIP_OK;
+    const int32_t brc = defer_barrier();       // (the calling thread's queued calls go first; the chain is freed whatever they return)
     for (void* p : c->peers) if (p) (void)hipIpcCloseMemHandle(p);
     if (c->arena) (void)hipFree(c->arena);
     if (c->images) (void)hipFree(c->images);
@@ -118,7 +119,7 @@ extern "C" int32_t tmac_hip_chain_free(tmac_hip_chain* c) {
     if (c->d_ops) (void)hipFree(c->d_ops);
     if (c->ctl) (void)hipFree(c->ctl);
     delete c;
-    return TMAC_HIP_OK;
+    return brc;
 }
 
 static void set_wpq(ChainOp& o, int wpq, int nwv) {   // waves per row quad of an op of nwv lookup waves, and what the kernels derive from it

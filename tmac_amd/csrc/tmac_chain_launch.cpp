@@ -5,6 +5,8 @@ using namespace tmac_host;
 
 extern "C" int32_t tmac_hip_chain_launch(tmac_hip_chain* c, void* stream) {
     bind_thread_device();
+    const int32_t brc = defer_barrier();       // behind the calling thread's deferred queue (the chain may read or overwrite what a queued call writes or reads)
+    if (brc) return brc;
     if (!c) return fail(TMAC_HIP_E_ARG, "null chain");
     hipStream_t st = (hipStream_t)stream;
     // One launch of a chain at a time (its hand-off buffers and control words are per chain): launches on ONE stream are

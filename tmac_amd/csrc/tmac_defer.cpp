@@ -13,6 +13,10 @@ using namespace tmac_host;
 // queue first, so a batch never carries a dependence and never needs a hand-off.  The recording built from a batch is cached by the
 // batch's signature (matrices, pointers, dtypes): a decode loop pays chain_build once per distinct batch.  What the persistent
 // kernels do not cover (chain_build returns -1) is launched call by call at the flush, as if it had never been queued.
+// Every other entry point that launches work or touches device memory for the caller goes behind the queue (defer_barrier: an
+// unconditional flush, no range analysis -- none of them is a hot path).  A call is checked when it is queued (fused_check: what it
+// would be refused for with deferral off), so a flush meets valid calls only; a flush launches ALL of them whatever fails on the way
+// (a failed stream launch: its calls one by one) and leaves the queue empty.
 // ---------------------------------------------------------------------------------------------
 namespace {
 struct DeferKey {
@@ -25,6 +29,7 @@ struct DeferKey {
 struct DeferEntry {
     std::vector<DeferKey> sig;
     std::vector<tmac_hip_chain*> chains;   // one stream-mode recording per configuration of the batch (bits, zero points, scale kind and dtype, output dtype)
+    std::vector<std::vector<uint32_t>> chain_calls;   // ... and the calls of the batch it stands for (launched one by one when its launch fails)
     std::vector<uint32_t> singles;         // calls of the batch launched one by one (no persistent form, or alone in their configuration)
     unsigned long long used;
 };
@@ -48,6 +53,12 @@ struct DeferState {
 thread_local DeferState g_defer;
 std::atomic<unsigned long long> g_defer_epoch{1};
 constexpr size_t DEFER_MAX_BATCH = 256, DEFER_CACHE = 32, DEFER_MIN_STREAM = 3;
+
+// tmac_hip_debug_defer_fail: is this launch attempt of a flush the one that was told to fail?  Host side only; one-shot.
+bool defer_injected_failure() {
+    if (g_knobs.defer_fail <= 0 || --g_knobs.defer_fail > 0) return false;
+    return true;
+}
 
 int32_t defer_flush(hipStream_t st) {
     DeferState& D = g_defer;
@@ -92,7 +103,7 @@ int32_t defer_flush(hipStream_t st) {
                 if (chain_build(calls, {}, &c) != TMAC_HIP_OK) c = nullptr;
                 if (c && !c->stream) { tmac_hip_chain_free(c); c = nullptr; }    // (a batch carries no dependence: anything but a stream is not worth a persistent launch)
             }
-            if (c) ne.chains.push_back(c);
+            if (c) { ne.chains.push_back(c); ne.chain_calls.push_back(grp); }
             else ne.singles.insert(ne.singles.end(), grp.begin(), grp.end());
         }
         if (D.cache.size() >= DEFER_CACHE) {                    // evict the least recently used recording
@@ -105,21 +116,27 @@ int32_t defer_flush(hipStream_t st) {
         hit = &D.cache.back();
     }
     hit->used = ++D.tick;
-    int32_t rc = TMAC_HIP_OK;
-    for (tmac_hip_chain* c : hit->chains) {
-        ++D.n_stream;
-        if ((rc = tmac_hip_chain_launch(c, st)) != TMAC_HIP_OK) return rc;
-    }
+    // Everything of the batch is launched whatever fails on the way; the first error of a call that was NOT launched is returned (a
+    // stream launch that failed and whose calls then went out one by one is no error of the flush).
+    int32_t first = TMAC_HIP_OK;
     const bool was_on = D.on;
     D.on = false;                                               // call by call, as if never queued
-    for (uint32_t j : hit->singles) {
+    auto single = [&](uint32_t j) {
         const ChainRecOp& r = batch[j];
         ++D.n_single;
-        rc = fused_impl(r.w.data(), (int)r.w.size(), r.B, r.act, r.C.data(), r.out, 1, nullptr, nullptr, st);
-        if (rc != TMAC_HIP_OK) break;
+        const int32_t rc = defer_injected_failure() ? fail(TMAC_HIP_E_RUNTIME, "deferred call: injected launch failure (tmac_hip_debug_defer_fail)")
+                                                    : fused_impl(r.w.data(), (int)r.w.size(), r.B, r.act, r.C.data(), r.out, 1, nullptr, nullptr, st);
+        if (rc != TMAC_HIP_OK && first == TMAC_HIP_OK) first = rc;
+    };
+    for (size_t g = 0; g < hit->chains.size(); ++g) {
+        ++D.n_stream;
+        const int32_t rc = defer_injected_failure() ? fail(TMAC_HIP_E_RUNTIME, "deferred batch: injected launch failure (tmac_hip_debug_defer_fail)")
+                                                    : tmac_hip_chain_launch(hit->chains[g], st);
+        if (rc != TMAC_HIP_OK) for (uint32_t j : hit->chain_calls[g]) single(j);
     }
+    for (uint32_t j : hit->singles) single(j);
     D.on = was_on;
-    return rc;
+    return first;
 }
 }  // namespace
 
@@ -128,12 +145,11 @@ bool tmac_host::defer_if_on(const tmac_hip_weights* const* wl, int nmat, const v
     DeferState& D = g_defer;
     if (!D.on) return false;
     *rc = TMAC_HIP_OK;
-    if (N != 1) { *rc = defer_flush(D.stream); return false; }               // (ordered behind the queue; launched as usual)
+    if (N != 1) { *rc = defer_flush(D.stream); return *rc != TMAC_HIP_OK; }    // (ordered behind the queue; launched as usual -- unless the queue failed)
+    // what the call would be refused for with deferral off: refused now, with that code and message, and the queue is left as it is
+    if ((*rc = fused_check(wl, nmat, C_list, 1)) != TMAC_HIP_OK) return true;
     ChainRecOp op;
-    for (int i = 0; i < nmat; ++i) {
-        if (!wl[i] || !C_list[i]) { *rc = fail(TMAC_HIP_E_ARG, "null matrix or output"); return true; }
-        op.w.push_back(wl[i]); op.C.push_back(C_list[i]);
-    }
+    for (int i = 0; i < nmat; ++i) { op.w.push_back(wl[i]); op.C.push_back(C_list[i]); }
     op.B = B_dev; op.act = act_dtype; op.out = out_dtype;
     memset(&op.xf, 0, sizeof(op.xf));
     // a dependence on the queue (RAW: reads a queued output; WAR / WAW: writes what a queued call reads or writes), another stream, or a
@@ -155,7 +171,12 @@ bool tmac_host::defer_if_on(const tmac_hip_weights* const* wl, int nmat, const v
     D.pending.push_back(op);
     return true;
 }
+int32_t tmac_host::defer_barrier() { return g_defer.pending.empty() ? TMAC_HIP_OK : defer_flush(g_defer.stream); }
 void tmac_host::defer_forget_all() { g_defer_epoch.fetch_add(1, std::memory_order_acq_rel); }
+void tmac_host::defer_reset_stats() {             // the calling thread's tmac_hip_defer_stats counters (tmac_hip_reset_state)
+    DeferState& D = g_defer;
+    D.n_flush = D.n_hit = D.n_stream = D.n_chain = D.n_single = 0;
+}
 void tmac_host::defer_release_thread() {          // the calling thread's cached recordings (nothing of them may be in flight: the caller has synchronised)
     DeferState& D = g_defer;
     for (DeferEntry& e : D.cache) defer_free_entry(e, false);
@@ -164,16 +185,17 @@ void tmac_host::defer_release_thread() {          // the calling thread's cached
 
 extern "C" int32_t tmac_hip_defer(int on) {
     DeferState& D = g_defer;
-    if (!on && !D.pending.empty()) {
-        const int32_t rc = defer_flush(D.stream);
-        if (rc != TMAC_HIP_OK) return rc;
-    }
+    const int32_t rc = on ? TMAC_HIP_OK : defer_barrier();      // (the queue is empty afterwards whatever the flush returns)
     D.on = on != 0;
-    return TMAC_HIP_OK;
+    return rc;
 }
 extern "C" int32_t tmac_hip_flush(void* stream) {
     (void)stream;                                               // (the queue remembers the stream its calls were issued on)
     return defer_flush(g_defer.stream);
+}
+extern "C" int32_t tmac_hip_debug_defer_fail(int nth) {
+    g_knobs.defer_fail = nth > 0 ? nth : 0;
+    return TMAC_HIP_OK;
 }
 extern "C" int32_t tmac_hip_defer_stats(uint64_t* flushes, uint64_t* cache_hits, uint64_t* stream_launches, uint64_t* single_calls) {
     const DeferState& D = g_defer;

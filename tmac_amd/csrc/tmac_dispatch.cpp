@@ -142,6 +142,11 @@ static Plan plan_fused(const tmac_hip_weights* const* wl, void* const* C_list, i
     return planned(layout_of(wl[0]->s) == L_QUAD ? R_GEMV_QUAD : R_GEMV_FUSED);
 }
 
+int32_t tmac_host::fused_check(const tmac_hip_weights* const* wl, int nmat, void* const* C_list, int N) {
+    const Plan p = plan_fused(wl, C_list, nmat, N, false);
+    return p.err ? fail(p.err, p.msg, p.mat) : TMAC_HIP_OK;
+}
+
 // ---- argument blocks of the planned kernels --------------------------------------------------------------------------------
 static void fill_gemm_mats(GemmMat* m, const tmac_hip_weights* const* wl, void* const* C_list, int nmat) {
     for (int i = 0; i < nmat; ++i) { m[i].W = wl[i]->W; m[i].SC = wl[i]->SC; m[i].C = C_list[i]; m[i].Mw = wl[i]->s.Mw; }
@@ -205,6 +210,8 @@ static int32_t planes_multi(const tmac_hip_weights* const* wl, int nmat, const t
 int32_t tmac_host::qgemm_impl(const tmac_hip_weights* w, const tmac_hip_workspace* ws, void* C_dev, tmac_dtype_t out_dtype,
                           int N, int32_t* dump, hipStream_t st) {
     bind_thread_device();
+    const int32_t brc = defer_barrier();       // behind the calling thread's deferred queue (the LUT may come from a queued output; C_dev may be one)
+    if (brc) return brc;
     if (!w || !ws || !C_dev) return fail(TMAC_HIP_E_ARG, "null argument");
     if (ws->K != w->s.K || ws->ags != w->s.ags)
         return fail(TMAC_HIP_E_ARG, "workspace LUT (K=%d, ags=%d) does not match the weights (K=%d, ags=%d)", ws->K, ws->ags, w->s.K, w->s.ags);
@@ -299,6 +306,8 @@ extern "C" int32_t tmac_hip_debug_gemm_kernel(int which) {
 // Parity tap of k_gemm_planes: the combined integer sums comb[n][o][kk] = sum_p 2^p PS_p it feeds into the fp32 chain.
 extern "C" int32_t tmac_hip_debug_gemm_comb_sums(const tmac_hip_weights* w, const tmac_hip_workspace* ws_c, int32_t* comb_host,
                                                  int N, void* stream) {
+    const int32_t brc = defer_barrier();
+    if (brc) return brc;
     if (!w || !ws_c || !comb_host) return fail(TMAC_HIP_E_ARG, "null argument");
     auto* ws = const_cast<tmac_hip_workspace*>(ws_c);
     hipStream_t st = (hipStream_t)stream;
@@ -316,6 +325,8 @@ extern "C" int32_t tmac_hip_debug_gemm_comb_sums(const tmac_hip_weights* w, cons
 // per-act-group entry sums, fp32 [N][K/64] each.
 extern "C" int32_t tmac_hip_debug_gemm_image_read(const tmac_hip_workspace* ws, int8_t* half_tables_host, float* lut_scales_host,
                                                   float* lut_biases_host, float* entry_sums_host, int N, void* stream) {
+    const int32_t brc = defer_barrier();
+    if (brc) return brc;
     if (!ws || !half_tables_host || !lut_scales_host || !lut_biases_host || !entry_sums_host) return fail(TMAC_HIP_E_ARG, "null argument");
     if (!ws->gimg_valid || N <= 0 || N > ws->N) return fail(TMAC_HIP_E_ARG, "the workspace holds no LUT image for N=%d", N);
     hipStream_t st = (hipStream_t)stream;
@@ -419,6 +430,9 @@ int32_t tmac_host::fused_impl(const tmac_hip_weights* const* wl, int nmat, const
     if (!tap) {           // deferred launches: queued until tmac_hip_flush (or a call that depends on a queued one)
         int32_t drc;
         if (defer_if_on(wl, nmat, B_dev, act_dtype, C_list, out_dtype, N, st, &drc)) return drc;
+    } else {              // a tap is never queued: it goes behind the queue (B_dev may be a queued output)
+        const int32_t brc = defer_barrier();
+        if (brc) return brc;
     }
     const Plan p = plan_fused(wl, C_list, nmat, N, tap);
     if (p.err) return fail(p.err, p.msg, p.mat);

@@ -103,6 +103,7 @@ struct Knobs {
     int ws_fill_sync = 1;          // test knob (tmac_hip_debug_ws_fill_sync): 0 re-opens the round-2 race between the workspace fills and its first user
     int chain_wpq = 0;             // waves per row quad for every op of chains built from now on (0 = per-op choice)
     unsigned chain_spin_limit = 1u << 18;   // polls of one hand-off before a wave gives up (~0.4 s)
+    int defer_fail = 0;            // test hook (tmac_hip_debug_defer_fail): the n-th launch attempted by the deferred queue's flushes fails on the host side; one-shot
     int chain_grid = 0;            // workgroups of chains built from now on (0 = one per CU; tests run two chains side by side on one device)
     unsigned long long* stamps = nullptr;        // phase stamps of the next fused launches (tmac_hip_debug_stamps)
     int32_t* stamp_dump = nullptr;               // scratch the stamp instantiation stores its tap into (allocated once, survives resets)
@@ -152,6 +153,9 @@ int32_t qgemm_impl(const tmac_hip_weights* w, const tmac_hip_workspace* ws, void
                    hipStream_t st);
 int32_t fused_impl(const tmac_hip_weights* const* wl, int nmat, const void* B_dev, tmac_dtype_t act_dtype, void* const* C_list,
                    tmac_dtype_t out_dtype, int N, int32_t* dump, float* lut_tap, hipStream_t st);
+// what a non-deferred, tap-less fused call is refused for (the per-matrix null checks and plan_fused): TMAC_HIP_OK, or fail(code, message).
+// Pure: reads its arguments and g_knobs.
+int32_t fused_check(const tmac_hip_weights* const* wl, int nmat, void* const* C_list, int N);
 void release_fused_workspaces();   // caller holds g_mu
 
 // ---- tuner (tmac_tuner.cpp) -----------------------------------------------------------------------
@@ -165,7 +169,12 @@ int32_t chain_record(const tmac_hip_weights* const* wl, int nmat, const void* B_
 // deferred launches (tmac_hip_defer): true (and *rc set) when the call was queued instead of launched
 bool defer_if_on(const tmac_hip_weights* const* wl, int nmat, const void* B_dev, tmac_dtype_t act_dtype, void* const* C_list, tmac_dtype_t out_dtype,
                  int N, hipStream_t st, int32_t* rc);
+// Orders an entry point behind the calling thread's queue: flushes it when it is not empty and returns the flush's status (one
+// vector::empty() otherwise).  First statement of every entry point that launches work or touches device memory for the caller; when it
+// fails, nothing of the entry point is launched.  defer_flush takes the queue before it launches: the entry points it calls see none.
+int32_t defer_barrier();
 void defer_release_thread();       // frees the calling thread's cached recordings (tmac_hip_cache_clear)
+void defer_reset_stats();          // zeroes the calling thread's tmac_hip_defer_stats counters (tmac_hip_reset_state)
 void defer_forget_all();           // weights were freed / the library was reset: cached recordings of every thread are stale from now on
 // true (and *rc set) when the calling thread is recording: the exchange step was noted, not executed
 bool chain_record_gather_if_recording(const void* send_dev, void* recv_dev, size_t bytes_per_rank, int rank, int world, int32_t* rc);

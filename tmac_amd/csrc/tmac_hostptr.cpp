@@ -218,6 +218,7 @@ static void evict_to_cap(const HostRun* keep) {
 }
 
 extern "C" int32_t tmac_hip_cache_clear(void) {
+    const int32_t brc = defer_barrier();      // the calling thread's queued calls are launched before anything they might use is released
     (void)hipDeviceSynchronize();
     defer_release_thread();                   // the calling thread's cached recordings of deferred batches (tmac_hip_defer)
     std::unique_lock<std::shared_mutex> hl(H.mu);
@@ -229,7 +230,7 @@ extern "C" int32_t tmac_hip_cache_clear(void) {
     H.runs.clear();
     H.cache_dev_bytes = 0;
     release_fused_workspaces();
-    return TMAC_HIP_OK;
+    return brc;
 }
 
 // A/B knob: 0 = serve every tile call on its own (the literal reading of the reference's ABI), 1 = whole runs (default)

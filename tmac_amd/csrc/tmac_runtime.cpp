@@ -161,9 +161,13 @@ extern "C" int32_t tmac_hip_debug_ws_fill_sync(int on) {
 }
 
 extern "C" int32_t tmac_hip_reset_state(void) {
-    (void)tmac_hip_defer(0);                  // (launches what the calling thread still has queued, then leaves deferred mode)
+    // launches what the calling thread still has queued, then leaves deferred mode: whatever that flush returns the queue is empty and
+    // the mode off afterwards, and the rest of the reset runs (the first error is returned at the end)
+    const int32_t drc = tmac_hip_defer(0);
+    defer_reset_stats();                      // (the counters are state like any other: a freshly loaded library has counted nothing)
     defer_forget_all();
     int32_t rc = tmac_hip_cache_clear();      // host-pointer tiles / runs, the fused entry point's per-stream workspaces
+    if (drc) rc = drc;
     host_route_release();                     // ... and the host-pointer layer's workspace, staging buffers and LUT memo
     {
         std::lock_guard<std::mutex> lk(g_mu);

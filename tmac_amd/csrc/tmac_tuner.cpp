@@ -95,6 +95,7 @@ extern "C" int32_t tmac_hip_autotune_fused(const tmac_hip_weights* const* wl, in
     if (!wl || nmat < 1 || nmat > 4) return fail(TMAC_HIP_E_ARG, "bad autotune arguments (1..4 matrices)");
     int32_t rc = ensure_device();
     if (rc) return rc;
+    if ((rc = defer_barrier())) return rc;    // (the timed launches are not queued; what the thread has queued goes first)
     size_t bytes = 0;
     for (int i = 0; i < nmat; ++i) {
         if (!wl[i] || layout_of(wl[i]->s) != L_QUAD || !wl[i]->tiled_ok) return fail(TMAC_HIP_E_NOMATCH, "matrix %d is not registered in the QUAD layout", i);

@@ -122,13 +122,16 @@ extern "C" int32_t tmac_hip_register_weights_dev(tmac_hip_weights** out, const v
 
 extern "C" int32_t tmac_hip_free_weights(tmac_hip_weights* w) {
     if (!w) return TMAC_HIP_OK;
+    // The calling thread's queue may name this matrix: its calls are launched first (a queue belongs to a thread: freeing weights another
+    // thread has queued is the caller's error).  The matrix is freed whatever they return -- the handle is dead either way.
+    const int32_t brc = defer_barrier();
     defer_forget_all();       // recordings cached by the deferred-launch queue may name this matrix
     if (w->W) (void)hipFree(w->W);
     if (w->SC) (void)hipFree(w->SC);
     if (w->A_ref) (void)hipFree(w->A_ref);
     if (w->S_ref) (void)hipFree(w->S_ref);
     delete w;
-    return TMAC_HIP_OK;
+    return brc;
 }
 
 extern "C" size_t tmac_hip_weights_bytes(const tmac_hip_weights* w) {

@@ -61,7 +61,9 @@ int32_t tmac_host::check_lut_shape(tmac_hip_workspace* ws, int K, int N, int ags
 extern "C" int32_t tmac_hip_preprocessor_dev(tmac_hip_workspace* ws, const void* B_dev, tmac_dtype_t act_dtype, int K,
                                              int N, int act_group_size, void* stream) {
     bind_thread_device();
-    int32_t rc = check_lut_shape(ws, K, N, act_group_size);
+    int32_t rc = defer_barrier();             // behind the calling thread's deferred queue (B_dev may be a queued call's output)
+    if (rc) return rc;
+    rc = check_lut_shape(ws, K, N, act_group_size);
     if (rc) return rc;
     if (!B_dev) return fail(TMAC_HIP_E_ARG, "null activations");
     ws->K = K; ws->N = N; ws->ags = act_group_size; ws->qdev_u4_per_row = qdev_u4_for_K(K);
@@ -104,7 +106,9 @@ extern "C" int32_t tmac_hip_workspace_ptrs(tmac_hip_workspace* ws, void** qlut_d
 
 extern "C" int32_t tmac_hip_workspace_read(tmac_hip_workspace* ws, int8_t* qlut_host, float* lut_scales_host,
                                            float* lut_biases_host, int K, int N, int act_group_size, void* stream) {
-    int32_t rc = check_lut_shape(ws, K, N, act_group_size);
+    int32_t rc = defer_barrier();
+    if (rc) return rc;
+    rc = check_lut_shape(ws, K, N, act_group_size);
     if (rc) return rc;
     if (ws->K != K || ws->N != N || ws->ags != act_group_size) return fail(TMAC_HIP_E_ARG, "workspace holds a different LUT");
     hipStream_t st = (hipStream_t)stream;
@@ -118,7 +122,9 @@ extern "C" int32_t tmac_hip_workspace_read(tmac_hip_workspace* ws, int8_t* qlut_
 
 extern "C" int32_t tmac_hip_workspace_write(tmac_hip_workspace* ws, const int8_t* qlut_host, const float* lut_scales_host,
                                             const float* lut_biases_host, int K, int N, int act_group_size, void* stream) {
-    int32_t rc = check_lut_shape(ws, K, N, act_group_size);
+    int32_t rc = defer_barrier();
+    if (rc) return rc;
+    rc = check_lut_shape(ws, K, N, act_group_size);
     if (rc) return rc;
     if (!qlut_host || !lut_scales_host || !lut_biases_host) return fail(TMAC_HIP_E_ARG, "null LUT pointer");
     hipStream_t st = (hipStream_t)stream;
