@@ -274,3 +274,77 @@ def make_case(seed: int, Mw: int, K: int, N: int = 1, bits: int = 2, gs: int = 1
             zr = zr.astype(np.float16).astype(np.float32)
         B = B.astype(np.float16).astype(np.float32)
     return dict(w=w, sc=sc, zr=zr, B=B)
+
+
+HARD_WEIGHTS = ("max", "min", "rows", "planes", "kblocks")
+HARD_ACTS = ("const", "negblocks", "spike")
+
+
+def hard_weights(name: str, Mw: int, K: int, bits: int) -> np.ndarray:
+    """uint8 [Mw][K] weight levels that drive the integer path to its limits (L = 2^bits - 1):
+    max / min: every level L / 0 (every bit-plane nibble 15 / 0); rows: odd output rows L, even rows 0 (neighbouring rows share
+    packed lanes and operand bytes); planes: even rows 0b1010 & L, odd rows 0b0101 & L (neighbouring bit-planes of one row at
+    opposite extremes); kblocks: L on the even 64-element blocks of K, 0 on the odd ones (the sums swing across every flush)."""
+    L = 2 ** bits - 1
+    w = np.zeros((Mw, K), np.uint8)
+    if name == "max":
+        w[:] = L
+    elif name == "min":
+        pass
+    elif name == "rows":
+        w[1::2] = L
+    elif name == "planes":
+        w[0::2] = 0b1010 & L
+        w[1::2] = 0b0101 & L
+    elif name == "kblocks":
+        w[:, (np.arange(K) // 64) % 2 == 0] = L
+    else:
+        raise ValueError(f"unknown weight pattern {name!r}")
+    return w
+
+
+def hard_acts(name: str, K: int, seed: int = 0) -> np.ndarray:
+    """float32 [K], fp16-representable.  const: every element 0.75 (table entries exactly +-127, +-64 -- the 63.5 round-to-even
+    tie -- and 0); negblocks: the sign of 0.75 alternates per 64 elements; spike: every 4-tuple is [3, 0, 0, 0] (all 16 entries of
+    every table +-127); normal: a standard-normal row (the fourth row of the N > 1 cycle)."""
+    if name == "const":
+        return np.full(K, 0.75, np.float32)
+    if name == "negblocks":
+        return np.where((np.arange(K) // 64) % 2 == 0, 0.75, -0.75).astype(np.float32)
+    if name == "spike":
+        return np.tile(np.array([3, 0, 0, 0], np.float32), K // 4)
+    if name == "normal":
+        return np.random.default_rng(seed).standard_normal(K).astype(np.float16).astype(np.float32)
+    raise ValueError(f"unknown activation pattern {name!r}")
+
+
+def assert_saturates(weights: str, acts: str, q_row: np.ndarray, sums_row: np.ndarray, ags: int, K: int) -> None:
+    """The self-check every saturating test starts with, on the ORACLE's results for activation row 0: the input is what it claims
+    to be.  q_row int8 [K/4][16]; sums_row: integer partial sums [M][K/ags] (per-group) or totals [M] (unified scale, ags == K)."""
+    aq = np.abs(q_row.astype(np.int32))
+    if acts == "spike":
+        assert aq.min() == 127, "spike: every table entry must be +-127"
+    else:
+        assert sorted(np.unique(aq)) == [0, 64, 127], "const / negblocks: table entries must be exactly {+-127, +-64, 0}"
+    # every lookup of a constant bit-plane returns the same +-127: a whole act group of one sign sums to +-127 ags / 4.  Where the sign
+    # flips per 64-element block inside the accumulation range (kblocks weights or negblocks activations under a unified scale, not
+    # both) the running total swings by +-2032 from block to block and ends where the blocks leave it: at 0 for an even number of
+    # blocks, at +-2032 for an odd one.  Those inputs exercise the swing, not the limit, and that end value pins them
+    one_sign = ags < K or ((weights == "kblocks") == (acts == "negblocks"))
+    if one_sign:
+        assert np.abs(sums_row).max() == 127 * ags // 4, "the accumulators do not reach their limit"
+    else:
+        assert np.abs(sums_row).max() == 2032 * ((K // 64) % 2), "the alternating blocks do not cancel as they should"
+
+
+def make_hard_case(weights: str, acts: str, Mw: int, K: int, N: int = 1, bits: int = 2, gs: int = 128, ags: int = 64,
+                   zero_point: bool = True, m_groups: int = -1, seed: int = 0):
+    """make_case's dict with saturating data: scales and zero points are make_case's (fp16-representable), ``w`` is the weight
+    pattern and row 0 of ``B`` the activation pattern named; for N > 1 the rows cycle on through const, negblocks, spike and one
+    standard-normal row, so that a row leaking into another row's tile shows."""
+    case = make_case(seed, Mw, K, N=N, bits=bits, gs=gs, ags=ags, zero_point=zero_point, m_groups=m_groups, fp16_values=True)
+    case["w"] = hard_weights(weights, Mw, K, bits)
+    cycle = HARD_ACTS + ("normal",)
+    first = cycle.index(acts)
+    case["B"] = np.stack([hard_acts(cycle[(first + n) % 4], K, seed + n) for n in range(N)])
+    return case

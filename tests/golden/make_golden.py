@@ -5,6 +5,7 @@ Run where the reference's sources lie (oracle.REF_ROOT) after `make -C oracle re
 
     python tests/golden/make_golden.py             # everything
     python tests/golden/make_golden.py vs_ref      # ref/oracle_vs_ref.npz alone (tests/test_oracle_vs_ref.py)
+    python tests/golden/make_golden.py saturating  # ref/saturating.npz alone (the saturating inputs of tests/test_oracle_vs_ref.py)
     python tests/golden/make_golden.py convert     # ref/convert_ref.json and ref/kcfg/ alone (tests/test_convert.py)
 
 Sources of truth used here (never our own restatement):
@@ -167,6 +168,32 @@ def gen_vs_ref():
     print("ref/oracle_vs_ref.npz", len(out), "arrays")
 
 
+def gen_saturating():
+    """ref/saturating.npz: the reference's answers for the saturating inputs of tests/test_oracle_vs_ref.py (oracle.make_hard_case;
+    its helpers build them)"""
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import test_oracle_vs_ref as T
+    out = {}
+    for K, ags in T.SAT_PRE_CASES:
+        for acts in orc.HARD_ACTS:
+            for n, v in zip(("q", "ls", "lb"), orc.ref_preprocessor(orc.hard_acts(acts, K), ags)):
+                out[T.key("pre", acts, K, ags, n)] = v
+    for weights in T.SAT_WEIGHTS:
+        for tag, cfgs, fa in (("fp", T.CFGS, False), ("fa", T.FA_CFGS, True)):
+            for bits, bm, kf, gs, ags, zp in cfgs:
+                A, S, q, ls, lb, case = T.sat_float_case(bits, bm, kf, gs, ags, zp, weights)
+                Mw, K = case["w"].shape
+                out[T.key(tag, weights, bits, bm, kf, gs, ags, zp, "cbits")] = orc.ref_cbits_float(A, q[0], S, ls[0], lb[0], Mw, K, bits, bm, kf, gs, ags, zp, fa=fa)
+                if not fa and T.has_int_partial_sums(bits, kf, ags):
+                    out[T.key(tag, weights, bits, bm, kf, gs, ags, zp, "ps")] = orc.ref_partial_sums(A, q[0], Mw, K, bits, bm, kf, ags)
+    for weights in ("max", "rows"):
+        for bits, bm, Mw, K in T.SAT_INT32_CASES:
+            A, q, ls, lb, case = T.sat_int32_case(bits, bm, Mw, K, weights)
+            out[T.key("i32", weights, bits, bm, Mw, K, "cb")] = orc.ref_cbits_int32(A, q[0], Mw, K, bits, bm, 16)
+    np.savez_compressed(os.path.join(HERE, "ref", "saturating.npz"), **out)
+    print("ref/saturating.npz", len(out), "arrays")
+
+
 def gen_convert_ref():
     """ref/convert_ref.json: what the reference's model_utils returns for the inputs tests/test_convert.py draws (its helpers build them);
     arrays as digests.  ref/kcfg/*.ini: the kcfg.ini files the reference ships for two prebuilt sets."""
@@ -205,7 +232,11 @@ if __name__ == "__main__":
     if sys.argv[1:] == ["vs_ref"]:
         gen_vs_ref()
         sys.exit(0)
+    if sys.argv[1:] == ["saturating"]:
+        gen_saturating()
+        sys.exit(0)
     gen_vs_ref()
+    gen_saturating()
     gen_convert_ref()
     gen_kat()
     gen("w2_zp_g128_a64", 1, 128, 512, 2, 128, 16, 128, 64, True)

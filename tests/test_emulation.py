@@ -87,3 +87,49 @@ def test_emulation_fast_aggregation(emu, bits, bm, kf, ags, Mw, K):
     for fa in (1, 2):
         _, tap = orc.qgemm_float_fa(A, q, S, ls, lb, Mw, K, 1, bits, bm, kf, 128, ags, True, fa)
         assert np.array_equal(run_emu(emu, A, q[0], Mw, K, bits, bm, kf, ags, 4 + fa), tap[0])
+
+
+# ---- saturating inputs (oracle.make_hard_case): LUTs from the LUT constructor, weights at the extremes -------------------------------
+HARD_EMU_CFGS = [  # bits, bm, kf, ags, Mw, K
+    (1, 128, 16, 64, 256, 1024), (2, 128, 16, 64, 128, 1024), (3, 192, 16, 64, 128, 1024), (4, 256, 16, 64, 128, 1024),
+    (2, 320, 16, 18432, 160, 18432), (4, 256, 16, 18432, 64, 18432),      # unified scale at the largest K: totals of +-127 K / 4
+]
+
+
+@pytest.mark.parametrize("acts", ["const", "spike"])
+@pytest.mark.parametrize("weights", orc.HARD_WEIGHTS)
+@pytest.mark.parametrize("bits,bm,kf,ags,Mw,K", HARD_EMU_CFGS)
+def test_emulation_saturating_inputs(emu, bits, bm, kf, ags, Mw, K, weights, acts):
+    """constant / alternating weight levels against tables whose entries are all +-127 (spike) or {+-127, +-64, 0} (const), built by the
+    LUT constructor: every 16-lookup packed sum sits at 16 x 254 or 16 x 0 of its 12-bit field, every act group at +-2032, a unified
+    total at +-127 K / 4 -- every emulation mode equal to the oracle's integers"""
+    mg = 1 if ags == K else -1
+    case = orc.make_hard_case(weights, acts, Mw, K, bits=bits, ags=ags, zero_point=mg == -1, m_groups=mg)
+    A = orc.preprocess_weights(case["w"], bits, bm, kf)
+    q, ls, lb = orc.preprocessor(case["B"], ags)
+    if mg == -1:
+        want = orc.partial_sums(A, q[0], Mw, K, bits, bm, kf, ags)
+    else:
+        _, cb = orc.qgemm_scale_final(A, q, case["sc"], ls[:, 0], lb[:, 0], Mw, K, 1, bits, bm, kf, 1)
+        want = cb[0][:, None]
+    orc.assert_saturates(weights, acts, q[0], want, ags, K)
+    for mode in (0, 1, 2, 3, 4):
+        assert np.array_equal(run_emu(emu, A, q[0], Mw, K, bits, bm, kf, ags, mode), want), mode
+
+
+@pytest.mark.parametrize("weights", ["max", "min", "rows"])
+@pytest.mark.parametrize("bits,bm,kf,ags,Mw,K", [
+    (1, 128, 16, 64, 256, 1024), (2, 128, 16, 64, 128, 1024), (3, 192, 16, 64, 128, 1024), (4, 256, 16, 64, 128, 1024),
+    (2, 128, 8, 32, 128, 1024),
+])
+def test_emulation_fast_aggregation_saturating_inputs(emu, bits, bm, kf, ags, Mw, K, weights):
+    """(a9) the halving-adder trees fed +-127 at every leaf: both flavours equal to the oracle's tree, whose results touch +-127"""
+    case = orc.make_hard_case(weights, "const", Mw, K, bits=bits, ags=ags)
+    A = orc.preprocess_weights(case["w"], bits, bm, kf)
+    S = orc.preprocess_scales(case["sc"], case["zr"], bits, bm)
+    q, ls, lb = orc.preprocessor(case["B"], ags)
+    orc.assert_saturates(weights, "const", q[0], orc.partial_sums(A, q[0], Mw, K, bits, bm, kf, ags), ags, K)
+    for fa in (1, 2):
+        _, tap = orc.qgemm_float_fa(A, q, S, ls, lb, Mw, K, 1, bits, bm, kf, 128, ags, True, fa)
+        assert tap.max() == (127 if weights != "min" else -127) and tap.min() == (-127 if weights != "max" else 127)
+        assert np.array_equal(run_emu(emu, A, q[0], Mw, K, bits, bm, kf, ags, 4 + fa), tap[0])

@@ -42,9 +42,12 @@ def rel_err(c, ref):
 class Model:
     """ops: list of (K, [Mw, ...], src) with src = None (external activations) or (op index, matrix index).
     mg = -1: per-group scales (+ zero points), act groups of 64 (tbl.cc:323-532); mg >= 1: unified scale(s), one act group
-    per row, int32 totals + scale-final (BitNet: tbl.cc:536-630, qgemm.py:170-174)."""
+    per row, int32 totals + scale-final (BitNet: tbl.cc:536-630, qgemm.py:170-174).
+    weights_fn(i, m, Mw, K, bits) -> uint8 [Mw][K] weight levels of op i's matrix m, or None for the random ones; x_fn(i, K) -> float32 [K]
+    external activations of op i, or None for the standard-normal ones (tests/test_gpu_saturating.py)."""
 
-    def __init__(self, tm, ops, bits=2, zp=True, dev_f16=True, seed=0, out_f16=True, mg=-1, ternary=False, ext_f32=False):
+    def __init__(self, tm, ops, bits=2, zp=True, dev_f16=True, seed=0, out_f16=True, mg=-1, ternary=False, ext_f32=False,
+                 weights_fn=None, x_fn=None):
         import torch
         self.tm, self.ops, self.bits, self.zp, self.mg = tm, ops, bits, zp and mg < 1, mg
         self.ext_f32 = ext_f32                   # vectors in memory are fp32 (a caller with an fp32 graph); handed-over ones stay fp16
@@ -62,6 +65,9 @@ class Model:
                     # BitNet's own data: ternary weights {-1, 0, 1} stored as levels {1, 2, 3} of the 2-bit format: zero-mean,
                     # variance 2/3 -- a chain of any depth keeps O(1) activations with scales around 1 / sqrt(2 K / 3)
                     case["w"] = np.random.default_rng(5000 + 1000 * seed + 10 * i + m).integers(1, 4, size=(Mw, K), dtype=np.uint8)
+                w_given = weights_fn(i, m, Mw, K, bits) if weights_fn is not None else None
+                if w_given is not None:
+                    case["w"] = np.ascontiguousarray(w_given, np.uint8)
                 A = orc.preprocess_weights(case["w"], bits, bm, KF)
                 if mg >= 1 and bits == 2 and ternary:
                     S = ((0.8 + 0.4 * np.minimum(case["sc"], 1.0)) / np.sqrt(2.0 * K / 3.0)).astype(np.float16).astype(np.float32)
@@ -84,7 +90,11 @@ class Model:
                 os_.append(torch.zeros(Mw, dtype=torch.float16 if out_f16 else torch.float32, device="cuda"))
             self.host.append(hs); self.ws.append(ws); self.outs.append(os_)
             if src is None:
-                self.x_ext[i] = torch.from_numpy(rng.standard_normal(K).astype(np.float32)).cuda()
+                x = rng.standard_normal(K).astype(np.float32)
+                x_given = x_fn(i, K) if x_fn is not None else None
+                if x_given is not None:
+                    x = np.ascontiguousarray(x_given, np.float32)
+                self.x_ext[i] = torch.from_numpy(x).cuda()
                 if not ext_f32:
                     self.x_ext[i] = self.x_ext[i].half()
 

@@ -178,3 +178,81 @@ def test_int32_scale_final_path(ref, bits, bm, Mw, K):
     assert np.array_equal(cb[0], ref[key("i32", bits, bm, Mw, K, "cb")])
     Cdq = orc.dequant_matmul(case["w"], case["sc"], None, case["B"], bits, 128, m_groups=1)[0]
     assert np.mean((Cdq - Cor[0]) ** 2) / np.mean(Cdq ** 2) < 5e-4
+
+
+# ---- saturating inputs (oracle.make_hard_case): the reference's answers are recorded in golden/ref/saturating.npz ---------------------
+SAT_GOLDEN = os.path.join(os.path.dirname(GOLDEN), "saturating.npz")
+SAT_PRE_CASES = [(1024, 64), (1024, 32), (3200, 3200)]
+SAT_WEIGHTS = ["max", "min", "rows", "planes"]
+SAT_INT32_CASES = [(2, 320, 320, 3200), (4, 256, 192, 12288), (3, 192, 64, 12288), (1, 64, 320, 8640)]
+
+
+@pytest.fixture(scope="module")
+def sat():
+    with np.load(SAT_GOLDEN) as z:
+        return {k: z[k] for k in z.files}
+
+
+def sat_float_case(bits, bm, kfactor, gs, ags, zp, weights):
+    Mw, K = bm // bits * 2, 1024
+    case = orc.make_hard_case(weights, "const", Mw, K, bits=bits, gs=gs, ags=ags, zero_point=zp, seed=11 * bits + ags)
+    A = orc.preprocess_weights(case["w"], bits, bm, kfactor)
+    S = orc.preprocess_scales(case["sc"], case["zr"], bits, bm)
+    q, ls, lb = orc.preprocessor(case["B"], ags)
+    return A, S, q, ls, lb, case
+
+
+def sat_int32_case(bits, bm, Mw, K, weights):
+    case = orc.make_hard_case(weights, "const", Mw, K, bits=bits, m_groups=1, ags=K, zero_point=False, seed=5)
+    A = orc.preprocess_weights(case["w"], bits, bm, 16)
+    q, ls, lb = orc.preprocessor(case["B"], K)
+    return A, q, ls, lb, case
+
+
+@pytest.mark.parametrize("acts", orc.HARD_ACTS)
+@pytest.mark.parametrize("K,ags", SAT_PRE_CASES)
+def test_preprocessor_saturating_inputs(sat, K, ags, acts):
+    """tables of +-127 only (spike) and the 63.5 round-to-even tie in every table (const, negblocks)"""
+    q, ls, lb = orc.preprocessor(orc.hard_acts(acts, K)[None, :], ags)
+    assert np.abs(q).min() == 127 if acts == "spike" else sorted(np.unique(np.abs(q.astype(np.int32)))) == [0, 64, 127]
+    qr, lsr, lbr = (sat[key("pre", acts, K, ags, n)] for n in ("q", "ls", "lb"))
+    assert np.array_equal(q[0], qr)
+    assert np.array_equal(ls[0].view(np.uint32), lsr.view(np.uint32))
+    assert np.array_equal(lb[0].view(np.uint32), lbr.view(np.uint32))
+
+
+@pytest.mark.parametrize("weights", SAT_WEIGHTS)
+@pytest.mark.parametrize("bits,bm,kfactor,gs,ags,zp", CFGS)
+def test_float_path_saturating_inputs(sat, bits, bm, kfactor, gs, ags, zp, weights):
+    A, S, q, ls, lb, case = sat_float_case(bits, bm, kfactor, gs, ags, zp, weights)
+    Mw, K = case["w"].shape
+    PS = orc.partial_sums(A, q[0], Mw, K, bits, bm, kfactor, ags)
+    orc.assert_saturates(weights, "const", q[0], PS, ags, K)
+    Cor = orc.qgemm_float(A, q, S, ls, lb, Mw, K, 1, bits, bm, kfactor, gs, ags, zp)
+    Cref = orc.combine_planes(sat[key("fp", weights, bits, bm, kfactor, gs, ags, zp, "cbits")], Mw, bits)
+    assert np.array_equal(Cor[0].view(np.uint32), Cref.view(np.uint32))
+    if has_int_partial_sums(bits, kfactor, ags):
+        assert np.array_equal(PS, sat[key("fp", weights, bits, bm, kfactor, gs, ags, zp, "ps")])
+
+
+@pytest.mark.parametrize("weights", SAT_WEIGHTS)
+@pytest.mark.parametrize("bits,bm,kfactor,gs,ags,zp", FA_CFGS)
+def test_fast_aggregation_saturating_inputs(sat, bits, bm, kfactor, gs, ags, zp, weights):
+    """(a9) the halving-adder tree with +-127 at every leaf"""
+    A, S, q, ls, lb, case = sat_float_case(bits, bm, kfactor, gs, ags, zp, weights)
+    Mw, K = case["w"].shape
+    orc.assert_saturates(weights, "const", q[0], orc.partial_sums(A, q[0], Mw, K, bits, bm, kfactor, ags), ags, K)
+    Cor, tap = orc.qgemm_float_fa(A, q, S, ls, lb, Mw, K, 1, bits, bm, kfactor, gs, ags, zp, fa_mode=2)
+    Cref = orc.combine_planes(sat[key("fa", weights, bits, bm, kfactor, gs, ags, zp, "cbits")], Mw, bits)
+    assert np.array_equal(Cor[0].view(np.uint32), Cref.view(np.uint32))
+    assert tap.max() == (127 if weights != "min" else -127) and tap.min() == (-127 if weights != "max" else 127)
+
+
+@pytest.mark.parametrize("weights", ["max", "rows"])
+@pytest.mark.parametrize("bits,bm,Mw,K", SAT_INT32_CASES)
+def test_int32_scale_final_saturating_inputs(sat, bits, bm, Mw, K, weights):
+    """one running total across the whole K: +-127 K / 4"""
+    A, q, ls, lb, case = sat_int32_case(bits, bm, Mw, K, weights)
+    _, cb = orc.qgemm_scale_final(A, q, case["sc"], ls[:, 0], lb[:, 0], Mw, K, 1, bits, bm, 16, 1)
+    orc.assert_saturates(weights, "const", q[0], cb[0], K, K)
+    assert np.array_equal(cb[0], sat[key("i32", weights, bits, bm, Mw, K, "cb")])
