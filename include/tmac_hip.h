@@ -93,6 +93,26 @@ int32_t tmac_hip_set_kcfg(int M, int K, int N, int bits, const tmac_kcfg* cfg);
 
 /* ---- (2) device-resident path ---------------------------------------------------------- */
 
+/* Alignment of the caller's DEVICE pointers.  The kernels read and write caller memory with vector accesses; a pointer below the widest
+ * access it gets is refused with TMAC_HIP_E_ARG and a message naming the argument -- at once, also while recording a chain or with
+ * deferral on (nothing is launched, recorded or queued; the queue and the recording stay as they were):
+ *   B_dev (activations, fp16 or fp32; every entry point)       16 bytes  (every LUT build loads uint4 / float4; rows follow each other
+ *                                                                         K elements apart, K is a multiple of 64: they stay aligned)
+ *   C_dev, C_dev[i] (outputs)                 fp32: 16 bytes, fp16: 8    (the GEMMs store four outputs of a row at a time; Mw is a
+ *                                                                         multiple of 4, so every row of [N][Mw] stays aligned)
+ *   tmac_hip_xform: in2, residual, gamma, residual_out          16 bytes  (16-byte loads into LDS; residual_out: 16-byte stores)
+ *   A_ref_dev, scales_ref_dev, the tap buffer of tmac_hip_chain_set_tap, recv / send of the exchange step: their element type
+ *     (copied, or read and written element by element)
+ * The rule goes by the argument's ROLE and dtype, not by the route a call takes: an fp32 C_dev needs 16 bytes for N = 1 too (where the
+ * kernels of today store narrower; the dispatcher is free to pick another), and an output that a later call takes as its B_dev or in2
+ * must satisfy THEIR 16 bytes as well -- also inside a recording, where the value travels through the hand-off image: the same pointers
+ * must stay valid for launching the calls one by one.  An allocator that aligns every tensor to 16 bytes or more (hipMalloc: 256, ggml:
+ * 32, torch: 512) never meets a refusal.
+ * The tests hold the kernels to no more than this: a base that is 32-byte and not 64-byte aligned (ggml's tensor alignment) is served like a 256-byte one, bit for
+ * bit (tests/test_gpu_footprint.py).  Host pointers (layer 1, the read-back taps) are copied and need the alignment of their element
+ * type only.  Intended, and asserted by the same test file: no kernel writes anything outside [pointer, pointer + extent) of an output,
+ * or lets a value from outside an input's extent reach a result. */
+
 /* Upload + re-tile one weight matrix given in the REFERENCE layout (python/t_mac/weights.py:57-87):
  *   A_ref      uint8 [M/bm][K/4][bm/2]           (M = Mw*bits bit-plane rows)
  *   scales_ref float_type: zero_point [M/bm][K/gs][bm/bits/8][2][8]; else [M/bm][K/gs][bm/bits/8][8];
@@ -120,12 +140,12 @@ int32_t tmac_hip_workspace_create(tmac_hip_workspace** out, int maxK, int maxN);
 int32_t tmac_hip_workspace_free(tmac_hip_workspace* ws);
 
 /* preprocessor (lut_ctor.cc:38-266 + generated glue): activations B_dev [N][K] (act_dtype) ->
- * ws {QLUT int8, lut_scales, lut_biases}.  Bit-exact with the reference's fp32 arithmetic. */
+ * ws {QLUT int8, lut_scales, lut_biases}.  Bit-exact with the reference's fp32 arithmetic.  B_dev: 16-byte aligned. */
 int32_t tmac_hip_preprocessor_dev(tmac_hip_workspace* ws, const void* B_dev, tmac_dtype_t act_dtype,
                                   int K, int N, int act_group_size, void* stream);
 
 /* qgemm_lut (tbl.cc + glue): C_dev [N][Mw] (out_dtype) = W x LUT(ws).  ws must hold the LUT of the
- * same K and act_group_size.  Whole matrix in one launch. */
+ * same K and act_group_size.  Whole matrix in one launch.  C_dev: 16-byte aligned (fp32), 8-byte (fp16). */
 int32_t tmac_hip_qgemm_dev(const tmac_hip_weights* w, const tmac_hip_workspace* ws, void* C_dev,
                            tmac_dtype_t out_dtype, int N, void* stream);
 
@@ -134,6 +154,7 @@ int32_t tmac_hip_qgemm_dev(const tmac_hip_weights* w, const tmac_hip_workspace* 
  * kernel (bit-exact with tmac_hip_preprocessor_dev) and every matrix is covered by one launch.
  *   weights[i] : registered matrices sharing K, bits and quantisation config
  *   B_dev      : activations [N][K] (act_dtype);   C_dev[i] : [N][Mw_i] (out_dtype)
+ *   B_dev 16-byte aligned, every C_dev[i] 16-byte (fp32) or 8-byte (fp16) aligned ("Alignment" above)
  * With N at or above the GEMM threshold (tmac_hip_set_gemm_min_n) the call runs the preprocessor once into a
  * library-owned, per-stream workspace and the one-hot MFMA GEMM per matrix; the workspace is allocated on first use
  * (call once outside any stream capture) and released by tmac_hip_cache_clear(). */
@@ -228,7 +249,9 @@ int32_t tmac_hip_chain_free(tmac_hip_chain* chain);
  * NO PER-CALL FALLBACK: "-1 from tmac_hip_chain_end, keep launching the calls one by one" holds for recordings WITHOUT transforms only --
  * a transform has no stand-alone counterpart in this library.  A caller that records transforms must be able to run the operators itself
  * (ggml does: the segment glue is an optimisation of a graph that already has norm / glu nodes) when tmac_hip_chain_end refuses the
- * recording (LDS beyond 160 KB, K beyond the limits above).  A transform declared in front of a call that is rejected is dropped with it. */
+ * recording (LDS beyond 160 KB, K beyond the limits above).  A transform declared in front of a call that is rejected is dropped with it.
+ * in2, residual (unless TMAC_XF_CARRY), gamma and residual_out are 16-byte aligned; a transform naming a vector that is not is refused with
+ * TMAC_HIP_E_ARG and declares nothing. */
 #define TMAC_XF_NONE 0
 #define TMAC_XF_NORM 1
 #define TMAC_XF_GLU 2

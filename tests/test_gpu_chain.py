@@ -44,10 +44,14 @@ class Model:
     mg = -1: per-group scales (+ zero points), act groups of 64 (tbl.cc:323-532); mg >= 1: unified scale(s), one act group
     per row, int32 totals + scale-final (BitNet: tbl.cc:536-630, qgemm.py:170-174).
     weights_fn(i, m, Mw, K, bits) -> uint8 [Mw][K] weight levels of op i's matrix m, or None for the random ones; x_fn(i, K) -> float32 [K]
-    external activations of op i, or None for the standard-normal ones (tests/test_gpu_saturating.py)."""
+    external activations of op i, or None for the standard-normal ones (tests/test_gpu_saturating.py).
+    out_alloc(i, m, Mw, torch dtype) -> the device tensor of op i's output m, ext_alloc(i, float32 numpy [K], torch dtype) -> the device
+    tensor holding op i's external activations in that dtype; by default ordinary torch tensors.  allocate() makes the outputs and
+    external vectors anew, with these or with other hooks (tests/test_gpu_footprint.py carves them out of a guarded arena and runs the
+    same matrices at several placements)."""
 
     def __init__(self, tm, ops, bits=2, zp=True, dev_f16=True, seed=0, out_f16=True, mg=-1, ternary=False, ext_f32=False,
-                 weights_fn=None, x_fn=None):
+                 weights_fn=None, x_fn=None, out_alloc=None, ext_alloc=None):
         import torch
         self.tm, self.ops, self.bits, self.zp, self.mg = tm, ops, bits, zp and mg < 1, mg
         self.ext_f32 = ext_f32                   # vectors in memory are fp32 (a caller with an fp32 graph); handed-over ones stay fp16
@@ -55,9 +59,9 @@ class Model:
         bm = BITS_BM[bits]
         self.wr = tm.TMACGeMMWrapper(act_group_size=AGS)
         rng = np.random.default_rng(seed)
-        self.host, self.ws, self.outs, self.x_ext = [], [], [], {}
+        self.host, self.ws, self.x_host, self.out_f16 = [], [], {}, out_f16
         for i, (K, rows, src) in enumerate(ops):
-            hs, ws, os_ = [], [], []
+            hs, ws = [], []
             for m, Mw in enumerate(rows):
                 ags = K if mg >= 1 else AGS
                 case = orc.make_case(1000 * seed + 10 * i + m, Mw, K, bits=bits, gs=GS, ags=ags, zero_point=zp, m_groups=mg, fp16_values=True)
@@ -87,16 +91,24 @@ class Model:
                 cfg = tm.KCfg.make(Mw, K, bits, bm, KF, GS, ags, zp, mg)
                 ws.append(self.wr.register_weights(A, S, Mw, K, bits, cfg, scales_dtype=tm.F32, dev_dtype=tm.F16 if dev_f16 else tm.F32))
                 hs.append((A, S))
-                os_.append(torch.zeros(Mw, dtype=torch.float16 if out_f16 else torch.float32, device="cuda"))
-            self.host.append(hs); self.ws.append(ws); self.outs.append(os_)
+            self.host.append(hs); self.ws.append(ws)
             if src is None:
                 x = rng.standard_normal(K).astype(np.float32)
                 x_given = x_fn(i, K) if x_fn is not None else None
                 if x_given is not None:
                     x = np.ascontiguousarray(x_given, np.float32)
-                self.x_ext[i] = torch.from_numpy(x).cuda()
-                if not ext_f32:
-                    self.x_ext[i] = self.x_ext[i].half()
+                self.x_host[i] = x
+        self.allocate(out_alloc, ext_alloc)
+
+    def allocate(self, out_alloc=None, ext_alloc=None):
+        import torch
+        odt = torch.float16 if self.out_f16 else torch.float32
+        xdt = torch.float32 if self.ext_f32 else torch.float16
+        self.outs, self.x_ext = [], {}
+        for i, (K, rows, src) in enumerate(self.ops):
+            self.outs.append([torch.zeros(Mw, dtype=odt, device="cuda") if out_alloc is None else out_alloc(i, m, Mw, odt) for m, Mw in enumerate(rows)])
+            if src is None:
+                self.x_ext[i] = torch.from_numpy(self.x_host[i]).cuda().to(xdt) if ext_alloc is None else ext_alloc(i, self.x_host[i], xdt)
 
     def x_of(self, i):
         src = self.ops[i][2]

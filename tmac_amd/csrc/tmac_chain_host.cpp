@@ -42,6 +42,11 @@ extern "C" int32_t tmac_hip_chain_xform(const tmac_hip_xform* xf) {
     if (!xf) return fail(TMAC_HIP_E_ARG, "null transform");
     if (xf->kind < 0 || xf->kind > 2) return fail(TMAC_HIP_E_ARG, "unknown transform kind %d", xf->kind);
     if (xf->kind == TMAC_XF_GLU && !xf->in2) return fail(TMAC_HIP_E_ARG, "GLU needs a second vector");
+    // (residual == (void*)1 is the CARRY tag, not an address)
+    const struct { const void* p; const char* name; } vec[] = {{xf->in2, "in2"}, {xf->residual == (const void*)1 ? nullptr : xf->residual, "residual"},
+                                                              {xf->gamma, "gamma"}, {xf->residual_out, "residual_out"}};
+    for (const auto& v : vec)
+        if (misaligned(v.p, XFORM_ALIGN)) return fail(TMAC_HIP_E_ARG, "transform vector %s must be %zu-byte aligned (read or written 16 bytes at a time)", v.name, XFORM_ALIGN);
     g_chain_xf = *xf;
     return TMAC_HIP_OK;
 }

@@ -213,6 +213,7 @@ int32_t tmac_host::qgemm_impl(const tmac_hip_weights* w, const tmac_hip_workspac
     const int32_t brc = defer_barrier();       // behind the calling thread's deferred queue (the LUT may come from a queued output; C_dev may be one)
     if (brc) return brc;
     if (!w || !ws || !C_dev) return fail(TMAC_HIP_E_ARG, "null argument");
+    if (misaligned(C_dev, out_align(out_dtype))) return fail(TMAC_HIP_E_ARG, "C_dev must be %zu-byte aligned (four outputs are stored at a time)", out_align(out_dtype));
     if (ws->K != w->s.K || ws->ags != w->s.ags)
         return fail(TMAC_HIP_E_ARG, "workspace LUT (K=%d, ags=%d) does not match the weights (K=%d, ags=%d)", ws->K, ws->ags, w->s.K, w->s.ags);
     if (N <= 0 || N > ws->N) return fail(TMAC_HIP_E_ARG, "N=%d but the workspace LUT holds %d rows", N, ws->N);
@@ -424,6 +425,15 @@ int32_t tmac_host::fused_impl(const tmac_hip_weights* const* wl, int nmat, const
     if (!wl || !C_list || !B_dev || nmat < 1 || nmat > 4 || N < 1) {
         if (chain_recording()) chain_clear_xform();      // a rejected call must not leave its transform pending for the next recorded call
         return fail(TMAC_HIP_E_ARG, "bad fused arguments (1..4 matrices)");
+    }
+    // the alignment contract, ahead of the recorder, the deferred queue and the planner alike: a refused call is neither recorded nor
+    // queued, launches nothing and leaves the queue as it is
+    int bad_c = -1;
+    for (int i = 0; i < nmat && bad_c < 0; ++i) if (misaligned(C_list[i], out_align(out_dtype))) bad_c = i;
+    if (misaligned(B_dev, ACT_ALIGN) || bad_c >= 0) {
+        if (chain_recording()) chain_clear_xform();
+        if (bad_c < 0) return fail(TMAC_HIP_E_ARG, "B_dev must be %zu-byte aligned (the LUT build reads 16 bytes at a time)", ACT_ALIGN);
+        return fail(TMAC_HIP_E_ARG, "C_dev[%d] must be %zu-byte aligned (four outputs are stored at a time)", bad_c, out_align(out_dtype));
     }
     const bool tap = dump || lut_tap;
     if (chain_recording() && !tap) return chain_record(wl, nmat, B_dev, act_dtype, C_list, out_dtype, N);

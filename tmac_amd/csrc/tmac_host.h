@@ -157,6 +157,12 @@ int32_t fused_impl(const tmac_hip_weights* const* wl, int nmat, const void* B_de
 // Pure: reads its arguments and g_knobs.
 int32_t fused_check(const tmac_hip_weights* const* wl, int nmat, void* const* C_list, int N);
 void release_fused_workspaces();   // caller holds g_mu
+// Alignment of caller-owned device pointers (include/tmac_hip.h, "Alignment"): every LUT build reads the activations 16 bytes at a time
+// (uint4 / float4), the GEMMs store four outputs at a time (fp32: 16 bytes, fp16: 8), the chain reads its transform vectors and writes
+// residual_out 16 bytes at a time.  A pointer below that is refused before anything is planned, queued or recorded.
+constexpr size_t ACT_ALIGN = 16, XFORM_ALIGN = 16;
+inline size_t out_align(tmac_dtype_t d) { return d == TMAC_F16 ? 8 : 16; }
+inline bool misaligned(const void* p, size_t a) { return (reinterpret_cast<uintptr_t>(p) & (a - 1)) != 0; }
 
 // ---- tuner (tmac_tuner.cpp) -----------------------------------------------------------------------
 void tuned_config(const FusedArgs& fa, int total_q, int& ft, int& wpq);   // leaves ft / wpq alone when nothing is recorded

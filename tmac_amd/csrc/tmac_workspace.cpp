@@ -66,6 +66,7 @@ extern "C" int32_t tmac_hip_preprocessor_dev(tmac_hip_workspace* ws, const void*
     rc = check_lut_shape(ws, K, N, act_group_size);
     if (rc) return rc;
     if (!B_dev) return fail(TMAC_HIP_E_ARG, "null activations");
+    if (misaligned(B_dev, ACT_ALIGN)) return fail(TMAC_HIP_E_ARG, "B_dev must be %zu-byte aligned (the LUT build reads 16 bytes at a time)", ACT_ALIGN);
     ws->K = K; ws->N = N; ws->ags = act_group_size; ws->qdev_u4_per_row = qdev_u4_for_K(K);
     // k_gemm_planes' LUT image is built when tmac_hip_qgemm_dev may pick that kernel: not for one row, and not below the GEMM threshold
     // (PLANES_MIN_N by default: the matrix, and with it the measured crossover plan_split applies, is not known here)
