@@ -157,7 +157,8 @@ int32_t tmac_hip_qgemm_dev(const tmac_hip_weights* w, const tmac_hip_workspace* 
  *   B_dev 16-byte aligned, every C_dev[i] 16-byte (fp32) or 8-byte (fp16) aligned ("Alignment" above)
  * With N at or above the GEMM threshold (tmac_hip_set_gemm_min_n) the call runs the preprocessor once into a
  * library-owned, per-stream workspace and the one-hot MFMA GEMM per matrix; the workspace is allocated on first use
- * (call once outside any stream capture) and released by tmac_hip_cache_clear(). */
+ * (call once outside any stream capture) and released by tmac_hip_cache_clear().  The same workspace, under the same rule, is used
+ * from N = 2 on where the rows kernel (k_gemv_rows, tmac_hip_debug_rows_kernel) serves the call. */
 int32_t tmac_hip_qgemm_fused_dev(const tmac_hip_weights* const* weights, int nmat, const void* B_dev,
                                  tmac_dtype_t act_dtype, void* const* C_dev, tmac_dtype_t out_dtype, int N,
                                  void* stream);
@@ -434,6 +435,26 @@ int32_t tmac_hip_debug_gemm_stamps(unsigned long long* dev_buffer);
 int32_t tmac_hip_debug_gemm_comb_sums(const tmac_hip_weights* w, const tmac_hip_workspace* ws, int32_t* comb_host, int N, void* stream);
 int32_t tmac_hip_debug_gemm_image_read(const tmac_hip_workspace* ws, int8_t* half_tables_host, float* lut_scales_host,
                                        float* lut_biases_host, float* entry_sums_host, int N, void* stream);
+/* k_gemv_rows (tmac_rows.hip): N >= 2 activation rows below the GEMM crossover on QUAD-layout weights, 2 / 4 / 8 rows per pass over the
+ * weights, the tables copied from the workspace's half-table image.  Taps (tmac_hip_qgemm_partial_sums, tmac_hip_qgemm_fused_partial_sums)
+ * never run it.
+ * tmac_hip_debug_rows_kernel: 0 (default) auto -- the kernel where it was measured faster than the routing without it (tmac_dispatch.cpp,
+ *   rows_auto); 1 off -- that routing bit for bit; 2 forced -- every N >= 2 call the kernel covers takes it, whatever the GEMM thresholds
+ *   say (tests, A/B).  tmac_hip_reset_state puts it back to 0.
+ * tmac_hip_debug_rows_stats: k_gemv_rows launches since the library was loaded or reset (a host counter; a call makes one launch for its
+ *   full row groups and one more when the last group has another capacity).
+ * tmac_hip_debug_rows_plan: the row groups of an N-row call, a pure function (no device is touched).  r_fit: the largest of 8 / 4 / 2
+ *   rows whose tables and LUT scales plus the kernel's fixed part fit 163840 bytes of LDS (lds_bytes: that footprint); ngroups =
+ *   ceil(N / r_fit); cap[g] / live[g] (each NULL or at least ngroups entries): every group but the last holds r_fit rows, the last the
+ *   remainder in the smallest capacity of 2 / 4 / 8 that takes it.  m_groups: -1 per-group scales, >= 1 unified (same footprint).
+ *   TMAC_HIP_E_ARG when not even two rows fit.  Launches and the tap below group by this function alone.
+ * tmac_hip_debug_rows_comb_sums: the integers k_gemv_rows feeds into its float part, for the LUT the workspace holds (N <= its rows), in
+ *   the row grouping of an untapped call of that N: per-group scales int32 [N][Mw][K/64] = sum_p 2^p PS_p; unified scales
+ *   int32 [N][Mw][bits], the exact per-plane totals. */
+int32_t tmac_hip_debug_rows_kernel(int mode);
+int32_t tmac_hip_debug_rows_stats(uint64_t* launches);
+int32_t tmac_hip_debug_rows_plan(int K, int m_groups, int N, int32_t* r_fit, int32_t* ngroups, int32_t* cap, int32_t* live, size_t* lds_bytes);
+int32_t tmac_hip_debug_rows_comb_sums(const tmac_hip_weights* w, const tmac_hip_workspace* ws, int32_t* comb_host, int N, void* stream);
 /* host-pointer entry points: 1 (default) = tiles with contiguous weight / scale pointers are grouped into runs once they
  * have been seen, and a run's output is computed in one launch per LUT and handed out tile by tile; 0 = every tile call is
  * served on its own */

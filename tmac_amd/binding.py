@@ -97,6 +97,10 @@ def load_library() -> C.CDLL:
         "tmac_hip_debug_gemm_kernel": ([C.c_int], i32),
         "tmac_hip_debug_gemm_stamps": ([vp], i32),
         "tmac_hip_debug_gemm_comb_sums": ([vp, vp, vp, C.c_int, vp], i32),
+        "tmac_hip_debug_rows_kernel": ([C.c_int], i32),
+        "tmac_hip_debug_rows_stats": ([C.POINTER(C.c_uint64)], i32),
+        "tmac_hip_debug_rows_plan": ([C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_size_t)], i32),
+        "tmac_hip_debug_rows_comb_sums": ([vp, vp, vp, C.c_int, vp], i32),
         "tmac_hip_debug_gemm_image_read": ([vp, vp, vp, vp, vp, C.c_int, vp], i32),
         "tmac_hip_set_variant": ([C.c_int], i32),
         "tmac_hip_set_gemm_min_n": ([C.c_int], i32),
@@ -146,7 +150,8 @@ def load_library() -> C.CDLL:
         "preprocessor_int8": ([C.c_int] * 4 + [vp] * 4, i32),
     }
     # $TMAC_HIP_LIB may name an OLDER build for an A/B run (tools/gpu): entry points it lacks stay unbound (calling one raises)
-    optional = {"tmac_hip_chain_is_stream", "tmac_hip_chain_xform", "tmac_hip_comm_init_ipc", "tmac_hip_comm_export", "tmac_hip_comm_connect", "tmac_hip_comm_status"} if os.environ.get("TMAC_HIP_LIB") else set()
+    optional = {"tmac_hip_chain_is_stream", "tmac_hip_chain_xform", "tmac_hip_comm_init_ipc", "tmac_hip_comm_export", "tmac_hip_comm_connect", "tmac_hip_comm_status",
+                "tmac_hip_debug_rows_kernel", "tmac_hip_debug_rows_stats", "tmac_hip_debug_rows_plan", "tmac_hip_debug_rows_comb_sums"} if os.environ.get("TMAC_HIP_LIB") else set()
     for name, (argt, rest) in sigs.items():
         try:
             fn = getattr(L, name)

@@ -10,6 +10,7 @@ enum Route {
     R_GEMM_PLANES,   // k_gemm_planes / k_gemm_planes_us on the workspace's LUT image
     R_GEMM_ONEHOT,   // k_gemm_onehot on the half-table image
     R_GEMV_QUAD,     // k_gemv_quad (QUAD layout)
+    R_GEMV_ROWS,     // k_gemv_rows (QUAD layout): 2-8 activation rows per weight pass, tables copied from the half-table image
     R_GEMV_FUSED,    // k_gemv_fused (row-block layout)
     R_GEMV_LO,       // k_gemv_lo (two-kernel path; v_mqsad or SDWA accumulate by the variant knob)
     R_REF_LAYOUT,    // k_gemv_ref_layout on the reference blobs
@@ -66,6 +67,25 @@ static bool gemm_pays(const Shape& s, long total_Mw, int N) { return planes_cove
 static bool planes_ok(const tmac_hip_weights* w) {
     return planes_covers(w->s) && w->tiled_ok && !w->fa && w->w_bytes < ((size_t)1 << 31);
 }
+// Where auto mode hands an N >= 2 call below the GEMM crossover to k_gemv_rows instead of the row loop (k_gemv_quad, grid.y = N).
+// The rule: only where the rows kernel's column of profiles/r09_small_n.txt beats the DEFAULT column of profiles/r09_small_n_parent.txt
+// (the parent commit, same GPU session) by more than 5 %, the margin planes_crossover gives the incumbent.  Measured (llama-2-7B shapes,
+// W2 and W4, N = 2 ... 16): no shape class and N clears it -- rows / parent default is 2.1 on o and qkv, 1.4-1.5 on gate/up, 1.02-1.27 on
+// down -- so auto is the routing without the kernel everywhere and planes_crossover keeps its fit against the row loop, the cheaper of the
+// two at every measured point.  Rows-kernel cost shape (W2 fit, not a bar): us ~ 5 + groups x (0.155 per MB of weights + live rows x
+// (1.3 + 0.16 per MB)); the per-row term is what the next round has to cut.
+static bool rows_auto(const Shape& s, long total_Mw, int N) {
+    (void)s; (void)total_Mw; (void)N;
+    return false;
+}
+// k_gemv_rows: can it serve these weights at all | does auto mode want it (tmac_hip_debug_rows_kernel: 1 never, 2 always)
+static bool rows_covers(const tmac_hip_weights* w) {
+    return (g_knobs.variant == V_AUTO || g_knobs.variant == V_QUAD) && layout_of(w->s) == L_QUAD && w->tiled_ok && !w->fa && gemv_rows_supported(w->s);
+}
+static bool rows_pays(const Shape& s, long total_Mw, int N) {
+    if (g_knobs.rows_kernel != 0) return g_knobs.rows_kernel == 2;
+    return rows_auto(s, total_Mw, N);
+}
 static bool planes_image_fits(const tmac_hip_workspace* ws, int K) { return ws->gimg && (size_t)2 * K * ws->gNpad < ((size_t)1 << 31); }
 
 // ---- the two planners ------------------------------------------------------------------------------------------------------
@@ -93,6 +113,16 @@ static bool planes_image_fits(const tmac_hip_workspace* ws, int K) { return ws->
 //  * image_fits: the LUT image of the stream's workspace, which has the row stride of the largest N the stream has seen, stays below
 //    2 GB.  fused_impl plans before the workspace exists and assumes it does; fused_prefill plans again where it does not.
 //  * N = 1, a tap, or a GEMM that does not pay: one fused GEMV launch; the matrices must share layout, K and quantisation config.
+//  * k_gemv_rows (R_GEMV_ROWS; tmac_hip_debug_rows_kernel: 0 auto, 1 off = everything above bit for bit, 2 forced).  It stands where
+//    k_gemv_quad would be launched with grid.y = N: N >= 2, no tap, neither GEMM chosen, QUAD-layout weights it covers (rows_covers: what
+//    gemv_quad_supported accepts, variant 0 or 6, no fast aggregation), and rows_pays says so (auto: rows_auto, the measured rule; forced:
+//    always).  Forced mode is asked BEFORE the GEMM thresholds: every N >= 2 call the kernel covers takes it.
+//    Split entry points: the workspace always holds the half-table image (tmac_hip_preprocessor_dev and tmac_hip_workspace_write fill
+//    qlut_lds), so the route needs nothing else.  Fused entry point: all matrices in the QUAD layout with same_lut and same_quant
+//    (rows_fused_ok) -> planned(R_GEMV_ROWS, LB_HALF_TABLES): the pair build into the stream's library workspace (fused_prefill), then ONE
+//    k_gemv_rows call over all matrices.  Unified-scale matrices with K > PAIRS_ROW_MAX_K keep the route above (the row-wise pair build
+//    does not reach them).  Taps (tmac_hip_qgemm_partial_sums, tmac_hip_qgemm_fused_partial_sums) never take it; its own tap is
+//    tmac_hip_debug_rows_comb_sums.  Recording and deferral sit in front of the planner (fused_impl) and do not know the route.
 static Plan plan_split(const tmac_hip_weights* w, const tmac_hip_workspace* ws, int N, bool tap) {
     Route r = R_REF_LAYOUT;
     if (g_knobs.variant != V_REF_LAYOUT && w->tiled_ok)
@@ -101,13 +131,29 @@ static Plan plan_split(const tmac_hip_weights* w, const tmac_hip_workspace* ws, 
     if (r == R_REF_LAYOUT && !w->A_ref)
         return refused(TMAC_HIP_E_NOMATCH, "reference-layout blobs were not kept for these weights (register them with variant 3 selected)");
     if (r != R_GEMV_QUAD && r != R_GEMV_FUSED) return planned(r);
+    const bool rows = r == R_GEMV_QUAD && N >= 2 && !tap && g_knobs.rows_kernel != 1 && rows_covers(w);
+    if (rows && g_knobs.rows_kernel == 2) return planned(R_GEMV_ROWS);
     if (!tap && ws->gimg_valid && ws->gimg_kind == gimg_kind_for(w->s) && planes_ok(w) && planes_image_fits(ws, w->s.K) && planes_pays(w->s, w->s.Mw, N))
         return planned(R_GEMM_PLANES);
     if (onehot_pays(w->s, w->s.Mw, N) && gemm_onehot_supported(w->s)) return planned(R_GEMM_ONEHOT);
+    if (rows && rows_pays(w->s, w->s.Mw, N)) return planned(R_GEMV_ROWS);
     return planned(r);
 }
 
+// every matrix in the QUAD layout, one LUT, one kernel instantiation, and a pair build that covers the LUT
+static bool rows_fused_ok(const tmac_hip_weights* const* wl, void* const* C_list, int nmat) {
+    long rows = 0;
+    for (int i = 0; i < nmat; ++i) {
+        const tmac_hip_weights* w = wl[i];
+        if (!w || !C_list[i] || !rows_covers(w) || !same_lut(w, wl[0]) || !same_quant(w, wl[0])) return false;
+        rows += w->s.Mw;
+    }
+    const Shape& s0 = wl[0]->s;
+    return rows > 0 && !(s0.m_groups >= 1 && s0.K > PAIRS_ROW_MAX_K);
+}
 static Plan plan_fused(const tmac_hip_weights* const* wl, void* const* C_list, int nmat, int N, bool tap, bool image_fits = true) {
+    const bool rows = N >= 2 && !tap && g_knobs.rows_kernel != 1 && rows_fused_ok(wl, C_list, nmat);
+    if (rows && g_knobs.rows_kernel == 2) return planned(R_GEMV_ROWS, LB_HALF_TABLES);
     if (g_knobs.gemm_min_n > 0 && N >= 2 && !tap) {       // (gemm_pays applies the threshold: a set one, or the measured crossover)
         bool ok = true, quant = true, all_planes = true, all_onehot = true, all_quad = true;
         long rows = 0;
@@ -138,6 +184,11 @@ static Plan plan_fused(const tmac_hip_weights* const* wl, void* const* C_list, i
             return refused(TMAC_HIP_E_NOMATCH, "matrix %d is not registered in the fused layout", i);
         if (!same_lut(w, wl[0]) || !same_quant(w, wl[0]))
             return refused(TMAC_HIP_E_ARG, "matrices fused in one launch must share K, bits and quantisation config");
+    }
+    if (rows) {
+        long total = 0;
+        for (int i = 0; i < nmat; ++i) total += wl[i]->s.Mw;
+        if (rows_pays(wl[0]->s, total, N)) return planned(R_GEMV_ROWS, LB_HALF_TABLES);
     }
     return planned(layout_of(wl[0]->s) == L_QUAD ? R_GEMV_QUAD : R_GEMV_FUSED);
 }
@@ -206,6 +257,25 @@ static int32_t planes_multi(const tmac_hip_weights* const* wl, int nmat, const t
     return TMAC_HIP_OK;
 }
 
+// k_gemv_rows over up to 4 matrices that share K and the quantisation config; the workspace holds the half-table image of N rows
+static int32_t rows_multi(const tmac_hip_weights* const* wl, int nmat, const tmac_hip_workspace* ws, void* const* C_list,
+                          tmac_dtype_t out_dtype, int N, int32_t* tap, hipStream_t st) {
+    FusedArgs fa;
+    fill_fused_args(fa, wl, C_list, nmat, out_dtype, nullptr);
+    RowsArgs ra;
+    memset(&ra, 0, sizeof(ra));
+    for (int i = 0; i < nmat; ++i) ra.m[i] = fa.m[i];
+    ra.nmat = nmat; ra.s = fa.s; ra.sc_f16 = fa.sc_f16; ra.out_f16 = fa.out_f16;
+    ra.qlut_lds = ws->qlut_lds; ra.lut_scales = ws->lut_scales; ra.lut_biases = ws->lut_biases;
+    ra.tap = tap; ra.N = N;
+    int launches = 0;
+    const hipError_t e = launch_gemv_rows(ra, st, &launches);
+    g_knobs.rows_launches += (uint64_t)launches;
+    if (e == hipErrorInvalidValue) return fail(TMAC_HIP_E_NOMATCH, "rows kernel: configuration or sizes not covered (matrices must stay below 2 GB)");
+    if (e != hipSuccess) return fail(TMAC_HIP_E_RUNTIME, "rows kernel launch: %s", hipGetErrorString(e));
+    return TMAC_HIP_OK;
+}
+
 // ---- split entry point -----------------------------------------------------------------------------------------------------
 int32_t tmac_host::qgemm_impl(const tmac_hip_weights* w, const tmac_hip_workspace* ws, void* C_dev, tmac_dtype_t out_dtype,
                           int N, int32_t* dump, hipStream_t st) {
@@ -223,6 +293,7 @@ int32_t tmac_host::qgemm_impl(const tmac_hip_weights* w, const tmac_hip_workspac
     switch (p.route) {
     case R_GEMM_PLANES: return planes_multi(&w, 1, ws, cl, out_dtype, N, nullptr, st);
     case R_GEMM_ONEHOT: return gemm_multi(&w, 1, ws, cl, out_dtype, N, dump, st);
+    case R_GEMV_ROWS: return rows_multi(&w, 1, ws, cl, out_dtype, N, nullptr, st);
     case R_GEMV_QUAD:
     case R_GEMV_FUSED: {
         FusedArgs fa;
@@ -322,6 +393,53 @@ extern "C" int32_t tmac_hip_debug_gemm_comb_sums(const tmac_hip_weights* w, cons
                    [&](int32_t* tap) { return planes_multi(&w, 1, ws, cl, TMAC_F32, N, tap, st); });
 }
 
+// ---- k_gemv_rows: knob, counter, the row-group rule, parity tap ------------------------------------------------------------
+extern "C" int32_t tmac_hip_debug_rows_kernel(int mode) {
+    if (mode < 0 || mode > 2) return fail(TMAC_HIP_E_ARG, "rows kernel mode must be 0 (auto), 1 (off) or 2 (forced)");
+    g_knobs.rows_kernel = mode;
+    return TMAC_HIP_OK;
+}
+
+extern "C" int32_t tmac_hip_debug_rows_stats(uint64_t* launches) {
+    if (!launches) return fail(TMAC_HIP_E_ARG, "null argument");
+    *launches = g_knobs.rows_launches;
+    return TMAC_HIP_OK;
+}
+
+extern "C" int32_t tmac_hip_debug_rows_plan(int K, int m_groups, int N, int32_t* r_fit, int32_t* ngroups, int32_t* cap, int32_t* live,
+                                            size_t* lds_bytes) {
+    RowsPlan p;
+    if (m_groups == 0 || m_groups < -1) return fail(TMAC_HIP_E_ARG, "m_groups must be -1 (per-group scales) or >= 1 (unified scales)");
+    if (!rows_plan(K, N, p)) return fail(TMAC_HIP_E_ARG, "no row groups for K=%d, N=%d (K a multiple of 64 whose tables of two rows fit %zu bytes of LDS)", K, N, ROWS_LDS_MAX);
+    if (r_fit) *r_fit = p.r_fit;
+    if (ngroups) *ngroups = p.ngroups;
+    if (lds_bytes) *lds_bytes = p.lds_bytes;
+    for (int g = 0; g < p.ngroups; ++g) {
+        const bool last = g == p.ngroups - 1;
+        if (cap) cap[g] = last ? p.cap_last : p.r_fit;
+        if (live) live[g] = last ? p.live_last : p.r_fit;
+    }
+    return TMAC_HIP_OK;
+}
+
+// Parity tap of k_gemv_rows: the integers as they enter the float part, in the row grouping of an untapped call of that N.
+extern "C" int32_t tmac_hip_debug_rows_comb_sums(const tmac_hip_weights* w, const tmac_hip_workspace* ws_c, int32_t* comb_host,
+                                                 int N, void* stream) {
+    const int32_t brc = defer_barrier();
+    if (brc) return brc;
+    if (!w || !ws_c || !comb_host) return fail(TMAC_HIP_E_ARG, "null argument");
+    auto* ws = const_cast<tmac_hip_workspace*>(ws_c);
+    hipStream_t st = (hipStream_t)stream;
+    if (ws->K != w->s.K || ws->ags != w->s.ags || N <= 0 || N > ws->N) return fail(TMAC_HIP_E_ARG, "the workspace holds no LUT for K=%d, N=%d", w->s.K, N);
+    if (!rows_covers(w)) return fail(TMAC_HIP_E_NOMATCH, "k_gemv_rows does not cover this configuration");
+    const size_t elems = (size_t)N * w->s.Mw * (w->s.m_groups >= 1 ? (size_t)w->s.bits : (size_t)w->s.K / 64);
+    DevBuf Ctmp;
+    HIP_TRY(Ctmp.alloc(sizeof(float) * (size_t)N * w->s.Mw));
+    void* cl[1] = {Ctmp.p};
+    return run_tap(ws->dump, ws->dump_elems, elems, comb_host, st, "rows comb-sum",
+                   [&](int32_t* tap) { return rows_multi(&w, 1, ws, cl, TMAC_F32, N, tap, st); });
+}
+
 // The LUT image of the workspace in plain layouts: half tables int8 [N][K/4][8], then lut_scales, lut_biases and the
 // per-act-group entry sums, fp32 [N][K/64] each.
 extern "C" int32_t tmac_hip_debug_gemm_image_read(const tmac_hip_workspace* ws, int8_t* half_tables_host, float* lut_scales_host,
@@ -416,6 +534,7 @@ static int32_t fused_prefill(Plan p, const tmac_hip_weights* const* wl, int nmat
     }
     if (p.route == R_GEMM_PLANES) return planes_multi(wl, nmat, ws, C_list, out_dtype, N, nullptr, st);
     if (p.route == R_GEMM_ONEHOT) return gemm_multi(wl, nmat, ws, C_list, out_dtype, N, nullptr, st);
+    if (p.route == R_GEMV_ROWS) return rows_multi(wl, nmat, ws, C_list, out_dtype, N, nullptr, st);
     for (int i = 0; i < nmat && rc == TMAC_HIP_OK; ++i) rc = tmac_hip_qgemm_dev(wl[i], ws, C_list[i], out_dtype, N, st);
     return rc;
 }

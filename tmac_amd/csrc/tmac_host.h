@@ -104,6 +104,8 @@ struct Knobs {
     int chain_wpq = 0;             // waves per row quad for every op of chains built from now on (0 = per-op choice)
     unsigned chain_spin_limit = 1u << 18;   // polls of one hand-off before a wave gives up (~0.4 s)
     int defer_fail = 0;            // test hook (tmac_hip_debug_defer_fail): the n-th launch attempted by the deferred queue's flushes fails on the host side; one-shot
+    int rows_kernel = 0;           // k_gemv_rows: 0 = where measured faster, 1 = never (the routing without it), 2 = wherever it covers the call (tmac_hip_debug_rows_kernel)
+    uint64_t rows_launches = 0;    // k_gemv_rows launches since load or reset (tmac_hip_debug_rows_stats): a counter, reset with the settings
     int chain_grid = 0;            // workgroups of chains built from now on (0 = one per CU; tests run two chains side by side on one device)
     unsigned long long* stamps = nullptr;        // phase stamps of the next fused launches (tmac_hip_debug_stamps)
     int32_t* stamp_dump = nullptr;               // scratch the stamp instantiation stores its tap into (allocated once, survives resets)

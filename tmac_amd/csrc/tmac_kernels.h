@@ -148,6 +148,31 @@ hipError_t launch_gemv_fused(const FusedArgs& a, int N, bool build_lut, hipStrea
 // quad kernel (tmac_quad.hip): a.m[i].nb_end = cumulative ROW QUAD counts; force_ft/force_wpq 0 = heuristic
 bool gemv_quad_supported(const Shape& s);
 hipError_t launch_gemv_quad(const FusedArgs& a, int N, bool build_lut, int force_ft, int force_wpq, hipStream_t st);
+// rows kernel (tmac_rows.hip): 2-8 activation rows per weight pass on QUAD-layout weights, tables copied from the half-table image
+struct RowsArgs {
+    FusedMat m[4];           // nb_end = cumulative ROW QUAD counts (fill_fused_args)
+    int nmat;
+    Shape s;                 // K, bits, gs, ags, zero_point, m_groups (Mw unused)
+    const void* qlut_lds;    // uint4 [N][qlut_lds_u4(K)]: the half-table image of the pair builds / k_preprocess
+    const float* lut_scales; // fp32 [N][K/ags]
+    const float* lut_biases;
+    int sc_f16, out_f16;
+    int32_t* tap;            // optional (nmat == 1): int32 [N][Mw][K/64] = sum_p 2^p PS_p | unified scales: [N][Mw][bits] plane totals
+    int N;
+    // filled by the launcher
+    int nu, nst, tstride, G, nsg, gs_shift;   // tstride: of the IMAGE (the LDS copy uses nst * 64 + 1)
+    int wpq;                 // waves per row quad (1, 2, 4): fixed by the shape alone
+    int n_base, rows_per_group;   // rows of workgroup row y: n_base + y * rows_per_group ..., min(R, N - first) of them live
+};
+// The row groups of N rows (pure): r_fit = largest of 8 / 4 / 2 whose LDS footprint fits 160 KiB (0: none); every group but the last
+// holds r_fit rows (capacity r_fit), the last the remainder in the smallest capacity of 2 / 4 / 8 that takes it.
+struct RowsPlan { int r_fit, ngroups, cap_last, live_last; size_t lds_bytes; };   // lds_bytes: of a capacity-r_fit workgroup
+constexpr size_t ROWS_LDS_MAX = 163840;
+size_t rows_lds_bytes(int K, int R);
+bool rows_plan(int K, int N, RowsPlan& p);       // false: K % 64, N < 1, or not even two rows fit
+bool gemv_rows_supported(const Shape& s);
+// *launches (optional) grows by the number of k_gemv_rows launches made (one for the full groups, one for a last group of another capacity)
+hipError_t launch_gemv_rows(const RowsArgs& a, hipStream_t st, int* launches);
 // returns hipErrorInvalidValue when the variant does not cover the configuration
 hipError_t launch_gemv(const GemvArgs& a, Variant v, hipStream_t st);
 bool gemv_lo_supported(const Shape& s);

@@ -487,6 +487,13 @@ class TMACGeMMWrapper:
         check(B.lib().tmac_hip_debug_gemm_comb_sums(weights.handle, self.workspace.handle, out.ctypes.data, N, _stream(stream)))
         return out
 
+    def rows_comb_sums(self, weights: Weights, N: int, stream=None) -> np.ndarray:
+        """Parity tap of the rows kernel (k_gemv_rows): int32 [N][Mw][K/64], sum_p 2^p PS_p; unified scales: [N][Mw][bits] plane totals."""
+        G = weights.bits if weights.cfg.m_groups >= 1 else weights.K // 64
+        out = np.zeros((N, weights.Mw, G), np.int32)
+        check(B.lib().tmac_hip_debug_rows_comb_sums(weights.handle, self.workspace.handle, out.ctypes.data, N, _stream(stream)))
+        return out
+
     def partial_sums(self, weights: Weights, N: int = 1, stream=None) -> np.ndarray:
         """Parity tap: int32 [N][M][K/ags] (or [N][M] for the unified-scale path), M-space row order."""
         s_final = weights.cfg.m_groups >= 1 and weights.cfg.act_group_size == weights.K
