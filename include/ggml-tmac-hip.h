@@ -60,6 +60,16 @@ const char* ggml_tmac_hip_last_error(void);
  * would be refused is refused when it is issued, not at the flush; a flush launches every queued call and returns the first error; outputs
  * of a batch match in-order launches to the stream kernel's tolerance (tmac_hip.h). */
 int ggml_tmac_hip_mul_mat_dev(const struct tmac_ggml_tensor* const* w, int nw, const void* x_dev, int x_is_f32, void* const* dst_dev, int dst_is_f32);
+/* The same call with one element-wise operator applied to x inside the kernel, in front of its LUT build (tmac_hip.h:
+ * tmac_hip_qgemm_fused_xf_dev) -- same tensors, same stream rules:
+ *   kind 1 (norm)  t = x + residual (fp32 [K], or NULL: t = x);  x' = norm_weight ? rmsnorm(t, eps) * norm_weight : t;  residual_out (fp32 [K],
+ *                  optional) receives t.  residual_out must not overlap x, residual, norm_weight or an output: a residual stream alternates
+ *                  between two buffers
+ *   kind 2 (glu)   x' = silu(x) * in2;  in2 has x's dtype
+ * All weights of the call consume x'.  Such a call is never queued: with deferral on it flushes the queue, then launches. */
+int ggml_tmac_hip_mul_mat_dev_xf(const struct tmac_ggml_tensor* const* w, int nw, const void* x_dev, int x_is_f32, int kind /* 1 norm, 2 glu */,
+                                 const void* in2_dev, const float* residual, const float* norm_weight, float eps, float* residual_out,
+                                 void* const* dst_dev, int dst_is_f32);
 int ggml_tmac_hip_set_deferred(int on);
 int ggml_tmac_hip_flush(void);
 int ggml_tmac_hip_synchronize(void);
@@ -94,8 +104,11 @@ int ggml_tmac_hip_segment_mul_mat(const struct tmac_ggml_tensor* const* w, int n
 int ggml_tmac_hip_segment_mul_mat_f32(const struct tmac_ggml_tensor* const* w, int nw, const float* x_f32, void* const* dst_f16);
 int ggml_tmac_hip_segment_end(ggml_tmac_hip_segment** seg);
 /* A segment is all or nothing: when ggml_tmac_hip_segment_mul_mat or _end returns non-zero the recording is over (no chain exists, nothing
- * is pending) and the caller evaluates the graph's own nodes -- the element-wise operators of a segment have no stand-alone counterpart in
- * this library.  ggml_tmac_hip_segment_abort ends a recording explicitly (after a failed _norm / _glu, or a change of mind). */
+ * is pending).  The caller then issues the segment call by call: ggml_tmac_hip_mul_mat_dev for the plain mat-muls and
+ * ggml_tmac_hip_mul_mat_dev_xf (above) for those behind a _norm / _glu, with the residual stream in two alternating buffers (a kept t
+ * does not outlive a launch: what _norm(NULL, 1, ...) took from LDS is read from the buffer the earlier call wrote as residual_out) -- also
+ * when ggml_tmac_hip_segment_wait reports a failed hand-off -- or evaluates the graph's own nodes.
+ * ggml_tmac_hip_segment_abort ends a recording explicitly (after a failed _norm / _glu, or a change of mind). */
 int ggml_tmac_hip_segment_abort(void);
 int ggml_tmac_hip_segment_compute(ggml_tmac_hip_segment* seg);   /* one launch on ggml_tmac_hip_stream(); does not wait */
 int ggml_tmac_hip_segment_wait(ggml_tmac_hip_segment* seg);      /* synchronises the stream; 0 if every hand-off of the segment's launches completed */

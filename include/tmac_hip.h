@@ -247,10 +247,12 @@ int32_t tmac_hip_chain_free(tmac_hip_chain* chain);
  * A decoder then runs one launch per segment between two operators that stay outside (attention): o -> gate/up -> down -> next q/k/v.
  * These are extensions without a reference counterpart (T-MAC has no norm operator): tests compare them with the same formulas in
  * numpy fed through the oracle (tolerance, not bits: the mean square is summed in another order).
- * NO PER-CALL FALLBACK: "-1 from tmac_hip_chain_end, keep launching the calls one by one" holds for recordings WITHOUT transforms only --
- * a transform has no stand-alone counterpart in this library.  A caller that records transforms must be able to run the operators itself
- * (ggml does: the segment glue is an optimisation of a graph that already has norm / glu nodes) when tmac_hip_chain_end refuses the
- * recording (LDS beyond 160 KB, K beyond the limits above).  A transform declared in front of a call that is rejected is dropped with it.
+ * EVERY RECORDING HAS A CALL-BY-CALL EQUIVALENT: "-1 from tmac_hip_chain_end, keep launching the calls one by one" holds for recordings
+ * with transforms too -- a recorded call that carries one is tmac_hip_qgemm_fused_xf_dev (below) outside the recording.  That is what a
+ * caller issues when tmac_hip_chain_end refuses the recording (LDS beyond 160 KB, K beyond the limits above, ...) or tmac_hip_chain_status
+ * reports invalid outputs; two things do not carry over, because nothing outlives a stand-alone launch: a kept t (TMAC_XF_CARRY) is read
+ * from the memory an earlier call wrote as residual_out, and an in-place residual stream alternates between two buffers (see there).
+ * tmac_hip_chain_launch itself falls back to nothing.  A transform declared in front of a call that is rejected is dropped with it.
  * in2, residual (unless TMAC_XF_CARRY), gamma and residual_out are 16-byte aligned; a transform naming a vector that is not is refused with
  * TMAC_HIP_E_ARG and declares nothing. */
 #define TMAC_XF_NONE 0
@@ -267,6 +269,30 @@ typedef struct {
     int32_t keep;
 } tmac_hip_xform;
 int32_t tmac_hip_chain_xform(const tmac_hip_xform* xf);
+/* The stand-alone form: tmac_hip_qgemm_fused_dev(..., N = 1, ...) with the transform `xf` applied to its activations (B_dev = `in`) inside
+ * the kernel, between the activation loads and the table build of k_gemv_quad -- every workgroup holds the whole vector there.  All
+ * matrices of the call consume the same transformed vector (q/k/v, or gate/up, behind one NORM).
+ *   xf == NULL or kind TMAC_XF_NONE   tmac_hip_qgemm_fused_dev(..., N = 1, ...) itself: same route, same kernel, same bits
+ *   TMAC_XF_NORM   t = fp32(in) + residual (fp32 [K]; NULL: t = in);  x = gamma ? t * (1 / sqrt(mean(t^2) + eps)) * gamma : t.  fp32 rn adds; the
+ *                  LUT is built from the fp32 x by the code of the plain call, so without gamma the outputs are those of a plain call on t,
+ *                  bit for bit.  residual_out (fp32 [K], optional) receives t: each element is written once, pair p (8 elements) by
+ *                  workgroup p mod grid.  `keep` is accepted and ignored; residual == TMAC_XF_CARRY is refused (TMAC_HIP_E_ARG)
+ *   TMAC_XF_GLU    x = silu(in) * in2;  in2 has act_dtype like `in` (fp16 or fp32); hardware exp and reciprocal, specified to a tolerance
+ * Scope: what tmac_hip_qgemm_fused_dev serves with k_gemv_quad at N = 1 -- QUAD layout, 1- to 4-bit, per-group scales (group size >= 64,
+ * act groups of 64) or unified scales (m_groups >= 1), MFMA accumulate -- for K up to 24576, the kernel's own limit (the transformed
+ * vector stays in registers, no LDS is added).  Anything else: TMAC_HIP_E_NOMATCH, nothing is launched.
+ * Refused with TMAC_HIP_E_ARG before anything is launched: a kind outside 0..2; GLU without in2; in2 / residual / gamma / residual_out
+ * not 16-byte aligned (B_dev and C_dev[i] as everywhere); residual_out overlapping B_dev, residual, gamma or a C_dev[i] -- every
+ * workgroup reads the whole of the inputs while one workgroup writes each pair of residual_out, so an in-place residual stream has no
+ * order here: alternate between two buffers.
+ * While the thread records a chain the call is tmac_hip_chain_xform(xf) followed by the recorded tmac_hip_qgemm_fused_dev -- one call site
+ * for both modes, the chain's rules apply there.  With deferral on a transformed call is never queued: it flushes the queue, then
+ * launches (a failed flush returns its status and nothing is launched).
+ * Launch configuration: tmac_hip_debug_quad_config and the tuned table are honoured; the transformed instantiations exist for (threads,
+ * waves per quad) = (512,1), (512,2), (768,3), (1024,4).  A forced configuration outside that set is TMAC_HIP_E_NOMATCH; a tuned or
+ * heuristic choice outside it runs on the nearest member (same waves per quad with 512 threads; (1024,4) for K > 12288). */
+int32_t tmac_hip_qgemm_fused_xf_dev(const tmac_hip_weights* const* weights, int nmat, const void* B_dev, tmac_dtype_t act_dtype,
+                                    const tmac_hip_xform* xf, void* const* C_dev, tmac_dtype_t out_dtype, void* stream);
 /* Row-sharded chains (one process per GPU; weight ROWS split over the ranks).  While recording, the exchange step between
  * a call and the calls that need its output whole is recorded too -- tmac_hip_comm_allgather(comm, send, recv, ...) notes itself, or
  * tmac_hip_chain_record_gather where no communicator exists -- and inside the launch it becomes part of the hand-off: every rank's

@@ -583,6 +583,76 @@ extern "C" int32_t tmac_hip_qgemm_fused_dev(const tmac_hip_weights* const* weigh
     return fused_impl(weights, nmat, B_dev, act_dtype, C_dev, out_dtype, N, nullptr, nullptr, (hipStream_t)stream);
 }
 
+// ---- fused entry point with a vector transform (N = 1) -----------------------------------------------------------------------
+// Outside a recording: k_gemv_quad's XF instantiations.  Everything is checked before anything is launched; a transformed call is never
+// queued (it goes behind the deferred queue like every non-hot entry point).
+static bool ranges_overlap(const void* a, size_t an, const void* b, size_t bn) {
+    const char* pa = (const char*)a; const char* pb = (const char*)b;
+    return a && b && pa < pb + bn && pb < pa + an;
+}
+extern "C" int32_t tmac_hip_qgemm_fused_xf_dev(const tmac_hip_weights* const* wl, int nmat, const void* B_dev, tmac_dtype_t act_dtype,
+                                               const tmac_hip_xform* xf, void* const* C_list, tmac_dtype_t out_dtype, void* stream) {
+    hipStream_t st = (hipStream_t)stream;
+    const int32_t drc = ensure_device();
+    if (drc) return drc;
+    if (!xf || xf->kind == TMAC_XF_NONE) return fused_impl(wl, nmat, B_dev, act_dtype, C_list, out_dtype, 1, nullptr, nullptr, st);
+    if (chain_recording()) {       // one call site for both modes: the chain's own rules apply (CARRY allowed, fp16 in2)
+        int32_t rc = tmac_hip_chain_xform(xf);
+        if (rc == TMAC_HIP_OK) rc = fused_impl(wl, nmat, B_dev, act_dtype, C_list, out_dtype, 1, nullptr, nullptr, st);
+        if (rc != TMAC_HIP_OK && chain_recording()) chain_clear_xform();      // a rejected call leaves no pending transform
+        return rc;
+    }
+    if (xf->kind < 0 || xf->kind > 2) return fail(TMAC_HIP_E_ARG, "unknown transform kind %d", xf->kind);
+    if (!wl || !C_list || !B_dev || nmat < 1 || nmat > 4) return fail(TMAC_HIP_E_ARG, "bad fused arguments (1..4 matrices)");
+    const bool norm = xf->kind == TMAC_XF_NORM;
+    if (!norm && !xf->in2) return fail(TMAC_HIP_E_ARG, "GLU needs a second vector");
+    if (norm && xf->residual == TMAC_XF_CARRY)
+        return fail(TMAC_HIP_E_ARG, "TMAC_XF_CARRY names a vector kept inside a chain launch: outside a recording the residual is a vector in memory");
+    // the vectors the call touches (a NORM ignores in2, a GLU the NORM's fields)
+    const void* in2 = norm ? nullptr : xf->in2;
+    const float* residual = norm ? xf->residual : nullptr;
+    const float* gamma = norm ? xf->gamma : nullptr;
+    float* rout = norm ? xf->residual_out : nullptr;
+    if (misaligned(B_dev, ACT_ALIGN)) return fail(TMAC_HIP_E_ARG, "B_dev must be %zu-byte aligned (the LUT build reads 16 bytes at a time)", ACT_ALIGN);
+    for (int i = 0; i < nmat; ++i)
+        if (misaligned(C_list[i], out_align(out_dtype)))
+            return fail(TMAC_HIP_E_ARG, "C_dev[%d] must be %zu-byte aligned (four outputs are stored at a time)", i, out_align(out_dtype));
+    const struct { const void* p; const char* name; } vec[] = {{in2, "in2"}, {residual, "residual"}, {gamma, "gamma"}, {rout, "residual_out"}};
+    for (const auto& v : vec)
+        if (misaligned(v.p, XFORM_ALIGN)) return fail(TMAC_HIP_E_ARG, "transform vector %s must be %zu-byte aligned (read or written 16 bytes at a time)", v.name, XFORM_ALIGN);
+    const Plan p = plan_fused(wl, C_list, nmat, 1, false);
+    if (p.err) return fail(p.err, p.msg, p.mat);
+    const Shape& s0 = wl[0]->s;
+    if (p.route != R_GEMV_QUAD || g_knobs.variant == V_QUAD_MQSAD || s0.K > QUAD_XF_MAX_K)
+        return fail(TMAC_HIP_E_NOMATCH, "a transformed call runs on k_gemv_quad with the MFMA accumulate only (QUAD layout, K <= %d)", QUAD_XF_MAX_K);
+    if (rout) {
+        // every workgroup reads the whole of the inputs while ONE workgroup writes each pair of residual_out: no order between the two
+        const size_t K = (size_t)s0.K, act_bytes = K * (act_dtype == TMAC_F16 ? 2 : 4);
+        const struct { const void* p; size_t n; const char* name; } rd[] = {{B_dev, act_bytes, "B_dev"}, {residual, K * 4, "residual"}, {gamma, K * 4, "gamma"}};
+        for (const auto& r : rd)
+            if (ranges_overlap(rout, K * 4, r.p, r.n))
+                return fail(TMAC_HIP_E_ARG, "residual_out overlaps %s, which every workgroup reads while one writes (alternate between two buffers)", r.name);
+        for (int i = 0; i < nmat; ++i)
+            if (ranges_overlap(rout, K * 4, C_list[i], (size_t)wl[i]->s.Mw * (out_dtype == TMAC_F16 ? 2 : 4)))
+                return fail(TMAC_HIP_E_ARG, "residual_out overlaps C_dev[%d]", i);
+    }
+    bind_thread_device();
+    const int32_t brc = defer_barrier();       // never queued: behind the calling thread's queue (B_dev may be a queued output)
+    if (brc) return brc;
+    FusedXfArgs fa;
+    const int nb = fill_fused_args(fa, wl, C_list, nmat, out_dtype, nullptr);
+    fa.B = B_dev; fa.act_f16 = act_dtype == TMAC_F16;
+    fa.xf_kind = xf->kind; fa.in2 = in2; fa.residual = residual; fa.gamma = gamma; fa.residual_out = rout; fa.eps = xf->eps;
+    // the launch configuration: forced (tmac_hip_debug_quad_config) -- it must have an XF instantiation -- else tuned, else the heuristic
+    int ft = g_knobs.force_ft, wpq = g_knobs.force_wpq;
+    const bool strict = ft || wpq;
+    if (!strict) tuned_config(fa, nb, ft, wpq);
+    const hipError_t e = launch_gemv_quad_xf(fa, ft, wpq, strict, st);
+    if (e == hipErrorInvalidValue) return fail(TMAC_HIP_E_NOMATCH, "no transformed GEMV kernel for this configuration (XF instantiations: (512,1), (512,2), (768,3), (1024,4))");
+    if (e != hipSuccess) return fail(TMAC_HIP_E_RUNTIME, "transformed gemv launch: %s", hipGetErrorString(e));
+    return TMAC_HIP_OK;
+}
+
 extern "C" int32_t tmac_hip_qgemm_fused_partial_sums(const tmac_hip_weights* w, const void* B_dev, tmac_dtype_t act_dtype,
                                                      int32_t* PS_host, float* C_host, float* lut_host, int N, void* stream) {
     if (!w || !PS_host) return fail(TMAC_HIP_E_ARG, "null argument");

@@ -46,6 +46,17 @@ struct FusedArgs {
     int nu, nsb, tstride, G, nsg, gs_shift;   // filled by launch_gemv_fused (host-side divides)
 };
 
+// k_gemv_quad's XF instantiations (tmac_hip_qgemm_fused_xf_dev): the N = 1 call plus a vector transform of its activations, applied
+// between the activation loads and the table build.  An argument block of its own: the plain instantiations keep theirs.
+struct FusedXfArgs : FusedArgs {
+    int xf_kind;             // TMAC_XF_NORM (1) | TMAC_XF_GLU (2)
+    const void* in2;         // GLU: second vector [K], dtype of B
+    const float* residual;   // NORM: fp32 [K] or null
+    const float* gamma;      // NORM: fp32 [K] or null (add only)
+    float* residual_out;     // NORM: fp32 [K] or null; pair p is stored by workgroup p mod gridDim.x
+    float eps;
+};
+
 // one-hot MFMA GEMM for N > 1 activation rows (tmac_gemm.hip); weights in the QUAD layout; up to 4 matrices that share
 // K, the quantisation config and the LUT in one launch
 struct GemmMat {
@@ -148,6 +159,12 @@ hipError_t launch_gemv_fused(const FusedArgs& a, int N, bool build_lut, hipStrea
 // quad kernel (tmac_quad.hip): a.m[i].nb_end = cumulative ROW QUAD counts; force_ft/force_wpq 0 = heuristic
 bool gemv_quad_supported(const Shape& s);
 hipError_t launch_gemv_quad(const FusedArgs& a, int N, bool build_lut, int force_ft, int force_wpq, hipStream_t st);
+// The same kernel with a vector transform in front of its table build (N = 1, LUT built in-kernel, MFMA accumulate).  The XF
+// instantiations cover a subset of the launch configurations (quad_xf_covered, tmac_quad.hip).  ft / wpq: 0 = heuristic; strict: the
+// configuration was forced by the caller and must be covered as it is (hipErrorInvalidValue otherwise) -- else it falls back to the
+// nearest covered one.
+constexpr int QUAD_XF_MAX_K = 24576;
+hipError_t launch_gemv_quad_xf(const FusedXfArgs& a, int ft, int wpq, bool strict, hipStream_t st);
 // rows kernel (tmac_rows.hip): 2-8 activation rows per weight pass on QUAD-layout weights, tables copied from the half-table image
 struct RowsArgs {
     FusedMat m[4];           // nb_end = cumulative ROW QUAD counts (fill_fused_args)

@@ -11,10 +11,13 @@
 // flight, then walk their (quad, step) list.  Template parameters: BITS 2|4; ZP zero points; SM 0 per-group scales /
 // 2 unified scale applied last (BitNet); LUTSRC 1 build the LUT in-kernel / 0 copy the image k_preprocess wrote;
 // NR tables built per thread; FT threads; WPQ waves per quad; DUMP integer tap; ACC 1 v_mfma_i32_16x16x64_i8
-// accumulate / 0 v_mqsad_pk_u16_u8 (A/B variant).  DESIGN.md 4.1, 4.2, 4.6.
+// accumulate / 0 v_mqsad_pk_u16_u8 (A/B variant); XF a vector transform of the activations (residual add + RMSNorm,
+// silu(in) * in2: tmac_hip_qgemm_fused_xf_dev) between the activation loads and the table build, where every workgroup
+// holds the whole vector.  DESIGN.md 4.1, 4.2, 4.6.
 #include <hip/hip_runtime.h>
 #include <hip/hip_fp16.h>
 #include <stdint.h>
+#include <type_traits>
 
 #include "tmac_core.h"
 #include "tmac_kernels.h"
@@ -95,8 +98,11 @@ __device__ __forceinline__ void load_q(QFrag<BITS>& f, const FusedArgs& a, const
 // k_gemv_fused for the operand construction; with 64 lanes = 64 units of one quad, source lane l = 16g + i and
 // D[i][4g+beta] lands in lane l' = 16*(i/4) + 4g + beta, register i%4: lane l' owns output row beta and the four
 // units 16g + 4*(l'/16) .. +3 of the step (two act groups, one 128-wide scale group).
-template <int BITS, bool ZP, int SM, int LUTSRC, int NR, int FT, int WPQ, bool DUMP, int ACC, bool SCF16, bool EARLY>
-__global__ __launch_bounds__(FT) void k_gemv_quad(FusedArgs a) {
+// XF (LUTSRC 1, ACC 1, no tap, one activation row): the argument block carries the transform's operands (FusedXfArgs); every line of it
+// sits under if constexpr (XF).
+template <int BITS, bool ZP, int SM, int LUTSRC, int NR, int FT, int WPQ, bool DUMP, int ACC, bool SCF16, bool EARLY, bool XF = false>
+__global__ __launch_bounds__(FT) void k_gemv_quad(std::conditional_t<XF, FusedXfArgs, FusedArgs> a) {
+    static_assert(!XF || (LUTSRC == 1 && ACC == 1 && !DUMP), "the transform lives in the in-kernel LUT build of the MFMA form");
     extern __shared__ uint4 lds[];
     const unsigned long long t_entry = DUMP ? __builtin_amdgcn_s_memtime() : 0ull;   // before the first kernel-argument load
     constexpr int NWV = FT / 64, IPI = NWV / WPQ;
@@ -155,18 +161,117 @@ __global__ __launch_bounds__(FT) void k_gemv_quad(FusedArgs a) {
             }
         }
     }
+    // XF: the transform's operands for the lane's own pairs, clamped like xr: NORM residual (xa) and gamma (xg), GLU in2 (xa)
+    uint32_t xa[XF ? NP : 1][8], xg[XF ? NP : 1][8];
+    if constexpr (XF) {
+#pragma unroll
+        for (int r = 0; r < NP; ++r) {
+            const int p = min(r * FT + tid, P - 1);
+#pragma unroll
+            for (int i = 0; i < 8; ++i) { xa[r][i] = 0u; xg[r][i] = 0u; }
+            const void* src_a = a.xf_kind == 1 ? (const void*)a.residual : a.in2;
+            if (src_a != nullptr) {
+                if (a.xf_kind == 2 && a.act_f16) {
+                    const uint4 v = reinterpret_cast<const uint4*>(src_a)[p];
+                    xa[r][0] = v.x; xa[r][1] = v.y; xa[r][2] = v.z; xa[r][3] = v.w;
+                } else {
+                    const uint4* src = reinterpret_cast<const uint4*>(src_a) + 2 * (size_t)p;
+                    const uint4 v0 = src[0], v1 = src[1];
+                    xa[r][0] = v0.x; xa[r][1] = v0.y; xa[r][2] = v0.z; xa[r][3] = v0.w;
+                    xa[r][4] = v1.x; xa[r][5] = v1.y; xa[r][6] = v1.z; xa[r][7] = v1.w;
+                }
+            }
+            if (a.xf_kind == 1 && a.gamma != nullptr) {
+                const uint4* src = reinterpret_cast<const uint4*>(a.gamma) + 2 * (size_t)p;
+                const uint4 v0 = src[0], v1 = src[1];
+                xg[r][0] = v0.x; xg[r][1] = v0.y; xg[r][2] = v0.z; xg[r][3] = v0.w;
+                xg[r][4] = v1.x; xg[r][5] = v1.y; xg[r][6] = v1.z; xg[r][7] = v1.w;
+            }
+        }
+    }
+    float xrs = 1.0f;                 // XF, NORM with gamma: 1 / rms, known behind the cross-wave sum below
+    bool xnorm = false;
     auto unpack = [&](int r, float (&x)[8]) {
-        if (a.act_f16) {
+        if (!XF && a.act_f16) {
 #pragma unroll
             for (int i = 0; i < 4; ++i) {
                 const __half2 hh = *reinterpret_cast<const __half2*>(&xr[r][i]);
                 x[2 * i] = __low2float(hh); x[2 * i + 1] = __high2float(hh);
             }
-        } else {
+        } else {      // (XF: xr holds the transformed vector as fp32)
 #pragma unroll
             for (int i = 0; i < 8; ++i) x[i] = __uint_as_float(xr[r][i]);
         }
+        if constexpr (XF) {
+            if (xnorm) {
+#pragma unroll
+                for (int i = 0; i < 8; ++i) x[i] = __fmul_rn(x[i], xrs);
+            }
+        }
     };
+    // ---- 1b. XF: the element-wise part of the transform, in place in xr (fp32 from here on) -----
+    // Before the weight fragments are issued: it waits for the operand loads, and nothing else is in flight yet.  NORM: t = in +
+    // residual (fp32 rn), t to residual_out by the ONE workgroup that owns the pair (p mod gridDim.x: a grid of one owns them all),
+    // the lane's part of sum t^2, and t * gamma; 1 / rms multiplies in unpack, once the sum is known.  Without gamma x = t, untouched:
+    // the table build then sees the bits a plain call on t would.  GLU: x = silu(in) * in2 with the hardware exp and reciprocal
+    // (tmac_chain.hip's formula).  The transformed vector stays in the registers the raw one arrived in (xr is [NP][8] for fp32
+    // activations anyway); the operands are dead behind this block.
+    float xss = 0.f;
+    if constexpr (XF) {
+        const bool in_f16 = a.act_f16 != 0;
+#pragma unroll
+        for (int r = 0; r < NP; ++r) {
+            const int p = r * FT + tid;
+            float x[8];
+            if (in_f16) {
+#pragma unroll
+                for (int i = 0; i < 4; ++i) {
+                    const __half2 hh = *reinterpret_cast<const __half2*>(&xr[r][i]);
+                    x[2 * i] = __low2float(hh); x[2 * i + 1] = __high2float(hh);
+                }
+            } else {
+#pragma unroll
+                for (int i = 0; i < 8; ++i) x[i] = __uint_as_float(xr[r][i]);
+            }
+            if (a.xf_kind == 1) {
+                if (a.residual != nullptr) {
+#pragma unroll
+                    for (int i = 0; i < 8; ++i) x[i] = __fadd_rn(x[i], __uint_as_float(xa[r][i]));
+                }
+                if (p < P) {
+                    if (a.residual_out != nullptr && (uint32_t)p % gridDim.x == blockIdx.x) {
+                        float4* ro = reinterpret_cast<float4*>(a.residual_out) + 2 * (size_t)p;
+                        ro[0] = make_float4(x[0], x[1], x[2], x[3]);
+                        ro[1] = make_float4(x[4], x[5], x[6], x[7]);
+                    }
+#pragma unroll
+                    for (int i = 0; i < 8; ++i) xss = __fmaf_rn(x[i], x[i], xss);
+                }
+                if (a.gamma != nullptr) {
+#pragma unroll
+                    for (int i = 0; i < 8; ++i) x[i] = __fmul_rn(x[i], __uint_as_float(xg[r][i]));
+                }
+            } else {
+                float u[8];
+                if (in_f16) {
+#pragma unroll
+                    for (int i = 0; i < 4; ++i) {
+                        const __half2 hh = *reinterpret_cast<const __half2*>(&xa[r][i]);
+                        u[2 * i] = __low2float(hh); u[2 * i + 1] = __high2float(hh);
+                    }
+                } else {
+#pragma unroll
+                    for (int i = 0; i < 8; ++i) u[i] = __uint_as_float(xa[r][i]);
+                }
+                // silu(v) = v / (1 + exp(-v)): hardware exp2 and reciprocal (1 ulp each; the transform is specified to a tolerance)
+#pragma unroll
+                for (int i = 0; i < 8; ++i)
+                    x[i] = __fmul_rn(__fmul_rn(x[i], __builtin_amdgcn_rcpf(__fadd_rn(1.0f, __expf(-x[i])))), u[i]);
+            }
+#pragma unroll
+            for (int i = 0; i < 8; ++i) xr[r][i] = __float_as_uint(x[i]);
+        }
+    }
 
     // ---- 2. this wave's work: quads slot, slot + stride, ...; steps h, h + WPQ, ... of each ------
     const int slot0 = blockIdx.x * IPI + w / WPQ, h = w % WPQ, stride = gridDim.x * IPI;
@@ -193,13 +298,34 @@ __global__ __launch_bounds__(FT) void k_gemv_quad(FusedArgs a) {
         for (int r = 0; r < NP; ++r)
 #pragma unroll
             for (int i = 0; i < 8; ++i)
-                if (i < 4 || !a.act_f16) asm volatile("" :: "v"(xr[r][i]));
+                if (i < 4 || XF || !a.act_f16) asm volatile("" :: "v"(xr[r][i]));
     }
     if (early) {
         issue(f0); issue(f1);
         if (RING == 4) { issue(f2); issue(f3); }
     }
     QSTAMP(1);
+    if constexpr (XF) {
+        // NORM with gamma: the mean square.  A wave sum per wave (four DPP steps inside the rows of 16 lanes, the four row sums through
+        // readlane), the partials through LDS (l_red: idle until the first finish_quad, behind the barrier that ends section 3), added in
+        // wave order by every thread.  The barrier is LDS-only: __syncthreads() carries s_waitcnt vmcnt(0) and would wait for the weight
+        // fragments issued a moment ago.
+        if (a.xf_kind == 1 && a.gamma != nullptr) {
+            float ss = xss;
+            ss = __fadd_rn(ss, qdpp_f<0xB1>(ss)); ss = __fadd_rn(ss, qdpp_f<0x4E>(ss));
+            ss = __fadd_rn(ss, qdpp_f<0x141>(ss)); ss = __fadd_rn(ss, qdpp_f<0x140>(ss));     // row_half_mirror, row_mirror
+            const int ssb = __builtin_bit_cast(int, ss);
+            const float sw = __fadd_rn(__fadd_rn(__builtin_bit_cast(float, __builtin_amdgcn_readlane(ssb, 0)), __builtin_bit_cast(float, __builtin_amdgcn_readlane(ssb, 16))),
+                                       __fadd_rn(__builtin_bit_cast(float, __builtin_amdgcn_readlane(ssb, 32)), __builtin_bit_cast(float, __builtin_amdgcn_readlane(ssb, 48))));
+            if (lane == 0) l_red[w] = sw;
+            asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
+            float tot = 0.f;
+#pragma unroll
+            for (int ww = 0; ww < NWV; ++ww) tot = __fadd_rn(tot, l_red[ww]);
+            xrs = __builtin_amdgcn_rsqf(__fmaf_rn(tot, __builtin_amdgcn_rcpf((float)s.K), a.eps));
+            xnorm = true;
+        }
+    }
 
     // ---- 3. LUT into LDS (all FT threads) ------------------------------------------------------
     if (LUTSRC == 0) {
@@ -869,19 +995,20 @@ static hipError_t qlaunch_nr(const FusedArgs& a, int total_q, int N, hipStream_t
     return hipGetLastError();
 }
 
-template <int BITS, bool ZP, int SM, int LUTSRC>
-static hipError_t qlaunch_cfg(const FusedArgs& a, int total_q, int N, int force_ft, int force_wpq, hipStream_t st) {
+// The (threads, waves per quad) of a launch: best_ft / best_wpq; false when the kernel has no such configuration.  need512: the launch
+// wants an instantiation that exists for 512-thread workgroups only (tap, prebuilt LUT, v_mqsad accumulate).
+static bool quad_config(const FusedArgs& a, int BITS, bool need512, int total_q, int force_ft, int force_wpq, int& best_ft, int& best_wpq) {
     // Configuration choice, from tools/tune_quad.py on MI355X (profiles/r01_tune_quad.txt, us per launch in a graph):
     //   W2: o 4096x4096: (512,2) 4.3 | qkv 12288x4096: (512,2) 6.5, (512,1) 6.6, (1024,1) 6.9 | gate_up 22016x4096:
     //   (512,1) 9.2, (512,2) 10.2 | down 4096x11008: (768,3) 6.9, (1024,4) 7.2, (512,2) 7.3, (512,1) 8.8.
     //   W4 (tune_quad.py 0 4): o (512,2) | qkv (512,2) | gate_up (512,1) | down (512,2).
     const int nst = (a.s.K / 32 + 63) / 64;
     // two waves per quad up to one quad per wave slot of the chip (4096), one beyond
-    int best_ft = 512, best_wpq = (total_q <= 4096 && nst >= 2) ? 2 : 1;
+    best_ft = 512; best_wpq = (total_q <= 4096 && nst >= 2) ? 2 : 1;
     // ... except where two waves per quad would leave the chip between one and two workgroups per CU (shards of a
     // row-split model: 3 x 2048 and 2 x 2752 rows measured 7 % faster with one, profiles/history/r01_autotune_shards_before_heuristic.txt)
     if (best_wpq == 2 && total_q > 1024 && total_q < 2048) best_wpq = 1;
-    if (BITS == 2 && total_q <= 1024 && nst >= 4 && !(a.dump || LUTSRC == 0 || !a.acc_mfma)) {
+    if (BITS == 2 && total_q <= 1024 && nst >= 4 && !need512) {
         // long rows, few quads: 3 waves per quad when that splits the steps evenly, else 4
         if (nst % 3 == 0 && a.s.K / 4 <= 6 * 768) { best_ft = 768; best_wpq = 3; }
         else { best_ft = 1024; best_wpq = 4; }
@@ -891,29 +1018,31 @@ static hipError_t qlaunch_cfg(const FusedArgs& a, int total_q, int N, int force_
     // Matches every case the tuner found on the llama-2-7B shapes and their 2-/4-/8-way row shards
     // (profiles/history/r01_autotune_shards_before_heuristic.txt and the runs after it): q/k/v 3 x 4096 rows -> (768,1) 5.6 against 6.1 us; 3 x 2048 -> (768,2);
     // gate/up 2 x 5504 -> (768,1) 5.45 against 5.9; 2 x 2752 -> (768,2); down 4096 x 11008 -> (768,3).
-    if (!(a.dump || LUTSRC == 0 || !a.acc_mfma) && a.s.K / 4 <= 6 * 768) {
+    if (!need512 && a.s.K / 4 <= 6 * 768) {
         for (int wq = 1; wq <= 3; ++wq) {
             if (wq > nst || nst % wq || (wq == 3 && BITS > 2)) continue;   // (W4 long rows measure better on (512,2): tune_quad.py 0 4)
             const int wgs = (total_q * wq + 11) / 12;
             if (wgs > 192 && wgs <= 256) { best_ft = 768; best_wpq = wq; break; }
         }
     }
-    double best = 0.0;
-    if (a.s.K / 4 > 6 * 512 && best_ft == 512 && !(a.dump || LUTSRC == 0 || !a.acc_mfma)) best_ft = 1024;   // LUT build: <= 6 tables per thread
+    if (a.s.K / 4 > 6 * 512 && best_ft == 512 && !need512) best_ft = 1024;   // LUT build: <= 6 tables per thread
     if (force_ft) { best_ft = force_ft; if (!force_wpq && best_wpq > 2) best_wpq = 2; }
     if (force_wpq) best_wpq = force_wpq;
-    const bool need512 = a.dump || LUTSRC == 0 || !a.acc_mfma;
-    if (best_ft == 768 || best_wpq == 3) {        // 12 waves: 3 per quad (balanced when the row has 3k steps), or 12 / 6 quads per workgroup
-        if (best_ft != 768 || need512 || a.s.K / 4 > 6 * 768) return hipErrorInvalidValue;
+    if (best_ft == 768 || best_wpq == 3)          // 12 waves: 3 per quad (balanced when the row has 3k steps), or 12 / 6 quads per workgroup
+        return best_ft == 768 && !need512 && a.s.K / 4 <= 6 * 768 && best_wpq >= 1 && best_wpq <= 3;
+    return !((need512 && best_ft != 512) || (best_wpq == 4 && best_ft != 1024) || (best_ft != 512 && best_ft != 1024) ||
+             (best_wpq != 1 && best_wpq != 2 && best_wpq != 4) || a.s.K / 4 > 6 * best_ft);
+}
+
+template <int BITS, bool ZP, int SM, int LUTSRC>
+static hipError_t qlaunch_cfg(const FusedArgs& a, int total_q, int N, int force_ft, int force_wpq, hipStream_t st) {
+    int best_ft, best_wpq;
+    if (!quad_config(a, BITS, a.dump || LUTSRC == 0 || !a.acc_mfma, total_q, force_ft, force_wpq, best_ft, best_wpq)) return hipErrorInvalidValue;
+    if (best_ft == 768) {
         if (best_wpq == 3) return qlaunch_nr<BITS, ZP, SM, LUTSRC, 768, 3>(a, total_q, N, st);
         if (best_wpq == 1) return qlaunch_nr<BITS, ZP, SM, LUTSRC, 768, 1>(a, total_q, N, st);
-        if (best_wpq == 2) return qlaunch_nr<BITS, ZP, SM, LUTSRC, 768, 2>(a, total_q, N, st);
-        return hipErrorInvalidValue;
+        return qlaunch_nr<BITS, ZP, SM, LUTSRC, 768, 2>(a, total_q, N, st);
     }
-    if ((need512 && best_ft != 512) || (best_wpq == 4 && best_ft != 1024) || (best_ft != 512 && best_ft != 1024) ||
-        (best_wpq != 1 && best_wpq != 2 && best_wpq != 4) || a.s.K / 4 > 6 * best_ft)
-        best = 1e30;
-    if (best >= 1e30) return hipErrorInvalidValue;
     if (best_ft == 512) return best_wpq == 1 ? qlaunch_nr<BITS, ZP, SM, LUTSRC, 512, 1>(a, total_q, N, st)
                                              : qlaunch_nr<BITS, ZP, SM, LUTSRC, 512, 2>(a, total_q, N, st);
     if (best_wpq == 4) return qlaunch_nr<BITS, ZP, SM, LUTSRC, 1024, 4>(a, total_q, N, st);
@@ -931,6 +1060,60 @@ static hipError_t qlaunch_b(const FusedArgs& a, int total_q, int N, int fft, int
                           : qlaunch_cfg<BITS, false, 0, LUTSRC>(a, total_q, N, fft, fwpq, st);
 }
 
+// ---- XF instantiations (tmac_hip_qgemm_fused_xf_dev) ----
+// They cover FOUR of the eight (threads, waves per quad) configurations -- one per waves-per-quad count, which is what shapes the K walk
+// and the cross-wave reductions: (512,1), (512,2), (768,3), (1024,4) -- so that eight translation units grow by 12 kernels per scale
+// flavour instead of 20.  A configuration the caller forced (tmac_hip_debug_quad_config) outside the set is refused; one the heuristic or
+// the tuned table chose falls back to the nearest covered one: same waves per quad in 512-thread workgroups ((768,1), (1024,1) -> (512,1);
+// (768,2), (1024,2) -> (512,2)), or (1024,4) where 512 threads cannot build the tables (K > 12288: more than six per thread).
+static bool quad_xf_covered(int ft, int wpq) { return (ft == 512 && (wpq == 1 || wpq == 2)) || (ft == 768 && wpq == 3) || (ft == 1024 && wpq == 4); }
+
+template <int BITS, bool ZP, int SM, int FT, int WPQ>
+static hipError_t qlaunch_xf_nr(const FusedXfArgs& a, int total_q, hipStream_t st) {
+    constexpr int IPI = FT / 64 / WPQ;
+    const size_t shmem = quad_lds_bytes(a.s, FT / 64);
+    int gx = (total_q + IPI - 1) / IPI;
+    const int cap = (FT > 512) ? 256 : 512;       // as qlaunch_nr
+    if (gx > cap) gx = cap;
+    dim3 g(gx, 1), b(FT);
+    const int T = a.s.K / 4;
+    const bool two = T <= 2 * FT;
+    if (!two && T > 6 * FT) return hipErrorInvalidValue;
+#define QX(NRV, EV) hipLaunchKernelGGL((k_gemv_quad<BITS, ZP, SM, 1, NRV, FT, WPQ, false, 1, QSCF16, EV, true>), g, b, shmem, st, a)
+    if constexpr (FT == 512) {
+        if (gx <= 256) { if (two) QX(2, true); else QX(6, true); }
+        else { if (two) QX(2, false); else QX(6, false); }
+    } else {
+        if (two) QX(2, true); else QX(6, true);
+    }
+#undef QX
+    return hipGetLastError();
+}
+
+template <int BITS, bool ZP, int SM>
+static hipError_t qlaunch_xf_cfg(const FusedXfArgs& a, int total_q, int ft, int wpq, bool strict, hipStream_t st) {
+    int best_ft, best_wpq;
+    if (!quad_config(a, BITS, false, total_q, ft, wpq, best_ft, best_wpq)) return hipErrorInvalidValue;
+    if (!quad_xf_covered(best_ft, best_wpq)) {
+        if (strict) return hipErrorInvalidValue;
+        if (a.s.K / 4 > 6 * 512) { best_ft = 1024; best_wpq = 4; }
+        else { best_ft = 512; best_wpq = best_wpq >= 2 ? 2 : 1; }
+    }
+    if (best_ft == 512) return best_wpq == 1 ? qlaunch_xf_nr<BITS, ZP, SM, 512, 1>(a, total_q, st) : qlaunch_xf_nr<BITS, ZP, SM, 512, 2>(a, total_q, st);
+    if (best_ft == 768) return qlaunch_xf_nr<BITS, ZP, SM, 768, 3>(a, total_q, st);
+    return qlaunch_xf_nr<BITS, ZP, SM, 1024, 4>(a, total_q, st);
+}
+
+template <int BITS>
+static hipError_t qlaunch_xf_b(const FusedXfArgs& a, int total_q, int ft, int wpq, bool strict, hipStream_t st) {
+    if (a.s.m_groups >= 1) {
+        if constexpr (QSCF16) return hipErrorInvalidValue;
+        else return qlaunch_xf_cfg<BITS, false, 2>(a, total_q, ft, wpq, strict, st);
+    }
+    return a.s.zero_point ? qlaunch_xf_cfg<BITS, true, 0>(a, total_q, ft, wpq, strict, st)
+                          : qlaunch_xf_cfg<BITS, false, 0>(a, total_q, ft, wpq, strict, st);
+}
+
 // a.m[i].nb_end must hold cumulative QUAD counts.  force_ft / force_wpq: 0 = heuristic (A/B knobs)
 #define QENTRY_(b, h) launch_gemv_quad_b##b##_h##h
 #define QENTRY(b, h) QENTRY_(b, h)
@@ -940,7 +1123,31 @@ hipError_t QENTRY(TMAC_QUAD_BITS, TMAC_QUAD_SCF16)(const FusedArgs& a, int total
     return build_lut ? qlaunch_b<TMAC_QUAD_BITS, 1>(a, total_q, N, force_ft, force_wpq, st)
                      : qlaunch_b<TMAC_QUAD_BITS, 0>(a, total_q, N, force_ft, force_wpq, st);
 }
+#define QXENTRY_(b, h) launch_gemv_quad_xf_b##b##_h##h
+#define QXENTRY(b, h) QXENTRY_(b, h)
+#define QXENTRY_DECL(b, h) hipError_t QXENTRY_(b, h)(const FusedXfArgs& a, int total_q, int ft, int wpq, bool strict, hipStream_t st)
+QXENTRY_DECL(1, 0); QXENTRY_DECL(1, 1); QXENTRY_DECL(2, 0); QXENTRY_DECL(2, 1); QXENTRY_DECL(3, 0); QXENTRY_DECL(3, 1); QXENTRY_DECL(4, 0); QXENTRY_DECL(4, 1);
+hipError_t QXENTRY(TMAC_QUAD_BITS, TMAC_QUAD_SCF16)(const FusedXfArgs& a, int total_q, int ft, int wpq, bool strict, hipStream_t st) {
+    return qlaunch_xf_b<TMAC_QUAD_BITS>(a, total_q, ft, wpq, strict, st);
+}
 #if TMAC_QUAD_BITS == 2 && TMAC_QUAD_SCF16 == 0
+hipError_t launch_gemv_quad_xf(const FusedXfArgs& a_in, int ft, int wpq, bool strict, hipStream_t st) {
+    if (!gemv_quad_supported(a_in.s) || a_in.s.K > QUAD_XF_MAX_K || a_in.nmat < 1 || a_in.nmat > 4 || !a_in.acc_mfma || a_in.dump ||
+        (a_in.xf_kind != 1 && a_in.xf_kind != 2))
+        return hipErrorInvalidValue;
+    FusedXfArgs a = a_in;
+    fused_precompute(a);
+    const int total_q = a.m[a.nmat - 1].nb_end;
+    const bool h = a.sc_f16 && a.s.m_groups < 1;
+#define QXDISP(B) return h ? launch_gemv_quad_xf_b##B##_h1(a, total_q, ft, wpq, strict, st) : launch_gemv_quad_xf_b##B##_h0(a, total_q, ft, wpq, strict, st)
+    switch (a.s.bits) {
+        case 1: QXDISP(1);
+        case 2: QXDISP(2);
+        case 3: QXDISP(3);
+        default: QXDISP(4);
+    }
+#undef QXDISP
+}
 hipError_t launch_gemv_quad(const FusedArgs& a_in, int N, bool build_lut, int force_ft, int force_wpq, hipStream_t st) {
     if (!gemv_quad_supported(a_in.s) || a_in.nmat < 1 || a_in.nmat > 4) return hipErrorInvalidValue;
     FusedArgs a = a_in;

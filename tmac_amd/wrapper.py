@@ -442,6 +442,33 @@ class TMACGeMMWrapper:
             rec.append((in2, residual, gamma, residual_out))      # kept alive with the chain
         check(B.lib().tmac_hip_chain_xform(C.byref(xf)))
 
+    def fused_xf(self, weights_list, B_dev, C_list, kind, in2=None, residual=None, gamma=None, eps: float = 1e-5, residual_out=None,
+                 act_dtype: Optional[int] = None, out_dtype: Optional[int] = None, stream=None) -> None:
+        """``fused`` (N = 1) with a vector transform of the activations applied inside the kernel's LUT build
+        (tmac_hip_qgemm_fused_xf_dev): kind "norm" / "glu" as in ``chain_xform``, or None (a plain ``fused`` call).  Outside a
+        recording the call launches by itself -- residual ``CARRY`` is refused there, and residual_out must not overlap a vector the
+        call reads; inside ``record_chain()`` it records the transform and the call."""
+        n = len(weights_list)
+        if act_dtype is None:
+            act_dtype = _dtype_code(B_dev)
+        if out_dtype is None:
+            out_dtype = _dtype_code(C_list[0])
+        xf = B.XForm()
+        xf.kind = {None: 0, "norm": 1, "glu": 2}[kind]
+        xf.in2 = _ptr(in2) if in2 is not None else None
+        xf.residual = 1 if residual is TMACGeMMWrapper.CARRY else (_ptr(residual) if residual is not None else None)
+        xf.gamma = _ptr(gamma) if gamma is not None else None
+        xf.eps = float(eps)
+        xf.residual_out = _ptr(residual_out) if residual_out is not None else None
+        xf.keep = 0
+        wa = (C.c_void_p * n)(*[w.handle.value for w in weights_list])
+        ca = (C.c_void_p * n)(*[_ptr(c) for c in C_list])
+        rec = getattr(self, "_recording", None)
+        if rec is not None:      # kept alive with the chain
+            rec.append((list(weights_list), B_dev, list(C_list), in2, residual, gamma, residual_out))
+        check(B.lib().tmac_hip_qgemm_fused_xf_dev(wa, n, _ptr(B_dev), act_dtype, C.byref(xf) if kind is not None else None, ca, out_dtype,
+                                                  _stream(stream)))
+
     def record_chain(self) -> "_ChainRecorder":
         """``with wr.record_chain() as rec: <the token's wr.fused(...) calls>`` — the calls are noted instead of launched;
         afterwards ``rec.chain.launch()`` executes all of them in ONE persistent kernel launch (tmac_hip_chain_*)."""
