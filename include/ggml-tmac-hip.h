@@ -70,6 +70,13 @@ int ggml_tmac_hip_mul_mat_dev(const struct tmac_ggml_tensor* const* w, int nw, c
 int ggml_tmac_hip_mul_mat_dev_xf(const struct tmac_ggml_tensor* const* w, int nw, const void* x_dev, int x_is_f32, int kind /* 1 norm, 2 glu */,
                                  const void* in2_dev, const float* residual, const float* norm_weight, float eps, float* residual_out,
                                  void* const* dst_dev, int dst_is_f32);
+/* The same for n_rows rows of x (tmac_hip.h: tmac_hip_qgemm_fused_xf_rows_dev), so that the hook serves decode, a small batch and prefill
+ * with one formula: x and in2 [n_rows][K], residual and residual_out fp32 [n_rows][K], norm_weight fp32 [K] shared by the rows, outputs
+ * [n_rows][M] each.  n_rows = 1 is the call above.  For n_rows >= 2 the operator runs inside the LUT build of the route the plain mat-mul
+ * of that many rows takes; residual_out must not overlap x, residual, norm_weight, in2 or an output. */
+int ggml_tmac_hip_mul_mat_dev_xf_rows(const struct tmac_ggml_tensor* const* w, int nw, const void* x_dev, int x_is_f32, int kind /* 1 norm, 2 glu */,
+                                      const void* in2_dev, const float* residual, const float* norm_weight, float eps, float* residual_out,
+                                      void* const* dst_dev, int dst_is_f32, int n_rows);
 int ggml_tmac_hip_set_deferred(int on);
 int ggml_tmac_hip_flush(void);
 int ggml_tmac_hip_synchronize(void);

@@ -293,6 +293,40 @@ int32_t tmac_hip_chain_xform(const tmac_hip_xform* xf);
  * heuristic choice outside it runs on the nearest member (same waves per quad with 512 threads; (1024,4) for K > 12288). */
 int32_t tmac_hip_qgemm_fused_xf_dev(const tmac_hip_weights* const* weights, int nmat, const void* B_dev, tmac_dtype_t act_dtype,
                                     const tmac_hip_xform* xf, void* const* C_dev, tmac_dtype_t out_dtype, void* stream);
+/* The same for N activation rows -- prefill, or a batch of 2-8 rows -- so that one call site serves every N with one formula.
+ * Layouts: B_dev and in2 [N][K] in act_dtype; residual and residual_out fp32 [N][K]; gamma fp32 [K], shared by the rows; C_dev[i]
+ * [N][Mw_i] in out_dtype.  Row n of every operand belongs to row n of the activations.
+ *   N = 1                             tmac_hip_qgemm_fused_xf_dev itself: same route, same kernel, same bits
+ *   xf == NULL or kind TMAC_XF_NONE   tmac_hip_qgemm_fused_dev(..., N, ...) itself
+ *   N >= 2   the call is planned like tmac_hip_qgemm_fused_dev(N) and the transform sits in the activation load of the planned LUT build
+ *            (k_lut_image for k_gemm_planes, the pair builds for k_gemm_onehot / k_gemv_rows / the row loop): the LUT is built from the fp32
+ *            x by the plain build's code, and the kernel behind it is the plain call's.  NORM with gamma or residual_out is preceded by
+ *            one row pass (k_xf_rows, a workgroup per row) that writes residual_out -- every element once -- and the row's
+ *            r = rsq(fma(sum t^2, rcp(K), eps)); the builders then form (t * gamma) * r.  The order of that sum depends on K alone: a row
+ *            gives the same x whatever N, its index or the route.  (At N = 1 k_gemv_quad sums in its own order: the two forms agree to
+ *            rounding, not bits, for NORM with gamma.)  Where the plain call would run k_gemv_quad with one LUT build per workgroup, the
+ *            transformed call builds the half-table image once and runs the row loop on it.
+ * Scope (N >= 2): QUAD layout, 1- to 4-bit, act groups of 64 or unified scales with K <= 12288, one configuration per call.
+ * TMAC_HIP_E_NOMATCH, nothing launched: anything outside that scope, a plan that would need the three-layout LUT build, the
+ * reference-layout variant, fast-aggregation weights.  TMAC_HIP_E_ARG, nothing launched: the refusals of the N = 1 form with extents
+ * x N -- kind outside 0..2, GLU without in2, TMAC_XF_CARRY, a transform vector below 16-byte alignment, residual_out overlapping B_dev,
+ * residual, gamma, in2 or an output (the LUT build reads `in` and `residual` after the row pass has written residual_out: alternate
+ * between two buffers).
+ * While the thread records a chain an N >= 2 transformed call is TMAC_HIP_E_NOMATCH: nothing is recorded, no transform stays pending.
+ * With deferral on it is never queued: it flushes the queue (a failed flush returns its status, nothing is launched), then launches.
+ * The row's r lives in the per-stream workspace of the fused entry point, allocated on first use: call once outside any stream capture.
+ * in2 is ignored by a NORM except in the overlap rule above: a NORM whose struct still names an in2 that residual_out overlaps is
+ * refused, where the N = 1 form does not look at it. */
+int32_t tmac_hip_qgemm_fused_xf_rows_dev(const tmac_hip_weights* const* weights, int nmat, const void* B_dev, tmac_dtype_t act_dtype,
+                                         const tmac_hip_xform* xf, void* const* C_dev, tmac_dtype_t out_dtype, int N, void* stream);
+/* What the call above would run for N >= 2 rows on these matrices, under the current knobs (host only: plans, launches nothing):
+ * route 0 k_gemm_planes, 1 k_gemm_onehot, 3 k_gemv_rows, 7 the row loop; lut 1 the LUT image, 2 the half-table image.  The planner's
+ * refusals come back as from the call (the scope checks of the call itself are not repeated). */
+int32_t tmac_hip_debug_xf_rows_plan(const tmac_hip_weights* const* weights, int nmat, void* const* C_dev, int N, int32_t* route, int32_t* lut);
+/* Parity tap: the fp32 x [N][K] that the LUT builds of the call above consume (the row pass plus a store around the builders' own load;
+ * residual_out is written as the call writes it).  kind NORM or GLU; argument rules as above; synchronises the stream. */
+int32_t tmac_hip_debug_xf_rows(const void* B_dev, tmac_dtype_t act_dtype, const tmac_hip_xform* xf, int K, int N, float* x_out_dev,
+                               void* stream);
 /* Row-sharded chains (one process per GPU; weight ROWS split over the ranks).  While recording, the exchange step between
  * a call and the calls that need its output whole is recorded too -- tmac_hip_comm_allgather(comm, send, recv, ...) notes itself, or
  * tmac_hip_chain_record_gather where no communicator exists -- and inside the launch it becomes part of the hand-off: every rank's

@@ -185,6 +185,28 @@ extern "C" int ggml_tmac_hip_mul_mat_dev_xf(const struct tmac_ggml_tensor* const
     else { xf.residual = residual; xf.gamma = norm_weight; xf.eps = eps; xf.residual_out = residual_out; }
     return tmac_hip_qgemm_fused_xf_dev(wl, nw, x_dev, x_is_f32 ? TMAC_F32 : TMAC_F16, &xf, cl, dst_is_f32 ? TMAC_F32 : TMAC_F16, g_stream);
 }
+// ... and for n_rows rows of x (tmac_hip_qgemm_fused_xf_rows_dev): prefill or a small batch through the same hook
+extern "C" int ggml_tmac_hip_mul_mat_dev_xf_rows(const struct tmac_ggml_tensor* const* w, int nw, const void* x_dev, int x_is_f32, int kind,
+                                                 const void* in2_dev, const float* residual, const float* norm_weight, float eps, float* residual_out,
+                                                 void* const* dst_dev, int dst_is_f32, int n_rows) {
+    if (!g_ready) return fail("ggml_tmac_hip_init has not been called");
+    if (!w || nw < 1 || nw > 4 || !x_dev || !dst_dev || n_rows < 1) return fail("bad mul_mat_dev_xf_rows");
+    if (kind != TMAC_XF_NORM && kind != TMAC_XF_GLU) return fail("mul_mat_dev_xf_rows: kind must be 1 (norm) or 2 (glu)");
+    g_err[0] = 0;
+    const tmac_hip_weights* wl[4];
+    void* cl[4];
+    for (int i = 0; i < nw; ++i) {
+        if (!w[i] || !w[i]->extra || !dst_dev[i]) return fail("null tensor");
+        wl[i] = ((const Handle*)w[i]->extra)->w;
+        cl[i] = dst_dev[i];
+    }
+    tmac_hip_xform xf;
+    memset(&xf, 0, sizeof(xf));
+    xf.kind = kind;
+    if (kind == TMAC_XF_GLU) xf.in2 = in2_dev;
+    else { xf.residual = residual; xf.gamma = norm_weight; xf.eps = eps; xf.residual_out = residual_out; }
+    return tmac_hip_qgemm_fused_xf_rows_dev(wl, nw, x_dev, x_is_f32 ? TMAC_F32 : TMAC_F16, &xf, cl, dst_is_f32 ? TMAC_F32 : TMAC_F16, n_rows, g_stream);
+}
 extern "C" int ggml_tmac_hip_set_deferred(int on) { return tmac_hip_defer(on); }
 extern "C" int ggml_tmac_hip_flush(void) { return tmac_hip_flush(g_stream); }
 extern "C" int ggml_tmac_hip_synchronize(void) {

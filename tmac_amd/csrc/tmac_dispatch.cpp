@@ -123,6 +123,10 @@ static bool planes_image_fits(const tmac_hip_workspace* ws, int K) { return ws->
 //    k_gemv_rows call over all matrices.  Unified-scale matrices with K > PAIRS_ROW_MAX_K keep the route above (the row-wise pair build
 //    does not reach them).  Taps (tmac_hip_qgemm_partial_sums, tmac_hip_qgemm_fused_partial_sums) never take it; its own tap is
 //    tmac_hip_debug_rows_comb_sums.  Recording and deferral sit in front of the planner (fused_impl) and do not know the route.
+//  * A transformed call of N >= 2 rows (tmac_hip_qgemm_fused_xf_rows_dev) takes plan_fused's answer with two rules of its own
+//    (xf_rows_plan, at the fused entry point): R_GEMV_QUAD becomes R_ROW_LOOP behind LB_HALF_TABLES -- the transform lives in the N > 1
+//    LUT builders, so the image is built once and each matrix is planned again by plan_split -- and a plan that needs LB_ALL is refused.
+//    Routing of untransformed calls is untouched.
 static Plan plan_split(const tmac_hip_weights* w, const tmac_hip_workspace* ws, int N, bool tap) {
     Route r = R_REF_LAYOUT;
     if (g_knobs.variant != V_REF_LAYOUT && w->tiled_ok)
@@ -487,8 +491,20 @@ extern "C" int32_t tmac_hip_debug_gemm_image_read(const tmac_hip_workspace* ws, 
 // share LUT buffers) and grows on demand; tmac_hip_cache_clear() releases them.
 static std::map<std::pair<int, hipStream_t>, tmac_hip_workspace*> g_fused_ws;   // per (device, stream): the null stream exists on every device
 
+// A transformed call of N >= 2 rows (tmac_hip_qgemm_fused_xf_rows_dev) runs on a plan of plan_fused with two rules of its own: where the
+// planner answers R_GEMV_QUAD (k_gemv_quad with grid.y = N, each workgroup building its row's LUT) the call takes R_ROW_LOOP behind
+// LB_HALF_TABLES -- the transform sits in the pair build, k_gemv_quad copies the image (LUTSRC == 0) -- and a plan that needs LB_ALL (the
+// three-layout build has no XF instantiation) is refused.
+static Plan xf_rows_plan(Plan p) {
+    if (p.err) return p;
+    if (p.route == R_GEMV_QUAD) return planned(R_ROW_LOOP, LB_HALF_TABLES);
+    if (p.lut != LB_IMAGE && p.lut != LB_HALF_TABLES)
+        return refused(TMAC_HIP_E_NOMATCH, "a transformed call of several rows needs the LUT image or the half-table image alone; this plan builds every layout");
+    return p;
+}
+// xf: the call carries a vector transform (N >= 2, plan from xf_rows_plan): the row pass, then the planned LUT build's XF instantiation
 static int32_t fused_prefill(Plan p, const tmac_hip_weights* const* wl, int nmat, const void* B_dev, tmac_dtype_t act_dtype,
-                             void* const* C_list, tmac_dtype_t out_dtype, int N, hipStream_t st) {
+                             void* const* C_list, tmac_dtype_t out_dtype, int N, hipStream_t st, XfRowsArgs* xf = nullptr) {
     const Shape& s0 = wl[0]->s;
     tmac_hip_workspace* ws = nullptr;
     {
@@ -511,22 +527,36 @@ static int32_t fused_prefill(Plan p, const tmac_hip_weights* const* wl, int nmat
         }
         ws = slot;
     }
-    if (p.route == R_GEMM_PLANES && !planes_image_fits(ws, s0.K)) p = plan_fused(wl, C_list, nmat, N, false, false);   // (see image_fits at the planners)
+    if (p.route == R_GEMM_PLANES && !planes_image_fits(ws, s0.K)) {   // (see image_fits at the planners)
+        p = plan_fused(wl, C_list, nmat, N, false, false);
+        if (xf) {
+            p = xf_rows_plan(p);
+            if (p.err) return fail(p.err, p.msg, p.mat);
+        }
+    }
     int32_t rc = p.lut == LB_ALL ? TMAC_HIP_OK : check_lut_shape(ws, s0.K, N, s0.ags);
     if (rc) return rc;
     const int f16 = act_dtype == TMAC_F16;
     hipError_t e = hipSuccess;
+    if (xf) {
+        xf->r = ws->xf_r;
+        if (xf->kind == TMAC_XF_NORM && (xf->gamma || xf->residual_out)) {
+            e = launch_xf_rows(*xf, B_dev, f16, xf->gamma ? ws->xf_r : nullptr, s0.K, N, st);
+            if (e != hipSuccess) return fail(TMAC_HIP_E_RUNTIME, "transform row pass launch: %s", hipGetErrorString(e));
+        }
+    }
     if (p.lut == LB_IMAGE) {
         ws->K = 0; ws->N = 0; ws->gimg_valid = false;      // the other layouts of this workspace are not built
         e = s0.m_groups >= 1
-            ? launch_preprocess_pairs_row(B_dev, f16, ws->qlut_lds, ws->lut_scales, ws->lut_biases, s0.K, N, nullptr, nullptr, 0, ws->gimg, ws->gcol, ws->gNpad, st)
-            : launch_lut_image(B_dev, f16, ws->gimg, ws->gcol, s0.K, N, ws->gNpad, st);
+            ? launch_preprocess_pairs_row(B_dev, f16, ws->qlut_lds, ws->lut_scales, ws->lut_biases, s0.K, N, nullptr, nullptr, 0, ws->gimg, ws->gcol, ws->gNpad, st, xf)
+            : launch_lut_image(B_dev, f16, ws->gimg, ws->gcol, s0.K, N, ws->gNpad, st, xf);
         if (e != hipSuccess) return fail(TMAC_HIP_E_RUNTIME, "LUT image launch: %s", hipGetErrorString(e));
     } else if (p.lut == LB_HALF_TABLES) {
         ws->K = s0.K; ws->N = N; ws->ags = s0.ags; ws->qdev_u4_per_row = qdev_u4_for_K(s0.K);
+        if (xf) ws->gimg_valid = false;      // an image an earlier call left on the stream was not built from the transformed rows
         e = s0.ags == 64
-            ? launch_preprocess_pairs(B_dev, f16, ws->qlut_lds, ws->lut_scales, ws->lut_biases, s0.K, N, nullptr, nullptr, 0, st)
-            : launch_preprocess_pairs_row(B_dev, f16, ws->qlut_lds, ws->lut_scales, ws->lut_biases, s0.K, N, nullptr, nullptr, 0, nullptr, nullptr, 0, st);
+            ? launch_preprocess_pairs(B_dev, f16, ws->qlut_lds, ws->lut_scales, ws->lut_biases, s0.K, N, nullptr, nullptr, 0, st, xf)
+            : launch_preprocess_pairs_row(B_dev, f16, ws->qlut_lds, ws->lut_scales, ws->lut_biases, s0.K, N, nullptr, nullptr, 0, nullptr, nullptr, 0, st, xf);
         if (e != hipSuccess) return fail(TMAC_HIP_E_RUNTIME, "preprocess launch: %s", hipGetErrorString(e));
     } else {
         rc = tmac_hip_preprocessor_dev(ws, B_dev, act_dtype, s0.K, N, s0.ags, st);
@@ -650,6 +680,122 @@ extern "C" int32_t tmac_hip_qgemm_fused_xf_dev(const tmac_hip_weights* const* wl
     const hipError_t e = launch_gemv_quad_xf(fa, ft, wpq, strict, st);
     if (e == hipErrorInvalidValue) return fail(TMAC_HIP_E_NOMATCH, "no transformed GEMV kernel for this configuration (XF instantiations: (512,1), (512,2), (768,3), (1024,4))");
     if (e != hipSuccess) return fail(TMAC_HIP_E_RUNTIME, "transformed gemv launch: %s", hipGetErrorString(e));
+    return TMAC_HIP_OK;
+}
+
+// ---- fused entry point with a vector transform, N >= 1 rows ------------------------------------------------------------------
+// N = 1 and "no transform" are the existing calls themselves.  N >= 2: every refusal comes before the first launch; then the row pass
+// (k_xf_rows), the planned LUT build with the transform in its activation load, the planned kernel (fused_prefill).  Never recorded, never
+// queued.
+static int32_t xf_rows_check(const void* B_dev, tmac_dtype_t act_dtype, const tmac_hip_xform* xf, int K, int N, XfRowsArgs& xa) {
+    if (xf->kind < 0 || xf->kind > 2) return fail(TMAC_HIP_E_ARG, "unknown transform kind %d", xf->kind);
+    const bool norm = xf->kind == TMAC_XF_NORM;
+    if (!norm && !xf->in2) return fail(TMAC_HIP_E_ARG, "GLU needs a second vector");
+    if (norm && xf->residual == TMAC_XF_CARRY)
+        return fail(TMAC_HIP_E_ARG, "TMAC_XF_CARRY names a vector kept inside a chain launch: outside a recording the residual is a vector in memory");
+    memset(&xa, 0, sizeof(xa));
+    xa.kind = xf->kind; xa.eps = xf->eps;
+    xa.in2 = norm ? nullptr : xf->in2;
+    xa.residual = norm ? xf->residual : nullptr;
+    xa.gamma = norm ? xf->gamma : nullptr;
+    xa.residual_out = norm ? xf->residual_out : nullptr;
+    if (misaligned(B_dev, ACT_ALIGN)) return fail(TMAC_HIP_E_ARG, "B_dev must be %zu-byte aligned (the LUT build reads 16 bytes at a time)", ACT_ALIGN);
+    const struct { const void* p; const char* name; } vec[] = {{xa.in2, "in2"}, {xa.residual, "residual"}, {xa.gamma, "gamma"}, {xa.residual_out, "residual_out"}};
+    for (const auto& v : vec)
+        if (misaligned(v.p, XFORM_ALIGN)) return fail(TMAC_HIP_E_ARG, "transform vector %s must be %zu-byte aligned (read or written 16 bytes at a time)", v.name, XFORM_ALIGN);
+    if (xa.residual_out) {
+        // the builders read in and residual again after the row pass has written residual_out
+        const size_t NK = (size_t)N * K, act_bytes = NK * (act_dtype == TMAC_F16 ? 2 : 4);
+        const struct { const void* p; size_t n; const char* name; } rd[] = {{B_dev, act_bytes, "B_dev"}, {xa.residual, NK * 4, "residual"}, {xa.gamma, (size_t)K * 4, "gamma"},
+                                                                           {xf->in2, act_bytes, "in2"}};
+        for (const auto& r : rd)
+            if (ranges_overlap(xa.residual_out, NK * 4, r.p, r.n))
+                return fail(TMAC_HIP_E_ARG, "residual_out overlaps %s, which the LUT build reads after the row pass has written it (alternate between two buffers)", r.name);
+    }
+    return TMAC_HIP_OK;
+}
+
+extern "C" int32_t tmac_hip_qgemm_fused_xf_rows_dev(const tmac_hip_weights* const* wl, int nmat, const void* B_dev, tmac_dtype_t act_dtype,
+                                                    const tmac_hip_xform* xf, void* const* C_list, tmac_dtype_t out_dtype, int N, void* stream) {
+    hipStream_t st = (hipStream_t)stream;
+    const int32_t drc = ensure_device();
+    if (drc) return drc;
+    if (N == 1) return tmac_hip_qgemm_fused_xf_dev(wl, nmat, B_dev, act_dtype, xf, C_list, out_dtype, stream);
+    if (!xf || xf->kind == TMAC_XF_NONE) return fused_impl(wl, nmat, B_dev, act_dtype, C_list, out_dtype, N, nullptr, nullptr, st);
+    if (chain_recording()) {
+        chain_clear_xform();           // (a transform declared for the next recorded call was meant for this one)
+        return fail(TMAC_HIP_E_NOMATCH, "a transformed call of N=%d rows cannot be recorded: a chain takes one activation row", N);
+    }
+    if (!wl || !C_list || !B_dev || nmat < 1 || nmat > 4 || N < 1) return fail(TMAC_HIP_E_ARG, "bad fused arguments (1..4 matrices)");
+    for (int i = 0; i < nmat; ++i) {
+        if (!wl[i] || !C_list[i]) return fail(TMAC_HIP_E_ARG, "null matrix or output");
+        if (misaligned(C_list[i], out_align(out_dtype)))
+            return fail(TMAC_HIP_E_ARG, "C_dev[%d] must be %zu-byte aligned (four outputs are stored at a time)", i, out_align(out_dtype));
+    }
+    const Shape& s0 = wl[0]->s;
+    XfRowsArgs xa;
+    int32_t rc = xf_rows_check(B_dev, act_dtype, xf, s0.K, N, xa);
+    if (rc) return rc;
+    for (int i = 0; i < nmat; ++i) {
+        if (!same_lut(wl[i], wl[0]) || !same_quant(wl[i], wl[0]))
+            return fail(TMAC_HIP_E_ARG, "matrices fused in one launch must share K, bits and quantisation config");
+        if (xa.residual_out && ranges_overlap(xa.residual_out, (size_t)N * s0.K * 4, C_list[i], (size_t)N * wl[i]->s.Mw * (out_dtype == TMAC_F16 ? 2 : 4)))
+            return fail(TMAC_HIP_E_ARG, "residual_out overlaps C_dev[%d]", i);
+    }
+    // the scope: what the N = 1 form accepts, within the pair builds' reach
+    if (g_knobs.variant == V_REF_LAYOUT) return fail(TMAC_HIP_E_NOMATCH, "a transformed call does not run on the reference layout");
+    for (int i = 0; i < nmat; ++i) {
+        const tmac_hip_weights* w = wl[i];
+        if (layout_of(w->s) != L_QUAD || !w->tiled_ok || !gemv_quad_supported(w->s))
+            return fail(TMAC_HIP_E_NOMATCH, "matrix %d: a transformed call takes QUAD-layout weights of 1 to 4 bits with act groups of 64 or unified scales", i);
+        if (w->fa) return fail(TMAC_HIP_E_NOMATCH, "fast-aggregation weights do not take a transformed call");
+    }
+    if (s0.m_groups >= 1 && s0.K > PAIRS_ROW_MAX_K)
+        return fail(TMAC_HIP_E_NOMATCH, "unified scales: K=%d is beyond the row-wise pair build (K <= %d)", s0.K, PAIRS_ROW_MAX_K);
+    const Plan p = xf_rows_plan(plan_fused(wl, C_list, nmat, N, false));
+    if (p.err) return fail(p.err, p.msg, p.mat);
+    bind_thread_device();
+    const int32_t brc = defer_barrier();       // never queued: behind the calling thread's queue (B_dev may be a queued output)
+    if (brc) return brc;
+    return fused_prefill(p, wl, nmat, B_dev, act_dtype, C_list, out_dtype, N, st, &xa);
+}
+
+// What a transformed call of N >= 2 rows on these matrices would run, by the rules of the call itself (host only: plans, launches nothing).
+// route: 0 k_gemm_planes, 1 k_gemm_onehot, 3 k_gemv_rows, 7 the row loop (enum Route); lut: 1 the LUT image, 2 the half-table image.
+extern "C" int32_t tmac_hip_debug_xf_rows_plan(const tmac_hip_weights* const* wl, int nmat, void* const* C_list, int N, int32_t* route, int32_t* lut) {
+    if (!wl || !C_list || nmat < 1 || nmat > 4 || N < 2) return fail(TMAC_HIP_E_ARG, "bad plan arguments (1..4 matrices, N >= 2)");
+    const Plan p = xf_rows_plan(plan_fused(wl, C_list, nmat, N, false));
+    if (p.err) return fail(p.err, p.msg, p.mat);
+    if (route) *route = (int32_t)p.route;
+    if (lut) *lut = (int32_t)p.lut;
+    return TMAC_HIP_OK;
+}
+
+// The fp32 x [N][K] that the LUT builders of a transformed call consume: the row pass plus a store around the builders' own load
+// (xf_rows_x8).  residual_out is written as the call would write it.
+extern "C" int32_t tmac_hip_debug_xf_rows(const void* B_dev, tmac_dtype_t act_dtype, const tmac_hip_xform* xf, int K, int N, float* x_out_dev,
+                                          void* stream) {
+    hipStream_t st = (hipStream_t)stream;
+    const int32_t drc = ensure_device();
+    if (drc) return drc;
+    bind_thread_device();
+    const int32_t brc = defer_barrier();
+    if (brc) return brc;
+    if (!B_dev || !xf || !x_out_dev || K <= 0 || K % 64 || N < 1) return fail(TMAC_HIP_E_ARG, "bad tap arguments (K a multiple of 64, N >= 1)");
+    if (xf->kind == TMAC_XF_NONE) return fail(TMAC_HIP_E_ARG, "the tap shows a transform: kind NORM or GLU");
+    XfRowsArgs xa;
+    const int32_t rc = xf_rows_check(B_dev, act_dtype, xf, K, N, xa);
+    if (rc) return rc;
+    if (misaligned(x_out_dev, XFORM_ALIGN)) return fail(TMAC_HIP_E_ARG, "x_out_dev must be %zu-byte aligned", XFORM_ALIGN);
+    if (xa.residual_out && ranges_overlap(xa.residual_out, (size_t)N * K * 4, x_out_dev, (size_t)N * K * 4)) return fail(TMAC_HIP_E_ARG, "residual_out overlaps x_out_dev");
+    const int f16 = act_dtype == TMAC_F16;
+    DevBuf r;
+    if (xa.gamma) { HIP_TRY(r.alloc(sizeof(float) * (size_t)N)); xa.r = r.as<float>(); }
+    hipError_t e = hipSuccess;
+    if (xa.kind == TMAC_XF_NORM && (xa.gamma || xa.residual_out)) e = launch_xf_rows(xa, B_dev, f16, r.as<float>(), K, N, st);
+    if (e == hipSuccess) e = launch_xf_rows_tap(xa, B_dev, f16, x_out_dev, K, N, st);
+    const hipError_t es = hipStreamSynchronize(st);      // r is freed on return
+    if (e != hipSuccess || es != hipSuccess) return fail(TMAC_HIP_E_RUNTIME, "transform tap: %s", hipGetErrorString(e != hipSuccess ? e : es));
     return TMAC_HIP_OK;
 }
 

@@ -64,14 +64,18 @@ typedef float p16f_t __attribute__((ext_vector_type(16)));
 // (the halves are exact: what the reference multiplies by 0.5 in tbl.cc:464-526).  n runs over Npad rows (rows >= N repeat row N-1:
 // finite values, never stored).
 // ---------------------------------------------------------------------------------------------
-template <bool F16>
+// XF (tmac_hip_qgemm_fused_xf_rows_dev): x is the vector transform of the clamped row (xf_rows_x8: every operand at row nn) and the
+// kernel takes an XfRowsArgs behind its own arguments; off, there is no such argument and the code is what it was.
+template <bool F16, bool XF = false, class... XA>
 __global__ __launch_bounds__(256) void k_lut_image(const void* __restrict__ B, uint4* __restrict__ bimg, float* __restrict__ colv,
-                                                   int K, int N, int Npad) {
+                                                   int K, int N, int Npad, XA... xa) {
     const int kk = blockIdx.y;
     const int n = blockIdx.x * 32 + (threadIdx.x >> 3), p = threadIdx.x & 7;
     const int nn = min(n, N - 1);
     float x[8];
-    if (F16) {
+    if constexpr (XF) {
+        xf_rows_x8(xf_rows_arg(xa...), B, F16, K, nn, kk * 8 + p, x);
+    } else if (F16) {
         const uint4 v = reinterpret_cast<const uint4*>(reinterpret_cast<const __half*>(B) + (size_t)nn * K + kk * 64)[p];
         const uint32_t r[4] = {v.x, v.y, v.z, v.w};
 #pragma unroll
@@ -116,9 +120,14 @@ __global__ __launch_bounds__(256) void k_lut_image(const void* __restrict__ B, u
     }
 }
 
-hipError_t launch_lut_image(const void* B, int act_f16, void* bimg, float* colv, int K, int N, int Npad, hipStream_t st) {
+hipError_t launch_lut_image(const void* B, int act_f16, void* bimg, float* colv, int K, int N, int Npad, hipStream_t st, const XfRowsArgs* xf) {
     if (K % 64 != 0 || N < 1 || Npad < N || Npad % 64 != 0) return hipErrorInvalidValue;
     dim3 g(Npad / 32, K / 64), b(256);
+    if (xf) {
+        if (act_f16) hipLaunchKernelGGL((k_lut_image<true, true, XfRowsArgs>), g, b, 0, st, B, (uint4*)bimg, colv, K, N, Npad, *xf);
+        else hipLaunchKernelGGL((k_lut_image<false, true, XfRowsArgs>), g, b, 0, st, B, (uint4*)bimg, colv, K, N, Npad, *xf);
+        return hipGetLastError();
+    }
     if (act_f16) hipLaunchKernelGGL((k_lut_image<true>), g, b, 0, st, B, (uint4*)bimg, colv, K, N, Npad);
     else hipLaunchKernelGGL((k_lut_image<false>), g, b, 0, st, B, (uint4*)bimg, colv, K, N, Npad);
     return hipGetLastError();

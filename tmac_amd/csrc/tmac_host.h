@@ -65,6 +65,7 @@ struct tmac_hip_workspace {
     float* gcol = nullptr;       // 4 (maxK / 64) gNpad floats: its column values
     int gNpad = 0;
     bool gimg_valid = false;
+    float* xf_r = nullptr;       // fp32 [maxN]: 1 / rms per activation row of a transformed N > 1 call (k_xf_rows -> the XF LUT builders)
     int gimg_kind = 0;           // 1: row-wise image (one act group per row, k_gemm_planes_us) | 2: chunk-major image (act groups of 64, k_gemm_planes)
 };
 

@@ -752,16 +752,20 @@ constexpr bool QSCF16 = TMAC_QUAD_SCF16 != 0;   // weight scales stored as fp16 
 // biases bit-identical to lut_ctor.cc by the same argument as in k_gemv_quad).  k_preprocess keeps one workgroup per
 // act group with 16 of 64 lanes building tables and writes three layouts; this one writes the image only.
 // ---------------------------------------------------------------------------------------------
-template <bool F16, bool ALL>
+// XF (both pair builds; tmac_hip_qgemm_fused_xf_rows_dev): x is the vector transform of (row n, pair p) -- xf_rows_x8, tmac_quad_core.h --
+// and the kernel takes an XfRowsArgs behind its own arguments; off, there is no such argument and the code is what it was.
+template <bool F16, bool ALL, bool XF = false, class... XA>
 __global__ __launch_bounds__(256) void k_preprocess_pairs(const void* __restrict__ B, uint4* __restrict__ qlut_lds,
                                                           float* __restrict__ lut_scales, float* __restrict__ lut_biases,
                                                           int K, int tstride, uint4* __restrict__ qlut_ref,
-                                                          uint2* __restrict__ qlut_dev, size_t qdev_u4_per_row) {
+                                                          uint2* __restrict__ qlut_dev, size_t qdev_u4_per_row, XA... xa) {
     const int P = K / 8, G = K / 64, n = blockIdx.y;
     const int p = blockIdx.x * 256 + threadIdx.x;
     if (p >= P) return;                     // P % 8 == 0: the 8 lanes of an act group leave together
     float x[8];
-    if (F16) {
+    if constexpr (XF) {
+        xf_rows_x8(xf_rows_arg(xa...), B, F16, K, n, p, x);
+    } else if (F16) {
         const uint4 v = reinterpret_cast<const uint4*>(reinterpret_cast<const __half*>(B) + (size_t)n * K)[p];
         const uint32_t r[4] = {v.x, v.y, v.z, v.w};
 #pragma unroll
@@ -815,12 +819,12 @@ __global__ __launch_bounds__(256) void k_preprocess_pairs(const void* __restrict
 // activation row.  Pass 1: abs-max of the row and the 8-table chunk sums of lut_biases (neither depends on the scale);
 // then one lane walks the reference's sequential fp32 chain over the chunk sums (lut_ctor.cc:157,218) while the other
 // waves quantise their tables -- the build phase of k_gemv_quad's SM == 2 path as a kernel of its own.
-template <bool F16, bool ALL, int PT>
+template <bool F16, bool ALL, int PT, bool XF = false, class... XA>
 __global__ __launch_bounds__(PT) void k_preprocess_pairs_row(const void* __restrict__ B, uint4* __restrict__ qlut_lds,
                                                                float* __restrict__ lut_scales, float* __restrict__ lut_biases,
                                                                int K, int tstride, uint4* __restrict__ qlut_ref,
                                                                uint2* __restrict__ qlut_dev, size_t qdev_u4_per_row,
-                                                               uint4* __restrict__ bimg, float* __restrict__ colv, int Npad) {
+                                                               uint4* __restrict__ bimg, float* __restrict__ colv, int Npad, XA... xa) {
     extern __shared__ float prs[];          // [PT/64] wave maxima | [K/32] chunk sums
     constexpr int NWV = PT / 64;
     const int P = K / 8, n = blockIdx.x, tid = threadIdx.x, w = tid >> 6, lane = tid & 63;
@@ -835,7 +839,9 @@ __global__ __launch_bounds__(PT) void k_preprocess_pairs_row(const void* __restr
     for (int r = 0; r < NPR; ++r) {
         const int p = r * PT + tid;
         if (p < P) {
-            if (F16) {
+            if constexpr (XF) {
+                xf_rows_x8(xf_rows_arg(xa...), B, F16, K, n, p, x[r]);
+            } else if (F16) {
                 const uint4 v = reinterpret_cast<const uint4*>(reinterpret_cast<const __half*>(B) + (size_t)n * K)[p];
                 const uint32_t rr[4] = {v.x, v.y, v.z, v.w};
 #pragma unroll
@@ -912,13 +918,86 @@ __global__ __launch_bounds__(PT) void k_preprocess_pairs_row(const void* __restr
     }
 }
 
+// ---------------------------------------------------------------------------------------------
+// Vector transforms for N > 1 rows: the row pass in front of an XF LUT build.  One workgroup per activation row.  NORM only: t = fp32(in)
+// + residual (xf_rows_t8: the add the builders repeat), t to residual_out -- pair p of row n has exactly one writer, thread p mod 256 of
+// workgroup n -- and, with gamma, r[n] = rsq(fma(sum t^2, rcp(K), eps)), k_gemv_quad's expression.  The order of the sum is a function of K
+// alone: thread j adds its pairs j, j + 256, ... element by element (fma), the wave's 64 sums fold by xor 32, 16, ... 1, the four wave
+// sums are added in wave order.  Neither N, the row's index nor any launch knob enters: a row's r is the same in every call.
+// ---------------------------------------------------------------------------------------------
+constexpr int XF_ROWS_PT = 256;
+template <bool F16>
+__global__ __launch_bounds__(XF_ROWS_PT) void k_xf_rows(XfRowsArgs a, const void* __restrict__ B, float* __restrict__ r_out, int K) {
+    __shared__ float l_ss[XF_ROWS_PT / 64];
+    const int P = K / 8, n = blockIdx.x, tid = threadIdx.x;
+    float ss = 0.f;
+    for (int p = tid; p < P; p += XF_ROWS_PT) {
+        float t[8];
+        xf_rows_t8(a, B, F16, K, n, p, t);
+        if (a.residual_out != nullptr) {
+            float4* ro = reinterpret_cast<float4*>(a.residual_out + (size_t)n * K) + 2 * (size_t)p;
+            ro[0] = make_float4(t[0], t[1], t[2], t[3]);
+            ro[1] = make_float4(t[4], t[5], t[6], t[7]);
+        }
+#pragma unroll
+        for (int i = 0; i < 8; ++i) ss = __fmaf_rn(t[i], t[i], ss);
+    }
+    if (r_out == nullptr) return;           // (uniform)
+#pragma unroll
+    for (int off = 32; off >= 1; off >>= 1) ss = __fadd_rn(ss, __shfl_xor(ss, off, 64));
+    if ((tid & 63) == 0) l_ss[tid >> 6] = ss;
+    __syncthreads();
+    if (tid == 0) {
+        float tot = 0.f;
+#pragma unroll
+        for (int w = 0; w < XF_ROWS_PT / 64; ++w) tot = __fadd_rn(tot, l_ss[w]);
+        r_out[n] = __builtin_amdgcn_rsqf(__fmaf_rn(tot, __builtin_amdgcn_rcpf((float)K), a.eps));
+    }
+}
+// the fp32 x [N][K] the XF builders consume (tmac_hip_debug_xf_rows): a store around xf_rows_x8
+template <bool F16>
+__global__ __launch_bounds__(256) void k_xf_rows_tap(XfRowsArgs a, const void* __restrict__ B, float* __restrict__ x_out, int K) {
+    const int P = K / 8, n = blockIdx.y;
+    const int p = blockIdx.x * 256 + threadIdx.x;
+    if (p >= P) return;
+    float x[8];
+    xf_rows_x8(a, B, F16, K, n, p, x);
+    float4* xo = reinterpret_cast<float4*>(x_out + (size_t)n * K) + 2 * (size_t)p;
+    xo[0] = make_float4(x[0], x[1], x[2], x[3]);
+    xo[1] = make_float4(x[4], x[5], x[6], x[7]);
+}
+
+hipError_t launch_xf_rows(const XfRowsArgs& xf, const void* B, int act_f16, float* r_out, int K, int N, hipStream_t st) {
+    if (K % 64 != 0 || N < 1 || xf.kind != 1 || (r_out == nullptr && xf.residual_out == nullptr)) return hipErrorInvalidValue;
+    dim3 g(N), b(XF_ROWS_PT);
+    if (act_f16) hipLaunchKernelGGL((k_xf_rows<true>), g, b, 0, st, xf, B, r_out, K);
+    else hipLaunchKernelGGL((k_xf_rows<false>), g, b, 0, st, xf, B, r_out, K);
+    return hipGetLastError();
+}
+hipError_t launch_xf_rows_tap(const XfRowsArgs& xf, const void* B, int act_f16, float* x_out, int K, int N, hipStream_t st) {
+    if (K % 64 != 0 || N < 1 || N > 65535 || xf.kind < 1 || xf.kind > 2 || !x_out) return hipErrorInvalidValue;
+    dim3 g((K / 8 + 255) / 256, N), b(256);
+    if (act_f16) hipLaunchKernelGGL((k_xf_rows_tap<true>), g, b, 0, st, xf, B, x_out, K);
+    else hipLaunchKernelGGL((k_xf_rows_tap<false>), g, b, 0, st, xf, B, x_out, K);
+    return hipGetLastError();
+}
+
 hipError_t launch_preprocess_pairs_row(const void* B, int act_f16, void* qlut_lds, float* lut_scales, float* lut_biases, int K, int N,
-                                       int8_t* qlut_ref, void* qlut_dev, size_t qdev_u4_per_row, void* bimg, float* colv, int Npad, hipStream_t st) {
+                                       int8_t* qlut_ref, void* qlut_dev, size_t qdev_u4_per_row, void* bimg, float* colv, int Npad, hipStream_t st,
+                                       const XfRowsArgs* xf) {
     constexpr int PT = 512;
     if (K % 64 != 0 || N < 1 || K > 24 * PT || ((qlut_ref == nullptr) != (qlut_dev == nullptr))) return hipErrorInvalidValue;
     const int tstride = (((K / 32) + 15) & ~15) + 1;
     const size_t shmem = sizeof(float) * (PT / 64 + K / 32 + 1);
     dim3 g(N), b(PT);
+    if (xf) {
+        if (qlut_ref) return hipErrorInvalidValue;
+#define PLRX(F) hipLaunchKernelGGL((k_preprocess_pairs_row<F, false, PT, true, XfRowsArgs>), g, b, shmem, st, B, (uint4*)qlut_lds, lut_scales, lut_biases, K, tstride, \
+                                   (uint4*)nullptr, (uint2*)nullptr, (size_t)0, (uint4*)bimg, colv, Npad, *xf)
+        if (act_f16) PLRX(true); else PLRX(false);
+#undef PLRX
+        return hipGetLastError();
+    }
 #define PLR(F, A) hipLaunchKernelGGL((k_preprocess_pairs_row<F, A, PT>), g, b, shmem, st, B, (uint4*)qlut_lds, lut_scales, lut_biases, K, tstride, \
                                      (uint4*)qlut_ref, (uint2*)qlut_dev, qdev_u4_per_row, (uint4*)bimg, colv, Npad)
     if (qlut_ref) { if (act_f16) PLR(true, true); else PLR(false, true); }
@@ -928,10 +1007,18 @@ hipError_t launch_preprocess_pairs_row(const void* B, int act_f16, void* qlut_ld
 }
 
 hipError_t launch_preprocess_pairs(const void* B, int act_f16, void* qlut_lds, float* lut_scales, float* lut_biases, int K, int N,
-                                   int8_t* qlut_ref, void* qlut_dev, size_t qdev_u4_per_row, hipStream_t st) {
+                                   int8_t* qlut_ref, void* qlut_dev, size_t qdev_u4_per_row, hipStream_t st, const XfRowsArgs* xf) {
     if (K % 64 != 0 || N < 1 || ((qlut_ref == nullptr) != (qlut_dev == nullptr))) return hipErrorInvalidValue;
     const int tstride = (((K / 32) + 15) & ~15) + 1;
     dim3 g((K / 8 + 255) / 256, N), b(256);
+    if (xf) {
+        if (qlut_ref) return hipErrorInvalidValue;
+#define PLX(F) hipLaunchKernelGGL((k_preprocess_pairs<F, false, true, XfRowsArgs>), g, b, 0, st, B, (uint4*)qlut_lds, lut_scales, lut_biases, K, tstride, \
+                                  (uint4*)nullptr, (uint2*)nullptr, (size_t)0, *xf)
+        if (act_f16) PLX(true); else PLX(false);
+#undef PLX
+        return hipGetLastError();
+    }
 #define PL(F, A) hipLaunchKernelGGL((k_preprocess_pairs<F, A>), g, b, 0, st, B, (uint4*)qlut_lds, lut_scales, lut_biases, K, tstride, \
                                     (uint4*)qlut_ref, (uint2*)qlut_dev, qdev_u4_per_row)
     if (qlut_ref) { if (act_f16) PL(true, true); else PL(false, true); }

@@ -175,5 +175,60 @@ __device__ __forceinline__ float q_xor_max_f(float x) {
 #endif
 }
 
+// ---- vector transforms for N > 1 activation rows (XA = XfRowsArgs, tmac_kernels.h) ----------------------------------------
+// The 8 elements of (row n, pair p) of an [N][K] operand as fp32.
+__device__ __forceinline__ void xf_rows_ld8(const void* __restrict__ base, bool f16, int K, int n, int p, float (&x)[8]) {
+    if (f16) {
+        const uint4 v = reinterpret_cast<const uint4*>(reinterpret_cast<const __half*>(base) + (size_t)n * K)[p];
+        const uint32_t r[4] = {v.x, v.y, v.z, v.w};
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            const __half2 hh = *reinterpret_cast<const __half2*>(&r[i]);
+            x[2 * i] = __low2float(hh); x[2 * i + 1] = __high2float(hh);
+        }
+    } else {
+        const float4* src = reinterpret_cast<const float4*>(reinterpret_cast<const float*>(base) + (size_t)n * K) + 2 * (size_t)p;
+        const float4 a0 = src[0], a1 = src[1];
+        x[0] = a0.x; x[1] = a0.y; x[2] = a0.z; x[3] = a0.w; x[4] = a1.x; x[5] = a1.y; x[6] = a1.z; x[7] = a1.w;
+    }
+}
+// NORM: t = fp32(in) + residual of (row n, pair p) -- the row pass (k_xf_rows) and every builder form it with this one fp32 rn add
+template <class XA>
+__device__ __forceinline__ void xf_rows_t8(const XA& a, const void* __restrict__ B, bool f16, int K, int n, int p, float (&t)[8]) {
+    xf_rows_ld8(B, f16, K, n, p, t);
+    if (a.residual != nullptr) {
+        float u[8];
+        xf_rows_ld8(a.residual, false, K, n, p, u);
+#pragma unroll
+        for (int i = 0; i < 8; ++i) t[i] = __fadd_rn(t[i], u[i]);
+    }
+}
+// The transformed x[8] of (row n, pair p): what an XF instantiation of an N > 1 LUT builder (and the tap, k_xf_rows_tap) takes in place
+// of its activation load.  NORM: (t * gamma) * r[n], k_gemv_quad's association (gamma first), r[n] from k_xf_rows; without gamma x = t
+// untouched.  GLU: k_gemv_quad's expression with in2[n] in the activations' dtype.  n is the row EVERY operand is read at: a builder
+// that clamps padding rows passes the clamped row, so nothing is read beyond row N - 1.
+template <class XA>
+__device__ __forceinline__ void xf_rows_x8(const XA& a, const void* __restrict__ B, bool f16, int K, int n, int p, float (&x)[8]) {
+    if (a.kind == 1) {
+        xf_rows_t8(a, B, f16, K, n, p, x);
+        if (a.gamma != nullptr) {
+            float g[8];
+            xf_rows_ld8(a.gamma, false, K, 0, p, g);
+            const float r = a.r[n];
+#pragma unroll
+            for (int i = 0; i < 8; ++i) x[i] = __fmul_rn(__fmul_rn(x[i], g[i]), r);
+        }
+    } else {
+        float u[8];
+        xf_rows_ld8(B, f16, K, n, p, x);
+        xf_rows_ld8(a.in2, f16, K, n, p, u);
+        // silu(v) = v / (1 + exp(-v)): hardware exp2 and reciprocal, as in k_gemv_quad
+#pragma unroll
+        for (int i = 0; i < 8; ++i)
+            x[i] = __fmul_rn(__fmul_rn(x[i], __builtin_amdgcn_rcpf(__fadd_rn(1.0f, __expf(-x[i])))), u[i]);
+    }
+}
+template <class XA> __device__ __forceinline__ const XA& xf_rows_arg(const XA& a) { return a; }
+
 
 }  // namespace tmac

@@ -19,6 +19,7 @@ extern "C" int32_t tmac_hip_workspace_create(tmac_hip_workspace** out, int maxK,
     if (e == hipSuccess) e = hipMemset(ws->qlut_lds, 0x80, nl);
     if (e == hipSuccess) e = hipMalloc((void**)&ws->lut_scales, ns);
     if (e == hipSuccess) e = hipMalloc((void**)&ws->lut_biases, ns);
+    if (e == hipSuccess) e = hipMalloc((void**)&ws->xf_r, sizeof(float) * (size_t)maxN);
     if (maxN > 1) {
         ws->gNpad = (maxN + 63) & ~63;
         if (e == hipSuccess) e = hipMalloc(&ws->gimg, (size_t)2 * maxK * ws->gNpad);
@@ -43,6 +44,7 @@ extern "C" int32_t tmac_hip_workspace_free(tmac_hip_workspace* ws) {
     if (ws->qlut_lds) (void)hipFree(ws->qlut_lds);
     if (ws->lut_scales) (void)hipFree(ws->lut_scales);
     if (ws->lut_biases) (void)hipFree(ws->lut_biases);
+    if (ws->xf_r) (void)hipFree(ws->xf_r);
     if (ws->gimg) (void)hipFree(ws->gimg);
     if (ws->gcol) (void)hipFree(ws->gcol);
     if (ws->dump) (void)hipFree(ws->dump);

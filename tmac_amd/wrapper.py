@@ -469,6 +469,46 @@ class TMACGeMMWrapper:
         check(B.lib().tmac_hip_qgemm_fused_xf_dev(wa, n, _ptr(B_dev), act_dtype, C.byref(xf) if kind is not None else None, ca, out_dtype,
                                                   _stream(stream)))
 
+    @staticmethod
+    def _xform_rows(kind, in2, residual, gamma, eps, residual_out) -> "B.XForm":
+        xf = B.XForm()
+        xf.kind = {None: 0, "norm": 1, "glu": 2}[kind]
+        xf.in2 = _ptr(in2) if in2 is not None else None
+        xf.residual = 1 if residual is TMACGeMMWrapper.CARRY else (_ptr(residual) if residual is not None else None)
+        xf.gamma = _ptr(gamma) if gamma is not None else None
+        xf.eps = float(eps)
+        xf.residual_out = _ptr(residual_out) if residual_out is not None else None
+        xf.keep = 0
+        return xf
+
+    def fused_xf_rows(self, weights_list, B_dev, C_list, kind, N, in2=None, residual=None, gamma=None, eps: float = 1e-5, residual_out=None,
+                      act_dtype: Optional[int] = None, out_dtype: Optional[int] = None, stream=None) -> None:
+        """``fused_xf`` for N activation rows (tmac_hip_qgemm_fused_xf_rows_dev): B_dev and in2 [N][K], residual and residual_out fp32
+        [N][K], gamma fp32 [K] shared by the rows, C_list[i] [N][Mw_i].  N = 1 is ``fused_xf`` itself, kind None is ``fused`` itself;
+        for N >= 2 the transform is applied inside the LUT build of the route ``fused`` would take.  Not recordable for N >= 2."""
+        n = len(weights_list)
+        if act_dtype is None:
+            act_dtype = _dtype_code(B_dev)
+        if out_dtype is None:
+            out_dtype = _dtype_code(C_list[0])
+        xf = self._xform_rows(kind, in2, residual, gamma, eps, residual_out)
+        wa = (C.c_void_p * n)(*[w.handle.value for w in weights_list])
+        ca = (C.c_void_p * n)(*[_ptr(c) for c in C_list])
+        rec = getattr(self, "_recording", None)
+        if rec is not None and N == 1:      # kept alive with the chain
+            rec.append((list(weights_list), B_dev, list(C_list), in2, residual, gamma, residual_out))
+        check(B.lib().tmac_hip_qgemm_fused_xf_rows_dev(wa, n, _ptr(B_dev), act_dtype, C.byref(xf) if kind is not None else None, ca, out_dtype,
+                                                       N, _stream(stream)))
+
+    def xf_rows_tap(self, B_dev, x_out, kind, K, N, in2=None, residual=None, gamma=None, eps: float = 1e-5, residual_out=None,
+                    act_dtype: Optional[int] = None, stream=None) -> None:
+        """the fp32 x [N][K] that the LUT builds of ``fused_xf_rows`` consume, into ``x_out`` (tmac_hip_debug_xf_rows); residual_out is
+        written as the call writes it.  Synchronises the stream."""
+        if act_dtype is None:
+            act_dtype = _dtype_code(B_dev)
+        xf = self._xform_rows(kind, in2, residual, gamma, eps, residual_out)
+        check(B.lib().tmac_hip_debug_xf_rows(_ptr(B_dev), act_dtype, C.byref(xf), K, N, _ptr(x_out), _stream(stream)))
+
     def record_chain(self) -> "_ChainRecorder":
         """``with wr.record_chain() as rec: <the token's wr.fused(...) calls>`` — the calls are noted instead of launched;
         afterwards ``rec.chain.launch()`` executes all of them in ONE persistent kernel launch (tmac_hip_chain_*)."""
