@@ -187,7 +187,9 @@ int32_t tmac_hip_qgemm_fused_dev(const tmac_hip_weights* const* weights, int nma
  * built from a batch is cached by the batch's signature (matrices, pointers, dtypes; invalidated when weights are freed): a decode loop
  * pays for it once.  A batch that mixes configurations (bits, zero points, per-group / unified scales, scale or output dtype) becomes one
  * stream launch per configuration -- its calls are independent of each other; calls the persistent kernels do not cover, and configurations
- * with fewer than three calls (a stream launch costs ~10 us before its first byte), are launched one by one at the flush.  The caller must flush before it
+ * with fewer than three calls (a stream launch costs ~10 us before its first byte), are launched one by one at the flush.  Group size is no
+ * part of a configuration: a batch's calls of group size 64 join the stream launch of their configuration as those of 128 do, and that
+ * launch then runs the two-scale-group instantiation (the results of its group-size >= 128 calls are bit-identical either way).  The caller must flush before it
  * synchronises the stream or reads an output.  tmac_hip_defer_stats: flushes, cache hits, stream-mode launches, calls launched singly.
  * The cached recordings of a thread are released by tmac_hip_cache_clear() / tmac_hip_reset_state() called on that thread. */
 int32_t tmac_hip_defer(int on);
@@ -207,11 +209,14 @@ int32_t tmac_hip_defer_stats(uint64_t* flushes, uint64_t* cache_hits, uint64_t* 
  * Data flow is inferred from pointer identity: a call whose B_dev equals an earlier call's C_dev[i] consumes that output
  * inside the launch; any other B_dev must hold its activations when the launch starts.  Calls execute in recorded order.
  * An output buffer may be written by several calls (a decoder reuses its buffers layer after layer); the last one wins.
- * Scope: 1- to 4-bit QUAD-layout weights; per-group scales (group size >= 128, a power of two) with act groups of 64, or
+ * Scope: 1- to 4-bit QUAD-layout weights; per-group scales (group size >= 64, a power of two; the calls of a chain may differ in it)
+ * with act groups of 64, or
  * unified scales (m_groups >= 1, BitNet) with one act group per row; fp16 activations, or fp32 for vectors that are in memory before the launch; chained outputs fp16; one weight
  * width, scale flavour, scale dtype and zero-point setting per chain.  Anything else: -1 from tmac_hip_chain_end and
  * the caller keeps launching the calls one by one.  Results are bit-identical to tmac_hip_qgemm_fused_dev with
  * the same threads per workgroup and waves per row quad (tmac_hip_debug_quad_config(tmac_hip_chain_threads(), wpq)).
+ * A recording with a call of group size 64 runs the kernels' two-scale-group instantiation (a lane's two act groups of a lookup item
+ * then lie in two scale groups); the results of its calls of group size >= 128 are bit-identical to those of a recording without one.
  * A chain must not be launched concurrently with itself; the GPU must be able to hold one workgroup per CU (true unless
  * other work occupies CUs for the whole duration: every wait inside the kernel is bounded and reports through
  * tmac_hip_chain_status instead of hanging). */
@@ -354,7 +359,9 @@ int32_t tmac_hip_chain_threads(void);   /* threads per workgroup of k_decode_cha
  * recorded order instead of largest first), TMAC_STREAM_SPLIT=1 (one workgroup per CU), TMAC_STREAM_QW=0 | 1 (item form, below)).  Same integers
  * as every N = 1 path (tmac_hip_chain_set_tap); float outputs: see the return value 2 below.  Per-group scales, or unified scales
  * (BitNet: the row's scale and the sequential bias chain by k_lut_images_us, scale-final on exact int32 totals);
- * TMAC_CHAIN_STREAM=0 in the environment keeps the ordinary chain (A/B). */
+ * TMAC_CHAIN_STREAM=0 in the environment keeps the ordinary chain (A/B).  Group size >= 64: a stream with a call of group size 64 runs
+ * the two-scale-group instantiation of k_gemv_stream (both forms); its calls of group size >= 128 give the bits they give in a stream
+ * without one.  (3-bit streams with such a call keep one workgroup per CU.) */
 /* Returns 0 (k_decode_chain), 1 (stream mode) or 2: stream mode in the QUARTER-WALK form -- rows dealt in groups of 16, K walked in quarters
  * of a 64-unit step, so that a K with a ragged last step (11008, 3200, 8640 ...) does not spend whole lookup items on zero tables.  Every
  * 1- or 2-bit stream whose matrices all have rows % 16 == 0 takes it (it is the faster form there even without a ragged step); a 3- or

@@ -94,8 +94,23 @@ hipError_t launch_decode_chain_b1(const ChainArgs& a, bool zp, bool sc_f16, int 
 hipError_t launch_decode_chain_b2(const ChainArgs& a, bool zp, bool sc_f16, int sm, int grid, size_t lds_bytes, hipStream_t st, int* resident);
 hipError_t launch_decode_chain_b3(const ChainArgs& a, bool zp, bool sc_f16, int sm, int grid, size_t lds_bytes, hipStream_t st, int* resident);
 hipError_t launch_decode_chain_b4(const ChainArgs& a, bool zp, bool sc_f16, int sm, int grid, size_t lds_bytes, hipStream_t st, int* resident);
-inline hipError_t launch_decode_chain(const ChainArgs& a, int bits, bool zp, bool sc_f16, int sm, int grid, size_t lds_bytes, hipStream_t st,
+// g2: the instances with two scale groups per lane and item (tmac_chain_core.h; translation units of their own: tmac_chain.hip with
+// -DTMAC_CHAIN_G2_TU=1) -- per-group scales only; for launches that hold an op with scale groups of 64
+hipError_t launch_decode_chain_g2_b1(const ChainArgs& a, bool zp, bool sc_f16, int sm, int grid, size_t lds_bytes, hipStream_t st, int* resident);
+hipError_t launch_decode_chain_g2_b2(const ChainArgs& a, bool zp, bool sc_f16, int sm, int grid, size_t lds_bytes, hipStream_t st, int* resident);
+hipError_t launch_decode_chain_g2_b3(const ChainArgs& a, bool zp, bool sc_f16, int sm, int grid, size_t lds_bytes, hipStream_t st, int* resident);
+hipError_t launch_decode_chain_g2_b4(const ChainArgs& a, bool zp, bool sc_f16, int sm, int grid, size_t lds_bytes, hipStream_t st, int* resident);
+inline hipError_t launch_decode_chain(const ChainArgs& a, int bits, bool zp, bool sc_f16, int sm, bool g2, int grid, size_t lds_bytes, hipStream_t st,
                                       int* resident = nullptr) {
+    if (g2) {
+        switch (bits) {
+            case 1: return launch_decode_chain_g2_b1(a, zp, sc_f16, sm, grid, lds_bytes, st, resident);
+            case 2: return launch_decode_chain_g2_b2(a, zp, sc_f16, sm, grid, lds_bytes, st, resident);
+            case 3: return launch_decode_chain_g2_b3(a, zp, sc_f16, sm, grid, lds_bytes, st, resident);
+            case 4: return launch_decode_chain_g2_b4(a, zp, sc_f16, sm, grid, lds_bytes, st, resident);
+            default: return hipErrorInvalidValue;
+        }
+    }
     switch (bits) {
         case 1: return launch_decode_chain_b1(a, zp, sc_f16, sm, grid, lds_bytes, st, resident);
         case 2: return launch_decode_chain_b2(a, zp, sc_f16, sm, grid, lds_bytes, st, resident);
@@ -172,6 +187,7 @@ inline size_t stream_lds_bytes(int buf_u4, int nops, bool qw = false) {
     return b;
 }
 hipError_t launch_lut_images(const ChainOp* d_ops, int nops, int max_nst, int sm, bool sc_f16, hipStream_t st);
-hipError_t launch_gemv_stream(const StreamArgs& a, int bits, bool zp, bool sc_f16, int sm, bool qw, int grid, size_t lds_bytes, hipStream_t st);
+// g2: as launch_decode_chain's (translation units tmac_stream.hip with -DTMAC_STREAM_G2_TU=1, both forms)
+hipError_t launch_gemv_stream(const StreamArgs& a, int bits, bool zp, bool sc_f16, int sm, bool qw, bool g2, int grid, size_t lds_bytes, hipStream_t st);
 
 }  // namespace tmac

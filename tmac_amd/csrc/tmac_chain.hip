@@ -14,8 +14,8 @@
 // Arithmetic is that of k_gemv_quad (tmac_quad.hip) — same LUT build (lut_ctor.cc:120-215), same lookup + MFMA adder
 // (tbl.cc:445-462), same per-act-group scale chain (tbl.cc:479-526), same lane/wave decomposition for a given number of
 // waves per quad — so results are bit-identical to the per-launch path with 768-thread workgroups.
-// Scope: 1- to 4-bit weights, fp16 activations; SM = 0: per-group scales with act groups of 64 and scale groups >= 128 (the
-// GPTQ-style path, tbl.cc:323-532); SM = 2: unified scale(s), one act group per row, exact int32 totals and the scale-final
+// Scope: 1- to 4-bit weights, fp16 activations; SM = 0: per-group scales with act groups of 64 and scale groups >= 64 (the
+// GPTQ-style path, tbl.cc:323-532; a launch with an op of group size 64 runs the G2 instantiations, tmac_chain_core.h); SM = 2: unified scale(s), one act group per row, exact int32 totals and the scale-final
 // epilogue (BitNet: tbl.cc:536-630, qgemm.py:170-174,192-206).
 // Deadlock freedom: workgroups process ops in order and producers never wait for consumers, so by induction over the op
 // index everything completes provided all workgroups are resident; the grid is one workgroup per CU and the kernel's
@@ -89,11 +89,15 @@ __device__ __forceinline__ void c_ext3(const uint4* p0, const uint4* p1, const u
 // XF: the chain holds vector transforms (tmac_hip_chain_xform) -- a kernel of its own, so that chains without them keep their registers.
 // TAP: the parity tap (tmac_hip_chain_set_tap), an instance of its own next to XF (end of round 6: inside the XF instance its conditional
 // stores -- per item and act group -- cost the decoder pattern, which needs XF and sets no tap, 2.8 %: 1.060 -> 1.031 ms per token)
-template <int BITS, bool ZP, bool SCF16, int SM, bool XF, bool TAP = false>
+// G2: two scale groups per lane and item (tmac_chain_core.h), for launches that hold an op with scale groups of 64 -- instances of their own
+// (translation units tmac_chain_g2_b*), so that every other launch runs the kernels it ran before.
+template <int BITS, bool ZP, bool SCF16, int SM, bool XF, bool TAP = false, bool G2 = false>
 __global__ __launch_bounds__(CHAIN_FT) void k_decode_chain(ChainArgs a) {
     extern __shared__ __attribute__((aligned(16))) uint4 lds[];
     constexpr int FT = CHAIN_FT, NWV = CHAIN_NWV;
-    constexpr int RING = (BITS <= 2) ? 4 : 2;       // fragments per ring; two rings (current op / next op)
+    // fragments per ring.  The G2 instance with the transforms (XF) has no registers left for the fragments' second scale words at 2 to 4 bits
+    // (168 VGPRs at three waves per SIMD): its ring is shallower instead of spilling -- a spill behind the ring waits for the weights
+    constexpr int RING = (G2 && XF && BITS >= 2) ? ((BITS == 2) ? 2 : 1) : ((BITS <= 2) ? 4 : 2);
     const int tid = threadIdx.x, w = __builtin_amdgcn_readfirstlane(tid >> 6), lane = tid & 63;
     const int bx = blockIdx.x, gx = gridDim.x;
     const unsigned gx_inv = gx == 1 ? 0u : (unsigned)((0x100000000ull + (unsigned)gx - 1u) / (unsigned)gx);      // ceil(2^32 / gx); one workgroup: p mod 1 = 0 = bx below (2^32 does not fit)
@@ -174,7 +178,7 @@ __global__ __launch_bounds__(CHAIN_FT) void k_decode_chain(ChainArgs a) {
         return r;
     };
 
-    CFrag<BITS> ring[RING];
+    CFrag<BITS, G2> ring[RING];
     int parity = 0;
     for (int i = 0; i < a.nops; ++i) {
         const cop_ptr d = ops + i;
@@ -212,9 +216,10 @@ __global__ __launch_bounds__(CHAIN_FT) void k_decode_chain(ChainArgs a) {
         // (c_issue_full) log2 of a scale group's bytes per row quad; the lane's constant part of a scale offset; is the last 64-unit step ragged?
         constexpr int SCSH = (ZP ? 1 : 0) + (SCF16 ? 3 : 4);
         const uint32_t v_sc0 = (((uint32_t)(4 * (lane & 12) + 4 * (lane >> 4)) >> gsh) << SCSH) + (uint32_t)(lane & 3) * (uint32_t)((ZP ? 2 : 1) * (SCF16 ? 2 : 4));
+        const uint32_t v_sc1 = G2 ? (((uint32_t)(4 * (lane & 12) + 4 * (lane >> 4) + 2) >> gsh) << SCSH) + (uint32_t)(lane & 3) * (uint32_t)((ZP ? 2 : 1) * (SCF16 ? 2 : 4)) : 0u;
         const bool rag = (nu & 63) != 0;
         int i_it = 0, i_st = h, issued = 0;
-        auto issue_next = [&](CFrag<BITS>& f) __attribute__((always_inline)) {
+        auto issue_next = [&](CFrag<BITS, G2>& f) __attribute__((always_inline)) {
             if (issued < n_items) {
                 if (q_res != i_it) {
                     const int gqi = ro.q_lo + ro.qs + i_it * ro.ipi;
@@ -229,8 +234,8 @@ __global__ __launch_bounds__(CHAIN_FT) void k_decode_chain(ChainArgs a) {
                     q_woff = lq * nst * (BITS * 1024);
                     q_res = i_it;
                 }
-                if (!TMAC_CHAIN_ISSUE_FULL || (rag && i_st == nst - 1)) c_issue<BITS, ZP, SCF16, SM>(f, q_rs, q_woff, q_sc, nsg, gsh, nu, i_st, lane, lane16);
-                else c_issue_full<BITS, ZP, SCF16, SM>(f, q_rs, q_woff + i_st * (BITS * 1024), q_sc + ((size_t)((i_st << 6) >> gsh) << SCSH), v_sc0, lane16);
+                if (!TMAC_CHAIN_ISSUE_FULL || (rag && i_st == nst - 1)) c_issue<BITS, ZP, SCF16, SM, G2>(f, q_rs, q_woff, q_sc, nsg, gsh, nu, i_st, lane, lane16);
+                else c_issue_full<BITS, ZP, SCF16, SM, G2>(f, q_rs, q_woff + i_st * (BITS * 1024), q_sc + ((size_t)((i_st << 6) >> gsh) << SCSH), v_sc0, lane16, v_sc1);
                 ++issued;
                 i_st += wpq;
                 if (i_st >= nst) { i_st = h; ++i_it; }
@@ -800,7 +805,7 @@ __global__ __launch_bounds__(CHAIN_FT) void k_decode_chain(ChainArgs a) {
 #pragma unroll
                 for (int k = 0; k < RING; ++k) {
                     // (the instance with the extensions is also the parity tap's: ChainArgs::tap)
-                    c_compute<BITS, ZP, SCF16, SM, TAP, TMAC_CHAIN_IMG2 != 0>(ring[k], tab, tstride, l_ls, l_lb, c_st * 64, lane16, lk4, sel, k3, cacc, iacc,
+                    c_compute<BITS, ZP, SCF16, SM, TAP, TMAC_CHAIN_IMG2 != 0, G2>(ring[k], tab, tstride, l_ls, l_lb, c_st * 64, lane16, lk4, sel, k3, cacc, iacc,
                                                              (TAP && a.tap) ? a.tap + a.tap_off[i] + (size_t)(4 * (ro.q_lo + ro.qs + c_it * ipi) + (lane & 3)) * G : nullptr, G,
                                                              c_st * (16 * IMG2_STEP));
                     issue_next(ring[k]);               // refill this slot with the item RING places ahead, if there is one
@@ -836,9 +841,17 @@ __global__ __launch_bounds__(CHAIN_FT) void k_decode_chain(ChainArgs a) {
 #endif
 constexpr int CB = TMAC_CHAIN_BITS;
 
+// one translation unit per weight width and flavour: -DTMAC_CHAIN_G2_TU=1 holds the G2 instances (per-group scales only)
+#ifndef TMAC_CHAIN_G2_TU
+#define TMAC_CHAIN_G2_TU 0
+#endif
+constexpr bool CG2 = TMAC_CHAIN_G2_TU != 0;
+
 template <bool ZP, bool SCF16, int SM, bool XF, bool TAP>
 static hipError_t chain_launch_x(const ChainArgs& a, int grid, size_t lds_bytes, hipStream_t st, int* resident) {
-    auto* kern = &k_decode_chain<CB, ZP, SCF16, SM, XF, TAP>;
+    if constexpr (CG2 && SM != 0) return hipErrorInvalidValue;      // (unified scales have one scale per matrix: no G2 instance)
+    else {
+    auto* kern = &k_decode_chain<CB, ZP, SCF16, SM, XF, TAP, CG2>;
     if (lds_bytes > 64 * 1024) {
         hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);
         if (e != hipSuccess) return e;
@@ -847,6 +860,7 @@ static hipError_t chain_launch_x(const ChainArgs& a, int grid, size_t lds_bytes,
         return hipOccupancyMaxActiveBlocksPerMultiprocessor(resident, reinterpret_cast<const void*>(kern), CHAIN_FT, lds_bytes);
     hipLaunchKernelGGL(kern, dim3(grid), dim3(CHAIN_FT), lds_bytes, st, a);
     return hipGetLastError();
+    }
 }
 
 template <bool ZP, bool SCF16, int SM>
@@ -866,14 +880,12 @@ static hipError_t chain_launch_one(const ChainArgs& a, int grid, size_t lds_byte
         return sc_f16 ? chain_launch_one<false, true, 0>(a, grid, lds_bytes, st, resident)                                       \
                       : chain_launch_one<false, false, 0>(a, grid, lds_bytes, st, resident);                                     \
     }
-#if TMAC_CHAIN_BITS == 1
-TMAC_CHAIN_LAUNCHER(launch_decode_chain_b1)
-#elif TMAC_CHAIN_BITS == 2
-TMAC_CHAIN_LAUNCHER(launch_decode_chain_b2)
-#elif TMAC_CHAIN_BITS == 3
-TMAC_CHAIN_LAUNCHER(launch_decode_chain_b3)
+#if TMAC_CHAIN_G2_TU
+#define TMAC_CHAIN_ENTRY_(b) launch_decode_chain_g2_b##b
 #else
-TMAC_CHAIN_LAUNCHER(launch_decode_chain_b4)
+#define TMAC_CHAIN_ENTRY_(b) launch_decode_chain_b##b
 #endif
+#define TMAC_CHAIN_ENTRY(b) TMAC_CHAIN_ENTRY_(b)
+TMAC_CHAIN_LAUNCHER(TMAC_CHAIN_ENTRY(TMAC_CHAIN_BITS))
 
 }  // namespace tmac

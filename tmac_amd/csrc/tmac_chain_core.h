@@ -27,19 +27,41 @@ __device__ __forceinline__ T* uni(T* p) {
     return reinterpret_cast<T*>(((unsigned long long)hi << 32) | lo);
 }
 
-template <int BITS>
-struct CFrag {
+// G2 ("two scale groups per lane and item", SM == 0 only): a lane's 4 units of an item are two act groups of 64; with scale groups of 64 they
+// lie in two scale groups, and the fragment carries the second one's scale (, zero) in t0 / t1 (layout of s0 / s1).  A G2 instantiation
+// serves any op with gs >= 64: for gs >= 128 both words name the same group and every result is bit-identical to G2 = false, so one
+// launch may mix group sizes.  G2 = false is the code of before: every difference sits under `if constexpr (G2)`.
+template <bool G2> struct CFragG2 {};
+template <> struct CFragG2<true> { uint32_t t0, t1; };
+template <int BITS, bool G2 = false>
+struct CFrag : CFragG2<G2> {
     u32x4q wq[BITS];     // the lane's 16 bytes of every bit-plane block of the item (dword 4 j + c of the item = wq[j][c])
     uint32_t s0, s1;     // the lane's scale (, zero) of the step's scale group: fp16 pair in s0, or fp32 in s0 (, s1)
 };
+// the second scale word (pair) of a G2 fragment, fetched as s0 / s1 are
+template <bool ZP, bool SCF16>
+__device__ __forceinline__ void c_ld_scale2(const TMAC_GLOBAL char* p, uint32_t& r0, uint32_t& r1) {
+    r0 = 0; r1 = 0;
+    if (SCF16) {
+        if (ZP) r0 = *reinterpret_cast<const TMAC_GLOBAL uint32_t*>(p);
+        else r0 = *reinterpret_cast<const TMAC_GLOBAL unsigned short*>(p);
+    } else {
+        const TMAC_GLOBAL uint32_t* p32 = reinterpret_cast<const TMAC_GLOBAL uint32_t*>(p);
+        r0 = p32[0];
+        if (ZP) r1 = p32[1];
+    }
+}
 
 // weights of (global quad gq, step st) + the lane's scale: the epilogue role of a lane is row lane & 3, units
-// st*64 + 16g + 4*lg .. +3 (see k_gemv_quad); scale groups span >= 4 units, so one scale group per lane and step.
+// st*64 + 16g + 4*lg .. +3 (see k_gemv_quad); scale groups of >= 128 span >= 4 units, so one scale group per lane and step; G2 adds
+// the group of the lane's second act group (unit c0 + 2), clamped like the first, never predicated: groups past K meet zero tables
+// and zero LUT scales, and the load stays inside the quad's scale block.
 // Lanes whose unit lies past K skip the weight load (their LUT entries are zero tables: whatever the registers hold
 // contributes exactly 0) -- the zero padding of the last step is stored but never fetched.
-template <int BITS, bool ZP, bool SCF16, int SM>
-__device__ __forceinline__ void c_issue(CFrag<BITS>& f, __amdgpu_buffer_rsrc_t rs, int woff, const TMAC_GLOBAL char* scq, int nsg, int gsh, int nu,
+template <int BITS, bool ZP, bool SCF16, int SM, bool G2 = false>
+__device__ __forceinline__ void c_issue(CFrag<BITS, G2>& f, __amdgpu_buffer_rsrc_t rs, int woff, const TMAC_GLOBAL char* scq, int nsg, int gsh, int nu,
                                         int st, int lane, uint32_t lane16) {
+    static_assert(!G2 || SM == 0, "two scale groups per lane: per-group scales only");
     constexpr int per = ZP ? 2 : 1;
     constexpr int esz = SCF16 ? 2 : 4;
     const int c0 = 4 * (lane & 12) + 4 * (lane >> 4);
@@ -57,6 +79,10 @@ __device__ __forceinline__ void c_issue(CFrag<BITS>& f, __amdgpu_buffer_rsrc_t r
         }
     }
     f.s0 = r0; f.s1 = r1;
+    if constexpr (G2) {
+        const uint32_t sg2 = min((uint32_t)st * (64u >> gsh) + (uint32_t)((c0 + 2) >> gsh), (uint32_t)nsg - 1u);
+        c_ld_scale2<ZP, SCF16>(scq + (sg2 * 4 + (lane & 3)) * (per * esz), f.t0, f.t1);
+    }
     if (st * 64 + lane < nu) {
         // Buffer loads: resource (matrix base) and the fragment's byte offset in SGPRs, the lane's byte offset in a VGPR of
         // its own (lane16, made opaque at kernel entry).  No VALU instruction takes part: when the address arithmetic
@@ -74,9 +100,12 @@ __device__ __forceinline__ void c_issue(CFrag<BITS>& f, __amdgpu_buffer_rsrc_t r
 
 // The same for an item whose 64 units all lie below K (every item but a ragged last step): the lane's scale group is
 // (st * 64 >> gsh) + (c0 >> gsh) -- the first term is uniform and goes into the scale POINTER on the scalar unit (scq_item), the second is a
-// per-lane constant of the op (v_sc0, with the row's offset folded in): no vector arithmetic, no exec mask (round 6).
-template <int BITS, bool ZP, bool SCF16, int SM>
-__device__ __forceinline__ void c_issue_full(CFrag<BITS>& f, __amdgpu_buffer_rsrc_t rs, int soff, const TMAC_GLOBAL char* scq_item, uint32_t v_sc0, uint32_t lane16) {
+// per-lane constant of the op (v_sc0, with the row's offset folded in): no vector arithmetic, no exec mask (round 6).  G2: v_sc1 is the
+// same constant for the lane's second act group ((c0 + 2) >> gsh in place of c0 >> gsh).
+template <int BITS, bool ZP, bool SCF16, int SM, bool G2 = false>
+__device__ __forceinline__ void c_issue_full(CFrag<BITS, G2>& f, __amdgpu_buffer_rsrc_t rs, int soff, const TMAC_GLOBAL char* scq_item, uint32_t v_sc0, uint32_t lane16,
+                                             uint32_t v_sc1 = 0) {
+    static_assert(!G2 || SM == 0, "two scale groups per lane: per-group scales only");
     uint32_t r0 = 0, r1 = 0;
     if (SM == 0) {
         if (SCF16) {
@@ -89,6 +118,7 @@ __device__ __forceinline__ void c_issue_full(CFrag<BITS>& f, __amdgpu_buffer_rsr
         }
     }
     f.s0 = r0; f.s1 = r1;
+    if constexpr (G2) c_ld_scale2<ZP, SCF16>(scq_item + v_sc1, f.t0, f.t1);
 #pragma unroll
     for (int j = 0; j < BITS; ++j) f.wq[j] = __builtin_amdgcn_raw_buffer_load_b128(rs, (int)lane16, soff + j * 1024, 2 /* nt */);
 }
@@ -105,8 +135,9 @@ struct CItemOps {
     const TMAC_GLOBAL char* sc;     // first scale group of the quad
     uint32_t boff;                  // per lane: byte offset of its scale (, zero) word(s)
     uint32_t l16;                   // per lane: byte offset inside a 1 KB block
+    uint32_t boff2;                 // G2 instantiations only, per lane: byte offset of the scale (, zero) word(s) of its second act group
 };
-template <int BITS, bool ZP, bool SCF16, int SM>
+template <int BITS, bool ZP, bool SCF16, int SM, bool G2 = false>
 __device__ __forceinline__ void c_item_operands(CItemOps& o, __amdgpu_buffer_rsrc_t rs, int woff, const TMAC_GLOBAL char* scq, int nsg, int gsh, int nu,
                                                 int st, int lane, uint32_t lane16) {
     constexpr int per = ZP ? 2 : 1;
@@ -115,11 +146,16 @@ __device__ __forceinline__ void c_item_operands(CItemOps& o, __amdgpu_buffer_rsr
     const uint32_t sg = min((uint32_t)st * (64u >> gsh) + (uint32_t)(c0 >> gsh), (uint32_t)nsg - 1u);
     o.rs = rs; o.sc = scq;
     o.boff = (sg * 4 + (lane & 3)) * (per * esz);
+    if constexpr (G2) {
+        const uint32_t sg2 = min((uint32_t)st * (64u >> gsh) + (uint32_t)((c0 + 2) >> gsh), (uint32_t)nsg - 1u);
+        o.boff2 = (sg2 * 4 + (lane & 3)) * (per * esz);
+    }
     o.l16 = (st * 64 + lane < nu) ? lane16 : 0u;
     o.soff = woff + st * (BITS * 1024);
 }
-template <int BITS, bool ZP, bool SCF16, int SM>
-__device__ __forceinline__ void c_issue_static(CFrag<BITS>& f, const CItemOps& o) {
+template <int BITS, bool ZP, bool SCF16, int SM, bool G2 = false>
+__device__ __forceinline__ void c_issue_static(CFrag<BITS, G2>& f, const CItemOps& o) {
+    static_assert(!G2 || SM == 0, "two scale groups per lane: per-group scales only");
     uint32_t r0 = 0, r1 = 0;
     if (SM == 0) {
         if (SCF16) {
@@ -132,6 +168,7 @@ __device__ __forceinline__ void c_issue_static(CFrag<BITS>& f, const CItemOps& o
         }
     }
     f.s0 = r0; f.s1 = r1;
+    if constexpr (G2) c_ld_scale2<ZP, SCF16>(o.sc + o.boff2, f.t0, f.t1);      // (a dummy issues it too: the counted waits depend on the number of loads)
 #pragma unroll
     for (int j = 0; j < BITS; ++j) f.wq[j] = __builtin_amdgcn_raw_buffer_load_b128(o.rs, (int)o.l16, o.soff + j * 1024, 2 /* nt */);
 }
@@ -187,8 +224,10 @@ __device__ __forceinline__ void c_selectors(CSel<BITS>& sel, int lane) {
 // + lane16) instead of four address computations with a run-time row stride (one of them a quarter-rate 64-bit multiply-add).  The 65th
 // uint4 of a row is padding: the LUT build of k_decode_chain stores the four rows of a unit from four neighbouring lanes (16 bytes apart
 // in the banks, not on top of each other).  (TMAC_IMG2_SC: an A/B knob, below.)
-template <int BITS, bool ZP, bool SCF16, int SM, bool TAP = false, bool IMG2 = false>
-__device__ __forceinline__ void c_compute(const CFrag<BITS>& f, const uint4* tab, int tstride, const float* l_ls, const float* l_lb,
+// G2: act group gi = 0 takes the scale (, zero) of s0 / s1, gi = 1 that of t0 / t1, decoded alike; the fp32 operations and their order are
+// k_gemv_quad's for gs = 64 (compute_mfma: per act group fma(comb, ls / 2, lb / 2), fma(., scale, acc), fma(2 zero, lb / 2, .)).
+template <int BITS, bool ZP, bool SCF16, int SM, bool TAP = false, bool IMG2 = false, bool G2 = false>
+__device__ __forceinline__ void c_compute(const CFrag<BITS, G2>& f, const uint4* tab, int tstride, const float* l_ls, const float* l_lb,
                                           int ub, uint32_t lane16, uint32_t lk4, const CSel<BITS>& sel, uint32_t k3, float& cacc, int32_t (&iacc)[BITS],
                                           int32_t* tap_row = nullptr, int G = 0, int tb_off = 0) {
     // ub: first unit of the item's table rows (64 x step for a (quad, 64-unit step) item, 16 x quarter-step for k_gemv_stream's quarter-walk form,
@@ -242,6 +281,16 @@ __device__ __forceinline__ void c_compute(const CFrag<BITS>& f, const uint4* tab
             sc = __uint_as_float(f.s0);
             if (ZP) zr = __uint_as_float(f.s1);
         }
+        float sc2 = sc, zr2 = zr;           // G2: the second act group's
+        if constexpr (G2) {
+            if (SCF16) {
+                sc2 = __half2float(__ushort_as_half((unsigned short)(f.t0 & 0xffff)));
+                if (ZP) zr2 = __half2float(__ushort_as_half((unsigned short)(f.t0 >> 16)));
+            } else {
+                sc2 = __uint_as_float(f.t0);
+                if (ZP) zr2 = __uint_as_float(f.t1);
+            }
+        }
         // act groups ub / 2 + lk4 / 4 + {0, 1}: ls / 2 and lb / 2 (groups past K hold zeros)
         float2 hls2, hlb2;
         if constexpr (IMG2 && TMAC_IMG2_SC) {
@@ -261,9 +310,15 @@ __device__ __forceinline__ void c_compute(const CFrag<BITS>& f, const uint4* tab
                 if (tap_row && kk < G) tap_row[kk] = comb;
             }
             const float v = __fmaf_rn((float)comb, hls, hlb);
-            float cc = __fmaf_rn(v, sc, cacc);
-            if (ZP) cc = __fmaf_rn(__fadd_rn(zr, zr), hlb, cc);
-            cacc = cc;
+            if constexpr (G2) {
+                float cc = __fmaf_rn(v, gi ? sc2 : sc, cacc);
+                if (ZP) { const float z = gi ? zr2 : zr; cc = __fmaf_rn(__fadd_rn(z, z), hlb, cc); }
+                cacc = cc;
+            } else {
+                float cc = __fmaf_rn(v, sc, cacc);
+                if (ZP) cc = __fmaf_rn(__fadd_rn(zr, zr), hlb, cc);
+                cacc = cc;
+            }
         }
     }
 }

@@ -227,6 +227,7 @@ struct BuildKnobs {
     bool lpt = env_int("TMAC_STREAM_LPT", 1) != 0;                    // the schedule deals larger calls first; 0: in recorded order
     int split = env_int("TMAC_STREAM_SPLIT", 2);                      // workgroups per row range at most
     int split_bits = env_int("TMAC_STREAM_SPLIT_BITS", 3);            // the widest weights whose workgroups share a CU
+    bool split_bits_set = getenv("TMAC_STREAM_SPLIT_BITS") != nullptr;   // (plan_stream lowers the default for recordings with a call of group size 64)
     int poll_sleep = env_int("TMAC_CHAIN_POLL_SLEEP", 8), poll_delay = env_int("TMAC_CHAIN_POLL_DELAY", 4);            // ChainArgs' fields of these names
     int issue_first = env_int("TMAC_CHAIN_ISSUE_FIRST", -1), poll_mode = env_int("TMAC_CHAIN_POLL_MODE", 0), poll_grid = env_int("TMAC_CHAIN_POLL_GRID", 0);
     explicit BuildKnobs(int grid) {
@@ -387,8 +388,9 @@ static int32_t describe_ops(const std::vector<ChainRecOp>& rec, const ChainFlow&
                             i, CHAIN_US_MAX_GROUPS);
         } else {
             gu = s0.gs / 32;
-            if (s0.ags != 64 || s0.gs < 128 || (gu & (gu - 1)) || s0.K % s0.gs || s0.K % 64)
-                return fail(TMAC_HIP_E_NOMATCH, "op %zu: the decode chain covers per-group scales (group >= 128, power of two) with act groups of 64", i);
+            if (s0.ags != 64 || s0.gs < 64 || (gu & (gu - 1)) || s0.K % s0.gs || s0.K % 64)
+                return fail(TMAC_HIP_E_NOMATCH, "op %zu: the decode chain covers per-group scales (group >= 64, power of two) with act groups of 64", i);
+            if (s0.gs == 64) c.g2 = 1;          // gu = 2, gs_shift = 1: a lane's two act groups of an item lie in two scale groups
         }
         int nq = 0;
         for (size_t m = 0; m < r.w.size(); ++m) {
@@ -564,7 +566,7 @@ struct StreamPlan {
 };
 // The stream-mode form of independent ops (their k_decode_chain descriptors, by value), or nothing when that form does not fit: the
 // recording then stays with k_decode_chain as described.
-static std::optional<StreamPlan> plan_stream(std::vector<ChainOp> ops, int bits, int grid, const BuildKnobs& kn) {
+static std::optional<StreamPlan> plan_stream(std::vector<ChainOp> ops, int bits, bool g2, int grid, const BuildKnobs& kn) {
     StreamPlan p;
     p.ops = std::move(ops);
     const int nop = (int)p.ops.size(), ncls = p.ncls = kn.ncls;
@@ -629,7 +631,11 @@ static std::optional<StreamPlan> plan_stream(std::vector<ChainOp> ops, int bits,
     // Two workgroups are co-resident on a CU only with <= 64 VGPRs and <= 80 SGPRs each (measured, profiles/r05_stream_stamps.txt): 1- to
     // 3-bit weights fit with two fragments in flight per wave (3-bit: 4.06 -> 3.55 us on 4096 x 11008); 4-bit ones only with one,
     // which loses to one workgroup with two (5.15 against 4.68 us): they keep one workgroup per CU.  TMAC_STREAM_SPLIT_BITS: A/B.
-    if (kn.split >= 2 && bits <= kn.split_bits && vmax >= 2 && 2 * lds2 + 2048 <= 160 * 1024) { p.nsplit = 2; p.lds_bytes = lds2; }
+    // G2 (a call of group size 64): a fragment carries a second scale word, and the 3-bit instance stays within 64 VGPRs only with ONE
+    // fragment in flight -- the position 4-bit weights are in above, so such recordings keep one workgroup per CU as well (an explicit
+    // TMAC_STREAM_SPLIT_BITS still decides: A/B)
+    const int split_bits = (g2 && !kn.split_bits_set && kn.split_bits > 2) ? 2 : kn.split_bits;
+    if (kn.split >= 2 && bits <= split_bits && vmax >= 2 && 2 * lds2 + 2048 <= 160 * 1024) { p.nsplit = 2; p.lds_bytes = lds2; }
     for (int ns = 3; ns <= kn.split && ns <= 4; ++ns) {            // (A/B builds with -DTMAC_STREAM_NLW=6: more, smaller workgroups per CU)
         const size_t ldsn = stream_lds_bytes(p.buf_u4, (vmax + ns - 1) / ns, qw);
         if (p.nsplit == ns - 1 && vmax >= ns && ns * (ldsn + 1024) <= 160 * 1024) { p.nsplit = ns; p.lds_bytes = ldsn; }
@@ -691,7 +697,7 @@ static int32_t commit(tmac_hip_chain& c, const ChainLayout& lay) {
         memset(&probe, 0, sizeof(probe));
         probe.nops = 1;
         int resident = 0;
-        hipError_t e = launch_decode_chain(probe, c.bits, c.zp != 0, c.sc_f16 != 0, c.sm, c.grid, c.lds_bytes, nullptr, &resident);
+        hipError_t e = launch_decode_chain(probe, c.bits, c.zp != 0, c.sc_f16 != 0, c.sm, c.g2 != 0, c.grid, c.lds_bytes, nullptr, &resident);
         if (e == hipErrorInvalidValue) return fail(TMAC_HIP_E_NOMATCH, "no decode-chain kernel for this configuration");
         if (e != hipSuccess || resident < 1)
             return fail(TMAC_HIP_E_NOMATCH, "the decode chain's workgroup does not fit a compute unit (%s, %zu bytes of LDS)",
@@ -758,7 +764,7 @@ int32_t tmac_host::chain_build(const std::vector<ChainRecOp>& rec, const std::ve
     if ((rc = describe_ops(rec, flow, kn, *c, lay)) != TMAC_HIP_OK) return rc;
     if ((rc = check_hazards(rec, flow, c->ops)) != TMAC_HIP_OK) return rc;
     std::optional<StreamPlan> plan;
-    if (kn.stream && independent(rec, gat, flow, c->ops)) plan = plan_stream(c->ops, c->bits, c->grid, kn);
+    if (kn.stream && independent(rec, gat, flow, c->ops)) plan = plan_stream(c->ops, c->bits, c->g2 != 0, c->grid, kn);
     if (plan && (rc = commit_stream(*c, *plan)) != TMAC_HIP_OK) return rc;
     if ((rc = commit(*c, lay)) != TMAC_HIP_OK) return rc;
     // A workgroup reaches the polls of an op right after publishing its own share of the previous one: the first poll cannot

@@ -38,6 +38,8 @@ struct tmac_hip_chain {
     int ncls = 1, vmax = 0;           // the schedule: classes of row ranges, records per class
     bool qw = false;                  // k_gemv_stream's quarter-walk form (rows dealt in groups of four quads: q_end / q_per / q_extra of the ops count groups)
     int nsplit = 1;                   // workgroups per row range (two share a CU and take alternate ops when LDS and registers allow)
+    int g2 = 0;                       // 1 iff some op has scale groups of 64: both launchers then run the instances with two scale groups per lane
+                                      // and item (tmac_chain_core.h, G2); a recording without such an op launches the kernels it always did
 };
 
 namespace tmac_host {

@@ -11,8 +11,8 @@
 // The tables are COPIED from the workspace's half-table image exactly as k_gemv_quad does with LUTSRC == 0 (xor 0x80808080 for the MFMA
 // adder, scales halved, zero tables between nu and the end of the last step): no LUT is built here, the tables are today's bit for bit.
 // r_compute below is c_compute's non-IMG2 body with ONE difference: the weight scales arrive decoded and per act group, because a lane's two
-// act groups of a step lie in two scale groups when gs = 64 (c_issue / c_compute carry one scale group per lane and step: gs >= 128; the
-// second one is fetched beside the fragment).  No waits between workgroups, no spins, no atomics.  DESIGN.md 4.9.
+// act groups of a step lie in two scale groups when gs = 64 (the plain c_issue / c_compute carry one scale group per lane and step; their G2
+// instantiations carry both at compile time, this kernel decides at run time: the second one is fetched beside the fragment).  No waits between workgroups, no spins, no atomics.  DESIGN.md 4.9.
 #include <hip/hip_runtime.h>
 #include <hip/hip_fp16.h>
 #include <stdint.h>

@@ -31,15 +31,19 @@
 
 #include "tmac_chain_core.h"
 
-// Two translation units (build time): -DTMAC_STREAM_QW_TU=0 (default) holds the LUT-image kernels and the (quad x 64 units) form of
-// k_gemv_stream, =1 its quarter-walk form.
+// Four translation units (build time): -DTMAC_STREAM_QW_TU=0 (default) holds the LUT-image kernels and the (quad x 64 units) form of
+// k_gemv_stream, =1 its quarter-walk form; with -DTMAC_STREAM_G2_TU=1 each holds the G2 instances of its form instead (two scale groups
+// per lane and item, tmac_chain_core.h: launches with a call of group size 64; per-group scales only) and nothing else.
 #ifndef TMAC_STREAM_QW_TU
 #define TMAC_STREAM_QW_TU 0
+#endif
+#ifndef TMAC_STREAM_G2_TU
+#define TMAC_STREAM_G2_TU 0
 #endif
 
 namespace tmac {
 
-#if !TMAC_STREAM_QW_TU
+#if !TMAC_STREAM_QW_TU && !TMAC_STREAM_G2_TU
 // ---------------------------------------------------------------------------------------------
 // LUT images: block (x, y) builds pairs 256 x .. 256 x + 255 (= the 64 units of step x) of op y -- the build phase of k_gemv_quad /
 // k_preprocess_pairs (lut_ctor.cc:120-215,240-256) writing what k_gemv_stream's LUT buffer holds, in the STEP-MAJOR layout (round 6;
@@ -183,7 +187,7 @@ hipError_t launch_lut_images(const ChainOp* d_ops, int nops, int max_nst, int sm
     else hipLaunchKernelGGL(k_lut_images, dim3(max_nst, nops), dim3(256), 0, st, d_ops);
     return hipGetLastError();
 }
-#endif   // !TMAC_STREAM_QW_TU
+#endif   // !TMAC_STREAM_QW_TU && !TMAC_STREAM_G2_TU
 
 // ---------------------------------------------------------------------------------------------
 #ifndef TMAC_STREAM_KO
@@ -212,7 +216,13 @@ hipError_t launch_lut_images(const ChainOp* d_ops, int nops, int max_nst, int sm
 // steps instead of four.  Integers are the same integers (tapped); the fp32 partial sums of a row are added in another order than
 // k_gemv_quad's, so per-group-scale outputs are specified to the oracle's tolerance (<= 1e-3, measured <= 2e-5) like every N = 1 kernel
 // against the reference, and no longer bit-identical to the stand-alone launch; unified-scale outputs stay bit-identical (exact totals).
-template <int BITS, bool ZP, bool SCF16, int RING, int MINW, int SM, bool TAP, bool QW>
+// G2: two scale groups per lane and item (tmac_chain_core.h).  In both forms the lane's second act group starts at unit c0 + 2 of the item
+// (c0: its first unit inside the step / quarter), so the second scale word is the first one's expression with c0 + 2.  c0 is a multiple of
+// 4, so (c0 + 2) >> gs_shift = (c0 >> gs_shift) + d with d = 1 for groups of 64 and 0 for larger ones: uniform per op, and the second word's
+// offset is the first one's plus d scale groups (i_sc2, bytes) -- one add per item, no per-lane state beyond v_sc0; a ragged last step /
+// quarter clamps the second group like the first.  A dummy item issues the second load too -- the counted waits depend on the number of
+// loads per item.
+template <int BITS, bool ZP, bool SCF16, int RING, int MINW, int SM, bool TAP, bool QW, bool G2 = false>
 __global__ __launch_bounds__(STREAM_FT, MINW) TMAC_STREAM_ATTR void k_gemv_stream(StreamArgs a) {
     extern __shared__ __attribute__((aligned(16))) uint4 lds[];
     constexpr int NWV = STREAM_NLW;                     // lookup waves; wave NWV is the loader
@@ -367,7 +377,7 @@ __global__ __launch_bounds__(STREAM_FT, MINW) TMAC_STREAM_ATTR void k_gemv_strea
     };
 
     // ---- the issue cursor: this wave's items of ops 0, 1, ... in order, RING items ahead of the lookups ----
-    CFrag<BITS> ring[RING];
+    CFrag<BITS, G2> ring[RING];
     const __amdgpu_buffer_rsrc_t null_rs = __builtin_amdgcn_make_buffer_rsrc(static_cast<uint4*>(nullptr), (short)0, 0, 0x00020000);   // every lane out of range: zeros, no fetch
     const TMAC_GLOBAL char* ops_g = as_global(reinterpret_cast<const char*>(a.ops));     // a dummy's scale word comes from a mapped address
     const uint32_t dummy_boff = (uint32_t)(lane & 3) * (uint32_t)((ZP ? 2 : 1) * (SCF16 ? 2 : 4));
@@ -387,8 +397,9 @@ __global__ __launch_bounds__(STREAM_FT, MINW) TMAC_STREAM_ATTR void k_gemv_strea
     int q_scstride = 0;
     const uint32_t c0 = QW ? (uint32_t)(4 * (lane >> 4)) : (uint32_t)(4 * (lane & 12) + 4 * (lane >> 4));       // the lane's first unit inside a step / quarter (c_issue)
     uint32_t c0g = c0;                                                       // c0 >> gs_shift of the issue cursor's op
+    int i_sc2 = 0;                                                           // G2, per op: bytes from the lane's first scale word to that of its second act group (one group | 0)
     constexpr int SC_SHIFT = (ZP ? 1 : 0) + (SCF16 ? 3 : 4);               // log2 of a scale group's bytes per row quad: 4 rows x (scale [, zero]) x 2 | 4
-    auto refill = [&](CFrag<BITS>& f) __attribute__((always_inline)) {
+    auto refill = [&](CFrag<BITS, G2>& f) __attribute__((always_inline)) {
         while (i_left == 0 && i_op < nops) {            // enter the next op in which this wave has items
             ++i_op;
             if (i_op < nops) {
@@ -402,6 +413,7 @@ __global__ __launch_bounds__(STREAM_FT, MINW) TMAC_STREAM_ATTR void k_gemv_strea
                 i_nsg1 = rc[SR_NSG] - 1; i_gsh = rc[SR_GSH]; i_nu = rc[SR_NU];
                 q_scstride = rc[SR_NSG] << SC_SHIFT;
                 c0g = c0 >> i_gsh;
+                if constexpr (G2) i_sc2 = i_gsh < 2 ? 1 << SC_SHIFT : 0;
                 if constexpr (QW) {
                     i_n64 = (rc[SR_TSTRIDE] - 1) >> 6;                   // 64-unit steps per quad in the weight layout
                     v_wq = (uint32_t)(lane >> 4) * (uint32_t)(i_n64 * (BITS * 1024)) + lane16;
@@ -443,15 +455,20 @@ __global__ __launch_bounds__(STREAM_FT, MINW) TMAC_STREAM_ATTR void k_gemv_strea
                 const uint32_t sg = min((uint32_t)(ub >> i_gsh) + c0g, (uint32_t)i_nsg1);
                 io.sc = q_sc;
                 io.boff = QW ? (sg << SC_SHIFT) + v_scq : ((sg << SC_SHIFT) | dummy_boff);
+                if constexpr (G2) {
+                    const uint32_t sg2 = min((uint32_t)(ub >> i_gsh) + c0g + (uint32_t)(i_sc2 >> SC_SHIFT), (uint32_t)i_nsg1);
+                    io.boff2 = QW ? (sg2 << SC_SHIFT) + v_scq : ((sg2 << SC_SHIFT) | dummy_boff);
+                }
                 io.l16 = QW ? v_wq : ((lane < i_nu - ub) ? lane16 : 0u);
             } else {
                 io.sc = q_sc + ((size_t)(ub >> i_gsh) << SC_SHIFT);
                 io.boff = v_sc0;
+                if constexpr (G2) io.boff2 = v_sc0 + (uint32_t)i_sc2;
                 io.l16 = QW ? v_wq : lane16;
             }
             io.soff = QW ? q_woff + (i_st >> 2) * (BITS * 1024) + (i_st & 3) * 256 : q_woff + i_st * (BITS * 1024);
-        } else { io.rs = null_rs; io.soff = 0; io.sc = ops_g; io.boff = dummy_boff; io.l16 = 0u; }      // behind the last op: keeps the FIFO's depth
-        c_issue_static<BITS, ZP, SCF16, SM>(f, io);
+        } else { io.rs = null_rs; io.soff = 0; io.sc = ops_g; io.boff = dummy_boff; io.l16 = 0u; if constexpr (G2) io.boff2 = dummy_boff; }      // behind the last op: keeps the FIFO's depth
+        c_issue_static<BITS, ZP, SCF16, SM, G2>(f, io);
         if (real) {
             --i_left;
             i_st += i_wpq;
@@ -571,14 +588,14 @@ __global__ __launch_bounds__(STREAM_FT, MINW) TMAC_STREAM_ATTR void k_gemv_strea
             if (!done) {
 #if defined(TMAC_STREAM_STAMPS) && TMAC_STREAM_STAMPS >= 2
                 {   // the wait the compiler places in front of the slot's first lookup, made explicit: the slot's loads are older than the other slots' refills
-                    constexpr int L = BITS + (SCF16 || !ZP ? 1 : 2);
+                    constexpr int L = BITS + (G2 ? 2 : 1) * (SCF16 || !ZP ? 1 : 2);      // loads per item: G2 fetches a second scale word (pair)
                     asm volatile("s_waitcnt vmcnt(%0)" :: "n"((RING - 1) * L) : "memory");
                     TMAC_ST(0);
                     if (lane == 0) (void)__hip_atomic_fetch_add(&t_lds[6], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
                 }
 #endif
                 if (TMAC_STREAM_KO & 8) cacc += __uint_as_float(ring[k].wq[0].x ^ ring[k].wq[BITS - 1].w ^ ring[k].s0); else
-                c_compute<BITS, ZP, SCF16, SM, TAP, true>(ring[k], tab, tstride, l_ls, l_lb, QW ? c_st * 16 : c_st * 64, lane16, lk4, sel, k3, cacc, iacc,
+                c_compute<BITS, ZP, SCF16, SM, TAP, true, G2>(ring[k], tab, tstride, l_ls, l_lb, QW ? c_st * 16 : c_st * 64, lane16, lk4, sel, k3, cacc, iacc,
                                                           (TAP && t_base) ? t_base + (size_t)(RPW * (t_gq0 + c_it * t_ipi) + (lane & (RPW - 1))) * t_G : nullptr, t_G,
                                                           QW ? (c_st >> 2) * (16 * IMG2_STEP) + (c_st & 3) * 256 : c_st * (16 * IMG2_STEP));
                 asm volatile("" : "+v"(cacc));        // the item's scale chain ends before the slot is refilled (the scale word keeps its register)
@@ -621,20 +638,27 @@ __global__ __launch_bounds__(STREAM_FT, MINW) TMAC_STREAM_ATTR void k_gemv_strea
 
 }
 
-template <int BITS, bool QWF>
+// Ring depths.  Two workgroups share a CU only with <= 64 VGPRs per wave; a G2 fragment is one or two registers larger, and where the
+// ring of the nsplit >= 2 instance would pass 64 with it the ring gets shallower (never a spill: a spill behind the ring waits for the
+// weights) -- 3-bit G2: one fragment, as 4-bit weights have at nsplit >= 2.  4-bit G2 has no ring left to give: a launch with nsplit >= 2
+// runs the one-workgroup instance there (the workgroups then do not share a CU; nothing in the kernel depends on that).  The host's
+// nsplit rule for G2 follows (plan_stream).
+template <int BITS, bool QWF, bool G2F>
 static hipError_t stream_launch_b(const StreamArgs& a, bool zp, bool sc_f16, int sm, int grid, size_t lds_bytes, hipStream_t st) {
-    constexpr int R2 = (BITS <= 3) ? 2 : 1;      // two workgroups per CU: <= 64 VGPRs
+    constexpr int R2 = G2F ? ((BITS <= 2) ? 2 : 1) : ((BITS <= 3) ? 2 : 1);      // two workgroups per CU: <= 64 VGPRs
     constexpr int R1 = (BITS <= 2) ? 4 : 2;      // one workgroup per CU: ring depth 2..8 measured flat (profiles/r05_stream_knockouts.txt)
 #define TMAC_SL2(Z, H, R, MW, S) do { \
-        auto* kern = a.tap ? &k_gemv_stream<BITS, Z, H, R1, 4, S, true, QWF> : &k_gemv_stream<BITS, Z, H, R, MW, S, false, QWF>; \
+        auto* kern = a.tap ? &k_gemv_stream<BITS, Z, H, R1, 4, S, true, QWF, G2F> : &k_gemv_stream<BITS, Z, H, R, MW, S, false, QWF, G2F>; \
         if (lds_bytes > 64 * 1024) { \
             hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes); \
             if (e != hipSuccess) return e; \
         } \
         hipLaunchKernelGGL(kern, dim3(grid * a.nsplit), dim3(STREAM_FT), lds_bytes, st, a); \
         return hipGetLastError(); } while (0)
-#define TMAC_SL(Z, H, S) do { if (a.nsplit >= 2) TMAC_SL2(Z, H, R2, 8, S); else TMAC_SL2(Z, H, R1, 4, S); } while (0)
-    if (sm == 2) { if (sc_f16) TMAC_SL(false, true, 2); else TMAC_SL(false, false, 2); }      // unified scales: no zero points (qgemm.py:170-174)
+#define TMAC_SL(Z, H, S) do { if constexpr (!(G2F && BITS == 4)) { if (a.nsplit >= 2) TMAC_SL2(Z, H, R2, 8, S); } TMAC_SL2(Z, H, R1, 4, S); } while (0)
+    if constexpr (!G2F) {
+        if (sm == 2) { if (sc_f16) TMAC_SL(false, true, 2); else TMAC_SL(false, false, 2); }      // unified scales: no zero points (qgemm.py:170-174)
+    } else if (sm != 0) return hipErrorInvalidValue;
     if (zp) { if (sc_f16) TMAC_SL(true, true, 0); else TMAC_SL(true, false, 0); }
     if (sc_f16) TMAC_SL(false, true, 0);
     TMAC_SL(false, false, 0);
@@ -642,29 +666,37 @@ static hipError_t stream_launch_b(const StreamArgs& a, bool zp, bool sc_f16, int
 #undef TMAC_SL2
 }
 
-#if TMAC_STREAM_QW_TU
-hipError_t launch_gemv_stream_qw(const StreamArgs& a, int bits, bool zp, bool sc_f16, int sm, int grid, size_t lds_bytes, hipStream_t st) {
-    switch (bits) {
-        case 1: return stream_launch_b<1, true>(a, zp, sc_f16, sm, grid, lds_bytes, st);
-        case 2: return stream_launch_b<2, true>(a, zp, sc_f16, sm, grid, lds_bytes, st);
-        case 3: return stream_launch_b<3, true>(a, zp, sc_f16, sm, grid, lds_bytes, st);
-        case 4: return stream_launch_b<4, true>(a, zp, sc_f16, sm, grid, lds_bytes, st);
-        default: return hipErrorInvalidValue;
+#define TMAC_STREAM_BITS_SWITCH(QWF, G2F) \
+    switch (bits) { \
+        case 1: return stream_launch_b<1, QWF, G2F>(a, zp, sc_f16, sm, grid, lds_bytes, st); \
+        case 2: return stream_launch_b<2, QWF, G2F>(a, zp, sc_f16, sm, grid, lds_bytes, st); \
+        case 3: return stream_launch_b<3, QWF, G2F>(a, zp, sc_f16, sm, grid, lds_bytes, st); \
+        case 4: return stream_launch_b<4, QWF, G2F>(a, zp, sc_f16, sm, grid, lds_bytes, st); \
+        default: return hipErrorInvalidValue; \
     }
+#if TMAC_STREAM_QW_TU && TMAC_STREAM_G2_TU
+hipError_t launch_gemv_stream_qw_g2(const StreamArgs& a, int bits, bool zp, bool sc_f16, int sm, int grid, size_t lds_bytes, hipStream_t st) {
+    TMAC_STREAM_BITS_SWITCH(true, true)
+}
+#elif TMAC_STREAM_G2_TU
+hipError_t launch_gemv_stream_g2(const StreamArgs& a, int bits, bool zp, bool sc_f16, int sm, int grid, size_t lds_bytes, hipStream_t st) {
+    TMAC_STREAM_BITS_SWITCH(false, true)
+}
+#elif TMAC_STREAM_QW_TU
+hipError_t launch_gemv_stream_qw(const StreamArgs& a, int bits, bool zp, bool sc_f16, int sm, int grid, size_t lds_bytes, hipStream_t st) {
+    TMAC_STREAM_BITS_SWITCH(true, false)
 }
 #else
 hipError_t launch_gemv_stream_qw(const StreamArgs& a, int bits, bool zp, bool sc_f16, int sm, int grid, size_t lds_bytes, hipStream_t st);
-hipError_t launch_gemv_stream(const StreamArgs& a, int bits, bool zp, bool sc_f16, int sm, bool qw, int grid, size_t lds_bytes, hipStream_t st) {
-    if (a.nops < 1 || grid < 1 || a.nsplit < 1 || a.nsplit > 4 || (sm != 0 && sm != 2)) return hipErrorInvalidValue;
+hipError_t launch_gemv_stream_g2(const StreamArgs& a, int bits, bool zp, bool sc_f16, int sm, int grid, size_t lds_bytes, hipStream_t st);
+hipError_t launch_gemv_stream_qw_g2(const StreamArgs& a, int bits, bool zp, bool sc_f16, int sm, int grid, size_t lds_bytes, hipStream_t st);
+hipError_t launch_gemv_stream(const StreamArgs& a, int bits, bool zp, bool sc_f16, int sm, bool qw, bool g2, int grid, size_t lds_bytes, hipStream_t st) {
+    if (a.nops < 1 || grid < 1 || a.nsplit < 1 || a.nsplit > 4 || (sm != 0 && sm != 2) || (g2 && sm != 0)) return hipErrorInvalidValue;
+    if (g2) return qw ? launch_gemv_stream_qw_g2(a, bits, zp, sc_f16, sm, grid, lds_bytes, st) : launch_gemv_stream_g2(a, bits, zp, sc_f16, sm, grid, lds_bytes, st);
     if (qw) return launch_gemv_stream_qw(a, bits, zp, sc_f16, sm, grid, lds_bytes, st);
-    switch (bits) {
-        case 1: return stream_launch_b<1, false>(a, zp, sc_f16, sm, grid, lds_bytes, st);
-        case 2: return stream_launch_b<2, false>(a, zp, sc_f16, sm, grid, lds_bytes, st);
-        case 3: return stream_launch_b<3, false>(a, zp, sc_f16, sm, grid, lds_bytes, st);
-        case 4: return stream_launch_b<4, false>(a, zp, sc_f16, sm, grid, lds_bytes, st);
-        default: return hipErrorInvalidValue;
-    }
+    TMAC_STREAM_BITS_SWITCH(false, false)
 }
 #endif
+#undef TMAC_STREAM_BITS_SWITCH
 
 }  // namespace tmac

@@ -2,7 +2,8 @@
 (k_lut_images + k_gemv_stream): NL matrices of one shape with distinct weights (> MALL in total) and a DISTINCT activation vector per
 call, one launch; us per GEMV (hipEvent pair, mean / best of 10), fraction of the 8 TB/s HBM peak on SURVEY 8d's algorithmic bytes, and
 a bit-comparison of every call's output with the same call launched on its own (tmac_hip_qgemm_fused_dev, the chain's configuration).
-usage: bench_stream.py [shape ...]   shape = MwxK[xCNT][:bits]   default: 4096x11008 4096x4096 11008x4096x2 4096x4096x3
+usage: bench_stream.py [--gs N] [shape ...]   shape = MwxK[xCNT][:bits]   default: 4096x11008 4096x4096 11008x4096x2 4096x4096x3
+--gs N: weight group size of every matrix (default 128; 64 runs the persistent kernels' two-scale-group instantiations; K % N == 0)
 env: NL (calls per launch, default 32), TMAC_CHAIN_STREAM=0 measures k_decode_chain on the same recording, FORCE_WPQ=n forces the waves per row quad,
 TMAC_STREAM_SPLIT=1 one workgroup per CU; STAMPS=1|2 with a profiling build of the library (tools/build_variant.sh x "-DTMAC_STREAM_STAMPS=1|2",
 TMAC_HIP_LIB=.../libtmac_hip_x.so): 1 = where and when every workgroup ran (co-residency), 2 = where a lookup wave's cycles go."""
@@ -17,6 +18,12 @@ L = tmac_amd.lib()
 if os.environ.get("FORCE_WPQ"):        # A/B: waves per row quad of the recorded calls (tmac_hip_debug_chain_config)
     tmac_amd.binding.check(L.tmac_hip_debug_chain_config(int(os.environ["FORCE_WPQ"]), 0))
 gen = torch.Generator(device=dev); gen.manual_seed(7)
+ARGS = sys.argv[1:]
+GS = 128
+if "--gs" in ARGS:
+    k = ARGS.index("--gs")
+    GS = int(ARGS[k + 1])
+    del ARGS[k:k + 2]
 
 
 def algorithmic_bytes(Mw, K, bits, gs=128, ags=64, zp=True):
@@ -26,14 +33,14 @@ def algorithmic_bytes(Mw, K, bits, gs=128, ags=64, zp=True):
 def run(Mw, K, cnt, bits):
     bm = {1: 64, 2: 128, 3: 192, 4: 256}[bits]
     wr = tmac_amd.TMACGeMMWrapper(act_group_size=64); wr.set_workspace(K, 1)
-    cfg = KCfg.make(Mw, K, bits, bm, 16, 128, 64, True, -1)
+    cfg = KCfg.make(Mw, K, bits, bm, 16, GS, 64, True, -1)
     sets, xs, outs = [], [], []
     c = 1.0 / np.sqrt(2.5 * K)
     for _ in range(NL):
         ws = []
         for _ in range(cnt):
             A = torch.randint(0, 256, (Mw * bits // bm, K // 4, bm // 2), dtype=torch.uint8, device=dev, generator=gen)
-            S = (torch.randn((Mw * bits // bm, K // 128, bm // bits // 8, 2, 8), device=dev, generator=gen) * c).half().contiguous()
+            S = (torch.randn((Mw * bits // bm, K // GS, bm // bits // 8, 2, 8), device=dev, generator=gen) * c).half().contiguous()
             ws.append(tmac_amd.Weights(A, S, Mw, K, bits, cfg, scales_dtype=F16, dev_dtype=F16, on_device=True))
         sets.append(ws)
         xs.append(torch.randn(K, device=dev, generator=gen).half())
@@ -70,9 +77,9 @@ def run(Mw, K, cnt, bits):
         else:
             same = same and all(torch.equal(a, b) for a, b in zip(got[i], ref))
     L.tmac_hip_debug_quad_config(0, 0)
-    hb = cnt * algorithmic_bytes(Mw, K, bits) - (cnt - 1) * (K // 4 * 16 + (K // 64) * 4)
+    hb = cnt * algorithmic_bytes(Mw, K, bits, gs=GS) - (cnt - 1) * (K // 4 * 16 + (K // 64) * 4)
     mean, best = float(np.mean(ts)), float(np.min(ts))
-    print(f"{Mw}x{K}x{cnt} W{bits} {('stream-qw' if getattr(ch, 'quarter_walk', False) else 'stream') if ch.stream else 'chain '} wpq={ch.wpq(0)}: {mean:6.2f} us/call (best {best:6.2f})  {hb / mean * 1e-3:7.1f} GB/s  "
+    print(f"{Mw}x{K}x{cnt} W{bits} gs={GS} {('stream-qw' if getattr(ch, 'quarter_walk', False) else 'stream') if ch.stream else 'chain '} wpq={ch.wpq(0)}: {mean:6.2f} us/call (best {best:6.2f})  {hb / mean * 1e-3:7.1f} GB/s  "
           f"frac {hb / mean * 1e-3 / 8000:.3f}  bit-identical to the stand-alone launches: {same}", flush=True)
     if stamps is not None:
         raw = stamps.cpu().numpy()
@@ -112,7 +119,7 @@ def run(Mw, K, cnt, bits):
             w.free()
 
 
-shapes = sys.argv[1:] or ["4096x11008", "4096x4096", "11008x4096x2", "4096x4096x3"]
+shapes = ARGS or ["4096x11008", "4096x4096", "11008x4096x2", "4096x4096x3"]
 for s in shapes:
     bits = 2
     if ":" in s:
