@@ -66,15 +66,17 @@ int ggml_tmac_hip_mul_mat_dev(const struct tmac_ggml_tensor* const* w, int nw, c
  *                  optional) receives t.  residual_out must not overlap x, residual, norm_weight or an output: a residual stream alternates
  *                  between two buffers
  *   kind 2 (glu)   x' = silu(x) * in2;  in2 has x's dtype
+ *   kind 4 (glu_norm)  g = silu(x) * in2;  x' = rmsnorm(g, eps) * norm_weight (required) -- BitNet's ffn_sub_norm in front of the down
+ *                  projection.  residual and residual_out must be NULL
  * All weights of the call consume x'.  Such a call is never queued: with deferral on it flushes the queue, then launches. */
-int ggml_tmac_hip_mul_mat_dev_xf(const struct tmac_ggml_tensor* const* w, int nw, const void* x_dev, int x_is_f32, int kind /* 1 norm, 2 glu */,
+int ggml_tmac_hip_mul_mat_dev_xf(const struct tmac_ggml_tensor* const* w, int nw, const void* x_dev, int x_is_f32, int kind /* 1 norm, 2 glu, 4 glu_norm */,
                                  const void* in2_dev, const float* residual, const float* norm_weight, float eps, float* residual_out,
                                  void* const* dst_dev, int dst_is_f32);
 /* The same for n_rows rows of x (tmac_hip.h: tmac_hip_qgemm_fused_xf_rows_dev), so that the hook serves decode, a small batch and prefill
  * with one formula: x and in2 [n_rows][K], residual and residual_out fp32 [n_rows][K], norm_weight fp32 [K] shared by the rows, outputs
  * [n_rows][M] each.  n_rows = 1 is the call above.  For n_rows >= 2 the operator runs inside the LUT build of the route the plain mat-mul
  * of that many rows takes; residual_out must not overlap x, residual, norm_weight, in2 or an output. */
-int ggml_tmac_hip_mul_mat_dev_xf_rows(const struct tmac_ggml_tensor* const* w, int nw, const void* x_dev, int x_is_f32, int kind /* 1 norm, 2 glu */,
+int ggml_tmac_hip_mul_mat_dev_xf_rows(const struct tmac_ggml_tensor* const* w, int nw, const void* x_dev, int x_is_f32, int kind /* 1 norm, 2 glu, 4 glu_norm */,
                                       const void* in2_dev, const float* residual, const float* norm_weight, float eps, float* residual_out,
                                       void* const* dst_dev, int dst_is_f32, int n_rows);
 int ggml_tmac_hip_set_deferred(int on);
@@ -99,11 +101,27 @@ int ggml_tmac_hip_synchronize(void);
  *     ggml_tmac_hip_segment_mul_mat(w_qkv_next, 3, down, qkv_next);
  *     ggml_tmac_hip_segment_end(&seg);
  *     per token:  <attention of layer l on ggml_tmac_hip_stream()>;  ggml_tmac_hip_segment_compute(seg_l);  ...
- * The transform declared by _norm / _glu applies to the NEXT _mul_mat, whose x is the transform's `in`. */
+ * The transform declared by _norm / _glu / _glu_norm applies to the NEXT _mul_mat, whose x is the transform's `in`.
+ * A BitNet b1.58 layer (1bitLLM/bitnet_b1_58-3B; llama.cpp's bitnet graph) has two sub-layer norms more: an RMSNorm on the attention
+ * output in front of o (attn_sub_norm: a _norm without residual) and one on silu(gate) * up in front of down (ffn_sub_norm: _glu_norm):
+ *     ggml_tmac_hip_segment_begin();
+ *     ggml_tmac_hip_segment_norm(NULL, 0, attn_sub_norm_w, eps, NULL, 0);                   // x = rmsnorm(attn_out) * w
+ *     ggml_tmac_hip_segment_mul_mat_f32(&wo, 1, attn_out_f32, &o);   (or _mul_mat on fp16)
+ *     ggml_tmac_hip_segment_norm(h, 0, ffn_norm_w, eps, NULL, 1);                           // t = o + h, x = rmsnorm(t) * w; t kept
+ *     ggml_tmac_hip_segment_mul_mat(w_gate_up, 2, o, gate_up);
+ *     ggml_tmac_hip_segment_glu_norm(up, ffn_sub_norm_w, eps);                              // x = rmsnorm(silu(gate) * up) * w
+ *     ggml_tmac_hip_segment_mul_mat(&wdown, 1, gate, &down);
+ *     ggml_tmac_hip_segment_norm(NULL, 1, next_attn_norm_w, eps, h_next, 0);
+ *     ggml_tmac_hip_segment_mul_mat(w_qkv_next, 3, down, qkv_next);
+ *     ggml_tmac_hip_segment_end(&seg);
+ * _glu_norm is recorded only in this form -- gate and up are outputs 0 and 1 of ONE _mul_mat and nothing else in the segment reads gate --
+ * where the gate/up call publishes silu(gate) * up itself; any other form makes _end return non-zero, and the caller issues the segment
+ * call by call with ggml_tmac_hip_mul_mat_dev_xf(kind 4) in front of down. */
 typedef struct ggml_tmac_hip_segment ggml_tmac_hip_segment;
 int ggml_tmac_hip_segment_begin(void);
 int ggml_tmac_hip_segment_norm(const float* residual, int residual_is_kept, const float* norm_weight, float eps, float* residual_out, int keep);
 int ggml_tmac_hip_segment_glu(const void* in2_f16);
+int ggml_tmac_hip_segment_glu_norm(const void* in2_f16, const float* norm_weight, float eps);
 int ggml_tmac_hip_segment_mul_mat(const struct tmac_ggml_tensor* const* w, int nw, const void* x_f16, void* const* dst_f16);
 /* the same with x as an fp32 vector in device memory that no earlier mat-mul of the segment wrote (ggml's graphs are fp32: the output of
  * the attention operator in front of the o projection, the token embedding in front of the first q/k/v): the tables are built from the
@@ -112,10 +130,10 @@ int ggml_tmac_hip_segment_mul_mat_f32(const struct tmac_ggml_tensor* const* w, i
 int ggml_tmac_hip_segment_end(ggml_tmac_hip_segment** seg);
 /* A segment is all or nothing: when ggml_tmac_hip_segment_mul_mat or _end returns non-zero the recording is over (no chain exists, nothing
  * is pending).  The caller then issues the segment call by call: ggml_tmac_hip_mul_mat_dev for the plain mat-muls and
- * ggml_tmac_hip_mul_mat_dev_xf (above) for those behind a _norm / _glu, with the residual stream in two alternating buffers (a kept t
+ * ggml_tmac_hip_mul_mat_dev_xf (above) for those behind a _norm / _glu / _glu_norm (kind 1 / 2 / 4), with the residual stream in two alternating buffers (a kept t
  * does not outlive a launch: what _norm(NULL, 1, ...) took from LDS is read from the buffer the earlier call wrote as residual_out) -- also
  * when ggml_tmac_hip_segment_wait reports a failed hand-off -- or evaluates the graph's own nodes.
- * ggml_tmac_hip_segment_abort ends a recording explicitly (after a failed _norm / _glu, or a change of mind). */
+ * ggml_tmac_hip_segment_abort ends a recording explicitly (after a failed _norm / _glu / _glu_norm, or a change of mind). */
 int ggml_tmac_hip_segment_abort(void);
 int ggml_tmac_hip_segment_compute(ggml_tmac_hip_segment* seg);   /* one launch on ggml_tmac_hip_stream(); does not wait */
 int ggml_tmac_hip_segment_wait(ggml_tmac_hip_segment* seg);      /* synchronises the stream; 0 if every hand-off of the segment's launches completed */

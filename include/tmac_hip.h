@@ -249,6 +249,13 @@ int32_t tmac_hip_chain_free(tmac_hip_chain* chain);
  *                 same kind as `in`; K <= 12288
  *                 (when `in` and `in2` are outputs 0 and 1 of one earlier two-matrix call of the chain and nothing else reads output 0 through a
  *                 hand-off, that call publishes silu(in) * in2 itself, once per row, rounded to fp16 like every handed-over vector)
+ *   TMAC_XF_GLU_NORM  g = silu(in) * in2;  x = g * (1 / sqrt(mean(g^2) + eps)) * gamma -- the sub-layer norm BitNet b1.58 puts between
+ *                 silu(gate) * up and the down projection (ffn_sub_norm).  in2 as for a GLU; gamma (fp32 [K]) is required; residual,
+ *                 residual_out and keep must be NULL / 0 (TMAC_HIP_E_ARG names the field).  Recorded in the PRODUCER FORM ONLY: `in` and
+ *                 `in2` are outputs 0 and 1 of one earlier two-matrix call that publishes silu(in) * in2 itself (the rule in brackets
+ *                 above), and this call is then a NORM without residual of that handed-over vector; K <= 12288.  Every other form --
+ *                 vectors in memory, gate and up from two calls, a gathered output, TMAC_CHAIN_GLU_EPILOGUE=0, a waves-per-quad choice
+ *                 that cannot deal row pairs -- is TMAC_HIP_E_NOMATCH from tmac_hip_chain_end: issue the calls one by one
  * A decoder then runs one launch per segment between two operators that stay outside (attention): o -> gate/up -> down -> next q/k/v.
  * These are extensions without a reference counterpart (T-MAC has no norm operator): tests compare them with the same formulas in
  * numpy fed through the oracle (tolerance, not bits: the mean square is summed in another order).
@@ -263,6 +270,7 @@ int32_t tmac_hip_chain_free(tmac_hip_chain* chain);
 #define TMAC_XF_NONE 0
 #define TMAC_XF_NORM 1
 #define TMAC_XF_GLU 2
+#define TMAC_XF_GLU_NORM 4   /* (3 is not a kind) */
 #define TMAC_XF_CARRY ((const float*)1)
 typedef struct {
     int32_t kind;
@@ -283,10 +291,13 @@ int32_t tmac_hip_chain_xform(const tmac_hip_xform* xf);
  *                  bit for bit.  residual_out (fp32 [K], optional) receives t: each element is written once, pair p (8 elements) by
  *                  workgroup p mod grid.  `keep` is accepted and ignored; residual == TMAC_XF_CARRY is refused (TMAC_HIP_E_ARG)
  *   TMAC_XF_GLU    x = silu(in) * in2;  in2 has act_dtype like `in` (fp16 or fp32); hardware exp and reciprocal, specified to a tolerance
+ *   TMAC_XF_GLU_NORM  g = silu(in) * in2, the GLU's expression;  x = (g * gamma) * rsq(fma(sum g^2, rcp(K), eps)), the NORM's association
+ *                  and reduction.  gamma is required; residual, residual_out and keep must be NULL / 0
  * Scope: what tmac_hip_qgemm_fused_dev serves with k_gemv_quad at N = 1 -- QUAD layout, 1- to 4-bit, per-group scales (group size >= 64,
  * act groups of 64) or unified scales (m_groups >= 1), MFMA accumulate -- for K up to 24576, the kernel's own limit (the transformed
  * vector stays in registers, no LDS is added).  Anything else: TMAC_HIP_E_NOMATCH, nothing is launched.
- * Refused with TMAC_HIP_E_ARG before anything is launched: a kind outside 0..2; GLU without in2; in2 / residual / gamma / residual_out
+ * Refused with TMAC_HIP_E_ARG before anything is launched: a kind other than 0, 1, 2, 4; GLU without in2; GLU_NORM without in2 or gamma, or
+ * with residual, residual_out or keep set (the message names the field); in2 / residual / gamma / residual_out
  * not 16-byte aligned (B_dev and C_dev[i] as everywhere); residual_out overlapping B_dev, residual, gamma or a C_dev[i] -- every
  * workgroup reads the whole of the inputs while one workgroup writes each pair of residual_out, so an in-place residual stream has no
  * order here: alternate between two buffers.
@@ -294,7 +305,7 @@ int32_t tmac_hip_chain_xform(const tmac_hip_xform* xf);
  * for both modes, the chain's rules apply there.  With deferral on a transformed call is never queued: it flushes the queue, then
  * launches (a failed flush returns its status and nothing is launched).
  * Launch configuration: tmac_hip_debug_quad_config and the tuned table are honoured; the transformed instantiations exist for (threads,
- * waves per quad) = (512,1), (512,2), (768,3), (1024,4).  A forced configuration outside that set is TMAC_HIP_E_NOMATCH; a tuned or
+ * waves per quad) = (512,1), (512,2), (768,3), (1024,4) -- once for NORM / GLU and once for GLU_NORM.  A forced configuration outside that set is TMAC_HIP_E_NOMATCH; a tuned or
  * heuristic choice outside it runs on the nearest member (same waves per quad with 512 threads; (1024,4) for K > 12288). */
 int32_t tmac_hip_qgemm_fused_xf_dev(const tmac_hip_weights* const* weights, int nmat, const void* B_dev, tmac_dtype_t act_dtype,
                                     const tmac_hip_xform* xf, void* const* C_dev, tmac_dtype_t out_dtype, void* stream);
@@ -307,14 +318,16 @@ int32_t tmac_hip_qgemm_fused_xf_dev(const tmac_hip_weights* const* weights, int 
  *            (k_lut_image for k_gemm_planes, the pair builds for k_gemm_onehot / k_gemv_rows / the row loop): the LUT is built from the fp32
  *            x by the plain build's code, and the kernel behind it is the plain call's.  NORM with gamma or residual_out is preceded by
  *            one row pass (k_xf_rows, a workgroup per row) that writes residual_out -- every element once -- and the row's
- *            r = rsq(fma(sum t^2, rcp(K), eps)); the builders then form (t * gamma) * r.  The order of that sum depends on K alone: a row
+ *            r = rsq(fma(sum t^2, rcp(K), eps)); the builders then form (t * gamma) * r.  GLU_NORM always takes the row pass: it sums g^2 in
+ *            the same order and writes r alone; the builders recompute g with the row pass's own function and form (g * gamma) * r.
+ *            The order of that sum depends on K alone: a row
  *            gives the same x whatever N, its index or the route.  (At N = 1 k_gemv_quad sums in its own order: the two forms agree to
  *            rounding, not bits, for NORM with gamma.)  Where the plain call would run k_gemv_quad with one LUT build per workgroup, the
  *            transformed call builds the half-table image once and runs the row loop on it.
  * Scope (N >= 2): QUAD layout, 1- to 4-bit, act groups of 64 or unified scales with K <= 12288, one configuration per call.
  * TMAC_HIP_E_NOMATCH, nothing launched: anything outside that scope, a plan that would need the three-layout LUT build, the
  * reference-layout variant, fast-aggregation weights.  TMAC_HIP_E_ARG, nothing launched: the refusals of the N = 1 form with extents
- * x N -- kind outside 0..2, GLU without in2, TMAC_XF_CARRY, a transform vector below 16-byte alignment, residual_out overlapping B_dev,
+ * x N -- kind other than 0, 1, 2, 4, GLU without in2, GLU_NORM's own refusals, TMAC_XF_CARRY, a transform vector below 16-byte alignment, residual_out overlapping B_dev,
  * residual, gamma, in2 or an output (the LUT build reads `in` and `residual` after the row pass has written residual_out: alternate
  * between two buffers).
  * While the thread records a chain an N >= 2 transformed call is TMAC_HIP_E_NOMATCH: nothing is recorded, no transform stays pending.
@@ -329,7 +342,7 @@ int32_t tmac_hip_qgemm_fused_xf_rows_dev(const tmac_hip_weights* const* weights,
  * refusals come back as from the call (the scope checks of the call itself are not repeated). */
 int32_t tmac_hip_debug_xf_rows_plan(const tmac_hip_weights* const* weights, int nmat, void* const* C_dev, int N, int32_t* route, int32_t* lut);
 /* Parity tap: the fp32 x [N][K] that the LUT builds of the call above consume (the row pass plus a store around the builders' own load;
- * residual_out is written as the call writes it).  kind NORM or GLU; argument rules as above; synchronises the stream. */
+ * residual_out is written as the call writes it).  kind NORM, GLU or GLU_NORM; argument rules as above; synchronises the stream. */
 int32_t tmac_hip_debug_xf_rows(const void* B_dev, tmac_dtype_t act_dtype, const tmac_hip_xform* xf, int K, int N, float* x_out_dev,
                                void* stream);
 /* Row-sharded chains (one process per GPU; weight ROWS split over the ranks).  While recording, the exchange step between

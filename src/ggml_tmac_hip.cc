@@ -169,7 +169,7 @@ extern "C" int ggml_tmac_hip_mul_mat_dev_xf(const struct tmac_ggml_tensor* const
                                             void* const* dst_dev, int dst_is_f32) {
     if (!g_ready) return fail("ggml_tmac_hip_init has not been called");
     if (!w || nw < 1 || nw > 4 || !x_dev || !dst_dev) return fail("bad mul_mat_dev_xf");
-    if (kind != TMAC_XF_NORM && kind != TMAC_XF_GLU) return fail("mul_mat_dev_xf: kind must be 1 (norm) or 2 (glu)");
+    if (kind != TMAC_XF_NORM && kind != TMAC_XF_GLU && kind != TMAC_XF_GLU_NORM) return fail("mul_mat_dev_xf: kind must be 1 (norm), 2 (glu) or 4 (glu_norm)");
     g_err[0] = 0;
     const tmac_hip_weights* wl[4];
     void* cl[4];
@@ -183,6 +183,7 @@ extern "C" int ggml_tmac_hip_mul_mat_dev_xf(const struct tmac_ggml_tensor* const
     xf.kind = kind;
     if (kind == TMAC_XF_GLU) xf.in2 = in2_dev;
     else { xf.residual = residual; xf.gamma = norm_weight; xf.eps = eps; xf.residual_out = residual_out; }
+    if (kind == TMAC_XF_GLU_NORM) xf.in2 = in2_dev;      // (a residual operand set here is refused by the library, which names the field)
     return tmac_hip_qgemm_fused_xf_dev(wl, nw, x_dev, x_is_f32 ? TMAC_F32 : TMAC_F16, &xf, cl, dst_is_f32 ? TMAC_F32 : TMAC_F16, g_stream);
 }
 // ... and for n_rows rows of x (tmac_hip_qgemm_fused_xf_rows_dev): prefill or a small batch through the same hook
@@ -191,7 +192,7 @@ extern "C" int ggml_tmac_hip_mul_mat_dev_xf_rows(const struct tmac_ggml_tensor* 
                                                  void* const* dst_dev, int dst_is_f32, int n_rows) {
     if (!g_ready) return fail("ggml_tmac_hip_init has not been called");
     if (!w || nw < 1 || nw > 4 || !x_dev || !dst_dev || n_rows < 1) return fail("bad mul_mat_dev_xf_rows");
-    if (kind != TMAC_XF_NORM && kind != TMAC_XF_GLU) return fail("mul_mat_dev_xf_rows: kind must be 1 (norm) or 2 (glu)");
+    if (kind != TMAC_XF_NORM && kind != TMAC_XF_GLU && kind != TMAC_XF_GLU_NORM) return fail("mul_mat_dev_xf_rows: kind must be 1 (norm), 2 (glu) or 4 (glu_norm)");
     g_err[0] = 0;
     const tmac_hip_weights* wl[4];
     void* cl[4];
@@ -205,6 +206,7 @@ extern "C" int ggml_tmac_hip_mul_mat_dev_xf_rows(const struct tmac_ggml_tensor* 
     xf.kind = kind;
     if (kind == TMAC_XF_GLU) xf.in2 = in2_dev;
     else { xf.residual = residual; xf.gamma = norm_weight; xf.eps = eps; xf.residual_out = residual_out; }
+    if (kind == TMAC_XF_GLU_NORM) xf.in2 = in2_dev;      // (a residual operand set here is refused by the library, which names the field)
     return tmac_hip_qgemm_fused_xf_rows_dev(wl, nw, x_dev, x_is_f32 ? TMAC_F32 : TMAC_F16, &xf, cl, dst_is_f32 ? TMAC_F32 : TMAC_F16, n_rows, g_stream);
 }
 extern "C" int ggml_tmac_hip_set_deferred(int on) { return tmac_hip_defer(on); }
@@ -250,6 +252,15 @@ extern "C" int ggml_tmac_hip_segment_glu(const void* in2_f16) {
     memset(&xf, 0, sizeof(xf));
     xf.kind = TMAC_XF_GLU;
     xf.in2 = in2_f16;
+    return tmac_hip_chain_xform(&xf);
+}
+
+extern "C" int ggml_tmac_hip_segment_glu_norm(const void* in2_f16, const float* norm_weight, float eps) {
+    tmac_hip_xform xf;
+    memset(&xf, 0, sizeof(xf));
+    xf.kind = TMAC_XF_GLU_NORM;
+    xf.in2 = in2_f16;
+    xf.gamma = norm_weight; xf.eps = eps;
     return tmac_hip_chain_xform(&xf);
 }
 

@@ -16,6 +16,7 @@ using namespace tmac_host;
 static thread_local std::vector<ChainRecOp>* g_chain_rec = nullptr;
 static thread_local std::vector<ChainRecGather>* g_chain_gat = nullptr;
 static thread_local tmac_hip_xform g_chain_xf = {};                  // applies to the next recorded call
+static bool has_glu(const tmac_hip_xform& xf) { return xf.kind == TMAC_XF_GLU || xf.kind == TMAC_XF_GLU_NORM; }   // reads a second vector
 bool tmac_host::chain_recording() { return g_chain_rec != nullptr; }
 void tmac_host::chain_clear_xform() { memset(&g_chain_xf, 0, sizeof(g_chain_xf)); }
 
@@ -40,7 +41,11 @@ int32_t tmac_host::chain_record(const tmac_hip_weights* const* wl, int nmat, con
 extern "C" int32_t tmac_hip_chain_xform(const tmac_hip_xform* xf) {
     if (!g_chain_rec) return fail(TMAC_HIP_E_ARG, "no chain is being recorded on this thread");
     if (!xf) return fail(TMAC_HIP_E_ARG, "null transform");
-    if (xf->kind < 0 || xf->kind > 2) return fail(TMAC_HIP_E_ARG, "unknown transform kind %d", xf->kind);
+    if ((xf->kind < 0 || xf->kind > 2) && xf->kind != TMAC_XF_GLU_NORM) return fail(TMAC_HIP_E_ARG, "unknown transform kind %d", xf->kind);
+    if (xf->kind == TMAC_XF_GLU_NORM) {
+        const int32_t grc = glu_norm_check(xf);
+        if (grc) return grc;
+    }
     if (xf->kind == TMAC_XF_GLU && !xf->in2) return fail(TMAC_HIP_E_ARG, "GLU needs a second vector");
     // (residual == (void*)1 is the CARRY tag, not an address)
     const struct { const void* p; const char* name; } vec[] = {{xf->in2, "in2"}, {xf->residual == (const void*)1 ? nullptr : xf->residual, "residual"},
@@ -300,7 +305,7 @@ static int32_t analyse_flow(const std::vector<ChainRecOp>& rec, const std::vecto
     }
     // the second vector of a GLU transform: the same rules as the activations (an earlier output, whole, or external memory)
     for (size_t i = 0; i < n; ++i) {
-        if (rec[i].xf.kind != TMAC_XF_GLU) continue;
+        if (!has_glu(rec[i].xf)) continue;
         const Range r2{(const char*)rec[i].xf.in2, (const char*)rec[i].xf.in2 + (size_t)rec[i].w[0]->s.K * 2};
         const Src s = latest_output(rec, f, i, r2, rec[i].xf.in2, &partial);
         if (partial) return fail(TMAC_HIP_E_NOMATCH, "op %zu: the GLU's second vector overlaps output %zu of op %zu without being that output", i, (size_t)s.mat, (size_t)s.op);
@@ -342,7 +347,7 @@ static void plan_glu_epilogue(const std::vector<ChainRecOp>& rec, ChainFlow& f, 
         if (f.src2[i].op >= 0) ++readers[f.src2[i].op][f.src2[i].mat];
     }
     for (size_t i = 0; i < n; ++i) {
-        if (rec[i].xf.kind != TMAC_XF_GLU || f.src[i].op < 0 || f.src2[i].op != f.src[i].op || f.src[i].mat != 0 || f.src2[i].mat != 1) continue;
+        if (!has_glu(rec[i].xf) || f.src[i].op < 0 || f.src2[i].op != f.src[i].op || f.src[i].mat != 0 || f.src2[i].mat != 1) continue;
         const size_t j = (size_t)f.src[i].op;
         if (rec[j].w.size() != 2 || rec[j].w[0]->s.Mw != rec[j].w[1]->s.Mw || f.gathered[j][0] || f.gathered[j][1] || readers[j][0] != 1 || f.epi_of[j]) continue;
         const Shape& sj = rec[j].w[0]->s;
@@ -376,7 +381,7 @@ static int32_t describe_ops(const std::vector<ChainRecOp>& rec, const ChainFlow&
         const Shape& s0 = r.w[0]->s;
         const Src src = f.src[i], src2 = f.src2[i];
         if (r.act != TMAC_F16 && r.act != TMAC_F32) return fail(TMAC_HIP_E_NOMATCH, "op %zu: the decode chain takes fp16 or fp32 activations", i);
-        if (r.act == TMAC_F32 && (src.op >= 0 || r.xf.kind == TMAC_XF_GLU))
+        if (r.act == TMAC_F32 && (src.op >= 0 || has_glu(r.xf)))
             return fail(TMAC_HIP_E_NOMATCH, "op %zu: fp32 activations are covered for vectors in memory (an earlier output is handed over as fp16), without a GLU transform", i);
         if ((r.out == TMAC_F16) != (c.out_f16 != 0)) return fail(TMAC_HIP_E_NOMATCH, "op %zu: one output dtype per chain", i);
         if (s0.K > 8 * 3 * CHAIN_FT) return fail(TMAC_HIP_E_NOMATCH, "op %zu: K = %d beyond the decode chain's %d", i, s0.K, 8 * 3 * CHAIN_FT);
@@ -461,6 +466,21 @@ static int32_t describe_ops(const std::vector<ChainRecOp>& rec, const ChainFlow&
                 if (xf.gamma && rf > c.gam_floats) c.gam_floats = rf;
                 o.gamma = xf.gamma; o.res_out = xf.residual_out;
                 memcpy(&o.eps_bits, &xf.eps, 4);
+            } else if (xf.kind == TMAC_XF_GLU_NORM) {
+                // Served in the producer form only: the gate/up call publishes g = silu(gate) * up (fp16, like every handed-over vector)
+                // and this call is a NORM of its handed-over `in` -- no residual, no carry -- which the kernel already runs.
+                if (!f.glu_in_producer[i])
+                    return fail(TMAC_HIP_E_NOMATCH, "op %zu: a GLU_NORM transform is recorded only where the call in front publishes silu(in) * in2 itself (in and in2 "
+                                                    "outputs 0 and 1 of one earlier two-matrix call that nothing else reads through a hand-off, not gathered, "
+                                                    "TMAC_CHAIN_GLU_EPILOGUE != 0, an even number of row quads per workgroup iteration): launch these calls one by one", i);
+                c.xforms = 1;
+                if (o.K > 2 * 8 * CHAIN_FT) return fail(TMAC_HIP_E_NOMATCH, "op %zu: a GLU_NORM transform is covered up to K = %d (the NORM's limit)", i, 2 * 8 * CHAIN_FT);
+                const int rf = chain_xf_region_floats(o.K);
+                o.xf_kind = TMAC_XF_NORM;
+                if (rf > c.tmp_floats) c.tmp_floats = rf;
+                if (rf > c.gam_floats) c.gam_floats = rf;
+                o.gamma = xf.gamma;
+                memcpy(&o.eps_bits, &xf.eps, 4);
             } else if (xf.kind == TMAC_XF_GLU && f.glu_in_producer[i]) {
                 o.xf_kind = TMAC_XF_NONE;                  // `in` already holds silu(gate) * up (the producer's epilogue)
             } else if (xf.kind == TMAC_XF_GLU) {
@@ -519,8 +539,9 @@ static int32_t check_hazards(const std::vector<ChainRecOp>& rec, const ChainFlow
             if (xf.residual && xf.residual != TMAC_XF_CARRY) xf_rd[i].push_back(Range{(const char*)xf.residual, (const char*)xf.residual + K * 4});
             if (xf.gamma) xf_rd[i].push_back(Range{(const char*)xf.gamma, (const char*)xf.gamma + K * 4});
             if (xf.residual_out) xf_wr[i] = Range{(const char*)xf.residual_out, (const char*)xf.residual_out + K * 4};
-        } else if (xf.kind == TMAC_XF_GLU && f.src2[i].op < 0) {
-            xf_rd[i].push_back(Range{(const char*)xf.in2, (const char*)xf.in2 + K * 2});
+        } else if (has_glu(xf)) {
+            if (f.src2[i].op < 0) xf_rd[i].push_back(Range{(const char*)xf.in2, (const char*)xf.in2 + K * 2});
+            if (xf.kind == TMAC_XF_GLU_NORM) xf_rd[i].push_back(Range{(const char*)xf.gamma, (const char*)xf.gamma + K * 4});
         }
     }
     for (size_t k = 0; k < n; ++k) {

@@ -540,7 +540,7 @@ static int32_t fused_prefill(Plan p, const tmac_hip_weights* const* wl, int nmat
     hipError_t e = hipSuccess;
     if (xf) {
         xf->r = ws->xf_r;
-        if (xf->kind == TMAC_XF_NORM && (xf->gamma || xf->residual_out)) {
+        if (xf->kind == TMAC_XF_GLU_NORM || (xf->kind == TMAC_XF_NORM && (xf->gamma || xf->residual_out))) {      // (GLU_NORM: always, gamma is required)
             e = launch_xf_rows(*xf, B_dev, f16, xf->gamma ? ws->xf_r : nullptr, s0.K, N, st);
             if (e != hipSuccess) return fail(TMAC_HIP_E_RUNTIME, "transform row pass launch: %s", hipGetErrorString(e));
         }
@@ -616,6 +616,16 @@ extern "C" int32_t tmac_hip_qgemm_fused_dev(const tmac_hip_weights* const* weigh
 // ---- fused entry point with a vector transform (N = 1) -----------------------------------------------------------------------
 // Outside a recording: k_gemv_quad's XF instantiations.  Everything is checked before anything is launched; a transformed call is never
 // queued (it goes behind the deferred queue like every non-hot entry point).
+// kind known to the transformed calls: NONE, NORM, GLU, GLU_NORM (3 is not a kind)
+static bool xf_kind_known(int kind) { return (kind >= TMAC_XF_NONE && kind <= TMAC_XF_GLU) || kind == TMAC_XF_GLU_NORM; }
+int32_t tmac_host::glu_norm_check(const tmac_hip_xform* xf) {
+    if (!xf->in2) return fail(TMAC_HIP_E_ARG, "GLU_NORM needs a second vector (in2)");
+    if (!xf->gamma) return fail(TMAC_HIP_E_ARG, "GLU_NORM needs the norm weights (gamma)");
+    if (xf->residual) return fail(TMAC_HIP_E_ARG, "GLU_NORM takes no residual: the field must be NULL");
+    if (xf->residual_out) return fail(TMAC_HIP_E_ARG, "GLU_NORM writes no residual_out: the field must be NULL");
+    if (xf->keep) return fail(TMAC_HIP_E_ARG, "GLU_NORM keeps no vector: keep must be 0");
+    return TMAC_HIP_OK;
+}
 static bool ranges_overlap(const void* a, size_t an, const void* b, size_t bn) {
     const char* pa = (const char*)a; const char* pb = (const char*)b;
     return a && b && pa < pb + bn && pb < pa + an;
@@ -632,16 +642,20 @@ extern "C" int32_t tmac_hip_qgemm_fused_xf_dev(const tmac_hip_weights* const* wl
         if (rc != TMAC_HIP_OK && chain_recording()) chain_clear_xform();      // a rejected call leaves no pending transform
         return rc;
     }
-    if (xf->kind < 0 || xf->kind > 2) return fail(TMAC_HIP_E_ARG, "unknown transform kind %d", xf->kind);
+    if (!xf_kind_known(xf->kind)) return fail(TMAC_HIP_E_ARG, "unknown transform kind %d", xf->kind);
     if (!wl || !C_list || !B_dev || nmat < 1 || nmat > 4) return fail(TMAC_HIP_E_ARG, "bad fused arguments (1..4 matrices)");
-    const bool norm = xf->kind == TMAC_XF_NORM;
+    const bool norm = xf->kind == TMAC_XF_NORM, glu_norm = xf->kind == TMAC_XF_GLU_NORM;
+    if (glu_norm) {
+        const int32_t grc = glu_norm_check(xf);
+        if (grc) return grc;
+    }
     if (!norm && !xf->in2) return fail(TMAC_HIP_E_ARG, "GLU needs a second vector");
     if (norm && xf->residual == TMAC_XF_CARRY)
         return fail(TMAC_HIP_E_ARG, "TMAC_XF_CARRY names a vector kept inside a chain launch: outside a recording the residual is a vector in memory");
-    // the vectors the call touches (a NORM ignores in2, a GLU the NORM's fields)
+    // the vectors the call touches (a NORM ignores in2, a GLU the NORM's fields; a GLU_NORM reads in2 and gamma)
     const void* in2 = norm ? nullptr : xf->in2;
     const float* residual = norm ? xf->residual : nullptr;
-    const float* gamma = norm ? xf->gamma : nullptr;
+    const float* gamma = norm || glu_norm ? xf->gamma : nullptr;
     float* rout = norm ? xf->residual_out : nullptr;
     if (misaligned(B_dev, ACT_ALIGN)) return fail(TMAC_HIP_E_ARG, "B_dev must be %zu-byte aligned (the LUT build reads 16 bytes at a time)", ACT_ALIGN);
     for (int i = 0; i < nmat; ++i)
@@ -688,8 +702,12 @@ extern "C" int32_t tmac_hip_qgemm_fused_xf_dev(const tmac_hip_weights* const* wl
 // (k_xf_rows), the planned LUT build with the transform in its activation load, the planned kernel (fused_prefill).  Never recorded, never
 // queued.
 static int32_t xf_rows_check(const void* B_dev, tmac_dtype_t act_dtype, const tmac_hip_xform* xf, int K, int N, XfRowsArgs& xa) {
-    if (xf->kind < 0 || xf->kind > 2) return fail(TMAC_HIP_E_ARG, "unknown transform kind %d", xf->kind);
-    const bool norm = xf->kind == TMAC_XF_NORM;
+    if (!xf_kind_known(xf->kind)) return fail(TMAC_HIP_E_ARG, "unknown transform kind %d", xf->kind);
+    const bool norm = xf->kind == TMAC_XF_NORM, glu_norm = xf->kind == TMAC_XF_GLU_NORM;
+    if (glu_norm) {
+        const int32_t grc = glu_norm_check(xf);
+        if (grc) return grc;
+    }
     if (!norm && !xf->in2) return fail(TMAC_HIP_E_ARG, "GLU needs a second vector");
     if (norm && xf->residual == TMAC_XF_CARRY)
         return fail(TMAC_HIP_E_ARG, "TMAC_XF_CARRY names a vector kept inside a chain launch: outside a recording the residual is a vector in memory");
@@ -697,7 +715,7 @@ static int32_t xf_rows_check(const void* B_dev, tmac_dtype_t act_dtype, const tm
     xa.kind = xf->kind; xa.eps = xf->eps;
     xa.in2 = norm ? nullptr : xf->in2;
     xa.residual = norm ? xf->residual : nullptr;
-    xa.gamma = norm ? xf->gamma : nullptr;
+    xa.gamma = norm || glu_norm ? xf->gamma : nullptr;
     xa.residual_out = norm ? xf->residual_out : nullptr;
     if (misaligned(B_dev, ACT_ALIGN)) return fail(TMAC_HIP_E_ARG, "B_dev must be %zu-byte aligned (the LUT build reads 16 bytes at a time)", ACT_ALIGN);
     const struct { const void* p; const char* name; } vec[] = {{xa.in2, "in2"}, {xa.residual, "residual"}, {xa.gamma, "gamma"}, {xa.residual_out, "residual_out"}};
@@ -782,7 +800,7 @@ extern "C" int32_t tmac_hip_debug_xf_rows(const void* B_dev, tmac_dtype_t act_dt
     const int32_t brc = defer_barrier();
     if (brc) return brc;
     if (!B_dev || !xf || !x_out_dev || K <= 0 || K % 64 || N < 1) return fail(TMAC_HIP_E_ARG, "bad tap arguments (K a multiple of 64, N >= 1)");
-    if (xf->kind == TMAC_XF_NONE) return fail(TMAC_HIP_E_ARG, "the tap shows a transform: kind NORM or GLU");
+    if (xf->kind == TMAC_XF_NONE) return fail(TMAC_HIP_E_ARG, "the tap shows a transform: kind NORM, GLU or GLU_NORM");
     XfRowsArgs xa;
     const int32_t rc = xf_rows_check(B_dev, act_dtype, xf, K, N, xa);
     if (rc) return rc;
@@ -792,7 +810,7 @@ extern "C" int32_t tmac_hip_debug_xf_rows(const void* B_dev, tmac_dtype_t act_dt
     DevBuf r;
     if (xa.gamma) { HIP_TRY(r.alloc(sizeof(float) * (size_t)N)); xa.r = r.as<float>(); }
     hipError_t e = hipSuccess;
-    if (xa.kind == TMAC_XF_NORM && (xa.gamma || xa.residual_out)) e = launch_xf_rows(xa, B_dev, f16, r.as<float>(), K, N, st);
+    if (xa.kind == TMAC_XF_GLU_NORM || (xa.kind == TMAC_XF_NORM && (xa.gamma || xa.residual_out))) e = launch_xf_rows(xa, B_dev, f16, r.as<float>(), K, N, st);
     if (e == hipSuccess) e = launch_xf_rows_tap(xa, B_dev, f16, x_out_dev, K, N, st);
     const hipError_t es = hipStreamSynchronize(st);      // r is freed on return
     if (e != hipSuccess || es != hipSuccess) return fail(TMAC_HIP_E_RUNTIME, "transform tap: %s", hipGetErrorString(e != hipSuccess ? e : es));

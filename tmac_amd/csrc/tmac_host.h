@@ -173,6 +173,9 @@ void tuned_config(const FusedArgs& fa, int total_q, int& ft, int& wpq);   // lea
 // ---- decode chain (tmac_chain_host.cpp) and deferred queue (tmac_defer.cpp) -----------------------------------------------------------
 bool chain_recording();            // is the calling thread between tmac_hip_chain_begin and tmac_hip_chain_end?
 void chain_clear_xform();          // drops a transform declared for the next recorded call (the call was rejected before it could be recorded)
+// TMAC_XF_GLU_NORM's own argument rules, the same on every path: in2 and gamma required, no residual operand.  TMAC_HIP_OK, or fail(E_ARG, ...)
+// naming the field.
+int32_t glu_norm_check(const tmac_hip_xform* xf);
 int32_t chain_record(const tmac_hip_weights* const* wl, int nmat, const void* B_dev, tmac_dtype_t act_dtype, void* const* C_list,
                      tmac_dtype_t out_dtype, int N);
 // deferred launches (tmac_hip_defer): true (and *rc set) when the call was queued instead of launched

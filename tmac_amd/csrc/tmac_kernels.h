@@ -49,10 +49,10 @@ struct FusedArgs {
 // k_gemv_quad's XF instantiations (tmac_hip_qgemm_fused_xf_dev): the N = 1 call plus a vector transform of its activations, applied
 // between the activation loads and the table build.  An argument block of its own: the plain instantiations keep theirs.
 struct FusedXfArgs : FusedArgs {
-    int xf_kind;             // TMAC_XF_NORM (1) | TMAC_XF_GLU (2)
-    const void* in2;         // GLU: second vector [K], dtype of B
+    int xf_kind;             // TMAC_XF_NORM (1) | TMAC_XF_GLU (2) | TMAC_XF_GLU_NORM (4)
+    const void* in2;         // GLU, GLU_NORM: second vector [K], dtype of B
     const float* residual;   // NORM: fp32 [K] or null
-    const float* gamma;      // NORM: fp32 [K] or null (add only)
+    const float* gamma;      // NORM: fp32 [K] or null (add only); GLU_NORM: fp32 [K], required
     float* residual_out;     // NORM: fp32 [K] or null; pair p is stored by workgroup p mod gridDim.x
     float eps;
 };
@@ -61,11 +61,11 @@ struct FusedXfArgs : FusedArgs {
 // and 1 / rms per row) and of the XF instantiations of the three N > 1 LUT builders (k_lut_image, k_preprocess_pairs, k_preprocess_pairs_row),
 // which replace their activation load by xf_rows_x8 (tmac_quad_core.h).  Row n of every [N][K] operand is read for row n of the activations.
 struct XfRowsArgs {
-    int kind;                // TMAC_XF_NORM (1) | TMAC_XF_GLU (2)
-    const void* in2;         // GLU: [N][K], dtype of B
+    int kind;                // TMAC_XF_NORM (1) | TMAC_XF_GLU (2) | TMAC_XF_GLU_NORM (4)
+    const void* in2;         // GLU, GLU_NORM: [N][K], dtype of B
     const float* residual;   // NORM: fp32 [N][K] or null
-    const float* gamma;      // NORM: fp32 [K] (shared by the rows) or null (add only)
-    const float* r;          // NORM with gamma: fp32 [N], 1 / rms of row n, written by k_xf_rows
+    const float* gamma;      // NORM: fp32 [K] (shared by the rows) or null (add only); GLU_NORM: fp32 [K], required
+    const float* r;          // NORM with gamma, GLU_NORM: fp32 [N], 1 / rms of row n, written by k_xf_rows
     float* residual_out;     // NORM: fp32 [N][K] or null; written by k_xf_rows alone
     float eps;
 };

@@ -99,10 +99,12 @@ __device__ __forceinline__ void load_q(QFrag<BITS>& f, const FusedArgs& a, const
 // D[i][4g+beta] lands in lane l' = 16*(i/4) + 4g + beta, register i%4: lane l' owns output row beta and the four
 // units 16g + 4*(l'/16) .. +3 of the step (two act groups, one 128-wide scale group).
 // XF (LUTSRC 1, ACC 1, no tap, one activation row): the argument block carries the transform's operands (FusedXfArgs); every line of it
-// sits under if constexpr (XF).
-template <int BITS, bool ZP, int SM, int LUTSRC, int NR, int FT, int WPQ, bool DUMP, int ACC, bool SCF16, bool EARLY, bool XF = false>
+// sits under if constexpr (XF).  GN (with XF): the instantiation serves TMAC_XF_GLU_NORM (xf_kind 4) and nothing else -- kinds 1 and 2 keep
+// the code they had (measured: sharing one instantiation moved the GLU by 1 %, profiles/r13_glunorm_bench.txt).
+template <int BITS, bool ZP, int SM, int LUTSRC, int NR, int FT, int WPQ, bool DUMP, int ACC, bool SCF16, bool EARLY, bool XF = false, bool GN = false>
 __global__ __launch_bounds__(FT) void k_gemv_quad(std::conditional_t<XF, FusedXfArgs, FusedArgs> a) {
     static_assert(!XF || (LUTSRC == 1 && ACC == 1 && !DUMP), "the transform lives in the in-kernel LUT build of the MFMA form");
+    static_assert(!GN || XF, "GLU_NORM is a transform");
     extern __shared__ uint4 lds[];
     const unsigned long long t_entry = DUMP ? __builtin_amdgcn_s_memtime() : 0ull;   // before the first kernel-argument load
     constexpr int NWV = FT / 64, IPI = NWV / WPQ;
@@ -161,7 +163,8 @@ __global__ __launch_bounds__(FT) void k_gemv_quad(std::conditional_t<XF, FusedXf
             }
         }
     }
-    // XF: the transform's operands for the lane's own pairs, clamped like xr: NORM residual (xa) and gamma (xg), GLU in2 (xa)
+    // XF: the transform's operands for the lane's own pairs, clamped like xr: NORM residual (xa) and gamma (xg), GLU in2 (xa), GLU_NORM
+    // (xf_kind 4) in2 (xa) and gamma (xg)
     uint32_t xa[XF ? NP : 1][8], xg[XF ? NP : 1][8];
     if constexpr (XF) {
 #pragma unroll
@@ -169,9 +172,9 @@ __global__ __launch_bounds__(FT) void k_gemv_quad(std::conditional_t<XF, FusedXf
             const int p = min(r * FT + tid, P - 1);
 #pragma unroll
             for (int i = 0; i < 8; ++i) { xa[r][i] = 0u; xg[r][i] = 0u; }
-            const void* src_a = a.xf_kind == 1 ? (const void*)a.residual : a.in2;
+            const void* src_a = (!GN && a.xf_kind == 1) ? (const void*)a.residual : a.in2;
             if (src_a != nullptr) {
-                if (a.xf_kind == 2 && a.act_f16) {
+                if ((GN || a.xf_kind == 2) && a.act_f16) {
                     const uint4 v = reinterpret_cast<const uint4*>(src_a)[p];
                     xa[r][0] = v.x; xa[r][1] = v.y; xa[r][2] = v.z; xa[r][3] = v.w;
                 } else {
@@ -181,7 +184,7 @@ __global__ __launch_bounds__(FT) void k_gemv_quad(std::conditional_t<XF, FusedXf
                     xa[r][4] = v1.x; xa[r][5] = v1.y; xa[r][6] = v1.z; xa[r][7] = v1.w;
                 }
             }
-            if (a.xf_kind == 1 && a.gamma != nullptr) {
+            if ((GN || a.xf_kind == 1) && a.gamma != nullptr) {
                 const uint4* src = reinterpret_cast<const uint4*>(a.gamma) + 2 * (size_t)p;
                 const uint4 v0 = src[0], v1 = src[1];
                 xg[r][0] = v0.x; xg[r][1] = v0.y; xg[r][2] = v0.z; xg[r][3] = v0.w;
@@ -189,7 +192,7 @@ __global__ __launch_bounds__(FT) void k_gemv_quad(std::conditional_t<XF, FusedXf
             }
         }
     }
-    float xrs = 1.0f;                 // XF, NORM with gamma: 1 / rms, known behind the cross-wave sum below
+    float xrs = 1.0f;                 // XF, NORM with gamma / GLU_NORM: 1 / rms, known behind the cross-wave sum below
     bool xnorm = false;
     auto unpack = [&](int r, float (&x)[8]) {
         if (!XF && a.act_f16) {
@@ -215,7 +218,8 @@ __global__ __launch_bounds__(FT) void k_gemv_quad(std::conditional_t<XF, FusedXf
     // the lane's part of sum t^2, and t * gamma; 1 / rms multiplies in unpack, once the sum is known.  Without gamma x = t, untouched:
     // the table build then sees the bits a plain call on t would.  GLU: x = silu(in) * in2 with the hardware exp and reciprocal
     // (tmac_chain.hip's formula).  The transformed vector stays in the registers the raw one arrived in (xr is [NP][8] for fp32
-    // activations anyway); the operands are dead behind this block.
+    // activations anyway); the operands are dead behind this block.  GLU_NORM: g = the GLU's x, then the NORM's tail on g -- the lane's
+    // part of sum g^2 (own pairs only: a clamped lane holds a copy of the last pair), g * gamma, 1 / rms in unpack.
     float xss = 0.f;
     if constexpr (XF) {
         const bool in_f16 = a.act_f16 != 0;
@@ -233,7 +237,7 @@ __global__ __launch_bounds__(FT) void k_gemv_quad(std::conditional_t<XF, FusedXf
 #pragma unroll
                 for (int i = 0; i < 8; ++i) x[i] = __uint_as_float(xr[r][i]);
             }
-            if (a.xf_kind == 1) {
+            if (!GN && a.xf_kind == 1) {
                 if (a.residual != nullptr) {
 #pragma unroll
                     for (int i = 0; i < 8; ++i) x[i] = __fadd_rn(x[i], __uint_as_float(xa[r][i]));
@@ -267,6 +271,14 @@ __global__ __launch_bounds__(FT) void k_gemv_quad(std::conditional_t<XF, FusedXf
 #pragma unroll
                 for (int i = 0; i < 8; ++i)
                     x[i] = __fmul_rn(__fmul_rn(x[i], __builtin_amdgcn_rcpf(__fadd_rn(1.0f, __expf(-x[i])))), u[i]);
+                if constexpr (GN) {
+                    if (p < P) {
+#pragma unroll
+                        for (int i = 0; i < 8; ++i) xss = __fmaf_rn(x[i], x[i], xss);
+                    }
+#pragma unroll
+                    for (int i = 0; i < 8; ++i) x[i] = __fmul_rn(x[i], __uint_as_float(xg[r][i]));
+                }
             }
 #pragma unroll
             for (int i = 0; i < 8; ++i) xr[r][i] = __float_as_uint(x[i]);
@@ -306,11 +318,11 @@ __global__ __launch_bounds__(FT) void k_gemv_quad(std::conditional_t<XF, FusedXf
     }
     QSTAMP(1);
     if constexpr (XF) {
-        // NORM with gamma: the mean square.  A wave sum per wave (four DPP steps inside the rows of 16 lanes, the four row sums through
+        // NORM with gamma, GLU_NORM: the mean square.  A wave sum per wave (four DPP steps inside the rows of 16 lanes, the four row sums through
         // readlane), the partials through LDS (l_red: idle until the first finish_quad, behind the barrier that ends section 3), added in
         // wave order by every thread.  The barrier is LDS-only: __syncthreads() carries s_waitcnt vmcnt(0) and would wait for the weight
         // fragments issued a moment ago.
-        if (a.xf_kind == 1 && a.gamma != nullptr) {
+        if ((GN || a.xf_kind == 1) && a.gamma != nullptr) {
             float ss = xss;
             ss = __fadd_rn(ss, qdpp_f<0xB1>(ss)); ss = __fadd_rn(ss, qdpp_f<0x4E>(ss));
             ss = __fadd_rn(ss, qdpp_f<0x141>(ss)); ss = __fadd_rn(ss, qdpp_f<0x140>(ss));     // row_half_mirror, row_mirror
@@ -919,11 +931,12 @@ __global__ __launch_bounds__(PT) void k_preprocess_pairs_row(const void* __restr
 }
 
 // ---------------------------------------------------------------------------------------------
-// Vector transforms for N > 1 rows: the row pass in front of an XF LUT build.  One workgroup per activation row.  NORM only: t = fp32(in)
+// Vector transforms for N > 1 rows: the row pass in front of an XF LUT build.  One workgroup per activation row.  NORM: t = fp32(in)
 // + residual (xf_rows_t8: the add the builders repeat), t to residual_out -- pair p of row n has exactly one writer, thread p mod 256 of
 // workgroup n -- and, with gamma, r[n] = rsq(fma(sum t^2, rcp(K), eps)), k_gemv_quad's expression.  The order of the sum is a function of K
 // alone: thread j adds its pairs j, j + 256, ... element by element (fma), the wave's 64 sums fold by xor 32, 16, ... 1, the four wave
 // sums are added in wave order.  Neither N, the row's index nor any launch knob enters: a row's r is the same in every call.
+// GLU_NORM (kind 4): t = g = silu(in) * in2 (xf_rows_g8: the product the builders repeat), summed in the same order; r[n] is all it writes.
 // ---------------------------------------------------------------------------------------------
 constexpr int XF_ROWS_PT = 256;
 template <bool F16>
@@ -933,7 +946,8 @@ __global__ __launch_bounds__(XF_ROWS_PT) void k_xf_rows(XfRowsArgs a, const void
     float ss = 0.f;
     for (int p = tid; p < P; p += XF_ROWS_PT) {
         float t[8];
-        xf_rows_t8(a, B, F16, K, n, p, t);
+        if (a.kind == 4) xf_rows_g8(a, B, F16, K, n, p, t);
+        else xf_rows_t8(a, B, F16, K, n, p, t);
         if (a.residual_out != nullptr) {
             float4* ro = reinterpret_cast<float4*>(a.residual_out + (size_t)n * K) + 2 * (size_t)p;
             ro[0] = make_float4(t[0], t[1], t[2], t[3]);
@@ -968,14 +982,15 @@ __global__ __launch_bounds__(256) void k_xf_rows_tap(XfRowsArgs a, const void* _
 }
 
 hipError_t launch_xf_rows(const XfRowsArgs& xf, const void* B, int act_f16, float* r_out, int K, int N, hipStream_t st) {
-    if (K % 64 != 0 || N < 1 || xf.kind != 1 || (r_out == nullptr && xf.residual_out == nullptr)) return hipErrorInvalidValue;
+    if (K % 64 != 0 || N < 1 || (xf.kind != 1 && xf.kind != 4) || (r_out == nullptr && xf.residual_out == nullptr)) return hipErrorInvalidValue;
+    if (xf.kind == 4 && (!xf.in2 || !xf.gamma || !r_out || xf.residual || xf.residual_out)) return hipErrorInvalidValue;
     dim3 g(N), b(XF_ROWS_PT);
     if (act_f16) hipLaunchKernelGGL((k_xf_rows<true>), g, b, 0, st, xf, B, r_out, K);
     else hipLaunchKernelGGL((k_xf_rows<false>), g, b, 0, st, xf, B, r_out, K);
     return hipGetLastError();
 }
 hipError_t launch_xf_rows_tap(const XfRowsArgs& xf, const void* B, int act_f16, float* x_out, int K, int N, hipStream_t st) {
-    if (K % 64 != 0 || N < 1 || N > 65535 || xf.kind < 1 || xf.kind > 2 || !x_out) return hipErrorInvalidValue;
+    if (K % 64 != 0 || N < 1 || N > 65535 || (xf.kind != 1 && xf.kind != 2 && xf.kind != 4) || !x_out) return hipErrorInvalidValue;
     dim3 g((K / 8 + 255) / 256, N), b(256);
     if (act_f16) hipLaunchKernelGGL((k_xf_rows_tap<true>), g, b, 0, st, xf, B, x_out, K);
     else hipLaunchKernelGGL((k_xf_rows_tap<false>), g, b, 0, st, xf, B, x_out, K);
@@ -1148,6 +1163,7 @@ static hipError_t qlaunch_b(const FusedArgs& a, int total_q, int N, int fft, int
 }
 
 // ---- XF instantiations (tmac_hip_qgemm_fused_xf_dev) ----
+// (each once for NORM / GLU and once, GN, for GLU_NORM)
 // They cover FOUR of the eight (threads, waves per quad) configurations -- one per waves-per-quad count, which is what shapes the K walk
 // and the cross-wave reductions: (512,1), (512,2), (768,3), (1024,4) -- so that eight translation units grow by 12 kernels per scale
 // flavour instead of 20.  A configuration the caller forced (tmac_hip_debug_quad_config) outside the set is refused; one the heuristic or
@@ -1155,7 +1171,7 @@ static hipError_t qlaunch_b(const FusedArgs& a, int total_q, int N, int fft, int
 // (768,2), (1024,2) -> (512,2)), or (1024,4) where 512 threads cannot build the tables (K > 12288: more than six per thread).
 static bool quad_xf_covered(int ft, int wpq) { return (ft == 512 && (wpq == 1 || wpq == 2)) || (ft == 768 && wpq == 3) || (ft == 1024 && wpq == 4); }
 
-template <int BITS, bool ZP, int SM, int FT, int WPQ>
+template <int BITS, bool ZP, int SM, int FT, int WPQ, bool GN>
 static hipError_t qlaunch_xf_nr(const FusedXfArgs& a, int total_q, hipStream_t st) {
     constexpr int IPI = FT / 64 / WPQ;
     const size_t shmem = quad_lds_bytes(a.s, FT / 64);
@@ -1166,7 +1182,7 @@ static hipError_t qlaunch_xf_nr(const FusedXfArgs& a, int total_q, hipStream_t s
     const int T = a.s.K / 4;
     const bool two = T <= 2 * FT;
     if (!two && T > 6 * FT) return hipErrorInvalidValue;
-#define QX(NRV, EV) hipLaunchKernelGGL((k_gemv_quad<BITS, ZP, SM, 1, NRV, FT, WPQ, false, 1, QSCF16, EV, true>), g, b, shmem, st, a)
+#define QX(NRV, EV) hipLaunchKernelGGL((k_gemv_quad<BITS, ZP, SM, 1, NRV, FT, WPQ, false, 1, QSCF16, EV, true, GN>), g, b, shmem, st, a)
     if constexpr (FT == 512) {
         if (gx <= 256) { if (two) QX(2, true); else QX(6, true); }
         else { if (two) QX(2, false); else QX(6, false); }
@@ -1186,9 +1202,15 @@ static hipError_t qlaunch_xf_cfg(const FusedXfArgs& a, int total_q, int ft, int 
         if (a.s.K / 4 > 6 * 512) { best_ft = 1024; best_wpq = 4; }
         else { best_ft = 512; best_wpq = best_wpq >= 2 ? 2 : 1; }
     }
-    if (best_ft == 512) return best_wpq == 1 ? qlaunch_xf_nr<BITS, ZP, SM, 512, 1>(a, total_q, st) : qlaunch_xf_nr<BITS, ZP, SM, 512, 2>(a, total_q, st);
-    if (best_ft == 768) return qlaunch_xf_nr<BITS, ZP, SM, 768, 3>(a, total_q, st);
-    return qlaunch_xf_nr<BITS, ZP, SM, 1024, 4>(a, total_q, st);
+    // GLU_NORM has instantiations of its own (GN): the ones NORM and GLU run on stay as they were
+    if (a.xf_kind == 4) {
+        if (best_ft == 512) return best_wpq == 1 ? qlaunch_xf_nr<BITS, ZP, SM, 512, 1, true>(a, total_q, st) : qlaunch_xf_nr<BITS, ZP, SM, 512, 2, true>(a, total_q, st);
+        if (best_ft == 768) return qlaunch_xf_nr<BITS, ZP, SM, 768, 3, true>(a, total_q, st);
+        return qlaunch_xf_nr<BITS, ZP, SM, 1024, 4, true>(a, total_q, st);
+    }
+    if (best_ft == 512) return best_wpq == 1 ? qlaunch_xf_nr<BITS, ZP, SM, 512, 1, false>(a, total_q, st) : qlaunch_xf_nr<BITS, ZP, SM, 512, 2, false>(a, total_q, st);
+    if (best_ft == 768) return qlaunch_xf_nr<BITS, ZP, SM, 768, 3, false>(a, total_q, st);
+    return qlaunch_xf_nr<BITS, ZP, SM, 1024, 4, false>(a, total_q, st);
 }
 
 template <int BITS>
@@ -1220,7 +1242,7 @@ hipError_t QXENTRY(TMAC_QUAD_BITS, TMAC_QUAD_SCF16)(const FusedXfArgs& a, int to
 #if TMAC_QUAD_BITS == 2 && TMAC_QUAD_SCF16 == 0
 hipError_t launch_gemv_quad_xf(const FusedXfArgs& a_in, int ft, int wpq, bool strict, hipStream_t st) {
     if (!gemv_quad_supported(a_in.s) || a_in.s.K > QUAD_XF_MAX_K || a_in.nmat < 1 || a_in.nmat > 4 || !a_in.acc_mfma || a_in.dump ||
-        (a_in.xf_kind != 1 && a_in.xf_kind != 2))
+        (a_in.xf_kind != 1 && a_in.xf_kind != 2 && a_in.xf_kind != 4) || (a_in.xf_kind == 4 && (!a_in.in2 || !a_in.gamma)))
         return hipErrorInvalidValue;
     FusedXfArgs a = a_in;
     fused_precompute(a);

@@ -203,9 +203,21 @@ __device__ __forceinline__ void xf_rows_t8(const XA& a, const void* __restrict__
         for (int i = 0; i < 8; ++i) t[i] = __fadd_rn(t[i], u[i]);
     }
 }
+// GLU: g = silu(fp32(in)) * fp32(in2) of (row n, pair p), k_gemv_quad's expression with in2[n] in the activations' dtype -- the row pass of a
+// GLU_NORM and every builder form it with this one function, so the builders recompute the g the row's sum was taken over, bit for bit
+template <class XA>
+__device__ __forceinline__ void xf_rows_g8(const XA& a, const void* __restrict__ B, bool f16, int K, int n, int p, float (&x)[8]) {
+    float u[8];
+    xf_rows_ld8(B, f16, K, n, p, x);
+    xf_rows_ld8(a.in2, f16, K, n, p, u);
+    // silu(v) = v / (1 + exp(-v)): hardware exp2 and reciprocal, as in k_gemv_quad
+#pragma unroll
+    for (int i = 0; i < 8; ++i)
+        x[i] = __fmul_rn(__fmul_rn(x[i], __builtin_amdgcn_rcpf(__fadd_rn(1.0f, __expf(-x[i])))), u[i]);
+}
 // The transformed x[8] of (row n, pair p): what an XF instantiation of an N > 1 LUT builder (and the tap, k_xf_rows_tap) takes in place
 // of its activation load.  NORM: (t * gamma) * r[n], k_gemv_quad's association (gamma first), r[n] from k_xf_rows; without gamma x = t
-// untouched.  GLU: k_gemv_quad's expression with in2[n] in the activations' dtype.  n is the row EVERY operand is read at: a builder
+// untouched.  GLU: xf_rows_g8.  GLU_NORM (kind 4): (g * gamma) * r[n], r[n] from k_xf_rows' sum over g.  n is the row EVERY operand is read at: a builder
 // that clamps padding rows passes the clamped row, so nothing is read beyond row N - 1.
 template <class XA>
 __device__ __forceinline__ void xf_rows_x8(const XA& a, const void* __restrict__ B, bool f16, int K, int n, int p, float (&x)[8]) {
@@ -219,13 +231,14 @@ __device__ __forceinline__ void xf_rows_x8(const XA& a, const void* __restrict__
             for (int i = 0; i < 8; ++i) x[i] = __fmul_rn(__fmul_rn(x[i], g[i]), r);
         }
     } else {
-        float u[8];
-        xf_rows_ld8(B, f16, K, n, p, x);
-        xf_rows_ld8(a.in2, f16, K, n, p, u);
-        // silu(v) = v / (1 + exp(-v)): hardware exp2 and reciprocal, as in k_gemv_quad
+        xf_rows_g8(a, B, f16, K, n, p, x);
+        if (a.kind == 4) {
+            float g[8];
+            xf_rows_ld8(a.gamma, false, K, 0, p, g);
+            const float r = a.r[n];
 #pragma unroll
-        for (int i = 0; i < 8; ++i)
-            x[i] = __fmul_rn(__fmul_rn(x[i], __builtin_amdgcn_rcpf(__fadd_rn(1.0f, __expf(-x[i])))), u[i]);
+            for (int i = 0; i < 8; ++i) x[i] = __fmul_rn(__fmul_rn(x[i], g[i]), r);
+        }
     }
 }
 template <class XA> __device__ __forceinline__ const XA& xf_rows_arg(const XA& a) { return a; }

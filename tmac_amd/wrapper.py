@@ -423,14 +423,16 @@ class TMACGeMMWrapper:
         check(B.lib().tmac_hip_chain_record_gather(_ptr(send_dev), _ptr(recv_dev), bytes_per_rank, rank, world))
 
     CARRY = "carry"
+    _XF_KINDS = {None: 0, "norm": 1, "glu": 2, "glu_norm": 4}      # TMAC_XF_* (3 is not a kind)
 
     def chain_xform(self, kind: str, in2=None, residual=None, gamma=None, eps: float = 1e-5, residual_out=None, keep: bool = False) -> None:
         """while recording a chain: a vector transform of the NEXT ``fused`` call's activations, applied inside its LUT build
         (tmac_hip_chain_xform).  kind "norm": t = in + residual (fp32 tensor, None, or ``TMACGeMMWrapper.CARRY`` = the t the latest
         kept NORM left in LDS); x = t * rsqrt(mean(t^2) + eps) * gamma (x = t without gamma); residual_out: t also goes to memory;
-        keep: leave t for a later CARRY.  kind "glu": x = silu(in) * in2."""
+        keep: leave t for a later CARRY.  kind "glu": x = silu(in) * in2.  kind "glu_norm": g = silu(in) * in2, x = g * rsqrt(mean(g^2) +
+        eps) * gamma (gamma required, no residual operand); recorded only where the gate/up call in front publishes g itself."""
         xf = B.XForm()
-        xf.kind = {"norm": 1, "glu": 2}[kind]
+        xf.kind = {k: v for k, v in self._XF_KINDS.items() if k is not None}[kind]
         xf.in2 = _ptr(in2) if in2 is not None else None
         xf.residual = 1 if residual is TMACGeMMWrapper.CARRY else (_ptr(residual) if residual is not None else None)
         xf.gamma = _ptr(gamma) if gamma is not None else None
@@ -445,7 +447,7 @@ class TMACGeMMWrapper:
     def fused_xf(self, weights_list, B_dev, C_list, kind, in2=None, residual=None, gamma=None, eps: float = 1e-5, residual_out=None,
                  act_dtype: Optional[int] = None, out_dtype: Optional[int] = None, stream=None) -> None:
         """``fused`` (N = 1) with a vector transform of the activations applied inside the kernel's LUT build
-        (tmac_hip_qgemm_fused_xf_dev): kind "norm" / "glu" as in ``chain_xform``, or None (a plain ``fused`` call).  Outside a
+        (tmac_hip_qgemm_fused_xf_dev): kind "norm" / "glu" / "glu_norm" as in ``chain_xform``, or None (a plain ``fused`` call).  Outside a
         recording the call launches by itself -- residual ``CARRY`` is refused there, and residual_out must not overlap a vector the
         call reads; inside ``record_chain()`` it records the transform and the call."""
         n = len(weights_list)
@@ -454,7 +456,7 @@ class TMACGeMMWrapper:
         if out_dtype is None:
             out_dtype = _dtype_code(C_list[0])
         xf = B.XForm()
-        xf.kind = {None: 0, "norm": 1, "glu": 2}[kind]
+        xf.kind = TMACGeMMWrapper._XF_KINDS[kind]
         xf.in2 = _ptr(in2) if in2 is not None else None
         xf.residual = 1 if residual is TMACGeMMWrapper.CARRY else (_ptr(residual) if residual is not None else None)
         xf.gamma = _ptr(gamma) if gamma is not None else None
@@ -472,7 +474,7 @@ class TMACGeMMWrapper:
     @staticmethod
     def _xform_rows(kind, in2, residual, gamma, eps, residual_out) -> "B.XForm":
         xf = B.XForm()
-        xf.kind = {None: 0, "norm": 1, "glu": 2}[kind]
+        xf.kind = TMACGeMMWrapper._XF_KINDS[kind]
         xf.in2 = _ptr(in2) if in2 is not None else None
         xf.residual = 1 if residual is TMACGeMMWrapper.CARRY else (_ptr(residual) if residual is not None else None)
         xf.gamma = _ptr(gamma) if gamma is not None else None
