@@ -65,18 +65,21 @@ int ggml_tmac_hip_mul_mat_dev(const struct tmac_ggml_tensor* const* w, int nw, c
  *   kind 1 (norm)  t = x + residual (fp32 [K], or NULL: t = x);  x' = norm_weight ? rmsnorm(t, eps) * norm_weight : t;  residual_out (fp32 [K],
  *                  optional) receives t.  residual_out must not overlap x, residual, norm_weight or an output: a residual stream alternates
  *                  between two buffers
- *   kind 2 (glu)   x' = silu(x) * in2;  in2 has x's dtype
- *   kind 4 (glu_norm)  g = silu(x) * in2;  x' = rmsnorm(g, eps) * norm_weight (required) -- BitNet's ffn_sub_norm in front of the down
+ *   kind 2 (glu)   x' = gate(x) * in2;  in2 has x's dtype
+ *   kind 4 (glu_norm)  g = gate(x) * in2;  x' = rmsnorm(g, eps) * norm_weight (required) -- BitNet's ffn_sub_norm in front of the down
  *                  projection.  residual and residual_out must be NULL
+ *   The gate of kinds 2 and 4 travels in bits 8..15 of `kind` (tmac_hip.h): kind | TMAC_XF_GATE_SILU (0, the default: silu), |
+ *   TMAC_XF_GATE_RELU2 (0x100: max(x, 0)^2, BitNet b1.58 2B-4T) or | TMAC_XF_GATE_GELU (0x200: tanh-approximated GELU, GeGLU decoders);
+ *   kind 0x104 is relu(x)^2 * in2 followed by the sub-norm.  Gate bits on kind 1, or another gate value, are refused by the library.
  * All weights of the call consume x'.  Such a call is never queued: with deferral on it flushes the queue, then launches. */
-int ggml_tmac_hip_mul_mat_dev_xf(const struct tmac_ggml_tensor* const* w, int nw, const void* x_dev, int x_is_f32, int kind /* 1 norm, 2 glu, 4 glu_norm */,
+int ggml_tmac_hip_mul_mat_dev_xf(const struct tmac_ggml_tensor* const* w, int nw, const void* x_dev, int x_is_f32, int kind /* 1 norm, 2 glu, 4 glu_norm, the last two | TMAC_XF_GATE_* */,
                                  const void* in2_dev, const float* residual, const float* norm_weight, float eps, float* residual_out,
                                  void* const* dst_dev, int dst_is_f32);
 /* The same for n_rows rows of x (tmac_hip.h: tmac_hip_qgemm_fused_xf_rows_dev), so that the hook serves decode, a small batch and prefill
  * with one formula: x and in2 [n_rows][K], residual and residual_out fp32 [n_rows][K], norm_weight fp32 [K] shared by the rows, outputs
  * [n_rows][M] each.  n_rows = 1 is the call above.  For n_rows >= 2 the operator runs inside the LUT build of the route the plain mat-mul
  * of that many rows takes; residual_out must not overlap x, residual, norm_weight, in2 or an output. */
-int ggml_tmac_hip_mul_mat_dev_xf_rows(const struct tmac_ggml_tensor* const* w, int nw, const void* x_dev, int x_is_f32, int kind /* 1 norm, 2 glu, 4 glu_norm */,
+int ggml_tmac_hip_mul_mat_dev_xf_rows(const struct tmac_ggml_tensor* const* w, int nw, const void* x_dev, int x_is_f32, int kind /* 1 norm, 2 glu, 4 glu_norm, the last two | TMAC_XF_GATE_* */,
                                       const void* in2_dev, const float* residual, const float* norm_weight, float eps, float* residual_out,
                                       void* const* dst_dev, int dst_is_f32, int n_rows);
 int ggml_tmac_hip_set_deferred(int on);
@@ -116,12 +119,18 @@ int ggml_tmac_hip_synchronize(void);
  *     ggml_tmac_hip_segment_end(&seg);
  * _glu_norm is recorded only in this form -- gate and up are outputs 0 and 1 of ONE _mul_mat and nothing else in the segment reads gate --
  * where the gate/up call publishes silu(gate) * up itself; any other form makes _end return non-zero, and the caller issues the segment
- * call by call with ggml_tmac_hip_mul_mat_dev_xf(kind 4) in front of down. */
+ * call by call with ggml_tmac_hip_mul_mat_dev_xf(kind 4) in front of down.
+ * Other gates: _glu and _glu_norm are _glu_gate(in2, TMAC_XF_GATE_SILU, NULL | norm_weight, eps).  A BitNet b1.58 2B-4T layer
+ * (ffn_sub_norm(relu(gate)^2 * up) in front of down) declares ggml_tmac_hip_segment_glu_gate(up, TMAC_XF_GATE_RELU2, ffn_sub_norm_w, eps)
+ * in the place of _glu_norm above, a GeGLU decoder ggml_tmac_hip_segment_glu_gate(up, TMAC_XF_GATE_GELU, NULL, 0) in the place of _glu;
+ * call by call the same layer issues ggml_tmac_hip_mul_mat_dev_xf(kind 4 | TMAC_XF_GATE_RELU2) / (kind 2 | TMAC_XF_GATE_GELU).  A gate other
+ * than the three TMAC_XF_GATE_* values is refused (non-zero, nothing declared). */
 typedef struct ggml_tmac_hip_segment ggml_tmac_hip_segment;
 int ggml_tmac_hip_segment_begin(void);
 int ggml_tmac_hip_segment_norm(const float* residual, int residual_is_kept, const float* norm_weight, float eps, float* residual_out, int keep);
 int ggml_tmac_hip_segment_glu(const void* in2_f16);
 int ggml_tmac_hip_segment_glu_norm(const void* in2_f16, const float* norm_weight, float eps);
+int ggml_tmac_hip_segment_glu_gate(const void* in2_f16, int gate /* TMAC_XF_GATE_* */, const float* norm_weight /* NULL: plain GLU */, float eps);
 int ggml_tmac_hip_segment_mul_mat(const struct tmac_ggml_tensor* const* w, int nw, const void* x_f16, void* const* dst_f16);
 /* the same with x as an fp32 vector in device memory that no earlier mat-mul of the segment wrote (ggml's graphs are fp32: the output of
  * the attention operator in front of the o projection, the token embedding in front of the first q/k/v): the tables are built from the

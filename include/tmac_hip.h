@@ -234,7 +234,7 @@ int32_t tmac_hip_chain_status(tmac_hip_chain* chain, uint32_t* error_word);
 int32_t tmac_hip_chain_info(const tmac_hip_chain* chain, int op, int32_t* nops, int32_t* wpq, int32_t* grid, size_t* bytes);
 int32_t tmac_hip_chain_free(tmac_hip_chain* chain);
 /* Vector transforms inside the chain.  Between two mpGEMMs of a decoder layer sit element-wise operators the hot path does not own
- * (residual add + RMSNorm in front of q/k/v and gate/up, silu(gate) * up in front of the down projection); as kernels of their own they
+ * (residual add + RMSNorm in front of q/k/v and gate/up, gate(gate) * up in front of the down projection); as kernels of their own they
  * would end the persistent launch after every call.  Every workgroup of the chain holds a call's whole activation vector when it builds
  * the LUT, so these operators are applied THERE: tmac_hip_chain_xform, while recording, describes a transform of the activations of the
  * NEXT recorded tmac_hip_qgemm_fused_dev call (B_dev = `in`).  fp32 arithmetic; the LUT is built from the fp32 result.
@@ -245,14 +245,15 @@ int32_t tmac_hip_chain_free(tmac_hip_chain* chain);
  *                 vector an EARLIER call of the chain reads from memory only when a hand-off path from a call in which every workgroup
  *                 owns rows leads to this one (the in-place residual stream of a decoder segment); never the vectors this or a later
  *                 call reads (a later NORM takes TMAC_XF_CARRY), never an output
- *   TMAC_XF_GLU   x = silu(in) * in2;  in2: fp16 [K], an earlier output of the chain (handed over like `in`) or external memory -- of the
- *                 same kind as `in`; K <= 12288
+ *   TMAC_XF_GLU   x = gate(in) * in2;  in2: fp16 [K], an earlier output of the chain (handed over like `in`) or external memory -- of the
+ *                 same kind as `in`; K <= 12288.  gate: silu unless bits 8..15 of `kind` name another (TMAC_XF_GATE_*, below)
  *                 (when `in` and `in2` are outputs 0 and 1 of one earlier two-matrix call of the chain and nothing else reads output 0 through a
- *                 hand-off, that call publishes silu(in) * in2 itself, once per row, rounded to fp16 like every handed-over vector)
- *   TMAC_XF_GLU_NORM  g = silu(in) * in2;  x = g * (1 / sqrt(mean(g^2) + eps)) * gamma -- the sub-layer norm BitNet b1.58 puts between
- *                 silu(gate) * up and the down projection (ffn_sub_norm).  in2 as for a GLU; gamma (fp32 [K]) is required; residual,
+ *                 hand-off, that call publishes gate(in) * in2 itself, once per row, rounded to fp16 like every handed-over vector)
+ *   TMAC_XF_GLU_NORM  g = gate(in) * in2;  x = g * (1 / sqrt(mean(g^2) + eps)) * gamma -- the sub-layer norm BitNet b1.58 puts between
+ *                 gate(gate) * up and the down projection (ffn_sub_norm; silu in the 3B checkpoints, relu^2 in 2B-4T).  in2 as for a GLU;
+ *                 gamma (fp32 [K]) is required; residual,
  *                 residual_out and keep must be NULL / 0 (TMAC_HIP_E_ARG names the field).  Recorded in the PRODUCER FORM ONLY: `in` and
- *                 `in2` are outputs 0 and 1 of one earlier two-matrix call that publishes silu(in) * in2 itself (the rule in brackets
+ *                 `in2` are outputs 0 and 1 of one earlier two-matrix call that publishes gate(in) * in2 itself (the rule in brackets
  *                 above), and this call is then a NORM without residual of that handed-over vector; K <= 12288.  Every other form --
  *                 vectors in memory, gate and up from two calls, a gathered output, TMAC_CHAIN_GLU_EPILOGUE=0, a waves-per-quad choice
  *                 that cannot deal row pairs -- is TMAC_HIP_E_NOMATCH from tmac_hip_chain_end: issue the calls one by one
@@ -266,11 +267,24 @@ int32_t tmac_hip_chain_free(tmac_hip_chain* chain);
  * from the memory an earlier call wrote as residual_out, and an in-place residual stream alternates between two buffers (see there).
  * tmac_hip_chain_launch itself falls back to nothing.  A transform declared in front of a call that is rejected is dropped with it.
  * in2, residual (unless TMAC_XF_CARRY), gamma and residual_out are 16-byte aligned; a transform naming a vector that is not is refused with
- * TMAC_HIP_E_ARG and declares nothing. */
+ * TMAC_HIP_E_ARG and declares nothing.
+ * THE GATE of a GLU / GLU_NORM travels in bits 8..15 of `kind`; the low byte is the kind.  kind = TMAC_XF_GLU_NORM | TMAC_XF_GATE_RELU2
+ * reads g = relu(in)^2 * in2, then the sub-norm (BitNet b1.58 2B-4T's FFN); TMAC_XF_GLU | TMAC_XF_GATE_GELU is a GeGLU.  fp32:
+ *   silu   v / (1 + exp(-v)), hardware exp and reciprocal: specified to a tolerance
+ *   relu2  m = max(v, 0);  g = (m * m) * in2, each product rounded to nearest: exact arithmetic, specified to the bit
+ *   gelu   the tanh form, written as the silu expression with z = 1.5957691216 v (1 + 0.044715 v^2) inside the exponential
+ *          (0.5 (1 + tanh y) = 1 / (1 + exp(-2 y))): specified to a tolerance like silu
+ * Refused with TMAC_HIP_E_ARG and a message naming the gate, by the one check tmac_hip_chain_xform, tmac_hip_qgemm_fused_xf_dev and
+ * tmac_hip_qgemm_fused_xf_rows_dev share: gate bits on TMAC_XF_NONE or TMAC_XF_NORM, a gate value other than the three, any bit above 15.
+ * (A low byte that is no kind -- 3, whatever the gate -- stays "unknown transform kind".)  The gate changes no rule above: routes, limits
+ * and the producer form are those of the kind. */
 #define TMAC_XF_NONE 0
 #define TMAC_XF_NORM 1
 #define TMAC_XF_GLU 2
 #define TMAC_XF_GLU_NORM 4   /* (3 is not a kind) */
+#define TMAC_XF_GATE_SILU  0x000   /* v / (1 + exp(-v))                                   (the default) */
+#define TMAC_XF_GATE_RELU2 0x100   /* max(v, 0)^2                                                       */
+#define TMAC_XF_GATE_GELU  0x200   /* tanh form: v / (1 + exp(-z)),  z = 1.5957691216f * v * (1 + 0.044715f * v * v) */
 #define TMAC_XF_CARRY ((const float*)1)
 typedef struct {
     int32_t kind;
@@ -290,13 +304,15 @@ int32_t tmac_hip_chain_xform(const tmac_hip_xform* xf);
  *                  LUT is built from the fp32 x by the code of the plain call, so without gamma the outputs are those of a plain call on t,
  *                  bit for bit.  residual_out (fp32 [K], optional) receives t: each element is written once, pair p (8 elements) by
  *                  workgroup p mod grid.  `keep` is accepted and ignored; residual == TMAC_XF_CARRY is refused (TMAC_HIP_E_ARG)
- *   TMAC_XF_GLU    x = silu(in) * in2;  in2 has act_dtype like `in` (fp16 or fp32); hardware exp and reciprocal, specified to a tolerance
- *   TMAC_XF_GLU_NORM  g = silu(in) * in2, the GLU's expression;  x = (g * gamma) * rsq(fma(sum g^2, rcp(K), eps)), the NORM's association
+ *   TMAC_XF_GLU    x = gate(in) * in2;  in2 has act_dtype like `in` (fp16 or fp32); silu and gelu: hardware exp and reciprocal, specified
+ *                  to a tolerance; relu2: exact, (max(in, 0) * max(in, 0)) * in2 to the bit (TMAC_XF_GATE_* above)
+ *   TMAC_XF_GLU_NORM  g = gate(in) * in2, the GLU's expression;  x = (g * gamma) * rsq(fma(sum g^2, rcp(K), eps)), the NORM's association
  *                  and reduction.  gamma is required; residual, residual_out and keep must be NULL / 0
  * Scope: what tmac_hip_qgemm_fused_dev serves with k_gemv_quad at N = 1 -- QUAD layout, 1- to 4-bit, per-group scales (group size >= 64,
  * act groups of 64) or unified scales (m_groups >= 1), MFMA accumulate -- for K up to 24576, the kernel's own limit (the transformed
  * vector stays in registers, no LDS is added).  Anything else: TMAC_HIP_E_NOMATCH, nothing is launched.
- * Refused with TMAC_HIP_E_ARG before anything is launched: a kind other than 0, 1, 2, 4; GLU without in2; GLU_NORM without in2 or gamma, or
+ * Refused with TMAC_HIP_E_ARG before anything is launched: a kind (low byte) other than 0, 1, 2, 4; gate bits (8..15) on kind 0 or 1, a gate
+ * other than TMAC_XF_GATE_SILU / _RELU2 / _GELU, any bit above 15 (the message names the gate); GLU without in2; GLU_NORM without in2 or gamma, or
  * with residual, residual_out or keep set (the message names the field); in2 / residual / gamma / residual_out
  * not 16-byte aligned (B_dev and C_dev[i] as everywhere); residual_out overlapping B_dev, residual, gamma or a C_dev[i] -- every
  * workgroup reads the whole of the inputs while one workgroup writes each pair of residual_out, so an in-place residual stream has no
@@ -305,7 +321,7 @@ int32_t tmac_hip_chain_xform(const tmac_hip_xform* xf);
  * for both modes, the chain's rules apply there.  With deferral on a transformed call is never queued: it flushes the queue, then
  * launches (a failed flush returns its status and nothing is launched).
  * Launch configuration: tmac_hip_debug_quad_config and the tuned table are honoured; the transformed instantiations exist for (threads,
- * waves per quad) = (512,1), (512,2), (768,3), (1024,4) -- once for NORM / GLU and once for GLU_NORM.  A forced configuration outside that set is TMAC_HIP_E_NOMATCH; a tuned or
+ * waves per quad) = (512,1), (512,2), (768,3), (1024,4) -- once for NORM / GLU and once for GLU_NORM, each serving the three gates.  A forced configuration outside that set is TMAC_HIP_E_NOMATCH; a tuned or
  * heuristic choice outside it runs on the nearest member (same waves per quad with 512 threads; (1024,4) for K > 12288). */
 int32_t tmac_hip_qgemm_fused_xf_dev(const tmac_hip_weights* const* weights, int nmat, const void* B_dev, tmac_dtype_t act_dtype,
                                     const tmac_hip_xform* xf, void* const* C_dev, tmac_dtype_t out_dtype, void* stream);
@@ -319,7 +335,8 @@ int32_t tmac_hip_qgemm_fused_xf_dev(const tmac_hip_weights* const* weights, int 
  *            x by the plain build's code, and the kernel behind it is the plain call's.  NORM with gamma or residual_out is preceded by
  *            one row pass (k_xf_rows, a workgroup per row) that writes residual_out -- every element once -- and the row's
  *            r = rsq(fma(sum t^2, rcp(K), eps)); the builders then form (t * gamma) * r.  GLU_NORM always takes the row pass: it sums g^2 in
- *            the same order and writes r alone; the builders recompute g with the row pass's own function and form (g * gamma) * r.
+ *            the same order and writes r alone; the builders recompute g with the row pass's own function (whatever the gate) and form
+ *            (g * gamma) * r.
  *            The order of that sum depends on K alone: a row
  *            gives the same x whatever N, its index or the route.  (At N = 1 k_gemv_quad sums in its own order: the two forms agree to
  *            rounding, not bits, for NORM with gamma.)  Where the plain call would run k_gemv_quad with one LUT build per workgroup, the
@@ -327,7 +344,7 @@ int32_t tmac_hip_qgemm_fused_xf_dev(const tmac_hip_weights* const* weights, int 
  * Scope (N >= 2): QUAD layout, 1- to 4-bit, act groups of 64 or unified scales with K <= 12288, one configuration per call.
  * TMAC_HIP_E_NOMATCH, nothing launched: anything outside that scope, a plan that would need the three-layout LUT build, the
  * reference-layout variant, fast-aggregation weights.  TMAC_HIP_E_ARG, nothing launched: the refusals of the N = 1 form with extents
- * x N -- kind other than 0, 1, 2, 4, GLU without in2, GLU_NORM's own refusals, TMAC_XF_CARRY, a transform vector below 16-byte alignment, residual_out overlapping B_dev,
+ * x N -- kind other than 0, 1, 2, 4, the gate's refusals, GLU without in2, GLU_NORM's own refusals, TMAC_XF_CARRY, a transform vector below 16-byte alignment, residual_out overlapping B_dev,
  * residual, gamma, in2 or an output (the LUT build reads `in` and `residual` after the row pass has written residual_out: alternate
  * between two buffers).
  * While the thread records a chain an N >= 2 transformed call is TMAC_HIP_E_NOMATCH: nothing is recorded, no transform stays pending.
@@ -342,7 +359,7 @@ int32_t tmac_hip_qgemm_fused_xf_rows_dev(const tmac_hip_weights* const* weights,
  * refusals come back as from the call (the scope checks of the call itself are not repeated). */
 int32_t tmac_hip_debug_xf_rows_plan(const tmac_hip_weights* const* weights, int nmat, void* const* C_dev, int N, int32_t* route, int32_t* lut);
 /* Parity tap: the fp32 x [N][K] that the LUT builds of the call above consume (the row pass plus a store around the builders' own load;
- * residual_out is written as the call writes it).  kind NORM, GLU or GLU_NORM; argument rules as above; synchronises the stream. */
+ * residual_out is written as the call writes it).  kind NORM, GLU or GLU_NORM (the last two with any gate); argument rules as above; synchronises the stream. */
 int32_t tmac_hip_debug_xf_rows(const void* B_dev, tmac_dtype_t act_dtype, const tmac_hip_xform* xf, int K, int N, float* x_out_dev,
                                void* stream);
 /* Row-sharded chains (one process per GPU; weight ROWS split over the ranks).  While recording, the exchange step between

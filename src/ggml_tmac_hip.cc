@@ -169,7 +169,8 @@ extern "C" int ggml_tmac_hip_mul_mat_dev_xf(const struct tmac_ggml_tensor* const
                                             void* const* dst_dev, int dst_is_f32) {
     if (!g_ready) return fail("ggml_tmac_hip_init has not been called");
     if (!w || nw < 1 || nw > 4 || !x_dev || !dst_dev) return fail("bad mul_mat_dev_xf");
-    if (kind != TMAC_XF_NORM && kind != TMAC_XF_GLU && kind != TMAC_XF_GLU_NORM) return fail("mul_mat_dev_xf: kind must be 1 (norm), 2 (glu) or 4 (glu_norm)");
+    const int base = kind & 0xff;      // bits 8..15: the gate of a glu / glu_norm (TMAC_XF_GATE_*), checked by the library
+    if (base != TMAC_XF_NORM && base != TMAC_XF_GLU && base != TMAC_XF_GLU_NORM) return fail("mul_mat_dev_xf: kind must be 1 (norm), 2 (glu) or 4 (glu_norm), the last two | a TMAC_XF_GATE_*");
     g_err[0] = 0;
     const tmac_hip_weights* wl[4];
     void* cl[4];
@@ -181,9 +182,9 @@ extern "C" int ggml_tmac_hip_mul_mat_dev_xf(const struct tmac_ggml_tensor* const
     tmac_hip_xform xf;
     memset(&xf, 0, sizeof(xf));
     xf.kind = kind;
-    if (kind == TMAC_XF_GLU) xf.in2 = in2_dev;
+    if (base == TMAC_XF_GLU) xf.in2 = in2_dev;
     else { xf.residual = residual; xf.gamma = norm_weight; xf.eps = eps; xf.residual_out = residual_out; }
-    if (kind == TMAC_XF_GLU_NORM) xf.in2 = in2_dev;      // (a residual operand set here is refused by the library, which names the field)
+    if (base == TMAC_XF_GLU_NORM) xf.in2 = in2_dev;      // (a residual operand set here is refused by the library, which names the field)
     return tmac_hip_qgemm_fused_xf_dev(wl, nw, x_dev, x_is_f32 ? TMAC_F32 : TMAC_F16, &xf, cl, dst_is_f32 ? TMAC_F32 : TMAC_F16, g_stream);
 }
 // ... and for n_rows rows of x (tmac_hip_qgemm_fused_xf_rows_dev): prefill or a small batch through the same hook
@@ -192,7 +193,8 @@ extern "C" int ggml_tmac_hip_mul_mat_dev_xf_rows(const struct tmac_ggml_tensor* 
                                                  void* const* dst_dev, int dst_is_f32, int n_rows) {
     if (!g_ready) return fail("ggml_tmac_hip_init has not been called");
     if (!w || nw < 1 || nw > 4 || !x_dev || !dst_dev || n_rows < 1) return fail("bad mul_mat_dev_xf_rows");
-    if (kind != TMAC_XF_NORM && kind != TMAC_XF_GLU && kind != TMAC_XF_GLU_NORM) return fail("mul_mat_dev_xf_rows: kind must be 1 (norm), 2 (glu) or 4 (glu_norm)");
+    const int base = kind & 0xff;      // bits 8..15: the gate of a glu / glu_norm (TMAC_XF_GATE_*), checked by the library
+    if (base != TMAC_XF_NORM && base != TMAC_XF_GLU && base != TMAC_XF_GLU_NORM) return fail("mul_mat_dev_xf_rows: kind must be 1 (norm), 2 (glu) or 4 (glu_norm), the last two | a TMAC_XF_GATE_*");
     g_err[0] = 0;
     const tmac_hip_weights* wl[4];
     void* cl[4];
@@ -204,9 +206,9 @@ extern "C" int ggml_tmac_hip_mul_mat_dev_xf_rows(const struct tmac_ggml_tensor* 
     tmac_hip_xform xf;
     memset(&xf, 0, sizeof(xf));
     xf.kind = kind;
-    if (kind == TMAC_XF_GLU) xf.in2 = in2_dev;
+    if (base == TMAC_XF_GLU) xf.in2 = in2_dev;
     else { xf.residual = residual; xf.gamma = norm_weight; xf.eps = eps; xf.residual_out = residual_out; }
-    if (kind == TMAC_XF_GLU_NORM) xf.in2 = in2_dev;      // (a residual operand set here is refused by the library, which names the field)
+    if (base == TMAC_XF_GLU_NORM) xf.in2 = in2_dev;      // (a residual operand set here is refused by the library, which names the field)
     return tmac_hip_qgemm_fused_xf_rows_dev(wl, nw, x_dev, x_is_f32 ? TMAC_F32 : TMAC_F16, &xf, cl, dst_is_f32 ? TMAC_F32 : TMAC_F16, n_rows, g_stream);
 }
 extern "C" int ggml_tmac_hip_set_deferred(int on) { return tmac_hip_defer(on); }
@@ -247,21 +249,29 @@ extern "C" int ggml_tmac_hip_segment_norm(const float* residual, int residual_is
     return tmac_hip_chain_xform(&xf);
 }
 
-extern "C" int ggml_tmac_hip_segment_glu(const void* in2_f16) {
+// x = gate(in) * in2, or (norm_weight != NULL) the RMSNorm of that product: the one form behind _glu and _glu_norm.  The gate is checked by
+// tmac_hip_chain_xform (a value other than the three TMAC_XF_GATE_* is refused there, naming it)
+extern "C" int ggml_tmac_hip_segment_glu_gate(const void* in2_f16, int gate, const float* norm_weight, float eps) {
+    if (gate & 0xff) return fail("segment_glu_gate: gate must be a TMAC_XF_GATE_* value (bits 8..15)");
     tmac_hip_xform xf;
     memset(&xf, 0, sizeof(xf));
-    xf.kind = TMAC_XF_GLU;
+    xf.kind = (norm_weight ? TMAC_XF_GLU_NORM : TMAC_XF_GLU) | gate;
     xf.in2 = in2_f16;
+    if (norm_weight) { xf.gamma = norm_weight; xf.eps = eps; }
     return tmac_hip_chain_xform(&xf);
 }
 
+extern "C" int ggml_tmac_hip_segment_glu(const void* in2_f16) { return ggml_tmac_hip_segment_glu_gate(in2_f16, TMAC_XF_GATE_SILU, nullptr, 0.0f); }
+
 extern "C" int ggml_tmac_hip_segment_glu_norm(const void* in2_f16, const float* norm_weight, float eps) {
-    tmac_hip_xform xf;
-    memset(&xf, 0, sizeof(xf));
-    xf.kind = TMAC_XF_GLU_NORM;
-    xf.in2 = in2_f16;
-    xf.gamma = norm_weight; xf.eps = eps;
-    return tmac_hip_chain_xform(&xf);
+    // (without the weights this is no plain GLU: the library refuses a GLU_NORM without gamma, naming the field)
+    if (!norm_weight) {
+        tmac_hip_xform xf;
+        memset(&xf, 0, sizeof(xf));
+        xf.kind = TMAC_XF_GLU_NORM; xf.in2 = in2_f16; xf.eps = eps;
+        return tmac_hip_chain_xform(&xf);
+    }
+    return ggml_tmac_hip_segment_glu_gate(in2_f16, TMAC_XF_GATE_SILU, norm_weight, eps);
 }
 
 static int segment_mul_mat(const struct tmac_ggml_tensor* const* w, int nw, const void* x, tmac_dtype_t x_dtype, void* const* dst_f16) {

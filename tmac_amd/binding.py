@@ -13,6 +13,9 @@ import subprocess
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 F32, F16 = 0, 1
+# tmac_hip_xform.kind (include/tmac_hip.h): the kind in the low byte, the gate of a GLU / GLU_NORM in bits 8..15
+XF_NONE, XF_NORM, XF_GLU, XF_GLU_NORM = 0, 1, 2, 4
+XF_GATE_SILU, XF_GATE_RELU2, XF_GATE_GELU = 0x000, 0x100, 0x200
 
 
 class TMACHipError(RuntimeError):

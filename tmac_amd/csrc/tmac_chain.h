@@ -39,16 +39,18 @@ struct ChainOp {
     int m_groups;        // unified-scale flavour: scales per matrix (rows split into m_groups equal runs; qgemm.py:170-174), else 0
     int ipi_inv;         // ceil(65536 / ipi)
     // vector transform of the activations inside the LUT build (tmac_hip_chain_xform; xf_kind 0: none)
-    const void* in2;     // GLU (xf_kind 2): x = silu(in) * in2 -- a second vector of the same kind as `in` (hand-off image / fp16 memory)
+    const void* in2;     // GLU (xf_kind 2): x = gate(in) * in2 (the gate: xf_flags bits 8..9) -- a second vector of the same kind as `in` (hand-off image / fp16 memory)
     const float* res;    // NORM (xf_kind 1): t = in + res (fp32 [K] in memory; nullptr: none, or the carry: xf_flags bit 1)
     const float* gamma;  //   x = t * rsqrt(mean(t^2) + eps) * gamma (fp32 [K]); nullptr: x = t
     float* res_out;      //   t is also written here (fp32 [K]); nullptr: not written
     int xf_kind;
-    int xf_flags;        // bit 1: the residual is the t kept by an earlier NORM of this launch (LDS); bit 2: keep this op's t
+    int xf_flags;        // bit 1: the residual is the t kept by an earlier NORM of this launch (LDS); bit 2: keep this op's t;
+                         // bits 8..9: the gate of a reader-form GLU (0 silu, 1 relu^2, 2 tanh-GELU: TMAC_XF_GATE_* as they come)
     int eps_bits;        // eps as the bits of a float
-    int epi;             // 1: this op's matrices 0 and 1 are gate and up of a GLU whose only reader is a later op of the chain: the row quads of
+    int epi;             // != 0: this op's matrices 0 and 1 are gate and up of a GLU whose only reader is a later op of the chain: the row quads of
                          //    the two are dealt in pairs (workgroup ranges in units of two: q_per / q_extra count pairs; virtual quad v = matrix v & 1,
-                         //    quad v >> 1) and matrix 0's hand-off image carries silu(gate) * up, computed once per row by the publishing wave
+                         //    quad v >> 1) and matrix 0's hand-off image carries gate(gate) * up, computed once per row by the publishing wave;
+                         //    the value names the gate: 1 silu, 2 relu^2, 3 tanh-GELU
     // stream mode (tmac_stream.hip): the op's prebuilt LUT image in global memory (layout of the LDS LUT buffer) and its size in uint4, whole KB
     const void* img;
     int img_u4;
@@ -86,6 +88,8 @@ struct ChainArgs {
     const unsigned long long* tap_off;   //   tap + tap_off[op]: per-group scales int32 [4 * total_q rows][K / 64] comb = sum_p 2^p PS_p; unified scales [rows][bits] totals
     unsigned long long* stamps;    // optional [nops][grid][8] of wave 0, s_memrealtime (100 MHz): 0 op entry, 1 activations complete, 2 LUT built
                                    // (barrier passed), 3 current ring landed, 5 last quad published, 6 everything in flight landed, 7 polls
+    int gates;                     // host side only (last: the fields the kernels read keep their places): some GLU of the launch has a gate other
+                                   // than silu (xf_flags bits 8..9, epi > 1) -- the launch takes the XF instances with the gate selector (GT)
 };
 
 // one translation unit per weight width (tmac_chain.hip with -DTMAC_CHAIN_BITS=b).  sm: 0 per-group scales, 2 unified scale.

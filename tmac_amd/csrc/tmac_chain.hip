@@ -91,8 +91,12 @@ __device__ __forceinline__ void c_ext3(const uint4* p0, const uint4* p1, const u
 // stores -- per item and act group -- cost the decoder pattern, which needs XF and sets no tap, 2.8 %: 1.060 -> 1.031 ms per token)
 // G2: two scale groups per lane and item (tmac_chain_core.h), for launches that hold an op with scale groups of 64 -- instances of their own
 // (translation units tmac_chain_g2_b*), so that every other launch runs the kernels it ran before.
-template <int BITS, bool ZP, bool SCF16, int SM, bool XF, bool TAP = false, bool G2 = false>
+// GT (with XF): the gate of a GLU is a run-time choice (reader form: xf_flags bits 8..9; producer form: epi 1 / 2 / 3) -- instances of their
+// own for launches that hold a gate other than silu (ChainArgs::gates): inside the one XF instance the selector cost every instance a
+// VGPR or two and eleven of them scratch (profiles/r14_gate_resources.txt), so the silu-only launches keep the kernels they ran.
+template <int BITS, bool ZP, bool SCF16, int SM, bool XF, bool TAP = false, bool G2 = false, bool GT = false>
 __global__ __launch_bounds__(CHAIN_FT) void k_decode_chain(ChainArgs a) {
+    static_assert(!GT || XF, "the gate selector belongs to the transforms");
     extern __shared__ __attribute__((aligned(16))) uint4 lds[];
     constexpr int FT = CHAIN_FT, NWV = CHAIN_NWV;
     // fragments per ring.  The G2 instance with the transforms (XF) has no registers left for the fragments' second scale words at 2 to 4 bits
@@ -207,7 +211,8 @@ __global__ __launch_bounds__(CHAIN_FT) void k_decode_chain(ChainArgs a) {
         // cursor enters the quad, not per item: scalar instructions are issued by ONE unit per CU, and 12 waves x ~60 of
         // them per fragment were 0.4 us per fragment issued (profiles/r02_chain_prefetch_ab.txt C).
         const int qe0 = uni(d->q_end[0]), qe1 = uni(d->q_end[1]), qe2 = uni(d->q_end[2]);
-        const bool epi = XF && uni(d->epi) != 0;                              // matrices 0 / 1 dealt in pairs, silu(gate) * up published (tmac_chain.h)
+        const int egate = XF ? uni(d->epi) : 0;                               // 1 / 2 / 3: silu / relu^2 / tanh-GELU
+        const bool epi = egate != 0;                                          // matrices 0 / 1 dealt in pairs, gate(gate) * up published (tmac_chain.h)
         const int n_items = ro.nquads * ro.nsteps;
         __amdgpu_buffer_rsrc_t q_rs = __builtin_amdgcn_make_buffer_rsrc(static_cast<uint4*>(nullptr), (short)0, 0, 0x00020000);
         const TMAC_GLOBAL char* q_sc = nullptr;
@@ -269,7 +274,7 @@ __global__ __launch_bounds__(CHAIN_FT) void k_decode_chain(ChainArgs a) {
         const int nr = (P + FT - 1) / FT;                            // rounds of FT pairs (<= NRMAX, checked on the host)
         constexpr int NRMAX = 3;
         uint32_t xw[NRMAX][4];
-        // a GLU transform (x = silu(in) * in2, tmac_hip_chain_xform) reads a second vector of the same kind -- both handed over or both in
+        // a GLU transform (x = gate(in) * in2, tmac_hip_chain_xform) reads a second vector of the same kind -- both handed over or both in
         // memory -- in at most two rounds; its granules are polled together with the first vector's (one fabric round trip for both)
         const int xk = XF ? uni(d->xf_kind) : 0;
         const bool glu = XF && xk == 2;
@@ -464,8 +469,9 @@ __global__ __launch_bounds__(CHAIN_FT) void k_decode_chain(ChainArgs a) {
         // registers -- two rounds x 8 fp32 -- the kernel spilled, with a vmcnt(0) in front of the spill.
         if constexpr (XF) {
         if (xk == 2) {
-            // GLU: x = silu(in) * in2, fp32
+            // GLU: x = gate(in) * in2, fp32
             xt = l_tmp;
+            const int xgate = GT ? (xfl >> 8) & 3 : XF_GATE_SILU;
 #pragma unroll
             for (int r = 0; r < 2; ++r) {
                 const int p = r * FT + tpair;
@@ -478,9 +484,11 @@ __global__ __launch_bounds__(CHAIN_FT) void k_decode_chain(ChainArgs a) {
                         const __half2 hh = *reinterpret_cast<const __half2*>(&w2);
                         const float u0 = __low2float(hh), u1 = __high2float(hh);
                         const float a0 = __low2float(ha), a1 = __high2float(ha);
-                        // silu(a) = a / (1 + exp(-a)): hardware exp2 and reciprocal (1 ulp each; the transform is specified to a tolerance)
-                        const float y0 = __fmul_rn(__fmul_rn(a0, __builtin_amdgcn_rcpf(__fadd_rn(1.0f, __expf(-a0)))), u0);
-                        const float y1 = __fmul_rn(__fmul_rn(a1, __builtin_amdgcn_rcpf(__fadd_rn(1.0f, __expf(-a1)))), u1);
+                        // gate(a) * u, the gate by xf_flags bits 8..9 (uniform): silu, relu^2 or tanh-GELU (tmac_quad_core.h)
+                        float y[2] = {a0, a1};
+                        const float u[2] = {u0, u1};
+                        xf_gate_mul(xgate, y, u);
+                        const float y0 = y[0], y1 = y[1];
                         if (q < 2) { x0[2 * q] = y0; x0[2 * q + 1] = y1; } else { x1[2 * q - 4] = y0; x1[2 * q - 3] = y1; }
                     }
                     *xslot(xt, r, 0) = x0; *xslot(xt, r, 1) = x1;
@@ -768,11 +776,14 @@ __global__ __launch_bounds__(CHAIN_FT) void k_decode_chain(ChainArgs a) {
                 const uint32_t hb = (uint32_t)__half_as_ushort(__float2half_rn(t));
                 uint32_t pb = hb;                                        // what the hand-off image carries: the fp16 output, or ...
                 if (epi) {
-                    // ... silu(gate) * up: the up quad of this row pair sits four lanes up (slot qs + 1, same DPP row); from the fp16
+                    // ... gate(gate) * up (epi 1 / 2 / 3: silu / relu^2 / tanh-GELU): the up quad of this row pair sits four lanes up (slot qs + 1, same DPP row); from the fp16
                     // values a reader would see, fp32 arithmetic, rounded to the fp16 the image holds
                     const uint32_t ub = qdpp_u<0x104>(hb);               // row_shl:4
                     const float gv = __half2float(__ushort_as_half((unsigned short)hb)), uv = __half2float(__ushort_as_half((unsigned short)ub));
-                    const float xv = __fmul_rn(__fmul_rn(gv, __builtin_amdgcn_rcpf(__fadd_rn(1.0f, __expf(-gv)))), uv);
+                    float xv1[1] = {gv};
+                    const float uv1[1] = {uv};
+                    xf_gate_mul(GT ? egate - 1 : XF_GATE_SILU, xv1, uv1);
+                    const float xv = xv1[0];
                     if (p_mi == 0) pb = (uint32_t)__half_as_ushort(__float2half_rn(xv));
                 }
                 const uint32_t nb = qdpp_u<0xB1>(pb);                    // quad_perm [1,0,3,2]: the neighbour's value
@@ -847,11 +858,11 @@ constexpr int CB = TMAC_CHAIN_BITS;
 #endif
 constexpr bool CG2 = TMAC_CHAIN_G2_TU != 0;
 
-template <bool ZP, bool SCF16, int SM, bool XF, bool TAP>
+template <bool ZP, bool SCF16, int SM, bool XF, bool TAP, bool GT = false>
 static hipError_t chain_launch_x(const ChainArgs& a, int grid, size_t lds_bytes, hipStream_t st, int* resident) {
     if constexpr (CG2 && SM != 0) return hipErrorInvalidValue;      // (unified scales have one scale per matrix: no G2 instance)
     else {
-    auto* kern = &k_decode_chain<CB, ZP, SCF16, SM, XF, TAP, CG2>;
+    auto* kern = &k_decode_chain<CB, ZP, SCF16, SM, XF, TAP, CG2, GT>;
     if (lds_bytes > 64 * 1024) {
         hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);
         if (e != hipSuccess) return e;
@@ -865,6 +876,8 @@ static hipError_t chain_launch_x(const ChainArgs& a, int grid, size_t lds_bytes,
 
 template <bool ZP, bool SCF16, int SM>
 static hipError_t chain_launch_one(const ChainArgs& a, int grid, size_t lds_bytes, hipStream_t st, int* resident) {
+    if (a.gates)       // a GLU with a gate other than silu: the XF instances with the selector
+        return a.tap ? chain_launch_x<ZP, SCF16, SM, true, true, true>(a, grid, lds_bytes, st, resident) : chain_launch_x<ZP, SCF16, SM, true, false, true>(a, grid, lds_bytes, st, resident);
     if (a.tap) return chain_launch_x<ZP, SCF16, SM, true, true>(a, grid, lds_bytes, st, resident);      // (the tap's instance carries the extensions too)
     return a.xforms ? chain_launch_x<ZP, SCF16, SM, true, false>(a, grid, lds_bytes, st, resident) : chain_launch_x<ZP, SCF16, SM, false, false>(a, grid, lds_bytes, st, resident);
 }

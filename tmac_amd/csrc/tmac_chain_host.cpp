@@ -15,7 +15,8 @@ using namespace tmac_host;
 // ---------------------------------------------------------------------------------------------
 static thread_local std::vector<ChainRecOp>* g_chain_rec = nullptr;
 static thread_local std::vector<ChainRecGather>* g_chain_gat = nullptr;
-static thread_local tmac_hip_xform g_chain_xf = {};                  // applies to the next recorded call
+static thread_local tmac_hip_xform g_chain_xf = {};                  // applies to the next recorded call (kind: the low byte alone)
+static thread_local int g_chain_gate = 0;                            // ... and its gate (xf_kind_check), meaningful with a GLU / GLU_NORM
 static bool has_glu(const tmac_hip_xform& xf) { return xf.kind == TMAC_XF_GLU || xf.kind == TMAC_XF_GLU_NORM; }   // reads a second vector
 bool tmac_host::chain_recording() { return g_chain_rec != nullptr; }
 void tmac_host::chain_clear_xform() { memset(&g_chain_xf, 0, sizeof(g_chain_xf)); }
@@ -31,7 +32,7 @@ int32_t tmac_host::chain_record(const tmac_hip_weights* const* wl, int nmat, con
         op.C.push_back(C_list[i]);
     }
     op.B = B_dev; op.act = act_dtype; op.out = out_dtype;
-    op.xf = g_chain_xf;
+    op.xf = g_chain_xf; op.gate = has_glu(g_chain_xf) ? g_chain_gate : 0;
     memset(&g_chain_xf, 0, sizeof(g_chain_xf));
     g_chain_rec->push_back(op);
     return TMAC_HIP_OK;
@@ -41,18 +42,20 @@ int32_t tmac_host::chain_record(const tmac_hip_weights* const* wl, int nmat, con
 extern "C" int32_t tmac_hip_chain_xform(const tmac_hip_xform* xf) {
     if (!g_chain_rec) return fail(TMAC_HIP_E_ARG, "no chain is being recorded on this thread");
     if (!xf) return fail(TMAC_HIP_E_ARG, "null transform");
-    if ((xf->kind < 0 || xf->kind > 2) && xf->kind != TMAC_XF_GLU_NORM) return fail(TMAC_HIP_E_ARG, "unknown transform kind %d", xf->kind);
-    if (xf->kind == TMAC_XF_GLU_NORM) {
+    int kind = 0, gate = 0;
+    const int32_t krc = xf_kind_check(xf->kind, &kind, &gate);
+    if (krc) return krc;
+    if (kind == TMAC_XF_GLU_NORM) {
         const int32_t grc = glu_norm_check(xf);
         if (grc) return grc;
     }
-    if (xf->kind == TMAC_XF_GLU && !xf->in2) return fail(TMAC_HIP_E_ARG, "GLU needs a second vector");
+    if (kind == TMAC_XF_GLU && !xf->in2) return fail(TMAC_HIP_E_ARG, "GLU needs a second vector");
     // (residual == (void*)1 is the CARRY tag, not an address)
     const struct { const void* p; const char* name; } vec[] = {{xf->in2, "in2"}, {xf->residual == (const void*)1 ? nullptr : xf->residual, "residual"},
                                                               {xf->gamma, "gamma"}, {xf->residual_out, "residual_out"}};
     for (const auto& v : vec)
         if (misaligned(v.p, XFORM_ALIGN)) return fail(TMAC_HIP_E_ARG, "transform vector %s must be %zu-byte aligned (read or written 16 bytes at a time)", v.name, XFORM_ALIGN);
-    g_chain_xf = *xf;
+    g_chain_xf = *xf; g_chain_xf.kind = kind; g_chain_gate = gate;
     return TMAC_HIP_OK;
 }
 
@@ -250,7 +253,7 @@ struct ChainFlow {
     std::vector<Src> src, src2;                               // [op] where the activations / the second vector of a GLU come from
     std::vector<std::vector<char>> consumed, gathered;        // [op][matrix] the output is handed over inside the launch / through an exchange step
     std::vector<std::vector<char>> dep;                       // dep[k][i]: op k runs after op i has published everything
-    std::vector<char> epi_of, glu_in_producer;                // [op] plan_glu_epilogue: the call publishes silu(gate) * up itself / reads that product
+    std::vector<char> epi_of, glu_in_producer;                // [op] plan_glu_epilogue: the call publishes gate(gate) * up itself (1 + the gate: ChainOp::epi) / reads that product
 };
 // The most recent output before call i that overlaps r: the source of the vector call i reads at p, provided it IS that output.  Partial
 // overlap with an earlier output cannot be handed over (the reader would see a mixture of launches): *partial is set, the caller refuses.
@@ -332,7 +335,7 @@ static int32_t analyse_flow(const std::vector<ChainRecOp>& rec, const std::vecto
 }
 
 // GLU in the producer: when the two vectors of a GLU are outputs 0 and 1 of ONE earlier two-matrix call (gate and up) and nothing else
-// in the chain reads the gate's hand-off image, the gate/up call publishes silu(gate) * up itself -- once per row, by the wave that
+// in the chain reads the gate's hand-off image, the gate/up call publishes gate(gate) * up itself (the GLU's gate travels in epi_of) -- once per row, by the wave that
 // publishes the rows anyway -- instead of all 256 workgroups of the reader evaluating K x (exp + rcp) each and polling two images
 // (A/B: TMAC_CHAIN_GLU_EPILOGUE=0 keeps the reader's form).  Needs both quads of a row pair in one workgroup iteration: pairs are dealt.
 // Fills f.epi_of / f.glu_in_producer; an up projection nobody else reads is no longer handed over (f.consumed).
@@ -354,7 +357,7 @@ static void plan_glu_epilogue(const std::vector<ChainRecOp>& rec, ChainFlow& f, 
         const int nqj = 2 * sj.nquads(), nstj = (sj.K / 32 + 63) / 64;
         const int wq = kn.wpq ? kn.wpq : chain_pick_wpq(nqj, nstj, grid);
         if (CHAIN_NWV % wq || ((CHAIN_NWV / wq) & 1)) continue;          // pairs need an even number of quads per workgroup iteration
-        f.epi_of[j] = 1; f.glu_in_producer[i] = 1;
+        f.epi_of[j] = (char)(1 + rec[i].gate); f.glu_in_producer[i] = 1;        // ChainOp::epi: 1 / 2 / 3 = silu / relu^2 / tanh-GELU
         if (readers[j][1] == 1) f.consumed[j][1] = 0;                    // nobody else reads the up projection through a hand-off
     }
 }
@@ -434,7 +437,7 @@ static int32_t describe_ops(const std::vector<ChainRecOp>& rec, const ChainFlow&
         set_wpq(o, wpq, CHAIN_NWV);
         if (nq / c.grid + 1 + o.ipi >= 4096) return fail(TMAC_HIP_E_NOMATCH, "op %zu: too many rows per workgroup for the decode chain", i);
         o.q_per = nq / c.grid; o.q_extra = nq % c.grid;
-        if (f.epi_of[i]) { o.epi = 1; c.xforms = 1; o.q_per = (nq / 2) / c.grid; o.q_extra = (nq / 2) % c.grid; }
+        if (f.epi_of[i]) { o.epi = f.epi_of[i]; c.xforms = 1; if (o.epi > 1) c.gates = 1; o.q_per = (nq / 2) / c.grid; o.q_extra = (nq / 2) % c.grid; }
         if (src.op >= 0) {
             const ChainMat& pm = c.ops[src.op].m[src.mat];
             const bool via_gather = f.gathered[src.op][src.mat] != 0;
@@ -467,7 +470,7 @@ static int32_t describe_ops(const std::vector<ChainRecOp>& rec, const ChainFlow&
                 o.gamma = xf.gamma; o.res_out = xf.residual_out;
                 memcpy(&o.eps_bits, &xf.eps, 4);
             } else if (xf.kind == TMAC_XF_GLU_NORM) {
-                // Served in the producer form only: the gate/up call publishes g = silu(gate) * up (fp16, like every handed-over vector)
+                // Served in the producer form only: the gate/up call publishes g = gate(gate) * up (fp16, like every handed-over vector)
                 // and this call is a NORM of its handed-over `in` -- no residual, no carry -- which the kernel already runs.
                 if (!f.glu_in_producer[i])
                     return fail(TMAC_HIP_E_NOMATCH, "op %zu: a GLU_NORM transform is recorded only where the call in front publishes silu(in) * in2 itself (in and in2 "
@@ -482,9 +485,11 @@ static int32_t describe_ops(const std::vector<ChainRecOp>& rec, const ChainFlow&
                 o.gamma = xf.gamma;
                 memcpy(&o.eps_bits, &xf.eps, 4);
             } else if (xf.kind == TMAC_XF_GLU && f.glu_in_producer[i]) {
-                o.xf_kind = TMAC_XF_NONE;                  // `in` already holds silu(gate) * up (the producer's epilogue)
+                o.xf_kind = TMAC_XF_NONE;                  // `in` already holds gate(gate) * up (the producer's epilogue)
             } else if (xf.kind == TMAC_XF_GLU) {
                 c.xforms = 1;
+                o.xf_flags |= r.gate << 8;                 // the reader evaluates gate(in) * in2 itself
+                if (r.gate) c.gates = 1;
                 if (o.K > 2 * 8 * CHAIN_FT) return fail(TMAC_HIP_E_NOMATCH, "op %zu: a GLU transform is covered up to K = %d", i, 2 * 8 * CHAIN_FT);
                 if (chain_xf_region_floats(o.K) > c.tmp_floats) c.tmp_floats = chain_xf_region_floats(o.K);
                 if (src2.op >= 0) {

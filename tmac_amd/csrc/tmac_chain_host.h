@@ -24,6 +24,7 @@ struct tmac_hip_chain {
     unsigned long long* d_tap_off = nullptr;
     size_t bytes = 0;                 // algorithmic weight + scale bytes of one launch
     int xforms = 0, carry_floats = 0;    // some op carries a vector transform; LDS floats of the kept vector
+    int gates = 0;                       // some GLU of the chain has a gate other than silu (ChainArgs::gates)
     int tmp_floats = 0, gam_floats = 0, ext_floats = 0, carry_K = 0;   // LDS floats of an op's own transform vector / norm weights; K of the latest kept vector
     int poll_sleep = 8, poll_delay = 4, issue_first = -1, poll_mode = 0, poll_grid = 0;   // read from the environment once, when the chain is built
     hipStream_t last_stream = nullptr;   // stream of the most recent launch (in-flight guard)
@@ -50,7 +51,8 @@ struct ChainRecOp {
     const void* B;
     std::vector<void*> C;
     tmac_dtype_t act, out;
-    tmac_hip_xform xf;               // vector transform of the activations (kind 0: none)
+    tmac_hip_xform xf;               // vector transform of the activations (kind 0: none); kind holds the low byte alone ...
+    int gate = 0;                    // ... and this the gate of a GLU / GLU_NORM: 0 silu, 1 relu^2, 2 tanh-GELU
 };
 // an exchange step noted while recording: recv = all-gather over the ranks of send (rank r's bytes at r * bytes)
 struct ChainRecGather {

@@ -504,7 +504,7 @@ static Plan xf_rows_plan(Plan p) {
 }
 // xf: the call carries a vector transform (N >= 2, plan from xf_rows_plan): the row pass, then the planned LUT build's XF instantiation
 static int32_t fused_prefill(Plan p, const tmac_hip_weights* const* wl, int nmat, const void* B_dev, tmac_dtype_t act_dtype,
-                             void* const* C_list, tmac_dtype_t out_dtype, int N, hipStream_t st, XfRowsArgs* xf = nullptr) {
+                             void* const* C_list, tmac_dtype_t out_dtype, int N, hipStream_t st, XfRowsGateArgs* xf = nullptr) {
     const Shape& s0 = wl[0]->s;
     tmac_hip_workspace* ws = nullptr;
     {
@@ -616,8 +616,17 @@ extern "C" int32_t tmac_hip_qgemm_fused_dev(const tmac_hip_weights* const* weigh
 // ---- fused entry point with a vector transform (N = 1) -----------------------------------------------------------------------
 // Outside a recording: k_gemv_quad's XF instantiations.  Everything is checked before anything is launched; a transformed call is never
 // queued (it goes behind the deferred queue like every non-hot entry point).
-// kind known to the transformed calls: NONE, NORM, GLU, GLU_NORM (3 is not a kind)
-static bool xf_kind_known(int kind) { return (kind >= TMAC_XF_NONE && kind <= TMAC_XF_GLU) || kind == TMAC_XF_GLU_NORM; }
+// kind known to the transformed calls: NONE, NORM, GLU, GLU_NORM (3 is not a kind), the last two with a gate in bits 8..15
+int32_t tmac_host::xf_kind_check(int32_t kind, int* base, int* gate) {
+    const int k = kind & 0xff, g = kind & ~0xff;
+    if (k != TMAC_XF_NONE && k != TMAC_XF_NORM && k != TMAC_XF_GLU && k != TMAC_XF_GLU_NORM) return fail(TMAC_HIP_E_ARG, "unknown transform kind %d", kind);
+    if (g != 0 && (k == TMAC_XF_NONE || k == TMAC_XF_NORM))
+        return fail(TMAC_HIP_E_ARG, "transform kind %d takes no gate: bits 8..15 of kind (0x%x here) select the gate of a GLU or GLU_NORM", k, (unsigned)g);
+    if (g != TMAC_XF_GATE_SILU && g != TMAC_XF_GATE_RELU2 && g != TMAC_XF_GATE_GELU)
+        return fail(TMAC_HIP_E_ARG, "unknown gate 0x%x in transform kind 0x%x (TMAC_XF_GATE_SILU, _RELU2 or _GELU in bits 8..15, nothing above)", (unsigned)g, (unsigned)kind);
+    *base = k; *gate = g >> 8;
+    return TMAC_HIP_OK;
+}
 int32_t tmac_host::glu_norm_check(const tmac_hip_xform* xf) {
     if (!xf->in2) return fail(TMAC_HIP_E_ARG, "GLU_NORM needs a second vector (in2)");
     if (!xf->gamma) return fail(TMAC_HIP_E_ARG, "GLU_NORM needs the norm weights (gamma)");
@@ -642,9 +651,11 @@ extern "C" int32_t tmac_hip_qgemm_fused_xf_dev(const tmac_hip_weights* const* wl
         if (rc != TMAC_HIP_OK && chain_recording()) chain_clear_xform();      // a rejected call leaves no pending transform
         return rc;
     }
-    if (!xf_kind_known(xf->kind)) return fail(TMAC_HIP_E_ARG, "unknown transform kind %d", xf->kind);
+    int kind = 0, gate = 0;
+    const int32_t krc = xf_kind_check(xf->kind, &kind, &gate);
+    if (krc) return krc;
     if (!wl || !C_list || !B_dev || nmat < 1 || nmat > 4) return fail(TMAC_HIP_E_ARG, "bad fused arguments (1..4 matrices)");
-    const bool norm = xf->kind == TMAC_XF_NORM, glu_norm = xf->kind == TMAC_XF_GLU_NORM;
+    const bool norm = kind == TMAC_XF_NORM, glu_norm = kind == TMAC_XF_GLU_NORM;
     if (glu_norm) {
         const int32_t grc = glu_norm_check(xf);
         if (grc) return grc;
@@ -686,7 +697,7 @@ extern "C" int32_t tmac_hip_qgemm_fused_xf_dev(const tmac_hip_weights* const* wl
     FusedXfArgs fa;
     const int nb = fill_fused_args(fa, wl, C_list, nmat, out_dtype, nullptr);
     fa.B = B_dev; fa.act_f16 = act_dtype == TMAC_F16;
-    fa.xf_kind = xf->kind; fa.in2 = in2; fa.residual = residual; fa.gamma = gamma; fa.residual_out = rout; fa.eps = xf->eps;
+    fa.xf_kind = kind | (gate << 8); fa.in2 = in2; fa.residual = residual; fa.gamma = gamma; fa.residual_out = rout; fa.eps = xf->eps;
     // the launch configuration: forced (tmac_hip_debug_quad_config) -- it must have an XF instantiation -- else tuned, else the heuristic
     int ft = g_knobs.force_ft, wpq = g_knobs.force_wpq;
     const bool strict = ft || wpq;
@@ -701,9 +712,11 @@ extern "C" int32_t tmac_hip_qgemm_fused_xf_dev(const tmac_hip_weights* const* wl
 // N = 1 and "no transform" are the existing calls themselves.  N >= 2: every refusal comes before the first launch; then the row pass
 // (k_xf_rows), the planned LUT build with the transform in its activation load, the planned kernel (fused_prefill).  Never recorded, never
 // queued.
-static int32_t xf_rows_check(const void* B_dev, tmac_dtype_t act_dtype, const tmac_hip_xform* xf, int K, int N, XfRowsArgs& xa) {
-    if (!xf_kind_known(xf->kind)) return fail(TMAC_HIP_E_ARG, "unknown transform kind %d", xf->kind);
-    const bool norm = xf->kind == TMAC_XF_NORM, glu_norm = xf->kind == TMAC_XF_GLU_NORM;
+static int32_t xf_rows_check(const void* B_dev, tmac_dtype_t act_dtype, const tmac_hip_xform* xf, int K, int N, XfRowsGateArgs& xa) {
+    int kind = 0, gate = 0;
+    const int32_t krc = xf_kind_check(xf->kind, &kind, &gate);
+    if (krc) return krc;
+    const bool norm = kind == TMAC_XF_NORM, glu_norm = kind == TMAC_XF_GLU_NORM;
     if (glu_norm) {
         const int32_t grc = glu_norm_check(xf);
         if (grc) return grc;
@@ -712,7 +725,7 @@ static int32_t xf_rows_check(const void* B_dev, tmac_dtype_t act_dtype, const tm
     if (norm && xf->residual == TMAC_XF_CARRY)
         return fail(TMAC_HIP_E_ARG, "TMAC_XF_CARRY names a vector kept inside a chain launch: outside a recording the residual is a vector in memory");
     memset(&xa, 0, sizeof(xa));
-    xa.kind = xf->kind; xa.eps = xf->eps;
+    xa.kind = kind; xa.gate = gate; xa.eps = xf->eps;
     xa.in2 = norm ? nullptr : xf->in2;
     xa.residual = norm ? xf->residual : nullptr;
     xa.gamma = norm || glu_norm ? xf->gamma : nullptr;
@@ -751,7 +764,7 @@ extern "C" int32_t tmac_hip_qgemm_fused_xf_rows_dev(const tmac_hip_weights* cons
             return fail(TMAC_HIP_E_ARG, "C_dev[%d] must be %zu-byte aligned (four outputs are stored at a time)", i, out_align(out_dtype));
     }
     const Shape& s0 = wl[0]->s;
-    XfRowsArgs xa;
+    XfRowsGateArgs xa;
     int32_t rc = xf_rows_check(B_dev, act_dtype, xf, s0.K, N, xa);
     if (rc) return rc;
     for (int i = 0; i < nmat; ++i) {
@@ -801,7 +814,7 @@ extern "C" int32_t tmac_hip_debug_xf_rows(const void* B_dev, tmac_dtype_t act_dt
     if (brc) return brc;
     if (!B_dev || !xf || !x_out_dev || K <= 0 || K % 64 || N < 1) return fail(TMAC_HIP_E_ARG, "bad tap arguments (K a multiple of 64, N >= 1)");
     if (xf->kind == TMAC_XF_NONE) return fail(TMAC_HIP_E_ARG, "the tap shows a transform: kind NORM, GLU or GLU_NORM");
-    XfRowsArgs xa;
+    XfRowsGateArgs xa;
     const int32_t rc = xf_rows_check(B_dev, act_dtype, xf, K, N, xa);
     if (rc) return rc;
     if (misaligned(x_out_dev, XFORM_ALIGN)) return fail(TMAC_HIP_E_ARG, "x_out_dev must be %zu-byte aligned", XFORM_ALIGN);

@@ -120,12 +120,15 @@ __global__ __launch_bounds__(256) void k_lut_image(const void* __restrict__ B, u
     }
 }
 
-hipError_t launch_lut_image(const void* B, int act_f16, void* bimg, float* colv, int K, int N, int Npad, hipStream_t st, const XfRowsArgs* xf) {
+hipError_t launch_lut_image(const void* B, int act_f16, void* bimg, float* colv, int K, int N, int Npad, hipStream_t st, const XfRowsGateArgs* xf) {
     if (K % 64 != 0 || N < 1 || Npad < N || Npad % 64 != 0) return hipErrorInvalidValue;
     dim3 g(Npad / 32, K / 64), b(256);
     if (xf) {
-        if (act_f16) hipLaunchKernelGGL((k_lut_image<true, true, XfRowsArgs>), g, b, 0, st, B, (uint4*)bimg, colv, K, N, Npad, *xf);
-        else hipLaunchKernelGGL((k_lut_image<false, true, XfRowsArgs>), g, b, 0, st, B, (uint4*)bimg, colv, K, N, Npad, *xf);
+        // silu: the instantiations on the plain block; another gate: those on the block that carries it
+#define LIX(F, T) hipLaunchKernelGGL((k_lut_image<F, true, T>), g, b, 0, st, B, (uint4*)bimg, colv, K, N, Npad, static_cast<const T&>(*xf))
+        if (xf->gate == XF_GATE_SILU) { if (act_f16) LIX(true, XfRowsArgs); else LIX(false, XfRowsArgs); }
+        else { if (act_f16) LIX(true, XfRowsGateArgs); else LIX(false, XfRowsGateArgs); }
+#undef LIX
         return hipGetLastError();
     }
     if (act_f16) hipLaunchKernelGGL((k_lut_image<true>), g, b, 0, st, B, (uint4*)bimg, colv, K, N, Npad);

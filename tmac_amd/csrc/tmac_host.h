@@ -176,6 +176,11 @@ void chain_clear_xform();          // drops a transform declared for the next re
 // TMAC_XF_GLU_NORM's own argument rules, the same on every path: in2 and gamma required, no residual operand.  TMAC_HIP_OK, or fail(E_ARG, ...)
 // naming the field.
 int32_t glu_norm_check(const tmac_hip_xform* xf);
+// tmac_hip_xform::kind split into the kind (low byte) and the gate of a GLU / GLU_NORM (bits 8..15: TMAC_XF_GATE_*), the same on every path.
+// *base: TMAC_XF_NONE / NORM / GLU / GLU_NORM; *gate: 0 silu, 1 relu^2, 2 tanh-GELU (the kernels' XF_GATE_*).  TMAC_HIP_OK, or fail(E_ARG, ...):
+// "unknown transform kind" for a low byte that is no kind (whatever the bits above it), else a message naming the gate -- gate bits on
+// NONE or NORM, a gate other than the three, any bit above 15.
+int32_t xf_kind_check(int32_t kind, int* base, int* gate);
 int32_t chain_record(const tmac_hip_weights* const* wl, int nmat, const void* B_dev, tmac_dtype_t act_dtype, void* const* C_list,
                      tmac_dtype_t out_dtype, int N);
 // deferred launches (tmac_hip_defer): true (and *rc set) when the call was queued instead of launched

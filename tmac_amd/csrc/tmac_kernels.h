@@ -49,7 +49,9 @@ struct FusedArgs {
 // k_gemv_quad's XF instantiations (tmac_hip_qgemm_fused_xf_dev): the N = 1 call plus a vector transform of its activations, applied
 // between the activation loads and the table build.  An argument block of its own: the plain instantiations keep theirs.
 struct FusedXfArgs : FusedArgs {
-    int xf_kind;             // TMAC_XF_NORM (1) | TMAC_XF_GLU (2) | TMAC_XF_GLU_NORM (4)
+    int xf_kind;             // TMAC_XF_NORM (1) | TMAC_XF_GLU (2) | TMAC_XF_GLU_NORM (4); GLU, GLU_NORM: | the gate << 8 (0 silu, 1 relu^2, 2 tanh-GELU:
+                             // tmac_quad_core.h XF_GATE_*) -- tmac_hip_xform::kind as it comes.  (No field of its own: the block keeps its size,
+                             // and the instantiations that never look at the gate their code)
     const void* in2;         // GLU, GLU_NORM: second vector [K], dtype of B
     const float* residual;   // NORM: fp32 [K] or null
     const float* gamma;      // NORM: fp32 [K] or null (add only); GLU_NORM: fp32 [K], required
@@ -68,6 +70,12 @@ struct XfRowsArgs {
     const float* r;          // NORM with gamma, GLU_NORM: fp32 [N], 1 / rms of row n, written by k_xf_rows
     float* residual_out;     // NORM: fp32 [N][K] or null; written by k_xf_rows alone
     float eps;
+};
+// ... with the gate of a GLU / GLU_NORM as a run-time choice: what the host passes down, and the argument block of the kernels' instantiations
+// for relu^2 and GELU (xf_rows_g8 reads `gate` where the block has one).  A call with silu runs the instantiations on the plain block above:
+// the code and the registers they had before the selector existed (profiles/r14_gate_resources.txt).
+struct XfRowsGateArgs : XfRowsArgs {
+    int gate;                // 0 silu | 1 relu^2 | 2 tanh-GELU (tmac_quad_core.h XF_GATE_*)
 };
 
 // one-hot MFMA GEMM for N > 1 activation rows (tmac_gemm.hip); weights in the QUAD layout; up to 4 matrices that share
@@ -150,17 +158,17 @@ hipError_t launch_qlut_ref_to_dev(const int8_t* qlut_ref, void* qlut_dev, void* 
 // pair-wise LUT build (tmac_quad.hip; ags = 64): the half-table image + LUT scales/biases, and -- when qlut_ref / qlut_dev are
 // given (both or neither) -- the other two layouts of the workspace as well
 hipError_t launch_preprocess_pairs(const void* B, int act_f16, void* qlut_lds, float* lut_scales, float* lut_biases, int K, int N,
-                                   int8_t* qlut_ref, void* qlut_dev, size_t qdev_u4_per_row, hipStream_t st, const XfRowsArgs* xf = nullptr);
+                                   int8_t* qlut_ref, void* qlut_dev, size_t qdev_u4_per_row, hipStream_t st, const XfRowsGateArgs* xf = nullptr);
 // the same for act_group_size = K (one act group per activation row; K <= 12288)
 // bimg / colv (both or neither; Npad = row stride of the image): also the LUT image k_gemm_planes_us streams (tmac_gemm2.hip)
 hipError_t launch_preprocess_pairs_row(const void* B, int act_f16, void* qlut_lds, float* lut_scales, float* lut_biases, int K, int N,
                                        int8_t* qlut_ref, void* qlut_dev, size_t qdev_u4_per_row, void* bimg, float* colv, int Npad, hipStream_t st,
-                                       const XfRowsArgs* xf = nullptr);
+                                       const XfRowsGateArgs* xf = nullptr);
 // xf (all three builders, and launch_lut_image below): the XF instantiation -- x = the transform of row n instead of the row itself; the
 // half-table image / LUT image alone (qlut_ref and qlut_dev must be null).  launch_xf_rows: the row pass in front of it (NORM with gamma or
 // residual_out; r_out: fp32 [N] or null); launch_xf_rows_tap: the fp32 x [N][K] the builders consume (tmac_hip_debug_xf_rows).
-hipError_t launch_xf_rows(const XfRowsArgs& xf, const void* B, int act_f16, float* r_out, int K, int N, hipStream_t st);
-hipError_t launch_xf_rows_tap(const XfRowsArgs& xf, const void* B, int act_f16, float* x_out, int K, int N, hipStream_t st);
+hipError_t launch_xf_rows(const XfRowsGateArgs& xf, const void* B, int act_f16, float* r_out, int K, int N, hipStream_t st);
+hipError_t launch_xf_rows_tap(const XfRowsGateArgs& xf, const void* B, int act_f16, float* x_out, int K, int N, hipStream_t st);
 hipError_t launch_stream_read(const void* src, size_t bytes, void* sink, hipStream_t st);
 // host-pointer route (tmac_kernels.hip): results into pinned host memory by the GPU's own stores, then a flag the host spins on
 hipError_t launch_host_copy3_flag(const void* q, size_t nq, const void* ls, const void* lb, size_t ns, void* dst_pinned, uint32_t* flag,
@@ -169,7 +177,7 @@ hipError_t launch_host_flag(uint32_t* flag, uint32_t val, hipStream_t st);   // 
 bool gemm_onehot_supported(const Shape& s);
 hipError_t launch_gemm_onehot(const GemmArgs& a, hipStream_t st);
 bool gemm_planes_supported(const Shape& s);
-hipError_t launch_lut_image(const void* B, int act_f16, void* bimg, float* colv, int K, int N, int Npad, hipStream_t st, const XfRowsArgs* xf = nullptr);
+hipError_t launch_lut_image(const void* B, int act_f16, void* bimg, float* colv, int K, int N, int Npad, hipStream_t st, const XfRowsGateArgs* xf = nullptr);
 hipError_t launch_gemm_planes(const Gemm2Args& a, hipStream_t st);
 // fused kernel (tmac_fused.hip)
 bool gemv_fused_supported(const Shape& s);

@@ -12,7 +12,7 @@
 // 2 unified scale applied last (BitNet); LUTSRC 1 build the LUT in-kernel / 0 copy the image k_preprocess wrote;
 // NR tables built per thread; FT threads; WPQ waves per quad; DUMP integer tap; ACC 1 v_mfma_i32_16x16x64_i8
 // accumulate / 0 v_mqsad_pk_u16_u8 (A/B variant); XF a vector transform of the activations (residual add + RMSNorm,
-// silu(in) * in2: tmac_hip_qgemm_fused_xf_dev) between the activation loads and the table build, where every workgroup
+// gate(in) * in2, the gate silu, relu^2 or tanh-GELU: tmac_hip_qgemm_fused_xf_dev) between the activation loads and the table build, where every workgroup
 // holds the whole vector.  DESIGN.md 4.1, 4.2, 4.6.
 #include <hip/hip_runtime.h>
 #include <hip/hip_fp16.h>
@@ -101,10 +101,15 @@ __device__ __forceinline__ void load_q(QFrag<BITS>& f, const FusedArgs& a, const
 // XF (LUTSRC 1, ACC 1, no tap, one activation row): the argument block carries the transform's operands (FusedXfArgs); every line of it
 // sits under if constexpr (XF).  GN (with XF): the instantiation serves TMAC_XF_GLU_NORM (xf_kind 4) and nothing else -- kinds 1 and 2 keep
 // the code they had (measured: sharing one instantiation moved the GLU by 1 %, profiles/r13_glunorm_bench.txt).
-template <int BITS, bool ZP, int SM, int LUTSRC, int NR, int FT, int WPQ, bool DUMP, int ACC, bool SCF16, bool EARLY, bool XF = false, bool GN = false>
+// GT (with XF): the gate of the GLU / GLU_NORM is a run-time choice (a.xf_kind >> 8) -- instantiations of their own for relu^2 and GELU.  Inside
+// the GN ones the selector cost the six-tables-per-thread forms (K > 4096 at 512 threads) up to 4 VGPRs; inside the shared NORM / GLU ones it
+// cost no register, but the silu GLU of llama-2-7B's down 0.14 us in 8.2, outside the spread of the parent's runs
+// (profiles/r14_gate_resources.txt, profiles/r14_gate_bench.txt).  Without GT the gate is silu, spelled out: the code of before.
+template <int BITS, bool ZP, int SM, int LUTSRC, int NR, int FT, int WPQ, bool DUMP, int ACC, bool SCF16, bool EARLY, bool XF = false, bool GN = false, bool GT = false>
 __global__ __launch_bounds__(FT) void k_gemv_quad(std::conditional_t<XF, FusedXfArgs, FusedArgs> a) {
     static_assert(!XF || (LUTSRC == 1 && ACC == 1 && !DUMP), "the transform lives in the in-kernel LUT build of the MFMA form");
     static_assert(!GN || XF, "GLU_NORM is a transform");
+    static_assert(!GT || XF, "the gate belongs to a transform");
     extern __shared__ uint4 lds[];
     const unsigned long long t_entry = DUMP ? __builtin_amdgcn_s_memtime() : 0ull;   // before the first kernel-argument load
     constexpr int NWV = FT / 64, IPI = NWV / WPQ;
@@ -174,7 +179,7 @@ __global__ __launch_bounds__(FT) void k_gemv_quad(std::conditional_t<XF, FusedXf
             for (int i = 0; i < 8; ++i) { xa[r][i] = 0u; xg[r][i] = 0u; }
             const void* src_a = (!GN && a.xf_kind == 1) ? (const void*)a.residual : a.in2;
             if (src_a != nullptr) {
-                if ((GN || a.xf_kind == 2) && a.act_f16) {
+                if ((GN || (GT ? a.xf_kind != 1 : a.xf_kind == 2)) && a.act_f16) {      // (GT: a GLU's xf_kind carries its gate)
                     const uint4 v = reinterpret_cast<const uint4*>(src_a)[p];
                     xa[r][0] = v.x; xa[r][1] = v.y; xa[r][2] = v.z; xa[r][3] = v.w;
                 } else {
@@ -216,7 +221,7 @@ __global__ __launch_bounds__(FT) void k_gemv_quad(std::conditional_t<XF, FusedXf
     // Before the weight fragments are issued: it waits for the operand loads, and nothing else is in flight yet.  NORM: t = in +
     // residual (fp32 rn), t to residual_out by the ONE workgroup that owns the pair (p mod gridDim.x: a grid of one owns them all),
     // the lane's part of sum t^2, and t * gamma; 1 / rms multiplies in unpack, once the sum is known.  Without gamma x = t, untouched:
-    // the table build then sees the bits a plain call on t would.  GLU: x = silu(in) * in2 with the hardware exp and reciprocal
+    // the table build then sees the bits a plain call on t would.  GLU: x = gate(in) * in2 (silu, GELU: the hardware exp and reciprocal)
     // (tmac_chain.hip's formula).  The transformed vector stays in the registers the raw one arrived in (xr is [NP][8] for fp32
     // activations anyway); the operands are dead behind this block.  GLU_NORM: g = the GLU's x, then the NORM's tail on g -- the lane's
     // part of sum g^2 (own pairs only: a clamped lane holds a copy of the last pair), g * gamma, 1 / rms in unpack.
@@ -267,10 +272,14 @@ __global__ __launch_bounds__(FT) void k_gemv_quad(std::conditional_t<XF, FusedXf
 #pragma unroll
                     for (int i = 0; i < 8; ++i) u[i] = __uint_as_float(xa[r][i]);
                 }
-                // silu(v) = v / (1 + exp(-v)): hardware exp2 and reciprocal (1 ulp each; the transform is specified to a tolerance)
+                // x = gate(x) * u, the gate by a.xf_kind >> 8 (uniform): silu, relu^2 or tanh-GELU (tmac_quad_core.h)
+                if constexpr (!GT) {      // silu, spelled out: the loop these instantiations had before the selector existed
 #pragma unroll
-                for (int i = 0; i < 8; ++i)
-                    x[i] = __fmul_rn(__fmul_rn(x[i], __builtin_amdgcn_rcpf(__fadd_rn(1.0f, __expf(-x[i])))), u[i]);
+                    for (int i = 0; i < 8; ++i)
+                        x[i] = __fmul_rn(__fmul_rn(x[i], __builtin_amdgcn_rcpf(__fadd_rn(1.0f, __expf(-x[i])))), u[i]);
+                } else {
+                    xf_gate_mul(a.xf_kind >> 8, x, u);
+                }
                 if constexpr (GN) {
                     if (p < P) {
 #pragma unroll
@@ -936,11 +945,11 @@ __global__ __launch_bounds__(PT) void k_preprocess_pairs_row(const void* __restr
 // workgroup n -- and, with gamma, r[n] = rsq(fma(sum t^2, rcp(K), eps)), k_gemv_quad's expression.  The order of the sum is a function of K
 // alone: thread j adds its pairs j, j + 256, ... element by element (fma), the wave's 64 sums fold by xor 32, 16, ... 1, the four wave
 // sums are added in wave order.  Neither N, the row's index nor any launch knob enters: a row's r is the same in every call.
-// GLU_NORM (kind 4): t = g = silu(in) * in2 (xf_rows_g8: the product the builders repeat), summed in the same order; r[n] is all it writes.
+// GLU_NORM (kind 4): t = g = gate(in) * in2 (xf_rows_g8: the product the builders repeat), summed in the same order; r[n] is all it writes.
 // ---------------------------------------------------------------------------------------------
 constexpr int XF_ROWS_PT = 256;
-template <bool F16>
-__global__ __launch_bounds__(XF_ROWS_PT) void k_xf_rows(XfRowsArgs a, const void* __restrict__ B, float* __restrict__ r_out, int K) {
+template <bool F16, class XA = XfRowsArgs>
+__global__ __launch_bounds__(XF_ROWS_PT) void k_xf_rows(XA a, const void* __restrict__ B, float* __restrict__ r_out, int K) {
     __shared__ float l_ss[XF_ROWS_PT / 64];
     const int P = K / 8, n = blockIdx.x, tid = threadIdx.x;
     float ss = 0.f;
@@ -969,8 +978,8 @@ __global__ __launch_bounds__(XF_ROWS_PT) void k_xf_rows(XfRowsArgs a, const void
     }
 }
 // the fp32 x [N][K] the XF builders consume (tmac_hip_debug_xf_rows): a store around xf_rows_x8
-template <bool F16>
-__global__ __launch_bounds__(256) void k_xf_rows_tap(XfRowsArgs a, const void* __restrict__ B, float* __restrict__ x_out, int K) {
+template <bool F16, class XA = XfRowsArgs>
+__global__ __launch_bounds__(256) void k_xf_rows_tap(XA a, const void* __restrict__ B, float* __restrict__ x_out, int K) {
     const int P = K / 8, n = blockIdx.y;
     const int p = blockIdx.x * 256 + threadIdx.x;
     if (p >= P) return;
@@ -981,25 +990,32 @@ __global__ __launch_bounds__(256) void k_xf_rows_tap(XfRowsArgs a, const void* _
     xo[1] = make_float4(x[4], x[5], x[6], x[7]);
 }
 
-hipError_t launch_xf_rows(const XfRowsArgs& xf, const void* B, int act_f16, float* r_out, int K, int N, hipStream_t st) {
+hipError_t launch_xf_rows(const XfRowsGateArgs& xf, const void* B, int act_f16, float* r_out, int K, int N, hipStream_t st) {
     if (K % 64 != 0 || N < 1 || (xf.kind != 1 && xf.kind != 4) || (r_out == nullptr && xf.residual_out == nullptr)) return hipErrorInvalidValue;
     if (xf.kind == 4 && (!xf.in2 || !xf.gamma || !r_out || xf.residual || xf.residual_out)) return hipErrorInvalidValue;
+    if (xf.gate < XF_GATE_SILU || xf.gate > XF_GATE_GELU) return hipErrorInvalidValue;
     dim3 g(N), b(XF_ROWS_PT);
-    if (act_f16) hipLaunchKernelGGL((k_xf_rows<true>), g, b, 0, st, xf, B, r_out, K);
-    else hipLaunchKernelGGL((k_xf_rows<false>), g, b, 0, st, xf, B, r_out, K);
+    // silu (and NORM): the instantiations on the plain block; another gate: those on the block that carries it
+#define XR(F, T) hipLaunchKernelGGL((k_xf_rows<F, T>), g, b, 0, st, static_cast<const T&>(xf), B, r_out, K)
+    if (xf.gate == XF_GATE_SILU) { if (act_f16) XR(true, XfRowsArgs); else XR(false, XfRowsArgs); }
+    else { if (act_f16) XR(true, XfRowsGateArgs); else XR(false, XfRowsGateArgs); }
+#undef XR
     return hipGetLastError();
 }
-hipError_t launch_xf_rows_tap(const XfRowsArgs& xf, const void* B, int act_f16, float* x_out, int K, int N, hipStream_t st) {
+hipError_t launch_xf_rows_tap(const XfRowsGateArgs& xf, const void* B, int act_f16, float* x_out, int K, int N, hipStream_t st) {
     if (K % 64 != 0 || N < 1 || N > 65535 || (xf.kind != 1 && xf.kind != 2 && xf.kind != 4) || !x_out) return hipErrorInvalidValue;
+    if (xf.gate < XF_GATE_SILU || xf.gate > XF_GATE_GELU) return hipErrorInvalidValue;
     dim3 g((K / 8 + 255) / 256, N), b(256);
-    if (act_f16) hipLaunchKernelGGL((k_xf_rows_tap<true>), g, b, 0, st, xf, B, x_out, K);
-    else hipLaunchKernelGGL((k_xf_rows_tap<false>), g, b, 0, st, xf, B, x_out, K);
+#define XT(F, T) hipLaunchKernelGGL((k_xf_rows_tap<F, T>), g, b, 0, st, static_cast<const T&>(xf), B, x_out, K)
+    if (xf.gate == XF_GATE_SILU) { if (act_f16) XT(true, XfRowsArgs); else XT(false, XfRowsArgs); }
+    else { if (act_f16) XT(true, XfRowsGateArgs); else XT(false, XfRowsGateArgs); }
+#undef XT
     return hipGetLastError();
 }
 
 hipError_t launch_preprocess_pairs_row(const void* B, int act_f16, void* qlut_lds, float* lut_scales, float* lut_biases, int K, int N,
                                        int8_t* qlut_ref, void* qlut_dev, size_t qdev_u4_per_row, void* bimg, float* colv, int Npad, hipStream_t st,
-                                       const XfRowsArgs* xf) {
+                                       const XfRowsGateArgs* xf) {
     constexpr int PT = 512;
     if (K % 64 != 0 || N < 1 || K > 24 * PT || ((qlut_ref == nullptr) != (qlut_dev == nullptr))) return hipErrorInvalidValue;
     const int tstride = (((K / 32) + 15) & ~15) + 1;
@@ -1007,9 +1023,10 @@ hipError_t launch_preprocess_pairs_row(const void* B, int act_f16, void* qlut_ld
     dim3 g(N), b(PT);
     if (xf) {
         if (qlut_ref) return hipErrorInvalidValue;
-#define PLRX(F) hipLaunchKernelGGL((k_preprocess_pairs_row<F, false, PT, true, XfRowsArgs>), g, b, shmem, st, B, (uint4*)qlut_lds, lut_scales, lut_biases, K, tstride, \
-                                   (uint4*)nullptr, (uint2*)nullptr, (size_t)0, (uint4*)bimg, colv, Npad, *xf)
-        if (act_f16) PLRX(true); else PLRX(false);
+#define PLRX(F, T) hipLaunchKernelGGL((k_preprocess_pairs_row<F, false, PT, true, T>), g, b, shmem, st, B, (uint4*)qlut_lds, lut_scales, lut_biases, K, tstride, \
+                                      (uint4*)nullptr, (uint2*)nullptr, (size_t)0, (uint4*)bimg, colv, Npad, static_cast<const T&>(*xf))
+        if (xf->gate == XF_GATE_SILU) { if (act_f16) PLRX(true, XfRowsArgs); else PLRX(false, XfRowsArgs); }
+        else { if (act_f16) PLRX(true, XfRowsGateArgs); else PLRX(false, XfRowsGateArgs); }
 #undef PLRX
         return hipGetLastError();
     }
@@ -1022,15 +1039,16 @@ hipError_t launch_preprocess_pairs_row(const void* B, int act_f16, void* qlut_ld
 }
 
 hipError_t launch_preprocess_pairs(const void* B, int act_f16, void* qlut_lds, float* lut_scales, float* lut_biases, int K, int N,
-                                   int8_t* qlut_ref, void* qlut_dev, size_t qdev_u4_per_row, hipStream_t st, const XfRowsArgs* xf) {
+                                   int8_t* qlut_ref, void* qlut_dev, size_t qdev_u4_per_row, hipStream_t st, const XfRowsGateArgs* xf) {
     if (K % 64 != 0 || N < 1 || ((qlut_ref == nullptr) != (qlut_dev == nullptr))) return hipErrorInvalidValue;
     const int tstride = (((K / 32) + 15) & ~15) + 1;
     dim3 g((K / 8 + 255) / 256, N), b(256);
     if (xf) {
         if (qlut_ref) return hipErrorInvalidValue;
-#define PLX(F) hipLaunchKernelGGL((k_preprocess_pairs<F, false, true, XfRowsArgs>), g, b, 0, st, B, (uint4*)qlut_lds, lut_scales, lut_biases, K, tstride, \
-                                  (uint4*)nullptr, (uint2*)nullptr, (size_t)0, *xf)
-        if (act_f16) PLX(true); else PLX(false);
+#define PLX(F, T) hipLaunchKernelGGL((k_preprocess_pairs<F, false, true, T>), g, b, 0, st, B, (uint4*)qlut_lds, lut_scales, lut_biases, K, tstride, \
+                                     (uint4*)nullptr, (uint2*)nullptr, (size_t)0, static_cast<const T&>(*xf))
+        if (xf->gate == XF_GATE_SILU) { if (act_f16) PLX(true, XfRowsArgs); else PLX(false, XfRowsArgs); }
+        else { if (act_f16) PLX(true, XfRowsGateArgs); else PLX(false, XfRowsGateArgs); }
 #undef PLX
         return hipGetLastError();
     }
@@ -1163,7 +1181,7 @@ static hipError_t qlaunch_b(const FusedArgs& a, int total_q, int N, int fft, int
 }
 
 // ---- XF instantiations (tmac_hip_qgemm_fused_xf_dev) ----
-// (each once for NORM / GLU and once, GN, for GLU_NORM)
+// (each once for NORM / GLU and once, GN, for GLU_NORM -- the gate silu -- and both once more, GT, with the gate as a run-time choice)
 // They cover FOUR of the eight (threads, waves per quad) configurations -- one per waves-per-quad count, which is what shapes the K walk
 // and the cross-wave reductions: (512,1), (512,2), (768,3), (1024,4) -- so that eight translation units grow by 12 kernels per scale
 // flavour instead of 20.  A configuration the caller forced (tmac_hip_debug_quad_config) outside the set is refused; one the heuristic or
@@ -1171,7 +1189,7 @@ static hipError_t qlaunch_b(const FusedArgs& a, int total_q, int N, int fft, int
 // (768,2), (1024,2) -> (512,2)), or (1024,4) where 512 threads cannot build the tables (K > 12288: more than six per thread).
 static bool quad_xf_covered(int ft, int wpq) { return (ft == 512 && (wpq == 1 || wpq == 2)) || (ft == 768 && wpq == 3) || (ft == 1024 && wpq == 4); }
 
-template <int BITS, bool ZP, int SM, int FT, int WPQ, bool GN>
+template <int BITS, bool ZP, int SM, int FT, int WPQ, bool GN, bool GT = false>
 static hipError_t qlaunch_xf_nr(const FusedXfArgs& a, int total_q, hipStream_t st) {
     constexpr int IPI = FT / 64 / WPQ;
     const size_t shmem = quad_lds_bytes(a.s, FT / 64);
@@ -1182,7 +1200,7 @@ static hipError_t qlaunch_xf_nr(const FusedXfArgs& a, int total_q, hipStream_t s
     const int T = a.s.K / 4;
     const bool two = T <= 2 * FT;
     if (!two && T > 6 * FT) return hipErrorInvalidValue;
-#define QX(NRV, EV) hipLaunchKernelGGL((k_gemv_quad<BITS, ZP, SM, 1, NRV, FT, WPQ, false, 1, QSCF16, EV, true, GN>), g, b, shmem, st, a)
+#define QX(NRV, EV) hipLaunchKernelGGL((k_gemv_quad<BITS, ZP, SM, 1, NRV, FT, WPQ, false, 1, QSCF16, EV, true, GN, GT>), g, b, shmem, st, a)
     if constexpr (FT == 512) {
         if (gx <= 256) { if (two) QX(2, true); else QX(6, true); }
         else { if (two) QX(2, false); else QX(6, false); }
@@ -1191,6 +1209,13 @@ static hipError_t qlaunch_xf_nr(const FusedXfArgs& a, int total_q, hipStream_t s
     }
 #undef QX
     return hipGetLastError();
+}
+
+template <int BITS, bool ZP, int SM, bool GN, bool GT>
+static hipError_t qlaunch_xf_pick(const FusedXfArgs& a, int total_q, int best_ft, int best_wpq, hipStream_t st) {
+    if (best_ft == 512) return best_wpq == 1 ? qlaunch_xf_nr<BITS, ZP, SM, 512, 1, GN, GT>(a, total_q, st) : qlaunch_xf_nr<BITS, ZP, SM, 512, 2, GN, GT>(a, total_q, st);
+    if (best_ft == 768) return qlaunch_xf_nr<BITS, ZP, SM, 768, 3, GN, GT>(a, total_q, st);
+    return qlaunch_xf_nr<BITS, ZP, SM, 1024, 4, GN, GT>(a, total_q, st);
 }
 
 template <int BITS, bool ZP, int SM>
@@ -1202,15 +1227,11 @@ static hipError_t qlaunch_xf_cfg(const FusedXfArgs& a, int total_q, int ft, int 
         if (a.s.K / 4 > 6 * 512) { best_ft = 1024; best_wpq = 4; }
         else { best_ft = 512; best_wpq = best_wpq >= 2 ? 2 : 1; }
     }
-    // GLU_NORM has instantiations of its own (GN): the ones NORM and GLU run on stay as they were
-    if (a.xf_kind == 4) {
-        if (best_ft == 512) return best_wpq == 1 ? qlaunch_xf_nr<BITS, ZP, SM, 512, 1, true>(a, total_q, st) : qlaunch_xf_nr<BITS, ZP, SM, 512, 2, true>(a, total_q, st);
-        if (best_ft == 768) return qlaunch_xf_nr<BITS, ZP, SM, 768, 3, true>(a, total_q, st);
-        return qlaunch_xf_nr<BITS, ZP, SM, 1024, 4, true>(a, total_q, st);
-    }
-    if (best_ft == 512) return best_wpq == 1 ? qlaunch_xf_nr<BITS, ZP, SM, 512, 1, false>(a, total_q, st) : qlaunch_xf_nr<BITS, ZP, SM, 512, 2, false>(a, total_q, st);
-    if (best_ft == 768) return qlaunch_xf_nr<BITS, ZP, SM, 768, 3, false>(a, total_q, st);
-    return qlaunch_xf_nr<BITS, ZP, SM, 1024, 4, false>(a, total_q, st);
+    // GLU_NORM has instantiations of its own (GN): the ones NORM and GLU run on stay as they were; and relu^2 and GELU have theirs (GT), next
+    // to both: a call with silu runs what it ran
+    const bool gn = (a.xf_kind & 0xff) == 4, gt = (a.xf_kind >> 8) != XF_GATE_SILU;
+    if (gn) return gt ? qlaunch_xf_pick<BITS, ZP, SM, true, true>(a, total_q, best_ft, best_wpq, st) : qlaunch_xf_pick<BITS, ZP, SM, true, false>(a, total_q, best_ft, best_wpq, st);
+    return gt ? qlaunch_xf_pick<BITS, ZP, SM, false, true>(a, total_q, best_ft, best_wpq, st) : qlaunch_xf_pick<BITS, ZP, SM, false, false>(a, total_q, best_ft, best_wpq, st);
 }
 
 template <int BITS>
@@ -1240,9 +1261,15 @@ hipError_t QXENTRY(TMAC_QUAD_BITS, TMAC_QUAD_SCF16)(const FusedXfArgs& a, int to
     return qlaunch_xf_b<TMAC_QUAD_BITS>(a, total_q, ft, wpq, strict, st);
 }
 #if TMAC_QUAD_BITS == 2 && TMAC_QUAD_SCF16 == 0
+static bool xf_args_bad(const FusedXfArgs& a) {
+    const int kind = a.xf_kind & 0xff, gate = a.xf_kind >> 8;
+    if (kind != 1 && kind != 2 && kind != 4) return true;
+    if (gate < XF_GATE_SILU || gate > XF_GATE_GELU || (kind == 1 && gate != XF_GATE_SILU)) return true;
+    return kind == 4 && (!a.in2 || !a.gamma);
+}
 hipError_t launch_gemv_quad_xf(const FusedXfArgs& a_in, int ft, int wpq, bool strict, hipStream_t st) {
     if (!gemv_quad_supported(a_in.s) || a_in.s.K > QUAD_XF_MAX_K || a_in.nmat < 1 || a_in.nmat > 4 || !a_in.acc_mfma || a_in.dump ||
-        (a_in.xf_kind != 1 && a_in.xf_kind != 2 && a_in.xf_kind != 4) || (a_in.xf_kind == 4 && (!a_in.in2 || !a_in.gamma)))
+        xf_args_bad(a_in))
         return hipErrorInvalidValue;
     FusedXfArgs a = a_in;
     fused_precompute(a);

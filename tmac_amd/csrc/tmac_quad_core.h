@@ -203,17 +203,49 @@ __device__ __forceinline__ void xf_rows_t8(const XA& a, const void* __restrict__
         for (int i = 0; i < 8; ++i) t[i] = __fadd_rn(t[i], u[i]);
     }
 }
-// GLU: g = silu(fp32(in)) * fp32(in2) of (row n, pair p), k_gemv_quad's expression with in2[n] in the activations' dtype -- the row pass of a
+// The gate of a GLU / GLU_NORM (bits 8..15 of tmac_hip_xform::kind, as the kernels carry it: 0 silu, 1 relu^2, 2 tanh-GELU), one
+// expression per gate for all four places that apply one (k_gemv_quad, xf_rows_g8, k_decode_chain's reader form and its producer
+// epilogue).  silu(v) * u = v / (1 + exp(-v)) * u: hardware exp2 and reciprocal (1 ulp each; specified to a tolerance).  GELU in its
+// tanh form is the same expression with z = 2 * sqrt(2 / pi) * v * (1 + 0.044715 v^2) inside the exponential (0.5 (1 + tanh y) =
+// sigmoid(2 y)): three more VALU.  relu^2 is exact arithmetic, specified to the bit: (max(v, 0) * max(v, 0)) * u, each product rounded.
+constexpr int XF_GATE_SILU = 0, XF_GATE_RELU2 = 1, XF_GATE_GELU = 2;
+__device__ __forceinline__ float xf_gate_silu(float v, float u) {
+    return __fmul_rn(__fmul_rn(v, __builtin_amdgcn_rcpf(__fadd_rn(1.0f, __expf(-v)))), u);
+}
+__device__ __forceinline__ float xf_gate_relu2(float v, float u) {
+    const float m = fmaxf(v, 0.0f);
+    return __fmul_rn(__fmul_rn(m, m), u);
+}
+__device__ __forceinline__ float xf_gate_gelu(float v, float u) {
+    const float z = __fmul_rn(v, __fmaf_rn(__fmul_rn(v, v), 1.5957691216f * 0.044715f, 1.5957691216f));
+    return __fmul_rn(__fmul_rn(v, __builtin_amdgcn_rcpf(__fadd_rn(1.0f, __expf(-z)))), u);
+}
+// x[i] = gate(x[i]) * u[i].  `gate` is wave-uniform (a kernel argument or a descriptor field): one scalar branch around three straight
+// loops, the silu loop being the code the kernels had before the selector existed.
+template <int NE>
+__device__ __forceinline__ void xf_gate_mul(int gate, float (&x)[NE], const float (&u)[NE]) {
+    if (gate == XF_GATE_SILU) {
+#pragma unroll
+        for (int i = 0; i < NE; ++i) x[i] = xf_gate_silu(x[i], u[i]);
+    } else if (gate == XF_GATE_RELU2) {
+#pragma unroll
+        for (int i = 0; i < NE; ++i) x[i] = xf_gate_relu2(x[i], u[i]);
+    } else {
+#pragma unroll
+        for (int i = 0; i < NE; ++i) x[i] = xf_gate_gelu(x[i], u[i]);
+    }
+}
+// the gate of an argument block: its `gate` field where it has one (XfRowsGateArgs), else silu -- a constant, and the code is the silu loop alone
+template <class XA> __device__ __forceinline__ auto xf_rows_gate(const XA& a, int) -> decltype(a.gate) { return a.gate; }
+template <class XA> __device__ __forceinline__ int xf_rows_gate(const XA&, long) { return XF_GATE_SILU; }
+// GLU: g = gate(fp32(in)) * fp32(in2) of (row n, pair p), k_gemv_quad's expression with in2[n] in the activations' dtype -- the row pass of a
 // GLU_NORM and every builder form it with this one function, so the builders recompute the g the row's sum was taken over, bit for bit
 template <class XA>
 __device__ __forceinline__ void xf_rows_g8(const XA& a, const void* __restrict__ B, bool f16, int K, int n, int p, float (&x)[8]) {
     float u[8];
     xf_rows_ld8(B, f16, K, n, p, x);
     xf_rows_ld8(a.in2, f16, K, n, p, u);
-    // silu(v) = v / (1 + exp(-v)): hardware exp2 and reciprocal, as in k_gemv_quad
-#pragma unroll
-    for (int i = 0; i < 8; ++i)
-        x[i] = __fmul_rn(__fmul_rn(x[i], __builtin_amdgcn_rcpf(__fadd_rn(1.0f, __expf(-x[i])))), u[i]);
+    xf_gate_mul(xf_rows_gate(a, 0), x, u);
 }
 // The transformed x[8] of (row n, pair p): what an XF instantiation of an N > 1 LUT builder (and the tap, k_xf_rows_tap) takes in place
 // of its activation load.  NORM: (t * gamma) * r[n], k_gemv_quad's association (gamma first), r[n] from k_xf_rows; without gamma x = t

@@ -424,15 +424,38 @@ class TMACGeMMWrapper:
 
     CARRY = "carry"
     _XF_KINDS = {None: 0, "norm": 1, "glu": 2, "glu_norm": 4}      # TMAC_XF_* (3 is not a kind)
+    _XF_GATES = {"silu": 0, "relu2": 0x100, "gelu": 0x200}         # TMAC_XF_GATE_*: bits 8..15 of the kind
+
+    @staticmethod
+    def _xf_kind(kind, none_ok: bool = True) -> int:
+        """``tmac_hip_xform.kind`` of a kind string: "norm", "glu", "glu_norm", the last two optionally with a gate -- "glu:relu2",
+        "glu_norm:gelu", ":silu" = the bare name -- or None (no transform).  An unknown gate name raises ValueError, an unknown kind
+        KeyError; a gate on a kind that takes none ("norm:relu2") is left to the library, which refuses it.  An int is passed through
+        (tests of the library's own refusals)."""
+        if isinstance(kind, int):
+            return kind
+        kinds = TMACGeMMWrapper._XF_KINDS
+        if kind is None:
+            if not none_ok:
+                raise KeyError(kind)
+            return kinds[None]
+        base, sep, gate = kind.partition(":")
+        if sep and gate not in TMACGeMMWrapper._XF_GATES:
+            raise ValueError(f"unknown gate {gate!r} in transform kind {kind!r}: one of {sorted(TMACGeMMWrapper._XF_GATES)}")
+        if base not in kinds:
+            raise KeyError(kind)
+        return kinds[base] | (TMACGeMMWrapper._XF_GATES[gate] if sep else 0)
 
     def chain_xform(self, kind: str, in2=None, residual=None, gamma=None, eps: float = 1e-5, residual_out=None, keep: bool = False) -> None:
         """while recording a chain: a vector transform of the NEXT ``fused`` call's activations, applied inside its LUT build
         (tmac_hip_chain_xform).  kind "norm": t = in + residual (fp32 tensor, None, or ``TMACGeMMWrapper.CARRY`` = the t the latest
         kept NORM left in LDS); x = t * rsqrt(mean(t^2) + eps) * gamma (x = t without gamma); residual_out: t also goes to memory;
         keep: leave t for a later CARRY.  kind "glu": x = silu(in) * in2.  kind "glu_norm": g = silu(in) * in2, x = g * rsqrt(mean(g^2) +
-        eps) * gamma (gamma required, no residual operand); recorded only where the gate/up call in front publishes g itself."""
+        eps) * gamma (gamma required, no residual operand); recorded only where the gate/up call in front publishes g itself.
+        Another gate in the place of silu rides in the string: "glu:relu2" (max(in, 0)^2 * in2), "glu:gelu" (tanh-approximated GELU),
+        "glu_norm:relu2" (BitNet b1.58 2B-4T's FFN), "glu_norm:gelu"; ":silu" is the bare name."""
         xf = B.XForm()
-        xf.kind = {k: v for k, v in self._XF_KINDS.items() if k is not None}[kind]
+        xf.kind = self._xf_kind(kind, none_ok=False)
         xf.in2 = _ptr(in2) if in2 is not None else None
         xf.residual = 1 if residual is TMACGeMMWrapper.CARRY else (_ptr(residual) if residual is not None else None)
         xf.gamma = _ptr(gamma) if gamma is not None else None
@@ -447,7 +470,7 @@ class TMACGeMMWrapper:
     def fused_xf(self, weights_list, B_dev, C_list, kind, in2=None, residual=None, gamma=None, eps: float = 1e-5, residual_out=None,
                  act_dtype: Optional[int] = None, out_dtype: Optional[int] = None, stream=None) -> None:
         """``fused`` (N = 1) with a vector transform of the activations applied inside the kernel's LUT build
-        (tmac_hip_qgemm_fused_xf_dev): kind "norm" / "glu" / "glu_norm" as in ``chain_xform``, or None (a plain ``fused`` call).  Outside a
+        (tmac_hip_qgemm_fused_xf_dev): kind "norm" / "glu" / "glu_norm" (the last two with an optional ":relu2" / ":gelu" gate) as in ``chain_xform``, or None (a plain ``fused`` call).  Outside a
         recording the call launches by itself -- residual ``CARRY`` is refused there, and residual_out must not overlap a vector the
         call reads; inside ``record_chain()`` it records the transform and the call."""
         n = len(weights_list)
@@ -456,7 +479,7 @@ class TMACGeMMWrapper:
         if out_dtype is None:
             out_dtype = _dtype_code(C_list[0])
         xf = B.XForm()
-        xf.kind = TMACGeMMWrapper._XF_KINDS[kind]
+        xf.kind = TMACGeMMWrapper._xf_kind(kind)
         xf.in2 = _ptr(in2) if in2 is not None else None
         xf.residual = 1 if residual is TMACGeMMWrapper.CARRY else (_ptr(residual) if residual is not None else None)
         xf.gamma = _ptr(gamma) if gamma is not None else None
@@ -474,7 +497,7 @@ class TMACGeMMWrapper:
     @staticmethod
     def _xform_rows(kind, in2, residual, gamma, eps, residual_out) -> "B.XForm":
         xf = B.XForm()
-        xf.kind = TMACGeMMWrapper._XF_KINDS[kind]
+        xf.kind = TMACGeMMWrapper._xf_kind(kind)
         xf.in2 = _ptr(in2) if in2 is not None else None
         xf.residual = 1 if residual is TMACGeMMWrapper.CARRY else (_ptr(residual) if residual is not None else None)
         xf.gamma = _ptr(gamma) if gamma is not None else None
