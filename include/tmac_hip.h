@@ -358,6 +358,20 @@ int32_t tmac_hip_qgemm_fused_xf_rows_dev(const tmac_hip_weights* const* weights,
  * route 0 k_gemm_planes, 1 k_gemm_onehot, 3 k_gemv_rows, 7 the row loop; lut 1 the LUT image, 2 the half-table image.  The planner's
  * refusals come back as from the call (the scope checks of the call itself are not repeated). */
 int32_t tmac_hip_debug_xf_rows_plan(const tmac_hip_weights* const* weights, int nmat, void* const* C_dev, int N, int32_t* route, int32_t* lut);
+/* What an untransformed tmac_hip_qgemm_fused_dev call of N >= 1 rows on these matrices would run, under the current knobs (host only:
+ * plans, launches nothing).  route, in the order of the dispatcher's enum: 0 k_gemm_planes / k_gemm_planes_us, 1 k_gemm_onehot,
+ * 2 k_gemv_quad (grid.y = N), 3 k_gemv_rows, 4 k_gemv_fused, 5 k_gemv_lo, 6 the reference-layout kernel, 7 the row loop (one LUT build,
+ * then every matrix planned again as by tmac_hip_qgemm_dev).  lut, the build in front of the kernel: 0 none (the GEMV kernel builds its
+ * own), 1 the LUT image, 2 the half-table image, 3 every layout of the workspace (tmac_hip_preprocessor_dev).  The planner's refusals
+ * come back as from the call.  A recording, the deferred queue and a tap sit in front of the planner and are not modelled. */
+int32_t tmac_hip_debug_fused_plan(const tmac_hip_weights* const* weights, int nmat, void* const* C_dev, int N, int32_t* route, int32_t* lut);
+/* Launches per planned route since the library was loaded or reset (host counters, zeroed by tmac_hip_reset_state): counts[r] for the
+ * route numbers above, r = 0 .. 7.  Counted where a planned route is launched -- tmac_hip_qgemm_dev and the host-pointer entry points
+ * behind it, the fused entry point and its transformed forms -- so a row-loop call counts 1 under route 7 and, per matrix, 1 under the
+ * route that matrix then took.  A call is counted when it is planned for launch, a tap's launch included; a recorded call is not
+ * (a chain is no route), nor is a queued one that a flush serves from a chain.  Plain counters like tmac_hip_debug_rows_stats': exact
+ * while one thread at a time makes calls. */
+int32_t tmac_hip_debug_route_stats(uint64_t counts[8]);
 /* Parity tap: the fp32 x [N][K] that the LUT builds of the call above consume (the row pass plus a store around the builders' own load;
  * residual_out is written as the call writes it).  kind NORM, GLU or GLU_NORM (the last two with any gate); argument rules as above; synchronises the stream. */
 int32_t tmac_hip_debug_xf_rows(const void* B_dev, tmac_dtype_t act_dtype, const tmac_hip_xform* xf, int K, int N, float* x_out_dev,

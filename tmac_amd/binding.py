@@ -95,6 +95,8 @@ def load_library() -> C.CDLL:
         "tmac_hip_qgemm_fused_xf_dev": ([C.POINTER(vp), C.c_int, vp, C.c_int, C.POINTER(XForm), C.POINTER(vp), C.c_int, vp], i32),
         "tmac_hip_qgemm_fused_xf_rows_dev": ([C.POINTER(vp), C.c_int, vp, C.c_int, C.POINTER(XForm), C.POINTER(vp), C.c_int, C.c_int, vp], i32),
         "tmac_hip_debug_xf_rows_plan": ([C.POINTER(vp), C.c_int, C.POINTER(vp), C.c_int, C.POINTER(C.c_int32), C.POINTER(C.c_int32)], i32),
+        "tmac_hip_debug_fused_plan": ([C.POINTER(vp), C.c_int, C.POINTER(vp), C.c_int, C.POINTER(C.c_int32), C.POINTER(C.c_int32)], i32),
+        "tmac_hip_debug_route_stats": ([C.POINTER(C.c_uint64)], i32),
         "tmac_hip_debug_xf_rows": ([vp, C.c_int, C.POINTER(XForm), C.c_int, C.c_int, vp, vp], i32),
         "tmac_hip_qgemm_fused_partial_sums": ([vp, vp, C.c_int, vp, vp, vp, C.c_int, vp], i32),
         "tmac_hip_workspace_ptrs": ([vp, C.POINTER(vp), C.POINTER(sz), C.POINTER(vp), C.POINTER(vp)], i32),
@@ -157,7 +159,7 @@ def load_library() -> C.CDLL:
         "preprocessor_int8": ([C.c_int] * 4 + [vp] * 4, i32),
     }
     # $TMAC_HIP_LIB may name an OLDER build for an A/B run (tools/gpu): entry points it lacks stay unbound (calling one raises)
-    optional = {"tmac_hip_chain_is_stream", "tmac_hip_chain_xform", "tmac_hip_qgemm_fused_xf_dev", "tmac_hip_qgemm_fused_xf_rows_dev", "tmac_hip_debug_xf_rows", "tmac_hip_debug_xf_rows_plan", "tmac_hip_comm_init_ipc", "tmac_hip_comm_export", "tmac_hip_comm_connect", "tmac_hip_comm_status",
+    optional = {"tmac_hip_chain_is_stream", "tmac_hip_chain_xform", "tmac_hip_qgemm_fused_xf_dev", "tmac_hip_qgemm_fused_xf_rows_dev", "tmac_hip_debug_xf_rows", "tmac_hip_debug_xf_rows_plan", "tmac_hip_debug_fused_plan", "tmac_hip_debug_route_stats", "tmac_hip_comm_init_ipc", "tmac_hip_comm_export", "tmac_hip_comm_connect", "tmac_hip_comm_status",
                 "tmac_hip_debug_rows_kernel", "tmac_hip_debug_rows_stats", "tmac_hip_debug_rows_plan", "tmac_hip_debug_rows_comb_sums"} if os.environ.get("TMAC_HIP_LIB") else set()
     for name, (argt, rest) in sigs.items():
         try:

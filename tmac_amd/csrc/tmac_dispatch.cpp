@@ -32,6 +32,9 @@ struct Plan {
 };
 static Plan planned(Route r, LutBuild lut = LB_NONE) { return Plan{r, lut, TMAC_HIP_OK, nullptr, 0}; }
 static Plan refused(int32_t code, const char* msg, int mat = 0) { return Plan{R_ROW_LOOP, LB_NONE, code, msg, mat}; }
+// tmac_hip_debug_route_stats: one count per planned route at the site that launches it (the row loop counts itself, then each matrix
+// counts the route plan_split gave it)
+static void count_route(Route r) { ++g_knobs.route_launches[r]; }
 
 // ---- predicates of the plan ------------------------------------------------------------------------------------------------
 // matrices that can be served from one LUT | by one kernel instantiation
@@ -97,7 +100,8 @@ static bool planes_image_fits(const tmac_hip_workspace* ws, int K) { return ws->
 //    the shape wants: tmac_hip_preprocessor_dev builds it from PLANES_MIN_N rows on (it does not know the matrix), while the
 //    crossover applied here is the measured one of the matrix -- between the two the image is built and not used, or wanted and not
 //    there.  Without the image only k_gemm_onehot's own, later crossover counts: below it the row loop is the faster kernel.  The
-//    image's K and N are not checked against the LUT the workspace holds (only gimg_valid and its kind are).
+//    image counts only while it was built from the rows the workspace's LUT was built from (image_serves_lut: valid, and its K and N
+//    are the LUT's): every build or write of the LUT that does not build the image invalidates it.
 //  * A tap bypasses k_gemm_planes on the split entry point, but not k_gemm_onehot, which has a per-plane tap of its own.  On the
 //    fused entry point a tap (dump / lut_tap) bypasses both GEMMs -- and, in fused_impl, recording and the deferred queue.
 //  * Fast-aggregation weights are accepted on V_REF_LAYOUT, V_LO_MQSAD and V_LO_SDWA only (registration puts them in the LO layout,
@@ -107,7 +111,7 @@ static bool planes_image_fits(const tmac_hip_workspace* ws, int K) { return ws->
 //    planes_ok then fails for the weights (fast aggregation, 2 GB) or the matrices differ, and k_gemm_onehot runs below its own
 //    crossover.  1- and 3-bit matrices that k_gemm_planes cannot take, a mix of configurations and V_REF_LAYOUT go to the row loop,
 //    where each matrix is planned again from the workspace's state: after LB_ALL that may be a GEMM after all, after
-//    LB_HALF_TABLES k_gemv_quad or k_gemm_onehot (gimg_valid is left as an earlier call on the stream set it).
+//    LB_HALF_TABLES k_gemv_quad or k_gemm_onehot (the half-table build invalidates the image: none is found, whatever ran before).
 //  * The K > PAIRS_ROW_MAX_K limit applies to the row-wise image: unified-scale matrices beyond it get k_gemm_onehot on the LUT of
 //    the one-workgroup-per-act-group build.
 //  * image_fits: the LUT image of the stream's workspace, which has the row stride of the largest N the stream has seen, stays below
@@ -137,7 +141,7 @@ static Plan plan_split(const tmac_hip_weights* w, const tmac_hip_workspace* ws, 
     if (r != R_GEMV_QUAD && r != R_GEMV_FUSED) return planned(r);
     const bool rows = r == R_GEMV_QUAD && N >= 2 && !tap && g_knobs.rows_kernel != 1 && rows_covers(w);
     if (rows && g_knobs.rows_kernel == 2) return planned(R_GEMV_ROWS);
-    if (!tap && ws->gimg_valid && ws->gimg_kind == gimg_kind_for(w->s) && planes_ok(w) && planes_image_fits(ws, w->s.K) && planes_pays(w->s, w->s.Mw, N))
+    if (!tap && image_serves_lut(ws) && ws->gimg_kind == gimg_kind_for(w->s) && planes_ok(w) && planes_image_fits(ws, w->s.K) && planes_pays(w->s, w->s.Mw, N))
         return planned(R_GEMM_PLANES);
     if (onehot_pays(w->s, w->s.Mw, N) && gemm_onehot_supported(w->s)) return planned(R_GEMM_ONEHOT);
     if (rows && rows_pays(w->s, w->s.Mw, N)) return planned(R_GEMV_ROWS);
@@ -293,6 +297,7 @@ int32_t tmac_host::qgemm_impl(const tmac_hip_weights* w, const tmac_hip_workspac
     if (N <= 0 || N > ws->N) return fail(TMAC_HIP_E_ARG, "N=%d but the workspace LUT holds %d rows", N, ws->N);
     const Plan p = plan_split(w, ws, N, dump != nullptr);
     if (p.err) return fail(p.err, p.msg, p.mat);
+    count_route(p.route);
     void* cl[1] = {C_dev};
     switch (p.route) {
     case R_GEMM_PLANES: return planes_multi(&w, 1, ws, cl, out_dtype, N, nullptr, st);
@@ -387,7 +392,7 @@ extern "C" int32_t tmac_hip_debug_gemm_comb_sums(const tmac_hip_weights* w, cons
     if (!w || !ws_c || !comb_host) return fail(TMAC_HIP_E_ARG, "null argument");
     auto* ws = const_cast<tmac_hip_workspace*>(ws_c);
     hipStream_t st = (hipStream_t)stream;
-    if (!ws->gimg_valid || ws->gimg_kind != gimg_kind_for(w->s) || ws->K != w->s.K || N <= 0 || N > ws->N) return fail(TMAC_HIP_E_ARG, "the workspace holds no LUT image for K=%d, N=%d", w->s.K, N);
+    if (!image_serves_lut(ws) || ws->gimg_kind != gimg_kind_for(w->s) || ws->K != w->s.K || N <= 0 || N > ws->N) return fail(TMAC_HIP_E_ARG, "the workspace holds no LUT image for K=%d, N=%d", w->s.K, N);
     if (!planes_ok(w)) return fail(TMAC_HIP_E_NOMATCH, "k_gemm_planes does not cover this configuration");
     const size_t elems = (size_t)N * w->s.Mw * (w->s.m_groups >= 1 ? 1 : w->s.K / 64);
     DevBuf Ctmp;
@@ -451,7 +456,7 @@ extern "C" int32_t tmac_hip_debug_gemm_image_read(const tmac_hip_workspace* ws, 
     const int32_t brc = defer_barrier();
     if (brc) return brc;
     if (!ws || !half_tables_host || !lut_scales_host || !lut_biases_host || !entry_sums_host) return fail(TMAC_HIP_E_ARG, "null argument");
-    if (!ws->gimg_valid || N <= 0 || N > ws->N) return fail(TMAC_HIP_E_ARG, "the workspace holds no LUT image for N=%d", N);
+    if (!image_serves_lut(ws) || N <= 0 || N > ws->N) return fail(TMAC_HIP_E_ARG, "the workspace holds no LUT image for N=%d", N);
     hipStream_t st = (hipStream_t)stream;
     const int K = ws->K, Np = ws->gNpad;
     const bool rowwise = ws->gimg_kind == 1;           // one act group per row: k_preprocess_pairs_row's layout
@@ -553,7 +558,7 @@ static int32_t fused_prefill(Plan p, const tmac_hip_weights* const* wl, int nmat
         if (e != hipSuccess) return fail(TMAC_HIP_E_RUNTIME, "LUT image launch: %s", hipGetErrorString(e));
     } else if (p.lut == LB_HALF_TABLES) {
         ws->K = s0.K; ws->N = N; ws->ags = s0.ags; ws->qdev_u4_per_row = qdev_u4_for_K(s0.K);
-        if (xf) ws->gimg_valid = false;      // an image an earlier call left on the stream was not built from the transformed rows
+        ws->gimg_valid = false;      // an image an earlier call left on the stream was not built from this call's rows
         e = s0.ags == 64
             ? launch_preprocess_pairs(B_dev, f16, ws->qlut_lds, ws->lut_scales, ws->lut_biases, s0.K, N, nullptr, nullptr, 0, st, xf)
             : launch_preprocess_pairs_row(B_dev, f16, ws->qlut_lds, ws->lut_scales, ws->lut_biases, s0.K, N, nullptr, nullptr, 0, nullptr, nullptr, 0, st, xf);
@@ -562,6 +567,7 @@ static int32_t fused_prefill(Plan p, const tmac_hip_weights* const* wl, int nmat
         rc = tmac_hip_preprocessor_dev(ws, B_dev, act_dtype, s0.K, N, s0.ags, st);
         if (rc) return rc;
     }
+    count_route(p.route);
     if (p.route == R_GEMM_PLANES) return planes_multi(wl, nmat, ws, C_list, out_dtype, N, nullptr, st);
     if (p.route == R_GEMM_ONEHOT) return gemm_multi(wl, nmat, ws, C_list, out_dtype, N, nullptr, st);
     if (p.route == R_GEMV_ROWS) return rows_multi(wl, nmat, ws, C_list, out_dtype, N, nullptr, st);
@@ -596,6 +602,7 @@ int32_t tmac_host::fused_impl(const tmac_hip_weights* const* wl, int nmat, const
     const Plan p = plan_fused(wl, C_list, nmat, N, tap);
     if (p.err) return fail(p.err, p.msg, p.mat);
     if (p.route != R_GEMV_QUAD && p.route != R_GEMV_FUSED) return fused_prefill(p, wl, nmat, B_dev, act_dtype, C_list, out_dtype, N, st);
+    count_route(p.route);
     FusedArgs fa;
     const int nb = fill_fused_args(fa, wl, C_list, nmat, out_dtype, dump);
     fa.B = B_dev; fa.act_f16 = act_dtype == TMAC_F16;
@@ -694,6 +701,7 @@ extern "C" int32_t tmac_hip_qgemm_fused_xf_dev(const tmac_hip_weights* const* wl
     bind_thread_device();
     const int32_t brc = defer_barrier();       // never queued: behind the calling thread's queue (B_dev may be a queued output)
     if (brc) return brc;
+    count_route(p.route);
     FusedXfArgs fa;
     const int nb = fill_fused_args(fa, wl, C_list, nmat, out_dtype, nullptr);
     fa.B = B_dev; fa.act_f16 = act_dtype == TMAC_F16;
@@ -799,6 +807,24 @@ extern "C" int32_t tmac_hip_debug_xf_rows_plan(const tmac_hip_weights* const* wl
     if (p.err) return fail(p.err, p.msg, p.mat);
     if (route) *route = (int32_t)p.route;
     if (lut) *lut = (int32_t)p.lut;
+    return TMAC_HIP_OK;
+}
+
+// What an untransformed fused call on these matrices would run: plan_fused's answer as the call gets it (host only: plans, launches nothing).
+// route: enum Route; lut: enum LutBuild.
+extern "C" int32_t tmac_hip_debug_fused_plan(const tmac_hip_weights* const* wl, int nmat, void* const* C_list, int N, int32_t* route, int32_t* lut) {
+    if (!wl || !C_list || nmat < 1 || nmat > 4 || N < 1) return fail(TMAC_HIP_E_ARG, "bad plan arguments (1..4 matrices, N >= 1)");
+    const Plan p = plan_fused(wl, C_list, nmat, N, false);
+    if (p.err) return fail(p.err, p.msg, p.mat);
+    if (route) *route = (int32_t)p.route;
+    if (lut) *lut = (int32_t)p.lut;
+    return TMAC_HIP_OK;
+}
+
+extern "C" int32_t tmac_hip_debug_route_stats(uint64_t counts[8]) {
+    if (!counts) return fail(TMAC_HIP_E_ARG, "null argument");
+    static_assert(R_ROW_LOOP == 7, "tmac_hip_debug_route_stats documents eight routes (include/tmac_hip.h)");
+    for (int r = 0; r <= R_ROW_LOOP; ++r) counts[r] = g_knobs.route_launches[r];
     return TMAC_HIP_OK;
 }
 

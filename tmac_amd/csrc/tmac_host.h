@@ -67,6 +67,7 @@ struct tmac_hip_workspace {
     bool gimg_valid = false;
     float* xf_r = nullptr;       // fp32 [maxN]: 1 / rms per activation row of a transformed N > 1 call (k_xf_rows -> the XF LUT builders)
     int gimg_kind = 0;           // 1: row-wise image (one act group per row, k_gemm_planes_us) | 2: chunk-major image (act groups of 64, k_gemm_planes)
+    int gimg_K = 0, gimg_N = 0;  // the activation rows the valid image was built from: it serves the LUT above only while these equal K and N
 };
 
 namespace tmac_host {
@@ -107,6 +108,7 @@ struct Knobs {
     int defer_fail = 0;            // test hook (tmac_hip_debug_defer_fail): the n-th launch attempted by the deferred queue's flushes fails on the host side; one-shot
     int rows_kernel = 0;           // k_gemv_rows: 0 = where measured faster, 1 = never (the routing without it), 2 = wherever it covers the call (tmac_hip_debug_rows_kernel)
     uint64_t rows_launches = 0;    // k_gemv_rows launches since load or reset (tmac_hip_debug_rows_stats): a counter, reset with the settings
+    uint64_t route_launches[8] = {};   // launches per planned route, indexed by enum Route of tmac_dispatch.cpp (tmac_hip_debug_route_stats): counters, reset with the settings
     int chain_grid = 0;            // workgroups of chains built from now on (0 = one per CU; tests run two chains side by side on one device)
     unsigned long long* stamps = nullptr;        // phase stamps of the next fused launches (tmac_hip_debug_stamps)
     int32_t* stamp_dump = nullptr;               // scratch the stamp instantiation stores its tap into (allocated once, survives resets)
@@ -128,6 +130,9 @@ constexpr int PAIRS_ROW_MAX_K = 12288;   // largest K of the row-wise pair build
 inline int gemm_min_rows(int fitted) { return g_knobs.gemm_min_n <= 0 ? INT_MAX : g_knobs.gemm_min_n != 32 ? g_knobs.gemm_min_n : fitted; }
 // the LUT-image kind (tmac_hip_workspace::gimg_kind) k_gemm_planes wants for this shape: row-wise for unified scales, else chunk-major
 inline int gimg_kind_for(const Shape& s) { return s.m_groups >= 1 ? 1 : 2; }
+// Does the workspace's LUT image belong to the LUT it holds?  Valid, and built from the same K x N activation rows: the only image
+// k_gemm_planes and the image taps may read (whoever rebuilds the LUT without the image clears gimg_valid; K and N guard the rest)
+inline bool image_serves_lut(const tmac_hip_workspace* ws) { return ws->gimg_valid && ws->gimg_K == ws->K && ws->gimg_N == ws->N; }
 // The device layout of registered weights, which Shape spells as the pair (ts, lay): 16-table segments for the two-kernel path
 // (k_gemv_lo), 8-table units in 16-row blocks (k_gemv_fused), or 8-table units in row quads (k_gemv_quad and the GEMMs).
 enum Layout { L_LO, L_ROWBLOCK, L_QUAD };

@@ -88,7 +88,7 @@ extern "C" int32_t tmac_hip_preprocessor_dev(tmac_hip_workspace* ws, const void*
         : launch_preprocess(B_dev, (Dtype)act_dtype, ws->qlut_ref, ws->qlut_dev, ws->qlut_lds, ws->lut_scales, ws->lut_biases,
                             K, N, act_group_size, ws->qdev_u4_per_row, (hipStream_t)stream);
     if (e != hipSuccess) return fail(TMAC_HIP_E_RUNTIME, "preprocess launch: %s", hipGetErrorString(e));
-    ws->gimg_valid = row_img; ws->gimg_kind = row_img ? 1 : 0;
+    ws->gimg_valid = row_img; ws->gimg_kind = row_img ? 1 : 0; ws->gimg_K = K; ws->gimg_N = N;
     if (act_group_size == 64 && want_img) {   // what k_gemm_planes streams (tmac_hip_qgemm_dev may pick it)
         e = launch_lut_image(B_dev, act_dtype == TMAC_F16, ws->gimg, ws->gcol, K, N, ws->gNpad, (hipStream_t)stream);
         if (e != hipSuccess) return fail(TMAC_HIP_E_RUNTIME, "LUT image launch: %s", hipGetErrorString(e));
