@@ -163,38 +163,18 @@ extern "C" int ggml_tmac_hip_mul_mat_dev(const struct tmac_ggml_tensor* const* w
     }
     return tmac_hip_qgemm_fused_dev(wl, nw, x_dev, x_is_f32 ? TMAC_F32 : TMAC_F16, cl, dst_is_f32 ? TMAC_F32 : TMAC_F16, 1, g_stream);
 }
-// the same call with an element-wise operator applied to x inside the kernel (tmac_hip_qgemm_fused_xf_dev): never queued
-extern "C" int ggml_tmac_hip_mul_mat_dev_xf(const struct tmac_ggml_tensor* const* w, int nw, const void* x_dev, int x_is_f32, int kind,
-                                            const void* in2_dev, const float* residual, const float* norm_weight, float eps, float* residual_out,
-                                            void* const* dst_dev, int dst_is_f32) {
+// the same call with an element-wise operator applied to x inside the kernel, for n_rows rows of x: the one form behind the two entry
+// points below (name: the entry point's, for its two messages)
+static int mul_mat_dev_xf(const char* name, const struct tmac_ggml_tensor* const* w, int nw, const void* x_dev, int x_is_f32, int kind, const void* in2_dev,
+                          const float* residual, const float* norm_weight, float eps, float* residual_out, void* const* dst_dev, int dst_is_f32, int n_rows) {
+    char msg[160];
     if (!g_ready) return fail("ggml_tmac_hip_init has not been called");
-    if (!w || nw < 1 || nw > 4 || !x_dev || !dst_dev) return fail("bad mul_mat_dev_xf");
+    if (!w || nw < 1 || nw > 4 || !x_dev || !dst_dev || n_rows < 1) { snprintf(msg, sizeof(msg), "bad %s", name); return fail(msg); }
     const int base = kind & 0xff;      // bits 8..15: the gate of a glu / glu_norm (TMAC_XF_GATE_*), checked by the library
-    if (base != TMAC_XF_NORM && base != TMAC_XF_GLU && base != TMAC_XF_GLU_NORM) return fail("mul_mat_dev_xf: kind must be 1 (norm), 2 (glu) or 4 (glu_norm), the last two | a TMAC_XF_GATE_*");
-    g_err[0] = 0;
-    const tmac_hip_weights* wl[4];
-    void* cl[4];
-    for (int i = 0; i < nw; ++i) {
-        if (!w[i] || !w[i]->extra || !dst_dev[i]) return fail("null tensor");
-        wl[i] = ((const Handle*)w[i]->extra)->w;
-        cl[i] = dst_dev[i];
+    if (base != TMAC_XF_NORM && base != TMAC_XF_GLU && base != TMAC_XF_GLU_NORM) {
+        snprintf(msg, sizeof(msg), "%s: kind must be 1 (norm), 2 (glu) or 4 (glu_norm), the last two | a TMAC_XF_GATE_*", name);
+        return fail(msg);
     }
-    tmac_hip_xform xf;
-    memset(&xf, 0, sizeof(xf));
-    xf.kind = kind;
-    if (base == TMAC_XF_GLU) xf.in2 = in2_dev;
-    else { xf.residual = residual; xf.gamma = norm_weight; xf.eps = eps; xf.residual_out = residual_out; }
-    if (base == TMAC_XF_GLU_NORM) xf.in2 = in2_dev;      // (a residual operand set here is refused by the library, which names the field)
-    return tmac_hip_qgemm_fused_xf_dev(wl, nw, x_dev, x_is_f32 ? TMAC_F32 : TMAC_F16, &xf, cl, dst_is_f32 ? TMAC_F32 : TMAC_F16, g_stream);
-}
-// ... and for n_rows rows of x (tmac_hip_qgemm_fused_xf_rows_dev): prefill or a small batch through the same hook
-extern "C" int ggml_tmac_hip_mul_mat_dev_xf_rows(const struct tmac_ggml_tensor* const* w, int nw, const void* x_dev, int x_is_f32, int kind,
-                                                 const void* in2_dev, const float* residual, const float* norm_weight, float eps, float* residual_out,
-                                                 void* const* dst_dev, int dst_is_f32, int n_rows) {
-    if (!g_ready) return fail("ggml_tmac_hip_init has not been called");
-    if (!w || nw < 1 || nw > 4 || !x_dev || !dst_dev || n_rows < 1) return fail("bad mul_mat_dev_xf_rows");
-    const int base = kind & 0xff;      // bits 8..15: the gate of a glu / glu_norm (TMAC_XF_GATE_*), checked by the library
-    if (base != TMAC_XF_NORM && base != TMAC_XF_GLU && base != TMAC_XF_GLU_NORM) return fail("mul_mat_dev_xf_rows: kind must be 1 (norm), 2 (glu) or 4 (glu_norm), the last two | a TMAC_XF_GATE_*");
     g_err[0] = 0;
     const tmac_hip_weights* wl[4];
     void* cl[4];
@@ -210,6 +190,18 @@ extern "C" int ggml_tmac_hip_mul_mat_dev_xf_rows(const struct tmac_ggml_tensor* 
     else { xf.residual = residual; xf.gamma = norm_weight; xf.eps = eps; xf.residual_out = residual_out; }
     if (base == TMAC_XF_GLU_NORM) xf.in2 = in2_dev;      // (a residual operand set here is refused by the library, which names the field)
     return tmac_hip_qgemm_fused_xf_rows_dev(wl, nw, x_dev, x_is_f32 ? TMAC_F32 : TMAC_F16, &xf, cl, dst_is_f32 ? TMAC_F32 : TMAC_F16, n_rows, g_stream);
+}
+// one row (tmac_hip_qgemm_fused_xf_dev, which the rows form is for N = 1): never queued
+extern "C" int ggml_tmac_hip_mul_mat_dev_xf(const struct tmac_ggml_tensor* const* w, int nw, const void* x_dev, int x_is_f32, int kind,
+                                            const void* in2_dev, const float* residual, const float* norm_weight, float eps, float* residual_out,
+                                            void* const* dst_dev, int dst_is_f32) {
+    return mul_mat_dev_xf("mul_mat_dev_xf", w, nw, x_dev, x_is_f32, kind, in2_dev, residual, norm_weight, eps, residual_out, dst_dev, dst_is_f32, 1);
+}
+// ... and n_rows rows of x (tmac_hip_qgemm_fused_xf_rows_dev): prefill or a small batch through the same hook
+extern "C" int ggml_tmac_hip_mul_mat_dev_xf_rows(const struct tmac_ggml_tensor* const* w, int nw, const void* x_dev, int x_is_f32, int kind,
+                                                 const void* in2_dev, const float* residual, const float* norm_weight, float eps, float* residual_out,
+                                                 void* const* dst_dev, int dst_is_f32, int n_rows) {
+    return mul_mat_dev_xf("mul_mat_dev_xf_rows", w, nw, x_dev, x_is_f32, kind, in2_dev, residual, norm_weight, eps, residual_out, dst_dev, dst_is_f32, n_rows);
 }
 extern "C" int ggml_tmac_hip_set_deferred(int on) { return tmac_hip_defer(on); }
 extern "C" int ggml_tmac_hip_flush(void) { return tmac_hip_flush(g_stream); }
@@ -249,28 +241,26 @@ extern "C" int ggml_tmac_hip_segment_norm(const float* residual, int residual_is
     return tmac_hip_chain_xform(&xf);
 }
 
+// the transform of the three calls below: x = gate(in) * in2 (kind GLU), or the RMSNorm of that product (GLU_NORM), the gate in the kind
+static int segment_glu_xform(int32_t kind, const void* in2_f16, const float* norm_weight, float eps) {
+    tmac_hip_xform xf;
+    memset(&xf, 0, sizeof(xf));
+    xf.kind = kind; xf.in2 = in2_f16; xf.gamma = norm_weight; xf.eps = eps;
+    return tmac_hip_chain_xform(&xf);
+}
+
 // x = gate(in) * in2, or (norm_weight != NULL) the RMSNorm of that product: the one form behind _glu and _glu_norm.  The gate is checked by
 // tmac_hip_chain_xform (a value other than the three TMAC_XF_GATE_* is refused there, naming it)
 extern "C" int ggml_tmac_hip_segment_glu_gate(const void* in2_f16, int gate, const float* norm_weight, float eps) {
     if (gate & 0xff) return fail("segment_glu_gate: gate must be a TMAC_XF_GATE_* value (bits 8..15)");
-    tmac_hip_xform xf;
-    memset(&xf, 0, sizeof(xf));
-    xf.kind = (norm_weight ? TMAC_XF_GLU_NORM : TMAC_XF_GLU) | gate;
-    xf.in2 = in2_f16;
-    if (norm_weight) { xf.gamma = norm_weight; xf.eps = eps; }
-    return tmac_hip_chain_xform(&xf);
+    return segment_glu_xform((norm_weight ? TMAC_XF_GLU_NORM : TMAC_XF_GLU) | gate, in2_f16, norm_weight, norm_weight ? eps : 0.0f);
 }
 
 extern "C" int ggml_tmac_hip_segment_glu(const void* in2_f16) { return ggml_tmac_hip_segment_glu_gate(in2_f16, TMAC_XF_GATE_SILU, nullptr, 0.0f); }
 
 extern "C" int ggml_tmac_hip_segment_glu_norm(const void* in2_f16, const float* norm_weight, float eps) {
     // (without the weights this is no plain GLU: the library refuses a GLU_NORM without gamma, naming the field)
-    if (!norm_weight) {
-        tmac_hip_xform xf;
-        memset(&xf, 0, sizeof(xf));
-        xf.kind = TMAC_XF_GLU_NORM; xf.in2 = in2_f16; xf.eps = eps;
-        return tmac_hip_chain_xform(&xf);
-    }
+    if (!norm_weight) return segment_glu_xform(TMAC_XF_GLU_NORM, in2_f16, nullptr, eps);
     return ggml_tmac_hip_segment_glu_gate(in2_f16, TMAC_XF_GATE_SILU, norm_weight, eps);
 }
 

@@ -14,9 +14,8 @@ import numpy as np
 import pytest
 
 from oracle import oracle as orc
-from test_gpu_xf import KF, Mat, dev, host, np_norm, rel_err
-from test_gpu_xf_gate import NP_GATE
 from test_gpu_xf_glunorm import LAYER_SHAPES, layers_of, outside
+from xf_common import KF, NP_GATE, Mat, dev, host, np_gated, np_norm, rel_err
 
 pytestmark = pytest.mark.gpu
 EPS = 1e-5
@@ -109,14 +108,6 @@ def test_reader_form_on_external_vectors(tm, grid):
 
 
 # ---- 2. / 3. a decoder segment, recorded and call by call --------------------------------------------------------------------
-def np_gated(kind, a, b, gamma, handed_over_f16):
-    base, gate = kind.split(":")
-    g = NP_GATE[gate](a, b)
-    if handed_over_f16:
-        g = g.astype(np.float16).astype(np.float32)
-    return np_norm(g, gamma, EPS) if base == "glu_norm" else g
-
-
 def check_segment(kind, L, Ln, a, on, g, u, d, hn, h_out, qkv, handed_over_f16):
     """every mpGEMM of the segment against the oracle on what it consumed; the residual stream bit for bit"""
     assert rel_err(on, L.o.oracle(a)) <= 2e-3, "o"
@@ -124,7 +115,7 @@ def check_segment(kind, L, Ln, a, on, g, u, d, hn, h_out, qkv, handed_over_f16):
     x2 = np_norm(t2, L.g2.cpu().numpy(), EPS)
     eg, eu = rel_err(g, L.gate.oracle(x2)), rel_err(u, L.up.oracle(x2))
     assert eg <= 2e-3 and eu <= 2e-3, f"gate {eg:.2e} up {eu:.2e}"
-    ed = rel_err(d, L.down.oracle(np_gated(kind, g, u, L.g3.cpu().numpy(), handed_over_f16)))
+    ed = rel_err(d, L.down.oracle(np_gated(kind, g, u, L.g3.cpu().numpy(), EPS, handed_over_f16)))
     print(f"{kind}: down behind the gated product rel err vs oracle {ed:.2e}")
     assert np.isfinite(d).all() and ed <= 2e-3, f"down {ed:.2e}"
     t3 = d + t2

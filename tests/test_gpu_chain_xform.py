@@ -12,10 +12,10 @@ the last bit, which can move a LUT entry by one step; the residual stream (fp32 
 import numpy as np
 import pytest
 
-from oracle import oracle as orc
+from xf_common import Mat, np_glu, np_norm, rel_err
 
 pytestmark = pytest.mark.gpu
-BITS, BM, KF, GS, AGS = 2, 128, 16, 128, 64
+AGS = 64
 
 
 @pytest.fixture(scope="module")
@@ -29,42 +29,6 @@ def tm():
 @pytest.fixture(autouse=True)
 def _short_spin(tm):
     tm.binding.check(tm.lib().tmac_hip_debug_chain_config(0, 1 << 17))
-
-
-def rel_err(c, ref):
-    return float(np.abs(c.astype(np.float64) - ref.astype(np.float64)).max() / max(np.abs(ref).max(), 1e-30))
-
-
-class Mat:
-    """one W2 matrix (zero points, group 128) with scales sized so that its outputs are O(1) for O(1) inputs"""
-
-    def __init__(self, tm, wr, seed, Mw, K):
-        case = orc.make_case(seed, Mw, K, bits=BITS, gs=GS, ags=AGS, zero_point=True, fp16_values=True)
-        c = 1.0 / np.sqrt(2.5 * K)
-        case["sc"] = (case["sc"] * c).astype(np.float16).astype(np.float32)
-        lvl = (2 ** BITS - 1) / 2.0 - 2 ** (BITS - 1)
-        case["zr"] = (case["zr"] * c + lvl * case["sc"]).astype(np.float16).astype(np.float32)
-        self.A = orc.preprocess_weights(case["w"], BITS, BM, KF)
-        self.S = orc.preprocess_scales(case["sc"], case["zr"], BITS, BM)
-        self.Mw, self.K = Mw, K
-        cfg = tm.KCfg.make(Mw, K, BITS, BM, KF, GS, AGS, True, -1)
-        self.w = wr.register_weights(self.A, self.S, Mw, K, BITS, cfg, scales_dtype=tm.F32, dev_dtype=tm.F16)
-
-    def oracle(self, x):
-        """fp32 outputs of the oracle on the fp32 activation vector x"""
-        q, ls, lb = orc.preprocessor(x[None, :].astype(np.float32), AGS)
-        return orc.qgemm_float(self.A, q, self.S, ls, lb, self.Mw, self.K, 1, BITS, BM, KF, GS, AGS, True)[0]
-
-
-def np_norm(t, gamma, eps):
-    t = t.astype(np.float32)
-    rs = np.float32(1.0) / np.sqrt(np.float32((t.astype(np.float64) ** 2).mean()) + np.float32(eps))
-    return (t * rs).astype(np.float32) * gamma.astype(np.float32)
-
-
-def np_glu(a, b):
-    a = a.astype(np.float32); b = b.astype(np.float32)
-    return (a / (np.float32(1.0) + np.exp(-a))).astype(np.float32) * b
 
 
 @pytest.mark.parametrize("grid", [0, 96, 7, 1])

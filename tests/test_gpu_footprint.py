@@ -24,9 +24,10 @@ import pytest
 import footprint as fp
 from oracle import oracle as orc
 from test_gpu_chain import BITS_BM, Model, tm, _short_spin, rel_err      # noqa: F401  (fixtures)
-from test_gpu_chain_xform import Layer, Mat, np_glu, np_norm
+from test_gpu_chain_xform import Layer
 from test_gpu_gemm_planes import mrow
 from test_gpu_parity import GOLD, REL_TOL, check_bits, oracle_case
+from xf_common import Mat, np_glu, np_norm
 
 pytestmark = pytest.mark.gpu
 

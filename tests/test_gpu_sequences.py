@@ -45,7 +45,8 @@ from collections import namedtuple
 import numpy as np
 import pytest
 
-from test_gpu_xf_rows import EPS, Mat, np_transform, poison, rel_err
+from test_gpu_xf_rows import EPS, np_transform
+from xf_common import Mat, poison, rel_err
 
 pytestmark = pytest.mark.gpu
 E_ARG = -4

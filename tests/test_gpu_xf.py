@@ -13,9 +13,10 @@ import pytest
 
 from oracle import oracle as orc
 from footprint import check_footprint
+from xf_common import Mat, dev, host, np_glu, np_norm, poison, rel_err
 
 pytestmark = pytest.mark.gpu
-BM, KF = 128, 16
+BM = 128
 XF_CONFIGS = [(512, 1), (512, 2), (768, 3), (1024, 4)]      # the (threads, waves per quad) with an XF instantiation (include/tmac_hip.h)
 
 
@@ -25,75 +26,6 @@ def tm():
     import tmac_amd
     assert torch.cuda.is_available(), "GPU tests need a GPU"
     return tmac_amd
-
-
-def rel_err(c, ref):
-    return float(np.abs(c.astype(np.float64) - ref.astype(np.float64)).max() / max(np.abs(ref).max(), 1e-30))
-
-
-def np_norm(t, gamma, eps):
-    t = t.astype(np.float32)
-    rs = np.float32(1.0) / np.sqrt(np.float32((t.astype(np.float64) ** 2).mean()) + np.float32(eps))
-    return (t * rs).astype(np.float32) * gamma.astype(np.float32)
-
-
-def np_glu(a, b):
-    a = a.astype(np.float32); b = b.astype(np.float32)
-    return (a / (np.float32(1.0) + np.exp(-a))).astype(np.float32) * b
-
-
-def pick_bm(Mw, bits):
-    """the largest bm of the usual ones that tiles M = Mw * bits (registration: bm % 32, (bm / bits) % 8, M % bm)"""
-    return next(b for b in {1: (128, 32), 2: (128, 32), 3: (192, 96), 4: (256, 128, 32)}[bits] if (Mw * bits) % b == 0)
-
-
-class Mat:
-    """one matrix with scales sized so that its outputs are O(1) for O(1) inputs.  m_groups >= 1: unified scales, one act group per row"""
-
-    def __init__(self, tm, wr, seed, Mw, K, bits=2, gs=128, m_groups=-1, ags=64, dev_dtype=None):
-        self.Mw, self.K, self.bits, self.gs, self.mg, self.ags = Mw, K, bits, gs, m_groups, ags
-        c = 1.0 / np.sqrt(2.5 * K)
-        if m_groups >= 1:
-            self.ags = K
-            case = orc.make_case(seed, Mw, K, bits=bits, ags=K, m_groups=m_groups, zero_point=False)
-            self.bm = pick_bm(Mw, bits)
-            self.S = (case["sc"] * c).astype(np.float32)
-            self.zp = False
-            cfg = tm.KCfg.make(Mw, K, bits, self.bm, KF, gs, K, False, m_groups)
-            self.A = orc.preprocess_weights(case["w"], bits, self.bm, KF)
-            self.w = wr.register_weights(self.A, self.S, Mw, K, bits, cfg, scales_dtype=tm.F32, dev_dtype=tm.F32)
-            return
-        self.zp = True
-        self.bm = pick_bm(Mw, bits)
-        case = orc.make_case(seed, Mw, K, bits=bits, gs=gs, ags=ags, zero_point=True, fp16_values=True)
-        case["sc"] = (case["sc"] * c).astype(np.float16).astype(np.float32)
-        lvl = (2 ** bits - 1) / 2.0 - 2 ** (bits - 1)
-        case["zr"] = (case["zr"] * c + lvl * case["sc"]).astype(np.float16).astype(np.float32)
-        self.A = orc.preprocess_weights(case["w"], bits, self.bm, KF)
-        self.S = orc.preprocess_scales(case["sc"], case["zr"], bits, self.bm)
-        cfg = tm.KCfg.make(Mw, K, bits, self.bm, KF, gs, ags, True, -1)
-        self.w = wr.register_weights(self.A, self.S, Mw, K, bits, cfg, scales_dtype=tm.F32, dev_dtype=tm.F16 if dev_dtype is None else dev_dtype)
-
-    def oracle(self, x):
-        """fp32 outputs of the oracle on the fp32 activation vector x"""
-        q, ls, lb = orc.preprocessor(x[None, :].astype(np.float32), self.ags)
-        if self.mg >= 1:
-            return orc.qgemm_scale_final(self.A, q, self.S, ls[:, 0], lb[:, 0], self.Mw, self.K, 1, self.bits, self.bm, KF, self.mg)[0][0]
-        return orc.qgemm_float(self.A, q, self.S, ls, lb, self.Mw, self.K, 1, self.bits, self.bm, KF, self.gs, self.ags, self.zp)[0]
-
-
-def dev(a):
-    import torch
-    return torch.from_numpy(np.ascontiguousarray(a)).cuda()
-
-
-def poison(n, dtype):
-    import torch
-    return torch.full((n,), float("nan"), dtype=dtype, device="cuda")
-
-
-def host(t):
-    return t.float().cpu().numpy()
 
 
 def vectors(K, seed, act_dtype):

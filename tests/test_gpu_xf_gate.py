@@ -2,7 +2,7 @@
 ffn_sub_norm(relu(gate)^2 * up) -- and the tanh-approximated GELU of GeGLU decoders, inside k_gemv_quad (tmac_hip_qgemm_fused_xf_dev).
 
 Reference and bar, those of tests/test_gpu_xf.py: every output within 2e-3 of max |C| of the ORACLE run on the vector transformed in numpy
-(np_relu2 / np_gelu below, float32, then np_norm for kind 4), all finite.  Where that bar cannot see a defect -- the mean square of kind 4
+(np_relu2 / np_gelu of tests/xf_common.py, float32, then np_norm for kind 4), all finite.  Where that bar cannot see a defect -- the mean square of kind 4
 taken over other numbers than the gate produced -- the kernel is compared bit for bit with its own NORM fed the g the tap shows; relu^2, which
 is exact arithmetic, is held to exact zeros.
 """
@@ -12,7 +12,8 @@ import numpy as np
 import pytest
 
 from footprint import check_footprint
-from test_gpu_xf import Mat, XF_CONFIGS, dev, host, np_norm, poison, rel_err, vectors
+from test_gpu_xf import XF_CONFIGS, vectors
+from xf_common import NP_GATE, Mat, dev, host, np_gated, np_norm, poison, rel_err
 
 pytestmark = pytest.mark.gpu
 EPS = 1e-5
@@ -37,27 +38,6 @@ def _knobs(tm):
     tm.binding.check(L.tmac_hip_debug_quad_config(0, 0))
 
 
-def np_relu2(a, b):
-    a = a.astype(np.float32); b = b.astype(np.float32)
-    return (np.maximum(a, 0) ** 2 * b).astype(np.float32)
-
-
-def np_gelu(a, b):
-    a = a.astype(np.float32); b = b.astype(np.float32)
-    return (np.float32(0.5) * a * (np.float32(1) + np.tanh(np.float32(0.7978845608) * (a + np.float32(0.044715) * a ** 3))) * b).astype(np.float32)
-
-
-NP_GATE = {"relu2": np_relu2, "gelu": np_gelu}
-
-
-def np_gated(kind, gate, a, b, gamma, handed_over_f16=False):
-    """the vector a call of `kind`:`gate` builds its tables from"""
-    g = NP_GATE[gate](a, b)
-    if handed_over_f16:
-        g = g.astype(np.float16).astype(np.float32)
-    return np_norm(g, gamma, EPS) if kind == "glu_norm" else g
-
-
 _MATS = {}
 
 
@@ -78,7 +58,7 @@ def run_gated(tm, wr, mats, K, kind, gate, act_dtype, out_dtype, seed=3, label="
         ops.update(gamma=v["gam"], eps=EPS)
     wr.fused_xf([m.w for m in mats], v["x"], outs, f"{kind}:{gate}", **ops)
     torch.cuda.synchronize()
-    xn = np_gated(kind, gate, v["xh"], v["x2h"], v["gamh"])
+    xn = np_gated(f"{kind}:{gate}", v["xh"], v["x2h"], v["gamh"], EPS)
     for i, (m, o) in enumerate(zip(mats, outs)):
         e = rel_err(host(o), m.oracle(xn))
         print(f"{kind}:{gate} {label} K={K} matrix {i}: rel err vs oracle {e:.2e}")
@@ -227,7 +207,7 @@ def test_refusals(tm):
     rc, msg = raw(4 | 0x100, 1)
     assert rc == 0, msg
     torch.cuda.synchronize()
-    assert rel_err(o.cpu().numpy()[:Mw], m.oracle(np_gated("glu_norm", "relu2", v["xh"], v["x2h"], v["gamh"]))) <= 2e-3
+    assert rel_err(o.cpu().numpy()[:Mw], m.oracle(np_gated("glu_norm:relu2", v["xh"], v["x2h"], v["gamh"], EPS))) <= 2e-3
     assert bool(torch.isnan(o[Mw:]).all())
 
 
@@ -262,7 +242,7 @@ def test_footprint(tm):
         wr.fused_xf([m.w for m in mats], xd, outs, "glu_norm:relu2", **ops)
 
     def check_want(want):
-        xt = np_gated("glu_norm", "relu2", x, x2, gam)
+        xt = np_gated("glu_norm:relu2", x, x2, gam, EPS)
         for i, m in enumerate(mats):
             assert rel_err(want[f"C{i}"].astype(np.float32), m.oracle(xt)) <= 2e-3
     check_footprint(call, check_want=check_want)

@@ -13,7 +13,8 @@ import numpy as np
 import pytest
 
 from footprint import check_footprint
-from test_gpu_xf import Mat, XF_CONFIGS, dev, host, np_glu, np_norm, poison, rel_err, vectors
+from test_gpu_xf import XF_CONFIGS, vectors
+from xf_common import Mat, dev, host, np_glu, np_norm, poison, rel_err
 
 pytestmark = pytest.mark.gpu
 EPS = 1e-5

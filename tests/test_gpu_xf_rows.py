@@ -19,11 +19,10 @@ import ctypes as C
 import numpy as np
 import pytest
 
-from oracle import oracle as orc
 from footprint import check_footprint
+from xf_common import Mat, dev, host, np_glu, np_norm, poison, rel_err
 
 pytestmark = pytest.mark.gpu
-KF = 16
 E_ARG, E_NOMATCH, E_RUNTIME = -4, -1, -3
 EPS = 1e-5
 
@@ -34,63 +33,6 @@ def tm():
     import tmac_amd
     assert torch.cuda.is_available(), "GPU tests need a GPU"
     return tmac_amd
-
-
-def rel_err(c, ref):
-    return float(np.abs(c.astype(np.float64) - ref.astype(np.float64)).max() / max(np.abs(ref).max(), 1e-30))
-
-
-def np_norm_rows(t, gamma, eps):
-    """tests/test_gpu_xf.py's np_norm, row by row"""
-    t = t.astype(np.float32)
-    rs = np.float32(1.0) / np.sqrt((t.astype(np.float64) ** 2).mean(axis=1).astype(np.float32) + np.float32(eps))
-    return (t * rs[:, None]).astype(np.float32) * gamma.astype(np.float32)[None, :]
-
-
-def np_glu(a, b):
-    a = a.astype(np.float32); b = b.astype(np.float32)
-    return (a / (np.float32(1.0) + np.exp(-a))).astype(np.float32) * b
-
-
-def pick_bm(Mw, bits):
-    return next(b for b in {1: (128, 32), 2: (128, 32), 3: (192, 96), 4: (256, 128, 32)}[bits] if (Mw * bits) % b == 0)
-
-
-class Mat:
-    """one matrix with scales sized so that its outputs are O(1) for O(1) inputs.  m_groups >= 1: unified scales, one act group per row"""
-
-    def __init__(self, tm, wr, seed, Mw, K, bits=2, gs=128, zp=True, m_groups=-1, ags=64, fa=0):
-        self.Mw, self.K, self.bits, self.gs, self.mg, self.zp = Mw, K, bits, gs, m_groups, zp and m_groups < 1
-        self.ags = K if m_groups >= 1 else ags
-        self.bm = pick_bm(Mw, bits)
-        c = 1.0 / np.sqrt(2.5 * K)
-        kf = KF if self.ags != 32 else 8
-        if m_groups >= 1:
-            case = orc.make_case(seed, Mw, K, bits=bits, ags=K, m_groups=m_groups, zero_point=False)
-            self.S = (case["sc"] * c).astype(np.float32)
-            cfg = tm.KCfg.make(Mw, K, bits, self.bm, kf, gs, K, False, m_groups)
-            self.A = orc.preprocess_weights(case["w"], bits, self.bm, kf)
-            self.w = wr.register_weights(self.A, self.S, Mw, K, bits, cfg, scales_dtype=tm.F32, dev_dtype=tm.F32)
-            return
-        case = orc.make_case(seed, Mw, K, bits=bits, gs=gs, ags=self.ags, zero_point=self.zp, fp16_values=True)
-        sc = (case["sc"] * c).astype(np.float16).astype(np.float32)
-        zr = None
-        if self.zp:
-            lvl = (2 ** bits - 1) / 2.0 - 2 ** (bits - 1)
-            zr = (case["zr"] * c + lvl * sc).astype(np.float16).astype(np.float32)
-        self.A = orc.preprocess_weights(case["w"], bits, self.bm, kf)
-        self.S = orc.preprocess_scales(sc, zr, bits, self.bm)
-        cfg = tm.KCfg.make(Mw, K, bits, self.bm, kf, gs, self.ags, self.zp, -1)
-        self.w = wr.register_weights(self.A, self.S, Mw, K, bits, cfg, scales_dtype=tm.F32, dev_dtype=tm.F16, fast_aggregation=fa)
-
-    def oracle(self, X):
-        """fp32 outputs [N][Mw] of the oracle on the fp32 activation rows X [N][K]"""
-        X = np.ascontiguousarray(X, np.float32)
-        N = X.shape[0]
-        q, ls, lb = orc.preprocessor(X, self.ags)
-        if self.mg >= 1:
-            return orc.qgemm_scale_final(self.A, q, self.S, ls[:, 0], lb[:, 0], self.Mw, self.K, N, self.bits, self.bm, KF, self.mg)[0]
-        return orc.qgemm_float(self.A, q, self.S, ls, lb, self.Mw, self.K, N, self.bits, self.bm, KF, self.gs, self.ags, self.zp)
 
 
 FLAVOURS = {
@@ -106,20 +48,6 @@ def make_mats(tm, flavour, seed=10):
     K, mws, kw = FLAVOURS[flavour]
     wr = tm.TMACGeMMWrapper(act_group_size=K if kw.get("m_groups", -1) >= 1 else 64)
     return wr, K, [Mat(tm, wr, seed + i, mw, K, **kw) for i, mw in enumerate(mws)]
-
-
-def dev(a):
-    import torch
-    return torch.from_numpy(np.ascontiguousarray(a)).cuda()
-
-
-def poison(shape, dtype):
-    import torch
-    return torch.full(shape if isinstance(shape, tuple) else (shape,), float("nan"), dtype=dtype, device="cuda")
-
-
-def host(t):
-    return t.float().cpu().numpy()
 
 
 _VEC = {}
@@ -196,7 +124,7 @@ def np_transform(v, kind):
     if kind == "glu":
         return np_glu(v["x"], v["x2"])
     t = v["x"].astype(np.float32) + v["res"]
-    return t if kind == "add" else np_norm_rows(t, v["gam"], EPS)
+    return t if kind == "add" else np_norm(t, v["gam"], EPS)
 
 
 def plain_same_route(tm, wr, mats, route, xt, N, out_dtype):
@@ -480,7 +408,7 @@ def test_refusals(tm):
     t = v["x"] + v["res"]
     assert np.array_equal(rout[:N * K].cpu().numpy().reshape(N, K), t) and bool(torch.isnan(rout[N * K:]).all())
     assert rows_launches(tm) > r0
-    assert rel_err(o.cpu().numpy(), m.oracle(np_norm_rows(t, v["gam"], EPS))) <= 2e-3
+    assert rel_err(o.cpu().numpy(), m.oracle(np_norm(t, v["gam"], EPS))) <= 2e-3
 
 
 def test_refused_while_recording(tm):
@@ -540,7 +468,7 @@ def test_deferral(tm):
         return mid, o
     mid_w, want = sequence()
     assert np.isfinite(host(want)).all()
-    assert rel_err(host(want), m1.oracle(np_norm_rows(host(mid_w), v["gam"], EPS))) <= 2e-3
+    assert rel_err(host(want), m1.oracle(np_norm(host(mid_w), v["gam"], EPS))) <= 2e-3
     tm.binding.check(L.tmac_hip_defer(1))
     try:
         f0 = defer_stats(tm)

@@ -15,8 +15,8 @@ import ctypes as C
 import numpy as np
 import pytest
 
-from test_gpu_xf_rows import (EPS, ROUTE_CODE, Mat, host, make_mats, np_norm_rows, on_device, plain_same_route, planned_route, poison, rel_err,
-                              rows_launches, set_route, vectors)
+from test_gpu_xf_rows import EPS, ROUTE_CODE, make_mats, on_device, plain_same_route, planned_route, rows_launches, set_route, vectors
+from xf_common import Mat, host, np_gated, np_relu2, poison, rel_err
 
 pytestmark = pytest.mark.gpu
 E_NOMATCH = -1
@@ -37,24 +37,9 @@ def _default_route(tm):
     set_route(tm, "loop")           # every knob of the routes back at its default
 
 
-def np_relu2(a, b):
-    a = a.astype(np.float32); b = b.astype(np.float32)
-    return (np.maximum(a, 0) ** 2 * b).astype(np.float32)
-
-
-def np_gelu(a, b):
-    a = a.astype(np.float32); b = b.astype(np.float32)
-    return (np.float32(0.5) * a * (np.float32(1) + np.tanh(np.float32(0.7978845608) * (a + np.float32(0.044715) * a ** 3))) * b).astype(np.float32)
-
-
-NP_GATE = {"relu2": np_relu2, "gelu": np_gelu}
-
-
 def np_rows(v, kind):
     """the rows a call of kind "glu:<gate>" / "glu_norm:<gate>" builds its tables from"""
-    base, gate = kind.split(":")
-    g = NP_GATE[gate](v["x"], v["x2"])
-    return np_norm_rows(g, v["gam"], EPS) if base == "glu_norm" else g
+    return np_gated(kind, v["x"], v["x2"], v["gam"], EPS)
 
 
 def ops_of(d, kind):

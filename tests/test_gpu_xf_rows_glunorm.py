@@ -4,7 +4,7 @@ row's r; the LUT builders recompute g with the same device function and take (g 
 
 Bars (those of tests/test_gpu_xf_rows.py):
   * a row of an N-row call is that row of an N = 1 tap call, bit for bit; the tap within 1e-5 (of max |x|, rel_err below: the value and the
-    form tests/test_gpu_xf_rows.py holds its tap to) of np_glu followed by np_norm_rows;
+    form tests/test_gpu_xf_rows.py holds its tap to) of np_glu followed by np_norm, row by row;
   * the LUT path: the outputs are those of the plain call on the same route fed the tapped x as fp32 activations, bit for bit;
   * every output within 2e-3 of max |C| of the oracle on the numpy-transformed rows.
 N = 5 for the small routes (k_gemm_onehot, k_gemv_rows forced, the row loop), N = 70 for k_gemm_planes: a second, padded tile whose rows
@@ -16,8 +16,8 @@ import numpy as np
 import pytest
 
 from footprint import check_footprint
-from test_gpu_xf_rows import (EPS, FLAVOURS, ROUTE_CODE, Mat, dev, host, make_mats, np_glu, np_norm_rows, on_device, plain_same_route, planned_route,
-                              poison, rel_err, rows_launches, set_route, vectors)
+from test_gpu_xf_rows import EPS, FLAVOURS, ROUTE_CODE, make_mats, on_device, plain_same_route, planned_route, rows_launches, set_route, vectors
+from xf_common import Mat, host, np_glu, np_norm, poison, rel_err
 
 pytestmark = pytest.mark.gpu
 E_ARG, E_NOMATCH = -4, -1
@@ -38,7 +38,7 @@ def _default_route(tm):
 
 
 def np_glunorm_rows(v):
-    return np_norm_rows(np_glu(v["x"], v["x2"]), v["gam"], EPS)
+    return np_norm(np_glu(v["x"], v["x2"]), v["gam"], EPS)
 
 
 def tap4(wr, d, K, N):

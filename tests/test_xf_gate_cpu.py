@@ -51,8 +51,8 @@ def test_wrapper_resolves_the_gate_and_keeps_its_kinds():
     assert W._xf_kind("glu:silu") == W._xf_kind("glu") == 2 and W._xf_kind("glu_norm:silu") == W._xf_kind("glu_norm") == 4
     assert W._xf_kind("norm") == 1 and W._xf_kind(None) == 0
     # all four methods go through the one resolver: the struct the row forms build carries the gate
-    assert W._xform_rows("glu_norm:relu2", None, None, None, 1e-5, None).kind == 0x104
-    assert W._xform_rows("glu:gelu", None, None, None, 1e-5, None).kind == 0x202
+    assert W._xform("glu_norm:relu2", None, None, None, 1e-5, None, False, True).kind == 0x104
+    assert W._xform("glu:gelu", None, None, None, 1e-5, None, False, True).kind == 0x202
 
 
 @pytest.mark.parametrize("kind", ["glu:tanh", "glu_norm:", "glu:RELU2"])
@@ -62,7 +62,7 @@ def test_an_unknown_gate_name_raises(kind):
     with pytest.raises(ValueError):
         W._xf_kind(kind)
     with pytest.raises(ValueError):
-        W._xform_rows(kind, None, None, None, 1e-5, None)
+        W._xform(kind, None, None, None, 1e-5, None, False, True)
 
 
 def test_no_device_is_reported():

@@ -32,7 +32,7 @@ def test_wrapper_maps_glu_norm_and_keeps_its_signatures():
     import tmac_amd
     W = tmac_amd.TMACGeMMWrapper
     assert W._XF_KINDS == {None: 0, "norm": 1, "glu": 2, "glu_norm": 4}
-    xf = W._xform_rows("glu_norm", None, None, None, 1e-5, None)
+    xf = W._xform("glu_norm", None, None, None, 1e-5, None, False, True)
     assert xf.kind == 4
     par = lambda f: list(inspect.signature(f).parameters)[1:]
     assert par(W.chain_xform) == ["kind", "in2", "residual", "gamma", "eps", "residual_out", "keep"]

@@ -15,25 +15,23 @@ using namespace tmac_host;
 // ---------------------------------------------------------------------------------------------
 static thread_local std::vector<ChainRecOp>* g_chain_rec = nullptr;
 static thread_local std::vector<ChainRecGather>* g_chain_gat = nullptr;
-static thread_local tmac_hip_xform g_chain_xf = {};                  // applies to the next recorded call (kind: the low byte alone)
-static thread_local int g_chain_gate = 0;                            // ... and its gate (xf_kind_check), meaningful with a GLU / GLU_NORM
-static bool has_glu(const tmac_hip_xform& xf) { return xf.kind == TMAC_XF_GLU || xf.kind == TMAC_XF_GLU_NORM; }   // reads a second vector
+static thread_local std::optional<XfSpec> g_chain_xf;               // the transform declared for the next recorded call, resolved (tmac_xform.h)
 bool tmac_host::chain_recording() { return g_chain_rec != nullptr; }
-void tmac_host::chain_clear_xform() { memset(&g_chain_xf, 0, sizeof(g_chain_xf)); }
+void tmac_host::chain_clear_xform() { g_chain_xf.reset(); }
 
 int32_t tmac_host::chain_record(const tmac_hip_weights* const* wl, int nmat, const void* B_dev, tmac_dtype_t act_dtype,
                             void* const* C_list, tmac_dtype_t out_dtype, int N) {
     // (a rejected call must not leave its transform pending for the next recorded call)
-    if (N != 1) { memset(&g_chain_xf, 0, sizeof(g_chain_xf)); return fail(TMAC_HIP_E_NOMATCH, "a decode chain records N = 1 calls only"); }
+    if (N != 1) { chain_clear_xform(); return fail(TMAC_HIP_E_NOMATCH, "a decode chain records N = 1 calls only"); }
     ChainRecOp op;
     for (int i = 0; i < nmat; ++i) {
-        if (!wl[i] || !C_list[i]) { memset(&g_chain_xf, 0, sizeof(g_chain_xf)); return fail(TMAC_HIP_E_ARG, "null matrix or output"); }
+        if (!wl[i] || !C_list[i]) { chain_clear_xform(); return fail(TMAC_HIP_E_ARG, "null matrix or output"); }
         op.w.push_back(wl[i]);
         op.C.push_back(C_list[i]);
     }
     op.B = B_dev; op.act = act_dtype; op.out = out_dtype;
-    op.xf = g_chain_xf; op.gate = has_glu(g_chain_xf) ? g_chain_gate : 0;
-    memset(&g_chain_xf, 0, sizeof(g_chain_xf));
+    op.xf = g_chain_xf.value_or(XfSpec{});
+    chain_clear_xform();
     g_chain_rec->push_back(op);
     return TMAC_HIP_OK;
 }
@@ -42,20 +40,10 @@ int32_t tmac_host::chain_record(const tmac_hip_weights* const* wl, int nmat, con
 extern "C" int32_t tmac_hip_chain_xform(const tmac_hip_xform* xf) {
     if (!g_chain_rec) return fail(TMAC_HIP_E_ARG, "no chain is being recorded on this thread");
     if (!xf) return fail(TMAC_HIP_E_ARG, "null transform");
-    int kind = 0, gate = 0;
-    const int32_t krc = xf_kind_check(xf->kind, &kind, &gate);
-    if (krc) return krc;
-    if (kind == TMAC_XF_GLU_NORM) {
-        const int32_t grc = glu_norm_check(xf);
-        if (grc) return grc;
-    }
-    if (kind == TMAC_XF_GLU && !xf->in2) return fail(TMAC_HIP_E_ARG, "GLU needs a second vector");
-    // (residual == (void*)1 is the CARRY tag, not an address)
-    const struct { const void* p; const char* name; } vec[] = {{xf->in2, "in2"}, {xf->residual == (const void*)1 ? nullptr : xf->residual, "residual"},
-                                                              {xf->gamma, "gamma"}, {xf->residual_out, "residual_out"}};
-    for (const auto& v : vec)
-        if (misaligned(v.p, XFORM_ALIGN)) return fail(TMAC_HIP_E_ARG, "transform vector %s must be %zu-byte aligned (read or written 16 bytes at a time)", v.name, XFORM_ALIGN);
-    g_chain_xf = *xf; g_chain_xf.kind = kind; g_chain_gate = gate;
+    XfSpec spec;
+    const int32_t rc = xf_resolve(xf, XF_SITE_CHAIN, &spec);
+    if (rc) return rc;
+    g_chain_xf = spec;
     return TMAC_HIP_OK;
 }
 
@@ -63,7 +51,7 @@ extern "C" int32_t tmac_hip_chain_begin(void) {
     if (g_chain_rec) return fail(TMAC_HIP_E_ARG, "a chain is already being recorded on this thread");
     g_chain_rec = new std::vector<ChainRecOp>();
     g_chain_gat = new std::vector<ChainRecGather>();
-    memset(&g_chain_xf, 0, sizeof(g_chain_xf));
+    chain_clear_xform();
     return TMAC_HIP_OK;
 }
 
@@ -74,7 +62,7 @@ extern "C" int32_t tmac_hip_chain_abort(void) {
     delete g_chain_gat;
     g_chain_rec = nullptr;
     g_chain_gat = nullptr;
-    memset(&g_chain_xf, 0, sizeof(g_chain_xf));
+    chain_clear_xform();
     return TMAC_HIP_OK;
 }
 
@@ -308,7 +296,7 @@ static int32_t analyse_flow(const std::vector<ChainRecOp>& rec, const std::vecto
     }
     // the second vector of a GLU transform: the same rules as the activations (an earlier output, whole, or external memory)
     for (size_t i = 0; i < n; ++i) {
-        if (!has_glu(rec[i].xf)) continue;
+        if (!xf_has_glu(rec[i].xf)) continue;
         const Range r2{(const char*)rec[i].xf.in2, (const char*)rec[i].xf.in2 + (size_t)rec[i].w[0]->s.K * 2};
         const Src s = latest_output(rec, f, i, r2, rec[i].xf.in2, &partial);
         if (partial) return fail(TMAC_HIP_E_NOMATCH, "op %zu: the GLU's second vector overlaps output %zu of op %zu without being that output", i, (size_t)s.mat, (size_t)s.op);
@@ -334,6 +322,23 @@ static int32_t analyse_flow(const std::vector<ChainRecOp>& rec, const std::vecto
     return TMAC_HIP_OK;
 }
 
+// XfSpec -> ChainOp, the only two places that know the descriptor's spelling of a transform.  chain_epi: ChainOp::epi of the call that
+// publishes gate(gate) * up for the reader with this transform -- 1 / 2 / 3 = silu / relu^2 / tanh-GELU.  fill_chain_xf: the reader's own
+// fields as the kernel runs them (in_producer: the call in front publishes the product, so a GLU has nothing left to do and a GLU_NORM is
+// a NORM of its handed-over `in`; otherwise the reader evaluates gate(in) * in2 itself, its gate in bits 8..9 of xf_flags; bit 1: the
+// residual is the kept vector, bit 2: keep).  in2 is the layout's (an image or the caller's vector): describe_ops and commit.
+static char chain_epi(const XfSpec& s) { return (char)(1 + s.gate); }
+static void fill_chain_xf(ChainOp& o, const XfSpec& s, bool in_producer) {
+    const bool norm = s.kind == TMAC_XF_NORM, glu_norm = s.kind == TMAC_XF_GLU_NORM;
+    o.xf_kind = glu_norm ? TMAC_XF_NORM : (s.kind == TMAC_XF_GLU && in_producer) ? TMAC_XF_NONE : s.kind;
+    if (o.xf_kind == TMAC_XF_GLU) o.xf_flags |= s.gate << 8;
+    if (norm) {
+        o.xf_flags |= (s.carry ? 2 : 0) | (s.keep ? 4 : 0);
+        o.res = s.residual; o.res_out = s.residual_out;
+    }
+    if (norm || glu_norm) { o.gamma = s.gamma; memcpy(&o.eps_bits, &s.eps, 4); }
+}
+
 // GLU in the producer: when the two vectors of a GLU are outputs 0 and 1 of ONE earlier two-matrix call (gate and up) and nothing else
 // in the chain reads the gate's hand-off image, the gate/up call publishes gate(gate) * up itself (the GLU's gate travels in epi_of) -- once per row, by the wave that
 // publishes the rows anyway -- instead of all 256 workgroups of the reader evaluating K x (exp + rcp) each and polling two images
@@ -350,14 +355,14 @@ static void plan_glu_epilogue(const std::vector<ChainRecOp>& rec, ChainFlow& f, 
         if (f.src2[i].op >= 0) ++readers[f.src2[i].op][f.src2[i].mat];
     }
     for (size_t i = 0; i < n; ++i) {
-        if (!has_glu(rec[i].xf) || f.src[i].op < 0 || f.src2[i].op != f.src[i].op || f.src[i].mat != 0 || f.src2[i].mat != 1) continue;
+        if (!xf_has_glu(rec[i].xf) || f.src[i].op < 0 || f.src2[i].op != f.src[i].op || f.src[i].mat != 0 || f.src2[i].mat != 1) continue;
         const size_t j = (size_t)f.src[i].op;
         if (rec[j].w.size() != 2 || rec[j].w[0]->s.Mw != rec[j].w[1]->s.Mw || f.gathered[j][0] || f.gathered[j][1] || readers[j][0] != 1 || f.epi_of[j]) continue;
         const Shape& sj = rec[j].w[0]->s;
         const int nqj = 2 * sj.nquads(), nstj = (sj.K / 32 + 63) / 64;
         const int wq = kn.wpq ? kn.wpq : chain_pick_wpq(nqj, nstj, grid);
         if (CHAIN_NWV % wq || ((CHAIN_NWV / wq) & 1)) continue;          // pairs need an even number of quads per workgroup iteration
-        f.epi_of[j] = (char)(1 + rec[i].gate); f.glu_in_producer[i] = 1;        // ChainOp::epi: 1 / 2 / 3 = silu / relu^2 / tanh-GELU
+        f.epi_of[j] = chain_epi(rec[i].xf); f.glu_in_producer[i] = 1;
         if (readers[j][1] == 1) f.consumed[j][1] = 0;                    // nobody else reads the up projection through a hand-off
     }
 }
@@ -384,7 +389,7 @@ static int32_t describe_ops(const std::vector<ChainRecOp>& rec, const ChainFlow&
         const Shape& s0 = r.w[0]->s;
         const Src src = f.src[i], src2 = f.src2[i];
         if (r.act != TMAC_F16 && r.act != TMAC_F32) return fail(TMAC_HIP_E_NOMATCH, "op %zu: the decode chain takes fp16 or fp32 activations", i);
-        if (r.act == TMAC_F32 && (src.op >= 0 || has_glu(r.xf)))
+        if (r.act == TMAC_F32 && (src.op >= 0 || xf_has_glu(r.xf)))
             return fail(TMAC_HIP_E_NOMATCH, "op %zu: fp32 activations are covered for vectors in memory (an earlier output is handed over as fp16), without a GLU transform", i);
         if ((r.out == TMAC_F16) != (c.out_f16 != 0)) return fail(TMAC_HIP_E_NOMATCH, "op %zu: one output dtype per chain", i);
         if (s0.K > 8 * 3 * CHAIN_FT) return fail(TMAC_HIP_E_NOMATCH, "op %zu: K = %d beyond the decode chain's %d", i, s0.K, 8 * 3 * CHAIN_FT);
@@ -450,54 +455,40 @@ static int32_t describe_ops(const std::vector<ChainRecOp>& rec, const ChainFlow&
             if (r.act == TMAC_F32) { o.in_gran = 2; c.xforms = 1;      // (the kernel instance with the extensions)
                 if (chain_xf_region_floats(s0.K) > c.ext_floats) c.ext_floats = chain_xf_region_floats(s0.K); }
         }
-        // ---- vector transform (tmac_hip_chain_xform)
-        {
-            const tmac_hip_xform& xf = r.xf;
-            o.xf_kind = xf.kind;
+        // ---- vector transform (tmac_hip_chain_xform; the field rules were applied when it was declared: tmac_xform.h)
+        if (r.xf.kind != TMAC_XF_NONE) {
+            const XfSpec& xf = r.xf;
+            const int rf = chain_xf_region_floats(o.K);
+            const bool reads_glu = xf.kind == TMAC_XF_GLU && !f.glu_in_producer[i];          // the reader evaluates gate(in) * in2 itself
+            const bool runs = xf.kind != TMAC_XF_GLU || reads_glu;                           // (a GLU whose product the producer publishes leaves this op nothing to do)
+            // GLU_NORM is served in the producer form only: the gate/up call publishes g = gate(gate) * up (fp16, like every handed-over
+            // vector) and this call is a NORM of its handed-over `in` -- no residual, no carry -- which the kernel already runs
+            if (xf.kind == TMAC_XF_GLU_NORM && !f.glu_in_producer[i])
+                return fail(TMAC_HIP_E_NOMATCH, "op %zu: a GLU_NORM transform is recorded only where the call in front publishes silu(in) * in2 itself (in and in2 "
+                                                "outputs 0 and 1 of one earlier two-matrix call that nothing else reads through a hand-off, not gathered, "
+                                                "TMAC_CHAIN_GLU_EPILOGUE != 0, an even number of row quads per workgroup iteration): launch these calls one by one", i);
+            if (runs) {
+                c.xforms = 1;
+                if (o.K > 2 * 8 * CHAIN_FT)
+                    return fail(TMAC_HIP_E_NOMATCH, "op %zu: a %s transform is covered up to K = %d%s", i, xf.kind == TMAC_XF_NORM ? "NORM" : xf.kind == TMAC_XF_GLU ? "GLU" : "GLU_NORM",
+                                2 * 8 * CHAIN_FT, xf.kind == TMAC_XF_GLU_NORM ? " (the NORM's limit)" : "");
+            }
             if (xf.kind == TMAC_XF_NORM) {
-                c.xforms = 1;
-                if (o.K > 2 * 8 * CHAIN_FT) return fail(TMAC_HIP_E_NOMATCH, "op %zu: a NORM transform is covered up to K = %d", i, 2 * 8 * CHAIN_FT);
-                if (o.K > 8192 && (xf.keep || xf.residual == TMAC_XF_CARRY))
-                    return fail(TMAC_HIP_E_NOMATCH, "op %zu: a kept residual vector is covered up to K = 8192", i);
-                const int rf = chain_xf_region_floats(o.K);
-                if (xf.residual == TMAC_XF_CARRY) {
-                    if (c.carry_K != o.K) return fail(TMAC_HIP_E_ARG, "op %zu: no earlier NORM of the chain keeps a vector of %d values", i, o.K);
-                    o.xf_flags |= 2;
-                } else o.res = xf.residual;
-                if (xf.keep) { o.xf_flags |= 4; c.carry_K = o.K; if (rf > c.carry_floats) c.carry_floats = rf; }
-                else if (rf > c.tmp_floats) c.tmp_floats = rf;
-                if (xf.gamma && rf > c.gam_floats) c.gam_floats = rf;
-                o.gamma = xf.gamma; o.res_out = xf.residual_out;
-                memcpy(&o.eps_bits, &xf.eps, 4);
-            } else if (xf.kind == TMAC_XF_GLU_NORM) {
-                // Served in the producer form only: the gate/up call publishes g = gate(gate) * up (fp16, like every handed-over vector)
-                // and this call is a NORM of its handed-over `in` -- no residual, no carry -- which the kernel already runs.
-                if (!f.glu_in_producer[i])
-                    return fail(TMAC_HIP_E_NOMATCH, "op %zu: a GLU_NORM transform is recorded only where the call in front publishes silu(in) * in2 itself (in and in2 "
-                                                    "outputs 0 and 1 of one earlier two-matrix call that nothing else reads through a hand-off, not gathered, "
-                                                    "TMAC_CHAIN_GLU_EPILOGUE != 0, an even number of row quads per workgroup iteration): launch these calls one by one", i);
-                c.xforms = 1;
-                if (o.K > 2 * 8 * CHAIN_FT) return fail(TMAC_HIP_E_NOMATCH, "op %zu: a GLU_NORM transform is covered up to K = %d (the NORM's limit)", i, 2 * 8 * CHAIN_FT);
-                const int rf = chain_xf_region_floats(o.K);
-                o.xf_kind = TMAC_XF_NORM;
-                if (rf > c.tmp_floats) c.tmp_floats = rf;
-                if (rf > c.gam_floats) c.gam_floats = rf;
-                o.gamma = xf.gamma;
-                memcpy(&o.eps_bits, &xf.eps, 4);
-            } else if (xf.kind == TMAC_XF_GLU && f.glu_in_producer[i]) {
-                o.xf_kind = TMAC_XF_NONE;                  // `in` already holds gate(gate) * up (the producer's epilogue)
-            } else if (xf.kind == TMAC_XF_GLU) {
-                c.xforms = 1;
-                o.xf_flags |= r.gate << 8;                 // the reader evaluates gate(in) * in2 itself
-                if (r.gate) c.gates = 1;
-                if (o.K > 2 * 8 * CHAIN_FT) return fail(TMAC_HIP_E_NOMATCH, "op %zu: a GLU transform is covered up to K = %d", i, 2 * 8 * CHAIN_FT);
-                if (chain_xf_region_floats(o.K) > c.tmp_floats) c.tmp_floats = chain_xf_region_floats(o.K);
+                if (o.K > 8192 && (xf.keep || xf.carry)) return fail(TMAC_HIP_E_NOMATCH, "op %zu: a kept residual vector is covered up to K = 8192", i);
+                if (xf.carry && c.carry_K != o.K) return fail(TMAC_HIP_E_ARG, "op %zu: no earlier NORM of the chain keeps a vector of %d values", i, o.K);
+                if (xf.keep) { c.carry_K = o.K; if (rf > c.carry_floats) c.carry_floats = rf; }
+            }
+            if (runs && !xf.keep && rf > c.tmp_floats) c.tmp_floats = rf;
+            if (xf.gamma && rf > c.gam_floats) c.gam_floats = rf;
+            if (reads_glu) {
+                if (xf.gate) c.gates = 1;
                 if (src2.op >= 0) {
                     const ChainMat& p2 = c.ops[src2.op].m[src2.mat];
                     if (p2.Mw != o.K) return fail(TMAC_HIP_E_ARG, "op %zu: the GLU's second vector has %d rows, K = %d", i, p2.Mw, o.K);
                     lay.in2[i] = lay.gr[src2.op][src2.mat];
                 } else o.in2 = xf.in2;
             }
+            fill_chain_xf(o, xf, f.glu_in_producer[i] != 0);
         }
         // weight fragments per wave in front of the polls: ONE.  The poll then returns after a fabric round trip plus 24 KB per
         // CU, and the wait behind it does not hold the LUT build until all of the op's weights have landed.  Putting the whole
@@ -538,16 +529,12 @@ static int32_t check_hazards(const std::vector<ChainRecOp>& rec, const ChainFlow
     std::vector<std::vector<Range>> xf_rd(n);
     std::vector<Range> xf_wr(n, Range{nullptr, nullptr});
     for (size_t i = 0; i < n; ++i) {
-        const tmac_hip_xform& xf = rec[i].xf;
+        const XfSpec& xf = rec[i].xf;          // (fields the kind does not read are null)
         const size_t K = (size_t)rec[i].w[0]->s.K;
-        if (xf.kind == TMAC_XF_NORM) {
-            if (xf.residual && xf.residual != TMAC_XF_CARRY) xf_rd[i].push_back(Range{(const char*)xf.residual, (const char*)xf.residual + K * 4});
-            if (xf.gamma) xf_rd[i].push_back(Range{(const char*)xf.gamma, (const char*)xf.gamma + K * 4});
-            if (xf.residual_out) xf_wr[i] = Range{(const char*)xf.residual_out, (const char*)xf.residual_out + K * 4};
-        } else if (has_glu(xf)) {
-            if (f.src2[i].op < 0) xf_rd[i].push_back(Range{(const char*)xf.in2, (const char*)xf.in2 + K * 2});
-            if (xf.kind == TMAC_XF_GLU_NORM) xf_rd[i].push_back(Range{(const char*)xf.gamma, (const char*)xf.gamma + K * 4});
-        }
+        if (xf.residual) xf_rd[i].push_back(Range{(const char*)xf.residual, (const char*)xf.residual + K * 4});
+        if (xf.in2 && f.src2[i].op < 0) xf_rd[i].push_back(Range{(const char*)xf.in2, (const char*)xf.in2 + K * 2});
+        if (xf.gamma) xf_rd[i].push_back(Range{(const char*)xf.gamma, (const char*)xf.gamma + K * 4});
+        if (xf.residual_out) xf_wr[i] = Range{(const char*)xf.residual_out, (const char*)xf.residual_out + K * 4};
     }
     for (size_t k = 0; k < n; ++k) {
         for (size_t i = 0; i < n; ++i)

@@ -51,8 +51,7 @@ struct ChainRecOp {
     const void* B;
     std::vector<void*> C;
     tmac_dtype_t act, out;
-    tmac_hip_xform xf;               // vector transform of the activations (kind 0: none); kind holds the low byte alone ...
-    int gate = 0;                    // ... and this the gate of a GLU / GLU_NORM: 0 silu, 1 relu^2, 2 tanh-GELU
+    XfSpec xf;                       // vector transform of the activations, resolved (tmac_xform.h; kind 0: none)
 };
 // an exchange step noted while recording: recv = all-gather over the ranks of send (rank r's bytes at r * bytes)
 struct ChainRecGather {

@@ -151,7 +151,6 @@ bool tmac_host::defer_if_on(const tmac_hip_weights* const* wl, int nmat, const v
     ChainRecOp op;
     for (int i = 0; i < nmat; ++i) { op.w.push_back(wl[i]); op.C.push_back(C_list[i]); }
     op.B = B_dev; op.act = act_dtype; op.out = out_dtype;
-    memset(&op.xf, 0, sizeof(op.xf));
     // a dependence on the queue (RAW: reads a queued output; WAR / WAW: writes what a queued call reads or writes), another stream, or a
     // full queue: the queue goes first
     bool must_flush = !D.pending.empty() && (st != D.stream || D.pending.size() >= DEFER_MAX_BATCH);

@@ -507,9 +507,16 @@ static Plan xf_rows_plan(Plan p) {
         return refused(TMAC_HIP_E_NOMATCH, "a transformed call of several rows needs the LUT image or the half-table image alone; this plan builds every layout");
     return p;
 }
-// xf: the call carries a vector transform (N >= 2, plan from xf_rows_plan): the row pass, then the planned LUT build's XF instantiation
+// XfSpec -> the argument block of the row pass and of the XF LUT builders (the only place that knows XfRowsGateArgs' spelling of a
+// transform: kind and gate side by side); r: the rows' 1 / rms, which k_xf_rows writes and the builders read
+static void fill_xf_rows_args(XfRowsGateArgs& xa, const XfSpec& s, float* r) {
+    memset(&xa, 0, sizeof(xa));
+    xa.kind = s.kind; xa.gate = s.gate; xa.eps = s.eps;
+    xa.in2 = s.in2; xa.residual = s.residual; xa.gamma = s.gamma; xa.residual_out = s.residual_out; xa.r = r;
+}
+// spec: the call carries a vector transform (N >= 2, plan from xf_rows_plan): the row pass, then the planned LUT build's XF instantiation
 static int32_t fused_prefill(Plan p, const tmac_hip_weights* const* wl, int nmat, const void* B_dev, tmac_dtype_t act_dtype,
-                             void* const* C_list, tmac_dtype_t out_dtype, int N, hipStream_t st, XfRowsGateArgs* xf = nullptr) {
+                             void* const* C_list, tmac_dtype_t out_dtype, int N, hipStream_t st, const XfSpec* spec = nullptr) {
     const Shape& s0 = wl[0]->s;
     tmac_hip_workspace* ws = nullptr;
     {
@@ -534,7 +541,7 @@ static int32_t fused_prefill(Plan p, const tmac_hip_weights* const* wl, int nmat
     }
     if (p.route == R_GEMM_PLANES && !planes_image_fits(ws, s0.K)) {   // (see image_fits at the planners)
         p = plan_fused(wl, C_list, nmat, N, false, false);
-        if (xf) {
+        if (spec) {
             p = xf_rows_plan(p);
             if (p.err) return fail(p.err, p.msg, p.mat);
         }
@@ -543,10 +550,12 @@ static int32_t fused_prefill(Plan p, const tmac_hip_weights* const* wl, int nmat
     if (rc) return rc;
     const int f16 = act_dtype == TMAC_F16;
     hipError_t e = hipSuccess;
-    if (xf) {
-        xf->r = ws->xf_r;
-        if (xf->kind == TMAC_XF_GLU_NORM || (xf->kind == TMAC_XF_NORM && (xf->gamma || xf->residual_out))) {      // (GLU_NORM: always, gamma is required)
-            e = launch_xf_rows(*xf, B_dev, f16, xf->gamma ? ws->xf_r : nullptr, s0.K, N, st);
+    XfRowsGateArgs xa;
+    XfRowsGateArgs* const xf = spec ? &xa : nullptr;
+    if (spec) {
+        fill_xf_rows_args(xa, *spec, ws->xf_r);
+        if (xf_needs_row_pass(*spec)) {
+            e = launch_xf_rows(xa, B_dev, f16, xa.gamma ? ws->xf_r : nullptr, s0.K, N, st);
             if (e != hipSuccess) return fail(TMAC_HIP_E_RUNTIME, "transform row pass launch: %s", hipGetErrorString(e));
         }
     }
@@ -574,6 +583,17 @@ static int32_t fused_prefill(Plan p, const tmac_hip_weights* const* wl, int nmat
     for (int i = 0; i < nmat && rc == TMAC_HIP_OK; ++i) rc = tmac_hip_qgemm_dev(wl[i], ws, C_list[i], out_dtype, N, st);
     return rc;
 }
+// the alignment contract of the activations and the outputs (include/tmac_hip.h, "Alignment")
+static int32_t act_align_check(const void* B_dev) {
+    if (misaligned(B_dev, ACT_ALIGN)) return fail(TMAC_HIP_E_ARG, "B_dev must be %zu-byte aligned (the LUT build reads 16 bytes at a time)", ACT_ALIGN);
+    return TMAC_HIP_OK;
+}
+static int32_t out_align_check(void* const* C_list, int nmat, tmac_dtype_t out_dtype) {
+    for (int i = 0; i < nmat; ++i)
+        if (misaligned(C_list[i], out_align(out_dtype)))
+            return fail(TMAC_HIP_E_ARG, "C_dev[%d] must be %zu-byte aligned (four outputs are stored at a time)", i, out_align(out_dtype));
+    return TMAC_HIP_OK;
+}
 int32_t tmac_host::fused_impl(const tmac_hip_weights* const* wl, int nmat, const void* B_dev, tmac_dtype_t act_dtype,
                           void* const* C_list, tmac_dtype_t out_dtype, int N, int32_t* dump, float* lut_tap, hipStream_t st) {
     bind_thread_device();
@@ -583,12 +603,11 @@ int32_t tmac_host::fused_impl(const tmac_hip_weights* const* wl, int nmat, const
     }
     // the alignment contract, ahead of the recorder, the deferred queue and the planner alike: a refused call is neither recorded nor
     // queued, launches nothing and leaves the queue as it is
-    int bad_c = -1;
-    for (int i = 0; i < nmat && bad_c < 0; ++i) if (misaligned(C_list[i], out_align(out_dtype))) bad_c = i;
-    if (misaligned(B_dev, ACT_ALIGN) || bad_c >= 0) {
+    int32_t arc = out_align_check(C_list, nmat, out_dtype);
+    if (arc == TMAC_HIP_OK) arc = act_align_check(B_dev);
+    if (arc) {
         if (chain_recording()) chain_clear_xform();
-        if (bad_c < 0) return fail(TMAC_HIP_E_ARG, "B_dev must be %zu-byte aligned (the LUT build reads 16 bytes at a time)", ACT_ALIGN);
-        return fail(TMAC_HIP_E_ARG, "C_dev[%d] must be %zu-byte aligned (four outputs are stored at a time)", bad_c, out_align(out_dtype));
+        return arc;
     }
     const bool tap = dump || lut_tap;
     if (chain_recording() && !tap) return chain_record(wl, nmat, B_dev, act_dtype, C_list, out_dtype, N);
@@ -623,28 +642,17 @@ extern "C" int32_t tmac_hip_qgemm_fused_dev(const tmac_hip_weights* const* weigh
 // ---- fused entry point with a vector transform (N = 1) -----------------------------------------------------------------------
 // Outside a recording: k_gemv_quad's XF instantiations.  Everything is checked before anything is launched; a transformed call is never
 // queued (it goes behind the deferred queue like every non-hot entry point).
-// kind known to the transformed calls: NONE, NORM, GLU, GLU_NORM (3 is not a kind), the last two with a gate in bits 8..15
-int32_t tmac_host::xf_kind_check(int32_t kind, int* base, int* gate) {
-    const int k = kind & 0xff, g = kind & ~0xff;
-    if (k != TMAC_XF_NONE && k != TMAC_XF_NORM && k != TMAC_XF_GLU && k != TMAC_XF_GLU_NORM) return fail(TMAC_HIP_E_ARG, "unknown transform kind %d", kind);
-    if (g != 0 && (k == TMAC_XF_NONE || k == TMAC_XF_NORM))
-        return fail(TMAC_HIP_E_ARG, "transform kind %d takes no gate: bits 8..15 of kind (0x%x here) select the gate of a GLU or GLU_NORM", k, (unsigned)g);
-    if (g != TMAC_XF_GATE_SILU && g != TMAC_XF_GATE_RELU2 && g != TMAC_XF_GATE_GELU)
-        return fail(TMAC_HIP_E_ARG, "unknown gate 0x%x in transform kind 0x%x (TMAC_XF_GATE_SILU, _RELU2 or _GELU in bits 8..15, nothing above)", (unsigned)g, (unsigned)kind);
-    *base = k; *gate = g >> 8;
-    return TMAC_HIP_OK;
+// The field rules are tmac_xform.h's (xf_resolve, xf_overlap_check); all of them come before anything about matrices, plans or routes.
+// residual_out against what an N-row call on these matrices reads and writes
+static int32_t xf_call_overlap_check(const XfSpec& spec, XfSite site, const tmac_hip_weights* const* wl, int nmat, const void* B_dev, tmac_dtype_t act_dtype,
+                                     const tmac_hip_xform* xf, void* const* C_list, tmac_dtype_t out_dtype, int N) {
+    XfOut outs[4];
+    for (int i = 0; i < nmat; ++i) outs[i] = XfOut{C_list[i], (size_t)N * wl[i]->s.Mw * (out_dtype == TMAC_F16 ? 2 : 4)};
+    return xf_overlap_check(spec, site, B_dev, act_dtype == TMAC_F16 ? 2 : 4, xf->in2, wl[0]->s.K, N, outs, nmat);
 }
-int32_t tmac_host::glu_norm_check(const tmac_hip_xform* xf) {
-    if (!xf->in2) return fail(TMAC_HIP_E_ARG, "GLU_NORM needs a second vector (in2)");
-    if (!xf->gamma) return fail(TMAC_HIP_E_ARG, "GLU_NORM needs the norm weights (gamma)");
-    if (xf->residual) return fail(TMAC_HIP_E_ARG, "GLU_NORM takes no residual: the field must be NULL");
-    if (xf->residual_out) return fail(TMAC_HIP_E_ARG, "GLU_NORM writes no residual_out: the field must be NULL");
-    if (xf->keep) return fail(TMAC_HIP_E_ARG, "GLU_NORM keeps no vector: keep must be 0");
-    return TMAC_HIP_OK;
-}
-static bool ranges_overlap(const void* a, size_t an, const void* b, size_t bn) {
-    const char* pa = (const char*)a; const char* pb = (const char*)b;
-    return a && b && pa < pb + bn && pb < pa + an;
+// XfSpec -> the transform fields of k_gemv_quad's XF block (the only place that knows FusedXfArgs' spelling: the gate in bits 8.. of xf_kind)
+static void fill_fused_xf_args(FusedXfArgs& fa, const XfSpec& s) {
+    fa.xf_kind = s.kind | (s.gate << 8); fa.in2 = s.in2; fa.residual = s.residual; fa.gamma = s.gamma; fa.residual_out = s.residual_out; fa.eps = s.eps;
 }
 extern "C" int32_t tmac_hip_qgemm_fused_xf_dev(const tmac_hip_weights* const* wl, int nmat, const void* B_dev, tmac_dtype_t act_dtype,
                                                const tmac_hip_xform* xf, void* const* C_list, tmac_dtype_t out_dtype, void* stream) {
@@ -658,46 +666,18 @@ extern "C" int32_t tmac_hip_qgemm_fused_xf_dev(const tmac_hip_weights* const* wl
         if (rc != TMAC_HIP_OK && chain_recording()) chain_clear_xform();      // a rejected call leaves no pending transform
         return rc;
     }
-    int kind = 0, gate = 0;
-    const int32_t krc = xf_kind_check(xf->kind, &kind, &gate);
-    if (krc) return krc;
+    XfSpec spec;
+    int32_t rc = xf_resolve(xf, XF_SITE_N1, &spec);
+    if (rc) return rc;
     if (!wl || !C_list || !B_dev || nmat < 1 || nmat > 4) return fail(TMAC_HIP_E_ARG, "bad fused arguments (1..4 matrices)");
-    const bool norm = kind == TMAC_XF_NORM, glu_norm = kind == TMAC_XF_GLU_NORM;
-    if (glu_norm) {
-        const int32_t grc = glu_norm_check(xf);
-        if (grc) return grc;
-    }
-    if (!norm && !xf->in2) return fail(TMAC_HIP_E_ARG, "GLU needs a second vector");
-    if (norm && xf->residual == TMAC_XF_CARRY)
-        return fail(TMAC_HIP_E_ARG, "TMAC_XF_CARRY names a vector kept inside a chain launch: outside a recording the residual is a vector in memory");
-    // the vectors the call touches (a NORM ignores in2, a GLU the NORM's fields; a GLU_NORM reads in2 and gamma)
-    const void* in2 = norm ? nullptr : xf->in2;
-    const float* residual = norm ? xf->residual : nullptr;
-    const float* gamma = norm || glu_norm ? xf->gamma : nullptr;
-    float* rout = norm ? xf->residual_out : nullptr;
-    if (misaligned(B_dev, ACT_ALIGN)) return fail(TMAC_HIP_E_ARG, "B_dev must be %zu-byte aligned (the LUT build reads 16 bytes at a time)", ACT_ALIGN);
-    for (int i = 0; i < nmat; ++i)
-        if (misaligned(C_list[i], out_align(out_dtype)))
-            return fail(TMAC_HIP_E_ARG, "C_dev[%d] must be %zu-byte aligned (four outputs are stored at a time)", i, out_align(out_dtype));
-    const struct { const void* p; const char* name; } vec[] = {{in2, "in2"}, {residual, "residual"}, {gamma, "gamma"}, {rout, "residual_out"}};
-    for (const auto& v : vec)
-        if (misaligned(v.p, XFORM_ALIGN)) return fail(TMAC_HIP_E_ARG, "transform vector %s must be %zu-byte aligned (read or written 16 bytes at a time)", v.name, XFORM_ALIGN);
+    if ((rc = act_align_check(B_dev)) != TMAC_HIP_OK || (rc = out_align_check(C_list, nmat, out_dtype)) != TMAC_HIP_OK) return rc;
     const Plan p = plan_fused(wl, C_list, nmat, 1, false);
     if (p.err) return fail(p.err, p.msg, p.mat);
     const Shape& s0 = wl[0]->s;
     if (p.route != R_GEMV_QUAD || g_knobs.variant == V_QUAD_MQSAD || s0.K > QUAD_XF_MAX_K)
         return fail(TMAC_HIP_E_NOMATCH, "a transformed call runs on k_gemv_quad with the MFMA accumulate only (QUAD layout, K <= %d)", QUAD_XF_MAX_K);
-    if (rout) {
-        // every workgroup reads the whole of the inputs while ONE workgroup writes each pair of residual_out: no order between the two
-        const size_t K = (size_t)s0.K, act_bytes = K * (act_dtype == TMAC_F16 ? 2 : 4);
-        const struct { const void* p; size_t n; const char* name; } rd[] = {{B_dev, act_bytes, "B_dev"}, {residual, K * 4, "residual"}, {gamma, K * 4, "gamma"}};
-        for (const auto& r : rd)
-            if (ranges_overlap(rout, K * 4, r.p, r.n))
-                return fail(TMAC_HIP_E_ARG, "residual_out overlaps %s, which every workgroup reads while one writes (alternate between two buffers)", r.name);
-        for (int i = 0; i < nmat; ++i)
-            if (ranges_overlap(rout, K * 4, C_list[i], (size_t)wl[i]->s.Mw * (out_dtype == TMAC_F16 ? 2 : 4)))
-                return fail(TMAC_HIP_E_ARG, "residual_out overlaps C_dev[%d]", i);
-    }
+    // (every workgroup reads the whole of the inputs while ONE workgroup writes each pair of residual_out: no order between the two)
+    if ((rc = xf_call_overlap_check(spec, XF_SITE_N1, wl, nmat, B_dev, act_dtype, xf, C_list, out_dtype, 1)) != TMAC_HIP_OK) return rc;
     bind_thread_device();
     const int32_t brc = defer_barrier();       // never queued: behind the calling thread's queue (B_dev may be a queued output)
     if (brc) return brc;
@@ -705,7 +685,7 @@ extern "C" int32_t tmac_hip_qgemm_fused_xf_dev(const tmac_hip_weights* const* wl
     FusedXfArgs fa;
     const int nb = fill_fused_args(fa, wl, C_list, nmat, out_dtype, nullptr);
     fa.B = B_dev; fa.act_f16 = act_dtype == TMAC_F16;
-    fa.xf_kind = kind | (gate << 8); fa.in2 = in2; fa.residual = residual; fa.gamma = gamma; fa.residual_out = rout; fa.eps = xf->eps;
+    fill_fused_xf_args(fa, spec);
     // the launch configuration: forced (tmac_hip_debug_quad_config) -- it must have an XF instantiation -- else tuned, else the heuristic
     int ft = g_knobs.force_ft, wpq = g_knobs.force_wpq;
     const bool strict = ft || wpq;
@@ -720,40 +700,6 @@ extern "C" int32_t tmac_hip_qgemm_fused_xf_dev(const tmac_hip_weights* const* wl
 // N = 1 and "no transform" are the existing calls themselves.  N >= 2: every refusal comes before the first launch; then the row pass
 // (k_xf_rows), the planned LUT build with the transform in its activation load, the planned kernel (fused_prefill).  Never recorded, never
 // queued.
-static int32_t xf_rows_check(const void* B_dev, tmac_dtype_t act_dtype, const tmac_hip_xform* xf, int K, int N, XfRowsGateArgs& xa) {
-    int kind = 0, gate = 0;
-    const int32_t krc = xf_kind_check(xf->kind, &kind, &gate);
-    if (krc) return krc;
-    const bool norm = kind == TMAC_XF_NORM, glu_norm = kind == TMAC_XF_GLU_NORM;
-    if (glu_norm) {
-        const int32_t grc = glu_norm_check(xf);
-        if (grc) return grc;
-    }
-    if (!norm && !xf->in2) return fail(TMAC_HIP_E_ARG, "GLU needs a second vector");
-    if (norm && xf->residual == TMAC_XF_CARRY)
-        return fail(TMAC_HIP_E_ARG, "TMAC_XF_CARRY names a vector kept inside a chain launch: outside a recording the residual is a vector in memory");
-    memset(&xa, 0, sizeof(xa));
-    xa.kind = kind; xa.gate = gate; xa.eps = xf->eps;
-    xa.in2 = norm ? nullptr : xf->in2;
-    xa.residual = norm ? xf->residual : nullptr;
-    xa.gamma = norm || glu_norm ? xf->gamma : nullptr;
-    xa.residual_out = norm ? xf->residual_out : nullptr;
-    if (misaligned(B_dev, ACT_ALIGN)) return fail(TMAC_HIP_E_ARG, "B_dev must be %zu-byte aligned (the LUT build reads 16 bytes at a time)", ACT_ALIGN);
-    const struct { const void* p; const char* name; } vec[] = {{xa.in2, "in2"}, {xa.residual, "residual"}, {xa.gamma, "gamma"}, {xa.residual_out, "residual_out"}};
-    for (const auto& v : vec)
-        if (misaligned(v.p, XFORM_ALIGN)) return fail(TMAC_HIP_E_ARG, "transform vector %s must be %zu-byte aligned (read or written 16 bytes at a time)", v.name, XFORM_ALIGN);
-    if (xa.residual_out) {
-        // the builders read in and residual again after the row pass has written residual_out
-        const size_t NK = (size_t)N * K, act_bytes = NK * (act_dtype == TMAC_F16 ? 2 : 4);
-        const struct { const void* p; size_t n; const char* name; } rd[] = {{B_dev, act_bytes, "B_dev"}, {xa.residual, NK * 4, "residual"}, {xa.gamma, (size_t)K * 4, "gamma"},
-                                                                           {xf->in2, act_bytes, "in2"}};
-        for (const auto& r : rd)
-            if (ranges_overlap(xa.residual_out, NK * 4, r.p, r.n))
-                return fail(TMAC_HIP_E_ARG, "residual_out overlaps %s, which the LUT build reads after the row pass has written it (alternate between two buffers)", r.name);
-    }
-    return TMAC_HIP_OK;
-}
-
 extern "C" int32_t tmac_hip_qgemm_fused_xf_rows_dev(const tmac_hip_weights* const* wl, int nmat, const void* B_dev, tmac_dtype_t act_dtype,
                                                     const tmac_hip_xform* xf, void* const* C_list, tmac_dtype_t out_dtype, int N, void* stream) {
     hipStream_t st = (hipStream_t)stream;
@@ -766,21 +712,18 @@ extern "C" int32_t tmac_hip_qgemm_fused_xf_rows_dev(const tmac_hip_weights* cons
         return fail(TMAC_HIP_E_NOMATCH, "a transformed call of N=%d rows cannot be recorded: a chain takes one activation row", N);
     }
     if (!wl || !C_list || !B_dev || nmat < 1 || nmat > 4 || N < 1) return fail(TMAC_HIP_E_ARG, "bad fused arguments (1..4 matrices)");
-    for (int i = 0; i < nmat; ++i) {
+    for (int i = 0; i < nmat; ++i)
         if (!wl[i] || !C_list[i]) return fail(TMAC_HIP_E_ARG, "null matrix or output");
-        if (misaligned(C_list[i], out_align(out_dtype)))
-            return fail(TMAC_HIP_E_ARG, "C_dev[%d] must be %zu-byte aligned (four outputs are stored at a time)", i, out_align(out_dtype));
-    }
-    const Shape& s0 = wl[0]->s;
-    XfRowsGateArgs xa;
-    int32_t rc = xf_rows_check(B_dev, act_dtype, xf, s0.K, N, xa);
+    int32_t rc = out_align_check(C_list, nmat, out_dtype);
     if (rc) return rc;
-    for (int i = 0; i < nmat; ++i) {
+    const Shape& s0 = wl[0]->s;
+    XfSpec spec;
+    if ((rc = xf_resolve(xf, XF_SITE_ROWS, &spec)) != TMAC_HIP_OK || (rc = act_align_check(B_dev)) != TMAC_HIP_OK) return rc;
+    // (the builders read in, in2 and residual again after the row pass has written residual_out)
+    if ((rc = xf_call_overlap_check(spec, XF_SITE_ROWS, wl, nmat, B_dev, act_dtype, xf, C_list, out_dtype, N)) != TMAC_HIP_OK) return rc;
+    for (int i = 0; i < nmat; ++i)
         if (!same_lut(wl[i], wl[0]) || !same_quant(wl[i], wl[0]))
             return fail(TMAC_HIP_E_ARG, "matrices fused in one launch must share K, bits and quantisation config");
-        if (xa.residual_out && ranges_overlap(xa.residual_out, (size_t)N * s0.K * 4, C_list[i], (size_t)N * wl[i]->s.Mw * (out_dtype == TMAC_F16 ? 2 : 4)))
-            return fail(TMAC_HIP_E_ARG, "residual_out overlaps C_dev[%d]", i);
-    }
     // the scope: what the N = 1 form accepts, within the pair builds' reach
     if (g_knobs.variant == V_REF_LAYOUT) return fail(TMAC_HIP_E_NOMATCH, "a transformed call does not run on the reference layout");
     for (int i = 0; i < nmat; ++i) {
@@ -796,7 +739,7 @@ extern "C" int32_t tmac_hip_qgemm_fused_xf_rows_dev(const tmac_hip_weights* cons
     bind_thread_device();
     const int32_t brc = defer_barrier();       // never queued: behind the calling thread's queue (B_dev may be a queued output)
     if (brc) return brc;
-    return fused_prefill(p, wl, nmat, B_dev, act_dtype, C_list, out_dtype, N, st, &xa);
+    return fused_prefill(p, wl, nmat, B_dev, act_dtype, C_list, out_dtype, N, st, &spec);
 }
 
 // What a transformed call of N >= 2 rows on these matrices would run, by the rules of the call itself (host only: plans, launches nothing).
@@ -840,16 +783,19 @@ extern "C" int32_t tmac_hip_debug_xf_rows(const void* B_dev, tmac_dtype_t act_dt
     if (brc) return brc;
     if (!B_dev || !xf || !x_out_dev || K <= 0 || K % 64 || N < 1) return fail(TMAC_HIP_E_ARG, "bad tap arguments (K a multiple of 64, N >= 1)");
     if (xf->kind == TMAC_XF_NONE) return fail(TMAC_HIP_E_ARG, "the tap shows a transform: kind NORM, GLU or GLU_NORM");
-    XfRowsGateArgs xa;
-    const int32_t rc = xf_rows_check(B_dev, act_dtype, xf, K, N, xa);
-    if (rc) return rc;
+    XfSpec spec;
+    int32_t rc = xf_resolve(xf, XF_SITE_ROWS, &spec);
+    if (rc || (rc = act_align_check(B_dev)) != TMAC_HIP_OK) return rc;
     if (misaligned(x_out_dev, XFORM_ALIGN)) return fail(TMAC_HIP_E_ARG, "x_out_dev must be %zu-byte aligned", XFORM_ALIGN);
-    if (xa.residual_out && ranges_overlap(xa.residual_out, (size_t)N * K * 4, x_out_dev, (size_t)N * K * 4)) return fail(TMAC_HIP_E_ARG, "residual_out overlaps x_out_dev");
     const int f16 = act_dtype == TMAC_F16;
+    const XfOut x_out{x_out_dev, (size_t)N * K * 4};
+    if ((rc = xf_overlap_check(spec, XF_SITE_ROWS, B_dev, f16 ? 2 : 4, xf->in2, K, N, &x_out, 1, "x_out_dev")) != TMAC_HIP_OK) return rc;
     DevBuf r;
-    if (xa.gamma) { HIP_TRY(r.alloc(sizeof(float) * (size_t)N)); xa.r = r.as<float>(); }
+    if (spec.gamma) HIP_TRY(r.alloc(sizeof(float) * (size_t)N));
+    XfRowsGateArgs xa;
+    fill_xf_rows_args(xa, spec, r.as<float>());
     hipError_t e = hipSuccess;
-    if (xa.kind == TMAC_XF_GLU_NORM || (xa.kind == TMAC_XF_NORM && (xa.gamma || xa.residual_out))) e = launch_xf_rows(xa, B_dev, f16, r.as<float>(), K, N, st);
+    if (xf_needs_row_pass(spec)) e = launch_xf_rows(xa, B_dev, f16, r.as<float>(), K, N, st);
     if (e == hipSuccess) e = launch_xf_rows_tap(xa, B_dev, f16, x_out_dev, K, N, st);
     const hipError_t es = hipStreamSynchronize(st);      // r is freed on return
     if (e != hipSuccess || es != hipSuccess) return fail(TMAC_HIP_E_RUNTIME, "transform tap: %s", hipGetErrorString(e != hipSuccess ? e : es));

@@ -5,6 +5,7 @@
 //   tmac_kcfg.cpp        the kcfg.ini table and its lookups
 //   tmac_weights.cpp     weight registration (reference layout -> device layout)
 //   tmac_workspace.cpp   LUT workspace + the preprocessor entry point
+//   tmac_xform.cpp       the field rules of tmac_hip_xform: one resolver for every transform site (tmac_xform.h: no HIP, builds with plain g++)
 //   tmac_dispatch.cpp    qgemm_lut dispatch (a call is planned -- enum Route -- then launched), the fused entry point, parity taps
 //   tmac_tuner.cpp       launch-configuration tuner of the decode kernel
 //   tmac_chain_host.cpp  recording and building the persistent decode chain (chain_build and its stages, the stream schedule)
@@ -34,6 +35,7 @@
 #include "../../include/tmac_hip.h"
 #include "tmac_chain.h"
 #include "tmac_kernels.h"
+#include "tmac_xform.h"
 
 // ---- the C-ABI's opaque objects ---------------------------------------------------------------
 struct tmac_hip_weights {
@@ -74,7 +76,7 @@ namespace tmac_host {
 using namespace tmac;
 
 // ---- errors -----------------------------------------------------------------------------------
-int32_t fail(int32_t code, const char* fmt, ...) __attribute__((format(printf, 2, 3)));   // sets the thread's message, returns code
+// fail(code, fmt, ...) sets the thread's message and returns code: declared in tmac_xform.h, defined in tmac_runtime.cpp
 
 // device scratch of the test taps and self-tests: freed on every return path
 struct DevBuf {
@@ -165,12 +167,9 @@ int32_t fused_impl(const tmac_hip_weights* const* wl, int nmat, const void* B_de
 // Pure: reads its arguments and g_knobs.
 int32_t fused_check(const tmac_hip_weights* const* wl, int nmat, void* const* C_list, int N);
 void release_fused_workspaces();   // caller holds g_mu
-// Alignment of caller-owned device pointers (include/tmac_hip.h, "Alignment"): every LUT build reads the activations 16 bytes at a time
-// (uint4 / float4), the GEMMs store four outputs at a time (fp32: 16 bytes, fp16: 8), the chain reads its transform vectors and writes
-// residual_out 16 bytes at a time.  A pointer below that is refused before anything is planned, queued or recorded.
-constexpr size_t ACT_ALIGN = 16, XFORM_ALIGN = 16;
+// Alignment of caller-owned device pointers: ACT_ALIGN, XFORM_ALIGN and misaligned are tmac_xform.h's; the GEMMs store four outputs at a
+// time (fp32: 16 bytes, fp16: 8).
 inline size_t out_align(tmac_dtype_t d) { return d == TMAC_F16 ? 8 : 16; }
-inline bool misaligned(const void* p, size_t a) { return (reinterpret_cast<uintptr_t>(p) & (a - 1)) != 0; }
 
 // ---- tuner (tmac_tuner.cpp) -----------------------------------------------------------------------
 void tuned_config(const FusedArgs& fa, int total_q, int& ft, int& wpq);   // leaves ft / wpq alone when nothing is recorded
@@ -178,14 +177,6 @@ void tuned_config(const FusedArgs& fa, int total_q, int& ft, int& wpq);   // lea
 // ---- decode chain (tmac_chain_host.cpp) and deferred queue (tmac_defer.cpp) -----------------------------------------------------------
 bool chain_recording();            // is the calling thread between tmac_hip_chain_begin and tmac_hip_chain_end?
 void chain_clear_xform();          // drops a transform declared for the next recorded call (the call was rejected before it could be recorded)
-// TMAC_XF_GLU_NORM's own argument rules, the same on every path: in2 and gamma required, no residual operand.  TMAC_HIP_OK, or fail(E_ARG, ...)
-// naming the field.
-int32_t glu_norm_check(const tmac_hip_xform* xf);
-// tmac_hip_xform::kind split into the kind (low byte) and the gate of a GLU / GLU_NORM (bits 8..15: TMAC_XF_GATE_*), the same on every path.
-// *base: TMAC_XF_NONE / NORM / GLU / GLU_NORM; *gate: 0 silu, 1 relu^2, 2 tanh-GELU (the kernels' XF_GATE_*).  TMAC_HIP_OK, or fail(E_ARG, ...):
-// "unknown transform kind" for a low byte that is no kind (whatever the bits above it), else a message naming the gate -- gate bits on
-// NONE or NORM, a gate other than the three, any bit above 15.
-int32_t xf_kind_check(int32_t kind, int* base, int* gate);
 int32_t chain_record(const tmac_hip_weights* const* wl, int nmat, const void* B_dev, tmac_dtype_t act_dtype, void* const* C_list,
                      tmac_dtype_t out_dtype, int N);
 // deferred launches (tmac_hip_defer): true (and *rc set) when the call was queued instead of launched

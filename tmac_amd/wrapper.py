@@ -446,6 +446,19 @@ class TMACGeMMWrapper:
             raise KeyError(kind)
         return kinds[base] | (TMACGeMMWrapper._XF_GATES[gate] if sep else 0)
 
+    @staticmethod
+    def _xform(kind, in2, residual, gamma, eps, residual_out, keep, none_ok) -> "B.XForm":
+        """the ``tmac_hip_xform`` of a transform given as the methods below take it (``residual`` may be ``CARRY``)"""
+        xf = B.XForm()
+        xf.kind = TMACGeMMWrapper._xf_kind(kind, none_ok=none_ok)
+        xf.in2 = _ptr(in2) if in2 is not None else None
+        xf.residual = 1 if residual is TMACGeMMWrapper.CARRY else (_ptr(residual) if residual is not None else None)
+        xf.gamma = _ptr(gamma) if gamma is not None else None
+        xf.eps = float(eps)
+        xf.residual_out = _ptr(residual_out) if residual_out is not None else None
+        xf.keep = 1 if keep else 0
+        return xf
+
     def chain_xform(self, kind: str, in2=None, residual=None, gamma=None, eps: float = 1e-5, residual_out=None, keep: bool = False) -> None:
         """while recording a chain: a vector transform of the NEXT ``fused`` call's activations, applied inside its LUT build
         (tmac_hip_chain_xform).  kind "norm": t = in + residual (fp32 tensor, None, or ``TMACGeMMWrapper.CARRY`` = the t the latest
@@ -454,14 +467,7 @@ class TMACGeMMWrapper:
         eps) * gamma (gamma required, no residual operand); recorded only where the gate/up call in front publishes g itself.
         Another gate in the place of silu rides in the string: "glu:relu2" (max(in, 0)^2 * in2), "glu:gelu" (tanh-approximated GELU),
         "glu_norm:relu2" (BitNet b1.58 2B-4T's FFN), "glu_norm:gelu"; ":silu" is the bare name."""
-        xf = B.XForm()
-        xf.kind = self._xf_kind(kind, none_ok=False)
-        xf.in2 = _ptr(in2) if in2 is not None else None
-        xf.residual = 1 if residual is TMACGeMMWrapper.CARRY else (_ptr(residual) if residual is not None else None)
-        xf.gamma = _ptr(gamma) if gamma is not None else None
-        xf.eps = float(eps)
-        xf.residual_out = _ptr(residual_out) if residual_out is not None else None
-        xf.keep = 1 if keep else 0
+        xf = self._xform(kind, in2, residual, gamma, eps, residual_out, keep, none_ok=False)
         rec = getattr(self, "_recording", None)
         if rec is not None:
             rec.append((in2, residual, gamma, residual_out))      # kept alive with the chain
@@ -478,14 +484,7 @@ class TMACGeMMWrapper:
             act_dtype = _dtype_code(B_dev)
         if out_dtype is None:
             out_dtype = _dtype_code(C_list[0])
-        xf = B.XForm()
-        xf.kind = TMACGeMMWrapper._xf_kind(kind)
-        xf.in2 = _ptr(in2) if in2 is not None else None
-        xf.residual = 1 if residual is TMACGeMMWrapper.CARRY else (_ptr(residual) if residual is not None else None)
-        xf.gamma = _ptr(gamma) if gamma is not None else None
-        xf.eps = float(eps)
-        xf.residual_out = _ptr(residual_out) if residual_out is not None else None
-        xf.keep = 0
+        xf = self._xform(kind, in2, residual, gamma, eps, residual_out, False, none_ok=True)
         wa = (C.c_void_p * n)(*[w.handle.value for w in weights_list])
         ca = (C.c_void_p * n)(*[_ptr(c) for c in C_list])
         rec = getattr(self, "_recording", None)
@@ -493,18 +492,6 @@ class TMACGeMMWrapper:
             rec.append((list(weights_list), B_dev, list(C_list), in2, residual, gamma, residual_out))
         check(B.lib().tmac_hip_qgemm_fused_xf_dev(wa, n, _ptr(B_dev), act_dtype, C.byref(xf) if kind is not None else None, ca, out_dtype,
                                                   _stream(stream)))
-
-    @staticmethod
-    def _xform_rows(kind, in2, residual, gamma, eps, residual_out) -> "B.XForm":
-        xf = B.XForm()
-        xf.kind = TMACGeMMWrapper._xf_kind(kind)
-        xf.in2 = _ptr(in2) if in2 is not None else None
-        xf.residual = 1 if residual is TMACGeMMWrapper.CARRY else (_ptr(residual) if residual is not None else None)
-        xf.gamma = _ptr(gamma) if gamma is not None else None
-        xf.eps = float(eps)
-        xf.residual_out = _ptr(residual_out) if residual_out is not None else None
-        xf.keep = 0
-        return xf
 
     def fused_xf_rows(self, weights_list, B_dev, C_list, kind, N, in2=None, residual=None, gamma=None, eps: float = 1e-5, residual_out=None,
                       act_dtype: Optional[int] = None, out_dtype: Optional[int] = None, stream=None) -> None:
@@ -516,7 +503,7 @@ class TMACGeMMWrapper:
             act_dtype = _dtype_code(B_dev)
         if out_dtype is None:
             out_dtype = _dtype_code(C_list[0])
-        xf = self._xform_rows(kind, in2, residual, gamma, eps, residual_out)
+        xf = self._xform(kind, in2, residual, gamma, eps, residual_out, False, none_ok=True)
         wa = (C.c_void_p * n)(*[w.handle.value for w in weights_list])
         ca = (C.c_void_p * n)(*[_ptr(c) for c in C_list])
         rec = getattr(self, "_recording", None)
@@ -531,7 +518,7 @@ class TMACGeMMWrapper:
         written as the call writes it.  Synchronises the stream."""
         if act_dtype is None:
             act_dtype = _dtype_code(B_dev)
-        xf = self._xform_rows(kind, in2, residual, gamma, eps, residual_out)
+        xf = self._xform(kind, in2, residual, gamma, eps, residual_out, False, none_ok=True)
         check(B.lib().tmac_hip_debug_xf_rows(_ptr(B_dev), act_dtype, C.byref(xf), K, N, _ptr(x_out), _stream(stream)))
 
     def record_chain(self) -> "_ChainRecorder":
