@@ -135,6 +135,48 @@ int32_t tmac_hip_free_weights(tmac_hip_weights* w);
  * algorithmic bytes minus the activation-side terms */
 size_t tmac_hip_weights_bytes(const tmac_hip_weights* w);
 
+/* ---- device-side packing: checkpoint tensors -> reference blob -> handle, without the host -------------------------------
+ * A quantised checkpoint holds no blob: it holds GPTQ tensors, or codes with scales.  The blob is a pure permutation of their bits
+ * (python/t_mac/weights.py:57-87), so tensors that are in device memory are packed there (k_pack_* in tmac_pack.hip: every input word read
+ * once, the [k][m] -> row-interleaved transposition through LDS, one writer per output byte) instead of by the host.  Two input forms:
+ *   GPTQ    qweight int32 [K*bits/32][Mw]   row kp packs k = kp*(32/bits) ... of column m, lowest field first
+ *           scales  scales_dtype [K/gs][Mw]
+ *           qzeros  int32 [K/gs][Mw*bits/32]   NULL exactly when cfg->zero_point == 0.  The blob's zero is T-MAC's,
+ *                   (z + (gptq_v2 ? 0 : 1) - 2^(bits-1)) * scale: AutoGPTQ v1 stores z - 1.  The product is rounded ONCE, to scales_dtype,
+ *                   then converted to ref_float -- numpy's result on the unpacked tensors, bit for bit (python/t_mac/model_utils.py:95-129)
+ *           bits 1, 2, 4: the widths whose fields do not straddle a word.  bits = 3: TMAC_HIP_E_NOMATCH naming the width (use the codes form);
+ *           m_groups >= 1: TMAC_HIP_E_ARG (GPTQ has per-group scales)
+ *   codes   codes  uint8 [Mw][K], bits above `bits` ignored;  bits 1 .. 4
+ *           scales, zeros  sz_dtype [Mw][K/gs], already in T-MAC's convention (zero = (z - 2^(bits-1)) * scale): copied and permuted only;
+ *                   zeros NULL exactly when the configuration has no zero points.  m_groups >= 1: scales is [m_groups], copied; zeros NULL
+ * Outputs: A_ref uint8 [M/bm][K/4][bm/2] and scales_ref in ref_float, the two arguments of tmac_hip_register_weights[_dev] (layouts above).
+ * tmac_hip_ref_blob_bytes gives their sizes; it is a pure host function (no device is touched).
+ * Refusals.  Shape and configuration: those of registration, same codes and messages (bm, kfactor, group sizes ...).  TMAC_HIP_E_ARG with
+ * a message naming the argument, nothing written: a NULL required pointer; ANY device pointer of these calls below 16-byte alignment (the
+ * kernels load and store 16 bytes at a time; rows stay aligned because Mw is a multiple of 8 and K of 4); zeros / qzeros present with
+ * zero_point == 0, or absent with it set; m_groups >= 1 through the GPTQ form; a dtype other than TMAC_F32 / TMAC_F16.
+ * tmac_hip_pack_*_dev write the two halves into the caller's device buffers, asynchronously on `stream`; they allocate nothing.  They are
+ * ordered behind the calling thread's deferred queue ("deferred launches" below).  Nothing outside [pointer, pointer + bytes) of either
+ * output is written, nothing outside the inputs' extents is read (tests/test_gpu_pack.py holds them to both).
+ * tmac_hip_register_weights_*_dev pack into temporaries of their own and hand them to the registration above: every layout variant
+ * (tmac_hip_set_variant), fast-aggregation mode and the kept-reference case behave as there, and the handle is the one registration from
+ * the host blob gives.  They allocate and synchronise the stream, like registration.
+ * While a chain is being recorded all four run at once and are not recorded, as registration does.  None of them is for use inside a
+ * stream capture. */
+int32_t tmac_hip_ref_blob_bytes(int Mw, int K, int bits, const tmac_kcfg* cfg, tmac_dtype_t ref_float, size_t* a_bytes, size_t* s_bytes);
+int32_t tmac_hip_pack_gptq_dev(const void* qweight, const void* scales, const void* qzeros, tmac_dtype_t scales_dtype, int gptq_v2,
+                               int Mw, int K, int bits, const tmac_kcfg* cfg, void* A_ref_out, void* scales_ref_out,
+                               tmac_dtype_t ref_float, void* stream);
+int32_t tmac_hip_pack_codes_dev(const void* codes, const void* scales, const void* zeros, tmac_dtype_t sz_dtype,
+                                int Mw, int K, int bits, const tmac_kcfg* cfg, void* A_ref_out, void* scales_ref_out,
+                                tmac_dtype_t ref_float, void* stream);
+int32_t tmac_hip_register_weights_gptq_dev(tmac_hip_weights** out, const void* qweight, const void* scales, const void* qzeros,
+                                           tmac_dtype_t scales_dtype, int gptq_v2, int Mw, int K, int bits, const tmac_kcfg* cfg,
+                                           tmac_dtype_t ref_float, tmac_dtype_t dev_float, void* stream);
+int32_t tmac_hip_register_weights_codes_dev(tmac_hip_weights** out, const void* codes, const void* scales, const void* zeros,
+                                            tmac_dtype_t sz_dtype, int Mw, int K, int bits, const tmac_kcfg* cfg,
+                                            tmac_dtype_t ref_float, tmac_dtype_t dev_float, void* stream);
+
 /* LUT workspace = TMACGeMMWrapper::set_workspace (tmac_gemm_wrapper.h:257-270) on the device. */
 int32_t tmac_hip_workspace_create(tmac_hip_workspace** out, int maxK, int maxN);
 int32_t tmac_hip_workspace_free(tmac_hip_workspace* ws);
@@ -174,7 +216,8 @@ int32_t tmac_hip_qgemm_fused_dev(const tmac_hip_weights* const* weights, int nma
  * EVERY other entry point that launches work or touches device memory for the caller is ordered behind the calling thread's queue too: it
  * flushes the queue first, unconditionally (no overlap analysis: none of them is a hot path) -- tmac_hip_preprocessor_dev,
  * tmac_hip_qgemm_dev, tmac_hip_qgemm_partial_sums, tmac_hip_qgemm_fused_partial_sums, tmac_hip_chain_launch, tmac_hip_workspace_read /
- * _write, tmac_hip_debug_gemm_comb_sums / _gemm_image_read, tmac_hip_autotune_fused, and tmac_hip_free_weights, tmac_hip_chain_free and
+ * _write, tmac_hip_debug_gemm_comb_sums / _gemm_image_read, tmac_hip_autotune_fused, tmac_hip_pack_gptq_dev / _pack_codes_dev (they write the
+ * caller's blob buffers; a refused one leaves the queue alone), and tmac_hip_free_weights, tmac_hip_chain_free and
  * tmac_hip_cache_clear (a queued call may name what they release).  When that flush fails the entry point returns its status and launches
  * nothing of its own (the three that release still release: the handle is dead either way).  A queue belongs to a thread: freeing, from
  * another thread, weights that this thread has queued is the caller's error.

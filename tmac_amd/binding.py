@@ -85,6 +85,13 @@ def load_library() -> C.CDLL:
         "tmac_hip_set_kcfg": ([C.c_int] * 4 + [C.POINTER(KCfg)], i32),
         "tmac_hip_register_weights": ([C.POINTER(vp), vp, vp, C.c_int, C.c_int, C.c_int, C.POINTER(KCfg), C.c_int, C.c_int, vp], i32),
         "tmac_hip_register_weights_dev": ([C.POINTER(vp), vp, vp, C.c_int, C.c_int, C.c_int, C.POINTER(KCfg), C.c_int, C.c_int, vp], i32),
+        "tmac_hip_ref_blob_bytes": ([C.c_int, C.c_int, C.c_int, C.POINTER(KCfg), C.c_int, C.POINTER(sz), C.POINTER(sz)], i32),
+        "tmac_hip_pack_gptq_dev": ([vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(KCfg), vp, vp, C.c_int, vp], i32),
+        "tmac_hip_pack_codes_dev": ([vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(KCfg), vp, vp, C.c_int, vp], i32),
+        "tmac_hip_register_weights_gptq_dev": ([C.POINTER(vp), vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(KCfg), C.c_int,
+                                                C.c_int, vp], i32),
+        "tmac_hip_register_weights_codes_dev": ([C.POINTER(vp), vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(KCfg), C.c_int, C.c_int,
+                                                 vp], i32),
         "tmac_hip_free_weights": ([vp], i32),
         "tmac_hip_weights_bytes": ([vp], sz),
         "tmac_hip_workspace_create": ([C.POINTER(vp), C.c_int, C.c_int], i32),
@@ -160,6 +167,8 @@ def load_library() -> C.CDLL:
     }
     # $TMAC_HIP_LIB may name an OLDER build for an A/B run (tools/gpu): entry points it lacks stay unbound (calling one raises)
     optional = {"tmac_hip_chain_is_stream", "tmac_hip_chain_xform", "tmac_hip_qgemm_fused_xf_dev", "tmac_hip_qgemm_fused_xf_rows_dev", "tmac_hip_debug_xf_rows", "tmac_hip_debug_xf_rows_plan", "tmac_hip_debug_fused_plan", "tmac_hip_debug_route_stats", "tmac_hip_comm_init_ipc", "tmac_hip_comm_export", "tmac_hip_comm_connect", "tmac_hip_comm_status",
+                "tmac_hip_ref_blob_bytes", "tmac_hip_pack_gptq_dev", "tmac_hip_pack_codes_dev", "tmac_hip_register_weights_gptq_dev",
+                "tmac_hip_register_weights_codes_dev",
                 "tmac_hip_debug_rows_kernel", "tmac_hip_debug_rows_stats", "tmac_hip_debug_rows_plan", "tmac_hip_debug_rows_comb_sums"} if os.environ.get("TMAC_HIP_LIB") else set()
     for name, (argt, rest) in sigs.items():
         try:

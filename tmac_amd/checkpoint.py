@@ -1,0 +1,144 @@
+"""GPTQ checkpoint directory -> registered weights, the blob packed on the GPU (``Weights.from_gptq``).
+
+Two steps, split so that the first runs without a GPU:
+
+* ``scan_gptq_dir``  reads the headers of the ``model*.safetensors`` parts (8-byte little-endian length + JSON, as
+  ``convert._safetensors_shapes`` does, with the ``data_offsets``) and ``config.json``: which (qweight, scales, qzeros) triples exist,
+  where their bytes lie, and whether the zeros are AutoGPTQ v1's (z - 1) or v2's.  No tensor is loaded.
+* ``load_gptq_dir``  maps each part with ``np.memmap``, uploads the three packed tensors of a layer and registers them.  The
+  ``safetensors`` package is not needed.
+
+Refused, naming the tensor: act-order checkpoints (``desc_act``, as the reference refuses them), a ``qweight`` without ``scales`` or
+``qzeros``, tensors of another element type than I32 (qweight, qzeros) / F16 or F32 (scales).
+"""
+import json
+import os
+import struct
+from typing import Dict, List, NamedTuple, Tuple
+
+import numpy as np
+
+from . import convert
+from .binding import F16
+
+_NP = {"I32": np.int32, "F16": np.float16, "F32": np.float32}
+
+
+class TensorRef(NamedTuple):
+    """where one tensor of a safetensors file lies: bytes [begin, end) of ``path``, counted from the start of the file"""
+    path: str
+    dtype: str
+    shape: Tuple[int, ...]
+    begin: int
+    end: int
+
+
+class GptqLayer(NamedTuple):
+    name: str               # the layer: "<name>.qweight" without its suffix
+    qweight: TensorRef
+    scales: TensorRef
+    qzeros: TensorRef
+    K: int
+    Mw: int
+    bits: int
+    group_size: int
+
+
+class GptqScan(NamedTuple):
+    layers: List[GptqLayer]
+    gptq_v2: bool
+    zero_point: bool
+    quantization_config: dict
+
+
+def safetensors_index(path: str) -> Dict[str, TensorRef]:
+    """{tensor name: TensorRef} from the header of a .safetensors file: ``convert._safetensors_shapes`` with the data offsets, made absolute
+    (the header stores them relative to its own end)"""
+    size = os.path.getsize(path)
+    with open(path, "rb") as f:
+        head = f.read(8)
+        if len(head) != 8:
+            raise RuntimeError("{}: not a safetensors file (shorter than its header length field)".format(path))
+        (n,) = struct.unpack("<Q", head)
+        if n == 0 or n > size - 8:
+            raise RuntimeError("{}: corrupt safetensors header (length {} in a file of {} bytes)".format(path, n, size))
+        try:
+            hdr = json.loads(f.read(n))
+            out = {}
+            for k, v in hdr.items():
+                if k == "__metadata__":
+                    continue
+                b, e = (int(x) for x in v["data_offsets"])
+                if not 0 <= b <= e <= size - 8 - n:
+                    raise ValueError("tensor {}: data_offsets [{}, {}) outside the file".format(k, b, e))
+                out[k] = TensorRef(path, v["dtype"], tuple(int(d) for d in v["shape"]), 8 + n + b, 8 + n + e)
+            return out
+        except (ValueError, KeyError, TypeError) as e:
+            raise RuntimeError("{}: corrupt safetensors header ({})".format(path, e))
+
+
+def gptq_is_v2(qc: dict) -> bool:
+    """AutoGPTQ (v1) stores z - 1 in qzeros, GPTQModel (v2) stores z: the reference's pipeline reads the difference off the checkpoint's
+    ``quantization_config.meta.quantizer`` -- a GPTQModel checkpoint names "gptqmodel" there -- and a quant_method of "gptq_v2" says the
+    same (deploy/compile.py:98 accepts both methods)."""
+    q = qc.get("quantizer", "")
+    q = " ".join(str(x) for x in q) if isinstance(q, (list, tuple)) else str(q)
+    return "gptqmodel" in q.lower() or qc.get("quant_method", "") == "gptq_v2"
+
+
+def scan_gptq_dir(model_dir: str) -> GptqScan:
+    """The GPTQ triples of a checkpoint directory, in order of first appearance, without loading a tensor."""
+    qc = convert.get_quantization_config(model_dir)           # refuses desc_act
+    parts = sorted(f for f in os.listdir(model_dir) if f.startswith("model") and f.endswith(".safetensors"))
+    if not parts:
+        raise RuntimeError("Models in {} not in GPTQ safetensors format (torch .bin checkpoints: convert them to safetensors first)".format(model_dir))
+    index: Dict[str, TensorRef] = {}
+    order: List[str] = []
+    for part in parts:
+        for name, ref in safetensors_index(os.path.join(model_dir, part)).items():
+            index[name] = ref
+            if name.endswith(".qweight"):
+                order.append(name)
+    layers = []
+    for qname in order:
+        base = qname[:-len(".qweight")]
+        qw, sc, qz = index[qname], index.get(base + ".scales"), index.get(base + ".qzeros")
+        if sc is None:
+            raise RuntimeError("{}.scales is missing".format(base))
+        if qz is None:
+            raise RuntimeError("{}.qzeros is missing".format(base))
+        for ref, suffix, ok in ((qw, ".qweight", ("I32",)), (qz, ".qzeros", ("I32",)), (sc, ".scales", ("F16", "F32"))):
+            if ref.dtype not in ok:
+                raise RuntimeError("{}{} has dtype {}: {} expected".format(base, suffix, ref.dtype, " or ".join(ok)))
+            if len(ref.shape) != 2 or (ref.end - ref.begin) != int(np.prod(ref.shape)) * np.dtype(_NP[ref.dtype]).itemsize:
+                raise RuntimeError("{}{}: shape {} does not match its {} bytes".format(base, suffix, ref.shape, ref.end - ref.begin))
+        if qz.shape[1] <= 0 or sc.shape[0] <= 0 or sc.shape[1] < qz.shape[1] or sc.shape[0] != qz.shape[0] or sc.shape[1] != qw.shape[1]:
+            raise RuntimeError("{}: qweight {} / scales {} / qzeros {} are not GPTQ-packed shapes".format(qname, qw.shape, sc.shape, qz.shape))
+        bits = 32 // (sc.shape[1] // qz.shape[1])                      # convert.parse_gptq on shapes alone
+        if bits not in (1, 2, 4):
+            raise RuntimeError("{}: GPTQ-packed width {} is not served (1, 2, 4)".format(qname, bits))
+        K, Mw = qw.shape[0] * (32 // bits), qw.shape[1]
+        layers.append(GptqLayer(base, qw, sc, qz, K, Mw, bits, K // sc.shape[0]))
+    if not layers:
+        raise RuntimeError("Models in {} not in GPTQ format".format(model_dir))
+    return GptqScan(layers, gptq_is_v2(qc), not qc.get("sym", False), qc)
+
+
+def read_tensor(ref: TensorRef) -> np.ndarray:
+    """the tensor's bytes as a read-only numpy view of the mapped file"""
+    return np.memmap(ref.path, dtype=_NP[ref.dtype], mode="r", offset=ref.begin, shape=ref.shape)
+
+
+def load_gptq_dir(model_dir: str, wrapper, dev_dtype=F16) -> Dict[str, "object"]:
+    """{layer name: Weights} for every ``*.qweight`` triple of the checkpoint: the packed tensors are uploaded as they lie in the file
+    and unpacked, permuted and re-tiled on the GPU (``wrapper.register_gptq``).  A symmetric checkpoint (``sym``) is registered without
+    zero points, as the reference compiles its kernels (deploy/compile.py:103)."""
+    from .binding import KCfg
+    scan = scan_gptq_dir(model_dir)
+    out = {}
+    for L in scan.layers:
+        cfg = KCfg.make(L.Mw, L.K, L.bits, convert.default_bm(L.bits, L.Mw), 16, L.group_size, wrapper._act_group_size, scan.zero_point)
+        # np.array: a writable copy in memory (the map is read-only, and the upload wants one contiguous source)
+        qz = np.array(read_tensor(L.qzeros)) if scan.zero_point else None
+        out[L.name] = wrapper.register_gptq(np.array(read_tensor(L.qweight)), np.array(read_tensor(L.scales)), qz, cfg, scan.gptq_v2, dev_dtype)
+    return out

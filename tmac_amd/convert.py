@@ -8,7 +8,8 @@
   its inverse split for registration on the GPU
 
 Nothing here touches a GPU: numpy in, numpy out.  Results are identical to the reference's functions (tests compare
-them against the reference's Python, which imports without TVM).
+them against the reference's Python, which imports without TVM).  One exception, named for it: ``preprocess_for_t_mac_gpu``
+produces the same blob from the packed GPTQ tensors on the GPU; the numpy functions are its reference.
 """
 import configparser
 import os
@@ -208,6 +209,21 @@ def preprocess_for_t_mac(kcfg_file: str, w: np.ndarray, scales: np.ndarray, zero
     A, S = preprocess_weights(w, scales, zeros, bits=bits, g=4, bm=e["bm"], kfactor=e["kfactor"],
                               simd_n_in=e["simd_n_in"], simd_n_out=e["simd_n_out"])
     return np.concatenate([A.reshape(-1), np.ascontiguousarray(S.astype(np.float32)).view(np.uint8).reshape(-1)])
+
+
+def preprocess_for_t_mac_gpu(kcfg_file: str, qweight, scales, qzeros, gptq_v2: bool = True) -> np.ndarray:
+    """``preprocess_for_t_mac(kcfg_file, w, scales, zeros, bits)`` on the tensors ``unpack_gptq(qweight, scales, qzeros, gptq_v2)`` gives,
+    byte for byte, with the unpacking and the permutation done on the GPU (``tmac_hip_pack_gptq_dev``): the converter's route to the blob
+    of a T-MAC GGUF tensor.  The one function of this module that needs a GPU; the numpy functions above stay the CPU reference.  A kcfg
+    section without zero points (scales_size = M * K / group_size) drops the zeros, as passing ``zeros=None`` does there."""
+    from . import wrapper
+    from .binding import KCfg, F32
+    K, Mw, bits, gs = parse_gptq(qweight, scales, qzeros)
+    e = read_kcfg_entry(kcfg_file, Mw, K, bits)
+    zp = e["scales_size"] >= 2 * Mw * (K // e["group_size"])
+    cfg = KCfg.make(Mw, K, bits, e["bm"], e["kfactor"], e["group_size"], 64, zp)
+    A, S = wrapper.pack_gptq(qweight, scales, qzeros if zp else None, cfg, gptq_v2, F32)
+    return np.concatenate([A.cpu().numpy(), S.cpu().numpy().view(np.uint8)])
 
 
 def split_blob(blob: np.ndarray, Mw: int, K: int, bits: int) -> Tuple[np.ndarray, np.ndarray]:

@@ -4,6 +4,7 @@
 //   tmac_runtime.cpp     error text, device binding, the knob block, lifecycle, self-tests, tmac_hip_reset_state
 //   tmac_kcfg.cpp        the kcfg.ini table and its lookups
 //   tmac_weights.cpp     weight registration (reference layout -> device layout)
+//   tmac_pack_host.cpp   device-side packing: GPTQ tensors / plain codes -> reference blob (tmac_pack.hip) -> register_impl
 //   tmac_workspace.cpp   LUT workspace + the preprocessor entry point
 //   tmac_xform.cpp       the field rules of tmac_hip_xform: one resolver for every transform site (tmac_xform.h: no HIP, builds with plain g++)
 //   tmac_dispatch.cpp    qgemm_lut dispatch (a call is planned -- enum Route -- then launched), the fused entry point, parity taps

@@ -138,6 +138,12 @@ hipError_t launch_selftest_mfma(const uint32_t* in, int32_t* out, hipStream_t st
 hipError_t launch_selftest_permlane(const uint32_t* in, uint32_t* out, hipStream_t st);
 hipError_t launch_retile_weights(const uint8_t* A_ref, void* Wd, const Shape& s, hipStream_t st);
 hipError_t launch_retile_scales(const void* S_ref, Dtype in_dt, void* Sd, Dtype out_dt, const Shape& s, hipStream_t st);
+// device-side packing (tmac_pack.hip): GPTQ tensors (bits 1, 2, 4; per-group scales) or plain codes (bits 1-4) -> the reference blob halves
+// A_out (ref_weight_bytes) and S_out (ref_scale_elems values of out_dt).  qzeros / zeros NULL = no zero points.
+hipError_t launch_pack_gptq(const void* qweight, const void* scales, const void* qzeros, Dtype scales_dt, int gptq_v2, void* A_out, void* S_out,
+                            Dtype out_dt, const Shape& s, hipStream_t st);
+hipError_t launch_pack_codes(const void* codes, const void* scales, const void* zeros, Dtype sz_dt, void* A_out, void* S_out, Dtype out_dt,
+                             const Shape& s, hipStream_t st);
 hipError_t launch_preprocess(const void* B, Dtype act_dt, int8_t* qlut_ref, void* qlut_dev, void* qlut_lds, float* lut_scales,
                              float* lut_biases, int K, int N, int ags, size_t qdev_u4_per_row, hipStream_t st);
 // all-gather over IPC-mapped windows (tmac_comm.cpp, transport "ipc"): workgroup p of `world` handles rank p's part

@@ -1,0 +1,114 @@
+// tmac_pack.h — index and nibble arithmetic of the weight packers (tmac_pack.hip), for host and device.
+//
+// GPTQ tensors or plain codes -> the reference's bit-interleaved blob (python/t_mac/weights.py:57-87; closed form in
+// tmac_amd/weights.py).  Everything here is a pure function of integers: tests/cpp/pack_main.cc compiles this header with plain g++
+// and packs whole matrices through it, byte for byte against tmac_amd/weights.py:preprocess_weights (tests/test_pack_cpu.py); the
+// kernels call the same functions.
+//
+//   M-space row     r    = (o / 8) * 8 * bits + p * 8 + o % 8                                (o: weight row, p: bit plane)
+//   nibble(r, t)         = sum_ig bit_p(w[o][4 t + ig]) << ig
+//   byte(r, t)           = tile * (bm / 2 * K / 4) + ((t / kfactor) * (bm / 32) + rr / 32) * kfactor * 16 + (t % kfactor) * 16 + rr % 16
+//                          tile = r / bm, rr = r % bm;  low nibble for rr % 32 < 16, high otherwise
+//   scale(o, sg, which)  = ((tile * SG + sg) * (rpt / 8) + ol / 8) * (8 | 16) + which * 8 + ol % 8,   rpt = bm / bits, tile = o / rpt, ol = o % rpt
+//                          (which: 0 scale, 1 zero; 16 per octet with zero points)
+#pragma once
+#include <stddef.h>
+#include <stdint.h>
+
+#if defined(__HIPCC__)
+#include <hip/hip_fp16.h>
+#define TMAC_PACK_HD __host__ __device__ __forceinline__
+#else
+#define TMAC_PACK_HD inline
+#endif
+
+namespace tmac_pack {
+
+// M-space row of (weight row o, plane p), and its inverse
+TMAC_PACK_HD int mrow(int o, int p, int bits) { return (o / 8) * 8 * bits + p * 8 + (o % 8); }
+TMAC_PACK_HD int mrow_weight_row(int r, int bits) { return (r / (8 * bits)) * 8 + r % 8; }
+TMAC_PACK_HD int mrow_plane(int r, int bits) { return (r % (8 * bits)) / 8; }
+
+// byte of the blob that holds nibble (r, t); T = K / 4
+TMAC_PACK_HD size_t blob_byte(int r, int t, int bm, int kfactor, int T) {
+    const int tile = r / bm, rr = r % bm;
+    return (size_t)tile * ((size_t)(bm / 2) * T) + ((size_t)(t / kfactor) * (bm / 32) + rr / 32) * ((size_t)kfactor * 16) +
+           (size_t)(t % kfactor) * 16 + rr % 16;
+}
+TMAC_PACK_HD bool blob_high(int r, int bm) { return (r % bm) % 32 >= 16; }
+// The 16 bytes that hold table t of the 32 M-space rows [32 g, 32 g + 32): byte j = nibble(32 g + j) | nibble(32 g + 16 + j) << 4.
+// bm is a multiple of 32, so a group never straddles a tile.
+TMAC_PACK_HD size_t blob_unit(int g, int t, int bm, int kfactor, int T) { return blob_byte(32 * g, t, bm, kfactor, T); }
+
+// element of scales_ref that holds the scale (which = 0) or zero (which = 1) of (weight row o, scale group sg)
+TMAC_PACK_HD size_t scale_index(int o, int sg, int which, int bm, int bits, int SG, int zero_point) {
+    const int rpt = bm / bits, tile = o / rpt, ol = o % rpt;
+    return (((size_t)tile * SG + sg) * (rpt / 8) + ol / 8) * (zero_point ? 16 : 8) + (size_t)which * 8 + ol % 8;
+}
+
+// Plain codes: the nibble of plane p from the four codes of one table (codes k = 4 t .. 4 t + 3 in bytes 0 .. 3 of `four`).  Bits of a
+// code above `bits` are never looked at.
+TMAC_PACK_HD uint32_t codes_nibble(uint32_t four, int p) {
+    return ((four >> p) & 1u) | (((four >> (8 + p)) & 1u) << 1) | (((four >> (16 + p)) & 1u) << 2) | (((four >> (24 + p)) & 1u) << 3);
+}
+
+// GPTQ: one qweight word holds 32 / bits codes of consecutive k, lowest field first -- 8 / bits tables.  Plane p of the word: bit f of
+// the result is bit p of field f, i.e. the nibbles of the word's tables, lowest table first (32 / bits valid bits).
+TMAC_PACK_HD uint32_t gptq_plane(uint32_t word, int p, int bits) {
+    if (bits == 1) return word;
+    uint32_t out = 0;
+    const int n = 32 / bits;
+    for (int f = 0; f < n; ++f) out |= ((word >> (f * bits + p)) & 1u) << f;
+    return out;
+}
+// field i of a packed row (qzeros: column m of row sg is field m % (32 / bits) of word m * bits / 32)
+TMAC_PACK_HD uint32_t gptq_field(uint32_t word, int i, int bits) { return (word >> (i * bits)) & ((1u << bits) - 1u); }
+
+// T-MAC's zero as a multiplier of the scale: z + (v1 ? 1 : 0) - 2^(bits-1), exact in fp16 and fp32 (convert.py:unpack_gptq; AutoGPTQ v1
+// stores z - 1).  The zero itself is multiplier * scale, rounded ONCE to the scales' dtype: the fp32 product of an fp16 scale and this
+// small integer is exact, so one conversion to fp16 gives numpy's fp16 product (overflow to infinity included).
+TMAC_PACK_HD float gptq_zero_multiplier(uint32_t z, int v1, int bits) { return (float)((int)z + (v1 ? 1 : 0) - (1 << (bits - 1))); }
+
+#if defined(__HIPCC__)
+TMAC_PACK_HD float round_to_f16(float v) { return __half2float(__float2half_rn(v)); }
+#else
+// IEEE binary16 bits of v, round to nearest even (subnormals, overflow to infinity, NaN), and back: what numpy's float16 does
+inline uint16_t f32_to_f16_bits(float v) {
+    uint32_t x;
+    __builtin_memcpy(&x, &v, 4);
+    const uint32_t sign = (x >> 16) & 0x8000u, mag = x & 0x7fffffffu;
+    if (mag >= 0x7f800000u) return (uint16_t)(sign | 0x7c00u | (mag > 0x7f800000u ? 0x200u : 0u));
+    if (mag >= 0x477ff000u) return (uint16_t)(sign | 0x7c00u);                 // >= 65520 rounds to infinity
+    if (mag < 0x33000001u) return (uint16_t)sign;                             // <= 2^-25 rounds to zero
+    const int e = (int)(mag >> 23) - 127;
+    uint32_t m = (mag & 0x7fffffu) | 0x800000u;
+    const int shift = e < -14 ? 13 + (-14 - e) : 13;                          // subnormal results lose more bits
+    const uint32_t rest = m & ((1u << shift) - 1u), half = 1u << (shift - 1);
+    m >>= shift;
+    if (rest > half || (rest == half && (m & 1u))) ++m;
+    // normal: m has the hidden bit at 0x400, adding (e + 14) << 10 lets a carry out of the mantissa bump the exponent
+    const uint32_t h = e < -14 ? m : (uint32_t)((e + 14) << 10) + m;
+    return (uint16_t)(sign | h);
+}
+inline float f16_bits_to_f32(uint16_t h) {
+    const uint32_t sign = (uint32_t)(h & 0x8000u) << 16, e = (h >> 10) & 31u, m = h & 0x3ffu;
+    float mag;
+    if (e == 31) {
+        const uint32_t x = 0x7f800000u | (m << 13);
+        __builtin_memcpy(&mag, &x, 4);
+    } else if (e == 0) {
+        mag = (float)m * (1.0f / 16777216.0f);                                 // m * 2^-24
+    } else {
+        const uint32_t x = ((e + 112u) << 23) | (m << 13);
+        __builtin_memcpy(&mag, &x, 4);
+    }
+    uint32_t x;
+    __builtin_memcpy(&x, &mag, 4);
+    x |= sign;
+    __builtin_memcpy(&mag, &x, 4);
+    return mag;
+}
+inline float round_to_f16(float v) { return f16_bits_to_f32(f32_to_f16_bits(v)); }
+#endif
+
+}  // namespace tmac_pack

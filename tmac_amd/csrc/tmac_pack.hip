@@ -1,0 +1,269 @@
+// tmac_pack.hip — device-side packing: GPTQ tensors or plain codes -> the reference's bit-interleaved blob (A_ref, scales_ref), the
+// input of weight registration.  A pure permutation of bits; index arithmetic in tmac_pack.h (shared with the host test).
+//
+// Weights: one workgroup per tile of 64 weight rows x 64 tables (256 values of K).
+//   stage 1  every input word of the tile is read once, coalesced along the input's fast axis (GPTQ [k][m]: 16 bytes per lane along m;
+//            codes [m][k]: 4 bytes per lane along k), split into bit planes and written to LDS as nibbles: row (plane, weight row), two
+//            tables per byte.  GPTQ: the 8 / bits tables of a word are contiguous bits of the plane word -- one LDS store per plane.
+//            Codes: the 8 lanes that hold 8 consecutive tables OR their nibbles together (3 xor shuffles), one 32-bit store per plane.
+//   stage 2  one thread per (group of 32 M-space rows, pair of tables): 32 LDS bytes -> the two 16-byte units of the blob, each written
+//            by exactly this thread.  Lanes walk the tables, so a wave's stores run along the blob's kfactor * 16-byte runs.
+// Tails (Mw not a multiple of 64, K / 4 not a multiple of 64) are guarded on both sides: nothing outside the inputs is loaded, nothing
+// outside the blob is stored.  No atomics, no read-modify-write.
+// Scales: one thread per (scale group, 8 weight rows) writes the 8 scales (and 8 zeros) of that octet as 16-byte stores.
+#include <hip/hip_fp16.h>
+#include <hip/hip_runtime.h>
+
+#include "tmac_kernels.h"
+#include "tmac_pack.h"
+
+namespace tmac {
+namespace {
+
+namespace pk = tmac_pack;
+
+constexpr int PACK_ROWS = 64;              // weight rows per tile
+constexpr int PACK_TABLES = 64;            // tables per tile
+constexpr int PACK_THREADS = 256;
+constexpr int PACK_STRIDE = PACK_TABLES / 2 + 4;   // bytes per LDS row: 9 words, consecutive rows fall on consecutive banks
+
+// LDS row of (plane p, local weight row ol)
+__device__ __forceinline__ int lds_row(int p, int ol) { return p * PACK_ROWS + ol; }
+
+// stage 2, shared by both input forms
+template <int BITS>
+__device__ __forceinline__ void pack_store_tile(const uint8_t* lds, uint8_t* __restrict__ A_out, int Mw, int T, int bm, int kfactor) {
+    const int t0 = blockIdx.x * PACK_TABLES;
+    const int ngroups = Mw * BITS / 32;                 // M is a multiple of 32 (bm is)
+    constexpr int GROUPS = PACK_ROWS * BITS / 32;       // groups of 32 M-space rows per tile
+    for (int item = threadIdx.x; item < GROUPS * (PACK_TABLES / 2); item += PACK_THREADS) {
+        const int gl = item / (PACK_TABLES / 2), tp = item % (PACK_TABLES / 2);
+        const int g = blockIdx.y * GROUPS + gl, t = t0 + 2 * tp;
+        if (g >= ngroups || t >= T) continue;
+        uint32_t u0[4] = {0, 0, 0, 0}, u1[4] = {0, 0, 0, 0};
+#pragma unroll
+        for (int j = 0; j < 16; ++j) {
+            const int rlo = gl * 32 + j, rhi = rlo + 16;
+            const uint32_t lo = lds[lds_row(pk::mrow_plane(rlo, BITS), pk::mrow_weight_row(rlo, BITS)) * PACK_STRIDE + tp];
+            const uint32_t hi = lds[lds_row(pk::mrow_plane(rhi, BITS), pk::mrow_weight_row(rhi, BITS)) * PACK_STRIDE + tp];
+            u0[j / 4] |= ((lo & 15u) | ((hi & 15u) << 4)) << (8 * (j % 4));
+            u1[j / 4] |= ((lo >> 4) | (hi & 0xf0u)) << (8 * (j % 4));
+        }
+        *reinterpret_cast<uint4*>(A_out + pk::blob_unit(g, t, bm, kfactor, T)) = make_uint4(u0[0], u0[1], u0[2], u0[3]);
+        if (t + 1 < T) *reinterpret_cast<uint4*>(A_out + pk::blob_unit(g, t + 1, bm, kfactor, T)) = make_uint4(u1[0], u1[1], u1[2], u1[3]);
+    }
+}
+
+// GPTQ qweight int32 [K * BITS / 32][Mw]
+template <int BITS>
+__global__ __launch_bounds__(PACK_THREADS) void k_pack_gptq_weights(const uint32_t* __restrict__ qweight, uint8_t* __restrict__ A_out, int Mw,
+                                                                    int K, int bm, int kfactor) {
+    __shared__ __attribute__((aligned(16))) uint8_t lds[PACK_ROWS * BITS * PACK_STRIDE];
+    const int T = K / 4, KP = K / (32 / BITS);
+    const int o0 = blockIdx.y * PACK_ROWS;
+    constexpr int WORD_ROWS = PACK_TABLES * BITS / 8;       // qweight rows per tile: a word holds 8 / BITS tables
+    const int kp0 = blockIdx.x * WORD_ROWS;
+    for (int idx = threadIdx.x; idx < WORD_ROWS * (PACK_ROWS / 4); idx += PACK_THREADS) {
+        const int kpl = idx / (PACK_ROWS / 4), mq = idx % (PACK_ROWS / 4);
+        const int kp = kp0 + kpl, m = o0 + 4 * mq;
+        uint4 w4 = make_uint4(0, 0, 0, 0);
+        if (kp < KP && m < Mw) w4 = *reinterpret_cast<const uint4*>(qweight + (size_t)kp * Mw + m);   // Mw is a multiple of 8: whole quads
+        const uint32_t w[4] = {w4.x, w4.y, w4.z, w4.w};
+#pragma unroll
+        for (int c = 0; c < 4; ++c) {
+#pragma unroll
+            for (int p = 0; p < BITS; ++p) {
+                const uint32_t v = pk::gptq_plane(w[c], p, BITS);
+                uint8_t* dst = lds + lds_row(p, 4 * mq + c) * PACK_STRIDE + kpl * (4 / BITS);    // 8 / BITS tables = 4 / BITS bytes
+                if (BITS == 1) *reinterpret_cast<uint32_t*>(dst) = v;
+                else if (BITS == 2) *reinterpret_cast<uint16_t*>(dst) = (uint16_t)v;
+                else *dst = (uint8_t)v;
+            }
+        }
+    }
+    __syncthreads();
+    pack_store_tile<BITS>(lds, A_out, Mw, T, bm, kfactor);
+}
+
+// plain codes uint8 [Mw][K]
+template <int BITS>
+__global__ __launch_bounds__(PACK_THREADS) void k_pack_codes_weights(const uint8_t* __restrict__ codes, uint8_t* __restrict__ A_out, int Mw, int K,
+                                                                     int bm, int kfactor) {
+    __shared__ __attribute__((aligned(16))) uint8_t lds[PACK_ROWS * BITS * PACK_STRIDE];
+    const int T = K / 4;
+    const int o0 = blockIdx.y * PACK_ROWS, t0 = blockIdx.x * PACK_TABLES;
+    // a wave takes one weight row's 64 tables per step (256 contiguous bytes); every lane runs every step (the shuffles need them all)
+    for (int idx = threadIdx.x; idx < PACK_ROWS * PACK_TABLES; idx += PACK_THREADS) {
+        const int ol = idx / PACK_TABLES, tl = idx % PACK_TABLES;
+        const int o = o0 + ol, t = t0 + tl;
+        uint32_t four = 0;
+        if (o < Mw && t < T) four = *reinterpret_cast<const uint32_t*>(codes + (size_t)o * K + 4 * (size_t)t);   // K is a multiple of 4
+#pragma unroll
+        for (int p = 0; p < BITS; ++p) {
+            uint32_t v = pk::codes_nibble(four, p) << (4 * (tl % 8));
+            v |= __shfl_xor(v, 1);
+            v |= __shfl_xor(v, 2);
+            v |= __shfl_xor(v, 4);
+            if (tl % 8 == 0) *reinterpret_cast<uint32_t*>(lds + lds_row(p, ol) * PACK_STRIDE + tl / 2) = v;
+        }
+    }
+    __syncthreads();
+    pack_store_tile<BITS>(lds, A_out, Mw, T, bm, kfactor);
+}
+
+// ---- scales -------------------------------------------------------------------------------------------------------------------------
+template <class T> __device__ __forceinline__ float to_f32(T v);
+template <> __device__ __forceinline__ float to_f32<float>(float v) { return v; }
+template <> __device__ __forceinline__ float to_f32<__half>(__half v) { return __half2float(v); }
+template <class T> __device__ __forceinline__ T from_f32(float v);
+template <> __device__ __forceinline__ float from_f32<float>(float v) { return v; }
+template <> __device__ __forceinline__ __half from_f32<__half>(float v) { return __float2half_rn(v); }
+
+// n contiguous elements (a multiple of 16 bytes, 16-byte aligned on both sides) as 16-byte accesses
+template <class T, int N>
+__device__ __forceinline__ void load_vec(const T* src, T (&v)[N]) {
+    static_assert(sizeof(T) * N % 16 == 0, "whole 16-byte accesses");
+    uint4 raw[sizeof(T) * N / 16];
+#pragma unroll
+    for (int i = 0; i < (int)(sizeof(T) * N / 16); ++i) raw[i] = reinterpret_cast<const uint4*>(src)[i];
+    __builtin_memcpy(v, raw, sizeof(raw));
+}
+template <class T, int N>
+__device__ __forceinline__ void store_vec(T* dst, const T (&v)[N]) {
+    static_assert(sizeof(T) * N % 16 == 0, "whole 16-byte accesses");
+    uint4 raw[sizeof(T) * N / 16];
+    __builtin_memcpy(raw, v, sizeof(raw));
+#pragma unroll
+    for (int i = 0; i < (int)(sizeof(T) * N / 16); ++i) reinterpret_cast<uint4*>(dst)[i] = raw[i];
+}
+
+// the octet's 8 scales (and 8 zeros) -> scales_ref
+template <class OT>
+__device__ __forceinline__ void store_octet(OT* out, int o, int sg, const float (&sc)[8], const float (&zr)[8], int bm, int bits, int SG, int zero_point) {
+    OT v[8];
+#pragma unroll
+    for (int i = 0; i < 8; ++i) v[i] = from_f32<OT>(sc[i]);
+    store_vec(out + pk::scale_index(o, sg, 0, bm, bits, SG, zero_point), v);
+    if (zero_point) {
+#pragma unroll
+        for (int i = 0; i < 8; ++i) v[i] = from_f32<OT>(zr[i]);
+        store_vec(out + pk::scale_index(o, sg, 1, bm, bits, SG, zero_point), v);
+    }
+}
+
+// GPTQ: scales ST [SG][Mw], qzeros int32 [SG][Mw * bits / 32] (NULL without zero points); consecutive threads take consecutive octets
+template <class ST, class OT>
+__global__ __launch_bounds__(256) void k_pack_gptq_scales(const ST* __restrict__ scales, const uint32_t* __restrict__ qzeros, int v1, OT* __restrict__ out,
+                                                         int Mw, int SG, int bits, int bm) {
+    const int noct = Mw / 8;
+    const size_t idx = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (idx >= (size_t)SG * noct) return;
+    const int sg = (int)(idx / noct), o = (int)(idx % noct) * 8;
+    ST s[8];
+    load_vec(scales + (size_t)sg * Mw + o, s);
+    float sc[8], zr[8];
+    uint32_t zw = 0;
+    if (qzeros) zw = qzeros[(size_t)sg * (Mw * bits / 32) + o * bits / 32] >> (o * bits % 32);   // 8 fields of an octet never straddle a word
+#pragma unroll
+    for (int i = 0; i < 8; ++i) {
+        sc[i] = to_f32(s[i]);
+        // one rounding to the scales' dtype (tmac_pack.h): fp32 scales -- the fp32 product; fp16 scales -- the exact product, rounded once
+        zr[i] = to_f32(from_f32<ST>(pk::gptq_zero_multiplier(pk::gptq_field(zw, i, bits), v1, bits) * sc[i]));
+    }
+    store_octet(out, o, sg, sc, zr, bm, bits, SG, qzeros != nullptr);
+}
+
+// codes form: scales / zeros ST [Mw][SG], already in T-MAC's convention; consecutive threads take consecutive scale groups
+template <class ST, class OT>
+__global__ __launch_bounds__(256) void k_pack_codes_scales(const ST* __restrict__ scales, const ST* __restrict__ zeros, OT* __restrict__ out, int Mw, int SG,
+                                                          int bits, int bm) {
+    const size_t idx = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (idx >= (size_t)SG * (Mw / 8)) return;
+    const int sg = (int)(idx % SG), o = (int)(idx / SG) * 8;
+    float sc[8], zr[8];
+#pragma unroll
+    for (int i = 0; i < 8; ++i) {
+        sc[i] = to_f32(scales[(size_t)(o + i) * SG + sg]);
+        zr[i] = zeros ? to_f32(zeros[(size_t)(o + i) * SG + sg]) : 0.0f;
+    }
+    store_octet(out, o, sg, sc, zr, bm, bits, SG, zeros != nullptr);
+}
+
+template <class ST, class OT>
+__global__ void k_pack_copy(const ST* __restrict__ in, OT* __restrict__ out, size_t n) {
+    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < n) out[i] = from_f32<OT>(to_f32(in[i]));
+}
+
+// instantiates `launch`, a generic lambda taking two value-less type tags, for the (input, output) dtype pair
+template <class F>
+void by_dtypes(Dtype in_dt, Dtype out_dt, F&& launch) {
+    if (in_dt == F32 && out_dt == F32) launch(float(), float());
+    else if (in_dt == F32) launch(float(), __half());
+    else if (out_dt == F32) launch(__half(), float());
+    else launch(__half(), __half());
+}
+
+dim3 weight_grid(const Shape& s) { return dim3((unsigned)((s.K / 4 + PACK_TABLES - 1) / PACK_TABLES), (unsigned)((s.Mw + PACK_ROWS - 1) / PACK_ROWS)); }
+
+}  // namespace
+
+hipError_t launch_pack_gptq(const void* qweight, const void* scales, const void* qzeros, Dtype scales_dt, int gptq_v2, void* A_out, void* S_out,
+                            Dtype out_dt, const Shape& s, hipStream_t st) {
+    const dim3 g = weight_grid(s), b(PACK_THREADS);
+    const uint32_t* qw = (const uint32_t*)qweight;
+    uint8_t* A = (uint8_t*)A_out;
+    switch (s.bits) {
+        case 1: hipLaunchKernelGGL(k_pack_gptq_weights<1>, g, b, 0, st, qw, A, s.Mw, s.K, s.bm, s.kfactor); break;
+        case 2: hipLaunchKernelGGL(k_pack_gptq_weights<2>, g, b, 0, st, qw, A, s.Mw, s.K, s.bm, s.kfactor); break;
+        case 4: hipLaunchKernelGGL(k_pack_gptq_weights<4>, g, b, 0, st, qw, A, s.Mw, s.K, s.bm, s.kfactor); break;
+        default: return hipErrorInvalidValue;
+    }
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return e;
+    const int SG = s.K / s.gs;
+    const size_t n = (size_t)SG * (s.Mw / 8);
+    by_dtypes(scales_dt, out_dt, [&](auto in_tag, auto out_tag) {
+        using ST = decltype(in_tag);
+        using OT = decltype(out_tag);
+        hipLaunchKernelGGL((k_pack_gptq_scales<ST, OT>), dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, (const ST*)scales, (const uint32_t*)qzeros,
+                           gptq_v2 ? 0 : 1, (OT*)S_out, s.Mw, SG, s.bits, s.bm);
+    });
+    return hipGetLastError();
+}
+
+hipError_t launch_pack_codes(const void* codes, const void* scales, const void* zeros, Dtype sz_dt, void* A_out, void* S_out, Dtype out_dt,
+                             const Shape& s, hipStream_t st) {
+    const dim3 g = weight_grid(s), b(PACK_THREADS);
+    const uint8_t* cd = (const uint8_t*)codes;
+    uint8_t* A = (uint8_t*)A_out;
+    switch (s.bits) {
+        case 1: hipLaunchKernelGGL(k_pack_codes_weights<1>, g, b, 0, st, cd, A, s.Mw, s.K, s.bm, s.kfactor); break;
+        case 2: hipLaunchKernelGGL(k_pack_codes_weights<2>, g, b, 0, st, cd, A, s.Mw, s.K, s.bm, s.kfactor); break;
+        case 3: hipLaunchKernelGGL(k_pack_codes_weights<3>, g, b, 0, st, cd, A, s.Mw, s.K, s.bm, s.kfactor); break;
+        case 4: hipLaunchKernelGGL(k_pack_codes_weights<4>, g, b, 0, st, cd, A, s.Mw, s.K, s.bm, s.kfactor); break;
+        default: return hipErrorInvalidValue;
+    }
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return e;
+    if (s.m_groups >= 1) {      // unified scale(s): the m_groups values, copied
+        const size_t n = (size_t)s.m_groups;
+        by_dtypes(sz_dt, out_dt, [&](auto in_tag, auto out_tag) {
+            using ST = decltype(in_tag);
+            using OT = decltype(out_tag);
+            hipLaunchKernelGGL((k_pack_copy<ST, OT>), dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, (const ST*)scales, (OT*)S_out, n);
+        });
+        return hipGetLastError();
+    }
+    const int SG = s.K / s.gs;
+    const size_t n = (size_t)SG * (s.Mw / 8);
+    by_dtypes(sz_dt, out_dt, [&](auto in_tag, auto out_tag) {
+        using ST = decltype(in_tag);
+        using OT = decltype(out_tag);
+        hipLaunchKernelGGL((k_pack_codes_scales<ST, OT>), dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, (const ST*)scales, (const ST*)zeros, (OT*)S_out,
+                           s.Mw, SG, s.bits, s.bm);
+    });
+    return hipGetLastError();
+}
+
+}  // namespace tmac

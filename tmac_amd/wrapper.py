@@ -51,8 +51,132 @@ def _dtype_code(t) -> int:
     raise TypeError(f"unsupported dtype {t.dtype}")
 
 
+def _on_device(x, what: str, np_dtypes):
+    """a contiguous torch CUDA tensor of ``x``: a CUDA tensor as it is, a numpy array or CPU tensor uploaded first.  ``np_dtypes``: the
+    element types the argument may have (a TypeError names the argument otherwise)."""
+    import torch
+    if isinstance(x, np.ndarray):
+        x = torch.from_numpy(np.ascontiguousarray(x))
+    name = str(x.dtype).replace("torch.", "")
+    if name not in np_dtypes:
+        raise TypeError(f"{what} must be {' or '.join(np_dtypes)}, not {name}")
+    return x.cuda().contiguous()
+
+
+def _float_code(t, what: str) -> int:
+    name = str(t.dtype).replace("torch.", "")
+    if name == "float16":
+        return F16
+    if name == "float32":
+        return F32
+    raise TypeError(f"{what} must be float16 or float32, not {name}")
+
+
+def _gptq_args(qweight, scales, qzeros, cfg, act_group_size):
+    """device tensors, shape and configuration of a GPTQ triple (qzeros None: no zero points, which needs a cfg -- the width is read off
+    the qzeros shape otherwise)"""
+    from . import convert
+    qw = _on_device(qweight, "qweight", ("int32",))
+    sc = _on_device(scales, "scales", ("float16", "float32"))
+    qz = _on_device(qzeros, "qzeros", ("int32",)) if qzeros is not None else None
+    if qw.dim() != 2 or sc.dim() != 2 or (qz is not None and qz.dim() != 2):
+        raise ValueError("qweight, scales and qzeros are 2-D: [K*bits/32][M], [K/gs][M], [K/gs][M*bits/32]")
+    if cfg is None:
+        if qz is None:
+            raise ValueError("without qzeros the width cannot be read off the shapes: pass a cfg (and its bits)")
+        K, Mw, bits, gs = convert.parse_gptq(qw, sc, qz)
+        cfg = KCfg.make(Mw, K, bits, convert.default_bm(bits, Mw), 16, gs, act_group_size, True)
+    else:
+        Mw, gs = int(qw.shape[1]), cfg.group_size
+        K = int(sc.shape[0]) * gs
+        bits = int(qw.shape[0]) * 32 // K
+    return qw, sc, qz, Mw, K, bits, cfg
+
+
+def _codes_args(codes, scales, zeros, bits, cfg, act_group_size):
+    from . import convert
+    cd = _on_device(codes, "codes", ("uint8",))
+    sc = _on_device(scales, "scales", ("float16", "float32"))
+    zr = _on_device(zeros, "zeros", ("float16", "float32")) if zeros is not None else None
+    if zr is not None and zr.dtype != sc.dtype:
+        raise TypeError("scales and zeros share one dtype")
+    Mw, K = int(cd.shape[0]), int(cd.shape[1])
+    if cfg is None:
+        if sc.dim() != 2:
+            raise ValueError("unified scales (m_groups >= 1) need a cfg")
+        cfg = KCfg.make(Mw, K, bits, convert.default_bm(bits, Mw), 16, K // int(sc.shape[1]), act_group_size, zr is not None)
+    return cd, sc, zr, Mw, K, cfg
+
+
+def ref_blob_bytes(Mw: int, K: int, bits: int, cfg: KCfg, ref_dtype=F32):
+    """(bytes of A_ref, bytes of scales_ref) of the reference blob of this shape (tmac_hip_ref_blob_bytes; host only)"""
+    a, s = C.c_size_t(0), C.c_size_t(0)
+    check(B.lib().tmac_hip_ref_blob_bytes(Mw, K, bits, C.byref(cfg), ref_dtype, C.byref(a), C.byref(s)))
+    return a.value, s.value
+
+
+def _blob_buffers(Mw, K, bits, cfg, ref_dtype):
+    import torch
+    a, s = ref_blob_bytes(Mw, K, bits, cfg, ref_dtype)
+    esz = 2 if ref_dtype == F16 else 4
+    return (torch.empty(a, dtype=torch.uint8, device="cuda"),
+            torch.empty(s // esz, dtype=torch.float16 if ref_dtype == F16 else torch.float32, device="cuda"))
+
+
+def pack_gptq(qweight, scales, qzeros, cfg: Optional[KCfg] = None, gptq_v2: bool = True, ref_dtype=F32, act_group_size: int = 64, stream=None):
+    """GPTQ tensors -> the reference blob, on the GPU (tmac_hip_pack_gptq_dev): (A_ref uint8, scales_ref) as flat CUDA tensors, exactly
+    ``weights.preprocess_weights(*convert.unpack_gptq(...))``.  Asynchronous on the stream.  (numpy inputs are uploaded on torch's current
+    stream and released in its order: leave ``stream`` at its default with them.)"""
+    qw, sc, qz, Mw, K, bits, cfg = _gptq_args(qweight, scales, qzeros, cfg, act_group_size)
+    A, S = _blob_buffers(Mw, K, bits, cfg, ref_dtype)
+    check(B.lib().tmac_hip_pack_gptq_dev(_ptr(qw), _ptr(sc), _ptr(qz), _float_code(sc, "scales"), int(bool(gptq_v2)), Mw, K, bits, C.byref(cfg),
+                                         _ptr(A), _ptr(S), ref_dtype, _stream(stream)))
+    return A, S
+
+
+def pack_codes(codes, scales, zeros, bits: int, cfg: Optional[KCfg] = None, ref_dtype=F32, act_group_size: int = 64, stream=None):
+    """codes uint8 [Mw][K] + scales / zeros [Mw][K/gs] in T-MAC's convention -> the reference blob, on the GPU (tmac_hip_pack_codes_dev)"""
+    cd, sc, zr, Mw, K, cfg = _codes_args(codes, scales, zeros, bits, cfg, act_group_size)
+    A, S = _blob_buffers(Mw, K, bits, cfg, ref_dtype)
+    check(B.lib().tmac_hip_pack_codes_dev(_ptr(cd), _ptr(sc), _ptr(zr), _float_code(sc, "scales"), Mw, K, bits, C.byref(cfg), _ptr(A), _ptr(S),
+                                          ref_dtype, _stream(stream)))
+    return A, S
+
+
 class Weights:
     """One weight matrix resident on the GPU (tmac_hip_register_weights)."""
+
+    @classmethod
+    def _adopt(cls, handle, Mw, K, bits, cfg):
+        self = cls.__new__(cls)
+        self.Mw, self.K, self.bits, self.cfg = Mw, K, bits, cfg
+        self._h, self._keep, self._caches = handle, None, []
+        return self
+
+    @classmethod
+    def from_gptq(cls, qweight, scales, qzeros, cfg: Optional[KCfg] = None, gptq_v2: bool = True, dev_dtype=F16, act_group_size: int = 64,
+                  stream=None) -> "Weights":
+        """Register straight from GPTQ tensors -- torch CUDA tensors, or numpy arrays that are uploaded first -- packed into the reference
+        blob on the GPU (tmac_hip_register_weights_gptq_dev).  The handle is the one ``Weights(*blob)`` gives.  Without a ``cfg`` the
+        shapes come from ``convert.parse_gptq`` and the M-tile from ``convert.default_bm``; ``qzeros=None`` (no zero points) needs one."""
+        qw, sc, qz, Mw, K, bits, cfg = _gptq_args(qweight, scales, qzeros, cfg, act_group_size)
+        h = C.c_void_p()
+        ref = _float_code(sc, "scales")        # the blob in the scales' own dtype: nothing is rounded on the way
+        check(B.lib().tmac_hip_register_weights_gptq_dev(C.byref(h), _ptr(qw), _ptr(sc), _ptr(qz), ref, int(bool(gptq_v2)), Mw, K, bits,
+                                                         C.byref(cfg), ref, dev_dtype, _stream(stream)))
+        return cls._adopt(h, Mw, K, bits, cfg)
+
+    @classmethod
+    def from_codes(cls, codes, scales, zeros, bits: int, cfg: Optional[KCfg] = None, dev_dtype=F16, act_group_size: int = 64,
+                   stream=None) -> "Weights":
+        """Register from unpacked codes uint8 [Mw][K] with scales / zeros [Mw][K/gs] already in T-MAC's convention (or [m_groups] unified
+        scales with a ``cfg``), packed on the GPU (tmac_hip_register_weights_codes_dev).  The route for 3-bit weights."""
+        cd, sc, zr, Mw, K, cfg = _codes_args(codes, scales, zeros, bits, cfg, act_group_size)
+        h = C.c_void_p()
+        ref = _float_code(sc, "scales")
+        check(B.lib().tmac_hip_register_weights_codes_dev(C.byref(h), _ptr(cd), _ptr(sc), _ptr(zr), ref, Mw, K, bits, C.byref(cfg), ref, dev_dtype,
+                                                          _stream(stream)))
+        return cls._adopt(h, Mw, K, bits, cfg)
 
     def __init__(self, A_ref, scales_ref, Mw: int, K: int, bits: int, cfg: KCfg, scales_dtype=F32, dev_dtype=F32,
                  on_device: bool = False, stream=None):
@@ -372,6 +496,15 @@ class TMACGeMMWrapper:
             return Weights(A_ref, scales_ref, M, K, bits, cfg, scales_dtype, dev_dtype, on_device)
         finally:
             B.lib().tmac_hip_set_fast_aggregation(0)
+
+    def register_gptq(self, qweight, scales, qzeros, cfg: Optional[KCfg] = None, gptq_v2: bool = True, dev_dtype=F16, stream=None) -> Weights:
+        """``Weights.from_gptq`` with this wrapper's act_group_size: GPTQ tensors (CUDA tensors, or numpy arrays uploaded first) -> handle,
+        the blob packed on the GPU"""
+        return Weights.from_gptq(qweight, scales, qzeros, cfg, gptq_v2, dev_dtype, self._act_group_size, stream)
+
+    def register_codes(self, codes, scales, zeros, bits: int, cfg: Optional[KCfg] = None, dev_dtype=F16, stream=None) -> Weights:
+        """``Weights.from_codes`` with this wrapper's act_group_size"""
+        return Weights.from_codes(codes, scales, zeros, bits, cfg, dev_dtype, self._act_group_size, stream)
 
     def llama_cpp_init(self, B_dev, M: int, K: int, N: int, bits: int, act_group_size: Optional[int] = None,
                        act_dtype: Optional[int] = None, stream=None) -> None:

@@ -1,0 +1,161 @@
+"""GPTQ tensors -> registered handle: the host route against the device route, and the pack kernels against a plain copy.
+
+llama-2-7B shapes (o, qkv, gate/up, down), W2 and W4, group size 128, seeded synthetic GPTQ tensors (fp16 scales).  Per shape:
+  (a) host route, SECONDS on the host clock, one run: convert.unpack_gptq + weights.preprocess_weights (numpy, one thread) +
+      tmac_hip_register_weights (upload of the blob + re-tile), ended by a device synchronise;
+  (b) device route, MILLISECONDS on the host clock: upload of the three packed tensors from pageable memory +
+      tmac_hip_register_weights_gptq_dev (pack + re-tile; it synchronises); first run and the median of the following three;
+  (c) the pack kernels alone (tmac_hip_pack_gptq_dev into preallocated buffers) under DEVICE EVENTS, as bytes read + written over time,
+      beside a device-to-device hipMemcpyAsync that moves the same number of bytes (it copies half of them: read + written are equal).
+      Both walk a pool of distinct buffer sets larger than the 256 MiB Infinity Cache, are warmed, and alternate pass by pass in one run
+      until each has filled a timed window of at least 0.3 s.
+No rate is required of (c): the file states the kernels' share of the copy's rate.  The one hard condition is (b) < (a) at every shape;
+the tool exits 1 when it does not hold.
+usage: bench_register.py [--out FILE] [--shapes o,qkv,gate_up,down] [--bits 2,4] [--skip-host]"""
+import argparse
+import ctypes as C
+import math
+import os
+import sys
+import time
+
+import numpy as np
+import torch
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+import tmac_amd  # noqa: E402
+from tmac_amd import F16, F32, KCfg, convert, weights, wrapper  # noqa: E402
+
+SHAPES = {"o": (4096, 4096), "qkv": (12288, 4096), "gate_up": (11008, 4096), "down": (4096, 11008)}     # (Mw, K)
+GS, AGS, POOL_BYTES, WINDOW_S = 128, 64, 640 << 20, 0.3
+
+
+def synthetic(seed, Mw, K, bits):
+    """GPTQ tensors with every field random: qweight int32 [K*bits/32][Mw], scales fp16 [K/gs][Mw], qzeros int32 [K/gs][Mw*bits/32]"""
+    rng = np.random.default_rng(seed)
+    qw = rng.integers(-2 ** 31, 2 ** 31, size=(K * bits // 32, Mw), dtype=np.int64).astype(np.int32)
+    qz = rng.integers(-2 ** 31, 2 ** 31, size=(K // GS, Mw * bits // 32), dtype=np.int64).astype(np.int32)
+    sc = (np.abs(rng.standard_normal((K // GS, Mw))) * 0.02 + 0.005).astype(np.float16)
+    return qw, sc, qz
+
+
+def hip_runtime():
+    """the HIP runtime this process already has (torch's): one more runtime in the process would be a second device context"""
+    with open("/proc/self/maps") as f:
+        for line in f:
+            if "libamdhip64" in line:
+                return C.CDLL(line.split()[-1])
+    raise RuntimeError("no libamdhip64 mapped")
+
+
+def host_route(qw, sc, qz, Mw, K, bits, cfg):
+    t0 = time.perf_counter()
+    w, s, z, b, g = convert.unpack_gptq(qw, sc, qz, gptq_v2=True)
+    t1 = time.perf_counter()
+    A, S = weights.preprocess_weights(w, s, z, bits=bits, bm=cfg.bm, kfactor=cfg.kfactor)
+    t2 = time.perf_counter()
+    h = tmac_amd.Weights(A, S, Mw, K, bits, cfg, scales_dtype=F16, dev_dtype=F16)
+    torch.cuda.synchronize()
+    t3 = time.perf_counter()
+    h.free()
+    return t1 - t0, t2 - t1, t3 - t2
+
+
+def device_route(qw, sc, qz, cfg):
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    h = tmac_amd.Weights.from_gptq(qw, sc, qz, cfg, True, F16)          # numpy in: uploaded first; the call synchronises
+    torch.cuda.synchronize()
+    t1 = time.perf_counter()
+    h.free()
+    return (t1 - t0) * 1e3
+
+
+def pack_vs_copy(hip, qw, sc, qz, Mw, K, bits, cfg):
+    """(bytes per call, pack GB/s, copy GB/s, calls timed, pack window s, copy window s)"""
+    a_bytes, s_bytes = wrapper.ref_blob_bytes(Mw, K, bits, cfg, F16)
+    in_bytes = qw.nbytes + sc.nbytes + qz.nbytes
+    moved = in_bytes + a_bytes + s_bytes
+    nsets = max(2, math.ceil(POOL_BYTES / moved))
+    dq, ds, dz = (torch.from_numpy(a).cuda() for a in (qw, sc, qz))
+    sets = [(dq.clone(), ds.clone(), dz.clone(), torch.empty(a_bytes, dtype=torch.uint8, device="cuda"),
+             torch.empty(s_bytes, dtype=torch.uint8, device="cuda")) for _ in range(nsets)]
+    half = (moved // 2 + 15) // 16 * 16
+    src = [torch.empty(half, dtype=torch.uint8, device="cuda") for _ in range(nsets)]
+    dst = [torch.empty(half, dtype=torch.uint8, device="cuda") for _ in range(nsets)]
+    st = torch.cuda.current_stream().cuda_stream
+    L = tmac_amd.lib()
+
+    def pack_pass():
+        for q, s, z, A, S in sets:
+            tmac_amd.binding.check(L.tmac_hip_pack_gptq_dev(q.data_ptr(), s.data_ptr(), z.data_ptr(), F16, 1, Mw, K, bits, C.byref(cfg),
+                                                            A.data_ptr(), S.data_ptr(), F16, st))
+
+    def copy_pass():
+        for a, b in zip(src, dst):
+            rc = hip.hipMemcpyAsync(C.c_void_p(b.data_ptr()), C.c_void_p(a.data_ptr()), C.c_size_t(half), 3, C.c_void_p(st))     # 3: device to device
+            if rc:
+                raise RuntimeError(f"hipMemcpyAsync: {rc}")
+
+    def timed(fn):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record(); fn(); e1.record(); torch.cuda.synchronize()
+        return e0.elapsed_time(e1) * 1e-3
+
+    pack_pass(); copy_pass(); torch.cuda.synchronize()       # warm: code objects, first touch of every buffer
+    tp = tc = 0.0
+    passes = 0
+    while passes < 3 or tp < WINDOW_S or tc < WINDOW_S:
+        tp += timed(pack_pass)
+        tc += timed(copy_pass)
+        passes += 1
+    calls = passes * nsets
+    return moved, moved * calls / tp / 1e9, 2 * half * calls / tc / 1e9, calls, tp, tc
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--out", default="")
+    ap.add_argument("--shapes", default="o,qkv,gate_up,down")
+    ap.add_argument("--bits", default="2,4")
+    ap.add_argument("--skip-host", action="store_true", help="leave (a) out (it takes seconds per shape)")
+    args = ap.parse_args()
+    assert torch.cuda.is_available(), "bench_register.py measures on a GPU"
+    hip = hip_runtime()
+    lines = ["# tools/bench_register.py: GPTQ tensors -> handle.  (a) host seconds, one run; (b) host-clock ms around upload + device-side",
+             "# registration; (c) pack kernels alone, device events, bytes read + written per second, beside hipMemcpyAsync D2D of the same bytes.",
+             f"# device: {torch.cuda.get_device_name(0)}; group size {GS}; fp16 scales; pool per contender >= {POOL_BYTES >> 20} MiB; window >= {WINDOW_S} s",
+             "shape     bits  Mw     K      | (a) unpack_s  preprocess_s  register_s  total_s | (b) first_ms  median3_ms  (a)/(b) | "
+             "(c) MB/call  calls  pack_GB/s  copy_GB/s  pack/copy"]
+    ok = True
+    for name in args.shapes.split(","):
+        Mw, K = SHAPES[name]
+        for bits in (int(b) for b in args.bits.split(",")):
+            cfg = KCfg.make(Mw, K, bits, convert.default_bm(bits, Mw), 16, GS, AGS, True)
+            qw, sc, qz = synthetic(1000 * bits + Mw % 997, Mw, K, bits)
+            dev = [device_route(qw, sc, qz, cfg) for _ in range(4)]
+            first, med = dev[0], float(np.median(dev[1:]))
+            if args.skip_host:
+                a_txt, ratio = "      -             -           -        -", "      -"
+            else:
+                tu, tpp, tr = host_route(qw, sc, qz, Mw, K, bits, cfg)
+                total = tu + tpp + tr
+                a_txt = f"{tu:9.3f}  {tpp:12.3f}  {tr:10.3f}  {total:7.3f}"
+                ratio = f"{total * 1e3 / med:7.0f}"
+                ok &= max(first, med) < total * 1e3
+            moved, pg, cg, calls, tp, tc = pack_vs_copy(hip, qw, sc, qz, Mw, K, bits, cfg)
+            line = (f"{name:9s} {bits:4d}  {Mw:5d}  {K:5d}  |    {a_txt} |    {first:9.2f}  {med:10.2f}  {ratio} |    "
+                    f"{moved / 1e6:8.2f}  {calls:5d}  {pg:9.0f}  {cg:9.0f}  {pg / cg:9.2f}")
+            print(line, flush=True)
+            lines.append(line)
+    lines.append("# (b) < (a) at every shape: " + ("yes" if ok else "NO"))
+    print(lines[-1])
+    if args.out:
+        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+        with open(args.out, "w") as f:
+            f.write("\n".join(lines) + "\n")
+    return 0 if ok else 1
+
+
+if __name__ == "__main__":
+    sys.exit(main())
