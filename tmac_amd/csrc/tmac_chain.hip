@@ -460,7 +460,7 @@ __global__ __launch_bounds__(CHAIN_FT) void k_decode_chain(ChainArgs a) {
 
         CSTAMP(i, 3);
 
-        // ---- 3. LUT into LDS (lut_ctor.cc:120-215, as in k_gemv_quad) ----
+        // ---- 3. LUT into LDS (the constructor of tmac_lut_build.h; the fp16 unpack and the act-group scale in this kernel's own words, see there) ----
         // the activations as fp32: the fp16 vector as it is, or -- tmac_hip_chain_xform -- a vector transform of it, computed here where
         // every workgroup holds the whole vector anyway (a decoder's residual add + RMSNorm in front of q/k/v and gate/up, its
         // silu(gate) * up in front of the down projection): the calls of a layer chain up without a kernel in between
@@ -533,8 +533,8 @@ __global__ __launch_bounds__(CHAIN_FT) void k_decode_chain(ChainArgs a) {
             if (uni(d->gamma) != nullptr) {
                 // sum over the wave: four DPP steps inside the rows of 16 lanes, the four row sums through readlane (__shfl_xor is a
                 // ds_bpermute round trip per step: six in a row cost 0.2 us here)
-                ss = __fadd_rn(ss, qdpp_f<0xB1>(ss)); ss = __fadd_rn(ss, qdpp_f<0x4E>(ss));
-                ss = __fadd_rn(ss, qdpp_f<0x141>(ss)); ss = __fadd_rn(ss, qdpp_f<0x140>(ss));     // row_half_mirror, row_mirror
+                ss = __fadd_rn(ss, dpp_f<0xB1>(ss)); ss = __fadd_rn(ss, dpp_f<0x4E>(ss));
+                ss = __fadd_rn(ss, dpp_f<0x141>(ss)); ss = __fadd_rn(ss, dpp_f<0x140>(ss));     // row_half_mirror, row_mirror
                 const int ssb = __builtin_bit_cast(int, ss);
                 const float sw = __fadd_rn(__fadd_rn(__builtin_bit_cast(float, __builtin_amdgcn_readlane(ssb, 0)), __builtin_bit_cast(float, __builtin_amdgcn_readlane(ssb, 16))),
                                            __fadd_rn(__builtin_bit_cast(float, __builtin_amdgcn_readlane(ssb, 32)), __builtin_bit_cast(float, __builtin_amdgcn_readlane(ssb, 48))));
@@ -588,31 +588,18 @@ __global__ __launch_bounds__(CHAIN_FT) void k_decode_chain(ChainArgs a) {
                 if (r < nr && p < P) {
                     float x[8];
                     unpack(r, x);
-                    mx = fmaxf(mx, __fadd_rn(__fadd_rn(fabsf(x[0]), fabsf(x[1])), __fadd_rn(fabsf(x[2]), fabsf(x[3]))));
-                    mx = fmaxf(mx, __fadd_rn(__fadd_rn(fabsf(x[4]), fabsf(x[5])), __fadd_rn(fabsf(x[6]), fabsf(x[7]))));
-                    float va = -__fadd_rn(__fadd_rn(__fadd_rn(x[0], x[1]), x[2]), x[3]);
-                    float vb = -__fadd_rn(__fadd_rn(__fadd_rn(x[4], x[5]), x[6]), x[7]);
-                    va = __fadd_rn(va, qdpp_f<0x4E>(va));      // lane ^ 2: v0+v4 | v2+v6      (lut_ctor.cc:25-31)
-                    vb = __fadd_rn(vb, qdpp_f<0x4E>(vb));      //           v1+v5 | v3+v7
-                    va = __fadd_rn(va, qdpp_f<0xB1>(va));      // lane ^ 1: (v0+v4)+(v2+v6)
-                    vb = __fadd_rn(vb, qdpp_f<0xB1>(vb));      //           (v1+v5)+(v3+v7)
-                    if ((p & 3) == 0) l_us[CHAIN_US_FLOATS + (p >> 2)] = __fadd_rn(va, vb);
+                    lut_row_pass1(LUT_X8(x), p, mx, l_us + CHAIN_US_FLOATS);
                 }
             }
-#ifdef TMAC_CHAIN_KO_PASS1      /* timing experiment (wrong scale): what the cross-wave maximum and its barrier cost */
-            mx = q_row_allmax(mx);
-            mx = q_xor_max_f(mx);
-#else
-            mx = q_row_allmax(mx);
-            mx = q_xor_max_f(mx);
+            mx = lut_wave_max(mx);
+#ifndef TMAC_CHAIN_KO_PASS1     /* defined: timing experiment (wrong scale): what the cross-wave maximum and its barrier cost */
             if (lane == 0) l_us[2 + w] = mx;
             __syncthreads();
             mx = l_us[2];
 #pragma unroll
             for (int ww = 1; ww < NWV; ++ww) mx = fmaxf(mx, l_us[2 + ww]);
 #endif
-            gscale = div127(mx);
-            gtinv = (gscale != 0.0f) ? rcp_exact(gscale) : 0.0f;
+            lut_scale(mx, gscale, gtinv);
             if (tid == 0) l_us[0] = gscale;
         }
 #pragma unroll
@@ -630,23 +617,14 @@ __global__ __launch_bounds__(CHAIN_FT) void k_decode_chain(ChainArgs a) {
                     scales = div127(mx);
                     t_scales = (scales != 0.0f) ? rcp_exact(scales) : 0.0f;
                 }
-                uint32_t lo0, hi0, lo1, hi1;
                 float La, Lb;
-                q_table8<true>(x[0], x[1], x[2], x[3], t_scales, lo0, hi0, La);
-                q_table8<true>(x[4], x[5], x[6], x[7], t_scales, lo1, hi1, Lb);
-                tab[TMAC_CHAIN_IMG2 ? img2_index(p >> 2, p & 3) : (p & 3) * tstride + (p >> 2)] = make_uint4(lo0, hi0, lo1, hi1);
+                tab[TMAC_CHAIN_IMG2 ? img2_index(p >> 2, p & 3) : (p & 3) * tstride + (p >> 2)] = lut_tables2<true>(LUT_X8(x), t_scales, La, Lb);
                 if (SM != 2) {
-                    // lut_biases (lut_ctor.cc:25-31): per 8-table chunk ((v0+v4)+(v2+v6)) + ((v1+v5)+(v3+v7)), v_i = -L15 of table i
-                    float va = -La, vb = -Lb;
-                    va = __fadd_rn(va, qdpp_f<0x4E>(va));
-                    vb = __fadd_rn(vb, qdpp_f<0x4E>(vb));
-                    va = __fadd_rn(va, qdpp_f<0xB1>(va));
-                    vb = __fadd_rn(vb, qdpp_f<0xB1>(vb));
-                    const float v = __fadd_rn(va, vb);
-                    const float c1 = qdpp_f<0x104>(v);      // row_shl:4: the second chunk of the act group
+                    const float v = lut_chunk_sum(La, Lb);
+                    const float c1 = lut_group_partner(v);      // (every lane of the act group takes part)
                     if ((p & 7) == 0) {
                         l_ls[p >> 3] = __fmul_rn(0.5f, scales);
-                        l_lb[p >> 3] = __fmul_rn(0.5f, __fadd_rn(__fadd_rn(0.0f, v), c1));
+                        l_lb[p >> 3] = __fmul_rn(0.5f, lut_group_bias(v, c1));
                     }
                 }
             }
@@ -702,8 +680,8 @@ __global__ __launch_bounds__(CHAIN_FT) void k_decode_chain(ChainArgs a) {
 #pragma unroll
                 for (int pl = 0; pl < BITS; ++pl) {
                     uint32_t v = have ? (uint32_t)iacc[pl] : 0u;
-                    v += qdpp_u<0x124>(v);
-                    v += qdpp_u<0x128>(v);
+                    v += dpp_u<0x124>(v);
+                    v += dpp_u<0x128>(v);
                     v = q_xor_add_u(v);
                     if (lane < 4) redi[(wl * 4 + lane) * CHAIN_RED + pl] = (int32_t)v;
                     iacc[pl] = 0;
@@ -712,8 +690,8 @@ __global__ __launch_bounds__(CHAIN_FT) void k_decode_chain(ChainArgs a) {
                 float acc = 0.f;
                 if (have) {
                     acc = cacc;
-                    acc = __fadd_rn(acc, qdpp_f<0x124>(acc));     // lanes with the same row: rotate by 4, 8 within the DPP row
-                    acc = __fadd_rn(acc, qdpp_f<0x128>(acc));
+                    acc = __fadd_rn(acc, dpp_f<0x124>(acc));     // lanes with the same row: rotate by 4, 8 within the DPP row
+                    acc = __fadd_rn(acc, dpp_f<0x128>(acc));
                     acc = q_xor_add_f(acc);
                 }
                 if (lane < 4) red[(wl * 4 + lane) * CHAIN_RED] = acc;
@@ -756,7 +734,7 @@ __global__ __launch_bounds__(CHAIN_FT) void k_decode_chain(ChainArgs a) {
                         float acc = 0.f;
 #pragma unroll
                         for (int pl = 0; pl < BITS; ++pl) {
-                            const float tp = __fmul_rn((float)cb[pl], q_alpha(pl));
+                            const float tp = __fmul_rn((float)cb[pl], alpha_of(pl));
                             acc = (pl == 0) ? tp : __fadd_rn(acc, tp);
                         }
                         const float v = __fadd_rn(__fmul_rn(acc, l_us[0]), __fmul_rn(l_us[1], 0.5f));
@@ -778,7 +756,7 @@ __global__ __launch_bounds__(CHAIN_FT) void k_decode_chain(ChainArgs a) {
                 if (epi) {
                     // ... gate(gate) * up (epi 1 / 2 / 3: silu / relu^2 / tanh-GELU): the up quad of this row pair sits four lanes up (slot qs + 1, same DPP row); from the fp16
                     // values a reader would see, fp32 arithmetic, rounded to the fp16 the image holds
-                    const uint32_t ub = qdpp_u<0x104>(hb);               // row_shl:4
+                    const uint32_t ub = dpp_u<0x104>(hb);               // row_shl:4
                     const float gv = __half2float(__ushort_as_half((unsigned short)hb)), uv = __half2float(__ushort_as_half((unsigned short)ub));
                     float xv1[1] = {gv};
                     const float uv1[1] = {uv};
@@ -786,7 +764,7 @@ __global__ __launch_bounds__(CHAIN_FT) void k_decode_chain(ChainArgs a) {
                     const float xv = xv1[0];
                     if (p_mi == 0) pb = (uint32_t)__half_as_ushort(__float2half_rn(xv));
                 }
-                const uint32_t nb = qdpp_u<0xB1>(pb);                    // quad_perm [1,0,3,2]: the neighbour's value
+                const uint32_t nb = dpp_u<0xB1>(pb);                    // quad_perm [1,0,3,2]: the neighbour's value
                 if (mine) {
                     const size_t oi = (size_t)(4 * p_lq + row);
                     if (a.out_f16) reinterpret_cast<TMAC_GLOBAL unsigned short*>(p_c)[oi] = (unsigned short)hb;

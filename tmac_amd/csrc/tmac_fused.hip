@@ -23,42 +23,15 @@
 
 #include "tmac_core.h"
 #include "tmac_kernels.h"
+#include "tmac_dev.h"
 
 namespace tmac {
 
 typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
 
-__device__ __forceinline__ float f_alpha(int p) { return p == 0 ? 0.5f : (p == 1 ? 1.0f : (p == 2 ? 2.0f : 4.0f)); }
-
-__device__ __forceinline__ int f_rne_sat_int8(float x) {
-    const float r = rintf(x);
-    int i = (r >= -2147483648.0f && r < 2147483648.0f) ? (int)r : INT32_MIN;
-    return max(-128, min(127, i));
-}
-
-__device__ __forceinline__ float ld_scale(const void* p, int f16, size_t i) {
-    return f16 ? __half2float(reinterpret_cast<const __half*>(p)[i]) : reinterpret_cast<const float*>(p)[i];
-}
-
-__device__ __forceinline__ void st_out(void* C, int f16, size_t i, float v) {
-    if (f16) reinterpret_cast<__half*>(C)[i] = __float2half_rn(v);
-    else reinterpret_cast<float*>(C)[i] = v;
-}
-
-// Cross-lane moves as DPP modifiers (no LDS round trip, unlike __shfl_xor -> ds_bpermute_b32).
-//   quad_perm [1,0,3,2] = 0xB1 (lane^1)   quad_perm [2,3,0,1] = 0x4E (lane^2)
-//   row_shl:n = 0x100+n (lane i reads lane i+n of its 16-lane row)   row_ror:n = 0x120+n
-//   row_half_mirror = 0x141 (i -> 7-i within 8)   row_mirror = 0x140 (i -> 15-i within 16)
-template <int CTRL>
-__device__ __forceinline__ float dpp_f(float v) {
-    return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), CTRL, 0xf, 0xf, false));
-}
-template <int CTRL>
-__device__ __forceinline__ uint32_t dpp_u(uint32_t v) {
-    return (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, CTRL, 0xf, 0xf, false);
-}
-// max over the 16 lanes of a DPP row, result in every lane (max is commutative and idempotent)
-__device__ __forceinline__ float row_allmax(float v) {
+// max over the 16 lanes of a DPP row, result in every lane (max is commutative and idempotent) -- through builtin DPP moves: another
+// instruction sequence than q_row_allmax (tmac_lut_build.h: v_max_f32 with a DPP operand), kept for this kernel as it was
+__device__ __forceinline__ float row_allmax_dppmov(float v) {
     v = fmaxf(v, dpp_f<0xB1>(v));
     v = fmaxf(v, dpp_f<0x4E>(v));
     v = fmaxf(v, dpp_f<0x141>(v));
@@ -71,23 +44,6 @@ __device__ __forceinline__ float row_allmax(float v) {
 constexpr int FT = 512;        // threads per workgroup
 constexpr int FW = FT / 64;    // waves
 constexpr int UPS = FW * KL;   // units per step (128)
-
-template <int BITS>
-struct WFrag {
-    uint32_t wd[8 * BITS / 2];
-    uint32_t sraw[4];     // raw scale / zero-point words of this lane's two rows, fetched WITH the weights
-};                        // (converted at use: converting at load time would stall on the load)
-
-// scale (which = 0) or zero point (which = 1) of row i (0/1) from the raw words
-template <bool ZP>
-__device__ __forceinline__ float frag_scale(const uint32_t (&sraw)[4], int f16, int i, int which) {
-    const int e = i * (ZP ? 2 : 1) + which;          // element index within the lane's 2*per values
-    if (f16) {
-        const uint32_t wv = sraw[e >> 1];
-        return __half2float(__ushort_as_half((unsigned short)((e & 1) ? (wv >> 16) : (wv & 0xffff))));
-    }
-    return __uint_as_float(sraw[e]);
-}
 
 // weights (non-temporal, 1 KiB per wave-instruction) + the lane's scale values for unit u
 template <int BITS, bool ZP, int SM, int ACC>
@@ -243,7 +199,7 @@ __global__ __launch_bounds__(FT) void k_gemv_fused(FusedArgs a) {
                     mx = fmaxf(mx, __fadd_rn(__fadd_rn(fabsf(x0), fabsf(x1)), __fadd_rn(fabsf(x2), fabsf(x3))));
                 }
             }
-            mx = row_allmax(mx);
+            mx = row_allmax_dppmov(mx);
             mx = fmaxf(mx, __shfl_xor(mx, 16, 64));
             mx = fmaxf(mx, __shfl_xor(mx, 32, 64));
             if (lane == 0) l_scr[w] = mx;
@@ -267,7 +223,7 @@ __global__ __launch_bounds__(FT) void k_gemv_fused(FusedArgs a) {
                 float scales, t_scales;
                 if (SM == 2) { scales = gscale; t_scales = gtinv; }
                 else {
-                    const float mx = row_allmax(__fadd_rn(__fadd_rn(fabsf(x0), fabsf(x1)), __fadd_rn(fabsf(x2), fabsf(x3))));
+                    const float mx = row_allmax_dppmov(__fadd_rn(__fadd_rn(fabsf(x0), fabsf(x1)), __fadd_rn(fabsf(x2), fabsf(x3))));
                     scales = __fdiv_rn(mx, 127.0f);
                     t_scales = (scales != 0.0f) ? __fdiv_rn(1.0f, scales) : 0.0f;
                 }
@@ -282,8 +238,8 @@ __global__ __launch_bounds__(FT) void k_gemv_fused(FusedArgs a) {
                 uint32_t lo = 0, hi = 0;
 #pragma unroll
                 for (int i = 0; i < 4; ++i) {
-                    lo |= (uint32_t)(max(f_rne_sat_int8(__fmul_rn(e[i], t_scales)), -127) + 128) << (8 * i);
-                    hi |= (uint32_t)(max(f_rne_sat_int8(__fmul_rn(e[4 + i], t_scales)), -127) + 128) << (8 * i);
+                    lo |= (uint32_t)(max(rne_sat_int8(__fmul_rn(e[i], t_scales)), -127) + 128) << (8 * i);
+                    hi |= (uint32_t)(max(rne_sat_int8(__fmul_rn(e[4 + i], t_scales)), -127) + 128) << (8 * i);
                 }
                 if (ACC == 1) { lo ^= 0x80808080u; hi ^= 0x80808080u; }   // signed entries for the MFMA path
                 const int u = t >> 3, tl = t & 7;
@@ -455,7 +411,7 @@ __global__ __launch_bounds__(FT) void k_gemv_fused(FusedArgs a) {
         if (ACC == 1 && SM != 2) {
             float acc = __fmul_rn(cacc[0][0], 0.5f);
 #pragma unroll
-            for (int pl = 1; pl < BITS; ++pl) acc = __fadd_rn(acc, __fmul_rn(cacc[0][pl], f_alpha(pl)));
+            for (int pl = 1; pl < BITS; ++pl) acc = __fadd_rn(acc, __fmul_rn(cacc[0][pl], alpha_of(pl)));
             acc = __fadd_rn(acc, __shfl_xor(acc, 16, 64));   // the 4 lane groups hold different unit quads of the row
             acc = __fadd_rn(acc, __shfl_xor(acc, 32, 64));
             if (lane < 16) red[w * 16 + lane] = acc;         // lane = 4*rlp + bp = row within the block
@@ -473,7 +429,7 @@ __global__ __launch_bounds__(FT) void k_gemv_fused(FusedArgs a) {
             for (int i = 0; i < 2; ++i) {
                 float acc = __fmul_rn(cacc[i][0], 0.5f);
 #pragma unroll
-                for (int pl = 1; pl < BITS; ++pl) acc = __fadd_rn(acc, __fmul_rn(cacc[i][pl], f_alpha(pl)));
+                for (int pl = 1; pl < BITS; ++pl) acc = __fadd_rn(acc, __fmul_rn(cacc[i][pl], alpha_of(pl)));
                 // sum over the 8 same-parity lanes of the row: lane^2, then rotate by 4 and by 8
                 acc = __fadd_rn(acc, dpp_f<0x4E>(acc));
                 acc = __fadd_rn(acc, dpp_f<0x124>(acc));
@@ -514,7 +470,7 @@ __global__ __launch_bounds__(FT) void k_gemv_fused(FusedArgs a) {
 #pragma unroll
                         for (int ww = 0; ww < FW; ++ww) cb += redi[((ww * RL + r) * 4 + pl) * 4 + be];
                         if (a.dump) a.dump[(size_t)n * M.Mw * BITS + mrow(o, pl, BITS)] = cb;
-                        const float t = __fmul_rn((float)cb, f_alpha(pl));
+                        const float t = __fmul_rn((float)cb, alpha_of(pl));
                         acc = (pl == 0) ? t : __fadd_rn(acc, t);
                     }
                     const float v = __fadd_rn(__fmul_rn(acc, l_ls[0]), __fmul_rn(l_lb[0], 0.5f));

@@ -32,16 +32,11 @@
 
 #include "tmac_core.h"
 #include "tmac_kernels.h"
+#include "tmac_dev.h"
 
 namespace tmac {
 
 typedef int gv4i_t __attribute__((ext_vector_type(4)));
-
-__device__ __forceinline__ float g_alpha(int p) { return p == 0 ? 0.5f : (p == 1 ? 1.0f : (p == 2 ? 2.0f : 4.0f)); }
-__device__ __forceinline__ void g_st(void* C, int f16, size_t i, float v) {
-    if (f16) reinterpret_cast<__half*>(C)[i] = __float2half_rn(v);
-    else reinterpret_cast<float*>(C)[i] = v;
-}
 
 constexpr int GRT = 2;   // MFMA row tiles per wave (16 bit-plane rows each)
 constexpr int GWV = 4;   // waves per workgroup (consecutive row blocks)
@@ -306,7 +301,7 @@ __global__ __launch_bounds__(64 * GWV) void k_gemm_onehot(GemmArgs a) {
                         const int r = (BITS == 2) ? (2 * pl + oo) : pl;
                         const int32_t cb = c[rt][nt][r];
                         if (DUMP && o < Mw) a.dump[(size_t)n * Mw * BITS + mrow(o, pl, BITS)] = cb;
-                        const float tp = __fmul_rn((float)cb, g_alpha(pl));
+                        const float tp = __fmul_rn((float)cb, alpha_of(pl));
                         t = (pl == 0) ? tp : __fadd_rn(t, tp);
                     }
                     const float v = __fadd_rn(__fmul_rn(t, a.lut_scales[n]), __fmul_rn(a.lut_biases[n], 0.5f));
@@ -320,9 +315,9 @@ __global__ __launch_bounds__(64 * GWV) void k_gemm_onehot(GemmArgs a) {
                 } else {
                     acc = __fmul_rn(facc[rt][nt][(oo * BITS) >> 1][0], 0.5f);
 #pragma unroll
-                    for (int pl = 1; pl < BITS; ++pl) acc = __fadd_rn(acc, __fmul_rn(facc[rt][nt][(oo * BITS + pl) >> 1][(oo * BITS + pl) & 1], g_alpha(pl)));
+                    for (int pl = 1; pl < BITS; ++pl) acc = __fadd_rn(acc, __fmul_rn(facc[rt][nt][(oo * BITS + pl) >> 1][(oo * BITS + pl) & 1], alpha_of(pl)));
                 }
-                if (o < Mw) g_st(M.C, a.out_f16, (size_t)n * Mw + o, acc);
+                if (o < Mw) st_out(M.C, a.out_f16, (size_t)n * Mw + o, acc);
             }
         }
     }

@@ -55,7 +55,7 @@ typedef float p4f_t __attribute__((ext_vector_type(4)));
 typedef float p16f_t __attribute__((ext_vector_type(16)));
 
 // ---------------------------------------------------------------------------------------------
-// LUT build for the GEMM: the pair-wise build of k_preprocess_pairs (same arithmetic, lut_ctor.cc:120-215 bit for bit)
+// LUT build for the GEMM: the pair-wise build of k_preprocess_pairs (the same pieces of tmac_lut_build.h)
 // with 8 activation rows x 8 pairs per 64 lanes, written in the layout the GEMM streams (round 6: chunk-major, so that everything a
 // step of k_gemm_planes fetches is ONE scalar offset plus immediates):
 //   bimg [act group kk][n tile = n / 64][part = 4 (unit & 1) + pair][n & 63] uint4   signed half tables of tables 2 pair, 2 pair + 1 of
@@ -75,47 +75,26 @@ __global__ __launch_bounds__(256) void k_lut_image(const void* __restrict__ B, u
     float x[8];
     if constexpr (XF) {
         xf_rows_x8(xf_rows_arg(xa...), B, F16, K, nn, kk * 8 + p, x);
-    } else if (F16) {
-        const uint4 v = reinterpret_cast<const uint4*>(reinterpret_cast<const __half*>(B) + (size_t)nn * K + kk * 64)[p];
-        const uint32_t r[4] = {v.x, v.y, v.z, v.w};
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            const __half2 hh = *reinterpret_cast<const __half2*>(&r[i]);
-            x[2 * i] = __low2float(hh); x[2 * i + 1] = __high2float(hh);
-        }
     } else {
-        const float4* src = reinterpret_cast<const float4*>(reinterpret_cast<const float*>(B) + (size_t)nn * K + kk * 64) + 2 * p;
-        const float4 a0 = src[0], a1 = src[1];
-        x[0] = a0.x; x[1] = a0.y; x[2] = a0.z; x[3] = a0.w; x[4] = a1.x; x[5] = a1.y; x[6] = a1.z; x[7] = a1.w;
+        lut_ld8(B, F16, (size_t)nn * K + kk * 64, p, x);
     }
-    const float s0 = __fadd_rn(__fadd_rn(fabsf(x[0]), fabsf(x[1])), __fadd_rn(fabsf(x[2]), fabsf(x[3])));
-    const float s1 = __fadd_rn(__fadd_rn(fabsf(x[4]), fabsf(x[5])), __fadd_rn(fabsf(x[6]), fabsf(x[7])));
-    const float mx = q_half_allmax(fmaxf(s0, s1));
-    const float scales = div127(mx);
-    const float t_scales = (scales != 0.0f) ? rcp_exact(scales) : 0.0f;
-    uint32_t lo0, hi0, lo1, hi1;
-    float La, Lb;
-    q_table8<true>(x[0], x[1], x[2], x[3], t_scales, lo0, hi0, La);
-    q_table8<true>(x[4], x[5], x[6], x[7], t_scales, lo1, hi1, Lb);
-    bimg[(((size_t)kk * (Npad >> 6) + (n >> 6)) * 8 + p) * 64 + (n & 63)] = make_uint4(lo0, hi0, lo1, hi1);
+    float scales, t_scales, La, Lb;
+    lut_group_scale(LUT_X8(x), scales, t_scales);
+    const uint4 t = lut_tables2<true>(LUT_X8(x), t_scales, La, Lb);
+    bimg[(((size_t)kk * (Npad >> 6) + (n >> 6)) * 8 + p) * 64 + (n & 63)] = t;
     // sum of the 16 signed entries of this lane's two half tables, then over the 8 lanes of the act group
     int h = 0;
-    const uint32_t d[4] = {lo0, hi0, lo1, hi1};
+    const uint32_t d[4] = {t.x, t.y, t.z, t.w};
 #pragma unroll
     for (int i = 0; i < 4; ++i)
         h += (int)(int8_t)(d[i] & 0xff) + (int)(int8_t)((d[i] >> 8) & 0xff) + (int)(int8_t)((d[i] >> 16) & 0xff) + ((int)d[i] >> 24);
-    h += (int)qdpp_u<0xB1>((uint32_t)h);
-    h += (int)qdpp_u<0x4E>((uint32_t)h);
-    h += (int)qdpp_u<0x104>((uint32_t)h);
-    float va = -La, vb = -Lb;               // lut_biases, lut_ctor.cc:25-31 (summation order as in k_preprocess_pairs)
-    va = __fadd_rn(va, qdpp_f<0x4E>(va));
-    vb = __fadd_rn(vb, qdpp_f<0x4E>(vb));
-    va = __fadd_rn(va, qdpp_f<0xB1>(va));
-    vb = __fadd_rn(vb, qdpp_f<0xB1>(vb));
-    const float v = __fadd_rn(va, vb);
-    const float c1 = qdpp_f<0x104>(v);
+    h += (int)dpp_u<0xB1>((uint32_t)h);
+    h += (int)dpp_u<0x4E>((uint32_t)h);
+    h += (int)dpp_u<0x104>((uint32_t)h);
+    const float v = lut_chunk_sum(La, Lb);
+    const float c1 = lut_group_partner(v);
     if (p == 0) {
-        const float lb = __fadd_rn(__fadd_rn(0.0f, v), c1);
+        const float lb = lut_group_bias(v, c1);
         reinterpret_cast<float4*>(colv)[(size_t)kk * Npad + n] = make_float4(__fmul_rn(0.5f, scales), __fmul_rn(0.5f, lb), (float)h, lb);
     }
 }
@@ -816,7 +795,7 @@ __global__ __launch_bounds__(64 * NWV, 8 / NWV) void k_gemm_planes_us(Gemm2Args 
                 if (DUMP) a.dump[(size_t)n * Mw + o + e] = c;
                 const float t = __fmul_rn((float)c, 0.5f);
                 const float x = __fadd_rn(__fmul_rn(t, ls), hlb);
-                r[e] = __fmul_rn(x, q_ld_scale(M.SC, a.sc_f16, (o + e) / (Mw / s.m_groups)));
+                r[e] = __fmul_rn(x, ld_scale(M.SC, a.sc_f16, (o + e) / (Mw / s.m_groups)));
             }
             if (a.out_f16) {
                 const __half2 h0 = __floats2half2_rn(r[0], r[1]), h1 = __floats2half2_rn(r[2], r[3]);

@@ -15,32 +15,9 @@
 
 #include "tmac_core.h"
 #include "tmac_kernels.h"
+#include "tmac_dev.h"
 
 namespace tmac {
-
-// ---------------------------------------------------------------------------------------------
-// small helpers
-// ---------------------------------------------------------------------------------------------
-template <typename T> __device__ __forceinline__ float to_f32(T v);
-template <> __device__ __forceinline__ float to_f32<float>(float v) { return v; }
-template <> __device__ __forceinline__ float to_f32<__half>(__half v) { return __half2float(v); }
-template <typename T> __device__ __forceinline__ T from_f32(float v);
-template <> __device__ __forceinline__ float from_f32<float>(float v) { return v; }
-template <> __device__ __forceinline__ __half from_f32<__half>(float v) { return __float2half_rn(v); }
-
-__device__ __forceinline__ void store_out(void* C, int is_f16, size_t idx, float v) {
-    if (is_f16) reinterpret_cast<__half*>(C)[idx] = __float2half_rn(v);
-    else reinterpret_cast<float*>(C)[idx] = v;
-}
-
-// cvtps_epi32(round_ps(x)) + packs_epi32 + packs_epi16 (lut_ctor.cc:169-177): RNE then saturate
-__device__ __forceinline__ int rne_sat_int8(float x) {
-    const float r = rintf(x);
-    int i = (r >= -2147483648.0f && r < 2147483648.0f) ? (int)r : INT32_MIN;
-    return max(-128, min(127, i));
-}
-
-__device__ __forceinline__ float alpha_of(int p) { return p == 0 ? 0.5f : (p == 1 ? 1.0f : (p == 2 ? 2.0f : 4.0f)); }
 
 // ---------------------------------------------------------------------------------------------
 // instruction self-test: lets the test-suite check the host models in tmac_core.h against the
@@ -410,7 +387,7 @@ __global__ __launch_bounds__(256) void k_gemv_lo(GemvPtrs p, Shape s) {
             float acc = red_f[0][r][beta];
 #pragma unroll
             for (int ww = 1; ww < NW; ++ww) acc = __fadd_rn(acc, red_f[ww][r][beta]);
-            if (o < s.Mw) store_out(p.C, p.out_f16, (size_t)n * s.Mw + o, acc);
+            if (o < s.Mw) st_out(p.C, p.out_f16, (size_t)n * s.Mw + o, acc);
         }
     } else {
         // exact integer reduction, then qgemm.py:170-174 / :192-206
@@ -439,7 +416,7 @@ __global__ __launch_bounds__(256) void k_gemv_lo(GemvPtrs p, Shape s) {
                 }
                 const float v = __fadd_rn(__fmul_rn(acc, p.LS[n]), __fmul_rn(p.LB[n], 0.5f));
                 const float sc = to_f32<ST>(reinterpret_cast<const ST*>(p.SC)[o / (s.Mw / s.m_groups)]);
-                store_out(p.C, p.out_f16, (size_t)n * s.Mw + o, __fmul_rn(v, sc));
+                st_out(p.C, p.out_f16, (size_t)n * s.Mw + o, __fmul_rn(v, sc));
             }
         }
     }
@@ -471,7 +448,7 @@ __global__ void k_gemv_ref_layout(const uint8_t* __restrict__ A, const int8_t* _
             acc = (pl == 0) ? tt : __fadd_rn(acc, tt);
         }
         const float v = __fadd_rn(__fmul_rn(acc, LS[n]), __fmul_rn(LB[n], 0.5f));
-        store_out(C, out_f16, (size_t)n * s.Mw + o, __fmul_rn(v, to_f32<ST>(SC[o / (s.Mw / s.m_groups)])));
+        st_out(C, out_f16, (size_t)n * s.Mw + o, __fmul_rn(v, to_f32<ST>(SC[o / (s.Mw / s.m_groups)])));
         return;
     }
     const int ActK = TGr < s.kfactor ? TGr : s.kfactor;
@@ -527,7 +504,7 @@ __global__ void k_gemv_ref_layout(const uint8_t* __restrict__ A, const int8_t* _
     }
     float acc = __fmul_rn(cb[0], 0.5f);
     for (int pl = 1; pl < bits; ++pl) acc = __fadd_rn(acc, __fmul_rn(cb[pl], alpha_of(pl)));
-    store_out(C, out_f16, (size_t)n * s.Mw + o, acc);
+    st_out(C, out_f16, (size_t)n * s.Mw + o, acc);
 }
 
 // ---------------------------------------------------------------------------------------------

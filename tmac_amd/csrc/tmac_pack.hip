@@ -14,6 +14,7 @@
 #include <hip/hip_fp16.h>
 #include <hip/hip_runtime.h>
 
+#include "tmac_dev.h"
 #include "tmac_kernels.h"
 #include "tmac_pack.h"
 
@@ -112,13 +113,6 @@ __global__ __launch_bounds__(PACK_THREADS) void k_pack_codes_weights(const uint8
 }
 
 // ---- scales -------------------------------------------------------------------------------------------------------------------------
-template <class T> __device__ __forceinline__ float to_f32(T v);
-template <> __device__ __forceinline__ float to_f32<float>(float v) { return v; }
-template <> __device__ __forceinline__ float to_f32<__half>(__half v) { return __half2float(v); }
-template <class T> __device__ __forceinline__ T from_f32(float v);
-template <> __device__ __forceinline__ float from_f32<float>(float v) { return v; }
-template <> __device__ __forceinline__ __half from_f32<__half>(float v) { return __float2half_rn(v); }
-
 // n contiguous elements (a multiple of 16 bytes, 16-byte aligned on both sides) as 16-byte accesses
 template <class T, int N>
 __device__ __forceinline__ void load_vec(const T* src, T (&v)[N]) {

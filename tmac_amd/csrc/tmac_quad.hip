@@ -29,7 +29,7 @@ namespace tmac {
 
 // weights of (local quad lq, step st) + the lane's scales (rows beta0, beta0+1 of its unit's scale group)
 template <int BITS, bool ZP, int SM, int ACC, bool SCF16>
-__device__ __forceinline__ void load_q(QFrag<BITS>& f, const FusedArgs& a, const FusedMat& M, int lq, int st, int nst, int lane) {
+__device__ __forceinline__ void load_q(WFrag<BITS>& f, const FusedArgs& a, const FusedMat& M, int lq, int st, int nst, int lane) {
     constexpr int NJ = 8 * BITS / 8;
     constexpr int per = ZP ? 2 : 1;
     const int u = st * 64 + lane;
@@ -297,9 +297,9 @@ __global__ __launch_bounds__(FT) void k_gemv_quad(std::conditional_t<XF, FusedXf
     // ---- 2. this wave's work: quads slot, slot + stride, ...; steps h, h + WPQ, ... of each ------
     const int slot0 = blockIdx.x * IPI + w / WPQ, h = w % WPQ, stride = gridDim.x * IPI;
     constexpr int RING = (BITS <= 2) ? 4 : 2;      // weight fragments in flight per wave (register budget)
-    QFrag<BITS> f0, f1, f2, f3;
+    WFrag<BITS> f0, f1, f2, f3;
     int p_q = (h < nst) ? slot0 : total_q, p_st = h;    // prefetch cursor (a wave without steps, WPQ > nst, never issues)
-    auto issue = [&](QFrag<BITS>& f) {
+    auto issue = [&](WFrag<BITS>& f) {
         if (p_q < total_q) {
             seek(pc, p_q);
             load_q<BITS, ZP, SM, ACC, SCF16>(f, a, pc.m, p_q - pc.base, p_st, nst, lane);
@@ -333,8 +333,8 @@ __global__ __launch_bounds__(FT) void k_gemv_quad(std::conditional_t<XF, FusedXf
         // fragments issued a moment ago.
         if ((GN || a.xf_kind == 1) && a.gamma != nullptr) {
             float ss = xss;
-            ss = __fadd_rn(ss, qdpp_f<0xB1>(ss)); ss = __fadd_rn(ss, qdpp_f<0x4E>(ss));
-            ss = __fadd_rn(ss, qdpp_f<0x141>(ss)); ss = __fadd_rn(ss, qdpp_f<0x140>(ss));     // row_half_mirror, row_mirror
+            ss = __fadd_rn(ss, dpp_f<0xB1>(ss)); ss = __fadd_rn(ss, dpp_f<0x4E>(ss));
+            ss = __fadd_rn(ss, dpp_f<0x141>(ss)); ss = __fadd_rn(ss, dpp_f<0x140>(ss));     // row_half_mirror, row_mirror
             const int ssb = __builtin_bit_cast(int, ss);
             const float sw = __fadd_rn(__fadd_rn(__builtin_bit_cast(float, __builtin_amdgcn_readlane(ssb, 0)), __builtin_bit_cast(float, __builtin_amdgcn_readlane(ssb, 16))),
                                        __fadd_rn(__builtin_bit_cast(float, __builtin_amdgcn_readlane(ssb, 32)), __builtin_bit_cast(float, __builtin_amdgcn_readlane(ssb, 48))));
@@ -349,6 +349,9 @@ __global__ __launch_bounds__(FT) void k_gemv_quad(std::conditional_t<XF, FusedXf
     }
 
     // ---- 3. LUT into LDS (all FT threads) ------------------------------------------------------
+    // The constructor of tmac_lut_build.h.  In this kernel's own words stay the fp16 unpack, pass 1 of the unified-scale path with its two
+    // divisions and the act-group scale: through the shared pieces some instantiations changed schedule or register counts
+    // (profiles/r18_lut_build_refactor.txt).
     if (LUTSRC == 0) {
         const uint4* src = reinterpret_cast<const uint4*>(a.qlut_lds) + (size_t)n * 4 * a.tstride;   // image stride (k_preprocess)
 #pragma unroll
@@ -379,15 +382,14 @@ __global__ __launch_bounds__(FT) void k_gemv_quad(std::conditional_t<XF, FusedXf
                     mx = fmaxf(mx, __fadd_rn(__fadd_rn(fabsf(x[4]), fabsf(x[5])), __fadd_rn(fabsf(x[6]), fabsf(x[7]))));
                     float va = -__fadd_rn(__fadd_rn(__fadd_rn(x[0], x[1]), x[2]), x[3]);
                     float vb = -__fadd_rn(__fadd_rn(__fadd_rn(x[4], x[5]), x[6]), x[7]);
-                    va = __fadd_rn(va, qdpp_f<0x4E>(va));      // lane ^ 2: v0+v4 | v2+v6      (lut_ctor.cc:25-31)
-                    vb = __fadd_rn(vb, qdpp_f<0x4E>(vb));      //           v1+v5 | v3+v7
-                    va = __fadd_rn(va, qdpp_f<0xB1>(va));      // lane ^ 1: (v0+v4)+(v2+v6)
-                    vb = __fadd_rn(vb, qdpp_f<0xB1>(vb));      //           (v1+v5)+(v3+v7)
+                    va = __fadd_rn(va, dpp_f<0x4E>(va));      // lane ^ 2: v0+v4 | v2+v6      (lut_ctor.cc:25-31)
+                    vb = __fadd_rn(vb, dpp_f<0x4E>(vb));      //           v1+v5 | v3+v7
+                    va = __fadd_rn(va, dpp_f<0xB1>(va));      // lane ^ 1: (v0+v4)+(v2+v6)
+                    vb = __fadd_rn(vb, dpp_f<0xB1>(vb));      //           (v1+v5)+(v3+v7)
                     if ((p & 3) == 0) l_scr[NWV + (p >> 2)] = __fadd_rn(va, vb);
                 }
             }
-            mx = q_row_allmax(mx);
-            mx = q_xor_max_f(mx);
+            mx = lut_wave_max(mx);
             if (lane == 0) l_scr[w] = mx;
             __syncthreads();
             mx = l_scr[0];
@@ -428,23 +430,15 @@ __global__ __launch_bounds__(FT) void k_gemv_quad(std::conditional_t<XF, FusedXf
                 }
                 uint32_t lo0, hi0, lo1, hi1;
                 float La, Lb;
-                q_table8<ACC == 1>(x[0], x[1], x[2], x[3], t_scales, lo0, hi0, La);
-                q_table8<ACC == 1>(x[4], x[5], x[6], x[7], t_scales, lo1, hi1, Lb);
+                lut_tables2_words<ACC == 1>(LUT_X8(x), t_scales, lo0, hi0, lo1, hi1, La, Lb);
                 // tables 2p, 2p+1 = the uint4 (j4 = p & 3) of unit p >> 2
                 tab[(p & 3) * tstride + (p >> 2)] = make_uint4(lo0, hi0, lo1, hi1);
-                // lut_biases (lut_ctor.cc:25-31): per 8-table chunk ((v0+v4)+(v2+v6)) + ((v1+v5)+(v3+v7)), v_i = LUT[0] of table i
-                // = -L15; the 4 lanes of a chunk hold (v0,v1), (v2,v3), (v4,v5), (v6,v7)
-                float va = -La, vb = -Lb;
-                va = __fadd_rn(va, qdpp_f<0x4E>(va));      // lane ^ 2: v0+v4 | v2+v6
-                vb = __fadd_rn(vb, qdpp_f<0x4E>(vb));      //           v1+v5 | v3+v7
-                va = __fadd_rn(va, qdpp_f<0xB1>(va));      // lane ^ 1: (v0+v4)+(v2+v6)
-                vb = __fadd_rn(vb, qdpp_f<0xB1>(vb));      //           (v1+v5)+(v3+v7)
-                const float v = __fadd_rn(va, vb);
+                const float v = lut_chunk_sum(La, Lb);
                 if (SM != 2) {
-                    const float c1 = qdpp_f<0x104>(v);      // row_shl:4: the second chunk of the act group
+                    const float c1 = lut_group_partner(v);      // (every lane of the act group takes part)
                     if ((p & 7) == 0) {
                         l_ls[p >> 3] = __fmul_rn(LSK, scales);
-                        l_lb[p >> 3] = __fmul_rn(LSK, __fadd_rn(__fadd_rn(0.0f, v), c1));
+                        l_lb[p >> 3] = __fmul_rn(LSK, lut_group_bias(v, c1));
                     }
                 }
             }
@@ -483,7 +477,7 @@ __global__ __launch_bounds__(FT) void k_gemv_quad(std::conditional_t<XF, FusedXf
     reset_acc();
     const int beta0 = 2 * (lane & 1);
 
-    auto compute = [&](const QFrag<BITS>& f, int st, int Mw_m, int lq) {
+    auto compute = [&](const WFrag<BITS>& f, int st, int Mw_m, int lq) {
         const int u = st * 64 + lane;
         if (u >= nu) return;                 // nu is even: both lanes of a pair are valid or not
         uint32_t tb[16];
@@ -507,8 +501,8 @@ __global__ __launch_bounds__(FT) void k_gemv_quad(std::conditional_t<XF, FusedXf
 #pragma unroll
         for (int pl = 0; pl < BITS; ++pl) {
             uint32_t lo = (uint32_t)acc.a[pl], hi = (uint32_t)(acc.a[pl] >> 32);
-            lo += qdpp_u<0xB1>(lo);          // the two 8-table halves of the act group: lanes (l, l^1)
-            hi += qdpp_u<0xB1>(hi);
+            lo += dpp_u<0xB1>(lo);          // the two 8-table halves of the act group: lanes (l, l^1)
+            hi += dpp_u<0xB1>(hi);
             const uint32_t mine = (lane & 1) ? hi : lo;
 #pragma unroll
             for (int i = 0; i < 2; ++i) {
@@ -518,8 +512,8 @@ __global__ __launch_bounds__(FT) void k_gemv_quad(std::conditional_t<XF, FusedXf
                     if (o < Mw_m) a.dump[((size_t)n * Mw_m * BITS + mrow(o, pl, BITS)) * G + kk] = ps;
                 }
                 const float v = (pl == 0) ? __fmaf_rn((float)ps, ls, lb) : __fmul_rn((float)ps, ls);
-                float c = __fmaf_rn(v, qfrag_scale<ZP>(f.sraw, SCF16, i, 0), cacc[i][pl]);
-                if (ZP && pl == 0) c = __fmaf_rn(qfrag_scale<ZP>(f.sraw, SCF16, i, 1), __fmul_rn(2.0f, lb), c);
+                float c = __fmaf_rn(v, frag_scale<ZP>(f.sraw, SCF16, i, 0), cacc[i][pl]);
+                if (ZP && pl == 0) c = __fmaf_rn(frag_scale<ZP>(f.sraw, SCF16, i, 1), __fmul_rn(2.0f, lb), c);
                 cacc[i][pl] = c;
             }
         }
@@ -534,7 +528,7 @@ __global__ __launch_bounds__(FT) void k_gemv_quad(std::conditional_t<XF, FusedXf
     }
     uint32_t k3 = 0x03020100u;
     asm volatile("" : "+v"(k3));     // keep the selector constant in a VGPR (operand of v_and_or_b32)
-    auto compute_mfma = [&](const QFrag<BITS>& f, int st, int Mw_m, int lq) {
+    auto compute_mfma = [&](const WFrag<BITS>& f, int st, int Mw_m, int lq) {
         const int u = st * 64 + lane;
         uint32_t tb[16];
 #pragma unroll
@@ -618,13 +612,13 @@ __global__ __launch_bounds__(FT) void k_gemv_quad(std::conditional_t<XF, FusedXf
             float acc = 0.f;
             if (have) {
                 acc = cacc[0][0];                             // planes already combined (compute_mfma)
-                acc = __fadd_rn(acc, qdpp_f<0x124>(acc));     // lanes with the same beta: rotate by 4, 8 within the row
-                acc = __fadd_rn(acc, qdpp_f<0x128>(acc));
+                acc = __fadd_rn(acc, dpp_f<0x124>(acc));     // lanes with the same beta: rotate by 4, 8 within the row
+                acc = __fadd_rn(acc, dpp_f<0x128>(acc));
                 acc = q_xor_add_f(acc);
             }
             if (WPQ == 1) {
                 const int o = 4 * lq + lane;
-                if (have && lane < 4 && o < M.Mw) q_st_out(M.C, a.out_f16, (size_t)n * M.Mw + o, acc);
+                if (have && lane < 4 && o < M.Mw) st_out(M.C, a.out_f16, (size_t)n * M.Mw + o, acc);
             } else {
                 if (lane < 4) red[w * 4 + lane] = acc;
                 __syncthreads();
@@ -633,7 +627,7 @@ __global__ __launch_bounds__(FT) void k_gemv_quad(std::conditional_t<XF, FusedXf
 #pragma unroll
                     for (int ww = 1; ww < WPQ; ++ww) t = __fadd_rn(t, red[(w + ww) * 4 + lane]);
                     const int o = 4 * lq + lane;
-                    if (o < M.Mw) q_st_out(M.C, a.out_f16, (size_t)n * M.Mw + o, t);
+                    if (o < M.Mw) st_out(M.C, a.out_f16, (size_t)n * M.Mw + o, t);
                 }
             }
         } else if (SM != 2) {
@@ -643,10 +637,10 @@ __global__ __launch_bounds__(FT) void k_gemv_quad(std::conditional_t<XF, FusedXf
                 for (int i = 0; i < 2; ++i) {
                     float acc = __fmul_rn(cacc[i][0], 0.5f);
 #pragma unroll
-                    for (int pl = 1; pl < BITS; ++pl) acc = __fadd_rn(acc, __fmul_rn(cacc[i][pl], q_alpha(pl)));
-                    acc = __fadd_rn(acc, qdpp_f<0x4E>(acc));      // lane ^ 2
-                    acc = __fadd_rn(acc, qdpp_f<0x124>(acc));     // rotate by 4, 8 within the 16-lane row
-                    acc = __fadd_rn(acc, qdpp_f<0x128>(acc));
+                    for (int pl = 1; pl < BITS; ++pl) acc = __fadd_rn(acc, __fmul_rn(cacc[i][pl], alpha_of(pl)));
+                    acc = __fadd_rn(acc, dpp_f<0x4E>(acc));      // lane ^ 2
+                    acc = __fadd_rn(acc, dpp_f<0x124>(acc));     // rotate by 4, 8 within the 16-lane row
+                    acc = __fadd_rn(acc, dpp_f<0x128>(acc));
                     acc = q_xor_add_f(acc);
                     part[i] = acc;
                 }
@@ -654,8 +648,8 @@ __global__ __launch_bounds__(FT) void k_gemv_quad(std::conditional_t<XF, FusedXf
             if (WPQ == 1) {
                 if (have && lane < 2) {
                     const int o = 4 * lq + 2 * lane;
-                    if (o < M.Mw) q_st_out(M.C, a.out_f16, (size_t)n * M.Mw + o, part[0]);
-                    if (o + 1 < M.Mw) q_st_out(M.C, a.out_f16, (size_t)n * M.Mw + o + 1, part[1]);
+                    if (o < M.Mw) st_out(M.C, a.out_f16, (size_t)n * M.Mw + o, part[0]);
+                    if (o + 1 < M.Mw) st_out(M.C, a.out_f16, (size_t)n * M.Mw + o + 1, part[1]);
                 }
             } else {
                 if (lane < 2) { red[w * 4 + 2 * lane] = part[0]; red[w * 4 + 2 * lane + 1] = part[1]; }
@@ -665,7 +659,7 @@ __global__ __launch_bounds__(FT) void k_gemv_quad(std::conditional_t<XF, FusedXf
 #pragma unroll
                     for (int ww = 1; ww < WPQ; ++ww) t = __fadd_rn(t, red[(w + ww) * 4 + lane]);
                     const int o = 4 * lq + lane;
-                    if (o < M.Mw) q_st_out(M.C, a.out_f16, (size_t)n * M.Mw + o, t);
+                    if (o < M.Mw) st_out(M.C, a.out_f16, (size_t)n * M.Mw + o, t);
                 }
             }
         } else {
@@ -675,8 +669,8 @@ __global__ __launch_bounds__(FT) void k_gemv_quad(std::conditional_t<XF, FusedXf
             for (int pl = 0; pl < BITS; ++pl) {
                 if (ACC == 1) {       // every lane holds a partial of row lane & 3: rotate by 4, 8 within the row, then rows
                     uint32_t v = have ? (uint32_t)iacc[pl][0] : 0u;
-                    v += qdpp_u<0x124>(v);
-                    v += qdpp_u<0x128>(v);
+                    v += dpp_u<0x124>(v);
+                    v += dpp_u<0x128>(v);
                     v = q_xor_add_u(v);
                     tot[pl] = (int32_t)v;
                 } else {
@@ -708,11 +702,11 @@ __global__ __launch_bounds__(FT) void k_gemv_quad(std::conditional_t<XF, FusedXf
 #pragma unroll
                             for (int ww = 1; ww < WPQ; ++ww) cb += redi[((w + ww) * 4 + lane) * 4 + pl];
                         if (DUMP && a.dump) a.dump[(size_t)n * M.Mw * BITS + mrow(o, pl, BITS)] = cb;
-                        const float t = __fmul_rn((float)cb, q_alpha(pl));
+                        const float t = __fmul_rn((float)cb, alpha_of(pl));
                         acc = (pl == 0) ? t : __fadd_rn(acc, t);
                     }
                     const float v = __fadd_rn(__fmul_rn(acc, l_ls[0]), __fmul_rn(l_lb[0], 0.5f));
-                    q_st_out(M.C, a.out_f16, (size_t)n * M.Mw + o, __fmul_rn(v, q_ld_scale(M.SC, a.sc_f16, o / (M.Mw / s.m_groups))));
+                    st_out(M.C, a.out_f16, (size_t)n * M.Mw + o, __fmul_rn(v, ld_scale(M.SC, a.sc_f16, o / (M.Mw / s.m_groups))));
                 }
             }
         }
@@ -770,7 +764,7 @@ constexpr bool QSCF16 = TMAC_QUAD_SCF16 != 0;   // weight scales stored as fp16 
 // the two tables of pair p (8 activations, one 16-byte fp16 load) of activation row n with the packed-fp32 sequence of
 // q_table8, the act group (64 activations = 8 lanes) shares its abs-max by DPP, and the result goes straight into the
 // unit-major half-table image the one-hot GEMM stages from (same bytes as k_preprocess writes there; QLUT, scales and
-// biases bit-identical to lut_ctor.cc by the same argument as in k_gemv_quad).  k_preprocess keeps one workgroup per
+// biases bit-identical to lut_ctor.cc: the pieces of tmac_lut_build.h).  k_preprocess keeps one workgroup per
 // act group with 16 of 64 lanes building tables and writes three layouts; this one writes the image only.
 // ---------------------------------------------------------------------------------------------
 // XF (both pair builds; tmac_hip_qgemm_fused_xf_rows_dev): x is the vector transform of (row n, pair p) -- xf_rows_x8, tmac_quad_core.h --
@@ -786,53 +780,19 @@ __global__ __launch_bounds__(256) void k_preprocess_pairs(const void* __restrict
     float x[8];
     if constexpr (XF) {
         xf_rows_x8(xf_rows_arg(xa...), B, F16, K, n, p, x);
-    } else if (F16) {
-        const uint4 v = reinterpret_cast<const uint4*>(reinterpret_cast<const __half*>(B) + (size_t)n * K)[p];
-        const uint32_t r[4] = {v.x, v.y, v.z, v.w};
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            const __half2 hh = *reinterpret_cast<const __half2*>(&r[i]);
-            x[2 * i] = __low2float(hh); x[2 * i + 1] = __high2float(hh);
-        }
     } else {
-        const float4* src = reinterpret_cast<const float4*>(reinterpret_cast<const float*>(B) + (size_t)n * K) + 2 * (size_t)p;
-        const float4 a0 = src[0], a1 = src[1];
-        x[0] = a0.x; x[1] = a0.y; x[2] = a0.z; x[3] = a0.w; x[4] = a1.x; x[5] = a1.y; x[6] = a1.z; x[7] = a1.w;
+        lut_ld8(B, F16, (size_t)n * K, p, x);
     }
-    const float s0 = __fadd_rn(__fadd_rn(fabsf(x[0]), fabsf(x[1])), __fadd_rn(fabsf(x[2]), fabsf(x[3])));
-    const float s1 = __fadd_rn(__fadd_rn(fabsf(x[4]), fabsf(x[5])), __fadd_rn(fabsf(x[6]), fabsf(x[7])));
-    const float mx = q_half_allmax(fmaxf(s0, s1));
-    const float scales = div127(mx);
-    const float t_scales = (scales != 0.0f) ? rcp_exact(scales) : 0.0f;
-    uint32_t lo0, hi0, lo1, hi1;
-    float La, Lb;
-    q_table8<false>(x[0], x[1], x[2], x[3], t_scales, lo0, hi0, La);     // biased bytes, as the image holds them
-    q_table8<false>(x[4], x[5], x[6], x[7], t_scales, lo1, hi1, Lb);
-    qlut_lds[((size_t)n * 4 + (p & 3)) * tstride + (p >> 2)] = make_uint4(lo0, hi0, lo1, hi1);
-    if (ALL) {
-        // the other two layouts of the workspace (tmac_hip_preprocessor_dev serves every consumer):
-        // 16-table-segment half tables for k_gemv_lo -- tables 2p, 2p+1 are one uint4 of segment p >> 3
-        const int seg = p >> 3, j8 = p & 7;
-        *reinterpret_cast<uint4*>(qlut_dev + ((size_t)n * qdev_u4_per_row + qlut_dev_u4_index(seg, j8)) * 2) = make_uint4(lo0, hi0, lo1, hi1);
-        // and the reference's int8 [K/4][16]: entries 0..7 signed, 8..15 = -entry(15 - j) (lut_ctor.cc:152-155); on biased
-        // bytes U in [1, 255] the bytewise negation 256 - U is one word subtraction without borrows
-        const uint32_t sg = 0x80808080u, rev = 0x00010203u;
-        const uint32_t n0l = __builtin_amdgcn_perm(0u, 0x01010100u - lo0, rev), n0h = __builtin_amdgcn_perm(0u, 0x01010100u - hi0, rev);
-        const uint32_t n1l = __builtin_amdgcn_perm(0u, 0x01010100u - lo1, rev), n1h = __builtin_amdgcn_perm(0u, 0x01010100u - hi1, rev);
-        uint4* r = qlut_ref + ((size_t)n * (K / 4) + 2 * (size_t)p);
-        r[0] = make_uint4(lo0 ^ sg, hi0 ^ sg, n0h ^ sg, n0l ^ sg);
-        r[1] = make_uint4(lo1 ^ sg, hi1 ^ sg, n1h ^ sg, n1l ^ sg);
-    }
-    float va = -La, vb = -Lb;               // lut_biases, lut_ctor.cc:25-31 (see k_gemv_quad)
-    va = __fadd_rn(va, qdpp_f<0x4E>(va));
-    vb = __fadd_rn(vb, qdpp_f<0x4E>(vb));
-    va = __fadd_rn(va, qdpp_f<0xB1>(va));
-    vb = __fadd_rn(vb, qdpp_f<0xB1>(vb));
-    const float v = __fadd_rn(va, vb);
-    const float c1 = qdpp_f<0x104>(v);
+    float scales, t_scales, La, Lb;
+    lut_group_scale(LUT_X8(x), scales, t_scales);
+    const uint4 t = lut_tables2<false>(LUT_X8(x), t_scales, La, Lb);     // biased bytes, as the image holds them
+    qlut_lds[((size_t)n * 4 + (p & 3)) * tstride + (p >> 2)] = t;
+    if (ALL) lut_store_ref_dev(t, K, n, p, qlut_ref, qlut_dev, qdev_u4_per_row);      // the workspace's other two layouts (tmac_hip_preprocessor_dev serves every consumer)
+    const float v = lut_chunk_sum(La, Lb);
+    const float c1 = lut_group_partner(v);
     if ((p & 7) == 0) {
         lut_scales[(size_t)n * G + (p >> 3)] = scales;
-        lut_biases[(size_t)n * G + (p >> 3)] = __fadd_rn(__fadd_rn(0.0f, v), c1);
+        lut_biases[(size_t)n * G + (p >> 3)] = lut_group_bias(v, c1);
     }
 }
 
@@ -840,6 +800,8 @@ __global__ __launch_bounds__(256) void k_preprocess_pairs(const void* __restrict
 // activation row.  Pass 1: abs-max of the row and the 8-table chunk sums of lut_biases (neither depends on the scale);
 // then one lane walks the reference's sequential fp32 chain over the chunk sums (lut_ctor.cc:157,218) while the other
 // waves quantise their tables -- the build phase of k_gemv_quad's SM == 2 path as a kernel of its own.
+// (The load of 8 and the ALL block stay in this kernel's own words: through lut_ld8 / lut_store_ref_dev two instantiations changed their
+// instruction count, profiles/r18_lut_build_refactor.txt.)
 template <bool F16, bool ALL, int PT, bool XF = false, class... XA>
 __global__ __launch_bounds__(PT) void k_preprocess_pairs_row(const void* __restrict__ B, uint4* __restrict__ qlut_lds,
                                                                float* __restrict__ lut_scales, float* __restrict__ lut_biases,
@@ -875,26 +837,21 @@ __global__ __launch_bounds__(PT) void k_preprocess_pairs_row(const void* __restr
                 const float4 a0 = src[0], a1 = src[1];
                 x[r][0] = a0.x; x[r][1] = a0.y; x[r][2] = a0.z; x[r][3] = a0.w; x[r][4] = a1.x; x[r][5] = a1.y; x[r][6] = a1.z; x[r][7] = a1.w;
             }
-            mx = fmaxf(mx, __fadd_rn(__fadd_rn(fabsf(x[r][0]), fabsf(x[r][1])), __fadd_rn(fabsf(x[r][2]), fabsf(x[r][3]))));
-            mx = fmaxf(mx, __fadd_rn(__fadd_rn(fabsf(x[r][4]), fabsf(x[r][5])), __fadd_rn(fabsf(x[r][6]), fabsf(x[r][7]))));
-            float va = -__fadd_rn(__fadd_rn(__fadd_rn(x[r][0], x[r][1]), x[r][2]), x[r][3]);
-            float vb = -__fadd_rn(__fadd_rn(__fadd_rn(x[r][4], x[r][5]), x[r][6]), x[r][7]);
-            va = __fadd_rn(va, qdpp_f<0x4E>(va));
-            vb = __fadd_rn(vb, qdpp_f<0x4E>(vb));
-            va = __fadd_rn(va, qdpp_f<0xB1>(va));
-            vb = __fadd_rn(vb, qdpp_f<0xB1>(vb));
+            mx = fmaxf(mx, lut_abssum4(x[r][0], x[r][1], x[r][2], x[r][3]));
+            mx = fmaxf(mx, lut_abssum4(x[r][4], x[r][5], x[r][6], x[r][7]));
+            float va = lut_lut0(x[r][0], x[r][1], x[r][2], x[r][3]), vb = lut_lut0(x[r][4], x[r][5], x[r][6], x[r][7]);
+            lut_chunk_fold(va, vb);
             if ((p & 3) == 0) l_cs[p >> 2] = __fadd_rn(va, vb);
         }
     }
-    mx = q_row_allmax(mx);
-    mx = q_xor_max_f(mx);
+    mx = lut_wave_max(mx);
     if (lane == 0) l_mx[w] = mx;
     __syncthreads();
     mx = l_mx[0];
 #pragma unroll
     for (int i = 1; i < NWV; ++i) mx = fmaxf(mx, l_mx[i]);
-    const float gscale = __fdiv_rn(mx, 127.0f);
-    const float gtinv = (gscale != 0.0f) ? __fdiv_rn(1.0f, gscale) : 0.0f;
+    float gscale, gtinv;
+    lut_scale<true>(mx, gscale, gtinv);
     if (tid == PT - 64) {
         float biases = 0.0f;
         const int nc = K / 32;
@@ -908,11 +865,10 @@ __global__ __launch_bounds__(PT) void k_preprocess_pairs_row(const void* __restr
     for (int r = 0; r < NPR; ++r) {
         const int p = r * PT + tid;
         if (p < P) {
-            uint32_t lo0, hi0, lo1, hi1;
             float La, Lb;
-            q_table8<false>(x[r][0], x[r][1], x[r][2], x[r][3], gtinv, lo0, hi0, La);
-            q_table8<false>(x[r][4], x[r][5], x[r][6], x[r][7], gtinv, lo1, hi1, Lb);
-            qlut_lds[((size_t)n * 4 + (p & 3)) * tstride + (p >> 2)] = make_uint4(lo0, hi0, lo1, hi1);
+            const uint4 t = lut_tables2<false>(LUT_X8(x[r]), gtinv, La, Lb);
+            const uint32_t lo0 = t.x, hi0 = t.y, lo1 = t.z, hi1 = t.w;
+            qlut_lds[((size_t)n * 4 + (p & 3)) * tstride + (p >> 2)] = t;
             if (bimg) {  // signed half tables, [unit][pair][n]: what the plane-combined GEMM streams
                 bimg[(size_t)p * Npad + n] = make_uint4(lo0 ^ 0x80808080u, hi0 ^ 0x80808080u, lo1 ^ 0x80808080u, hi1 ^ 0x80808080u);
                 // the 16 entries are biased bytes U = entry + 128: sum of the bytes - 16 * 128

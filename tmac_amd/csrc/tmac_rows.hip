@@ -241,8 +241,8 @@ __global__ __launch_bounds__(ROWS_FT) void k_gemv_rows(RowsArgs a) {
                 float v = 0.f;
                 if (have && r < nr) {
                     v = cacc[r];
-                    v = __fadd_rn(v, qdpp_f<0x124>(v));     // lanes with the same beta: rotate by 4, 8 within the row
-                    v = __fadd_rn(v, qdpp_f<0x128>(v));
+                    v = __fadd_rn(v, dpp_f<0x124>(v));     // lanes with the same beta: rotate by 4, 8 within the row
+                    v = __fadd_rn(v, dpp_f<0x128>(v));
                     v = q_xor_add_f(v);
                 }
                 acc[r] = v;
@@ -250,7 +250,7 @@ __global__ __launch_bounds__(ROWS_FT) void k_gemv_rows(RowsArgs a) {
             if (wpq == 1) {
 #pragma unroll
                 for (int r = 0; r < R; ++r)
-                    if (have && r < nr && lane < 4 && o < M.Mw) q_st_out(M.C, a.out_f16, (size_t)(n0 + r) * M.Mw + o, acc[r]);
+                    if (have && r < nr && lane < 4 && o < M.Mw) st_out(M.C, a.out_f16, (size_t)(n0 + r) * M.Mw + o, acc[r]);
             } else {
                 if (lane < 4) {
 #pragma unroll
@@ -263,7 +263,7 @@ __global__ __launch_bounds__(ROWS_FT) void k_gemv_rows(RowsArgs a) {
                         if (r < nr) {
                             float t = red[(r * NWV + w) * 4 + lane];
                             for (int ww = 1; ww < wpq; ++ww) t = __fadd_rn(t, red[(r * NWV + w + ww) * 4 + lane]);
-                            q_st_out(M.C, a.out_f16, (size_t)(n0 + r) * M.Mw + o, t);
+                            st_out(M.C, a.out_f16, (size_t)(n0 + r) * M.Mw + o, t);
                         }
                     }
                 }
@@ -276,8 +276,8 @@ __global__ __launch_bounds__(ROWS_FT) void k_gemv_rows(RowsArgs a) {
 #pragma unroll
                 for (int pl = 0; pl < BITS; ++pl) {       // every lane holds a partial of row lane & 3: rotate by 4, 8 within the row, then rows
                     uint32_t v = (have && r < nr) ? (uint32_t)iacc[r][pl] : 0u;
-                    v += qdpp_u<0x124>(v);
-                    v += qdpp_u<0x128>(v);
+                    v += dpp_u<0x124>(v);
+                    v += dpp_u<0x128>(v);
                     v = q_xor_add_u(v);
                     tot[r][pl] = (int32_t)v;
                 }
@@ -292,7 +292,7 @@ __global__ __launch_bounds__(ROWS_FT) void k_gemv_rows(RowsArgs a) {
                 __syncthreads();
             }
             if (have && h == 0 && lane < 4 && o < M.Mw) {
-                const float wsc = q_ld_scale(M.SC, a.sc_f16, o / (M.Mw / a.s.m_groups));
+                const float wsc = ld_scale(M.SC, a.sc_f16, o / (M.Mw / a.s.m_groups));
 #pragma unroll
                 for (int r = 0; r < R; ++r) {
                     if (r < nr) {
@@ -303,11 +303,11 @@ __global__ __launch_bounds__(ROWS_FT) void k_gemv_rows(RowsArgs a) {
                             int32_t cb = tot[r][pl];
                             for (int ww = 1; ww < wpq; ++ww) cb += redi[((r * NWV + w + ww) * 4 + lane) * 4 + pl];
                             if (a.tap) a.tap[((size_t)(n0 + r) * M.Mw + o) * BITS + pl] = cb;
-                            const float t = __fmul_rn((float)cb, q_alpha(pl));
+                            const float t = __fmul_rn((float)cb, alpha_of(pl));
                             acc = (pl == 0) ? t : __fadd_rn(acc, t);
                         }
                         const float v = __fadd_rn(__fmul_rn(acc, l_ls[0]), __fmul_rn(l_ls[GP], 0.5f));
-                        q_st_out(M.C, a.out_f16, (size_t)(n0 + r) * M.Mw + o, __fmul_rn(v, wsc));
+                        st_out(M.C, a.out_f16, (size_t)(n0 + r) * M.Mw + o, __fmul_rn(v, wsc));
                     }
                 }
             }

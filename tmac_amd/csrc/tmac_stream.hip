@@ -46,7 +46,7 @@ namespace tmac {
 #if !TMAC_STREAM_QW_TU && !TMAC_STREAM_G2_TU
 // ---------------------------------------------------------------------------------------------
 // LUT images: block (x, y) builds pairs 256 x .. 256 x + 255 (= the 64 units of step x) of op y -- the build phase of k_gemv_quad /
-// k_preprocess_pairs (lut_ctor.cc:120-215,240-256) writing what k_gemv_stream's LUT buffer holds, in the STEP-MAJOR layout (round 6;
+// k_preprocess_pairs (tmac_lut_build.h) writing what k_gemv_stream's LUT buffer holds, in the STEP-MAJOR layout (round 6;
 // c_compute's IMG2): [64-unit step][4][65] uint4 of signed half tables (pair p = unit p >> 2, row p & 3), then ls / 2 and lb / 2 per act
 // group (32 per step each); zero tables / zero scales for the units between K and the end of the last step.
 // ---------------------------------------------------------------------------------------------
@@ -69,39 +69,15 @@ __global__ __launch_bounds__(256) void k_lut_images(const ChainOp* __restrict__ 
         return;
     }
     float x[8];
-    if (d.in_gran & 2) {
-        const float4* src = reinterpret_cast<const float4*>(d.in) + 2 * (size_t)p;
-        const float4 a0 = src[0], a1 = src[1];
-        x[0] = a0.x; x[1] = a0.y; x[2] = a0.z; x[3] = a0.w; x[4] = a1.x; x[5] = a1.y; x[6] = a1.z; x[7] = a1.w;
-    } else {
-        const uint4 v = reinterpret_cast<const uint4*>(d.in)[p];
-        const uint32_t r[4] = {v.x, v.y, v.z, v.w};
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            const __half2 hh = *reinterpret_cast<const __half2*>(&r[i]);
-            x[2 * i] = __low2float(hh); x[2 * i + 1] = __high2float(hh);
-        }
-    }
-    const float s0 = __fadd_rn(__fadd_rn(fabsf(x[0]), fabsf(x[1])), __fadd_rn(fabsf(x[2]), fabsf(x[3])));
-    const float s1 = __fadd_rn(__fadd_rn(fabsf(x[4]), fabsf(x[5])), __fadd_rn(fabsf(x[6]), fabsf(x[7])));
-    const float mx = q_half_allmax(fmaxf(s0, s1));
-    const float scales = div127(mx);
-    const float t_scales = (scales != 0.0f) ? rcp_exact(scales) : 0.0f;
-    uint32_t lo0, hi0, lo1, hi1;
-    float La, Lb;
-    q_table8<true>(x[0], x[1], x[2], x[3], t_scales, lo0, hi0, La);
-    q_table8<true>(x[4], x[5], x[6], x[7], t_scales, lo1, hi1, Lb);
-    *tslot = make_uint4(lo0, hi0, lo1, hi1);
-    float va = -La, vb = -Lb;               // lut_biases, lut_ctor.cc:25-31 (see k_gemv_quad)
-    va = __fadd_rn(va, qdpp_f<0x4E>(va));
-    vb = __fadd_rn(vb, qdpp_f<0x4E>(vb));
-    va = __fadd_rn(va, qdpp_f<0xB1>(va));
-    vb = __fadd_rn(vb, qdpp_f<0xB1>(vb));
-    const float v = __fadd_rn(va, vb);
-    const float c1 = qdpp_f<0x104>(v);
+    lut_ld8(d.in, (d.in_gran & 2) == 0, 0, p, x);
+    float scales, t_scales, La, Lb;
+    lut_group_scale(LUT_X8(x), scales, t_scales);
+    *tslot = lut_tables2<true>(LUT_X8(x), t_scales, La, Lb);
+    const float v = lut_chunk_sum(La, Lb);
+    const float c1 = lut_group_partner(v);
     if ((p & 7) == 0) {
         scslot[0] = __fmul_rn(0.5f, scales);
-        scslot[TMAC_IMG2_SC ? 2 : 32 * nst] = __fmul_rn(0.5f, __fadd_rn(__fadd_rn(0.0f, v), c1));
+        scslot[TMAC_IMG2_SC ? 2 : 32 * nst] = __fmul_rn(0.5f, lut_group_bias(v, c1));
     }
 }
 
@@ -120,50 +96,22 @@ __global__ __launch_bounds__(256) void k_lut_images_us(const ChainOp* __restrict
     const int tid = threadIdx.x, w = tid >> 6, lane = tid & 63;
     uint4* tab = reinterpret_cast<uint4*>(const_cast<void*>(d.img));
     float* l_us = reinterpret_cast<float*>(tab + IMG2_STEP * nst);
-    auto load8 = [&](int p, float (&x)[8]) __attribute__((always_inline)) {
-        if (d.in_gran & 2) {
-            const float4* src = reinterpret_cast<const float4*>(d.in) + 2 * (size_t)p;
-            const float4 a0 = src[0], a1 = src[1];
-            x[0] = a0.x; x[1] = a0.y; x[2] = a0.z; x[3] = a0.w; x[4] = a1.x; x[5] = a1.y; x[6] = a1.z; x[7] = a1.w;
-        } else {
-            const uint4 v = reinterpret_cast<const uint4*>(d.in)[p];
-            const uint32_t r[4] = {v.x, v.y, v.z, v.w};
-#pragma unroll
-            for (int i = 0; i < 4; ++i) {
-                const __half2 hh = *reinterpret_cast<const __half2*>(&r[i]);
-                x[2 * i] = __low2float(hh); x[2 * i + 1] = __high2float(hh);
-            }
-        }
-    };
     float mx = 0.f;
     for (int p = tid; p < P; p += 256) {        // (P % 4 == 0: the four lanes of a chunk are valid together)
         float x[8];
-        load8(p, x);
-        mx = fmaxf(mx, __fadd_rn(__fadd_rn(fabsf(x[0]), fabsf(x[1])), __fadd_rn(fabsf(x[2]), fabsf(x[3]))));
-        mx = fmaxf(mx, __fadd_rn(__fadd_rn(fabsf(x[4]), fabsf(x[5])), __fadd_rn(fabsf(x[6]), fabsf(x[7]))));
-        float va = -__fadd_rn(__fadd_rn(__fadd_rn(x[0], x[1]), x[2]), x[3]);
-        float vb = -__fadd_rn(__fadd_rn(__fadd_rn(x[4], x[5]), x[6]), x[7]);
-        va = __fadd_rn(va, qdpp_f<0x4E>(va));      // lane ^ 2: v0+v4 | v2+v6      (lut_ctor.cc:25-31)
-        vb = __fadd_rn(vb, qdpp_f<0x4E>(vb));
-        va = __fadd_rn(va, qdpp_f<0xB1>(va));      // lane ^ 1: (v0+v4)+(v2+v6)
-        vb = __fadd_rn(vb, qdpp_f<0xB1>(vb));
-        if ((p & 3) == 0) s_cs[p >> 2] = __fadd_rn(va, vb);
+        lut_ld8(d.in, (d.in_gran & 2) == 0, 0, p, x);
+        lut_row_pass1(LUT_X8(x), p, mx, s_cs);
     }
-    mx = q_row_allmax(mx);
-    mx = q_xor_max_f(mx);
+    mx = lut_wave_max(mx);
     if (lane == 0) s_mx[w] = mx;
     __syncthreads();
     mx = fmaxf(fmaxf(s_mx[0], s_mx[1]), fmaxf(s_mx[2], s_mx[3]));
-    const float gscale = div127(mx);
-    const float gtinv = (gscale != 0.0f) ? rcp_exact(gscale) : 0.0f;
+    float gscale, gtinv;
+    lut_scale(mx, gscale, gtinv);
     for (int p = tid; p < P; p += 256) {
-        float x[8];
-        load8(p, x);
-        uint32_t lo0, hi0, lo1, hi1;
-        float La, Lb;
-        q_table8<true>(x[0], x[1], x[2], x[3], gtinv, lo0, hi0, La);
-        q_table8<true>(x[4], x[5], x[6], x[7], gtinv, lo1, hi1, Lb);
-        tab[img2_index(p >> 2, p & 3)] = make_uint4(lo0, hi0, lo1, hi1);
+        float x[8], La, Lb;
+        lut_ld8(d.in, (d.in_gran & 2) == 0, 0, p, x);
+        tab[img2_index(p >> 2, p & 3)] = lut_tables2<true>(LUT_X8(x), gtinv, La, Lb);
     }
     for (int j4 = 0; j4 < 4; ++j4)
         for (int u = nu + tid; u < nst * 64; u += 256) tab[img2_index(u, j4)] = make_uint4(0u, 0u, 0u, 0u);
@@ -311,7 +259,7 @@ __global__ __launch_bounds__(STREAM_FT, MINW) TMAC_STREAM_ATTR void k_gemv_strea
                     float acc = 0.f;
 #pragma unroll
                     for (int pl = 0; pl < BITS; ++pl) {
-                        const float tp = __fmul_rn((float)cb[pl], q_alpha(pl));
+                        const float tp = __fmul_rn((float)cb[pl], alpha_of(pl));
                         acc = (pl == 0) ? tp : __fadd_rn(acc, tp);
                     }
                     const float* l_us = reinterpret_cast<const float*>(lds + (size_t)(j & 1) * a.buf_u4 + IMG2_STEP * (size_t)uni(d->nst));
@@ -524,8 +472,8 @@ __global__ __launch_bounds__(STREAM_FT, MINW) TMAC_STREAM_ATTR void k_gemv_strea
             for (int pl = 0; pl < BITS; ++pl) {
                 uint32_t v = have ? (uint32_t)iacc[pl] : 0u;
                 if constexpr (!QW) {
-                    v += qdpp_u<0x124>(v);
-                    v += qdpp_u<0x128>(v);
+                    v += dpp_u<0x124>(v);
+                    v += dpp_u<0x128>(v);
                 }
                 v = q_xor_add_u(v);
                 if (lane < RPW) redi[(wl * RPW + lane) * CHAIN_RED + pl] = (int32_t)v;
@@ -536,8 +484,8 @@ __global__ __launch_bounds__(STREAM_FT, MINW) TMAC_STREAM_ATTR void k_gemv_strea
         if (have) {
             acc = acc_in;
             if constexpr (!QW) {
-                acc = __fadd_rn(acc, qdpp_f<0x124>(acc));     // lanes with the same row: rotate by 4, 8 within the DPP row
-                acc = __fadd_rn(acc, qdpp_f<0x128>(acc));
+                acc = __fadd_rn(acc, dpp_f<0x124>(acc));     // lanes with the same row: rotate by 4, 8 within the DPP row
+                acc = __fadd_rn(acc, dpp_f<0x128>(acc));
             }
             acc = q_xor_add_f(acc);
         }

@@ -1,14 +1,17 @@
 #!/usr/bin/env python3
 """Register / scratch / LDS figures of every kernel in a build directory, read from the code objects' metadata.
 
-    tools/kernel_resources.py tmac_amd/csrc/build [--arch gfx950] [--filter k_gemv_stream]
+    tools/kernel_resources.py tmac_amd/csrc/build [--arch gfx950] [--filter k_gemv_stream] [--opcodes]
 
 One line per kernel: demangled name | VGPRs, AGPRs, SGPRs, scratch bytes per lane (private_segment_fixed_size), static LDS bytes,
 VGPR / SGPR spill counts.  Needs no GPU: it unbundles the device code object of each *.o (clang-offload-bundler) and reads its notes
 (llvm-readelf).  Two listings made from two commits can be compared with diff(1); an added template argument shows in the names.
+--opcodes adds, per kernel, the number of instructions and a short hash of the sequence of their mnemonics (llvm-objdump -d of the same
+code object, operands dropped): between two commits, diff(1) then also shows which kernels the compiler scheduled differently.
 """
 import argparse
 import glob
+import hashlib
 import os
 import re
 import shutil
@@ -21,7 +24,24 @@ KEYS = [("vgpr_count", "VGPR"), ("agpr_count", "AGPR"), ("sgpr_count", "SGPR"), 
         ("group_segment_fixed_size", "LDS"), ("vgpr_spill_count", "vspill"), ("sgpr_spill_count", "sspill")]
 
 
-def kernels_of(obj, arch, tmp):
+def opcodes_of(co):
+    """symbol -> (instruction count, hash of the mnemonic sequence) for every function of a code object"""
+    dis = subprocess.run([os.path.join(LLVM, "llvm-objdump"), "-d", "--no-show-raw-insn", co], capture_output=True, text=True).stdout
+    out, name, ops = {}, None, []
+    for line in dis.splitlines():
+        m = re.match(r"^[0-9a-f]+ <(.+)>:$", line)
+        if m:
+            if name is not None:
+                out[name] = (len(ops), hashlib.sha1(" ".join(ops).encode()).hexdigest()[:12])
+            name, ops = m.group(1), []
+        elif name is not None and line.startswith((" ", "\t")) and line.strip():
+            ops.append(line.split("//")[0].split()[0])
+    if name is not None:
+        out[name] = (len(ops), hashlib.sha1(" ".join(ops).encode()).hexdigest()[:12])
+    return out
+
+
+def kernels_of(obj, arch, tmp, opcodes=False):
     # the device code sits in the object's .hip_fatbin section as an offload bundle
     sec = subprocess.run([os.path.join(LLVM, "llvm-readelf"), "-S", "-W", obj], capture_output=True, text=True).stdout
     m = re.search(r"\.hip_fatbin\s+PROGBITS\s+[0-9a-f]+\s+([0-9a-f]+)\s+([0-9a-f]+)", sec)
@@ -50,7 +70,12 @@ def kernels_of(obj, arch, tmp):
             out.append(cur)
         if m and cur is not None:
             cur[m.group(1)] = m.group(2).strip().strip("'")
-    return [k for k in out if "name" in k]
+    out = [k for k in out if "name" in k]
+    if opcodes:
+        ops = opcodes_of(co)
+        for k in out:
+            k["insts"], k["ophash"] = ops.get(k["name"], ("?", "?"))
+    return out
 
 
 def main():
@@ -58,11 +83,13 @@ def main():
     ap.add_argument("build_dir")
     ap.add_argument("--arch", default="gfx950")
     ap.add_argument("--filter", default="", help="only kernels whose demangled name contains this")
+    ap.add_argument("--opcodes", action="store_true", help="also print each kernel's instruction count and a hash of its mnemonic sequence")
     a = ap.parse_args()
+    keys = KEYS + ([("insts", "insts"), ("ophash", "ops")] if a.opcodes else [])
     rows = []
     with tempfile.TemporaryDirectory() as tmp:
         for obj in sorted(glob.glob(os.path.join(a.build_dir, "*.o"))):
-            for k in kernels_of(obj, a.arch, tmp):
+            for k in kernels_of(obj, a.arch, tmp, a.opcodes):
                 rows.append((os.path.basename(obj), k))
     filt = shutil.which("c++filt")
     names = [k["name"] for _, k in rows]
@@ -71,7 +98,7 @@ def main():
     for (obj, k), d in zip(rows, dem):
         if a.filter and a.filter not in d:
             continue
-        lines.append(f"{obj}: {d} | " + " ".join(f"{lab} {k.get(key, '?')}" for key, lab in KEYS))
+        lines.append(f"{obj}: {d} | " + " ".join(f"{lab} {k.get(key, '?')}" for key, lab in keys))
     print("\n".join(sorted(lines)))
     return 0
 
