@@ -4,6 +4,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "tmac_launch_plan.h"
+
 namespace tmac {
 
 #ifndef TMAC_CHAIN_FT
@@ -92,37 +94,15 @@ struct ChainArgs {
                                    // than silu (xf_flags bits 8..9, epi > 1) -- the launch takes the XF instances with the gate selector (GT)
 };
 
-// one translation unit per weight width (tmac_chain.hip with -DTMAC_CHAIN_BITS=b).  sm: 0 per-group scales, 2 unified scale.
+// One translation unit per weight width (tmac_chain.hip with -DTMAC_CHAIN_BITS=b) defines and instantiates its launcher.  g2: the instances
+// with two scale groups per lane and item (tmac_chain_core.h; translation units of their own: -DTMAC_CHAIN_G2_TU=1) -- per-group scales only;
+// for launches that hold an op with scale groups of 64.  sm: 0 per-group scales, 2 unified scale.
 // resident != nullptr: no launch -- returns how many workgroups of that kernel one CU can hold with lds_bytes of LDS.
-hipError_t launch_decode_chain_b1(const ChainArgs& a, bool zp, bool sc_f16, int sm, int grid, size_t lds_bytes, hipStream_t st, int* resident);
-hipError_t launch_decode_chain_b2(const ChainArgs& a, bool zp, bool sc_f16, int sm, int grid, size_t lds_bytes, hipStream_t st, int* resident);
-hipError_t launch_decode_chain_b3(const ChainArgs& a, bool zp, bool sc_f16, int sm, int grid, size_t lds_bytes, hipStream_t st, int* resident);
-hipError_t launch_decode_chain_b4(const ChainArgs& a, bool zp, bool sc_f16, int sm, int grid, size_t lds_bytes, hipStream_t st, int* resident);
-// g2: the instances with two scale groups per lane and item (tmac_chain_core.h; translation units of their own: tmac_chain.hip with
-// -DTMAC_CHAIN_G2_TU=1) -- per-group scales only; for launches that hold an op with scale groups of 64
-hipError_t launch_decode_chain_g2_b1(const ChainArgs& a, bool zp, bool sc_f16, int sm, int grid, size_t lds_bytes, hipStream_t st, int* resident);
-hipError_t launch_decode_chain_g2_b2(const ChainArgs& a, bool zp, bool sc_f16, int sm, int grid, size_t lds_bytes, hipStream_t st, int* resident);
-hipError_t launch_decode_chain_g2_b3(const ChainArgs& a, bool zp, bool sc_f16, int sm, int grid, size_t lds_bytes, hipStream_t st, int* resident);
-hipError_t launch_decode_chain_g2_b4(const ChainArgs& a, bool zp, bool sc_f16, int sm, int grid, size_t lds_bytes, hipStream_t st, int* resident);
-inline hipError_t launch_decode_chain(const ChainArgs& a, int bits, bool zp, bool sc_f16, int sm, bool g2, int grid, size_t lds_bytes, hipStream_t st,
-                                      int* resident = nullptr) {
-    if (g2) {
-        switch (bits) {
-            case 1: return launch_decode_chain_g2_b1(a, zp, sc_f16, sm, grid, lds_bytes, st, resident);
-            case 2: return launch_decode_chain_g2_b2(a, zp, sc_f16, sm, grid, lds_bytes, st, resident);
-            case 3: return launch_decode_chain_g2_b3(a, zp, sc_f16, sm, grid, lds_bytes, st, resident);
-            case 4: return launch_decode_chain_g2_b4(a, zp, sc_f16, sm, grid, lds_bytes, st, resident);
-            default: return hipErrorInvalidValue;
-        }
-    }
-    switch (bits) {
-        case 1: return launch_decode_chain_b1(a, zp, sc_f16, sm, grid, lds_bytes, st, resident);
-        case 2: return launch_decode_chain_b2(a, zp, sc_f16, sm, grid, lds_bytes, st, resident);
-        case 3: return launch_decode_chain_b3(a, zp, sc_f16, sm, grid, lds_bytes, st, resident);
-        case 4: return launch_decode_chain_b4(a, zp, sc_f16, sm, grid, lds_bytes, st, resident);
-        default: return hipErrorInvalidValue;
-    }
-}
+template <int BITS, bool G2>
+hipError_t launch_decode_chain_unit(const ChainArgs& a, bool zp, bool sc_f16, int sm, int grid, size_t lds_bytes, hipStream_t st, int* resident);
+// picks the unit (tmac_launch.cpp: out of the units' sight, or each would instantiate every unit's kernels)
+hipError_t launch_decode_chain(const ChainArgs& a, int bits, bool zp, bool sc_f16, int sm, bool g2, int grid, size_t lds_bytes, hipStream_t st,
+                               int* resident = nullptr);
 // LDS: two LUT buffers of buf_u4 uint4 each ([4][tstride] half tables + the act groups' scales / biases, or the unified-scale
 // scratch), the split-quad reduction buffer, the op descriptors, the transforms' scratch and carry
 inline int chain_buf_u4(int K) {
@@ -191,7 +171,10 @@ inline size_t stream_lds_bytes(int buf_u4, int nops, bool qw = false) {
     return b;
 }
 hipError_t launch_lut_images(const ChainOp* d_ops, int nops, int max_nst, int sm, bool sc_f16, hipStream_t st);
-// g2: as launch_decode_chain's (translation units tmac_stream.hip with -DTMAC_STREAM_G2_TU=1, both forms)
+// Four translation units (tmac_stream.hip: the quarter-walk form with -DTMAC_STREAM_QW_TU=1; g2 as launch_decode_chain's, both forms, with
+// -DTMAC_STREAM_G2_TU=1), each defines and instantiates its launcher
+template <bool QW, bool G2>
+hipError_t launch_gemv_stream_unit(const StreamArgs& a, int bits, bool zp, bool sc_f16, int sm, int grid, size_t lds_bytes, hipStream_t st);
 hipError_t launch_gemv_stream(const StreamArgs& a, int bits, bool zp, bool sc_f16, int sm, bool qw, bool g2, int grid, size_t lds_bytes, hipStream_t st);
 
 }  // namespace tmac

@@ -25,6 +25,7 @@
 #include <stdint.h>
 
 #include "tmac_chain_core.h"
+#include "tmac_select.h"
 
 namespace tmac {
 
@@ -828,55 +829,31 @@ __global__ __launch_bounds__(CHAIN_FT) void k_decode_chain(ChainArgs a) {
 #if !defined(TMAC_CHAIN_BITS)
 #error "compile with -DTMAC_CHAIN_BITS=1..4 (one translation unit per weight width keeps the build parallel)"
 #endif
-constexpr int CB = TMAC_CHAIN_BITS;
-
 // one translation unit per weight width and flavour: -DTMAC_CHAIN_G2_TU=1 holds the G2 instances (per-group scales only)
 #ifndef TMAC_CHAIN_G2_TU
 #define TMAC_CHAIN_G2_TU 0
 #endif
-constexpr bool CG2 = TMAC_CHAIN_G2_TU != 0;
 
-template <bool ZP, bool SCF16, int SM, bool XF, bool TAP, bool GT = false>
-static hipError_t chain_launch_x(const ChainArgs& a, int grid, size_t lds_bytes, hipStream_t st, int* resident) {
-    if constexpr (CG2 && SM != 0) return hipErrorInvalidValue;      // (unified scales have one scale per matrix: no G2 instance)
-    else {
-    auto* kern = &k_decode_chain<CB, ZP, SCF16, SM, XF, TAP, CG2, GT>;
-    if (lds_bytes > 64 * 1024) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);
-        if (e != hipSuccess) return e;
-    }
-    if (resident)       // query only: workgroups of this kernel one CU can hold (the chain needs >= 1 on EVERY CU at once)
-        return hipOccupancyMaxActiveBlocksPerMultiprocessor(resident, reinterpret_cast<const void*>(kern), CHAIN_FT, lds_bytes);
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(CHAIN_FT), lds_bytes, st, a);
-    return hipGetLastError();
-    }
+// This unit's launcher (declared in tmac_chain.h).  The instantiation: by the scale flavour, and XF -- some op carries a transform; TAP --
+// the parity tap, whose instance carries the transforms too; GT -- a GLU with a gate other than silu.  chain_inst_exists
+// (tmac_launch_plan.h) says which exist.
+template <int BITS, bool G2>
+hipError_t launch_decode_chain_unit(const ChainArgs& a, bool zp, bool sc_f16, int sm, int grid, size_t lds_bytes, hipStream_t st, int* resident) {
+    if (a.nops < 1 || grid < 1) return hipErrorInvalidValue;
+    const bool gt = a.gates != 0, tap = a.tap != nullptr, xf = gt || tap || a.xforms;
+    return sel_int<0, 2>(sm, [&](auto SM) { return sel_bool(sm == 0 && zp, [&](auto ZP) { return sel_bool(sc_f16, [&](auto SCF16) {
+        return sel_bool(xf, [&](auto XF) { return sel_bool(tap, [&](auto TAP) { return sel_bool(gt, [&](auto GT) {
+            if constexpr (!chain_inst_exists(ZP, SM, XF, TAP, G2, GT)) return hipErrorInvalidValue;
+            else {
+                auto* kern = &k_decode_chain<BITS, ZP, SCF16, SM, XF, TAP, G2, GT>;
+                if (!resident) return launch_lds(kern, dim3(grid), dim3(CHAIN_FT), lds_bytes, st, a);
+                // query only: workgroups of this kernel one CU can hold (the chain needs >= 1 on EVERY CU at once)
+                const hipError_t e = allow_lds(kern, lds_bytes);
+                return e != hipSuccess ? e : hipOccupancyMaxActiveBlocksPerMultiprocessor(resident, reinterpret_cast<const void*>(kern), CHAIN_FT, lds_bytes);
+            }
+        }); }); });
+    }); }); });
 }
-
-template <bool ZP, bool SCF16, int SM>
-static hipError_t chain_launch_one(const ChainArgs& a, int grid, size_t lds_bytes, hipStream_t st, int* resident) {
-    if (a.gates)       // a GLU with a gate other than silu: the XF instances with the selector
-        return a.tap ? chain_launch_x<ZP, SCF16, SM, true, true, true>(a, grid, lds_bytes, st, resident) : chain_launch_x<ZP, SCF16, SM, true, false, true>(a, grid, lds_bytes, st, resident);
-    if (a.tap) return chain_launch_x<ZP, SCF16, SM, true, true>(a, grid, lds_bytes, st, resident);      // (the tap's instance carries the extensions too)
-    return a.xforms ? chain_launch_x<ZP, SCF16, SM, true, false>(a, grid, lds_bytes, st, resident) : chain_launch_x<ZP, SCF16, SM, false, false>(a, grid, lds_bytes, st, resident);
-}
-
-#define TMAC_CHAIN_LAUNCHER(NAME)                                                                                               \
-    hipError_t NAME(const ChainArgs& a, bool zp, bool sc_f16, int sm, int grid, size_t lds_bytes, hipStream_t st, int* resident) { \
-        if (a.nops < 1 || grid < 1) return hipErrorInvalidValue;                                                                  \
-        if (sm == 2) return sc_f16 ? chain_launch_one<false, true, 2>(a, grid, lds_bytes, st, resident)                          \
-                                   : chain_launch_one<false, false, 2>(a, grid, lds_bytes, st, resident);                        \
-        if (sm != 0) return hipErrorInvalidValue;                                                                                 \
-        if (zp) return sc_f16 ? chain_launch_one<true, true, 0>(a, grid, lds_bytes, st, resident)                                \
-                              : chain_launch_one<true, false, 0>(a, grid, lds_bytes, st, resident);                              \
-        return sc_f16 ? chain_launch_one<false, true, 0>(a, grid, lds_bytes, st, resident)                                       \
-                      : chain_launch_one<false, false, 0>(a, grid, lds_bytes, st, resident);                                     \
-    }
-#if TMAC_CHAIN_G2_TU
-#define TMAC_CHAIN_ENTRY_(b) launch_decode_chain_g2_b##b
-#else
-#define TMAC_CHAIN_ENTRY_(b) launch_decode_chain_b##b
-#endif
-#define TMAC_CHAIN_ENTRY(b) TMAC_CHAIN_ENTRY_(b)
-TMAC_CHAIN_LAUNCHER(TMAC_CHAIN_ENTRY(TMAC_CHAIN_BITS))
+template hipError_t launch_decode_chain_unit<TMAC_CHAIN_BITS, TMAC_CHAIN_G2_TU != 0>(const ChainArgs&, bool, bool, int, int, size_t, hipStream_t, int*);
 
 }  // namespace tmac

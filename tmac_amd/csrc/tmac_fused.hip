@@ -507,24 +507,6 @@ __global__ __launch_bounds__(FT) void k_gemv_fused(FusedArgs a) {
 }
 
 // ---------------------------------------------------------------------------------------------
-bool gemv_fused_supported(const Shape& s) {
-    if (s.bits < 1 || s.bits > 4 || s.K % 64 != 0 || s.K > 16384) return false;
-    if (s.m_groups >= 1) return s.ags == s.K && s.Mw % s.m_groups == 0;
-    const int gu = s.gs / 32;   // scale group in units; must be a power of two (shift instead of divide)
-    return s.ags == 64 && s.gs >= 64 && s.gs % 64 == 0 && s.K % s.gs == 0 && (gu & (gu - 1)) == 0;
-}
-
-void fused_precompute(FusedArgs& a) {
-    const Shape& s = a.s;
-    a.nu = s.K / 32;
-    a.nsb = (a.nu + KL - 1) / KL;
-    a.tstride = ((a.nu + 15) & ~15) + 1;
-    a.G = s.K / s.ags;
-    a.nsg = s.gs > 0 ? s.K / s.gs : 1;
-    a.gs_shift = 0;
-    if (s.gs > 0) for (int g = s.gs / 32; g > 1; g >>= 1) ++a.gs_shift;
-}
-
 size_t fused_lds_bytes(const Shape& s) {
     const int nu = s.K / 32, nu_pad = (nu + 15) & ~15, G = s.K / s.ags;
     return (size_t)4 * (nu_pad + 1) * 16 + sizeof(float) * (2 * G + 2 * FW * RL * 4 * 4 + FW + s.K / 32);

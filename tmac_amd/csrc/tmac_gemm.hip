@@ -32,6 +32,7 @@
 
 #include "tmac_core.h"
 #include "tmac_kernels.h"
+#include "tmac_select.h"
 #include "tmac_dev.h"
 
 namespace tmac {
@@ -343,17 +344,14 @@ hipError_t launch_gemm_onehot(const GemmArgs& a_in, hipStream_t st) {
     const bool narrow = (long)gx * ((a.N + 63) / 64) < 2 * 256 && a.N > 32;
     const int ncols = narrow ? 32 : 64;
     dim3 g(gx, (a.N + ncols - 1) / ncols), b(64 * GWV);
-#define GL2(B, Z, D, U) do { if (narrow) hipLaunchKernelGGL((k_gemm_onehot<B, Z, D, 2, 8, U>), g, b, 0, st, a); \
-                             else hipLaunchKernelGGL((k_gemm_onehot<B, Z, D, 4, 4, U>), g, b, 0, st, a); } while (0)
-#define GL(B, Z) do { if (a.dump) GL2(B, Z, true, false); else GL2(B, Z, false, false); } while (0)
-    if (a.s.m_groups >= 1) {
-        if (bits == 2) { if (a.dump) GL2(2, false, true, true); else GL2(2, false, false, true); }
-        else { if (a.dump) GL2(4, false, true, true); else GL2(4, false, false, true); }
-    } else if (bits == 2) { if (a.s.zero_point) GL(2, true); else GL(2, false); }
-    else { if (a.s.zero_point) GL(4, true); else GL(4, false); }
-#undef GL
-#undef GL2
-    return hipGetLastError();
+    // k_gemm_onehot<BITS, ZP, DUMP, GNT, GCH, US>: 2- and 4-bit weights; a unified scale (US) has no zero points
+    const bool us = a.s.m_groups >= 1;
+    return sel_int<2, 4>(bits, [&](auto BITS) { return sel_bool(us, [&](auto US) { return sel_bool(!us && a.s.zero_point, [&](auto ZP) {
+        return sel_bool(a.dump != nullptr, [&](auto DUMP) { return sel_bool(narrow, [&](auto NARROW) {
+            if constexpr (US && ZP) return hipErrorInvalidValue;
+            else return launch_lds(k_gemm_onehot<BITS, ZP, DUMP, NARROW ? 2 : 4, NARROW ? 8 : 4, US>, g, b, 0, st, a);
+        }); });
+    }); }); });
 }
 
 }  // namespace tmac

@@ -45,6 +45,7 @@
 
 #include "tmac_quad_core.h"
 #include "tmac_kernels.h"
+#include "tmac_select.h"
 
 namespace tmac {
 
@@ -102,17 +103,12 @@ __global__ __launch_bounds__(256) void k_lut_image(const void* __restrict__ B, u
 hipError_t launch_lut_image(const void* B, int act_f16, void* bimg, float* colv, int K, int N, int Npad, hipStream_t st, const XfRowsGateArgs* xf) {
     if (K % 64 != 0 || N < 1 || Npad < N || Npad % 64 != 0) return hipErrorInvalidValue;
     dim3 g(Npad / 32, K / 64), b(256);
-    if (xf) {
-        // silu: the instantiations on the plain block; another gate: those on the block that carries it
-#define LIX(F, T) hipLaunchKernelGGL((k_lut_image<F, true, T>), g, b, 0, st, B, (uint4*)bimg, colv, K, N, Npad, static_cast<const T&>(*xf))
-        if (xf->gate == XF_GATE_SILU) { if (act_f16) LIX(true, XfRowsArgs); else LIX(false, XfRowsArgs); }
-        else { if (act_f16) LIX(true, XfRowsGateArgs); else LIX(false, XfRowsGateArgs); }
-#undef LIX
-        return hipGetLastError();
-    }
-    if (act_f16) hipLaunchKernelGGL((k_lut_image<true>), g, b, 0, st, B, (uint4*)bimg, colv, K, N, Npad);
-    else hipLaunchKernelGGL((k_lut_image<false>), g, b, 0, st, B, (uint4*)bimg, colv, K, N, Npad);
-    return hipGetLastError();
+    return sel_bool(act_f16 != 0, [&](auto F16) {
+        if (xf) return sel_xf_block(*xf, [&](const auto& blk) {
+            return launch_lds(k_lut_image<F16.value, true, std::decay_t<decltype(blk)>>, g, b, 0, st, B, (uint4*)bimg, colv, K, N, Npad, blk);
+        });
+        return launch_lds(k_lut_image<F16.value>, g, b, 0, st, B, (uint4*)bimg, colv, K, N, Npad);
+    });
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -851,39 +847,17 @@ hipError_t launch_gemm_planes(const Gemm2Args& a_in, hipStream_t st) {
     dim3 g(((gx + 7) & ~7) * a.gy), b(64 * nwv);
     const bool us = a.s.m_groups >= 1;
     const int lds_bytes = nwv == 8 ? (us ? PFormU<8>::LDS_BYTES : PForm<8>::LDS_BYTES) : (us ? PFormU<4>::LDS_BYTES : PForm<4>::LDS_BYTES);
-#define PLAUNCH(KERNEL) do { \
-        static bool attr_set = false; \
-        if (!attr_set) { \
-            hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&KERNEL), hipFuncAttributeMaxDynamicSharedMemorySize, lds_bytes); \
-            if (e != hipSuccess) return e; \
-            attr_set = true; \
-        } \
-        hipLaunchKernelGGL((KERNEL), g, b, lds_bytes, st, a); } while (0)
-#define PLW(...) do { if (nwv == 8) PLAUNCH((__VA_ARGS__, 8>)); else PLAUNCH((__VA_ARGS__, 4>)); } while (0)
-    if (a.s.m_groups >= 1) {
-#define PLU(B) do { if (a.dump) PLW(k_gemm_planes_us<B, true); else PLW(k_gemm_planes_us<B, false); } while (0)
-        switch (a.s.bits) {
-            case 1: PLU(1); break;
-            case 2: PLU(2); break;
-            case 3: PLU(3); break;
-            default: PLU(4); break;
+    // dynamic LDS above 64 KB is allowed per kernel, once (an instantiation's footprint never changes)
+    return sel_int<1, 2, 3, 4>(a.s.bits, [&](auto BITS) { return sel_bool(a.dump != nullptr, [&](auto DUMP) { return sel_int<4, 8>(nwv, [&](auto NWV) {
+        if (us) {
+            static size_t allowed = 0;
+            return launch_lds_once(allowed, lds_bytes, k_gemm_planes_us<BITS, DUMP, NWV>, g, b, lds_bytes, st, a);
         }
-#undef PLU
-        return hipGetLastError();
-    }
-#define PL3(B, Z, D) do { if (a.sc_f16) PLW(k_gemm_planes<B, Z, D, true); else PLW(k_gemm_planes<B, Z, D, false); } while (0)
-#define PL2(B, Z) do { if (a.dump) PL3(B, Z, true); else PL3(B, Z, false); } while (0)
-    switch (a.s.bits) {
-        case 1: if (a.s.zero_point) PL2(1, true); else PL2(1, false); break;
-        case 2: if (a.s.zero_point) PL2(2, true); else PL2(2, false); break;
-        case 3: if (a.s.zero_point) PL2(3, true); else PL2(3, false); break;
-        default: if (a.s.zero_point) PL2(4, true); else PL2(4, false); break;
-    }
-#undef PL2
-#undef PL3
-#undef PLW
-#undef PLAUNCH
-    return hipGetLastError();
+        return sel_bool(a.s.zero_point != 0, [&](auto ZP) { return sel_bool(a.sc_f16 != 0, [&](auto SCF16) {
+            static size_t allowed = 0;
+            return launch_lds_once(allowed, lds_bytes, k_gemm_planes<BITS, ZP, DUMP, SCF16, NWV>, g, b, lds_bytes, st, a);
+        }); });
+    }); }); });
 }
 
 }  // namespace tmac

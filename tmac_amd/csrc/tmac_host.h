@@ -7,6 +7,10 @@
 //   tmac_pack_host.cpp   device-side packing: GPTQ tensors / plain codes -> reference blob (tmac_pack.hip) -> register_impl
 //   tmac_workspace.cpp   LUT workspace + the preprocessor entry point
 //   tmac_xform.cpp       the field rules of tmac_hip_xform: one resolver for every transform site (tmac_xform.h: no HIP, builds with plain g++)
+//   tmac_launch_plan.cpp launch planning of k_gemv_quad / k_gemv_rows and what the fused kernels support: pure functions that fill a plan or refuse
+//                        (tmac_launch_plan.h: also the instantiation policy of every kernel family as constexpr predicates; no HIP, plain g++)
+//   tmac_launch.cpp      launch_gemv_quad(_xf) / launch_gemv_rows / launch_decode_chain / launch_gemv_stream: plan, pick the translation unit of
+//                        the call's width or form; the unit selects the instantiation (tmac_select.h) and launches
 //   tmac_dispatch.cpp    qgemm_lut dispatch (a call is planned -- enum Route -- then launched), the fused entry point, parity taps
 //   tmac_tuner.cpp       launch-configuration tuner of the decode kernel
 //   tmac_chain_host.cpp  recording and building the persistent decode chain (chain_build and its stages, the stream schedule)

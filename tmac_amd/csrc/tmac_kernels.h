@@ -4,6 +4,7 @@
 #include <stdint.h>
 
 #include "tmac_layout.h"
+#include "tmac_launch_plan.h"      // what the fused kernels support, and how a launch is planned (plain C++)
 
 namespace tmac {
 
@@ -43,7 +44,7 @@ struct FusedArgs {
     unsigned long long* stamps; // optional s_memtime phase stamps [blocks][8] (debug/profiling)
     float* lut_tap;          // optional: block 0 writes [N][2][G] LUT scales | biases it built (parity tap)
     int acc_mfma;            // 1: v_mfma_i32_16x16x64_i8 accumulate, 0: v_mqsad_pk_u16_u8 (default: measured faster, profiles/)
-    int nu, nsb, tstride, G, nsg, gs_shift;   // filled by launch_gemv_fused (host-side divides)
+    int nu, nsb, tstride, G, nsg, gs_shift;   // filled by the launchers (fused_precompute, tmac_launch_plan.h: host-side divides)
 };
 
 // k_gemv_quad's XF instantiations (tmac_hip_qgemm_fused_xf_dev): the N = 1 call plus a vector transform of its activations, applied
@@ -77,6 +78,9 @@ struct XfRowsArgs {
 struct XfRowsGateArgs : XfRowsArgs {
     int gate;                // 0 silu | 1 relu^2 | 2 tanh-GELU (tmac_quad_core.h XF_GATE_*)
 };
+// the launchers' selector of the two: f(the block the call's instantiation takes)
+template <class F>
+inline hipError_t sel_xf_block(const XfRowsGateArgs& xf, F&& f) { return xf.gate == 0 ? f(static_cast<const XfRowsArgs&>(xf)) : f(xf); }
 
 // one-hot MFMA GEMM for N > 1 activation rows (tmac_gemm.hip); weights in the QUAD layout; up to 4 matrices that share
 // K, the quantisation config and the LUT in one launch
@@ -161,7 +165,7 @@ struct IpcGatherArgs {
 };
 hipError_t launch_ipc_allgather(const IpcGatherArgs& a, hipStream_t st);
 hipError_t launch_qlut_ref_to_dev(const int8_t* qlut_ref, void* qlut_dev, void* qlut_lds, int K, int N, size_t qdev_u4_per_row, hipStream_t st);
-// pair-wise LUT build (tmac_quad.hip; ags = 64): the half-table image + LUT scales/biases, and -- when qlut_ref / qlut_dev are
+// pair-wise LUT build (tmac_prefill_lut.hip; ags = 64): the half-table image + LUT scales/biases, and -- when qlut_ref / qlut_dev are
 // given (both or neither) -- the other two layouts of the workspace as well
 hipError_t launch_preprocess_pairs(const void* B, int act_f16, void* qlut_lds, float* lut_scales, float* lut_biases, int K, int N,
                                    int8_t* qlut_ref, void* qlut_dev, size_t qdev_u4_per_row, hipStream_t st, const XfRowsGateArgs* xf = nullptr);
@@ -186,18 +190,20 @@ bool gemm_planes_supported(const Shape& s);
 hipError_t launch_lut_image(const void* B, int act_f16, void* bimg, float* colv, int K, int N, int Npad, hipStream_t st, const XfRowsGateArgs* xf = nullptr);
 hipError_t launch_gemm_planes(const Gemm2Args& a, hipStream_t st);
 // fused kernel (tmac_fused.hip)
-bool gemv_fused_supported(const Shape& s);
 size_t qlut_lds_u4(int K);   // uint4 per activation row of the LDS-image LUT
 hipError_t launch_gemv_fused(const FusedArgs& a, int N, bool build_lut, hipStream_t st);
-// quad kernel (tmac_quad.hip): a.m[i].nb_end = cumulative ROW QUAD counts; force_ft/force_wpq 0 = heuristic
-bool gemv_quad_supported(const Shape& s);
+// quad kernel (tmac_quad.hip, one translation unit per width and scale dtype; the entry points: tmac_launch.cpp): a.m[i].nb_end =
+// cumulative ROW QUAD counts; force_ft/force_wpq 0 = heuristic
 hipError_t launch_gemv_quad(const FusedArgs& a, int N, bool build_lut, int force_ft, int force_wpq, hipStream_t st);
 // The same kernel with a vector transform in front of its table build (N = 1, LUT built in-kernel, MFMA accumulate).  The XF
-// instantiations cover a subset of the launch configurations (quad_xf_covered, tmac_quad.hip).  ft / wpq: 0 = heuristic; strict: the
+// instantiations cover a subset of the launch configurations (quad_xf_covered, tmac_launch_plan.h).  ft / wpq: 0 = heuristic; strict: the
 // configuration was forced by the caller and must be covered as it is (hipErrorInvalidValue otherwise) -- else it falls back to the
 // nearest covered one.
-constexpr int QUAD_XF_MAX_K = 24576;
 hipError_t launch_gemv_quad_xf(const FusedXfArgs& a, int ft, int wpq, bool strict, hipStream_t st);
+// the launcher of one translation unit of tmac_quad.hip (defined and instantiated there for its BITS, SCF16 and both argument blocks): the
+// instantiation the plan names; a: precomputed (fused_precompute)
+template <int BITS, bool SCF16, class Args>
+hipError_t launch_gemv_quad_unit(const Args& a, const QuadPlan& p, int N, hipStream_t st);
 // rows kernel (tmac_rows.hip): 2-8 activation rows per weight pass on QUAD-layout weights, tables copied from the half-table image
 struct RowsArgs {
     FusedMat m[4];           // nb_end = cumulative ROW QUAD counts (fill_fused_args)
@@ -214,15 +220,12 @@ struct RowsArgs {
     int wpq;                 // waves per row quad (1, 2, 4): fixed by the shape alone
     int n_base, rows_per_group;   // rows of workgroup row y: n_base + y * rows_per_group ..., min(R, N - first) of them live
 };
-// The row groups of N rows (pure): r_fit = largest of 8 / 4 / 2 whose LDS footprint fits 160 KiB (0: none); every group but the last
-// holds r_fit rows (capacity r_fit), the last the remainder in the smallest capacity of 2 / 4 / 8 that takes it.
-struct RowsPlan { int r_fit, ngroups, cap_last, live_last; size_t lds_bytes; };   // lds_bytes: of a capacity-r_fit workgroup
-constexpr size_t ROWS_LDS_MAX = 163840;
-size_t rows_lds_bytes(int K, int R);
-bool rows_plan(int K, int N, RowsPlan& p);       // false: K % 64, N < 1, or not even two rows fit
-bool gemv_rows_supported(const Shape& s);
+// (the row groups of N rows, the waves per quad and the launches: rows_launch_plan, tmac_launch_plan.h)
 // *launches (optional) grows by the number of k_gemv_rows launches made (one for the full groups, one for a last group of another capacity)
 hipError_t launch_gemv_rows(const RowsArgs& a, hipStream_t st, int* launches);
+// the launcher of one translation unit of tmac_rows.hip (defined and instantiated there for its BITS): one planned launch
+template <int BITS>
+hipError_t launch_gemv_rows_unit(const RowsArgs& a, const RowsLaunch& l, hipStream_t st);
 // returns hipErrorInvalidValue when the variant does not cover the configuration
 hipError_t launch_gemv(const GemvArgs& a, Variant v, hipStream_t st);
 bool gemv_lo_supported(const Shape& s);

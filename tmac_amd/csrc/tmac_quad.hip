@@ -23,6 +23,7 @@
 #include "tmac_kernels.h"
 #include "tmac_fastdiv.h"
 #include "tmac_quad_core.h"
+#include "tmac_select.h"
 
 namespace tmac {
 
@@ -758,504 +759,41 @@ q_done:
 #endif
 constexpr bool QSCF16 = TMAC_QUAD_SCF16 != 0;   // weight scales stored as fp16 (1) / fp32 (0): a kernel template parameter
 
-#if TMAC_QUAD_BITS == 2 && TMAC_QUAD_SCF16 == 0
-// ---------------------------------------------------------------------------------------------
-// Prefill LUT build for the fused entry point: the quad kernel's build phase as a kernel of its own.  One lane builds
-// the two tables of pair p (8 activations, one 16-byte fp16 load) of activation row n with the packed-fp32 sequence of
-// q_table8, the act group (64 activations = 8 lanes) shares its abs-max by DPP, and the result goes straight into the
-// unit-major half-table image the one-hot GEMM stages from (same bytes as k_preprocess writes there; QLUT, scales and
-// biases bit-identical to lut_ctor.cc: the pieces of tmac_lut_build.h).  k_preprocess keeps one workgroup per
-// act group with 16 of 64 lanes building tables and writes three layouts; this one writes the image only.
-// ---------------------------------------------------------------------------------------------
-// XF (both pair builds; tmac_hip_qgemm_fused_xf_rows_dev): x is the vector transform of (row n, pair p) -- xf_rows_x8, tmac_quad_core.h --
-// and the kernel takes an XfRowsArgs behind its own arguments; off, there is no such argument and the code is what it was.
-template <bool F16, bool ALL, bool XF = false, class... XA>
-__global__ __launch_bounds__(256) void k_preprocess_pairs(const void* __restrict__ B, uint4* __restrict__ qlut_lds,
-                                                          float* __restrict__ lut_scales, float* __restrict__ lut_biases,
-                                                          int K, int tstride, uint4* __restrict__ qlut_ref,
-                                                          uint2* __restrict__ qlut_dev, size_t qdev_u4_per_row, XA... xa) {
-    const int P = K / 8, G = K / 64, n = blockIdx.y;
-    const int p = blockIdx.x * 256 + threadIdx.x;
-    if (p >= P) return;                     // P % 8 == 0: the 8 lanes of an act group leave together
-    float x[8];
-    if constexpr (XF) {
-        xf_rows_x8(xf_rows_arg(xa...), B, F16, K, n, p, x);
-    } else {
-        lut_ld8(B, F16, (size_t)n * K, p, x);
-    }
-    float scales, t_scales, La, Lb;
-    lut_group_scale(LUT_X8(x), scales, t_scales);
-    const uint4 t = lut_tables2<false>(LUT_X8(x), t_scales, La, Lb);     // biased bytes, as the image holds them
-    qlut_lds[((size_t)n * 4 + (p & 3)) * tstride + (p >> 2)] = t;
-    if (ALL) lut_store_ref_dev(t, K, n, p, qlut_ref, qlut_dev, qdev_u4_per_row);      // the workspace's other two layouts (tmac_hip_preprocessor_dev serves every consumer)
-    const float v = lut_chunk_sum(La, Lb);
-    const float c1 = lut_group_partner(v);
-    if ((p & 7) == 0) {
-        lut_scales[(size_t)n * G + (p >> 3)] = scales;
-        lut_biases[(size_t)n * G + (p >> 3)] = lut_group_bias(v, c1);
-    }
-}
-
-// The same for one act group per row (act_group_size = K, the unified-scale / BitNet flavour): a workgroup owns an
-// activation row.  Pass 1: abs-max of the row and the 8-table chunk sums of lut_biases (neither depends on the scale);
-// then one lane walks the reference's sequential fp32 chain over the chunk sums (lut_ctor.cc:157,218) while the other
-// waves quantise their tables -- the build phase of k_gemv_quad's SM == 2 path as a kernel of its own.
-// (The load of 8 and the ALL block stay in this kernel's own words: through lut_ld8 / lut_store_ref_dev two instantiations changed their
-// instruction count, profiles/r18_lut_build_refactor.txt.)
-template <bool F16, bool ALL, int PT, bool XF = false, class... XA>
-__global__ __launch_bounds__(PT) void k_preprocess_pairs_row(const void* __restrict__ B, uint4* __restrict__ qlut_lds,
-                                                               float* __restrict__ lut_scales, float* __restrict__ lut_biases,
-                                                               int K, int tstride, uint4* __restrict__ qlut_ref,
-                                                               uint2* __restrict__ qlut_dev, size_t qdev_u4_per_row,
-                                                               uint4* __restrict__ bimg, float* __restrict__ colv, int Npad, XA... xa) {
-    extern __shared__ float prs[];          // [PT/64] wave maxima | [K/32] chunk sums
-    constexpr int NWV = PT / 64;
-    const int P = K / 8, n = blockIdx.x, tid = threadIdx.x, w = tid >> 6, lane = tid & 63;
-    float* l_mx = prs;
-    float* l_cs = prs + NWV;
-    int* l_hs = reinterpret_cast<int*>(prs + NWV + K / 32);      // sum of all signed half-table entries of the row (LUT image only)
-    if (tid == 0) *l_hs = 0;
-    constexpr int NPR = 3;                   // pairs per thread: K <= 24 * PT
-    float x[NPR][8];
-    float mx = 0.f;
-#pragma unroll
-    for (int r = 0; r < NPR; ++r) {
-        const int p = r * PT + tid;
-        if (p < P) {
+// This unit's launcher (declared in tmac_kernels.h; launch_gemv_quad / launch_gemv_quad_xf, tmac_launch.cpp, plan and pick the unit): select
+// the instantiation the plan names and launch it.  Which instantiations exist is quad_inst_exists (tmac_launch_plan.h) -- the selector
+// instantiates what passes it, so the predicate is the list of kernels this unit emits; the planner never names another.
+template <int BITS, bool SCF16, class Args>
+hipError_t launch_gemv_quad_unit(const Args& a, const QuadPlan& p, int N, hipStream_t st) {
+    constexpr bool XF = std::is_same_v<Args, FusedXfArgs>;
+    if (p.xf != XF || (XF && N != 1)) return hipErrorInvalidValue;
+    const dim3 g(p.gx, N), b(p.ft);
+    // scale flavour: unified scale (SM 2: one scalar read per output, the dtype stays a run-time flag -- fp32 unit only), or per-group scales
+    // with / without zero points
+    auto flavour = [&](auto&& f) {
+        if (a.s.m_groups >= 1) {
+            if constexpr (SCF16) return hipErrorInvalidValue;
+            else return f(std::false_type{}, std::integral_constant<int, 2>{});
+        }
+        return sel_bool(a.s.zero_point != 0, [&](auto ZP) { return f(ZP, std::integral_constant<int, 0>{}); });
+    };
+    return flavour([&](auto ZP, auto SM) { return sel_int<512, 768, 1024>(p.ft, [&](auto FT) { return sel_int<1, 2, 3, 4>(p.wpq, [&](auto WPQ) {
+        if constexpr (!quad_config_exists(FT, WPQ) || (XF && !quad_xf_covered(FT, WPQ))) return hipErrorInvalidValue;
+        else return sel_int<2, 6>(p.nr, [&](auto NR) { return sel_bool(p.early, [&](auto EARLY) {
             if constexpr (XF) {
-                xf_rows_x8(xf_rows_arg(xa...), B, F16, K, n, p, x[r]);
-            } else if (F16) {
-                const uint4 v = reinterpret_cast<const uint4*>(reinterpret_cast<const __half*>(B) + (size_t)n * K)[p];
-                const uint32_t rr[4] = {v.x, v.y, v.z, v.w};
-#pragma unroll
-                for (int i = 0; i < 4; ++i) {
-                    const __half2 hh = *reinterpret_cast<const __half2*>(&rr[i]);
-                    x[r][2 * i] = __low2float(hh); x[r][2 * i + 1] = __high2float(hh);
-                }
+                return sel_bool(p.gn, [&](auto GN) { return sel_bool(p.gt, [&](auto GT) {
+                    if constexpr (!quad_inst_exists(1, NR, FT, WPQ, false, 1, EARLY, true)) return hipErrorInvalidValue;
+                    else return launch_lds(k_gemv_quad<BITS, ZP, SM, 1, NR, FT, WPQ, false, 1, SCF16, EARLY, true, GN, GT>, g, b, p.lds_bytes, st, a);
+                }); });
             } else {
-                const float4* src = reinterpret_cast<const float4*>(reinterpret_cast<const float*>(B) + (size_t)n * K) + 2 * (size_t)p;
-                const float4 a0 = src[0], a1 = src[1];
-                x[r][0] = a0.x; x[r][1] = a0.y; x[r][2] = a0.z; x[r][3] = a0.w; x[r][4] = a1.x; x[r][5] = a1.y; x[r][6] = a1.z; x[r][7] = a1.w;
+                return sel_bool(p.lutsrc != 0, [&](auto LUTSRC) { return sel_bool(p.dump, [&](auto DUMP) { return sel_bool(p.acc != 0, [&](auto ACC) {
+                    if constexpr (!quad_inst_exists(LUTSRC, NR, FT, WPQ, DUMP, ACC, EARLY, false)) return hipErrorInvalidValue;
+                    else return launch_lds(k_gemv_quad<BITS, ZP, SM, LUTSRC, NR, FT, WPQ, DUMP, ACC, SCF16, EARLY>, g, b, p.lds_bytes, st, a);
+                }); }); });
             }
-            mx = fmaxf(mx, lut_abssum4(x[r][0], x[r][1], x[r][2], x[r][3]));
-            mx = fmaxf(mx, lut_abssum4(x[r][4], x[r][5], x[r][6], x[r][7]));
-            float va = lut_lut0(x[r][0], x[r][1], x[r][2], x[r][3]), vb = lut_lut0(x[r][4], x[r][5], x[r][6], x[r][7]);
-            lut_chunk_fold(va, vb);
-            if ((p & 3) == 0) l_cs[p >> 2] = __fadd_rn(va, vb);
-        }
-    }
-    mx = lut_wave_max(mx);
-    if (lane == 0) l_mx[w] = mx;
-    __syncthreads();
-    mx = l_mx[0];
-#pragma unroll
-    for (int i = 1; i < NWV; ++i) mx = fmaxf(mx, l_mx[i]);
-    float gscale, gtinv;
-    lut_scale<true>(mx, gscale, gtinv);
-    if (tid == PT - 64) {
-        float biases = 0.0f;
-        const int nc = K / 32;
-        for (int c = 0; c < nc; ++c) biases = __fadd_rn(biases, l_cs[c]);
-        lut_scales[n] = gscale;
-        lut_biases[n] = biases;
-        if (colv) { colv[n] = gscale; colv[Npad + n] = biases; }      // the layout k_gemm_planes_us reads (tmac_gemm2.hip)
-    }
-    int hsum = 0;
-#pragma unroll
-    for (int r = 0; r < NPR; ++r) {
-        const int p = r * PT + tid;
-        if (p < P) {
-            float La, Lb;
-            const uint4 t = lut_tables2<false>(LUT_X8(x[r]), gtinv, La, Lb);
-            const uint32_t lo0 = t.x, hi0 = t.y, lo1 = t.z, hi1 = t.w;
-            qlut_lds[((size_t)n * 4 + (p & 3)) * tstride + (p >> 2)] = t;
-            if (bimg) {  // signed half tables, [unit][pair][n]: what the plane-combined GEMM streams
-                bimg[(size_t)p * Npad + n] = make_uint4(lo0 ^ 0x80808080u, hi0 ^ 0x80808080u, lo1 ^ 0x80808080u, hi1 ^ 0x80808080u);
-                // the 16 entries are biased bytes U = entry + 128: sum of the bytes - 16 * 128
-                hsum += (int)__builtin_amdgcn_sad_u8(lo0, 0u, __builtin_amdgcn_sad_u8(hi0, 0u, __builtin_amdgcn_sad_u8(lo1, 0u, __builtin_amdgcn_sad_u8(hi1, 0u, 0u)))) - 2048;
-            }
-            if (ALL) {
-                const int seg = p >> 3, j8 = p & 7;
-                *reinterpret_cast<uint4*>(qlut_dev + ((size_t)n * qdev_u4_per_row + qlut_dev_u4_index(seg, j8)) * 2) = make_uint4(lo0, hi0, lo1, hi1);
-                const uint32_t sg = 0x80808080u, rev = 0x00010203u;
-                const uint32_t n0l = __builtin_amdgcn_perm(0u, 0x01010100u - lo0, rev), n0h = __builtin_amdgcn_perm(0u, 0x01010100u - hi0, rev);
-                const uint32_t n1l = __builtin_amdgcn_perm(0u, 0x01010100u - lo1, rev), n1h = __builtin_amdgcn_perm(0u, 0x01010100u - hi1, rev);
-                uint4* rp = qlut_ref + ((size_t)n * (K / 4) + 2 * (size_t)p);
-                rp[0] = make_uint4(lo0 ^ sg, hi0 ^ sg, n0h ^ sg, n0l ^ sg);
-                rp[1] = make_uint4(lo1 ^ sg, hi1 ^ sg, n1h ^ sg, n1l ^ sg);
-            }
-        }
-    }
-    if (colv) {   // (uniform) the row's entry sum, int32 bits: what the +7 / +15 operand bytes of 3- / 4-bit rows add per unit of it
-#pragma unroll
-        for (int off = 32; off >= 1; off >>= 1) hsum += __shfl_xor(hsum, off);
-        if (lane == 0) atomicAdd(l_hs, hsum);
-        __syncthreads();
-        if (tid == 0) colv[2 * (size_t)Npad + n] = __int_as_float(*l_hs);
-    }
+        }); });
+    }); }); });
 }
-
-// ---------------------------------------------------------------------------------------------
-// Vector transforms for N > 1 rows: the row pass in front of an XF LUT build.  One workgroup per activation row.  NORM: t = fp32(in)
-// + residual (xf_rows_t8: the add the builders repeat), t to residual_out -- pair p of row n has exactly one writer, thread p mod 256 of
-// workgroup n -- and, with gamma, r[n] = rsq(fma(sum t^2, rcp(K), eps)), k_gemv_quad's expression.  The order of the sum is a function of K
-// alone: thread j adds its pairs j, j + 256, ... element by element (fma), the wave's 64 sums fold by xor 32, 16, ... 1, the four wave
-// sums are added in wave order.  Neither N, the row's index nor any launch knob enters: a row's r is the same in every call.
-// GLU_NORM (kind 4): t = g = gate(in) * in2 (xf_rows_g8: the product the builders repeat), summed in the same order; r[n] is all it writes.
-// ---------------------------------------------------------------------------------------------
-constexpr int XF_ROWS_PT = 256;
-template <bool F16, class XA = XfRowsArgs>
-__global__ __launch_bounds__(XF_ROWS_PT) void k_xf_rows(XA a, const void* __restrict__ B, float* __restrict__ r_out, int K) {
-    __shared__ float l_ss[XF_ROWS_PT / 64];
-    const int P = K / 8, n = blockIdx.x, tid = threadIdx.x;
-    float ss = 0.f;
-    for (int p = tid; p < P; p += XF_ROWS_PT) {
-        float t[8];
-        if (a.kind == 4) xf_rows_g8(a, B, F16, K, n, p, t);
-        else xf_rows_t8(a, B, F16, K, n, p, t);
-        if (a.residual_out != nullptr) {
-            float4* ro = reinterpret_cast<float4*>(a.residual_out + (size_t)n * K) + 2 * (size_t)p;
-            ro[0] = make_float4(t[0], t[1], t[2], t[3]);
-            ro[1] = make_float4(t[4], t[5], t[6], t[7]);
-        }
-#pragma unroll
-        for (int i = 0; i < 8; ++i) ss = __fmaf_rn(t[i], t[i], ss);
-    }
-    if (r_out == nullptr) return;           // (uniform)
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) ss = __fadd_rn(ss, __shfl_xor(ss, off, 64));
-    if ((tid & 63) == 0) l_ss[tid >> 6] = ss;
-    __syncthreads();
-    if (tid == 0) {
-        float tot = 0.f;
-#pragma unroll
-        for (int w = 0; w < XF_ROWS_PT / 64; ++w) tot = __fadd_rn(tot, l_ss[w]);
-        r_out[n] = __builtin_amdgcn_rsqf(__fmaf_rn(tot, __builtin_amdgcn_rcpf((float)K), a.eps));
-    }
-}
-// the fp32 x [N][K] the XF builders consume (tmac_hip_debug_xf_rows): a store around xf_rows_x8
-template <bool F16, class XA = XfRowsArgs>
-__global__ __launch_bounds__(256) void k_xf_rows_tap(XA a, const void* __restrict__ B, float* __restrict__ x_out, int K) {
-    const int P = K / 8, n = blockIdx.y;
-    const int p = blockIdx.x * 256 + threadIdx.x;
-    if (p >= P) return;
-    float x[8];
-    xf_rows_x8(a, B, F16, K, n, p, x);
-    float4* xo = reinterpret_cast<float4*>(x_out + (size_t)n * K) + 2 * (size_t)p;
-    xo[0] = make_float4(x[0], x[1], x[2], x[3]);
-    xo[1] = make_float4(x[4], x[5], x[6], x[7]);
-}
-
-hipError_t launch_xf_rows(const XfRowsGateArgs& xf, const void* B, int act_f16, float* r_out, int K, int N, hipStream_t st) {
-    if (K % 64 != 0 || N < 1 || (xf.kind != 1 && xf.kind != 4) || (r_out == nullptr && xf.residual_out == nullptr)) return hipErrorInvalidValue;
-    if (xf.kind == 4 && (!xf.in2 || !xf.gamma || !r_out || xf.residual || xf.residual_out)) return hipErrorInvalidValue;
-    if (xf.gate < XF_GATE_SILU || xf.gate > XF_GATE_GELU) return hipErrorInvalidValue;
-    dim3 g(N), b(XF_ROWS_PT);
-    // silu (and NORM): the instantiations on the plain block; another gate: those on the block that carries it
-#define XR(F, T) hipLaunchKernelGGL((k_xf_rows<F, T>), g, b, 0, st, static_cast<const T&>(xf), B, r_out, K)
-    if (xf.gate == XF_GATE_SILU) { if (act_f16) XR(true, XfRowsArgs); else XR(false, XfRowsArgs); }
-    else { if (act_f16) XR(true, XfRowsGateArgs); else XR(false, XfRowsGateArgs); }
-#undef XR
-    return hipGetLastError();
-}
-hipError_t launch_xf_rows_tap(const XfRowsGateArgs& xf, const void* B, int act_f16, float* x_out, int K, int N, hipStream_t st) {
-    if (K % 64 != 0 || N < 1 || N > 65535 || (xf.kind != 1 && xf.kind != 2 && xf.kind != 4) || !x_out) return hipErrorInvalidValue;
-    if (xf.gate < XF_GATE_SILU || xf.gate > XF_GATE_GELU) return hipErrorInvalidValue;
-    dim3 g((K / 8 + 255) / 256, N), b(256);
-#define XT(F, T) hipLaunchKernelGGL((k_xf_rows_tap<F, T>), g, b, 0, st, static_cast<const T&>(xf), B, x_out, K)
-    if (xf.gate == XF_GATE_SILU) { if (act_f16) XT(true, XfRowsArgs); else XT(false, XfRowsArgs); }
-    else { if (act_f16) XT(true, XfRowsGateArgs); else XT(false, XfRowsGateArgs); }
-#undef XT
-    return hipGetLastError();
-}
-
-hipError_t launch_preprocess_pairs_row(const void* B, int act_f16, void* qlut_lds, float* lut_scales, float* lut_biases, int K, int N,
-                                       int8_t* qlut_ref, void* qlut_dev, size_t qdev_u4_per_row, void* bimg, float* colv, int Npad, hipStream_t st,
-                                       const XfRowsGateArgs* xf) {
-    constexpr int PT = 512;
-    if (K % 64 != 0 || N < 1 || K > 24 * PT || ((qlut_ref == nullptr) != (qlut_dev == nullptr))) return hipErrorInvalidValue;
-    const int tstride = (((K / 32) + 15) & ~15) + 1;
-    const size_t shmem = sizeof(float) * (PT / 64 + K / 32 + 1);
-    dim3 g(N), b(PT);
-    if (xf) {
-        if (qlut_ref) return hipErrorInvalidValue;
-#define PLRX(F, T) hipLaunchKernelGGL((k_preprocess_pairs_row<F, false, PT, true, T>), g, b, shmem, st, B, (uint4*)qlut_lds, lut_scales, lut_biases, K, tstride, \
-                                      (uint4*)nullptr, (uint2*)nullptr, (size_t)0, (uint4*)bimg, colv, Npad, static_cast<const T&>(*xf))
-        if (xf->gate == XF_GATE_SILU) { if (act_f16) PLRX(true, XfRowsArgs); else PLRX(false, XfRowsArgs); }
-        else { if (act_f16) PLRX(true, XfRowsGateArgs); else PLRX(false, XfRowsGateArgs); }
-#undef PLRX
-        return hipGetLastError();
-    }
-#define PLR(F, A) hipLaunchKernelGGL((k_preprocess_pairs_row<F, A, PT>), g, b, shmem, st, B, (uint4*)qlut_lds, lut_scales, lut_biases, K, tstride, \
-                                     (uint4*)qlut_ref, (uint2*)qlut_dev, qdev_u4_per_row, (uint4*)bimg, colv, Npad)
-    if (qlut_ref) { if (act_f16) PLR(true, true); else PLR(false, true); }
-    else { if (act_f16) PLR(true, false); else PLR(false, false); }
-#undef PLR
-    return hipGetLastError();
-}
-
-hipError_t launch_preprocess_pairs(const void* B, int act_f16, void* qlut_lds, float* lut_scales, float* lut_biases, int K, int N,
-                                   int8_t* qlut_ref, void* qlut_dev, size_t qdev_u4_per_row, hipStream_t st, const XfRowsGateArgs* xf) {
-    if (K % 64 != 0 || N < 1 || ((qlut_ref == nullptr) != (qlut_dev == nullptr))) return hipErrorInvalidValue;
-    const int tstride = (((K / 32) + 15) & ~15) + 1;
-    dim3 g((K / 8 + 255) / 256, N), b(256);
-    if (xf) {
-        if (qlut_ref) return hipErrorInvalidValue;
-#define PLX(F, T) hipLaunchKernelGGL((k_preprocess_pairs<F, false, true, T>), g, b, 0, st, B, (uint4*)qlut_lds, lut_scales, lut_biases, K, tstride, \
-                                     (uint4*)nullptr, (uint2*)nullptr, (size_t)0, static_cast<const T&>(*xf))
-        if (xf->gate == XF_GATE_SILU) { if (act_f16) PLX(true, XfRowsArgs); else PLX(false, XfRowsArgs); }
-        else { if (act_f16) PLX(true, XfRowsGateArgs); else PLX(false, XfRowsGateArgs); }
-#undef PLX
-        return hipGetLastError();
-    }
-#define PL(F, A) hipLaunchKernelGGL((k_preprocess_pairs<F, A>), g, b, 0, st, B, (uint4*)qlut_lds, lut_scales, lut_biases, K, tstride, \
-                                    (uint4*)qlut_ref, (uint2*)qlut_dev, qdev_u4_per_row)
-    if (qlut_ref) { if (act_f16) PL(true, true); else PL(false, true); }
-    else { if (act_f16) PL(true, false); else PL(false, false); }
-#undef PL
-    return hipGetLastError();
-}
-
-bool gemv_quad_supported(const Shape& s) {
-    if (s.bits < 1 || s.bits > 4 || s.K % 64 != 0 || s.K > 24576 || s.Mw % 4 != 0) return false;
-    if (s.m_groups >= 1) return s.ags == s.K && s.Mw % s.m_groups == 0;
-    const int gu = s.gs / 32;
-    return s.ags == 64 && s.gs >= 64 && s.gs % 64 == 0 && s.K % s.gs == 0 && (gu & (gu - 1)) == 0;
-}
-
-#endif
-
-static size_t quad_lds_bytes(const Shape& s, int nwv) {
-    const int nu = s.K / 32, nst = (nu + 63) / 64, G = s.K / s.ags;
-    return (size_t)4 * (nst * 64 + 1) * 16 + sizeof(float) * (2 * (nst * 32 > G ? nst * 32 : G) + 2 * nwv * 16 + nwv + s.K / 32);
-}
-
-void fused_precompute(FusedArgs& a);   // tmac_fused.hip
-
-// Instantiation policy (compile time): the v_mqsad accumulate (ACC 0, A/B variant 7), the prebuilt-LUT source
-// (LUTSRC 0) and the integer tap (DUMP) exist for 512-thread workgroups only.
-template <int BITS, bool ZP, int SM, int LUTSRC, int FT, int WPQ>
-static hipError_t qlaunch_nr(const FusedArgs& a, int total_q, int N, hipStream_t st) {
-    constexpr int IPI = FT / 64 / WPQ;
-    const size_t shmem = quad_lds_bytes(a.s, FT / 64);
-    int gx = (total_q + IPI - 1) / IPI;
-    const int cap = (FT > 512) ? 256 : 512;       // persistent: <= 1 (FT = 768, 1024) / 2 (FT = 512) workgroups per CU (measured best)
-    if (gx > cap) gx = cap;
-    dim3 g(gx, N), b(FT);
-    const int T = a.s.K / 4;
-    constexpr int A1 = 1;
-#define QLE(NRV, DV, AV, EV) hipLaunchKernelGGL((k_gemv_quad<BITS, ZP, SM, LUTSRC, NRV, FT, WPQ, DV, AV, QSCF16, EV>), g, b, shmem, st, a)
-#define QL(NRV, DV, AV) QLE(NRV, DV, AV, false)
-    const bool early = LUTSRC == 1 && gx <= 256;   // one workgroup per CU: overlap the weight stream with the LUT build (see the kernel)
-    const bool two = (LUTSRC == 0 || T <= 2 * FT);
-    if (!two && T > 6 * FT) return hipErrorInvalidValue;
-    if constexpr (FT == 512) {
-        const int acc = a.acc_mfma ? 1 : 0;
-        if (a.dump) {
-            if (acc) { if (two) QL(2, true, A1); else if constexpr (LUTSRC == 1) QL(6, true, A1); }
-            else { if (two) QL(2, true, 0); else if constexpr (LUTSRC == 1) QL(6, true, 0); }
-        } else {
-            if (acc) {
-                if constexpr (LUTSRC == 1) {
-                    if (early) { if (two) QLE(2, false, A1, true); else QLE(6, false, A1, true); }
-                    else { if (two) QL(2, false, A1); else QL(6, false, A1); }
-                } else QL(2, false, A1);
-            } else { if (two) QL(2, false, 0); else if constexpr (LUTSRC == 1) QL(6, false, 0); }
-        }
-    } else {
-        if (a.dump || LUTSRC == 0 || !a.acc_mfma) return hipErrorInvalidValue;
-        if constexpr (LUTSRC == 1) { if (two) QLE(2, false, A1, true); else QLE(6, false, A1, true); }   // grids of these sizes never exceed one workgroup per CU
-    }
-#undef QL
-#undef QLE
-    return hipGetLastError();
-}
-
-// The (threads, waves per quad) of a launch: best_ft / best_wpq; false when the kernel has no such configuration.  need512: the launch
-// wants an instantiation that exists for 512-thread workgroups only (tap, prebuilt LUT, v_mqsad accumulate).
-static bool quad_config(const FusedArgs& a, int BITS, bool need512, int total_q, int force_ft, int force_wpq, int& best_ft, int& best_wpq) {
-    // Configuration choice, from tools/tune_quad.py on MI355X (profiles/r01_tune_quad.txt, us per launch in a graph):
-    //   W2: o 4096x4096: (512,2) 4.3 | qkv 12288x4096: (512,2) 6.5, (512,1) 6.6, (1024,1) 6.9 | gate_up 22016x4096:
-    //   (512,1) 9.2, (512,2) 10.2 | down 4096x11008: (768,3) 6.9, (1024,4) 7.2, (512,2) 7.3, (512,1) 8.8.
-    //   W4 (tune_quad.py 0 4): o (512,2) | qkv (512,2) | gate_up (512,1) | down (512,2).
-    const int nst = (a.s.K / 32 + 63) / 64;
-    // two waves per quad up to one quad per wave slot of the chip (4096), one beyond
-    best_ft = 512; best_wpq = (total_q <= 4096 && nst >= 2) ? 2 : 1;
-    // ... except where two waves per quad would leave the chip between one and two workgroups per CU (shards of a
-    // row-split model: 3 x 2048 and 2 x 2752 rows measured 7 % faster with one, profiles/history/r01_autotune_shards_before_heuristic.txt)
-    if (best_wpq == 2 && total_q > 1024 && total_q < 2048) best_wpq = 1;
-    if (BITS == 2 && total_q <= 1024 && nst >= 4 && !need512) {
-        // long rows, few quads: 3 waves per quad when that splits the steps evenly, else 4
-        if (nst % 3 == 0 && a.s.K / 4 <= 6 * 768) { best_ft = 768; best_wpq = 3; }
-        else { best_ft = 1024; best_wpq = 4; }
-    }
-    // One balanced pass: if twelve-wave workgroups with 1, 2 or 3 waves per quad cover the quads in a single pass over
-    // 75-100 % of the CUs, every CU gets the same work, the LUT is built once per CU and the weights can be issued early.
-    // Matches every case the tuner found on the llama-2-7B shapes and their 2-/4-/8-way row shards
-    // (profiles/history/r01_autotune_shards_before_heuristic.txt and the runs after it): q/k/v 3 x 4096 rows -> (768,1) 5.6 against 6.1 us; 3 x 2048 -> (768,2);
-    // gate/up 2 x 5504 -> (768,1) 5.45 against 5.9; 2 x 2752 -> (768,2); down 4096 x 11008 -> (768,3).
-    if (!need512 && a.s.K / 4 <= 6 * 768) {
-        for (int wq = 1; wq <= 3; ++wq) {
-            if (wq > nst || nst % wq || (wq == 3 && BITS > 2)) continue;   // (W4 long rows measure better on (512,2): tune_quad.py 0 4)
-            const int wgs = (total_q * wq + 11) / 12;
-            if (wgs > 192 && wgs <= 256) { best_ft = 768; best_wpq = wq; break; }
-        }
-    }
-    if (a.s.K / 4 > 6 * 512 && best_ft == 512 && !need512) best_ft = 1024;   // LUT build: <= 6 tables per thread
-    if (force_ft) { best_ft = force_ft; if (!force_wpq && best_wpq > 2) best_wpq = 2; }
-    if (force_wpq) best_wpq = force_wpq;
-    if (best_ft == 768 || best_wpq == 3)          // 12 waves: 3 per quad (balanced when the row has 3k steps), or 12 / 6 quads per workgroup
-        return best_ft == 768 && !need512 && a.s.K / 4 <= 6 * 768 && best_wpq >= 1 && best_wpq <= 3;
-    return !((need512 && best_ft != 512) || (best_wpq == 4 && best_ft != 1024) || (best_ft != 512 && best_ft != 1024) ||
-             (best_wpq != 1 && best_wpq != 2 && best_wpq != 4) || a.s.K / 4 > 6 * best_ft);
-}
-
-template <int BITS, bool ZP, int SM, int LUTSRC>
-static hipError_t qlaunch_cfg(const FusedArgs& a, int total_q, int N, int force_ft, int force_wpq, hipStream_t st) {
-    int best_ft, best_wpq;
-    if (!quad_config(a, BITS, a.dump || LUTSRC == 0 || !a.acc_mfma, total_q, force_ft, force_wpq, best_ft, best_wpq)) return hipErrorInvalidValue;
-    if (best_ft == 768) {
-        if (best_wpq == 3) return qlaunch_nr<BITS, ZP, SM, LUTSRC, 768, 3>(a, total_q, N, st);
-        if (best_wpq == 1) return qlaunch_nr<BITS, ZP, SM, LUTSRC, 768, 1>(a, total_q, N, st);
-        return qlaunch_nr<BITS, ZP, SM, LUTSRC, 768, 2>(a, total_q, N, st);
-    }
-    if (best_ft == 512) return best_wpq == 1 ? qlaunch_nr<BITS, ZP, SM, LUTSRC, 512, 1>(a, total_q, N, st)
-                                             : qlaunch_nr<BITS, ZP, SM, LUTSRC, 512, 2>(a, total_q, N, st);
-    if (best_wpq == 4) return qlaunch_nr<BITS, ZP, SM, LUTSRC, 1024, 4>(a, total_q, N, st);
-    return best_wpq == 1 ? qlaunch_nr<BITS, ZP, SM, LUTSRC, 1024, 1>(a, total_q, N, st)
-                         : qlaunch_nr<BITS, ZP, SM, LUTSRC, 1024, 2>(a, total_q, N, st);
-}
-
-template <int BITS, int LUTSRC>
-static hipError_t qlaunch_b(const FusedArgs& a, int total_q, int N, int fft, int fwpq, hipStream_t st) {
-    if (a.s.m_groups >= 1) {   // unified scale: one scalar read per output, dtype stays a run-time flag (fp32 TU only)
-        if constexpr (QSCF16) return hipErrorInvalidValue;
-        else return qlaunch_cfg<BITS, false, 2, LUTSRC>(a, total_q, N, fft, fwpq, st);
-    }
-    return a.s.zero_point ? qlaunch_cfg<BITS, true, 0, LUTSRC>(a, total_q, N, fft, fwpq, st)
-                          : qlaunch_cfg<BITS, false, 0, LUTSRC>(a, total_q, N, fft, fwpq, st);
-}
-
-// ---- XF instantiations (tmac_hip_qgemm_fused_xf_dev) ----
-// (each once for NORM / GLU and once, GN, for GLU_NORM -- the gate silu -- and both once more, GT, with the gate as a run-time choice)
-// They cover FOUR of the eight (threads, waves per quad) configurations -- one per waves-per-quad count, which is what shapes the K walk
-// and the cross-wave reductions: (512,1), (512,2), (768,3), (1024,4) -- so that eight translation units grow by 12 kernels per scale
-// flavour instead of 20.  A configuration the caller forced (tmac_hip_debug_quad_config) outside the set is refused; one the heuristic or
-// the tuned table chose falls back to the nearest covered one: same waves per quad in 512-thread workgroups ((768,1), (1024,1) -> (512,1);
-// (768,2), (1024,2) -> (512,2)), or (1024,4) where 512 threads cannot build the tables (K > 12288: more than six per thread).
-static bool quad_xf_covered(int ft, int wpq) { return (ft == 512 && (wpq == 1 || wpq == 2)) || (ft == 768 && wpq == 3) || (ft == 1024 && wpq == 4); }
-
-template <int BITS, bool ZP, int SM, int FT, int WPQ, bool GN, bool GT = false>
-static hipError_t qlaunch_xf_nr(const FusedXfArgs& a, int total_q, hipStream_t st) {
-    constexpr int IPI = FT / 64 / WPQ;
-    const size_t shmem = quad_lds_bytes(a.s, FT / 64);
-    int gx = (total_q + IPI - 1) / IPI;
-    const int cap = (FT > 512) ? 256 : 512;       // as qlaunch_nr
-    if (gx > cap) gx = cap;
-    dim3 g(gx, 1), b(FT);
-    const int T = a.s.K / 4;
-    const bool two = T <= 2 * FT;
-    if (!two && T > 6 * FT) return hipErrorInvalidValue;
-#define QX(NRV, EV) hipLaunchKernelGGL((k_gemv_quad<BITS, ZP, SM, 1, NRV, FT, WPQ, false, 1, QSCF16, EV, true, GN, GT>), g, b, shmem, st, a)
-    if constexpr (FT == 512) {
-        if (gx <= 256) { if (two) QX(2, true); else QX(6, true); }
-        else { if (two) QX(2, false); else QX(6, false); }
-    } else {
-        if (two) QX(2, true); else QX(6, true);
-    }
-#undef QX
-    return hipGetLastError();
-}
-
-template <int BITS, bool ZP, int SM, bool GN, bool GT>
-static hipError_t qlaunch_xf_pick(const FusedXfArgs& a, int total_q, int best_ft, int best_wpq, hipStream_t st) {
-    if (best_ft == 512) return best_wpq == 1 ? qlaunch_xf_nr<BITS, ZP, SM, 512, 1, GN, GT>(a, total_q, st) : qlaunch_xf_nr<BITS, ZP, SM, 512, 2, GN, GT>(a, total_q, st);
-    if (best_ft == 768) return qlaunch_xf_nr<BITS, ZP, SM, 768, 3, GN, GT>(a, total_q, st);
-    return qlaunch_xf_nr<BITS, ZP, SM, 1024, 4, GN, GT>(a, total_q, st);
-}
-
-template <int BITS, bool ZP, int SM>
-static hipError_t qlaunch_xf_cfg(const FusedXfArgs& a, int total_q, int ft, int wpq, bool strict, hipStream_t st) {
-    int best_ft, best_wpq;
-    if (!quad_config(a, BITS, false, total_q, ft, wpq, best_ft, best_wpq)) return hipErrorInvalidValue;
-    if (!quad_xf_covered(best_ft, best_wpq)) {
-        if (strict) return hipErrorInvalidValue;
-        if (a.s.K / 4 > 6 * 512) { best_ft = 1024; best_wpq = 4; }
-        else { best_ft = 512; best_wpq = best_wpq >= 2 ? 2 : 1; }
-    }
-    // GLU_NORM has instantiations of its own (GN): the ones NORM and GLU run on stay as they were; and relu^2 and GELU have theirs (GT), next
-    // to both: a call with silu runs what it ran
-    const bool gn = (a.xf_kind & 0xff) == 4, gt = (a.xf_kind >> 8) != XF_GATE_SILU;
-    if (gn) return gt ? qlaunch_xf_pick<BITS, ZP, SM, true, true>(a, total_q, best_ft, best_wpq, st) : qlaunch_xf_pick<BITS, ZP, SM, true, false>(a, total_q, best_ft, best_wpq, st);
-    return gt ? qlaunch_xf_pick<BITS, ZP, SM, false, true>(a, total_q, best_ft, best_wpq, st) : qlaunch_xf_pick<BITS, ZP, SM, false, false>(a, total_q, best_ft, best_wpq, st);
-}
-
-template <int BITS>
-static hipError_t qlaunch_xf_b(const FusedXfArgs& a, int total_q, int ft, int wpq, bool strict, hipStream_t st) {
-    if (a.s.m_groups >= 1) {
-        if constexpr (QSCF16) return hipErrorInvalidValue;
-        else return qlaunch_xf_cfg<BITS, false, 2>(a, total_q, ft, wpq, strict, st);
-    }
-    return a.s.zero_point ? qlaunch_xf_cfg<BITS, true, 0>(a, total_q, ft, wpq, strict, st)
-                          : qlaunch_xf_cfg<BITS, false, 0>(a, total_q, ft, wpq, strict, st);
-}
-
-// a.m[i].nb_end must hold cumulative QUAD counts.  force_ft / force_wpq: 0 = heuristic (A/B knobs)
-#define QENTRY_(b, h) launch_gemv_quad_b##b##_h##h
-#define QENTRY(b, h) QENTRY_(b, h)
-#define QENTRY_DECL(b, h) hipError_t QENTRY_(b, h)(const FusedArgs& a, int total_q, int N, bool build_lut, int force_ft, int force_wpq, hipStream_t st)
-QENTRY_DECL(1, 0); QENTRY_DECL(1, 1); QENTRY_DECL(2, 0); QENTRY_DECL(2, 1); QENTRY_DECL(3, 0); QENTRY_DECL(3, 1); QENTRY_DECL(4, 0); QENTRY_DECL(4, 1);
-hipError_t QENTRY(TMAC_QUAD_BITS, TMAC_QUAD_SCF16)(const FusedArgs& a, int total_q, int N, bool build_lut, int force_ft, int force_wpq, hipStream_t st) {
-    return build_lut ? qlaunch_b<TMAC_QUAD_BITS, 1>(a, total_q, N, force_ft, force_wpq, st)
-                     : qlaunch_b<TMAC_QUAD_BITS, 0>(a, total_q, N, force_ft, force_wpq, st);
-}
-#define QXENTRY_(b, h) launch_gemv_quad_xf_b##b##_h##h
-#define QXENTRY(b, h) QXENTRY_(b, h)
-#define QXENTRY_DECL(b, h) hipError_t QXENTRY_(b, h)(const FusedXfArgs& a, int total_q, int ft, int wpq, bool strict, hipStream_t st)
-QXENTRY_DECL(1, 0); QXENTRY_DECL(1, 1); QXENTRY_DECL(2, 0); QXENTRY_DECL(2, 1); QXENTRY_DECL(3, 0); QXENTRY_DECL(3, 1); QXENTRY_DECL(4, 0); QXENTRY_DECL(4, 1);
-hipError_t QXENTRY(TMAC_QUAD_BITS, TMAC_QUAD_SCF16)(const FusedXfArgs& a, int total_q, int ft, int wpq, bool strict, hipStream_t st) {
-    return qlaunch_xf_b<TMAC_QUAD_BITS>(a, total_q, ft, wpq, strict, st);
-}
-#if TMAC_QUAD_BITS == 2 && TMAC_QUAD_SCF16 == 0
-static bool xf_args_bad(const FusedXfArgs& a) {
-    const int kind = a.xf_kind & 0xff, gate = a.xf_kind >> 8;
-    if (kind != 1 && kind != 2 && kind != 4) return true;
-    if (gate < XF_GATE_SILU || gate > XF_GATE_GELU || (kind == 1 && gate != XF_GATE_SILU)) return true;
-    return kind == 4 && (!a.in2 || !a.gamma);
-}
-hipError_t launch_gemv_quad_xf(const FusedXfArgs& a_in, int ft, int wpq, bool strict, hipStream_t st) {
-    if (!gemv_quad_supported(a_in.s) || a_in.s.K > QUAD_XF_MAX_K || a_in.nmat < 1 || a_in.nmat > 4 || !a_in.acc_mfma || a_in.dump ||
-        xf_args_bad(a_in))
-        return hipErrorInvalidValue;
-    FusedXfArgs a = a_in;
-    fused_precompute(a);
-    const int total_q = a.m[a.nmat - 1].nb_end;
-    const bool h = a.sc_f16 && a.s.m_groups < 1;
-#define QXDISP(B) return h ? launch_gemv_quad_xf_b##B##_h1(a, total_q, ft, wpq, strict, st) : launch_gemv_quad_xf_b##B##_h0(a, total_q, ft, wpq, strict, st)
-    switch (a.s.bits) {
-        case 1: QXDISP(1);
-        case 2: QXDISP(2);
-        case 3: QXDISP(3);
-        default: QXDISP(4);
-    }
-#undef QXDISP
-}
-hipError_t launch_gemv_quad(const FusedArgs& a_in, int N, bool build_lut, int force_ft, int force_wpq, hipStream_t st) {
-    if (!gemv_quad_supported(a_in.s) || a_in.nmat < 1 || a_in.nmat > 4) return hipErrorInvalidValue;
-    FusedArgs a = a_in;
-    fused_precompute(a);
-    const int total_q = a.m[a.nmat - 1].nb_end;
-    const bool h = a.sc_f16 && a.s.m_groups < 1;
-#define QDISP(B) return h ? launch_gemv_quad_b##B##_h1(a, total_q, N, build_lut, force_ft, force_wpq, st) \
-                          : launch_gemv_quad_b##B##_h0(a, total_q, N, build_lut, force_ft, force_wpq, st)
-    switch (a.s.bits) {
-        case 1: QDISP(1);
-        case 2: QDISP(2);
-        case 3: QDISP(3);
-        default: QDISP(4);
-    }
-#undef QDISP
-}
-#endif
+template hipError_t launch_gemv_quad_unit<TMAC_QUAD_BITS, QSCF16, FusedArgs>(const FusedArgs&, const QuadPlan&, int, hipStream_t);
+template hipError_t launch_gemv_quad_unit<TMAC_QUAD_BITS, QSCF16, FusedXfArgs>(const FusedXfArgs&, const QuadPlan&, int, hipStream_t);
 
 }  // namespace tmac

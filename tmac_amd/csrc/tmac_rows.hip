@@ -20,10 +20,9 @@
 #include "tmac_core.h"
 #include "tmac_kernels.h"
 #include "tmac_chain_core.h"
+#include "tmac_select.h"
 
 namespace tmac {
-
-constexpr int ROWS_FT = 512, ROWS_NWV = ROWS_FT / 64;
 
 template <int BITS>
 struct RFrag {
@@ -353,103 +352,22 @@ r_done:;
 #error "compile with -DTMAC_ROWS_BITS=1..4 (one translation unit per weight width keeps the build parallel)"
 #endif
 
-#define RENTRY_(b) launch_gemv_rows_b##b
-#define RENTRY(b) RENTRY_(b)
-#define RENTRY_DECL(b) hipError_t RENTRY_(b)(const RowsArgs& a, int R, dim3 g, size_t shmem, hipStream_t st)
-RENTRY_DECL(1); RENTRY_DECL(2); RENTRY_DECL(3); RENTRY_DECL(4);
-
-template <int BITS, bool ZP, bool SCF16, int SM>
-static hipError_t rlaunch_r(const RowsArgs& a, int R, dim3 g, size_t shmem, hipStream_t st) {
-    // dynamic LDS above 64 KB must be allowed per kernel; the largest footprint of a capacity is set once
-#define RLAUNCH(RV) do { \
-        static size_t attr_bytes = 0; \
-        if (shmem > attr_bytes) { \
-            hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&k_gemv_rows<BITS, ZP, SCF16, SM, RV>), \
-                                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)ROWS_LDS_MAX); \
-            if (e != hipSuccess) return e; \
-            attr_bytes = ROWS_LDS_MAX; \
-        } \
-        hipLaunchKernelGGL((k_gemv_rows<BITS, ZP, SCF16, SM, RV>), g, dim3(ROWS_FT), shmem, st, a); } while (0)
-    if (R == 2) RLAUNCH(2); else if (R == 4) RLAUNCH(4); else if (R == 8) RLAUNCH(8); else return hipErrorInvalidValue;
-#undef RLAUNCH
-    return hipGetLastError();
-}
-
-hipError_t RENTRY(TMAC_ROWS_BITS)(const RowsArgs& a, int R, dim3 g, size_t shmem, hipStream_t st) {
-    constexpr int B = TMAC_ROWS_BITS;
-    if (a.s.m_groups >= 1) return rlaunch_r<B, false, false, 2>(a, R, g, shmem, st);   // unified scale: one scalar read per output, dtype a run-time flag
-    if (a.s.zero_point) return a.sc_f16 ? rlaunch_r<B, true, true, 0>(a, R, g, shmem, st) : rlaunch_r<B, true, false, 0>(a, R, g, shmem, st);
-    return a.sc_f16 ? rlaunch_r<B, false, true, 0>(a, R, g, shmem, st) : rlaunch_r<B, false, false, 0>(a, R, g, shmem, st);
-}
-
-#if TMAC_ROWS_BITS == 2
-// LDS of a capacity-R workgroup: R rows of [4][nst * 64 + 1] uint4 tables + ls / 2, lb / 2 [nst * 32], then the fixed part: partials of the
-// eight waves [2 parities][R][8][4 rows][4]
-size_t rows_lds_bytes(int K, int R) {
-    const int nst = (K / 32 + 63) / 64;
-    return (size_t)R * ((size_t)4 * (nst * 64 + 1) * 16 + sizeof(float) * 2 * nst * 32) + sizeof(float) * 2 * R * ROWS_NWV * 16;
-}
-
-bool rows_plan(int K, int N, RowsPlan& p) {
-    p = RowsPlan{0, 0, 0, 0, 0};
-    if (K < 64 || K % 64 != 0 || N < 1) return false;
-    for (int R = 8; R >= 2 && !p.r_fit; R >>= 1)
-        if (rows_lds_bytes(K, R) <= ROWS_LDS_MAX) p.r_fit = R;
-    if (!p.r_fit) return false;
-    p.lds_bytes = rows_lds_bytes(K, p.r_fit);
-    p.ngroups = (N + p.r_fit - 1) / p.r_fit;
-    p.live_last = N - (p.ngroups - 1) * p.r_fit;
-    p.cap_last = p.live_last <= 2 ? 2 : p.live_last <= 4 ? 4 : 8;
-    return true;
-}
-
-bool gemv_rows_supported(const Shape& s) {
-    RowsPlan p;
-    return gemv_quad_supported(s) && rows_plan(s.K, 2, p);
-}
-
-hipError_t launch_gemv_rows(const RowsArgs& a_in, hipStream_t st, int* launches) {
-    RowsArgs a = a_in;
-    RowsPlan p;
-    if (!gemv_rows_supported(a.s) || a.nmat < 1 || a.nmat > 4 || a.N < 1 || !rows_plan(a.s.K, a.N, p) || (a.tap && a.nmat != 1)) return hipErrorInvalidValue;
-    const Shape& s = a.s;
-    a.nu = s.K / 32; a.nst = (a.nu + 63) / 64; a.tstride = ((a.nu + 15) & ~15) + 1;
-    a.G = s.K / s.ags; a.nsg = s.gs > 0 && s.m_groups < 1 ? s.K / s.gs : 1;
-    a.gs_shift = 0;
-    if (s.gs > 0) for (int g = s.gs / 32; g > 1; g >>= 1) ++a.gs_shift;
-    if (s.m_groups >= 1) a.gs_shift = 2;
-    const int total_q = a.m[a.nmat - 1].nb_end;
-    for (int i = 0; i < a.nmat; ++i) {
-        // fragment offsets are 32-bit buffer offsets
-        if ((size_t)((a.m[i].Mw + 3) / 4) * a.nst * s.bits * 1024 >= ((size_t)1 << 31)) return hipErrorInvalidValue;
-    }
-    // waves per quad, by the shape alone (never by N: a row's bits must not depend on the call's N): the fewest of 1 / 2 / 4 that give every
-    // CU a workgroup, at most one wave per step
-    a.wpq = 1;
-    while (a.wpq < 4 && a.wpq * 2 <= a.nst && (total_q * a.wpq + ROWS_NWV - 1) / ROWS_NWV < 256) a.wpq *= 2;
-    const int ipi = ROWS_NWV / a.wpq;
-    const int need = (total_q + ipi - 1) / ipi;
-    hipError_t e = hipSuccess;
-    auto go = [&](int R, int n_base, int groups) {
-        const size_t shmem = rows_lds_bytes(s.K, R);
-        const int occ = shmem * 2 <= ROWS_LDS_MAX ? 2 : 1;             // persistent: at most two workgroups per CU
-        dim3 g(need < 256 * occ ? need : 256 * occ, groups);
-        a.n_base = n_base; a.rows_per_group = R;
-        hipError_t le;
-        switch (s.bits) {
-            case 1: le = launch_gemv_rows_b1(a, R, g, shmem, st); break;
-            case 2: le = launch_gemv_rows_b2(a, R, g, shmem, st); break;
-            case 3: le = launch_gemv_rows_b3(a, R, g, shmem, st); break;
-            default: le = launch_gemv_rows_b4(a, R, g, shmem, st); break;
-        }
-        if (le == hipSuccess && launches) ++*launches;
-        return le;
+// This unit's launcher (declared in tmac_kernels.h; launch_gemv_rows, tmac_launch.cpp, plans the launches and picks the unit).
+template <int BITS>
+hipError_t launch_gemv_rows_unit(const RowsArgs& a, const RowsLaunch& l, hipStream_t st) {
+    // scale flavour: unified scale (one scalar read per output, the dtype a run-time flag), or per-group scales by zero points and dtype
+    auto flavour = [&](auto&& f) {
+        if (a.s.m_groups >= 1) return f(std::false_type{}, std::false_type{}, std::integral_constant<int, 2>{});
+        return sel_bool(a.s.zero_point != 0, [&](auto ZP) { return sel_bool(a.sc_f16 != 0, [&](auto SCF16) {
+            return f(ZP, SCF16, std::integral_constant<int, 0>{});
+        }); });
     };
-    const int full = p.cap_last == p.r_fit ? p.ngroups : p.ngroups - 1;      // groups of capacity r_fit: one launch, blockIdx.y = group
-    if (full > 0) e = go(p.r_fit, 0, full);
-    if (e == hipSuccess && full < p.ngroups) e = go(p.cap_last, full * p.r_fit, 1);
-    return e;
+    return flavour([&](auto ZP, auto SCF16, auto SM) { return sel_int<2, 4, 8>(l.R, [&](auto R) {
+        static_assert(rows_inst_exists(R), "k_gemv_rows: row capacity 2, 4 or 8");
+        static size_t allowed = 0;      // per kernel: the largest footprint of a capacity is allowed once
+        return launch_lds_once(allowed, ROWS_LDS_MAX, k_gemv_rows<BITS, ZP, SCF16, SM, R>, dim3(l.gx, l.gy), dim3(ROWS_FT), l.lds_bytes, st, a);
+    }); });
 }
-#endif
+template hipError_t launch_gemv_rows_unit<TMAC_ROWS_BITS>(const RowsArgs&, const RowsLaunch&, hipStream_t);
 
 }  // namespace tmac

@@ -30,6 +30,7 @@
 #include <stdint.h>
 
 #include "tmac_chain_core.h"
+#include "tmac_select.h"
 
 // Four translation units (build time): -DTMAC_STREAM_QW_TU=0 (default) holds the LUT-image kernels and the (quad x 64 units) form of
 // k_gemv_stream, =1 its quarter-walk form; with -DTMAC_STREAM_G2_TU=1 each holds the G2 instances of its form instead (two scale groups
@@ -586,65 +587,18 @@ __global__ __launch_bounds__(STREAM_FT, MINW) TMAC_STREAM_ATTR void k_gemv_strea
 
 }
 
-// Ring depths.  Two workgroups share a CU only with <= 64 VGPRs per wave; a G2 fragment is one or two registers larger, and where the
-// ring of the nsplit >= 2 instance would pass 64 with it the ring gets shallower (never a spill: a spill behind the ring waits for the
-// weights) -- 3-bit G2: one fragment, as 4-bit weights have at nsplit >= 2.  4-bit G2 has no ring left to give: a launch with nsplit >= 2
-// runs the one-workgroup instance there (the workgroups then do not share a CU; nothing in the kernel depends on that).  The host's
-// nsplit rule for G2 follows (plan_stream).
-template <int BITS, bool QWF, bool G2F>
-static hipError_t stream_launch_b(const StreamArgs& a, bool zp, bool sc_f16, int sm, int grid, size_t lds_bytes, hipStream_t st) {
-    constexpr int R2 = G2F ? ((BITS <= 2) ? 2 : 1) : ((BITS <= 3) ? 2 : 1);      // two workgroups per CU: <= 64 VGPRs
-    constexpr int R1 = (BITS <= 2) ? 4 : 2;      // one workgroup per CU: ring depth 2..8 measured flat (profiles/r05_stream_knockouts.txt)
-#define TMAC_SL2(Z, H, R, MW, S) do { \
-        auto* kern = a.tap ? &k_gemv_stream<BITS, Z, H, R1, 4, S, true, QWF, G2F> : &k_gemv_stream<BITS, Z, H, R, MW, S, false, QWF, G2F>; \
-        if (lds_bytes > 64 * 1024) { \
-            hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes); \
-            if (e != hipSuccess) return e; \
-        } \
-        hipLaunchKernelGGL(kern, dim3(grid * a.nsplit), dim3(STREAM_FT), lds_bytes, st, a); \
-        return hipGetLastError(); } while (0)
-#define TMAC_SL(Z, H, S) do { if constexpr (!(G2F && BITS == 4)) { if (a.nsplit >= 2) TMAC_SL2(Z, H, R2, 8, S); } TMAC_SL2(Z, H, R1, 4, S); } while (0)
-    if constexpr (!G2F) {
-        if (sm == 2) { if (sc_f16) TMAC_SL(false, true, 2); else TMAC_SL(false, false, 2); }      // unified scales: no zero points (qgemm.py:170-174)
-    } else if (sm != 0) return hipErrorInvalidValue;
-    if (zp) { if (sc_f16) TMAC_SL(true, true, 0); else TMAC_SL(true, false, 0); }
-    if (sc_f16) TMAC_SL(false, true, 0);
-    TMAC_SL(false, false, 0);
-#undef TMAC_SL
-#undef TMAC_SL2
+// This unit's launcher (declared in tmac_chain.h).  Ring depth and waves of the instance: stream_inst (tmac_launch_plan.h), by the width, G2,
+// nsplit and the tap; stream_inst_exists says which instances there are.
+template <bool QW, bool G2>
+hipError_t launch_gemv_stream_unit(const StreamArgs& a, int bits, bool zp, bool sc_f16, int sm, int grid, size_t lds_bytes, hipStream_t st) {
+    return sel_int<1, 2, 3, 4>(bits, [&](auto BITS) { return sel_int<0, 2>(sm, [&](auto SM) { return sel_bool(sm == 0 && zp, [&](auto ZP) {
+        return sel_bool(sc_f16, [&](auto SCF16) { return sel_bool(a.tap != nullptr, [&](auto TAP) { return sel_bool(a.nsplit >= 2, [&](auto SPLIT) {
+            constexpr StreamInst I = stream_inst(BITS, G2, SPLIT ? 2 : 1, TAP);
+            if constexpr (!stream_inst_exists(ZP, SM, G2)) return hipErrorInvalidValue;
+            else return launch_lds(k_gemv_stream<BITS, ZP, SCF16, I.ring, I.mw, SM, TAP, QW, G2>, dim3(grid * a.nsplit), dim3(STREAM_FT), lds_bytes, st, a);
+        }); }); });
+    }); }); });
 }
-
-#define TMAC_STREAM_BITS_SWITCH(QWF, G2F) \
-    switch (bits) { \
-        case 1: return stream_launch_b<1, QWF, G2F>(a, zp, sc_f16, sm, grid, lds_bytes, st); \
-        case 2: return stream_launch_b<2, QWF, G2F>(a, zp, sc_f16, sm, grid, lds_bytes, st); \
-        case 3: return stream_launch_b<3, QWF, G2F>(a, zp, sc_f16, sm, grid, lds_bytes, st); \
-        case 4: return stream_launch_b<4, QWF, G2F>(a, zp, sc_f16, sm, grid, lds_bytes, st); \
-        default: return hipErrorInvalidValue; \
-    }
-#if TMAC_STREAM_QW_TU && TMAC_STREAM_G2_TU
-hipError_t launch_gemv_stream_qw_g2(const StreamArgs& a, int bits, bool zp, bool sc_f16, int sm, int grid, size_t lds_bytes, hipStream_t st) {
-    TMAC_STREAM_BITS_SWITCH(true, true)
-}
-#elif TMAC_STREAM_G2_TU
-hipError_t launch_gemv_stream_g2(const StreamArgs& a, int bits, bool zp, bool sc_f16, int sm, int grid, size_t lds_bytes, hipStream_t st) {
-    TMAC_STREAM_BITS_SWITCH(false, true)
-}
-#elif TMAC_STREAM_QW_TU
-hipError_t launch_gemv_stream_qw(const StreamArgs& a, int bits, bool zp, bool sc_f16, int sm, int grid, size_t lds_bytes, hipStream_t st) {
-    TMAC_STREAM_BITS_SWITCH(true, false)
-}
-#else
-hipError_t launch_gemv_stream_qw(const StreamArgs& a, int bits, bool zp, bool sc_f16, int sm, int grid, size_t lds_bytes, hipStream_t st);
-hipError_t launch_gemv_stream_g2(const StreamArgs& a, int bits, bool zp, bool sc_f16, int sm, int grid, size_t lds_bytes, hipStream_t st);
-hipError_t launch_gemv_stream_qw_g2(const StreamArgs& a, int bits, bool zp, bool sc_f16, int sm, int grid, size_t lds_bytes, hipStream_t st);
-hipError_t launch_gemv_stream(const StreamArgs& a, int bits, bool zp, bool sc_f16, int sm, bool qw, bool g2, int grid, size_t lds_bytes, hipStream_t st) {
-    if (a.nops < 1 || grid < 1 || a.nsplit < 1 || a.nsplit > 4 || (sm != 0 && sm != 2) || (g2 && sm != 0)) return hipErrorInvalidValue;
-    if (g2) return qw ? launch_gemv_stream_qw_g2(a, bits, zp, sc_f16, sm, grid, lds_bytes, st) : launch_gemv_stream_g2(a, bits, zp, sc_f16, sm, grid, lds_bytes, st);
-    if (qw) return launch_gemv_stream_qw(a, bits, zp, sc_f16, sm, grid, lds_bytes, st);
-    TMAC_STREAM_BITS_SWITCH(false, false)
-}
-#endif
-#undef TMAC_STREAM_BITS_SWITCH
+template hipError_t launch_gemv_stream_unit<TMAC_STREAM_QW_TU != 0, TMAC_STREAM_G2_TU != 0>(const StreamArgs&, int, bool, bool, int, int, size_t, hipStream_t);
 
 }  // namespace tmac

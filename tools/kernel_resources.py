@@ -34,7 +34,8 @@ def opcodes_of(co):
             if name is not None:
                 out[name] = (len(ops), hashlib.sha1(" ".join(ops).encode()).hexdigest()[:12])
             name, ops = m.group(1), []
-        elif name is not None and line.startswith((" ", "\t")) and line.strip():
+        elif name is not None and line.startswith((" ", "\t")) and line.strip() and line.strip() != "...":
+            # ("...": llvm-objdump's mark for zero padding behind a function -- where the next one starts, not what this one does)
             ops.append(line.split("//")[0].split()[0])
     if name is not None:
         out[name] = (len(ops), hashlib.sha1(" ".join(ops).encode()).hexdigest()[:12])
