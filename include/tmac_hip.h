@@ -177,6 +177,54 @@ int32_t tmac_hip_register_weights_codes_dev(tmac_hip_weights** out, const void* 
                                             tmac_dtype_t sz_dtype, int Mw, int K, int bits, const tmac_kcfg* cfg,
                                             tmac_dtype_t ref_float, tmac_dtype_t dev_float, void* stream);
 
+/* ---- act-order (desc_act) GPTQ matrices: the K permutation ---------------------------------------------------------------
+ * An act-order matrix is a group-quantised matrix whose K axis is permuted: g_idx[k] names the group of column k.  With
+ * perm = stable_argsort(g_idx) the columns q[:, perm] lie in contiguous groups of group_size, scales / qzeros are in group order already,
+ * and y = W x = W' x[perm].  The handle holds W'; every LUT build that serves it reads its activations through perm.
+ *
+ * tmac_hip_kperm_from_gidx_dev  g_idx_dev: int32 [K] in device memory, 16-byte aligned.  One device-to-host copy, a stable counting sort
+ *   on the host, one upload of perm (int32 [K]); synchronises the stream.  Ordered behind the calling thread's deferred queue.  Refused
+ *   with TMAC_HIP_E_ARG and a message naming the first offending group, nothing created: a NULL or misaligned pointer, K % group_size != 0,
+ *   a value outside [0, K / group_size), a group without exactly group_size members.  After success every perm[k'] < K, which keeps every
+ *   device gather inside its row.
+ * tmac_hip_kperm_info   K; identity = 1 when perm[k'] == k' throughout (g_idx == k / group_size, what every non-act-order exporter writes);
+ *   id = a 64-bit hash of the contents, never 0.  Any out pointer may be NULL.
+ * tmac_hip_kperm_read   the K values of perm to host memory.
+ * tmac_hip_kperm_free   releases the caller's reference; handles registered through the object keep it alive.
+ * Two objects are the same permutation when they are one object or K, hash and contents (memcmp) are equal.
+ *
+ * Packing and registration through a permutation take the argument lists of their plain twins plus `perm` behind the inputs.  perm NULL
+ * or an identity: the plain twin is called.  Otherwise the twin's argument rules apply, and TMAC_HIP_E_ARG for: the permutation's K or
+ * group size differing from the call's K / cfg->group_size; unified scales (m_groups >= 1).  The blob (tmac_hip_pack_*_perm_dev) is bit
+ * for bit the plain pack's of the matrix with its columns gathered, w[:, perm]; scales and zeros are the plain pack's.  The registered
+ * handle carries the permutation (tmac_hip_weights_kperm_id: its id, 0 for a plain handle).
+ *
+ * What serves such handles: tmac_hip_qgemm_fused_dev -- all matrices of a call must carry the same permutation, or none ("matrices fused
+ * in one launch must share the K permutation", TMAC_HIP_E_ARG); N = 1 runs k_gemv_quad's gather instantiations, N >= 2 is routed as
+ * tmac_hip_qgemm_fused_xf_rows_dev routes a transformed call with the LUT build gathering; QUAD layout and the MFMA accumulate only
+ * (TMAC_HIP_E_NOMATCH otherwise).  The call is never queued (deferred mode: it goes behind the queue and launches stand-alone) and never
+ * recorded (between tmac_hip_chain_begin and _end it is refused, TMAC_HIP_E_ARG; the recording stays usable).  The split path:
+ * tmac_hip_preprocessor_perm_dev + tmac_hip_qgemm_dev, below.  Refused with TMAC_HIP_E_ARG and a message: the parity taps of the fused
+ * entry point (tmac_hip_qgemm_fused_partial_sums) and vector transforms (tmac_hip_qgemm_fused_xf_dev, _xf_rows_dev) on such handles. */
+typedef struct tmac_hip_kperm tmac_hip_kperm;
+int32_t tmac_hip_kperm_from_gidx_dev(const int32_t* g_idx_dev, int K, int group_size, tmac_hip_kperm** out, void* stream);
+int32_t tmac_hip_kperm_info(const tmac_hip_kperm* p, int* K, int* identity, uint64_t* id);
+int32_t tmac_hip_kperm_read(const tmac_hip_kperm* p, int32_t* perm_host);     /* K values */
+int32_t tmac_hip_kperm_free(tmac_hip_kperm* p);                               /* handles that use it keep it alive */
+int32_t tmac_hip_weights_kperm_id(const tmac_hip_weights* w, uint64_t* id);   /* 0: the handle carries no permutation */
+int32_t tmac_hip_pack_gptq_perm_dev(const void* qweight, const void* scales, const void* qzeros, tmac_dtype_t scales_dtype, int gptq_v2,
+                                    const tmac_hip_kperm* perm, int Mw, int K, int bits, const tmac_kcfg* cfg, void* A_ref_out,
+                                    void* scales_ref_out, tmac_dtype_t ref_float, void* stream);
+int32_t tmac_hip_pack_codes_perm_dev(const void* codes, const void* scales, const void* zeros, tmac_dtype_t sz_dtype,
+                                     const tmac_hip_kperm* perm, int Mw, int K, int bits, const tmac_kcfg* cfg, void* A_ref_out,
+                                     void* scales_ref_out, tmac_dtype_t ref_float, void* stream);
+int32_t tmac_hip_register_weights_gptq_perm_dev(tmac_hip_weights** out, const void* qweight, const void* scales, const void* qzeros,
+                                                tmac_dtype_t scales_dtype, int gptq_v2, const tmac_hip_kperm* perm, int Mw, int K, int bits,
+                                                const tmac_kcfg* cfg, tmac_dtype_t ref_float, tmac_dtype_t dev_float, void* stream);
+int32_t tmac_hip_register_weights_codes_perm_dev(tmac_hip_weights** out, const void* codes, const void* scales, const void* zeros,
+                                                 tmac_dtype_t sz_dtype, const tmac_hip_kperm* perm, int Mw, int K, int bits,
+                                                 const tmac_kcfg* cfg, tmac_dtype_t ref_float, tmac_dtype_t dev_float, void* stream);
+
 /* LUT workspace = TMACGeMMWrapper::set_workspace (tmac_gemm_wrapper.h:257-270) on the device. */
 int32_t tmac_hip_workspace_create(tmac_hip_workspace** out, int maxK, int maxN);
 int32_t tmac_hip_workspace_free(tmac_hip_workspace* ws);
@@ -186,8 +234,16 @@ int32_t tmac_hip_workspace_free(tmac_hip_workspace* ws);
 int32_t tmac_hip_preprocessor_dev(tmac_hip_workspace* ws, const void* B_dev, tmac_dtype_t act_dtype,
                                   int K, int N, int act_group_size, void* stream);
 
+/* The same through a K permutation (act-order handles, above): every layout of the workspace from B_dev[:, perm], by the gathered
+ * pair-wise build, for every N; act_group_size must be 64 (TMAC_HIP_E_NOMATCH otherwise) and the permutation's K the call's
+ * (TMAC_HIP_E_ARG).  The workspace records the id of the permutation its LUT was built through -- 0 for none, which every other build
+ * and tmac_hip_workspace_write set.  perm NULL or an identity: tmac_hip_preprocessor_dev itself. */
+int32_t tmac_hip_preprocessor_perm_dev(tmac_hip_workspace* ws, const void* B_dev, tmac_dtype_t act_dtype,
+                                       int K, int N, int act_group_size, const tmac_hip_kperm* perm, void* stream);
+
 /* qgemm_lut (tbl.cc + glue): C_dev [N][Mw] (out_dtype) = W x LUT(ws).  ws must hold the LUT of the
- * same K and act_group_size.  Whole matrix in one launch.  C_dev: 16-byte aligned (fp32), 8-byte (fp16). */
+ * same K and act_group_size.  Whole matrix in one launch.  C_dev: 16-byte aligned (fp32), 8-byte (fp16).
+ * TMAC_HIP_E_ARG when the weights carry a K permutation and the workspace's LUT was not built through it, or the reverse. */
 int32_t tmac_hip_qgemm_dev(const tmac_hip_weights* w, const tmac_hip_workspace* ws, void* C_dev,
                            tmac_dtype_t out_dtype, int N, void* stream);
 

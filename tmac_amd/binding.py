@@ -92,6 +92,19 @@ def load_library() -> C.CDLL:
                                                 C.c_int, vp], i32),
         "tmac_hip_register_weights_codes_dev": ([C.POINTER(vp), vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(KCfg), C.c_int, C.c_int,
                                                  vp], i32),
+        # act-order (K permutation from g_idx): the object, packing / registration / the split path's LUT build through it
+        "tmac_hip_kperm_from_gidx_dev": ([vp, C.c_int, C.c_int, C.POINTER(vp), vp], i32),
+        "tmac_hip_kperm_info": ([vp, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_uint64)], i32),
+        "tmac_hip_kperm_read": ([vp, vp], i32),
+        "tmac_hip_kperm_free": ([vp], i32),
+        "tmac_hip_weights_kperm_id": ([vp, C.POINTER(C.c_uint64)], i32),
+        "tmac_hip_pack_gptq_perm_dev": ([vp, vp, vp, C.c_int, C.c_int, vp, C.c_int, C.c_int, C.c_int, C.POINTER(KCfg), vp, vp, C.c_int, vp], i32),
+        "tmac_hip_pack_codes_perm_dev": ([vp, vp, vp, C.c_int, vp, C.c_int, C.c_int, C.c_int, C.POINTER(KCfg), vp, vp, C.c_int, vp], i32),
+        "tmac_hip_register_weights_gptq_perm_dev": ([C.POINTER(vp), vp, vp, vp, C.c_int, C.c_int, vp, C.c_int, C.c_int, C.c_int, C.POINTER(KCfg), C.c_int,
+                                                     C.c_int, vp], i32),
+        "tmac_hip_register_weights_codes_perm_dev": ([C.POINTER(vp), vp, vp, vp, C.c_int, vp, C.c_int, C.c_int, C.c_int, C.POINTER(KCfg), C.c_int, C.c_int,
+                                                      vp], i32),
+        "tmac_hip_preprocessor_perm_dev": ([vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp], i32),
         "tmac_hip_free_weights": ([vp], i32),
         "tmac_hip_weights_bytes": ([vp], sz),
         "tmac_hip_workspace_create": ([C.POINTER(vp), C.c_int, C.c_int], i32),
@@ -169,6 +182,9 @@ def load_library() -> C.CDLL:
     optional = {"tmac_hip_chain_is_stream", "tmac_hip_chain_xform", "tmac_hip_qgemm_fused_xf_dev", "tmac_hip_qgemm_fused_xf_rows_dev", "tmac_hip_debug_xf_rows", "tmac_hip_debug_xf_rows_plan", "tmac_hip_debug_fused_plan", "tmac_hip_debug_route_stats", "tmac_hip_comm_init_ipc", "tmac_hip_comm_export", "tmac_hip_comm_connect", "tmac_hip_comm_status",
                 "tmac_hip_ref_blob_bytes", "tmac_hip_pack_gptq_dev", "tmac_hip_pack_codes_dev", "tmac_hip_register_weights_gptq_dev",
                 "tmac_hip_register_weights_codes_dev",
+                "tmac_hip_kperm_from_gidx_dev", "tmac_hip_kperm_info", "tmac_hip_kperm_read", "tmac_hip_kperm_free", "tmac_hip_weights_kperm_id",
+                "tmac_hip_pack_gptq_perm_dev", "tmac_hip_pack_codes_perm_dev", "tmac_hip_register_weights_gptq_perm_dev",
+                "tmac_hip_register_weights_codes_perm_dev", "tmac_hip_preprocessor_perm_dev",
                 "tmac_hip_debug_rows_kernel", "tmac_hip_debug_rows_stats", "tmac_hip_debug_rows_plan", "tmac_hip_debug_rows_comb_sums"} if os.environ.get("TMAC_HIP_LIB") else set()
     for name, (argt, rest) in sigs.items():
         try:

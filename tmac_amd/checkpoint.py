@@ -8,13 +8,17 @@ Two steps, split so that the first runs without a GPU:
 * ``load_gptq_dir``  maps each part with ``np.memmap``, uploads the three packed tensors of a layer and registers them.  The
   ``safetensors`` package is not needed.
 
-Refused, naming the tensor: act-order checkpoints (``desc_act``, as the reference refuses them), a ``qweight`` without ``scales`` or
-``qzeros``, tensors of another element type than I32 (qweight, qzeros) / F16 or F32 (scales).
+Refused, naming the tensor: act-order checkpoints (``desc_act``, as the reference refuses them) unless ``act_order=True`` is passed, a
+``qweight`` without ``scales`` or ``qzeros``, tensors of another element type than I32 (qweight, qzeros) / F16 or F32 (scales).
+
+``act_order=True``: each layer's ``.g_idx`` (int32 [K], required then) becomes the K permutation its handle carries (``wrapper.KPerm``);
+one object per distinct content, so q/k/v and gate/up -- quantised against the same inputs -- share theirs and can be fused.  An identity
+g_idx registers a plain handle.
 """
 import json
 import os
 import struct
-from typing import Dict, List, NamedTuple, Tuple
+from typing import Dict, List, NamedTuple, Optional, Tuple
 
 import numpy as np
 
@@ -42,6 +46,7 @@ class GptqLayer(NamedTuple):
     Mw: int
     bits: int
     group_size: int
+    g_idx: Optional[TensorRef] = None      # scan_gptq_dir(..., act_order=True) only
 
 
 class GptqScan(NamedTuple):
@@ -86,9 +91,10 @@ def gptq_is_v2(qc: dict) -> bool:
     return "gptqmodel" in q.lower() or qc.get("quant_method", "") == "gptq_v2"
 
 
-def scan_gptq_dir(model_dir: str) -> GptqScan:
-    """The GPTQ triples of a checkpoint directory, in order of first appearance, without loading a tensor."""
-    qc = convert.get_quantization_config(model_dir)           # refuses desc_act
+def scan_gptq_dir(model_dir: str, act_order: bool = False) -> GptqScan:
+    """The GPTQ triples of a checkpoint directory, in order of first appearance, without loading a tensor.  act_order: desc_act
+    checkpoints are accepted and every layer must come with its ``.g_idx``."""
+    qc = convert.get_quantization_config(model_dir, allow_desc_act=act_order)           # refuses desc_act otherwise
     parts = sorted(f for f in os.listdir(model_dir) if f.startswith("model") and f.endswith(".safetensors"))
     if not parts:
         raise RuntimeError("Models in {} not in GPTQ safetensors format (torch .bin checkpoints: convert them to safetensors first)".format(model_dir))
@@ -118,7 +124,14 @@ def scan_gptq_dir(model_dir: str) -> GptqScan:
         if bits not in (1, 2, 4):
             raise RuntimeError("{}: GPTQ-packed width {} is not served (1, 2, 4)".format(qname, bits))
         K, Mw = qw.shape[0] * (32 // bits), qw.shape[1]
-        layers.append(GptqLayer(base, qw, sc, qz, K, Mw, bits, K // sc.shape[0]))
+        gi = None
+        if act_order:
+            gi = index.get(base + ".g_idx")
+            if gi is None:
+                raise RuntimeError("{}.g_idx is missing (act_order=True reads every layer's group indices)".format(base))
+            if gi.dtype != "I32" or gi.shape != (K,) or (gi.end - gi.begin) != 4 * K:
+                raise RuntimeError("{}.g_idx has dtype {} and shape {}: I32 [{}] expected".format(base, gi.dtype, gi.shape, K))
+        layers.append(GptqLayer(base, qw, sc, qz, K, Mw, bits, K // sc.shape[0], gi))
     if not layers:
         raise RuntimeError("Models in {} not in GPTQ format".format(model_dir))
     return GptqScan(layers, gptq_is_v2(qc), not qc.get("sym", False), qc)
@@ -129,16 +142,25 @@ def read_tensor(ref: TensorRef) -> np.ndarray:
     return np.memmap(ref.path, dtype=_NP[ref.dtype], mode="r", offset=ref.begin, shape=ref.shape)
 
 
-def load_gptq_dir(model_dir: str, wrapper, dev_dtype=F16) -> Dict[str, "object"]:
+def load_gptq_dir(model_dir: str, wrapper, dev_dtype=F16, act_order: bool = False) -> Dict[str, "object"]:
     """{layer name: Weights} for every ``*.qweight`` triple of the checkpoint: the packed tensors are uploaded as they lie in the file
     and unpacked, permuted and re-tiled on the GPU (``wrapper.register_gptq``).  A symmetric checkpoint (``sym``) is registered without
-    zero points, as the reference compiles its kernels (deploy/compile.py:103)."""
+    zero points, as the reference compiles its kernels (deploy/compile.py:103).  act_order: see the head of this file."""
     from .binding import KCfg
-    scan = scan_gptq_dir(model_dir)
+    from .wrapper import KPerm
+    scan = scan_gptq_dir(model_dir, act_order)
     out = {}
+    perms: Dict[Tuple[int, bytes], "object"] = {}      # one KPerm per distinct (group size, g_idx content)
     for L in scan.layers:
         cfg = KCfg.make(L.Mw, L.K, L.bits, convert.default_bm(L.bits, L.Mw), 16, L.group_size, wrapper._act_group_size, scan.zero_point)
         # np.array: a writable copy in memory (the map is read-only, and the upload wants one contiguous source)
         qz = np.array(read_tensor(L.qzeros)) if scan.zero_point else None
-        out[L.name] = wrapper.register_gptq(np.array(read_tensor(L.qweight)), np.array(read_tensor(L.scales)), qz, cfg, scan.gptq_v2, dev_dtype)
+        kp = None
+        if L.g_idx is not None:
+            g = np.array(read_tensor(L.g_idx))
+            key = (L.group_size, g.tobytes())
+            if key not in perms:
+                perms[key] = KPerm(g, L.group_size)
+            kp = perms[key]
+        out[L.name] = wrapper.register_gptq(np.array(read_tensor(L.qweight)), np.array(read_tensor(L.scales)), qz, cfg, scan.gptq_v2, dev_dtype, g_idx=kp)
     return out

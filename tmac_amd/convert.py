@@ -113,16 +113,18 @@ def _scan_checkpoint(model_dir: Optional[str]) -> Tuple[List[List[int]], int]:
     return ks, int(gs_all)
 
 
-def get_quantization_config(model_dir: str) -> dict:
+def get_quantization_config(model_dir: str, allow_desc_act: bool = False) -> dict:
     """what the pipeline reads from a checkpoint's config.json (``model_utils.py:219-240``): GPTQ fields of ``quantization_config`` and
-    BitNet's ``weight_bits``; act-order checkpoints (desc_act) are refused as the reference refuses them"""
+    BitNet's ``weight_bits``; act-order checkpoints (desc_act) are refused as the reference refuses them -- unless ``allow_desc_act``:
+    the device-side registration takes them (``checkpoint.load_gptq_dir(..., act_order=True)``), and the result then says ``desc_act``"""
     import json
     with open(os.path.join(model_dir, "config.json"), "r", encoding="utf-8") as f:
         hp = json.load(f)
     qc = hp.get("quantization_config", {})
-    if qc.get("desc_act", False):
+    if qc.get("desc_act", False) and not allow_desc_act:
         raise AssertionError("desc_act=True currently unsupported by T-MAC")
-    return {"quantizer": qc.get("meta", {}).get("quantizer", ""), "group_size": qc.get("group_size", 0), "bits": qc.get("bits", 0),
+    extra = {"desc_act": bool(qc.get("desc_act", False))} if allow_desc_act else {}
+    return {**extra, "quantizer": qc.get("meta", {}).get("quantizer", ""), "group_size": qc.get("group_size", 0), "bits": qc.get("bits", 0),
             "sym": qc.get("sym", False), "quant_method": qc.get("quant_method", ""), "weight_bits": hp.get("weight_bits", 0)}
 
 

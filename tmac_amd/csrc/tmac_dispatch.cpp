@@ -284,6 +284,29 @@ static int32_t rows_multi(const tmac_hip_weights* const* wl, int nmat, const tma
     return TMAC_HIP_OK;
 }
 
+// ---- act-order handles (tmac_kperm.h) ------------------------------------------------------------------------------------------
+// A handle that carries a K permutation holds W[:, perm]: every LUT it meets must have been built from x[perm].  The fused entry point
+// gathers in its LUT build (k_gemv_quad's GA instantiations for N = 1, the gathered pair build / LUT image for N >= 2); the split entry
+// point checks the workspace's record of the permutation its LUT was built through; everything else refuses such handles.
+static const KPermData* perm_of(const tmac_hip_weights* w) { return w ? w->kperm.get() : nullptr; }
+static uint64_t perm_id_of(const tmac_hip_weights* w) { return w && w->kperm ? w->kperm->h.id : 0; }
+// 0: no matrix carries a permutation | 1: all carry the same one (tmac_kperm.h: one object, or equal contents) | -1: a mix
+static int perm_state(const tmac_hip_weights* const* wl, int nmat) {
+    int with = 0;
+    for (int i = 0; i < nmat; ++i) with += perm_of(wl[i]) ? 1 : 0;
+    if (with == 0) return 0;
+    if (with != nmat) return -1;
+    for (int i = 1; i < nmat; ++i)
+        if (!kperm_equal(&perm_of(wl[0])->h, &perm_of(wl[i])->h)) return -1;
+    return 1;
+}
+// entry points that do not serve act-order handles: refused by name
+static int32_t refuse_perm(const tmac_hip_weights* const* wl, int nmat, const char* what) {
+    for (int i = 0; wl && i < nmat; ++i)
+        if (perm_of(wl[i])) return fail(TMAC_HIP_E_ARG, "matrix %d carries a K permutation (act-order): %s on such handles is not served yet", i, what);
+    return TMAC_HIP_OK;
+}
+
 // ---- split entry point -----------------------------------------------------------------------------------------------------
 int32_t tmac_host::qgemm_impl(const tmac_hip_weights* w, const tmac_hip_workspace* ws, void* C_dev, tmac_dtype_t out_dtype,
                           int N, int32_t* dump, hipStream_t st) {
@@ -295,6 +318,9 @@ int32_t tmac_host::qgemm_impl(const tmac_hip_weights* w, const tmac_hip_workspac
     if (ws->K != w->s.K || ws->ags != w->s.ags)
         return fail(TMAC_HIP_E_ARG, "workspace LUT (K=%d, ags=%d) does not match the weights (K=%d, ags=%d)", ws->K, ws->ags, w->s.K, w->s.ags);
     if (N <= 0 || N > ws->N) return fail(TMAC_HIP_E_ARG, "N=%d but the workspace LUT holds %d rows", N, ws->N);
+    if (perm_id_of(w) != ws->perm_id)
+        return fail(TMAC_HIP_E_ARG, perm_of(w) ? "the weights carry a K permutation (act-order) but the workspace LUT was not built through it (tmac_hip_preprocessor_perm_dev)"
+                                               : "the workspace LUT was built through a K permutation the weights do not carry");
     const Plan p = plan_split(w, ws, N, dump != nullptr);
     if (p.err) return fail(p.err, p.msg, p.mat);
     count_route(p.route);
@@ -515,8 +541,9 @@ static void fill_xf_rows_args(XfRowsGateArgs& xa, const XfSpec& s, float* r) {
     xa.in2 = s.in2; xa.residual = s.residual; xa.gamma = s.gamma; xa.residual_out = s.residual_out; xa.r = r;
 }
 // spec: the call carries a vector transform (N >= 2, plan from xf_rows_plan): the row pass, then the planned LUT build's XF instantiation
+// kp: the matrices carry this K permutation (N >= 2, plan from xf_rows_plan, never with spec): the planned LUT build's gather instantiation
 static int32_t fused_prefill(Plan p, const tmac_hip_weights* const* wl, int nmat, const void* B_dev, tmac_dtype_t act_dtype,
-                             void* const* C_list, tmac_dtype_t out_dtype, int N, hipStream_t st, const XfSpec* spec = nullptr) {
+                             void* const* C_list, tmac_dtype_t out_dtype, int N, hipStream_t st, const XfSpec* spec = nullptr, const KPermData* kp = nullptr) {
     const Shape& s0 = wl[0]->s;
     tmac_hip_workspace* ws = nullptr;
     {
@@ -541,7 +568,7 @@ static int32_t fused_prefill(Plan p, const tmac_hip_weights* const* wl, int nmat
     }
     if (p.route == R_GEMM_PLANES && !planes_image_fits(ws, s0.K)) {   // (see image_fits at the planners)
         p = plan_fused(wl, C_list, nmat, N, false, false);
-        if (spec) {
+        if (spec || kp) {
             p = xf_rows_plan(p);
             if (p.err) return fail(p.err, p.msg, p.mat);
         }
@@ -552,6 +579,8 @@ static int32_t fused_prefill(Plan p, const tmac_hip_weights* const* wl, int nmat
     hipError_t e = hipSuccess;
     XfRowsGateArgs xa;
     XfRowsGateArgs* const xf = spec ? &xa : nullptr;
+    const int32_t* const perm = kp ? kp->dev : nullptr;
+    ws->perm_id = kp ? kp->h.id : 0;      // what the row loop's tmac_hip_qgemm_dev holds the matrices to
     if (spec) {
         fill_xf_rows_args(xa, *spec, ws->xf_r);
         if (xf_needs_row_pass(*spec)) {
@@ -563,13 +592,13 @@ static int32_t fused_prefill(Plan p, const tmac_hip_weights* const* wl, int nmat
         ws->K = 0; ws->N = 0; ws->gimg_valid = false;      // the other layouts of this workspace are not built
         e = s0.m_groups >= 1
             ? launch_preprocess_pairs_row(B_dev, f16, ws->qlut_lds, ws->lut_scales, ws->lut_biases, s0.K, N, nullptr, nullptr, 0, ws->gimg, ws->gcol, ws->gNpad, st, xf)
-            : launch_lut_image(B_dev, f16, ws->gimg, ws->gcol, s0.K, N, ws->gNpad, st, xf);
+            : launch_lut_image(B_dev, f16, ws->gimg, ws->gcol, s0.K, N, ws->gNpad, st, xf, perm);
         if (e != hipSuccess) return fail(TMAC_HIP_E_RUNTIME, "LUT image launch: %s", hipGetErrorString(e));
     } else if (p.lut == LB_HALF_TABLES) {
         ws->K = s0.K; ws->N = N; ws->ags = s0.ags; ws->qdev_u4_per_row = qdev_u4_for_K(s0.K);
         ws->gimg_valid = false;      // an image an earlier call left on the stream was not built from this call's rows
         e = s0.ags == 64
-            ? launch_preprocess_pairs(B_dev, f16, ws->qlut_lds, ws->lut_scales, ws->lut_biases, s0.K, N, nullptr, nullptr, 0, st, xf)
+            ? launch_preprocess_pairs(B_dev, f16, ws->qlut_lds, ws->lut_scales, ws->lut_biases, s0.K, N, nullptr, nullptr, 0, st, xf, perm)
             : launch_preprocess_pairs_row(B_dev, f16, ws->qlut_lds, ws->lut_scales, ws->lut_biases, s0.K, N, nullptr, nullptr, 0, nullptr, nullptr, 0, st, xf);
         if (e != hipSuccess) return fail(TMAC_HIP_E_RUNTIME, "preprocess launch: %s", hipGetErrorString(e));
     } else {
@@ -594,6 +623,42 @@ static int32_t out_align_check(void* const* C_list, int nmat, tmac_dtype_t out_d
             return fail(TMAC_HIP_E_ARG, "C_dev[%d] must be %zu-byte aligned (four outputs are stored at a time)", i, out_align(out_dtype));
     return TMAC_HIP_OK;
 }
+// A fused call on matrices that all carry the same K permutation (fused_impl has checked that, the arguments and the alignment).  Behind
+// the calling thread's deferred queue, stand-alone, like a call of several rows.  N = 1: k_gemv_quad's gather instantiations (the covered
+// configurations and the fall-back of a transformed call).  N >= 2: routed as tmac_hip_qgemm_fused_xf_rows_dev routes a transformed call
+// (xf_rows_plan), the planned LUT build gathering.
+static int32_t fused_perm(const tmac_hip_weights* const* wl, int nmat, const void* B_dev, tmac_dtype_t act_dtype, void* const* C_list,
+                          tmac_dtype_t out_dtype, int N, hipStream_t st) {
+    const KPermData* kp = perm_of(wl[0]);
+    for (int i = 0; i < nmat; ++i) {
+        const tmac_hip_weights* w = wl[i];
+        if (!C_list[i]) return fail(TMAC_HIP_E_ARG, "null matrix or output");
+        if (g_knobs.variant == V_REF_LAYOUT || g_knobs.variant == V_QUAD_MQSAD || layout_of(w->s) != L_QUAD || !w->tiled_ok || w->fa || !gemv_quad_supported(w->s) ||
+            w->s.m_groups >= 1)
+            return fail(TMAC_HIP_E_NOMATCH, "matrix %d: act-order handles run on k_gemv_quad's MFMA form and the prefill kernels behind it (QUAD layout, per-group scales)", i);
+        if (!same_lut(w, wl[0]) || !same_quant(w, wl[0])) return fail(TMAC_HIP_E_ARG, "matrices fused in one launch must share K, bits and quantisation config");
+    }
+    Plan p = plan_fused(wl, C_list, nmat, N, false);
+    if (N >= 2) p = xf_rows_plan(p);
+    if (p.err) return fail(p.err, p.msg, p.mat);
+    if (N == 1 && p.route != R_GEMV_QUAD) return fail(TMAC_HIP_E_NOMATCH, "act-order handles of one row run on k_gemv_quad only");
+    const int32_t brc = defer_barrier();
+    if (brc) return brc;
+    if (N >= 2) return fused_prefill(p, wl, nmat, B_dev, act_dtype, C_list, out_dtype, N, st, nullptr, kp);
+    count_route(p.route);
+    FusedPermArgs fa;
+    const int nb = fill_fused_args(fa, wl, C_list, nmat, out_dtype, nullptr);
+    fa.B = B_dev; fa.act_f16 = act_dtype == TMAC_F16;
+    fa.perm = kp->dev;
+    // the launch configuration: forced (tmac_hip_debug_quad_config) -- it must have a gather instantiation -- else tuned, else the heuristic
+    int ft = g_knobs.force_ft, wpq = g_knobs.force_wpq;
+    const bool strict = ft || wpq;
+    if (!strict) tuned_config(fa, nb, ft, wpq);
+    const hipError_t e = launch_gemv_quad_perm(fa, ft, wpq, strict, st);
+    if (e == hipErrorInvalidValue) return fail(TMAC_HIP_E_NOMATCH, "no gathering GEMV kernel for this configuration (gather instantiations: (512,1), (512,2), (768,3), (1024,4))");
+    if (e != hipSuccess) return fail(TMAC_HIP_E_RUNTIME, "gathering gemv launch: %s", hipGetErrorString(e));
+    return TMAC_HIP_OK;
+}
 int32_t tmac_host::fused_impl(const tmac_hip_weights* const* wl, int nmat, const void* B_dev, tmac_dtype_t act_dtype,
                           void* const* C_list, tmac_dtype_t out_dtype, int N, int32_t* dump, float* lut_tap, hipStream_t st) {
     bind_thread_device();
@@ -610,6 +675,14 @@ int32_t tmac_host::fused_impl(const tmac_hip_weights* const* wl, int nmat, const
         return arc;
     }
     const bool tap = dump || lut_tap;
+    const int ps = perm_state(wl, nmat);
+    if (ps != 0) {        // act-order handles: never recorded, never queued, never tapped
+        if (chain_recording()) chain_clear_xform();
+        if (ps < 0) return fail(TMAC_HIP_E_ARG, "matrices fused in one launch must share the K permutation");
+        if (tap) return refuse_perm(wl, nmat, "a parity tap");
+        if (chain_recording()) return refuse_perm(wl, nmat, "a recorded call (tmac_hip_chain_begin ... _end)");
+        return fused_perm(wl, nmat, B_dev, act_dtype, C_list, out_dtype, N, st);
+    }
     if (chain_recording() && !tap) return chain_record(wl, nmat, B_dev, act_dtype, C_list, out_dtype, N);
     if (!tap) {           // deferred launches: queued until tmac_hip_flush (or a call that depends on a queued one)
         int32_t drc;
@@ -670,6 +743,7 @@ extern "C" int32_t tmac_hip_qgemm_fused_xf_dev(const tmac_hip_weights* const* wl
     int32_t rc = xf_resolve(xf, XF_SITE_N1, &spec);
     if (rc) return rc;
     if (!wl || !C_list || !B_dev || nmat < 1 || nmat > 4) return fail(TMAC_HIP_E_ARG, "bad fused arguments (1..4 matrices)");
+    if ((rc = refuse_perm(wl, nmat, "a vector transform")) != TMAC_HIP_OK) return rc;
     if ((rc = act_align_check(B_dev)) != TMAC_HIP_OK || (rc = out_align_check(C_list, nmat, out_dtype)) != TMAC_HIP_OK) return rc;
     const Plan p = plan_fused(wl, C_list, nmat, 1, false);
     if (p.err) return fail(p.err, p.msg, p.mat);
@@ -714,7 +788,9 @@ extern "C" int32_t tmac_hip_qgemm_fused_xf_rows_dev(const tmac_hip_weights* cons
     if (!wl || !C_list || !B_dev || nmat < 1 || nmat > 4 || N < 1) return fail(TMAC_HIP_E_ARG, "bad fused arguments (1..4 matrices)");
     for (int i = 0; i < nmat; ++i)
         if (!wl[i] || !C_list[i]) return fail(TMAC_HIP_E_ARG, "null matrix or output");
-    int32_t rc = out_align_check(C_list, nmat, out_dtype);
+    int32_t rc = refuse_perm(wl, nmat, "a vector transform");
+    if (rc) return rc;
+    rc = out_align_check(C_list, nmat, out_dtype);
     if (rc) return rc;
     const Shape& s0 = wl[0]->s;
     XfSpec spec;

@@ -100,10 +100,12 @@ __global__ __launch_bounds__(256) void k_lut_image(const void* __restrict__ B, u
     }
 }
 
-hipError_t launch_lut_image(const void* B, int act_f16, void* bimg, float* colv, int K, int N, int Npad, hipStream_t st, const XfRowsGateArgs* xf) {
-    if (K % 64 != 0 || N < 1 || Npad < N || Npad % 64 != 0) return hipErrorInvalidValue;
+hipError_t launch_lut_image(const void* B, int act_f16, void* bimg, float* colv, int K, int N, int Npad, hipStream_t st, const XfRowsGateArgs* xf,
+                            const int32_t* perm) {
+    if (K % 64 != 0 || N < 1 || Npad < N || Npad % 64 != 0 || (xf && perm)) return hipErrorInvalidValue;
     dim3 g(Npad / 32, K / 64), b(256);
     return sel_bool(act_f16 != 0, [&](auto F16) {
+        if (perm) return launch_lds(k_lut_image<F16.value, true, GatherRowsArgs>, g, b, 0, st, B, (uint4*)bimg, colv, K, N, Npad, GatherRowsArgs{perm});      // act-order: the gathered build
         if (xf) return sel_xf_block(*xf, [&](const auto& blk) {
             return launch_lds(k_lut_image<F16.value, true, std::decay_t<decltype(blk)>>, g, b, 0, st, B, (uint4*)bimg, colv, K, N, Npad, blk);
         });

@@ -4,6 +4,7 @@
 //   tmac_runtime.cpp     error text, device binding, the knob block, lifecycle, self-tests, tmac_hip_reset_state
 //   tmac_kcfg.cpp        the kcfg.ini table and its lookups
 //   tmac_weights.cpp     weight registration (reference layout -> device layout)
+//   tmac_kperm.cpp       the K permutation of act-order matrices from g_idx (tmac_kperm.h: no HIP, builds with plain g++); its C-ABI: tmac_pack_host.cpp
 //   tmac_pack_host.cpp   device-side packing: GPTQ tensors / plain codes -> reference blob (tmac_pack.hip) -> register_impl
 //   tmac_workspace.cpp   LUT workspace + the preprocessor entry point
 //   tmac_xform.cpp       the field rules of tmac_hip_xform: one resolver for every transform site (tmac_xform.h: no HIP, builds with plain g++)
@@ -31,6 +32,7 @@
 #include <cstring>
 #include <fstream>
 #include <map>
+#include <memory>
 #include <mutex>
 #include <shared_mutex>
 #include <sstream>
@@ -40,9 +42,19 @@
 #include "../../include/tmac_hip.h"
 #include "tmac_chain.h"
 #include "tmac_kernels.h"
+#include "tmac_kperm.h"
 #include "tmac_xform.h"
 
 // ---- the C-ABI's opaque objects ---------------------------------------------------------------
+// The K permutation of act-order matrices (tmac_kperm.h): host copy, hash, and the device copy the gathers read (int32 [K], hipMalloc:
+// 256-byte aligned).  Shared: the caller's object and every handle registered through it hold one reference each.
+struct KPermData {
+    tmac_host::KPermHost h;
+    int32_t* dev = nullptr;
+    ~KPermData() { if (dev) (void)hipFree(dev); }
+};
+struct tmac_hip_kperm { std::shared_ptr<KPermData> d; };
+
 struct tmac_hip_weights {
     tmac::Shape s;
     void* W = nullptr;      // device layout weights
@@ -54,6 +66,7 @@ struct tmac_hip_weights {
     bool tiled_ok = false;  // W / SC hold the device layout s names (layout_of) and its tiled kernel covers the configuration; else only the reference blobs serve
     int fa = 0;             // fast-aggregation mode these weights were registered under (0 = exact)
     size_t w_bytes = 0, sc_bytes = 0;
+    std::shared_ptr<KPermData> kperm;   // act-order: the matrix is W[:, perm] and every LUT build gathers x[perm]; null = none
 };
 
 struct tmac_hip_workspace {
@@ -75,6 +88,7 @@ struct tmac_hip_workspace {
     float* xf_r = nullptr;       // fp32 [maxN]: 1 / rms per activation row of a transformed N > 1 call (k_xf_rows -> the XF LUT builders)
     int gimg_kind = 0;           // 1: row-wise image (one act group per row, k_gemm_planes_us) | 2: chunk-major image (act groups of 64, k_gemm_planes)
     int gimg_K = 0, gimg_N = 0;  // the activation rows the valid image was built from: it serves the LUT above only while these equal K and N
+    uint64_t perm_id = 0;        // id of the K permutation the LUT was built through (tmac_hip_preprocessor_perm_dev); 0 = none: every other build and write
 };
 
 namespace tmac_host {

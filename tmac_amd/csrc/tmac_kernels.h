@@ -60,6 +60,12 @@ struct FusedXfArgs : FusedArgs {
     float eps;
 };
 
+// k_gemv_quad's gather instantiations (a fused N = 1 call on act-order handles): the LUT build loads x[perm[k']] for position k'.  An argument
+// block of its own: the plain instantiations keep theirs.
+struct FusedPermArgs : FusedArgs {
+    const int32_t* perm;     // int32 [K], every value < K, 16-byte aligned (tmac_hip_kperm)
+};
+
 // The same transforms for N > 1 activation rows (tmac_hip_qgemm_fused_xf_rows_dev): the argument block of k_xf_rows (the row pass: residual_out
 // and 1 / rms per row) and of the XF instantiations of the three N > 1 LUT builders (k_lut_image, k_preprocess_pairs, k_preprocess_pairs_row),
 // which replace their activation load by xf_rows_x8 (tmac_quad_core.h).  Row n of every [N][K] operand is read for row n of the activations.
@@ -143,11 +149,12 @@ hipError_t launch_selftest_permlane(const uint32_t* in, uint32_t* out, hipStream
 hipError_t launch_retile_weights(const uint8_t* A_ref, void* Wd, const Shape& s, hipStream_t st);
 hipError_t launch_retile_scales(const void* S_ref, Dtype in_dt, void* Sd, Dtype out_dt, const Shape& s, hipStream_t st);
 // device-side packing (tmac_pack.hip): GPTQ tensors (bits 1, 2, 4; per-group scales) or plain codes (bits 1-4) -> the reference blob halves
-// A_out (ref_weight_bytes) and S_out (ref_scale_elems values of out_dt).  qzeros / zeros NULL = no zero points.
+// A_out (ref_weight_bytes) and S_out (ref_scale_elems values of out_dt).  qzeros / zeros NULL = no zero points.  perm (device, int32 [K],
+// every value < K, 16-byte aligned; NULL = none): act-order -- the blob of the matrix whose column k' is source column perm[k'].
 hipError_t launch_pack_gptq(const void* qweight, const void* scales, const void* qzeros, Dtype scales_dt, int gptq_v2, void* A_out, void* S_out,
-                            Dtype out_dt, const Shape& s, hipStream_t st);
+                            Dtype out_dt, const Shape& s, hipStream_t st, const int32_t* perm = nullptr);
 hipError_t launch_pack_codes(const void* codes, const void* scales, const void* zeros, Dtype sz_dt, void* A_out, void* S_out, Dtype out_dt,
-                             const Shape& s, hipStream_t st);
+                             const Shape& s, hipStream_t st, const int32_t* perm = nullptr);
 hipError_t launch_preprocess(const void* B, Dtype act_dt, int8_t* qlut_ref, void* qlut_dev, void* qlut_lds, float* lut_scales,
                              float* lut_biases, int K, int N, int ags, size_t qdev_u4_per_row, hipStream_t st);
 // all-gather over IPC-mapped windows (tmac_comm.cpp, transport "ipc"): workgroup p of `world` handles rank p's part
@@ -168,7 +175,10 @@ hipError_t launch_qlut_ref_to_dev(const int8_t* qlut_ref, void* qlut_dev, void* 
 // pair-wise LUT build (tmac_prefill_lut.hip; ags = 64): the half-table image + LUT scales/biases, and -- when qlut_ref / qlut_dev are
 // given (both or neither) -- the other two layouts of the workspace as well
 hipError_t launch_preprocess_pairs(const void* B, int act_f16, void* qlut_lds, float* lut_scales, float* lut_biases, int K, int N,
-                                   int8_t* qlut_ref, void* qlut_dev, size_t qdev_u4_per_row, hipStream_t st, const XfRowsGateArgs* xf = nullptr);
+                                   int8_t* qlut_ref, void* qlut_dev, size_t qdev_u4_per_row, hipStream_t st, const XfRowsGateArgs* xf = nullptr,
+                                   const int32_t* perm = nullptr);
+// (perm, here and at launch_lut_image: the gather instantiation of an act-order permutation -- x = row n read through perm (device, int32 [K],
+// every value < K, 16-byte aligned) instead of the row itself; never together with xf; with qlut_ref / qlut_dev it writes every layout)
 // the same for act_group_size = K (one act group per activation row; K <= 12288)
 // bimg / colv (both or neither; Npad = row stride of the image): also the LUT image k_gemm_planes_us streams (tmac_gemm2.hip)
 hipError_t launch_preprocess_pairs_row(const void* B, int act_f16, void* qlut_lds, float* lut_scales, float* lut_biases, int K, int N,
@@ -187,7 +197,8 @@ hipError_t launch_host_flag(uint32_t* flag, uint32_t val, hipStream_t st);   // 
 bool gemm_onehot_supported(const Shape& s);
 hipError_t launch_gemm_onehot(const GemmArgs& a, hipStream_t st);
 bool gemm_planes_supported(const Shape& s);
-hipError_t launch_lut_image(const void* B, int act_f16, void* bimg, float* colv, int K, int N, int Npad, hipStream_t st, const XfRowsGateArgs* xf = nullptr);
+hipError_t launch_lut_image(const void* B, int act_f16, void* bimg, float* colv, int K, int N, int Npad, hipStream_t st, const XfRowsGateArgs* xf = nullptr,
+                            const int32_t* perm = nullptr);
 hipError_t launch_gemm_planes(const Gemm2Args& a, hipStream_t st);
 // fused kernel (tmac_fused.hip)
 size_t qlut_lds_u4(int K);   // uint4 per activation row of the LDS-image LUT
@@ -200,8 +211,11 @@ hipError_t launch_gemv_quad(const FusedArgs& a, int N, bool build_lut, int force
 // configuration was forced by the caller and must be covered as it is (hipErrorInvalidValue otherwise) -- else it falls back to the
 // nearest covered one.
 hipError_t launch_gemv_quad_xf(const FusedXfArgs& a, int ft, int wpq, bool strict, hipStream_t st);
+// ... and with the gather of an act-order permutation in its activation loads (N = 1, LUT built in-kernel, MFMA accumulate, per-group
+// scales): the same covered configurations, the same fall-back, the same meaning of strict.
+hipError_t launch_gemv_quad_perm(const FusedPermArgs& a, int ft, int wpq, bool strict, hipStream_t st);
 // the launcher of one translation unit of tmac_quad.hip (defined and instantiated there for its BITS, SCF16 and both argument blocks): the
-// instantiation the plan names; a: precomputed (fused_precompute)
+// instantiation the plan names; a: precomputed (fused_precompute).  (Also for FusedPermArgs.)
 template <int BITS, bool SCF16, class Args>
 hipError_t launch_gemv_quad_unit(const Args& a, const QuadPlan& p, int N, hipStream_t st);
 // rows kernel (tmac_rows.hip): 2-8 activation rows per weight pass on QUAD-layout weights, tables copied from the half-table image

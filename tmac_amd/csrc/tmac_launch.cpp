@@ -39,6 +39,15 @@ hipError_t launch_gemv_quad_xf(const FusedXfArgs& a_in, int ft, int wpq, bool st
     return quad_unit(a, p, 1, st);
 }
 
+hipError_t launch_gemv_quad_perm(const FusedPermArgs& a_in, int ft, int wpq, bool strict, hipStream_t st) {
+    if (a_in.nmat < 1 || a_in.nmat > 4 || !a_in.acc_mfma || a_in.dump || a_in.lut_tap || !a_in.perm) return hipErrorInvalidValue;
+    QuadPlan p;
+    if (!quad_plan_perm(a_in.s, a_in.m[a_in.nmat - 1].nb_end, ft, wpq, strict, p)) return hipErrorInvalidValue;
+    FusedPermArgs a = a_in;
+    fused_precompute(a);
+    return quad_unit(a, p, 1, st);
+}
+
 // *launches (optional) grows by the number of k_gemv_rows launches made
 hipError_t launch_gemv_rows(const RowsArgs& a_in, hipStream_t st, int* launches) {
     RowsArgs a = a_in;

@@ -74,6 +74,7 @@ static bool quad_plan_finish(const Shape& s, int total_q, QuadPlan& p) {
     // one workgroup per CU: overlap the weight stream with the LUT build (see the kernel); grids of the 768- and 1024-thread
     // configurations never exceed one workgroup per CU
     p.early = p.ft != 512 || (p.lutsrc == 1 && p.acc == 1 && !p.dump && p.gx <= 256);
+    if (p.ga) return quad_ga_inst_exists(p.nr, p.ft, p.wpq, p.early);
     return quad_inst_exists(p.lutsrc, p.nr, p.ft, p.wpq, p.dump, p.acc, p.early, p.xf);
 }
 
@@ -85,10 +86,8 @@ bool quad_plan(const Shape& s, int total_q, bool build_lut, bool dump, bool acc_
     return quad_plan_finish(s, total_q, p);
 }
 
-bool quad_plan_xf(const Shape& s, int total_q, int xf_kind, int force_ft, int force_wpq, bool strict, QuadPlan& p) {
-    p = QuadPlan{};
-    if (!gemv_quad_supported(s) || s.K > QUAD_XF_MAX_K) return false;
-    p.lutsrc = 1; p.acc = 1; p.xf = true;
+// the configuration of an XF or GA launch: the heuristic's (or the forced one) where the instantiations cover it, else the fall-back below
+static bool quad_config_covered(const Shape& s, int total_q, int force_ft, int force_wpq, bool strict, QuadPlan& p) {
     if (!quad_config(s, false, total_q, force_ft, force_wpq, p.ft, p.wpq)) return false;
     // A configuration the caller forced (tmac_hip_debug_quad_config) outside the covered set is refused; one the heuristic or the tuned table
     // chose falls back to the nearest covered one: same waves per quad in 512-thread workgroups ((768,1), (1024,1) -> (512,1); (768,2),
@@ -98,9 +97,25 @@ bool quad_plan_xf(const Shape& s, int total_q, int xf_kind, int force_ft, int fo
         if (s.K / 4 > 6 * 512) { p.ft = 1024; p.wpq = 4; }
         else { p.ft = 512; p.wpq = p.wpq >= 2 ? 2 : 1; }
     }
+    return true;
+}
+
+bool quad_plan_xf(const Shape& s, int total_q, int xf_kind, int force_ft, int force_wpq, bool strict, QuadPlan& p) {
+    p = QuadPlan{};
+    if (!gemv_quad_supported(s) || s.K > QUAD_XF_MAX_K) return false;
+    p.lutsrc = 1; p.acc = 1; p.xf = true;
+    if (!quad_config_covered(s, total_q, force_ft, force_wpq, strict, p)) return false;
     // GLU_NORM has instantiations of its own (GN): the ones NORM and GLU run on stay as they were; and relu^2 and GELU have theirs (GT), next
     // to both: a call with silu runs what it ran
     p.gn = (xf_kind & 0xff) == 4; p.gt = (xf_kind >> 8) != 0;
+    return quad_plan_finish(s, total_q, p);
+}
+
+bool quad_plan_perm(const Shape& s, int total_q, int force_ft, int force_wpq, bool strict, QuadPlan& p) {
+    p = QuadPlan{};
+    if (!gemv_quad_supported(s) || s.m_groups >= 1 || s.K > QUAD_XF_MAX_K) return false;
+    p.lutsrc = 1; p.acc = 1; p.ga = true;
+    if (!quad_config_covered(s, total_q, force_ft, force_wpq, strict, p)) return false;
     return quad_plan_finish(s, total_q, p);
 }
 

@@ -50,6 +50,10 @@ constexpr bool quad_inst_exists(int lutsrc, int nr, int ft, int wpq, bool dump, 
     return ft == 512 ? (!early || production) : (production && early);
 }
 
+// The gather of an act-order permutation (GA) lives where the transform lives -- the in-kernel LUT build of the MFMA form, in the covered
+// configurations, no tap -- and never together with one.
+constexpr bool quad_ga_inst_exists(int nr, int ft, int wpq, bool early) { return quad_inst_exists(1, nr, ft, wpq, false, 1, early, true); }
+
 struct QuadPlan {
     int ft, wpq;             // threads, waves per quad
     int nr;                  // tables built per thread (2 | 6)
@@ -59,6 +63,7 @@ struct QuadPlan {
     bool xf, gn, gt;         // vector transform; its GLU_NORM form; its gate a run-time choice
     int gx;                  // grid (x)
     size_t lds_bytes;
+    bool ga;                 // the gather of an act-order permutation in the activation loads (never with xf)
 };
 constexpr int QUAD_XF_MAX_K = 24576;
 size_t quad_lds_bytes(const Shape& s, int nwv);
@@ -70,6 +75,8 @@ bool quad_plan(const Shape& s, int total_q, bool build_lut, bool dump, bool acc_
 // xf_kind: tmac_hip_xform::kind as it comes (kind | gate << 8).  strict: the configuration was forced by the caller and must be covered as
 // it is; else one outside the covered set falls back to the nearest covered one.
 bool quad_plan_xf(const Shape& s, int total_q, int xf_kind, int force_ft, int force_wpq, bool strict, QuadPlan& p);
+// the gather instantiations: quad_plan_xf's configuration rule (covered set, fall-back, strict), per-group scales only
+bool quad_plan_perm(const Shape& s, int total_q, int force_ft, int force_wpq, bool strict, QuadPlan& p);
 
 // ---- k_gemv_rows --------------------------------------------------------------------------------------------------------------------
 constexpr int ROWS_FT = 512, ROWS_NWV = ROWS_FT / 64;

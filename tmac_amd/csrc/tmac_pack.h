@@ -64,6 +64,13 @@ TMAC_PACK_HD uint32_t gptq_plane(uint32_t word, int p, int bits) {
 // field i of a packed row (qzeros: column m of row sg is field m % (32 / bits) of word m * bits / 32)
 TMAC_PACK_HD uint32_t gptq_field(uint32_t word, int i, int bits) { return (word >> (i * bits)) & ((1u << bits) - 1u); }
 
+// Act-order (packing through a K permutation, tmac_kperm.h): table t of the packed matrix takes its four codes from the SOURCE columns
+// perm[4 t .. 4 t + 3].  GPTQ: the code of source column k sits in qweight word row k / (32 / bits) at bit (k % (32 / bits)) * bits.
+TMAC_PACK_HD int gptq_word_row(int k, int bits) { return k / (32 / bits); }
+TMAC_PACK_HD uint32_t gptq_code(uint32_t word, int k, int bits) { return gptq_field(word, k % (32 / bits), bits); }
+// four gathered codes -> the `four` codes_nibble takes (code i in byte i)
+TMAC_PACK_HD uint32_t codes_four(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3) { return c0 | (c1 << 8) | (c2 << 16) | (c3 << 24); }
+
 // T-MAC's zero as a multiplier of the scale: z + (v1 ? 1 : 0) - 2^(bits-1), exact in fp16 and fp32 (convert.py:unpack_gptq; AutoGPTQ v1
 // stores z - 1).  The zero itself is multiplier * scale, rounded ONCE to the scales' dtype: the fp32 product of an fp16 scale and this
 // small integer is exact, so one conversion to fp16 gives numpy's fp16 product (overflow to infinity included).

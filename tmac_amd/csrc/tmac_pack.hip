@@ -112,6 +112,80 @@ __global__ __launch_bounds__(PACK_THREADS) void k_pack_codes_weights(const uint8
     pack_store_tile<BITS>(lds, A_out, Mw, T, bm, kfactor);
 }
 
+// ---- act-order: stage 1 through a K permutation (tmac_kperm.h) ----------------------------------------------------------------------
+// Table t of the tile takes its four codes from the source columns perm[4 t .. 4 t + 3] (one 16-byte load: perm is [K], K a multiple of 4,
+// 16-byte aligned).  Every perm value is < K (tmac_hip_kperm_from_gidx_dev refuses anything else), so the gathers stay inside the inputs;
+// the guards on t and on the weight row are those of the plain kernels.  A thread takes a PAIR of tables and writes the byte that holds
+// their two nibbles itself: no two threads share an LDS byte.  Stage 2 and the scale kernels are the plain ones (scales and zeros are in
+// group order already).  The gather reads a whole qweight word (a whole codes byte) per code: 8 / bits times the plain traffic, once.
+template <int BITS>
+__global__ __launch_bounds__(PACK_THREADS) void k_pack_gptq_weights_perm(const uint32_t* __restrict__ qweight, const int32_t* __restrict__ perm,
+                                                                         uint8_t* __restrict__ A_out, int Mw, int K, int bm, int kfactor) {
+    __shared__ __attribute__((aligned(16))) uint8_t lds[PACK_ROWS * BITS * PACK_STRIDE];
+    const int T = K / 4;
+    const int o0 = blockIdx.y * PACK_ROWS, t0 = blockIdx.x * PACK_TABLES;
+    // consecutive threads take consecutive row quads of one table pair: the 16-byte loads of a source column run along m
+    for (int idx = threadIdx.x; idx < (PACK_TABLES / 2) * (PACK_ROWS / 4); idx += PACK_THREADS) {
+        const int tp = idx / (PACK_ROWS / 4), mq = idx % (PACK_ROWS / 4);
+        const int m = o0 + 4 * mq;
+        uint32_t nib[2][4][BITS];      // [table of the pair][row of the quad][plane]
+#pragma unroll
+        for (int h = 0; h < 2; ++h) {
+            const int t = t0 + 2 * tp + h;
+            uint32_t code[4][4] = {};  // [row of the quad][column of the table]
+            if (t < T && m < Mw) {
+                const int4 src = *reinterpret_cast<const int4*>(perm + 4 * (size_t)t);
+                const int k4[4] = {src.x, src.y, src.z, src.w};
+#pragma unroll
+                for (int ig = 0; ig < 4; ++ig) {
+                    const uint4 w4 = *reinterpret_cast<const uint4*>(qweight + (size_t)pk::gptq_word_row(k4[ig], BITS) * Mw + m);   // Mw is a multiple of 8: whole quads
+                    code[0][ig] = pk::gptq_code(w4.x, k4[ig], BITS); code[1][ig] = pk::gptq_code(w4.y, k4[ig], BITS);
+                    code[2][ig] = pk::gptq_code(w4.z, k4[ig], BITS); code[3][ig] = pk::gptq_code(w4.w, k4[ig], BITS);
+                }
+            }
+#pragma unroll
+            for (int c = 0; c < 4; ++c) {
+                const uint32_t four = pk::codes_four(code[c][0], code[c][1], code[c][2], code[c][3]);
+#pragma unroll
+                for (int p = 0; p < BITS; ++p) nib[h][c][p] = pk::codes_nibble(four, p);
+            }
+        }
+#pragma unroll
+        for (int c = 0; c < 4; ++c)
+#pragma unroll
+            for (int p = 0; p < BITS; ++p) lds[lds_row(p, 4 * mq + c) * PACK_STRIDE + tp] = (uint8_t)(nib[0][c][p] | (nib[1][c][p] << 4));
+    }
+    __syncthreads();
+    pack_store_tile<BITS>(lds, A_out, Mw, T, bm, kfactor);
+}
+
+// plain codes uint8 [Mw][K]: one byte load per code; consecutive threads take consecutive table pairs of one weight row
+template <int BITS>
+__global__ __launch_bounds__(PACK_THREADS) void k_pack_codes_weights_perm(const uint8_t* __restrict__ codes, const int32_t* __restrict__ perm,
+                                                                          uint8_t* __restrict__ A_out, int Mw, int K, int bm, int kfactor) {
+    __shared__ __attribute__((aligned(16))) uint8_t lds[PACK_ROWS * BITS * PACK_STRIDE];
+    const int T = K / 4;
+    const int o0 = blockIdx.y * PACK_ROWS, t0 = blockIdx.x * PACK_TABLES;
+    for (int idx = threadIdx.x; idx < PACK_ROWS * (PACK_TABLES / 2); idx += PACK_THREADS) {
+        const int ol = idx / (PACK_TABLES / 2), tp = idx % (PACK_TABLES / 2);
+        const int o = o0 + ol;
+        uint32_t four[2] = {0, 0};
+#pragma unroll
+        for (int h = 0; h < 2; ++h) {
+            const int t = t0 + 2 * tp + h;
+            if (t < T && o < Mw) {
+                const int4 src = *reinterpret_cast<const int4*>(perm + 4 * (size_t)t);
+                const uint8_t* row = codes + (size_t)o * K;
+                four[h] = pk::codes_four(row[src.x], row[src.y], row[src.z], row[src.w]);
+            }
+        }
+#pragma unroll
+        for (int p = 0; p < BITS; ++p) lds[lds_row(p, ol) * PACK_STRIDE + tp] = (uint8_t)(pk::codes_nibble(four[0], p) | (pk::codes_nibble(four[1], p) << 4));
+    }
+    __syncthreads();
+    pack_store_tile<BITS>(lds, A_out, Mw, T, bm, kfactor);
+}
+
 // ---- scales -------------------------------------------------------------------------------------------------------------------------
 // n contiguous elements (a multiple of 16 bytes, 16-byte aligned on both sides) as 16-byte accesses
 template <class T, int N>
@@ -203,14 +277,20 @@ dim3 weight_grid(const Shape& s) { return dim3((unsigned)((s.K / 4 + PACK_TABLES
 }  // namespace
 
 hipError_t launch_pack_gptq(const void* qweight, const void* scales, const void* qzeros, Dtype scales_dt, int gptq_v2, void* A_out, void* S_out,
-                            Dtype out_dt, const Shape& s, hipStream_t st) {
+                            Dtype out_dt, const Shape& s, hipStream_t st, const int32_t* perm) {
     const dim3 g = weight_grid(s), b(PACK_THREADS);
     const uint32_t* qw = (const uint32_t*)qweight;
     uint8_t* A = (uint8_t*)A_out;
-    switch (s.bits) {
+    if (!perm) switch (s.bits) {
         case 1: hipLaunchKernelGGL(k_pack_gptq_weights<1>, g, b, 0, st, qw, A, s.Mw, s.K, s.bm, s.kfactor); break;
         case 2: hipLaunchKernelGGL(k_pack_gptq_weights<2>, g, b, 0, st, qw, A, s.Mw, s.K, s.bm, s.kfactor); break;
         case 4: hipLaunchKernelGGL(k_pack_gptq_weights<4>, g, b, 0, st, qw, A, s.Mw, s.K, s.bm, s.kfactor); break;
+        default: return hipErrorInvalidValue;
+    }
+    else switch (s.bits) {      // act-order: stage 1 through the permutation
+        case 1: hipLaunchKernelGGL(k_pack_gptq_weights_perm<1>, g, b, 0, st, qw, perm, A, s.Mw, s.K, s.bm, s.kfactor); break;
+        case 2: hipLaunchKernelGGL(k_pack_gptq_weights_perm<2>, g, b, 0, st, qw, perm, A, s.Mw, s.K, s.bm, s.kfactor); break;
+        case 4: hipLaunchKernelGGL(k_pack_gptq_weights_perm<4>, g, b, 0, st, qw, perm, A, s.Mw, s.K, s.bm, s.kfactor); break;
         default: return hipErrorInvalidValue;
     }
     hipError_t e = hipGetLastError();
@@ -227,15 +307,22 @@ hipError_t launch_pack_gptq(const void* qweight, const void* scales, const void*
 }
 
 hipError_t launch_pack_codes(const void* codes, const void* scales, const void* zeros, Dtype sz_dt, void* A_out, void* S_out, Dtype out_dt,
-                             const Shape& s, hipStream_t st) {
+                             const Shape& s, hipStream_t st, const int32_t* perm) {
     const dim3 g = weight_grid(s), b(PACK_THREADS);
     const uint8_t* cd = (const uint8_t*)codes;
     uint8_t* A = (uint8_t*)A_out;
-    switch (s.bits) {
+    if (!perm) switch (s.bits) {
         case 1: hipLaunchKernelGGL(k_pack_codes_weights<1>, g, b, 0, st, cd, A, s.Mw, s.K, s.bm, s.kfactor); break;
         case 2: hipLaunchKernelGGL(k_pack_codes_weights<2>, g, b, 0, st, cd, A, s.Mw, s.K, s.bm, s.kfactor); break;
         case 3: hipLaunchKernelGGL(k_pack_codes_weights<3>, g, b, 0, st, cd, A, s.Mw, s.K, s.bm, s.kfactor); break;
         case 4: hipLaunchKernelGGL(k_pack_codes_weights<4>, g, b, 0, st, cd, A, s.Mw, s.K, s.bm, s.kfactor); break;
+        default: return hipErrorInvalidValue;
+    }
+    else switch (s.bits) {      // act-order: stage 1 through the permutation
+        case 1: hipLaunchKernelGGL(k_pack_codes_weights_perm<1>, g, b, 0, st, cd, perm, A, s.Mw, s.K, s.bm, s.kfactor); break;
+        case 2: hipLaunchKernelGGL(k_pack_codes_weights_perm<2>, g, b, 0, st, cd, perm, A, s.Mw, s.K, s.bm, s.kfactor); break;
+        case 3: hipLaunchKernelGGL(k_pack_codes_weights_perm<3>, g, b, 0, st, cd, perm, A, s.Mw, s.K, s.bm, s.kfactor); break;
+        case 4: hipLaunchKernelGGL(k_pack_codes_weights_perm<4>, g, b, 0, st, cd, perm, A, s.Mw, s.K, s.bm, s.kfactor); break;
         default: return hipErrorInvalidValue;
     }
     hipError_t e = hipGetLastError();

@@ -49,43 +49,156 @@ int32_t check_codes(Shape& s, const CodesIn& in, const void* A_out, const void* 
     return pack_check(s, false, args, 5, in.zeros, "zeros", in.sz_dtype, "sz_dtype", Mw, K, bits, cfg, ref_float);
 }
 
-int32_t launch(const Shape& s, const GptqIn& in, void* A_out, void* S_out, tmac_dtype_t ref_float, hipStream_t st) {
-    const hipError_t e = launch_pack_gptq(in.qweight, in.scales, in.qzeros, (Dtype)in.scales_dtype, in.gptq_v2, A_out, S_out, (Dtype)ref_float, s, st);
+// perm: the device copy of an act-order permutation (every value < K), or null
+int32_t launch(const Shape& s, const GptqIn& in, void* A_out, void* S_out, tmac_dtype_t ref_float, hipStream_t st, const int32_t* perm = nullptr) {
+    const hipError_t e = launch_pack_gptq(in.qweight, in.scales, in.qzeros, (Dtype)in.scales_dtype, in.gptq_v2, A_out, S_out, (Dtype)ref_float, s, st, perm);
     return e == hipSuccess ? TMAC_HIP_OK : fail(TMAC_HIP_E_RUNTIME, "pack_gptq: %s", hipGetErrorString(e));
 }
-int32_t launch(const Shape& s, const CodesIn& in, void* A_out, void* S_out, tmac_dtype_t ref_float, hipStream_t st) {
-    const hipError_t e = launch_pack_codes(in.codes, in.scales, in.zeros, (Dtype)in.sz_dtype, A_out, S_out, (Dtype)ref_float, s, st);
+int32_t launch(const Shape& s, const CodesIn& in, void* A_out, void* S_out, tmac_dtype_t ref_float, hipStream_t st, const int32_t* perm = nullptr) {
+    const hipError_t e = launch_pack_codes(in.codes, in.scales, in.zeros, (Dtype)in.sz_dtype, A_out, S_out, (Dtype)ref_float, s, st, perm);
     return e == hipSuccess ? TMAC_HIP_OK : fail(TMAC_HIP_E_RUNTIME, "pack_codes: %s", hipGetErrorString(e));
 }
 
 // pack into the caller's buffers: behind the calling thread's deferred queue like every entry point that writes caller memory
 template <class In>
-int32_t pack_to(const Shape& s, const In& in, void* A_out, void* S_out, tmac_dtype_t ref_float, void* stream) {
+int32_t pack_to(const Shape& s, const In& in, void* A_out, void* S_out, tmac_dtype_t ref_float, void* stream, const int32_t* perm = nullptr) {
     int32_t rc = ensure_device();
     if (rc) return rc;
     rc = defer_barrier();
     if (rc) return rc;
-    return launch(s, in, A_out, S_out, ref_float, (hipStream_t)stream);
+    return launch(s, in, A_out, S_out, ref_float, (hipStream_t)stream, perm);
 }
 
 // Pack into temporaries, register from them, free them.  register_impl uses device sources in place when it keeps no reference copy and
 // copies them otherwise; either way the temporaries stay ours, and no work that names them is in flight once it has synchronised.
+// kperm (act-order): the pack reads through it, and the new handle shares its ownership.
 template <class In>
 int32_t register_from(tmac_hip_weights** out, const Shape& s, const In& in, int Mw, int K, int bits, const tmac_kcfg* cfg, tmac_dtype_t ref_float,
-                      tmac_dtype_t dev_float, void* stream) {
+                      tmac_dtype_t dev_float, void* stream, const std::shared_ptr<KPermData>& kperm = nullptr) {
     int32_t rc = ensure_device();
     if (rc) return rc;
     hipStream_t st = (hipStream_t)stream;
     DevBuf dA, dS;      // freed on every return path; hipFree waits for the device, so also after a failure in front of the synchronise
     HIP_TRY(dA.alloc(ref_weight_bytes(s)));
     HIP_TRY(dS.alloc(ref_scale_elems(s) * dt_size((Dtype)ref_float)));
-    rc = launch(s, in, dA.p, dS.p, ref_float, st);
+    rc = launch(s, in, dA.p, dS.p, ref_float, st, kperm ? kperm->dev : nullptr);
     if (rc == TMAC_HIP_OK) rc = register_impl(out, dA.p, dS.p, true, Mw, K, bits, cfg, ref_float, dev_float, stream);
     if (rc != TMAC_HIP_OK) (void)hipStreamSynchronize(st);
+    else (*out)->kperm = kperm;
     return rc;
 }
 
+// What a permuted pack adds to the argument rules of its plain twin: per-group scales, and the permutation's K and group size are the
+// call's.  (A null or identity permutation never gets here: the plain twin is called.)
+int32_t check_perm(const Shape& s, const tmac_hip_kperm* perm) {
+    if (s.m_groups >= 1) return fail(TMAC_HIP_E_ARG, "m_groups = %d: unified-scale weights take no K permutation", s.m_groups);
+    const KPermHost& h = perm->d->h;
+    if (h.K != s.K || h.gs != s.gs)
+        return fail(TMAC_HIP_E_ARG, "the K permutation was built for K=%d, group_size=%d; the call has K=%d, group_size=%d", h.K, h.gs, s.K, s.gs);
+    return TMAC_HIP_OK;
+}
+bool perm_is_plain(const tmac_hip_kperm* perm) { return !perm || !perm->d || perm->d->h.identity; }
+
 }  // namespace
+
+// ---- the K permutation object (tmac_kperm.h: the rules; here: the device copies and the lifetime) -----------------------------------------
+extern "C" int32_t tmac_hip_kperm_from_gidx_dev(const int32_t* g_idx_dev, int K, int group_size, tmac_hip_kperm** out, void* stream) {
+    if (!out) return fail(TMAC_HIP_E_ARG, "out is NULL");
+    if (!g_idx_dev) return fail(TMAC_HIP_E_ARG, "g_idx_dev is NULL");
+    if (misaligned(g_idx_dev, PACK_ALIGN)) return fail(TMAC_HIP_E_ARG, "g_idx_dev is not %zu-byte aligned", PACK_ALIGN);
+    if (K <= 0 || group_size <= 0) return fail(TMAC_HIP_E_ARG, "g_idx: K=%d and group_size=%d must be positive", K, group_size);
+    int32_t rc = ensure_device();
+    if (rc) return rc;
+    rc = defer_barrier();       // g_idx_dev may have been written by queued work
+    if (rc) return rc;
+    hipStream_t st = (hipStream_t)stream;
+    std::vector<int32_t> g((size_t)K);
+    HIP_TRY(hipMemcpyAsync(g.data(), g_idx_dev, sizeof(int32_t) * (size_t)K, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    auto d = std::make_shared<KPermData>();
+    rc = kperm_build(g.data(), K, group_size, &d->h);
+    if (rc) return rc;
+    HIP_TRY(hipMalloc((void**)&d->dev, sizeof(int32_t) * (size_t)K));
+    HIP_TRY(hipMemcpyAsync(d->dev, d->h.perm.data(), sizeof(int32_t) * (size_t)K, hipMemcpyHostToDevice, st));
+    HIP_TRY(hipStreamSynchronize(st));      // the host copy is pageable: done before anyone can free the object
+    *out = new tmac_hip_kperm{std::move(d)};
+    return TMAC_HIP_OK;
+}
+
+extern "C" int32_t tmac_hip_kperm_info(const tmac_hip_kperm* p, int* K, int* identity, uint64_t* id) {
+    if (!p || !p->d) return fail(TMAC_HIP_E_ARG, "null permutation");
+    if (K) *K = p->d->h.K;
+    if (identity) *identity = p->d->h.identity ? 1 : 0;
+    if (id) *id = p->d->h.id;
+    return TMAC_HIP_OK;
+}
+
+extern "C" int32_t tmac_hip_kperm_read(const tmac_hip_kperm* p, int32_t* perm_host) {
+    if (!p || !p->d || !perm_host) return fail(TMAC_HIP_E_ARG, "null argument");
+    memcpy(perm_host, p->d->h.perm.data(), sizeof(int32_t) * (size_t)p->d->h.K);
+    return TMAC_HIP_OK;
+}
+
+extern "C" int32_t tmac_hip_kperm_free(tmac_hip_kperm* p) {
+    delete p;       // the data lives on while a handle registered through it does
+    return TMAC_HIP_OK;
+}
+
+// ---- packing and registration through a permutation: the plain twins' argument lists plus `perm`; null or identity calls the twin --------
+extern "C" int32_t tmac_hip_pack_gptq_perm_dev(const void* qweight, const void* scales, const void* qzeros, tmac_dtype_t scales_dtype, int gptq_v2,
+                                               const tmac_hip_kperm* perm, int Mw, int K, int bits, const tmac_kcfg* cfg, void* A_ref_out,
+                                               void* scales_ref_out, tmac_dtype_t ref_float, void* stream) {
+    if (perm_is_plain(perm))
+        return tmac_hip_pack_gptq_dev(qweight, scales, qzeros, scales_dtype, gptq_v2, Mw, K, bits, cfg, A_ref_out, scales_ref_out, ref_float, stream);
+    const GptqIn in{qweight, scales, qzeros, scales_dtype, gptq_v2};
+    Shape s;
+    int32_t rc = check_gptq(s, in, A_ref_out, scales_ref_out, true, Mw, K, bits, cfg, ref_float);
+    if (rc == TMAC_HIP_OK) rc = check_perm(s, perm);
+    return rc ? rc : pack_to(s, in, A_ref_out, scales_ref_out, ref_float, stream, perm->d->dev);
+}
+
+extern "C" int32_t tmac_hip_pack_codes_perm_dev(const void* codes, const void* scales, const void* zeros, tmac_dtype_t sz_dtype,
+                                                const tmac_hip_kperm* perm, int Mw, int K, int bits, const tmac_kcfg* cfg, void* A_ref_out,
+                                                void* scales_ref_out, tmac_dtype_t ref_float, void* stream) {
+    if (perm_is_plain(perm)) return tmac_hip_pack_codes_dev(codes, scales, zeros, sz_dtype, Mw, K, bits, cfg, A_ref_out, scales_ref_out, ref_float, stream);
+    const CodesIn in{codes, scales, zeros, sz_dtype};
+    Shape s;
+    int32_t rc = check_codes(s, in, A_ref_out, scales_ref_out, true, Mw, K, bits, cfg, ref_float);
+    if (rc == TMAC_HIP_OK) rc = check_perm(s, perm);
+    return rc ? rc : pack_to(s, in, A_ref_out, scales_ref_out, ref_float, stream, perm->d->dev);
+}
+
+extern "C" int32_t tmac_hip_register_weights_gptq_perm_dev(tmac_hip_weights** out, const void* qweight, const void* scales, const void* qzeros,
+                                                           tmac_dtype_t scales_dtype, int gptq_v2, const tmac_hip_kperm* perm, int Mw, int K, int bits,
+                                                           const tmac_kcfg* cfg, tmac_dtype_t ref_float, tmac_dtype_t dev_float, void* stream) {
+    if (perm_is_plain(perm))
+        return tmac_hip_register_weights_gptq_dev(out, qweight, scales, qzeros, scales_dtype, gptq_v2, Mw, K, bits, cfg, ref_float, dev_float, stream);
+    if (!out) return fail(TMAC_HIP_E_ARG, "out is NULL");
+    const GptqIn in{qweight, scales, qzeros, scales_dtype, gptq_v2};
+    Shape s;
+    int32_t rc = check_gptq(s, in, nullptr, nullptr, false, Mw, K, bits, cfg, ref_float);
+    if (rc == TMAC_HIP_OK) rc = check_perm(s, perm);
+    return rc ? rc : register_from(out, s, in, Mw, K, bits, cfg, ref_float, dev_float, stream, perm->d);
+}
+
+extern "C" int32_t tmac_hip_register_weights_codes_perm_dev(tmac_hip_weights** out, const void* codes, const void* scales, const void* zeros,
+                                                            tmac_dtype_t sz_dtype, const tmac_hip_kperm* perm, int Mw, int K, int bits,
+                                                            const tmac_kcfg* cfg, tmac_dtype_t ref_float, tmac_dtype_t dev_float, void* stream) {
+    if (perm_is_plain(perm))
+        return tmac_hip_register_weights_codes_dev(out, codes, scales, zeros, sz_dtype, Mw, K, bits, cfg, ref_float, dev_float, stream);
+    if (!out) return fail(TMAC_HIP_E_ARG, "out is NULL");
+    const CodesIn in{codes, scales, zeros, sz_dtype};
+    Shape s;
+    int32_t rc = check_codes(s, in, nullptr, nullptr, false, Mw, K, bits, cfg, ref_float);
+    if (rc == TMAC_HIP_OK) rc = check_perm(s, perm);
+    return rc ? rc : register_from(out, s, in, Mw, K, bits, cfg, ref_float, dev_float, stream, perm->d);
+}
+
+extern "C" int32_t tmac_hip_weights_kperm_id(const tmac_hip_weights* w, uint64_t* id) {
+    if (!w || !id) return fail(TMAC_HIP_E_ARG, "null argument");
+    *id = w->kperm ? w->kperm->h.id : 0;
+    return TMAC_HIP_OK;
+}
 
 extern "C" int32_t tmac_hip_ref_blob_bytes(int Mw, int K, int bits, const tmac_kcfg* cfg, tmac_dtype_t ref_float, size_t* a_bytes, size_t* s_bytes) {
     if (ref_float != TMAC_F32 && ref_float != TMAC_F16) return fail(TMAC_HIP_E_ARG, "ref_float must be TMAC_F32 or TMAC_F16");

@@ -241,12 +241,17 @@ hipError_t launch_preprocess_pairs_row(const void* B, int act_f16, void* qlut_ld
 }
 
 hipError_t launch_preprocess_pairs(const void* B, int act_f16, void* qlut_lds, float* lut_scales, float* lut_biases, int K, int N,
-                                   int8_t* qlut_ref, void* qlut_dev, size_t qdev_u4_per_row, hipStream_t st, const XfRowsGateArgs* xf) {
+                                   int8_t* qlut_ref, void* qlut_dev, size_t qdev_u4_per_row, hipStream_t st, const XfRowsGateArgs* xf, const int32_t* perm) {
     if (K % 64 != 0 || N < 1 || ((qlut_ref == nullptr) != (qlut_dev == nullptr))) return hipErrorInvalidValue;
-    if (xf && qlut_ref) return hipErrorInvalidValue;
+    if ((xf && qlut_ref) || (xf && perm)) return hipErrorInvalidValue;
     const int tstride = (((K / 32) + 15) & ~15) + 1;
     const dim3 g((K / 8 + 255) / 256, N), b(256);
     return sel_bool(act_f16 != 0, [&](auto F16) {
+        // act-order: the gathered build, the image alone or every layout (tmac_hip_preprocessor_perm_dev)
+        if (perm) return sel_bool(qlut_ref != nullptr, [&](auto ALL) {
+            return launch_lds(k_preprocess_pairs<F16.value, ALL.value, true, GatherRowsArgs>, g, b, 0, st, B, (uint4*)qlut_lds, lut_scales, lut_biases, K, tstride,
+                              (uint4*)qlut_ref, (uint2*)qlut_dev, qdev_u4_per_row, GatherRowsArgs{perm});
+        });
         if (xf) return sel_xf_block(*xf, [&](const auto& blk) {
             using T = std::decay_t<decltype(blk)>;
             return launch_lds(k_preprocess_pairs<F16.value, false, true, T>, g, b, 0, st, B, (uint4*)qlut_lds, lut_scales, lut_biases, K, tstride,

@@ -106,9 +106,14 @@ __device__ __forceinline__ void load_q(WFrag<BITS>& f, const FusedArgs& a, const
 // the GN ones the selector cost the six-tables-per-thread forms (K > 4096 at 512 threads) up to 4 VGPRs; inside the shared NORM / GLU ones it
 // cost no register, but the silu GLU of llama-2-7B's down 0.14 us in 8.2, outside the spread of the parent's runs
 // (profiles/r14_gate_resources.txt, profiles/r14_gate_bench.txt).  Without GT the gate is silu, spelled out: the code of before.
-template <int BITS, bool ZP, int SM, int LUTSRC, int NR, int FT, int WPQ, bool DUMP, int ACC, bool SCF16, bool EARLY, bool XF = false, bool GN = false, bool GT = false>
-__global__ __launch_bounds__(FT) void k_gemv_quad(std::conditional_t<XF, FusedXfArgs, FusedArgs> a) {
+// GA (LUTSRC 1, ACC 1, no tap, no transform): the gather of an act-order matrix -- the lane's eight activations are x[perm[8 p .. 8 p + 7]]
+// instead of x[8 p .. 8 p + 7] (FusedPermArgs); every line of it sits under if constexpr (GA), and everything from the act-group scale on is
+// the text of the plain build.
+template <int BITS, bool ZP, int SM, int LUTSRC, int NR, int FT, int WPQ, bool DUMP, int ACC, bool SCF16, bool EARLY, bool XF = false, bool GN = false, bool GT = false,
+          bool GA = false>
+__global__ __launch_bounds__(FT) void k_gemv_quad(std::conditional_t<XF, FusedXfArgs, std::conditional_t<GA, FusedPermArgs, FusedArgs>> a) {
     static_assert(!XF || (LUTSRC == 1 && ACC == 1 && !DUMP), "the transform lives in the in-kernel LUT build of the MFMA form");
+    static_assert(!GA || (LUTSRC == 1 && ACC == 1 && !DUMP && !XF && SM == 0), "the gather lives in the in-kernel LUT build of the MFMA form, per-group scales");
     static_assert(!GN || XF, "GLU_NORM is a transform");
     static_assert(!GT || XF, "the gate belongs to a transform");
     extern __shared__ uint4 lds[];
@@ -154,7 +159,28 @@ __global__ __launch_bounds__(FT) void k_gemv_quad(std::conditional_t<XF, FusedXf
     constexpr int NP = NR / 2;                                   // pairs per thread
     const int P = T / 2;
     uint32_t xr[NP][8];
-    if (LUTSRC == 1) {
+    if constexpr (GA) {
+        // Two dependent loads: the pair's eight source indices (two 16-byte loads, clamped like the plain pair), then eight elements.  Every
+        // index is < K (tmac_hip_kperm_from_gidx_dev refuses anything else), so the element loads stay inside row n.  xr holds fp32, the
+        // form the XF instantiations use.  Issued here, in front of the weight fragments: vmcnt retires in order.
+#pragma unroll
+        for (int r = 0; r < NP; ++r) {
+            const int p = min(r * FT + tid, P - 1);
+            const int4* ip = reinterpret_cast<const int4*>(a.perm) + 2 * (size_t)p;
+            const int4 i0 = ip[0], i1 = ip[1];
+            const int k8[8] = {i0.x, i0.y, i0.z, i0.w, i1.x, i1.y, i1.z, i1.w};
+            if (a.act_f16) {
+                const __half* xb = reinterpret_cast<const __half*>(a.B) + (size_t)n * s.K;
+#pragma unroll
+                for (int i = 0; i < 8; ++i) xr[r][i] = __float_as_uint(__half2float(xb[k8[i]]));
+            } else {
+                const uint32_t* xb = reinterpret_cast<const uint32_t*>(a.B) + (size_t)n * s.K;
+#pragma unroll
+                for (int i = 0; i < 8; ++i) xr[r][i] = xb[k8[i]];
+            }
+        }
+    }
+    if (LUTSRC == 1 && !GA) {
 #pragma unroll
         for (int r = 0; r < NP; ++r) {
             const int p = min(r * FT + tid, P - 1);     // clamped, not predicated (see load_q)
@@ -201,13 +227,13 @@ __global__ __launch_bounds__(FT) void k_gemv_quad(std::conditional_t<XF, FusedXf
     float xrs = 1.0f;                 // XF, NORM with gamma / GLU_NORM: 1 / rms, known behind the cross-wave sum below
     bool xnorm = false;
     auto unpack = [&](int r, float (&x)[8]) {
-        if (!XF && a.act_f16) {
+        if (!XF && !GA && a.act_f16) {
 #pragma unroll
             for (int i = 0; i < 4; ++i) {
                 const __half2 hh = *reinterpret_cast<const __half2*>(&xr[r][i]);
                 x[2 * i] = __low2float(hh); x[2 * i + 1] = __high2float(hh);
             }
-        } else {      // (XF: xr holds the transformed vector as fp32)
+        } else {      // (XF: xr holds the transformed vector as fp32; GA: the gathered one)
 #pragma unroll
             for (int i = 0; i < 8; ++i) x[i] = __uint_as_float(xr[r][i]);
         }
@@ -320,7 +346,7 @@ __global__ __launch_bounds__(FT) void k_gemv_quad(std::conditional_t<XF, FusedXf
         for (int r = 0; r < NP; ++r)
 #pragma unroll
             for (int i = 0; i < 8; ++i)
-                if (i < 4 || XF || !a.act_f16) asm volatile("" :: "v"(xr[r][i]));
+                if (i < 4 || XF || GA || !a.act_f16) asm volatile("" :: "v"(xr[r][i]));
     }
     if (early) {
         issue(f0); issue(f1);
@@ -764,8 +790,8 @@ constexpr bool QSCF16 = TMAC_QUAD_SCF16 != 0;   // weight scales stored as fp16 
 // instantiates what passes it, so the predicate is the list of kernels this unit emits; the planner never names another.
 template <int BITS, bool SCF16, class Args>
 hipError_t launch_gemv_quad_unit(const Args& a, const QuadPlan& p, int N, hipStream_t st) {
-    constexpr bool XF = std::is_same_v<Args, FusedXfArgs>;
-    if (p.xf != XF || (XF && N != 1)) return hipErrorInvalidValue;
+    constexpr bool XF = std::is_same_v<Args, FusedXfArgs>, GA = std::is_same_v<Args, FusedPermArgs>;
+    if (p.xf != XF || p.ga != GA || ((XF || GA) && N != 1)) return hipErrorInvalidValue;
     const dim3 g(p.gx, N), b(p.ft);
     // scale flavour: unified scale (SM 2: one scalar read per output, the dtype stays a run-time flag -- fp32 unit only), or per-group scales
     // with / without zero points
@@ -777,13 +803,16 @@ hipError_t launch_gemv_quad_unit(const Args& a, const QuadPlan& p, int N, hipStr
         return sel_bool(a.s.zero_point != 0, [&](auto ZP) { return f(ZP, std::integral_constant<int, 0>{}); });
     };
     return flavour([&](auto ZP, auto SM) { return sel_int<512, 768, 1024>(p.ft, [&](auto FT) { return sel_int<1, 2, 3, 4>(p.wpq, [&](auto WPQ) {
-        if constexpr (!quad_config_exists(FT, WPQ) || (XF && !quad_xf_covered(FT, WPQ))) return hipErrorInvalidValue;
+        if constexpr (!quad_config_exists(FT, WPQ) || ((XF || GA) && !quad_xf_covered(FT, WPQ))) return hipErrorInvalidValue;
         else return sel_int<2, 6>(p.nr, [&](auto NR) { return sel_bool(p.early, [&](auto EARLY) {
             if constexpr (XF) {
                 return sel_bool(p.gn, [&](auto GN) { return sel_bool(p.gt, [&](auto GT) {
                     if constexpr (!quad_inst_exists(1, NR, FT, WPQ, false, 1, EARLY, true)) return hipErrorInvalidValue;
                     else return launch_lds(k_gemv_quad<BITS, ZP, SM, 1, NR, FT, WPQ, false, 1, SCF16, EARLY, true, GN, GT>, g, b, p.lds_bytes, st, a);
                 }); });
+            } else if constexpr (GA) {
+                if constexpr (SM != 0 || !quad_ga_inst_exists(NR, FT, WPQ, EARLY)) return hipErrorInvalidValue;
+                else return launch_lds(k_gemv_quad<BITS, ZP, 0, 1, NR, FT, WPQ, false, 1, SCF16, EARLY, false, false, false, true>, g, b, p.lds_bytes, st, a);
             } else {
                 return sel_bool(p.lutsrc != 0, [&](auto LUTSRC) { return sel_bool(p.dump, [&](auto DUMP) { return sel_bool(p.acc != 0, [&](auto ACC) {
                     if constexpr (!quad_inst_exists(LUTSRC, NR, FT, WPQ, DUMP, ACC, EARLY, false)) return hipErrorInvalidValue;
@@ -795,5 +824,6 @@ hipError_t launch_gemv_quad_unit(const Args& a, const QuadPlan& p, int N, hipStr
 }
 template hipError_t launch_gemv_quad_unit<TMAC_QUAD_BITS, QSCF16, FusedArgs>(const FusedArgs&, const QuadPlan&, int, hipStream_t);
 template hipError_t launch_gemv_quad_unit<TMAC_QUAD_BITS, QSCF16, FusedXfArgs>(const FusedXfArgs&, const QuadPlan&, int, hipStream_t);
+template hipError_t launch_gemv_quad_unit<TMAC_QUAD_BITS, QSCF16, FusedPermArgs>(const FusedPermArgs&, const QuadPlan&, int, hipStream_t);
 
 }  // namespace tmac

@@ -121,4 +121,26 @@ __device__ __forceinline__ void xf_rows_x8(const XA& a, const void* __restrict__
 }
 template <class XA> __device__ __forceinline__ const XA& xf_rows_arg(const XA& a) { return a; }
 
+// ---- the gather of an act-order permutation for N > 1 rows ------------------------------------------------------------------------
+// The same slot of the builders -- "x[8] of (row n, pair p) in place of the activation load" -- filled with x[n][perm[8 p .. 8 p + 7]]: two
+// 16-byte index loads, then eight element loads.  Every index is < K (tmac_hip_kperm_from_gidx_dev refuses anything else), so the element
+// loads stay inside row n, which the builder has clamped already.
+struct GatherRowsArgs {
+    const int32_t* perm;     // int32 [K], 16-byte aligned
+};
+__device__ __forceinline__ void xf_rows_x8(const GatherRowsArgs& a, const void* __restrict__ B, bool f16, int K, int n, int p, float (&x)[8]) {
+    const int4* ip = reinterpret_cast<const int4*>(a.perm) + 2 * (size_t)p;
+    const int4 i0 = ip[0], i1 = ip[1];
+    const int k8[8] = {i0.x, i0.y, i0.z, i0.w, i1.x, i1.y, i1.z, i1.w};
+    if (f16) {
+        const __half* xb = reinterpret_cast<const __half*>(B) + (size_t)n * K;
+#pragma unroll
+        for (int i = 0; i < 8; ++i) x[i] = __half2float(xb[k8[i]]);
+    } else {
+        const float* xb = reinterpret_cast<const float*>(B) + (size_t)n * K;
+#pragma unroll
+        for (int i = 0; i < 8; ++i) x[i] = xb[k8[i]];
+    }
+}
+
 }  // namespace tmac

@@ -70,6 +70,7 @@ extern "C" int32_t tmac_hip_preprocessor_dev(tmac_hip_workspace* ws, const void*
     if (!B_dev) return fail(TMAC_HIP_E_ARG, "null activations");
     if (misaligned(B_dev, ACT_ALIGN)) return fail(TMAC_HIP_E_ARG, "B_dev must be %zu-byte aligned (the LUT build reads 16 bytes at a time)", ACT_ALIGN);
     ws->K = K; ws->N = N; ws->ags = act_group_size; ws->qdev_u4_per_row = qdev_u4_for_K(K);
+    ws->perm_id = 0;
     // k_gemm_planes' LUT image is built when tmac_hip_qgemm_dev may pick that kernel: not for one row, and not below the GEMM threshold
     // (PLANES_MIN_N by default: the matrix, and with it the measured crossover plan_split applies, is not known here)
     const bool want_img = N >= 2 && N >= gemm_min_rows(PLANES_MIN_N) && ws->gimg && g_knobs.gemm_kernel != 1;
@@ -93,6 +94,36 @@ extern "C" int32_t tmac_hip_preprocessor_dev(tmac_hip_workspace* ws, const void*
         e = launch_lut_image(B_dev, act_dtype == TMAC_F16, ws->gimg, ws->gcol, K, N, ws->gNpad, (hipStream_t)stream);
         if (e != hipSuccess) return fail(TMAC_HIP_E_RUNTIME, "LUT image launch: %s", hipGetErrorString(e));
         ws->gimg_valid = true; ws->gimg_kind = 2;      // (K == 64 with one act group per row: this image wins, the unified-scale GEMM is not offered it)
+    }
+    return TMAC_HIP_OK;
+}
+
+// The same through a K permutation (act-order handles, tmac_kperm.h): every layout of the workspace from x[perm], by the gathered pair build,
+// for every N; the workspace records the permutation's id, which tmac_hip_qgemm_dev holds the weights to.  NULL or identity: the plain call.
+extern "C" int32_t tmac_hip_preprocessor_perm_dev(tmac_hip_workspace* ws, const void* B_dev, tmac_dtype_t act_dtype, int K, int N, int act_group_size,
+                                                  const tmac_hip_kperm* perm, void* stream) {
+    if (!perm || !perm->d || perm->d->h.identity) return tmac_hip_preprocessor_dev(ws, B_dev, act_dtype, K, N, act_group_size, stream);
+    bind_thread_device();
+    int32_t rc = defer_barrier();
+    if (rc) return rc;
+    rc = check_lut_shape(ws, K, N, act_group_size);
+    if (rc) return rc;
+    if (!B_dev) return fail(TMAC_HIP_E_ARG, "null activations");
+    if (misaligned(B_dev, ACT_ALIGN)) return fail(TMAC_HIP_E_ARG, "B_dev must be %zu-byte aligned (the LUT build reads 16 bytes at a time)", ACT_ALIGN);
+    if (act_group_size != 64) return fail(TMAC_HIP_E_NOMATCH, "the gathered LUT build takes act groups of 64 (act_group_size=%d)", act_group_size);
+    if (perm->d->h.K != K) return fail(TMAC_HIP_E_ARG, "the K permutation was built for K=%d; the call has K=%d", perm->d->h.K, K);
+    hipStream_t st = (hipStream_t)stream;
+    const int f16 = act_dtype == TMAC_F16;
+    ws->K = K; ws->N = N; ws->ags = act_group_size; ws->qdev_u4_per_row = qdev_u4_for_K(K);
+    ws->perm_id = perm->d->h.id;
+    ws->gimg_valid = false; ws->gimg_kind = 0; ws->gimg_K = K; ws->gimg_N = N;
+    hipError_t e = launch_preprocess_pairs(B_dev, f16, ws->qlut_lds, ws->lut_scales, ws->lut_biases, K, N, ws->qlut_ref, ws->qlut_dev, ws->qdev_u4_per_row, st,
+                                           nullptr, perm->d->dev);
+    if (e != hipSuccess) return fail(TMAC_HIP_E_RUNTIME, "preprocess launch: %s", hipGetErrorString(e));
+    if (N >= 2 && N >= gemm_min_rows(PLANES_MIN_N) && ws->gimg && g_knobs.gemm_kernel != 1) {      // tmac_hip_preprocessor_dev's rule for the LUT image
+        e = launch_lut_image(B_dev, f16, ws->gimg, ws->gcol, K, N, ws->gNpad, st, nullptr, perm->d->dev);
+        if (e != hipSuccess) return fail(TMAC_HIP_E_RUNTIME, "LUT image launch: %s", hipGetErrorString(e));
+        ws->gimg_valid = true; ws->gimg_kind = 2;
     }
     return TMAC_HIP_OK;
 }
@@ -134,6 +165,7 @@ extern "C" int32_t tmac_hip_workspace_write(tmac_hip_workspace* ws, const int8_t
     const size_t G = (size_t)K / act_group_size;
     ws->K = K; ws->N = N; ws->ags = act_group_size; ws->qdev_u4_per_row = qdev_u4_for_K(K);
     ws->gimg_valid = false;      // k_gemm_planes' LUT image (built from activations by tmac_hip_preprocessor_dev) no longer matches this LUT
+    ws->perm_id = 0;
     HIP_TRY(hipMemcpyAsync(ws->qlut_ref, qlut_host, (size_t)N * (K / 4) * 16, hipMemcpyHostToDevice, st));
     HIP_TRY(hipMemcpyAsync(ws->lut_scales, lut_scales_host, sizeof(float) * N * G, hipMemcpyHostToDevice, st));
     HIP_TRY(hipMemcpyAsync(ws->lut_biases, lut_biases_host, sizeof(float) * N * G, hipMemcpyHostToDevice, st));

@@ -123,21 +123,80 @@ def _blob_buffers(Mw, K, bits, cfg, ref_dtype):
             torch.empty(s // esz, dtype=torch.float16 if ref_dtype == F16 else torch.float32, device="cuda"))
 
 
-def pack_gptq(qweight, scales, qzeros, cfg: Optional[KCfg] = None, gptq_v2: bool = True, ref_dtype=F32, act_group_size: int = 64, stream=None):
+class KPerm:
+    """The K permutation of an act-order (``desc_act``) GPTQ matrix (tmac_hip_kperm): ``perm = stable_argsort(g_idx)``.  Built from a CUDA
+    int32 tensor or a numpy array (uploaded first) of K group indices; refused (TMACHipError) unless every group has exactly
+    ``group_size`` members.  ``identity``: g_idx == k // group_size, what every non-act-order exporter writes.  Handles registered through
+    it keep the native object alive; two objects of equal content count as the same permutation."""
+
+    def __init__(self, g_idx, group_size: int, stream=None):
+        g = _on_device(g_idx, "g_idx", ("int32",))
+        if g.dim() != 1:
+            raise ValueError("g_idx is 1-D: [K]")
+        self._h = C.c_void_p()
+        check(B.lib().tmac_hip_kperm_from_gidx_dev(_ptr(g), int(g.shape[0]), int(group_size), C.byref(self._h), _stream(stream)))
+        k, ident, pid = C.c_int(0), C.c_int(0), C.c_uint64(0)
+        check(B.lib().tmac_hip_kperm_info(self._h, C.byref(k), C.byref(ident), C.byref(pid)))
+        self.K, self.group_size, self.identity, self.id = k.value, int(group_size), bool(ident.value), pid.value
+
+    @property
+    def handle(self):
+        return self._h
+
+    def perm(self) -> np.ndarray:
+        """int32 [K]: position k' of the permuted matrix holds source column (and activation) perm[k']"""
+        out = np.empty(self.K, np.int32)
+        check(B.lib().tmac_hip_kperm_read(self._h, out.ctypes.data))
+        return out
+
+    def free(self):
+        if self._h:
+            B.lib().tmac_hip_kperm_free(self._h)
+            self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.free()
+        except Exception:
+            pass
+
+
+def _kperm(g_idx, group_size: int, stream=None) -> Optional[KPerm]:
+    """``g_idx`` of the registration / packing calls -> a KPerm, or None where there is nothing to permute (None, or an identity)"""
+    if g_idx is None:
+        return None
+    kp = g_idx if isinstance(g_idx, KPerm) else KPerm(g_idx, group_size, stream)
+    return None if kp.identity else kp
+
+
+def pack_gptq(qweight, scales, qzeros, cfg: Optional[KCfg] = None, gptq_v2: bool = True, ref_dtype=F32, act_group_size: int = 64, stream=None,
+              g_idx=None):
     """GPTQ tensors -> the reference blob, on the GPU (tmac_hip_pack_gptq_dev): (A_ref uint8, scales_ref) as flat CUDA tensors, exactly
     ``weights.preprocess_weights(*convert.unpack_gptq(...))``.  Asynchronous on the stream.  (numpy inputs are uploaded on torch's current
-    stream and released in its order: leave ``stream`` at its default with them.)"""
+    stream and released in its order: leave ``stream`` at its default with them.)  ``g_idx`` (act-order; a KPerm or the tensor): the blob
+    of the matrix with its columns in group order, ``w[:, perm]`` (tmac_hip_pack_gptq_perm_dev)."""
     qw, sc, qz, Mw, K, bits, cfg = _gptq_args(qweight, scales, qzeros, cfg, act_group_size)
     A, S = _blob_buffers(Mw, K, bits, cfg, ref_dtype)
+    kp = _kperm(g_idx, cfg.group_size, stream)
+    if kp is not None:
+        check(B.lib().tmac_hip_pack_gptq_perm_dev(_ptr(qw), _ptr(sc), _ptr(qz), _float_code(sc, "scales"), int(bool(gptq_v2)), kp.handle, Mw, K, bits,
+                                                  C.byref(cfg), _ptr(A), _ptr(S), ref_dtype, _stream(stream)))
+        return A, S
     check(B.lib().tmac_hip_pack_gptq_dev(_ptr(qw), _ptr(sc), _ptr(qz), _float_code(sc, "scales"), int(bool(gptq_v2)), Mw, K, bits, C.byref(cfg),
                                          _ptr(A), _ptr(S), ref_dtype, _stream(stream)))
     return A, S
 
 
-def pack_codes(codes, scales, zeros, bits: int, cfg: Optional[KCfg] = None, ref_dtype=F32, act_group_size: int = 64, stream=None):
-    """codes uint8 [Mw][K] + scales / zeros [Mw][K/gs] in T-MAC's convention -> the reference blob, on the GPU (tmac_hip_pack_codes_dev)"""
+def pack_codes(codes, scales, zeros, bits: int, cfg: Optional[KCfg] = None, ref_dtype=F32, act_group_size: int = 64, stream=None, g_idx=None):
+    """codes uint8 [Mw][K] + scales / zeros [Mw][K/gs] in T-MAC's convention -> the reference blob, on the GPU (tmac_hip_pack_codes_dev;
+    with ``g_idx``: of ``codes[:, perm]``, tmac_hip_pack_codes_perm_dev)"""
     cd, sc, zr, Mw, K, cfg = _codes_args(codes, scales, zeros, bits, cfg, act_group_size)
     A, S = _blob_buffers(Mw, K, bits, cfg, ref_dtype)
+    kp = _kperm(g_idx, cfg.group_size, stream)
+    if kp is not None:
+        check(B.lib().tmac_hip_pack_codes_perm_dev(_ptr(cd), _ptr(sc), _ptr(zr), _float_code(sc, "scales"), kp.handle, Mw, K, bits, C.byref(cfg),
+                                                   _ptr(A), _ptr(S), ref_dtype, _stream(stream)))
+        return A, S
     check(B.lib().tmac_hip_pack_codes_dev(_ptr(cd), _ptr(sc), _ptr(zr), _float_code(sc, "scales"), Mw, K, bits, C.byref(cfg), _ptr(A), _ptr(S),
                                           ref_dtype, _stream(stream)))
     return A, S
@@ -151,32 +210,51 @@ class Weights:
         self = cls.__new__(cls)
         self.Mw, self.K, self.bits, self.cfg = Mw, K, bits, cfg
         self._h, self._keep, self._caches = handle, None, []
+        self.kperm = None
         return self
 
     @classmethod
     def from_gptq(cls, qweight, scales, qzeros, cfg: Optional[KCfg] = None, gptq_v2: bool = True, dev_dtype=F16, act_group_size: int = 64,
-                  stream=None) -> "Weights":
+                  stream=None, g_idx=None) -> "Weights":
         """Register straight from GPTQ tensors -- torch CUDA tensors, or numpy arrays that are uploaded first -- packed into the reference
         blob on the GPU (tmac_hip_register_weights_gptq_dev).  The handle is the one ``Weights(*blob)`` gives.  Without a ``cfg`` the
-        shapes come from ``convert.parse_gptq`` and the M-tile from ``convert.default_bm``; ``qzeros=None`` (no zero points) needs one."""
+        shapes come from ``convert.parse_gptq`` and the M-tile from ``convert.default_bm``; ``qzeros=None`` (no zero points) needs one.
+        ``g_idx`` (act-order checkpoints: a CUDA int32 tensor, a numpy array or a KPerm): the handle holds the matrix in group order and
+        carries the permutation (``.kperm``), through which every fused call gathers its activations; an identity g_idx gives a plain
+        handle (tmac_hip_register_weights_gptq_perm_dev)."""
         qw, sc, qz, Mw, K, bits, cfg = _gptq_args(qweight, scales, qzeros, cfg, act_group_size)
         h = C.c_void_p()
         ref = _float_code(sc, "scales")        # the blob in the scales' own dtype: nothing is rounded on the way
-        check(B.lib().tmac_hip_register_weights_gptq_dev(C.byref(h), _ptr(qw), _ptr(sc), _ptr(qz), ref, int(bool(gptq_v2)), Mw, K, bits,
-                                                         C.byref(cfg), ref, dev_dtype, _stream(stream)))
-        return cls._adopt(h, Mw, K, bits, cfg)
+        kp = _kperm(g_idx, cfg.group_size, stream)
+        if kp is not None:
+            check(B.lib().tmac_hip_register_weights_gptq_perm_dev(C.byref(h), _ptr(qw), _ptr(sc), _ptr(qz), ref, int(bool(gptq_v2)), kp.handle, Mw, K,
+                                                                  bits, C.byref(cfg), ref, dev_dtype, _stream(stream)))
+        else:
+            check(B.lib().tmac_hip_register_weights_gptq_dev(C.byref(h), _ptr(qw), _ptr(sc), _ptr(qz), ref, int(bool(gptq_v2)), Mw, K, bits,
+                                                             C.byref(cfg), ref, dev_dtype, _stream(stream)))
+        self = cls._adopt(h, Mw, K, bits, cfg)
+        self.kperm = kp
+        return self
 
     @classmethod
     def from_codes(cls, codes, scales, zeros, bits: int, cfg: Optional[KCfg] = None, dev_dtype=F16, act_group_size: int = 64,
-                   stream=None) -> "Weights":
+                   stream=None, g_idx=None) -> "Weights":
         """Register from unpacked codes uint8 [Mw][K] with scales / zeros [Mw][K/gs] already in T-MAC's convention (or [m_groups] unified
-        scales with a ``cfg``), packed on the GPU (tmac_hip_register_weights_codes_dev).  The route for 3-bit weights."""
+        scales with a ``cfg``), packed on the GPU (tmac_hip_register_weights_codes_dev).  The route for 3-bit weights.  ``g_idx``: as in
+        ``from_gptq`` (codes in the checkpoint's column order, scales / zeros in group order)."""
         cd, sc, zr, Mw, K, cfg = _codes_args(codes, scales, zeros, bits, cfg, act_group_size)
         h = C.c_void_p()
         ref = _float_code(sc, "scales")
-        check(B.lib().tmac_hip_register_weights_codes_dev(C.byref(h), _ptr(cd), _ptr(sc), _ptr(zr), ref, Mw, K, bits, C.byref(cfg), ref, dev_dtype,
-                                                          _stream(stream)))
-        return cls._adopt(h, Mw, K, bits, cfg)
+        kp = _kperm(g_idx, cfg.group_size, stream)
+        if kp is not None:
+            check(B.lib().tmac_hip_register_weights_codes_perm_dev(C.byref(h), _ptr(cd), _ptr(sc), _ptr(zr), ref, kp.handle, Mw, K, bits, C.byref(cfg),
+                                                                   ref, dev_dtype, _stream(stream)))
+        else:
+            check(B.lib().tmac_hip_register_weights_codes_dev(C.byref(h), _ptr(cd), _ptr(sc), _ptr(zr), ref, Mw, K, bits, C.byref(cfg), ref, dev_dtype,
+                                                              _stream(stream)))
+        self = cls._adopt(h, Mw, K, bits, cfg)
+        self.kperm = kp
+        return self
 
     def __init__(self, A_ref, scales_ref, Mw: int, K: int, bits: int, cfg: KCfg, scales_dtype=F32, dev_dtype=F32,
                  on_device: bool = False, stream=None):
@@ -192,6 +270,7 @@ class Weights:
                  _stream(stream)))
         self._keep = None
         self._caches = []          # fused-call caches holding this handle (TMACGeMMWrapper.fused)
+        self.kperm = None          # the K permutation of an act-order matrix (from_gptq / from_codes with g_idx)
 
     @property
     def handle(self):
@@ -497,21 +576,26 @@ class TMACGeMMWrapper:
         finally:
             B.lib().tmac_hip_set_fast_aggregation(0)
 
-    def register_gptq(self, qweight, scales, qzeros, cfg: Optional[KCfg] = None, gptq_v2: bool = True, dev_dtype=F16, stream=None) -> Weights:
+    def register_gptq(self, qweight, scales, qzeros, cfg: Optional[KCfg] = None, gptq_v2: bool = True, dev_dtype=F16, stream=None,
+                      g_idx=None) -> Weights:
         """``Weights.from_gptq`` with this wrapper's act_group_size: GPTQ tensors (CUDA tensors, or numpy arrays uploaded first) -> handle,
-        the blob packed on the GPU"""
-        return Weights.from_gptq(qweight, scales, qzeros, cfg, gptq_v2, dev_dtype, self._act_group_size, stream)
+        the blob packed on the GPU.  ``g_idx``: an act-order checkpoint's group indices (tensor, array or KPerm)"""
+        return Weights.from_gptq(qweight, scales, qzeros, cfg, gptq_v2, dev_dtype, self._act_group_size, stream, g_idx)
 
-    def register_codes(self, codes, scales, zeros, bits: int, cfg: Optional[KCfg] = None, dev_dtype=F16, stream=None) -> Weights:
+    def register_codes(self, codes, scales, zeros, bits: int, cfg: Optional[KCfg] = None, dev_dtype=F16, stream=None, g_idx=None) -> Weights:
         """``Weights.from_codes`` with this wrapper's act_group_size"""
-        return Weights.from_codes(codes, scales, zeros, bits, cfg, dev_dtype, self._act_group_size, stream)
+        return Weights.from_codes(codes, scales, zeros, bits, cfg, dev_dtype, self._act_group_size, stream, g_idx)
 
     def llama_cpp_init(self, B_dev, M: int, K: int, N: int, bits: int, act_group_size: Optional[int] = None,
-                       act_dtype: Optional[int] = None, stream=None) -> None:
-        """preprocessor_int8(M*bits, K, N, bits, B, lut_scales, lut_biases, qlut) on the device."""
+                       act_dtype: Optional[int] = None, stream=None, kperm: Optional[KPerm] = None) -> None:
+        """preprocessor_int8(M*bits, K, N, bits, B, lut_scales, lut_biases, qlut) on the device.  ``kperm``: the LUT of act-order weights
+        (``Weights.kperm``), built from B[:, perm] (tmac_hip_preprocessor_perm_dev); llama_cpp_compute refuses a mismatch."""
         ags = act_group_size or self._act_group_size
         if act_dtype is None:
             act_dtype = _dtype_code(B_dev)
+        if kperm is not None:
+            check(B.lib().tmac_hip_preprocessor_perm_dev(self.workspace.handle, _ptr(B_dev), act_dtype, K, N, ags, kperm.handle, _stream(stream)))
+            return
         check(B.lib().tmac_hip_preprocessor_dev(self.workspace.handle, _ptr(B_dev), act_dtype, K, N, ags, _stream(stream)))
 
     def llama_cpp_compute(self, weights: Weights, C_dev, N: int = 1, out_dtype: Optional[int] = None, stream=None) -> None:
