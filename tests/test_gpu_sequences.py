@@ -412,3 +412,59 @@ def test_split_entry_sequences(tm, first, second):
         assert ei.value.code == E_ARG and "does not match" in str(ei.value)
         torch.cuda.synchronize()
         assert torch.isnan(o).all(), "a refused call wrote its output"
+
+
+# ---- 8. a caller's workspace through a permuted build, a write and a smaller build ------------------------------------------------------
+def test_split_workspace_perm_write_shrink(tm):
+    """a caller's Workspace(256, 13), W2 with groups of 64, Mw = 64, K = 256, N = 13 -- the first N past PLANES_MIN_N, so the builds
+    come with the LUT image.  What the workspace holds after each step decides what the next call may read:
+    1. a permuted init: the image is there, the permuted handle computes (the oracle on x[perm], the bar of test_gpu_actorder's split path);
+    2. workspace.write of the oracle's LUT of x[perm]: no image any more, the plain handle of the gathered matrix computes on k_gemv_quad,
+       the permuted handle is refused and its output stays as it was;
+    3. a plain init of 4 rows: the image tap of 13 rows is refused."""
+    import torch
+    from oracle import oracle as orc
+    from test_gpu_actorder import acts, gathered, mat as perm_mat
+    bits, K, N, gs = 2, 256, 13, 64
+    m = perm_mat(tm, 310, 64, K, bits, gs, "random")
+    wr = tm.TMACGeMMWrapper(act_group_size=64)
+    wr.set_workspace(K, N)
+    x = acts(311, N, K, torch.float32)
+    xg = gathered(m, x)
+    xg_host = xg.cpu().numpy()
+    ref = m.oracle(xg_host)
+
+    def close(out, what):
+        torch.cuda.synchronize()
+        got = out.cpu().numpy()
+        assert np.isfinite(got).all(), what
+        assert np.abs(got - ref).max() < 1e-3 * np.abs(ref).max(), (what, float(np.abs(got - ref).max()))
+
+    # 1
+    wr.llama_cpp_init(x, m.Mw, K, N, bits, kperm=m.kperm)
+    wr.workspace.read_gemm_image(K, N)
+    out = poison((N, m.Mw), torch.float32)
+    wr.llama_cpp_compute(m.wp, out, N)
+    close(out, "permuted handle after the permuted init")
+    # 2
+    wr.workspace.write(*orc.preprocessor(xg_host, 64), 64)
+    with pytest.raises(tm.binding.TMACHipError) as ei:
+        wr.workspace.read_gemm_image(K, N)
+    assert ei.value.code == E_ARG and "holds no LUT image" in str(ei.value)
+    out = poison((N, m.Mw), torch.float32)
+    before = route_stats(tm)
+    wr.llama_cpp_compute(m.wt, out, N)
+    delta = stats_delta(before, route_stats(tm))
+    close(out, "plain handle after the write")
+    assert delta == {QUAD: 1}, named(delta)
+    out = poison((N, m.Mw), torch.float32)
+    with pytest.raises(tm.binding.TMACHipError) as ei:
+        wr.llama_cpp_compute(m.wp, out, N)
+    assert ei.value.code == E_ARG and "K permutation" in str(ei.value)
+    torch.cuda.synchronize()
+    assert torch.isnan(out).all(), "a refused call wrote its output"
+    # 3
+    wr.llama_cpp_init(xg[:4].contiguous(), m.Mw, K, 4, bits)
+    with pytest.raises(tm.binding.TMACHipError) as ei:
+        wr.comb_sums(m.wt, N)
+    assert ei.value.code == E_ARG and "holds no LUT image" in str(ei.value)

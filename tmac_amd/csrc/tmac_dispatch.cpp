@@ -16,16 +16,10 @@ enum Route {
     R_REF_LAYOUT,    // k_gemv_ref_layout on the reference blobs
     R_ROW_LOOP       // fused entry point's last resort: one LUT build, then tmac_hip_qgemm_dev (plan_split) per matrix
 };
-// the LUT the fused entry point builds before the planned kernel (the split entry points find theirs in the workspace)
-enum LutBuild {
-    LB_NONE,         // none: the GEMV kernel builds its own
-    LB_IMAGE,        // k_gemm_planes' LUT image alone
-    LB_HALF_TABLES,  // the half-table image (qlut_lds) alone, two tables per lane: all that k_gemm_onehot and k_gemv_quad read
-    LB_ALL           // tmac_hip_preprocessor_dev: every layout of the workspace
-};
+static const char* const ROUTE_NAMES[] = {"k_gemm_planes", "k_gemm_onehot", "k_gemv_quad", "k_gemv_rows", "k_gemv_fused", "k_gemv_lo", "k_gemv_ref_layout", "the row loop"};
 struct Plan {
     Route route;
-    LutBuild lut;
+    LutBuild lut;      // the LUT the fused entry point builds before the planned kernel (tmac_lut_held.h; the split entry points find theirs in the workspace)
     int32_t err;       // TMAC_HIP_OK, or the call is refused: fail(err, msg, mat)
     const char* msg;   // (may name the offending matrix: %d)
     int mat;
@@ -89,7 +83,6 @@ static bool rows_pays(const Shape& s, long total_Mw, int N) {
     if (g_knobs.rows_kernel != 0) return g_knobs.rows_kernel == 2;
     return rows_auto(s, total_Mw, N);
 }
-static bool planes_image_fits(const tmac_hip_workspace* ws, int K) { return ws->gimg && (size_t)2 * K * ws->gNpad < ((size_t)1 << 31); }
 
 // ---- the two planners ------------------------------------------------------------------------------------------------------
 // They read g_knobs and their arguments, take no lock, allocate nothing and launch nothing.  Today's routing, quirks included
@@ -100,8 +93,8 @@ static bool planes_image_fits(const tmac_hip_workspace* ws, int K) { return ws->
 //    the shape wants: tmac_hip_preprocessor_dev builds it from PLANES_MIN_N rows on (it does not know the matrix), while the
 //    crossover applied here is the measured one of the matrix -- between the two the image is built and not used, or wanted and not
 //    there.  Without the image only k_gemm_onehot's own, later crossover counts: below it the row loop is the faster kernel.  The
-//    image counts only while it was built from the rows the workspace's LUT was built from (image_serves_lut: valid, and its K and N
-//    are the LUT's): every build or write of the LUT that does not build the image invalidates it.
+//    image counts only while the workspace holds it (LutHeld::serves_image): every build or write of the LUT starts from a workspace
+//    that holds nothing.
 //  * A tap bypasses k_gemm_planes on the split entry point, but not k_gemm_onehot, which has a per-plane tap of its own.  On the
 //    fused entry point a tap (dump / lut_tap) bypasses both GEMMs -- and, in fused_impl, recording and the deferred queue.
 //  * Fast-aggregation weights are accepted on V_REF_LAYOUT, V_LO_MQSAD and V_LO_SDWA only (registration puts them in the LO layout,
@@ -141,7 +134,7 @@ static Plan plan_split(const tmac_hip_weights* w, const tmac_hip_workspace* ws, 
     if (r != R_GEMV_QUAD && r != R_GEMV_FUSED) return planned(r);
     const bool rows = r == R_GEMV_QUAD && N >= 2 && !tap && g_knobs.rows_kernel != 1 && rows_covers(w);
     if (rows && g_knobs.rows_kernel == 2) return planned(R_GEMV_ROWS);
-    if (!tap && image_serves_lut(ws) && ws->gimg_kind == gimg_kind_for(w->s) && planes_ok(w) && planes_image_fits(ws, w->s.K) && planes_pays(w->s, w->s.Mw, N))
+    if (!tap && ws->held.serves_image(image_kind_for(w->s), w->s.K, N) && planes_ok(w) && ws->image_fits(w->s.K) && planes_pays(w->s, w->s.Mw, N))
         return planned(R_GEMM_PLANES);
     if (onehot_pays(w->s, w->s.Mw, N) && gemm_onehot_supported(w->s)) return planned(R_GEMM_ONEHOT);
     if (rows && rows_pays(w->s, w->s.Mw, N)) return planned(R_GEMV_ROWS);
@@ -315,14 +308,21 @@ int32_t tmac_host::qgemm_impl(const tmac_hip_weights* w, const tmac_hip_workspac
     if (brc) return brc;
     if (!w || !ws || !C_dev) return fail(TMAC_HIP_E_ARG, "null argument");
     if (misaligned(C_dev, out_align(out_dtype))) return fail(TMAC_HIP_E_ARG, "C_dev must be %zu-byte aligned (four outputs are stored at a time)", out_align(out_dtype));
-    if (ws->K != w->s.K || ws->ags != w->s.ags)
-        return fail(TMAC_HIP_E_ARG, "workspace LUT (K=%d, ags=%d) does not match the weights (K=%d, ags=%d)", ws->K, ws->ags, w->s.K, w->s.ags);
-    if (N <= 0 || N > ws->N) return fail(TMAC_HIP_E_ARG, "N=%d but the workspace LUT holds %d rows", N, ws->N);
-    if (perm_id_of(w) != ws->perm_id)
+    const LutHeld& held = ws->held;
+    if (!held.serves_lut(w->s.K, w->s.ags, 1))
+        return fail(TMAC_HIP_E_ARG, "workspace LUT (K=%d, ags=%d) does not match the weights (K=%d, ags=%d)", held.K(), held.ags(), w->s.K, w->s.ags);
+    if (!held.serves_lut(w->s.K, w->s.ags, N)) return fail(TMAC_HIP_E_ARG, "N=%d but the workspace LUT holds %d rows", N, held.N());
+    if (!held.built_through(perm_id_of(w)))
         return fail(TMAC_HIP_E_ARG, perm_of(w) ? "the weights carry a K permutation (act-order) but the workspace LUT was not built through it (tmac_hip_preprocessor_perm_dev)"
                                                : "the workspace LUT was built through a K permutation the weights do not carry");
     const Plan p = plan_split(w, ws, N, dump != nullptr);
     if (p.err) return fail(p.err, p.msg, p.mat);
+    // the planned kernel reads tables somebody built: its layout of the LUT, or the LUT image, is in the workspace's record
+    const bool planes = p.route == R_GEMM_PLANES;
+    const LutLayout reads = p.route == R_REF_LAYOUT ? LUT_REF : p.route == R_GEMV_LO ? LUT_DEV : LUT_HALF;
+    if (planes ? !held.serves_image(image_kind_for(w->s), w->s.K, N) : !held.has_layout(reads))
+        return fail(TMAC_HIP_E_RUNTIME, "route %s reads %s, which the workspace's last LUT build did not write", ROUTE_NAMES[p.route],
+                    planes ? "the LUT image" : reads == LUT_REF ? "qlut_ref" : reads == LUT_DEV ? "qlut_dev" : "the half-table image");
     count_route(p.route);
     void* cl[1] = {C_dev};
     switch (p.route) {
@@ -418,7 +418,7 @@ extern "C" int32_t tmac_hip_debug_gemm_comb_sums(const tmac_hip_weights* w, cons
     if (!w || !ws_c || !comb_host) return fail(TMAC_HIP_E_ARG, "null argument");
     auto* ws = const_cast<tmac_hip_workspace*>(ws_c);
     hipStream_t st = (hipStream_t)stream;
-    if (!image_serves_lut(ws) || ws->gimg_kind != gimg_kind_for(w->s) || ws->K != w->s.K || N <= 0 || N > ws->N) return fail(TMAC_HIP_E_ARG, "the workspace holds no LUT image for K=%d, N=%d", w->s.K, N);
+    if (!ws->held.serves_image(image_kind_for(w->s), w->s.K, N)) return fail(TMAC_HIP_E_ARG, "the workspace holds no LUT image for K=%d, N=%d", w->s.K, N);
     if (!planes_ok(w)) return fail(TMAC_HIP_E_NOMATCH, "k_gemm_planes does not cover this configuration");
     const size_t elems = (size_t)N * w->s.Mw * (w->s.m_groups >= 1 ? 1 : w->s.K / 64);
     DevBuf Ctmp;
@@ -465,7 +465,7 @@ extern "C" int32_t tmac_hip_debug_rows_comb_sums(const tmac_hip_weights* w, cons
     if (!w || !ws_c || !comb_host) return fail(TMAC_HIP_E_ARG, "null argument");
     auto* ws = const_cast<tmac_hip_workspace*>(ws_c);
     hipStream_t st = (hipStream_t)stream;
-    if (ws->K != w->s.K || ws->ags != w->s.ags || N <= 0 || N > ws->N) return fail(TMAC_HIP_E_ARG, "the workspace holds no LUT for K=%d, N=%d", w->s.K, N);
+    if (!ws->held.serves_lut(w->s.K, w->s.ags, N)) return fail(TMAC_HIP_E_ARG, "the workspace holds no LUT for K=%d, N=%d", w->s.K, N);
     if (!rows_covers(w)) return fail(TMAC_HIP_E_NOMATCH, "k_gemv_rows does not cover this configuration");
     const size_t elems = (size_t)N * w->s.Mw * (w->s.m_groups >= 1 ? (size_t)w->s.bits : (size_t)w->s.K / 64);
     DevBuf Ctmp;
@@ -482,10 +482,10 @@ extern "C" int32_t tmac_hip_debug_gemm_image_read(const tmac_hip_workspace* ws, 
     const int32_t brc = defer_barrier();
     if (brc) return brc;
     if (!ws || !half_tables_host || !lut_scales_host || !lut_biases_host || !entry_sums_host) return fail(TMAC_HIP_E_ARG, "null argument");
-    if (!image_serves_lut(ws) || N <= 0 || N > ws->N) return fail(TMAC_HIP_E_ARG, "the workspace holds no LUT image for N=%d", N);
+    const int K = ws->held.K(), Np = ws->gNpad;
+    if (!ws->held.serves_image(ws->held.image(), K, N)) return fail(TMAC_HIP_E_ARG, "the workspace holds no LUT image for N=%d", N);
     hipStream_t st = (hipStream_t)stream;
-    const int K = ws->K, Np = ws->gNpad;
-    const bool rowwise = ws->gimg_kind == 1;           // one act group per row: k_preprocess_pairs_row's layout
+    const bool rowwise = ws->held.image() == IMG_ROWWISE;           // one act group per row: k_preprocess_pairs_row's layout
     const int G = rowwise ? 1 : K / 64;
     std::vector<uint8_t> img((size_t)2 * K * Np);
     std::vector<float> col((size_t)(rowwise ? 3 : 4) * G * Np);
@@ -517,11 +517,8 @@ extern "C" int32_t tmac_hip_debug_gemm_image_read(const tmac_hip_workspace* ws, 
 }
 
 // ---- fused entry point -----------------------------------------------------------------------------------------------------
-// Prefill through the fused entry point: one LUT build (k_preprocess) into a workspace owned by the library, one
-// one-hot MFMA GEMM per matrix.  The workspace is per stream (launches on one stream are ordered; two streams must not
-// share LUT buffers) and grows on demand; tmac_hip_cache_clear() releases them.
-static std::map<std::pair<int, hipStream_t>, tmac_hip_workspace*> g_fused_ws;   // per (device, stream): the null stream exists on every device
-
+// Prefill through the fused entry point: one LUT build into the stream's workspace, owned by the library (stream_workspace; tmac_hip_cache_clear()
+// releases them), then the planned kernel.
 // A transformed call of N >= 2 rows (tmac_hip_qgemm_fused_xf_rows_dev) runs on a plan of plan_fused with two rules of its own: where the
 // planner answers R_GEMV_QUAD (k_gemv_quad with grid.y = N, each workgroup building its row's LUT) the call takes R_ROW_LOOP behind
 // LB_HALF_TABLES -- the transform sits in the pair build, k_gemv_quad copies the image (LUTSRC == 0) -- and a plan that needs LB_ALL (the
@@ -546,65 +543,31 @@ static int32_t fused_prefill(Plan p, const tmac_hip_weights* const* wl, int nmat
                              void* const* C_list, tmac_dtype_t out_dtype, int N, hipStream_t st, const XfSpec* spec = nullptr, const KPermData* kp = nullptr) {
     const Shape& s0 = wl[0]->s;
     tmac_hip_workspace* ws = nullptr;
-    {
-        std::lock_guard<std::mutex> lk(g_mu);
-        tmac_hip_workspace*& slot = g_fused_ws[std::make_pair(g_device, st)];
-        int needK = s0.K, needN = N;
-        if (slot && (slot->maxK < s0.K || slot->maxN < N)) {
-            // grow to the maximum seen in BOTH dimensions (mixed shapes -- K = 4096 / 11008, growing N -- would otherwise
-            // free and reallocate on every other call); the old buffers may still be read by launches in flight
-            needK = slot->maxK > s0.K ? slot->maxK : s0.K;
-            needN = slot->maxN > N ? slot->maxN : N;
-            hipError_t e = hipStreamSynchronize(st);
-            if (e != hipSuccess) return fail(TMAC_HIP_E_RUNTIME, "stream sync: %s", hipGetErrorString(e));
-            tmac_hip_workspace_free(slot);
-            slot = nullptr;
-        }
-        if (!slot) {
-            int32_t rc = tmac_hip_workspace_create(&slot, needK, needN);
-            if (rc) { slot = nullptr; return rc; }
-        }
-        ws = slot;
-    }
-    if (p.route == R_GEMM_PLANES && !planes_image_fits(ws, s0.K)) {   // (see image_fits at the planners)
+    int32_t rc = stream_workspace(st, s0.K, N, &ws);
+    if (rc) return rc;
+    if (p.route == R_GEMM_PLANES && !ws->image_fits(s0.K)) {   // (see image_fits at the planners)
         p = plan_fused(wl, C_list, nmat, N, false, false);
         if (spec || kp) {
             p = xf_rows_plan(p);
             if (p.err) return fail(p.err, p.msg, p.mat);
         }
     }
-    int32_t rc = p.lut == LB_ALL ? TMAC_HIP_OK : check_lut_shape(ws, s0.K, N, s0.ags);
+    LutBuildReq q;
+    q.K = s0.K; q.N = N; q.ags = s0.ags; q.want = p.lut; q.unified = s0.m_groups >= 1; q.xf = spec != nullptr;
+    if (kp) { q.perm_id = kp->h.id; q.perm_K = kp->h.K; }      // (recorded: what the row loop's tmac_hip_qgemm_dev holds the matrices to)
+    LutBuildPlan lb;
+    rc = lut_build_plan(q, lut_caps(ws), &lb);
     if (rc) return rc;
-    const int f16 = act_dtype == TMAC_F16;
-    hipError_t e = hipSuccess;
     XfRowsGateArgs xa;
-    XfRowsGateArgs* const xf = spec ? &xa : nullptr;
-    const int32_t* const perm = kp ? kp->dev : nullptr;
-    ws->perm_id = kp ? kp->h.id : 0;      // what the row loop's tmac_hip_qgemm_dev holds the matrices to
     if (spec) {
         fill_xf_rows_args(xa, *spec, ws->xf_r);
         if (xf_needs_row_pass(*spec)) {
-            e = launch_xf_rows(xa, B_dev, f16, xa.gamma ? ws->xf_r : nullptr, s0.K, N, st);
+            const hipError_t e = launch_xf_rows(xa, B_dev, act_dtype == TMAC_F16, xa.gamma ? ws->xf_r : nullptr, s0.K, N, st);
             if (e != hipSuccess) return fail(TMAC_HIP_E_RUNTIME, "transform row pass launch: %s", hipGetErrorString(e));
         }
     }
-    if (p.lut == LB_IMAGE) {
-        ws->K = 0; ws->N = 0; ws->gimg_valid = false;      // the other layouts of this workspace are not built
-        e = s0.m_groups >= 1
-            ? launch_preprocess_pairs_row(B_dev, f16, ws->qlut_lds, ws->lut_scales, ws->lut_biases, s0.K, N, nullptr, nullptr, 0, ws->gimg, ws->gcol, ws->gNpad, st, xf)
-            : launch_lut_image(B_dev, f16, ws->gimg, ws->gcol, s0.K, N, ws->gNpad, st, xf, perm);
-        if (e != hipSuccess) return fail(TMAC_HIP_E_RUNTIME, "LUT image launch: %s", hipGetErrorString(e));
-    } else if (p.lut == LB_HALF_TABLES) {
-        ws->K = s0.K; ws->N = N; ws->ags = s0.ags; ws->qdev_u4_per_row = qdev_u4_for_K(s0.K);
-        ws->gimg_valid = false;      // an image an earlier call left on the stream was not built from this call's rows
-        e = s0.ags == 64
-            ? launch_preprocess_pairs(B_dev, f16, ws->qlut_lds, ws->lut_scales, ws->lut_biases, s0.K, N, nullptr, nullptr, 0, st, xf, perm)
-            : launch_preprocess_pairs_row(B_dev, f16, ws->qlut_lds, ws->lut_scales, ws->lut_biases, s0.K, N, nullptr, nullptr, 0, nullptr, nullptr, 0, st, xf);
-        if (e != hipSuccess) return fail(TMAC_HIP_E_RUNTIME, "preprocess launch: %s", hipGetErrorString(e));
-    } else {
-        rc = tmac_hip_preprocessor_dev(ws, B_dev, act_dtype, s0.K, N, s0.ags, st);
-        if (rc) return rc;
-    }
+    rc = lut_build(ws, lb, B_dev, act_dtype, spec ? &xa : nullptr, kp ? kp->dev : nullptr, st);
+    if (rc) return rc;
     count_route(p.route);
     if (p.route == R_GEMM_PLANES) return planes_multi(wl, nmat, ws, C_list, out_dtype, N, nullptr, st);
     if (p.route == R_GEMM_ONEHOT) return gemm_multi(wl, nmat, ws, C_list, out_dtype, N, nullptr, st);
@@ -896,13 +859,4 @@ extern "C" int32_t tmac_hip_qgemm_fused_partial_sums(const tmac_hip_weights* w, 
     if (C_host) HIP_TRY(hipMemcpy(C_host, Ctmp.p, sizeof(float) * (size_t)N * w->s.Mw, hipMemcpyDeviceToHost));
     if (lut_host) HIP_TRY(hipMemcpy(lut_host, ltap.p, lt * sizeof(float), hipMemcpyDeviceToHost));
     return TMAC_HIP_OK;
-}
-
-// the per-stream workspaces of the fused entry point's prefill route (tmac_hip_cache_clear; caller holds g_mu)
-void tmac_host::release_fused_workspaces() {
-    for (auto& kv : g_fused_ws) {
-        (void)hipStreamSynchronize(kv.first.second);      // launches in flight may still read the LUT workspace
-        tmac_hip_workspace_free(kv.second);
-    }
-    g_fused_ws.clear();
 }

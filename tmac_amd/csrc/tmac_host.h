@@ -6,7 +6,8 @@
 //   tmac_weights.cpp     weight registration (reference layout -> device layout)
 //   tmac_kperm.cpp       the K permutation of act-order matrices from g_idx (tmac_kperm.h: no HIP, builds with plain g++); its C-ABI: tmac_pack_host.cpp
 //   tmac_pack_host.cpp   device-side packing: GPTQ tensors / plain codes -> reference blob (tmac_pack.hip) -> register_impl
-//   tmac_workspace.cpp   LUT workspace + the preprocessor entry point
+//   tmac_workspace.cpp   LUT workspace: the preprocessor entry points, lut_build (the one caller of the LUT builders; what a workspace holds and
+//                        which launches put it there: tmac_lut_held.h, no HIP, plain g++), the per-stream workspaces of the fused entry point
 //   tmac_xform.cpp       the field rules of tmac_hip_xform: one resolver for every transform site (tmac_xform.h: no HIP, builds with plain g++)
 //   tmac_launch_plan.cpp launch planning of k_gemv_quad / k_gemv_rows and what the fused kernels support: pure functions that fill a plan or refuse
 //                        (tmac_launch_plan.h: also the instantiation policy of every kernel family as constexpr predicates; no HIP, plain g++)
@@ -43,6 +44,7 @@
 #include "tmac_chain.h"
 #include "tmac_kernels.h"
 #include "tmac_kperm.h"
+#include "tmac_lut_held.h"
 #include "tmac_xform.h"
 
 // ---- the C-ABI's opaque objects ---------------------------------------------------------------
@@ -78,17 +80,14 @@ struct tmac_hip_workspace {
     float* lut_biases = nullptr;
     int32_t* dump = nullptr;     // lazily sized parity tap
     size_t dump_elems = 0;
-    int K = 0, N = 0, ags = 0;   // what the LUT currently holds
-    size_t qdev_u4_per_row = 0;
-    // the LUT as k_gemm_planes streams it (tmac_gemm2.hip): built next to the layouts above when N > 1 and ags = 64
+    tmac_host::LutHeld held;     // what the buffers above and the LUT image below hold (tmac_lut_held.h): changed by lut_build and tmac_hip_workspace_write alone
+    // the LUT as k_gemm_planes streams it (tmac_gemm2.hip): built next to the layouts above when N > 1
     void* gimg = nullptr;        // 2 maxK gNpad bytes: the LUT image of the plane-combined GEMM (layouts: Gemm2Args, tmac_kernels.h)
     float* gcol = nullptr;       // 4 (maxK / 64) gNpad floats: its column values
-    int gNpad = 0;
-    bool gimg_valid = false;
+    int gNpad = 0;               // its row stride: maxN rounded up to 64
     float* xf_r = nullptr;       // fp32 [maxN]: 1 / rms per activation row of a transformed N > 1 call (k_xf_rows -> the XF LUT builders)
-    int gimg_kind = 0;           // 1: row-wise image (one act group per row, k_gemm_planes_us) | 2: chunk-major image (act groups of 64, k_gemm_planes)
-    int gimg_K = 0, gimg_N = 0;  // the activation rows the valid image was built from: it serves the LUT above only while these equal K and N
-    uint64_t perm_id = 0;        // id of the K permutation the LUT was built through (tmac_hip_preprocessor_perm_dev); 0 = none: every other build and write
+    // can k_gemm_planes address the LUT image of K at this row stride (below 2 GB)?
+    bool image_fits(int K) const { return gimg && (size_t)2 * K * gNpad < ((size_t)1 << 31); }
 };
 
 namespace tmac_host {
@@ -145,21 +144,16 @@ void bind_thread_device();
 int32_t ensure_device();
 
 constexpr int PLANES_MIN_N = 12;   // default GEMM threshold where k_gemm_planes covers the configuration (tmac_dispatch.cpp)
-constexpr int PAIRS_ROW_MAX_K = 12288;   // largest K of the row-wise pair build (k_preprocess_pairs_row) and so of the row-wise LUT image
 // Fewest activation rows that go to a GEMM instead of the row loop: none when switched off (tmac_hip_set_gemm_min_n(0)), an explicitly
 // set threshold literally, else `fitted`, the caller's own default (setting 32, the knob's initial value, counts as "not set").
 inline int gemm_min_rows(int fitted) { return g_knobs.gemm_min_n <= 0 ? INT_MAX : g_knobs.gemm_min_n != 32 ? g_knobs.gemm_min_n : fitted; }
-// the LUT-image kind (tmac_hip_workspace::gimg_kind) k_gemm_planes wants for this shape: row-wise for unified scales, else chunk-major
-inline int gimg_kind_for(const Shape& s) { return s.m_groups >= 1 ? 1 : 2; }
-// Does the workspace's LUT image belong to the LUT it holds?  Valid, and built from the same K x N activation rows: the only image
-// k_gemm_planes and the image taps may read (whoever rebuilds the LUT without the image clears gimg_valid; K and N guard the rest)
-inline bool image_serves_lut(const tmac_hip_workspace* ws) { return ws->gimg_valid && ws->gimg_K == ws->K && ws->gimg_N == ws->N; }
+// the LUT-image kind k_gemm_planes wants for this shape: row-wise for unified scales, else chunk-major
+inline LutImage image_kind_for(const Shape& s) { return s.m_groups >= 1 ? IMG_ROWWISE : IMG_CHUNK; }
 // The device layout of registered weights, which Shape spells as the pair (ts, lay): 16-table segments for the two-kernel path
 // (k_gemv_lo), 8-table units in 16-row blocks (k_gemv_fused), or 8-table units in row quads (k_gemv_quad and the GEMMs).
 enum Layout { L_LO, L_ROWBLOCK, L_QUAD };
 inline Layout layout_of(const Shape& s) { return s.lay == 2 ? L_QUAD : s.ts == 8 ? L_ROWBLOCK : L_LO; }
 inline void set_layout(Shape& s, Layout l) { s.ts = l == L_LO ? 16 : 8; s.lay = l == L_QUAD ? 2 : 0; }
-inline size_t qdev_u4_for_K(int K) { return (size_t)((K / (4 * TS) + KL - 1) / KL) * 8 * KL; }
 
 // ---- kcfg (tmac_kcfg.cpp; callers hold g_mu) -----------------------------------------------------
 // 1 = found, 0 = no section matches, -1 = several sections match and disagree on what the bytes mean
@@ -176,6 +170,15 @@ int32_t register_impl(tmac_hip_weights** out, const void* A_ref, const void* sca
 
 // ---- workspace (tmac_workspace.cpp) ---------------------------------------------------------------
 int32_t check_lut_shape(tmac_hip_workspace* ws, int K, int N, int ags);
+LutBuildCaps lut_caps(const tmac_hip_workspace* ws);   // the knobs and the workspace as lut_build_plan reads them
+// The launches of a plan of lut_build_plan (the only caller of launch_preprocess* and launch_lut_image): ws->held is cleared, and says what
+// the plan says once the last launch was enqueued.  xf / perm_dev: the transform block / device permutation the request spoke of, or null.
+int32_t lut_build(tmac_hip_workspace* ws, const LutBuildPlan& plan, const void* B_dev, tmac_dtype_t act_dtype, const XfRowsGateArgs* xf,
+                  const int32_t* perm_dev, hipStream_t st);
+// The fused entry point's workspace of this stream on the calling thread's device, large enough for K x N: one per (device, stream) --
+// launches on one stream are ordered, two streams must not share LUT buffers -- grown on demand to the largest K and N seen.
+int32_t stream_workspace(hipStream_t st, int K, int N, tmac_hip_workspace** out);
+void release_fused_workspaces();    // tmac_hip_cache_clear; caller holds g_mu
 
 // ---- dispatch (tmac_dispatch.cpp) -----------------------------------------------------------------
 int32_t qgemm_impl(const tmac_hip_weights* w, const tmac_hip_workspace* ws, void* C_dev, tmac_dtype_t out_dtype, int N, int32_t* dump,
@@ -185,7 +188,6 @@ int32_t fused_impl(const tmac_hip_weights* const* wl, int nmat, const void* B_de
 // what a non-deferred, tap-less fused call is refused for (the per-matrix null checks and plan_fused): TMAC_HIP_OK, or fail(code, message).
 // Pure: reads its arguments and g_knobs.
 int32_t fused_check(const tmac_hip_weights* const* wl, int nmat, void* const* C_list, int N);
-void release_fused_workspaces();   // caller holds g_mu
 // Alignment of caller-owned device pointers: ACT_ALIGN, XFORM_ALIGN and misaligned are tmac_xform.h's; the GEMMs store four outputs at a
 // time (fp32: 16 bytes, fp16: 8).
 inline size_t out_align(tmac_dtype_t d) { return d == TMAC_F16 ? 8 : 16; }

@@ -1,5 +1,6 @@
-// tmac_workspace.cpp — the LUT workspace (TMACGeMMWrapper::set_workspace, tmac_gemm_wrapper.h:257-270, on the device) and
-// the preprocessor entry point that fills it (lut_ctor.cc:38-266 + generated glue).
+// tmac_workspace.cpp — the LUT workspace (TMACGeMMWrapper::set_workspace, tmac_gemm_wrapper.h:257-270, on the device), the preprocessor
+// entry points that fill it (lut_ctor.cc:38-266 + generated glue) through lut_build, the one caller of the LUT builders (what they leave in
+// the workspace: tmac_lut_held.h), and the per-stream workspaces of the fused entry point's N >= 2 routes.
 #include "tmac_host.h"
 
 using namespace tmac_host;
@@ -54,14 +55,55 @@ extern "C" int32_t tmac_hip_workspace_free(tmac_hip_workspace* ws) {
 
 int32_t tmac_host::check_lut_shape(tmac_hip_workspace* ws, int K, int N, int ags) {
     if (!ws) return fail(TMAC_HIP_E_ARG, "null workspace");
-    if (K <= 0 || K > ws->maxK || N <= 0 || N > ws->maxN) return fail(TMAC_HIP_E_ARG, "K=%d N=%d exceed the workspace (%d, %d)", K, N, ws->maxK, ws->maxN);
-    if (ags <= 0 || ags % 32 || K % ags) return fail(TMAC_HIP_E_NOMATCH, "act_group_size=%d must be a multiple of 32 dividing K=%d (qgemm.py:402-404)", ags, K);
-    if (K % 64) return fail(TMAC_HIP_E_NOMATCH, "K=%d must be a multiple of 64", K);
+    return lut_shape_check(K, N, ags, ws->maxK, ws->maxN);
+}
+
+LutBuildCaps tmac_host::lut_caps(const tmac_hip_workspace* ws) {
+    LutBuildCaps c;
+    c.pairs_min_n = g_knobs.pairs_min_n;
+    c.image_min_n = g_knobs.gemm_kernel == 1 ? INT_MAX : gemm_min_rows(PLANES_MIN_N);
+    c.image_buffers = ws->gimg != nullptr;
+    c.maxK = ws->maxK; c.maxN = ws->maxN;
+    return c;
+}
+
+int32_t tmac_host::lut_build(tmac_hip_workspace* ws, const LutBuildPlan& plan, const void* B_dev, tmac_dtype_t act_dtype, const XfRowsGateArgs* xf,
+                             const int32_t* perm_dev, hipStream_t st) {
+    ws->held.clear();
+    const LutHeld& h = plan.held;
+    const int K = h.K(), N = h.N(), f16 = act_dtype == TMAC_F16;
+    const bool all = plan.all_layouts, row_img = plan.row_image;
+    int8_t* const ref = all ? ws->qlut_ref : nullptr;
+    void* const dev = all ? ws->qlut_dev : nullptr;
+    const size_t dev_u4 = all ? h.qdev_u4_per_row() : 0;
+    hipError_t e = hipSuccess;
+    switch (plan.builder) {
+    case LUTB_PREPROCESS:
+        e = launch_preprocess(B_dev, (Dtype)act_dtype, ws->qlut_ref, ws->qlut_dev, ws->qlut_lds, ws->lut_scales, ws->lut_biases, K, N, h.ags(), dev_u4, st);
+        break;
+    case LUTB_PAIRS:
+        e = launch_preprocess_pairs(B_dev, f16, ws->qlut_lds, ws->lut_scales, ws->lut_biases, K, N, ref, dev, dev_u4, st, xf, perm_dev);
+        break;
+    case LUTB_PAIRS_ROW:
+        e = launch_preprocess_pairs_row(B_dev, f16, ws->qlut_lds, ws->lut_scales, ws->lut_biases, K, N, ref, dev, dev_u4, row_img ? ws->gimg : nullptr,
+                                        row_img ? ws->gcol : nullptr, all || row_img ? ws->gNpad : 0, st, xf);
+        break;
+    case LUTB_NONE: break;
+    }
+    // (a builder that writes no layout is there for its image)
+    if (e != hipSuccess) return fail(TMAC_HIP_E_RUNTIME, "%s launch: %s", h.has_layout(LUT_HALF) ? "preprocess" : "LUT image", hipGetErrorString(e));
+    if (plan.lut_image) {
+        e = launch_lut_image(B_dev, f16, ws->gimg, ws->gcol, K, N, ws->gNpad, st, xf, perm_dev);
+        if (e != hipSuccess) return fail(TMAC_HIP_E_RUNTIME, "LUT image launch: %s", hipGetErrorString(e));
+    }
+    ws->held.commit(plan);
     return TMAC_HIP_OK;
 }
 
-extern "C" int32_t tmac_hip_preprocessor_dev(tmac_hip_workspace* ws, const void* B_dev, tmac_dtype_t act_dtype, int K,
-                                             int N, int act_group_size, void* stream) {
+// kp: through this K permutation (act-order handles, tmac_kperm.h): every layout of the workspace from x[perm], by the gathered pair build,
+// for every N; the workspace records the permutation's id, which tmac_hip_qgemm_dev holds the weights to
+static int32_t preprocessor_impl(tmac_hip_workspace* ws, const void* B_dev, tmac_dtype_t act_dtype, int K, int N, int act_group_size,
+                                 const KPermData* kp, hipStream_t st) {
     bind_thread_device();
     int32_t rc = defer_barrier();             // behind the calling thread's deferred queue (B_dev may be a queued call's output)
     if (rc) return rc;
@@ -69,70 +111,32 @@ extern "C" int32_t tmac_hip_preprocessor_dev(tmac_hip_workspace* ws, const void*
     if (rc) return rc;
     if (!B_dev) return fail(TMAC_HIP_E_ARG, "null activations");
     if (misaligned(B_dev, ACT_ALIGN)) return fail(TMAC_HIP_E_ARG, "B_dev must be %zu-byte aligned (the LUT build reads 16 bytes at a time)", ACT_ALIGN);
-    ws->K = K; ws->N = N; ws->ags = act_group_size; ws->qdev_u4_per_row = qdev_u4_for_K(K);
-    ws->perm_id = 0;
-    // k_gemm_planes' LUT image is built when tmac_hip_qgemm_dev may pick that kernel: not for one row, and not below the GEMM threshold
-    // (PLANES_MIN_N by default: the matrix, and with it the measured crossover plan_split applies, is not known here)
-    const bool want_img = N >= 2 && N >= gemm_min_rows(PLANES_MIN_N) && ws->gimg && g_knobs.gemm_kernel != 1;
-    const bool pairs_row = act_group_size == K && K <= PAIRS_ROW_MAX_K && N >= g_knobs.pairs_min_n;
-    // one act group per row: the row-wise pair build also writes the LUT image of the plane-combined GEMM when that may be chosen
-    const bool row_img = pairs_row && want_img;
-    // several activation rows with 64-activation groups: the pair-wise build (two tables per lane, all three layouts);
-    // otherwise one workgroup per act group (any act_group_size, and cheaper than it looks for a single row)
-    hipError_t e = (act_group_size == 64 && N >= g_knobs.pairs_min_n)
-        ? launch_preprocess_pairs(B_dev, act_dtype == TMAC_F16, ws->qlut_lds, ws->lut_scales, ws->lut_biases, K, N, ws->qlut_ref,
-                                  ws->qlut_dev, ws->qdev_u4_per_row, (hipStream_t)stream)
-        : pairs_row
-        ? launch_preprocess_pairs_row(B_dev, act_dtype == TMAC_F16, ws->qlut_lds, ws->lut_scales, ws->lut_biases, K, N, ws->qlut_ref,
-                                      ws->qlut_dev, ws->qdev_u4_per_row, row_img ? ws->gimg : nullptr, row_img ? ws->gcol : nullptr, ws->gNpad,
-                                      (hipStream_t)stream)
-        : launch_preprocess(B_dev, (Dtype)act_dtype, ws->qlut_ref, ws->qlut_dev, ws->qlut_lds, ws->lut_scales, ws->lut_biases,
-                            K, N, act_group_size, ws->qdev_u4_per_row, (hipStream_t)stream);
-    if (e != hipSuccess) return fail(TMAC_HIP_E_RUNTIME, "preprocess launch: %s", hipGetErrorString(e));
-    ws->gimg_valid = row_img; ws->gimg_kind = row_img ? 1 : 0; ws->gimg_K = K; ws->gimg_N = N;
-    if (act_group_size == 64 && want_img) {   // what k_gemm_planes streams (tmac_hip_qgemm_dev may pick it)
-        e = launch_lut_image(B_dev, act_dtype == TMAC_F16, ws->gimg, ws->gcol, K, N, ws->gNpad, (hipStream_t)stream);
-        if (e != hipSuccess) return fail(TMAC_HIP_E_RUNTIME, "LUT image launch: %s", hipGetErrorString(e));
-        ws->gimg_valid = true; ws->gimg_kind = 2;      // (K == 64 with one act group per row: this image wins, the unified-scale GEMM is not offered it)
-    }
-    return TMAC_HIP_OK;
+    LutBuildReq q;
+    q.K = K; q.N = N; q.ags = act_group_size; q.want = LB_ALL;
+    if (kp) { q.perm_id = kp->h.id; q.perm_K = kp->h.K; }
+    LutBuildPlan plan;
+    rc = lut_build_plan(q, lut_caps(ws), &plan);
+    if (rc) return rc;
+    return lut_build(ws, plan, B_dev, act_dtype, nullptr, kp ? kp->dev : nullptr, st);
 }
 
-// The same through a K permutation (act-order handles, tmac_kperm.h): every layout of the workspace from x[perm], by the gathered pair build,
-// for every N; the workspace records the permutation's id, which tmac_hip_qgemm_dev holds the weights to.  NULL or identity: the plain call.
+extern "C" int32_t tmac_hip_preprocessor_dev(tmac_hip_workspace* ws, const void* B_dev, tmac_dtype_t act_dtype, int K,
+                                             int N, int act_group_size, void* stream) {
+    return preprocessor_impl(ws, B_dev, act_dtype, K, N, act_group_size, nullptr, (hipStream_t)stream);
+}
+
+// NULL or identity: the plain call
 extern "C" int32_t tmac_hip_preprocessor_perm_dev(tmac_hip_workspace* ws, const void* B_dev, tmac_dtype_t act_dtype, int K, int N, int act_group_size,
                                                   const tmac_hip_kperm* perm, void* stream) {
-    if (!perm || !perm->d || perm->d->h.identity) return tmac_hip_preprocessor_dev(ws, B_dev, act_dtype, K, N, act_group_size, stream);
-    bind_thread_device();
-    int32_t rc = defer_barrier();
-    if (rc) return rc;
-    rc = check_lut_shape(ws, K, N, act_group_size);
-    if (rc) return rc;
-    if (!B_dev) return fail(TMAC_HIP_E_ARG, "null activations");
-    if (misaligned(B_dev, ACT_ALIGN)) return fail(TMAC_HIP_E_ARG, "B_dev must be %zu-byte aligned (the LUT build reads 16 bytes at a time)", ACT_ALIGN);
-    if (act_group_size != 64) return fail(TMAC_HIP_E_NOMATCH, "the gathered LUT build takes act groups of 64 (act_group_size=%d)", act_group_size);
-    if (perm->d->h.K != K) return fail(TMAC_HIP_E_ARG, "the K permutation was built for K=%d; the call has K=%d", perm->d->h.K, K);
-    hipStream_t st = (hipStream_t)stream;
-    const int f16 = act_dtype == TMAC_F16;
-    ws->K = K; ws->N = N; ws->ags = act_group_size; ws->qdev_u4_per_row = qdev_u4_for_K(K);
-    ws->perm_id = perm->d->h.id;
-    ws->gimg_valid = false; ws->gimg_kind = 0; ws->gimg_K = K; ws->gimg_N = N;
-    hipError_t e = launch_preprocess_pairs(B_dev, f16, ws->qlut_lds, ws->lut_scales, ws->lut_biases, K, N, ws->qlut_ref, ws->qlut_dev, ws->qdev_u4_per_row, st,
-                                           nullptr, perm->d->dev);
-    if (e != hipSuccess) return fail(TMAC_HIP_E_RUNTIME, "preprocess launch: %s", hipGetErrorString(e));
-    if (N >= 2 && N >= gemm_min_rows(PLANES_MIN_N) && ws->gimg && g_knobs.gemm_kernel != 1) {      // tmac_hip_preprocessor_dev's rule for the LUT image
-        e = launch_lut_image(B_dev, f16, ws->gimg, ws->gcol, K, N, ws->gNpad, st, nullptr, perm->d->dev);
-        if (e != hipSuccess) return fail(TMAC_HIP_E_RUNTIME, "LUT image launch: %s", hipGetErrorString(e));
-        ws->gimg_valid = true; ws->gimg_kind = 2;
-    }
-    return TMAC_HIP_OK;
+    const KPermData* kp = perm && perm->d && !perm->d->h.identity ? perm->d.get() : nullptr;
+    return preprocessor_impl(ws, B_dev, act_dtype, K, N, act_group_size, kp, (hipStream_t)stream);
 }
 
 extern "C" int32_t tmac_hip_workspace_ptrs(tmac_hip_workspace* ws, void** qlut_dev, size_t* nbytes_qlut_per_row,
                                            void** lut_scales, void** lut_biases) {
     if (!ws) return fail(TMAC_HIP_E_ARG, "null workspace");
     if (qlut_dev) *qlut_dev = ws->qlut_dev;
-    if (nbytes_qlut_per_row) *nbytes_qlut_per_row = ws->qdev_u4_per_row * 16;
+    if (nbytes_qlut_per_row) *nbytes_qlut_per_row = ws->held.qdev_u4_per_row() * 16;
     if (lut_scales) *lut_scales = ws->lut_scales;
     if (lut_biases) *lut_biases = ws->lut_biases;
     return TMAC_HIP_OK;
@@ -144,7 +148,7 @@ extern "C" int32_t tmac_hip_workspace_read(tmac_hip_workspace* ws, int8_t* qlut_
     if (rc) return rc;
     rc = check_lut_shape(ws, K, N, act_group_size);
     if (rc) return rc;
-    if (ws->K != K || ws->N != N || ws->ags != act_group_size) return fail(TMAC_HIP_E_ARG, "workspace holds a different LUT");
+    if (!ws->held.holds_exactly(K, N, act_group_size)) return fail(TMAC_HIP_E_ARG, "workspace holds a different LUT");
     hipStream_t st = (hipStream_t)stream;
     const size_t G = (size_t)K / act_group_size;
     if (qlut_host) HIP_TRY(hipMemcpyAsync(qlut_host, ws->qlut_ref, (size_t)N * (K / 4) * 16, hipMemcpyDeviceToHost, st));
@@ -163,13 +167,46 @@ extern "C" int32_t tmac_hip_workspace_write(tmac_hip_workspace* ws, const int8_t
     if (!qlut_host || !lut_scales_host || !lut_biases_host) return fail(TMAC_HIP_E_ARG, "null LUT pointer");
     hipStream_t st = (hipStream_t)stream;
     const size_t G = (size_t)K / act_group_size;
-    ws->K = K; ws->N = N; ws->ags = act_group_size; ws->qdev_u4_per_row = qdev_u4_for_K(K);
-    ws->gimg_valid = false;      // k_gemm_planes' LUT image (built from activations by tmac_hip_preprocessor_dev) no longer matches this LUT
-    ws->perm_id = 0;
+    const LutBuildPlan plan = lut_write_plan(K, N, act_group_size);      // (no image: the one there was built from activations, not from this LUT)
+    ws->held.clear();
     HIP_TRY(hipMemcpyAsync(ws->qlut_ref, qlut_host, (size_t)N * (K / 4) * 16, hipMemcpyHostToDevice, st));
     HIP_TRY(hipMemcpyAsync(ws->lut_scales, lut_scales_host, sizeof(float) * N * G, hipMemcpyHostToDevice, st));
     HIP_TRY(hipMemcpyAsync(ws->lut_biases, lut_biases_host, sizeof(float) * N * G, hipMemcpyHostToDevice, st));
-    hipError_t e = launch_qlut_ref_to_dev(ws->qlut_ref, ws->qlut_dev, ws->qlut_lds, K, N, ws->qdev_u4_per_row, st);
+    hipError_t e = launch_qlut_ref_to_dev(ws->qlut_ref, ws->qlut_dev, ws->qlut_lds, K, N, plan.held.qdev_u4_per_row(), st);
     if (e != hipSuccess) return fail(TMAC_HIP_E_RUNTIME, "qlut_ref_to_dev launch: %s", hipGetErrorString(e));
+    ws->held.commit(plan);
     return TMAC_HIP_OK;
+}
+
+// ---- the fused entry point's workspaces ------------------------------------------------------------------------------------------------
+static std::map<std::pair<int, hipStream_t>, tmac_hip_workspace*> g_fused_ws;   // per (device, stream): the null stream exists on every device
+
+int32_t tmac_host::stream_workspace(hipStream_t st, int K, int N, tmac_hip_workspace** out) {
+    std::lock_guard<std::mutex> lk(g_mu);
+    tmac_hip_workspace*& slot = g_fused_ws[std::make_pair(g_device, st)];
+    int needK = K, needN = N;
+    if (slot && (slot->maxK < K || slot->maxN < N)) {
+        // grow to the maximum seen in BOTH dimensions (mixed shapes -- K = 4096 / 11008, growing N -- would otherwise
+        // free and reallocate on every other call); the old buffers may still be read by launches in flight
+        needK = slot->maxK > K ? slot->maxK : K;
+        needN = slot->maxN > N ? slot->maxN : N;
+        hipError_t e = hipStreamSynchronize(st);
+        if (e != hipSuccess) return fail(TMAC_HIP_E_RUNTIME, "stream sync: %s", hipGetErrorString(e));
+        tmac_hip_workspace_free(slot);
+        slot = nullptr;
+    }
+    if (!slot) {
+        int32_t rc = tmac_hip_workspace_create(&slot, needK, needN);
+        if (rc) { slot = nullptr; return rc; }
+    }
+    *out = slot;
+    return TMAC_HIP_OK;
+}
+
+void tmac_host::release_fused_workspaces() {
+    for (auto& kv : g_fused_ws) {
+        (void)hipStreamSynchronize(kv.first.second);      // launches in flight may still read the LUT workspace
+        tmac_hip_workspace_free(kv.second);
+    }
+    g_fused_ws.clear();
 }
