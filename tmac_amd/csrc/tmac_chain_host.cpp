@@ -19,17 +19,12 @@ static thread_local std::optional<XfSpec> g_chain_xf;               // the trans
 bool tmac_host::chain_recording() { return g_chain_rec != nullptr; }
 void tmac_host::chain_clear_xform() { g_chain_xf.reset(); }
 
-int32_t tmac_host::chain_record(const tmac_hip_weights* const* wl, int nmat, const void* B_dev, tmac_dtype_t act_dtype,
-                            void* const* C_list, tmac_dtype_t out_dtype, int N) {
+int32_t tmac_host::chain_record(const FusedCall& c) {
     // (a rejected call must not leave its transform pending for the next recorded call)
-    if (N != 1) { chain_clear_xform(); return fail(TMAC_HIP_E_NOMATCH, "a decode chain records N = 1 calls only"); }
-    ChainRecOp op;
-    for (int i = 0; i < nmat; ++i) {
-        if (!wl[i] || !C_list[i]) { chain_clear_xform(); return fail(TMAC_HIP_E_ARG, "null matrix or output"); }
-        op.w.push_back(wl[i]);
-        op.C.push_back(C_list[i]);
-    }
-    op.B = B_dev; op.act = act_dtype; op.out = out_dtype;
+    if (c.N != 1) { chain_clear_xform(); return fail(TMAC_HIP_E_NOMATCH, "a decode chain records N = 1 calls only"); }
+    const int32_t nrc = nulls_check(c);
+    if (nrc) { chain_clear_xform(); return nrc; }
+    ChainRecOp op(c);
     op.xf = g_chain_xf.value_or(XfSpec{});
     chain_clear_xform();
     g_chain_rec->push_back(op);

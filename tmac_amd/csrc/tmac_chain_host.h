@@ -52,6 +52,12 @@ struct ChainRecOp {
     std::vector<void*> C;
     tmac_dtype_t act, out;
     XfSpec xf;                       // vector transform of the activations, resolved (tmac_xform.h; kind 0: none)
+    ChainRecOp() = default;
+    explicit ChainRecOp(const FusedCall& c) : w(c.wl, c.wl + c.nmat), B(c.B), C(c.C, c.C + c.nmat), act(c.act), out(c.out) {}
+    // ... and back: the call as a view over this op's own lists
+    FusedCall call(hipStream_t st) const { return FusedCall{w.data(), (int)w.size(), B, act, C.data(), out, 1, st}; }
+    // the fields that make two noted calls the same call (a deferred batch's signature is its calls)
+    bool same_call(const ChainRecOp& o) const { return B == o.B && act == o.act && out == o.out && w == o.w && C == o.C; }
 };
 // an exchange step noted while recording: recv = all-gather over the ranks of send (rank r's bytes at r * bytes)
 struct ChainRecGather {

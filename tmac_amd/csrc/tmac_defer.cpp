@@ -1,5 +1,6 @@
 // tmac_defer.cpp — the deferred queue (tmac_hip_defer / tmac_hip_flush): independent N = 1 calls launched together as one stream-mode chain.
 #include "tmac_chain_host.h"
+#include <algorithm>
 #include <atomic>
 
 using namespace tmac_host;
@@ -19,15 +20,8 @@ using namespace tmac_host;
 // (a failed stream launch: its calls one by one) and leaves the queue empty.
 // ---------------------------------------------------------------------------------------------
 namespace {
-struct DeferKey {
-    std::vector<const tmac_hip_weights*> w;
-    std::vector<void*> C;
-    const void* B;
-    int act, out;
-    bool operator==(const DeferKey& o) const { return B == o.B && act == o.act && out == o.out && w == o.w && C == o.C; }
-};
 struct DeferEntry {
-    std::vector<DeferKey> sig;
+    std::vector<ChainRecOp> sig;           // the batch it was built from (compared by ChainRecOp::same_call)
     std::vector<tmac_hip_chain*> chains;   // one stream-mode recording per configuration of the batch (bits, zero points, scale kind and dtype, output dtype)
     std::vector<std::vector<uint32_t>> chain_calls;   // ... and the calls of the batch it stands for (launched one by one when its launch fails)
     std::vector<uint32_t> singles;         // calls of the batch launched one by one (no persistent form, or alone in their configuration)
@@ -72,17 +66,17 @@ int32_t defer_flush(hipStream_t st) {
         D.cache.clear();
         D.epoch = ep;
     }
-    std::vector<DeferKey> sig(batch.size());
-    for (size_t i = 0; i < batch.size(); ++i) { sig[i].w = batch[i].w; sig[i].C = batch[i].C; sig[i].B = batch[i].B; sig[i].act = (int)batch[i].act; sig[i].out = (int)batch[i].out; }
+    auto same = [](const ChainRecOp& a, const ChainRecOp& b) { return a.same_call(b); };
     DeferEntry* hit = nullptr;
-    for (DeferEntry& e : D.cache) if (e.sig == sig) { hit = &e; break; }
+    for (DeferEntry& e : D.cache)
+        if (e.sig.size() == batch.size() && std::equal(batch.begin(), batch.end(), e.sig.begin(), same)) { hit = &e; break; }
     if (hit) ++D.n_hit;
     else {
         // The calls of a batch are independent of each other (defer_if_on), so they may be regrouped: one recording per configuration
         // a persistent kernel is instantiated for -- a caller that mixes 2- and 4-bit matrices (qgemm.py:98-116 allows any mix) gets one
         // stream launch per width instead of a launch per call.
         DeferEntry ne;
-        ne.sig = sig; ne.used = 0;
+        ne.sig = batch; ne.used = 0;
         std::vector<char> taken(batch.size(), 0);
         for (size_t i = 0; i < batch.size(); ++i) {
             if (taken[i]) continue;
@@ -122,10 +116,9 @@ int32_t defer_flush(hipStream_t st) {
     const bool was_on = D.on;
     D.on = false;                                               // call by call, as if never queued
     auto single = [&](uint32_t j) {
-        const ChainRecOp& r = batch[j];
         ++D.n_single;
         const int32_t rc = defer_injected_failure() ? fail(TMAC_HIP_E_RUNTIME, "deferred call: injected launch failure (tmac_hip_debug_defer_fail)")
-                                                    : fused_impl(r.w.data(), (int)r.w.size(), r.B, r.act, r.C.data(), r.out, 1, nullptr, nullptr, st);
+                                                    : fused_impl(batch[j].call(st), nullptr, nullptr);
         if (rc != TMAC_HIP_OK && first == TMAC_HIP_OK) first = rc;
     };
     for (size_t g = 0; g < hit->chains.size(); ++g) {
@@ -140,20 +133,17 @@ int32_t defer_flush(hipStream_t st) {
 }
 }  // namespace
 
-bool tmac_host::defer_if_on(const tmac_hip_weights* const* wl, int nmat, const void* B_dev, tmac_dtype_t act_dtype, void* const* C_list,
-                            tmac_dtype_t out_dtype, int N, hipStream_t st, int32_t* rc) {
+bool tmac_host::defer_if_on(const FusedCall& c, int32_t* rc) {
     DeferState& D = g_defer;
     if (!D.on) return false;
     *rc = TMAC_HIP_OK;
-    if (N != 1) { *rc = defer_flush(D.stream); return *rc != TMAC_HIP_OK; }    // (ordered behind the queue; launched as usual -- unless the queue failed)
+    if (c.N != 1) { *rc = defer_flush(D.stream); return *rc != TMAC_HIP_OK; }    // (ordered behind the queue; launched as usual -- unless the queue failed)
     // what the call would be refused for with deferral off: refused now, with that code and message, and the queue is left as it is
-    if ((*rc = fused_check(wl, nmat, C_list, 1)) != TMAC_HIP_OK) return true;
-    ChainRecOp op;
-    for (int i = 0; i < nmat; ++i) { op.w.push_back(wl[i]); op.C.push_back(C_list[i]); }
-    op.B = B_dev; op.act = act_dtype; op.out = out_dtype;
+    if ((*rc = fused_check(c)) != TMAC_HIP_OK) return true;
+    const ChainRecOp op(c);
     // a dependence on the queue (RAW: reads a queued output; WAR / WAW: writes what a queued call reads or writes), another stream, or a
     // full queue: the queue goes first
-    bool must_flush = !D.pending.empty() && (st != D.stream || D.pending.size() >= DEFER_MAX_BATCH);
+    bool must_flush = !D.pending.empty() && (c.st != D.stream || D.pending.size() >= DEFER_MAX_BATCH);
     const Range in = act_range(op);
     for (size_t j = 0; j < D.pending.size() && !must_flush; ++j) {
         const ChainRecOp& p = D.pending[j];
@@ -166,7 +156,7 @@ bool tmac_host::defer_if_on(const tmac_hip_weights* const* wl, int nmat, const v
         for (size_t k = 0; k < op.C.size(); ++k) if (overlap(out_range(op, k, op.out), pin)) must_flush = true;
     }
     if (must_flush && (*rc = defer_flush(D.stream)) != TMAC_HIP_OK) return true;
-    D.stream = st;
+    D.stream = c.st;
     D.pending.push_back(op);
     return true;
 }

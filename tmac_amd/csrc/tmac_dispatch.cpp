@@ -1,6 +1,7 @@
 // tmac_dispatch.cpp — qgemm_lut dispatch: which kernel serves a call (decode GEMV variants, the N > 1 GEMMs, the fused
 // LUT-build + GEMV entry point and its prefill route) and the parity taps around them.  A call is planned (plan_split /
-// plan_fused name the kernel: enum Route), then launched.
+// plan_fused name the kernel: enum Route), then launched.  A fused call is one value (FusedCall, tmac_host.h): its doors share named
+// checks, one planner call (plan_call) and one launch site for k_gemv_quad (launch_quad).
 #include "tmac_host.h"
 
 using namespace tmac_host;
@@ -37,6 +38,8 @@ static bool same_quant(const tmac_hip_weights* a, const tmac_hip_weights* b) {
     return a->s.bits == b->s.bits && a->s.gs == b->s.gs && a->s.zero_point == b->s.zero_point && a->s.m_groups == b->s.m_groups &&
            a->sc_dtype == b->sc_dtype;
 }
+// ... what a call that breaks either is told (plan_fused, one_lut_check)
+static const char* const ONE_LUT_MSG = "matrices fused in one launch must share K, bits and quantisation config";
 // GEMM or row loop for N activation rows on matrices with total_Mw output rows?  An explicitly set threshold
 // (tmac_hip_set_gemm_min_n) is taken literally.  Otherwise: the measured crossover per launch where k_gemm_planes covers the
 // configuration (planes_pays), and k_gemm_onehot only from 32 rows on with a grid that fills the chip (onehot_pays: with fewer
@@ -183,8 +186,7 @@ static Plan plan_fused(const tmac_hip_weights* const* wl, void* const* C_list, i
         if (!w || !C_list[i]) return refused(TMAC_HIP_E_ARG, "null matrix or output");
         if (layout_of(w->s) == L_LO || !w->tiled_ok || layout_of(w->s) != layout_of(wl[0]->s))
             return refused(TMAC_HIP_E_NOMATCH, "matrix %d is not registered in the fused layout", i);
-        if (!same_lut(w, wl[0]) || !same_quant(w, wl[0]))
-            return refused(TMAC_HIP_E_ARG, "matrices fused in one launch must share K, bits and quantisation config");
+        if (!same_lut(w, wl[0]) || !same_quant(w, wl[0])) return refused(TMAC_HIP_E_ARG, ONE_LUT_MSG);
     }
     if (rows) {
         long total = 0;
@@ -194,83 +196,101 @@ static Plan plan_fused(const tmac_hip_weights* const* wl, void* const* C_list, i
     return planned(layout_of(wl[0]->s) == L_QUAD ? R_GEMV_QUAD : R_GEMV_FUSED);
 }
 
-int32_t tmac_host::fused_check(const tmac_hip_weights* const* wl, int nmat, void* const* C_list, int N) {
-    const Plan p = plan_fused(wl, C_list, nmat, N, false);
+// ---- one plan per call -----------------------------------------------------------------------------------------------------
+// A transformed call of N >= 2 rows (tmac_hip_qgemm_fused_xf_rows_dev) runs on a plan of plan_fused with two rules of its own: where the
+// planner answers R_GEMV_QUAD (k_gemv_quad with grid.y = N, each workgroup building its row's LUT) the call takes R_ROW_LOOP behind
+// LB_HALF_TABLES -- the transform sits in the pair build, k_gemv_quad copies the image (LUTSRC == 0) -- and a plan that needs LB_ALL (the
+// three-layout build has no XF instantiation) is refused.  A call on act-order handles takes the same two (its gather sits where the
+// transform would).
+static Plan xf_rows_plan(Plan p) {
+    if (p.err) return p;
+    if (p.route == R_GEMV_QUAD) return planned(R_ROW_LOOP, LB_HALF_TABLES);
+    if (p.lut != LB_IMAGE && p.lut != LB_HALF_TABLES)
+        return refused(TMAC_HIP_E_NOMATCH, "a transformed call of several rows needs the LUT image or the half-table image alone; this plan builds every layout");
+    return p;
+}
+// The plan of a fused call, for every door, both debug twins and fused_prefill's re-plan.  in_build: the call carries a vector transform
+// or a K permutation, which for N >= 2 rows lives in the LUT build (xf_rows_plan); image_fits: see the planners.
+static Plan plan_call(const FusedCall& c, bool tap, bool in_build = false, bool image_fits = true) {
+    const Plan p = plan_fused(c.wl, c.C, c.nmat, c.N, tap, image_fits);
+    return in_build && c.N >= 2 ? xf_rows_plan(p) : p;
+}
+int32_t tmac_host::fused_check(const FusedCall& c) {
+    const Plan p = plan_call(c, false);
     return p.err ? fail(p.err, p.msg, p.mat) : TMAC_HIP_OK;
 }
 
 // ---- argument blocks of the planned kernels --------------------------------------------------------------------------------
-static void fill_gemm_mats(GemmMat* m, const tmac_hip_weights* const* wl, void* const* C_list, int nmat) {
-    for (int i = 0; i < nmat; ++i) { m[i].W = wl[i]->W; m[i].SC = wl[i]->SC; m[i].C = C_list[i]; m[i].Mw = wl[i]->s.Mw; }
+// the split entry point's matrix (and the taps') as a one-matrix call for the launch helpers below
+static FusedCall one_matrix(const tmac_hip_weights* const* w, void* const* C, tmac_dtype_t out, int N, hipStream_t st) {
+    return FusedCall{w, 1, nullptr, TMAC_F32, C, out, N, st};
 }
-// what the two GEMV sites share; returns the launch's row blocks (row quads in the QUAD layout) over all matrices
-static int fill_fused_args(FusedArgs& fa, const tmac_hip_weights* const* wl, void* const* C_list, int nmat, tmac_dtype_t out_dtype, int32_t* dump) {
+static void fill_gemm_mats(GemmMat* m, const FusedCall& c) {
+    for (int i = 0; i < c.nmat; ++i) { m[i].W = c.wl[i]->W; m[i].SC = c.wl[i]->SC; m[i].C = c.C[i]; m[i].Mw = c.wl[i]->s.Mw; }
+}
+int tmac_host::fill_fused_args(FusedArgs& fa, const FusedCall& c) {
     memset(&fa, 0, sizeof(fa));
-    fa.nmat = nmat; fa.s = wl[0]->s;
+    fa.nmat = c.nmat; fa.s = c.s0();
     const bool quad = layout_of(fa.s) == L_QUAD;
     int nb = 0;
-    for (int i = 0; i < nmat; ++i) {
-        const Shape& a = wl[i]->s;
+    for (int i = 0; i < c.nmat; ++i) {
+        const Shape& a = c.wl[i]->s;
         nb += quad ? a.nquads() : a.nb();
-        fa.m[i].W = (const uint4*)wl[i]->W; fa.m[i].SC = wl[i]->SC; fa.m[i].C = C_list[i]; fa.m[i].Mw = a.Mw; fa.m[i].nb_end = nb;
+        fa.m[i].W = (const uint4*)c.wl[i]->W; fa.m[i].SC = c.wl[i]->SC; fa.m[i].C = c.C[i]; fa.m[i].Mw = a.Mw; fa.m[i].nb_end = nb;
     }
-    fa.sc_f16 = wl[0]->sc_dtype == F16; fa.out_f16 = out_dtype == TMAC_F16; fa.dump = dump;
+    fa.B = c.B; fa.act_f16 = c.act_f16();
+    fa.sc_f16 = c.wl[0]->sc_dtype == F16; fa.out_f16 = c.out_f16();
     fa.acc_mfma = quad ? (g_knobs.variant != V_QUAD_MQSAD) : (g_knobs.variant == V_FUSED_MFMA);
     return nb;
 }
-static int32_t fused_gemv_rc(hipError_t e) {
-    if (e == hipErrorInvalidValue) return fail(TMAC_HIP_E_NOMATCH, "no fused GEMV kernel for this configuration");
-    if (e != hipSuccess) return fail(TMAC_HIP_E_RUNTIME, "fused gemv launch: %s", hipGetErrorString(e));
+static int32_t fused_gemv_rc(hipError_t e, const char* nomatch = "no fused GEMV kernel for this configuration", const char* what = "fused gemv") {
+    if (e == hipErrorInvalidValue) return fail(TMAC_HIP_E_NOMATCH, "%s", nomatch);
+    if (e != hipSuccess) return fail(TMAC_HIP_E_RUNTIME, "%s launch: %s", what, hipGetErrorString(e));
     return TMAC_HIP_OK;
 }
 
 // one-hot MFMA GEMM over 1..4 matrices that share K, the quantisation config (checked by the planners) and the LUT in ws
-static int32_t gemm_multi(const tmac_hip_weights* const* wl, int nmat, const tmac_hip_workspace* ws, void* const* C_list,
-                          tmac_dtype_t out_dtype, int N, int32_t* dump, hipStream_t st) {
+static int32_t gemm_multi(const FusedCall& c, const tmac_hip_workspace* ws, int32_t* dump) {
     GemmArgs ga;
     memset(&ga, 0, sizeof(ga));
-    const tmac_hip_weights* w0 = wl[0];
-    ga.s = w0->s; ga.nmat = nmat;
-    fill_gemm_mats(ga.m, wl, C_list, nmat);
-    ga.sc_f16 = w0->sc_dtype == F16; ga.out_f16 = out_dtype == TMAC_F16;
-    ga.qlut_lds = ws->qlut_lds; ga.tstride = (((w0->s.K / 32) + 15) & ~15) + 1; ga.lut_scales = ws->lut_scales; ga.lut_biases = ws->lut_biases;
-    ga.dump = dump; ga.N = N;
-    hipError_t e = launch_gemm_onehot(ga, st);
+    ga.s = c.s0(); ga.nmat = c.nmat;
+    fill_gemm_mats(ga.m, c);
+    ga.sc_f16 = c.wl[0]->sc_dtype == F16; ga.out_f16 = c.out_f16();
+    ga.qlut_lds = ws->qlut_lds; ga.tstride = (((ga.s.K / 32) + 15) & ~15) + 1; ga.lut_scales = ws->lut_scales; ga.lut_biases = ws->lut_biases;
+    ga.dump = dump; ga.N = c.N;
+    hipError_t e = launch_gemm_onehot(ga, c.st);
     if (e != hipSuccess) return fail(TMAC_HIP_E_RUNTIME, "one-hot gemm launch: %s", hipGetErrorString(e));
     return TMAC_HIP_OK;
 }
 
 // k_gemm_planes over up to 4 matrices that share K and the quantisation config; the workspace holds the LUT image
-static int32_t planes_multi(const tmac_hip_weights* const* wl, int nmat, const tmac_hip_workspace* ws, void* const* C_list,
-                            tmac_dtype_t out_dtype, int N, int32_t* comb_dump, hipStream_t st) {
+static int32_t planes_multi(const FusedCall& c, const tmac_hip_workspace* ws, int32_t* comb_dump) {
     Gemm2Args ga;
     memset(&ga, 0, sizeof(ga));
-    const tmac_hip_weights* w0 = wl[0];
-    ga.s = w0->s; ga.nmat = nmat;
-    fill_gemm_mats(ga.m, wl, C_list, nmat);
-    ga.sc_f16 = w0->sc_dtype == F16; ga.out_f16 = out_dtype == TMAC_F16;
-    ga.bimg = (const uint4*)ws->gimg; ga.colv = ws->gcol; ga.Npad = ws->gNpad; ga.N = N; ga.dump = comb_dump;
+    ga.s = c.s0(); ga.nmat = c.nmat;
+    fill_gemm_mats(ga.m, c);
+    ga.sc_f16 = c.wl[0]->sc_dtype == F16; ga.out_f16 = c.out_f16();
+    ga.bimg = (const uint4*)ws->gimg; ga.colv = ws->gcol; ga.Npad = ws->gNpad; ga.N = c.N; ga.dump = comb_dump;
     ga.stamps = g_knobs.gemm_stamps;
     ga.form = g_knobs.gemm_kernel == 2 ? 1 : g_knobs.gemm_kernel == 3 ? 2 : 0;
-    hipError_t e = launch_gemm_planes(ga, st);
+    hipError_t e = launch_gemm_planes(ga, c.st);
     if (e == hipErrorInvalidValue) return fail(TMAC_HIP_E_NOMATCH, "plane-combined gemm: configuration or sizes not covered (LUT image and matrices must stay below 2 GB)");
     if (e != hipSuccess) return fail(TMAC_HIP_E_RUNTIME, "plane-combined gemm launch: %s", hipGetErrorString(e));
     return TMAC_HIP_OK;
 }
 
 // k_gemv_rows over up to 4 matrices that share K and the quantisation config; the workspace holds the half-table image of N rows
-static int32_t rows_multi(const tmac_hip_weights* const* wl, int nmat, const tmac_hip_workspace* ws, void* const* C_list,
-                          tmac_dtype_t out_dtype, int N, int32_t* tap, hipStream_t st) {
+static int32_t rows_multi(const FusedCall& c, const tmac_hip_workspace* ws, int32_t* tap) {
     FusedArgs fa;
-    fill_fused_args(fa, wl, C_list, nmat, out_dtype, nullptr);
+    fill_fused_args(fa, c);
     RowsArgs ra;
     memset(&ra, 0, sizeof(ra));
-    for (int i = 0; i < nmat; ++i) ra.m[i] = fa.m[i];
-    ra.nmat = nmat; ra.s = fa.s; ra.sc_f16 = fa.sc_f16; ra.out_f16 = fa.out_f16;
+    for (int i = 0; i < c.nmat; ++i) ra.m[i] = fa.m[i];
+    ra.nmat = c.nmat; ra.s = fa.s; ra.sc_f16 = fa.sc_f16; ra.out_f16 = fa.out_f16;
     ra.qlut_lds = ws->qlut_lds; ra.lut_scales = ws->lut_scales; ra.lut_biases = ws->lut_biases;
-    ra.tap = tap; ra.N = N;
+    ra.tap = tap; ra.N = c.N;
     int launches = 0;
-    const hipError_t e = launch_gemv_rows(ra, st, &launches);
+    const hipError_t e = launch_gemv_rows(ra, c.st, &launches);
     g_knobs.rows_launches += (uint64_t)launches;
     if (e == hipErrorInvalidValue) return fail(TMAC_HIP_E_NOMATCH, "rows kernel: configuration or sizes not covered (matrices must stay below 2 GB)");
     if (e != hipSuccess) return fail(TMAC_HIP_E_RUNTIME, "rows kernel launch: %s", hipGetErrorString(e));
@@ -284,20 +304,60 @@ static int32_t rows_multi(const tmac_hip_weights* const* wl, int nmat, const tma
 static const KPermData* perm_of(const tmac_hip_weights* w) { return w ? w->kperm.get() : nullptr; }
 static uint64_t perm_id_of(const tmac_hip_weights* w) { return w && w->kperm ? w->kperm->h.id : 0; }
 // 0: no matrix carries a permutation | 1: all carry the same one (tmac_kperm.h: one object, or equal contents) | -1: a mix
-static int perm_state(const tmac_hip_weights* const* wl, int nmat) {
+static int perm_state(const FusedCall& c) {
     int with = 0;
-    for (int i = 0; i < nmat; ++i) with += perm_of(wl[i]) ? 1 : 0;
+    for (int i = 0; i < c.nmat; ++i) with += perm_of(c.wl[i]) ? 1 : 0;
     if (with == 0) return 0;
-    if (with != nmat) return -1;
-    for (int i = 1; i < nmat; ++i)
-        if (!kperm_equal(&perm_of(wl[0])->h, &perm_of(wl[i])->h)) return -1;
+    if (with != c.nmat) return -1;
+    for (int i = 1; i < c.nmat; ++i)
+        if (!kperm_equal(&perm_of(c.wl[0])->h, &perm_of(c.wl[i])->h)) return -1;
     return 1;
 }
-// entry points that do not serve act-order handles: refused by name
-static int32_t refuse_perm(const tmac_hip_weights* const* wl, int nmat, const char* what) {
-    for (int i = 0; wl && i < nmat; ++i)
-        if (perm_of(wl[i])) return fail(TMAC_HIP_E_ARG, "matrix %d carries a K permutation (act-order): %s on such handles is not served yet", i, what);
+
+// ---- the checks of the fused doors -----------------------------------------------------------------------------------------------
+// Each rule is said once, with its message.  The ORDER in which a door asks them is the door's own -- fused_impl holds the outputs to
+// their alignment before the activations, tmac_hip_qgemm_fused_xf_dev the other way round -- and a caller with two faults gets the
+// message of the first: tests/golden/fused_refusals.json pins every door's order (tests/test_gpu_fused_refusals.py).
+static int32_t args_check(const FusedCall& c) {
+    if (!c.wl || !c.C || !c.B || c.nmat < 1 || c.nmat > 4 || c.N < 1) return fail(TMAC_HIP_E_ARG, "bad fused arguments (1..4 matrices)");
     return TMAC_HIP_OK;
+}
+int32_t tmac_host::nulls_check(const FusedCall& c) {
+    for (int i = 0; i < c.nmat; ++i)
+        if (!c.wl[i] || !c.C[i]) return fail(TMAC_HIP_E_ARG, "null matrix or output");
+    return TMAC_HIP_OK;
+}
+// the alignment contract of the activations and the outputs (include/tmac_hip.h, "Alignment")
+static int32_t act_align_check(const void* B_dev) {
+    if (misaligned(B_dev, ACT_ALIGN)) return fail(TMAC_HIP_E_ARG, "B_dev must be %zu-byte aligned (the LUT build reads 16 bytes at a time)", ACT_ALIGN);
+    return TMAC_HIP_OK;
+}
+static int32_t out_align_check(const FusedCall& c) {
+    for (int i = 0; i < c.nmat; ++i)
+        if (misaligned(c.C[i], out_align(c.out)))
+            return fail(TMAC_HIP_E_ARG, "C_dev[%d] must be %zu-byte aligned (four outputs are stored at a time)", i, out_align(c.out));
+    return TMAC_HIP_OK;
+}
+// one LUT, one kernel instantiation for all matrices of the call
+static int32_t one_lut_check(const FusedCall& c) {
+    for (int i = 0; i < c.nmat; ++i)
+        if (!same_lut(c.wl[i], c.wl[0]) || !same_quant(c.wl[i], c.wl[0])) return fail(TMAC_HIP_E_ARG, "%s", ONE_LUT_MSG);
+    return TMAC_HIP_OK;
+}
+// doors that do not serve act-order handles: refused by name
+static int32_t refuse_perm(const FusedCall& c, const char* what) {
+    for (int i = 0; c.wl && i < c.nmat; ++i)
+        if (perm_of(c.wl[i])) return fail(TMAC_HIP_E_ARG, "matrix %d carries a K permutation (act-order): %s on such handles is not served yet", i, what);
+    return TMAC_HIP_OK;
+}
+// What k_gemv_quad's MFMA form with an in-kernel LUT build takes, as the set of conditions a matrix misses (0: it is served).  A door
+// asks for the conditions in its scope and words its own refusal.
+// The conditions: the reference-layout variant or the v_mqsad accumulate is selected | not registered in the QUAD layout, or its tiled
+// kernel does not cover the configuration | fast-aggregation weights | gemv_quad_supported says no.
+enum : unsigned { QM_REF_VARIANT = 1, QM_MQSAD_VARIANT = 2, QM_LAYOUT = 4, QM_FAST_AGG = 8, QM_SHAPE = 16 };
+static unsigned quad_mfma_misses(const tmac_hip_weights* w) {
+    return (g_knobs.variant == V_REF_LAYOUT ? QM_REF_VARIANT : 0u) | (g_knobs.variant == V_QUAD_MQSAD ? QM_MQSAD_VARIANT : 0u) |
+           (layout_of(w->s) != L_QUAD || !w->tiled_ok ? QM_LAYOUT : 0u) | (w->fa ? QM_FAST_AGG : 0u) | (!gemv_quad_supported(w->s) ? QM_SHAPE : 0u);
 }
 
 // ---- split entry point -----------------------------------------------------------------------------------------------------
@@ -325,16 +385,18 @@ int32_t tmac_host::qgemm_impl(const tmac_hip_weights* w, const tmac_hip_workspac
                     planes ? "the LUT image" : reads == LUT_REF ? "qlut_ref" : reads == LUT_DEV ? "qlut_dev" : "the half-table image");
     count_route(p.route);
     void* cl[1] = {C_dev};
+    const FusedCall one = one_matrix(&w, cl, out_dtype, N, st);
     switch (p.route) {
-    case R_GEMM_PLANES: return planes_multi(&w, 1, ws, cl, out_dtype, N, nullptr, st);
-    case R_GEMM_ONEHOT: return gemm_multi(&w, 1, ws, cl, out_dtype, N, dump, st);
-    case R_GEMV_ROWS: return rows_multi(&w, 1, ws, cl, out_dtype, N, nullptr, st);
+    case R_GEMM_PLANES: return planes_multi(one, ws, nullptr);
+    case R_GEMM_ONEHOT: return gemm_multi(one, ws, dump);
+    case R_GEMV_ROWS: return rows_multi(one, ws, nullptr);
     case R_GEMV_QUAD:
     case R_GEMV_FUSED: {
         FusedArgs fa;
-        fill_fused_args(fa, &w, cl, 1, out_dtype, dump);
+        fill_fused_args(fa, one);
+        fa.dump = dump;
         fa.qlut_lds = ws->qlut_lds; fa.lut_scales = ws->lut_scales; fa.lut_biases = ws->lut_biases;
-        return fused_gemv_rc(p.route == R_GEMV_QUAD ? launch_gemv_quad(fa, N, false, g_knobs.force_ft, g_knobs.force_wpq, st)
+        return fused_gemv_rc(p.route == R_GEMV_QUAD ? launch_gemv_quad(fa, N, false, g_knobs.force_ft, g_knobs.force_wpq, false, st)
                                                     : launch_gemv_fused(fa, N, false, st));
     }
     default: break;
@@ -425,7 +487,7 @@ extern "C" int32_t tmac_hip_debug_gemm_comb_sums(const tmac_hip_weights* w, cons
     HIP_TRY(Ctmp.alloc(sizeof(float) * (size_t)N * w->s.Mw));
     void* cl[1] = {Ctmp.p};
     return run_tap(ws->dump, ws->dump_elems, elems, comb_host, st, "comb-sum",
-                   [&](int32_t* tap) { return planes_multi(&w, 1, ws, cl, TMAC_F32, N, tap, st); });
+                   [&](int32_t* tap) { return planes_multi(one_matrix(&w, cl, TMAC_F32, N, st), ws, tap); });
 }
 
 // ---- k_gemv_rows: knob, counter, the row-group rule, parity tap ------------------------------------------------------------
@@ -472,7 +534,7 @@ extern "C" int32_t tmac_hip_debug_rows_comb_sums(const tmac_hip_weights* w, cons
     HIP_TRY(Ctmp.alloc(sizeof(float) * (size_t)N * w->s.Mw));
     void* cl[1] = {Ctmp.p};
     return run_tap(ws->dump, ws->dump_elems, elems, comb_host, st, "rows comb-sum",
-                   [&](int32_t* tap) { return rows_multi(&w, 1, ws, cl, TMAC_F32, N, tap, st); });
+                   [&](int32_t* tap) { return rows_multi(one_matrix(&w, cl, TMAC_F32, N, st), ws, tap); });
 }
 
 // The LUT image of the workspace in plain layouts: half tables int8 [N][K/4][8], then lut_scales, lut_biases and the
@@ -519,17 +581,6 @@ extern "C" int32_t tmac_hip_debug_gemm_image_read(const tmac_hip_workspace* ws, 
 // ---- fused entry point -----------------------------------------------------------------------------------------------------
 // Prefill through the fused entry point: one LUT build into the stream's workspace, owned by the library (stream_workspace; tmac_hip_cache_clear()
 // releases them), then the planned kernel.
-// A transformed call of N >= 2 rows (tmac_hip_qgemm_fused_xf_rows_dev) runs on a plan of plan_fused with two rules of its own: where the
-// planner answers R_GEMV_QUAD (k_gemv_quad with grid.y = N, each workgroup building its row's LUT) the call takes R_ROW_LOOP behind
-// LB_HALF_TABLES -- the transform sits in the pair build, k_gemv_quad copies the image (LUTSRC == 0) -- and a plan that needs LB_ALL (the
-// three-layout build has no XF instantiation) is refused.
-static Plan xf_rows_plan(Plan p) {
-    if (p.err) return p;
-    if (p.route == R_GEMV_QUAD) return planned(R_ROW_LOOP, LB_HALF_TABLES);
-    if (p.lut != LB_IMAGE && p.lut != LB_HALF_TABLES)
-        return refused(TMAC_HIP_E_NOMATCH, "a transformed call of several rows needs the LUT image or the half-table image alone; this plan builds every layout");
-    return p;
-}
 // XfSpec -> the argument block of the row pass and of the XF LUT builders (the only place that knows XfRowsGateArgs' spelling of a
 // transform: kind and gate side by side); r: the rows' 1 / rms, which k_xf_rows writes and the builders read
 static void fill_xf_rows_args(XfRowsGateArgs& xa, const XfSpec& s, float* r) {
@@ -537,20 +588,18 @@ static void fill_xf_rows_args(XfRowsGateArgs& xa, const XfSpec& s, float* r) {
     xa.kind = s.kind; xa.gate = s.gate; xa.eps = s.eps;
     xa.in2 = s.in2; xa.residual = s.residual; xa.gamma = s.gamma; xa.residual_out = s.residual_out; xa.r = r;
 }
-// spec: the call carries a vector transform (N >= 2, plan from xf_rows_plan): the row pass, then the planned LUT build's XF instantiation
-// kp: the matrices carry this K permutation (N >= 2, plan from xf_rows_plan, never with spec): the planned LUT build's gather instantiation
-static int32_t fused_prefill(Plan p, const tmac_hip_weights* const* wl, int nmat, const void* B_dev, tmac_dtype_t act_dtype,
-                             void* const* C_list, tmac_dtype_t out_dtype, int N, hipStream_t st, const XfSpec* spec = nullptr, const KPermData* kp = nullptr) {
-    const Shape& s0 = wl[0]->s;
+// spec: the call carries a vector transform (N >= 2, plan_call's in_build): the row pass, then the planned LUT build's XF instantiation
+// kp: the matrices carry this K permutation (N >= 2, plan_call's in_build, never with spec): the planned LUT build's gather instantiation
+static int32_t fused_prefill(Plan p, const FusedCall& c, const XfSpec* spec = nullptr, const KPermData* kp = nullptr) {
+    const Shape& s0 = c.s0();
+    const int N = c.N;
+    const hipStream_t st = c.st;
     tmac_hip_workspace* ws = nullptr;
     int32_t rc = stream_workspace(st, s0.K, N, &ws);
     if (rc) return rc;
     if (p.route == R_GEMM_PLANES && !ws->image_fits(s0.K)) {   // (see image_fits at the planners)
-        p = plan_fused(wl, C_list, nmat, N, false, false);
-        if (spec || kp) {
-            p = xf_rows_plan(p);
-            if (p.err) return fail(p.err, p.msg, p.mat);
-        }
+        p = plan_call(c, false, spec || kp, false);
+        if (p.err) return fail(p.err, p.msg, p.mat);
     }
     LutBuildReq q;
     q.K = s0.K; q.N = N; q.ags = s0.ags; q.want = p.lut; q.unified = s0.m_groups >= 1; q.xf = spec != nullptr;
@@ -562,117 +611,104 @@ static int32_t fused_prefill(Plan p, const tmac_hip_weights* const* wl, int nmat
     if (spec) {
         fill_xf_rows_args(xa, *spec, ws->xf_r);
         if (xf_needs_row_pass(*spec)) {
-            const hipError_t e = launch_xf_rows(xa, B_dev, act_dtype == TMAC_F16, xa.gamma ? ws->xf_r : nullptr, s0.K, N, st);
+            const hipError_t e = launch_xf_rows(xa, c.B, c.act_f16(), xa.gamma ? ws->xf_r : nullptr, s0.K, N, st);
             if (e != hipSuccess) return fail(TMAC_HIP_E_RUNTIME, "transform row pass launch: %s", hipGetErrorString(e));
         }
     }
-    rc = lut_build(ws, lb, B_dev, act_dtype, spec ? &xa : nullptr, kp ? kp->dev : nullptr, st);
+    rc = lut_build(ws, lb, c.B, c.act, spec ? &xa : nullptr, kp ? kp->dev : nullptr, st);
     if (rc) return rc;
     count_route(p.route);
-    if (p.route == R_GEMM_PLANES) return planes_multi(wl, nmat, ws, C_list, out_dtype, N, nullptr, st);
-    if (p.route == R_GEMM_ONEHOT) return gemm_multi(wl, nmat, ws, C_list, out_dtype, N, nullptr, st);
-    if (p.route == R_GEMV_ROWS) return rows_multi(wl, nmat, ws, C_list, out_dtype, N, nullptr, st);
-    for (int i = 0; i < nmat && rc == TMAC_HIP_OK; ++i) rc = tmac_hip_qgemm_dev(wl[i], ws, C_list[i], out_dtype, N, st);
+    if (p.route == R_GEMM_PLANES) return planes_multi(c, ws, nullptr);
+    if (p.route == R_GEMM_ONEHOT) return gemm_multi(c, ws, nullptr);
+    if (p.route == R_GEMV_ROWS) return rows_multi(c, ws, nullptr);
+    for (int i = 0; i < c.nmat && rc == TMAC_HIP_OK; ++i) rc = tmac_hip_qgemm_dev(c.wl[i], ws, c.C[i], c.out, N, st);
     return rc;
 }
-// the alignment contract of the activations and the outputs (include/tmac_hip.h, "Alignment")
-static int32_t act_align_check(const void* B_dev) {
-    if (misaligned(B_dev, ACT_ALIGN)) return fail(TMAC_HIP_E_ARG, "B_dev must be %zu-byte aligned (the LUT build reads 16 bytes at a time)", ACT_ALIGN);
-    return TMAC_HIP_OK;
-}
-static int32_t out_align_check(void* const* C_list, int nmat, tmac_dtype_t out_dtype) {
-    for (int i = 0; i < nmat; ++i)
-        if (misaligned(C_list[i], out_align(out_dtype)))
-            return fail(TMAC_HIP_E_ARG, "C_dev[%d] must be %zu-byte aligned (four outputs are stored at a time)", i, out_align(out_dtype));
-    return TMAC_HIP_OK;
+// The one site that launches k_gemv_quad with an in-kernel LUT build, for the three argument blocks (FusedArgs, FusedXfArgs,
+// FusedPermArgs): counts the route, fills what the call decides, lets the door add its own fields (extra), decides the launch
+// configuration -- forced (tmac_hip_debug_quad_config), which is strict: the block must have that instantiation; else, for one row and no
+// tap, the tuned one; else the heuristic -- launches, and words a failure the door's way.
+template <class Args, class Extra>
+static int32_t launch_quad(const FusedCall& c, Extra extra, const char* nomatch, const char* what) {
+    count_route(R_GEMV_QUAD);
+    Args fa;
+    const int nb = fill_fused_args(fa, c);
+    extra(fa);
+    int ft = g_knobs.force_ft, wpq = g_knobs.force_wpq;
+    const bool strict = ft || wpq;
+    if (!strict && !fa.dump && c.N == 1) tuned_config(fa, nb, ft, wpq);
+    return fused_gemv_rc(launch_gemv_quad(fa, c.N, true, ft, wpq, strict, c.st), nomatch, what);
 }
 // A fused call on matrices that all carry the same K permutation (fused_impl has checked that, the arguments and the alignment).  Behind
 // the calling thread's deferred queue, stand-alone, like a call of several rows.  N = 1: k_gemv_quad's gather instantiations (the covered
 // configurations and the fall-back of a transformed call).  N >= 2: routed as tmac_hip_qgemm_fused_xf_rows_dev routes a transformed call
-// (xf_rows_plan), the planned LUT build gathering.
-static int32_t fused_perm(const tmac_hip_weights* const* wl, int nmat, const void* B_dev, tmac_dtype_t act_dtype, void* const* C_list,
-                          tmac_dtype_t out_dtype, int N, hipStream_t st) {
-    const KPermData* kp = perm_of(wl[0]);
-    for (int i = 0; i < nmat; ++i) {
-        const tmac_hip_weights* w = wl[i];
-        if (!C_list[i]) return fail(TMAC_HIP_E_ARG, "null matrix or output");
-        if (g_knobs.variant == V_REF_LAYOUT || g_knobs.variant == V_QUAD_MQSAD || layout_of(w->s) != L_QUAD || !w->tiled_ok || w->fa || !gemv_quad_supported(w->s) ||
-            w->s.m_groups >= 1)
+// (plan_call's in_build), the planned LUT build gathering.
+static int32_t fused_perm(const FusedCall& c) {
+    const KPermData* kp = perm_of(c.wl[0]);
+    for (int i = 0; i < c.nmat; ++i) {
+        const tmac_hip_weights* w = c.wl[i];
+        if (!c.C[i]) return fail(TMAC_HIP_E_ARG, "null matrix or output");
+        if (quad_mfma_misses(w) || w->s.m_groups >= 1)
             return fail(TMAC_HIP_E_NOMATCH, "matrix %d: act-order handles run on k_gemv_quad's MFMA form and the prefill kernels behind it (QUAD layout, per-group scales)", i);
-        if (!same_lut(w, wl[0]) || !same_quant(w, wl[0])) return fail(TMAC_HIP_E_ARG, "matrices fused in one launch must share K, bits and quantisation config");
+        if (!same_lut(w, c.wl[0]) || !same_quant(w, c.wl[0])) return fail(TMAC_HIP_E_ARG, "%s", ONE_LUT_MSG);
     }
-    Plan p = plan_fused(wl, C_list, nmat, N, false);
-    if (N >= 2) p = xf_rows_plan(p);
+    const Plan p = plan_call(c, false, true);
     if (p.err) return fail(p.err, p.msg, p.mat);
-    if (N == 1 && p.route != R_GEMV_QUAD) return fail(TMAC_HIP_E_NOMATCH, "act-order handles of one row run on k_gemv_quad only");
+    if (c.N == 1 && p.route != R_GEMV_QUAD) return fail(TMAC_HIP_E_NOMATCH, "act-order handles of one row run on k_gemv_quad only");
     const int32_t brc = defer_barrier();
     if (brc) return brc;
-    if (N >= 2) return fused_prefill(p, wl, nmat, B_dev, act_dtype, C_list, out_dtype, N, st, nullptr, kp);
-    count_route(p.route);
-    FusedPermArgs fa;
-    const int nb = fill_fused_args(fa, wl, C_list, nmat, out_dtype, nullptr);
-    fa.B = B_dev; fa.act_f16 = act_dtype == TMAC_F16;
-    fa.perm = kp->dev;
-    // the launch configuration: forced (tmac_hip_debug_quad_config) -- it must have a gather instantiation -- else tuned, else the heuristic
-    int ft = g_knobs.force_ft, wpq = g_knobs.force_wpq;
-    const bool strict = ft || wpq;
-    if (!strict) tuned_config(fa, nb, ft, wpq);
-    const hipError_t e = launch_gemv_quad_perm(fa, ft, wpq, strict, st);
-    if (e == hipErrorInvalidValue) return fail(TMAC_HIP_E_NOMATCH, "no gathering GEMV kernel for this configuration (gather instantiations: (512,1), (512,2), (768,3), (1024,4))");
-    if (e != hipSuccess) return fail(TMAC_HIP_E_RUNTIME, "gathering gemv launch: %s", hipGetErrorString(e));
-    return TMAC_HIP_OK;
+    if (c.N >= 2) return fused_prefill(p, c, nullptr, kp);
+    return launch_quad<FusedPermArgs>(c, [&](FusedPermArgs& fa) { fa.perm = kp->dev; },
+                                      "no gathering GEMV kernel for this configuration (gather instantiations: (512,1), (512,2), (768,3), (1024,4))", "gathering gemv");
 }
-int32_t tmac_host::fused_impl(const tmac_hip_weights* const* wl, int nmat, const void* B_dev, tmac_dtype_t act_dtype,
-                          void* const* C_list, tmac_dtype_t out_dtype, int N, int32_t* dump, float* lut_tap, hipStream_t st) {
+int32_t tmac_host::fused_impl(const FusedCall& c, int32_t* dump, float* lut_tap) {
     bind_thread_device();
-    if (!wl || !C_list || !B_dev || nmat < 1 || nmat > 4 || N < 1) {
-        if (chain_recording()) chain_clear_xform();      // a rejected call must not leave its transform pending for the next recorded call
-        return fail(TMAC_HIP_E_ARG, "bad fused arguments (1..4 matrices)");
-    }
-    // the alignment contract, ahead of the recorder, the deferred queue and the planner alike: a refused call is neither recorded nor
-    // queued, launches nothing and leaves the queue as it is
-    int32_t arc = out_align_check(C_list, nmat, out_dtype);
-    if (arc == TMAC_HIP_OK) arc = act_align_check(B_dev);
+    // the argument and alignment checks, ahead of the recorder, the deferred queue and the planner alike: a refused call is neither
+    // recorded nor queued, launches nothing and leaves the queue as it is
+    int32_t arc = args_check(c);
+    if (arc == TMAC_HIP_OK) arc = out_align_check(c);
+    if (arc == TMAC_HIP_OK) arc = act_align_check(c.B);
     if (arc) {
-        if (chain_recording()) chain_clear_xform();
+        if (chain_recording()) chain_clear_xform();      // a rejected call must not leave its transform pending for the next recorded call
         return arc;
     }
     const bool tap = dump || lut_tap;
-    const int ps = perm_state(wl, nmat);
+    const int ps = perm_state(c);
     if (ps != 0) {        // act-order handles: never recorded, never queued, never tapped
         if (chain_recording()) chain_clear_xform();
         if (ps < 0) return fail(TMAC_HIP_E_ARG, "matrices fused in one launch must share the K permutation");
-        if (tap) return refuse_perm(wl, nmat, "a parity tap");
-        if (chain_recording()) return refuse_perm(wl, nmat, "a recorded call (tmac_hip_chain_begin ... _end)");
-        return fused_perm(wl, nmat, B_dev, act_dtype, C_list, out_dtype, N, st);
+        if (tap) return refuse_perm(c, "a parity tap");
+        if (chain_recording()) return refuse_perm(c, "a recorded call (tmac_hip_chain_begin ... _end)");
+        return fused_perm(c);
     }
-    if (chain_recording() && !tap) return chain_record(wl, nmat, B_dev, act_dtype, C_list, out_dtype, N);
+    if (chain_recording() && !tap) return chain_record(c);
     if (!tap) {           // deferred launches: queued until tmac_hip_flush (or a call that depends on a queued one)
         int32_t drc;
-        if (defer_if_on(wl, nmat, B_dev, act_dtype, C_list, out_dtype, N, st, &drc)) return drc;
+        if (defer_if_on(c, &drc)) return drc;
     } else {              // a tap is never queued: it goes behind the queue (B_dev may be a queued output)
         const int32_t brc = defer_barrier();
         if (brc) return brc;
     }
-    const Plan p = plan_fused(wl, C_list, nmat, N, tap);
+    const Plan p = plan_call(c, tap);
     if (p.err) return fail(p.err, p.msg, p.mat);
-    if (p.route != R_GEMV_QUAD && p.route != R_GEMV_FUSED) return fused_prefill(p, wl, nmat, B_dev, act_dtype, C_list, out_dtype, N, st);
+    if (p.route != R_GEMV_QUAD && p.route != R_GEMV_FUSED) return fused_prefill(p, c);
+    auto taps = [&](FusedArgs& fa) {
+        fa.dump = dump;
+        fa.stamps = g_knobs.stamps;
+        if (g_knobs.stamps && !fa.dump) fa.dump = g_knobs.stamp_dump;   // the stamps live in the tap (DUMP) instantiation of the kernel
+        fa.lut_tap = lut_tap;
+    };
+    if (p.route == R_GEMV_QUAD) return launch_quad<FusedArgs>(c, taps, "no fused GEMV kernel for this configuration", "fused gemv");
     count_route(p.route);
     FusedArgs fa;
-    const int nb = fill_fused_args(fa, wl, C_list, nmat, out_dtype, dump);
-    fa.B = B_dev; fa.act_f16 = act_dtype == TMAC_F16;
-    fa.stamps = g_knobs.stamps;
-    if (g_knobs.stamps && !fa.dump) fa.dump = g_knobs.stamp_dump;   // the stamps live in the tap (DUMP) instantiation of the kernel
-    fa.lut_tap = lut_tap;
-    if (p.route == R_GEMV_FUSED) return fused_gemv_rc(launch_gemv_fused(fa, N, true, st));
-    int ft = g_knobs.force_ft, wpq = g_knobs.force_wpq;
-    if (!ft && !wpq && !fa.dump && N == 1) tuned_config(fa, nb, ft, wpq);
-    return fused_gemv_rc(launch_gemv_quad(fa, N, true, ft, wpq, st));
+    fill_fused_args(fa, c);
+    taps(fa);
+    return fused_gemv_rc(launch_gemv_fused(fa, c.N, true, c.st));
 }
 extern "C" int32_t tmac_hip_qgemm_fused_dev(const tmac_hip_weights* const* weights, int nmat, const void* B_dev,
                                             tmac_dtype_t act_dtype, void* const* C_dev, tmac_dtype_t out_dtype, int N,
                                             void* stream) {
-    return fused_impl(weights, nmat, B_dev, act_dtype, C_dev, out_dtype, N, nullptr, nullptr, (hipStream_t)stream);
+    return fused_impl(FusedCall{weights, nmat, B_dev, act_dtype, C_dev, out_dtype, N, (hipStream_t)stream}, nullptr, nullptr);
 }
 
 // ---- fused entry point with a vector transform (N = 1) -----------------------------------------------------------------------
@@ -680,11 +716,10 @@ extern "C" int32_t tmac_hip_qgemm_fused_dev(const tmac_hip_weights* const* weigh
 // queued (it goes behind the deferred queue like every non-hot entry point).
 // The field rules are tmac_xform.h's (xf_resolve, xf_overlap_check); all of them come before anything about matrices, plans or routes.
 // residual_out against what an N-row call on these matrices reads and writes
-static int32_t xf_call_overlap_check(const XfSpec& spec, XfSite site, const tmac_hip_weights* const* wl, int nmat, const void* B_dev, tmac_dtype_t act_dtype,
-                                     const tmac_hip_xform* xf, void* const* C_list, tmac_dtype_t out_dtype, int N) {
+static int32_t xf_call_overlap_check(const XfSpec& spec, XfSite site, const FusedCall& c, const tmac_hip_xform* xf) {
     XfOut outs[4];
-    for (int i = 0; i < nmat; ++i) outs[i] = XfOut{C_list[i], (size_t)N * wl[i]->s.Mw * (out_dtype == TMAC_F16 ? 2 : 4)};
-    return xf_overlap_check(spec, site, B_dev, act_dtype == TMAC_F16 ? 2 : 4, xf->in2, wl[0]->s.K, N, outs, nmat);
+    for (int i = 0; i < c.nmat; ++i) outs[i] = XfOut{c.C[i], c.out_bytes(i)};
+    return xf_overlap_check(spec, site, c.B, c.act_f16() ? 2 : 4, xf->in2, c.s0().K, c.N, outs, c.nmat);
 }
 // XfSpec -> the transform fields of k_gemv_quad's XF block (the only place that knows FusedXfArgs' spelling: the gate in bits 8.. of xf_kind)
 static void fill_fused_xf_args(FusedXfArgs& fa, const XfSpec& s) {
@@ -692,45 +727,31 @@ static void fill_fused_xf_args(FusedXfArgs& fa, const XfSpec& s) {
 }
 extern "C" int32_t tmac_hip_qgemm_fused_xf_dev(const tmac_hip_weights* const* wl, int nmat, const void* B_dev, tmac_dtype_t act_dtype,
                                                const tmac_hip_xform* xf, void* const* C_list, tmac_dtype_t out_dtype, void* stream) {
-    hipStream_t st = (hipStream_t)stream;
+    const FusedCall c{wl, nmat, B_dev, act_dtype, C_list, out_dtype, 1, (hipStream_t)stream};
     const int32_t drc = ensure_device();
     if (drc) return drc;
-    if (!xf || xf->kind == TMAC_XF_NONE) return fused_impl(wl, nmat, B_dev, act_dtype, C_list, out_dtype, 1, nullptr, nullptr, st);
+    if (!xf || xf->kind == TMAC_XF_NONE) return fused_impl(c, nullptr, nullptr);
     if (chain_recording()) {       // one call site for both modes: the chain's own rules apply (CARRY allowed, fp16 in2)
         int32_t rc = tmac_hip_chain_xform(xf);
-        if (rc == TMAC_HIP_OK) rc = fused_impl(wl, nmat, B_dev, act_dtype, C_list, out_dtype, 1, nullptr, nullptr, st);
+        if (rc == TMAC_HIP_OK) rc = fused_impl(c, nullptr, nullptr);
         if (rc != TMAC_HIP_OK && chain_recording()) chain_clear_xform();      // a rejected call leaves no pending transform
         return rc;
     }
     XfSpec spec;
     int32_t rc = xf_resolve(xf, XF_SITE_N1, &spec);
-    if (rc) return rc;
-    if (!wl || !C_list || !B_dev || nmat < 1 || nmat > 4) return fail(TMAC_HIP_E_ARG, "bad fused arguments (1..4 matrices)");
-    if ((rc = refuse_perm(wl, nmat, "a vector transform")) != TMAC_HIP_OK) return rc;
-    if ((rc = act_align_check(B_dev)) != TMAC_HIP_OK || (rc = out_align_check(C_list, nmat, out_dtype)) != TMAC_HIP_OK) return rc;
-    const Plan p = plan_fused(wl, C_list, nmat, 1, false);
+    if (rc || (rc = args_check(c)) != TMAC_HIP_OK || (rc = refuse_perm(c, "a vector transform")) != TMAC_HIP_OK) return rc;
+    if ((rc = act_align_check(c.B)) != TMAC_HIP_OK || (rc = out_align_check(c)) != TMAC_HIP_OK) return rc;
+    const Plan p = plan_call(c, false, true);
     if (p.err) return fail(p.err, p.msg, p.mat);
-    const Shape& s0 = wl[0]->s;
-    if (p.route != R_GEMV_QUAD || g_knobs.variant == V_QUAD_MQSAD || s0.K > QUAD_XF_MAX_K)
+    if (p.route != R_GEMV_QUAD || (quad_mfma_misses(wl[0]) & QM_MQSAD_VARIANT) || c.s0().K > QUAD_XF_MAX_K)
         return fail(TMAC_HIP_E_NOMATCH, "a transformed call runs on k_gemv_quad with the MFMA accumulate only (QUAD layout, K <= %d)", QUAD_XF_MAX_K);
     // (every workgroup reads the whole of the inputs while ONE workgroup writes each pair of residual_out: no order between the two)
-    if ((rc = xf_call_overlap_check(spec, XF_SITE_N1, wl, nmat, B_dev, act_dtype, xf, C_list, out_dtype, 1)) != TMAC_HIP_OK) return rc;
+    if ((rc = xf_call_overlap_check(spec, XF_SITE_N1, c, xf)) != TMAC_HIP_OK) return rc;
     bind_thread_device();
     const int32_t brc = defer_barrier();       // never queued: behind the calling thread's queue (B_dev may be a queued output)
     if (brc) return brc;
-    count_route(p.route);
-    FusedXfArgs fa;
-    const int nb = fill_fused_args(fa, wl, C_list, nmat, out_dtype, nullptr);
-    fa.B = B_dev; fa.act_f16 = act_dtype == TMAC_F16;
-    fill_fused_xf_args(fa, spec);
-    // the launch configuration: forced (tmac_hip_debug_quad_config) -- it must have an XF instantiation -- else tuned, else the heuristic
-    int ft = g_knobs.force_ft, wpq = g_knobs.force_wpq;
-    const bool strict = ft || wpq;
-    if (!strict) tuned_config(fa, nb, ft, wpq);
-    const hipError_t e = launch_gemv_quad_xf(fa, ft, wpq, strict, st);
-    if (e == hipErrorInvalidValue) return fail(TMAC_HIP_E_NOMATCH, "no transformed GEMV kernel for this configuration (XF instantiations: (512,1), (512,2), (768,3), (1024,4))");
-    if (e != hipSuccess) return fail(TMAC_HIP_E_RUNTIME, "transformed gemv launch: %s", hipGetErrorString(e));
-    return TMAC_HIP_OK;
+    return launch_quad<FusedXfArgs>(c, [&](FusedXfArgs& fa) { fill_fused_xf_args(fa, spec); },
+                                    "no transformed GEMV kernel for this configuration (XF instantiations: (512,1), (512,2), (768,3), (1024,4))", "transformed gemv");
 }
 
 // ---- fused entry point with a vector transform, N >= 1 rows ------------------------------------------------------------------
@@ -739,68 +760,59 @@ extern "C" int32_t tmac_hip_qgemm_fused_xf_dev(const tmac_hip_weights* const* wl
 // queued.
 extern "C" int32_t tmac_hip_qgemm_fused_xf_rows_dev(const tmac_hip_weights* const* wl, int nmat, const void* B_dev, tmac_dtype_t act_dtype,
                                                     const tmac_hip_xform* xf, void* const* C_list, tmac_dtype_t out_dtype, int N, void* stream) {
-    hipStream_t st = (hipStream_t)stream;
+    const FusedCall c{wl, nmat, B_dev, act_dtype, C_list, out_dtype, N, (hipStream_t)stream};
     const int32_t drc = ensure_device();
     if (drc) return drc;
     if (N == 1) return tmac_hip_qgemm_fused_xf_dev(wl, nmat, B_dev, act_dtype, xf, C_list, out_dtype, stream);
-    if (!xf || xf->kind == TMAC_XF_NONE) return fused_impl(wl, nmat, B_dev, act_dtype, C_list, out_dtype, N, nullptr, nullptr, st);
+    if (!xf || xf->kind == TMAC_XF_NONE) return fused_impl(c, nullptr, nullptr);
     if (chain_recording()) {
         chain_clear_xform();           // (a transform declared for the next recorded call was meant for this one)
         return fail(TMAC_HIP_E_NOMATCH, "a transformed call of N=%d rows cannot be recorded: a chain takes one activation row", N);
     }
-    if (!wl || !C_list || !B_dev || nmat < 1 || nmat > 4 || N < 1) return fail(TMAC_HIP_E_ARG, "bad fused arguments (1..4 matrices)");
-    for (int i = 0; i < nmat; ++i)
-        if (!wl[i] || !C_list[i]) return fail(TMAC_HIP_E_ARG, "null matrix or output");
-    int32_t rc = refuse_perm(wl, nmat, "a vector transform");
-    if (rc) return rc;
-    rc = out_align_check(C_list, nmat, out_dtype);
-    if (rc) return rc;
-    const Shape& s0 = wl[0]->s;
+    int32_t rc = args_check(c);
+    if (rc || (rc = nulls_check(c)) != TMAC_HIP_OK || (rc = refuse_perm(c, "a vector transform")) != TMAC_HIP_OK || (rc = out_align_check(c)) != TMAC_HIP_OK) return rc;
+    const Shape& s0 = c.s0();
     XfSpec spec;
-    if ((rc = xf_resolve(xf, XF_SITE_ROWS, &spec)) != TMAC_HIP_OK || (rc = act_align_check(B_dev)) != TMAC_HIP_OK) return rc;
+    if ((rc = xf_resolve(xf, XF_SITE_ROWS, &spec)) != TMAC_HIP_OK || (rc = act_align_check(c.B)) != TMAC_HIP_OK) return rc;
     // (the builders read in, in2 and residual again after the row pass has written residual_out)
-    if ((rc = xf_call_overlap_check(spec, XF_SITE_ROWS, wl, nmat, B_dev, act_dtype, xf, C_list, out_dtype, N)) != TMAC_HIP_OK) return rc;
-    for (int i = 0; i < nmat; ++i)
-        if (!same_lut(wl[i], wl[0]) || !same_quant(wl[i], wl[0]))
-            return fail(TMAC_HIP_E_ARG, "matrices fused in one launch must share K, bits and quantisation config");
-    // the scope: what the N = 1 form accepts, within the pair builds' reach
-    if (g_knobs.variant == V_REF_LAYOUT) return fail(TMAC_HIP_E_NOMATCH, "a transformed call does not run on the reference layout");
+    if ((rc = xf_call_overlap_check(spec, XF_SITE_ROWS, c, xf)) != TMAC_HIP_OK || (rc = one_lut_check(c)) != TMAC_HIP_OK) return rc;
+    // the scope: what the N = 1 form accepts (but for the accumulate, which the kernels behind the pair build choose), within the pair builds' reach
+    if (quad_mfma_misses(wl[0]) & QM_REF_VARIANT) return fail(TMAC_HIP_E_NOMATCH, "a transformed call does not run on the reference layout");
     for (int i = 0; i < nmat; ++i) {
-        const tmac_hip_weights* w = wl[i];
-        if (layout_of(w->s) != L_QUAD || !w->tiled_ok || !gemv_quad_supported(w->s))
+        const unsigned miss = quad_mfma_misses(wl[i]);
+        if (miss & (QM_LAYOUT | QM_SHAPE))
             return fail(TMAC_HIP_E_NOMATCH, "matrix %d: a transformed call takes QUAD-layout weights of 1 to 4 bits with act groups of 64 or unified scales", i);
-        if (w->fa) return fail(TMAC_HIP_E_NOMATCH, "fast-aggregation weights do not take a transformed call");
+        if (miss & QM_FAST_AGG) return fail(TMAC_HIP_E_NOMATCH, "fast-aggregation weights do not take a transformed call");
     }
     if (s0.m_groups >= 1 && s0.K > PAIRS_ROW_MAX_K)
         return fail(TMAC_HIP_E_NOMATCH, "unified scales: K=%d is beyond the row-wise pair build (K <= %d)", s0.K, PAIRS_ROW_MAX_K);
-    const Plan p = xf_rows_plan(plan_fused(wl, C_list, nmat, N, false));
+    const Plan p = plan_call(c, false, true);
     if (p.err) return fail(p.err, p.msg, p.mat);
     bind_thread_device();
     const int32_t brc = defer_barrier();       // never queued: behind the calling thread's queue (B_dev may be a queued output)
     if (brc) return brc;
-    return fused_prefill(p, wl, nmat, B_dev, act_dtype, C_list, out_dtype, N, st, &spec);
+    return fused_prefill(p, c, &spec);
 }
 
-// What a transformed call of N >= 2 rows on these matrices would run, by the rules of the call itself (host only: plans, launches nothing).
-// route: 0 k_gemm_planes, 1 k_gemm_onehot, 3 k_gemv_rows, 7 the row loop (enum Route); lut: 1 the LUT image, 2 the half-table image.
-extern "C" int32_t tmac_hip_debug_xf_rows_plan(const tmac_hip_weights* const* wl, int nmat, void* const* C_list, int N, int32_t* route, int32_t* lut) {
-    if (!wl || !C_list || nmat < 1 || nmat > 4 || N < 2) return fail(TMAC_HIP_E_ARG, "bad plan arguments (1..4 matrices, N >= 2)");
-    const Plan p = xf_rows_plan(plan_fused(wl, C_list, nmat, N, false));
+// the two debug twins of plan_call: the plan's route and LUT form, or its refusal
+static int32_t report_plan(const Plan& p, int32_t* route, int32_t* lut) {
     if (p.err) return fail(p.err, p.msg, p.mat);
     if (route) *route = (int32_t)p.route;
     if (lut) *lut = (int32_t)p.lut;
     return TMAC_HIP_OK;
+}
+// What a transformed call of N >= 2 rows on these matrices would run, by the rules of the call itself (host only: plans, launches nothing).
+// route: 0 k_gemm_planes, 1 k_gemm_onehot, 3 k_gemv_rows, 7 the row loop (enum Route); lut: 1 the LUT image, 2 the half-table image.
+extern "C" int32_t tmac_hip_debug_xf_rows_plan(const tmac_hip_weights* const* wl, int nmat, void* const* C_list, int N, int32_t* route, int32_t* lut) {
+    if (!wl || !C_list || nmat < 1 || nmat > 4 || N < 2) return fail(TMAC_HIP_E_ARG, "bad plan arguments (1..4 matrices, N >= 2)");
+    return report_plan(plan_call(FusedCall{wl, nmat, nullptr, TMAC_F32, C_list, TMAC_F32, N, nullptr}, false, true), route, lut);
 }
 
 // What an untransformed fused call on these matrices would run: plan_fused's answer as the call gets it (host only: plans, launches nothing).
 // route: enum Route; lut: enum LutBuild.
 extern "C" int32_t tmac_hip_debug_fused_plan(const tmac_hip_weights* const* wl, int nmat, void* const* C_list, int N, int32_t* route, int32_t* lut) {
     if (!wl || !C_list || nmat < 1 || nmat > 4 || N < 1) return fail(TMAC_HIP_E_ARG, "bad plan arguments (1..4 matrices, N >= 1)");
-    const Plan p = plan_fused(wl, C_list, nmat, N, false);
-    if (p.err) return fail(p.err, p.msg, p.mat);
-    if (route) *route = (int32_t)p.route;
-    if (lut) *lut = (int32_t)p.lut;
-    return TMAC_HIP_OK;
+    return report_plan(plan_call(FusedCall{wl, nmat, nullptr, TMAC_F32, C_list, TMAC_F32, N, nullptr}, false), route, lut);
 }
 
 extern "C" int32_t tmac_hip_debug_route_stats(uint64_t counts[8]) {
@@ -853,7 +865,7 @@ extern "C" int32_t tmac_hip_qgemm_fused_partial_sums(const tmac_hip_weights* w, 
     int32_t* tap = nullptr;      // scratch of this call, unlike the workspace's tap of the two entry points above
     size_t cap = 0;
     int32_t rc = run_tap(tap, cap, ps_elems(w->s, N), PS_host, st, "fused tap",
-                         [&](int32_t* t) { return fused_impl(&w, 1, B_dev, act_dtype, cl, TMAC_F32, N, t, ltap.as<float>(), st); });
+                         [&](int32_t* t) { return fused_impl(FusedCall{&w, 1, B_dev, act_dtype, cl, TMAC_F32, N, st}, t, ltap.as<float>()); });
     if (tap) (void)hipFree(tap);
     if (rc) return rc;
     if (C_host) HIP_TRY(hipMemcpy(C_host, Ctmp.p, sizeof(float) * (size_t)N * w->s.Mw, hipMemcpyDeviceToHost));

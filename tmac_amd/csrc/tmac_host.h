@@ -11,9 +11,10 @@
 //   tmac_xform.cpp       the field rules of tmac_hip_xform: one resolver for every transform site (tmac_xform.h: no HIP, builds with plain g++)
 //   tmac_launch_plan.cpp launch planning of k_gemv_quad / k_gemv_rows and what the fused kernels support: pure functions that fill a plan or refuse
 //                        (tmac_launch_plan.h: also the instantiation policy of every kernel family as constexpr predicates; no HIP, plain g++)
-//   tmac_launch.cpp      launch_gemv_quad(_xf) / launch_gemv_rows / launch_decode_chain / launch_gemv_stream: plan, pick the translation unit of
-//                        the call's width or form; the unit selects the instantiation (tmac_select.h) and launches
-//   tmac_dispatch.cpp    qgemm_lut dispatch (a call is planned -- enum Route -- then launched), the fused entry point, parity taps
+//   tmac_launch.cpp      launch_gemv_quad (one overload per argument block) / launch_gemv_rows / launch_decode_chain / launch_gemv_stream: plan,
+//                        pick the translation unit of the call's width or form; the unit selects the instantiation (tmac_select.h) and launches
+//   tmac_dispatch.cpp    qgemm_lut dispatch (a call is planned -- enum Route -- then launched); the fused entry point: its doors, the named
+//                        checks they share, plan_call, the one k_gemv_quad launch site (a fused call is one value: FusedCall, below); parity taps
 //   tmac_tuner.cpp       launch-configuration tuner of the decode kernel
 //   tmac_chain_host.cpp  recording and building the persistent decode chain (chain_build and its stages, the stream schedule)
 //   tmac_chain_launch.cpp  launching a built chain, IPC export / connect, status, info, taps, stamps
@@ -183,11 +184,31 @@ void release_fused_workspaces();    // tmac_hip_cache_clear; caller holds g_mu
 // ---- dispatch (tmac_dispatch.cpp) -----------------------------------------------------------------
 int32_t qgemm_impl(const tmac_hip_weights* w, const tmac_hip_workspace* ws, void* C_dev, tmac_dtype_t out_dtype, int N, int32_t* dump,
                    hipStream_t st);
-int32_t fused_impl(const tmac_hip_weights* const* wl, int nmat, const void* B_dev, tmac_dtype_t act_dtype, void* const* C_list,
-                   tmac_dtype_t out_dtype, int N, int32_t* dump, float* lut_tap, hipStream_t st);
+// A fused call as one value: what tmac_hip_qgemm_fused_dev was handed.  A view: it owns nothing and allocates nothing; the lists live
+// with the caller (or in a ChainRecOp, tmac_chain_host.h).  The split entry point wraps its matrix in a one-matrix call (B null) for the
+// launch helpers it shares with the fused one.
+struct FusedCall {
+    const tmac_hip_weights* const* wl;
+    int nmat;
+    const void* B;
+    tmac_dtype_t act;
+    void* const* C;
+    tmac_dtype_t out;
+    int N;
+    hipStream_t st;
+    const Shape& s0() const { return wl[0]->s; }
+    bool act_f16() const { return act == TMAC_F16; }
+    bool out_f16() const { return out == TMAC_F16; }
+    size_t out_bytes(int i) const { return (size_t)N * wl[i]->s.Mw * (out_f16() ? 2 : 4); }
+};
+int32_t fused_impl(const FusedCall& c, int32_t* dump, float* lut_tap);
 // what a non-deferred, tap-less fused call is refused for (the per-matrix null checks and plan_fused): TMAC_HIP_OK, or fail(code, message).
-// Pure: reads its arguments and g_knobs.
-int32_t fused_check(const tmac_hip_weights* const* wl, int nmat, void* const* C_list, int N);
+// Pure: reads its argument and g_knobs.
+int32_t fused_check(const FusedCall& c);
+int32_t nulls_check(const FusedCall& c);      // a matrix or an output of the call is null (one of the doors' named checks)
+// The fields of k_gemv_quad's / k_gemv_fused's argument block that the call decides (the door adds its own: taps, transform, permutation);
+// returns the launch's row blocks (row quads in the QUAD layout) over all matrices.
+int fill_fused_args(FusedArgs& fa, const FusedCall& c);
 // Alignment of caller-owned device pointers: ACT_ALIGN, XFORM_ALIGN and misaligned are tmac_xform.h's; the GEMMs store four outputs at a
 // time (fp32: 16 bytes, fp16: 8).
 inline size_t out_align(tmac_dtype_t d) { return d == TMAC_F16 ? 8 : 16; }
@@ -198,11 +219,9 @@ void tuned_config(const FusedArgs& fa, int total_q, int& ft, int& wpq);   // lea
 // ---- decode chain (tmac_chain_host.cpp) and deferred queue (tmac_defer.cpp) -----------------------------------------------------------
 bool chain_recording();            // is the calling thread between tmac_hip_chain_begin and tmac_hip_chain_end?
 void chain_clear_xform();          // drops a transform declared for the next recorded call (the call was rejected before it could be recorded)
-int32_t chain_record(const tmac_hip_weights* const* wl, int nmat, const void* B_dev, tmac_dtype_t act_dtype, void* const* C_list,
-                     tmac_dtype_t out_dtype, int N);
+int32_t chain_record(const FusedCall& c);
 // deferred launches (tmac_hip_defer): true (and *rc set) when the call was queued instead of launched
-bool defer_if_on(const tmac_hip_weights* const* wl, int nmat, const void* B_dev, tmac_dtype_t act_dtype, void* const* C_list, tmac_dtype_t out_dtype,
-                 int N, hipStream_t st, int32_t* rc);
+bool defer_if_on(const FusedCall& c, int32_t* rc);
 // Orders an entry point behind the calling thread's queue: flushes it when it is not empty and returns the flush's status (one
 // vector::empty() otherwise).  First statement of every entry point that launches work or touches device memory for the caller; when it
 // fails, nothing of the entry point is launched.  defer_flush takes the queue before it launches: the entry points it calls see none.

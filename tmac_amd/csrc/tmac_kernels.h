@@ -204,16 +204,16 @@ hipError_t launch_gemm_planes(const Gemm2Args& a, hipStream_t st);
 size_t qlut_lds_u4(int K);   // uint4 per activation row of the LDS-image LUT
 hipError_t launch_gemv_fused(const FusedArgs& a, int N, bool build_lut, hipStream_t st);
 // quad kernel (tmac_quad.hip, one translation unit per width and scale dtype; the entry points: tmac_launch.cpp): a.m[i].nb_end =
-// cumulative ROW QUAD counts; force_ft/force_wpq 0 = heuristic
-hipError_t launch_gemv_quad(const FusedArgs& a, int N, bool build_lut, int force_ft, int force_wpq, hipStream_t st);
-// The same kernel with a vector transform in front of its table build (N = 1, LUT built in-kernel, MFMA accumulate).  The XF
-// instantiations cover a subset of the launch configurations (quad_xf_covered, tmac_launch_plan.h).  ft / wpq: 0 = heuristic; strict: the
-// configuration was forced by the caller and must be covered as it is (hipErrorInvalidValue otherwise) -- else it falls back to the
-// nearest covered one.
-hipError_t launch_gemv_quad_xf(const FusedXfArgs& a, int ft, int wpq, bool strict, hipStream_t st);
+// cumulative ROW QUAD counts; ft / wpq: 0 = heuristic.  One signature for the three argument blocks.  strict: the configuration was forced
+// by the caller and must be covered as it is (hipErrorInvalidValue otherwise) -- else it falls back to the nearest covered one; the plain
+// block ignores it: every configuration exists for it.
+hipError_t launch_gemv_quad(const FusedArgs& a, int N, bool build_lut, int ft, int wpq, bool strict, hipStream_t st);
+// The same kernel with a vector transform in front of its table build (N = 1, LUT built in-kernel, MFMA accumulate: anything else is
+// hipErrorInvalidValue).  The XF instantiations cover a subset of the launch configurations (quad_xf_covered, tmac_launch_plan.h).
+hipError_t launch_gemv_quad(const FusedXfArgs& a, int N, bool build_lut, int ft, int wpq, bool strict, hipStream_t st);
 // ... and with the gather of an act-order permutation in its activation loads (N = 1, LUT built in-kernel, MFMA accumulate, per-group
-// scales): the same covered configurations, the same fall-back, the same meaning of strict.
-hipError_t launch_gemv_quad_perm(const FusedPermArgs& a, int ft, int wpq, bool strict, hipStream_t st);
+// scales): the same covered configurations, the same fall-back.
+hipError_t launch_gemv_quad(const FusedPermArgs& a, int N, bool build_lut, int ft, int wpq, bool strict, hipStream_t st);
 // the launcher of one translation unit of tmac_quad.hip (defined and instantiated there for its BITS, SCF16 and both argument blocks): the
 // instantiation the plan names; a: precomputed (fused_precompute).  (Also for FusedPermArgs.)
 template <int BITS, bool SCF16, class Args>

@@ -14,14 +14,18 @@ static hipError_t quad_unit(const Args& a, const QuadPlan& p, int N, hipStream_t
     }); });
 }
 
-// a.m[i].nb_end must hold cumulative QUAD counts.  force_ft / force_wpq: 0 = heuristic (A/B knobs)
-hipError_t launch_gemv_quad(const FusedArgs& a_in, int N, bool build_lut, int force_ft, int force_wpq, hipStream_t st) {
-    if (a_in.nmat < 1 || a_in.nmat > 4) return hipErrorInvalidValue;
+// launch_gemv_quad, one overload per argument block: what the block's instantiations take (ok), its planner, then the unit.
+// a.m[i].nb_end must hold cumulative QUAD counts.  ft / wpq: 0 = heuristic (A/B knobs)
+template <class Args, class Planner>
+static hipError_t quad_launch(const Args& a_in, bool ok, int N, hipStream_t st, Planner plan) {
     QuadPlan p;
-    if (!quad_plan(a_in.s, a_in.m[a_in.nmat - 1].nb_end, build_lut, a_in.dump != nullptr, a_in.acc_mfma != 0, force_ft, force_wpq, p)) return hipErrorInvalidValue;
-    FusedArgs a = a_in;
+    if (a_in.nmat < 1 || a_in.nmat > 4 || !ok || !plan(a_in.m[a_in.nmat - 1].nb_end, p)) return hipErrorInvalidValue;
+    Args a = a_in;
     fused_precompute(a);
     return quad_unit(a, p, N, st);
+}
+hipError_t launch_gemv_quad(const FusedArgs& a, int N, bool build_lut, int ft, int wpq, bool, hipStream_t st) {
+    return quad_launch(a, true, N, st, [&](int total_q, QuadPlan& p) { return quad_plan(a.s, total_q, build_lut, a.dump != nullptr, a.acc_mfma != 0, ft, wpq, p); });
 }
 
 static bool xf_args_bad(const FusedXfArgs& a) {
@@ -30,22 +34,13 @@ static bool xf_args_bad(const FusedXfArgs& a) {
     if (gate < 0 || gate > 2 || (kind == 1 && gate != 0)) return true;      // silu, relu^2, tanh-GELU (tmac_quad_core.h XF_GATE_*); NORM has no gate
     return kind == 4 && (!a.in2 || !a.gamma);
 }
-hipError_t launch_gemv_quad_xf(const FusedXfArgs& a_in, int ft, int wpq, bool strict, hipStream_t st) {
-    if (a_in.nmat < 1 || a_in.nmat > 4 || !a_in.acc_mfma || a_in.dump || xf_args_bad(a_in)) return hipErrorInvalidValue;
-    QuadPlan p;
-    if (!quad_plan_xf(a_in.s, a_in.m[a_in.nmat - 1].nb_end, a_in.xf_kind, ft, wpq, strict, p)) return hipErrorInvalidValue;
-    FusedXfArgs a = a_in;
-    fused_precompute(a);
-    return quad_unit(a, p, 1, st);
+hipError_t launch_gemv_quad(const FusedXfArgs& a, int N, bool build_lut, int ft, int wpq, bool strict, hipStream_t st) {
+    return quad_launch(a, N == 1 && build_lut && a.acc_mfma && !a.dump && !xf_args_bad(a), 1, st,
+                       [&](int total_q, QuadPlan& p) { return quad_plan_xf(a.s, total_q, a.xf_kind, ft, wpq, strict, p); });
 }
-
-hipError_t launch_gemv_quad_perm(const FusedPermArgs& a_in, int ft, int wpq, bool strict, hipStream_t st) {
-    if (a_in.nmat < 1 || a_in.nmat > 4 || !a_in.acc_mfma || a_in.dump || a_in.lut_tap || !a_in.perm) return hipErrorInvalidValue;
-    QuadPlan p;
-    if (!quad_plan_perm(a_in.s, a_in.m[a_in.nmat - 1].nb_end, ft, wpq, strict, p)) return hipErrorInvalidValue;
-    FusedPermArgs a = a_in;
-    fused_precompute(a);
-    return quad_unit(a, p, 1, st);
+hipError_t launch_gemv_quad(const FusedPermArgs& a, int N, bool build_lut, int ft, int wpq, bool strict, hipStream_t st) {
+    return quad_launch(a, N == 1 && build_lut && a.acc_mfma && !a.dump && !a.lut_tap && a.perm, 1, st,
+                       [&](int total_q, QuadPlan& p) { return quad_plan_perm(a.s, total_q, ft, wpq, strict, p); });
 }
 
 // *launches (optional) grows by the number of k_gemv_rows launches made

@@ -70,7 +70,7 @@ size_t quad_lds_bytes(const Shape& s, int nwv);
 // The (threads, waves per quad) of a launch: best_ft / best_wpq; false when the kernel has no such configuration.  need512: the launch
 // wants an instantiation that exists for 512-thread workgroups only (tap, prebuilt LUT, v_mqsad accumulate).  force_*: 0 = heuristic.
 bool quad_config(const Shape& s, bool need512, int total_q, int force_ft, int force_wpq, int& best_ft, int& best_wpq);
-// total_q: row quads of all matrices.  false: refused (launch_gemv_quad / launch_gemv_quad_xf then return hipErrorInvalidValue).
+// total_q: row quads of all matrices.  false: refused (launch_gemv_quad's overloads then return hipErrorInvalidValue).
 bool quad_plan(const Shape& s, int total_q, bool build_lut, bool dump, bool acc_mfma, int force_ft, int force_wpq, QuadPlan& p);
 // xf_kind: tmac_hip_xform::kind as it comes (kind | gate << 8).  strict: the configuration was forced by the caller and must be covered as
 // it is; else one outside the covered set falls back to the nearest covered one.

@@ -785,7 +785,7 @@ q_done:
 #endif
 constexpr bool QSCF16 = TMAC_QUAD_SCF16 != 0;   // weight scales stored as fp16 (1) / fp32 (0): a kernel template parameter
 
-// This unit's launcher (declared in tmac_kernels.h; launch_gemv_quad / launch_gemv_quad_xf, tmac_launch.cpp, plan and pick the unit): select
+// This unit's launcher (declared in tmac_kernels.h; the overloads of launch_gemv_quad, tmac_launch.cpp, plan and pick the unit): select
 // the instantiation the plan names and launch it.  Which instantiations exist is quad_inst_exists (tmac_launch_plan.h) -- the selector
 // instantiates what passes it, so the predicate is the list of kernels this unit emits; the planner never names another.
 template <int BITS, bool SCF16, class Args>

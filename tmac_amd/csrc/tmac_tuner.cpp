@@ -127,29 +127,26 @@ extern "C" int32_t tmac_hip_autotune_fused(const tmac_hip_weights* const* wl, in
     ok = ok && hipMemsetAsync(Bd, 0x3c, (size_t)s0.K * 4, st) == hipSuccess && hipStreamSynchronize(st) == hipSuccess;
     if (!ok) { release(); (void)hipStreamDestroy(st); return fail(TMAC_HIP_E_RUNTIME, "autotune: device allocation / copy failed"); }
 
+    // the call on the scratch vectors, its matrices replaced by replica r (the MFMA accumulate whatever the variant knob says)
+    const FusedCall call{wl, nmat, Bd, act_dtype, Cd.data(), out_dtype, 1, st};
+    int total_q = 0;
     auto make_args = [&](int r) {
         FusedArgs fa;
-        memset(&fa, 0, sizeof(fa));
-        fa.nmat = nmat;
-        int nb = 0;
+        total_q = fill_fused_args(fa, call);
         for (int i = 0; i < nmat; ++i) {
-            nb += wl[i]->s.nquads();
             fa.m[i].W = (const uint4*)(Wc[i] + (size_t)r * wl[i]->w_bytes);
             fa.m[i].SC = Sc[i] + (size_t)r * wl[i]->sc_bytes;
-            fa.m[i].C = Cd[i]; fa.m[i].Mw = wl[i]->s.Mw; fa.m[i].nb_end = nb;
         }
-        fa.s = s0; fa.B = Bd; fa.act_f16 = act_dtype == TMAC_F16;
-        fa.sc_f16 = wl[0]->sc_dtype == F16; fa.out_f16 = out_dtype == TMAC_F16;
         fa.acc_mfma = 1;
         return fa;
     };
     auto time_config = [&](int ft, int wpq, float& us) -> hipError_t {
-        hipError_t e = launch_gemv_quad(make_args(0), 1, true, ft, wpq, st);   // validity probe + code-object warm-up
+        hipError_t e = launch_gemv_quad(make_args(0), 1, true, ft, wpq, false, st);   // validity probe + code-object warm-up
         if (e != hipSuccess) return e;
         if ((e = hipStreamSynchronize(st)) != hipSuccess) return e;
         hipGraph_t g = nullptr; hipGraphExec_t ge = nullptr;
         if ((e = hipStreamBeginCapture(st, hipStreamCaptureModeThreadLocal)) != hipSuccess) return e;
-        for (int r = 0; r < R && e == hipSuccess; ++r) e = launch_gemv_quad(make_args(r), 1, true, ft, wpq, st);
+        for (int r = 0; r < R && e == hipSuccess; ++r) e = launch_gemv_quad(make_args(r), 1, true, ft, wpq, false, st);
         hipError_t e2 = hipStreamEndCapture(st, &g);
         if (e == hipSuccess) e = e2;
         if (e == hipSuccess) e = hipGraphInstantiate(&ge, g, nullptr, nullptr, 0);
@@ -195,11 +192,9 @@ extern "C" int32_t tmac_hip_autotune_fused(const tmac_hip_weights* const* wl, in
         bestv.ft = 0;
     }
     if (bestv.ft) {
-        FusedArgs fa = make_args(0);
-        int nb = 0;
-        for (int i = 0; i < nmat; ++i) nb += wl[i]->s.nquads();
+        const FusedArgs fa = make_args(0);
         std::lock_guard<std::mutex> lk(g_tune_mu);
-        g_tuned[tune_key(fa, nb)] = bestv;
+        g_tuned[tune_key(fa, total_q)] = bestv;
     }
     if (best_ft) *best_ft = bestv.ft;
     if (best_wpq) *best_wpq = bestv.ft ? bestv.wpq : 0;
