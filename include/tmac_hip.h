@@ -202,8 +202,11 @@ int32_t tmac_hip_register_weights_codes_dev(tmac_hip_weights** out, const void* 
  * What serves such handles: tmac_hip_qgemm_fused_dev -- all matrices of a call must carry the same permutation, or none ("matrices fused
  * in one launch must share the K permutation", TMAC_HIP_E_ARG); N = 1 runs k_gemv_quad's gather instantiations, N >= 2 is routed as
  * tmac_hip_qgemm_fused_xf_rows_dev routes a transformed call with the LUT build gathering; QUAD layout and the MFMA accumulate only
- * (TMAC_HIP_E_NOMATCH otherwise).  The call is never queued (deferred mode: it goes behind the queue and launches stand-alone) and never
- * recorded (between tmac_hip_chain_begin and _end it is refused, TMAC_HIP_E_ARG; the recording stays usable).  The split path:
+ * (TMAC_HIP_E_NOMATCH otherwise).  The call is never queued (deferred mode: it goes behind the queue and launches stand-alone).  Between
+ * tmac_hip_chain_begin and _end it is refused (TMAC_HIP_E_ARG; the recording stays usable): such a recording may end as k_decode_chain,
+ * which has no gather.  A recording that was DECLARED INDEPENDENT (tmac_hip_chain_begin_independent, below) notes it (N = 1): that
+ * recording can only become stream mode, whose LUT build (k_lut_images) gathers x[perm] per call; k_gemv_stream sees finished tables, so
+ * the launch is the one the plain twins W[:, perm] on x[perm] get, bit for bit.  The chain keeps its calls' permutations alive.  The split path:
  * tmac_hip_preprocessor_perm_dev + tmac_hip_qgemm_dev, below.  Refused with TMAC_HIP_E_ARG and a message: the parity taps of the fused
  * entry point (tmac_hip_qgemm_fused_partial_sums) and vector transforms (tmac_hip_qgemm_fused_xf_dev, _xf_rows_dev) on such handles. */
 typedef struct tmac_hip_kperm tmac_hip_kperm;
@@ -321,6 +324,17 @@ int32_t tmac_hip_defer_stats(uint64_t* flushes, uint64_t* cache_hits, uint64_t* 
  * tmac_hip_chain_status instead of hanging). */
 typedef struct tmac_hip_chain tmac_hip_chain;
 int32_t tmac_hip_chain_begin(void);
+/* A recording DECLARED INDEPENDENT when it begins: the caller states that no recorded call reads another's output.  It works like
+ * tmac_hip_chain_begin (_end, _abort, the launch and the inspection calls are the same), and in return tmac_hip_chain_end builds a
+ * STREAM-MODE chain (k_lut_images + k_gemv_stream, tmac_hip_chain_is_stream != 0) or fails -- never k_decode_chain.  Its failures are
+ * TMAC_HIP_E_ARG with a message naming the first offending call: a call reads an earlier call's output (both are named), a call carries
+ * a transform, an exchange step was recorded, the stream planner has no form for the calls, or TMAC_CHAIN_STREAM=0 is set; as after
+ * every failed _end the recording is over and the thread launches calls again.  tmac_hip_chain_xform and tmac_hip_chain_record_gather
+ * are refused at once inside it (TMAC_HIP_E_ARG; the recording stays usable).  Because it can only become a stream, calls on act-order
+ * handles (above) are noted in it: all matrices of a call carry the same permutation or none; the calls of a chain may mix plain
+ * handles and different permutations.  A chain without such a call launches exactly what a tmac_hip_chain_begin recording of the same
+ * independent calls launches. */
+int32_t tmac_hip_chain_begin_independent(void);
 int32_t tmac_hip_chain_end(tmac_hip_chain** out);
 /* ends the recording without building a chain (after an error while recording: the thread launches its calls again) */
 int32_t tmac_hip_chain_abort(void);

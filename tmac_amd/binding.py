@@ -154,6 +154,7 @@ def load_library() -> C.CDLL:
         "tmac_hip_debug_defer_fail": ([C.c_int], i32),
         "tmac_hip_defer_stats": ([C.POINTER(C.c_uint64)] * 4, i32),
         "tmac_hip_chain_begin": ([], i32),
+        "tmac_hip_chain_begin_independent": ([], i32),
         "tmac_hip_chain_end": ([C.POINTER(vp)], i32),
         "tmac_hip_chain_launch": ([vp, vp], i32),
         "tmac_hip_chain_status": ([vp, C.POINTER(C.c_uint32)], i32),
@@ -179,7 +180,7 @@ def load_library() -> C.CDLL:
         "preprocessor_int8": ([C.c_int] * 4 + [vp] * 4, i32),
     }
     # $TMAC_HIP_LIB may name an OLDER build for an A/B run (tools/gpu): entry points it lacks stay unbound (calling one raises)
-    optional = {"tmac_hip_chain_is_stream", "tmac_hip_chain_xform", "tmac_hip_qgemm_fused_xf_dev", "tmac_hip_qgemm_fused_xf_rows_dev", "tmac_hip_debug_xf_rows", "tmac_hip_debug_xf_rows_plan", "tmac_hip_debug_fused_plan", "tmac_hip_debug_route_stats", "tmac_hip_comm_init_ipc", "tmac_hip_comm_export", "tmac_hip_comm_connect", "tmac_hip_comm_status",
+    optional = {"tmac_hip_chain_is_stream", "tmac_hip_chain_begin_independent", "tmac_hip_chain_xform", "tmac_hip_qgemm_fused_xf_dev", "tmac_hip_qgemm_fused_xf_rows_dev", "tmac_hip_debug_xf_rows", "tmac_hip_debug_xf_rows_plan", "tmac_hip_debug_fused_plan", "tmac_hip_debug_route_stats", "tmac_hip_comm_init_ipc", "tmac_hip_comm_export", "tmac_hip_comm_connect", "tmac_hip_comm_status",
                 "tmac_hip_ref_blob_bytes", "tmac_hip_pack_gptq_dev", "tmac_hip_pack_codes_dev", "tmac_hip_register_weights_gptq_dev",
                 "tmac_hip_register_weights_codes_dev",
                 "tmac_hip_kperm_from_gidx_dev", "tmac_hip_kperm_info", "tmac_hip_kperm_read", "tmac_hip_kperm_free", "tmac_hip_weights_kperm_id",

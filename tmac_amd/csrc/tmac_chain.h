@@ -170,7 +170,8 @@ inline size_t stream_lds_bytes(int buf_u4, int nops, bool qw = false) {
 #endif
     return b;
 }
-hipError_t launch_lut_images(const ChainOp* d_ops, int nops, int max_nst, int sm, bool sc_f16, hipStream_t st);
+// d_perms: null, or (a chain with an op on act-order matrices) one device permutation per op, null for its plain ops: the gather build
+hipError_t launch_lut_images(const ChainOp* d_ops, const int32_t* const* d_perms, int nops, int max_nst, int sm, bool sc_f16, hipStream_t st);
 // Four translation units (tmac_stream.hip: the quarter-walk form with -DTMAC_STREAM_QW_TU=1; g2 as launch_decode_chain's, both forms, with
 // -DTMAC_STREAM_G2_TU=1), each defines and instantiates its launcher
 template <bool QW, bool G2>

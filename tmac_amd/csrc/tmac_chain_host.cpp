@@ -1,5 +1,6 @@
 // tmac_chain_host.cpp — recording and building the persistent decode chain (kernels: tmac_chain.hip, tmac_stream.hip).
 #include "tmac_chain_host.h"
+#include "tmac_chain_indep.h"
 #include <algorithm>
 #include <array>
 #include <memory>
@@ -16,7 +17,11 @@ using namespace tmac_host;
 static thread_local std::vector<ChainRecOp>* g_chain_rec = nullptr;
 static thread_local std::vector<ChainRecGather>* g_chain_gat = nullptr;
 static thread_local std::optional<XfSpec> g_chain_xf;               // the transform declared for the next recorded call, resolved (tmac_xform.h)
+// The recording was declared independent when it began (tmac_hip_chain_begin_independent): it ends as a stream chain or not at all, so
+// transforms and exchange steps are refused as they come, and calls on act-order handles -- whose gather only k_lut_images has -- are noted.
+static thread_local bool g_chain_declared = false;
 bool tmac_host::chain_recording() { return g_chain_rec != nullptr; }
+bool tmac_host::chain_recording_independent() { return g_chain_rec != nullptr && g_chain_declared; }
 void tmac_host::chain_clear_xform() { g_chain_xf.reset(); }
 
 int32_t tmac_host::chain_record(const FusedCall& c) {
@@ -25,6 +30,7 @@ int32_t tmac_host::chain_record(const FusedCall& c) {
     const int32_t nrc = nulls_check(c);
     if (nrc) { chain_clear_xform(); return nrc; }
     ChainRecOp op(c);
+    op.perm = c.wl[0]->kperm;           // (fused_impl: all matrices carry it, or none does; non-null in a declared-independent recording only)
     op.xf = g_chain_xf.value_or(XfSpec{});
     chain_clear_xform();
     g_chain_rec->push_back(op);
@@ -34,6 +40,7 @@ int32_t tmac_host::chain_record(const FusedCall& c) {
 // A vector transform for the NEXT recorded call (include/tmac_hip.h): validated when the chain is built.
 extern "C" int32_t tmac_hip_chain_xform(const tmac_hip_xform* xf) {
     if (!g_chain_rec) return fail(TMAC_HIP_E_ARG, "no chain is being recorded on this thread");
+    if (g_chain_declared) return fail(TMAC_HIP_E_ARG, "this recording was declared independent (tmac_hip_chain_begin_independent): its calls carry no vector transform");
     if (!xf) return fail(TMAC_HIP_E_ARG, "null transform");
     XfSpec spec;
     const int32_t rc = xf_resolve(xf, XF_SITE_CHAIN, &spec);
@@ -42,13 +49,17 @@ extern "C" int32_t tmac_hip_chain_xform(const tmac_hip_xform* xf) {
     return TMAC_HIP_OK;
 }
 
-extern "C" int32_t tmac_hip_chain_begin(void) {
+static int32_t chain_begin(bool declared) {
     if (g_chain_rec) return fail(TMAC_HIP_E_ARG, "a chain is already being recorded on this thread");
     g_chain_rec = new std::vector<ChainRecOp>();
     g_chain_gat = new std::vector<ChainRecGather>();
+    g_chain_declared = declared;
     chain_clear_xform();
     return TMAC_HIP_OK;
 }
+extern "C" int32_t tmac_hip_chain_begin(void) { return chain_begin(false); }
+// ... declared independent (include/tmac_hip.h): tmac_hip_chain_end builds stream mode or fails
+extern "C" int32_t tmac_hip_chain_begin_independent(void) { return chain_begin(true); }
 
 // Ends a recording without building anything (a caller whose recording hit an error: the thread is free to launch calls again).
 extern "C" int32_t tmac_hip_chain_abort(void) {
@@ -57,6 +68,7 @@ extern "C" int32_t tmac_hip_chain_abort(void) {
     delete g_chain_gat;
     g_chain_rec = nullptr;
     g_chain_gat = nullptr;
+    g_chain_declared = false;
     chain_clear_xform();
     return TMAC_HIP_OK;
 }
@@ -72,14 +84,17 @@ extern "C" int32_t tmac_hip_chain_end(tmac_hip_chain** out) {
     delete g_chain_gat;
     g_chain_rec = nullptr;
     g_chain_gat = nullptr;
+    const bool declared = g_chain_declared;
+    g_chain_declared = false;
     if (!out) return fail(TMAC_HIP_E_ARG, "null argument");
-    return chain_build(rec, gat, out);
+    return chain_build(rec, gat, out, declared);
 }
 
 // The exchange step of a row-sharded chain, noted instead of executed (tmac_hip_comm_allgather calls this while the thread
 // records): the calls that read recv_dev afterwards consume, inside the launch, what every rank's producer of send_dev publishes.
 extern "C" int32_t tmac_hip_chain_record_gather(const void* send_dev, void* recv_dev, size_t bytes_per_rank, int rank, int world) {
     if (!g_chain_rec) return fail(TMAC_HIP_E_ARG, "no chain is being recorded on this thread");
+    if (g_chain_declared) return fail(TMAC_HIP_E_ARG, "this recording was declared independent (tmac_hip_chain_begin_independent): it takes no exchange step");
     if (!send_dev || !recv_dev || !bytes_per_rank || world < 1 || world > 8 || rank < 0 || rank >= world)
         return fail(TMAC_HIP_E_ARG, "bad gather (1..8 ranks)");
     g_chain_gat->push_back(ChainRecGather{send_dev, recv_dev, bytes_per_rank, rank, world, g_chain_rec->size()});
@@ -113,6 +128,7 @@ extern "C" int32_t tmac_hip_chain_free(tmac_hip_chain* c) {
     if (c->images) (void)hipFree(c->images);
     if (c->d_tap_off) (void)hipFree(c->d_tap_off);
     if (c->d_ops) (void)hipFree(c->d_ops);
+    if (c->d_perms) (void)hipFree(c->d_perms);
     if (c->ctl) (void)hipFree(c->ctl);
     delete c;
     return brc;
@@ -389,6 +405,7 @@ static int32_t describe_ops(const std::vector<ChainRecOp>& rec, const ChainFlow&
         if ((r.out == TMAC_F16) != (c.out_f16 != 0)) return fail(TMAC_HIP_E_NOMATCH, "op %zu: one output dtype per chain", i);
         if (s0.K > 8 * 3 * CHAIN_FT) return fail(TMAC_HIP_E_NOMATCH, "op %zu: K = %d beyond the decode chain's %d", i, s0.K, 8 * 3 * CHAIN_FT);
         if (((s0.m_groups >= 1) ? 2 : 0) != c.sm) return fail(TMAC_HIP_E_NOMATCH, "op %zu: per-group and unified scales cannot share a chain", i);
+        if (r.perm && c.sm == 2) return fail(TMAC_HIP_E_NOMATCH, "op %zu: act-order handles are served with per-group scales only", i);
         int gu = 1;
         if (c.sm == 2) {
             if (s0.ags != s0.K || s0.K % 64 || s0.m_groups > CHAIN_US_MAX_GROUPS)
@@ -558,11 +575,21 @@ static int32_t check_hazards(const std::vector<ChainRecOp>& rec, const ChainFlow
 // a caller that evaluates many vectors against many matrices).  The reference's call structure then applies as it stands: tables
 // once per activation vector (llama_cpp_init), lookups per matrix (llama_cpp_compute); see tmac_stream.hip.  The hazard analysis
 // has already refused every write of the launch that touches a vector another op reads from memory.  TMAC_CHAIN_STREAM=0: A/B.
-static bool independent(const std::vector<ChainRecOp>& rec, const std::vector<ChainRecGather>& gat, const ChainFlow& f, const std::vector<ChainOp>& ops) {
-    if (!gat.empty()) return false;
-    for (size_t i = 0; i < rec.size(); ++i)
-        if (f.src[i].op >= 0 || f.src2[i].op >= 0 || rec[i].xf.kind != TMAC_XF_NONE || ops[i].epi) return false;
-    return true;
+// The verdict (tmac_chain_indep.h) names the first call that stands in the way: a recording declared independent is refused with it.
+static IndepVerdict independent(const std::vector<ChainRecOp>& rec, const std::vector<ChainRecGather>& gat, const ChainFlow& f) {
+    std::vector<IndepOp> io(rec.size());
+    for (size_t i = 0; i < rec.size(); ++i) io[i] = IndepOp{f.src[i].op, f.src2[i].op, (int)rec[i].xf.kind, f.epi_of[i]};
+    return indep_verdict(io.data(), io.size(), gat.size());
+}
+static int32_t refuse_declared(const IndepVerdict& v) {
+    static const char* const DECL = "the recording was declared independent (tmac_hip_chain_begin_independent)";
+    switch (v.why) {
+    case INDEP_FLOW: return fail(TMAC_HIP_E_ARG, "op %d reads an output of op %d as its activations: %s", v.op, v.other, DECL);
+    case INDEP_FLOW2: return fail(TMAC_HIP_E_ARG, "op %d reads an output of op %d as the second vector of its GLU: %s", v.op, v.other, DECL);
+    case INDEP_XFORM: return fail(TMAC_HIP_E_ARG, "op %d carries a vector transform: %s", v.op, DECL);
+    case INDEP_EPILOGUE: return fail(TMAC_HIP_E_ARG, "op %d publishes a GLU's product for a later call: %s", v.op, DECL);
+    default: return fail(TMAC_HIP_E_ARG, "an exchange step was recorded: %s", DECL);
+    }
 }
 struct StreamPlan {
     std::vector<ChainOp> ops;             // the descriptors as k_lut_images / k_gemv_stream read them (img: written by commit_stream)
@@ -734,6 +761,13 @@ static int32_t commit(tmac_hip_chain& c, const ChainLayout& lay) {
     if (hipMalloc((void**)&c.d_ops, sizeof(ChainOp) * c.ops.size()) != hipSuccess ||
         hipMemcpy(c.d_ops, c.ops.data(), sizeof(ChainOp) * c.ops.size(), hipMemcpyHostToDevice) != hipSuccess)
         return fail(TMAC_HIP_E_RUNTIME, "descriptor upload failed");
+    if (c.has_perm) {        // k_lut_images' second argument: one device permutation per op, null for the plain ones
+        std::vector<const int32_t*> dp(c.ops.size(), nullptr);
+        for (size_t i = 0; i < dp.size(); ++i) if (c.perms[i]) dp[i] = c.perms[i]->dev;
+        if (hipMalloc((void**)&c.d_perms, sizeof(const int32_t*) * dp.size()) != hipSuccess ||
+            hipMemcpy(c.d_perms, dp.data(), sizeof(const int32_t*) * dp.size(), hipMemcpyHostToDevice) != hipSuccess)
+            return fail(TMAC_HIP_E_RUNTIME, "permutation table upload failed");
+    }
     const unsigned ctl0[4] = {1u, 0u, 0u, 0u};
     if (hipMalloc((void**)&c.ctl, sizeof(ctl0)) != hipSuccess || hipMemcpy(c.ctl, ctl0, sizeof(ctl0), hipMemcpyHostToDevice) != hipSuccess)
         return fail(TMAC_HIP_E_RUNTIME, "control word allocation failed");
@@ -744,7 +778,7 @@ static int32_t commit(tmac_hip_chain& c, const ChainLayout& lay) {
 
 struct ChainFree { void operator()(tmac_hip_chain* c) const { (void)tmac_hip_chain_free(c); } };
 
-int32_t tmac_host::chain_build(const std::vector<ChainRecOp>& rec, const std::vector<ChainRecGather>& gat, tmac_hip_chain** out) {
+int32_t tmac_host::chain_build(const std::vector<ChainRecOp>& rec, const std::vector<ChainRecGather>& gat, tmac_hip_chain** out, bool declared) {
     *out = nullptr;
     if (rec.empty()) return fail(TMAC_HIP_E_ARG, "nothing was recorded");
     int32_t rc = ensure_device();
@@ -768,11 +802,26 @@ int32_t tmac_host::chain_build(const std::vector<ChainRecOp>& rec, const std::ve
     ChainFlow flow;
     if ((rc = analyse_flow(rec, gat, rec[0].out, flow)) != TMAC_HIP_OK) return rc;
     plan_glu_epilogue(rec, flow, c->grid, kn);
+    const IndepVerdict indep = independent(rec, gat, flow);
+    // a declared-independent recording becomes a stream or nothing: refused here, by the first call that breaks the declaration, before
+    // anything is said about k_decode_chain's own limits
+    if (declared && indep.why != INDEP_OK) return refuse_declared(indep);
+    for (const ChainRecOp& r : rec) {
+        if (r.perm && !declared) return fail(TMAC_HIP_E_ARG, "a call on act-order handles is recorded only in a recording declared independent");
+        c->has_perm = c->has_perm || r.perm;
+    }
     ChainLayout lay;
     if ((rc = describe_ops(rec, flow, kn, *c, lay)) != TMAC_HIP_OK) return rc;
     if ((rc = check_hazards(rec, flow, c->ops)) != TMAC_HIP_OK) return rc;
     std::optional<StreamPlan> plan;
-    if (kn.stream && independent(rec, gat, flow, c->ops)) plan = plan_stream(c->ops, c->bits, c->g2 != 0, c->grid, kn);
+    if (kn.stream && indep.why == INDEP_OK) plan = plan_stream(c->ops, c->bits, c->g2 != 0, c->grid, kn);
+    if (declared && !plan)
+        return fail(TMAC_HIP_E_ARG, kn.stream ? "the stream planner has no form for these calls (rows per workgroup, or LDS for the LUT images): the recording was declared independent "
+                                                "(tmac_hip_chain_begin_independent) and is not built as k_decode_chain"
+                                              : "TMAC_CHAIN_STREAM=0 keeps every recording out of stream mode: the recording was declared independent "
+                                                "(tmac_hip_chain_begin_independent) and is not built as k_decode_chain");
+    if (c->has_perm)         // (the chain owns its ops' permutations: the device arrays outlive the handles and the caller's objects)
+        for (const ChainRecOp& r : rec) c->perms.push_back(r.perm);
     if (plan && (rc = commit_stream(*c, *plan)) != TMAC_HIP_OK) return rc;
     if ((rc = commit(*c, lay)) != TMAC_HIP_OK) return rc;
     // A workgroup reaches the polls of an op right after publishing its own share of the previous one: the first poll cannot

@@ -39,6 +39,12 @@ struct tmac_hip_chain {
     int ncls = 1, vmax = 0;           // the schedule: classes of row ranges, records per class
     bool qw = false;                  // k_gemv_stream's quarter-walk form (rows dealt in groups of four quads: q_end / q_per / q_extra of the ops count groups)
     int nsplit = 1;                   // workgroups per row range (two share a CU and take alternate ops when LDS and registers allow)
+    // act-order ops (a recording declared independent, tmac_hip_chain_begin_independent): perms[op] is the K permutation the op's matrices
+    // carry (null: a plain op) -- owned here, so that the device arrays k_lut_images' gather form reads outlive the handles and the
+    // caller's tmac_hip_kperm -- and d_perms their device pointers, one per op, uploaded beside d_ops; both empty / null without such an op
+    bool has_perm = false;
+    std::vector<std::shared_ptr<KPermData>> perms;
+    const int32_t** d_perms = nullptr;
     int g2 = 0;                       // 1 iff some op has scale groups of 64: both launchers then run the instances with two scale groups per lane
                                       // and item (tmac_chain_core.h, G2); a recording without such an op launches the kernels it always did
 };
@@ -52,12 +58,13 @@ struct ChainRecOp {
     std::vector<void*> C;
     tmac_dtype_t act, out;
     XfSpec xf;                       // vector transform of the activations, resolved (tmac_xform.h; kind 0: none)
+    std::shared_ptr<KPermData> perm; // the K permutation all matrices of the call carry (act-order; a declared-independent recording only), or null
     ChainRecOp() = default;
     explicit ChainRecOp(const FusedCall& c) : w(c.wl, c.wl + c.nmat), B(c.B), C(c.C, c.C + c.nmat), act(c.act), out(c.out) {}
     // ... and back: the call as a view over this op's own lists
     FusedCall call(hipStream_t st) const { return FusedCall{w.data(), (int)w.size(), B, act, C.data(), out, 1, st}; }
     // the fields that make two noted calls the same call (a deferred batch's signature is its calls)
-    bool same_call(const ChainRecOp& o) const { return B == o.B && act == o.act && out == o.out && w == o.w && C == o.C; }
+    bool same_call(const ChainRecOp& o) const { return B == o.B && act == o.act && out == o.out && w == o.w && C == o.C && perm == o.perm; }
 };
 // an exchange step noted while recording: recv = all-gather over the ranks of send (rank r's bytes at r * bytes)
 struct ChainRecGather {
@@ -78,6 +85,7 @@ inline Range out_range(const ChainRecOp& r, size_t m, tmac_dtype_t out) {
 }
 
 // Builds the chain of the calls `rec` (and the exchange steps noted between them): tmac_hip_chain_end's return codes and messages.
-int32_t chain_build(const std::vector<ChainRecOp>& rec, const std::vector<ChainRecGather>& gat, tmac_hip_chain** out);
+// declared: the recording was declared independent when it began -- a stream chain or TMAC_HIP_E_ARG, never k_decode_chain.
+int32_t chain_build(const std::vector<ChainRecOp>& rec, const std::vector<ChainRecGather>& gat, tmac_hip_chain** out, bool declared = false);
 
 }  // namespace tmac_host

@@ -17,7 +17,7 @@ extern "C" int32_t tmac_hip_chain_launch(tmac_hip_chain* c, void* stream) {
     }
     if (!c->connected) return fail(TMAC_HIP_E_ARG, "a row-sharded chain must be connected to its peers first (tmac_hip_chain_export / tmac_hip_chain_connect)");
     if (c->stream) {
-        hipError_t e = launch_lut_images(c->d_ops, (int)c->ops.size(), c->max_nst, c->sm, c->sc_f16 != 0, st);
+        hipError_t e = launch_lut_images(c->d_ops, c->d_perms, (int)c->ops.size(), c->max_nst, c->sm, c->sc_f16 != 0, st);
         if (e != hipSuccess) return fail(TMAC_HIP_E_RUNTIME, "LUT image launch: %s", hipGetErrorString(e));
         StreamArgs sa;
         memset(&sa, 0, sizeof(sa));

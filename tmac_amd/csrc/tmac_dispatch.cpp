@@ -678,6 +678,11 @@ int32_t tmac_host::fused_impl(const FusedCall& c, int32_t* dump, float* lut_tap)
         if (chain_recording()) chain_clear_xform();
         if (ps < 0) return fail(TMAC_HIP_E_ARG, "matrices fused in one launch must share the K permutation");
         if (tap) return refuse_perm(c, "a parity tap");
+        if (chain_recording_independent()) {     // ... but noted where the recording can only become a stream: k_lut_images gathers (N = 1)
+            for (int i = 0; i < c.nmat; ++i)
+                if (c.wl[i]->s.m_groups >= 1) return fail(TMAC_HIP_E_NOMATCH, "matrix %d: act-order handles are served with per-group scales only", i);
+            return chain_record(c);
+        }
         if (chain_recording()) return refuse_perm(c, "a recorded call (tmac_hip_chain_begin ... _end)");
         return fused_perm(c);
     }

@@ -218,6 +218,7 @@ void tuned_config(const FusedArgs& fa, int total_q, int& ft, int& wpq);   // lea
 
 // ---- decode chain (tmac_chain_host.cpp) and deferred queue (tmac_defer.cpp) -----------------------------------------------------------
 bool chain_recording();            // is the calling thread between tmac_hip_chain_begin and tmac_hip_chain_end?
+bool chain_recording_independent();   // ... in a recording that was declared independent (tmac_hip_chain_begin_independent)?
 void chain_clear_xform();          // drops a transform declared for the next recorded call (the call was rejected before it could be recorded)
 int32_t chain_record(const FusedCall& c);
 // deferred launches (tmac_hip_defer): true (and *rc set) when the call was queued instead of launched

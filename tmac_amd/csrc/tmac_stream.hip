@@ -50,8 +50,13 @@ namespace tmac {
 // k_preprocess_pairs (tmac_lut_build.h) writing what k_gemv_stream's LUT buffer holds, in the STEP-MAJOR layout (round 6;
 // c_compute's IMG2): [64-unit step][4][65] uint4 of signed half tables (pair p = unit p >> 2, row p & 3), then ls / 2 and lb / 2 per act
 // group (32 per step each); zero tables / zero scales for the units between K and the end of the last step.
+// GA: the launch holds an op on act-order matrices (W[:, perm], tmac_kperm.h) -- perms[op] is that op's device permutation (int32 [K], 16-byte
+// aligned, every value < K) or null for a plain op, and the pair's eight activations are x[perm[8 p .. 8 p + 7]] (the gather of the N >= 2
+// builders, xf_rows_x8 on GatherRowsArgs: two 16-byte index loads, then eight element loads, all issued before the first use).  Every line
+// of it sits under if constexpr (GA); launches without such an op run the plain instantiation, which never reads perms.
 // ---------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(256) void k_lut_images(const ChainOp* __restrict__ ops) {
+template <bool GA>
+__global__ __launch_bounds__(256) void k_lut_images(const ChainOp* __restrict__ ops, const int32_t* const* __restrict__ perms) {
     const ChainOp& d = ops[blockIdx.y];
     const int K = d.K, P = K / 8, nst = d.nst;
     if ((int)blockIdx.x >= nst) return;
@@ -70,7 +75,13 @@ __global__ __launch_bounds__(256) void k_lut_images(const ChainOp* __restrict__ 
         return;
     }
     float x[8];
-    lut_ld8(d.in, (d.in_gran & 2) == 0, 0, p, x);
+    if constexpr (GA) {
+        const int32_t* perm = perms[blockIdx.y];
+        if (perm != nullptr) xf_rows_x8(GatherRowsArgs{perm}, d.in, (d.in_gran & 2) == 0, K, 0, p, x);
+        else lut_ld8(d.in, (d.in_gran & 2) == 0, 0, p, x);
+    } else {
+        lut_ld8(d.in, (d.in_gran & 2) == 0, 0, p, x);
+    }
     float scales, t_scales, La, Lb;
     lut_group_scale(LUT_X8(x), scales, t_scales);
     *tslot = lut_tables2<true>(LUT_X8(x), t_scales, La, Lb);
@@ -129,11 +140,12 @@ __global__ __launch_bounds__(256) void k_lut_images_us(const ChainOp* __restrict
     }
 }
 
-hipError_t launch_lut_images(const ChainOp* d_ops, int nops, int max_nst, int sm, bool sc_f16, hipStream_t st) {
-    if (nops < 1 || max_nst < 1) return hipErrorInvalidValue;
-    if (sm == 2 && sc_f16) hipLaunchKernelGGL(k_lut_images_us<true>, dim3(nops), dim3(256), 0, st, d_ops);
+hipError_t launch_lut_images(const ChainOp* d_ops, const int32_t* const* d_perms, int nops, int max_nst, int sm, bool sc_f16, hipStream_t st) {
+    if (nops < 1 || max_nst < 1 || (d_perms && sm == 2)) return hipErrorInvalidValue;
+    if (d_perms) hipLaunchKernelGGL(k_lut_images<true>, dim3(max_nst, nops), dim3(256), 0, st, d_ops, d_perms);      // some op gathers (act-order)
+    else if (sm == 2 && sc_f16) hipLaunchKernelGGL(k_lut_images_us<true>, dim3(nops), dim3(256), 0, st, d_ops);
     else if (sm == 2) hipLaunchKernelGGL(k_lut_images_us<false>, dim3(nops), dim3(256), 0, st, d_ops);
-    else hipLaunchKernelGGL(k_lut_images, dim3(max_nst, nops), dim3(256), 0, st, d_ops);
+    else hipLaunchKernelGGL(k_lut_images<false>, dim3(max_nst, nops), dim3(256), 0, st, d_ops, (const int32_t* const*)nullptr);
     return hipGetLastError();
 }
 #endif   // !TMAC_STREAM_QW_TU && !TMAC_STREAM_G2_TU

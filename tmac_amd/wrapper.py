@@ -428,7 +428,12 @@ class Comm:
 
 class DecodeChain:
     """A recorded sequence of ``TMACGeMMWrapper.fused`` calls (N = 1) executed by ONE persistent kernel launch
-    (tmac_hip_chain_*, include/tmac_hip.h).  Built by ``TMACGeMMWrapper.record_chain``."""
+    (tmac_hip_chain_*, include/tmac_hip.h).  Built by ``TMACGeMMWrapper.record_chain``.
+
+    ``record_chain(independent=True)`` declares that no recorded call reads another's output: the chain is then a stream-mode one
+    (``stream`` is True: k_lut_images + k_gemv_stream) or the recording fails -- it never becomes k_decode_chain.  Only such a
+    recording notes calls on act-order handles (``register_weights_*_perm``): k_lut_images gathers x[perm] per call, and the chain
+    keeps the permutations it reads alive, whatever becomes of the ``KPerm`` objects."""
 
     def __init__(self, handle, keep):
         self._h = handle
@@ -505,12 +510,13 @@ class DecodeChain:
 
 
 class _ChainRecorder:
-    def __init__(self, wrapper):
+    def __init__(self, wrapper, independent=False):
         self.wr = wrapper
+        self.independent = independent
         self.chain: Optional[DecodeChain] = None
 
     def __enter__(self):
-        check(B.lib().tmac_hip_chain_begin())
+        check(B.lib().tmac_hip_chain_begin_independent() if self.independent else B.lib().tmac_hip_chain_begin())
         self.wr._recording = []
         return self
 
@@ -738,10 +744,13 @@ class TMACGeMMWrapper:
         xf = self._xform(kind, in2, residual, gamma, eps, residual_out, False, none_ok=True)
         check(B.lib().tmac_hip_debug_xf_rows(_ptr(B_dev), act_dtype, C.byref(xf), K, N, _ptr(x_out), _stream(stream)))
 
-    def record_chain(self) -> "_ChainRecorder":
+    def record_chain(self, independent: bool = False) -> "_ChainRecorder":
         """``with wr.record_chain() as rec: <the token's wr.fused(...) calls>`` — the calls are noted instead of launched;
-        afterwards ``rec.chain.launch()`` executes all of them in ONE persistent kernel launch (tmac_hip_chain_*)."""
-        return _ChainRecorder(self)
+        afterwards ``rec.chain.launch()`` executes all of them in ONE persistent kernel launch (tmac_hip_chain_*).
+        ``independent=True`` (tmac_hip_chain_begin_independent): the calls are declared to carry no data flow -- the chain is a
+        stream-mode one or the block's exit raises (TMAC_HIP_E_ARG naming the offending call); transforms are refused inside, and
+        calls on act-order handles are noted."""
+        return _ChainRecorder(self, independent)
 
     def autotune(self, weights_list, act_dtype=F16, out_dtype=F16):
         """Measure the launch configurations of the fused decode kernel on these matrices (the list ``fused`` will be

@@ -8,7 +8,16 @@ Reported: (b) / (a) and (b) / (c) per shape.  The yardstick is (c) from the same
 Second part: registration through the permutation (tmac_hip_register_weights_gptq_perm_dev) against the plain registration, host-clock ms
 around the call with the tensors already on the device, first run and the median of the following three (tools/bench_register.py's
 method for its column (b), without the upload).  No bar: the word-wise gather reads 8 / bits times the plain pack's qweight bytes, once.
-usage: bench_actorder.py [--out FILE] [--bits 2,4] [--shapes o,qkv,gate_up,down]"""
+--stream: act-order handles in stream mode instead (a recording declared independent, record_chain(independent=True)): NL calls per launch
+over NL distinct weight sets and activation vectors, ten launches per event pair, mean and best of ten pairs (DESIGN.md 4.4's method), us per
+call and fraction of the 8 TB/s HBM peak on the algorithmic bytes of
+  (a) plain handles in a stream on pre-gathered vectors: the floor;
+  (b) permuted handles in a declared-independent stream: k_lut_images gathers;
+  (c) one torch index_select per call into scratch, then the plain stream: what a caller could do before (replayed from a hipGraph);
+  (d) the permuted handles called stand-alone (k_gemv_quad's gather instantiations), replayed from a hipGraph: their route before.
+--launches N (with --stream): N timed event pairs per variant instead of ten (a profiler run: k_lut_images' own duration with and
+without the gather is read from its kernel trace, the two instantiations have two names).
+usage: bench_actorder.py [--out FILE] [--bits 2,4] [--shapes o,qkv,gate_up,down] [--stream [--nl 96] [--launches 10]]"""
 import argparse
 import os
 import sys
@@ -73,13 +82,120 @@ def register_ms(tensors, cfg, kperm):
     return out[0], float(np.median(out[1:]))
 
 
+def algorithmic_bytes(Mw, K, bits, cnt):
+    """SURVEY 8d's bytes of one fused call of cnt matrices (tools/bench_stream.py): weights, scales and zeros, the LUT once, the outputs"""
+    return cnt * (Mw * K * bits // 8 + Mw * (K // GS) * 2 * 2 + Mw * 2) + K // 4 * 16 + (K // AGS) * 4
+
+
+def device_gptq(gen, Mw, K, bits):
+    qw = torch.randint(-2 ** 31, 2 ** 31 - 1, (K * bits // 32, Mw), dtype=torch.int32, device=dev, generator=gen)
+    qz = torch.randint(-2 ** 31, 2 ** 31 - 1, (K // GS, Mw * bits // 32), dtype=torch.int32, device=dev, generator=gen)
+    sc = (torch.randn((K // GS, Mw), device=dev, generator=gen).abs() * 0.02 + 0.005).half()
+    return qw, sc, qz
+
+
+def event_pairs(fn, pairs, per_pair=10):
+    """fn() enqueues one launch of NL calls: us per launch, (mean, best) over `pairs` event pairs of per_pair launches, after three warm-up pairs"""
+    ts = []
+    for r in range(pairs + 3):
+        e0 = torch.cuda.Event(enable_timing=True); e1 = torch.cuda.Event(enable_timing=True)
+        e0.record()
+        for _ in range(per_pair):
+            fn()
+        e1.record(); torch.cuda.synchronize()
+        if r >= 3:
+            ts.append(e0.elapsed_time(e1) * 1e3 / per_pair)
+    return float(np.mean(ts)), float(np.min(ts))
+
+
+def stream_part(args):
+    wr = tmac_amd.TMACGeMMWrapper(act_group_size=AGS)
+    NL = args.nl
+    gen = torch.Generator(device=dev); gen.manual_seed(11)
+    lines = [f"# tools/bench_actorder.py --stream: {NL} calls per launch over {NL} distinct weight sets and vectors, 10 launches per event pair, mean (best) of "
+             f"{args.launches} pairs; fp16 activations and outputs",
+             f"# device: {torch.cuda.get_device_name(0)}; group size {GS}; random g_idx with exactly {GS} members per group; frac = of the 8 TB/s HBM peak",
+             "# (a) plain stream, pre-gathered x | (b) permuted handles, declared-independent stream | (c) torch index_select per call + plain stream (hipGraph) | "
+             "(d) permuted handles stand-alone (hipGraph)",
+             "shape     bits |  (a) us/call   frac |  (b) us/call   frac |  (c) us/call   frac |  (d) us/call   frac | (b)/(a)  (b)/(c)  (b)/(d)"]
+    for name in args.shapes.split(","):
+        Mw, K, nshare = SHAPES[name]
+        for bits in (int(b) for b in args.bits.split(",")):
+            cfg = KCfg.make(Mw, K, bits, convert.default_bm(bits, Mw), 16, GS, AGS, True)
+            kperm = tmac_amd.KPerm(random_g_idx(K + bits, K), GS)
+            perm = torch.from_numpy(kperm.perm().astype(np.int64)).to(dev)
+            plain_sets, perm_sets = [], []
+            for s in range(NL):
+                ts = [device_gptq(gen, Mw, K, bits) for _ in range(nshare)]
+                plain_sets.append([tmac_amd.Weights.from_gptq(*t, cfg, True, F16) for t in ts])
+                perm_sets.append([tmac_amd.Weights.from_gptq(*t, cfg, True, F16, g_idx=kperm) for t in ts])
+                del ts
+            xs = [torch.randn(K, device=dev, generator=gen).half() for _ in range(NL)]
+            xg = [x.index_select(0, perm).contiguous() for x in xs]
+            scratch = [torch.empty(K, dtype=torch.float16, device=dev) for _ in range(NL)]
+            outs = [[torch.empty(Mw, dtype=torch.float16, device=dev) for _ in range(nshare)] for _ in range(NL)]
+
+            def chain_of(sets, vecs):
+                with wr.record_chain(independent=True) as rec:
+                    for ws, v, o in zip(sets, vecs, outs):
+                        wr.fused(ws, v, o, 1, act_dtype=F16, out_dtype=F16)
+                assert rec.chain.stream
+                return rec.chain
+
+            ca, cb, cc = chain_of(plain_sets, xg), chain_of(perm_sets, xs), chain_of(plain_sets, scratch)
+            side = torch.cuda.Stream()
+
+            def select_then_stream():
+                for x, sc in zip(xs, scratch):
+                    torch.index_select(x, 0, perm, out=sc)
+                cc.launch(side)
+
+            def stand_alone():
+                for ws, x, o in zip(perm_sets, xs, outs):
+                    wr.fused(ws, x, o, 1, act_dtype=F16, out_dtype=F16, stream=side)
+
+            graphs = []
+            for fn in (select_then_stream, stand_alone):
+                with torch.cuda.stream(side):
+                    fn()
+                torch.cuda.synchronize()
+                g = torch.cuda.CUDAGraph()
+                with torch.cuda.graph(g, stream=side):
+                    fn()
+                graphs.append(g)
+            res = [event_pairs(f, args.launches) for f in (ca.launch, cb.launch, graphs[0].replay, graphs[1].replay)]
+            assert ca.status() == 0 and cb.status() == 0 and cc.status() == 0
+            hb = algorithmic_bytes(Mw, K, bits, nshare)
+            us = [m / NL for m, _ in res]
+            cols = " | ".join(f"{m / NL:6.2f} ({b / NL:5.2f}) {hb / (m / NL) * 1e-3 / 8000:5.3f}" for m, b in res)
+            line = f"{name:9s} {bits:4d} | {cols} | {us[1] / us[0]:7.3f}  {us[1] / us[2]:7.3f}  {us[1] / us[3]:7.3f}"
+            print(line, flush=True)
+            lines.append(line)
+            del graphs
+            for c in (ca, cb, cc):
+                c.free()
+            for ws in plain_sets + perm_sets:
+                for w in ws:
+                    w.free()
+    if args.out:
+        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+        with open(args.out, "w") as f:
+            f.write("\n".join(lines) + "\n")
+    return 0
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--stream", action="store_true")
+    ap.add_argument("--nl", type=int, default=96)
+    ap.add_argument("--launches", type=int, default=10)
     ap.add_argument("--out", default="")
     ap.add_argument("--bits", default="2,4")
     ap.add_argument("--shapes", default="o,qkv,gate_up,down")
     args = ap.parse_args()
     assert torch.cuda.is_available(), "bench_actorder.py measures on a GPU"
+    if args.stream:
+        return stream_part(args)
     wr = tmac_amd.TMACGeMMWrapper(act_group_size=AGS)
     lines = ["# tools/bench_actorder.py: us per call in a replayed hipGraph, best of 5 replays of 3 passes over 8 rotating weight sets; fp16 activations and outputs",
              f"# device: {torch.cuda.get_device_name(0)}; group size {GS}; random g_idx with exactly {GS} members per group",
