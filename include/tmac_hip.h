@@ -177,6 +177,41 @@ int32_t tmac_hip_register_weights_codes_dev(tmac_hip_weights** out, const void* 
                                             tmac_dtype_t sz_dtype, int Mw, int K, int bits, const tmac_kcfg* cfg,
                                             tmac_dtype_t ref_float, tmac_dtype_t dev_float, void* stream);
 
+/* ---- BitNet b1.58 master weights: the absmean rule on the device ------------------------------------------------------------
+ * A BitNet checkpoint from its authors holds no codes: it holds master weights W [Mw][K], row-major, in fp32, fp16 or bf16 (src_dtype; a
+ * dtype of its own -- tmac_dtype_t keeps its two values and its refusals).  The ternary levels come from the absmean rule of the BitNet
+ * b1.58 paper, applied here at load time.  The rows are divided into m_groups blocks of R = Mw / m_groups rows; for block g
+ *   gamma_g = fp32(sum |fp64(w)| / (R K))      accumulated in fp64 (k_absmean: fixed chunks, no atomics, chunk sums added in index order:
+ *                                              the same bits on every launch, stream and GPU)
+ *   s_g     = fmaxf(gamma_g, eps)              the unified scale stored for the block; eps: finite, > 0 (the paper's and the authors' 1e-5f)
+ *   t       = clamp(rintf(fp32(w) * (1.0f / s_g)), -1, 1)      every operation fp32 and correctly rounded, halves to even; a NaN gives 0
+ *   level   = t + 2                            {-1, 0, 1} -> levels 1, 2, 3 of the 2-bit format (w_real = (level - 2) s_g), level 0 unused
+ * The conversions of fp16 / bf16 masters to fp32 and of |w| to fp64 are exact.  scales_in_dev (fp32 [m_groups], device) hands in the s_g
+ * themselves -- a scale computed elsewhere or one the checkpoint carries: the reduction is skipped and the values are used as they are;
+ * keeping them > 0 is the caller's job.  NULL: computed.  Non-finite masters with a computed scale: an infinity makes its block's scale
+ * +infinity (every level of the block is then 2), a NaN is dropped by fmaxf (s_g = eps); no address depends on either.
+ *   tmac_hip_absmean_dev                   the reduction alone: s_g -> scales_out_dev (fp32 [m_groups]); K a multiple of 4
+ *   tmac_hip_pack_absmean_dev              -> the reference blob (sizes: tmac_hip_ref_blob_bytes with bits = 2); the levels go straight into
+ *                                          A_ref_out (k_pack_dense_weights: the codes kernel with a quantising stage 1 -- no [Mw][K] code
+ *                                          tensor is written anywhere), the m_groups scales into scales_ref_out as host_float
+ *   tmac_hip_register_weights_absmean_dev  packs into temporaries, then registers as tmac_hip_register_weights_codes_dev does
+ * Scope: bits = 2, unified scales (cfg->m_groups >= 1, Mw a multiple of it), whatever else registration accepts for such a configuration.
+ * Refusals, nothing launched and nothing written.  TMAC_HIP_E_ARG naming the argument: a NULL pointer (scales_in_dev excepted) or one below
+ * 16-byte alignment; an unknown src_dtype; eps not finite or <= 0; m_groups < 1 (per-group scales: register codes or GPTQ tensors);
+ * Mw % m_groups.  Shape refusals are registration's own codes and messages, as in tmac_hip_pack_codes_dev.
+ * All three are ordered behind the calling thread's deferred queue: they flush it first, a refused call leaves it alone, a failed flush
+ * returns its status and launches nothing.  The reduction needs scratch (8 bytes per 16384 masters), allocated and freed by the call: with
+ * a computed scale a call waits for `stream` before it returns; with scales_in_dev the pack allocates nothing and is asynchronous. */
+typedef enum { TMAC_SRC_F32 = 0, TMAC_SRC_F16 = 1, TMAC_SRC_BF16 = 2 } tmac_src_dtype_t;
+int32_t tmac_hip_absmean_dev(const void* W_dev, tmac_src_dtype_t src_dtype, int Mw, int K, int m_groups, float eps, float* scales_out_dev,
+                             void* stream);
+int32_t tmac_hip_pack_absmean_dev(const void* W_dev, tmac_src_dtype_t src_dtype, const float* scales_in_dev /* NULL: computed */, float eps,
+                                  int Mw, int K, const tmac_kcfg* cfg, void* A_ref_out, void* scales_ref_out, tmac_dtype_t host_float,
+                                  void* stream);
+int32_t tmac_hip_register_weights_absmean_dev(tmac_hip_weights** out, const void* W_dev, tmac_src_dtype_t src_dtype,
+                                              const float* scales_in_dev /* NULL: computed */, float eps, int Mw, int K, const tmac_kcfg* cfg,
+                                              tmac_dtype_t host_float, tmac_dtype_t dev_float, void* stream);
+
 /* ---- act-order (desc_act) GPTQ matrices: the K permutation ---------------------------------------------------------------
  * An act-order matrix is a group-quantised matrix whose K axis is permuted: g_idx[k] names the group of column k.  With
  * perm = stable_argsort(g_idx) the columns q[:, perm] lie in contiguous groups of group_size, scales / qzeros are in group order already,
@@ -276,7 +311,8 @@ int32_t tmac_hip_qgemm_fused_dev(const tmac_hip_weights* const* weights, int nma
  * flushes the queue first, unconditionally (no overlap analysis: none of them is a hot path) -- tmac_hip_preprocessor_dev,
  * tmac_hip_qgemm_dev, tmac_hip_qgemm_partial_sums, tmac_hip_qgemm_fused_partial_sums, tmac_hip_chain_launch, tmac_hip_workspace_read /
  * _write, tmac_hip_debug_gemm_comb_sums / _gemm_image_read, tmac_hip_autotune_fused, tmac_hip_pack_gptq_dev / _pack_codes_dev (they write the
- * caller's blob buffers; a refused one leaves the queue alone), and tmac_hip_free_weights, tmac_hip_chain_free and
+ * caller's blob buffers; a refused one leaves the queue alone), tmac_hip_absmean_dev / _pack_absmean_dev /
+ * _register_weights_absmean_dev (the same), and tmac_hip_free_weights, tmac_hip_chain_free and
  * tmac_hip_cache_clear (a queued call may name what they release).  When that flush fails the entry point returns its status and launches
  * nothing of its own (the three that release still release: the handle is dead either way).  A queue belongs to a thread: freeing, from
  * another thread, weights that this thread has queued is the caller's error.

@@ -13,6 +13,8 @@ import subprocess
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 F32, F16 = 0, 1
+# tmac_src_dtype_t: the element type of BitNet master weights (bf16 exists there alone)
+SRC_F32, SRC_F16, SRC_BF16 = 0, 1, 2
 # tmac_hip_xform.kind (include/tmac_hip.h): the kind in the low byte, the gate of a GLU / GLU_NORM in bits 8..15
 XF_NONE, XF_NORM, XF_GLU, XF_GLU_NORM = 0, 1, 2, 4
 XF_GATE_SILU, XF_GATE_RELU2, XF_GATE_GELU = 0x000, 0x100, 0x200
@@ -92,6 +94,10 @@ def load_library() -> C.CDLL:
                                                 C.c_int, vp], i32),
         "tmac_hip_register_weights_codes_dev": ([C.POINTER(vp), vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(KCfg), C.c_int, C.c_int,
                                                  vp], i32),
+        # BitNet master weights (the absmean rule): the scales alone, the blob, the handle
+        "tmac_hip_absmean_dev": ([vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, vp, vp], i32),
+        "tmac_hip_pack_absmean_dev": ([vp, C.c_int, vp, C.c_float, C.c_int, C.c_int, C.POINTER(KCfg), vp, vp, C.c_int, vp], i32),
+        "tmac_hip_register_weights_absmean_dev": ([C.POINTER(vp), vp, C.c_int, vp, C.c_float, C.c_int, C.c_int, C.POINTER(KCfg), C.c_int, C.c_int, vp], i32),
         # act-order (K permutation from g_idx): the object, packing / registration / the split path's LUT build through it
         "tmac_hip_kperm_from_gidx_dev": ([vp, C.c_int, C.c_int, C.POINTER(vp), vp], i32),
         "tmac_hip_kperm_info": ([vp, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_uint64)], i32),
@@ -183,6 +189,7 @@ def load_library() -> C.CDLL:
     optional = {"tmac_hip_chain_is_stream", "tmac_hip_chain_begin_independent", "tmac_hip_chain_xform", "tmac_hip_qgemm_fused_xf_dev", "tmac_hip_qgemm_fused_xf_rows_dev", "tmac_hip_debug_xf_rows", "tmac_hip_debug_xf_rows_plan", "tmac_hip_debug_fused_plan", "tmac_hip_debug_route_stats", "tmac_hip_comm_init_ipc", "tmac_hip_comm_export", "tmac_hip_comm_connect", "tmac_hip_comm_status",
                 "tmac_hip_ref_blob_bytes", "tmac_hip_pack_gptq_dev", "tmac_hip_pack_codes_dev", "tmac_hip_register_weights_gptq_dev",
                 "tmac_hip_register_weights_codes_dev",
+                "tmac_hip_absmean_dev", "tmac_hip_pack_absmean_dev", "tmac_hip_register_weights_absmean_dev",
                 "tmac_hip_kperm_from_gidx_dev", "tmac_hip_kperm_info", "tmac_hip_kperm_read", "tmac_hip_kperm_free", "tmac_hip_weights_kperm_id",
                 "tmac_hip_pack_gptq_perm_dev", "tmac_hip_pack_codes_perm_dev", "tmac_hip_register_weights_gptq_perm_dev",
                 "tmac_hip_register_weights_codes_perm_dev", "tmac_hip_preprocessor_perm_dev",

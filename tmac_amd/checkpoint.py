@@ -14,18 +14,22 @@ Refused, naming the tensor: act-order checkpoints (``desc_act``, as the referenc
 ``act_order=True``: each layer's ``.g_idx`` (int32 [K], required then) becomes the K permutation its handle carries (``wrapper.KPerm``);
 one object per distinct content, so q/k/v and gate/up -- quantised against the same inputs -- share theirs and can be fused.  An identity
 g_idx registers a plain handle.
+
+BitNet b1.58 checkpoints of master weights take the same two steps: ``scan_bitnet_dir`` / ``load_bitnet_dir`` (``Weights.from_bitnet``:
+the absmean rule and the packing on the GPU), at the end of this file.
 """
 import json
 import os
+import re
 import struct
 from typing import Dict, List, NamedTuple, Optional, Tuple
 
 import numpy as np
 
 from . import convert
-from .binding import F16
+from .binding import F16, F32
 
-_NP = {"I32": np.int32, "F16": np.float16, "F32": np.float32}
+_NP = {"I32": np.int32, "F16": np.float16, "F32": np.float32, "BF16": np.uint16}      # BF16: its 16-bit words (numpy has no bfloat16)
 
 
 class TensorRef(NamedTuple):
@@ -164,3 +168,64 @@ def load_gptq_dir(model_dir: str, wrapper, dev_dtype=F16, act_order: bool = Fals
             kp = perms[key]
         out[L.name] = wrapper.register_gptq(np.array(read_tensor(L.qweight)), np.array(read_tensor(L.scales)), qz, cfg, scan.gptq_v2, dev_dtype, g_idx=kp)
     return out
+
+
+# ---- BitNet b1.58 checkpoints of master weights ------------------------------------------------------------------------------------------
+class BitnetLayer(NamedTuple):
+    name: str               # the layer: "<name>.weight" without its suffix
+    weight: TensorRef       # F32, F16 or BF16 [Mw][K]
+    Mw: int
+    K: int
+
+
+class BitnetScan(NamedTuple):
+    layers: List[BitnetLayer]
+    weight_bits: int
+
+
+_BITNET_LAYER = re.compile(r"^model\.layers\..*_proj\.weight$")
+
+
+def scan_bitnet_dir(model_dir: str) -> BitnetScan:
+    """The linear layers of a BitNet b1.58 checkpoint of MASTER weights (``1bitLLM/bitnet_b1_58-3B``: fp16, bf16 or fp32 tensors, the
+    ternary levels come from the absmean rule at load time), without loading a tensor.  ``config.json`` must carry a non-zero
+    ``weight_bits`` (what ``convert.get_quantization_config`` reads); a layer is every tensor named ``model.layers.*_proj.weight`` in the
+    ``model*.safetensors`` parts, in order of first appearance -- embeddings, norms and the head are not.  Refused (RuntimeError naming
+    the tensor): another element type than F32 / F16 / BF16, a shape that is not 2-D, byte ranges that do not match the shape, and a
+    layer with a sibling ``.weight_scale`` -- a pre-packed ternary checkpoint, another format."""
+    qc = convert.get_quantization_config(model_dir)
+    if not qc["weight_bits"]:
+        raise RuntimeError("Models in {} not in BitNet format (config.json carries no weight_bits)".format(model_dir))
+    parts = sorted(f for f in os.listdir(model_dir) if f.startswith("model") and f.endswith(".safetensors"))
+    if not parts:
+        raise RuntimeError("Models in {} not in safetensors format (torch .bin checkpoints: convert them to safetensors first)".format(model_dir))
+    index: Dict[str, TensorRef] = {}
+    order: List[str] = []
+    for part in parts:
+        for name, ref in safetensors_index(os.path.join(model_dir, part)).items():
+            if name not in index and _BITNET_LAYER.match(name):
+                order.append(name)
+            index[name] = ref
+    layers = []
+    for wname in order:
+        ref = index[wname]
+        if wname + "_scale" in index:
+            raise RuntimeError("{} comes with {}_scale: a pre-packed ternary checkpoint, not master weights".format(wname, wname))
+        if ref.dtype not in ("F32", "F16", "BF16"):
+            raise RuntimeError("{} has dtype {}: F32, F16 or BF16 expected".format(wname, ref.dtype))
+        if len(ref.shape) != 2:
+            raise RuntimeError("{} has shape {}: a 2-D tensor expected".format(wname, ref.shape))
+        if (ref.end - ref.begin) != int(np.prod(ref.shape)) * np.dtype(_NP[ref.dtype]).itemsize:
+            raise RuntimeError("{}: shape {} does not match its {} bytes".format(wname, ref.shape, ref.end - ref.begin))
+        layers.append(BitnetLayer(wname[:-len(".weight")], ref, ref.shape[0], ref.shape[1]))
+    if not layers:
+        raise RuntimeError("Models in {} hold no model.layers.*_proj.weight tensor".format(model_dir))
+    return BitnetScan(layers, int(qc["weight_bits"]))
+
+
+def load_bitnet_dir(model_dir: str, wrapper, dev_dtype=F32, eps: float = 1e-5) -> Dict[str, "object"]:
+    """{layer name: Weights} for every layer ``scan_bitnet_dir`` finds: the master weights are uploaded as they lie in the file -- BF16
+    as its 16-bit words, no conversion on the host -- and quantised (absmean, one scale per matrix) and packed on the GPU
+    (``wrapper.register_bitnet``)."""
+    scan = scan_bitnet_dir(model_dir)
+    return {L.name: wrapper.register_bitnet(np.array(read_tensor(L.weight)), None, 1, eps, None, dev_dtype) for L in scan.layers}

@@ -158,6 +158,42 @@ def unpack_gptq(qweight: np.ndarray, scales: np.ndarray, qzeros: np.ndarray, gpt
     return np.ascontiguousarray(w), sc, (z - (2 ** (bits - 1))) * sc, bits, gs
 
 
+def bf16_bits_to_f32(bits: np.ndarray) -> np.ndarray:
+    """uint16 bf16 bit patterns -> float32, exactly (the bits shifted left by 16; numpy has no bfloat16)"""
+    return (np.ascontiguousarray(bits, np.uint16).astype(np.uint32) << np.uint32(16)).view(np.float32)
+
+
+def bitnet_absmean_quant(w: np.ndarray, m_groups: int = 1, eps: float = 1e-5, scale=None) -> Tuple[np.ndarray, np.ndarray]:
+    """BitNet b1.58 master weights [Mw][K] -> (levels uint8 [Mw][K] in {1, 2, 3}, scales float32 [m_groups]) by the absmean rule of the
+    paper and of the checkpoint authors' modelling code (``1 / mean|W|.clamp(min=1e-5)``, round, clamp to [-1, 1]): the host reference
+    of ``tmac_hip_pack_absmean_dev`` (include/tmac_hip.h states the rule operation by operation).  ``w``: float32, float16, or uint16
+    holding bf16 bit patterns.  One scale per block of Mw / m_groups rows: ``max(float32(mean |w|), eps)`` with the mean in float64, or
+    ``scale`` (a float or [m_groups] values) as it is.  The element-wise part is float32: ``rint(w * (1 / s))`` -- halves to even --
+    clamped to [-1, 1], a NaN product 0; level = that + 2, so ``w_real = (level - 2) * s``."""
+    w = np.asarray(w)
+    if w.dtype == np.uint16:
+        w = bf16_bits_to_f32(w)
+    elif w.dtype not in (np.float32, np.float16):
+        raise TypeError("w must be float32, float16 or uint16 (bf16 bit patterns)")
+    if w.ndim != 2 or m_groups < 1 or w.shape[0] % m_groups:
+        raise ValueError("w is [Mw][K] with Mw a multiple of m_groups >= 1")
+    Mw, K = w.shape
+    eps = np.float32(eps)
+    if not np.isfinite(eps) or not eps > 0:
+        raise ValueError("eps must be finite and > 0")
+    if scale is None:
+        with np.errstate(invalid="ignore", over="ignore"):
+            gamma = np.abs(w.astype(np.float64)).reshape(m_groups, -1).sum(axis=1) / float(Mw // m_groups * K)
+            s = np.fmax(gamma.astype(np.float32), eps)               # fmaxf: a NaN mean gives eps
+    else:
+        s = np.broadcast_to(np.asarray(scale, np.float32).reshape(-1), (m_groups,)).copy()
+    with np.errstate(invalid="ignore", over="ignore", divide="ignore"):
+        inv = np.float32(1.0) / s                                    # float32 / float32, correctly rounded
+        q = w.astype(np.float32).reshape(m_groups, -1) * inv[:, None]
+        t = np.where(np.isnan(q), np.float32(0.0), np.clip(np.rint(q), np.float32(-1.0), np.float32(1.0)))
+    return (t.astype(np.int8) + 2).astype(np.uint8).reshape(Mw, K), s.astype(np.float32)
+
+
 def kernel_name(M_bits: int, K: int, N: int, bits: int) -> str:
     return f"qgemm_lut_t1_int8_m{M_bits}_k{K}_n{N}_b{bits}"
 

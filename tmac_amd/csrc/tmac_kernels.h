@@ -155,6 +155,13 @@ hipError_t launch_pack_gptq(const void* qweight, const void* scales, const void*
                             Dtype out_dt, const Shape& s, hipStream_t st, const int32_t* perm = nullptr);
 hipError_t launch_pack_codes(const void* codes, const void* scales, const void* zeros, Dtype sz_dt, void* A_out, void* S_out, Dtype out_dt,
                              const Shape& s, hipStream_t st, const int32_t* perm = nullptr);
+// BitNet master weights W [Mw][K] (src: tmac_src_dtype_t; 16-byte aligned, K a multiple of 4, Mw of m_groups).  launch_absmean: the fp32
+// scale of each of the m_groups row blocks, fmaxf(mean |w|, eps), through `partials` (absmean_partial_count doubles of scratch).
+// launch_pack_dense: bits = 2, unified scales -- the levels of the absmean rule under `scales` (fp32 [m_groups], all > 0) straight into
+// A_out, and the scales into S_out as out_dt.
+size_t absmean_partial_count(int Mw, int K, int m_groups);
+hipError_t launch_absmean(const void* W, int src, int Mw, int K, int m_groups, float eps, double* partials, float* scales_out, hipStream_t st);
+hipError_t launch_pack_dense(const void* W, int src, const float* scales, void* A_out, void* S_out, Dtype out_dt, const Shape& s, hipStream_t st);
 hipError_t launch_preprocess(const void* B, Dtype act_dt, int8_t* qlut_ref, void* qlut_dev, void* qlut_lds, float* lut_scales,
                              float* lut_biases, int K, int N, int ags, size_t qdev_u4_per_row, hipStream_t st);
 // all-gather over IPC-mapped windows (tmac_comm.cpp, transport "ipc"): workgroup p of `world` handles rank p's part

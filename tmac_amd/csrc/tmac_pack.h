@@ -3,7 +3,8 @@
 // GPTQ tensors or plain codes -> the reference's bit-interleaved blob (python/t_mac/weights.py:57-87; closed form in
 // tmac_amd/weights.py).  Everything here is a pure function of integers: tests/cpp/pack_main.cc compiles this header with plain g++
 // and packs whole matrices through it, byte for byte against tmac_amd/weights.py:preprocess_weights (tests/test_pack_cpu.py); the
-// kernels call the same functions.
+// kernels call the same functions.  The one piece of floating point: the BitNet absmean rule (master weights -> ternary levels), shared
+// the same way with tests/cpp/pack_dense_main.cc.
 //
 //   M-space row     r    = (o / 8) * 8 * bits + p * 8 + o % 8                                (o: weight row, p: bit plane)
 //   nibble(r, t)         = sum_ig bit_p(w[o][4 t + ig]) << ig
@@ -12,6 +13,7 @@
 //   scale(o, sg, which)  = ((tile * SG + sg) * (rpt / 8) + ol / 8) * (8 | 16) + which * 8 + ol % 8,   rpt = bm / bits, tile = o / rpt, ol = o % rpt
 //                          (which: 0 scale, 1 zero; 16 per octet with zero points)
 #pragma once
+#include <math.h>
 #include <stddef.h>
 #include <stdint.h>
 
@@ -75,6 +77,56 @@ TMAC_PACK_HD uint32_t codes_four(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t
 // stores z - 1).  The zero itself is multiplier * scale, rounded ONCE to the scales' dtype: the fp32 product of an fp16 scale and this
 // small integer is exact, so one conversion to fp16 gives numpy's fp16 product (overflow to infinity included).
 TMAC_PACK_HD float gptq_zero_multiplier(uint32_t z, int v1, int bits) { return (float)((int)z + (v1 ? 1 : 0) - (1 << (bits - 1))); }
+
+// ---- BitNet b1.58: master weights -> ternary levels (the absmean rule) -----------------------------------------------
+// A row block of R = Mw / m_groups rows has ONE scale:
+//   gamma = fp32(sum |fp64(w)| / (R K))     the sum in fp64, in an order (Mw, K, m_groups) alone decide: absmean_chunks, k_absmean
+//   s     = fmaxf(gamma, eps)               the unified scale the blob stores
+//   level = absmean_level(w, 1 / s)         {-1, 0, 1} + 2: levels 1, 2, 3 of the 2-bit format, w_real = (level - 2) s; level 0 unused
+// Every step is one correctly rounded fp32 operation, written the same for the device and for plain g++ (tests/cpp/pack_dense_main.cc);
+// the conversions of fp16 and bf16 masters to fp32, and of |w| to fp64, are exact.
+// Non-finite masters: an infinity makes gamma, and so s, +infinity and 1 / s zero -- every finite master of the block then quantises
+// to 0 and the infinities themselves (inf * 0 is NaN) too; a NaN makes gamma NaN, which fmaxf drops: s = eps.  Neither changes an address.
+enum { SRC_F32 = 0, SRC_F16 = 1, SRC_BF16 = 2 };       // tmac_src_dtype_t
+
+// fp64 reduction, stage A: a workgroup sums one chunk of ABSMEAN_CHUNK consecutive elements of a row block (the block's last chunk may be
+// short); stage B adds a block's chunk sums in index order.  A function of the block's element count alone.
+constexpr int ABSMEAN_THREADS = 256;
+constexpr int ABSMEAN_VEC = 4;                          // elements per load: 16 bytes of fp32, 8 bytes of fp16 / bf16
+constexpr int ABSMEAN_STEPS = 16;                       // loads per thread
+constexpr size_t ABSMEAN_CHUNK = (size_t)ABSMEAN_THREADS * ABSMEAN_VEC * ABSMEAN_STEPS;
+TMAC_PACK_HD size_t absmean_chunks(size_t block_elems) { return (block_elems + ABSMEAN_CHUNK - 1) / ABSMEAN_CHUNK; }
+
+TMAC_PACK_HD float bf16_bits_to_f32(uint16_t h) {
+    const uint32_t x = (uint32_t)h << 16;
+    float f;
+    __builtin_memcpy(&f, &x, 4);
+    return f;
+}
+// sum: the block's fp64 sum of |w|; count: its R * K elements
+TMAC_PACK_HD float absmean_scale(double sum, double count, float eps) { return fmaxf((float)(sum / count), eps); }
+TMAC_PACK_HD float absmean_inv(float s) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    return __fdiv_rn(1.0f, s);
+#else
+    return 1.0f / s;
+#endif
+}
+TMAC_PACK_HD uint32_t absmean_level(float w, float inv) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    const float q = __fmul_rn(w, inv);
+#else
+    const float q = w * inv;
+#endif
+    // round half to even (rintf in the default rounding mode), clamp to [-1, 1].  A NaN -- a NaN master, or an infinite one times a zero
+    // inverse -- is 0: said here, because fmaxf / fminf would turn it into -1.
+    const float t = q != q ? 0.0f : fminf(fmaxf(rintf(q), -1.0f), 1.0f);
+    return (uint32_t)((int)t + 2);
+}
+// four masters of one table -> the `four` codes_nibble takes
+TMAC_PACK_HD uint32_t absmean_four(float w0, float w1, float w2, float w3, float inv) {
+    return codes_four(absmean_level(w0, inv), absmean_level(w1, inv), absmean_level(w2, inv), absmean_level(w3, inv));
+}
 
 #if defined(__HIPCC__)
 TMAC_PACK_HD float round_to_f16(float v) { return __half2float(__float2half_rn(v)); }

@@ -11,6 +11,8 @@
 // Tails (Mw not a multiple of 64, K / 4 not a multiple of 64) are guarded on both sides: nothing outside the inputs is loaded, nothing
 // outside the blob is stored.  No atomics, no read-modify-write.
 // Scales: one thread per (scale group, 8 weight rows) writes the 8 scales (and 8 zeros) of that octet as 16-byte stores.
+// BitNet master weights (fp32 / fp16 / bf16 [Mw][K]): the scale of each row block by a two-stage fp64 reduction (k_absmean,
+// k_absmean_scales), then the codes kernel with a stage 1 that quantises four masters per lane (k_pack_dense_weights).
 #include <hip/hip_fp16.h>
 #include <hip/hip_runtime.h>
 
@@ -186,6 +188,103 @@ __global__ __launch_bounds__(PACK_THREADS) void k_pack_codes_weights_perm(const 
     pack_store_tile<BITS>(lds, A_out, Mw, T, bm, kfactor);
 }
 
+// ---- BitNet master weights: W [Mw][K] in fp32, fp16 or bf16 -> levels -> the 2-bit blob (the absmean rule: tmac_pack.h) -------------------
+// four masters of consecutive k (e: element index, a multiple of 4) as fp32, exactly: one 16-byte load of fp32, one 8-byte load of fp16 / bf16
+template <int SRC>
+__device__ __forceinline__ void load_masters(const void* __restrict__ W, size_t e, float (&w)[4]) {
+    if constexpr (SRC == pk::SRC_F32) {
+        const float4 v = *reinterpret_cast<const float4*>(static_cast<const float*>(W) + e);
+        w[0] = v.x; w[1] = v.y; w[2] = v.z; w[3] = v.w;
+    } else {
+        const uint2 v = *reinterpret_cast<const uint2*>(static_cast<const uint16_t*>(W) + e);
+        const uint16_t h[4] = {(uint16_t)v.x, (uint16_t)(v.x >> 16), (uint16_t)v.y, (uint16_t)(v.y >> 16)};
+#pragma unroll
+        for (int i = 0; i < 4; ++i) w[i] = SRC == pk::SRC_F16 ? __half2float(__ushort_as_half(h[i])) : pk::bf16_bits_to_f32(h[i]);
+    }
+}
+
+// The scale, stage A: workgroup (row block g, chunk c) sums |w| over elements [c ABSMEAN_CHUNK, (c + 1) ABSMEAN_CHUNK) of the block -- a
+// row block is block_elems = (Mw / m_groups) K consecutive elements, a multiple of 4 -- in fp64 into partials[g chunks + c].  A lane adds
+// its ABSMEAN_STEPS loads in order, the 64 lanes of a wave meet in a xor butterfly (both partners form the same sum: addition commutes),
+// the waves are added in index order.  No atomics: the bits depend on (block_elems, the data) alone.
+template <int SRC>
+__global__ __launch_bounds__(pk::ABSMEAN_THREADS) void k_absmean(const void* __restrict__ W, double* __restrict__ partials, size_t block_elems, unsigned chunks) {
+    __shared__ double wave_sum[pk::ABSMEAN_THREADS / 64];
+    const unsigned g = blockIdx.x / chunks, c = blockIdx.x % chunks;
+    const size_t base = (size_t)g * block_elems, c0 = (size_t)c * pk::ABSMEAN_CHUNK;
+    double acc = 0.0;
+#pragma unroll 4
+    for (int i = 0; i < pk::ABSMEAN_STEPS; ++i) {
+        const size_t e = c0 + ((size_t)i * pk::ABSMEAN_THREADS + threadIdx.x) * pk::ABSMEAN_VEC;
+        if (e < block_elems) {
+            float w[4];
+            load_masters<SRC>(W, base + e, w);
+#pragma unroll
+            for (int j = 0; j < 4; ++j) acc += (double)fabsf(w[j]);
+        }
+    }
+#pragma unroll
+    for (int off = 32; off >= 1; off >>= 1) acc += __shfl_xor(acc, off);
+    if (threadIdx.x % 64 == 0) wave_sum[threadIdx.x / 64] = acc;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        double sum = wave_sum[0];
+#pragma unroll
+        for (int v = 1; v < pk::ABSMEAN_THREADS / 64; ++v) sum += wave_sum[v];
+        partials[blockIdx.x] = sum;
+    }
+}
+
+// stage B: one workgroup per row block adds the block's chunk sums in index order (256 at a time through LDS, added by thread 0) and
+// writes s = fmaxf(fp32(sum / count), eps)
+__global__ __launch_bounds__(256) void k_absmean_scales(const double* __restrict__ partials, unsigned chunks, double count, float eps, float* __restrict__ scales_out) {
+    __shared__ double tile[256];
+    const double* p = partials + (size_t)blockIdx.x * chunks;
+    double sum = 0.0;
+    for (unsigned c0 = 0; c0 < chunks; c0 += 256) {
+        const unsigned n = chunks - c0 < 256u ? chunks - c0 : 256u;
+        if (threadIdx.x < n) tile[threadIdx.x] = p[c0 + threadIdx.x];
+        __syncthreads();
+        if (threadIdx.x == 0)
+            for (unsigned i = 0; i < n; ++i) sum += tile[i];
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) scales_out[blockIdx.x] = pk::absmean_scale(sum, count, eps);
+}
+
+// k_pack_codes_weights<2> with another stage 1: the lane that took the four code bytes of a table takes its four masters and quantises
+// them (pk::absmean_four) into the same `four`; no [Mw][K] code tensor exists anywhere.  scales: fp32 [Mw / rows_per_scale], the s of each
+// row block.  A wave's step is one weight row, so the row block's scale is one scalar load per weight row.
+template <int SRC>
+__global__ __launch_bounds__(PACK_THREADS) void k_pack_dense_weights(const void* __restrict__ W, const float* __restrict__ scales, int rows_per_scale,
+                                                                     uint8_t* __restrict__ A_out, int Mw, int K, int bm, int kfactor) {
+    constexpr int BITS = 2;
+    __shared__ __attribute__((aligned(16))) uint8_t lds[PACK_ROWS * BITS * PACK_STRIDE];
+    const int T = K / 4;
+    const int o0 = blockIdx.y * PACK_ROWS, t0 = blockIdx.x * PACK_TABLES;
+    for (int idx = threadIdx.x; idx < PACK_ROWS * PACK_TABLES; idx += PACK_THREADS) {
+        const int ol = idx / PACK_TABLES, tl = idx % PACK_TABLES;
+        const int o = o0 + ol, t = t0 + tl;
+        uint32_t four = 0;
+        if (o < Mw && t < T) {
+            const float inv = pk::absmean_inv(scales[__builtin_amdgcn_readfirstlane(o / rows_per_scale)]);     // o is the wave's
+            float w[4];
+            load_masters<SRC>(W, (size_t)o * K + 4 * (size_t)t, w);      // K is a multiple of 4
+            four = pk::absmean_four(w[0], w[1], w[2], w[3], inv);
+        }
+#pragma unroll
+        for (int p = 0; p < BITS; ++p) {
+            uint32_t v = pk::codes_nibble(four, p) << (4 * (tl % 8));
+            v |= __shfl_xor(v, 1);
+            v |= __shfl_xor(v, 2);
+            v |= __shfl_xor(v, 4);
+            if (tl % 8 == 0) *reinterpret_cast<uint32_t*>(lds + lds_row(p, ol) * PACK_STRIDE + tl / 2) = v;
+        }
+    }
+    __syncthreads();
+    pack_store_tile<BITS>(lds, A_out, Mw, T, bm, kfactor);
+}
+
 // ---- scales -------------------------------------------------------------------------------------------------------------------------
 // n contiguous elements (a multiple of 16 bytes, 16-byte aligned on both sides) as 16-byte accesses
 template <class T, int N>
@@ -343,6 +442,48 @@ hipError_t launch_pack_codes(const void* codes, const void* scales, const void* 
         using OT = decltype(out_tag);
         hipLaunchKernelGGL((k_pack_codes_scales<ST, OT>), dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, (const ST*)scales, (const ST*)zeros, (OT*)S_out,
                            s.Mw, SG, s.bits, s.bm);
+    });
+    return hipGetLastError();
+}
+
+// ---- BitNet master weights ----------------------------------------------------------------------------------------------------------
+size_t absmean_partial_count(int Mw, int K, int m_groups) { return pk::absmean_chunks((size_t)(Mw / m_groups) * K) * (size_t)m_groups; }
+
+hipError_t launch_absmean(const void* W, int src, int Mw, int K, int m_groups, float eps, double* partials, float* scales_out, hipStream_t st) {
+    const size_t block_elems = (size_t)(Mw / m_groups) * K, chunks = pk::absmean_chunks(block_elems), total = chunks * (size_t)m_groups;
+    if (total > (size_t)INT32_MAX) return hipErrorInvalidValue;
+    const dim3 g((unsigned)total), b(pk::ABSMEAN_THREADS);
+    switch (src) {
+        case pk::SRC_F32: hipLaunchKernelGGL(k_absmean<pk::SRC_F32>, g, b, 0, st, W, partials, block_elems, (unsigned)chunks); break;
+        case pk::SRC_F16: hipLaunchKernelGGL(k_absmean<pk::SRC_F16>, g, b, 0, st, W, partials, block_elems, (unsigned)chunks); break;
+        case pk::SRC_BF16: hipLaunchKernelGGL(k_absmean<pk::SRC_BF16>, g, b, 0, st, W, partials, block_elems, (unsigned)chunks); break;
+        default: return hipErrorInvalidValue;
+    }
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(k_absmean_scales, dim3((unsigned)m_groups), dim3(256), 0, st, (const double*)partials, (unsigned)chunks, (double)block_elems, eps,
+                       scales_out);
+    return hipGetLastError();
+}
+
+hipError_t launch_pack_dense(const void* W, int src, const float* scales, void* A_out, void* S_out, Dtype out_dt, const Shape& s, hipStream_t st) {
+    if (s.bits != 2 || s.m_groups < 1) return hipErrorInvalidValue;
+    const dim3 g = weight_grid(s), b(PACK_THREADS);
+    const int R = s.Mw / s.m_groups;
+    uint8_t* A = (uint8_t*)A_out;
+    switch (src) {
+        case pk::SRC_F32: hipLaunchKernelGGL(k_pack_dense_weights<pk::SRC_F32>, g, b, 0, st, W, scales, R, A, s.Mw, s.K, s.bm, s.kfactor); break;
+        case pk::SRC_F16: hipLaunchKernelGGL(k_pack_dense_weights<pk::SRC_F16>, g, b, 0, st, W, scales, R, A, s.Mw, s.K, s.bm, s.kfactor); break;
+        case pk::SRC_BF16: hipLaunchKernelGGL(k_pack_dense_weights<pk::SRC_BF16>, g, b, 0, st, W, scales, R, A, s.Mw, s.K, s.bm, s.kfactor); break;
+        default: return hipErrorInvalidValue;
+    }
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return e;
+    const size_t n = (size_t)s.m_groups;      // the unified scales into the blob: the copy of the codes form
+    by_dtypes(F32, out_dt, [&](auto in_tag, auto out_tag) {
+        using ST = decltype(in_tag);
+        using OT = decltype(out_tag);
+        hipLaunchKernelGGL((k_pack_copy<ST, OT>), dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, (const ST*)scales, (OT*)S_out, n);
     });
     return hipGetLastError();
 }

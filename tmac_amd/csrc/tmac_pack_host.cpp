@@ -1,5 +1,8 @@
 // tmac_pack_host.cpp — the entry points in front of the pack kernels (tmac_pack.hip): GPTQ tensors or plain codes, in device memory, ->
 // the reference blob (tmac_hip_pack_*_dev) or straight to a registered handle (tmac_hip_register_weights_*_dev, through register_impl).
+// BitNet master weights (fp32 / fp16 / bf16) take the same two ways through the absmean rule (tmac_hip_*_absmean_dev).
+#include <cmath>
+
 #include "tmac_host.h"
 
 using namespace tmac_host;
@@ -99,7 +102,112 @@ int32_t check_perm(const Shape& s, const tmac_hip_kperm* perm) {
 }
 bool perm_is_plain(const tmac_hip_kperm* perm) { return !perm || !perm->d || perm->d->h.identity; }
 
+// ---- BitNet master weights (the absmean rule: tmac_pack.h) -------------------------------------------------------------------------------
+struct DenseIn { const void* W; int src; const float* scales_in; float eps; };
+
+// The argument rules the three entry points share, in front of any shape rule: NULL required pointers, the source dtype, eps, the row
+// blocks.  (m_groups is the call's own argument for the reduction alone and cfg->m_groups otherwise.)
+int32_t masters_check(const PackArg* args, int nargs, int src_dtype, float eps, int Mw, int m_groups) {
+    for (int i = 0; i < nargs; ++i)
+        if (args[i].required && !args[i].p) return fail(TMAC_HIP_E_ARG, "%s is NULL", args[i].name);
+    if (src_dtype != TMAC_SRC_F32 && src_dtype != TMAC_SRC_F16 && src_dtype != TMAC_SRC_BF16)
+        return fail(TMAC_HIP_E_ARG, "src_dtype must be TMAC_SRC_F32, TMAC_SRC_F16 or TMAC_SRC_BF16");
+    if (!std::isfinite(eps) || !(eps > 0.0f)) return fail(TMAC_HIP_E_ARG, "eps must be finite and > 0");
+    if (m_groups < 1) return fail(TMAC_HIP_E_ARG, "m_groups = %d: master weights take unified scales (per-group scales: register codes or GPTQ tensors)", m_groups);
+    if (Mw % m_groups) return fail(TMAC_HIP_E_ARG, "Mw=%d is no whole number of m_groups=%d row blocks", Mw, m_groups);
+    return TMAC_HIP_OK;
+}
+int32_t aligned_check(const PackArg* args, int nargs) {
+    for (int i = 0; i < nargs; ++i)
+        if (args[i].p && misaligned(args[i].p, PACK_ALIGN)) return fail(TMAC_HIP_E_ARG, "%s is not %zu-byte aligned", args[i].name, PACK_ALIGN);
+    return TMAC_HIP_OK;
+}
+// ... and of the two that pack: the rules above, then make_shape's own refusals (bits = 2), then alignment
+int32_t check_dense(Shape& s, const DenseIn& in, const void* A_out, const void* S_out, bool outs, int Mw, int K, const tmac_kcfg* cfg, tmac_dtype_t ref_float) {
+    if (!cfg) return fail(TMAC_HIP_E_ARG, "null kcfg");
+    const PackArg args[] = {{"W_dev", in.W, true}, {"scales_in_dev", in.scales_in, false}, {"A_ref_out", A_out, outs}, {"scales_ref_out", S_out, outs}};
+    int32_t rc = masters_check(args, 4, in.src, in.eps, Mw, cfg->m_groups);
+    if (rc) return rc;
+    if (ref_float != TMAC_F32 && ref_float != TMAC_F16) return fail(TMAC_HIP_E_ARG, "host_float must be TMAC_F32 or TMAC_F16");
+    rc = make_shape(s, Mw, K, 2, cfg);
+    return rc ? rc : aligned_check(args, 4);
+}
+
+// The launches: the reduction into scratch of our own unless the caller brought the scales, then the pack.  With a computed scale the
+// stream is waited for before the scratch goes.
+int32_t launch(const Shape& s, const DenseIn& in, void* A_out, void* S_out, tmac_dtype_t ref_float, hipStream_t st) {
+    const float* scales = in.scales_in;
+    DevBuf scratch;     // [partials: doubles][scales: m_groups floats]
+    hipError_t e = hipSuccess;
+    if (!scales) {
+        const size_t np = absmean_partial_count(s.Mw, s.K, s.m_groups);
+        HIP_TRY(scratch.alloc(sizeof(double) * np + sizeof(float) * (size_t)s.m_groups));
+        float* sc = reinterpret_cast<float*>(scratch.as<double>() + np);
+        e = launch_absmean(in.W, in.src, s.Mw, s.K, s.m_groups, in.eps, scratch.as<double>(), sc, st);
+        scales = sc;
+    }
+    if (e == hipSuccess) e = launch_pack_dense(in.W, in.src, scales, A_out, S_out, (Dtype)ref_float, s, st);
+    if (e != hipSuccess) return fail(TMAC_HIP_E_RUNTIME, "pack_absmean: %s", hipGetErrorString(e));
+    if (scratch.p) HIP_TRY(hipStreamSynchronize(st));
+    return TMAC_HIP_OK;
+}
+
 }  // namespace
+
+extern "C" int32_t tmac_hip_absmean_dev(const void* W_dev, tmac_src_dtype_t src_dtype, int Mw, int K, int m_groups, float eps, float* scales_out_dev,
+                                        void* stream) {
+    const PackArg args[] = {{"W_dev", W_dev, true}, {"scales_out_dev", scales_out_dev, true}};
+    int32_t rc = masters_check(args, 2, src_dtype, eps, Mw, m_groups);
+    if (rc) return rc;
+    if (Mw <= 0 || K <= 0 || K % 4) return fail(TMAC_HIP_E_ARG, "Mw=%d and K=%d must be positive, K a multiple of 4", Mw, K);
+    rc = aligned_check(args, 2);
+    if (rc) return rc;
+    rc = ensure_device();
+    if (rc) return rc;
+    rc = defer_barrier();
+    if (rc) return rc;
+    hipStream_t st = (hipStream_t)stream;
+    DevBuf partials;
+    HIP_TRY(partials.alloc(sizeof(double) * absmean_partial_count(Mw, K, m_groups)));
+    const hipError_t e = launch_absmean(W_dev, src_dtype, Mw, K, m_groups, eps, partials.as<double>(), scales_out_dev, st);
+    if (e != hipSuccess) return fail(TMAC_HIP_E_RUNTIME, "absmean: %s", hipGetErrorString(e));
+    HIP_TRY(hipStreamSynchronize(st));      // the scratch goes with this call
+    return TMAC_HIP_OK;
+}
+
+extern "C" int32_t tmac_hip_pack_absmean_dev(const void* W_dev, tmac_src_dtype_t src_dtype, const float* scales_in_dev, float eps, int Mw, int K,
+                                             const tmac_kcfg* cfg, void* A_ref_out, void* scales_ref_out, tmac_dtype_t host_float, void* stream) {
+    const DenseIn in{W_dev, src_dtype, scales_in_dev, eps};
+    Shape s;
+    int32_t rc = check_dense(s, in, A_ref_out, scales_ref_out, true, Mw, K, cfg, host_float);
+    if (rc) return rc;
+    rc = ensure_device();
+    if (rc) return rc;
+    rc = defer_barrier();
+    return rc ? rc : launch(s, in, A_ref_out, scales_ref_out, host_float, (hipStream_t)stream);
+}
+
+extern "C" int32_t tmac_hip_register_weights_absmean_dev(tmac_hip_weights** out, const void* W_dev, tmac_src_dtype_t src_dtype, const float* scales_in_dev,
+                                                         float eps, int Mw, int K, const tmac_kcfg* cfg, tmac_dtype_t host_float, tmac_dtype_t dev_float,
+                                                         void* stream) {
+    if (!out) return fail(TMAC_HIP_E_ARG, "out is NULL");
+    const DenseIn in{W_dev, src_dtype, scales_in_dev, eps};
+    Shape s;
+    int32_t rc = check_dense(s, in, nullptr, nullptr, false, Mw, K, cfg, host_float);
+    if (rc) return rc;
+    rc = ensure_device();
+    if (rc) return rc;
+    rc = defer_barrier();       // W_dev / scales_in_dev may have been written by queued work
+    if (rc) return rc;
+    hipStream_t st = (hipStream_t)stream;
+    DevBuf dA, dS;      // as register_from: ours on every return path
+    HIP_TRY(dA.alloc(ref_weight_bytes(s)));
+    HIP_TRY(dS.alloc(ref_scale_elems(s) * dt_size((Dtype)host_float)));
+    rc = launch(s, in, dA.p, dS.p, host_float, st);
+    if (rc == TMAC_HIP_OK) rc = register_impl(out, dA.p, dS.p, true, Mw, K, 2, cfg, host_float, dev_float, stream);
+    if (rc != TMAC_HIP_OK) (void)hipStreamSynchronize(st);
+    return rc;
+}
 
 // ---- the K permutation object (tmac_kperm.h: the rules; here: the device copies and the lifetime) -----------------------------------------
 extern "C" int32_t tmac_hip_kperm_from_gidx_dev(const int32_t* g_idx_dev, int K, int group_size, tmac_hip_kperm** out, void* stream) {

@@ -202,6 +202,67 @@ def pack_codes(codes, scales, zeros, bits: int, cfg: Optional[KCfg] = None, ref_
     return A, S
 
 
+_SRC_CODES = {"float32": B.SRC_F32, "float16": B.SRC_F16, "bfloat16": B.SRC_BF16}
+
+
+def _masters_on_device(weight):
+    """(contiguous 2-D CUDA tensor, tmac_src_dtype_t) of BitNet master weights: a torch tensor in fp32, fp16 or bf16 (uploaded if it is
+    not on the GPU), or a numpy array uploaded as it is -- float32, float16, or uint16 holding bf16 bit patterns (numpy has no bfloat16;
+    what ``checkpoint.read_tensor`` gives for a BF16 tensor).  Nothing is converted on the host."""
+    import torch
+    if isinstance(weight, np.ndarray):
+        if weight.dtype == np.uint16:
+            weight = torch.from_numpy(np.ascontiguousarray(weight).view(np.int16)).view(torch.bfloat16)
+        elif weight.dtype in (np.float32, np.float16):
+            weight = torch.from_numpy(np.ascontiguousarray(weight))
+        else:
+            raise TypeError(f"weight must be float32, float16 or uint16 (bf16 bit patterns), not {weight.dtype}")
+    name = str(weight.dtype).replace("torch.", "")
+    if name not in _SRC_CODES:
+        raise TypeError(f"weight must be float32, float16 or bfloat16, not {name}")
+    if weight.dim() != 2:
+        raise ValueError("weight is 2-D: [Mw][K]")
+    return weight.cuda().contiguous(), _SRC_CODES[name]
+
+
+def _bitnet_args(weight, cfg, m_groups, eps, scale):
+    """device tensors, shape and configuration of a BitNet matrix.  Without a cfg: the unified-scale configuration ``from_codes`` is handed
+    for BitNet -- ``convert.default_bm``, kfactor 16, one activation group per row (act_group_size = K).  With one, its m_groups counts."""
+    from . import convert
+    w, src = _masters_on_device(weight)
+    Mw, K = int(w.shape[0]), int(w.shape[1])
+    if cfg is None:
+        cfg = KCfg.make(Mw, K, 2, convert.default_bm(2, Mw), 16, 128, K, False, int(m_groups))
+    sc = None
+    if scale is not None:
+        if isinstance(scale, (int, float)):
+            scale = np.full(max(cfg.m_groups, 1), scale, np.float32)
+        sc = _on_device(scale, "scale", ("float32",)).reshape(-1)
+        if int(sc.shape[0]) != cfg.m_groups:
+            raise ValueError(f"scale holds {int(sc.shape[0])} values: one per row block, m_groups = {cfg.m_groups}")
+    return w, src, sc, float(eps), Mw, K, cfg
+
+
+def absmean(weight, m_groups: int = 1, eps: float = 1e-5, stream=None):
+    """The BitNet absmean scales of master weights [Mw][K] (fp32 / fp16 / bf16, see ``Weights.from_bitnet``): fp32 [m_groups] on the GPU,
+    ``max(mean |w|, eps)`` per block of Mw / m_groups rows, the mean accumulated in fp64 (tmac_hip_absmean_dev)."""
+    import torch
+    w, src = _masters_on_device(weight)
+    out = torch.empty(max(int(m_groups), 1), dtype=torch.float32, device="cuda")
+    check(B.lib().tmac_hip_absmean_dev(_ptr(w), src, int(w.shape[0]), int(w.shape[1]), int(m_groups), float(eps), _ptr(out), _stream(stream)))
+    return out
+
+
+def pack_bitnet(weight, cfg: Optional[KCfg] = None, m_groups: int = 1, eps: float = 1e-5, scale=None, ref_dtype=F32, stream=None):
+    """BitNet master weights -> the reference blob of their ternary levels, on the GPU (tmac_hip_pack_absmean_dev): (A_ref uint8,
+    scales_ref) as ``pack_codes`` returns them, exactly ``weights.preprocess_weights(*convert.bitnet_absmean_quant(...))`` under the same
+    scales.  ``scale`` (a float, or fp32 [m_groups]): the scales themselves instead of the absmean."""
+    w, src, sc, eps, Mw, K, cfg = _bitnet_args(weight, cfg, m_groups, eps, scale)
+    A, S = _blob_buffers(Mw, K, 2, cfg, ref_dtype)
+    check(B.lib().tmac_hip_pack_absmean_dev(_ptr(w), src, _ptr(sc), eps, Mw, K, C.byref(cfg), _ptr(A), _ptr(S), ref_dtype, _stream(stream)))
+    return A, S
+
+
 class Weights:
     """One weight matrix resident on the GPU (tmac_hip_register_weights)."""
 
@@ -255,6 +316,21 @@ class Weights:
         self = cls._adopt(h, Mw, K, bits, cfg)
         self.kperm = kp
         return self
+
+    @classmethod
+    def from_bitnet(cls, weight, cfg: Optional[KCfg] = None, m_groups: int = 1, eps: float = 1e-5, scale=None, dev_dtype=F32,
+                    stream=None) -> "Weights":
+        """Register BitNet b1.58 master weights [Mw][K] -- a torch tensor in fp32, fp16 or bf16, or a numpy array uploaded as it is
+        (float32, float16, uint16 = bf16 bit patterns): quantised to ternary levels by the absmean rule and packed on the GPU
+        (tmac_hip_register_weights_absmean_dev; include/tmac_hip.h states the rule).  One scale per block of Mw / m_groups rows,
+        ``max(mean |w|, eps)``, or ``scale`` (a float, or fp32 [m_groups]) as it is.  The handle is the one
+        ``from_codes(levels, scales, None, 2, cfg)`` gives for ``convert.bitnet_absmean_quant``'s levels under the same scales.  Without a
+        ``cfg``: ``convert.default_bm``, kfactor 16, act_group_size = K (one activation group per row, BitNet's)."""
+        w, src, sc, eps, Mw, K, cfg = _bitnet_args(weight, cfg, m_groups, eps, scale)
+        h = C.c_void_p()
+        check(B.lib().tmac_hip_register_weights_absmean_dev(C.byref(h), _ptr(w), src, _ptr(sc), eps, Mw, K, C.byref(cfg), F32, dev_dtype,
+                                                            _stream(stream)))
+        return cls._adopt(h, Mw, K, 2, cfg)
 
     def __init__(self, A_ref, scales_ref, Mw: int, K: int, bits: int, cfg: KCfg, scales_dtype=F32, dev_dtype=F32,
                  on_device: bool = False, stream=None):
@@ -591,6 +667,12 @@ class TMACGeMMWrapper:
     def register_codes(self, codes, scales, zeros, bits: int, cfg: Optional[KCfg] = None, dev_dtype=F16, stream=None, g_idx=None) -> Weights:
         """``Weights.from_codes`` with this wrapper's act_group_size"""
         return Weights.from_codes(codes, scales, zeros, bits, cfg, dev_dtype, self._act_group_size, stream, g_idx)
+
+    def register_bitnet(self, weight, cfg: Optional[KCfg] = None, m_groups: int = 1, eps: float = 1e-5, scale=None, dev_dtype=F32,
+                        stream=None) -> Weights:
+        """``Weights.from_bitnet``: BitNet master weights (fp32 / fp16 / bf16) -> handle, quantised and packed on the GPU.  (Unified
+        scales have one activation group per row: the wrapper's act_group_size plays no part.)"""
+        return Weights.from_bitnet(weight, cfg, m_groups, eps, scale, dev_dtype, stream)
 
     def llama_cpp_init(self, B_dev, M: int, K: int, N: int, bits: int, act_group_size: Optional[int] = None,
                        act_dtype: Optional[int] = None, stream=None, kperm: Optional[KPerm] = None) -> None:

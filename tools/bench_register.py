@@ -11,7 +11,8 @@ llama-2-7B shapes (o, qkv, gate/up, down), W2 and W4, group size 128, seeded syn
       until each has filled a timed window of at least 0.3 s.
 No rate is required of (c): the file states the kernels' share of the copy's rate.  The one hard condition is (b) < (a) at every shape;
 the tool exits 1 when it does not hold.
-usage: bench_register.py [--out FILE] [--shapes o,qkv,gate_up,down] [--bits 2,4] [--skip-host]"""
+--bitnet: BitNet-3B master weights (fp16 / bf16, on the device) -> handle instead: see bitnet() below.
+usage: bench_register.py [--out FILE] [--shapes o,qkv,gate_up,down] [--bits 2,4] [--skip-host] | --bitnet [--out FILE]"""
 import argparse
 import ctypes as C
 import math
@@ -113,14 +114,85 @@ def pack_vs_copy(hip, qw, sc, qz, Mw, K, bits, cfg):
     return moved, moved * calls / tp / 1e9, 2 * half * calls / tc / 1e9, calls, tp, tc
 
 
+BITNET_SHAPES = {"attn": (3200, 3200), "gate_up": (8640, 3200), "down": (3200, 8640)}      # BitNet-3B (hf-bitnet-3b), (Mw, K)
+
+
+def wall_ms(fn):
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    r = fn()
+    torch.cuda.synchronize()
+    return (time.perf_counter() - t0) * 1e3, r
+
+
+def median3(fn, free=False):
+    """median of three runs after one warm-up, host-clock ms with a device synchronise on either side"""
+    ts = []
+    for i in range(4):
+        t, r = wall_ms(fn)
+        if free:
+            r.free()
+        if i:
+            ts.append(t)
+    return float(np.median(ts))
+
+
+def bitnet(out):
+    """BitNet-3B master weights -> handle, fp16 and bf16 masters ON THE DEVICE, median of three (host clock, ms):
+      (a) host route: download + convert.bitnet_absmean_quant + weights.preprocess_weights + tmac_hip_register_weights;
+      (b) Weights.from_bitnet (reduction + quantising pack + re-tile);
+      (c) Weights.from_codes on pre-made levels on the device (the existing device pack; (b) reads 2 - 4 times its input bytes, twice);
+    and (b) taken apart: the reduction alone (wrapper.absmean), the quantising pack alone (wrapper.pack_bitnet with the scale handed in),
+    the codes pack alone (wrapper.pack_codes).  No threshold: the ratios are recorded."""
+    lines = ["# tools/bench_register.py --bitnet: BitNet-3B master weights on the device -> handle; host-clock ms, median of three after a warm-up.",
+             f"# device: {torch.cuda.get_device_name(0)}; unified scale (m_groups = 1), act_group_size = K, fp32 device scales",
+             "shape    src   Mw     K     | (a) host_ms | (b) from_bitnet_ms | (c) from_codes_ms | (b)/(a)  (b)/(c) | absmean_ms  pack_given_scale_ms  pack_codes_ms"]
+    for name, (Mw, K) in BITNET_SHAPES.items():
+        cfg = KCfg.make(Mw, K, 2, convert.default_bm(2, Mw), 16, 128, K, False, 1)
+        w32 = (np.random.default_rng(Mw + K).standard_normal((Mw, K)) * 0.02).astype(np.float32)
+        for src, dt in (("fp16", torch.float16), ("bf16", torch.bfloat16)):
+            wd = torch.from_numpy(w32).cuda().to(dt)
+            torch.cuda.synchronize()
+
+            def host():
+                st = wd.view(torch.int16).cpu().numpy()
+                st = st.view(np.float16) if dt == torch.float16 else st.view(np.uint16)
+                lv, s = convert.bitnet_absmean_quant(st)
+                A, S = weights.preprocess_weights(lv, s, None, bits=2, bm=cfg.bm, kfactor=cfg.kfactor)
+                return tmac_amd.Weights(A, S, Mw, K, 2, cfg, scales_dtype=F32, dev_dtype=F32)
+            ta, h = wall_ms(host)                                    # seconds-class: one run
+            h.free()
+            tb = median3(lambda: tmac_amd.Weights.from_bitnet(wd, cfg), free=True)
+            s_dev = wrapper.absmean(wd)
+            lv, _ = convert.bitnet_absmean_quant(wd.view(torch.int16).cpu().numpy().view(np.float16 if dt == torch.float16 else np.uint16),
+                                                 scale=s_dev.cpu().numpy())
+            lvd = torch.from_numpy(lv).cuda()
+            tc = median3(lambda: tmac_amd.Weights.from_codes(lvd, s_dev, None, 2, cfg, F32), free=True)
+            t_mean = median3(lambda: wrapper.absmean(wd))
+            t_pack = median3(lambda: wrapper.pack_bitnet(wd, cfg, scale=s_dev))
+            t_codes = median3(lambda: wrapper.pack_codes(lvd, s_dev, None, 2, cfg, F32))
+            line = (f"{name:8s} {src:5s} {Mw:5d}  {K:5d} | {ta:11.1f} | {tb:18.3f} | {tc:17.3f} | {tb / ta:7.4f}  {tb / tc:7.2f} | "
+                    f"{t_mean:10.3f}  {t_pack:19.3f}  {t_codes:13.3f}")
+            print(line, flush=True)
+            lines.append(line)
+    if out:
+        os.makedirs(os.path.dirname(os.path.abspath(out)), exist_ok=True)
+        with open(out, "w") as f:
+            f.write("\n".join(lines) + "\n")
+    return 0
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--out", default="")
+    ap.add_argument("--bitnet", action="store_true", help="the BitNet-3B master-weight shapes instead: host route, from_bitnet, from_codes")
     ap.add_argument("--shapes", default="o,qkv,gate_up,down")
     ap.add_argument("--bits", default="2,4")
     ap.add_argument("--skip-host", action="store_true", help="leave (a) out (it takes seconds per shape)")
     args = ap.parse_args()
     assert torch.cuda.is_available(), "bench_register.py measures on a GPU"
+    if args.bitnet:
+        return bitnet(args.out)
     hip = hip_runtime()
     lines = ["# tools/bench_register.py: GPTQ tensors -> handle.  (a) host seconds, one run; (b) host-clock ms around upload + device-side",
              "# registration; (c) pack kernels alone, device events, bytes read + written per second, beside hipMemcpyAsync D2D of the same bytes.",
