@@ -212,6 +212,42 @@ int32_t tmac_hip_register_weights_absmean_dev(tmac_hip_weights** out, const void
                                               const float* scales_in_dev /* NULL: computed */, float eps, int Mw, int K, const tmac_kcfg* cfg,
                                               tmac_dtype_t host_float, tmac_dtype_t dev_float, void* stream);
 
+/* ---- BitNet b1.58 packed ternary checkpoints: four weight rows per byte, unpacked on the device --------------------------------
+ * A checkpoint written by the Hugging Face BitNet quantiser (quant_method "bitnet", offline mode; microsoft/bitnet-b1.58-2B-4T) holds no
+ * master weights: it holds the ternary levels, packed.  packed_dev is uint8 [Mw / 4][K], row-major.  With R4 = Mw / 4, weight row o lives in
+ * packed row o % R4, in the 2-bit field o / R4 at bit 2 (o / R4): the four row blocks of the matrix share a byte.  The stored field is
+ * v = t + 1, t in {-1, 0, 1}; the blob's 2-bit level is t + 2 = v + 1 (levels 1, 2, 3, w_real = (level - 2) s, as above).  v = 3 occurs in no
+ * well-formed file and has no level: it is packed as level 3 (t = 2 clamped to 1) and COUNTED.
+ * scales_dev: fp32 [cfg->m_groups] in device memory, the unified scale s of each block of Mw / m_groups rows, copied into the blob as
+ * host_float.  A checkpoint carries one `weight_scale`; which s it means is the caller's to say (quantization_config.linear_class:
+ * "autobitlinear" multiplies by it, s = weight_scale; "bitlinear" divides, s = 1.0f / weight_scale -- tmac_amd/convert.py:bitnet_packed_scale).
+ *   tmac_hip_pack_ternary_dev              -> the reference blob (sizes: tmac_hip_ref_blob_bytes with bits = 2).  The levels go straight into
+ *                                          A_ref_out: no [Mw][K] code tensor is written anywhere.  Where (Mw / 4) % 16 == 0 -- every matrix of
+ *                                          the 2B-4T and 3B models -- k_pack_ternary_weights_x4 reads every packed byte once and writes the four
+ *                                          output tiles it feeds; otherwise k_pack_ternary_weights, the codes kernel with an extracting stage 1,
+ *                                          reads each byte from four tiles.  invalid_count_dev (device int32; NULL: not counted): zeroed on the
+ *                                          stream, then the number of fields of value 3 is added to it, at most one atomicAdd per workgroup.
+ *                                          Asynchronous on `stream`; allocates nothing.
+ *   tmac_hip_register_weights_ternary_dev  packs into temporaries with a counter of its own, synchronises and reads the counter: non-zero is
+ *                                          TMAC_HIP_E_ARG, "packed weight holds %d fields of value 3 (no ternary level)", and no handle;
+ *                                          otherwise registers as tmac_hip_register_weights_codes_dev does.
+ * Scope: bits = 2, unified scales (cfg->m_groups >= 1, Mw a multiple of it), whatever else registration accepts for such a configuration
+ * (Mw is then a multiple of 16 and K of 32).
+ * Refusals, nothing launched and nothing written.  TMAC_HIP_E_ARG naming the argument: a NULL pointer (invalid_count_dev excepted) or any
+ * device pointer below 16-byte alignment, the counter's included; m_groups < 1 (per-group scales: register codes or GPTQ tensors);
+ * Mw % m_groups; host_float / dev_float other than TMAC_F32 / TMAC_F16.  Shape refusals are registration's own codes and messages, as in
+ * tmac_hip_pack_codes_dev.
+ * Both are ordered behind the calling thread's deferred queue: they flush it first, a refused call leaves it alone, a failed flush returns
+ * its status and launches nothing.  While a chain is being recorded both run at once and are not recorded, as registration does.
+ * tmac_hip_debug_pack_ternary_kernel: 0 (default) the read-once kernel where it applies; 1 the general form everywhere (tests, A/B).
+ * tmac_hip_reset_state puts it back to 0. */
+int32_t tmac_hip_pack_ternary_dev(const void* packed_dev, const float* scales_dev /* fp32 [m_groups] */, int Mw, int K, const tmac_kcfg* cfg,
+                                  void* A_ref_out, void* scales_ref_out, tmac_dtype_t host_float, int32_t* invalid_count_dev /* NULL: not counted */,
+                                  void* stream);
+int32_t tmac_hip_register_weights_ternary_dev(tmac_hip_weights** out, const void* packed_dev, const float* scales_dev, int Mw, int K,
+                                              const tmac_kcfg* cfg, tmac_dtype_t host_float, tmac_dtype_t dev_float, void* stream);
+int32_t tmac_hip_debug_pack_ternary_kernel(int mode);
+
 /* ---- act-order (desc_act) GPTQ matrices: the K permutation ---------------------------------------------------------------
  * An act-order matrix is a group-quantised matrix whose K axis is permuted: g_idx[k] names the group of column k.  With
  * perm = stable_argsort(g_idx) the columns q[:, perm] lie in contiguous groups of group_size, scales / qzeros are in group order already,
@@ -312,7 +348,7 @@ int32_t tmac_hip_qgemm_fused_dev(const tmac_hip_weights* const* weights, int nma
  * tmac_hip_qgemm_dev, tmac_hip_qgemm_partial_sums, tmac_hip_qgemm_fused_partial_sums, tmac_hip_chain_launch, tmac_hip_workspace_read /
  * _write, tmac_hip_debug_gemm_comb_sums / _gemm_image_read, tmac_hip_autotune_fused, tmac_hip_pack_gptq_dev / _pack_codes_dev (they write the
  * caller's blob buffers; a refused one leaves the queue alone), tmac_hip_absmean_dev / _pack_absmean_dev /
- * _register_weights_absmean_dev (the same), and tmac_hip_free_weights, tmac_hip_chain_free and
+ * _register_weights_absmean_dev (the same), tmac_hip_pack_ternary_dev / _register_weights_ternary_dev (the same), and tmac_hip_free_weights, tmac_hip_chain_free and
  * tmac_hip_cache_clear (a queued call may name what they release).  When that flush fails the entry point returns its status and launches
  * nothing of its own (the three that release still release: the handle is dead either way).  A queue belongs to a thread: freeing, from
  * another thread, weights that this thread has queued is the caller's error.

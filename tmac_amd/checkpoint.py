@@ -16,7 +16,8 @@ one object per distinct content, so q/k/v and gate/up -- quantised against the s
 g_idx registers a plain handle.
 
 BitNet b1.58 checkpoints of master weights take the same two steps: ``scan_bitnet_dir`` / ``load_bitnet_dir`` (``Weights.from_bitnet``:
-the absmean rule and the packing on the GPU), at the end of this file.
+the absmean rule and the packing on the GPU), and checkpoints of PACKED ternary weights (the Hugging Face BitNet quantiser, four weight
+rows per byte) ``scan_bitnet_packed_dir`` / ``load_bitnet_packed_dir`` (``Weights.from_bitnet_packed``), both at the end of this file.
 """
 import json
 import os
@@ -29,7 +30,7 @@ import numpy as np
 from . import convert
 from .binding import F16, F32
 
-_NP = {"I32": np.int32, "F16": np.float16, "F32": np.float32, "BF16": np.uint16}      # BF16: its 16-bit words (numpy has no bfloat16)
+_NP = {"I32": np.int32, "F16": np.float16, "F32": np.float32, "BF16": np.uint16, "U8": np.uint8}      # BF16: its 16-bit words (numpy has no bfloat16)
 
 
 class TensorRef(NamedTuple):
@@ -229,3 +230,78 @@ def load_bitnet_dir(model_dir: str, wrapper, dev_dtype=F32, eps: float = 1e-5) -
     (``wrapper.register_bitnet``)."""
     scan = scan_bitnet_dir(model_dir)
     return {L.name: wrapper.register_bitnet(np.array(read_tensor(L.weight)), None, 1, eps, None, dev_dtype) for L in scan.layers}
+
+
+# ---- BitNet b1.58 checkpoints of PACKED ternary weights (the Hugging Face BitNet quantiser, offline mode) ----------------------------------
+class BitnetPackedLayer(NamedTuple):
+    name: str               # the layer: "<name>.weight" without its suffix
+    weight: TensorRef       # U8 [Mw / 4][K]: four weight rows per byte (convert.unpack_bitnet_packed)
+    weight_scale: TensorRef # one element, BF16 / F16 / F32
+    Mw: int                 # 4 * weight.shape[0]: the file does not record it
+    K: int
+
+
+class BitnetPackedScan(NamedTuple):
+    layers: List[BitnetPackedLayer]
+    linear_class: str       # "bitlinear" | "autobitlinear": whether a layer divides or multiplies by its weight_scale
+    use_rms_norm: bool
+    rms_norm_eps: float
+    quantization_config: dict
+
+
+def scan_bitnet_packed_dir(model_dir: str) -> BitnetPackedScan:
+    """The linear layers of a PACKED ternary BitNet checkpoint (``quantization_config.quant_method == "bitnet"``, offline mode;
+    ``microsoft/bitnet-b1.58-2B-4T``), without loading a tensor.  A layer is every tensor named ``*.weight`` with dtype U8 that has a
+    sibling ``.weight_scale``, in order of first appearance in the ``model*.safetensors`` parts -- embeddings, norms, ``lm_head`` and
+    whatever ``modules_to_not_convert`` names are floating tensors without a scale, so they are not layers.  ``linear_class`` defaults to
+    "bitlinear" as ``BitNetQuantConfig`` does.  Refused (RuntimeError naming the tensor or the field): another ``quant_method``,
+    ``quantization_mode == "online"`` (master weights: load_bitnet_dir), an unknown ``linear_class``, a U8 ``.weight`` without
+    ``.weight_scale``, a scale that is not one element of BF16 / F16 / F32, a weight that is not 2-D, byte ranges that do not match the
+    shape, and a directory without any layer."""
+    with open(os.path.join(model_dir, "config.json"), "r", encoding="utf-8") as f:
+        qc = json.load(f).get("quantization_config") or {}
+    if qc.get("quant_method") != "bitnet":
+        raise RuntimeError("Models in {} not in packed BitNet format (config.json: quantization_config.quant_method is {!r}, \"bitnet\" expected)".format(
+            model_dir, qc.get("quant_method")))
+    if qc.get("quantization_mode", "offline") == "online":
+        raise RuntimeError("quantization_config.quantization_mode is \"online\": a checkpoint of master weights: load_bitnet_dir")
+    linear_class = qc.get("linear_class", "bitlinear")
+    if linear_class not in convert.BITNET_LINEAR_CLASSES:
+        raise RuntimeError("quantization_config.linear_class is {!r}: \"bitlinear\" or \"autobitlinear\" expected".format(linear_class))
+    parts = sorted(f for f in os.listdir(model_dir) if f.startswith("model") and f.endswith(".safetensors"))
+    if not parts:
+        raise RuntimeError("Models in {} not in safetensors format (torch .bin checkpoints: convert them to safetensors first)".format(model_dir))
+    index: Dict[str, TensorRef] = {}
+    order: List[str] = []
+    for part in parts:
+        for name, ref in safetensors_index(os.path.join(model_dir, part)).items():
+            if name not in index and name.endswith(".weight") and ref.dtype == "U8":
+                order.append(name)
+            index[name] = ref
+    layers = []
+    for wname in order:
+        ref, sc = index[wname], index.get(wname + "_scale")
+        if sc is None:
+            raise RuntimeError("{}_scale is missing ({} is U8: a packed ternary weight)".format(wname, wname))
+        if sc.dtype not in ("BF16", "F16", "F32") or int(np.prod(sc.shape)) != 1 or len(sc.shape) > 1 or \
+                (sc.end - sc.begin) != np.dtype(_NP[sc.dtype]).itemsize:
+            raise RuntimeError("{}_scale has dtype {} and shape {}: one element of BF16, F16 or F32 expected".format(wname, sc.dtype, sc.shape))
+        if len(ref.shape) != 2:
+            raise RuntimeError("{} has shape {}: a 2-D tensor expected".format(wname, ref.shape))
+        if (ref.end - ref.begin) != int(np.prod(ref.shape)):
+            raise RuntimeError("{}: shape {} does not match its {} bytes".format(wname, ref.shape, ref.end - ref.begin))
+        layers.append(BitnetPackedLayer(wname[:-len(".weight")], ref, sc, 4 * ref.shape[0], ref.shape[1]))
+    if not layers:
+        raise RuntimeError("Models in {} hold no packed ternary layer (a U8 *.weight with a .weight_scale)".format(model_dir))
+    return BitnetPackedScan(layers, linear_class, bool(qc.get("use_rms_norm", False)), float(qc.get("rms_norm_eps") or 1e-6), qc)
+
+
+def load_bitnet_packed_dir(model_dir: str, wrapper, dev_dtype=F32) -> Dict[str, "object"]:
+    """{layer name: Weights} for every layer ``scan_bitnet_packed_dir`` finds: the packed bytes are uploaded as they lie in the file and
+    unpacked and re-tiled on the GPU (``wrapper.register_bitnet_packed``); the scale is a host scalar, read from the file and turned into
+    the blob's scale by the checkpoint's ``linear_class`` (``convert.bitnet_packed_scale``).  Handles only: where the checkpoint sets
+    ``use_rms_norm`` (the scan result says so, with ``rms_norm_eps``), a layer's ``<layer>.rms_norm.weight`` vector is the caller's to
+    apply to the activations, for example through ``fused_xf(..., "norm", gamma=...)``; biases are not read either."""
+    scan = scan_bitnet_packed_dir(model_dir)
+    return {L.name: wrapper.register_bitnet_packed(np.array(read_tensor(L.weight)), np.array(read_tensor(L.weight_scale._replace(shape=(1,)))), None,
+                                                   scan.linear_class, dev_dtype) for L in scan.layers}

@@ -194,6 +194,53 @@ def bitnet_absmean_quant(w: np.ndarray, m_groups: int = 1, eps: float = 1e-5, sc
     return (t.astype(np.int8) + 2).astype(np.uint8).reshape(Mw, K), s.astype(np.float32)
 
 
+def unpack_bitnet_packed(packed: np.ndarray) -> Tuple[np.ndarray, int]:
+    """Packed ternary weights of the Hugging Face BitNet quantiser (``transformers.integrations.bitnet.pack_weights``), uint8 [Mw/4][K]
+    -> (levels uint8 [Mw][K], invalid): the host reference of ``tmac_hip_pack_ternary_dev``, never the route.  With R4 = Mw / 4, weight
+    row o is field o // R4 (bits 2 (o // R4) and up) of packed row o % R4; the field holds v = t + 1, the level is t + 2 = v + 1 in
+    {1, 2, 3} (``w_real = (level - 2) * s``).  A field of 3 has no level: it becomes level 3 and is counted in ``invalid``."""
+    packed = np.asarray(packed)
+    if packed.dtype != np.uint8 or packed.ndim != 2:
+        raise TypeError("packed must be uint8 [Mw/4][K]")
+    v = np.concatenate([(packed >> np.uint8(2 * i)) & np.uint8(3) for i in range(4)], axis=0)
+    return np.minimum(v + np.uint8(1), np.uint8(3)).astype(np.uint8), int(np.count_nonzero(v == 3))
+
+
+def pack_bitnet_packed(levels: np.ndarray) -> np.ndarray:
+    """the inverse: levels uint8 [Mw][K] in {1, 2, 3}, Mw a multiple of 4 -> packed uint8 [Mw/4][K] (fixtures and tests)"""
+    levels = np.asarray(levels)
+    if levels.dtype != np.uint8 or levels.ndim != 2 or levels.shape[0] % 4 or levels.size == 0 or levels.min() < 1 or levels.max() > 3:
+        raise ValueError("levels must be uint8 [Mw][K] in {1, 2, 3} with Mw a multiple of 4")
+    R4 = levels.shape[0] // 4
+    v = (levels - np.uint8(1)).reshape(4, R4, levels.shape[1])
+    return (v[0] | (v[1] << np.uint8(2)) | (v[2] << np.uint8(4)) | (v[3] << np.uint8(6))).astype(np.uint8)
+
+
+BITNET_LINEAR_CLASSES = ("bitlinear", "autobitlinear")
+
+
+def bitnet_packed_scale(weight_scale, linear_class: str = "bitlinear") -> np.float32:
+    """The unified scale s (``w_real = (level - 2) * s``) a packed BitNet checkpoint's one-element ``weight_scale`` stands for.
+    ``weight_scale``: a float, or a one-element array in float32, float16 or uint16 (bf16 bit patterns); its conversion to float32 is
+    exact.  ``linear_class`` is ``quantization_config.linear_class``: "autobitlinear" (bitnet-b1.58-2B-4T) computes
+    ``y = (x . levels) * weight_scale``, so s = float32(weight_scale); "bitlinear" (the default of ``BitNetQuantConfig``) computes
+    ``y = (x . levels) / weight_scale``, so s = float32(1) / float32(weight_scale), one correctly rounded float32 division."""
+    if linear_class not in BITNET_LINEAR_CLASSES:
+        raise ValueError("linear_class must be one of {}, not {!r}".format(BITNET_LINEAR_CLASSES, linear_class))
+    a = np.asarray(weight_scale)
+    if a.size != 1:
+        raise ValueError("weight_scale holds {} values: one expected".format(a.size))
+    a = a.reshape(1)
+    if a.dtype == np.uint16:
+        ws = bf16_bits_to_f32(a)[0]
+    elif a.dtype in (np.float32, np.float16) or a.dtype.kind in "fiu":
+        ws = a.astype(np.float32)[0]
+    else:
+        raise TypeError("weight_scale must be a float, or float32 / float16 / uint16 (bf16 bit patterns), not {}".format(a.dtype))
+    with np.errstate(divide="ignore"):
+        return np.float32(ws) if linear_class == "autobitlinear" else np.float32(1.0) / np.float32(ws)
+
+
 def kernel_name(M_bits: int, K: int, N: int, bits: int) -> str:
     return f"qgemm_lut_t1_int8_m{M_bits}_k{K}_n{N}_b{bits}"
 

@@ -130,6 +130,7 @@ struct Knobs {
     int rows_kernel = 0;           // k_gemv_rows: 0 = where measured faster, 1 = never (the routing without it), 2 = wherever it covers the call (tmac_hip_debug_rows_kernel)
     uint64_t rows_launches = 0;    // k_gemv_rows launches since load or reset (tmac_hip_debug_rows_stats): a counter, reset with the settings
     uint64_t route_launches[8] = {};   // launches per planned route, indexed by enum Route of tmac_dispatch.cpp (tmac_hip_debug_route_stats): counters, reset with the settings
+    int pack_ternary_kernel = 0;   // packed ternary weights: 0 = the read-once kernel where it applies, 1 = k_pack_ternary_weights (the general form) everywhere (tmac_hip_debug_pack_ternary_kernel)
     int chain_grid = 0;            // workgroups of chains built from now on (0 = one per CU; tests run two chains side by side on one device)
     unsigned long long* stamps = nullptr;        // phase stamps of the next fused launches (tmac_hip_debug_stamps)
     int32_t* stamp_dump = nullptr;               // scratch the stamp instantiation stores its tap into (allocated once, survives resets)

@@ -162,6 +162,13 @@ hipError_t launch_pack_codes(const void* codes, const void* scales, const void* 
 size_t absmean_partial_count(int Mw, int K, int m_groups);
 hipError_t launch_absmean(const void* W, int src, int Mw, int K, int m_groups, float eps, double* partials, float* scales_out, hipStream_t st);
 hipError_t launch_pack_dense(const void* W, int src, const float* scales, void* A_out, void* S_out, Dtype out_dt, const Shape& s, hipStream_t st);
+// BitNet packed ternary checkpoints: packed uint8 [Mw / 4][K] (four weight rows per byte: tmac_pack.h; 16-byte aligned), bits = 2, unified
+// scales -- the levels straight into A_out, `scales` (fp32 [m_groups]) into S_out as out_dt.  invalid (device int32, NULL = not counted):
+// the fields of value 3 are ADDED to it, at most one atomicAdd per workgroup; the caller zeroes it.  The read-once kernel
+// (k_pack_ternary_weights_x4) where pack_ternary_reads_once(s), i.e. (Mw / 4) % 16 == 0, unless `general` forces k_pack_ternary_weights.
+bool pack_ternary_reads_once(const Shape& s);
+hipError_t launch_pack_ternary(const void* packed, const float* scales, void* A_out, void* S_out, Dtype out_dt, const Shape& s, int32_t* invalid,
+                               bool general, hipStream_t st);
 hipError_t launch_preprocess(const void* B, Dtype act_dt, int8_t* qlut_ref, void* qlut_dev, void* qlut_lds, float* lut_scales,
                              float* lut_biases, int K, int N, int ags, size_t qdev_u4_per_row, hipStream_t st);
 // all-gather over IPC-mapped windows (tmac_comm.cpp, transport "ipc"): workgroup p of `world` handles rank p's part

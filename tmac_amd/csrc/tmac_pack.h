@@ -4,7 +4,8 @@
 // tmac_amd/weights.py).  Everything here is a pure function of integers: tests/cpp/pack_main.cc compiles this header with plain g++
 // and packs whole matrices through it, byte for byte against tmac_amd/weights.py:preprocess_weights (tests/test_pack_cpu.py); the
 // kernels call the same functions.  The one piece of floating point: the BitNet absmean rule (master weights -> ternary levels), shared
-// the same way with tests/cpp/pack_dense_main.cc.
+// the same way with tests/cpp/pack_dense_main.cc.  The packed ternary format of BitNet checkpoints (four weight rows per byte) is integers
+// again: tests/cpp/pack_ternary_main.cc.
 //
 //   M-space row     r    = (o / 8) * 8 * bits + p * 8 + o % 8                                (o: weight row, p: bit plane)
 //   nibble(r, t)         = sum_ig bit_p(w[o][4 t + ig]) << ig
@@ -126,6 +127,22 @@ TMAC_PACK_HD uint32_t absmean_level(float w, float inv) {
 // four masters of one table -> the `four` codes_nibble takes
 TMAC_PACK_HD uint32_t absmean_four(float w0, float w1, float w2, float w3, float inv) {
     return codes_four(absmean_level(w0, inv), absmean_level(w1, inv), absmean_level(w2, inv), absmean_level(w3, inv));
+}
+
+// ---- BitNet b1.58: packed ternary checkpoints (the Hugging Face BitNet quantiser, offline mode) -----------------------
+// packed uint8 [R4][K], R4 = Mw / 4: weight row o lives in packed row o % R4, in the 2-bit field o / R4 at bit 2 (o / R4) -- the four row
+// blocks of the matrix share a byte.  The stored field is v = t + 1 with t in {-1, 0, 1}; the 2-bit level of the blob is t + 2 = v + 1
+// (levels 1, 2, 3 as above).  v = 3 occurs in no well-formed file: it has no level, is packed as level 3 (t = 2 clamped to 1) and counted.
+TMAC_PACK_HD int ternary_packed_row(int o, int R4) { return o % R4; }
+TMAC_PACK_HD int ternary_field(int o, int R4) { return o / R4; }
+TMAC_PACK_HD uint32_t ternary_level(uint32_t v) { return v >= 3u ? 3u : v + 1u; }
+// The four packed bytes of one table (columns 4 t .. 4 t + 3 of a packed row, column i in byte i of `bytes`) and a field index -> the
+// `four` codes_nibble takes for the weight row that owns the field; *invalid: how many of the four fields were 3.
+TMAC_PACK_HD uint32_t ternary_four(uint32_t bytes, int field, int* invalid) {
+    const uint32_t v = (bytes >> (2 * field)) & 0x03030303u;
+    const uint32_t three = v & (v >> 1) & 0x01010101u;      // 1 in the bytes whose field is 3
+    *invalid = __builtin_popcount(three);
+    return v + 0x01010101u - three;                         // ternary_level of each byte: no carry leaves a byte
 }
 
 #if defined(__HIPCC__)

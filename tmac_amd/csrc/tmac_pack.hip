@@ -13,6 +13,9 @@
 // Scales: one thread per (scale group, 8 weight rows) writes the 8 scales (and 8 zeros) of that octet as 16-byte stores.
 // BitNet master weights (fp32 / fp16 / bf16 [Mw][K]): the scale of each row block by a two-stage fp64 reduction (k_absmean,
 // k_absmean_scales), then the codes kernel with a stage 1 that quantises four masters per lane (k_pack_dense_weights).
+// BitNet packed ternary weights (uint8 [Mw / 4][K], four weight rows per byte): the codes kernel with a stage 1 that extracts a field
+// (k_pack_ternary_weights), or, where no group of 32 M-space rows straddles two fields, one load of every byte feeding four output tiles
+// (k_pack_ternary_weights_x4); fields without a ternary level are counted.
 #include <hip/hip_fp16.h>
 #include <hip/hip_runtime.h>
 
@@ -33,16 +36,16 @@ constexpr int PACK_STRIDE = PACK_TABLES / 2 + 4;   // bytes per LDS row: 9 words
 // LDS row of (plane p, local weight row ol)
 __device__ __forceinline__ int lds_row(int p, int ol) { return p * PACK_ROWS + ol; }
 
-// stage 2, shared by both input forms
+// stage 2, shared by every input form: the LDS tile `lds` holds the groups of 32 M-space rows [g0, g0 + GROUPS) of the matrix, of which
+// those below g_end exist
 template <int BITS>
-__device__ __forceinline__ void pack_store_tile(const uint8_t* lds, uint8_t* __restrict__ A_out, int Mw, int T, int bm, int kfactor) {
+__device__ __forceinline__ void pack_store_groups(const uint8_t* lds, uint8_t* __restrict__ A_out, int g0, int g_end, int T, int bm, int kfactor) {
     const int t0 = blockIdx.x * PACK_TABLES;
-    const int ngroups = Mw * BITS / 32;                 // M is a multiple of 32 (bm is)
     constexpr int GROUPS = PACK_ROWS * BITS / 32;       // groups of 32 M-space rows per tile
     for (int item = threadIdx.x; item < GROUPS * (PACK_TABLES / 2); item += PACK_THREADS) {
         const int gl = item / (PACK_TABLES / 2), tp = item % (PACK_TABLES / 2);
-        const int g = blockIdx.y * GROUPS + gl, t = t0 + 2 * tp;
-        if (g >= ngroups || t >= T) continue;
+        const int g = g0 + gl, t = t0 + 2 * tp;
+        if (g >= g_end || t >= T) continue;
         uint32_t u0[4] = {0, 0, 0, 0}, u1[4] = {0, 0, 0, 0};
 #pragma unroll
         for (int j = 0; j < 16; ++j) {
@@ -55,6 +58,12 @@ __device__ __forceinline__ void pack_store_tile(const uint8_t* lds, uint8_t* __r
         *reinterpret_cast<uint4*>(A_out + pk::blob_unit(g, t, bm, kfactor, T)) = make_uint4(u0[0], u0[1], u0[2], u0[3]);
         if (t + 1 < T) *reinterpret_cast<uint4*>(A_out + pk::blob_unit(g, t + 1, bm, kfactor, T)) = make_uint4(u1[0], u1[1], u1[2], u1[3]);
     }
+}
+// ... of the tile of weight rows blockIdx.y names
+template <int BITS>
+__device__ __forceinline__ void pack_store_tile(const uint8_t* lds, uint8_t* __restrict__ A_out, int Mw, int T, int bm, int kfactor) {
+    // M is a multiple of 32 (bm is)
+    pack_store_groups<BITS>(lds, A_out, blockIdx.y * (PACK_ROWS * BITS / 32), Mw * BITS / 32, T, bm, kfactor);
 }
 
 // GPTQ qweight int32 [K * BITS / 32][Mw]
@@ -285,6 +294,107 @@ __global__ __launch_bounds__(PACK_THREADS) void k_pack_dense_weights(const void*
     pack_store_tile<BITS>(lds, A_out, Mw, T, bm, kfactor);
 }
 
+// ---- BitNet packed ternary checkpoints: packed uint8 [R4][K], four weight rows per byte (the format: tmac_pack.h) ------------------------
+// Fields of value 3, which have no level: a lane counts its own (`bad`), a wave adds its lanes' counts with shuffles and leaves the sum in
+// `wave_bad` IN FRONT of the kernel's barrier between the stages; behind it thread 0 adds the waves' sums and, when the workgroup saw any,
+// adds them to *counter with one atomicAdd.  counter == NULL: nothing is counted (uniform over the launch).
+__device__ __forceinline__ void invalid_fold(int bad, int* wave_bad, const int32_t* counter) {
+    if (!counter) return;
+#pragma unroll
+    for (int off = 32; off >= 1; off >>= 1) bad += __shfl_xor(bad, off);
+    if (threadIdx.x % 64 == 0) wave_bad[threadIdx.x / 64] = bad;
+}
+__device__ __forceinline__ void invalid_report(const int* wave_bad, int32_t* counter) {
+    if (!counter || threadIdx.x != 0) return;
+    int sum = 0;
+#pragma unroll
+    for (int v = 0; v < PACK_THREADS / 64; ++v) sum += wave_bad[v];
+    if (sum) atomicAdd(counter, sum);
+}
+
+// The general form: k_pack_codes_weights<2> with another stage 1 -- the lane that took the four code bytes of (weight row o, table t) takes
+// the four packed bytes of (packed row o % R4, table t) and extracts field o / R4.  Every Mw registration accepts (a multiple of 16, so R4
+// is whole); each source byte is read from four tiles.  No [Mw][K] code tensor exists anywhere.
+__global__ __launch_bounds__(PACK_THREADS) void k_pack_ternary_weights(const uint8_t* __restrict__ packed, uint8_t* __restrict__ A_out, int32_t* __restrict__ invalid,
+                                                                       int Mw, int K, int bm, int kfactor) {
+    constexpr int BITS = 2;
+    __shared__ __attribute__((aligned(16))) uint8_t lds[PACK_ROWS * BITS * PACK_STRIDE];
+    __shared__ int wave_bad[PACK_THREADS / 64];
+    const int T = K / 4, R4 = Mw / 4;
+    const int o0 = blockIdx.y * PACK_ROWS, t0 = blockIdx.x * PACK_TABLES;
+    int bad = 0;
+    for (int idx = threadIdx.x; idx < PACK_ROWS * PACK_TABLES; idx += PACK_THREADS) {
+        const int ol = idx / PACK_TABLES, tl = idx % PACK_TABLES;
+        const int o = o0 + ol, t = t0 + tl;
+        uint32_t four = 0;
+        if (o < Mw && t < T) {
+            const uint32_t bytes = *reinterpret_cast<const uint32_t*>(packed + (size_t)pk::ternary_packed_row(o, R4) * K + 4 * (size_t)t);   // K is a multiple of 4
+            int n;
+            four = pk::ternary_four(bytes, pk::ternary_field(o, R4), &n);
+            bad += n;
+        }
+#pragma unroll
+        for (int p = 0; p < BITS; ++p) {
+            uint32_t v = pk::codes_nibble(four, p) << (4 * (tl % 8));
+            v |= __shfl_xor(v, 1);
+            v |= __shfl_xor(v, 2);
+            v |= __shfl_xor(v, 4);
+            if (tl % 8 == 0) *reinterpret_cast<uint32_t*>(lds + lds_row(p, ol) * PACK_STRIDE + tl / 2) = v;
+        }
+    }
+    invalid_fold(bad, wave_bad, invalid);
+    __syncthreads();
+    invalid_report(wave_bad, invalid);
+    pack_store_tile<BITS>(lds, A_out, Mw, T, bm, kfactor);
+}
+
+// The read-once form, for R4 a multiple of 16: no group of 32 M-space rows (16 weight rows) then straddles two fields.  One workgroup loads
+// a tile of 64 packed rows x 64 tables ONCE, 16 bytes (four tables) per lane along k -- K is a multiple of 32 (make_shape: K / 4 of
+// kfactor, K of the activation group), so every such load is aligned and lies inside its row -- splits every byte into its four fields,
+// fills four LDS tiles (one per field: 4 x 2 planes x 64 rows x PACK_STRIDE bytes) and runs stage 2 four times, once per output tile at
+// weight rows i R4 + pr0 ...  The two lanes that hold the eight tables of an LDS word OR their halves together (one xor shuffle), one
+// 32-bit store per (field, plane); every lane runs every step.  Tails: packed rows >= R4 and tables >= T load nothing and store nothing.
+__global__ __launch_bounds__(PACK_THREADS) void k_pack_ternary_weights_x4(const uint8_t* __restrict__ packed, uint8_t* __restrict__ A_out,
+                                                                          int32_t* __restrict__ invalid, int Mw, int K, int bm, int kfactor) {
+    constexpr int BITS = 2, TILE = PACK_ROWS * BITS * PACK_STRIDE, LANES = PACK_TABLES / 4;      // LANES: 16-byte loads per packed row of the tile
+    __shared__ __attribute__((aligned(16))) uint8_t lds[4 * TILE];
+    __shared__ int wave_bad[PACK_THREADS / 64];
+    const int T = K / 4, R4 = Mw / 4;
+    const int pr0 = blockIdx.y * PACK_ROWS, t0 = blockIdx.x * PACK_TABLES;
+    int bad = 0;
+    for (int idx = threadIdx.x; idx < PACK_ROWS * LANES; idx += PACK_THREADS) {
+        const int prl = idx / LANES, q = idx % LANES;
+        const int pr = pr0 + prl, t = t0 + 4 * q;
+        uint4 w4 = make_uint4(0, 0, 0, 0);
+        if (pr < R4 && t < T) w4 = *reinterpret_cast<const uint4*>(packed + (size_t)pr * K + 4 * (size_t)t);      // T is a multiple of 8: whole quads of tables
+        const uint32_t w[4] = {w4.x, w4.y, w4.z, w4.w};
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            uint32_t nib[BITS] = {};          // the nibbles of the lane's four tables, lowest table first
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                int n;
+                const uint32_t four = pk::ternary_four(w[j], i, &n);
+                bad += n;
+#pragma unroll
+                for (int p = 0; p < BITS; ++p) nib[p] |= pk::codes_nibble(four, p) << (4 * j);
+            }
+#pragma unroll
+            for (int p = 0; p < BITS; ++p) {
+                uint32_t v = nib[p] << (16 * (q % 2));
+                v |= __shfl_xor(v, 1);
+                if (q % 2 == 0) *reinterpret_cast<uint32_t*>(lds + i * TILE + lds_row(p, prl) * PACK_STRIDE + 2 * q) = v;
+            }
+        }
+    }
+    invalid_fold(bad, wave_bad, invalid);
+    __syncthreads();
+    invalid_report(wave_bad, invalid);
+    // output tile i: weight rows i R4 + pr0 ..., i.e. groups of 16 weight rows from (i R4 + pr0) / 16; field i ends at group (i + 1) R4 / 16
+#pragma unroll
+    for (int i = 0; i < 4; ++i) pack_store_groups<BITS>(lds + i * TILE, A_out, (i * R4 + pr0) / 16, (i + 1) * (R4 / 16), T, bm, kfactor);
+}
+
 // ---- scales -------------------------------------------------------------------------------------------------------------------------
 // n contiguous elements (a multiple of 16 bytes, 16-byte aligned on both sides) as 16-byte accesses
 template <class T, int N>
@@ -476,6 +586,32 @@ hipError_t launch_pack_dense(const void* W, int src, const float* scales, void* 
         case pk::SRC_F16: hipLaunchKernelGGL(k_pack_dense_weights<pk::SRC_F16>, g, b, 0, st, W, scales, R, A, s.Mw, s.K, s.bm, s.kfactor); break;
         case pk::SRC_BF16: hipLaunchKernelGGL(k_pack_dense_weights<pk::SRC_BF16>, g, b, 0, st, W, scales, R, A, s.Mw, s.K, s.bm, s.kfactor); break;
         default: return hipErrorInvalidValue;
+    }
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return e;
+    const size_t n = (size_t)s.m_groups;      // the unified scales into the blob: the copy of the codes form
+    by_dtypes(F32, out_dt, [&](auto in_tag, auto out_tag) {
+        using ST = decltype(in_tag);
+        using OT = decltype(out_tag);
+        hipLaunchKernelGGL((k_pack_copy<ST, OT>), dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, (const ST*)scales, (OT*)S_out, n);
+    });
+    return hipGetLastError();
+}
+
+// ---- BitNet packed ternary checkpoints ------------------------------------------------------------------------------------------------
+bool pack_ternary_reads_once(const Shape& s) { return (s.Mw / 4) % 16 == 0; }
+
+hipError_t launch_pack_ternary(const void* packed, const float* scales, void* A_out, void* S_out, Dtype out_dt, const Shape& s, int32_t* invalid,
+                               bool general, hipStream_t st) {
+    if (s.bits != 2 || s.m_groups < 1) return hipErrorInvalidValue;
+    const uint8_t* src = (const uint8_t*)packed;
+    uint8_t* A = (uint8_t*)A_out;
+    const dim3 b(PACK_THREADS);
+    if (!general && pack_ternary_reads_once(s)) {
+        const dim3 g((unsigned)((s.K / 4 + PACK_TABLES - 1) / PACK_TABLES), (unsigned)((s.Mw / 4 + PACK_ROWS - 1) / PACK_ROWS));
+        hipLaunchKernelGGL(k_pack_ternary_weights_x4, g, b, 0, st, src, A, invalid, s.Mw, s.K, s.bm, s.kfactor);
+    } else {
+        hipLaunchKernelGGL(k_pack_ternary_weights, weight_grid(s), b, 0, st, src, A, invalid, s.Mw, s.K, s.bm, s.kfactor);
     }
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return e;

@@ -1,6 +1,7 @@
 // tmac_pack_host.cpp — the entry points in front of the pack kernels (tmac_pack.hip): GPTQ tensors or plain codes, in device memory, ->
 // the reference blob (tmac_hip_pack_*_dev) or straight to a registered handle (tmac_hip_register_weights_*_dev, through register_impl).
-// BitNet master weights (fp32 / fp16 / bf16) take the same two ways through the absmean rule (tmac_hip_*_absmean_dev).
+// BitNet master weights (fp32 / fp16 / bf16) take the same two ways through the absmean rule (tmac_hip_*_absmean_dev), packed ternary
+// BitNet weights (four weight rows per byte) through tmac_hip_*_ternary_dev.
 #include <cmath>
 
 #include "tmac_host.h"
@@ -152,7 +153,83 @@ int32_t launch(const Shape& s, const DenseIn& in, void* A_out, void* S_out, tmac
     return TMAC_HIP_OK;
 }
 
+// ---- BitNet packed ternary checkpoints (the format: tmac_pack.h) ---------------------------------------------------------------------------
+struct TernaryIn { const void* packed; const float* scales; };
+
+// Everything that is refused before anything is written, in the order of check_dense: NULL required pointers, the row blocks, the blob's
+// dtype, make_shape's own refusals (bits = 2), alignment -- of the counter too, where one is given.
+int32_t check_ternary(Shape& s, const TernaryIn& in, const void* A_out, const void* S_out, bool outs, const int32_t* invalid, int Mw, int K, const tmac_kcfg* cfg,
+                      tmac_dtype_t ref_float) {
+    if (!cfg) return fail(TMAC_HIP_E_ARG, "null kcfg");
+    const PackArg args[] = {{"packed_dev", in.packed, true}, {"scales_dev", in.scales, true}, {"A_ref_out", A_out, outs}, {"scales_ref_out", S_out, outs},
+                            {"invalid_count_dev", invalid, false}};
+    for (const PackArg& a : args)
+        if (a.required && !a.p) return fail(TMAC_HIP_E_ARG, "%s is NULL", a.name);
+    if (cfg->m_groups < 1)
+        return fail(TMAC_HIP_E_ARG, "m_groups = %d: packed ternary weights take unified scales (per-group scales: register codes or GPTQ tensors)", cfg->m_groups);
+    if (Mw % cfg->m_groups) return fail(TMAC_HIP_E_ARG, "Mw=%d is no whole number of m_groups=%d row blocks", Mw, cfg->m_groups);
+    if (ref_float != TMAC_F32 && ref_float != TMAC_F16) return fail(TMAC_HIP_E_ARG, "host_float must be TMAC_F32 or TMAC_F16");
+    const int32_t rc = make_shape(s, Mw, K, 2, cfg);
+    return rc ? rc : aligned_check(args, 5);
+}
+
+// the counter zeroed on the stream, then the pack
+int32_t launch(const Shape& s, const TernaryIn& in, void* A_out, void* S_out, tmac_dtype_t ref_float, int32_t* invalid, hipStream_t st) {
+    if (invalid) HIP_TRY(hipMemsetAsync(invalid, 0, sizeof(int32_t), st));
+    const hipError_t e = launch_pack_ternary(in.packed, in.scales, A_out, S_out, (Dtype)ref_float, s, invalid, g_knobs.pack_ternary_kernel == 1, st);
+    return e == hipSuccess ? TMAC_HIP_OK : fail(TMAC_HIP_E_RUNTIME, "pack_ternary: %s", hipGetErrorString(e));
+}
+
 }  // namespace
+
+extern "C" int32_t tmac_hip_debug_pack_ternary_kernel(int mode) {
+    if (mode < 0 || mode > 1) return fail(TMAC_HIP_E_ARG, "packed ternary kernel mode must be 0 (auto: read-once where it applies) or 1 (the general form everywhere)");
+    g_knobs.pack_ternary_kernel = mode;
+    return TMAC_HIP_OK;
+}
+
+extern "C" int32_t tmac_hip_pack_ternary_dev(const void* packed_dev, const float* scales_dev, int Mw, int K, const tmac_kcfg* cfg, void* A_ref_out,
+                                             void* scales_ref_out, tmac_dtype_t host_float, int32_t* invalid_count_dev, void* stream) {
+    const TernaryIn in{packed_dev, scales_dev};
+    Shape s;
+    int32_t rc = check_ternary(s, in, A_ref_out, scales_ref_out, true, invalid_count_dev, Mw, K, cfg, host_float);
+    if (rc) return rc;
+    rc = ensure_device();
+    if (rc) return rc;
+    rc = defer_barrier();
+    return rc ? rc : launch(s, in, A_ref_out, scales_ref_out, host_float, invalid_count_dev, (hipStream_t)stream);
+}
+
+extern "C" int32_t tmac_hip_register_weights_ternary_dev(tmac_hip_weights** out, const void* packed_dev, const float* scales_dev, int Mw, int K,
+                                                         const tmac_kcfg* cfg, tmac_dtype_t host_float, tmac_dtype_t dev_float, void* stream) {
+    if (!out) return fail(TMAC_HIP_E_ARG, "out is NULL");
+    const TernaryIn in{packed_dev, scales_dev};
+    Shape s;
+    int32_t rc = check_ternary(s, in, nullptr, nullptr, false, nullptr, Mw, K, cfg, host_float);
+    if (rc) return rc;
+    if (dev_float != TMAC_F32 && dev_float != TMAC_F16) return fail(TMAC_HIP_E_ARG, "dev_float must be TMAC_F32 or TMAC_F16");
+    rc = ensure_device();
+    if (rc) return rc;
+    rc = defer_barrier();       // packed_dev / scales_dev may have been written by queued work
+    if (rc) return rc;
+    hipStream_t st = (hipStream_t)stream;
+    DevBuf dA, dS, dN;  // as register_from: ours on every return path
+    HIP_TRY(dA.alloc(ref_weight_bytes(s)));
+    HIP_TRY(dS.alloc(ref_scale_elems(s) * dt_size((Dtype)host_float)));
+    HIP_TRY(dN.alloc(sizeof(int32_t)));
+    rc = launch(s, in, dA.p, dS.p, host_float, dN.as<int32_t>(), st);
+    if (rc != TMAC_HIP_OK) {
+        (void)hipStreamSynchronize(st);
+        return rc;
+    }
+    int32_t invalid = 0;
+    HIP_TRY(hipMemcpyAsync(&invalid, dN.p, sizeof(int32_t), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    if (invalid) return fail(TMAC_HIP_E_ARG, "packed weight holds %d fields of value 3 (no ternary level)", invalid);
+    rc = register_impl(out, dA.p, dS.p, true, Mw, K, 2, cfg, host_float, dev_float, stream);
+    if (rc != TMAC_HIP_OK) (void)hipStreamSynchronize(st);
+    return rc;
+}
 
 extern "C" int32_t tmac_hip_absmean_dev(const void* W_dev, tmac_src_dtype_t src_dtype, int Mw, int K, int m_groups, float eps, float* scales_out_dev,
                                         void* stream) {

@@ -263,6 +263,49 @@ def pack_bitnet(weight, cfg: Optional[KCfg] = None, m_groups: int = 1, eps: floa
     return A, S
 
 
+def _bitnet_packed_args(packed, scale, cfg):
+    """device tensors, shape and configuration of a packed ternary matrix (uint8 [Mw/4][K]: a torch CUDA tensor, or a numpy array
+    uploaded as it is) and its scale(s): a float, or fp32 [m_groups].  Without a cfg: what ``from_bitnet`` builds, one scale."""
+    from . import convert
+    pk = _on_device(packed, "packed", ("uint8",))
+    if pk.dim() != 2:
+        raise ValueError("packed is 2-D: [Mw/4][K]")
+    Mw, K = 4 * int(pk.shape[0]), int(pk.shape[1])
+    if cfg is None:
+        cfg = KCfg.make(Mw, K, 2, convert.default_bm(2, Mw), 16, 128, K, False, 1)
+    if isinstance(scale, (int, float, np.floating)):
+        scale = np.full(max(cfg.m_groups, 1), scale, np.float32)
+    sc = _on_device(scale, "scale", ("float32",)).reshape(-1)
+    if int(sc.shape[0]) != cfg.m_groups:
+        raise ValueError(f"scale holds {int(sc.shape[0])} values: one per row block, m_groups = {cfg.m_groups}")
+    return pk, sc, Mw, K, cfg
+
+
+def _bitnet_weight_scale(weight_scale):
+    """``weight_scale`` of a packed BitNet checkpoint as ``convert.bitnet_packed_scale`` takes it: a one-element torch tensor (bf16,
+    fp16 or fp32) becomes the float32 it converts to exactly; floats and numpy arrays pass through"""
+    if hasattr(weight_scale, "detach"):
+        name = str(weight_scale.dtype).replace("torch.", "")
+        if name not in ("bfloat16", "float16", "float32"):
+            raise TypeError(f"weight_scale must be bfloat16, float16 or float32, not {name}")
+        return weight_scale.detach().float().cpu().numpy()
+    return weight_scale
+
+
+def pack_ternary(packed, scale, cfg: Optional[KCfg] = None, ref_dtype=F32, stream=None, count_invalid: bool = False):
+    """Packed ternary weights uint8 [Mw/4][K] (the Hugging Face BitNet quantiser's format; ``convert.unpack_bitnet_packed`` states it) +
+    the unified scale(s) -> the reference blob, on the GPU (tmac_hip_pack_ternary_dev): (A_ref uint8, scales_ref) as ``pack_codes``
+    returns them, exactly ``weights.preprocess_weights`` of the unpacked levels.  ``scale``: a float or fp32 [m_groups], the s of
+    ``w_real = (level - 2) * s`` (``convert.bitnet_packed_scale`` of a checkpoint's ``weight_scale``).  ``count_invalid``: a third
+    result, an int32 CUDA tensor of one element -- the number of fields of value 3 (they are packed as level 3).  Asynchronous."""
+    import torch
+    pk, sc, Mw, K, cfg = _bitnet_packed_args(packed, scale, cfg)
+    A, S = _blob_buffers(Mw, K, 2, cfg, ref_dtype)
+    n = torch.empty(4, dtype=torch.int32, device="cuda") if count_invalid else None      # 16 bytes: the call's alignment rule
+    check(B.lib().tmac_hip_pack_ternary_dev(_ptr(pk), _ptr(sc), Mw, K, C.byref(cfg), _ptr(A), _ptr(S), ref_dtype, _ptr(n), _stream(stream)))
+    return (A, S, n[:1]) if count_invalid else (A, S)
+
+
 class Weights:
     """One weight matrix resident on the GPU (tmac_hip_register_weights)."""
 
@@ -330,6 +373,24 @@ class Weights:
         h = C.c_void_p()
         check(B.lib().tmac_hip_register_weights_absmean_dev(C.byref(h), _ptr(w), src, _ptr(sc), eps, Mw, K, C.byref(cfg), F32, dev_dtype,
                                                             _stream(stream)))
+        return cls._adopt(h, Mw, K, 2, cfg)
+
+    @classmethod
+    def from_bitnet_packed(cls, packed, weight_scale, cfg: Optional[KCfg] = None, linear_class: str = "autobitlinear", dev_dtype=F32,
+                           stream=None) -> "Weights":
+        """Register a layer of a PACKED ternary BitNet checkpoint (``quant_method: "bitnet"``, offline mode; bitnet-b1.58-2B-4T):
+        ``packed`` uint8 [Mw/4][K], four weight rows per byte -- a torch CUDA tensor, or a numpy array uploaded as it is -- unpacked and
+        packed into the blob on the GPU (tmac_hip_register_weights_ternary_dev; no [Mw][K] tensor exists anywhere).  ``weight_scale``:
+        the checkpoint's one-element tensor (bf16 / fp16 / fp32), a float, or a one-element numpy array (uint16 = bf16 bits);
+        ``linear_class`` (``quantization_config.linear_class``) says whether the layer multiplies by it ("autobitlinear") or divides
+        ("bitlinear"): ``convert.bitnet_packed_scale``.  The handle is the one ``from_codes(levels, [s], None, 2, cfg)`` gives for
+        ``convert.unpack_bitnet_packed``'s levels.  A field of value 3 (no ternary level) is refused (TMACHipError naming the count).
+        Without a ``cfg``: as ``from_bitnet``.  With a ``cfg`` of m_groups > 1 every row block gets the same scale."""
+        from . import convert
+        s = convert.bitnet_packed_scale(_bitnet_weight_scale(weight_scale), linear_class)
+        pk, sc, Mw, K, cfg = _bitnet_packed_args(packed, float(s), cfg)
+        h = C.c_void_p()
+        check(B.lib().tmac_hip_register_weights_ternary_dev(C.byref(h), _ptr(pk), _ptr(sc), Mw, K, C.byref(cfg), F32, dev_dtype, _stream(stream)))
         return cls._adopt(h, Mw, K, 2, cfg)
 
     def __init__(self, A_ref, scales_ref, Mw: int, K: int, bits: int, cfg: KCfg, scales_dtype=F32, dev_dtype=F32,
@@ -673,6 +734,11 @@ class TMACGeMMWrapper:
         """``Weights.from_bitnet``: BitNet master weights (fp32 / fp16 / bf16) -> handle, quantised and packed on the GPU.  (Unified
         scales have one activation group per row: the wrapper's act_group_size plays no part.)"""
         return Weights.from_bitnet(weight, cfg, m_groups, eps, scale, dev_dtype, stream)
+
+    def register_bitnet_packed(self, packed, weight_scale, cfg: Optional[KCfg] = None, linear_class: str = "autobitlinear", dev_dtype=F32,
+                               stream=None) -> Weights:
+        """``Weights.from_bitnet_packed``: a layer of a packed ternary BitNet checkpoint (uint8 [Mw/4][K] + its weight_scale) -> handle"""
+        return Weights.from_bitnet_packed(packed, weight_scale, cfg, linear_class, dev_dtype, stream)
 
     def llama_cpp_init(self, B_dev, M: int, K: int, N: int, bits: int, act_group_size: Optional[int] = None,
                        act_dtype: Optional[int] = None, stream=None, kperm: Optional[KPerm] = None) -> None:
