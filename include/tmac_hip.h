@@ -248,6 +248,45 @@ int32_t tmac_hip_register_weights_ternary_dev(tmac_hip_weights** out, const void
                                               const tmac_kcfg* cfg, tmac_dtype_t host_float, tmac_dtype_t dev_float, void* stream);
 int32_t tmac_hip_debug_pack_ternary_kernel(int mode);
 
+/* ---- dense master weights to W1 - W4 with per-group scales: round to nearest on the device -----------------------------------
+ * An unquantised model holds W [Mw][K], row-major, in fp32, fp16 or bf16 (src_dtype, as above).  The codes and the per-group scales come
+ * from GPTQ's quantiser without the error search (Quantizer.find_params with mse = False, then quantize), applied here at load time.  For
+ * weight row o and group sg of group_size consecutive k, maxq = 2^bits - 1, every step one correctly rounded fp32 operation:
+ *   lo = min(min_k w, 0), hi = max(max_k w, 0)
+ *   without zero points (cfg->zero_point == 0):  hi = max(|lo|, hi), lo = -hi, zq = 2^(bits-1)
+ *   scale = (hi - lo) / maxq;    lo == hi == 0, or scale below the smallest normal fp32:  lo = -1, hi = +1
+ *   scale_f16:  scale = fp16(scale) -- the scale that divides is the scale that is stored
+ *   with zero points:  zq = rint(-lo / scale)                       halves to even
+ *   code = clamp(rint(w / scale) + zq, 0, maxq);   T-MAC's zero = (zq - 2^(bits-1)) * scale, so |w - w_real| <= scale / 2
+ * A group is INVALID when a master of it is not finite, or when its scale is 0 or not finite (an fp16 scale that under- or overflowed): it
+ * gets the parameters of the all-zero group, a NaN master code 0, and it is COUNTED.
+ *   tmac_hip_rtn_params_dev            scale and zq of every (row, group) -> scales_out_dev / zq_out_dev, fp32 [Mw][K / group_size] each;
+ *                                      group_size a multiple of 4 that divides K.  invalid_count_dev (device int32; NULL: not counted):
+ *                                      zeroed on the stream, then the number of invalid groups is added to it, at most one atomicAdd per
+ *                                      workgroup.  Asynchronous on `stream`; allocates nothing.
+ *   tmac_hip_pack_rtn_dev              -> the reference blob (sizes: tmac_hip_ref_blob_bytes): k_rtn_params into scratch of the call's own
+ *                                      (12 bytes per group), then the codes straight into A_ref_out (k_pack_rtn_weights: the codes kernel
+ *                                      with a quantising stage 1 -- no [Mw][K] code tensor is written anywhere) and scales and zeros into
+ *                                      scales_ref_out as host_float.  scale_f16 is host_float == TMAC_F16.  Invalid groups are counted as
+ *                                      above, not refused.  Waits for `stream` before it returns (the scratch goes with the call).
+ *   tmac_hip_register_weights_rtn_dev  packs into temporaries with a counter of its own (scale_f16 where host_float or dev_float is
+ *                                      TMAC_F16), reads the counter: non-zero is TMAC_HIP_E_ARG, "master weights hold %d groups that cannot
+ *                                      be quantised ...", and no handle; otherwise registers as tmac_hip_register_weights_codes_dev does.
+ *                                      The handle is the one that call gives for the codes, scales and zeros of the rule.
+ * Scope: bits 1 to 4, per-group scales (cfg->m_groups < 1), with or without zero points, whatever else registration accepts.
+ * Refusals, nothing launched and nothing written.  TMAC_HIP_E_ARG naming the argument: a NULL pointer (invalid_count_dev excepted) or one
+ * below 16-byte alignment; an unknown src_dtype; m_groups >= 1 (unified scales from master weights: tmac_hip_register_weights_absmean_dev);
+ * host_float / dev_float other than TMAC_F32 / TMAC_F16; for the parameters alone, bits outside 1 to 4 or a group_size that is no positive
+ * multiple of 4 dividing K.  Shape refusals of the two that pack are registration's own, code and message.
+ * All three are ordered behind the calling thread's deferred queue: they flush it first, a refused call leaves it alone, a failed flush
+ * returns its status and launches nothing. */
+int32_t tmac_hip_rtn_params_dev(const void* W_dev, tmac_src_dtype_t src_dtype, int Mw, int K, int bits, int group_size, int zero_point, int scale_f16,
+                                float* scales_out_dev, float* zq_out_dev, int32_t* invalid_count_dev /* NULL: not counted */, void* stream);
+int32_t tmac_hip_pack_rtn_dev(const void* W_dev, tmac_src_dtype_t src_dtype, int Mw, int K, int bits, const tmac_kcfg* cfg, void* A_ref_out,
+                              void* scales_ref_out, tmac_dtype_t host_float, int32_t* invalid_count_dev /* NULL: not counted */, void* stream);
+int32_t tmac_hip_register_weights_rtn_dev(tmac_hip_weights** out, const void* W_dev, tmac_src_dtype_t src_dtype, int Mw, int K, int bits,
+                                          const tmac_kcfg* cfg, tmac_dtype_t host_float, tmac_dtype_t dev_float, void* stream);
+
 /* ---- act-order (desc_act) GPTQ matrices: the K permutation ---------------------------------------------------------------
  * An act-order matrix is a group-quantised matrix whose K axis is permuted: g_idx[k] names the group of column k.  With
  * perm = stable_argsort(g_idx) the columns q[:, perm] lie in contiguous groups of group_size, scales / qzeros are in group order already,
@@ -348,7 +387,8 @@ int32_t tmac_hip_qgemm_fused_dev(const tmac_hip_weights* const* weights, int nma
  * tmac_hip_qgemm_dev, tmac_hip_qgemm_partial_sums, tmac_hip_qgemm_fused_partial_sums, tmac_hip_chain_launch, tmac_hip_workspace_read /
  * _write, tmac_hip_debug_gemm_comb_sums / _gemm_image_read, tmac_hip_autotune_fused, tmac_hip_pack_gptq_dev / _pack_codes_dev (they write the
  * caller's blob buffers; a refused one leaves the queue alone), tmac_hip_absmean_dev / _pack_absmean_dev /
- * _register_weights_absmean_dev (the same), tmac_hip_pack_ternary_dev / _register_weights_ternary_dev (the same), and tmac_hip_free_weights, tmac_hip_chain_free and
+ * _register_weights_absmean_dev (the same), tmac_hip_pack_ternary_dev / _register_weights_ternary_dev (the same), tmac_hip_rtn_params_dev / _pack_rtn_dev /
+ * _register_weights_rtn_dev (the same), and tmac_hip_free_weights, tmac_hip_chain_free and
  * tmac_hip_cache_clear (a queued call may name what they release).  When that flush fails the entry point returns its status and launches
  * nothing of its own (the three that release still release: the handle is dead either way).  A queue belongs to a thread: freeing, from
  * another thread, weights that this thread has queued is the caller's error.

@@ -102,6 +102,10 @@ def load_library() -> C.CDLL:
         "tmac_hip_pack_ternary_dev": ([vp, vp, C.c_int, C.c_int, C.POINTER(KCfg), vp, vp, C.c_int, vp, vp], i32),
         "tmac_hip_register_weights_ternary_dev": ([C.POINTER(vp), vp, vp, C.c_int, C.c_int, C.POINTER(KCfg), C.c_int, C.c_int, vp], i32),
         "tmac_hip_debug_pack_ternary_kernel": ([C.c_int], i32),
+        # dense master weights to W1 - W4 with per-group scales (round to nearest): the parameters alone, the blob, the handle
+        "tmac_hip_rtn_params_dev": ([vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, vp, vp], i32),
+        "tmac_hip_pack_rtn_dev": ([vp, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(KCfg), vp, vp, C.c_int, vp, vp], i32),
+        "tmac_hip_register_weights_rtn_dev": ([C.POINTER(vp), vp, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(KCfg), C.c_int, C.c_int, vp], i32),
         # act-order (K permutation from g_idx): the object, packing / registration / the split path's LUT build through it
         "tmac_hip_kperm_from_gidx_dev": ([vp, C.c_int, C.c_int, C.POINTER(vp), vp], i32),
         "tmac_hip_kperm_info": ([vp, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_uint64)], i32),
@@ -195,6 +199,7 @@ def load_library() -> C.CDLL:
                 "tmac_hip_register_weights_codes_dev",
                 "tmac_hip_absmean_dev", "tmac_hip_pack_absmean_dev", "tmac_hip_register_weights_absmean_dev",
                 "tmac_hip_pack_ternary_dev", "tmac_hip_register_weights_ternary_dev", "tmac_hip_debug_pack_ternary_kernel",
+                "tmac_hip_rtn_params_dev", "tmac_hip_pack_rtn_dev", "tmac_hip_register_weights_rtn_dev",
                 "tmac_hip_kperm_from_gidx_dev", "tmac_hip_kperm_info", "tmac_hip_kperm_read", "tmac_hip_kperm_free", "tmac_hip_weights_kperm_id",
                 "tmac_hip_pack_gptq_perm_dev", "tmac_hip_pack_codes_perm_dev", "tmac_hip_register_weights_gptq_perm_dev",
                 "tmac_hip_register_weights_codes_perm_dev", "tmac_hip_preprocessor_perm_dev",

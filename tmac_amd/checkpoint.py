@@ -17,7 +17,9 @@ g_idx registers a plain handle.
 
 BitNet b1.58 checkpoints of master weights take the same two steps: ``scan_bitnet_dir`` / ``load_bitnet_dir`` (``Weights.from_bitnet``:
 the absmean rule and the packing on the GPU), and checkpoints of PACKED ternary weights (the Hugging Face BitNet quantiser, four weight
-rows per byte) ``scan_bitnet_packed_dir`` / ``load_bitnet_packed_dir`` (``Weights.from_bitnet_packed``), both at the end of this file.
+rows per byte) ``scan_bitnet_packed_dir`` / ``load_bitnet_packed_dir`` (``Weights.from_bitnet_packed``), both further down this file.
+UNQUANTISED checkpoints (fp16 / bf16 / fp32 matrices) come last: ``scan_dense_dir`` / ``load_dense_dir`` (``Weights.from_dense``: per-group
+round to nearest and the packing on the GPU).
 """
 import json
 import os
@@ -305,3 +307,76 @@ def load_bitnet_packed_dir(model_dir: str, wrapper, dev_dtype=F32) -> Dict[str, 
     scan = scan_bitnet_packed_dir(model_dir)
     return {L.name: wrapper.register_bitnet_packed(np.array(read_tensor(L.weight)), np.array(read_tensor(L.weight_scale._replace(shape=(1,)))), None,
                                                    scan.linear_class, dev_dtype) for L in scan.layers}
+
+
+# ---- unquantised checkpoints: dense fp16 / bf16 / fp32 matrices, quantised at load time (round to nearest) ----------------------------------
+class DenseLayer(NamedTuple):
+    name: str               # the layer: "<name>.weight" without its suffix
+    weight: TensorRef       # F32, F16 or BF16 [Mw][K]
+    Mw: int
+    K: int
+
+
+class DenseScan(NamedTuple):
+    layers: List[DenseLayer]
+
+
+def scan_dense_dir(model_dir: str) -> DenseScan:
+    """The linear layers of an UNQUANTISED checkpoint (an ordinary fp16 / bf16 / fp32 model: llama-3, Mistral, a fine-tune, a merged
+    LoRA), without loading a tensor: every tensor named ``model.layers.*_proj.weight`` in the ``model*.safetensors`` parts, in order of
+    first appearance -- embeddings, norms and the head are not.  Refused (RuntimeError naming the config key): a ``config.json`` with a
+    ``quantization_config`` -- the refusal names the loader of that format, ``load_gptq_dir`` for GPTQ methods, ``load_bitnet_packed_dir``
+    / ``load_bitnet_dir`` for "bitnet" -- or with a non-zero ``weight_bits`` (BitNet master weights: ``load_bitnet_dir``).  Refused naming
+    the tensor: another element type than F32 / F16 / BF16, a shape that is not 2-D, byte ranges that do not match the shape, a sibling
+    ``.weight_scale``.  A directory without ``config.json`` is an unquantised one."""
+    path = os.path.join(model_dir, "config.json")
+    hp = {}
+    if os.path.exists(path):
+        with open(path, "r", encoding="utf-8") as f:
+            hp = json.load(f)
+    qc = hp.get("quantization_config")
+    if qc:
+        method = qc.get("quant_method", "")
+        if method == "bitnet":
+            use = "load_bitnet_dir" if qc.get("quantization_mode", "offline") == "online" else "load_bitnet_packed_dir"
+        elif str(method).startswith("gptq") or "bits" in qc:
+            use = "load_gptq_dir"
+        else:
+            use = None
+        raise RuntimeError("config.json carries a quantization_config (quant_method {!r}): a quantised checkpoint, not dense weights{}".format(
+            method, ": use {}".format(use) if use else ""))
+    if hp.get("weight_bits", 0):
+        raise RuntimeError("config.json carries weight_bits = {}: BitNet master weights take the absmean rule: use load_bitnet_dir".format(hp["weight_bits"]))
+    parts = sorted(f for f in os.listdir(model_dir) if f.startswith("model") and f.endswith(".safetensors"))
+    if not parts:
+        raise RuntimeError("Models in {} not in safetensors format (torch .bin checkpoints: convert them to safetensors first)".format(model_dir))
+    index: Dict[str, TensorRef] = {}
+    order: List[str] = []
+    for part in parts:
+        for name, ref in safetensors_index(os.path.join(model_dir, part)).items():
+            if name not in index and _BITNET_LAYER.match(name):
+                order.append(name)
+            index[name] = ref
+    layers = []
+    for wname in order:
+        ref = index[wname]
+        if wname + "_scale" in index:
+            raise RuntimeError("{} comes with {}_scale: a pre-packed ternary checkpoint, not dense weights".format(wname, wname))
+        if ref.dtype not in ("F32", "F16", "BF16"):
+            raise RuntimeError("{} has dtype {}: F32, F16 or BF16 expected".format(wname, ref.dtype))
+        if len(ref.shape) != 2:
+            raise RuntimeError("{} has shape {}: a 2-D tensor expected".format(wname, ref.shape))
+        if (ref.end - ref.begin) != int(np.prod(ref.shape)) * np.dtype(_NP[ref.dtype]).itemsize:
+            raise RuntimeError("{}: shape {} does not match its {} bytes".format(wname, ref.shape, ref.end - ref.begin))
+        layers.append(DenseLayer(wname[:-len(".weight")], ref, ref.shape[0], ref.shape[1]))
+    if not layers:
+        raise RuntimeError("Models in {} hold no model.layers.*_proj.weight tensor".format(model_dir))
+    return DenseScan(layers)
+
+
+def load_dense_dir(model_dir: str, wrapper, bits: int, group_size: int = 128, zero_point: bool = True, dev_dtype=F16) -> Dict[str, "object"]:
+    """{layer name: Weights} for every layer ``scan_dense_dir`` finds: the matrix is uploaded as it lies in the file -- BF16 as its 16-bit
+    words, no conversion on the host, one upload per tensor -- and quantised to ``bits`` (1 to 4) with per-group scales by round to nearest
+    and packed on the GPU (``wrapper.register_dense``)."""
+    scan = scan_dense_dir(model_dir)
+    return {L.name: wrapper.register_dense(np.array(read_tensor(L.weight)), bits, group_size, zero_point, None, dev_dtype) for L in scan.layers}

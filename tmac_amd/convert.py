@@ -194,6 +194,77 @@ def bitnet_absmean_quant(w: np.ndarray, m_groups: int = 1, eps: float = 1e-5, sc
     return (t.astype(np.int8) + 2).astype(np.uint8).reshape(Mw, K), s.astype(np.float32)
 
 
+def _masters_f32(w: np.ndarray) -> np.ndarray:
+    """master weights in their storage form (float32, float16, uint16 = bf16 bit patterns) -> float32, exactly"""
+    w = np.asarray(w)
+    if w.dtype == np.uint16:
+        return bf16_bits_to_f32(w)
+    if w.dtype not in (np.float32, np.float16):
+        raise TypeError("w must be float32, float16 or uint16 (bf16 bit patterns)")
+    return w.astype(np.float32)
+
+
+def rtn_params(w: np.ndarray, bits: int, group_size: int, zero_point: bool = True, scale_f16: bool = False):
+    """The parameters of ``rtn_quant``: (scales float32 [Mw][K/gs], zq float32 [Mw][K/gs] -- the zero CODE, an integer value --, invalid:
+    bool [Mw][K/gs]).  The host reference of ``tmac_hip_rtn_params_dev``; include/tmac_hip.h states the rule operation by operation.  An
+    invalid group -- a master that is not finite, or a scale that is 0 or not finite (``scale_f16``: after its rounding to float16) --
+    carries the parameters of the all-zero group."""
+    w = _masters_f32(w)
+    if w.ndim != 2 or not 1 <= bits <= 4 or group_size <= 0 or group_size % 4 or w.shape[1] % group_size:
+        raise ValueError("w is [Mw][K], bits 1 to 4, group_size a positive multiple of 4 that divides K")
+    Mw, K = w.shape
+    g = w.reshape(Mw, K // group_size, group_size)
+    f32 = np.float32
+    maxq, one = f32(2 ** bits - 1), f32(1.0)
+    with np.errstate(invalid="ignore", over="ignore", divide="ignore", under="ignore"):
+        finite = np.isfinite(g).all(axis=2)
+        lo = np.where(finite, np.fmin(np.fmin.reduce(g, axis=2), f32(0.0)), f32(0.0))       # fmin / fmax: a NaN is dropped
+        hi = np.where(finite, np.fmax(np.fmax.reduce(g, axis=2), f32(0.0)), f32(0.0))
+        if not zero_point:
+            hi = np.fmax(np.abs(lo), hi)
+            lo = -hi
+        flat = (lo == 0) & (hi == 0)
+        lo, hi = np.where(flat, -one, lo), np.where(flat, one, hi)
+        s = ((hi - lo) / maxq).astype(f32)
+        tiny = s < np.finfo(f32).tiny
+        lo, hi, s = np.where(tiny, -one, lo), np.where(tiny, one, hi), np.where(tiny, f32(2.0) / maxq, s).astype(f32)
+        if scale_f16:
+            s = s.astype(np.float16).astype(f32)
+        ok = finite & (s != 0) & np.isfinite(s)
+        s0 = f32(2.0) / maxq
+        if scale_f16:
+            s0 = f32(np.float16(s0))
+        lo, s = np.where(ok, lo, -one).astype(f32), np.where(ok, s, s0).astype(f32)
+        zq = (np.rint((-lo) / s) + f32(0.0)).astype(f32) if zero_point else np.full(s.shape, 2 ** (bits - 1), f32)
+    return s, zq, ~ok
+
+
+def rtn_quant(w: np.ndarray, bits: int, group_size: int, zero_point: bool = True, scale_f16: bool = False):
+    """Dense master weights [Mw][K] (float32, float16, or uint16 holding bf16 bit patterns) -> (codes uint8 [Mw][K] in [0, 2^bits),
+    scales float32 [Mw][K/gs], zeros float32 [Mw][K/gs] in T-MAC's convention -- what ``Weights.from_codes`` takes; zeros None without
+    zero points) by per-group round to nearest: GPTQ's quantiser without the error search (``Quantizer.find_params`` with ``mse=False``,
+    then ``quantize``).  The host reference of ``tmac_hip_pack_rtn_dev`` and ``Weights.from_dense``, never the route.  Everything is
+    float32, one correctly rounded operation per step, in the device's order: ``scale = (hi - lo) / maxq`` from the group's minimum and
+    maximum (each taken with 0; symmetric about 0 without zero points), ``zq = rint(-lo / scale)`` (2^(bits-1) without zero points),
+    ``code = clip(rint(w / scale) + zq, 0, maxq)``, ``zero = (zq - 2^(bits-1)) * scale``, so ``w_real = (code - zq) * scale``.
+    ``scale_f16``: the scale is rounded to float16 BEFORE zq and the codes are derived (a handle that stores fp16 scales).  Invalid groups
+    (``rtn_params``) get the all-zero group's parameters; ``rtn_invalid`` counts them."""
+    s, zq, _ = rtn_params(w, bits, group_size, zero_point, scale_f16)
+    w = _masters_f32(w)
+    Mw, K = w.shape
+    f32 = np.float32
+    with np.errstate(invalid="ignore", over="ignore", divide="ignore", under="ignore"):
+        q = np.rint(w.reshape(Mw, -1, group_size) / s[:, :, None]) + zq[:, :, None]
+        codes = np.fmin(np.fmax(q, f32(0.0)), f32(2 ** bits - 1)).astype(np.uint8).reshape(Mw, K)       # fmax: a NaN gives 0
+        zeros = ((zq - f32(2 ** (bits - 1))) * s).astype(f32) if zero_point else None
+    return codes, s, zeros
+
+
+def rtn_invalid(w: np.ndarray, bits: int, group_size: int, zero_point: bool = True, scale_f16: bool = False) -> int:
+    """how many (row, group) pairs ``rtn_params`` calls invalid: what ``Weights.from_dense`` refuses, naming this count"""
+    return int(np.count_nonzero(rtn_params(w, bits, group_size, zero_point, scale_f16)[2]))
+
+
 def unpack_bitnet_packed(packed: np.ndarray) -> Tuple[np.ndarray, int]:
     """Packed ternary weights of the Hugging Face BitNet quantiser (``transformers.integrations.bitnet.pack_weights``), uint8 [Mw/4][K]
     -> (levels uint8 [Mw][K], invalid): the host reference of ``tmac_hip_pack_ternary_dev``, never the route.  With R4 = Mw / 4, weight

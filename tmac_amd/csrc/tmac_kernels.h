@@ -162,6 +162,15 @@ hipError_t launch_pack_codes(const void* codes, const void* scales, const void* 
 size_t absmean_partial_count(int Mw, int K, int m_groups);
 hipError_t launch_absmean(const void* W, int src, int Mw, int K, int m_groups, float eps, double* partials, float* scales_out, hipStream_t st);
 hipError_t launch_pack_dense(const void* W, int src, const float* scales, void* A_out, void* S_out, Dtype out_dt, const Shape& s, hipStream_t st);
+// Dense master weights W [Mw][K] -> W1 - W4 with per-group scales, round to nearest (the rule: tmac_pack.h; gs a multiple of 4 that divides
+// K).  launch_rtn_params: fp32 [Mw][K / gs] each -- the scale, the zero code zq and (zeros != NULL) T-MAC's zero of every (row, group);
+// invalid (device int32, NULL = not counted): the invalid groups are ADDED to it, at most one atomicAdd per workgroup; the caller zeroes it.
+// launch_pack_rtn: per-group scales only -- the codes under (scales, zq) straight into A_out, scales and zeros (NULL exactly without zero
+// points) into S_out as out_dt.
+hipError_t launch_rtn_params(const void* W, int src, int Mw, int K, int bits, int gs, int zero_point, int scale_f16, float* scales, float* zq, float* zeros,
+                             int32_t* invalid, hipStream_t st);
+hipError_t launch_pack_rtn(const void* W, int src, const float* scales, const float* zq, const float* zeros, void* A_out, void* S_out, Dtype out_dt,
+                           const Shape& s, hipStream_t st);
 // BitNet packed ternary checkpoints: packed uint8 [Mw / 4][K] (four weight rows per byte: tmac_pack.h; 16-byte aligned), bits = 2, unified
 // scales -- the levels straight into A_out, `scales` (fp32 [m_groups]) into S_out as out_dt.  invalid (device int32, NULL = not counted):
 // the fields of value 3 are ADDED to it, at most one atomicAdd per workgroup; the caller zeroes it.  The read-once kernel

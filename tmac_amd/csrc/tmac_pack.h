@@ -5,7 +5,8 @@
 // and packs whole matrices through it, byte for byte against tmac_amd/weights.py:preprocess_weights (tests/test_pack_cpu.py); the
 // kernels call the same functions.  The one piece of floating point: the BitNet absmean rule (master weights -> ternary levels), shared
 // the same way with tests/cpp/pack_dense_main.cc.  The packed ternary format of BitNet checkpoints (four weight rows per byte) is integers
-// again: tests/cpp/pack_ternary_main.cc.
+// again: tests/cpp/pack_ternary_main.cc.  Floating point once more: per-group round to nearest of dense masters to W1 - W4 codes (scale, zero
+// code, code, the fp16 rounding of the scale), shared with tests/cpp/pack_rtn_main.cc.
 //
 //   M-space row     r    = (o / 8) * 8 * bits + p * 8 + o % 8                                (o: weight row, p: bit plane)
 //   nibble(r, t)         = sum_ig bit_p(w[o][4 t + ig]) << ig
@@ -143,6 +144,66 @@ TMAC_PACK_HD uint32_t ternary_four(uint32_t bytes, int field, int* invalid) {
     const uint32_t three = v & (v >> 1) & 0x01010101u;      // 1 in the bytes whose field is 3
     *invalid = __builtin_popcount(three);
     return v + 0x01010101u - three;                         // ternary_level of each byte: no carry leaves a byte
+}
+
+// ---- dense master weights -> W1 - W4 codes with per-group scales: round to nearest -----------------------------------
+// GPTQ's quantiser without the error search (Quantizer.find_params with mse = False, then quantize).  For weight row o and group sg of gs
+// consecutive k, maxq = 2^bits - 1, every step one correctly rounded fp32 operation:
+//   lo = min(min_k w, 0), hi = max(max_k w, 0)              exact: the order of the reduction cannot matter
+//   symmetric (no zero points):  hi = max(|lo|, hi), lo = -hi, zq = 2^(bits-1)
+//   scale = (hi - lo) / maxq;   lo == hi == 0, or scale below the smallest normal fp32: lo = -1, hi = +1 (GPTQ's all-zero group)
+//   scale_f16: scale = fp16(scale) -- the scale that divides is the scale the handle stores
+//   asymmetric:  zq = rint(-lo / scale)                     ties to even; no clamp, as in GPTQ
+//   code = clamp(rint(w / scale) + zq, 0, maxq);   T-MAC's zero = (zq - 2^(bits-1)) * scale, w_real = (code - 2^(bits-1)) * scale - zero
+// A group is INVALID when a master of it is not finite or its scale is 0 or not finite (an fp16 scale that under- or overflowed): it gets
+// the parameters of the all-zero group and is counted.  Parameters live in fp32 [Mw][SG] arrays, SG = K / gs: rtn_param_index.
+TMAC_PACK_HD float round_to_f16(float v);
+TMAC_PACK_HD size_t rtn_param_index(int o, int sg, int SG) { return (size_t)o * SG + sg; }
+TMAC_PACK_HD float rtn_div(float a, float b) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    return __fdiv_rn(a, b);
+#else
+    return a / b;
+#endif
+}
+TMAC_PACK_HD bool rtn_finite(float v) { return v - v == 0.0f; }        // false for an infinity and for a NaN
+// lo <= 0 <= hi: the group's minimum and maximum, each already taken with 0 (fminf / fmaxf: a NaN master is dropped); finite: every master
+// of the group is.  Returns whether the group is valid; *scale and *zq of an invalid group are those of the all-zero group.
+TMAC_PACK_HD bool rtn_scale_zq(float lo, float hi, bool finite, int bits, int zero_point, int scale_f16, float* scale, float* zq) {
+    const float maxq = (float)((1 << bits) - 1);
+    if (!finite) lo = hi = 0.0f;
+    if (!zero_point) {
+        hi = fmaxf(fabsf(lo), hi);
+        lo = -hi;
+    }
+    if (lo == 0.0f && hi == 0.0f) { lo = -1.0f; hi = 1.0f; }
+    float s = rtn_div(hi - lo, maxq);
+    if (s < 1.17549435e-38f) { lo = -1.0f; hi = 1.0f; s = rtn_div(2.0f, maxq); }
+    if (scale_f16) s = round_to_f16(s);
+    const bool ok = finite && s != 0.0f && rtn_finite(s);
+    if (!ok) {
+        lo = -1.0f; hi = 1.0f;
+        s = rtn_div(2.0f, maxq);
+        if (scale_f16) s = round_to_f16(s);
+    }
+    *scale = s;
+    *zq = zero_point ? rintf(rtn_div(-lo, s)) + 0.0f : (float)(1 << (bits - 1));      // + 0: -0 (lo = +0) becomes +0
+    return ok;
+}
+// a NaN quotient -- a NaN master; its group is invalid -- gives code 0: fmaxf drops it
+TMAC_PACK_HD uint32_t rtn_code(float w, float scale, float zq, int bits) {
+    return (uint32_t)fminf(fmaxf(rintf(rtn_div(w, scale)) + zq, 0.0f), (float)((1 << bits) - 1));
+}
+TMAC_PACK_HD float rtn_zero(float scale, float zq, int bits) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    return __fmul_rn(zq - (float)(1 << (bits - 1)), scale);
+#else
+    return (zq - (float)(1 << (bits - 1))) * scale;
+#endif
+}
+// four masters of one table -> the `four` codes_nibble takes
+TMAC_PACK_HD uint32_t rtn_four(float w0, float w1, float w2, float w3, float scale, float zq, int bits) {
+    return codes_four(rtn_code(w0, scale, zq, bits), rtn_code(w1, scale, zq, bits), rtn_code(w2, scale, zq, bits), rtn_code(w3, scale, zq, bits));
 }
 
 #if defined(__HIPCC__)

@@ -16,6 +16,9 @@
 // BitNet packed ternary weights (uint8 [Mw / 4][K], four weight rows per byte): the codes kernel with a stage 1 that extracts a field
 // (k_pack_ternary_weights), or, where no group of 32 M-space rows straddles two fields, one load of every byte feeding four output tiles
 // (k_pack_ternary_weights_x4); fields without a ternary level are counted.
+// Dense master weights to W1 - W4 with per-group scales (round to nearest): the scale and zero code of every (row, group) from its minimum
+// and maximum (k_rtn_params; groups that cannot be quantised are counted), then the codes kernel with a stage 1 that quantises four masters
+// per lane under them (k_pack_rtn_weights) and the codes form's scales kernel.
 #include <hip/hip_fp16.h>
 #include <hip/hip_runtime.h>
 
@@ -395,6 +398,106 @@ __global__ __launch_bounds__(PACK_THREADS) void k_pack_ternary_weights_x4(const 
     for (int i = 0; i < 4; ++i) pack_store_groups<BITS>(lds + i * TILE, A_out, (i * R4 + pr0) / 16, (i + 1) * (R4 / 16), T, bm, kfactor);
 }
 
+// ---- dense master weights -> W1 - W4 with per-group scales: round to nearest (the rule: tmac_pack.h) -------------------------------------
+// EPL masters of consecutive k as fp32, exactly, in one 16-byte load: 4 of fp32, 8 of fp16 / bf16.  EPL = 4 of a 16-bit dtype (group sizes
+// that are no multiple of 8): load_masters' 8-byte load.
+template <int SRC, int EPL>
+__device__ __forceinline__ void load_masters_vec(const void* __restrict__ W, size_t e, float (&w)[EPL]) {
+    if constexpr (EPL == 4) {
+        load_masters<SRC>(W, e, w);
+    } else {
+        static_assert(SRC != pk::SRC_F32 && EPL == 8, "16 bytes per load");
+        const uint4 v = *reinterpret_cast<const uint4*>(static_cast<const uint16_t*>(W) + e);
+        const uint32_t u[4] = {v.x, v.y, v.z, v.w};
+#pragma unroll
+        for (int i = 0; i < 8; ++i) {
+            const uint16_t h = (uint16_t)(u[i / 2] >> (16 * (i % 2)));
+            w[i] = SRC == pk::SRC_F16 ? __half2float(__ushort_as_half(h)) : pk::bf16_bits_to_f32(h);
+        }
+    }
+}
+
+// The parameters: item = (weight row o, group sg) = o SG + sg owns the gs CONSECUTIVE masters [item gs, (item + 1) gs) of the row-major
+// matrix, and element `item` of each output (pk::rtn_param_index).  seg lanes (a power of two, <= 64: the host picks the smallest that
+// covers gs / EPL loads, or 64) share an item and a wave takes 64 / seg consecutive items per step: where seg EPL == gs -- gs 64 to 256
+// of fp32, 128 to 512 of fp16 / bf16 -- a step is one contiguous run of 64 16-byte loads.  min, max and "every master finite" meet in a
+// xor butterfly over the item's lanes; minimum and maximum are exact, so no order shows.  The loop bound is the wave's: every lane runs
+// every step.  Grid-stride over the items; nothing is read or written beyond `items`.  zeros (T-MAC's, for k_pack_codes_scales) may be
+// NULL; invalid groups are counted as the ternary pack counts (invalid_fold / invalid_report).
+template <int SRC, int EPL>
+__global__ __launch_bounds__(PACK_THREADS) void k_rtn_params(const void* __restrict__ W, float* __restrict__ scales, float* __restrict__ zq,
+                                                             float* __restrict__ zeros, int32_t* __restrict__ invalid, size_t items, int gs, int seg,
+                                                             int bits, int zero_point, int scale_f16) {
+    __shared__ int wave_bad[PACK_THREADS / 64];
+    const int lane = threadIdx.x % 64, sub = lane % seg, gl = lane / seg, per_wave = 64 / seg, vecs = gs / EPL;
+    const size_t wave = (size_t)blockIdx.x * (PACK_THREADS / 64) + threadIdx.x / 64, stride = (size_t)gridDim.x * (PACK_THREADS / 64) * per_wave;
+    int bad = 0;
+    for (size_t first = wave * per_wave; first < items; first += stride) {
+        const size_t item = first + gl;
+        float lo = 0.0f, hi = 0.0f, nf = 0.0f;      // nf: 0 while every master is finite (w * 0 is NaN for an infinity and for a NaN)
+        if (item < items)
+            for (int v = sub; v < vecs; v += seg) {
+                float w[EPL];
+                load_masters_vec<SRC, EPL>(W, item * gs + (size_t)v * EPL, w);
+#pragma unroll
+                for (int j = 0; j < EPL; ++j) {
+                    lo = fminf(lo, w[j]);
+                    hi = fmaxf(hi, w[j]);
+                    nf = __fmaf_rn(w[j], 0.0f, nf);
+                }
+            }
+#pragma unroll
+        for (int off = 32; off >= 1; off >>= 1)
+            if (off < seg) {
+                lo = fminf(lo, __shfl_xor(lo, off));
+                hi = fmaxf(hi, __shfl_xor(hi, off));
+                nf += __shfl_xor(nf, off);
+            }
+        if (sub == 0 && item < items) {
+            float s, z;
+            if (!pk::rtn_scale_zq(lo, hi, nf == 0.0f, bits, zero_point, scale_f16, &s, &z)) ++bad;
+            scales[item] = s;
+            zq[item] = z;
+            if (zeros) zeros[item] = pk::rtn_zero(s, z, bits);
+        }
+    }
+    invalid_fold(bad, wave_bad, invalid);
+    __syncthreads();
+    invalid_report(wave_bad, invalid);
+}
+
+// k_pack_codes_weights<BITS> with another stage 1: the lane that took the four code bytes of a table takes its four masters and quantises
+// them (pk::rtn_four) with the (scale, zq) of its row and group -- gs is a multiple of 4, so a table lies in one group; the lanes of a
+// group load the same two words.  No [Mw][K] code tensor exists anywhere.
+template <int SRC, int BITS>
+__global__ __launch_bounds__(PACK_THREADS) void k_pack_rtn_weights(const void* __restrict__ W, const float* __restrict__ scales, const float* __restrict__ zq,
+                                                                   uint8_t* __restrict__ A_out, int Mw, int K, int gs, int bm, int kfactor) {
+    __shared__ __attribute__((aligned(16))) uint8_t lds[PACK_ROWS * BITS * PACK_STRIDE];
+    const int T = K / 4, SG = K / gs;
+    const int o0 = blockIdx.y * PACK_ROWS, t0 = blockIdx.x * PACK_TABLES;
+    for (int idx = threadIdx.x; idx < PACK_ROWS * PACK_TABLES; idx += PACK_THREADS) {
+        const int ol = idx / PACK_TABLES, tl = idx % PACK_TABLES;
+        const int o = o0 + ol, t = t0 + tl;
+        uint32_t four = 0;
+        if (o < Mw && t < T) {
+            const size_t pi = pk::rtn_param_index(o, 4 * t / gs, SG);
+            float w[4];
+            load_masters<SRC>(W, (size_t)o * K + 4 * (size_t)t, w);      // K is a multiple of 4
+            four = pk::rtn_four(w[0], w[1], w[2], w[3], scales[pi], zq[pi], BITS);
+        }
+#pragma unroll
+        for (int p = 0; p < BITS; ++p) {
+            uint32_t v = pk::codes_nibble(four, p) << (4 * (tl % 8));
+            v |= __shfl_xor(v, 1);
+            v |= __shfl_xor(v, 2);
+            v |= __shfl_xor(v, 4);
+            if (tl % 8 == 0) *reinterpret_cast<uint32_t*>(lds + lds_row(p, ol) * PACK_STRIDE + tl / 2) = v;
+        }
+    }
+    __syncthreads();
+    pack_store_tile<BITS>(lds, A_out, Mw, T, bm, kfactor);
+}
+
 // ---- scales -------------------------------------------------------------------------------------------------------------------------
 // n contiguous elements (a multiple of 16 bytes, 16-byte aligned on both sides) as 16-byte accesses
 template <class T, int N>
@@ -594,6 +697,65 @@ hipError_t launch_pack_dense(const void* W, int src, const float* scales, void* 
         using ST = decltype(in_tag);
         using OT = decltype(out_tag);
         hipLaunchKernelGGL((k_pack_copy<ST, OT>), dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, (const ST*)scales, (OT*)S_out, n);
+    });
+    return hipGetLastError();
+}
+
+// ---- dense master weights, round to nearest --------------------------------------------------------------------------------------------
+hipError_t launch_rtn_params(const void* W, int src, int Mw, int K, int bits, int gs, int zero_point, int scale_f16, float* scales, float* zq, float* zeros,
+                             int32_t* invalid, hipStream_t st) {
+    if (bits < 1 || bits > 4 || gs <= 0 || gs % 4 || K % gs) return hipErrorInvalidValue;
+    const size_t items = (size_t)Mw * (K / gs);
+    const int epl = src != pk::SRC_F32 && gs % 8 == 0 ? 8 : 4, vecs = gs / epl;
+    int seg = 1;
+    while (seg < vecs && seg < 64) seg <<= 1;
+    // memory bound: enough workgroups of four waves to cover the items once, at most 2048 of them (the rest by the grid stride)
+    const size_t per_block = (size_t)(PACK_THREADS / 64) * (64 / seg), blocks = (items + per_block - 1) / per_block;
+    const dim3 g((unsigned)(blocks < 2048 ? blocks : 2048)), b(PACK_THREADS);
+    const int zp = zero_point ? 1 : 0, f16 = scale_f16 ? 1 : 0;
+    if (src == pk::SRC_F32) hipLaunchKernelGGL((k_rtn_params<pk::SRC_F32, 4>), g, b, 0, st, W, scales, zq, zeros, invalid, items, gs, seg, bits, zp, f16);
+    else if (src == pk::SRC_F16 && epl == 8) hipLaunchKernelGGL((k_rtn_params<pk::SRC_F16, 8>), g, b, 0, st, W, scales, zq, zeros, invalid, items, gs, seg, bits, zp, f16);
+    else if (src == pk::SRC_F16) hipLaunchKernelGGL((k_rtn_params<pk::SRC_F16, 4>), g, b, 0, st, W, scales, zq, zeros, invalid, items, gs, seg, bits, zp, f16);
+    else if (src == pk::SRC_BF16 && epl == 8) hipLaunchKernelGGL((k_rtn_params<pk::SRC_BF16, 8>), g, b, 0, st, W, scales, zq, zeros, invalid, items, gs, seg, bits, zp, f16);
+    else if (src == pk::SRC_BF16) hipLaunchKernelGGL((k_rtn_params<pk::SRC_BF16, 4>), g, b, 0, st, W, scales, zq, zeros, invalid, items, gs, seg, bits, zp, f16);
+    else return hipErrorInvalidValue;
+    return hipGetLastError();
+}
+
+namespace {
+template <int SRC>
+hipError_t launch_pack_rtn_weights(const void* W, const float* scales, const float* zq, uint8_t* A, const Shape& s, hipStream_t st) {
+    const dim3 g = weight_grid(s), b(PACK_THREADS);
+    switch (s.bits) {
+        case 1: hipLaunchKernelGGL((k_pack_rtn_weights<SRC, 1>), g, b, 0, st, W, scales, zq, A, s.Mw, s.K, s.gs, s.bm, s.kfactor); break;
+        case 2: hipLaunchKernelGGL((k_pack_rtn_weights<SRC, 2>), g, b, 0, st, W, scales, zq, A, s.Mw, s.K, s.gs, s.bm, s.kfactor); break;
+        case 3: hipLaunchKernelGGL((k_pack_rtn_weights<SRC, 3>), g, b, 0, st, W, scales, zq, A, s.Mw, s.K, s.gs, s.bm, s.kfactor); break;
+        case 4: hipLaunchKernelGGL((k_pack_rtn_weights<SRC, 4>), g, b, 0, st, W, scales, zq, A, s.Mw, s.K, s.gs, s.bm, s.kfactor); break;
+        default: return hipErrorInvalidValue;
+    }
+    return hipGetLastError();
+}
+}  // namespace
+
+hipError_t launch_pack_rtn(const void* W, int src, const float* scales, const float* zq, const float* zeros, void* A_out, void* S_out, Dtype out_dt,
+                           const Shape& s, hipStream_t st) {
+    if (s.m_groups >= 1 || (zeros != nullptr) != (s.zero_point != 0)) return hipErrorInvalidValue;
+    uint8_t* A = (uint8_t*)A_out;
+    hipError_t e;
+    switch (src) {
+        case pk::SRC_F32: e = launch_pack_rtn_weights<pk::SRC_F32>(W, scales, zq, A, s, st); break;
+        case pk::SRC_F16: e = launch_pack_rtn_weights<pk::SRC_F16>(W, scales, zq, A, s, st); break;
+        case pk::SRC_BF16: e = launch_pack_rtn_weights<pk::SRC_BF16>(W, scales, zq, A, s, st); break;
+        default: return hipErrorInvalidValue;
+    }
+    if (e != hipSuccess) return e;
+    const int SG = s.K / s.gs;      // the parameters into the blob: the scales kernel of the codes form
+    const size_t n = (size_t)SG * (s.Mw / 8);
+    by_dtypes(F32, out_dt, [&](auto in_tag, auto out_tag) {
+        using ST = decltype(in_tag);
+        using OT = decltype(out_tag);
+        hipLaunchKernelGGL((k_pack_codes_scales<ST, OT>), dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, (const ST*)scales, (const ST*)zeros, (OT*)S_out,
+                           s.Mw, SG, s.bits, s.bm);
     });
     return hipGetLastError();
 }

@@ -1,7 +1,8 @@
 // tmac_pack_host.cpp — the entry points in front of the pack kernels (tmac_pack.hip): GPTQ tensors or plain codes, in device memory, ->
 // the reference blob (tmac_hip_pack_*_dev) or straight to a registered handle (tmac_hip_register_weights_*_dev, through register_impl).
 // BitNet master weights (fp32 / fp16 / bf16) take the same two ways through the absmean rule (tmac_hip_*_absmean_dev), packed ternary
-// BitNet weights (four weight rows per byte) through tmac_hip_*_ternary_dev.
+// BitNet weights (four weight rows per byte) through tmac_hip_*_ternary_dev, dense master weights to W1 - W4 with per-group scales by
+// round to nearest through tmac_hip_*_rtn_dev.
 #include <cmath>
 
 #include "tmac_host.h"
@@ -282,6 +283,122 @@ extern "C" int32_t tmac_hip_register_weights_absmean_dev(tmac_hip_weights** out,
     HIP_TRY(dS.alloc(ref_scale_elems(s) * dt_size((Dtype)host_float)));
     rc = launch(s, in, dA.p, dS.p, host_float, st);
     if (rc == TMAC_HIP_OK) rc = register_impl(out, dA.p, dS.p, true, Mw, K, 2, cfg, host_float, dev_float, stream);
+    if (rc != TMAC_HIP_OK) (void)hipStreamSynchronize(st);
+    return rc;
+}
+
+// ---- dense master weights -> W1 - W4 with per-group scales: round to nearest (the rule: tmac_pack.h) ---------------------------------------
+namespace {
+
+struct RtnIn { const void* W; int src; };
+
+int32_t src_dtype_check(int src_dtype) {
+    if (src_dtype != TMAC_SRC_F32 && src_dtype != TMAC_SRC_F16 && src_dtype != TMAC_SRC_BF16)
+        return fail(TMAC_HIP_E_ARG, "src_dtype must be TMAC_SRC_F32, TMAC_SRC_F16 or TMAC_SRC_BF16");
+    return TMAC_HIP_OK;
+}
+
+// Everything that is refused before anything is written, in the order of check_dense: NULL required pointers, the source dtype, the scales'
+// form, the blob's dtype, make_shape's own refusals, alignment -- of the counter too, where one is given.
+int32_t check_rtn(Shape& s, const RtnIn& in, const void* A_out, const void* S_out, bool outs, const int32_t* invalid, int Mw, int K, int bits,
+                  const tmac_kcfg* cfg, tmac_dtype_t ref_float) {
+    if (!cfg) return fail(TMAC_HIP_E_ARG, "null kcfg");
+    const PackArg args[] = {{"W_dev", in.W, true}, {"A_ref_out", A_out, outs}, {"scales_ref_out", S_out, outs}, {"invalid_count_dev", invalid, false}};
+    for (const PackArg& a : args)
+        if (a.required && !a.p) return fail(TMAC_HIP_E_ARG, "%s is NULL", a.name);
+    int32_t rc = src_dtype_check(in.src);
+    if (rc) return rc;
+    if (cfg->m_groups >= 1)
+        return fail(TMAC_HIP_E_ARG, "m_groups = %d: round to nearest gives per-group scales (unified scales from master weights: "
+                                    "tmac_hip_register_weights_absmean_dev)", cfg->m_groups);
+    if (ref_float != TMAC_F32 && ref_float != TMAC_F16) return fail(TMAC_HIP_E_ARG, "host_float must be TMAC_F32 or TMAC_F16");
+    rc = make_shape(s, Mw, K, bits, cfg);
+    return rc ? rc : aligned_check(args, 4);
+}
+
+// The launches: the parameters of every (row, group) into scratch of our own, the counter zeroed on the stream in front of them, then the
+// pack.  The stream is waited for before the scratch goes.
+int32_t launch(const Shape& s, const RtnIn& in, int scale_f16, void* A_out, void* S_out, tmac_dtype_t ref_float, int32_t* invalid, hipStream_t st) {
+    const size_t items = (size_t)s.Mw * (s.K / s.gs);
+    DevBuf params;      // [scales][zq][zeros]: fp32 [Mw][K / gs] each
+    HIP_TRY(params.alloc(sizeof(float) * items * 3));
+    float *sc = params.as<float>(), *zq = sc + items, *zr = s.zero_point ? zq + items : nullptr;
+    if (invalid) HIP_TRY(hipMemsetAsync(invalid, 0, sizeof(int32_t), st));
+    hipError_t e = launch_rtn_params(in.W, in.src, s.Mw, s.K, s.bits, s.gs, s.zero_point, scale_f16, sc, zq, zr, invalid, st);
+    if (e == hipSuccess) e = launch_pack_rtn(in.W, in.src, sc, zq, zr, A_out, S_out, (Dtype)ref_float, s, st);
+    if (e != hipSuccess) return fail(TMAC_HIP_E_RUNTIME, "pack_rtn: %s", hipGetErrorString(e));
+    HIP_TRY(hipStreamSynchronize(st));
+    return TMAC_HIP_OK;
+}
+
+}  // namespace
+
+extern "C" int32_t tmac_hip_rtn_params_dev(const void* W_dev, tmac_src_dtype_t src_dtype, int Mw, int K, int bits, int group_size, int zero_point,
+                                           int scale_f16, float* scales_out_dev, float* zq_out_dev, int32_t* invalid_count_dev, void* stream) {
+    const PackArg args[] = {{"W_dev", W_dev, true}, {"scales_out_dev", scales_out_dev, true}, {"zq_out_dev", zq_out_dev, true},
+                            {"invalid_count_dev", invalid_count_dev, false}};
+    for (const PackArg& a : args)
+        if (a.required && !a.p) return fail(TMAC_HIP_E_ARG, "%s is NULL", a.name);
+    int32_t rc = src_dtype_check(src_dtype);
+    if (rc) return rc;
+    if (bits < 1 || bits > 4) return fail(TMAC_HIP_E_ARG, "bits=%d: 1 to 4 are served", bits);
+    if (Mw <= 0 || K <= 0 || group_size <= 0 || group_size % 4 || K % group_size)
+        return fail(TMAC_HIP_E_ARG, "Mw=%d, K=%d and group_size=%d must be positive, group_size a multiple of 4 that divides K", Mw, K, group_size);
+    rc = aligned_check(args, 4);
+    if (rc) return rc;
+    rc = ensure_device();
+    if (rc) return rc;
+    rc = defer_barrier();
+    if (rc) return rc;
+    hipStream_t st = (hipStream_t)stream;
+    if (invalid_count_dev) HIP_TRY(hipMemsetAsync(invalid_count_dev, 0, sizeof(int32_t), st));
+    const hipError_t e = launch_rtn_params(W_dev, src_dtype, Mw, K, bits, group_size, zero_point, scale_f16, scales_out_dev, zq_out_dev, nullptr,
+                                           invalid_count_dev, st);
+    return e == hipSuccess ? TMAC_HIP_OK : fail(TMAC_HIP_E_RUNTIME, "rtn_params: %s", hipGetErrorString(e));
+}
+
+extern "C" int32_t tmac_hip_pack_rtn_dev(const void* W_dev, tmac_src_dtype_t src_dtype, int Mw, int K, int bits, const tmac_kcfg* cfg, void* A_ref_out,
+                                         void* scales_ref_out, tmac_dtype_t host_float, int32_t* invalid_count_dev, void* stream) {
+    const RtnIn in{W_dev, src_dtype};
+    Shape s;
+    int32_t rc = check_rtn(s, in, A_ref_out, scales_ref_out, true, invalid_count_dev, Mw, K, bits, cfg, host_float);
+    if (rc) return rc;
+    rc = ensure_device();
+    if (rc) return rc;
+    rc = defer_barrier();
+    return rc ? rc : launch(s, in, host_float == TMAC_F16, A_ref_out, scales_ref_out, host_float, invalid_count_dev, (hipStream_t)stream);
+}
+
+extern "C" int32_t tmac_hip_register_weights_rtn_dev(tmac_hip_weights** out, const void* W_dev, tmac_src_dtype_t src_dtype, int Mw, int K, int bits,
+                                                     const tmac_kcfg* cfg, tmac_dtype_t host_float, tmac_dtype_t dev_float, void* stream) {
+    if (!out) return fail(TMAC_HIP_E_ARG, "out is NULL");
+    const RtnIn in{W_dev, src_dtype};
+    Shape s;
+    int32_t rc = check_rtn(s, in, nullptr, nullptr, false, nullptr, Mw, K, bits, cfg, host_float);
+    if (rc) return rc;
+    if (dev_float != TMAC_F32 && dev_float != TMAC_F16) return fail(TMAC_HIP_E_ARG, "dev_float must be TMAC_F32 or TMAC_F16");
+    rc = ensure_device();
+    if (rc) return rc;
+    rc = defer_barrier();       // W_dev may have been written by queued work
+    if (rc) return rc;
+    hipStream_t st = (hipStream_t)stream;
+    DevBuf dA, dS, dN;  // as register_from: ours on every return path
+    HIP_TRY(dA.alloc(ref_weight_bytes(s)));
+    HIP_TRY(dS.alloc(ref_scale_elems(s) * dt_size((Dtype)host_float)));
+    HIP_TRY(dN.alloc(sizeof(int32_t)));
+    // the scale that divides is the scale the handle stores: rounded to fp16 up front wherever the blob or the handle keeps fp16 scales
+    rc = launch(s, in, host_float == TMAC_F16 || dev_float == TMAC_F16, dA.p, dS.p, host_float, dN.as<int32_t>(), st);
+    if (rc != TMAC_HIP_OK) {
+        (void)hipStreamSynchronize(st);
+        return rc;
+    }
+    int32_t invalid = 0;
+    HIP_TRY(hipMemcpyAsync(&invalid, dN.p, sizeof(int32_t), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    if (invalid)
+        return fail(TMAC_HIP_E_ARG, "master weights hold %d groups that cannot be quantised (a master that is not finite, or a scale that is 0 or "
+                                    "not finite in the scales' dtype)", invalid);
+    rc = register_impl(out, dA.p, dS.p, true, Mw, K, bits, cfg, host_float, dev_float, stream);
     if (rc != TMAC_HIP_OK) (void)hipStreamSynchronize(st);
     return rc;
 }

@@ -306,6 +306,46 @@ def pack_ternary(packed, scale, cfg: Optional[KCfg] = None, ref_dtype=F32, strea
     return (A, S, n[:1]) if count_invalid else (A, S)
 
 
+def _dense_args(weight, bits, group_size, zero_point, cfg, act_group_size):
+    """device tensor, shape and configuration of an unquantised matrix (``_masters_on_device`` says what it may be).  Without a cfg:
+    per-group scales of ``group_size``, ``convert.default_bm``, kfactor 16."""
+    from . import convert
+    w, src = _masters_on_device(weight)
+    Mw, K = int(w.shape[0]), int(w.shape[1])
+    if cfg is None:
+        cfg = KCfg.make(Mw, K, int(bits), convert.default_bm(int(bits), Mw), 16, int(group_size), act_group_size, bool(zero_point))
+    return w, src, Mw, K, cfg
+
+
+def rtn_params(weight, bits: int, group_size: int, zero_point: bool = True, scale_f16: bool = False, stream=None, count_invalid: bool = False):
+    """The round-to-nearest parameters of an unquantised matrix [Mw][K] (fp32 / fp16 / bf16, see ``Weights.from_dense``): (scales, zq),
+    fp32 [Mw][K/group_size] CUDA tensors -- ``convert.rtn_params``'s, bit for bit (tmac_hip_rtn_params_dev).  ``count_invalid``: a third
+    result, an int32 CUDA tensor of one element -- the number of groups that cannot be quantised.  Asynchronous."""
+    import torch
+    w, src = _masters_on_device(weight)
+    Mw, K = int(w.shape[0]), int(w.shape[1])
+    sg = K // int(group_size) if int(group_size) > 0 else 0
+    sc = torch.empty((Mw, sg), dtype=torch.float32, device="cuda")
+    zq = torch.empty((Mw, sg), dtype=torch.float32, device="cuda")
+    n = torch.empty(4, dtype=torch.int32, device="cuda") if count_invalid else None      # 16 bytes: the call's alignment rule
+    check(B.lib().tmac_hip_rtn_params_dev(_ptr(w), src, Mw, K, int(bits), int(group_size), int(bool(zero_point)), int(bool(scale_f16)), _ptr(sc), _ptr(zq),
+                                          _ptr(n), _stream(stream)))
+    return (sc, zq, n[:1]) if count_invalid else (sc, zq)
+
+
+def pack_rtn(weight, bits: int, group_size: int = 128, zero_point: bool = True, cfg: Optional[KCfg] = None, ref_dtype=F32, act_group_size: int = 64,
+             stream=None, count_invalid: bool = False):
+    """An unquantised matrix -> the reference blob of its round-to-nearest codes, on the GPU (tmac_hip_pack_rtn_dev): (A_ref uint8,
+    scales_ref) as ``pack_codes`` returns them, exactly ``weights.preprocess_weights(*convert.rtn_quant(weight, bits, group_size,
+    zero_point, ref_dtype == F16))`` -- a blob of fp16 scales holds the scales that divided.  ``count_invalid``: as in ``rtn_params``."""
+    import torch
+    w, src, Mw, K, cfg = _dense_args(weight, bits, group_size, zero_point, cfg, act_group_size)
+    A, S = _blob_buffers(Mw, K, int(bits), cfg, ref_dtype)
+    n = torch.empty(4, dtype=torch.int32, device="cuda") if count_invalid else None
+    check(B.lib().tmac_hip_pack_rtn_dev(_ptr(w), src, Mw, K, int(bits), C.byref(cfg), _ptr(A), _ptr(S), ref_dtype, _ptr(n), _stream(stream)))
+    return (A, S, n[:1]) if count_invalid else (A, S)
+
+
 class Weights:
     """One weight matrix resident on the GPU (tmac_hip_register_weights)."""
 
@@ -392,6 +432,21 @@ class Weights:
         h = C.c_void_p()
         check(B.lib().tmac_hip_register_weights_ternary_dev(C.byref(h), _ptr(pk), _ptr(sc), Mw, K, C.byref(cfg), F32, dev_dtype, _stream(stream)))
         return cls._adopt(h, Mw, K, 2, cfg)
+
+    @classmethod
+    def from_dense(cls, weight, bits: int, group_size: int = 128, zero_point: bool = True, cfg: Optional[KCfg] = None, dev_dtype=F16,
+                   act_group_size: int = 64, stream=None) -> "Weights":
+        """Register an UNQUANTISED matrix [Mw][K] -- a torch tensor in fp32, fp16 or bf16, or a numpy array uploaded as it is (float32,
+        float16, uint16 = bf16 bit patterns) -- as a W1 - W4 handle with per-group scales: quantised by per-group round to nearest
+        (GPTQ's quantiser without the error search) and packed on the GPU (tmac_hip_register_weights_rtn_dev; include/tmac_hip.h states
+        the rule).  The handle is the one ``from_codes(*convert.rtn_quant(weight, bits, group_size, zero_point, dev_dtype == F16), bits,
+        cfg, dev_dtype)`` gives: with fp16 device scales the scale is rounded to fp16 before the codes are derived.  A group that cannot
+        be quantised -- a master that is not finite, a scale that is 0 or not finite in the scales' dtype -- is refused (TMACHipError
+        naming the count).  Without a ``cfg``: ``convert.default_bm``, kfactor 16; with one, its group_size and zero_point count."""
+        w, src, Mw, K, cfg = _dense_args(weight, bits, group_size, zero_point, cfg, act_group_size)
+        h = C.c_void_p()
+        check(B.lib().tmac_hip_register_weights_rtn_dev(C.byref(h), _ptr(w), src, Mw, K, int(bits), C.byref(cfg), F32, dev_dtype, _stream(stream)))
+        return cls._adopt(h, Mw, K, int(bits), cfg)
 
     def __init__(self, A_ref, scales_ref, Mw: int, K: int, bits: int, cfg: KCfg, scales_dtype=F32, dev_dtype=F32,
                  on_device: bool = False, stream=None):
@@ -739,6 +794,12 @@ class TMACGeMMWrapper:
                                stream=None) -> Weights:
         """``Weights.from_bitnet_packed``: a layer of a packed ternary BitNet checkpoint (uint8 [Mw/4][K] + its weight_scale) -> handle"""
         return Weights.from_bitnet_packed(packed, weight_scale, cfg, linear_class, dev_dtype, stream)
+
+    def register_dense(self, weight, bits: int, group_size: int = 128, zero_point: bool = True, cfg: Optional[KCfg] = None, dev_dtype=F16,
+                       stream=None) -> Weights:
+        """``Weights.from_dense`` with this wrapper's act_group_size: an unquantised matrix (fp32 / fp16 / bf16) -> a W1 - W4 handle with
+        per-group scales, quantised (round to nearest) and packed on the GPU"""
+        return Weights.from_dense(weight, bits, group_size, zero_point, cfg, dev_dtype, self._act_group_size, stream)
 
     def llama_cpp_init(self, B_dev, M: int, K: int, N: int, bits: int, act_group_size: Optional[int] = None,
                        act_dtype: Optional[int] = None, stream=None, kperm: Optional[KPerm] = None) -> None:

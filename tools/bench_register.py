@@ -14,7 +14,9 @@ the tool exits 1 when it does not hold.
 --bitnet: BitNet-3B master weights (fp16 / bf16, on the device) -> handle instead: see bitnet() below.
 --bitnet-packed: packed ternary BitNet weights (four weight rows per byte) -> handle, and the two pack kernels beside the codes kernel
 and a copy: see bitnet_packed() below.
-usage: bench_register.py [--out FILE] [--shapes o,qkv,gate_up,down] [--bits 2,4] [--skip-host] | --bitnet [--out FILE] | --bitnet-packed [--out FILE]"""
+--dense: unquantised fp16 matrices of the same llama-2-7B shapes -> W2 / W4 handles by per-group round to nearest: see dense() below.
+usage: bench_register.py [--out FILE] [--shapes o,qkv,gate_up,down] [--bits 2,4] [--skip-host] | --bitnet [--out FILE] | --bitnet-packed [--out FILE]
+       | --dense [--out FILE] [--shapes ...] [--bits 2,4] [--skip-host]"""
 import argparse
 import ctypes as C
 import math
@@ -184,6 +186,71 @@ def bitnet(out):
     return 0
 
 
+def dense(out, shapes, bits_list, skip_host):
+    """Unquantised llama-2-7B matrices -> W2 / W4 handles with per-group scales (group size 128, zero points, fp16 device scales), fp16
+    masters ON THE DEVICE.  Host clock with a device synchronise on either side, ms, median of ten after a warm-up, one process:
+      (a) Weights.from_dense (k_rtn_params + k_pack_rtn_weights + the scales kernel + re-tile);
+      (b) Weights.from_codes on codes, scales and zeros already on the device (the existing device pack: reads Mw K code bytes);
+      (d) hipMemcpyAsync device-to-device of the masters' bytes: what reading them once and writing as much costs;
+    and (c) the host route, ONE run (it takes seconds): download + convert.rtn_quant + weights.preprocess_weights +
+    tmac_hip_register_weights.  (a) reads the masters twice (2 x 2 Mw K bytes) where (b) reads Mw K bytes once: the expectation is (a)
+    near (b) plus one or two (d), orders of magnitude below (c).  No threshold: the figures are recorded."""
+    hip = hip_runtime()
+    st = torch.cuda.current_stream().cuda_stream
+
+    def median10(fn, free=False):
+        ts = []
+        for i in range(11):
+            t, r = wall_ms(fn)
+            if free:
+                r.free()
+            if i:
+                ts.append(t)
+        return float(np.median(ts))
+
+    lines = ["# tools/bench_register.py --dense: fp16 matrices on the device -> W2 / W4 handles, per-group round to nearest.  Host-clock ms with a",
+             "# device synchronise on either side, median of ten after a warm-up; (c) one run.  (a) from_dense  (b) from_codes on device codes",
+             f"# (c) host route  (d) D2D copy of the masters' bytes.  device: {torch.cuda.get_device_name(0)}; group size {GS}, zero points, fp16 scales",
+             "shape     bits  Mw     K      | (a) dense_ms  (b) codes_ms  (d) copy_ms  (c) host_ms | (a)-(b) in (d)  (a)/(b)  (c)/(a)"]
+    for name in shapes:
+        Mw, K = SHAPES[name]
+        w32 = (np.random.default_rng(Mw + K).standard_normal((Mw, K)) * 0.02).astype(np.float32)
+        wd = torch.from_numpy(w32).cuda().half()
+        dst = torch.empty_like(wd)
+        nbytes = wd.numel() * 2
+
+        def copy():
+            rc = hip.hipMemcpyAsync(C.c_void_p(dst.data_ptr()), C.c_void_p(wd.data_ptr()), C.c_size_t(nbytes), 3, C.c_void_p(st))     # 3: device to device
+            if rc:
+                raise RuntimeError(f"hipMemcpyAsync: {rc}")
+        td = median10(copy)
+        for bits in bits_list:
+            cfg = KCfg.make(Mw, K, bits, convert.default_bm(bits, Mw), 16, GS, AGS, True)
+            ta = median10(lambda: tmac_amd.Weights.from_dense(wd, bits, GS, True, cfg, F16, AGS), free=True)
+            stored = wd.cpu().numpy()
+            codes, sc, zr = convert.rtn_quant(stored, bits, GS, True, True)
+            cd, sd, zd = torch.from_numpy(codes).cuda(), torch.from_numpy(sc).cuda(), torch.from_numpy(zr).cuda()
+            tb = median10(lambda: tmac_amd.Weights.from_codes(cd, sd, zd, bits, cfg, F16, AGS), free=True)
+            if skip_host:
+                tc = float("nan")
+            else:
+                def host():
+                    c, s, z = convert.rtn_quant(wd.cpu().numpy(), bits, GS, True, True)
+                    A, S = weights.preprocess_weights(c, s, z, bits=bits, bm=cfg.bm, kfactor=cfg.kfactor)
+                    return tmac_amd.Weights(A, S, Mw, K, bits, cfg, scales_dtype=F32, dev_dtype=F16)
+                tc, h = wall_ms(host)
+                h.free()
+            line = (f"{name:9s} {bits:4d}  {Mw:5d}  {K:5d}  | {ta:12.3f}  {tb:12.3f}  {td:11.3f}  {tc:11.1f} | {(ta - tb) / td:14.2f}  {ta / tb:7.2f}  "
+                    f"{tc / ta:7.0f}")
+            print(line, flush=True)
+            lines.append(line)
+    if out:
+        os.makedirs(os.path.dirname(os.path.abspath(out)), exist_ok=True)
+        with open(out, "w") as f:
+            f.write("\n".join(lines) + "\n")
+    return 0
+
+
 # bitnet-b1.58-2B-4T (q/o, k/v, gate/up, down) and the 3B preset, (Mw, K): Mw / 4 is a multiple of 16 at every one of them
 BITNET_PACKED_SHAPES = {"2b4t_qo": (2560, 2560), "2b4t_kv": (640, 2560), "2b4t_gate_up": (6912, 2560), "2b4t_down": (2560, 6912),
                         "3b_attn": (3200, 3200), "3b_gate_up": (8640, 3200), "3b_down": (3200, 8640)}
@@ -294,6 +361,7 @@ def main():
     ap.add_argument("--out", default="")
     ap.add_argument("--bitnet-packed", action="store_true", help="packed ternary BitNet weights instead: from_bitnet_packed, from_codes, from_bitnet, the kernels alone")
     ap.add_argument("--bitnet", action="store_true", help="the BitNet-3B master-weight shapes instead: host route, from_bitnet, from_codes")
+    ap.add_argument("--dense", action="store_true", help="unquantised fp16 llama-2-7B matrices instead: from_dense, from_codes, the host route, a copy")
     ap.add_argument("--shapes", default="o,qkv,gate_up,down")
     ap.add_argument("--bits", default="2,4")
     ap.add_argument("--skip-host", action="store_true", help="leave (a) out (it takes seconds per shape)")
@@ -303,6 +371,8 @@ def main():
         return bitnet(args.out)
     if args.bitnet_packed:
         return bitnet_packed(args.out)
+    if args.dense:
+        return dense(args.out, args.shapes.split(","), [int(b) for b in args.bits.split(",")], args.skip_host)
     hip = hip_runtime()
     lines = ["# tools/bench_register.py: GPTQ tensors -> handle.  (a) host seconds, one run; (b) host-clock ms around upload + device-side",
              "# registration; (c) pack kernels alone, device events, bytes read + written per second, beside hipMemcpyAsync D2D of the same bytes.",
