@@ -824,7 +824,14 @@ int32_t tmac_hip_tune_clear(void);
  * preprocessor.  Tile weights are uploaded on first use and cached by host pointer (llama.cpp
  * keeps weights mmap'd for the life of the model); tmac_hip_cache_clear() drops the cache.
  * Configuration (group_size, zero_point, act_group_size) comes from the loaded kcfg
- * (tmac_hip_load_kcfg / $TMAC_KCFG_FILE), exactly as the reference couples kernels to kcfg.ini. */
+ * (tmac_hip_load_kcfg / $TMAC_KCFG_FILE), exactly as the reference couples kernels to kcfg.ini.
+ * What a tile call answers for (tests/test_gpu_hostptr_purity.py):
+ *   - the LUT: always the bytes it is passed.  QLUT, LUT_Scales and LUT_Biases are compared in full with the LUT the cached
+ *     result was computed from, on every tile call, whichever buffers they arrive in (about 6 us of a 42 us 4096 x 4096 GEMV
+ *     of 64 tile calls, profiles/hostptr_purity.txt);
+ *   - the weights and scales behind a cached pointer: taken as unchanged.  A replacement that changes every 16-byte window
+ *     of a tile's weights or of its scales -- a model reloaded at the same addresses, two tiles exchanged, new scales -- is
+ *     detected from a sample and the tile registered afresh; after any other in-place edit call tmac_hip_cache_clear(). */
 int32_t qgemm_lut_int8(int m, int k, int n, int b, void* A, void* LUT, void* Scales, void* LUT_Scales,
                        void* LUT_Biases, void* C);
 int32_t preprocessor_int8(int m, int k, int n, int b, void* B, void* LUT_Scales, void* LUT_Biases, void* QLUT);

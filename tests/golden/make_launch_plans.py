@@ -7,7 +7,9 @@ PROGRAM answers the queries of tests/cpp/launch_plan_main.cc; without --exe that
 file was recorded with a PROGRAM built around the selection code as it stood before tmac_launch_plan.cpp existed (quad_config, qlaunch_nr,
 qlaunch_xf_nr, qlaunch_xf_cfg, rows_plan and launch_gemv_rows' waves-per-quad and grid rule inside tmac_quad.hip / tmac_rows.hip, the launch
 replaced by a print of its template arguments, grid and LDS bytes); run on the tree, this script must reproduce it byte for byte
-(tests/test_launch_plan_cpu.py).
+(tests/test_launch_plan_cpu.py).  One rule has changed since and the file was recorded again from the tree: a k_gemv_quad launch that
+copies the workspace's LUT image (build_lut = 0) used to be refused for K > 12288 by the builder's limit of six tables per thread, which
+kept K = 14336 from the split and host-pointer entry points; those 908 answers are plans now and every other answer is as it was.
 
 The file: "axes" (named lists of values), "answers" (the distinct answer lines) and "cases": [query template, axis, answer index per value
 of the axis] -- the query is the template with {} replaced by the value.

@@ -93,6 +93,12 @@ def fixtures(tmp_path, Mw, K, bits, bm, N=1, seed=3):
     A.tofile(os.path.join(d, "A.bin")); S.astype(np.float32).tofile(os.path.join(d, "S.bin"))
     np.concatenate([A.reshape(-1), S.astype(np.float32).view(np.uint8).reshape(-1)]).tofile(os.path.join(d, "blob.bin"))
     case["B"].astype(np.float32).tofile(os.path.join(d, "x.bin")); ref.astype(np.float32).tofile(os.path.join(d, "ref.bin"))
+    # a second matrix of the same shape, to be copied over the first at the same addresses (hostptr_threads.cc), and the oracle's result for it
+    case2 = orc.make_case(seed + 1000, Mw, K, N=N, bits=bits, fp16_values=False)
+    A2 = orc.preprocess_weights(case2["w"], bits, bm, 16)
+    S2 = orc.preprocess_scales(case2["sc"], case2["zr"], bits, bm)
+    ref2 = orc.qgemm_float(A2, q, S2, ls, lb, Mw, K, N, bits, bm, 16, 128, 64, True)
+    A2.tofile(os.path.join(d, "A2.bin")); S2.astype(np.float32).tofile(os.path.join(d, "S2.bin")); ref2.astype(np.float32).tofile(os.path.join(d, "ref2.bin"))
     convert.write_kcfg(os.path.join(d, "kcfg.ini"), [[bits, Mw, K, 1, -1], [bits, Mw, K, N, -1]] if N != 1 else [[bits, Mw, K, 1, -1]],
                        bm={(bits, Mw, K): bm})
     return d
@@ -108,6 +114,7 @@ def test_reference_wrapper_host_pointers_eight_threads(tm, tmp_path):
     assert r.returncode == 0, r.stdout + r.stderr
     line = [x for x in r.stdout.splitlines() if x.startswith("RESULT")][0].split()
     assert float(line[2]) <= 2e-5 and int(line[6]) > Mw // 2
+    assert line[7] == "reload_rel_err" and float(line[8]) <= 2e-5, r.stdout      # a second matrix copied over A and S: its own reference
     print(r.stdout)
 
 

@@ -19,8 +19,13 @@ struct TileKey {
 // host-pointer layer learns the matrices behind the tiles: tiles whose weight and scale pointers are contiguous (the
 // reference layout stores a matrix tile after tile) form a RUN; once a run has been seen whole, the first tile call
 // that arrives with a new LUT computes the run's entire output in one launch and the following tile calls are served
-// from that result as long as the LUT they pass is the one it was computed from (same three pointers and a 192-byte sample
-// of the table bytes on the shared-lock fast path; scales, biases and the whole table are compared when a pointer differs).
+// from that result as long as the LUT they pass is, byte for byte, the one it was computed from: the table, its scales and its
+// biases are compared in full on every tile call (lut_matches), whichever buffers they arrive in.  A tile call answers for the
+// LUT bytes it is given.
+// The WEIGHTS and SCALES behind a cached pointer are taken as unchanged (re-reading every tile on every call would undo the
+// cache).  A sample is still looked at, so that a replacement which changes every 16-byte window of a tile's weights or of its
+// scales -- a model reloaded at the same addresses, two tiles exchanged, new scales -- is detected and re-registered; any other
+// in-place edit needs tmac_hip_cache_clear().
 // verbatim sample of a tile's weight and scale bytes (4 x 16 + 2 x 16 bytes): what the per-call staleness check of a grouped
 // tile compares (a memcmp of 96 bytes instead of a 192-byte hash per tile call)
 struct TileBytes { unsigned char b[96]; };
@@ -79,11 +84,10 @@ struct HostRoute {
     std::shared_mutex mu;
     unsigned long long use_clock = 0;
     size_t cache_dev_bytes = 0, cache_cap_bytes = 0;
-    // host copy of the LUT (qlut | lut_scales | lut_biases) that `ws` currently holds, its generation, and the caller's buffers it was taken from
+    // host copy of the LUT (qlut | lut_scales | lut_biases) that `ws` currently holds, and its generation
     std::vector<unsigned char> lut_host;
     int lut_k = 0, lut_n = 0, lut_ags = 0;
     unsigned long long lut_gen = 0;
-    const void *lut_q = nullptr, *lut_ls = nullptr, *lut_lb = nullptr;
     // completion flag in pinned host memory that the last launch of a call sets and the calling thread spins on
     uint32_t* flag = nullptr;
     uint32_t flag_gen = 0;
@@ -164,21 +168,18 @@ static int32_t host_pin(size_t bytes) {
     return TMAC_HIP_OK;
 }
 
-// Is the LUT the caller passes the one the workspace holds?  Same buffers as at the last full comparison and a matching
-// sample: yes (llama.cpp builds the LUT once per matmul and passes it to every tile call).  Otherwise compare in full.
-static bool lut_sample_ok(const void* q, size_t nq) {
-    const size_t n = nq < 64 ? nq : 64;
-    return memcmp(H.lut_host.data(), q, n) == 0 && memcmp(H.lut_host.data() + (nq - n) / 2, (const char*)q + (nq - n) / 2, n) == 0 &&
-           memcmp(H.lut_host.data() + nq - n, (const char*)q + nq - n, n) == 0;
-}
-static bool lut_is_current(const void* q, const void* ls, const void* lb, int k, int n, int ags) {
-    if (H.lut_k != k || H.lut_n != n || H.lut_ags != ags) return false;
-    const size_t nq = (size_t)n * (k / 4) * 16, ns = sizeof(float) * (size_t)n * (k / ags);
+// Is the LUT the caller passes the one the workspace holds?  Decided by the bytes alone: the whole table, its scales and its biases
+// against the host copy taken when the workspace was written.  (A sample of the table cannot tell: two activations of one act group
+// swapped across two tables leave scales, biases and all but 32 table bytes as they were.)  Caller holds H.mu, shared or exclusive.
+static bool lut_matches(const void* q, const void* ls, const void* lb, int k, int n) {
+    if (H.lut_k != k || H.lut_n != n || H.lut_ags <= 0) return false;
+    const size_t nq = (size_t)n * (k / 4) * 16, ns = sizeof(float) * (size_t)n * (k / H.lut_ags);
     if (H.lut_host.size() != nq + 2 * ns) return false;
-    if (q == H.lut_q && ls == H.lut_ls && lb == H.lut_lb)
-        return lut_sample_ok(q, nq) && memcmp(H.lut_host.data() + nq, ls, ns) == 0 && memcmp(H.lut_host.data() + nq + ns, lb, ns) == 0;
     return memcmp(H.lut_host.data(), q, nq) == 0 && memcmp(H.lut_host.data() + nq, ls, ns) == 0 &&
            memcmp(H.lut_host.data() + nq + ns, lb, ns) == 0;
+}
+static bool lut_is_current(const void* q, const void* ls, const void* lb, int k, int n, int ags) {
+    return H.lut_ags == ags && lut_matches(q, ls, lb, k, n);
 }
 static void lut_remember(const void* q, const void* ls, const void* lb, int k, int n, int ags) {
     const size_t nq = (size_t)n * (k / 4) * 16, ns = sizeof(float) * (size_t)n * (k / ags);
@@ -187,7 +188,6 @@ static void lut_remember(const void* q, const void* ls, const void* lb, int k, i
     memcpy(H.lut_host.data() + nq, ls, ns);
     memcpy(H.lut_host.data() + nq + ns, lb, ns);
     H.lut_k = k; H.lut_n = n; H.lut_ags = ags;
-    H.lut_q = q; H.lut_ls = ls; H.lut_lb = lb;
     ++H.lut_gen;
 }
 
@@ -298,6 +298,9 @@ static HostRun* build_run(const TileKey& key, const tmac_kcfg& cfg, int Mw_tile,
         auto it = H.tiles.find(kk);
         if (it == H.tiles.end() || it->second.run || !it->second.w) return H.tiles.end();
         if ((const char*)it->second.S != (const char*)ti.S + d * (long)s_bytes) return H.tiles.end();
+        // unified scale: the run is registered as ONE matrix with ONE scale (m_groups = 1 below), so a neighbour joins only when
+        // its scale VALUE is the run's (scales_size = 2 over four tiles: tiles 1 and 2 are contiguous and differ)
+        if (cfg.m_groups >= 1 && memcmp(it->second.S, ti.S, sizeof(float)) != 0) return H.tiles.end();
         return it;
     };
     auto first = H.tiles.find(key);
@@ -359,8 +362,7 @@ extern "C" int32_t qgemm_lut_int8(int m, int k, int n, int b, void* A, void* LUT
             if (r->m == m && r->k == k && r->b == b && da >= 0 && (size_t)da < r->a_bytes * (size_t)r->ntile && (size_t)da % r->a_bytes == 0) {
                 const int idx = (int)((size_t)da / r->a_bytes);
                 if ((const char*)Scales == r->S0 + (size_t)idx * r->s_bytes && r->gen == H.lut_gen && r->C &&
-                    r->C_elems == (size_t)n * r->ntile * Mw_tile && LUT == H.lut_q && LUT_Scales == H.lut_ls && LUT_Biases == H.lut_lb &&
-                    H.lut_k == k && H.lut_n == n && lut_sample_ok(LUT, (size_t)n * (k / 4) * 16) &&
+                    r->C_elems == (size_t)n * r->ntile * Mw_tile && lut_matches(LUT, LUT_Scales, LUT_Biases, k, n) &&
                     tile_bytes_match(A, r->a_bytes, Scales, r->s_bytes, r->bytes[idx])) {
                     const size_t Mw_run = (size_t)r->ntile * Mw_tile;
                     for (int i = 0; i < n; ++i)
@@ -373,8 +375,7 @@ extern "C" int32_t qgemm_lut_int8(int m, int k, int n, int b, void* A, void* LUT
         if (it != H.tiles.end() && it->second.run && it->second.S == Scales) {
             const TileInfo& ti = it->second;
             const HostRun* r = ti.run;
-            if (r->gen == H.lut_gen && r->C && r->C_elems == (size_t)n * r->ntile * Mw_tile && LUT == H.lut_q && LUT_Scales == H.lut_ls &&
-                LUT_Biases == H.lut_lb && H.lut_k == k && H.lut_n == n && lut_sample_ok(LUT, (size_t)n * (k / 4) * 16) &&
+            if (r->gen == H.lut_gen && r->C && r->C_elems == (size_t)n * r->ntile * Mw_tile && lut_matches(LUT, LUT_Scales, LUT_Biases, k, n) &&
                 tile_sample(A, ti.a_bytes, Scales, ti.s_bytes) == ti.sample) {
                 serve_from_run(r, ti, n, Mw_tile, C);
                 memo_run = r; memo_epoch = H.run_epoch;
@@ -501,6 +502,5 @@ void tmac_host::host_route_release() {
     if (H.pin) { (void)hipHostFree(H.pin); H.pin = nullptr; H.pin_bytes = 0; }
     H.lut_host.clear();
     H.lut_k = H.lut_n = H.lut_ags = 0;
-    H.lut_q = H.lut_ls = H.lut_lb = nullptr;
     ++H.lut_gen;
 }

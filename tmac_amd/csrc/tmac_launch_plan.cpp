@@ -56,8 +56,10 @@ bool quad_config(const Shape& s, bool need512, int total_q, int force_ft, int fo
     if (force_wpq) best_wpq = force_wpq;
     if (best_ft == 768 || best_wpq == 3)          // 12 waves: 3 per quad (balanced when the row has 3k steps), or 12 / 6 quads per workgroup
         return best_ft == 768 && !need512 && s.K / 4 <= 6 * 768 && best_wpq >= 1 && best_wpq <= 3;
+    // (six tables per thread is the limit of a launch that BUILDS the LUT: quad_plan_finish applies it there.  A launch that copies the
+    // workspace's image has no build to spread and takes any K -- K = 14336, llama-3-8B's down projection, through the split entry point)
     return !((need512 && best_ft != 512) || (best_wpq == 4 && best_ft != 1024) || (best_ft != 512 && best_ft != 1024) ||
-             (best_wpq != 1 && best_wpq != 2 && best_wpq != 4) || s.K / 4 > 6 * best_ft);
+             (best_wpq != 1 && best_wpq != 2 && best_wpq != 4));
 }
 
 // grid, tables per thread, EARLY and LDS of a plan whose configuration and instantiation flags are set; false: no such instantiation
