@@ -101,6 +101,7 @@ int32_t tmac_hip_set_kcfg(int M, int K, int N, int bits, const tmac_kcfg* cfg);
  *   C_dev, C_dev[i] (outputs)                 fp32: 16 bytes, fp16: 8    (the GEMMs store four outputs of a row at a time; Mw is a
  *                                                                         multiple of 4, so every row of [N][Mw] stays aligned)
  *   tmac_hip_xform: in2, residual, gamma, residual_out          16 bytes  (16-byte loads into LDS; residual_out: 16-byte stores)
+ *   bias_dev (tmac_hip_weights_set_bias_dev)                    16 bytes  (copied once into the handle; the kernels read the copy)
  *   A_ref_dev, scales_ref_dev, the tap buffer of tmac_hip_chain_set_tap, recv / send of the exchange step: their element type
  *     (copied, or read and written element by element)
  * The rule goes by the argument's ROLE and dtype, not by the route a call takes: an fp32 C_dev needs 16 bytes for N = 1 too (where the
@@ -337,6 +338,27 @@ int32_t tmac_hip_register_weights_gptq_perm_dev(tmac_hip_weights** out, const vo
 int32_t tmac_hip_register_weights_codes_perm_dev(tmac_hip_weights** out, const void* codes, const void* scales, const void* zeros,
                                                  tmac_dtype_t sz_dtype, const tmac_hip_kperm* perm, int Mw, int K, int bits,
                                                  const tmac_kcfg* cfg, tmac_dtype_t ref_float, tmac_dtype_t dev_float, void* stream);
+
+/* ---- biased linear layers: y = W x + b -------------------------------------------------------------------------------------
+ * tmac_hip_weights_set_bias_dev gives a registered handle a bias: bias_dev is [Mw] of dtype F32, F16 or BF16 in device memory, 16-byte
+ * aligned.  The handle owns an fp32 copy (the conversions are exact; padded with zeros to a multiple of 64 elements, so that a 16-byte
+ * load at a tile's edge reads the library's own zeros); the call flushes the calling thread's deferred queue first and returns with the
+ * copy made: the caller's buffer is free for reuse once `stream` is synchronised.  tmac_hip_free_weights frees the copy.  Set once,
+ * straight after registration: a chain recorded earlier on the handle (and a launch of it) does not see the bias.
+ * From then on every call on the handle computes y = W x + b: the bias is added to the fp32 output value in front of its one store -- one
+ * correctly rounded add (rn), so a biased call equals rn(plain call's fp32 value + b) bit for bit, and its fp16 output is that sum rounded
+ * once.  Two kernels carry the add: k_gemv_quad's MFMA form and k_gemm_planes' per-group flavour.  tmac_hip_qgemm_fused_dev (one call may mix
+ * biased and plain matrices) and tmac_hip_qgemm_dev take the plan the plain call takes and are refused with TMAC_HIP_E_NOMATCH, naming the
+ * route, before the first launch where it lands on another kernel (k_gemm_onehot, k_gemv_rows forced, variants 3 and 7, ...).
+ * tmac_hip_qgemm_fused_xf_dev / _xf_rows_dev: TMAC_XF_NORM and the silu GLU are served; TMAC_XF_GLU_NORM and the relu^2 / GELU gates in
+ * front of a biased matrix are refused with TMAC_HIP_E_NOMATCH at every N.  A call with a biased matrix is never recorded (refused with
+ * TMAC_HIP_E_ARG, "carries a bias", in plain and declared-independent recordings alike; the recording stays usable), never queued (it
+ * runs behind the deferred queue, stand-alone) and never tapped (TMAC_HIP_E_ARG).
+ * Refused with a message, the handle unchanged: a NULL or misaligned bias_dev, a dtype outside the three, a handle that already has a bias,
+ * a handle that carries a K permutation (TMAC_HIP_E_ARG); unified-scale handles, and handles outside the QUAD layout, with fast
+ * aggregation or of a shape k_gemv_quad does not take (TMAC_HIP_E_NOMATCH). */
+int32_t tmac_hip_weights_set_bias_dev(tmac_hip_weights* w, const void* bias_dev, tmac_src_dtype_t dtype, void* stream);
+int32_t tmac_hip_weights_has_bias(const tmac_hip_weights* w, int* has);
 
 /* LUT workspace = TMACGeMMWrapper::set_workspace (tmac_gemm_wrapper.h:257-270) on the device. */
 int32_t tmac_hip_workspace_create(tmac_hip_workspace** out, int maxK, int maxN);

@@ -119,6 +119,9 @@ def load_library() -> C.CDLL:
         "tmac_hip_register_weights_codes_perm_dev": ([C.POINTER(vp), vp, vp, vp, C.c_int, vp, C.c_int, C.c_int, C.c_int, C.POINTER(KCfg), C.c_int, C.c_int,
                                                       vp], i32),
         "tmac_hip_preprocessor_perm_dev": ([vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp], i32),
+        # biased linear layers (y = W x + b): the handle's own fp32 copy of b
+        "tmac_hip_weights_set_bias_dev": ([vp, vp, C.c_int, vp], i32),
+        "tmac_hip_weights_has_bias": ([vp, C.POINTER(C.c_int)], i32),
         "tmac_hip_free_weights": ([vp], i32),
         "tmac_hip_weights_bytes": ([vp], sz),
         "tmac_hip_workspace_create": ([C.POINTER(vp), C.c_int, C.c_int], i32),
@@ -203,6 +206,7 @@ def load_library() -> C.CDLL:
                 "tmac_hip_kperm_from_gidx_dev", "tmac_hip_kperm_info", "tmac_hip_kperm_read", "tmac_hip_kperm_free", "tmac_hip_weights_kperm_id",
                 "tmac_hip_pack_gptq_perm_dev", "tmac_hip_pack_codes_perm_dev", "tmac_hip_register_weights_gptq_perm_dev",
                 "tmac_hip_register_weights_codes_perm_dev", "tmac_hip_preprocessor_perm_dev",
+                "tmac_hip_weights_set_bias_dev", "tmac_hip_weights_has_bias",
                 "tmac_hip_debug_rows_kernel", "tmac_hip_debug_rows_stats", "tmac_hip_debug_rows_plan", "tmac_hip_debug_rows_comb_sums"} if os.environ.get("TMAC_HIP_LIB") else set()
     for name, (argt, rest) in sigs.items():
         try:

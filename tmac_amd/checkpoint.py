@@ -15,6 +15,10 @@ Refused, naming the tensor: act-order checkpoints (``desc_act``, as the referenc
 one object per distinct content, so q/k/v and gate/up -- quantised against the same inputs -- share theirs and can be fused.  An identity
 g_idx registers a plain handle.
 
+A layer's ``<layer>.bias`` ([Mw], F32 / F16 / BF16) is found by the GPTQ and the dense scan (``GptqLayer.bias`` / ``DenseLayer.bias``) and
+attached to the handle by their loaders (y = W x + b: the constructors' ``bias=``); a malformed one is refused, naming the tensor.  Where a handle
+cannot take one -- act-order layers, BitNet's unified scales -- the loader raises, naming the layer, instead of dropping it.
+
 BitNet b1.58 checkpoints of master weights take the same two steps: ``scan_bitnet_dir`` / ``load_bitnet_dir`` (``Weights.from_bitnet``:
 the absmean rule and the packing on the GPU), and checkpoints of PACKED ternary weights (the Hugging Face BitNet quantiser, four weight
 rows per byte) ``scan_bitnet_packed_dir`` / ``load_bitnet_packed_dir`` (``Weights.from_bitnet_packed``), both further down this file.
@@ -54,6 +58,7 @@ class GptqLayer(NamedTuple):
     bits: int
     group_size: int
     g_idx: Optional[TensorRef] = None      # scan_gptq_dir(..., act_order=True) only
+    bias: Optional[TensorRef] = None       # "<name>.bias", F32 / F16 / BF16 [Mw], where the layer has one (Qwen2's q/k/v, OPT, BLOOM, ...)
 
 
 class GptqScan(NamedTuple):
@@ -87,6 +92,26 @@ def safetensors_index(path: str) -> Dict[str, TensorRef]:
             return out
         except (ValueError, KeyError, TypeError) as e:
             raise RuntimeError("{}: corrupt safetensors header ({})".format(path, e))
+
+
+def _bias_ref(index: Dict[str, TensorRef], base: str, Mw: int) -> Optional[TensorRef]:
+    """``<base>.bias`` of a layer with Mw output rows, or None where the checkpoint has none.  Refused (RuntimeError naming the tensor):
+    another element type than F32 / F16 / BF16, another shape than [Mw], byte ranges that do not match the shape."""
+    ref = index.get(base + ".bias")
+    if ref is None:
+        return None
+    if ref.dtype not in ("F32", "F16", "BF16"):
+        raise RuntimeError("{}.bias has dtype {}: F32, F16 or BF16 expected".format(base, ref.dtype))
+    if ref.shape != (Mw,):
+        raise RuntimeError("{}.bias has shape {}: [{}] expected (one value per output row)".format(base, ref.shape, Mw))
+    if (ref.end - ref.begin) != Mw * np.dtype(_NP[ref.dtype]).itemsize:
+        raise RuntimeError("{}.bias: shape {} does not match its {} bytes".format(base, ref.shape, ref.end - ref.begin))
+    return ref
+
+
+def _refuse_bias(index: Dict[str, TensorRef], base: str, why: str) -> None:
+    if base + ".bias" in index:
+        raise RuntimeError("{} comes with {}.bias: {}".format(base, base, why))
 
 
 def gptq_is_v2(qc: dict) -> bool:
@@ -138,7 +163,7 @@ def scan_gptq_dir(model_dir: str, act_order: bool = False) -> GptqScan:
                 raise RuntimeError("{}.g_idx is missing (act_order=True reads every layer's group indices)".format(base))
             if gi.dtype != "I32" or gi.shape != (K,) or (gi.end - gi.begin) != 4 * K:
                 raise RuntimeError("{}.g_idx has dtype {} and shape {}: I32 [{}] expected".format(base, gi.dtype, gi.shape, K))
-        layers.append(GptqLayer(base, qw, sc, qz, K, Mw, bits, K // sc.shape[0], gi))
+        layers.append(GptqLayer(base, qw, sc, qz, K, Mw, bits, K // sc.shape[0], gi, _bias_ref(index, base, Mw)))
     if not layers:
         raise RuntimeError("Models in {} not in GPTQ format".format(model_dir))
     return GptqScan(layers, gptq_is_v2(qc), not qc.get("sym", False), qc)
@@ -152,10 +177,15 @@ def read_tensor(ref: TensorRef) -> np.ndarray:
 def load_gptq_dir(model_dir: str, wrapper, dev_dtype=F16, act_order: bool = False) -> Dict[str, "object"]:
     """{layer name: Weights} for every ``*.qweight`` triple of the checkpoint: the packed tensors are uploaded as they lie in the file
     and unpacked, permuted and re-tiled on the GPU (``wrapper.register_gptq``).  A symmetric checkpoint (``sym``) is registered without
-    zero points, as the reference compiles its kernels (deploy/compile.py:103).  act_order: see the head of this file."""
+    zero points, as the reference compiles its kernels (deploy/compile.py:103).  act_order: see the head of this file.  A layer's
+    ``.bias`` ([Mw], F32 / F16 / BF16) is uploaded as it lies in the file and attached to the handle, which then computes y = W x + b;
+    with act_order a layer that has one is refused, naming the layer (act-order handles take no bias yet)."""
     from .binding import KCfg
     from .wrapper import KPerm
     scan = scan_gptq_dir(model_dir, act_order)
+    for L in scan.layers:       # (before anything is registered)
+        if L.g_idx is not None and L.bias is not None:
+            raise RuntimeError("{} comes with {}.bias: an act-order handle with a bias is not served yet (the bias would be dropped)".format(L.name, L.name))
     out = {}
     perms: Dict[Tuple[int, bytes], "object"] = {}      # one KPerm per distinct (group size, g_idx content)
     for L in scan.layers:
@@ -169,7 +199,9 @@ def load_gptq_dir(model_dir: str, wrapper, dev_dtype=F16, act_order: bool = Fals
             if key not in perms:
                 perms[key] = KPerm(g, L.group_size)
             kp = perms[key]
-        out[L.name] = wrapper.register_gptq(np.array(read_tensor(L.qweight)), np.array(read_tensor(L.scales)), qz, cfg, scan.gptq_v2, dev_dtype, g_idx=kp)
+        bias = np.array(read_tensor(L.bias)) if L.bias is not None else None
+        out[L.name] = wrapper.register_gptq(np.array(read_tensor(L.qweight)), np.array(read_tensor(L.scales)), qz, cfg, scan.gptq_v2, dev_dtype, g_idx=kp,
+                                            bias=bias)
     return out
 
 
@@ -214,6 +246,7 @@ def scan_bitnet_dir(model_dir: str) -> BitnetScan:
         ref = index[wname]
         if wname + "_scale" in index:
             raise RuntimeError("{} comes with {}_scale: a pre-packed ternary checkpoint, not master weights".format(wname, wname))
+        _refuse_bias(index, wname[:-len(".weight")], "unified-scale (BitNet) handles take no bias (it would be dropped)")
         if ref.dtype not in ("F32", "F16", "BF16"):
             raise RuntimeError("{} has dtype {}: F32, F16 or BF16 expected".format(wname, ref.dtype))
         if len(ref.shape) != 2:
@@ -288,6 +321,7 @@ def scan_bitnet_packed_dir(model_dir: str) -> BitnetPackedScan:
         if sc.dtype not in ("BF16", "F16", "F32") or int(np.prod(sc.shape)) != 1 or len(sc.shape) > 1 or \
                 (sc.end - sc.begin) != np.dtype(_NP[sc.dtype]).itemsize:
             raise RuntimeError("{}_scale has dtype {} and shape {}: one element of BF16, F16 or F32 expected".format(wname, sc.dtype, sc.shape))
+        _refuse_bias(index, wname[:-len(".weight")], "unified-scale (BitNet) handles take no bias (it would be dropped)")
         if len(ref.shape) != 2:
             raise RuntimeError("{} has shape {}: a 2-D tensor expected".format(wname, ref.shape))
         if (ref.end - ref.begin) != int(np.prod(ref.shape)):
@@ -303,7 +337,8 @@ def load_bitnet_packed_dir(model_dir: str, wrapper, dev_dtype=F32) -> Dict[str, 
     unpacked and re-tiled on the GPU (``wrapper.register_bitnet_packed``); the scale is a host scalar, read from the file and turned into
     the blob's scale by the checkpoint's ``linear_class`` (``convert.bitnet_packed_scale``).  Handles only: where the checkpoint sets
     ``use_rms_norm`` (the scan result says so, with ``rms_norm_eps``), a layer's ``<layer>.rms_norm.weight`` vector is the caller's to
-    apply to the activations, for example through ``fused_xf(..., "norm", gamma=...)``; biases are not read either."""
+    apply to the activations, for example through ``fused_xf(..., "norm", gamma=...)``.  A layer with a ``.bias`` is refused by the scan,
+    naming the layer: unified-scale handles take none."""
     scan = scan_bitnet_packed_dir(model_dir)
     return {L.name: wrapper.register_bitnet_packed(np.array(read_tensor(L.weight)), np.array(read_tensor(L.weight_scale._replace(shape=(1,)))), None,
                                                    scan.linear_class, dev_dtype) for L in scan.layers}
@@ -315,6 +350,7 @@ class DenseLayer(NamedTuple):
     weight: TensorRef       # F32, F16 or BF16 [Mw][K]
     Mw: int
     K: int
+    bias: Optional[TensorRef] = None       # "<name>.bias", F32 / F16 / BF16 [Mw], where the layer has one
 
 
 class DenseScan(NamedTuple):
@@ -368,7 +404,7 @@ def scan_dense_dir(model_dir: str) -> DenseScan:
             raise RuntimeError("{} has shape {}: a 2-D tensor expected".format(wname, ref.shape))
         if (ref.end - ref.begin) != int(np.prod(ref.shape)) * np.dtype(_NP[ref.dtype]).itemsize:
             raise RuntimeError("{}: shape {} does not match its {} bytes".format(wname, ref.shape, ref.end - ref.begin))
-        layers.append(DenseLayer(wname[:-len(".weight")], ref, ref.shape[0], ref.shape[1]))
+        layers.append(DenseLayer(wname[:-len(".weight")], ref, ref.shape[0], ref.shape[1], _bias_ref(index, wname[:-len(".weight")], ref.shape[0])))
     if not layers:
         raise RuntimeError("Models in {} hold no model.layers.*_proj.weight tensor".format(model_dir))
     return DenseScan(layers)
@@ -377,6 +413,7 @@ def scan_dense_dir(model_dir: str) -> DenseScan:
 def load_dense_dir(model_dir: str, wrapper, bits: int, group_size: int = 128, zero_point: bool = True, dev_dtype=F16) -> Dict[str, "object"]:
     """{layer name: Weights} for every layer ``scan_dense_dir`` finds: the matrix is uploaded as it lies in the file -- BF16 as its 16-bit
     words, no conversion on the host, one upload per tensor -- and quantised to ``bits`` (1 to 4) with per-group scales by round to nearest
-    and packed on the GPU (``wrapper.register_dense``)."""
+    and packed on the GPU (``wrapper.register_dense``).  A layer's ``.bias`` is attached to its handle (y = W x + b)."""
     scan = scan_dense_dir(model_dir)
-    return {L.name: wrapper.register_dense(np.array(read_tensor(L.weight)), bits, group_size, zero_point, None, dev_dtype) for L in scan.layers}
+    return {L.name: wrapper.register_dense(np.array(read_tensor(L.weight)), bits, group_size, zero_point, None, dev_dtype,
+                                           bias=np.array(read_tensor(L.bias)) if L.bias is not None else None) for L in scan.layers}

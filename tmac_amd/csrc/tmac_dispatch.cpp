@@ -127,7 +127,9 @@ static bool rows_pays(const Shape& s, long total_Mw, int N) {
 //    (xf_rows_plan, at the fused entry point): R_GEMV_QUAD becomes R_ROW_LOOP behind LB_HALF_TABLES -- the transform lives in the N > 1
 //    LUT builders, so the image is built once and each matrix is planned again by plan_split -- and a plan that needs LB_ALL is refused.
 //    Routing of untransformed calls is untouched.
-static Plan plan_split(const tmac_hip_weights* w, const tmac_hip_workspace* ws, int N, bool tap) {
+// image_ok: the workspace holds a valid LUT image of the kind the shape wants for N rows, addressable by k_gemm_planes (plan_split: of the
+// call's workspace; bias_routes_check asks both ways before a workspace exists)
+static Plan plan_split_on(const tmac_hip_weights* w, bool image_ok, int N, bool tap) {
     Route r = R_REF_LAYOUT;
     if (g_knobs.variant != V_REF_LAYOUT && w->tiled_ok)
         r = layout_of(w->s) == L_QUAD ? R_GEMV_QUAD : layout_of(w->s) == L_ROWBLOCK ? R_GEMV_FUSED : R_GEMV_LO;
@@ -137,11 +139,14 @@ static Plan plan_split(const tmac_hip_weights* w, const tmac_hip_workspace* ws, 
     if (r != R_GEMV_QUAD && r != R_GEMV_FUSED) return planned(r);
     const bool rows = r == R_GEMV_QUAD && N >= 2 && !tap && g_knobs.rows_kernel != 1 && rows_covers(w);
     if (rows && g_knobs.rows_kernel == 2) return planned(R_GEMV_ROWS);
-    if (!tap && ws->held.serves_image(image_kind_for(w->s), w->s.K, N) && planes_ok(w) && ws->image_fits(w->s.K) && planes_pays(w->s, w->s.Mw, N))
+    if (!tap && image_ok && planes_ok(w) && planes_pays(w->s, w->s.Mw, N))
         return planned(R_GEMM_PLANES);
     if (onehot_pays(w->s, w->s.Mw, N) && gemm_onehot_supported(w->s)) return planned(R_GEMM_ONEHOT);
     if (rows && rows_pays(w->s, w->s.Mw, N)) return planned(R_GEMV_ROWS);
     return planned(r);
+}
+static Plan plan_split(const tmac_hip_weights* w, const tmac_hip_workspace* ws, int N, bool tap) {
+    return plan_split_on(w, ws->held.serves_image(image_kind_for(w->s), w->s.K, N) && ws->image_fits(w->s.K), N, tap);
 }
 
 // every matrix in the QUAD layout, one LUT, one kernel instantiation, and a pair build that covers the LUT
@@ -225,6 +230,12 @@ int32_t tmac_host::fused_check(const FusedCall& c) {
 static FusedCall one_matrix(const tmac_hip_weights* const* w, void* const* C, tmac_dtype_t out, int N, hipStream_t st) {
     return FusedCall{w, 1, nullptr, TMAC_F32, C, out, N, st};
 }
+// does a matrix of the call carry a bias (tmac_hip_weights_set_bias_dev)?  One fused call may mix biased and plain matrices.
+static bool any_bias(const FusedCall& c) {
+    for (int i = 0; c.wl && i < c.nmat; ++i)
+        if (c.wl[i] && c.wl[i]->bias) return true;
+    return false;
+}
 static void fill_gemm_mats(GemmMat* m, const FusedCall& c) {
     for (int i = 0; i < c.nmat; ++i) { m[i].W = c.wl[i]->W; m[i].SC = c.wl[i]->SC; m[i].C = c.C[i]; m[i].Mw = c.wl[i]->s.Mw; }
 }
@@ -264,16 +275,19 @@ static int32_t gemm_multi(const FusedCall& c, const tmac_hip_workspace* ws, int3
 }
 
 // k_gemm_planes over up to 4 matrices that share K and the quantisation config; the workspace holds the LUT image
+// (a call with a biased matrix: the bias instantiations, never with the tap)
 static int32_t planes_multi(const FusedCall& c, const tmac_hip_workspace* ws, int32_t* comb_dump) {
-    Gemm2Args ga;
+    Gemm2BiasArgs ga;
     memset(&ga, 0, sizeof(ga));
+    for (int i = 0; i < c.nmat; ++i) ga.bias[i] = c.wl[i]->bias;
     ga.s = c.s0(); ga.nmat = c.nmat;
     fill_gemm_mats(ga.m, c);
     ga.sc_f16 = c.wl[0]->sc_dtype == F16; ga.out_f16 = c.out_f16();
     ga.bimg = (const uint4*)ws->gimg; ga.colv = ws->gcol; ga.Npad = ws->gNpad; ga.N = c.N; ga.dump = comb_dump;
     ga.stamps = g_knobs.gemm_stamps;
     ga.form = g_knobs.gemm_kernel == 2 ? 1 : g_knobs.gemm_kernel == 3 ? 2 : 0;
-    hipError_t e = launch_gemm_planes(ga, c.st);
+    if (comb_dump && any_bias(c)) return fail(TMAC_HIP_E_ARG, "a parity tap on a handle that carries a bias is not served");
+    hipError_t e = any_bias(c) ? launch_gemm_planes(ga, c.st) : launch_gemm_planes(static_cast<const Gemm2Args&>(ga), c.st);
     if (e == hipErrorInvalidValue) return fail(TMAC_HIP_E_NOMATCH, "plane-combined gemm: configuration or sizes not covered (LUT image and matrices must stay below 2 GB)");
     if (e != hipSuccess) return fail(TMAC_HIP_E_RUNTIME, "plane-combined gemm launch: %s", hipGetErrorString(e));
     return TMAC_HIP_OK;
@@ -350,14 +364,62 @@ static int32_t refuse_perm(const FusedCall& c, const char* what) {
         if (perm_of(c.wl[i])) return fail(TMAC_HIP_E_ARG, "matrix %d carries a K permutation (act-order): %s on such handles is not served yet", i, what);
     return TMAC_HIP_OK;
 }
-// What k_gemv_quad's MFMA form with an in-kernel LUT build takes, as the set of conditions a matrix misses (0: it is served).  A door
-// asks for the conditions in its scope and words its own refusal.
-// The conditions: the reference-layout variant or the v_mqsad accumulate is selected | not registered in the QUAD layout, or its tiled
-// kernel does not cover the configuration | fast-aggregation weights | gemv_quad_supported says no.
-enum : unsigned { QM_REF_VARIANT = 1, QM_MQSAD_VARIANT = 2, QM_LAYOUT = 4, QM_FAST_AGG = 8, QM_SHAPE = 16 };
-static unsigned quad_mfma_misses(const tmac_hip_weights* w) {
+// (what k_gemv_quad's MFMA form takes, as the conditions a matrix misses: tmac_host.h)
+unsigned tmac_host::quad_mfma_misses(const tmac_hip_weights* w) {
     return (g_knobs.variant == V_REF_LAYOUT ? QM_REF_VARIANT : 0u) | (g_knobs.variant == V_QUAD_MQSAD ? QM_MQSAD_VARIANT : 0u) |
            (layout_of(w->s) != L_QUAD || !w->tiled_ok ? QM_LAYOUT : 0u) | (w->fa ? QM_FAST_AGG : 0u) | (!gemv_quad_supported(w->s) ? QM_SHAPE : 0u);
+}
+
+// ---- handles with a bias (tmac_hip_weights_set_bias_dev) -----------------------------------------------------------------------
+// y = W x + b is computed by k_gemv_quad's MFMA form (bias instantiations: LUT built in-kernel or copied) and by k_gemm_planes' per-group
+// flavour, in front of the output's one store; every other kernel would drop the bias, so a plan that lands on one is refused, naming the
+// route, before the first launch.  A call with a biased matrix is never recorded, never queued and never tapped (fused_impl); apart from
+// that it takes the plan the plain call takes.
+static int32_t bias_split_check(const tmac_hip_weights* w, Route r) {
+    if (!w->bias) return TMAC_HIP_OK;
+    if (r != R_GEMV_QUAD && r != R_GEMM_PLANES)
+        return fail(TMAC_HIP_E_NOMATCH, "the matrix carries a bias, which %s does not add (k_gemv_quad's MFMA form and k_gemm_planes do)", ROUTE_NAMES[r]);
+    if (r == R_GEMV_QUAD && quad_mfma_misses(w))
+        return fail(TMAC_HIP_E_NOMATCH, "the matrix carries a bias, which k_gemv_quad adds in its MFMA form only (variant 0 or 6)");
+    if (r == R_GEMV_QUAD) {      // the copy form's own plan, asked here so that a forced configuration it lacks is refused before any launch
+        QuadPlan qp;
+        if (!quad_plan_bias(w->s, w->s.nquads(), false, 0, g_knobs.force_ft, g_knobs.force_wpq, g_knobs.force_ft || g_knobs.force_wpq, qp))
+            return fail(TMAC_HIP_E_NOMATCH, "the matrix carries a bias: no biased GEMV kernel copies the workspace's LUT in this configuration (copy form: (512,1), (512,2))");
+    }
+    return TMAC_HIP_OK;
+}
+static int32_t bias_plan_check(const Plan& p, const FusedCall& c) {
+    if (!any_bias(c)) return TMAC_HIP_OK;
+    if (p.route == R_ROW_LOOP) {
+        // each matrix is planned again from the workspace's state (plan_split): the half-table build leaves no LUT image, the
+        // three-layout build may -- asked both ways
+        for (int i = 0; i < c.nmat; ++i)
+            for (int img = 0; img <= (p.lut == LB_HALF_TABLES ? 0 : 1); ++img) {
+                const Plan q = plan_split_on(c.wl[i], img != 0, c.N, false);
+                if (q.err) return fail(q.err, q.msg, q.mat);
+                const int32_t rc = bias_split_check(c.wl[i], q.route);
+                if (rc) return rc;
+            }
+        return TMAC_HIP_OK;
+    }
+    if (p.route != R_GEMV_QUAD && p.route != R_GEMM_PLANES)
+        return fail(TMAC_HIP_E_NOMATCH, "a matrix of the call carries a bias, which %s does not add (k_gemv_quad's MFMA form and k_gemm_planes do)", ROUTE_NAMES[p.route]);
+    for (int i = 0; p.route == R_GEMV_QUAD && i < c.nmat; ++i)
+        if (quad_mfma_misses(c.wl[i]) || c.wl[i]->s.m_groups >= 1)
+            return fail(TMAC_HIP_E_NOMATCH, "a matrix of the call carries a bias, which k_gemv_quad adds in its MFMA form only (variant 0 or 6, per-group scales): matrix %d", i);
+    return TMAC_HIP_OK;
+}
+// k_gemv_quad's bias block: the handles' own copies (null: the matrix has none)
+template <class Args>
+static void fill_bias(Args& fa, const FusedCall& c) {
+    for (int i = 0; i < 4; ++i) fa.bias[i] = i < c.nmat ? c.wl[i]->bias : nullptr;
+}
+// A transform in front of a biased matrix: NORM and the silu GLU have instantiations with the add; the rule is the same for every N.
+static int32_t xf_bias_check(const XfSpec& spec, const FusedCall& c) {
+    if (!any_bias(c)) return TMAC_HIP_OK;
+    if (spec.kind == TMAC_XF_GLU_NORM || spec.gate != 0)
+        return fail(TMAC_HIP_E_NOMATCH, "a matrix of the call carries a bias: GLU_NORM and the relu^2 / GELU gates in front of a biased matrix are not served (NORM and the silu GLU are)");
+    return TMAC_HIP_OK;
 }
 
 // ---- split entry point -----------------------------------------------------------------------------------------------------
@@ -375,8 +437,11 @@ int32_t tmac_host::qgemm_impl(const tmac_hip_weights* w, const tmac_hip_workspac
     if (!held.built_through(perm_id_of(w)))
         return fail(TMAC_HIP_E_ARG, perm_of(w) ? "the weights carry a K permutation (act-order) but the workspace LUT was not built through it (tmac_hip_preprocessor_perm_dev)"
                                                : "the workspace LUT was built through a K permutation the weights do not carry");
+    if (w->bias && dump) return fail(TMAC_HIP_E_ARG, "a parity tap on a handle that carries a bias is not served");
     const Plan p = plan_split(w, ws, N, dump != nullptr);
     if (p.err) return fail(p.err, p.msg, p.mat);
+    const int32_t bias_rc = bias_split_check(w, p.route);
+    if (bias_rc) return bias_rc;
     // the planned kernel reads tables somebody built: its layout of the LUT, or the LUT image, is in the workspace's record
     const bool planes = p.route == R_GEMM_PLANES;
     const LutLayout reads = p.route == R_REF_LAYOUT ? LUT_REF : p.route == R_GEMV_LO ? LUT_DEV : LUT_HALF;
@@ -396,6 +461,13 @@ int32_t tmac_host::qgemm_impl(const tmac_hip_weights* w, const tmac_hip_workspac
         fill_fused_args(fa, one);
         fa.dump = dump;
         fa.qlut_lds = ws->qlut_lds; fa.lut_scales = ws->lut_scales; fa.lut_biases = ws->lut_biases;
+        if (w->bias) {       // (R_GEMV_QUAD: bias_split_check) the copy form of the bias instantiations
+            FusedBiasArgs fb;
+            static_cast<FusedArgs&>(fb) = fa;
+            fill_bias(fb, one);
+            return fused_gemv_rc(launch_gemv_quad(fb, N, false, g_knobs.force_ft, g_knobs.force_wpq, g_knobs.force_ft || g_knobs.force_wpq, st),
+                                 "no biased GEMV kernel for this configuration (copy form: (512,1), (512,2))", "biased gemv");
+        }
         return fused_gemv_rc(p.route == R_GEMV_QUAD ? launch_gemv_quad(fa, N, false, g_knobs.force_ft, g_knobs.force_wpq, false, st)
                                                     : launch_gemv_fused(fa, N, false, st));
     }
@@ -600,6 +672,7 @@ static int32_t fused_prefill(Plan p, const FusedCall& c, const XfSpec* spec = nu
     if (p.route == R_GEMM_PLANES && !ws->image_fits(s0.K)) {   // (see image_fits at the planners)
         p = plan_call(c, false, spec || kp, false);
         if (p.err) return fail(p.err, p.msg, p.mat);
+        if ((rc = bias_plan_check(p, c)) != TMAC_HIP_OK) return rc;      // (the new plan's route must add the bias too; nothing is launched yet)
     }
     LutBuildReq q;
     q.K = s0.K; q.N = N; q.ags = s0.ags; q.want = p.lut; q.unified = s0.m_groups >= 1; q.xf = spec != nullptr;
@@ -661,6 +734,20 @@ static int32_t fused_perm(const FusedCall& c) {
     return launch_quad<FusedPermArgs>(c, [&](FusedPermArgs& fa) { fa.perm = kp->dev; },
                                       "no gathering GEMV kernel for this configuration (gather instantiations: (512,1), (512,2), (768,3), (1024,4))", "gathering gemv");
 }
+// A fused call with at least one biased matrix (fused_impl has checked the arguments and the alignment; no matrix carries a permutation:
+// tmac_hip_weights_set_bias_dev refuses those).  The plan of the plain call, held to the routes that add a bias before anything is
+// launched; behind the calling thread's deferred queue, stand-alone.
+static int32_t fused_bias(const FusedCall& c) {
+    const Plan p = plan_call(c, false);
+    if (p.err) return fail(p.err, p.msg, p.mat);
+    int32_t rc = bias_plan_check(p, c);
+    if (rc) return rc;
+    rc = defer_barrier();
+    if (rc) return rc;
+    if (p.route != R_GEMV_QUAD) return fused_prefill(p, c);
+    return launch_quad<FusedBiasArgs>(c, [&](FusedBiasArgs& fa) { fill_bias(fa, c); },
+                                      "no biased GEMV kernel for this configuration (bias instantiations: (512,1), (512,2), (768,3), (1024,4))", "biased gemv");
+}
 int32_t tmac_host::fused_impl(const FusedCall& c, int32_t* dump, float* lut_tap) {
     bind_thread_device();
     // the argument and alignment checks, ahead of the recorder, the deferred queue and the planner alike: a refused call is neither
@@ -685,6 +772,14 @@ int32_t tmac_host::fused_impl(const FusedCall& c, int32_t* dump, float* lut_tap)
         }
         if (chain_recording()) return refuse_perm(c, "a recorded call (tmac_hip_chain_begin ... _end)");
         return fused_perm(c);
+    }
+    if (any_bias(c)) {    // handles with a bias: never recorded (plain and declared-independent alike), never queued, never tapped
+        if (chain_recording()) {
+            chain_clear_xform();
+            return fail(TMAC_HIP_E_ARG, "a matrix of the call carries a bias: such a call cannot be recorded (tmac_hip_chain_begin ... _end)");
+        }
+        if (tap) return fail(TMAC_HIP_E_ARG, "a matrix of the call carries a bias: a parity tap on such handles is not served");
+        return fused_bias(c);
     }
     if (chain_recording() && !tap) return chain_record(c);
     if (!tap) {           // deferred launches: queued until tmac_hip_flush (or a call that depends on a queued one)
@@ -745,16 +840,21 @@ extern "C" int32_t tmac_hip_qgemm_fused_xf_dev(const tmac_hip_weights* const* wl
     XfSpec spec;
     int32_t rc = xf_resolve(xf, XF_SITE_N1, &spec);
     if (rc || (rc = args_check(c)) != TMAC_HIP_OK || (rc = refuse_perm(c, "a vector transform")) != TMAC_HIP_OK) return rc;
-    if ((rc = act_align_check(c.B)) != TMAC_HIP_OK || (rc = out_align_check(c)) != TMAC_HIP_OK) return rc;
+    if ((rc = act_align_check(c.B)) != TMAC_HIP_OK || (rc = out_align_check(c)) != TMAC_HIP_OK || (rc = xf_bias_check(spec, c)) != TMAC_HIP_OK) return rc;
     const Plan p = plan_call(c, false, true);
     if (p.err) return fail(p.err, p.msg, p.mat);
     if (p.route != R_GEMV_QUAD || (quad_mfma_misses(wl[0]) & QM_MQSAD_VARIANT) || c.s0().K > QUAD_XF_MAX_K)
         return fail(TMAC_HIP_E_NOMATCH, "a transformed call runs on k_gemv_quad with the MFMA accumulate only (QUAD layout, K <= %d)", QUAD_XF_MAX_K);
+    if ((rc = bias_plan_check(p, c)) != TMAC_HIP_OK) return rc;
     // (every workgroup reads the whole of the inputs while ONE workgroup writes each pair of residual_out: no order between the two)
     if ((rc = xf_call_overlap_check(spec, XF_SITE_N1, c, xf)) != TMAC_HIP_OK) return rc;
     bind_thread_device();
     const int32_t brc = defer_barrier();       // never queued: behind the calling thread's queue (B_dev may be a queued output)
     if (brc) return brc;
+    if (any_bias(c))     // NORM or the silu GLU (xf_bias_check) in front of a biased matrix: the XF + BI instantiations
+        return launch_quad<FusedXfBiasArgs>(c, [&](FusedXfBiasArgs& fa) { fill_fused_xf_args(fa, spec); fill_bias(fa, c); },
+                                            "no transformed GEMV kernel with a bias for this configuration (instantiations: (512,1), (512,2), (768,3), (1024,4))",
+                                            "transformed gemv with a bias");
     return launch_quad<FusedXfArgs>(c, [&](FusedXfArgs& fa) { fill_fused_xf_args(fa, spec); },
                                     "no transformed GEMV kernel for this configuration (XF instantiations: (512,1), (512,2), (768,3), (1024,4))", "transformed gemv");
 }
@@ -779,6 +879,7 @@ extern "C" int32_t tmac_hip_qgemm_fused_xf_rows_dev(const tmac_hip_weights* cons
     const Shape& s0 = c.s0();
     XfSpec spec;
     if ((rc = xf_resolve(xf, XF_SITE_ROWS, &spec)) != TMAC_HIP_OK || (rc = act_align_check(c.B)) != TMAC_HIP_OK) return rc;
+    if ((rc = xf_bias_check(spec, c)) != TMAC_HIP_OK) return rc;      // (the N = 1 door's rule: it does not depend on N)
     // (the builders read in, in2 and residual again after the row pass has written residual_out)
     if ((rc = xf_call_overlap_check(spec, XF_SITE_ROWS, c, xf)) != TMAC_HIP_OK || (rc = one_lut_check(c)) != TMAC_HIP_OK) return rc;
     // the scope: what the N = 1 form accepts (but for the accumulate, which the kernels behind the pair build choose), within the pair builds' reach
@@ -793,6 +894,7 @@ extern "C" int32_t tmac_hip_qgemm_fused_xf_rows_dev(const tmac_hip_weights* cons
         return fail(TMAC_HIP_E_NOMATCH, "unified scales: K=%d is beyond the row-wise pair build (K <= %d)", s0.K, PAIRS_ROW_MAX_K);
     const Plan p = plan_call(c, false, true);
     if (p.err) return fail(p.err, p.msg, p.mat);
+    if ((rc = bias_plan_check(p, c)) != TMAC_HIP_OK) return rc;       // (the transform lives in the LUT build, the bias in the kernel behind it)
     bind_thread_device();
     const int32_t brc = defer_barrier();       // never queued: behind the calling thread's queue (B_dev may be a queued output)
     if (brc) return brc;

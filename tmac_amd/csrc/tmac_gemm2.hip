@@ -100,6 +100,10 @@ __global__ __launch_bounds__(256) void k_lut_image(const void* __restrict__ B, u
     }
 }
 
+#ifndef TMAC_GEMM2_BI_TU
+#define TMAC_GEMM2_BI_TU 0      // 1: the object of k_gemm_planes' bias instantiations and their launcher, nothing else of this file
+#endif
+#if !TMAC_GEMM2_BI_TU
 hipError_t launch_lut_image(const void* B, int act_f16, void* bimg, float* colv, int K, int N, int Npad, hipStream_t st, const XfRowsGateArgs* xf,
                             const int32_t* perm) {
     if (K % 64 != 0 || N < 1 || Npad < N || Npad % 64 != 0 || (xf && perm)) return hipErrorInvalidValue;
@@ -112,6 +116,7 @@ hipError_t launch_lut_image(const void* B, int act_f16, void* bimg, float* colv,
         return launch_lds(k_lut_image<F16.value>, g, b, 0, st, B, (uint4*)bimg, colv, K, N, Npad);
     });
 }
+#endif
 
 // ---------------------------------------------------------------------------------------------
 // Two forms of the workgroup (same tile, same arithmetic, same order of the fp32 sums within a K range):
@@ -150,8 +155,12 @@ struct PFormU {                  // the unified-scale kernel: operand rows only 
 // again, harmlessly): the step is one basic block and every wait is counted by the compiler -- for that the prologue issues its loads
 // in the order a step does (the wait counts of both ways into the loop are merged: another order, or a conditional load, turned waits
 // of every step into vmcnt(0), a drain of the B loads issued last).
-template <int BITS, bool ZP, bool DUMP, bool SCF16, int NWV>
-__global__ __launch_bounds__(64 * NWV, 8 / NWV) void k_gemm_planes(Gemm2Args a) {
+// BI (no tap): y = W x + b -- the matrix' bias (Gemm2BiasArgs: the handle's fp32 copy, padded with zeros to whole tiles, or null) is added
+// to the four outputs of a store, one 16-byte load per thread and quartet, four correctly rounded adds; every line of it sits under
+// if constexpr (BI), and the argument block without it is the one the other instantiations had.
+template <int BITS, bool ZP, bool DUMP, bool SCF16, int NWV, bool BI = false>
+__global__ __launch_bounds__(64 * NWV, 8 / NWV) void k_gemm_planes(std::conditional_t<BI, Gemm2BiasArgs, Gemm2Args> a) {
+    static_assert(!BI || !DUMP, "the bias instantiations have no tap");
     extern __shared__ __attribute__((aligned(16))) unsigned char plds[];
     using PF = PForm<NWV>;
     constexpr int P_NWV = NWV, P_SC_OFF = PF::SC_OFF, P_SC_WAVE = PF::SC_WAVE;
@@ -579,6 +588,13 @@ __global__ __launch_bounds__(64 * NWV, 8 / NWV) void k_gemm_planes(Gemm2Args a) 
         for (int ww = 1; ww < P_NWV; ++ww) v += *reinterpret_cast<const p4f_t*>(p + ww * 16384);
         const int n = n0 + nl, o = row0 + sl * 4;
         if (n < a.N && o < Mw) {
+            if constexpr (BI) {
+                const float* bp = a.bias[mi];
+                if (bp != nullptr) {       // (o is a multiple of 4 below Mw: inside the copy, 16-byte aligned)
+                    const p4f_t b4 = *reinterpret_cast<const p4f_t*>(bp + o);
+                    v = (p4f_t){__fadd_rn(v.x, b4.x), __fadd_rn(v.y, b4.y), __fadd_rn(v.z, b4.z), __fadd_rn(v.w, b4.w)};
+                }
+            }
             if (a.out_f16) {
                 const __half2 h0 = __floats2half2_rn(v.x, v.y), h1 = __floats2half2_rn(v.z, v.w);
                 *reinterpret_cast<uint2*>(reinterpret_cast<__half*>(M.C) + (size_t)n * Mw + o) =
@@ -806,6 +822,7 @@ __global__ __launch_bounds__(64 * NWV, 8 / NWV) void k_gemm_planes_us(Gemm2Args 
     }
 }
 
+#if !TMAC_GEMM2_BI_TU
 bool gemm_planes_us_supported(const Shape& s) {
     return s.lay == 2 && s.bits >= 1 && s.bits <= 4 && s.K % 64 == 0 && s.Mw % 4 == 0 && s.m_groups >= 1 && s.ags == s.K && s.Mw % s.m_groups == 0;
 }
@@ -817,14 +834,21 @@ bool gemm_planes_supported(const Shape& s) {
     return s.ags == 64 && s.gs >= 64 && s.gs % 64 == 0 && s.K % s.gs == 0 && (apg & (apg - 1)) == 0;
 }
 
-hipError_t launch_gemm_planes(const Gemm2Args& a_in, hipStream_t st) {
+#endif      // !TMAC_GEMM2_BI_TU
+
+// One launcher for both argument blocks.  The bias block (Gemm2BiasArgs): per-group scales, no tap; its instantiations sit in an object of
+// their own (-DTMAC_GEMM2_BI_TU=1), so that the other one holds exactly the kernels it held before and the build stays parallel.
+template <class Args>
+static hipError_t launch_gemm_planes_any(const Args& a_in, hipStream_t st) {
+    constexpr bool BI = std::is_same_v<Args, Gemm2BiasArgs>;
+    if (BI && (a_in.s.m_groups >= 1 || a_in.dump)) return hipErrorInvalidValue;
     if (!gemm_planes_supported(a_in.s) || a_in.nmat < 1 || a_in.nmat > 4 || (a_in.dump && a_in.nmat != 1)) return hipErrorInvalidValue;
     if (a_in.N < 1 || a_in.Npad % 64 != 0 || a_in.Npad < ((a_in.N + 63) & ~63)) return hipErrorInvalidValue;
     // buffer instructions address with 32-bit byte offsets: the LUT image and every weight matrix must stay below 2 GB
     if ((size_t)2 * a_in.s.K * a_in.Npad >= ((size_t)1 << 31)) return hipErrorInvalidValue;
     for (int i = 0; i < a_in.nmat; ++i)
         if ((size_t)((a_in.m[i].Mw + 3) / 4) * ((a_in.s.K / 32 + 63) / 64) * a_in.s.bits * 1024 >= ((size_t)1 << 31)) return hipErrorInvalidValue;
-    Gemm2Args a = a_in;
+    Args a = a_in;
     int gx = 0;
     for (int i = 0; i < a.nmat; ++i) {
         if (a.m[i].Mw % 4 != 0) return hipErrorInvalidValue;
@@ -850,16 +874,31 @@ hipError_t launch_gemm_planes(const Gemm2Args& a_in, hipStream_t st) {
     const bool us = a.s.m_groups >= 1;
     const int lds_bytes = nwv == 8 ? (us ? PFormU<8>::LDS_BYTES : PForm<8>::LDS_BYTES) : (us ? PFormU<4>::LDS_BYTES : PForm<4>::LDS_BYTES);
     // dynamic LDS above 64 KB is allowed per kernel, once (an instantiation's footprint never changes)
-    return sel_int<1, 2, 3, 4>(a.s.bits, [&](auto BITS) { return sel_bool(a.dump != nullptr, [&](auto DUMP) { return sel_int<4, 8>(nwv, [&](auto NWV) {
-        if (us) {
-            static size_t allowed = 0;
-            return launch_lds_once(allowed, lds_bytes, k_gemm_planes_us<BITS, DUMP, NWV>, g, b, lds_bytes, st, a);
-        }
-        return sel_bool(a.s.zero_point != 0, [&](auto ZP) { return sel_bool(a.sc_f16 != 0, [&](auto SCF16) {
-            static size_t allowed = 0;
-            return launch_lds_once(allowed, lds_bytes, k_gemm_planes<BITS, ZP, DUMP, SCF16, NWV>, g, b, lds_bytes, st, a);
+    if constexpr (BI) {
+        return sel_int<1, 2, 3, 4>(a.s.bits, [&](auto BITS) { return sel_int<4, 8>(nwv, [&](auto NWV) {
+            return sel_bool(a.s.zero_point != 0, [&](auto ZP) { return sel_bool(a.sc_f16 != 0, [&](auto SCF16) {
+                static size_t allowed = 0;
+                return launch_lds_once(allowed, lds_bytes, k_gemm_planes<BITS, ZP, false, SCF16, NWV, true>, g, b, lds_bytes, st, a);
+            }); });
         }); });
-    }); }); });
+    } else {
+        return sel_int<1, 2, 3, 4>(a.s.bits, [&](auto BITS) { return sel_bool(a.dump != nullptr, [&](auto DUMP) { return sel_int<4, 8>(nwv, [&](auto NWV) {
+            if (us) {
+                static size_t allowed = 0;
+                return launch_lds_once(allowed, lds_bytes, k_gemm_planes_us<BITS, DUMP, NWV>, g, b, lds_bytes, st, a);
+            }
+            return sel_bool(a.s.zero_point != 0, [&](auto ZP) { return sel_bool(a.sc_f16 != 0, [&](auto SCF16) {
+                static size_t allowed = 0;
+                return launch_lds_once(allowed, lds_bytes, k_gemm_planes<BITS, ZP, DUMP, SCF16, NWV>, g, b, lds_bytes, st, a);
+            }); });
+        }); }); });
+    }
 }
+
+#if TMAC_GEMM2_BI_TU
+hipError_t launch_gemm_planes(const Gemm2BiasArgs& a, hipStream_t st) { return launch_gemm_planes_any(a, st); }
+#else
+hipError_t launch_gemm_planes(const Gemm2Args& a, hipStream_t st) { return launch_gemm_planes_any(a, st); }
+#endif
 
 }  // namespace tmac

@@ -4,6 +4,7 @@
 //   tmac_runtime.cpp     error text, device binding, the knob block, lifecycle, self-tests, tmac_hip_reset_state
 //   tmac_kcfg.cpp        the kcfg.ini table and its lookups
 //   tmac_weights.cpp     weight registration (reference layout -> device layout)
+//   tmac_bias.cpp        the bias of a handle (y = W x + b): tmac_hip_weights_set_bias_dev, the handle's own fp32 copy
 //   tmac_kperm.cpp       the K permutation of act-order matrices from g_idx (tmac_kperm.h: no HIP, builds with plain g++); its C-ABI: tmac_pack_host.cpp
 //   tmac_pack_host.cpp   device-side packing: GPTQ tensors / plain codes -> reference blob (tmac_pack.hip) -> register_impl
 //   tmac_workspace.cpp   LUT workspace: the preprocessor entry points, lut_build (the one caller of the LUT builders; what a workspace holds and
@@ -70,6 +71,7 @@ struct tmac_hip_weights {
     int fa = 0;             // fast-aggregation mode these weights were registered under (0 = exact)
     size_t w_bytes = 0, sc_bytes = 0;
     std::shared_ptr<KPermData> kperm;   // act-order: the matrix is W[:, perm] and every LUT build gathers x[perm]; null = none
+    float* bias = nullptr;  // y = W x + b (tmac_hip_weights_set_bias_dev): the handle's own fp32 copy, [Mw] padded with zeros to a multiple of 64 elements; null = none
 };
 
 struct tmac_hip_workspace {
@@ -213,6 +215,12 @@ int fill_fused_args(FusedArgs& fa, const FusedCall& c);
 // Alignment of caller-owned device pointers: ACT_ALIGN, XFORM_ALIGN and misaligned are tmac_xform.h's; the GEMMs store four outputs at a
 // time (fp32: 16 bytes, fp16: 8).
 inline size_t out_align(tmac_dtype_t d) { return d == TMAC_F16 ? 8 : 16; }
+// What k_gemv_quad's MFMA form with an in-kernel LUT build takes, as the set of conditions a matrix misses (0: it is served).  A door
+// asks for the conditions in its scope and words its own refusal.
+// The conditions: the reference-layout variant or the v_mqsad accumulate is selected | not registered in the QUAD layout, or its tiled
+// kernel does not cover the configuration | fast-aggregation weights | gemv_quad_supported says no.
+enum : unsigned { QM_REF_VARIANT = 1, QM_MQSAD_VARIANT = 2, QM_LAYOUT = 4, QM_FAST_AGG = 8, QM_SHAPE = 16 };
+unsigned quad_mfma_misses(const tmac_hip_weights* w);
 
 // ---- tuner (tmac_tuner.cpp) -----------------------------------------------------------------------
 void tuned_config(const FusedArgs& fa, int total_q, int& ft, int& wpq);   // leaves ft / wpq alone when nothing is recorded

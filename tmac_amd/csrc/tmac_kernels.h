@@ -66,6 +66,17 @@ struct FusedPermArgs : FusedArgs {
     const int32_t* perm;     // int32 [K], every value < K, 16-byte aligned (tmac_hip_kperm)
 };
 
+// k_gemv_quad's bias instantiations (BI: handles registered with a bias, tmac_hip_weights_set_bias_dev): y = W x + b, the add in front of
+// the output's one store.  bias[i]: the handle's own fp32 copy for matrix i ([Mw] padded with zeros to a multiple of 64 elements,
+// 256-byte aligned), or null -- the matrix has none and stores what the plain call stores.  Argument blocks of their own, plain and
+// transformed: the other instantiations keep theirs.
+struct FusedBiasArgs : FusedArgs {
+    const float* bias[4];
+};
+struct FusedXfBiasArgs : FusedXfArgs {
+    const float* bias[4];
+};
+
 // The same transforms for N > 1 activation rows (tmac_hip_qgemm_fused_xf_rows_dev): the argument block of k_xf_rows (the row pass: residual_out
 // and 1 / rms per row) and of the XF instantiations of the three N > 1 LUT builders (k_lut_image, k_preprocess_pairs, k_preprocess_pairs_row),
 // which replace their activation load by xf_rows_x8 (tmac_quad_core.h).  Row n of every [N][K] operand is read for row n of the activations.
@@ -125,6 +136,10 @@ struct Gemm2Args {
     int apg_shift;            // filled by the launcher: log2(act groups per weight group)
     unsigned long long* stamps; // optional s_memrealtime stamps of workgroup 0: [wave 8][step 64][8] (profiling; tools/gemm2_stamps.py)
     int form;                 // 0: by the number of tiles | 1: eight-wave workgroups, one per CU | 2: four-wave workgroups, two per CU
+};
+// k_gemm_planes' bias instantiations (per-group scales): bias[i] as in FusedBiasArgs, added to the four outputs of a store
+struct Gemm2BiasArgs : Gemm2Args {
+    const float* bias[4];
 };
 
 struct GemvArgs {
@@ -223,6 +238,10 @@ bool gemm_planes_supported(const Shape& s);
 hipError_t launch_lut_image(const void* B, int act_f16, void* bimg, float* colv, int K, int N, int Npad, hipStream_t st, const XfRowsGateArgs* xf = nullptr,
                             const int32_t* perm = nullptr);
 hipError_t launch_gemm_planes(const Gemm2Args& a, hipStream_t st);
+// ... with a bias on at least one matrix (per-group scales, no tap: anything else is hipErrorInvalidValue)
+hipError_t launch_gemm_planes(const Gemm2BiasArgs& a, hipStream_t st);
+// a handle's own copy of its bias (tmac_pack.hip): bias [Mw] of dtype src (tmac_src_dtype_t) -> fp32 out [Mpad], elements Mw .. Mpad - 1 zero
+hipError_t launch_bias_copy(const void* bias, int src, float* out, int Mw, int Mpad, hipStream_t st);
 // fused kernel (tmac_fused.hip)
 size_t qlut_lds_u4(int K);   // uint4 per activation row of the LDS-image LUT
 hipError_t launch_gemv_fused(const FusedArgs& a, int N, bool build_lut, hipStream_t st);
@@ -237,6 +256,11 @@ hipError_t launch_gemv_quad(const FusedXfArgs& a, int N, bool build_lut, int ft,
 // ... and with the gather of an act-order permutation in its activation loads (N = 1, LUT built in-kernel, MFMA accumulate, per-group
 // scales): the same covered configurations, the same fall-back.
 hipError_t launch_gemv_quad(const FusedPermArgs& a, int N, bool build_lut, int ft, int wpq, bool strict, hipStream_t st);
+// ... and with a bias added at the store (MFMA accumulate, per-group scales, no tap; any N): the LUT built in-kernel in the covered
+// configurations with the same fall-back, or copied from the workspace's image (512-thread workgroups: both are covered).  The transformed
+// form: N = 1, NORM and the silu GLU.
+hipError_t launch_gemv_quad(const FusedBiasArgs& a, int N, bool build_lut, int ft, int wpq, bool strict, hipStream_t st);
+hipError_t launch_gemv_quad(const FusedXfBiasArgs& a, int N, bool build_lut, int ft, int wpq, bool strict, hipStream_t st);
 // the launcher of one translation unit of tmac_quad.hip (defined and instantiated there for its BITS, SCF16 and both argument blocks): the
 // instantiation the plan names; a: precomputed (fused_precompute).  (Also for FusedPermArgs.)
 template <int BITS, bool SCF16, class Args>

@@ -43,6 +43,22 @@ hipError_t launch_gemv_quad(const FusedPermArgs& a, int N, bool build_lut, int f
                        [&](int total_q, QuadPlan& p) { return quad_plan_perm(a.s, total_q, ft, wpq, strict, p); });
 }
 
+// the bias blocks: per-group scales, MFMA accumulate, no tap of any kind; at least one matrix with a bias (the others: null)
+template <class Args>
+static bool bias_args_ok(const Args& a) {
+    bool any = false;
+    for (int i = 0; i < a.nmat && i < 4; ++i) any = any || a.bias[i] != nullptr;
+    return any && a.acc_mfma && !a.dump && !a.lut_tap && !a.stamps && a.s.m_groups < 1;
+}
+hipError_t launch_gemv_quad(const FusedBiasArgs& a, int N, bool build_lut, int ft, int wpq, bool strict, hipStream_t st) {
+    return quad_launch(a, N >= 1 && bias_args_ok(a), N, st,
+                       [&](int total_q, QuadPlan& p) { return quad_plan_bias(a.s, total_q, build_lut, 0, ft, wpq, strict, p); });
+}
+hipError_t launch_gemv_quad(const FusedXfBiasArgs& a, int N, bool build_lut, int ft, int wpq, bool strict, hipStream_t st) {
+    return quad_launch(a, N == 1 && build_lut && bias_args_ok(a) && !xf_args_bad(a), 1, st,
+                       [&](int total_q, QuadPlan& p) { return quad_plan_bias(a.s, total_q, true, a.xf_kind, ft, wpq, strict, p); });
+}
+
 // *launches (optional) grows by the number of k_gemv_rows launches made
 hipError_t launch_gemv_rows(const RowsArgs& a_in, hipStream_t st, int* launches) {
     RowsArgs a = a_in;

@@ -77,6 +77,7 @@ static bool quad_plan_finish(const Shape& s, int total_q, QuadPlan& p) {
     // configurations never exceed one workgroup per CU
     p.early = p.ft != 512 || (p.lutsrc == 1 && p.acc == 1 && !p.dump && p.gx <= 256);
     if (p.ga) return quad_ga_inst_exists(p.nr, p.ft, p.wpq, p.early);
+    if (p.bi) return quad_bi_inst_exists(p.lutsrc, p.nr, p.ft, p.wpq, p.early, p.xf);
     return quad_inst_exists(p.lutsrc, p.nr, p.ft, p.wpq, p.dump, p.acc, p.early, p.xf);
 }
 
@@ -118,6 +119,19 @@ bool quad_plan_perm(const Shape& s, int total_q, int force_ft, int force_wpq, bo
     if (!gemv_quad_supported(s) || s.m_groups >= 1 || s.K > QUAD_XF_MAX_K) return false;
     p.lutsrc = 1; p.acc = 1; p.ga = true;
     if (!quad_config_covered(s, total_q, force_ft, force_wpq, strict, p)) return false;
+    return quad_plan_finish(s, total_q, p);
+}
+
+bool quad_plan_bias(const Shape& s, int total_q, bool build_lut, int xf_kind, int force_ft, int force_wpq, bool strict, QuadPlan& p) {
+    p = QuadPlan{};
+    if (!gemv_quad_supported(s) || s.m_groups >= 1) return false;
+    if (xf_kind != 0 && (!build_lut || ((xf_kind & 0xff) != 1 && (xf_kind & 0xff) != 2) || (xf_kind >> 8) != 0)) return false;   // NORM, silu GLU
+    p.lutsrc = build_lut ? 1 : 0; p.acc = 1; p.bi = true; p.xf = xf_kind != 0;
+    if (build_lut) {
+        if (s.K > QUAD_XF_MAX_K || !quad_config_covered(s, total_q, force_ft, force_wpq, strict, p)) return false;
+    } else if (!quad_config(s, true, total_q, force_ft, force_wpq, p.ft, p.wpq)) {
+        return false;
+    }
     return quad_plan_finish(s, total_q, p);
 }
 

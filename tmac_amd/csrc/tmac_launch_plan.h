@@ -37,7 +37,7 @@ constexpr bool quad_config_exists(int ft, int wpq) {
 }
 constexpr bool quad_xf_covered(int ft, int wpq) { return (ft == 512 && (wpq == 1 || wpq == 2)) || (ft == 768 && wpq == 3) || (ft == 1024 && wpq == 4); }
 // Instantiation policy of k_gemv_quad<BITS, ZP, SM, LUTSRC, NR, FT, WPQ, DUMP, ACC, SCF16, EARLY, XF, GN, GT> (BITS, ZP, SM, SCF16: by translation
-// unit and scale flavour; GN, GT: every XF form has all four):
+// unit and scale flavour; GN, GT: every XF form has all four; GA and BI: quad_ga_inst_exists, quad_bi_inst_exists below):
 //   * NR is 2 or 6 tables per thread; 6 only where the kernel builds the LUT (LUTSRC 1) -- a copied image has no build to spread;
 //   * the v_mqsad accumulate (ACC 0, A/B variant 7), the prebuilt-LUT source (LUTSRC 0) and the integer tap (DUMP) exist for 512-thread
 //     workgroups only, and without EARLY;
@@ -54,6 +54,14 @@ constexpr bool quad_inst_exists(int lutsrc, int nr, int ft, int wpq, bool dump, 
 // configurations, no tap -- and never together with one.
 constexpr bool quad_ga_inst_exists(int nr, int ft, int wpq, bool early) { return quad_inst_exists(1, nr, ft, wpq, false, 1, early, true); }
 
+// The bias add (BI) lives at the store of the MFMA form, per-group scales, no tap.  LUT built in-kernel: where the transform and the gather
+// live (with a transform: NORM and the silu GLU, i.e. neither GN nor GT).  LUT copied from the workspace's image (the row loop behind a
+// half-table build, the split entry point): what the plain kernel has there -- 512-thread workgroups, two tables per thread, no EARLY.
+constexpr bool quad_bi_inst_exists(int lutsrc, int nr, int ft, int wpq, bool early, bool xf) {
+    if (lutsrc == 0) return !xf && quad_xf_covered(ft, wpq) && quad_inst_exists(0, nr, ft, wpq, false, 1, early, false);
+    return quad_inst_exists(1, nr, ft, wpq, false, 1, early, true);
+}
+
 struct QuadPlan {
     int ft, wpq;             // threads, waves per quad
     int nr;                  // tables built per thread (2 | 6)
@@ -64,6 +72,7 @@ struct QuadPlan {
     int gx;                  // grid (x)
     size_t lds_bytes;
     bool ga;                 // the gather of an act-order permutation in the activation loads (never with xf)
+    bool bi;                 // the bias add at the store (never with ga, gn, gt, dump or the v_mqsad accumulate)
 };
 constexpr int QUAD_XF_MAX_K = 24576;
 size_t quad_lds_bytes(const Shape& s, int nwv);
@@ -77,6 +86,10 @@ bool quad_plan(const Shape& s, int total_q, bool build_lut, bool dump, bool acc_
 bool quad_plan_xf(const Shape& s, int total_q, int xf_kind, int force_ft, int force_wpq, bool strict, QuadPlan& p);
 // the gather instantiations: quad_plan_xf's configuration rule (covered set, fall-back, strict), per-group scales only
 bool quad_plan_perm(const Shape& s, int total_q, int force_ft, int force_wpq, bool strict, QuadPlan& p);
+// The bias instantiations, per-group scales only.  build_lut: quad_plan_xf's configuration rule (covered set, fall-back, strict); xf_kind 0 =
+// no transform, else NORM or the silu GLU (anything else is refused).  !build_lut (never with a transform): the 512-thread configuration the
+// plain copy form takes -- a forced one outside (512,1) / (512,2) is refused as it is for the plain block.
+bool quad_plan_bias(const Shape& s, int total_q, bool build_lut, int xf_kind, int force_ft, int force_wpq, bool strict, QuadPlan& p);
 
 // ---- k_gemv_rows --------------------------------------------------------------------------------------------------------------------
 constexpr int ROWS_FT = 512, ROWS_NWV = ROWS_FT / 64;

@@ -786,4 +786,32 @@ hipError_t launch_pack_ternary(const void* packed, const float* scales, void* A_
     return hipGetLastError();
 }
 
+// ---- a handle's bias (tmac_hip_weights_set_bias_dev) --------------------------------------------------------------------------------------
+// bias [Mw] in fp32, fp16 or bf16 -> the handle's own fp32 copy out [Mpad]: the conversions are exact, elements Mw .. Mpad - 1 are zero (a
+// 16-byte load at a tile's edge reads the library's zeros).  Element-wise loads: nothing outside [bias, bias + Mw) is read.
+template <int SRC>
+__global__ __launch_bounds__(256) void k_bias_copy(const void* __restrict__ bias, float* __restrict__ out, int Mw, int Mpad) {
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= Mpad) return;
+    float v = 0.f;
+    if (i < Mw) {
+        if constexpr (SRC == pk::SRC_F32) v = static_cast<const float*>(bias)[i];
+        else if constexpr (SRC == pk::SRC_F16) v = __half2float(__ushort_as_half(static_cast<const uint16_t*>(bias)[i]));
+        else v = pk::bf16_bits_to_f32(static_cast<const uint16_t*>(bias)[i]);
+    }
+    out[i] = v;
+}
+
+hipError_t launch_bias_copy(const void* bias, int src, float* out, int Mw, int Mpad, hipStream_t st) {
+    if (Mw < 1 || Mpad < Mw) return hipErrorInvalidValue;
+    const dim3 g((unsigned)((Mpad + 255) / 256)), b(256);
+    switch (src) {
+        case pk::SRC_F32: hipLaunchKernelGGL(k_bias_copy<pk::SRC_F32>, g, b, 0, st, bias, out, Mw, Mpad); break;
+        case pk::SRC_F16: hipLaunchKernelGGL(k_bias_copy<pk::SRC_F16>, g, b, 0, st, bias, out, Mw, Mpad); break;
+        case pk::SRC_BF16: hipLaunchKernelGGL(k_bias_copy<pk::SRC_BF16>, g, b, 0, st, bias, out, Mw, Mpad); break;
+        default: return hipErrorInvalidValue;
+    }
+    return hipGetLastError();
+}
+
 }  // namespace tmac

@@ -13,7 +13,7 @@
 // NR tables built per thread; FT threads; WPQ waves per quad; DUMP integer tap; ACC 1 v_mfma_i32_16x16x64_i8
 // accumulate / 0 v_mqsad_pk_u16_u8 (A/B variant); XF a vector transform of the activations (residual add + RMSNorm,
 // gate(in) * in2, the gate silu, relu^2 or tanh-GELU: tmac_hip_qgemm_fused_xf_dev) between the activation loads and the table build, where every workgroup
-// holds the whole vector.  DESIGN.md 4.1, 4.2, 4.6.
+// holds the whole vector; BI the bias of a handle added in front of the output's store (y = W x + b).  DESIGN.md 4.1, 4.2, 4.6, 4.15.
 #include <hip/hip_runtime.h>
 #include <hip/hip_fp16.h>
 #include <stdint.h>
@@ -109,13 +109,21 @@ __device__ __forceinline__ void load_q(WFrag<BITS>& f, const FusedArgs& a, const
 // GA (LUTSRC 1, ACC 1, no tap, no transform): the gather of an act-order matrix -- the lane's eight activations are x[perm[8 p .. 8 p + 7]]
 // instead of x[8 p .. 8 p + 7] (FusedPermArgs); every line of it sits under if constexpr (GA), and everything from the act-group scale on is
 // the text of the plain build.
+// BI (MFMA form, per-group scales, no tap; with XF: NORM and the silu GLU): y = W x + b -- the matrix' bias (FusedBiasArgs / FusedXfBiasArgs:
+// the handle's fp32 copy, padded to whole quads, or null) is added to the output value in front of its one store, one correctly rounded
+// add; every line of it sits under if constexpr (BI).  Lane l < 4 loads the bias of its own output row at the store (one vector load of 4
+// bytes per output).  The other candidate -- the quad's four biases from their ONE wave-uniform address through the scalar unit's load path,
+// which does not queue behind the weight fragments in flight as a vector load does -- measured 1.7 % SLOWER over the eight llama-2-7B
+// N = 1 cells (seven of eight; profiles/r25_bias.txt), so it is not in the code.
 template <int BITS, bool ZP, int SM, int LUTSRC, int NR, int FT, int WPQ, bool DUMP, int ACC, bool SCF16, bool EARLY, bool XF = false, bool GN = false, bool GT = false,
-          bool GA = false>
-__global__ __launch_bounds__(FT) void k_gemv_quad(std::conditional_t<XF, FusedXfArgs, std::conditional_t<GA, FusedPermArgs, FusedArgs>> a) {
+          bool GA = false, bool BI = false>
+__global__ __launch_bounds__(FT) void k_gemv_quad(std::conditional_t<BI, std::conditional_t<XF, FusedXfBiasArgs, FusedBiasArgs>,
+                                                                     std::conditional_t<XF, FusedXfArgs, std::conditional_t<GA, FusedPermArgs, FusedArgs>>> a) {
     static_assert(!XF || (LUTSRC == 1 && ACC == 1 && !DUMP), "the transform lives in the in-kernel LUT build of the MFMA form");
     static_assert(!GA || (LUTSRC == 1 && ACC == 1 && !DUMP && !XF && SM == 0), "the gather lives in the in-kernel LUT build of the MFMA form, per-group scales");
     static_assert(!GN || XF, "GLU_NORM is a transform");
     static_assert(!GT || XF, "the gate belongs to a transform");
+    static_assert(!BI || (ACC == 1 && SM == 0 && !DUMP && !GA && !GN && !GT), "the bias: MFMA form, per-group scales, no tap; NORM and the silu GLU");
     extern __shared__ uint4 lds[];
     const unsigned long long t_entry = DUMP ? __builtin_amdgcn_s_memtime() : 0ull;   // before the first kernel-argument load
     constexpr int NWV = FT / 64, IPI = NWV / WPQ;
@@ -633,6 +641,15 @@ __global__ __launch_bounds__(FT) void k_gemv_quad(std::conditional_t<XF, FusedXf
     // reduce one quad over the 64 lanes (same-parity lanes of a row by DPP, rows by ds_bpermute), combine the
     // WPQ waves through LDS (double-buffered by iteration parity), store 4 outputs
     int parity = 0;
+    // BI: the bias of output row o = 4 lq + lane (lane < 4) of matrix mi; -0.0f, the add's neutral element, for a matrix without one
+    auto bias_of = [&](int mi, int o) -> float {
+        if constexpr (BI) {
+            const float* bp = a.bias[mi];
+            return bp != nullptr ? bp[o] : -0.0f;
+        } else {
+            return 0.f;
+        }
+    };
     auto finish_quad = [&](bool have, const FusedMat& M, int lq) {
         float* red = l_red + parity * (NWV * 16);
         if (ACC == 1 && SM != 2) {   // per-group scales: fp32 partials
@@ -645,7 +662,10 @@ __global__ __launch_bounds__(FT) void k_gemv_quad(std::conditional_t<XF, FusedXf
             }
             if (WPQ == 1) {
                 const int o = 4 * lq + lane;
-                if (have && lane < 4 && o < M.Mw) st_out(M.C, a.out_f16, (size_t)n * M.Mw + o, acc);
+                if (have && lane < 4 && o < M.Mw) {
+                    if constexpr (BI) acc = __fadd_rn(acc, bias_of(cc.mi, o));
+                    st_out(M.C, a.out_f16, (size_t)n * M.Mw + o, acc);
+                }
             } else {
                 if (lane < 4) red[w * 4 + lane] = acc;
                 __syncthreads();
@@ -654,7 +674,10 @@ __global__ __launch_bounds__(FT) void k_gemv_quad(std::conditional_t<XF, FusedXf
 #pragma unroll
                     for (int ww = 1; ww < WPQ; ++ww) t = __fadd_rn(t, red[(w + ww) * 4 + lane]);
                     const int o = 4 * lq + lane;
-                    if (o < M.Mw) st_out(M.C, a.out_f16, (size_t)n * M.Mw + o, t);
+                    if (o < M.Mw) {
+                        if constexpr (BI) t = __fadd_rn(t, bias_of(cc.mi, o));
+                        st_out(M.C, a.out_f16, (size_t)n * M.Mw + o, t);
+                    }
                 }
             }
         } else if (SM != 2) {
@@ -790,8 +813,9 @@ constexpr bool QSCF16 = TMAC_QUAD_SCF16 != 0;   // weight scales stored as fp16 
 // instantiates what passes it, so the predicate is the list of kernels this unit emits; the planner never names another.
 template <int BITS, bool SCF16, class Args>
 hipError_t launch_gemv_quad_unit(const Args& a, const QuadPlan& p, int N, hipStream_t st) {
-    constexpr bool XF = std::is_same_v<Args, FusedXfArgs>, GA = std::is_same_v<Args, FusedPermArgs>;
-    if (p.xf != XF || p.ga != GA || ((XF || GA) && N != 1)) return hipErrorInvalidValue;
+    constexpr bool BI = std::is_same_v<Args, FusedBiasArgs> || std::is_same_v<Args, FusedXfBiasArgs>;
+    constexpr bool XF = std::is_same_v<Args, FusedXfArgs> || std::is_same_v<Args, FusedXfBiasArgs>, GA = std::is_same_v<Args, FusedPermArgs>;
+    if (p.xf != XF || p.ga != GA || p.bi != BI || ((XF || GA) && N != 1)) return hipErrorInvalidValue;
     const dim3 g(p.gx, N), b(p.ft);
     // scale flavour: unified scale (SM 2: one scalar read per output, the dtype stays a run-time flag -- fp32 unit only), or per-group scales
     // with / without zero points
@@ -803,9 +827,19 @@ hipError_t launch_gemv_quad_unit(const Args& a, const QuadPlan& p, int N, hipStr
         return sel_bool(a.s.zero_point != 0, [&](auto ZP) { return f(ZP, std::integral_constant<int, 0>{}); });
     };
     return flavour([&](auto ZP, auto SM) { return sel_int<512, 768, 1024>(p.ft, [&](auto FT) { return sel_int<1, 2, 3, 4>(p.wpq, [&](auto WPQ) {
-        if constexpr (!quad_config_exists(FT, WPQ) || ((XF || GA) && !quad_xf_covered(FT, WPQ))) return hipErrorInvalidValue;
+        if constexpr (!quad_config_exists(FT, WPQ) || ((XF || GA || BI) && !quad_xf_covered(FT, WPQ))) return hipErrorInvalidValue;
         else return sel_int<2, 6>(p.nr, [&](auto NR) { return sel_bool(p.early, [&](auto EARLY) {
-            if constexpr (XF) {
+            if constexpr (BI) {      // per-group scales; transformed: NORM and the silu GLU (no GN, no GT); plain: the LUT built or copied
+                if (p.gn || p.gt || p.dump || p.acc != 1) return hipErrorInvalidValue;
+                if constexpr (SM != 0) return hipErrorInvalidValue;
+                else if constexpr (XF) {
+                    if constexpr (!quad_bi_inst_exists(1, NR, FT, WPQ, EARLY, true)) return hipErrorInvalidValue;
+                    else return launch_lds(k_gemv_quad<BITS, ZP, 0, 1, NR, FT, WPQ, false, 1, SCF16, EARLY, true, false, false, false, true>, g, b, p.lds_bytes, st, a);
+                } else return sel_bool(p.lutsrc != 0, [&](auto LUTSRC) {
+                    if constexpr (!quad_bi_inst_exists(LUTSRC, NR, FT, WPQ, EARLY, false)) return hipErrorInvalidValue;
+                    else return launch_lds(k_gemv_quad<BITS, ZP, 0, LUTSRC, NR, FT, WPQ, false, 1, SCF16, EARLY, false, false, false, false, true>, g, b, p.lds_bytes, st, a);
+                });
+            } else if constexpr (XF) {
                 return sel_bool(p.gn, [&](auto GN) { return sel_bool(p.gt, [&](auto GT) {
                     if constexpr (!quad_inst_exists(1, NR, FT, WPQ, false, 1, EARLY, true)) return hipErrorInvalidValue;
                     else return launch_lds(k_gemv_quad<BITS, ZP, SM, 1, NR, FT, WPQ, false, 1, SCF16, EARLY, true, GN, GT>, g, b, p.lds_bytes, st, a);
@@ -822,8 +856,15 @@ hipError_t launch_gemv_quad_unit(const Args& a, const QuadPlan& p, int N, hipStr
         }); });
     }); }); });
 }
+// (the bias instantiations in objects of their own, -DTMAC_QUAD_BI_TU=1: the ones above hold exactly the kernels they held before, and the
+// build stays parallel)
+#if defined(TMAC_QUAD_BI_TU) && TMAC_QUAD_BI_TU
+template hipError_t launch_gemv_quad_unit<TMAC_QUAD_BITS, QSCF16, FusedBiasArgs>(const FusedBiasArgs&, const QuadPlan&, int, hipStream_t);
+template hipError_t launch_gemv_quad_unit<TMAC_QUAD_BITS, QSCF16, FusedXfBiasArgs>(const FusedXfBiasArgs&, const QuadPlan&, int, hipStream_t);
+#else
 template hipError_t launch_gemv_quad_unit<TMAC_QUAD_BITS, QSCF16, FusedArgs>(const FusedArgs&, const QuadPlan&, int, hipStream_t);
 template hipError_t launch_gemv_quad_unit<TMAC_QUAD_BITS, QSCF16, FusedXfArgs>(const FusedXfArgs&, const QuadPlan&, int, hipStream_t);
 template hipError_t launch_gemv_quad_unit<TMAC_QUAD_BITS, QSCF16, FusedPermArgs>(const FusedPermArgs&, const QuadPlan&, int, hipStream_t);
+#endif
 
 }  // namespace tmac

@@ -130,6 +130,7 @@ extern "C" int32_t tmac_hip_free_weights(tmac_hip_weights* w) {
     if (w->SC) (void)hipFree(w->SC);
     if (w->A_ref) (void)hipFree(w->A_ref);
     if (w->S_ref) (void)hipFree(w->S_ref);
+    if (w->bias) (void)hipFree(w->bias);
     delete w;
     return brc;
 }

@@ -225,6 +225,26 @@ def _masters_on_device(weight):
     return weight.cuda().contiguous(), _SRC_CODES[name]
 
 
+def _bias_on_device(bias):
+    """(contiguous 1-D CUDA tensor, tmac_src_dtype_t) of a layer's bias: a torch tensor in fp32, fp16 or bf16 (uploaded if it is not on
+    the GPU), or a numpy array uploaded as it is -- float32, float16, or uint16 holding bf16 bit patterns.  Nothing is converted on the
+    host."""
+    import torch
+    if isinstance(bias, np.ndarray):
+        if bias.dtype == np.uint16:
+            bias = torch.from_numpy(np.ascontiguousarray(bias).view(np.int16)).view(torch.bfloat16)
+        elif bias.dtype in (np.float32, np.float16):
+            bias = torch.from_numpy(np.ascontiguousarray(bias))
+        else:
+            raise TypeError(f"bias must be float32, float16 or uint16 (bf16 bit patterns), not {bias.dtype}")
+    name = str(bias.dtype).replace("torch.", "")
+    if name not in _SRC_CODES:
+        raise TypeError(f"bias must be float32, float16 or bfloat16, not {name}")
+    if bias.dim() != 1:
+        raise ValueError("bias is 1-D: [Mw]")
+    return bias.cuda().contiguous(), _SRC_CODES[name]
+
+
 def _bitnet_args(weight, cfg, m_groups, eps, scale):
     """device tensors, shape and configuration of a BitNet matrix.  Without a cfg: the unified-scale configuration ``from_codes`` is handed
     for BitNet -- ``convert.default_bm``, kfactor 16, one activation group per row (act_group_size = K).  With one, its m_groups counts."""
@@ -359,13 +379,14 @@ class Weights:
 
     @classmethod
     def from_gptq(cls, qweight, scales, qzeros, cfg: Optional[KCfg] = None, gptq_v2: bool = True, dev_dtype=F16, act_group_size: int = 64,
-                  stream=None, g_idx=None) -> "Weights":
+                  stream=None, g_idx=None, bias=None) -> "Weights":
         """Register straight from GPTQ tensors -- torch CUDA tensors, or numpy arrays that are uploaded first -- packed into the reference
         blob on the GPU (tmac_hip_register_weights_gptq_dev).  The handle is the one ``Weights(*blob)`` gives.  Without a ``cfg`` the
         shapes come from ``convert.parse_gptq`` and the M-tile from ``convert.default_bm``; ``qzeros=None`` (no zero points) needs one.
         ``g_idx`` (act-order checkpoints: a CUDA int32 tensor, a numpy array or a KPerm): the handle holds the matrix in group order and
         carries the permutation (``.kperm``), through which every fused call gathers its activations; an identity g_idx gives a plain
-        handle (tmac_hip_register_weights_gptq_perm_dev)."""
+        handle (tmac_hip_register_weights_gptq_perm_dev).  ``bias`` ([Mw], fp32 / fp16 / bf16: a CUDA tensor or a numpy array): the
+        handle computes y = W x + b (tmac_hip_weights_set_bias_dev); with a ``g_idx`` that permutes, the library's refusal is raised."""
         qw, sc, qz, Mw, K, bits, cfg = _gptq_args(qweight, scales, qzeros, cfg, act_group_size)
         h = C.c_void_p()
         ref = _float_code(sc, "scales")        # the blob in the scales' own dtype: nothing is rounded on the way
@@ -378,14 +399,14 @@ class Weights:
                                                              C.byref(cfg), ref, dev_dtype, _stream(stream)))
         self = cls._adopt(h, Mw, K, bits, cfg)
         self.kperm = kp
-        return self
+        return self._with_bias(bias, stream)
 
     @classmethod
     def from_codes(cls, codes, scales, zeros, bits: int, cfg: Optional[KCfg] = None, dev_dtype=F16, act_group_size: int = 64,
-                   stream=None, g_idx=None) -> "Weights":
+                   stream=None, g_idx=None, bias=None) -> "Weights":
         """Register from unpacked codes uint8 [Mw][K] with scales / zeros [Mw][K/gs] already in T-MAC's convention (or [m_groups] unified
         scales with a ``cfg``), packed on the GPU (tmac_hip_register_weights_codes_dev).  The route for 3-bit weights.  ``g_idx``: as in
-        ``from_gptq`` (codes in the checkpoint's column order, scales / zeros in group order)."""
+        ``from_gptq`` (codes in the checkpoint's column order, scales / zeros in group order).  ``bias``: as in ``from_gptq``."""
         cd, sc, zr, Mw, K, cfg = _codes_args(codes, scales, zeros, bits, cfg, act_group_size)
         h = C.c_void_p()
         ref = _float_code(sc, "scales")
@@ -398,7 +419,7 @@ class Weights:
                                                               _stream(stream)))
         self = cls._adopt(h, Mw, K, bits, cfg)
         self.kperm = kp
-        return self
+        return self._with_bias(bias, stream)
 
     @classmethod
     def from_bitnet(cls, weight, cfg: Optional[KCfg] = None, m_groups: int = 1, eps: float = 1e-5, scale=None, dev_dtype=F32,
@@ -435,18 +456,19 @@ class Weights:
 
     @classmethod
     def from_dense(cls, weight, bits: int, group_size: int = 128, zero_point: bool = True, cfg: Optional[KCfg] = None, dev_dtype=F16,
-                   act_group_size: int = 64, stream=None) -> "Weights":
+                   act_group_size: int = 64, stream=None, bias=None) -> "Weights":
         """Register an UNQUANTISED matrix [Mw][K] -- a torch tensor in fp32, fp16 or bf16, or a numpy array uploaded as it is (float32,
         float16, uint16 = bf16 bit patterns) -- as a W1 - W4 handle with per-group scales: quantised by per-group round to nearest
         (GPTQ's quantiser without the error search) and packed on the GPU (tmac_hip_register_weights_rtn_dev; include/tmac_hip.h states
         the rule).  The handle is the one ``from_codes(*convert.rtn_quant(weight, bits, group_size, zero_point, dev_dtype == F16), bits,
         cfg, dev_dtype)`` gives: with fp16 device scales the scale is rounded to fp16 before the codes are derived.  A group that cannot
         be quantised -- a master that is not finite, a scale that is 0 or not finite in the scales' dtype -- is refused (TMACHipError
-        naming the count).  Without a ``cfg``: ``convert.default_bm``, kfactor 16; with one, its group_size and zero_point count."""
+        naming the count).  Without a ``cfg``: ``convert.default_bm``, kfactor 16; with one, its group_size and zero_point count.
+        ``bias``: as in ``from_gptq``."""
         w, src, Mw, K, cfg = _dense_args(weight, bits, group_size, zero_point, cfg, act_group_size)
         h = C.c_void_p()
         check(B.lib().tmac_hip_register_weights_rtn_dev(C.byref(h), _ptr(w), src, Mw, K, int(bits), C.byref(cfg), F32, dev_dtype, _stream(stream)))
-        return cls._adopt(h, Mw, K, int(bits), cfg)
+        return cls._adopt(h, Mw, K, int(bits), cfg)._with_bias(bias, stream)
 
     def __init__(self, A_ref, scales_ref, Mw: int, K: int, bits: int, cfg: KCfg, scales_dtype=F32, dev_dtype=F32,
                  on_device: bool = False, stream=None):
@@ -467,6 +489,31 @@ class Weights:
     @property
     def handle(self):
         return self._h
+
+    def _set_bias(self, bias, stream=None) -> None:
+        """y = W x + b from now on (tmac_hip_weights_set_bias_dev): ``bias`` is [Mw] in fp32, fp16 or bf16 -- a CUDA tensor, or a numpy
+        array uploaded first (uint16 = bf16 bit patterns).  The handle keeps an fp32 copy of its own.  Once per handle, straight after
+        registration; unified-scale and act-order handles are refused (TMACHipError)."""
+        b, src = _bias_on_device(bias)
+        if int(b.shape[0]) != self.Mw:
+            raise ValueError(f"bias holds {int(b.shape[0])} values: one per output row, Mw = {self.Mw}")
+        check(B.lib().tmac_hip_weights_set_bias_dev(self._h, _ptr(b), src, _stream(stream)))
+
+    def _with_bias(self, bias, stream=None) -> "Weights":
+        """the constructors' ``bias=``: set it, or free the new handle and raise what the library (or the shape check) raises"""
+        if bias is not None:
+            try:
+                self._set_bias(bias, stream)
+            except Exception:
+                self.free()
+                raise
+        return self
+
+    @property
+    def has_bias(self) -> bool:
+        has = C.c_int(0)
+        check(B.lib().tmac_hip_weights_has_bias(self._h, C.byref(has)))
+        return bool(has.value)
 
     def algorithmic_bytes(self) -> int:
         return int(B.lib().tmac_hip_weights_bytes(self._h))
@@ -775,14 +822,15 @@ class TMACGeMMWrapper:
             B.lib().tmac_hip_set_fast_aggregation(0)
 
     def register_gptq(self, qweight, scales, qzeros, cfg: Optional[KCfg] = None, gptq_v2: bool = True, dev_dtype=F16, stream=None,
-                      g_idx=None) -> Weights:
+                      g_idx=None, bias=None) -> Weights:
         """``Weights.from_gptq`` with this wrapper's act_group_size: GPTQ tensors (CUDA tensors, or numpy arrays uploaded first) -> handle,
-        the blob packed on the GPU.  ``g_idx``: an act-order checkpoint's group indices (tensor, array or KPerm)"""
-        return Weights.from_gptq(qweight, scales, qzeros, cfg, gptq_v2, dev_dtype, self._act_group_size, stream, g_idx)
+        the blob packed on the GPU.  ``g_idx``: an act-order checkpoint's group indices (tensor, array or KPerm); ``bias``: the layer's [Mw]"""
+        return Weights.from_gptq(qweight, scales, qzeros, cfg, gptq_v2, dev_dtype, self._act_group_size, stream, g_idx, bias)
 
-    def register_codes(self, codes, scales, zeros, bits: int, cfg: Optional[KCfg] = None, dev_dtype=F16, stream=None, g_idx=None) -> Weights:
+    def register_codes(self, codes, scales, zeros, bits: int, cfg: Optional[KCfg] = None, dev_dtype=F16, stream=None, g_idx=None,
+                       bias=None) -> Weights:
         """``Weights.from_codes`` with this wrapper's act_group_size"""
-        return Weights.from_codes(codes, scales, zeros, bits, cfg, dev_dtype, self._act_group_size, stream, g_idx)
+        return Weights.from_codes(codes, scales, zeros, bits, cfg, dev_dtype, self._act_group_size, stream, g_idx, bias)
 
     def register_bitnet(self, weight, cfg: Optional[KCfg] = None, m_groups: int = 1, eps: float = 1e-5, scale=None, dev_dtype=F32,
                         stream=None) -> Weights:
@@ -796,10 +844,10 @@ class TMACGeMMWrapper:
         return Weights.from_bitnet_packed(packed, weight_scale, cfg, linear_class, dev_dtype, stream)
 
     def register_dense(self, weight, bits: int, group_size: int = 128, zero_point: bool = True, cfg: Optional[KCfg] = None, dev_dtype=F16,
-                       stream=None) -> Weights:
+                       stream=None, bias=None) -> Weights:
         """``Weights.from_dense`` with this wrapper's act_group_size: an unquantised matrix (fp32 / fp16 / bf16) -> a W1 - W4 handle with
         per-group scales, quantised (round to nearest) and packed on the GPU"""
-        return Weights.from_dense(weight, bits, group_size, zero_point, cfg, dev_dtype, self._act_group_size, stream)
+        return Weights.from_dense(weight, bits, group_size, zero_point, cfg, dev_dtype, self._act_group_size, stream, bias)
 
     def llama_cpp_init(self, B_dev, M: int, K: int, N: int, bits: int, act_group_size: Optional[int] = None,
                        act_dtype: Optional[int] = None, stream=None, kperm: Optional[KPerm] = None) -> None:
