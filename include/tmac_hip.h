@@ -178,6 +178,29 @@ int32_t tmac_hip_register_weights_codes_dev(tmac_hip_weights** out, const void* 
                                             tmac_dtype_t sz_dtype, int Mw, int K, int bits, const tmac_kcfg* cfg,
                                             tmac_dtype_t ref_float, tmac_dtype_t dev_float, void* stream);
 
+/* ---- AutoAWQ checkpoints (WQLinear_GEMM, quantization_config.version "gemm", 4 bits) ---------------------------------------------
+ * A third input form of the device-side packing above.  AWQ packs eight WEIGHT ROWS per word, along the output axis, interleaved:
+ *   qweight int32 [K][Mw/8]     field i (bits 4i .. 4i+3) of word (k, c) is the code of weight row 8c + ORDER[i] at column k,
+ *                               ORDER = (0, 2, 4, 6, 1, 3, 5, 7); row 8c + j sits in field INV[j], INV = (0, 4, 1, 5, 2, 6, 3, 7).
+ *                               The word 0x76543210 gives rows 8c .. 8c+7 the codes 0, 4, 1, 5, 2, 6, 3, 7.
+ *   scales  scales_dtype [K/gs][Mw]
+ *   qzeros  int32 [K/gs][Mw/8]  the same field order; NULL exactly when cfg->zero_point == 0.  w = (q - z) * s with the stored z as it
+ *                               is (no + 1): the codes are T-MAC's, the blob's zero is (z - 8) * scale, rounded ONCE to scales_dtype,
+ *                               then converted to ref_float -- numpy's result on convert.unpack_awq's tensors, bit for bit
+ * The width is 4 and no argument: cfg must describe 4 bits (cfg->bm * cfg->n_tile_num == 4 * Mw where n_tile_num is filled in), anything
+ * else is TMAC_HIP_E_ARG, "AWQ is packed at 4 bits".  k_pack_awq_weights (tmac_pack.hip) reads every qweight word once; 16-byte loads
+ * where Mw is a multiple of 32 (every row of qweight then is 16-byte aligned), word loads otherwise.  The two calls are ordered behind
+ * the calling thread's deferred queue, which comes first.  Refusals, nothing launched and nothing written: as for the GPTQ pair --
+ * TMAC_HIP_E_ARG naming the argument for a NULL required pointer, any of the five base pointers below 16-byte alignment, qzeros present
+ * with zero_point == 0 or absent with it set, m_groups >= 1, a dtype other than TMAC_F32 / TMAC_F16; shape and configuration refusals are
+ * registration's own.  The handle is an ordinary per-group handle: tmac_hip_weights_set_bias_dev works on it unchanged.  Not served: the
+ * GEMV, GEMV-fast and Marlin versions of the format, widths other than 4, bf16 scales. */
+int32_t tmac_hip_pack_awq_dev(const void* qweight, const void* scales, const void* qzeros, tmac_dtype_t scales_dtype, int Mw, int K,
+                              const tmac_kcfg* cfg, void* A_ref_out, void* scales_ref_out, tmac_dtype_t ref_float, void* stream);
+int32_t tmac_hip_register_weights_awq_dev(tmac_hip_weights** out, const void* qweight, const void* scales, const void* qzeros,
+                                          tmac_dtype_t scales_dtype, int Mw, int K, const tmac_kcfg* cfg, tmac_dtype_t ref_float,
+                                          tmac_dtype_t dev_float, void* stream);
+
 /* ---- BitNet b1.58 master weights: the absmean rule on the device ------------------------------------------------------------
  * A BitNet checkpoint from its authors holds no codes: it holds master weights W [Mw][K], row-major, in fp32, fp16 or bf16 (src_dtype; a
  * dtype of its own -- tmac_dtype_t keeps its two values and its refusals).  The ternary levels come from the absmean rule of the BitNet

@@ -94,6 +94,9 @@ def load_library() -> C.CDLL:
                                                 C.c_int, vp], i32),
         "tmac_hip_register_weights_codes_dev": ([C.POINTER(vp), vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(KCfg), C.c_int, C.c_int,
                                                  vp], i32),
+        # AutoAWQ tensors (WQLinear_GEMM, 4 bits): the blob, the handle
+        "tmac_hip_pack_awq_dev": ([vp, vp, vp, C.c_int, C.c_int, C.c_int, C.POINTER(KCfg), vp, vp, C.c_int, vp], i32),
+        "tmac_hip_register_weights_awq_dev": ([C.POINTER(vp), vp, vp, vp, C.c_int, C.c_int, C.c_int, C.POINTER(KCfg), C.c_int, C.c_int, vp], i32),
         # BitNet master weights (the absmean rule): the scales alone, the blob, the handle
         "tmac_hip_absmean_dev": ([vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, vp, vp], i32),
         "tmac_hip_pack_absmean_dev": ([vp, C.c_int, vp, C.c_float, C.c_int, C.c_int, C.POINTER(KCfg), vp, vp, C.c_int, vp], i32),
@@ -207,6 +210,7 @@ def load_library() -> C.CDLL:
                 "tmac_hip_pack_gptq_perm_dev", "tmac_hip_pack_codes_perm_dev", "tmac_hip_register_weights_gptq_perm_dev",
                 "tmac_hip_register_weights_codes_perm_dev", "tmac_hip_preprocessor_perm_dev",
                 "tmac_hip_weights_set_bias_dev", "tmac_hip_weights_has_bias",
+                "tmac_hip_pack_awq_dev", "tmac_hip_register_weights_awq_dev",
                 "tmac_hip_debug_rows_kernel", "tmac_hip_debug_rows_stats", "tmac_hip_debug_rows_plan", "tmac_hip_debug_rows_comb_sums"} if os.environ.get("TMAC_HIP_LIB") else set()
     for name, (argt, rest) in sigs.items():
         try:

@@ -23,7 +23,8 @@ BitNet b1.58 checkpoints of master weights take the same two steps: ``scan_bitne
 the absmean rule and the packing on the GPU), and checkpoints of PACKED ternary weights (the Hugging Face BitNet quantiser, four weight
 rows per byte) ``scan_bitnet_packed_dir`` / ``load_bitnet_packed_dir`` (``Weights.from_bitnet_packed``), both further down this file.
 UNQUANTISED checkpoints (fp16 / bf16 / fp32 matrices) come last: ``scan_dense_dir`` / ``load_dense_dir`` (``Weights.from_dense``: per-group
-round to nearest and the packing on the GPU).
+round to nearest and the packing on the GPU).  AutoAWQ checkpoints (GEMM version, 4 bits: the Qwen2 ``*-AWQ`` releases) are at the end:
+``scan_awq_dir`` / ``load_awq_dir`` (``Weights.from_awq``); ``load_gptq_dir`` refuses them, naming that loader.
 """
 import json
 import os
@@ -127,6 +128,9 @@ def scan_gptq_dir(model_dir: str, act_order: bool = False) -> GptqScan:
     """The GPTQ triples of a checkpoint directory, in order of first appearance, without loading a tensor.  act_order: desc_act
     checkpoints are accepted and every layer must come with its ``.g_idx``."""
     qc = convert.get_quantization_config(model_dir, allow_desc_act=act_order)           # refuses desc_act otherwise
+    if str(qc.get("quant_method", "")).lower() == "awq":
+        raise RuntimeError("Models in {} are AWQ checkpoints (config.json: quantization_config.quant_method is \"awq\"), not GPTQ: AWQ packs along the "
+                           "output axis: use load_awq_dir".format(model_dir))
     parts = sorted(f for f in os.listdir(model_dir) if f.startswith("model") and f.endswith(".safetensors"))
     if not parts:
         raise RuntimeError("Models in {} not in GPTQ safetensors format (torch .bin checkpoints: convert them to safetensors first)".format(model_dir))
@@ -375,6 +379,8 @@ def scan_dense_dir(model_dir: str) -> DenseScan:
         method = qc.get("quant_method", "")
         if method == "bitnet":
             use = "load_bitnet_dir" if qc.get("quantization_mode", "offline") == "online" else "load_bitnet_packed_dir"
+        elif str(method).lower() == "awq":
+            use = "load_awq_dir"
         elif str(method).startswith("gptq") or "bits" in qc:
             use = "load_gptq_dir"
         else:
@@ -417,3 +423,100 @@ def load_dense_dir(model_dir: str, wrapper, bits: int, group_size: int = 128, ze
     scan = scan_dense_dir(model_dir)
     return {L.name: wrapper.register_dense(np.array(read_tensor(L.weight)), bits, group_size, zero_point, None, dev_dtype,
                                            bias=np.array(read_tensor(L.bias)) if L.bias is not None else None) for L in scan.layers}
+
+
+# ---- AutoAWQ checkpoints (WQLinear_GEMM, 4 bits): the official Qwen2 / Qwen2.5 *-AWQ releases and their like ----------------------------------
+class AwqLayer(NamedTuple):
+    name: str               # the layer: "<name>.qweight" without its suffix
+    qweight: TensorRef      # I32 [K][Mw / 8]: eight weight rows per word along the output axis (convert.unpack_awq)
+    scales: TensorRef       # F16 / F32 [K / gs][Mw]
+    qzeros: TensorRef       # I32 [K / gs][Mw / 8]
+    K: int
+    Mw: int
+    group_size: int
+    bias: Optional[TensorRef] = None       # "<name>.bias", F32 / F16 / BF16 [Mw], where the layer has one (Qwen2's q/k/v)
+
+
+class AwqScan(NamedTuple):
+    layers: List[AwqLayer]
+    skipped: List[str]      # dense layers the quantiser left alone (lm_head, modules_to_not_convert): "<name>.weight" without a .qweight
+    quantization_config: dict
+
+
+_AWQ_NOT_SERVED = ("gemv", "gemv_fast", "marlin")
+
+
+def scan_awq_dir(model_dir: str) -> AwqScan:
+    """The (qweight, scales, qzeros) triples of an AutoAWQ checkpoint directory, in order of first appearance, without loading a tensor.
+    ``config.json`` is read directly.  Refused (RuntimeError naming the field or the tensor): a ``quant_method`` other than "awq"; a
+    ``version`` other than "gemm" (case-insensitive; "gemv", "gemv_fast" and "marlin" lay the words out differently and are not served);
+    ``bits`` other than 4; ``zero_point: false`` (symmetric AWQ); a ``qweight`` without ``scales`` or ``qzeros``; another element type
+    than I32 (qweight, qzeros) / F16 or F32 (scales); shapes that are not [K][Mw/8], [K/gs][Mw], [K/gs][Mw/8] or byte ranges that do not
+    match them; a ``group_size`` that disagrees with the shapes (-1: one group per row, K).  Dense layers -- ``lm_head``, the entries of
+    ``modules_to_not_convert`` -- have a ``.weight`` and no ``.qweight``: they are no layers here, ``skipped`` names those of them that are
+    2-D.  A layer's ``.bias`` is found as the GPTQ scan finds it."""
+    with open(os.path.join(model_dir, "config.json"), "r", encoding="utf-8") as f:
+        qc = json.load(f).get("quantization_config") or {}
+    if str(qc.get("quant_method", "")).lower() != "awq":
+        raise RuntimeError("Models in {} not in AWQ format (config.json: quantization_config.quant_method is {!r}, \"awq\" expected)".format(
+            model_dir, qc.get("quant_method")))
+    version = str(qc.get("version", "gemm")).lower()
+    if version != "gemm":
+        raise RuntimeError("quantization_config.version is {!r}: the \"gemm\" layout (WQLinear_GEMM) is served; {} are not".format(
+            qc.get("version"), ", ".join(_AWQ_NOT_SERVED)))
+    if int(qc.get("bits", 4)) != 4:
+        raise RuntimeError("quantization_config.bits is {}: AWQ is served at 4 bits".format(qc.get("bits")))
+    if not qc.get("zero_point", True):
+        raise RuntimeError("quantization_config.zero_point is false: symmetric AWQ is not served")
+    parts = sorted(f for f in os.listdir(model_dir) if f.startswith("model") and f.endswith(".safetensors"))
+    if not parts:
+        raise RuntimeError("Models in {} not in AWQ safetensors format (torch .bin checkpoints: convert them to safetensors first)".format(model_dir))
+    index: Dict[str, TensorRef] = {}
+    order: List[str] = []
+    for part in parts:
+        for name, ref in safetensors_index(os.path.join(model_dir, part)).items():
+            if name not in index and name.endswith(".qweight"):
+                order.append(name)
+            index[name] = ref
+    gs_cfg = int(qc.get("group_size", 128))
+    layers = []
+    for qname in order:
+        base = qname[:-len(".qweight")]
+        qw, sc, qz = index[qname], index.get(base + ".scales"), index.get(base + ".qzeros")
+        if sc is None:
+            raise RuntimeError("{}.scales is missing".format(base))
+        if qz is None:
+            raise RuntimeError("{}.qzeros is missing".format(base))
+        for ref, suffix, ok in ((qw, ".qweight", ("I32",)), (qz, ".qzeros", ("I32",)), (sc, ".scales", ("F16", "F32"))):
+            if ref.dtype not in ok:
+                raise RuntimeError("{}{} has dtype {}: {} expected".format(base, suffix, ref.dtype, " or ".join(ok)))
+            if len(ref.shape) != 2 or (ref.end - ref.begin) != int(np.prod(ref.shape)) * np.dtype(_NP[ref.dtype]).itemsize:
+                raise RuntimeError("{}{}: shape {} does not match its {} bytes".format(base, suffix, ref.shape, ref.end - ref.begin))
+        K, Mw = qw.shape[0], sc.shape[1]
+        if K <= 0 or Mw <= 0 or qw.shape[1] * 8 != Mw or sc.shape[0] <= 0 or K % sc.shape[0] or qz.shape != (sc.shape[0], qw.shape[1]):
+            raise RuntimeError("{}: qweight {} / scales {} / qzeros {} are not AWQ GEMM shapes ([K][Mw/8], [K/gs][Mw], [K/gs][Mw/8])".format(
+                qname, qw.shape, sc.shape, qz.shape))
+        gs = K // sc.shape[0]
+        if gs != (K if gs_cfg == -1 else gs_cfg):
+            raise RuntimeError("{}.scales has {} groups of {} for K={}: quantization_config.group_size is {}".format(base, sc.shape[0], gs, K, gs_cfg))
+        layers.append(AwqLayer(base, qw, sc, qz, K, Mw, gs, _bias_ref(index, base, Mw)))
+    if not layers:
+        raise RuntimeError("Models in {} hold no AWQ layer (a *.qweight with .scales and .qzeros)".format(model_dir))
+    quantised = {L.name for L in layers}
+    skipped = [n[:-len(".weight")] for n, ref in index.items() if n.endswith(".weight") and len(ref.shape) == 2 and n[:-len(".weight")] not in quantised]
+    return AwqScan(layers, skipped, qc)
+
+
+def load_awq_dir(model_dir: str, wrapper, dev_dtype=F16) -> Dict[str, "object"]:
+    """{layer name: Weights} for every layer ``scan_awq_dir`` finds: the three packed tensors are uploaded as they lie in the file and
+    unpacked, permuted and re-tiled on the GPU (``wrapper.register_awq``).  A layer's ``.bias`` is uploaded as it lies in the file and
+    attached to the handle (y = W x + b).  The dense layers the scan skipped are the caller's."""
+    from .binding import KCfg
+    scan = scan_awq_dir(model_dir)
+    out = {}
+    for L in scan.layers:
+        cfg = KCfg.make(L.Mw, L.K, 4, convert.default_bm(4, L.Mw), 16, L.group_size, wrapper._act_group_size, True)
+        bias = np.array(read_tensor(L.bias)) if L.bias is not None else None
+        out[L.name] = wrapper.register_awq(np.array(read_tensor(L.qweight)), np.array(read_tensor(L.scales)), np.array(read_tensor(L.qzeros)), cfg,
+                                           dev_dtype, bias=bias)
+    return out

@@ -2,6 +2,8 @@
 ``tmac_hip_register_weights``.
 
 * GPTQ (v1 / v2) packed tensors -> biased uint weights, scales, T-MAC zeros      (``python/t_mac/model_utils.py:95-129``)
+* AutoAWQ (GEMM version, 4 bits) packed tensors -> the same four things (``unpack_awq``; the format is restated above it: nothing of
+  AutoAWQ is needed)
 * ``kcfg.ini`` emission for a set of (bits, M, K, N, m_groups) kernels           (``deploy/compile.py:153-165``; the
   file the converter and the runtime must share because bm / kfactor are baked into the weight bytes)
 * the per-tensor blob a T-MAC GGUF stores: ``[permuted weight bytes][fp32 scales]`` (``model_utils.py:243-271``), and
@@ -156,6 +158,59 @@ def unpack_gptq(qweight: np.ndarray, scales: np.ndarray, qzeros: np.ndarray, gpt
     if not gptq_v2:
         z = z + 1
     return np.ascontiguousarray(w), sc, (z - (2 ** (bits - 1))) * sc, bits, gs
+
+
+# AutoAWQ, WQLinear_GEMM (quantization_config.version "gemm"), 4 bits: eight fields per int32 word, packed along the OUTPUT axis.
+# Field i (bits 4i .. 4i+3) of qweight[k][c] holds the code of weight row 8c + AWQ_ORDER[i] at column k; row 8c + j sits in field
+# AWQ_INV[j].  qzeros the same.  Known answer: the word 0x76543210 gives rows 8c .. 8c+7 the codes 0, 4, 1, 5, 2, 6, 3, 7.
+AWQ_ORDER = (0, 2, 4, 6, 1, 3, 5, 7)
+AWQ_INV = (0, 4, 1, 5, 2, 6, 3, 7)
+
+
+def parse_awq(qweight, scales, qzeros) -> Tuple[int, int, int, int]:
+    """(K, M, bits = 4, group_size) from the AWQ tensor shapes: qweight int32 [K][M/8], scales [K/gs][M], qzeros int32 [K/gs][M/8]"""
+    K, M = int(qweight.shape[0]), int(scales.shape[1])
+    if len(qweight.shape) != 2 or len(scales.shape) != 2 or int(qweight.shape[1]) * 8 != M or int(scales.shape[0]) <= 0 or K % int(scales.shape[0]) or \
+            (qzeros is not None and tuple(int(d) for d in qzeros.shape) != (int(scales.shape[0]), M // 8)):
+        raise ValueError("qweight {} / scales {} / qzeros {} are not AWQ (GEMM, 4-bit) shapes: [K][M/8], [K/gs][M], [K/gs][M/8]".format(
+            tuple(qweight.shape), tuple(scales.shape), None if qzeros is None else tuple(qzeros.shape)))
+    return K, M, 4, K // int(scales.shape[0])
+
+
+def _unpack_awq_fields(x: np.ndarray) -> np.ndarray:
+    """int32 [R][C] -> uint8 [R][8 C]: column 8c + j is field AWQ_INV[j] of word c"""
+    f = _unpack_fields(x, 4)                                      # [R][C][8], field order
+    return np.ascontiguousarray(f[..., list(AWQ_INV)]).reshape(x.shape[0], -1)
+
+
+def unpack_awq(qweight: np.ndarray, scales: np.ndarray, qzeros: np.ndarray):
+    """AutoAWQ GEMM tensors -> (w uint8 [M][K] in [0, 16), scales [M][K/gs], zeros [M][K/gs], 4, group_size): what ``unpack_gptq`` returns.
+    AWQ dequantises ``(q - z) * s`` with the stored z as it is, so the codes are T-MAC's and the zeros are ``(z - 8) * scale`` in the
+    scales' dtype (``weights.py:29-31``).  The host reference of ``tmac_hip_pack_awq_dev`` / ``Weights.from_awq``, never the route."""
+    if qzeros is None:
+        raise ValueError("qzeros is None: AWQ without zero points (symmetric AWQ) is not served")
+    if qweight.dtype != np.int32 or qzeros.dtype != np.int32:
+        raise TypeError("qweight and qzeros must be int32")
+    K, M, bits, gs = parse_awq(qweight, scales, qzeros)
+    w = _unpack_awq_fields(qweight).T                             # [K][M] -> [M][K]
+    sc = np.ascontiguousarray(scales.T)
+    z = _unpack_awq_fields(qzeros).T.astype(sc.dtype)
+    return np.ascontiguousarray(w), sc, (z - 8) * sc, bits, gs
+
+
+def pack_awq(w: np.ndarray, scales: np.ndarray, z: np.ndarray):
+    """The inverse of ``unpack_awq`` (tests, fixtures, the benchmark tool): codes uint8 [M][K] in [0, 16), scales [M][K/gs] and the
+    integer zero points z uint8 [M][K/gs] in [0, 16) -- ``unpack_awq``'s zeros are ``(z - 8) * scales`` -- -> (qweight int32 [K][M/8],
+    scales [K/gs][M], qzeros int32 [K/gs][M/8])."""
+    w, z = np.asarray(w), np.asarray(z)
+    if w.ndim != 2 or w.shape[0] % 8 or z.ndim != 2 or z.shape[0] != w.shape[0] or tuple(scales.shape) != tuple(z.shape) or max(int(w.max()), int(z.max())) > 15:
+        raise ValueError("w is [M][K] and z [M][K/gs], both in [0, 16), M a multiple of 8; scales is [M][K/gs]")
+
+    def fields(a):                                                # uint8 [M][C] -> int32 [C][M/8]
+        f = a.T.reshape(a.shape[1], a.shape[0] // 8, 8)[..., list(AWQ_ORDER)].astype(np.uint32)      # field i takes row 8c + ORDER[i]
+        return (f << (np.arange(8, dtype=np.uint32) * np.uint32(4))).sum(axis=-1, dtype=np.uint32).view(np.int32)
+
+    return np.ascontiguousarray(fields(w)), np.ascontiguousarray(np.asarray(scales).T), np.ascontiguousarray(fields(z))
 
 
 def bf16_bits_to_f32(bits: np.ndarray) -> np.ndarray:
@@ -379,6 +434,20 @@ def preprocess_for_t_mac_gpu(kcfg_file: str, qweight, scales, qzeros, gptq_v2: b
     zp = e["scales_size"] >= 2 * Mw * (K // e["group_size"])
     cfg = KCfg.make(Mw, K, bits, e["bm"], e["kfactor"], e["group_size"], 64, zp)
     A, S = wrapper.pack_gptq(qweight, scales, qzeros if zp else None, cfg, gptq_v2, F32)
+    return np.concatenate([A.cpu().numpy(), S.cpu().numpy().view(np.uint8)])
+
+
+def preprocess_awq_for_t_mac_gpu(kcfg_file: str, qweight, scales, qzeros) -> np.ndarray:
+    """``preprocess_for_t_mac(kcfg_file, w, scales, zeros, 4)`` on the tensors ``unpack_awq(qweight, scales, qzeros)`` gives, byte for byte,
+    with the unpacking and the permutation done on the GPU (``tmac_hip_pack_awq_dev``): the twin of ``preprocess_for_t_mac_gpu`` for AutoAWQ
+    GEMM checkpoints.  A kcfg section without zero points drops the zeros, as there."""
+    from . import wrapper
+    from .binding import KCfg, F32
+    K, Mw, bits, gs = parse_awq(qweight, scales, qzeros)
+    e = read_kcfg_entry(kcfg_file, Mw, K, bits)
+    zp = e["scales_size"] >= 2 * Mw * (K // e["group_size"])
+    cfg = KCfg.make(Mw, K, bits, e["bm"], e["kfactor"], e["group_size"], 64, zp)
+    A, S = wrapper.pack_awq(qweight, scales, qzeros if zp else None, cfg, F32)
     return np.concatenate([A.cpu().numpy(), S.cpu().numpy().view(np.uint8)])
 
 

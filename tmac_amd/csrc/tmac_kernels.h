@@ -170,6 +170,10 @@ hipError_t launch_pack_gptq(const void* qweight, const void* scales, const void*
                             Dtype out_dt, const Shape& s, hipStream_t st, const int32_t* perm = nullptr);
 hipError_t launch_pack_codes(const void* codes, const void* scales, const void* zeros, Dtype sz_dt, void* A_out, void* S_out, Dtype out_dt,
                              const Shape& s, hipStream_t st, const int32_t* perm = nullptr);
+// AutoAWQ tensors (WQLinear_GEMM: qweight int32 [K][Mw / 8], scales [K / gs][Mw], qzeros int32 [K / gs][Mw / 8] or NULL = no zero points;
+// the format: tmac_pack.h), bits = 4, per-group scales, Mw a multiple of 8 -> the same two halves.
+hipError_t launch_pack_awq(const void* qweight, const void* scales, const void* qzeros, Dtype scales_dt, void* A_out, void* S_out, Dtype out_dt,
+                           const Shape& s, hipStream_t st);
 // BitNet master weights W [Mw][K] (src: tmac_src_dtype_t; 16-byte aligned, K a multiple of 4, Mw of m_groups).  launch_absmean: the fp32
 // scale of each of the m_groups row blocks, fmaxf(mean |w|, eps), through `partials` (absmean_partial_count doubles of scratch).
 // launch_pack_dense: bits = 2, unified scales -- the levels of the absmean rule under `scales` (fp32 [m_groups], all > 0) straight into

@@ -6,7 +6,8 @@
 // kernels call the same functions.  The one piece of floating point: the BitNet absmean rule (master weights -> ternary levels), shared
 // the same way with tests/cpp/pack_dense_main.cc.  The packed ternary format of BitNet checkpoints (four weight rows per byte) is integers
 // again: tests/cpp/pack_ternary_main.cc.  Floating point once more: per-group round to nearest of dense masters to W1 - W4 codes (scale, zero
-// code, code, the fp16 rounding of the scale), shared with tests/cpp/pack_rtn_main.cc.
+// code, code, the fp16 rounding of the scale), shared with tests/cpp/pack_rtn_main.cc.  Integers again: the AutoAWQ field rule and its plane
+// extraction (eight weight rows per word along the output axis), shared with tests/cpp/pack_awq_main.cc.
 //
 //   M-space row     r    = (o / 8) * 8 * bits + p * 8 + o % 8                                (o: weight row, p: bit plane)
 //   nibble(r, t)         = sum_ig bit_p(w[o][4 t + ig]) << ig
@@ -79,6 +80,25 @@ TMAC_PACK_HD uint32_t codes_four(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t
 // stores z - 1).  The zero itself is multiplier * scale, rounded ONCE to the scales' dtype: the fp32 product of an fp16 scale and this
 // small integer is exact, so one conversion to fp16 gives numpy's fp16 product (overflow to infinity included).
 TMAC_PACK_HD float gptq_zero_multiplier(uint32_t z, int v1, int bits) { return (float)((int)z + (v1 ? 1 : 0) - (1 << (bits - 1))); }
+
+// ---- AutoAWQ (WQLinear_GEMM, 4 bits) -------------------------------------------------------------------------------------
+// qweight int32 [K][Mw / 8] packs along the OUTPUT axis: word (k, c) holds the codes of the eight weight rows 8 c .. 8 c + 7 at column k,
+// interleaved -- field i (bits 4 i .. 4 i + 3) belongs to row 8 c + ORDER[i], ORDER = (0, 2, 4, 6, 1, 3, 5, 7); row 8 c + j sits in field
+// INV[j], INV = (0, 4, 1, 5, 2, 6, 3, 7).  qzeros int32 [K / gs][Mw / 8] the same way.  Known answer: 0x76543210 gives rows 8 c .. 8 c + 7
+// the codes 0, 4, 1, 5, 2, 6, 3, 7.  The codes are T-MAC's as they stand; the stored zero is z itself (no + 1): gptq_zero_multiplier(z, 0, 4).
+TMAC_PACK_HD int awq_row_of_field(int i) { return (i % 4) * 2 + i / 4; }        // ORDER
+TMAC_PACK_HD int awq_field_of_row(int j) { return (j % 2) * 4 + j / 2; }        // INV
+TMAC_PACK_HD uint32_t awq_code(uint32_t word, int row_in_octet) { return (word >> (4 * awq_field_of_row(row_in_octet))) & 15u; }
+// Plane extraction.  The four words of one octet of weight rows at the four columns of ONE table (k = 4 t .. 4 t + 3) -> the eight
+// nibbles of plane p, in FIELD order: bit ig of nibble i is bit p of field i of word ig, so the nibble of row j of the octet is
+// awq_code(result, j) -- eight rows for four shift-and-mask steps.
+TMAC_PACK_HD uint32_t awq_plane_nibbles(uint32_t w0, uint32_t w1, uint32_t w2, uint32_t w3, int p) {
+    const uint32_t m = 0x11111111u;
+    return ((w0 >> p) & m) | (((w1 >> p) & m) << 1) | (((w2 >> p) & m) << 2) | (((w3 >> p) & m) << 3);
+}
+// lo / hi: awq_plane_nibbles of tables 2 tp and 2 tp + 1 -> the byte a packer's LDS image holds for (plane, row j of the octet, table pair
+// tp): the nibble of table 2 tp in the low half, of table 2 tp + 1 in the high half
+TMAC_PACK_HD uint32_t awq_plane_byte(uint32_t lo, uint32_t hi, int row_in_octet) { return awq_code(lo, row_in_octet) | (awq_code(hi, row_in_octet) << 4); }
 
 // ---- BitNet b1.58: master weights -> ternary levels (the absmean rule) -----------------------------------------------
 // A row block of R = Mw / m_groups rows has ONE scale:

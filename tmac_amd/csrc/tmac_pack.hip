@@ -19,6 +19,9 @@
 // Dense master weights to W1 - W4 with per-group scales (round to nearest): the scale and zero code of every (row, group) from its minimum
 // and maximum (k_rtn_params; groups that cannot be quantised are counted), then the codes kernel with a stage 1 that quantises four masters
 // per lane under them (k_pack_rtn_weights) and the codes form's scales kernel.
+// AutoAWQ GEMM tensors (qweight int32 [K][Mw / 8], eight weight rows per word along the output axis, interleaved): a stage 1 that owns
+// (octets of weight rows, a pair of tables) and turns eight words of consecutive k into the LDS bytes of eight rows (k_pack_awq_weights),
+// several 64-row output tiles per workgroup, and the GPTQ scales kernel with the zero taken from the interleaved field (k_pack_awq_scales).
 #include <hip/hip_fp16.h>
 #include <hip/hip_runtime.h>
 
@@ -398,6 +401,60 @@ __global__ __launch_bounds__(PACK_THREADS) void k_pack_ternary_weights_x4(const 
     for (int i = 0; i < 4; ++i) pack_store_groups<BITS>(lds + i * TILE, A_out, (i * R4 + pr0) / 16, (i + 1) * (R4 / 16), T, bm, kfactor);
 }
 
+// ---- AutoAWQ: qweight int32 [K][Mw / 8], eight weight rows per word along the OUTPUT axis, interleaved (the format: tmac_pack.h) ----------
+// A word holds one column of eight weight rows, and a byte of the LDS image is eight consecutive columns of ONE row and plane.  A thread
+// owns (V octets of weight rows, a pair of tables) and loads its 8 x V words (V = 4: one 16-byte load per k, for Mw a multiple of 32,
+// where every qweight row is 16-byte aligned; V = 1: word loads, any Mw a multiple of 8).  Per octet and plane it folds the four words of
+// each table into eight nibbles in field order (pk::awq_plane_nibbles: four shift-and-mask steps), takes row j's nibble of both tables
+// from field INV[j] (pk::awq_plane_byte) and writes the 32 x V bytes of (plane, row of the octets, its table pair) itself: one writer per
+// LDS byte, no shuffles.  Consecutive
+// threads take consecutive octets of one table pair, so a load instruction of a wave runs along the words of a qweight row.
+// TILES output tiles of 64 weight rows per workgroup, one LDS image each, stage 2 once per image (as k_pack_ternary_weights_x4):
+// 8 TILES words = 32 TILES contiguous bytes of every qweight row of the tile.  Tails: octets >= Mw / 8 and columns >= K load nothing
+// (a column >= K counts as zeros, in a byte whose upper table stage 2 does not store); stage 2 stores nothing past Mw / 8 groups or T tables.
+constexpr int AWQ_TILES = 4;               // 64-row output tiles per workgroup: 32 octets = one 128-byte line of every qweight row
+template <int V>
+__global__ __launch_bounds__(PACK_THREADS) void k_pack_awq_weights(const uint32_t* __restrict__ qweight, uint8_t* __restrict__ A_out, int Mw, int K,
+                                                                   int bm, int kfactor) {
+    constexpr int BITS = 4, TILES = AWQ_TILES, TILE = PACK_ROWS * BITS * PACK_STRIDE, OCTETS = TILES * PACK_ROWS / 8, LOADS = OCTETS / V;
+    static_assert(V == 1 || V == 4, "word loads or 16-byte loads");
+    __shared__ __attribute__((aligned(16))) uint8_t lds[TILES * TILE];
+    const int T = K / 4, MO = Mw / 8;      // MO: octets of weight rows = words per qweight row = groups of 32 M-space rows
+    const int c0 = blockIdx.y * OCTETS, k0 = blockIdx.x * (PACK_TABLES * 4);
+    for (int idx = threadIdx.x; idx < LOADS * (PACK_TABLES / 2); idx += PACK_THREADS) {
+        const int tp = idx / LOADS, cl = (idx % LOADS) * V;
+        const int c = c0 + cl;
+        if (c >= MO) continue;              // V = 4: MO is a multiple of 4, so are c0 and cl -- a quad is inside the row or outside it
+        uint32_t w[V][8];
+#pragma unroll
+        for (int kk = 0; kk < 8; ++kk) {
+            const int k = k0 + 8 * tp + kk;
+            if constexpr (V == 4) {
+                uint4 w4 = make_uint4(0, 0, 0, 0);
+                if (k < K) w4 = *reinterpret_cast<const uint4*>(qweight + (size_t)k * MO + c);
+                w[0][kk] = w4.x; w[1][kk] = w4.y; w[2][kk] = w4.z; w[3][kk] = w4.w;
+            } else {
+                w[0][kk] = k < K ? qweight[(size_t)k * MO + c] : 0u;
+            }
+        }
+#pragma unroll
+        for (int v = 0; v < V; ++v) {
+            const int row0 = (cl + v) * 8;          // the octet's first weight row, counted from the workgroup's
+            uint8_t* img = lds + (row0 / PACK_ROWS) * TILE;
+#pragma unroll
+            for (int p = 0; p < BITS; ++p) {
+                const uint32_t lo = pk::awq_plane_nibbles(w[v][0], w[v][1], w[v][2], w[v][3], p), hi = pk::awq_plane_nibbles(w[v][4], w[v][5], w[v][6], w[v][7], p);
+#pragma unroll
+                for (int j = 0; j < 8; ++j) img[lds_row(p, row0 % PACK_ROWS + j) * PACK_STRIDE + tp] = (uint8_t)pk::awq_plane_byte(lo, hi, j);
+            }
+        }
+    }
+    __syncthreads();
+    // output tile i: weight rows 8 c0 + 64 i ..., i.e. groups from c0 + 8 i; the matrix ends at group MO
+#pragma unroll
+    for (int i = 0; i < TILES; ++i) pack_store_groups<BITS>(lds + i * TILE, A_out, c0 + i * (PACK_ROWS / 8), MO, T, bm, kfactor);
+}
+
 // ---- dense master weights -> W1 - W4 with per-group scales: round to nearest (the rule: tmac_pack.h) -------------------------------------
 // EPL masters of consecutive k as fp32, exactly, in one 16-byte load: 4 of fp32, 8 of fp16 / bf16.  EPL = 4 of a 16-bit dtype (group sizes
 // that are no multiple of 8): load_masters' 8-byte load.
@@ -553,6 +610,28 @@ __global__ __launch_bounds__(256) void k_pack_gptq_scales(const ST* __restrict__
     store_octet(out, o, sg, sc, zr, bm, bits, SG, qzeros != nullptr);
 }
 
+// AutoAWQ: k_pack_gptq_scales at 4 bits with the zero of row o + i taken from field INV[i] of the octet's word -- scales ST [SG][Mw],
+// qzeros int32 [SG][Mw / 8] (NULL without zero points), the stored zero is z itself
+template <class ST, class OT>
+__global__ __launch_bounds__(256) void k_pack_awq_scales(const ST* __restrict__ scales, const uint32_t* __restrict__ qzeros, OT* __restrict__ out, int Mw,
+                                                        int SG, int bm) {
+    constexpr int BITS = 4;
+    const int noct = Mw / 8;
+    const size_t idx = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (idx >= (size_t)SG * noct) return;
+    const int sg = (int)(idx / noct), o = (int)(idx % noct) * 8;
+    ST s[8];
+    load_vec(scales + (size_t)sg * Mw + o, s);
+    float sc[8], zr[8];
+    const uint32_t zw = qzeros ? qzeros[idx] : 0u;      // word (sg, o / 8)
+#pragma unroll
+    for (int i = 0; i < 8; ++i) {
+        sc[i] = to_f32(s[i]);
+        zr[i] = to_f32(from_f32<ST>(pk::gptq_zero_multiplier(pk::awq_code(zw, i), 0, BITS) * sc[i]));     // one rounding, to the scales' dtype
+    }
+    store_octet(out, o, sg, sc, zr, bm, BITS, SG, qzeros != nullptr);
+}
+
 // codes form: scales / zeros ST [Mw][SG], already in T-MAC's convention; consecutive threads take consecutive scale groups
 template <class ST, class OT>
 __global__ __launch_bounds__(256) void k_pack_codes_scales(const ST* __restrict__ scales, const ST* __restrict__ zeros, OT* __restrict__ out, int Mw, int SG,
@@ -614,6 +693,30 @@ hipError_t launch_pack_gptq(const void* qweight, const void* scales, const void*
         using OT = decltype(out_tag);
         hipLaunchKernelGGL((k_pack_gptq_scales<ST, OT>), dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, (const ST*)scales, (const uint32_t*)qzeros,
                            gptq_v2 ? 0 : 1, (OT*)S_out, s.Mw, SG, s.bits, s.bm);
+    });
+    return hipGetLastError();
+}
+
+// ---- AutoAWQ ---------------------------------------------------------------------------------------------------------------------------
+
+hipError_t launch_pack_awq(const void* qweight, const void* scales, const void* qzeros, Dtype scales_dt, void* A_out, void* S_out, Dtype out_dt,
+                           const Shape& s, hipStream_t st) {
+    if (s.bits != 4 || s.m_groups >= 1 || s.Mw % 8) return hipErrorInvalidValue;
+    const dim3 g((unsigned)((s.K / 4 + PACK_TABLES - 1) / PACK_TABLES), (unsigned)((s.Mw + AWQ_TILES * PACK_ROWS - 1) / (AWQ_TILES * PACK_ROWS))), b(PACK_THREADS);
+    const uint32_t* qw = (const uint32_t*)qweight;
+    uint8_t* A = (uint8_t*)A_out;
+    // 16-byte loads where every qweight row is 16-byte aligned (Mw / 8 words, a multiple of 4), word loads otherwise
+    if (s.Mw % 32 == 0) hipLaunchKernelGGL(k_pack_awq_weights<4>, g, b, 0, st, qw, A, s.Mw, s.K, s.bm, s.kfactor);
+    else hipLaunchKernelGGL(k_pack_awq_weights<1>, g, b, 0, st, qw, A, s.Mw, s.K, s.bm, s.kfactor);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return e;
+    const int SG = s.K / s.gs;
+    const size_t n = (size_t)SG * (s.Mw / 8);
+    by_dtypes(scales_dt, out_dt, [&](auto in_tag, auto out_tag) {
+        using ST = decltype(in_tag);
+        using OT = decltype(out_tag);
+        hipLaunchKernelGGL((k_pack_awq_scales<ST, OT>), dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, (const ST*)scales, (const uint32_t*)qzeros,
+                           (OT*)S_out, s.Mw, SG, s.bm);
     });
     return hipGetLastError();
 }

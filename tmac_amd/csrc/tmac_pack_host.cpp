@@ -2,7 +2,7 @@
 // the reference blob (tmac_hip_pack_*_dev) or straight to a registered handle (tmac_hip_register_weights_*_dev, through register_impl).
 // BitNet master weights (fp32 / fp16 / bf16) take the same two ways through the absmean rule (tmac_hip_*_absmean_dev), packed ternary
 // BitNet weights (four weight rows per byte) through tmac_hip_*_ternary_dev, dense master weights to W1 - W4 with per-group scales by
-// round to nearest through tmac_hip_*_rtn_dev.
+// round to nearest through tmac_hip_*_rtn_dev, AutoAWQ GEMM tensors (4 bits) through tmac_hip_*_awq_dev.
 #include <cmath>
 
 #include "tmac_host.h"
@@ -62,6 +62,29 @@ int32_t launch(const Shape& s, const GptqIn& in, void* A_out, void* S_out, tmac_
 int32_t launch(const Shape& s, const CodesIn& in, void* A_out, void* S_out, tmac_dtype_t ref_float, hipStream_t st, const int32_t* perm = nullptr) {
     const hipError_t e = launch_pack_codes(in.codes, in.scales, in.zeros, (Dtype)in.sz_dtype, A_out, S_out, (Dtype)ref_float, s, st, perm);
     return e == hipSuccess ? TMAC_HIP_OK : fail(TMAC_HIP_E_RUNTIME, "pack_codes: %s", hipGetErrorString(e));
+}
+
+// ---- AutoAWQ (the format: tmac_pack.h) ---------------------------------------------------------------------------------------------------
+struct AwqIn { const void *qweight, *scales, *qzeros; tmac_dtype_t scales_dtype; };
+
+// pack_check's rules for the codes form (NULL pointers, dtypes, make_shape's refusals, zeros against zero_point, alignment) and the format's
+// own: 4 bits, per-group scales
+int32_t check_awq(Shape& s, const AwqIn& in, const void* A_out, const void* S_out, bool outs, int Mw, int K, const tmac_kcfg* cfg, tmac_dtype_t ref_float) {
+    const PackArg args[] = {{"qweight", in.qweight, true}, {"scales", in.scales, true}, {"qzeros", in.qzeros, false},
+                            {"A_ref_out", A_out, outs}, {"scales_ref_out", S_out, outs}};
+    // the width a configuration describes is bm * n_tile_num / Mw (n_tile_num <= 0: not filled in, nothing to contradict)
+    if (cfg && cfg->n_tile_num > 0 && (long long)cfg->bm * cfg->n_tile_num != 4ll * Mw)
+        return fail(TMAC_HIP_E_ARG, "AWQ is packed at 4 bits: the configuration (bm=%d x n_tile_num=%d) does not describe Mw=%d rows of 4 bits", cfg->bm,
+                    cfg->n_tile_num, Mw);
+    const int32_t rc = pack_check(s, false, args, 5, in.qzeros, "qzeros", in.scales_dtype, "scales_dtype", Mw, K, 4, cfg, ref_float);
+    if (rc) return rc;
+    if (s.m_groups >= 1) return fail(TMAC_HIP_E_ARG, "m_groups = %d: the AWQ form has per-group scales only", s.m_groups);
+    return TMAC_HIP_OK;
+}
+
+int32_t launch(const Shape& s, const AwqIn& in, void* A_out, void* S_out, tmac_dtype_t ref_float, hipStream_t st, const int32_t* = nullptr) {
+    const hipError_t e = launch_pack_awq(in.qweight, in.scales, in.qzeros, (Dtype)in.scales_dtype, A_out, S_out, (Dtype)ref_float, s, st);
+    return e == hipSuccess ? TMAC_HIP_OK : fail(TMAC_HIP_E_RUNTIME, "pack_awq: %s", hipGetErrorString(e));
 }
 
 // pack into the caller's buffers: behind the calling thread's deferred queue like every entry point that writes caller memory
@@ -547,4 +570,28 @@ extern "C" int32_t tmac_hip_register_weights_codes_dev(tmac_hip_weights** out, c
     Shape s;
     const int32_t rc = check_codes(s, in, nullptr, nullptr, false, Mw, K, bits, cfg, ref_float);
     return rc ? rc : register_from(out, s, in, Mw, K, bits, cfg, ref_float, dev_float, stream);
+}
+
+// ---- AutoAWQ ---------------------------------------------------------------------------------------------------------------------------
+extern "C" int32_t tmac_hip_pack_awq_dev(const void* qweight, const void* scales, const void* qzeros, tmac_dtype_t scales_dtype, int Mw, int K,
+                                         const tmac_kcfg* cfg, void* A_ref_out, void* scales_ref_out, tmac_dtype_t ref_float, void* stream) {
+    const AwqIn in{qweight, scales, qzeros, scales_dtype};
+    Shape s;
+    const int32_t rc = check_awq(s, in, A_ref_out, scales_ref_out, true, Mw, K, cfg, ref_float);
+    return rc ? rc : pack_to(s, in, A_ref_out, scales_ref_out, ref_float, stream);
+}
+
+extern "C" int32_t tmac_hip_register_weights_awq_dev(tmac_hip_weights** out, const void* qweight, const void* scales, const void* qzeros,
+                                                     tmac_dtype_t scales_dtype, int Mw, int K, const tmac_kcfg* cfg, tmac_dtype_t ref_float,
+                                                     tmac_dtype_t dev_float, void* stream) {
+    if (!out) return fail(TMAC_HIP_E_ARG, "out is NULL");
+    const AwqIn in{qweight, scales, qzeros, scales_dtype};
+    Shape s;
+    int32_t rc = check_awq(s, in, nullptr, nullptr, false, Mw, K, cfg, ref_float);
+    if (rc) return rc;
+    if (dev_float != TMAC_F32 && dev_float != TMAC_F16) return fail(TMAC_HIP_E_ARG, "dev_float must be TMAC_F32 or TMAC_F16");
+    rc = ensure_device();
+    if (rc) return rc;
+    rc = defer_barrier();       // the three tensors may have been written by queued work
+    return rc ? rc : register_from(out, s, in, Mw, K, 4, cfg, ref_float, dev_float, stream);
 }

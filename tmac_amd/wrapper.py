@@ -187,6 +187,30 @@ def pack_gptq(qweight, scales, qzeros, cfg: Optional[KCfg] = None, gptq_v2: bool
     return A, S
 
 
+def _awq_args(qweight, scales, qzeros, cfg, act_group_size):
+    """device tensors, shape and configuration of an AutoAWQ GEMM triple (qweight int32 [K][Mw/8], scales [K/gs][Mw], qzeros int32
+    [K/gs][Mw/8] or None: no zero points, which needs a cfg saying so)"""
+    from . import convert
+    qw = _on_device(qweight, "qweight", ("int32",))
+    sc = _on_device(scales, "scales", ("float16", "float32"))
+    qz = _on_device(qzeros, "qzeros", ("int32",)) if qzeros is not None else None
+    K, Mw, bits, gs = convert.parse_awq(qw, sc, qz)
+    if cfg is None:
+        cfg = KCfg.make(Mw, K, bits, convert.default_bm(bits, Mw), 16, gs, act_group_size, qz is not None)
+    return qw, sc, qz, Mw, K, cfg
+
+
+def pack_awq(qweight, scales, qzeros, cfg: Optional[KCfg] = None, ref_dtype=F32, act_group_size: int = 64, stream=None):
+    """AutoAWQ GEMM tensors (4 bits) -> the reference blob, on the GPU (tmac_hip_pack_awq_dev): (A_ref uint8, scales_ref) as flat CUDA
+    tensors, exactly ``weights.preprocess_weights(*convert.unpack_awq(...))``.  Asynchronous on the stream; numpy inputs as in
+    ``pack_gptq``."""
+    qw, sc, qz, Mw, K, cfg = _awq_args(qweight, scales, qzeros, cfg, act_group_size)
+    A, S = _blob_buffers(Mw, K, 4, cfg, ref_dtype)
+    check(B.lib().tmac_hip_pack_awq_dev(_ptr(qw), _ptr(sc), _ptr(qz), _float_code(sc, "scales"), Mw, K, C.byref(cfg), _ptr(A), _ptr(S), ref_dtype,
+                                        _stream(stream)))
+    return A, S
+
+
 def pack_codes(codes, scales, zeros, bits: int, cfg: Optional[KCfg] = None, ref_dtype=F32, act_group_size: int = 64, stream=None, g_idx=None):
     """codes uint8 [Mw][K] + scales / zeros [Mw][K/gs] in T-MAC's convention -> the reference blob, on the GPU (tmac_hip_pack_codes_dev;
     with ``g_idx``: of ``codes[:, perm]``, tmac_hip_pack_codes_perm_dev)"""
@@ -400,6 +424,21 @@ class Weights:
         self = cls._adopt(h, Mw, K, bits, cfg)
         self.kperm = kp
         return self._with_bias(bias, stream)
+
+    @classmethod
+    def from_awq(cls, qweight, scales, qzeros, cfg: Optional[KCfg] = None, dev_dtype=F16, act_group_size: int = 64, stream=None,
+                 bias=None) -> "Weights":
+        """Register straight from AutoAWQ GEMM tensors (``quantization_config.version == "gemm"``, 4 bits: qweight int32 [K][Mw/8], scales
+        [K/gs][Mw], qzeros int32 [K/gs][Mw/8]) -- torch CUDA tensors, or numpy arrays uploaded as they are -- unpacked and packed into the
+        reference blob on the GPU (tmac_hip_register_weights_awq_dev).  The handle is the one ``from_codes(*convert.unpack_awq(...)[:3], 4)``
+        gives.  Without a ``cfg`` the shape is read off the tensors and the M-tile comes from ``convert.default_bm``.  ``bias``: as in
+        ``from_gptq``."""
+        qw, sc, qz, Mw, K, cfg = _awq_args(qweight, scales, qzeros, cfg, act_group_size)
+        h = C.c_void_p()
+        ref = _float_code(sc, "scales")        # the blob in the scales' own dtype: nothing is rounded on the way
+        check(B.lib().tmac_hip_register_weights_awq_dev(C.byref(h), _ptr(qw), _ptr(sc), _ptr(qz), ref, Mw, K, C.byref(cfg), ref, dev_dtype,
+                                                        _stream(stream)))
+        return cls._adopt(h, Mw, K, 4, cfg)._with_bias(bias, stream)
 
     @classmethod
     def from_codes(cls, codes, scales, zeros, bits: int, cfg: Optional[KCfg] = None, dev_dtype=F16, act_group_size: int = 64,
@@ -826,6 +865,11 @@ class TMACGeMMWrapper:
         """``Weights.from_gptq`` with this wrapper's act_group_size: GPTQ tensors (CUDA tensors, or numpy arrays uploaded first) -> handle,
         the blob packed on the GPU.  ``g_idx``: an act-order checkpoint's group indices (tensor, array or KPerm); ``bias``: the layer's [Mw]"""
         return Weights.from_gptq(qweight, scales, qzeros, cfg, gptq_v2, dev_dtype, self._act_group_size, stream, g_idx, bias)
+
+    def register_awq(self, qweight, scales, qzeros, cfg: Optional[KCfg] = None, dev_dtype=F16, stream=None, bias=None) -> Weights:
+        """``Weights.from_awq`` with this wrapper's act_group_size: AutoAWQ GEMM tensors (CUDA tensors, or numpy arrays uploaded first) ->
+        handle, the blob packed on the GPU"""
+        return Weights.from_awq(qweight, scales, qzeros, cfg, dev_dtype, self._act_group_size, stream, bias)
 
     def register_codes(self, codes, scales, zeros, bits: int, cfg: Optional[KCfg] = None, dev_dtype=F16, stream=None, g_idx=None,
                        bias=None) -> Weights:
