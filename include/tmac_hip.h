@@ -419,6 +419,42 @@ int32_t tmac_hip_qgemm_fused_dev(const tmac_hip_weights* const* weights, int nma
                                  tmac_dtype_t act_dtype, void* const* C_dev, tmac_dtype_t out_dtype, int N,
                                  void* stream);
 
+/* ---- expert banks: the top-k GEMVs of a mixture-of-experts layer, expert ids read on the GPU ---------------------------------------
+ * A BANK is E registered handles of one projection (all `gate`, all `up` or all `down` matrices of a layer) that a launch may pick among.
+ * It owns a device table with one entry per expert (QUAD-layout weights, device scales), so the kernel reaches expert e with two loads.
+ * The handles must match in Mw, K, bits, group size, zero-point setting and scale dtype, lie inside what k_gemv_quad's layout serves and
+ * carry per-group scales, no bias and no K permutation: anything else is refused with TMAC_HIP_E_ARG / TMAC_HIP_E_NOMATCH and a message
+ * that names the first offending expert index (E < 1: TMAC_HIP_E_ARG).  Banks of unified-scale (BitNet), biased and act-order handles
+ * are open.  A bank names its handles, it does not own them: free the bank before any of its experts (tmac_amd.ExpertBank keeps its
+ * Weights objects alive).  tmac_hip_bank_create returns when the table is on the device.
+ *
+ * tmac_hip_qgemm_experts_dev: S slots (1 <= S <= 8) whose experts ids_dev[S] (int32, device) names, over one or two banks that share the
+ * ids (gate / up in one launch; the banks share K and the quantisation config, their row counts may differ).  The activations B_dev are
+ * lut_rows rows of K values: 1 -- every slot reads the same vector -- or S -- slot s reads row s.
+ *   gates_dev == NULL (SLOTS):   C_dev[b] [S][Mw_b]: row s = W_b[ids[s]] . x_row(s)
+ *   gates_dev != NULL (COMBINE): one bank, lut_rows = S; C_dev[0] [Mw] = sum_s gates[s] * (W[ids[s]] . x_s) (fp32 [S], device), computed
+ *                                as acc = acc + gates[s] * y_s in slot order from 0 with y_s the value SLOTS stores (fp32): two roundings
+ *                                per slot, bit-reproducible from the SLOTS outputs; one store per output, no atomics, no second kernel.
+ * A slot whose id lies outside [0, E) is EMPTY (-1 is the documented "no expert" value): nothing is read through it, its SLOTS row is
+ * stored as zeros, it adds nothing to a COMBINE output.  The host reads neither ids_dev nor gates_dev.
+ * The call builds the LUT of its lut_rows rows into the stream's library-owned workspace (the builder and the rule of
+ * tmac_hip_qgemm_fused_dev: first use outside any stream capture) and launches k_gemv_experts once: capturable into a hipGraph, with the
+ * ids rewritten on the device between replays.  Like every entry point it runs behind the calling thread's deferred queue; inside a
+ * recording it is refused (TMAC_HIP_E_ARG).  B_dev 16-byte aligned, C_dev[b] 16-byte (fp32) / 8-byte (fp16), ids_dev and gates_dev
+ * 4-byte.  Refused by name: COMBINE with nbanks != 1 or lut_rows != S; activation rows whose tables do not fit 160 KiB of LDS
+ * (TMAC_HIP_E_NOMATCH; 8 rows fit up to K = 8192, 4 up to 18432, 2 up to 24576); S > 8.
+ * tmac_hip_debug_experts_plan: the launch plan of such a call (pure, no device), or its refusal. */
+typedef struct tmac_hip_bank tmac_hip_bank;
+int32_t tmac_hip_bank_create(tmac_hip_bank** out, const tmac_hip_weights* const* experts, int E, void* stream);
+int32_t tmac_hip_bank_free(tmac_hip_bank* bank);
+int32_t tmac_hip_bank_info(const tmac_hip_bank* bank, int* E, int* Mw, int* K, int* bits);
+int32_t tmac_hip_qgemm_experts_dev(const tmac_hip_bank* const* banks, int nbanks,
+        const void* B_dev, tmac_dtype_t act_dtype, int lut_rows,   /* 1 (shared x) or S */
+        const int32_t* ids_dev, const float* gates_dev /* NULL: SLOTS; else COMBINE */, int S,
+        void* const* C_dev, tmac_dtype_t out_dtype, void* stream);
+int32_t tmac_hip_debug_experts_plan(int K, int bits, int group_size, const int* bank_Mw, int nbanks, int S, int lut_rows, int combine,
+                                    int32_t* waves_per_quad, int32_t* grid, int32_t* items, size_t* lds_bytes);
+
 /* ---- deferred launches ---------------------------------------------------------------------
  * For callers that do not record (a backend hook called mat-mul by mat-mul).  tmac_hip_defer(1): from now on the calling thread's N = 1
  * tmac_hip_qgemm_fused_dev calls are QUEUED instead of launched; tmac_hip_flush launches what is queued as ONE stream-mode launch

@@ -132,6 +132,13 @@ def load_library() -> C.CDLL:
         "tmac_hip_preprocessor_dev": ([vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, vp], i32),
         "tmac_hip_qgemm_dev": ([vp, vp, vp, C.c_int, C.c_int, vp], i32),
         "tmac_hip_qgemm_fused_dev": ([C.POINTER(vp), C.c_int, vp, C.c_int, C.POINTER(vp), C.c_int, C.c_int, vp], i32),
+        # expert banks (mixture-of-experts layers): the bank, the top-k call with the ids read on the device, its plan
+        "tmac_hip_bank_create": ([C.POINTER(vp), C.POINTER(vp), C.c_int, vp], i32),
+        "tmac_hip_bank_free": ([vp], i32),
+        "tmac_hip_bank_info": ([vp] + [C.POINTER(C.c_int)] * 4, i32),
+        "tmac_hip_qgemm_experts_dev": ([C.POINTER(vp), C.c_int, vp, C.c_int, C.c_int, vp, vp, C.c_int, C.POINTER(vp), C.c_int, vp], i32),
+        "tmac_hip_debug_experts_plan": ([C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int), C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int32),
+                                         C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(sz)], i32),
         "tmac_hip_qgemm_fused_xf_dev": ([C.POINTER(vp), C.c_int, vp, C.c_int, C.POINTER(XForm), C.POINTER(vp), C.c_int, vp], i32),
         "tmac_hip_qgemm_fused_xf_rows_dev": ([C.POINTER(vp), C.c_int, vp, C.c_int, C.POINTER(XForm), C.POINTER(vp), C.c_int, C.c_int, vp], i32),
         "tmac_hip_debug_xf_rows_plan": ([C.POINTER(vp), C.c_int, C.POINTER(vp), C.c_int, C.POINTER(C.c_int32), C.POINTER(C.c_int32)], i32),
@@ -211,7 +218,8 @@ def load_library() -> C.CDLL:
                 "tmac_hip_register_weights_codes_perm_dev", "tmac_hip_preprocessor_perm_dev",
                 "tmac_hip_weights_set_bias_dev", "tmac_hip_weights_has_bias",
                 "tmac_hip_pack_awq_dev", "tmac_hip_register_weights_awq_dev",
-                "tmac_hip_debug_rows_kernel", "tmac_hip_debug_rows_stats", "tmac_hip_debug_rows_plan", "tmac_hip_debug_rows_comb_sums"} if os.environ.get("TMAC_HIP_LIB") else set()
+                "tmac_hip_debug_rows_kernel", "tmac_hip_debug_rows_stats", "tmac_hip_debug_rows_plan", "tmac_hip_debug_rows_comb_sums",
+                "tmac_hip_bank_create", "tmac_hip_bank_free", "tmac_hip_bank_info", "tmac_hip_qgemm_experts_dev", "tmac_hip_debug_experts_plan"} if os.environ.get("TMAC_HIP_LIB") else set()
     for name, (argt, rest) in sigs.items():
         try:
             fn = getattr(L, name)

@@ -1,0 +1,174 @@
+// tmac_experts.cpp — expert banks (tmac_hip_bank_*) and the entry point of a mixture-of-experts layer's top-k GEMVs
+// (tmac_hip_qgemm_experts_dev): check the call, build the half-table image of its activation rows into the stream's library workspace
+// with the existing builder, then ONE k_gemv_experts launch (tmac_experts.hip) that picks every slot's matrix on the device.  Nothing
+// here reads ids or gates.  DESIGN.md 4.17.
+#include "tmac_host.h"
+#include "tmac_select.h"
+
+using namespace tmac_host;
+
+// E interchangeable matrices of one projection.  `experts`: the handles as given (the caller keeps them registered while the bank lives:
+// a handle has no reference count of its own; ExpertBank of the Python layer holds its Weights objects); `tab`: the device table.
+struct tmac_hip_bank {
+    std::vector<const tmac_hip_weights*> experts;
+    ExpertEntry* tab = nullptr;
+    Shape s;                       // of expert 0: every expert has the same
+    Dtype sc_dtype = F32;
+};
+
+// what of expert i differs from expert 0 (null: nothing a launch depends on)
+static const char* bank_mismatch(const tmac_hip_weights* w, const tmac_hip_weights* w0) {
+    const Shape &a = w->s, &b = w0->s;
+    if (a.Mw != b.Mw) return "Mw";
+    if (a.K != b.K) return "K";
+    if (a.bits != b.bits) return "bits";
+    if (a.gs != b.gs || a.ags != b.ags) return "group size";
+    if (a.zero_point != b.zero_point) return "zero-point setting";
+    if (w->sc_dtype != w0->sc_dtype) return "scale dtype";
+    return nullptr;
+}
+
+extern "C" int32_t tmac_hip_bank_create(tmac_hip_bank** out, const tmac_hip_weights* const* experts, int E, void* stream) {
+    if (!out || !experts) return fail(TMAC_HIP_E_ARG, "null argument");
+    if (E < 1) return fail(TMAC_HIP_E_ARG, "a bank holds at least one expert (E=%d)", E);
+    int32_t rc = ensure_device();
+    if (rc) return rc;
+    for (int i = 0; i < E; ++i) {
+        const tmac_hip_weights* w = experts[i];
+        if (!w) return fail(TMAC_HIP_E_ARG, "expert %d: null handle", i);
+        if (w->s.m_groups >= 1) return fail(TMAC_HIP_E_NOMATCH, "expert %d: unified-scale (BitNet) handles are not served in a bank", i);
+        if (quad_mfma_misses(w) & (QM_LAYOUT | QM_FAST_AGG | QM_SHAPE))
+            return fail(TMAC_HIP_E_NOMATCH, "expert %d: outside what k_gemv_quad's layout serves (QUAD layout, K a multiple of 64 up to 24576, Mw of 4, group sizes 64 x 2^n, exact sums)", i);
+        if (w->bias) return fail(TMAC_HIP_E_ARG, "expert %d: handles with a bias are not served in a bank", i);
+        if (w->kperm) return fail(TMAC_HIP_E_ARG, "expert %d: act-order handles (a K permutation) are not served in a bank", i);
+        if (const char* what = bank_mismatch(w, experts[0])) return fail(TMAC_HIP_E_ARG, "expert %d: %s differs from expert 0's", i, what);
+    }
+    const hipStream_t st = (hipStream_t)stream;
+    std::vector<ExpertEntry> host((size_t)E);
+    for (int i = 0; i < E; ++i) host[i] = ExpertEntry{(const uint4*)experts[i]->W, experts[i]->SC};
+    auto bank = std::make_unique<tmac_hip_bank>();
+    bank->experts.assign(experts, experts + E);
+    bank->s = experts[0]->s; bank->sc_dtype = experts[0]->sc_dtype;
+    HIP_TRY(hipMalloc((void**)&bank->tab, sizeof(ExpertEntry) * (size_t)E));
+    hipError_t e = hipMemcpyAsync(bank->tab, host.data(), sizeof(ExpertEntry) * (size_t)E, hipMemcpyHostToDevice, st);
+    if (e == hipSuccess) e = hipStreamSynchronize(st);      // `host` leaves scope; the table is complete before its first reader on any stream
+    if (e != hipSuccess) {
+        (void)hipFree(bank->tab);
+        return fail(TMAC_HIP_E_RUNTIME, "bank table upload: %s", hipGetErrorString(e));
+    }
+    *out = bank.release();
+    return TMAC_HIP_OK;
+}
+
+extern "C" int32_t tmac_hip_bank_free(tmac_hip_bank* bank) {
+    if (!bank) return TMAC_HIP_OK;
+    if (bank->tab) (void)hipFree(bank->tab);
+    delete bank;
+    return TMAC_HIP_OK;
+}
+
+extern "C" int32_t tmac_hip_bank_info(const tmac_hip_bank* bank, int* E, int* Mw, int* K, int* bits) {
+    if (!bank) return fail(TMAC_HIP_E_ARG, "null bank");
+    if (E) *E = (int)bank->experts.size();
+    if (Mw) *Mw = bank->s.Mw;
+    if (K) *K = bank->s.K;
+    if (bits) *bits = bank->s.bits;
+    return TMAC_HIP_OK;
+}
+
+extern "C" int32_t tmac_hip_debug_experts_plan(int K, int bits, int group_size, const int* bank_Mw, int nbanks, int S, int lut_rows, int combine,
+                                               int32_t* wpq, int32_t* grid, int32_t* items, size_t* lds_bytes) {
+    if (!bank_Mw) return fail(TMAC_HIP_E_ARG, "null argument");
+    Shape s{};
+    s.K = K; s.bits = bits; s.gs = group_size; s.ags = 64; s.m_groups = -1; s.zero_point = 1;
+    set_layout(s, L_QUAD);
+    ExpertsPlan p;
+    if (!experts_plan(s, bank_Mw, nbanks, S, lut_rows, combine ? EXPERTS_COMBINE : EXPERTS_SLOTS, p)) return fail(TMAC_HIP_E_NOMATCH, "experts call: %s", p.why);
+    if (wpq) *wpq = p.wpq;
+    if (grid) *grid = p.gx;
+    if (items) *items = p.items;
+    if (lds_bytes) *lds_bytes = p.lds_bytes;
+    return TMAC_HIP_OK;
+}
+
+hipError_t tmac::launch_gemv_experts(const ExpertsArgs& a_in, hipStream_t st) {
+    ExpertsArgs a = a_in;
+    const Shape& s = a.s;
+    const int mode = a.gates ? EXPERTS_COMBINE : EXPERTS_SLOTS;
+    int Mw[EXPERTS_MAX_BANKS] = {0, 0};
+    if (a.nbanks < 1 || a.nbanks > EXPERTS_MAX_BANKS) return hipErrorInvalidValue;
+    for (int b = 0; b < a.nbanks; ++b) Mw[b] = a.b[b].Mw;
+    ExpertsPlan p;
+    if (!experts_plan(s, Mw, a.nbanks, a.S, a.lut_rows, mode, p)) return hipErrorInvalidValue;
+    a.nu = s.K / 32; a.nst = (a.nu + 63) / 64; a.tstride = ((a.nu + 15) & ~15) + 1;
+    a.G = s.K / s.ags; a.nsg = s.K / s.gs;
+    a.gs_shift = 0;
+    for (int g = s.gs / 32; g > 1; g >>= 1) ++a.gs_shift;
+    int q = 0;
+    for (int b = 0; b < a.nbanks; ++b) {
+        // fragment offsets are 32-bit buffer offsets
+        if ((size_t)(Mw[b] / 4) * a.nst * s.bits * 1024 >= ((size_t)1 << 31)) return hipErrorInvalidValue;
+        q += Mw[b] / 4;
+        a.b[b].q_end = q;
+    }
+    a.wpq = p.wpq;
+    return sel_int<1, 2, 3, 4>(s.bits, [&](auto BITS) { return launch_gemv_experts_unit<decltype(BITS)::value>(a, p, mode, st); });
+}
+
+extern "C" int32_t tmac_hip_qgemm_experts_dev(const tmac_hip_bank* const* banks, int nbanks, const void* B_dev, tmac_dtype_t act_dtype, int lut_rows,
+                                              const int32_t* ids_dev, const float* gates_dev, int S, void* const* C_dev, tmac_dtype_t out_dtype,
+                                              void* stream) {
+    bind_thread_device();
+    // every check before anything is launched or flushed: a refused call launches nothing and leaves the deferred queue as it is
+    if (!banks || !C_dev || nbanks < 1 || nbanks > EXPERTS_MAX_BANKS) return fail(TMAC_HIP_E_ARG, "tmac_hip_qgemm_experts_dev takes one or two banks (nbanks=%d)", nbanks);
+    for (int b = 0; b < nbanks; ++b)
+        if (!banks[b] || !C_dev[b]) return fail(TMAC_HIP_E_ARG, "null bank or output");
+    if (!B_dev || !ids_dev) return fail(TMAC_HIP_E_ARG, "null activations or ids");
+    if (chain_recording()) return fail(TMAC_HIP_E_ARG, "tmac_hip_qgemm_experts_dev cannot be recorded (tmac_hip_chain_begin ... _end): expert calls run stand-alone");
+    if (S < 1 || S > EXPERTS_MAX_SLOTS) return fail(TMAC_HIP_E_ARG, "S=%d: an experts call takes 1 to %d slots", S, EXPERTS_MAX_SLOTS);
+    if (lut_rows != 1 && lut_rows != S) return fail(TMAC_HIP_E_ARG, "lut_rows=%d: 1 (one activation row shared by the slots) or S=%d", lut_rows, S);
+    const bool combine = gates_dev != nullptr;
+    if (combine && nbanks != 1) return fail(TMAC_HIP_E_ARG, "COMBINE (gates given) takes one bank, the call has %d", nbanks);
+    if (combine && lut_rows != S) return fail(TMAC_HIP_E_ARG, "COMBINE (gates given) takes one activation row per slot: lut_rows=%d, S=%d", lut_rows, S);
+    for (int b = 0; b < nbanks; ++b)
+        if (misaligned(C_dev[b], out_align(out_dtype)))
+            return fail(TMAC_HIP_E_ARG, "C_dev[%d] must be %zu-byte aligned (four outputs are stored at a time)", b, out_align(out_dtype));
+    if (misaligned(B_dev, ACT_ALIGN)) return fail(TMAC_HIP_E_ARG, "B_dev must be %zu-byte aligned (the LUT build reads 16 bytes at a time)", ACT_ALIGN);
+    if (misaligned(ids_dev, 4) || misaligned(gates_dev, 4)) return fail(TMAC_HIP_E_ARG, "ids_dev and gates_dev must be 4-byte aligned");
+    const tmac_hip_bank* b0 = banks[0];
+    const Shape& s0 = b0->s;
+    if (nbanks == 2) {
+        const Shape& s1 = banks[1]->s;
+        if (s1.K != s0.K || s1.bits != s0.bits || s1.gs != s0.gs || s1.ags != s0.ags || s1.zero_point != s0.zero_point || banks[1]->sc_dtype != b0->sc_dtype)
+            return fail(TMAC_HIP_E_ARG, "banks of one call share K, bits, group size, zero-point setting and scale dtype (their rows may differ)");
+    }
+    ExpertsArgs a;
+    memset(&a, 0, sizeof(a));
+    int Mw[EXPERTS_MAX_BANKS] = {0, 0};
+    for (int b = 0; b < nbanks; ++b) {
+        Mw[b] = banks[b]->s.Mw;
+        a.b[b].tab = banks[b]->tab; a.b[b].C = C_dev[b]; a.b[b].E = (int)banks[b]->experts.size(); a.b[b].Mw = Mw[b];
+    }
+    ExpertsPlan p;
+    if (!experts_plan(s0, Mw, nbanks, S, lut_rows, combine ? EXPERTS_COMBINE : EXPERTS_SLOTS, p))
+        return fail(TMAC_HIP_E_NOMATCH, "experts call (K=%d, S=%d, lut_rows=%d): %s", s0.K, S, lut_rows, p.why);
+    int32_t rc = defer_barrier();             // never queued: behind the calling thread's queue (B_dev, ids_dev may be a queued call's output)
+    if (rc) return rc;
+    // the half-table image of the call's rows, by the builder k_gemv_rows is fed by
+    const hipStream_t st = (hipStream_t)stream;
+    tmac_hip_workspace* ws = nullptr;
+    if ((rc = stream_workspace(st, s0.K, lut_rows, &ws)) != TMAC_HIP_OK) return rc;
+    LutBuildReq q;
+    q.K = s0.K; q.N = lut_rows; q.ags = s0.ags; q.want = LB_HALF_TABLES;
+    LutBuildPlan lb;
+    if ((rc = lut_build_plan(q, lut_caps(ws), &lb)) != TMAC_HIP_OK) return rc;
+    if ((rc = lut_build(ws, lb, B_dev, act_dtype, nullptr, nullptr, st)) != TMAC_HIP_OK) return rc;
+    a.nbanks = nbanks; a.s = s0;
+    a.ids = ids_dev; a.gates = gates_dev; a.S = S; a.lut_rows = lut_rows;
+    a.qlut_lds = ws->qlut_lds; a.lut_scales = ws->lut_scales; a.lut_biases = ws->lut_biases;
+    a.sc_f16 = b0->sc_dtype == F16; a.out_f16 = out_dtype == TMAC_F16;
+    const hipError_t e = launch_gemv_experts(a, st);
+    if (e == hipErrorInvalidValue) return fail(TMAC_HIP_E_NOMATCH, "experts kernel: configuration or sizes not covered (an expert's matrix must stay below 2 GB)");
+    if (e != hipSuccess) return fail(TMAC_HIP_E_RUNTIME, "experts kernel launch: %s", hipGetErrorString(e));
+    return TMAC_HIP_OK;
+}

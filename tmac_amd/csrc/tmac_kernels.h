@@ -291,6 +291,37 @@ hipError_t launch_gemv_rows(const RowsArgs& a, hipStream_t st, int* launches);
 // the launcher of one translation unit of tmac_rows.hip (defined and instantiated there for its BITS): one planned launch
 template <int BITS>
 hipError_t launch_gemv_rows_unit(const RowsArgs& a, const RowsLaunch& l, hipStream_t st);
+// experts kernel (tmac_experts.hip): top-k expert GEMVs on QUAD-layout weights, the expert of a slot picked on the device
+struct ExpertEntry {         // one expert of a bank's device table: what a wave needs to reach it, in one 16-byte load
+    const uint4* W;          // QUAD layout weights
+    const void* SC;          // QUAD layout scales
+};
+struct ExpertsBank {
+    const ExpertEntry* tab;  // device, [E]
+    void* C;                 // SLOTS: [S][Mw] | COMBINE: [Mw]
+    int E, Mw;
+    int q_end;               // cumulative ROW QUAD count up to and including this bank (filled by the launcher)
+};
+struct ExpertsArgs {
+    ExpertsBank b[EXPERTS_MAX_BANKS];
+    int nbanks;
+    Shape s;                 // K, bits, gs, ags = 64, zero_point of every expert (Mw unused)
+    const int32_t* ids;      // device, [S]: the expert of each slot; outside [0, E): the slot is empty
+    const float* gates;      // device, [S] (COMBINE) or null (SLOTS)
+    int S, lut_rows;         // slots; activation rows in the image: 1 (shared by the slots) or S
+    const void* qlut_lds;    // uint4 [lut_rows][qlut_lds_u4(K)]: the half-table image of the pair build
+    const float* lut_scales; // fp32 [lut_rows][K/64]
+    const float* lut_biases;
+    int sc_f16, out_f16;
+    // filled by the launcher
+    int nu, nst, tstride, G, nsg, gs_shift;   // tstride: of the IMAGE (the LDS copy uses nst * 64 + 1)
+    int wpq;
+};
+// plans the call (experts_plan), fills the derived fields, launches; hipErrorInvalidValue: the plan refuses, or a bank's matrices pass 2 GB
+hipError_t launch_gemv_experts(const ExpertsArgs& a, hipStream_t st);
+// the launcher of one translation unit of tmac_experts.hip (defined and instantiated there for its BITS)
+template <int BITS>
+hipError_t launch_gemv_experts_unit(const ExpertsArgs& a, const ExpertsPlan& p, int mode, hipStream_t st);
 // returns hipErrorInvalidValue when the variant does not cover the configuration
 hipError_t launch_gemv(const GemvArgs& a, Variant v, hipStream_t st);
 bool gemv_lo_supported(const Shape& s);

@@ -182,4 +182,42 @@ bool rows_launch_plan(const Shape& s, int N, int total_q, RowsLaunchPlan& p) {
     return true;
 }
 
+size_t experts_lds_bytes(int K, int rows) {
+    const int nst = (K / 32 + 63) / 64;
+    return (size_t)rows * ((size_t)4 * (nst * 64 + 1) * 16 + sizeof(float) * 2 * nst * 32) + sizeof(float) * 2 * EXPERTS_NWV * 4;
+}
+
+bool experts_plan(const Shape& s, const int* bank_Mw, int nbanks, int S, int lut_rows, int mode, ExpertsPlan& p) {
+    p = ExpertsPlan{false, nullptr, 0, 0, 0, 0};
+    auto refuse = [&](const char* why) { p.why = why; return false; };
+    if (nbanks < 1 || nbanks > EXPERTS_MAX_BANKS) return refuse("one or two banks per call");
+    if (S < 1 || S > EXPERTS_MAX_SLOTS) return refuse("1 to 8 slots per call");
+    if (lut_rows != 1 && lut_rows != S) return refuse("lut_rows is 1 (one activation row shared by the slots) or S (one per slot)");
+    if (mode != EXPERTS_SLOTS && mode != EXPERTS_COMBINE) return refuse("mode is SLOTS or COMBINE");
+    if (mode == EXPERTS_COMBINE && nbanks != 1) return refuse("COMBINE takes one bank");
+    if (mode == EXPERTS_COMBINE && lut_rows != S) return refuse("COMBINE takes one activation row per slot (lut_rows = S)");
+    int total_q = 0;
+    for (int b = 0; b < nbanks; ++b) {
+        Shape sb = s;
+        sb.Mw = bank_Mw[b];
+        if (!gemv_quad_supported(sb)) return refuse("a bank's matrices are outside what k_gemv_quad's layout serves");
+        total_q += sb.Mw / 4;
+    }
+    if (!experts_inst_exists(s.bits, s.m_groups >= 1 ? 2 : 0, mode)) return refuse("unified-scale banks are not served");
+    p.lds_bytes = experts_lds_bytes(s.K, lut_rows);
+    if (p.lds_bytes > ROWS_LDS_MAX) return refuse("the tables of the call's activation rows do not fit LDS (fewer slots, or a smaller K)");
+    const int nst = (s.K / 32 + 63) / 64;
+    // waves per quad as rows_launch_plan chooses them, from the banks' quads: a slot's bits must not depend on S, on the mode or on
+    // whether x is shared
+    p.wpq = 1;
+    while (p.wpq < 4 && p.wpq * 2 <= nst && (total_q * p.wpq + EXPERTS_NWV - 1) / EXPERTS_NWV < 256) p.wpq *= 2;
+    const int ipi = EXPERTS_NWV / p.wpq;
+    p.items = mode == EXPERTS_COMBINE ? total_q : S * total_q;
+    const int need = (p.items + ipi - 1) / ipi;
+    const int occ = p.lds_bytes * 2 <= ROWS_LDS_MAX ? 2 : 1;      // persistent: at most two workgroups per CU
+    p.gx = need < 256 * occ ? need : 256 * occ;
+    p.served = true;
+    return true;
+}
+
 }  // namespace tmac

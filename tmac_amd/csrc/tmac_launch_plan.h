@@ -106,6 +106,29 @@ struct RowsLaunch { int R, n_base, gx, gy; size_t lds_bytes; };
 struct RowsLaunchPlan { RowsPlan rows; int wpq; int nlaunch; RowsLaunch l[2]; };
 bool rows_launch_plan(const Shape& s, int N, int total_q, RowsLaunchPlan& p);
 
+// ---- k_gemv_experts<BITS, ZP, SCF16, MODE> (tmac_experts.hip) -----------------------------------------------------------------------
+// Top-k expert GEMVs with the expert ids read on the device: S slots, up to two banks of interchangeable matrices that share the ids.
+constexpr int EXPERTS_FT = 512, EXPERTS_NWV = EXPERTS_FT / 64, EXPERTS_MAX_SLOTS = 8, EXPERTS_MAX_BANKS = 2;
+enum ExpertsMode { EXPERTS_SLOTS = 0, EXPERTS_COMBINE = 1 };      // one output row per slot and bank | sum_s g[s] (W[ids[s]] x_s), one bank
+// every width, zero-point setting and scale dtype in both modes; per-group scales alone (sm: 0 per-group, 2 unified)
+constexpr bool experts_inst_exists(int bits, int sm, int mode) {
+    return bits >= 1 && bits <= 4 && sm == 0 && (mode == EXPERTS_SLOTS || mode == EXPERTS_COMBINE);
+}
+// LDS of a workgroup that holds `rows` activation rows: per row what rows_lds_bytes counts per row, then the partials of the eight waves
+// [2 parities][8][4 rows]
+size_t experts_lds_bytes(int K, int rows);
+struct ExpertsPlan {
+    bool served;             // false: refused, `why` names the cause
+    const char* why;
+    int wpq;                 // waves per row quad (1, 2, 4): by K and the banks' row counts alone, never by S, lut_rows or the mode
+    int gx;                  // persistent eight-wave workgroups
+    int items;               // work items of the launch: (bank, slot, row quad) | COMBINE: row quads (a wave walks the slots of its quad)
+    size_t lds_bytes;
+};
+// s: the banks' common shape (Mw unused); bank_Mw: rows of each bank's matrices; lut_rows: 1 (one x shared by the slots) or S.
+// Pure.  Returns p.served.
+bool experts_plan(const Shape& s, const int* bank_Mw, int nbanks, int S, int lut_rows, int mode, ExpertsPlan& p);
+
 // ---- k_decode_chain<BITS, ZP, SCF16, SM, XF, TAP, G2, GT> ---------------------------------------------------------------------------
 // The tap's instance carries the transforms too, and a gate other than silu belongs to a transform: TAP and GT imply XF.  Unified scales
 // (SM 2) have one scale per matrix: no G2 instance (two scale groups per lane and item), and no zero points.

@@ -574,6 +574,40 @@ class Weights:
             pass
 
 
+class ExpertBank:
+    """E registered matrices of one projection of a mixture-of-experts layer (all ``gate``, all ``up`` or all ``down`` experts) that a
+    launch picks among on the GPU (tmac_hip_bank_create).  The bank keeps its :class:`Weights` objects alive."""
+
+    @classmethod
+    def from_handles(cls, experts, stream=None) -> "ExpertBank":
+        """``experts``: Weights of equal Mw, K, bits, group size, zero-point setting and scale dtype, per-group scales, no bias, no
+        act-order permutation; expert e of a call's ids is ``experts[e]``.  Anything else raises TMACHipError naming the expert."""
+        self = cls.__new__(cls)
+        self.experts = list(experts)
+        self._h = C.c_void_p()
+        arr = (C.c_void_p * max(len(self.experts), 1))(*[w.handle.value for w in self.experts])
+        check(B.lib().tmac_hip_bank_create(C.byref(self._h), arr, len(self.experts), _stream(stream)))
+        w0 = self.experts[0]
+        self.E, self.Mw, self.K, self.bits = len(self.experts), w0.Mw, w0.K, w0.bits
+        return self
+
+    @property
+    def handle(self):
+        return self._h
+
+    def free(self):
+        if getattr(self, "_h", None):
+            B.lib().tmac_hip_bank_free(self._h)
+            self._h = C.c_void_p()
+        self.experts = []
+
+    def __del__(self):
+        try:
+            self.free()
+        except Exception:
+            pass
+
+
 class Workspace:
     """QLUT / LUT_Scales / LUT_Biases on the device (TMACGeMMWrapper::set_workspace)."""
 
@@ -937,6 +971,32 @@ class TMACGeMMWrapper:
         if rec is not None:
             rec.append((list(weights_list), B_dev, list(C_list)))
         check(B.lib().tmac_hip_qgemm_fused_dev(wa, n, _ptr(B_dev), act_dtype, ca, out_dtype, N, _stream(stream)))
+
+    def experts(self, banks, x, ids, gates=None, out=None, stream=None):
+        """The top-k expert GEMVs of one token, the experts picked on the GPU (tmac_hip_qgemm_experts_dev).  ``banks``: one or two
+        :class:`ExpertBank` that share ``ids`` (gate / up); ``ids``: CUDA int32 [S], S <= 8, an id outside [0, E) (``-1``) marks an empty
+        slot; ``x``: CUDA fp16 / fp32, [K] or [1, K] -- every slot reads it -- or [S, K] -- slot s reads row s.
+        ``gates=None``: returns one [S, Mw] tensor per bank, row s = W[ids[s]] x_row(s) (an empty slot's row is zero).
+        ``gates`` (CUDA fp32 [S]; one bank, x [S, K]): returns [Mw] = sum_s gates[s] (W[ids[s]] x_s), the ``down`` projection with the
+        router-weighted sum.  ``out``: the tensor(s) to write instead of new fp32 ones (fp16 or fp32).  Nothing is copied to the host."""
+        import torch
+        banks = list(banks) if isinstance(banks, (list, tuple)) else [banks]
+        S = int(ids.numel())
+        if ids.dtype != torch.int32 or not ids.is_cuda:
+            raise TypeError("ids must be a CUDA int32 tensor")
+        if gates is not None and (gates.dtype != torch.float32 or not gates.is_cuda or int(gates.numel()) != S):
+            raise TypeError("gates must be a CUDA float32 tensor with one value per slot")
+        lut_rows = 1 if x.dim() == 1 else int(x.shape[0])
+        if out is None:
+            out = [torch.empty((b.Mw,) if gates is not None else (S, b.Mw), dtype=torch.float32, device=x.device) for b in banks]
+        outs = list(out) if isinstance(out, (list, tuple)) else [out]
+        if len(outs) != len(banks):
+            raise ValueError("one output per bank")
+        ba = (C.c_void_p * len(banks))(*[b.handle.value for b in banks])
+        ca = (C.c_void_p * len(banks))(*[_ptr(c) for c in outs])
+        check(B.lib().tmac_hip_qgemm_experts_dev(ba, len(banks), _ptr(x), _dtype_code(x), lut_rows, _ptr(ids), _ptr(gates), S, ca,
+                                                 _dtype_code(outs[0]), _stream(stream)))
+        return outs[0] if gates is not None else outs
 
     def record_gather(self, send_dev, recv_dev, bytes_per_rank: int, rank: int, world: int) -> None:
         """while recording a chain: the exchange step ``recv = all-gather over the ranks of send`` (what ``Comm.allgather`` records
