@@ -455,6 +455,35 @@ int32_t tmac_hip_qgemm_experts_dev(const tmac_hip_bank* const* banks, int nbanks
 int32_t tmac_hip_debug_experts_plan(int K, int bits, int group_size, const int* bank_Mw, int nbanks, int S, int lut_rows, int combine,
                                     int32_t* waves_per_quad, int32_t* grid, int32_t* items, size_t* lds_bytes);
 
+/* ---- expert banks for token batches: routing and gated sum --------------------------------------------------------------------------
+ * N > 1 tokens of a mixture-of-experts layer, S slots each: ids_dev int32 [N][S], token-major, device.  The FLAT SLOT of (n, s) is
+ * f = n S + s; an id outside [0, E) marks it empty, as above.  Neither call reads ids, the routing or gates on
+ * the host, and every grid depends on the call's shape alone: they are capturable into a hipGraph and replays follow ids rewritten on
+ * the device.  The routing orders the rows of a grouped GEMM (one expert per tile of 64 rows, P rows in all); the gated sum folds its
+ * fp32 output C [P][Mw] back into one row per token.  Each call runs behind the calling thread's deferred queue and is refused inside a recording (TMAC_HIP_E_ARG).
+ *
+ * tmac_hip_experts_rows_sizes: T_max = floor(N S / 64) + min(E, N S) tiles of 64 POSITIONS, P = 64 T_max positions -- a bound on
+ * sum_e ceil(c_e / 64) for any ids (c_e: slots of expert e).  Limits, refused by name with TMAC_HIP_E_ARG: 1 <= S <= 8, N S <= 32768,
+ * 1 <= E <= 256.
+ *
+ * tmac_hip_experts_route_dev (k_experts_route): a stable counting sort of the flat slots by expert into positions.  Experts in increasing
+ * id; every expert's segment starts on a multiple of 64 positions; inside a segment increasing f.  A pure function of ids (no global
+ * atomic decides an order).  Outputs, int32, device, caller-allocated, 4-byte aligned, every element written:
+ *   tile_expert[T_max]  the expert that owns the 64 positions of tile t, or -1 for a tile past the last one in use
+ *   src[P]              the flat slot at position i, or -1 for a padding position (behind an expert's last slot, and in unused tiles)
+ *   pos[N S]            the position of flat slot f, or -1 for an empty slot
+ *
+ * tmac_hip_experts_combine_dev (k_experts_combine): y_dev [N][Mw] = sum_s gates_dev[n][s] * C_dev[pos_dev[n S + s]][:] over fp32
+ * C_dev [P][Mw], in slot order from acc = 0 as acc = rn(acc + rn(g c)) (no contraction); an empty slot (pos outside [0, P)) adds nothing.
+ * fp32 or fp16 output, no atomics.  Mw a multiple of 4; C_dev 16-byte aligned, y_dev 16-byte (fp32) / 8-byte (fp16).
+ * Open: the grouped GEMM between the two (k_gemm_planes instantiations that pick the expert of a tile on the device), a 32-position tile for layers with few tokens per expert, unified-scale banks, a fused router, ggml mul_mat_id glue, the
+ * persistent and deferred paths. */
+int32_t tmac_hip_experts_rows_sizes(int N, int S, int E, int32_t* T_max, int32_t* P);
+int32_t tmac_hip_experts_route_dev(const int32_t* ids_dev, int N, int S, int E, int32_t* tile_expert_dev, int32_t* src_dev, int32_t* pos_dev,
+                                   void* stream);
+int32_t tmac_hip_experts_combine_dev(const float* C_dev, const int32_t* pos_dev, const float* gates_dev, int N, int S, int Mw, int P, void* y_dev,
+                                     tmac_dtype_t out_dtype, void* stream);
+
 /* ---- deferred launches ---------------------------------------------------------------------
  * For callers that do not record (a backend hook called mat-mul by mat-mul).  tmac_hip_defer(1): from now on the calling thread's N = 1
  * tmac_hip_qgemm_fused_dev calls are QUEUED instead of launched; tmac_hip_flush launches what is queued as ONE stream-mode launch

@@ -91,6 +91,49 @@ extern "C" int32_t tmac_hip_debug_experts_plan(int K, int bits, int group_size, 
     return TMAC_HIP_OK;
 }
 
+// ---- token batches: routing and gated sum.  Nothing here reads ids, the routing or gates. ------------------------------
+extern "C" int32_t tmac_hip_experts_rows_sizes(int N, int S, int E, int32_t* T_max, int32_t* P) {
+    ExpertsRowsSizes z;
+    if (!experts_rows_sizes(N, S, E, z)) return fail(TMAC_HIP_E_ARG, "experts routing (N=%d, S=%d, E=%d): %s", N, S, E, z.why);
+    if (T_max) *T_max = z.T_max;
+    if (P) *P = z.P;
+    return TMAC_HIP_OK;
+}
+
+extern "C" int32_t tmac_hip_experts_route_dev(const int32_t* ids_dev, int N, int S, int E, int32_t* tile_expert_dev, int32_t* src_dev, int32_t* pos_dev,
+                                              void* stream) {
+    bind_thread_device();
+    if (!ids_dev || !tile_expert_dev || !src_dev || !pos_dev) return fail(TMAC_HIP_E_ARG, "null ids or routing output");
+    ExpertsRowsSizes z;
+    if (!experts_rows_sizes(N, S, E, z)) return fail(TMAC_HIP_E_ARG, "experts routing (N=%d, S=%d, E=%d): %s", N, S, E, z.why);
+    if (chain_recording()) return fail(TMAC_HIP_E_ARG, "tmac_hip_experts_route_dev cannot be recorded (tmac_hip_chain_begin ... _end): expert calls run stand-alone");
+    if (misaligned(ids_dev, 4) || misaligned(tile_expert_dev, 4) || misaligned(src_dev, 4) || misaligned(pos_dev, 4))
+        return fail(TMAC_HIP_E_ARG, "ids_dev and the routing outputs must be 4-byte aligned");
+    const int32_t rc = defer_barrier();
+    if (rc) return rc;
+    const hipError_t e = launch_experts_route(ids_dev, N * S, E, z.T_max, tile_expert_dev, src_dev, pos_dev, (hipStream_t)stream);
+    if (e != hipSuccess) return fail(TMAC_HIP_E_RUNTIME, "experts routing launch: %s", hipGetErrorString(e));
+    return TMAC_HIP_OK;
+}
+
+extern "C" int32_t tmac_hip_experts_combine_dev(const float* C_dev, const int32_t* pos_dev, const float* gates_dev, int N, int S, int Mw, int P, void* y_dev,
+                                                tmac_dtype_t out_dtype, void* stream) {
+    bind_thread_device();
+    if (!C_dev || !pos_dev || !gates_dev || !y_dev) return fail(TMAC_HIP_E_ARG, "null argument");
+    ExpertsRowsSizes z;
+    if (!experts_rows_sizes(N, S, 1, z)) return fail(TMAC_HIP_E_ARG, "experts combine (N=%d, S=%d): %s", N, S, z.why);
+    if (Mw < 4 || Mw % 4 != 0 || P < 64 || P % 64 != 0) return fail(TMAC_HIP_E_ARG, "experts combine: Mw=%d must be a multiple of 4, P=%d of 64", Mw, P);
+    if (chain_recording()) return fail(TMAC_HIP_E_ARG, "tmac_hip_experts_combine_dev cannot be recorded (tmac_hip_chain_begin ... _end): expert calls run stand-alone");
+    if (misaligned(C_dev, 16) || misaligned(y_dev, out_align(out_dtype)))
+        return fail(TMAC_HIP_E_ARG, "C_dev must be 16-byte and y_dev %zu-byte aligned (four values are loaded and stored at a time)", out_align(out_dtype));
+    if (misaligned(pos_dev, 4) || misaligned(gates_dev, 4)) return fail(TMAC_HIP_E_ARG, "pos_dev and gates_dev must be 4-byte aligned");
+    const int32_t rc = defer_barrier();
+    if (rc) return rc;
+    const hipError_t e = launch_experts_combine(C_dev, pos_dev, gates_dev, N, S, Mw, P, y_dev, out_dtype == TMAC_F16, (hipStream_t)stream);
+    if (e != hipSuccess) return fail(TMAC_HIP_E_RUNTIME, "experts combine launch: %s", hipGetErrorString(e));
+    return TMAC_HIP_OK;
+}
+
 hipError_t tmac::launch_gemv_experts(const ExpertsArgs& a_in, hipStream_t st) {
     ExpertsArgs a = a_in;
     const Shape& s = a.s;

@@ -322,6 +322,14 @@ hipError_t launch_gemv_experts(const ExpertsArgs& a, hipStream_t st);
 // the launcher of one translation unit of tmac_experts.hip (defined and instantiated there for its BITS)
 template <int BITS>
 hipError_t launch_gemv_experts_unit(const ExpertsArgs& a, const ExpertsPlan& p, int mode, hipStream_t st);
+// Expert banks for token batches (tmac_experts_rows.hip).  A POSITION is a row of a grouped GEMM: the (token, slot)
+// pairs sorted by expert, every expert's segment padded to whole tiles of 64.
+// k_experts_route: ids [N][S] -> tile_expert [T_max], src [64 T_max], pos [N S] (stable counting sort by expert, segments padded to 64;
+// the order and the -1 values: include/tmac_hip.h).  One workgroup; N S <= EXPERTS_ROWS_MAX_NS, E <= EXPERTS_ROWS_MAX_E.
+hipError_t launch_experts_route(const int32_t* ids, int NS, int E, int T_max, int32_t* tile_expert, int32_t* src, int32_t* pos, hipStream_t st);
+// k_experts_combine: y [N][Mw] = sum_s gates[n][s] * C[pos[n S + s]][:] over fp32 C, slot order, two roundings per slot; a pos outside
+// [0, P) adds nothing
+hipError_t launch_experts_combine(const float* C, const int32_t* pos, const float* gates, int N, int S, int Mw, int P, void* y, int out_f16, hipStream_t st);
 // returns hipErrorInvalidValue when the variant does not cover the configuration
 hipError_t launch_gemv(const GemvArgs& a, Variant v, hipStream_t st);
 bool gemv_lo_supported(const Shape& s);

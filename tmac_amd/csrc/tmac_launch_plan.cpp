@@ -220,4 +220,17 @@ bool experts_plan(const Shape& s, const int* bank_Mw, int nbanks, int S, int lut
     return true;
 }
 
+bool experts_rows_sizes(long long N, long long S, long long E, ExpertsRowsSizes& z) {
+    z = ExpertsRowsSizes{nullptr, 0, 0};
+    if (N < 1) z.why = "N: at least one token";
+    else if (S < 1 || S > EXPERTS_MAX_SLOTS) z.why = "S: 1 to 8 slots per token";
+    else if (E < 1 || E > EXPERTS_ROWS_MAX_E) z.why = "E: the routing kernel takes 1 to 256 experts";
+    else if (N * S > EXPERTS_ROWS_MAX_NS) z.why = "N x S: the routing kernel takes at most 32768 slots";
+    if (z.why) return false;
+    const long long ns = N * S;
+    z.T_max = (int)(ns / 64 + (E < ns ? E : ns));
+    z.P = 64 * z.T_max;
+    return true;
+}
+
 }  // namespace tmac

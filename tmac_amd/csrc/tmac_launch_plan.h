@@ -129,6 +129,18 @@ struct ExpertsPlan {
 // Pure.  Returns p.served.
 bool experts_plan(const Shape& s, const int* bank_Mw, int nbanks, int S, int lut_rows, int mode, ExpertsPlan& p);
 
+// ---- expert banks for token batches: k_experts_route, k_experts_combine (tmac_experts_rows.hip) -----------------------------------------
+// N tokens x S slots are sorted by expert into POSITIONS, every expert's segment padded to whole tiles of 64 positions.  Tiles needed:
+// sum_e ceil(c_e / 64) <= floor(sum_e c_e / 64) + #non-empty experts <= T_max below, which depends on the call's shape alone: the grids of
+// the launches behind the routing are fixed before any id is known.
+constexpr int EXPERTS_ROWS_MAX_NS = 32768, EXPERTS_ROWS_MAX_E = 256;
+struct ExpertsRowsSizes {
+    const char* why;         // null: served
+    int T_max, P;            // tiles of 64 positions; positions = 64 T_max
+};
+// Pure.  Returns why == null.
+bool experts_rows_sizes(long long N, long long S, long long E, ExpertsRowsSizes& z);
+
 // ---- k_decode_chain<BITS, ZP, SCF16, SM, XF, TAP, G2, GT> ---------------------------------------------------------------------------
 // The tap's instance carries the transforms too, and a gate other than silu belongs to a transform: TAP and GT imply XF.  Unified scales
 // (SM 2) have one scale per matrix: no G2 instance (two scale groups per lane and item), and no zero points.

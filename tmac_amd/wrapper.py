@@ -998,6 +998,42 @@ class TMACGeMMWrapper:
                                                  _dtype_code(outs[0]), _stream(stream)))
         return outs[0] if gates is not None else outs
 
+    # ---- expert banks for N > 1 tokens: routing by expert and the gated sum over routed rows ---------------------
+    def experts_route(self, ids, E: int, out=None, stream=None):
+        """Sorts the slots of ``ids`` (CUDA int32 [N, S], S <= 8, N S <= 32768; an id outside [0, E), E <= 256, marks an empty slot) by
+        expert on the GPU (tmac_hip_experts_route_dev).  Returns ``(tile_expert [T_max], src [64 T_max], pos [N S])``, CUDA int32: the
+        expert of every tile of 64 positions (-1: unused), the flat slot ``n S + s`` at every position (-1: padding) and the position of
+        every flat slot (-1: empty).  T_max depends on (N, S, E) alone.  ``out``: three tensors of these sizes to write instead."""
+        import torch
+        if ids.dtype != torch.int32 or not ids.is_cuda or ids.dim() != 2 or not ids.is_contiguous():
+            raise TypeError("ids must be a contiguous CUDA int32 tensor [N, S]")
+        N, S = int(ids.shape[0]), int(ids.shape[1])
+        T, P = C.c_int32(), C.c_int32()
+        check(B.lib().tmac_hip_experts_rows_sizes(N, S, int(E), C.byref(T), C.byref(P)))
+        if out is None:
+            out = tuple(torch.empty(n, dtype=torch.int32, device=ids.device) for n in (T.value, P.value, N * S))
+        te, src, pos = out
+        if (int(te.numel()), int(src.numel()), int(pos.numel())) != (T.value, P.value, N * S) or any(t.dtype != torch.int32 or not t.is_cuda for t in out):
+            raise ValueError(f"routing outputs are CUDA int32 of {T.value}, {P.value} and {N * S} elements")
+        check(B.lib().tmac_hip_experts_route_dev(_ptr(ids), N, S, int(E), _ptr(te), _ptr(src), _ptr(pos), _stream(stream)))
+        return te, src, pos
+
+    def experts_combine(self, c, route, gates, out=None, stream=None):
+        """``y[n] = sum_s gates[n, s] * c[pos[n S + s]]`` over fp32 rows ``c`` [P, Mw] in the position order of ``route`` (tmac_hip_experts_combine_dev):
+        slot order from 0, a rounded multiply and a rounded add per slot, empty slots add nothing.  ``gates``: CUDA fp32 [N, S].  Returns
+        [N, Mw] (``out``: fp16 or fp32, else new fp32)."""
+        import torch
+        pos = route[2]
+        if gates.dtype != torch.float32 or not gates.is_cuda or gates.dim() != 2 or not gates.is_contiguous() or gates.numel() != pos.numel():
+            raise TypeError("gates must be a contiguous CUDA float32 tensor [N, S] with one value per routed slot")
+        if c.dtype != torch.float32 or c.dim() != 2 or not c.is_contiguous() or int(c.shape[0]) != int(route[1].numel()):
+            raise TypeError("c must be a contiguous fp32 [P, Mw] tensor with one row per position of this routing")
+        N, S, P, Mw = int(gates.shape[0]), int(gates.shape[1]), int(c.shape[0]), int(c.shape[1])
+        if out is None:
+            out = torch.empty((N, Mw), dtype=torch.float32, device=c.device)
+        check(B.lib().tmac_hip_experts_combine_dev(_ptr(c), _ptr(pos), _ptr(gates), N, S, Mw, P, _ptr(out), _dtype_code(out), _stream(stream)))
+        return out
+
     def record_gather(self, send_dev, recv_dev, bytes_per_rank: int, rank: int, world: int) -> None:
         """while recording a chain: the exchange step ``recv = all-gather over the ranks of send`` (what ``Comm.allgather`` records
         by itself); inside the launch it becomes part of the hand-off"""
