@@ -476,13 +476,30 @@ int32_t tmac_hip_debug_experts_plan(int K, int bits, int group_size, const int* 
  * tmac_hip_experts_combine_dev (k_experts_combine): y_dev [N][Mw] = sum_s gates_dev[n][s] * C_dev[pos_dev[n S + s]][:] over fp32
  * C_dev [P][Mw], in slot order from acc = 0 as acc = rn(acc + rn(g c)) (no contraction); an empty slot (pos outside [0, P)) adds nothing.
  * fp32 or fp16 output, no atomics.  Mw a multiple of 4; C_dev 16-byte aligned, y_dev 16-byte (fp32) / 8-byte (fp16).
- * Open: the grouped GEMM between the two (k_gemm_planes instantiations that pick the expert of a tile on the device), a 32-position tile for layers with few tokens per expert, unified-scale banks, a fused router, ggml mul_mat_id glue, the
+ *
+ * tmac_hip_qgemm_experts_rows_dev (k_lut_image_pos + k_gemm_experts): the grouped GEMM between the two.  For every position p of a used
+ * tile, C_dev[b][p][:] = W_b[tile_expert_dev[p / 64]] . x_row(p) over one or two banks that share the routing (gate / up in one launch;
+ * the banks share K, the quantisation config and E, their row counts may differ).  x_rows says what B_dev is: N -- token-major [N][K],
+ * x_row(p) = row src_dev[p] / S (gate, up) -- or P = 64 T_max -- position-major [P][K], x_row(p) = row p (down behind the caller's GLU);
+ * anything else is refused.  Rows of B_dev at positions with src_dev[p] < 0 are never read.  C_dev[b] is [P][Mw_b], fp32 or fp16: a
+ * padding position of a used tile gets +0.0, the rows of an unused tile are not written.  An output's bits depend on its expert and its
+ * activation row alone.  Every check comes first (alignment as above, the banks' agreement, the 2 GB limits of the position image and of
+ * an expert's matrix); then the call runs behind the deferred queue, builds the position-ordered LUT image in the stream's library
+ * workspace and launches once.  It never reads the routing on the host: capturable after the workspace's first use, and replays follow
+ * a routing rewritten on the device.  tmac_hip_debug_experts_gemm_plan: the launch plan of such a call with outputs of P positions
+ * (pure, no device), or its refusal -- P != 64 T_max of (N, S, E) among them.
+ * Open: a 32-position tile for layers with few tokens per expert, unified-scale banks, a fused router, ggml mul_mat_id glue, the
  * persistent and deferred paths. */
 int32_t tmac_hip_experts_rows_sizes(int N, int S, int E, int32_t* T_max, int32_t* P);
 int32_t tmac_hip_experts_route_dev(const int32_t* ids_dev, int N, int S, int E, int32_t* tile_expert_dev, int32_t* src_dev, int32_t* pos_dev,
                                    void* stream);
 int32_t tmac_hip_experts_combine_dev(const float* C_dev, const int32_t* pos_dev, const float* gates_dev, int N, int S, int Mw, int P, void* y_dev,
                                      tmac_dtype_t out_dtype, void* stream);
+int32_t tmac_hip_qgemm_experts_rows_dev(const tmac_hip_bank* const* banks, int nbanks, const void* B_dev, tmac_dtype_t act_dtype, int x_rows,
+                                        const int32_t* tile_expert_dev, const int32_t* src_dev, int N, int S, void* const* C_dev,
+                                        tmac_dtype_t out_dtype, void* stream);
+int32_t tmac_hip_debug_experts_gemm_plan(int K, int bits, int group_size, const int* bank_Mw, int nbanks, int N, int S, int E, int P,
+                                         int32_t* grid_x, int32_t* grid_y, size_t* lds_bytes);
 
 /* ---- deferred launches ---------------------------------------------------------------------
  * For callers that do not record (a backend hook called mat-mul by mat-mul).  tmac_hip_defer(1): from now on the calling thread's N = 1

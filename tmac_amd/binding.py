@@ -143,6 +143,10 @@ def load_library() -> C.CDLL:
         "tmac_hip_experts_rows_sizes": ([C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int32), C.POINTER(C.c_int32)], i32),
         "tmac_hip_experts_route_dev": ([vp, C.c_int, C.c_int, C.c_int, vp, vp, vp, vp], i32),
         "tmac_hip_experts_combine_dev": ([vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, vp, C.c_int, vp], i32),
+        # ... and the grouped GEMM between the two, its plan
+        "tmac_hip_qgemm_experts_rows_dev": ([C.POINTER(vp), C.c_int, vp, C.c_int, C.c_int, vp, vp, C.c_int, C.c_int, C.POINTER(vp), C.c_int, vp], i32),
+        "tmac_hip_debug_experts_gemm_plan": ([C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int), C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
+                                              C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(sz)], i32),
         "tmac_hip_qgemm_fused_xf_dev": ([C.POINTER(vp), C.c_int, vp, C.c_int, C.POINTER(XForm), C.POINTER(vp), C.c_int, vp], i32),
         "tmac_hip_qgemm_fused_xf_rows_dev": ([C.POINTER(vp), C.c_int, vp, C.c_int, C.POINTER(XForm), C.POINTER(vp), C.c_int, C.c_int, vp], i32),
         "tmac_hip_debug_xf_rows_plan": ([C.POINTER(vp), C.c_int, C.POINTER(vp), C.c_int, C.POINTER(C.c_int32), C.POINTER(C.c_int32)], i32),
@@ -224,7 +228,8 @@ def load_library() -> C.CDLL:
                 "tmac_hip_pack_awq_dev", "tmac_hip_register_weights_awq_dev",
                 "tmac_hip_debug_rows_kernel", "tmac_hip_debug_rows_stats", "tmac_hip_debug_rows_plan", "tmac_hip_debug_rows_comb_sums",
                 "tmac_hip_bank_create", "tmac_hip_bank_free", "tmac_hip_bank_info", "tmac_hip_qgemm_experts_dev", "tmac_hip_debug_experts_plan",
-                "tmac_hip_experts_rows_sizes", "tmac_hip_experts_route_dev", "tmac_hip_experts_combine_dev"} if os.environ.get("TMAC_HIP_LIB") else set()
+                "tmac_hip_experts_rows_sizes", "tmac_hip_experts_route_dev", "tmac_hip_experts_combine_dev",
+                "tmac_hip_qgemm_experts_rows_dev", "tmac_hip_debug_experts_gemm_plan"} if os.environ.get("TMAC_HIP_LIB") else set()
     for name, (argt, rest) in sigs.items():
         try:
             fn = getattr(L, name)

@@ -215,3 +215,84 @@ extern "C" int32_t tmac_hip_qgemm_experts_dev(const tmac_hip_bank* const* banks,
     if (e != hipSuccess) return fail(TMAC_HIP_E_RUNTIME, "experts kernel launch: %s", hipGetErrorString(e));
     return TMAC_HIP_OK;
 }
+
+// ---- token batches: the grouped GEMM over routed positions (k_lut_image_pos + k_gemm_experts, tmac_experts_gemm.hip) ----
+extern "C" int32_t tmac_hip_debug_experts_gemm_plan(int K, int bits, int group_size, const int* bank_Mw, int nbanks, int N, int S, int E, int P,
+                                                    int32_t* grid_x, int32_t* grid_y, size_t* lds_bytes) {
+    if (!bank_Mw) return fail(TMAC_HIP_E_ARG, "null argument");
+    Shape s{};
+    s.K = K; s.bits = bits; s.gs = group_size; s.ags = 64; s.m_groups = -1; s.zero_point = 1;
+    set_layout(s, L_QUAD);
+    ExpertsGemmPlan p;
+    if (!experts_gemm_plan(s, bank_Mw, nbanks, N, S, E, P, p)) return fail(TMAC_HIP_E_NOMATCH, "experts rows call: %s", p.why);
+    if (grid_x) *grid_x = p.gx;
+    if (grid_y) *grid_y = p.gy;
+    if (lds_bytes) *lds_bytes = p.lds_bytes;
+    return TMAC_HIP_OK;
+}
+
+hipError_t tmac::launch_gemm_experts(const ExpertsGemmArgs& a_in, const ExpertsGemmPlan& p, hipStream_t st) {
+    ExpertsGemmArgs a = a_in;
+    if (p.why || a.nbanks < 1 || a.nbanks > EXPERTS_MAX_BANKS || a.P != 64 * p.gy) return hipErrorInvalidValue;
+    for (int b = 0; b < a.nbanks; ++b) a.b[b].wg_end = p.wg_end[b];
+    a.apg_shift = 0;
+    while ((64 << a.apg_shift) < a.s.gs) ++a.apg_shift;
+    return sel_int<1, 2, 3, 4>(a.s.bits, [&](auto BITS) { return launch_gemm_experts_unit<decltype(BITS)::value>(a, p, st); });
+}
+
+extern "C" int32_t tmac_hip_qgemm_experts_rows_dev(const tmac_hip_bank* const* banks, int nbanks, const void* B_dev, tmac_dtype_t act_dtype, int x_rows,
+                                                   const int32_t* tile_expert_dev, const int32_t* src_dev, int N, int S, void* const* C_dev,
+                                                   tmac_dtype_t out_dtype, void* stream) {
+    bind_thread_device();
+    // every check before anything is launched or flushed: a refused call launches nothing and leaves the deferred queue as it is
+    if (!banks || !C_dev || nbanks < 1 || nbanks > EXPERTS_MAX_BANKS) return fail(TMAC_HIP_E_ARG, "tmac_hip_qgemm_experts_rows_dev takes one or two banks (nbanks=%d)", nbanks);
+    for (int b = 0; b < nbanks; ++b)
+        if (!banks[b] || !C_dev[b]) return fail(TMAC_HIP_E_ARG, "null bank or output");
+    if (!B_dev || !tile_expert_dev || !src_dev) return fail(TMAC_HIP_E_ARG, "null activations or routing");
+    if (chain_recording()) return fail(TMAC_HIP_E_ARG, "tmac_hip_qgemm_experts_rows_dev cannot be recorded (tmac_hip_chain_begin ... _end): expert calls run stand-alone");
+    const tmac_hip_bank* b0 = banks[0];
+    const Shape& s0 = b0->s;
+    const int E = (int)b0->experts.size();
+    if (nbanks == 2) {
+        const Shape& s1 = banks[1]->s;
+        if (s1.K != s0.K || s1.bits != s0.bits || s1.gs != s0.gs || s1.ags != s0.ags || s1.zero_point != s0.zero_point || banks[1]->sc_dtype != b0->sc_dtype)
+            return fail(TMAC_HIP_E_ARG, "banks of one call share K, bits, group size, zero-point setting and scale dtype (their rows may differ)");
+        if ((int)banks[1]->experts.size() != E) return fail(TMAC_HIP_E_ARG, "banks of one call share the routing: %d and %d experts", E, (int)banks[1]->experts.size());
+    }
+    ExpertsRowsSizes z;
+    if (!experts_rows_sizes(N, S, E, z)) return fail(TMAC_HIP_E_ARG, "experts rows call (N=%d, S=%d, E=%d): %s", N, S, E, z.why);
+    if (x_rows != N && x_rows != z.P)
+        return fail(TMAC_HIP_E_ARG, "x_rows=%d: N=%d (token-major activations) or P=%d (position-major)", x_rows, N, z.P);
+    for (int b = 0; b < nbanks; ++b)
+        if (misaligned(C_dev[b], out_align(out_dtype)))
+            return fail(TMAC_HIP_E_ARG, "C_dev[%d] must be %zu-byte aligned (four outputs are stored at a time)", b, out_align(out_dtype));
+    if (misaligned(B_dev, ACT_ALIGN)) return fail(TMAC_HIP_E_ARG, "B_dev must be %zu-byte aligned (the LUT build reads 16 bytes at a time)", ACT_ALIGN);
+    if (misaligned(tile_expert_dev, 4) || misaligned(src_dev, 4)) return fail(TMAC_HIP_E_ARG, "tile_expert_dev and src_dev must be 4-byte aligned");
+    ExpertsGemmArgs a;
+    memset(&a, 0, sizeof(a));
+    int Mw[EXPERTS_MAX_BANKS] = {0, 0};
+    for (int b = 0; b < nbanks; ++b) {
+        Mw[b] = banks[b]->s.Mw;
+        a.b[b].tab = banks[b]->tab; a.b[b].C = C_dev[b]; a.b[b].E = E; a.b[b].Mw = Mw[b];
+    }
+    ExpertsGemmPlan p;
+    if (!experts_gemm_plan(s0, Mw, nbanks, N, S, E, z.P, p)) return fail(TMAC_HIP_E_NOMATCH, "experts rows call (K=%d, N=%d, S=%d): %s", s0.K, N, S, p.why);
+    int32_t rc = defer_barrier();             // never queued: behind the calling thread's queue (B_dev may be a queued call's output)
+    if (rc) return rc;
+    const hipStream_t st = (hipStream_t)stream;
+    tmac_hip_workspace* ws = nullptr;
+    if ((rc = stream_workspace(st, s0.K, z.P, &ws)) != TMAC_HIP_OK) return rc;
+    LutBuildReq q;
+    q.K = s0.K; q.N = z.P; q.ags = s0.ags; q.want = LB_IMAGE;
+    q.src_dev = src_dev; q.row_div = x_rows == z.P ? 0 : S; q.x_rows = x_rows;      // (P > N S >= N: the two never coincide)
+    LutBuildPlan lb;
+    if ((rc = lut_build_plan(q, lut_caps(ws), &lb)) != TMAC_HIP_OK) return rc;
+    if ((rc = lut_build(ws, lb, B_dev, act_dtype, nullptr, nullptr, st)) != TMAC_HIP_OK) return rc;
+    a.nbanks = nbanks; a.s = s0;
+    a.tile_expert = tile_expert_dev; a.src = src_dev;
+    a.bimg = (const uint4*)ws->gimg; a.colv = ws->gcol; a.P = z.P;
+    a.sc_f16 = b0->sc_dtype == F16; a.out_f16 = out_dtype == TMAC_F16;
+    const hipError_t e = launch_gemm_experts(a, p, st);
+    if (e != hipSuccess) return fail(TMAC_HIP_E_RUNTIME, "experts rows kernel launch: %s", hipGetErrorString(e));
+    return TMAC_HIP_OK;
+}

@@ -330,6 +330,35 @@ hipError_t launch_experts_route(const int32_t* ids, int NS, int E, int T_max, in
 // k_experts_combine: y [N][Mw] = sum_s gates[n][s] * C[pos[n S + s]][:] over fp32 C, slot order, two roundings per slot; a pos outside
 // [0, P) adds nothing
 hipError_t launch_experts_combine(const float* C, const int32_t* pos, const float* gates, int N, int S, int Mw, int P, void* y, int out_f16, hipStream_t st);
+// The grouped GEMM between the two (tmac_experts_gemm.hip): C[b][p][:] = W_b[tile_expert[p / 64]] . (activation row of position p) over the
+// position-ordered LUT image k_lut_image_pos writes.
+struct ExpertsGemmBank {
+    const ExpertEntry* tab;  // device, [E]
+    void* C;                 // [P][Mw]
+    int E, Mw;
+    int wg_end;              // cumulative workgroups along x up to and including this bank (filled by the launcher)
+};
+struct ExpertsGemmArgs {
+    ExpertsGemmBank b[EXPERTS_MAX_BANKS];
+    int nbanks;
+    Shape s;                 // K, bits, gs, ags = 64, zero_point of every expert (Mw unused)
+    const int32_t* tile_expert;   // device, [P / 64]: the expert of a position tile; outside [0, E): the tile is unused
+    const int32_t* src;      // device, [P]: < 0 marks a padding position
+    const uint4* bimg;       // uint4 [K/64][P/64][8][64]: k_lut_image's chunk-major layout over positions
+    const float* colv;       // float4 [K/64][P]
+    int P;
+    int sc_f16, out_f16;
+    int apg_shift;           // filled by the launcher: log2(act groups per weight group)
+};
+// k_lut_image_pos: image row p = the build of row src[p] / row_div of x [x_rows][K] (row_div >= 1) or of row p (row_div == 0, x_rows == P);
+// src[p] < 0 or a row beyond x_rows: nothing is read, the row and its column values are zeros.  Called by lut_build alone.
+hipError_t launch_lut_image_pos(const void* x, int act_f16, const int32_t* src, int row_div, int x_rows, void* bimg, float* colv, int K, int P,
+                                hipStream_t st);
+// fills wg_end and apg_shift from the plan and launches once (tmac_experts.cpp); the launcher of one translation unit of
+// tmac_experts_gemm.hip (defined and instantiated there for its BITS)
+hipError_t launch_gemm_experts(const ExpertsGemmArgs& a, const ExpertsGemmPlan& p, hipStream_t st);
+template <int BITS>
+hipError_t launch_gemm_experts_unit(const ExpertsGemmArgs& a, const ExpertsGemmPlan& p, hipStream_t st);
 // returns hipErrorInvalidValue when the variant does not cover the configuration
 hipError_t launch_gemv(const GemvArgs& a, Variant v, hipStream_t st);
 bool gemv_lo_supported(const Shape& s);

@@ -233,4 +233,32 @@ bool experts_rows_sizes(long long N, long long S, long long E, ExpertsRowsSizes&
     return true;
 }
 
+bool experts_gemm_plan(const Shape& s, const int* bank_Mw, int nbanks, long long N, long long S, long long E, long long P, ExpertsGemmPlan& p) {
+    p = ExpertsGemmPlan{nullptr, 0, 0, {0, 0}, 0};
+    auto refuse = [&](const char* why) { p.why = why; return false; };
+    if (nbanks < 1 || nbanks > EXPERTS_MAX_BANKS) return refuse("one or two banks per call");
+    // the per-group-scale branch of gemm_planes_supported (tmac_gemm2.hip), which this file cannot call: QUAD layout, 1-4 bits, act groups
+    // of 64, weight groups of 64 x 2^n that divide K
+    const int apg = s.gs / 64;
+    if (s.lay != 2 || s.bits < 1 || s.bits > 4 || s.K < 64 || s.K % 64 != 0 || s.m_groups >= 1 || s.ags != 64 || s.gs < 64 || s.gs % 64 != 0 ||
+        s.K % s.gs != 0 || (apg & (apg - 1)) != 0)
+        return refuse("outside what k_gemm_planes' per-group arithmetic serves (QUAD layout, 1-4 bits, K a multiple of 64, act groups of 64, group sizes 64 x 2^n, per-group scales)");
+    ExpertsRowsSizes z;
+    if (!experts_rows_sizes(N, S, E, z)) return refuse(z.why);
+    if (P != z.P) return refuse("P is not 64 x T_max of (N, S, E): the outputs and the routing belong to another call shape");
+    if ((size_t)2 * s.K * (size_t)P >= ((size_t)1 << 31)) return refuse("the position image reaches 2 GB (32-bit buffer offsets): fewer tokens per call");
+    int gx = 0;
+    for (int b = 0; b < nbanks; ++b) {
+        const int Mw = bank_Mw[b];
+        if (Mw < 4 || Mw % 4 != 0) return refuse("a bank's Mw must be a multiple of 4");
+        if ((size_t)(Mw / 4) * ((s.K / 32 + 63) / 64) * s.bits * 1024 >= ((size_t)1 << 31)) return refuse("an expert's matrix reaches 2 GB (32-bit buffer offsets)");
+        const int tiles = (Mw + 63) / 64;
+        gx += (tiles + EXPERTS_GEMM_NWV - 1) / EXPERTS_GEMM_NWV;
+        p.wg_end[b] = gx;
+    }
+    p.gx = gx; p.gy = z.T_max;
+    p.lds_bytes = EXPERTS_GEMM_LDS_BYTES;
+    return true;
+}
+
 }  // namespace tmac

@@ -141,6 +141,21 @@ struct ExpertsRowsSizes {
 // Pure.  Returns why == null.
 bool experts_rows_sizes(long long N, long long S, long long E, ExpertsRowsSizes& z);
 
+// ---- the grouped GEMM over routed positions: k_gemm_experts<BITS, ZP, SCF16> (tmac_experts_gemm.hip) -----------------------------------
+// A workgroup of four waves serves one position tile and four adjacent 64-row tiles of one bank; every wave walks the whole K.  LDS: the
+// operand rows (64 KB, shared) + 1 KB of weight scales / zeros per wave.
+constexpr int EXPERTS_GEMM_NWV = 4, EXPERTS_GEMM_LDS_BYTES = 65536 + EXPERTS_GEMM_NWV * 1024;
+struct ExpertsGemmPlan {
+    const char* why;         // null: served
+    int gx, gy;              // x: the row-tile quartets of the banks, each bank rounded up to whole workgroups of its own; y: T_max
+    int wg_end[EXPERTS_MAX_BANKS];   // cumulative workgroups along x up to and including bank b
+    size_t lds_bytes;
+};
+// s: the banks' common shape (Mw unused); bank_Mw: rows of each bank's matrices; P: positions of the call's image and outputs.  Refuses a
+// configuration outside k_gemm_planes' per-group-scale arithmetic (gemm_planes_supported), an image or an expert matrix at or beyond 2 GB
+// (32-bit buffer offsets) and P != 64 T_max of (N, S, E).  Pure.  Returns why == null.
+bool experts_gemm_plan(const Shape& s, const int* bank_Mw, int nbanks, long long N, long long S, long long E, long long P, ExpertsGemmPlan& p);
+
 // ---- k_decode_chain<BITS, ZP, SCF16, SM, XF, TAP, G2, GT> ---------------------------------------------------------------------------
 // The tap's instance carries the transforms too, and a gate other than silu belongs to a transform: TAP and GT imply XF.  Unified scales
 // (SM 2) have one scale per matrix: no G2 instance (two scale groups per lane and item), and no zero points.

@@ -43,6 +43,10 @@ struct LutBuildReq {
     bool xf = false;           // the build carries a vector transform
     uint64_t perm_id = 0;      // the build gathers through this K permutation (0 = none) ...
     int perm_K = 0;            // ... which was built for this K
+    // row map of a POSITION image (the grouped expert GEMM, LB_IMAGE alone): image row p of N = P positions is the build of row
+    // src_dev[p] / row_div of x [x_rows][K] (row_div >= 1) or of row p (row_div == 0), zeros where src_dev[p] < 0.  Null: no map
+    const int32_t* src_dev = nullptr;
+    int row_div = 0, x_rows = 0;
 };
 struct LutBuildCaps {
     int pairs_min_n = 2;       // rows from which LB_ALL uses the pair builds (Knobs::pairs_min_n)
@@ -87,6 +91,10 @@ struct LutBuildPlan {
     bool row_image = false;     // LUTB_PAIRS_ROW also writes the row-wise LUT image
     bool lut_image = false;     // k_lut_image runs after the builder: the chunk-major LUT image
     LutHeld held;               // what the workspace holds once every launch of the plan is enqueued
+    // a position image (k_lut_image_pos, nothing else): K x P and the request's row map.  `held` stays empty -- the image is the routing's,
+    // no later call may reuse it
+    const int32_t* src_dev = nullptr;
+    int row_div = 0, x_rows = 0, pos_K = 0, pos_P = 0;
 };
 inline void LutHeld::commit(const LutBuildPlan& p) { *this = p.held; }
 
@@ -110,6 +118,15 @@ inline int32_t lut_build_plan(const LutBuildReq& q, const LutBuildCaps& c, LutBu
         return fail(TMAC_HIP_E_NOMATCH, "a transformed call of several rows needs the LUT image or the half-table image alone; this plan builds every layout");
     if (q.xf && perm) return fail(TMAC_HIP_E_NOMATCH, "a LUT build takes a vector transform or a K permutation, not both");
     LutBuildPlan p;
+    if (q.src_dev) {
+        if (q.want != LB_IMAGE || q.unified || q.xf || perm || q.ags != 64)
+            return fail(TMAC_HIP_E_NOMATCH, "a row map goes with the chunk-major LUT image alone (act groups of 64, no transform, no K permutation)");
+        if (q.N % 64 || q.row_div < 0 || q.x_rows < 1 || (q.row_div == 0 && q.x_rows != q.N))
+            return fail(TMAC_HIP_E_ARG, "row map: N=%d positions must be whole tiles of 64; x_rows=%d is the token count (row_div=%d >= 1) or N", q.N, q.x_rows, q.row_div);
+        p.src_dev = q.src_dev; p.row_div = q.row_div; p.x_rows = q.x_rows; p.pos_K = q.K; p.pos_P = q.N;
+        *out = p;
+        return TMAC_HIP_OK;
+    }
     LutHeld& h = p.held;
     h.K_ = q.K; h.N_ = q.N; h.ags_ = q.ags; h.perm_id_ = q.perm_id;
     switch (q.want) {

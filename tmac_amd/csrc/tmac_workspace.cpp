@@ -70,6 +70,12 @@ LutBuildCaps tmac_host::lut_caps(const tmac_hip_workspace* ws) {
 int32_t tmac_host::lut_build(tmac_hip_workspace* ws, const LutBuildPlan& plan, const void* B_dev, tmac_dtype_t act_dtype, const XfRowsGateArgs* xf,
                              const int32_t* perm_dev, hipStream_t st) {
     ws->held.clear();
+    if (plan.src_dev) {      // a position image: the workspace holds nothing a later call may reuse, before and after
+        if (!ws->gimg || plan.pos_K > ws->maxK || plan.pos_P > ws->gNpad) return fail(TMAC_HIP_E_ARG, "K=%d P=%d exceed the workspace's LUT image", plan.pos_K, plan.pos_P);
+        const hipError_t e = launch_lut_image_pos(B_dev, act_dtype == TMAC_F16, plan.src_dev, plan.row_div, plan.x_rows, ws->gimg, ws->gcol, plan.pos_K, plan.pos_P, st);
+        if (e != hipSuccess) return fail(TMAC_HIP_E_RUNTIME, "position LUT image launch: %s", hipGetErrorString(e));
+        return TMAC_HIP_OK;
+    }
     const LutHeld& h = plan.held;
     const int K = h.K(), N = h.N(), f16 = act_dtype == TMAC_F16;
     const bool all = plan.all_layouts, row_img = plan.row_image;

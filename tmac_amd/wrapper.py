@@ -1034,6 +1034,45 @@ class TMACGeMMWrapper:
         check(B.lib().tmac_hip_experts_combine_dev(_ptr(c), _ptr(pos), _ptr(gates), N, S, Mw, P, _ptr(out), _dtype_code(out), _stream(stream)))
         return out
 
+    def experts_rows(self, banks, x, route, S: int, out=None, stream=None):
+        """The grouped GEMM over the positions of ``route`` (tmac_hip_qgemm_experts_rows_dev): one ``[P, Mw]`` tensor per bank, row p =
+        ``W[tile_expert[p // 64]] x_row(p)``.  ``banks``: one or two :class:`ExpertBank` that share the routing (gate / up).  ``x``: CUDA
+        fp16 / fp32, token-major ``[N, K]`` -- position p reads row ``src[p] // S`` -- or position-major ``[P, K]`` -- position p reads
+        row p; rows at padding positions are never read.  A padding position of a used tile gets +0, the rows of an unused tile are left
+        as they are.  ``out``: the tensors to write instead of new fp32 ones (fp16 or fp32).  Nothing is copied to the host.  A layer::
+
+            route = wr.experts_route(ids, E)                                  # ids [N, S] from the router
+            g, u = wr.experts_rows([gate, up], x, route, S)                   # x [N, K]: token-major
+            h = torch.nn.functional.silu(g) * u                               # the caller's GLU, in position order [P, F]
+            (d,) = wr.experts_rows(down, h, route, S)                         # position-major
+            y = wr.experts_combine(d, route, gates)                           # [N, Mw]
+        """
+        import torch
+        banks = list(banks) if isinstance(banks, (list, tuple)) else [banks]
+        te, src, pos = route
+        S = int(S)
+        if S < 1 or int(pos.numel()) % S:
+            raise ValueError("S does not divide the routing's flat slots")
+        N, P = int(pos.numel()) // S, int(src.numel())
+        if x.dim() != 2 or not x.is_contiguous():
+            raise TypeError("x must be a contiguous [N, K] or [P, K] tensor")
+        if out is None:
+            out = [torch.empty((P, b.Mw), dtype=torch.float32, device=x.device) for b in banks]
+        outs = list(out) if isinstance(out, (list, tuple)) else [out]
+        if len(outs) != len(banks):
+            raise ValueError("one output per bank")
+        # the routing's sizes against the call's shape (P = 64 T_max of (N, S, E)), by the planner, before anything is launched
+        b0 = banks[0]
+        mw = (C.c_int * len(banks))(*[b.Mw for b in banks])
+        check(B.lib().tmac_hip_debug_experts_gemm_plan(b0.K, b0.bits, b0.experts[0].cfg.group_size, mw, len(banks), N, S, b0.E, P, None, None, None))
+        if int(te.numel()) * 64 != P or any(tuple(o.shape) != (P, b.Mw) or not o.is_contiguous() for o, b in zip(outs, banks)):
+            raise ValueError(f"outputs are contiguous [P={P}, Mw] tensors and tile_expert has P / 64 elements")
+        ba = (C.c_void_p * len(banks))(*[b.handle.value for b in banks])
+        ca = (C.c_void_p * len(banks))(*[_ptr(c) for c in outs])
+        check(B.lib().tmac_hip_qgemm_experts_rows_dev(ba, len(banks), _ptr(x), _dtype_code(x), int(x.shape[0]), _ptr(te), _ptr(src), N, S, ca,
+                                                      _dtype_code(outs[0]), _stream(stream)))
+        return outs
+
     def record_gather(self, send_dev, recv_dev, bytes_per_rank: int, rank: int, world: int) -> None:
         """while recording a chain: the exchange step ``recv = all-gather over the ranks of send`` (what ``Comm.allgather`` records
         by itself); inside the launch it becomes part of the hand-off"""
