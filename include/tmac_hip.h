@@ -706,6 +706,29 @@ int32_t tmac_hip_qgemm_fused_xf_dev(const tmac_hip_weights* const* weights, int 
  * refused, where the N = 1 form does not look at it. */
 int32_t tmac_hip_qgemm_fused_xf_rows_dev(const tmac_hip_weights* const* weights, int nmat, const void* B_dev, tmac_dtype_t act_dtype,
                                          const tmac_hip_xform* xf, void* const* C_dev, tmac_dtype_t out_dtype, int N, void* stream);
+
+/* ---- expert banks: the tables built in the launch, optionally behind a GLU -----------------------------------------------------------
+ * tmac_hip_qgemm_experts_fused_dev: tmac_hip_qgemm_experts_dev (above) with the tables of the call's lut_rows rows built INSIDE the one
+ * k_gemv_experts launch, by the same constructor -- no pair-build launch, no image in the workspace.  Same arguments, same plan, same
+ * outputs to the bit (SLOTS and COMBINE, empty slots, the refusals above under this function's name).  The call touches no workspace:
+ * nothing is created, read or invalidated, there is no first-use rule, and it is capturable on a stream the library has never seen.
+ *   xf == NULL or kind TMAC_XF_NONE   the tables of B_dev
+ *   TMAC_XF_GLU | gate                the tables of x = gate(B_dev) * in2, row by row: in2 [S][K] in act_dtype, 16-byte aligned, lut_rows = S;
+ *                                     the expression and the gates of tmac_hip_qgemm_fused_xf_dev (silu, gelu: to a tolerance; relu2: to
+ *                                     the bit).  With gates_dev this is the `down` projection of a layer fed gate_out and up_out directly:
+ *                                     an MoE layer's token is two launches.  The other fields of xf are ignored.
+ * Refused with TMAC_HIP_E_ARG before anything is launched or flushed: TMAC_XF_NORM and TMAC_XF_GLU_NORM (by name), an unknown kind or
+ * gate, GLU without in2, with a misaligned in2 or with lut_rows != S.  Inside a recording it is refused; it runs behind the calling
+ * thread's deferred queue.  tmac_hip_debug_experts_fused_plan: tmac_hip_debug_experts_plan's arguments and the kind; the same plan for
+ * every kind the call takes, or its refusal (pure, no device). */
+int32_t tmac_hip_qgemm_experts_fused_dev(const tmac_hip_bank* const* banks, int nbanks,
+        const void* B_dev, tmac_dtype_t act_dtype, int lut_rows,
+        const tmac_hip_xform* xf /* NULL, TMAC_XF_NONE or TMAC_XF_GLU | gate */,
+        const int32_t* ids_dev, const float* gates_dev, int S,
+        void* const* C_dev, tmac_dtype_t out_dtype, void* stream);
+int32_t tmac_hip_debug_experts_fused_plan(int K, int bits, int group_size, const int* bank_Mw, int nbanks, int S, int lut_rows, int combine,
+                                          int32_t kind, int32_t* waves_per_quad, int32_t* grid, int32_t* items, size_t* lds_bytes);
+
 /* What the call above would run for N >= 2 rows on these matrices, under the current knobs (host only: plans, launches nothing):
  * route 0 k_gemm_planes, 1 k_gemm_onehot, 3 k_gemv_rows, 7 the row loop; lut 1 the LUT image, 2 the half-table image.  The planner's
  * refusals come back as from the call (the scope checks of the call itself are not repeated). */

@@ -139,6 +139,11 @@ def load_library() -> C.CDLL:
         "tmac_hip_qgemm_experts_dev": ([C.POINTER(vp), C.c_int, vp, C.c_int, C.c_int, vp, vp, C.c_int, C.POINTER(vp), C.c_int, vp], i32),
         "tmac_hip_debug_experts_plan": ([C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int), C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int32),
                                          C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(sz)], i32),
+        # ... with the tables built in the launch, optionally behind a GLU; its plan
+        "tmac_hip_qgemm_experts_fused_dev": ([C.POINTER(vp), C.c_int, vp, C.c_int, C.c_int, C.POINTER(XForm), vp, vp, C.c_int, C.POINTER(vp), C.c_int, vp],
+                                             i32),
+        "tmac_hip_debug_experts_fused_plan": ([C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int), C.c_int, C.c_int, C.c_int, C.c_int, C.c_int32,
+                                               C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(sz)], i32),
         # ... for token batches: the tile bound of a call shape, the routing, the gated sum
         "tmac_hip_experts_rows_sizes": ([C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int32), C.POINTER(C.c_int32)], i32),
         "tmac_hip_experts_route_dev": ([vp, C.c_int, C.c_int, C.c_int, vp, vp, vp, vp], i32),
@@ -229,7 +234,8 @@ def load_library() -> C.CDLL:
                 "tmac_hip_debug_rows_kernel", "tmac_hip_debug_rows_stats", "tmac_hip_debug_rows_plan", "tmac_hip_debug_rows_comb_sums",
                 "tmac_hip_bank_create", "tmac_hip_bank_free", "tmac_hip_bank_info", "tmac_hip_qgemm_experts_dev", "tmac_hip_debug_experts_plan",
                 "tmac_hip_experts_rows_sizes", "tmac_hip_experts_route_dev", "tmac_hip_experts_combine_dev",
-                "tmac_hip_qgemm_experts_rows_dev", "tmac_hip_debug_experts_gemm_plan"} if os.environ.get("TMAC_HIP_LIB") else set()
+                "tmac_hip_qgemm_experts_rows_dev", "tmac_hip_debug_experts_gemm_plan",
+                "tmac_hip_qgemm_experts_fused_dev", "tmac_hip_debug_experts_fused_plan"} if os.environ.get("TMAC_HIP_LIB") else set()
     for name, (argt, rest) in sigs.items():
         try:
             fn = getattr(L, name)

@@ -1,7 +1,8 @@
-// tmac_experts.cpp — expert banks (tmac_hip_bank_*) and the entry point of a mixture-of-experts layer's top-k GEMVs
-// (tmac_hip_qgemm_experts_dev): check the call, build the half-table image of its activation rows into the stream's library workspace
-// with the existing builder, then ONE k_gemv_experts launch (tmac_experts.hip) that picks every slot's matrix on the device.  Nothing
-// here reads ids or gates.  DESIGN.md 4.17.
+// tmac_experts.cpp — expert banks (tmac_hip_bank_*) and the entry points of a mixture-of-experts layer's top-k GEMVs:
+// tmac_hip_qgemm_experts_dev -- check the call, build the half-table image of its activation rows into the stream's library workspace
+// with the existing builder, then ONE k_gemv_experts launch (tmac_experts.hip) that picks every slot's matrix on the device -- and
+// tmac_hip_qgemm_experts_fused_dev -- the same checks, then that launch alone: the kernel builds its tables itself, optionally behind a
+// GLU.  Nothing here reads ids or gates.  DESIGN.md 4.17.
 #include "tmac_host.h"
 #include "tmac_select.h"
 
@@ -158,16 +159,15 @@ hipError_t tmac::launch_gemv_experts(const ExpertsArgs& a_in, hipStream_t st) {
     return sel_int<1, 2, 3, 4>(s.bits, [&](auto BITS) { return launch_gemv_experts_unit<decltype(BITS)::value>(a, p, mode, st); });
 }
 
-extern "C" int32_t tmac_hip_qgemm_experts_dev(const tmac_hip_bank* const* banks, int nbanks, const void* B_dev, tmac_dtype_t act_dtype, int lut_rows,
-                                              const int32_t* ids_dev, const float* gates_dev, int S, void* const* C_dev, tmac_dtype_t out_dtype,
-                                              void* stream) {
-    bind_thread_device();
-    // every check before anything is launched or flushed: a refused call launches nothing and leaves the deferred queue as it is
-    if (!banks || !C_dev || nbanks < 1 || nbanks > EXPERTS_MAX_BANKS) return fail(TMAC_HIP_E_ARG, "tmac_hip_qgemm_experts_dev takes one or two banks (nbanks=%d)", nbanks);
+// The checks the two top-k entry points share, in the order tmac_hip_qgemm_experts_dev always made them (`fn` names the entry point in the
+// messages), then the argument block without its table source and the plan.  Launches nothing, flushes nothing.
+static int32_t experts_call_check(const char* fn, const tmac_hip_bank* const* banks, int nbanks, const void* B_dev, int lut_rows, const int32_t* ids_dev,
+                                  const float* gates_dev, int S, void* const* C_dev, tmac_dtype_t out_dtype, ExpertsArgs& a) {
+    if (!banks || !C_dev || nbanks < 1 || nbanks > EXPERTS_MAX_BANKS) return fail(TMAC_HIP_E_ARG, "%s takes one or two banks (nbanks=%d)", fn, nbanks);
     for (int b = 0; b < nbanks; ++b)
         if (!banks[b] || !C_dev[b]) return fail(TMAC_HIP_E_ARG, "null bank or output");
     if (!B_dev || !ids_dev) return fail(TMAC_HIP_E_ARG, "null activations or ids");
-    if (chain_recording()) return fail(TMAC_HIP_E_ARG, "tmac_hip_qgemm_experts_dev cannot be recorded (tmac_hip_chain_begin ... _end): expert calls run stand-alone");
+    if (chain_recording()) return fail(TMAC_HIP_E_ARG, "%s cannot be recorded (tmac_hip_chain_begin ... _end): expert calls run stand-alone", fn);
     if (S < 1 || S > EXPERTS_MAX_SLOTS) return fail(TMAC_HIP_E_ARG, "S=%d: an experts call takes 1 to %d slots", S, EXPERTS_MAX_SLOTS);
     if (lut_rows != 1 && lut_rows != S) return fail(TMAC_HIP_E_ARG, "lut_rows=%d: 1 (one activation row shared by the slots) or S=%d", lut_rows, S);
     const bool combine = gates_dev != nullptr;
@@ -185,7 +185,6 @@ extern "C" int32_t tmac_hip_qgemm_experts_dev(const tmac_hip_bank* const* banks,
         if (s1.K != s0.K || s1.bits != s0.bits || s1.gs != s0.gs || s1.ags != s0.ags || s1.zero_point != s0.zero_point || banks[1]->sc_dtype != b0->sc_dtype)
             return fail(TMAC_HIP_E_ARG, "banks of one call share K, bits, group size, zero-point setting and scale dtype (their rows may differ)");
     }
-    ExpertsArgs a;
     memset(&a, 0, sizeof(a));
     int Mw[EXPERTS_MAX_BANKS] = {0, 0};
     for (int b = 0; b < nbanks; ++b) {
@@ -195,10 +194,32 @@ extern "C" int32_t tmac_hip_qgemm_experts_dev(const tmac_hip_bank* const* banks,
     ExpertsPlan p;
     if (!experts_plan(s0, Mw, nbanks, S, lut_rows, combine ? EXPERTS_COMBINE : EXPERTS_SLOTS, p))
         return fail(TMAC_HIP_E_NOMATCH, "experts call (K=%d, S=%d, lut_rows=%d): %s", s0.K, S, lut_rows, p.why);
-    int32_t rc = defer_barrier();             // never queued: behind the calling thread's queue (B_dev, ids_dev may be a queued call's output)
+    a.nbanks = nbanks; a.s = s0;
+    a.ids = ids_dev; a.gates = gates_dev; a.S = S; a.lut_rows = lut_rows;
+    a.sc_f16 = b0->sc_dtype == F16; a.out_f16 = out_dtype == TMAC_F16;
+    return TMAC_HIP_OK;
+}
+
+static int32_t experts_launch(const ExpertsArgs& a, hipStream_t st) {
+    const hipError_t e = launch_gemv_experts(a, st);
+    if (e == hipErrorInvalidValue) return fail(TMAC_HIP_E_NOMATCH, "experts kernel: configuration or sizes not covered (an expert's matrix must stay below 2 GB)");
+    if (e != hipSuccess) return fail(TMAC_HIP_E_RUNTIME, "experts kernel launch: %s", hipGetErrorString(e));
+    return TMAC_HIP_OK;
+}
+
+extern "C" int32_t tmac_hip_qgemm_experts_dev(const tmac_hip_bank* const* banks, int nbanks, const void* B_dev, tmac_dtype_t act_dtype, int lut_rows,
+                                              const int32_t* ids_dev, const float* gates_dev, int S, void* const* C_dev, tmac_dtype_t out_dtype,
+                                              void* stream) {
+    bind_thread_device();
+    // every check before anything is launched or flushed: a refused call launches nothing and leaves the deferred queue as it is
+    ExpertsArgs a;
+    int32_t rc = experts_call_check("tmac_hip_qgemm_experts_dev", banks, nbanks, B_dev, lut_rows, ids_dev, gates_dev, S, C_dev, out_dtype, a);
+    if (rc) return rc;
+    rc = defer_barrier();                     // never queued: behind the calling thread's queue (B_dev, ids_dev may be a queued call's output)
     if (rc) return rc;
     // the half-table image of the call's rows, by the builder k_gemv_rows is fed by
     const hipStream_t st = (hipStream_t)stream;
+    const Shape& s0 = a.s;
     tmac_hip_workspace* ws = nullptr;
     if ((rc = stream_workspace(st, s0.K, lut_rows, &ws)) != TMAC_HIP_OK) return rc;
     LutBuildReq q;
@@ -206,14 +227,57 @@ extern "C" int32_t tmac_hip_qgemm_experts_dev(const tmac_hip_bank* const* banks,
     LutBuildPlan lb;
     if ((rc = lut_build_plan(q, lut_caps(ws), &lb)) != TMAC_HIP_OK) return rc;
     if ((rc = lut_build(ws, lb, B_dev, act_dtype, nullptr, nullptr, st)) != TMAC_HIP_OK) return rc;
-    a.nbanks = nbanks; a.s = s0;
-    a.ids = ids_dev; a.gates = gates_dev; a.S = S; a.lut_rows = lut_rows;
     a.qlut_lds = ws->qlut_lds; a.lut_scales = ws->lut_scales; a.lut_biases = ws->lut_biases;
-    a.sc_f16 = b0->sc_dtype == F16; a.out_f16 = out_dtype == TMAC_F16;
-    const hipError_t e = launch_gemv_experts(a, st);
-    if (e == hipErrorInvalidValue) return fail(TMAC_HIP_E_NOMATCH, "experts kernel: configuration or sizes not covered (an expert's matrix must stay below 2 GB)");
-    if (e != hipSuccess) return fail(TMAC_HIP_E_RUNTIME, "experts kernel launch: %s", hipGetErrorString(e));
+    return experts_launch(a, st);
+}
+
+// ---- the same call with its tables built in the launch (k_gemv_experts LUTSRC 1), optionally behind x = gate(in) * in2 (LUTSRC 2): one
+//      launch, no workspace -- nothing of the stream's workspace is read, written or created, so the call may be the first thing a
+//      capturing stream sees.  The plan is experts_plan's: it does not know how the tables are made.
+// The transform of such a call: NONE or a GLU.  NORM and GLU_NORM are refused by name before their own field rules are looked at; kind,
+// gate, the GLU's in2 and its alignment are the resolver's; a GLU reads one row of in and in2 per slot.
+static int32_t experts_xf_check(const tmac_hip_xform* xf, int lut_rows, int S, XfSpec* x) {
+    const int k = xf->kind & 0xff;
+    if (k == TMAC_XF_NORM || k == TMAC_XF_GLU_NORM)
+        return fail(TMAC_HIP_E_ARG, "experts call: %s is not served in front of an experts call (TMAC_XF_NONE or TMAC_XF_GLU)", k == TMAC_XF_NORM ? "TMAC_XF_NORM" : "TMAC_XF_GLU_NORM");
+    const int32_t rc = xf_resolve(xf, XF_SITE_N1, x);
+    if (rc) return rc;
+    if (x->kind == TMAC_XF_GLU && lut_rows != S)
+        return fail(TMAC_HIP_E_ARG, "experts call: a GLU takes one row of in and in2 per slot: lut_rows=%d, S=%d", lut_rows, S);
     return TMAC_HIP_OK;
+}
+
+extern "C" int32_t tmac_hip_debug_experts_fused_plan(int K, int bits, int group_size, const int* bank_Mw, int nbanks, int S, int lut_rows, int combine,
+                                                     int32_t kind, int32_t* wpq, int32_t* grid, int32_t* items, size_t* lds_bytes) {
+    alignas(16) static const char operand[16] = {};      // (a pure twin has no operands: this passes the resolver's in2 rules)
+    tmac_hip_xform xf{};
+    xf.kind = kind;
+    xf.in2 = operand;
+    XfSpec x;
+    const int32_t rc = experts_xf_check(&xf, lut_rows, S, &x);
+    if (rc) return rc;
+    return tmac_hip_debug_experts_plan(K, bits, group_size, bank_Mw, nbanks, S, lut_rows, combine, wpq, grid, items, lds_bytes);
+}
+
+extern "C" int32_t tmac_hip_qgemm_experts_fused_dev(const tmac_hip_bank* const* banks, int nbanks, const void* B_dev, tmac_dtype_t act_dtype, int lut_rows,
+                                                    const tmac_hip_xform* xf, const int32_t* ids_dev, const float* gates_dev, int S, void* const* C_dev,
+                                                    tmac_dtype_t out_dtype, void* stream) {
+    bind_thread_device();
+    // every check before anything is launched or flushed: a refused call launches nothing and leaves the deferred queue as it is
+    XfSpec x;
+    if (xf) {
+        const int32_t xrc = experts_xf_check(xf, lut_rows, S, &x);
+        if (xrc) return xrc;
+    }
+    ExpertsArgs a;
+    int32_t rc = experts_call_check("tmac_hip_qgemm_experts_fused_dev", banks, nbanks, B_dev, lut_rows, ids_dev, gates_dev, S, C_dev, out_dtype, a);
+    if (rc) return rc;
+    rc = defer_barrier();                     // never queued: behind the calling thread's queue
+    if (rc) return rc;
+    a.lutsrc = x.kind == TMAC_XF_GLU ? 2 : 1;
+    a.B = B_dev; a.in2 = x.in2; a.act_f16 = act_dtype == TMAC_F16;
+    a.xf_kind = x.kind | (x.gate << 8);
+    return experts_launch(a, (hipStream_t)stream);
 }
 
 // ---- token batches: the grouped GEMM over routed positions (k_lut_image_pos + k_gemm_experts, tmac_experts_gemm.hip) ----

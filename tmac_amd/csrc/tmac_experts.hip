@@ -16,11 +16,20 @@
 //             pointer from them.  One unsigned compare decides whether the slot is EMPTY (id outside [0, E); -1 is the documented
 //             value): no address is formed from such an id, its SLOTS row is stored as zeros, it adds nothing to a COMBINE output.
 //   x_row(s)  row 0 for every slot (lut_rows = 1: gate / up read the token's one vector, ONE set of tables in LDS) or row s (lut_rows = S).
-// The tables are COPIED from the workspace's half-table image exactly as k_gemv_rows / k_gemv_quad (LUTSRC == 0) copy them (xor 0x80808080
-// for the MFMA adder, scales halved, zero tables between nu and the end of the last step): no LUT is built here.  The first weight fragments
+// LUTSRC 0: the tables are COPIED from the workspace's half-table image exactly as k_gemv_rows / k_gemv_quad (LUTSRC == 0) copy them (xor
+// 0x80808080 for the MFMA adder, scales halved, zero tables between nu and the end of the last step).  The first weight fragments
 // are issued before the copy, and the copy takes the rows four at a time -- 16 table loads per thread in flight before the first LDS
 // store -- so a call's rows cost one or two memory latencies, not one each (the cost k_gemv_rows measured).
+// LUTSRC 1: the tables are BUILT in the launch from the call's activation rows, by the constructor of tmac_lut_build.h; LUTSRC 2: from
+// x = gate(in) * in2 (xf_gate_mul, the gate a run-time value: silu, relu^2, tanh-GELU), the GLU between gate / up and down.  The
+// lut_rows * K / 8 pairs (8 activations, two tables) are ONE flat index over the 512 threads -- the rows are contiguous, a lane holds a
+// pair, the 8 adjacent lanes of an act group of 64 never straddle a row (K is a multiple of 64) -- walked in batches of EXPERTS_LUT_NB
+// (4; 2 behind a GLU) pairs per thread; lanes past the end are clamped to the last pair and their stores dropped.  Order of the memory stream (k_gemv_quad's):
+// the first batch's activation loads, a wait for those registers alone, the weight ring, then the build on the VALU while the fragments
+// fly, the LDS stores and an LDS-only barrier.  Later batches' loads queue behind the ring.  The LDS image is the copy's to the bit, so
+// everything behind the barrier is the same code, and a slot's bits do not depend on which form made its tables.
 // No waits between workgroups, no spins, no atomics.  DESIGN.md 4.17.
+#define TMAC_LUT_SINGLE_F32 1      // (this unit is built without packed-fp32 instructions: tmac_lut_build.h)
 #include <hip/hip_runtime.h>
 #include <hip/hip_fp16.h>
 #include <stdint.h>
@@ -28,6 +37,8 @@
 #include "tmac_core.h"
 #include "tmac_kernels.h"
 #include "tmac_chain_core.h"
+#include "tmac_quad_core.h"
+#include "tmac_lut_build.h"
 #include "tmac_select.h"
 
 namespace tmac {
@@ -49,7 +60,13 @@ struct ECur {
     int woff;                          // byte offset of the quad's first fragment
 };
 
-template <int BITS, bool ZP, bool SCF16, int MODE>
+// Pairs per thread and batch of the in-launch build, from the register figures (profiles/r30_experts_fused_resources.txt).  LUTSRC 1: 4 --
+// 32 fp32 registers of activations beside the weight ring, 82 - 107 VGPRs where the copy form (16 table loads in flight) has 109 - 133; one
+// batch covers 16384 activations.  LUTSRC 2 holds both operands of the GLU until the ring is out: with 4 pairs every instantiation passed
+// 128 VGPRs (135 - 160) and lost the second workgroup per CU; with 2 they have 83 - 108.  No instantiation uses scratch.
+template <int LUTSRC> constexpr int EXPERTS_LUT_NB = LUTSRC == 2 ? 2 : 4;
+
+template <int BITS, bool ZP, bool SCF16, int MODE, int LUTSRC = 0>
 __global__ __launch_bounds__(EXPERTS_FT) void k_gemv_experts(ExpertsArgs a) {
     extern __shared__ uint4 lds[];
     constexpr int NWV = EXPERTS_NWV, FT = EXPERTS_FT;
@@ -72,6 +89,39 @@ __global__ __launch_bounds__(EXPERTS_FT) void k_gemv_experts(ExpertsArgs a) {
     asm volatile("" : "+v"(lk4));
 
     const int slot0 = (int)blockIdx.x * IPI + w / wpq, h = w % wpq, stride = (int)gridDim.x * IPI;
+
+    // ---- 0. LUTSRC >= 1: the activations of the first batch of pairs leave first (LUTSRC 2: both operands of the GLU) ------------------
+    constexpr int NB = EXPERTS_LUT_NB<LUTSRC>;
+    const int PR = 4 * nu, NPAIR = LR * PR;                           // pairs of a row, of the call
+    [[maybe_unused]] float xr[LUTSRC != 0 ? NB * 8 : 1], xa[LUTSRC == 2 ? NB * 8 : 1];
+    auto lut_load = [&](int b) {
+        if constexpr (LUTSRC != 0) {
+            auto ld = [&](const void* src, float* x) {                 // [lut_rows][K] contiguous: pair f of the call is pair f of the buffer
+                if (a.act_f16) {
+                    uint4 v[NB];
+#pragma unroll
+                    for (int r = 0; r < NB; ++r) v[r] = reinterpret_cast<const uint4*>(src)[min((b * NB + r) * FT + tid, NPAIR - 1)];
+#pragma unroll
+                    for (int r = 0; r < NB; ++r) {
+                        const uint32_t wd[4] = {v[r].x, v[r].y, v[r].z, v[r].w};
+                        const lut_f32x8 t = lut_unpack_f16v(wd);
+#pragma unroll
+                        for (int i = 0; i < 8; ++i) x[r * 8 + i] = t[i];
+                    }
+                } else {
+#pragma unroll
+                    for (int r = 0; r < NB; ++r) {
+                        const lut_f32x8 t = lut_ld8v(src, false, 0, min((b * NB + r) * FT + tid, NPAIR - 1));
+#pragma unroll
+                        for (int i = 0; i < 8; ++i) x[r * 8 + i] = t[i];
+                    }
+                }
+            };
+            ld(a.B, xr);
+            if constexpr (LUTSRC == 2) ld(a.in2, xa);
+        }
+    };
+    lut_load(0);
 
     // ---- device-side selection: (item gq, slot `sub` of a COMBINE item) -> output position and, for a live one, the expert's pointers.
     //      Everything here is wave-uniform: scalar loads of ids[slot] and of the bank's 16-byte entry, nothing else touches the id.
@@ -131,11 +181,18 @@ __global__ __launch_bounds__(EXPERTS_FT) void k_gemv_experts(ExpertsArgs a) {
         }
     };
     p_seek();
+    if constexpr (LUTSRC != 0) {      // wait for the activation registers alone (the empty asm reads them), THEN the ring: k_gemv_quad's `early`
+#pragma unroll
+        for (int i = 0; i < NB * 8; ++i) {
+            asm volatile("" :: "v"(xr[i]));
+            if constexpr (LUTSRC == 2) asm volatile("" :: "v"(xa[i]));
+        }
+    }
     issue(f0); issue(f1);
     if (RING == 4) { issue(f2); issue(f3); }
 
     // ---- 2. tables of the call's rows into LDS (k_gemv_quad, LUTSRC == 0), four rows' loads in flight before the first store ----------
-    {
+    if constexpr (LUTSRC == 0) {
         const uint4* img = reinterpret_cast<const uint4*>(a.qlut_lds);
         auto row_tab = [&](int r) { return lds + (size_t)r * row_u4; };
 #pragma unroll 1
@@ -184,8 +241,53 @@ __global__ __launch_bounds__(EXPERTS_FT) void k_gemv_experts(ExpertsArgs a) {
                 }
             }
         }
+        __syncthreads();
+    } else {
+        // ---- 2'. ... or built here, on the VALU while the fragments fly: batch by batch the pieces of tmac_lut_build.h on the lane's pair,
+        //      into the image section 3 reads -- tables 2p, 2p + 1 = the uint4 (j4 = p & 3) of unit p >> 2; ls / 2, lb / 2 per act group
+        auto lut_build = [&](int b) {
+            if constexpr (LUTSRC == 2) xf_gate_mul(a.xf_kind >> 8, xr, xa);      // x = gate(in) * in2, in the registers `in` arrived in
+#pragma unroll
+            for (int r = 0; r < NB; ++r) {
+                const int f = (b * NB + r) * FT + tid, fc = min(f, NPAIR - 1);
+                int row = 0;
+#pragma unroll
+                for (int j = 1; j < EXPERTS_MAX_SLOTS; ++j) row += fc >= j * PR ? 1 : 0;      // (fc < LR * PR: nothing counts behind LR - 1)
+                const int p = fc - row * PR;
+                const float* x = xr + r * 8;
+                float scales, t_scales, La, Lb;
+                lut_group_scale(LUT_X8(x), scales, t_scales);
+                const uint4 t = lut_tables2<true>(LUT_X8(x), t_scales, La, Lb);
+                const float v = lut_chunk_sum(La, Lb);
+                const float c1 = lut_group_partner(v);                  // (every lane of the act group takes part)
+                if (f < NPAIR) {                                        // NPAIR % 8 == 0: an act group stores or drops as a whole
+                    uint4* tab = lds + (size_t)row * row_u4;
+                    tab[(p & 3) * tstride + (p >> 2)] = t;
+                    if ((p & 7) == 0) {
+                        float* l_ls = reinterpret_cast<float*>(tab + 4 * tstride);
+                        l_ls[p >> 3] = __fmul_rn(0.5f, scales);
+                        l_ls[GP + (p >> 3)] = __fmul_rn(0.5f, lut_group_bias(v, c1));
+                    }
+                }
+            }
+        };
+        lut_build(0);
+#pragma unroll 1
+        for (int b = 1; b * (NB * FT) < NPAIR; ++b) {                   // the loads of these batches queue behind the ring
+            lut_load(b);
+            lut_build(b);
+        }
+#pragma unroll 1
+        for (int r = 0; r < LR; ++r) {                                  // zero tables for units >= nu, zero scales for groups >= G
+            uint4* tab = lds + (size_t)r * row_u4;
+            float* l_ls = reinterpret_cast<float*>(tab + 4 * tstride);
+            for (int u = nu + tid; u < nst * 64; u += FT)
+#pragma unroll
+                for (int j4 = 0; j4 < 4; ++j4) tab[j4 * tstride + u] = make_uint4(0u, 0u, 0u, 0u);
+            for (int i = G + tid; i < GP; i += FT) { l_ls[i] = 0.f; l_ls[GP + i] = 0.f; }
+        }
+        c_lds_barrier();              // LDS only: __syncthreads() carries vmcnt(0) and would drain the ring
     }
-    __syncthreads();
 
     // ---- 3. stream this wave's items ----------------------------------------------------------------------------------------------
     float cacc = 0.f;                 // the slot's partial of the lane's row
@@ -285,9 +387,11 @@ template <int BITS>
 hipError_t launch_gemv_experts_unit(const ExpertsArgs& a, const ExpertsPlan& p, int mode, hipStream_t st) {
     return sel_bool(a.s.zero_point != 0, [&](auto ZP) { return sel_bool(a.sc_f16 != 0, [&](auto SCF16) {
         return sel_int<EXPERTS_SLOTS, EXPERTS_COMBINE>(mode, [&](auto MODE) {
-            static_assert(experts_inst_exists(BITS, 0, MODE), "k_gemv_experts: per-group scales, SLOTS or COMBINE");
-            static size_t allowed = 0;      // per kernel: the largest footprint is allowed once
-            return launch_lds_once(allowed, ROWS_LDS_MAX, k_gemv_experts<BITS, ZP, SCF16, MODE>, dim3(p.gx), dim3(EXPERTS_FT), p.lds_bytes, st, a);
+            return sel_int<0, 1, 2>(a.lutsrc, [&](auto LUTSRC) {
+                static_assert(experts_inst_exists(BITS, 0, MODE, LUTSRC), "k_gemv_experts: per-group scales, SLOTS or COMBINE, tables copied or built");
+                static size_t allowed = 0;      // per kernel: the largest footprint is allowed once
+                return launch_lds_once(allowed, ROWS_LDS_MAX, k_gemv_experts<BITS, ZP, SCF16, MODE, LUTSRC>, dim3(p.gx), dim3(EXPERTS_FT), p.lds_bytes, st, a);
+            });
         });
     }); });
 }

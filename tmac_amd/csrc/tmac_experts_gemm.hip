@@ -19,8 +19,8 @@
 //   stores     C[b][P][Mw] straight from the accumulators (a lane holds 4 x 4 consecutive rows of one position per 32 x 32 tile): a live
 //              position its row, a padding position of a live tile +0.0, the rows of an unused tile nothing.
 // An output is one wave's chain in plain K order: its bits depend on its (expert, activation row) alone.
-// The unit is compiled without packed-fp32 instructions: q_table8 (tmac_lut_build.h) is restated below in single fp32 operations, each
-// rounded as its packed half is, and the fp32 chains are plain fmas.
+// The unit is compiled without packed-fp32 instructions: the LUT build takes q_table8_single (tmac_lut_build.h), q_table8
+// in single fp32 operations, and the fp32 chains are plain fmas.
 #include <hip/hip_runtime.h>
 #include <hip/hip_fp16.h>
 #include <stdint.h>
@@ -42,21 +42,6 @@ typedef float e4f_t __attribute__((ext_vector_type(4)));
 typedef float e16f_t __attribute__((ext_vector_type(16)));
 
 #if TMAC_EXPERTS_GEMM_BITS == 1      // the LUT build has no width: it lives in the first unit
-// q_table8<true> in single operations: the same adds in the same association, q = rne(L * t_scales) through the 1.5 * 2^23 magic add
-__device__ __forceinline__ void pos_table8(float x0, float x1, float x2, float x3, float t, uint32_t& lo, uint32_t& hi, float& L15) {
-    const float ap = __fadd_rn(x0, x1), am = __fsub_rn(x0, x1);
-    const float pm = __fsub_rn(ap, x2), mm = __fsub_rn(am, x2), pp = __fadd_rn(ap, x2), mp = __fadd_rn(am, x2);
-    const float L3 = __fsub_rn(pm, x3), L1 = __fsub_rn(mm, x3), L11 = __fadd_rn(pm, x3), L9 = __fadd_rn(mm, x3);
-    const float L7 = __fsub_rn(pp, x3), L5 = __fsub_rn(mp, x3), L13 = __fadd_rn(mp, x3);
-    L15 = __fadd_rn(pp, x3);
-    const float mg = 12582912.0f;
-    auto q = [&](float L) { return __float_as_uint(__fadd_rn(__fmul_rn(L, t), mg)) & 0xffu; };
-    auto qn = [&](float L) { return __float_as_uint(__fsub_rn(mg, __fmul_rn(L, t))) & 0xffu; };
-    // half table j = 0..7: {-L15, L1, -L13, L3, -L11, L5, -L9, L7}
-    lo = qn(L15) | (q(L1) << 8) | (qn(L13) << 16) | (q(L3) << 24);
-    hi = qn(L11) | (q(L5) << 8) | (qn(L9) << 16) | (q(L7) << 24);
-}
-
 template <bool F16>
 __global__ __launch_bounds__(256) void k_lut_image_pos(const void* __restrict__ x, const int32_t* __restrict__ src, int row_div, int x_rows,
                                                        uint4* __restrict__ bimg, float* __restrict__ colv, int K, int P) {
@@ -70,8 +55,8 @@ __global__ __launch_bounds__(256) void k_lut_image_pos(const void* __restrict__ 
     float scales, t_scales, La, Lb;
     lut_group_scale(LUT_X8(v8), scales, t_scales);
     uint4 t;
-    pos_table8(v8[0], v8[1], v8[2], v8[3], t_scales, t.x, t.y, La);
-    pos_table8(v8[4], v8[5], v8[6], v8[7], t_scales, t.z, t.w, Lb);
+    q_table8_single<true>(v8[0], v8[1], v8[2], v8[3], t_scales, t.x, t.y, La);
+    q_table8_single<true>(v8[4], v8[5], v8[6], v8[7], t_scales, t.z, t.w, Lb);
     if (!live) t = make_uint4(0u, 0u, 0u, 0u);
     bimg[(((size_t)kk * (P >> 6) + (n >> 6)) * 8 + p) * 64 + (n & 63)] = t;
     int h = 0;

@@ -316,8 +316,15 @@ struct ExpertsArgs {
     // filled by the launcher
     int nu, nst, tstride, G, nsg, gs_shift;   // tstride: of the IMAGE (the LDS copy uses nst * 64 + 1)
     int wpq;
+    // the tables built in the launch (lutsrc 1, 2: no image, no scales, no biases above; behind the fields the copy reads, so that its
+    // instantiations load what they always loaded)
+    int lutsrc;              // 0 copy the image | 1 build from B | 2 build from gate(B) * in2
+    const void* B;           // [lut_rows][K] activations, fp16 or fp32 (act_f16)
+    const void* in2;         // lutsrc 2: [lut_rows][K] in the dtype of B
+    int act_f16, xf_kind;    // xf_kind: the resolved kind, the gate in bits 8..15 as k_gemv_quad carries it (XF_GATE_*)
 };
-// plans the call (experts_plan), fills the derived fields, launches; hipErrorInvalidValue: the plan refuses, or a bank's matrices pass 2 GB
+// plans the call (experts_plan), fills the derived fields, launches the instantiation a.lutsrc names; hipErrorInvalidValue: the plan
+// refuses, or a bank's matrices pass 2 GB
 hipError_t launch_gemv_experts(const ExpertsArgs& a, hipStream_t st);
 // the launcher of one translation unit of tmac_experts.hip (defined and instantiated there for its BITS)
 template <int BITS>

@@ -106,13 +106,14 @@ struct RowsLaunch { int R, n_base, gx, gy; size_t lds_bytes; };
 struct RowsLaunchPlan { RowsPlan rows; int wpq; int nlaunch; RowsLaunch l[2]; };
 bool rows_launch_plan(const Shape& s, int N, int total_q, RowsLaunchPlan& p);
 
-// ---- k_gemv_experts<BITS, ZP, SCF16, MODE> (tmac_experts.hip) -----------------------------------------------------------------------
+// ---- k_gemv_experts<BITS, ZP, SCF16, MODE, LUTSRC> (tmac_experts.hip) ---------------------------------------------------------------
 // Top-k expert GEMVs with the expert ids read on the device: S slots, up to two banks of interchangeable matrices that share the ids.
 constexpr int EXPERTS_FT = 512, EXPERTS_NWV = EXPERTS_FT / 64, EXPERTS_MAX_SLOTS = 8, EXPERTS_MAX_BANKS = 2;
 enum ExpertsMode { EXPERTS_SLOTS = 0, EXPERTS_COMBINE = 1 };      // one output row per slot and bank | sum_s g[s] (W[ids[s]] x_s), one bank
-// every width, zero-point setting and scale dtype in both modes; per-group scales alone (sm: 0 per-group, 2 unified)
-constexpr bool experts_inst_exists(int bits, int sm, int mode) {
-    return bits >= 1 && bits <= 4 && sm == 0 && (mode == EXPERTS_SLOTS || mode == EXPERTS_COMBINE);
+// every width, zero-point setting and scale dtype in both modes; per-group scales alone (sm: 0 per-group, 2 unified); the tables copied
+// from the image (lutsrc 0), built in the launch from the activations (1) or from gate(in) * in2 (2)
+constexpr bool experts_inst_exists(int bits, int sm, int mode, int lutsrc = 0) {
+    return bits >= 1 && bits <= 4 && sm == 0 && (mode == EXPERTS_SLOTS || mode == EXPERTS_COMBINE) && lutsrc >= 0 && lutsrc <= 2;
 }
 // LDS of a workgroup that holds `rows` activation rows: per row what rows_lds_bytes counts per row, then the partials of the eight waves
 // [2 parities][8][4 rows]

@@ -153,13 +153,36 @@ __device__ __forceinline__ void q_table8(float x0, float x1, float x2, float x3,
     hi = __builtin_amdgcn_perm(__float_as_uint(zb.y), __float_as_uint(zc.x), 0x0c0c0400u) |
          __builtin_amdgcn_perm(__float_as_uint(zb.x), __float_as_uint(zc.y), 0x04000c0cu);
 }
+// q_table8 in single fp32 operations, for the units compiled without packed-fp32 instructions (k_gemv_experts, k_gemm_experts: the
+// assembler refuses v_pk_* there): the same adds in the same association, each rounded as its packed half is, q = rne(L * t_scales)
+// through the same magic add -- the same bits.
+template <bool SIGNED>
+__device__ __forceinline__ void q_table8_single(float x0, float x1, float x2, float x3, float t, uint32_t& lo, uint32_t& hi, float& L15) {
+    const float ap = __fadd_rn(x0, x1), am = __fsub_rn(x0, x1);
+    const float pm = __fsub_rn(ap, x2), mm = __fsub_rn(am, x2), pp = __fadd_rn(ap, x2), mp = __fadd_rn(am, x2);
+    const float L3 = __fsub_rn(pm, x3), L1 = __fsub_rn(mm, x3), L11 = __fadd_rn(pm, x3), L9 = __fadd_rn(mm, x3);
+    const float L7 = __fsub_rn(pp, x3), L5 = __fsub_rn(mp, x3), L13 = __fadd_rn(mp, x3);
+    L15 = __fadd_rn(pp, x3);
+    const float mg = SIGNED ? 12582912.0f : 12583040.0f;
+    auto q = [&](float L) { return __float_as_uint(__fadd_rn(__fmul_rn(L, t), mg)) & 0xffu; };
+    auto qn = [&](float L) { return __float_as_uint(__fsub_rn(mg, __fmul_rn(L, t))) & 0xffu; };
+    // half table j = 0..7: {-L15, L1, -L13, L3, -L11, L5, -L9, L7}
+    lo = qn(L15) | (q(L1) << 8) | (qn(L13) << 16) | (q(L3) << 24);
+    hi = qn(L11) | (q(L5) << 8) | (qn(L9) << 16) | (q(L7) << 24);
+}
 // The two tables of a pair: {lo, hi} of table 2p | {lo, hi} of table 2p + 1, signed bytes (SIGNED: what the MFMA forms look up) or
-// biased by 128; La, Lb = their L15.  As four words, or as the uint4 the images hold.
+// biased by 128; La, Lb = their L15.  As four words, or as the uint4 the images hold.  A unit built without packed-fp32 instructions
+// defines TMAC_LUT_SINGLE_F32 in front of this header and gets the single-operation form.
 template <bool SIGNED>
 __device__ __forceinline__ void lut_tables2_words(float x0, float x1, float x2, float x3, float x4, float x5, float x6, float x7,
                                                   float t_scales, uint32_t& lo0, uint32_t& hi0, uint32_t& lo1, uint32_t& hi1, float& La, float& Lb) {
+#if defined(TMAC_LUT_SINGLE_F32)
+    q_table8_single<SIGNED>(x0, x1, x2, x3, t_scales, lo0, hi0, La);
+    q_table8_single<SIGNED>(x4, x5, x6, x7, t_scales, lo1, hi1, Lb);
+#else
     q_table8<SIGNED>(x0, x1, x2, x3, t_scales, lo0, hi0, La);
     q_table8<SIGNED>(x4, x5, x6, x7, t_scales, lo1, hi1, Lb);
+#endif
 }
 template <bool SIGNED>
 __device__ __forceinline__ uint4 lut_tables2(float x0, float x1, float x2, float x3, float x4, float x5, float x6, float x7,

@@ -972,13 +972,16 @@ class TMACGeMMWrapper:
             rec.append((list(weights_list), B_dev, list(C_list)))
         check(B.lib().tmac_hip_qgemm_fused_dev(wa, n, _ptr(B_dev), act_dtype, ca, out_dtype, N, _stream(stream)))
 
-    def experts(self, banks, x, ids, gates=None, out=None, stream=None):
+    def experts(self, banks, x, ids, gates=None, out=None, stream=None, build="image", glu=None, in2=None):
         """The top-k expert GEMVs of one token, the experts picked on the GPU (tmac_hip_qgemm_experts_dev).  ``banks``: one or two
         :class:`ExpertBank` that share ``ids`` (gate / up); ``ids``: CUDA int32 [S], S <= 8, an id outside [0, E) (``-1``) marks an empty
         slot; ``x``: CUDA fp16 / fp32, [K] or [1, K] -- every slot reads it -- or [S, K] -- slot s reads row s.
         ``gates=None``: returns one [S, Mw] tensor per bank, row s = W[ids[s]] x_row(s) (an empty slot's row is zero).
         ``gates`` (CUDA fp32 [S]; one bank, x [S, K]): returns [Mw] = sum_s gates[s] (W[ids[s]] x_s), the ``down`` projection with the
-        router-weighted sum.  ``out``: the tensor(s) to write instead of new fp32 ones (fp16 or fp32).  Nothing is copied to the host."""
+        router-weighted sum.  ``out``: the tensor(s) to write instead of new fp32 ones (fp16 or fp32).  Nothing is copied to the host.
+        ``build``: "image" -- a pair-build launch into the stream's workspace, then the kernel -- or "kernel" -- the kernel builds its
+        tables itself (tmac_hip_qgemm_experts_fused_dev): one launch, no workspace, the same bits.  ``glu`` ("glu", "glu:relu2",
+        "glu:gelu"; implies build="kernel"): the tables of gate(x) * in2, ``in2`` [S, K] of x's dtype -- ``down`` fed gate_out and up_out."""
         import torch
         banks = list(banks) if isinstance(banks, (list, tuple)) else [banks]
         S = int(ids.numel())
@@ -986,6 +989,10 @@ class TMACGeMMWrapper:
             raise TypeError("ids must be a CUDA int32 tensor")
         if gates is not None and (gates.dtype != torch.float32 or not gates.is_cuda or int(gates.numel()) != S):
             raise TypeError("gates must be a CUDA float32 tensor with one value per slot")
+        if build not in ("image", "kernel"):
+            raise ValueError(f"build is 'image' or 'kernel', not {build!r}")
+        if in2 is not None and (in2.dtype != x.dtype or in2.shape != x.shape):
+            raise TypeError("in2 has the dtype and shape of x")
         lut_rows = 1 if x.dim() == 1 else int(x.shape[0])
         if out is None:
             out = [torch.empty((b.Mw,) if gates is not None else (S, b.Mw), dtype=torch.float32, device=x.device) for b in banks]
@@ -994,8 +1001,13 @@ class TMACGeMMWrapper:
             raise ValueError("one output per bank")
         ba = (C.c_void_p * len(banks))(*[b.handle.value for b in banks])
         ca = (C.c_void_p * len(banks))(*[_ptr(c) for c in outs])
-        check(B.lib().tmac_hip_qgemm_experts_dev(ba, len(banks), _ptr(x), _dtype_code(x), lut_rows, _ptr(ids), _ptr(gates), S, ca,
-                                                 _dtype_code(outs[0]), _stream(stream)))
+        if glu is not None or build == "kernel":
+            xf = self._xform(glu, in2, None, None, 0.0, None, False, none_ok=True)
+            check(B.lib().tmac_hip_qgemm_experts_fused_dev(ba, len(banks), _ptr(x), _dtype_code(x), lut_rows, C.byref(xf) if glu is not None else None,
+                                                           _ptr(ids), _ptr(gates), S, ca, _dtype_code(outs[0]), _stream(stream)))
+        else:
+            check(B.lib().tmac_hip_qgemm_experts_dev(ba, len(banks), _ptr(x), _dtype_code(x), lut_rows, _ptr(ids), _ptr(gates), S, ca,
+                                                     _dtype_code(outs[0]), _stream(stream)))
         return outs[0] if gates is not None else outs
 
     # ---- expert banks for N > 1 tokens: routing by expert and the gated sum over routed rows ---------------------

@@ -3,7 +3,11 @@
   (b) today's caller: ids copied to the host and waited for, then S plain fused calls per projection (+ torch multiply-adds for the
       gated sum); eager, wall clock per layer step -- the wait rules a graph out
   (c) the same S plain calls with the ids known in advance, no wait, graph replay: the bound a host-routed caller cannot beat
-Rounds alternate the three columns; a column's figure is its best round, us per call group.  usage: bench_experts.py [rounds]"""
+  (a') the experts call with its tables built in the launch (build="kernel": tmac_hip_qgemm_experts_fused_dev), graph replay
+Rounds alternate the columns; a column's figure is its best round, us per call group, with the spread of its rounds behind it.
+A last row per shape is the whole layer step for one token, graph replay: today's five launches (pair build, gate + up, a torch silu(g) * u,
+pair build, down with the gated sum) against the two fused calls (gate + up from x; down from silu(G) * U with the gated sum).
+usage: bench_experts.py [rounds]"""
 import os, sys, time
 import torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -49,7 +53,12 @@ def eager_us(fn, reps=50):
     return (time.perf_counter() - t0) * 1e6 / reps
 
 
-print("us per call group, best of", ROUNDS, "alternating rounds: (a) experts call | (b) host-routed with the wait | (c) host-routed, ids known; a/c")
+def col(v):
+    return f"{min(v):7.1f} ({min(v):.1f}-{max(v):.1f})"
+
+
+print("us per call group, best of", ROUNDS, "alternating rounds (spread): (a) experts call | (a') tables built in the launch | (b) host-routed with the "
+      "wait | (c) host-routed, ids known; a/c, a'/a, a'/c")
 for name, E, S, H, F, bits in [("mixtral W2", 8, 2, 4096, 14336, 2), ("mixtral W4", 8, 2, 4096, 14336, 4), ("qwen-moe W4", 60, 4, 2048, 1408, 4)]:
     gate, up, down = experts(E, F, H, bits), experts(E, F, H, bits), experts(E, H, F, bits)
     bg, bu, bd = (tmac_amd.ExpertBank.from_handles(w) for w in (gate, up, down))
@@ -72,14 +81,33 @@ for name, E, S, H, F, bits in [("mixtral W2", 8, 2, 4096, 14336, 2), ("mixtral W
         torch.mv(ys.t(), gates_h, out=od)            # the gated sum as a torch kernel
 
     cols = {"gate_up": [lambda st: wr.experts([bg, bu], x, ids, out=[og, ou], stream=st), lambda: gu_plain(ids.tolist()),
-                        lambda st: gu_plain(known, st)],
+                        lambda st: gu_plain(known, st), lambda st: wr.experts([bg, bu], x, ids, out=[og, ou], stream=st, build="kernel")],
             "down": [lambda st: wr.experts(bd, h, ids, gates=gates, out=od, stream=st), lambda: down_plain(ids.tolist()),
-                     lambda st: down_plain(known, st)]}      # (graph_us makes `st` the current stream: the torch kernel follows)
-    for proj, (fa, fb, fc) in cols.items():
-        best = [1e9, 1e9, 1e9]
+                     lambda st: down_plain(known, st),      # (graph_us makes `st` the current stream: the torch kernel follows)
+                     lambda st: wr.experts(bd, h, ids, gates=gates, out=od, stream=st, build="kernel")]}
+    for proj, (fa, fb, fc, fk) in cols.items():
+        r = [[], [], [], []]
         for _ in range(ROUNDS):
-            best = [min(best[0], graph_us(fa)), min(best[1], eager_us(fb)), min(best[2], graph_us(fc))]
-        print(f"{name:12s} {proj:8s} S={S} E={E}: (a) {best[0]:7.1f} | (b) {best[1]:7.1f} | (c) {best[2]:7.1f}   a/c {best[0] / best[2]:.2f}", flush=True)
+            for v, t in zip(r, (graph_us(fa), eager_us(fb), graph_us(fc), graph_us(fk))):
+                v.append(t)
+        a, b, c, k = (min(v) for v in r)
+        print(f"{name:12s} {proj:8s} S={S} E={E}: (a) {col(r[0])} | (a') {col(r[3])} | (b) {col(r[1])} | (c) {col(r[2])}   a/c {a / c:.2f}  a'/a {k / a:.2f}  "
+              f"a'/c {k / c:.2f}", flush=True)
+
+    hb = torch.empty(S, F, dtype=torch.float16, device=dev)
+
+    def layer5(st):
+        wr.experts([bg, bu], x, ids, out=[og, ou], stream=st)
+        torch.mul(torch.nn.functional.silu(og), ou, out=hb)
+        wr.experts(bd, hb, ids, gates=gates, out=od, stream=st)
+
+    def layer2(st):
+        wr.experts([bg, bu], x, ids, out=[og, ou], stream=st, build="kernel")
+        wr.experts(bd, og, ids, gates=gates, out=od, stream=st, glu="glu", in2=ou)
+    r = [[], []]
+    for _ in range(ROUNDS):
+        r[0].append(graph_us(layer5)); r[1].append(graph_us(layer2))
+    print(f"{name:12s} layer    S={S} E={E}: five launches {col(r[0])} | two fused launches {col(r[1])}   fused / five {min(r[1]) / min(r[0]):.2f}", flush=True)
     for b in (bg, bu, bd):
         b.free()
     for w in gate + up + down:
