@@ -161,7 +161,10 @@ size_t tmac_hip_weights_bytes(const tmac_hip_weights* w);
  * output is written, nothing outside the inputs' extents is read (tests/test_gpu_pack.py holds them to both).
  * tmac_hip_register_weights_*_dev pack into temporaries of their own and hand them to the registration above: every layout variant
  * (tmac_hip_set_variant), fast-aggregation mode and the kept-reference case behave as there, and the handle is the one registration from
- * the host blob gives.  They allocate and synchronise the stream, like registration.
+ * the host blob gives.  They allocate and synchronise the stream, like registration.  Like every register door of the formats below they
+ * are ordered behind the calling thread's deferred queue too (the tensors may have been written by queued work): they flush it first,
+ * after every argument check -- a refused call leaves it alone --, and a failed flush returns its status and launches nothing.  A
+ * dev_float other than TMAC_F32 / TMAC_F16 is TMAC_HIP_E_ARG, "dev_float must be TMAC_F32 or TMAC_F16": the last argument check.
  * While a chain is being recorded all four run at once and are not recorded, as registration does.  None of them is for use inside a
  * stream capture. */
 int32_t tmac_hip_ref_blob_bytes(int Mw, int K, int bits, const tmac_kcfg* cfg, tmac_dtype_t ref_float, size_t* a_bytes, size_t* s_bytes);
@@ -222,7 +225,8 @@ int32_t tmac_hip_register_weights_awq_dev(tmac_hip_weights** out, const void* qw
  * Scope: bits = 2, unified scales (cfg->m_groups >= 1, Mw a multiple of it), whatever else registration accepts for such a configuration.
  * Refusals, nothing launched and nothing written.  TMAC_HIP_E_ARG naming the argument: a NULL pointer (scales_in_dev excepted) or one below
  * 16-byte alignment; an unknown src_dtype; eps not finite or <= 0; m_groups < 1 (per-group scales: register codes or GPTQ tensors);
- * Mw % m_groups.  Shape refusals are registration's own codes and messages, as in tmac_hip_pack_codes_dev.
+ * Mw % m_groups; host_float / dev_float other than TMAC_F32 / TMAC_F16 (dev_float: the last argument check, as at every register door).
+ * Shape refusals are registration's own codes and messages, as in tmac_hip_pack_codes_dev.
  * All three are ordered behind the calling thread's deferred queue: they flush it first, a refused call leaves it alone, a failed flush
  * returns its status and launches nothing.  The reduction needs scratch (8 bytes per 16384 masters), allocated and freed by the call: with
  * a computed scale a call waits for `stream` before it returns; with scales_in_dev the pack allocates nothing and is asynchronous. */
@@ -513,7 +517,8 @@ int32_t tmac_hip_debug_experts_gemm_plan(int K, int bits, int group_size, const 
  * flushes the queue first, unconditionally (no overlap analysis: none of them is a hot path) -- tmac_hip_preprocessor_dev,
  * tmac_hip_qgemm_dev, tmac_hip_qgemm_partial_sums, tmac_hip_qgemm_fused_partial_sums, tmac_hip_chain_launch, tmac_hip_workspace_read /
  * _write, tmac_hip_debug_gemm_comb_sums / _gemm_image_read, tmac_hip_autotune_fused, tmac_hip_pack_gptq_dev / _pack_codes_dev (they write the
- * caller's blob buffers; a refused one leaves the queue alone), tmac_hip_absmean_dev / _pack_absmean_dev /
+ * caller's blob buffers; a refused one leaves the queue alone), tmac_hip_register_weights_gptq_dev / _codes_dev, the _perm_ twins and the
+ * AWQ pair (the same: their tensors may be a queued call's output), tmac_hip_absmean_dev / _pack_absmean_dev /
  * _register_weights_absmean_dev (the same), tmac_hip_pack_ternary_dev / _register_weights_ternary_dev (the same), tmac_hip_rtn_params_dev / _pack_rtn_dev /
  * _register_weights_rtn_dev (the same), and tmac_hip_free_weights, tmac_hip_chain_free and
  * tmac_hip_cache_clear (a queued call may name what they release).  When that flush fails the entry point returns its status and launches

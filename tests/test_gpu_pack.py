@@ -355,6 +355,67 @@ def test_pack_flushes_the_deferred_queue_first(tm):
     w.free()
 
 
+def test_register_flushes_the_deferred_queue_first(tm):
+    """register_gptq and register_codes go behind the queue like the pack calls: the flush happens AT the call, the handle is the one
+    registered outside deferred mode, and a refused call leaves the queue as it was"""
+    import torch
+    Mw, K, bits, ags = 128, 256, 2, 64
+    wr = tm.TMACGeMMWrapper(act_group_size=ags)
+    (qw, sc, qz), _, cfg = small_matrix(tm, wr, 21)
+    _, _, (cd, csc, czr, _, _) = pc.host_blob_gptq(qw, sc, qz, True, 128, 16)
+    dq, ds, dz = (torch.from_numpy(a).cuda() for a in (qw, sc, qz))
+    dcd, dcs, dcz = (torch.from_numpy(np.ascontiguousarray(a)).cuda() for a in (cd, csc.astype(np.float16), czr.astype(np.float16)))
+    doors = {"gptq": lambda: wr.register_gptq(dq, ds, dz, cfg, True, tm.F32), "codes": lambda: wr.register_codes(dcd, dcs, dcz, bits, cfg, tm.F32)}
+    w = doors["gptq"]()
+    xs = [torch.from_numpy(np.random.default_rng(i).standard_normal(K).astype(np.float32)).cuda() for i in range(2)]
+
+    def run(h, x):
+        o = torch.zeros(Mw, dtype=torch.float32, device="cuda")
+        wr.fused([h], x, [o], 1)
+        return o
+    want = [run(w, x) for x in xs]
+    eager = {}
+    for name, door in doors.items():                             # the handles registered outside deferred mode
+        h = door()
+        eager[name] = run(h, xs[0])
+        torch.cuda.synchronize()
+        h.free()
+    for name, door in doors.items():
+        tm.binding.check(tm.lib().tmac_hip_defer(1))
+        outs = [run(w, x) for x in xs]                           # (queued)
+        before = defer_stats(tm)
+        h = door()
+        after = defer_stats(tm)
+        assert after[0] == before[0] + 1, (name, before, after)  # the flush happened AT the register call
+        tm.binding.check(tm.lib().tmac_hip_flush(None))
+        assert defer_stats(tm)[0] == after[0], "nothing was left to flush"
+        got = run(h, xs[0])
+        tm.binding.check(tm.lib().tmac_hip_defer(0))
+        torch.cuda.synchronize()
+        for o, r in zip(outs, want):
+            assert float((o - r).abs().max()) <= 1e-3 * float(r.abs().max()), name
+        assert torch.equal(got, eager[name]), name
+        h.free()
+    # a refused call (qweight 8 bytes off the alignment rule) leaves the queue alone: no flush at the call, the two calls still queued after it
+    off = torch.zeros(dq.numel() + 2, dtype=torch.int32, device="cuda")[2:].view(dq.shape)
+    off.copy_(dq)
+    torch.cuda.synchronize()
+    tm.binding.check(tm.lib().tmac_hip_defer(1))
+    outs = [run(w, x) for x in xs]
+    before = defer_stats(tm)
+    with pytest.raises(tm.TMACHipError, match="qweight is not 16-byte aligned"):
+        wr.register_gptq(off, ds, dz, cfg, True, tm.F32)
+    assert defer_stats(tm) == before
+    tm.binding.check(tm.lib().tmac_hip_flush(None))
+    after = defer_stats(tm)
+    assert after[0] == before[0] + 1 and after[2] + after[3] > before[2] + before[3], "the queued calls were still there to launch"
+    tm.binding.check(tm.lib().tmac_hip_defer(0))
+    torch.cuda.synchronize()
+    for o, r in zip(outs, want):
+        assert float((o - r).abs().max()) <= 1e-3 * float(r.abs().max())
+    w.free()
+
+
 def test_registration_inside_a_recording_is_not_recorded(tm):
     import torch
     Mw, K, bits, ags = 128, 256, 2, 64

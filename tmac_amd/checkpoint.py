@@ -95,24 +95,88 @@ def safetensors_index(path: str) -> Dict[str, TensorRef]:
             raise RuntimeError("{}: corrupt safetensors header ({})".format(path, e))
 
 
+def _index_parts(model_dir: str, is_layer, fmt: str) -> Tuple[Dict[str, TensorRef], List[str]]:
+    """(index, order) of a checkpoint directory: {tensor name: TensorRef} over its ``model*.safetensors`` parts in sorted order (a later
+    part wins a name that comes twice), and the names ``is_layer(name, ref)`` accepts, in order of first appearance.  fmt: the format the
+    refusal of a directory without parts names (RuntimeError)."""
+    parts = sorted(f for f in os.listdir(model_dir) if f.startswith("model") and f.endswith(".safetensors"))
+    if not parts:
+        raise RuntimeError("Models in {} not in {} format (torch .bin checkpoints: convert them to safetensors first)".format(model_dir, fmt))
+    index: Dict[str, TensorRef] = {}
+    order: List[str] = []
+    for part in parts:
+        for name, ref in safetensors_index(os.path.join(model_dir, part)).items():
+            if name not in index and is_layer(name, ref):
+                order.append(name)
+            index[name] = ref
+    return index, order
+
+
+_FLOATS = ("F32", "F16", "BF16")
+
+
+def _check_ref(name: str, ref: TensorRef, dtypes, shape_ok: bool, wanted: Optional[str] = None) -> None:
+    """Refused (RuntimeError naming the tensor), in this order: another element type than ``dtypes``; a shape the caller found wrong
+    (``shape_ok``), in the words of ``wanted`` where it has any; byte ranges that do not match the shape."""
+    if ref.dtype not in dtypes:
+        raise RuntimeError("{} has dtype {}: {} expected".format(name, ref.dtype, " or ".join(filter(None, (", ".join(dtypes[:-1]), dtypes[-1])))))
+    if not shape_ok and wanted:
+        raise RuntimeError("{} has shape {}: {}".format(name, ref.shape, wanted))
+    if not shape_ok or (ref.end - ref.begin) != int(np.prod(ref.shape)) * np.dtype(_NP[ref.dtype]).itemsize:
+        raise RuntimeError("{}: shape {} does not match its {} bytes".format(name, ref.shape, ref.end - ref.begin))
+
+
 def _bias_ref(index: Dict[str, TensorRef], base: str, Mw: int) -> Optional[TensorRef]:
     """``<base>.bias`` of a layer with Mw output rows, or None where the checkpoint has none.  Refused (RuntimeError naming the tensor):
     another element type than F32 / F16 / BF16, another shape than [Mw], byte ranges that do not match the shape."""
     ref = index.get(base + ".bias")
-    if ref is None:
-        return None
-    if ref.dtype not in ("F32", "F16", "BF16"):
-        raise RuntimeError("{}.bias has dtype {}: F32, F16 or BF16 expected".format(base, ref.dtype))
-    if ref.shape != (Mw,):
-        raise RuntimeError("{}.bias has shape {}: [{}] expected (one value per output row)".format(base, ref.shape, Mw))
-    if (ref.end - ref.begin) != Mw * np.dtype(_NP[ref.dtype]).itemsize:
-        raise RuntimeError("{}.bias: shape {} does not match its {} bytes".format(base, ref.shape, ref.end - ref.begin))
+    if ref is not None:
+        _check_ref(base + ".bias", ref, _FLOATS, ref.shape == (Mw,), "[{}] expected (one value per output row)".format(Mw))
     return ref
 
 
 def _refuse_bias(index: Dict[str, TensorRef], base: str, why: str) -> None:
     if base + ".bias" in index:
         raise RuntimeError("{} comes with {}.bias: {}".format(base, base, why))
+
+
+def _triple(index: Dict[str, TensorRef], qname: str) -> Tuple[str, TensorRef, TensorRef, TensorRef]:
+    """(layer name, qweight, scales, qzeros) of ``<layer>.qweight``, as GPTQ and AWQ store a layer.  Refused (RuntimeError naming the
+    tensor): scales or qzeros missing, another element type than I32 (qweight, qzeros) / F16 or F32 (scales), a tensor that is not 2-D
+    or whose byte range does not match its shape."""
+    base = qname[:-len(".qweight")]
+    qw, sc, qz = index[qname], index.get(base + ".scales"), index.get(base + ".qzeros")
+    if sc is None:
+        raise RuntimeError("{}.scales is missing".format(base))
+    if qz is None:
+        raise RuntimeError("{}.qzeros is missing".format(base))
+    for ref, suffix, ok in ((qw, ".qweight", ("I32",)), (qz, ".qzeros", ("I32",)), (sc, ".scales", ("F16", "F32"))):
+        _check_ref(base + suffix, ref, ok, len(ref.shape) == 2)
+    return base, qw, sc, qz
+
+
+_MASTER_LAYER = re.compile(r"^model\.layers\..*_proj\.weight$")
+_NO_BIAS = "unified-scale (BitNet) handles take no bias (it would be dropped)"
+
+
+def _master_layers(model_dir: str, not_what: str, bias: bool) -> List[Tuple[str, TensorRef, Optional[TensorRef]]]:
+    """[(layer name, weight, bias)] of a checkpoint of floating matrices: every tensor named ``model.layers.*_proj.weight``, in order of
+    first appearance.  Refused (RuntimeError naming the tensor): a sibling ``.weight_scale`` (a pre-packed ternary checkpoint, not
+    ``not_what``), another element type than F32 / F16 / BF16, a shape that is not 2-D, byte ranges that do not match the shape, a
+    directory without any layer.  bias: a layer's ``.bias`` is found and checked (``_bias_ref``); without it, one is refused."""
+    index, order = _index_parts(model_dir, lambda name, ref: _MASTER_LAYER.match(name), "safetensors")
+    layers = []
+    for wname in order:
+        ref, base = index[wname], wname[:-len(".weight")]
+        if wname + "_scale" in index:
+            raise RuntimeError("{} comes with {}_scale: a pre-packed ternary checkpoint, not {}".format(wname, wname, not_what))
+        if not bias:
+            _refuse_bias(index, base, _NO_BIAS)
+        _check_ref(wname, ref, _FLOATS, len(ref.shape) == 2, "a 2-D tensor expected")
+        layers.append((base, ref, _bias_ref(index, base, ref.shape[0]) if bias else None))
+    if not layers:
+        raise RuntimeError("Models in {} hold no model.layers.*_proj.weight tensor".format(model_dir))
+    return layers
 
 
 def gptq_is_v2(qc: dict) -> bool:
@@ -131,29 +195,10 @@ def scan_gptq_dir(model_dir: str, act_order: bool = False) -> GptqScan:
     if str(qc.get("quant_method", "")).lower() == "awq":
         raise RuntimeError("Models in {} are AWQ checkpoints (config.json: quantization_config.quant_method is \"awq\"), not GPTQ: AWQ packs along the "
                            "output axis: use load_awq_dir".format(model_dir))
-    parts = sorted(f for f in os.listdir(model_dir) if f.startswith("model") and f.endswith(".safetensors"))
-    if not parts:
-        raise RuntimeError("Models in {} not in GPTQ safetensors format (torch .bin checkpoints: convert them to safetensors first)".format(model_dir))
-    index: Dict[str, TensorRef] = {}
-    order: List[str] = []
-    for part in parts:
-        for name, ref in safetensors_index(os.path.join(model_dir, part)).items():
-            index[name] = ref
-            if name.endswith(".qweight"):
-                order.append(name)
+    index, order = _index_parts(model_dir, lambda name, ref: name.endswith(".qweight"), "GPTQ safetensors")
     layers = []
     for qname in order:
-        base = qname[:-len(".qweight")]
-        qw, sc, qz = index[qname], index.get(base + ".scales"), index.get(base + ".qzeros")
-        if sc is None:
-            raise RuntimeError("{}.scales is missing".format(base))
-        if qz is None:
-            raise RuntimeError("{}.qzeros is missing".format(base))
-        for ref, suffix, ok in ((qw, ".qweight", ("I32",)), (qz, ".qzeros", ("I32",)), (sc, ".scales", ("F16", "F32"))):
-            if ref.dtype not in ok:
-                raise RuntimeError("{}{} has dtype {}: {} expected".format(base, suffix, ref.dtype, " or ".join(ok)))
-            if len(ref.shape) != 2 or (ref.end - ref.begin) != int(np.prod(ref.shape)) * np.dtype(_NP[ref.dtype]).itemsize:
-                raise RuntimeError("{}{}: shape {} does not match its {} bytes".format(base, suffix, ref.shape, ref.end - ref.begin))
+        base, qw, sc, qz = _triple(index, qname)
         if qz.shape[1] <= 0 or sc.shape[0] <= 0 or sc.shape[1] < qz.shape[1] or sc.shape[0] != qz.shape[0] or sc.shape[1] != qw.shape[1]:
             raise RuntimeError("{}: qweight {} / scales {} / qzeros {} are not GPTQ-packed shapes".format(qname, qw.shape, sc.shape, qz.shape))
         bits = 32 // (sc.shape[1] // qz.shape[1])                      # convert.parse_gptq on shapes alone
@@ -222,9 +267,6 @@ class BitnetScan(NamedTuple):
     weight_bits: int
 
 
-_BITNET_LAYER = re.compile(r"^model\.layers\..*_proj\.weight$")
-
-
 def scan_bitnet_dir(model_dir: str) -> BitnetScan:
     """The linear layers of a BitNet b1.58 checkpoint of MASTER weights (``1bitLLM/bitnet_b1_58-3B``: fp16, bf16 or fp32 tensors, the
     ternary levels come from the absmean rule at load time), without loading a tensor.  ``config.json`` must carry a non-zero
@@ -235,32 +277,8 @@ def scan_bitnet_dir(model_dir: str) -> BitnetScan:
     qc = convert.get_quantization_config(model_dir)
     if not qc["weight_bits"]:
         raise RuntimeError("Models in {} not in BitNet format (config.json carries no weight_bits)".format(model_dir))
-    parts = sorted(f for f in os.listdir(model_dir) if f.startswith("model") and f.endswith(".safetensors"))
-    if not parts:
-        raise RuntimeError("Models in {} not in safetensors format (torch .bin checkpoints: convert them to safetensors first)".format(model_dir))
-    index: Dict[str, TensorRef] = {}
-    order: List[str] = []
-    for part in parts:
-        for name, ref in safetensors_index(os.path.join(model_dir, part)).items():
-            if name not in index and _BITNET_LAYER.match(name):
-                order.append(name)
-            index[name] = ref
-    layers = []
-    for wname in order:
-        ref = index[wname]
-        if wname + "_scale" in index:
-            raise RuntimeError("{} comes with {}_scale: a pre-packed ternary checkpoint, not master weights".format(wname, wname))
-        _refuse_bias(index, wname[:-len(".weight")], "unified-scale (BitNet) handles take no bias (it would be dropped)")
-        if ref.dtype not in ("F32", "F16", "BF16"):
-            raise RuntimeError("{} has dtype {}: F32, F16 or BF16 expected".format(wname, ref.dtype))
-        if len(ref.shape) != 2:
-            raise RuntimeError("{} has shape {}: a 2-D tensor expected".format(wname, ref.shape))
-        if (ref.end - ref.begin) != int(np.prod(ref.shape)) * np.dtype(_NP[ref.dtype]).itemsize:
-            raise RuntimeError("{}: shape {} does not match its {} bytes".format(wname, ref.shape, ref.end - ref.begin))
-        layers.append(BitnetLayer(wname[:-len(".weight")], ref, ref.shape[0], ref.shape[1]))
-    if not layers:
-        raise RuntimeError("Models in {} hold no model.layers.*_proj.weight tensor".format(model_dir))
-    return BitnetScan(layers, int(qc["weight_bits"]))
+    layers = _master_layers(model_dir, "master weights", bias=False)
+    return BitnetScan([BitnetLayer(name, ref, ref.shape[0], ref.shape[1]) for name, ref, _ in layers], int(qc["weight_bits"]))
 
 
 def load_bitnet_dir(model_dir: str, wrapper, dev_dtype=F32, eps: float = 1e-5) -> Dict[str, "object"]:
@@ -307,16 +325,7 @@ def scan_bitnet_packed_dir(model_dir: str) -> BitnetPackedScan:
     linear_class = qc.get("linear_class", "bitlinear")
     if linear_class not in convert.BITNET_LINEAR_CLASSES:
         raise RuntimeError("quantization_config.linear_class is {!r}: \"bitlinear\" or \"autobitlinear\" expected".format(linear_class))
-    parts = sorted(f for f in os.listdir(model_dir) if f.startswith("model") and f.endswith(".safetensors"))
-    if not parts:
-        raise RuntimeError("Models in {} not in safetensors format (torch .bin checkpoints: convert them to safetensors first)".format(model_dir))
-    index: Dict[str, TensorRef] = {}
-    order: List[str] = []
-    for part in parts:
-        for name, ref in safetensors_index(os.path.join(model_dir, part)).items():
-            if name not in index and name.endswith(".weight") and ref.dtype == "U8":
-                order.append(name)
-            index[name] = ref
+    index, order = _index_parts(model_dir, lambda name, ref: name.endswith(".weight") and ref.dtype == "U8", "safetensors")
     layers = []
     for wname in order:
         ref, sc = index[wname], index.get(wname + "_scale")
@@ -325,11 +334,8 @@ def scan_bitnet_packed_dir(model_dir: str) -> BitnetPackedScan:
         if sc.dtype not in ("BF16", "F16", "F32") or int(np.prod(sc.shape)) != 1 or len(sc.shape) > 1 or \
                 (sc.end - sc.begin) != np.dtype(_NP[sc.dtype]).itemsize:
             raise RuntimeError("{}_scale has dtype {} and shape {}: one element of BF16, F16 or F32 expected".format(wname, sc.dtype, sc.shape))
-        _refuse_bias(index, wname[:-len(".weight")], "unified-scale (BitNet) handles take no bias (it would be dropped)")
-        if len(ref.shape) != 2:
-            raise RuntimeError("{} has shape {}: a 2-D tensor expected".format(wname, ref.shape))
-        if (ref.end - ref.begin) != int(np.prod(ref.shape)):
-            raise RuntimeError("{}: shape {} does not match its {} bytes".format(wname, ref.shape, ref.end - ref.begin))
+        _refuse_bias(index, wname[:-len(".weight")], _NO_BIAS)
+        _check_ref(wname, ref, ("U8",), len(ref.shape) == 2, "a 2-D tensor expected")
         layers.append(BitnetPackedLayer(wname[:-len(".weight")], ref, sc, 4 * ref.shape[0], ref.shape[1]))
     if not layers:
         raise RuntimeError("Models in {} hold no packed ternary layer (a U8 *.weight with a .weight_scale)".format(model_dir))
@@ -389,31 +395,7 @@ def scan_dense_dir(model_dir: str) -> DenseScan:
             method, ": use {}".format(use) if use else ""))
     if hp.get("weight_bits", 0):
         raise RuntimeError("config.json carries weight_bits = {}: BitNet master weights take the absmean rule: use load_bitnet_dir".format(hp["weight_bits"]))
-    parts = sorted(f for f in os.listdir(model_dir) if f.startswith("model") and f.endswith(".safetensors"))
-    if not parts:
-        raise RuntimeError("Models in {} not in safetensors format (torch .bin checkpoints: convert them to safetensors first)".format(model_dir))
-    index: Dict[str, TensorRef] = {}
-    order: List[str] = []
-    for part in parts:
-        for name, ref in safetensors_index(os.path.join(model_dir, part)).items():
-            if name not in index and _BITNET_LAYER.match(name):
-                order.append(name)
-            index[name] = ref
-    layers = []
-    for wname in order:
-        ref = index[wname]
-        if wname + "_scale" in index:
-            raise RuntimeError("{} comes with {}_scale: a pre-packed ternary checkpoint, not dense weights".format(wname, wname))
-        if ref.dtype not in ("F32", "F16", "BF16"):
-            raise RuntimeError("{} has dtype {}: F32, F16 or BF16 expected".format(wname, ref.dtype))
-        if len(ref.shape) != 2:
-            raise RuntimeError("{} has shape {}: a 2-D tensor expected".format(wname, ref.shape))
-        if (ref.end - ref.begin) != int(np.prod(ref.shape)) * np.dtype(_NP[ref.dtype]).itemsize:
-            raise RuntimeError("{}: shape {} does not match its {} bytes".format(wname, ref.shape, ref.end - ref.begin))
-        layers.append(DenseLayer(wname[:-len(".weight")], ref, ref.shape[0], ref.shape[1], _bias_ref(index, wname[:-len(".weight")], ref.shape[0])))
-    if not layers:
-        raise RuntimeError("Models in {} hold no model.layers.*_proj.weight tensor".format(model_dir))
-    return DenseScan(layers)
+    return DenseScan([DenseLayer(name, ref, ref.shape[0], ref.shape[1], bias) for name, ref, bias in _master_layers(model_dir, "dense weights", bias=True)])
 
 
 def load_dense_dir(model_dir: str, wrapper, bits: int, group_size: int = 128, zero_point: bool = True, dev_dtype=F16) -> Dict[str, "object"]:
@@ -468,30 +450,11 @@ def scan_awq_dir(model_dir: str) -> AwqScan:
         raise RuntimeError("quantization_config.bits is {}: AWQ is served at 4 bits".format(qc.get("bits")))
     if not qc.get("zero_point", True):
         raise RuntimeError("quantization_config.zero_point is false: symmetric AWQ is not served")
-    parts = sorted(f for f in os.listdir(model_dir) if f.startswith("model") and f.endswith(".safetensors"))
-    if not parts:
-        raise RuntimeError("Models in {} not in AWQ safetensors format (torch .bin checkpoints: convert them to safetensors first)".format(model_dir))
-    index: Dict[str, TensorRef] = {}
-    order: List[str] = []
-    for part in parts:
-        for name, ref in safetensors_index(os.path.join(model_dir, part)).items():
-            if name not in index and name.endswith(".qweight"):
-                order.append(name)
-            index[name] = ref
+    index, order = _index_parts(model_dir, lambda name, ref: name.endswith(".qweight"), "AWQ safetensors")
     gs_cfg = int(qc.get("group_size", 128))
     layers = []
     for qname in order:
-        base = qname[:-len(".qweight")]
-        qw, sc, qz = index[qname], index.get(base + ".scales"), index.get(base + ".qzeros")
-        if sc is None:
-            raise RuntimeError("{}.scales is missing".format(base))
-        if qz is None:
-            raise RuntimeError("{}.qzeros is missing".format(base))
-        for ref, suffix, ok in ((qw, ".qweight", ("I32",)), (qz, ".qzeros", ("I32",)), (sc, ".scales", ("F16", "F32"))):
-            if ref.dtype not in ok:
-                raise RuntimeError("{}{} has dtype {}: {} expected".format(base, suffix, ref.dtype, " or ".join(ok)))
-            if len(ref.shape) != 2 or (ref.end - ref.begin) != int(np.prod(ref.shape)) * np.dtype(_NP[ref.dtype]).itemsize:
-                raise RuntimeError("{}{}: shape {} does not match its {} bytes".format(base, suffix, ref.shape, ref.end - ref.begin))
+        base, qw, sc, qz = _triple(index, qname)
         K, Mw = qw.shape[0], sc.shape[1]
         if K <= 0 or Mw <= 0 or qw.shape[1] * 8 != Mw or sc.shape[0] <= 0 or K % sc.shape[0] or qz.shape != (sc.shape[0], qw.shape[1]):
             raise RuntimeError("{}: qweight {} / scales {} / qzeros {} are not AWQ GEMM shapes ([K][Mw/8], [K/gs][Mw], [K/gs][Mw/8])".format(

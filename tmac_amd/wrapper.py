@@ -169,6 +169,11 @@ def _kperm(g_idx, group_size: int, stream=None) -> Optional[KPerm]:
     return None if kp.identity else kp
 
 
+def _door(name: str, kp: Optional[KPerm]):
+    """(entry point, the arguments its ``perm`` adds) of ``tmac_hip_<name>_dev``: the ``_perm_`` twin where a KPerm permutes"""
+    return (getattr(B.lib(), f"tmac_hip_{name}_dev"), ()) if kp is None else (getattr(B.lib(), f"tmac_hip_{name}_perm_dev"), (kp.handle,))
+
+
 def pack_gptq(qweight, scales, qzeros, cfg: Optional[KCfg] = None, gptq_v2: bool = True, ref_dtype=F32, act_group_size: int = 64, stream=None,
               g_idx=None):
     """GPTQ tensors -> the reference blob, on the GPU (tmac_hip_pack_gptq_dev): (A_ref uint8, scales_ref) as flat CUDA tensors, exactly
@@ -177,13 +182,9 @@ def pack_gptq(qweight, scales, qzeros, cfg: Optional[KCfg] = None, gptq_v2: bool
     of the matrix with its columns in group order, ``w[:, perm]`` (tmac_hip_pack_gptq_perm_dev)."""
     qw, sc, qz, Mw, K, bits, cfg = _gptq_args(qweight, scales, qzeros, cfg, act_group_size)
     A, S = _blob_buffers(Mw, K, bits, cfg, ref_dtype)
-    kp = _kperm(g_idx, cfg.group_size, stream)
-    if kp is not None:
-        check(B.lib().tmac_hip_pack_gptq_perm_dev(_ptr(qw), _ptr(sc), _ptr(qz), _float_code(sc, "scales"), int(bool(gptq_v2)), kp.handle, Mw, K, bits,
-                                                  C.byref(cfg), _ptr(A), _ptr(S), ref_dtype, _stream(stream)))
-        return A, S
-    check(B.lib().tmac_hip_pack_gptq_dev(_ptr(qw), _ptr(sc), _ptr(qz), _float_code(sc, "scales"), int(bool(gptq_v2)), Mw, K, bits, C.byref(cfg),
-                                         _ptr(A), _ptr(S), ref_dtype, _stream(stream)))
+    fn, perm = _door("pack_gptq", _kperm(g_idx, cfg.group_size, stream))
+    check(fn(_ptr(qw), _ptr(sc), _ptr(qz), _float_code(sc, "scales"), int(bool(gptq_v2)), *perm, Mw, K, bits, C.byref(cfg), _ptr(A), _ptr(S), ref_dtype,
+             _stream(stream)))
     return A, S
 
 
@@ -216,64 +217,45 @@ def pack_codes(codes, scales, zeros, bits: int, cfg: Optional[KCfg] = None, ref_
     with ``g_idx``: of ``codes[:, perm]``, tmac_hip_pack_codes_perm_dev)"""
     cd, sc, zr, Mw, K, cfg = _codes_args(codes, scales, zeros, bits, cfg, act_group_size)
     A, S = _blob_buffers(Mw, K, bits, cfg, ref_dtype)
-    kp = _kperm(g_idx, cfg.group_size, stream)
-    if kp is not None:
-        check(B.lib().tmac_hip_pack_codes_perm_dev(_ptr(cd), _ptr(sc), _ptr(zr), _float_code(sc, "scales"), kp.handle, Mw, K, bits, C.byref(cfg),
-                                                   _ptr(A), _ptr(S), ref_dtype, _stream(stream)))
-        return A, S
-    check(B.lib().tmac_hip_pack_codes_dev(_ptr(cd), _ptr(sc), _ptr(zr), _float_code(sc, "scales"), Mw, K, bits, C.byref(cfg), _ptr(A), _ptr(S),
-                                          ref_dtype, _stream(stream)))
+    fn, perm = _door("pack_codes", _kperm(g_idx, cfg.group_size, stream))
+    check(fn(_ptr(cd), _ptr(sc), _ptr(zr), _float_code(sc, "scales"), *perm, Mw, K, bits, C.byref(cfg), _ptr(A), _ptr(S), ref_dtype, _stream(stream)))
     return A, S
 
 
 _SRC_CODES = {"float32": B.SRC_F32, "float16": B.SRC_F16, "bfloat16": B.SRC_BF16}
 
 
-def _masters_on_device(weight):
-    """(contiguous 2-D CUDA tensor, tmac_src_dtype_t) of BitNet master weights: a torch tensor in fp32, fp16 or bf16 (uploaded if it is
-    not on the GPU), or a numpy array uploaded as it is -- float32, float16, or uint16 holding bf16 bit patterns (numpy has no bfloat16;
-    what ``checkpoint.read_tensor`` gives for a BF16 tensor).  Nothing is converted on the host."""
+def _floats_on_device(x, what: str = "weight", rank: int = 2):
+    """(contiguous CUDA tensor, tmac_src_dtype_t) of master weights (rank 2) or a layer's bias (``what="bias"``, rank 1): a torch tensor in
+    fp32, fp16 or bf16 (uploaded if it is not on the GPU), or a numpy array uploaded as it is -- float32, float16, or uint16 holding bf16
+    bit patterns (numpy has no bfloat16; what ``checkpoint.read_tensor`` gives for a BF16 tensor).  Nothing is converted on the host."""
     import torch
-    if isinstance(weight, np.ndarray):
-        if weight.dtype == np.uint16:
-            weight = torch.from_numpy(np.ascontiguousarray(weight).view(np.int16)).view(torch.bfloat16)
-        elif weight.dtype in (np.float32, np.float16):
-            weight = torch.from_numpy(np.ascontiguousarray(weight))
+    if isinstance(x, np.ndarray):
+        if x.dtype == np.uint16:
+            x = torch.from_numpy(np.ascontiguousarray(x).view(np.int16)).view(torch.bfloat16)
+        elif x.dtype in (np.float32, np.float16):
+            x = torch.from_numpy(np.ascontiguousarray(x))
         else:
-            raise TypeError(f"weight must be float32, float16 or uint16 (bf16 bit patterns), not {weight.dtype}")
-    name = str(weight.dtype).replace("torch.", "")
+            raise TypeError(f"{what} must be float32, float16 or uint16 (bf16 bit patterns), not {x.dtype}")
+    name = str(x.dtype).replace("torch.", "")
     if name not in _SRC_CODES:
-        raise TypeError(f"weight must be float32, float16 or bfloat16, not {name}")
-    if weight.dim() != 2:
-        raise ValueError("weight is 2-D: [Mw][K]")
-    return weight.cuda().contiguous(), _SRC_CODES[name]
+        raise TypeError(f"{what} must be float32, float16 or bfloat16, not {name}")
+    if x.dim() != rank:
+        raise ValueError(f"{what} is {rank}-D: {'[Mw][K]' if rank == 2 else '[Mw]'}")
+    return x.cuda().contiguous(), _SRC_CODES[name]
 
 
-def _bias_on_device(bias):
-    """(contiguous 1-D CUDA tensor, tmac_src_dtype_t) of a layer's bias: a torch tensor in fp32, fp16 or bf16 (uploaded if it is not on
-    the GPU), or a numpy array uploaded as it is -- float32, float16, or uint16 holding bf16 bit patterns.  Nothing is converted on the
-    host."""
+def _invalid_counter(wanted: bool):
+    """the int32 counter of a ``count_invalid`` call, or None: 16 bytes, the calls' alignment rule; its first element is the count"""
     import torch
-    if isinstance(bias, np.ndarray):
-        if bias.dtype == np.uint16:
-            bias = torch.from_numpy(np.ascontiguousarray(bias).view(np.int16)).view(torch.bfloat16)
-        elif bias.dtype in (np.float32, np.float16):
-            bias = torch.from_numpy(np.ascontiguousarray(bias))
-        else:
-            raise TypeError(f"bias must be float32, float16 or uint16 (bf16 bit patterns), not {bias.dtype}")
-    name = str(bias.dtype).replace("torch.", "")
-    if name not in _SRC_CODES:
-        raise TypeError(f"bias must be float32, float16 or bfloat16, not {name}")
-    if bias.dim() != 1:
-        raise ValueError("bias is 1-D: [Mw]")
-    return bias.cuda().contiguous(), _SRC_CODES[name]
+    return torch.empty(4, dtype=torch.int32, device="cuda") if wanted else None
 
 
 def _bitnet_args(weight, cfg, m_groups, eps, scale):
     """device tensors, shape and configuration of a BitNet matrix.  Without a cfg: the unified-scale configuration ``from_codes`` is handed
     for BitNet -- ``convert.default_bm``, kfactor 16, one activation group per row (act_group_size = K).  With one, its m_groups counts."""
     from . import convert
-    w, src = _masters_on_device(weight)
+    w, src = _floats_on_device(weight)
     Mw, K = int(w.shape[0]), int(w.shape[1])
     if cfg is None:
         cfg = KCfg.make(Mw, K, 2, convert.default_bm(2, Mw), 16, 128, K, False, int(m_groups))
@@ -291,7 +273,7 @@ def absmean(weight, m_groups: int = 1, eps: float = 1e-5, stream=None):
     """The BitNet absmean scales of master weights [Mw][K] (fp32 / fp16 / bf16, see ``Weights.from_bitnet``): fp32 [m_groups] on the GPU,
     ``max(mean |w|, eps)`` per block of Mw / m_groups rows, the mean accumulated in fp64 (tmac_hip_absmean_dev)."""
     import torch
-    w, src = _masters_on_device(weight)
+    w, src = _floats_on_device(weight)
     out = torch.empty(max(int(m_groups), 1), dtype=torch.float32, device="cuda")
     check(B.lib().tmac_hip_absmean_dev(_ptr(w), src, int(w.shape[0]), int(w.shape[1]), int(m_groups), float(eps), _ptr(out), _stream(stream)))
     return out
@@ -342,19 +324,18 @@ def pack_ternary(packed, scale, cfg: Optional[KCfg] = None, ref_dtype=F32, strea
     returns them, exactly ``weights.preprocess_weights`` of the unpacked levels.  ``scale``: a float or fp32 [m_groups], the s of
     ``w_real = (level - 2) * s`` (``convert.bitnet_packed_scale`` of a checkpoint's ``weight_scale``).  ``count_invalid``: a third
     result, an int32 CUDA tensor of one element -- the number of fields of value 3 (they are packed as level 3).  Asynchronous."""
-    import torch
     pk, sc, Mw, K, cfg = _bitnet_packed_args(packed, scale, cfg)
     A, S = _blob_buffers(Mw, K, 2, cfg, ref_dtype)
-    n = torch.empty(4, dtype=torch.int32, device="cuda") if count_invalid else None      # 16 bytes: the call's alignment rule
+    n = _invalid_counter(count_invalid)
     check(B.lib().tmac_hip_pack_ternary_dev(_ptr(pk), _ptr(sc), Mw, K, C.byref(cfg), _ptr(A), _ptr(S), ref_dtype, _ptr(n), _stream(stream)))
     return (A, S, n[:1]) if count_invalid else (A, S)
 
 
 def _dense_args(weight, bits, group_size, zero_point, cfg, act_group_size):
-    """device tensor, shape and configuration of an unquantised matrix (``_masters_on_device`` says what it may be).  Without a cfg:
+    """device tensor, shape and configuration of an unquantised matrix (``_floats_on_device`` says what it may be).  Without a cfg:
     per-group scales of ``group_size``, ``convert.default_bm``, kfactor 16."""
     from . import convert
-    w, src = _masters_on_device(weight)
+    w, src = _floats_on_device(weight)
     Mw, K = int(w.shape[0]), int(w.shape[1])
     if cfg is None:
         cfg = KCfg.make(Mw, K, int(bits), convert.default_bm(int(bits), Mw), 16, int(group_size), act_group_size, bool(zero_point))
@@ -366,12 +347,12 @@ def rtn_params(weight, bits: int, group_size: int, zero_point: bool = True, scal
     fp32 [Mw][K/group_size] CUDA tensors -- ``convert.rtn_params``'s, bit for bit (tmac_hip_rtn_params_dev).  ``count_invalid``: a third
     result, an int32 CUDA tensor of one element -- the number of groups that cannot be quantised.  Asynchronous."""
     import torch
-    w, src = _masters_on_device(weight)
+    w, src = _floats_on_device(weight)
     Mw, K = int(w.shape[0]), int(w.shape[1])
     sg = K // int(group_size) if int(group_size) > 0 else 0
     sc = torch.empty((Mw, sg), dtype=torch.float32, device="cuda")
     zq = torch.empty((Mw, sg), dtype=torch.float32, device="cuda")
-    n = torch.empty(4, dtype=torch.int32, device="cuda") if count_invalid else None      # 16 bytes: the call's alignment rule
+    n = _invalid_counter(count_invalid)
     check(B.lib().tmac_hip_rtn_params_dev(_ptr(w), src, Mw, K, int(bits), int(group_size), int(bool(zero_point)), int(bool(scale_f16)), _ptr(sc), _ptr(zq),
                                           _ptr(n), _stream(stream)))
     return (sc, zq, n[:1]) if count_invalid else (sc, zq)
@@ -382,10 +363,9 @@ def pack_rtn(weight, bits: int, group_size: int = 128, zero_point: bool = True, 
     """An unquantised matrix -> the reference blob of its round-to-nearest codes, on the GPU (tmac_hip_pack_rtn_dev): (A_ref uint8,
     scales_ref) as ``pack_codes`` returns them, exactly ``weights.preprocess_weights(*convert.rtn_quant(weight, bits, group_size,
     zero_point, ref_dtype == F16))`` -- a blob of fp16 scales holds the scales that divided.  ``count_invalid``: as in ``rtn_params``."""
-    import torch
     w, src, Mw, K, cfg = _dense_args(weight, bits, group_size, zero_point, cfg, act_group_size)
     A, S = _blob_buffers(Mw, K, int(bits), cfg, ref_dtype)
-    n = torch.empty(4, dtype=torch.int32, device="cuda") if count_invalid else None
+    n = _invalid_counter(count_invalid)
     check(B.lib().tmac_hip_pack_rtn_dev(_ptr(w), src, Mw, K, int(bits), C.byref(cfg), _ptr(A), _ptr(S), ref_dtype, _ptr(n), _stream(stream)))
     return (A, S, n[:1]) if count_invalid else (A, S)
 
@@ -415,12 +395,8 @@ class Weights:
         h = C.c_void_p()
         ref = _float_code(sc, "scales")        # the blob in the scales' own dtype: nothing is rounded on the way
         kp = _kperm(g_idx, cfg.group_size, stream)
-        if kp is not None:
-            check(B.lib().tmac_hip_register_weights_gptq_perm_dev(C.byref(h), _ptr(qw), _ptr(sc), _ptr(qz), ref, int(bool(gptq_v2)), kp.handle, Mw, K,
-                                                                  bits, C.byref(cfg), ref, dev_dtype, _stream(stream)))
-        else:
-            check(B.lib().tmac_hip_register_weights_gptq_dev(C.byref(h), _ptr(qw), _ptr(sc), _ptr(qz), ref, int(bool(gptq_v2)), Mw, K, bits,
-                                                             C.byref(cfg), ref, dev_dtype, _stream(stream)))
+        fn, perm = _door("register_weights_gptq", kp)
+        check(fn(C.byref(h), _ptr(qw), _ptr(sc), _ptr(qz), ref, int(bool(gptq_v2)), *perm, Mw, K, bits, C.byref(cfg), ref, dev_dtype, _stream(stream)))
         self = cls._adopt(h, Mw, K, bits, cfg)
         self.kperm = kp
         return self._with_bias(bias, stream)
@@ -450,12 +426,8 @@ class Weights:
         h = C.c_void_p()
         ref = _float_code(sc, "scales")
         kp = _kperm(g_idx, cfg.group_size, stream)
-        if kp is not None:
-            check(B.lib().tmac_hip_register_weights_codes_perm_dev(C.byref(h), _ptr(cd), _ptr(sc), _ptr(zr), ref, kp.handle, Mw, K, bits, C.byref(cfg),
-                                                                   ref, dev_dtype, _stream(stream)))
-        else:
-            check(B.lib().tmac_hip_register_weights_codes_dev(C.byref(h), _ptr(cd), _ptr(sc), _ptr(zr), ref, Mw, K, bits, C.byref(cfg), ref, dev_dtype,
-                                                              _stream(stream)))
+        fn, perm = _door("register_weights_codes", kp)
+        check(fn(C.byref(h), _ptr(cd), _ptr(sc), _ptr(zr), ref, *perm, Mw, K, bits, C.byref(cfg), ref, dev_dtype, _stream(stream)))
         self = cls._adopt(h, Mw, K, bits, cfg)
         self.kperm = kp
         return self._with_bias(bias, stream)
@@ -533,7 +505,7 @@ class Weights:
         """y = W x + b from now on (tmac_hip_weights_set_bias_dev): ``bias`` is [Mw] in fp32, fp16 or bf16 -- a CUDA tensor, or a numpy
         array uploaded first (uint16 = bf16 bit patterns).  The handle keeps an fp32 copy of its own.  Once per handle, straight after
         registration; unified-scale and act-order handles are refused (TMACHipError)."""
-        b, src = _bias_on_device(bias)
+        b, src = _floats_on_device(bias, "bias", 1)
         if int(b.shape[0]) != self.Mw:
             raise ValueError(f"bias holds {int(b.shape[0])} values: one per output row, Mw = {self.Mw}")
         check(B.lib().tmac_hip_weights_set_bias_dev(self._h, _ptr(b), src, _stream(stream)))
