@@ -492,8 +492,8 @@ int32_t tmac_hip_debug_experts_plan(int K, int bits, int group_size, const int* 
  * workspace and launches once.  It never reads the routing on the host: capturable after the workspace's first use, and replays follow
  * a routing rewritten on the device.  tmac_hip_debug_experts_gemm_plan: the launch plan of such a call with outputs of P positions
  * (pure, no device), or its refusal -- P != 64 T_max of (N, S, E) among them.
- * Open: a 32-position tile for layers with few tokens per expert, unified-scale banks, a fused router, ggml mul_mat_id glue, the
- * persistent and deferred paths. */
+ * Open: a 32-position tile for layers with few tokens per expert, unified-scale banks, ggml mul_mat_id glue, the persistent and
+ * deferred paths. */
 int32_t tmac_hip_experts_rows_sizes(int N, int S, int E, int32_t* T_max, int32_t* P);
 int32_t tmac_hip_experts_route_dev(const int32_t* ids_dev, int N, int S, int E, int32_t* tile_expert_dev, int32_t* src_dev, int32_t* pos_dev,
                                    void* stream);
@@ -504,6 +504,37 @@ int32_t tmac_hip_qgemm_experts_rows_dev(const tmac_hip_bank* const* banks, int n
                                         tmac_dtype_t out_dtype, void* stream);
 int32_t tmac_hip_debug_experts_gemm_plan(int K, int bits, int group_size, const int* bank_Mw, int nbanks, int N, int S, int E, int P,
                                          int32_t* grid_x, int32_t* grid_y, size_t* lds_bytes);
+
+/* ---- the fused router: logits, softmax and top-k in one launch ------------------------------------------------------------------------
+ * tmac_hip_experts_router_dev (k_experts_router) makes the ids and gates the calls above read.  For every token row n of x_dev [N][K]
+ * (act_dtype) and a dense router matrix Wr_dev [E][K] (w_dtype; each TMAC_F16 or TMAC_F32 -- bf16 router weights are the caller's to widen
+ * to fp32, which is exact):
+ *   1. logit[n][e] = sum_k x[n][k] Wr[e][k], accumulated in fp32 on the matrix cores (both operands fp16: the f16 instruction; else the fp32
+ *      one, an fp16 operand widened exactly);
+ *   2. p = softmax(logit[n][:]) over all E experts, in fp32, the row's maximum subtracted;
+ *   3. ids_dev[n][0..S): the S experts of largest logit, largest first; among equal logits (-0 = +0) the lower expert id wins;
+ *   4. gates_dev[n][s] = p[ids[n][s]]; with TMAC_ROUTER_RENORM divided by the sum of the S selected values (Mixtral's softmax over the
+ *      selected logits, Qwen-MoE's norm_topk_prob).  Every division is a true division.
+ * ids_dev int32 [N][S] and gates_dev fp32 [N][S] are the layouts tmac_hip_qgemm_experts_dev, tmac_hip_experts_route_dev and
+ * tmac_hip_experts_combine_dev take: nothing is cast or copied in between.  logits_dev (fp32 [N][E], may be NULL) receives the logits.
+ * For ANY input bits, NaN and +-Inf included, the S ids of a token are distinct and lie in [0, E): the selection orders an integer key made
+ * of the fp32 bits with the expert index as the low part, in which a NaN has a place (beyond the infinity of its sign); no id is ever an
+ * empty slot's.  (Gates of a row that holds a NaN or a +Inf are NaN.)  A token's logits, ids and gates are the same bits at N = 1 and at
+ * any place in a batch: the walk over K depends on (K, E) alone.
+ * Limits, refused by name with TMAC_HIP_E_ARG before any launch: 1 <= S <= 8, S <= E <= 256, N >= 1, N S <= 32768, K a multiple of 64;
+ * Wr_dev and x_dev 16-byte aligned, ids_dev, gates_dev and logits_dev 4-byte; flag bits other than TMAC_ROUTER_RENORM; a NULL pointer
+ * other than logits_dev.  The call creates, reads and invalidates nothing in the library workspace and reads nothing on the host: it is
+ * capturable on a stream the library has never seen, and replays follow a rewritten x.  It runs behind the calling thread's deferred
+ * queue and is refused inside a recording.  One workgroup serves 32 tokens: at N = 1 one compute unit reads all of Wr.
+ * tmac_hip_debug_experts_router_plan: the launch plan of such a call (pure, no device) -- waves that multiply, column tiles of 32 experts,
+ * K slices, 64-value steps per slice, workgroups, LDS bytes -- or its refusal.
+ * Open: sigmoid scoring, a correction bias, grouped top-k (DeepSeek-V3), a split of one token tile's K over several workgroups. */
+#define TMAC_ROUTER_RENORM 1u
+int32_t tmac_hip_experts_router_dev(const void* Wr_dev, tmac_dtype_t w_dtype, const void* x_dev, tmac_dtype_t act_dtype,
+                                    int N, int K, int E, int S, uint32_t flags,   /* TMAC_ROUTER_RENORM = 1 */
+                                    int32_t* ids_dev, float* gates_dev, float* logits_dev /* may be NULL */, void* stream);
+int32_t tmac_hip_debug_experts_router_plan(int K, int E, int S, int N, tmac_dtype_t w_dtype, tmac_dtype_t act_dtype, int32_t* waves,
+                                           int32_t* col_tiles, int32_t* k_slices, int32_t* steps_per_slice, int32_t* grid, size_t* lds_bytes);
 
 /* ---- deferred launches ---------------------------------------------------------------------
  * For callers that do not record (a backend hook called mat-mul by mat-mul).  tmac_hip_defer(1): from now on the calling thread's N = 1

@@ -152,6 +152,9 @@ def load_library() -> C.CDLL:
         "tmac_hip_qgemm_experts_rows_dev": ([C.POINTER(vp), C.c_int, vp, C.c_int, C.c_int, vp, vp, C.c_int, C.c_int, C.POINTER(vp), C.c_int, vp], i32),
         "tmac_hip_debug_experts_gemm_plan": ([C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int), C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
                                               C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(sz)], i32),
+        # ... and the fused router in front of them (logits, softmax, top-k -> ids, gates), its plan
+        "tmac_hip_experts_router_dev": ([vp, C.c_int, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_uint32, vp, vp, vp, vp], i32),
+        "tmac_hip_debug_experts_router_plan": ([C.c_int] * 6 + [C.POINTER(C.c_int32)] * 5 + [C.POINTER(sz)], i32),
         "tmac_hip_qgemm_fused_xf_dev": ([C.POINTER(vp), C.c_int, vp, C.c_int, C.POINTER(XForm), C.POINTER(vp), C.c_int, vp], i32),
         "tmac_hip_qgemm_fused_xf_rows_dev": ([C.POINTER(vp), C.c_int, vp, C.c_int, C.POINTER(XForm), C.POINTER(vp), C.c_int, C.c_int, vp], i32),
         "tmac_hip_debug_xf_rows_plan": ([C.POINTER(vp), C.c_int, C.POINTER(vp), C.c_int, C.POINTER(C.c_int32), C.POINTER(C.c_int32)], i32),
@@ -235,7 +238,8 @@ def load_library() -> C.CDLL:
                 "tmac_hip_bank_create", "tmac_hip_bank_free", "tmac_hip_bank_info", "tmac_hip_qgemm_experts_dev", "tmac_hip_debug_experts_plan",
                 "tmac_hip_experts_rows_sizes", "tmac_hip_experts_route_dev", "tmac_hip_experts_combine_dev",
                 "tmac_hip_qgemm_experts_rows_dev", "tmac_hip_debug_experts_gemm_plan",
-                "tmac_hip_qgemm_experts_fused_dev", "tmac_hip_debug_experts_fused_plan"} if os.environ.get("TMAC_HIP_LIB") else set()
+                "tmac_hip_qgemm_experts_fused_dev", "tmac_hip_debug_experts_fused_plan",
+                "tmac_hip_experts_router_dev", "tmac_hip_debug_experts_router_plan"} if os.environ.get("TMAC_HIP_LIB") else set()
     for name, (argt, rest) in sigs.items():
         try:
             fn = getattr(L, name)

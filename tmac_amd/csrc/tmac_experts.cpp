@@ -135,6 +135,56 @@ extern "C" int32_t tmac_hip_experts_combine_dev(const float* C_dev, const int32_
     return TMAC_HIP_OK;
 }
 
+// ---- the fused router in front of both: logits, softmax and top-S in one launch (k_experts_router).  Nothing of the
+//      library workspace is created, read or invalidated; nothing is read on the host. -------------------------------------------------------
+// dtypes and the plan of a router call, or the refusal that names the field (pure)
+static int32_t router_plan_check(int K, int E, int S, int N, tmac_dtype_t w_dtype, tmac_dtype_t act_dtype, ExpertsRouterPlan& p) {
+    if ((w_dtype != TMAC_F16 && w_dtype != TMAC_F32) || (act_dtype != TMAC_F16 && act_dtype != TMAC_F32))
+        return fail(TMAC_HIP_E_ARG, "experts router: w_dtype and act_dtype must be TMAC_F32 or TMAC_F16");
+    if (!experts_router_plan(K, E, S, N, act_dtype == TMAC_F16, w_dtype == TMAC_F16, p))
+        return fail(TMAC_HIP_E_ARG, "experts router (N=%d, K=%d, E=%d, S=%d): %s", N, K, E, S, p.why);
+    return TMAC_HIP_OK;
+}
+
+extern "C" int32_t tmac_hip_debug_experts_router_plan(int K, int E, int S, int N, tmac_dtype_t w_dtype, tmac_dtype_t act_dtype, int32_t* waves,
+                                                      int32_t* col_tiles, int32_t* k_slices, int32_t* steps_per_slice, int32_t* grid, size_t* lds_bytes) {
+    ExpertsRouterPlan p;
+    const int32_t rc = router_plan_check(K, E, S, N, w_dtype, act_dtype, p);
+    if (rc) return rc;
+    if (waves) *waves = p.waves;
+    if (col_tiles) *col_tiles = p.ctiles;
+    if (k_slices) *k_slices = p.slices;
+    if (steps_per_slice) *steps_per_slice = p.steps;
+    if (grid) *grid = p.gx;
+    if (lds_bytes) *lds_bytes = p.lds_bytes;
+    return TMAC_HIP_OK;
+}
+
+extern "C" int32_t tmac_hip_experts_router_dev(const void* Wr_dev, tmac_dtype_t w_dtype, const void* x_dev, tmac_dtype_t act_dtype, int N, int K, int E, int S,
+                                               uint32_t flags, int32_t* ids_dev, float* gates_dev, float* logits_dev, void* stream) {
+    const int32_t drc = ensure_device();
+    if (drc) return drc;
+    if (!Wr_dev || !x_dev || !ids_dev || !gates_dev) return fail(TMAC_HIP_E_ARG, "null Wr_dev, x_dev, ids_dev or gates_dev");
+    if (flags & ~(uint32_t)TMAC_ROUTER_RENORM) return fail(TMAC_HIP_E_ARG, "flags=0x%x: unknown bits (TMAC_ROUTER_RENORM is the one flag)", flags);
+    ExpertsRouterPlan p;
+    const int32_t prc = router_plan_check(K, E, S, N, w_dtype, act_dtype, p);
+    if (prc) return prc;
+    if (misaligned(Wr_dev, ACT_ALIGN) || misaligned(x_dev, ACT_ALIGN))
+        return fail(TMAC_HIP_E_ARG, "Wr_dev and x_dev must be %zu-byte aligned (rows are read 16 bytes at a time)", ACT_ALIGN);
+    if (misaligned(ids_dev, 4) || misaligned(gates_dev, 4) || misaligned(logits_dev, 4))
+        return fail(TMAC_HIP_E_ARG, "ids_dev, gates_dev and logits_dev must be 4-byte aligned");
+    if (chain_recording()) return fail(TMAC_HIP_E_ARG, "tmac_hip_experts_router_dev cannot be recorded (tmac_hip_chain_begin ... _end): expert calls run stand-alone");
+    const int32_t rc = defer_barrier();       // never queued: behind the calling thread's queue (x_dev may be a queued call's output)
+    if (rc) return rc;
+    ExpertsRouterArgs a;
+    a.Wr = Wr_dev; a.x = x_dev; a.w_f16 = w_dtype == TMAC_F16; a.x_f16 = act_dtype == TMAC_F16;
+    a.N = N; a.K = K; a.E = E; a.S = S; a.renorm = (flags & TMAC_ROUTER_RENORM) != 0;
+    a.ids = ids_dev; a.gates = gates_dev; a.logits = logits_dev;
+    const hipError_t e = launch_experts_router(a, p, (hipStream_t)stream);
+    if (e != hipSuccess) return fail(TMAC_HIP_E_RUNTIME, "experts router launch: %s", hipGetErrorString(e));
+    return TMAC_HIP_OK;
+}
+
 hipError_t tmac::launch_gemv_experts(const ExpertsArgs& a_in, hipStream_t st) {
     ExpertsArgs a = a_in;
     const Shape& s = a.s;

@@ -366,6 +366,19 @@ hipError_t launch_lut_image_pos(const void* x, int act_f16, const int32_t* src, 
 hipError_t launch_gemm_experts(const ExpertsGemmArgs& a, const ExpertsGemmPlan& p, hipStream_t st);
 template <int BITS>
 hipError_t launch_gemm_experts_unit(const ExpertsGemmArgs& a, const ExpertsGemmPlan& p, hipStream_t st);
+// The fused router in front of them (tmac_experts_router.hip): logits = x Wr^T, softmax, top-S -> ids, gates.
+struct ExpertsRouterArgs {
+    const void* Wr;          // device, [E][K], fp16 or fp32
+    const void* x;           // device, [N][K], fp16 or fp32
+    int w_f16, x_f16;
+    int N, K, E, S;
+    int renorm;              // gates divided by the sum of the S selected
+    int32_t* ids;            // device, [N][S]
+    float* gates;            // device, [N][S]
+    float* logits;           // device, [N][E], or null
+};
+// k_experts_router<HH>: one launch of p.gx workgroups (p: experts_router_plan of the same K, E, S, N)
+hipError_t launch_experts_router(const ExpertsRouterArgs& a, const ExpertsRouterPlan& p, hipStream_t st);
 // returns hipErrorInvalidValue when the variant does not cover the configuration
 hipError_t launch_gemv(const GemvArgs& a, Variant v, hipStream_t st);
 bool gemv_lo_supported(const Shape& s);

@@ -233,6 +233,29 @@ bool experts_rows_sizes(long long N, long long S, long long E, ExpertsRowsSizes&
     return true;
 }
 
+bool experts_router_plan(long long K, long long E, long long S, long long N, bool x_f16, bool w_f16, ExpertsRouterPlan& p) {
+    (void)x_f16; (void)w_f16;      // (the two arithmetics walk K alike)
+    p = ExpertsRouterPlan{nullptr, 0, 0, 0, 0, 0, 0, 0};
+    if (N < 1) p.why = "N: at least one token";
+    else if (S < 1 || S > EXPERTS_MAX_SLOTS) p.why = "S: 1 to 8 experts per token";
+    else if (E < S) p.why = "E: at least S experts (S <= E)";
+    else if (E > ROUTER_MAX_E) p.why = "E: the router takes at most 256 experts";
+    else if (N * S > EXPERTS_ROWS_MAX_NS) p.why = "N x S: the router takes at most 32768 slots";
+    else if (K < ROUTER_KSTEP || K % ROUTER_KSTEP != 0 || K > (1 << 24)) p.why = "K: a multiple of 64 (up to 2^24)";
+    if (p.why) return false;
+    const int nsteps = (int)(K / ROUTER_KSTEP);
+    p.ctiles = (int)((E + 31) / 32);
+    const int want = ROUTER_NWV / p.ctiles < nsteps ? ROUTER_NWV / p.ctiles : nsteps;
+    p.steps = (nsteps + want - 1) / want;
+    p.slices = (nsteps + p.steps - 1) / p.steps;         // (no empty slice)
+    p.waves = p.ctiles * p.slices;
+    p.e_pad = 32 * p.ctiles;
+    p.gx = (int)((N + ROUTER_TOKENS - 1) / ROUTER_TOKENS);
+    p.lds_bytes = sizeof(float) * p.slices * ROUTER_TOKENS * p.e_pad;
+    if (p.lds_bytes > ROWS_LDS_MAX) { p.why = "the slices' partial tiles do not fit LDS"; return false; }
+    return true;
+}
+
 bool experts_gemm_plan(const Shape& s, const int* bank_Mw, int nbanks, long long N, long long S, long long E, long long P, ExpertsGemmPlan& p) {
     p = ExpertsGemmPlan{nullptr, 0, 0, {0, 0}, 0};
     auto refuse = [&](const char* why) { p.why = why; return false; };

@@ -157,6 +157,24 @@ struct ExpertsGemmPlan {
 // (32-bit buffer offsets) and P != 64 T_max of (N, S, E).  Pure.  Returns why == null.
 bool experts_gemm_plan(const Shape& s, const int* bank_Mw, int nbanks, long long N, long long S, long long E, long long P, ExpertsGemmPlan& p);
 
+// ---- the fused router: k_experts_router<HH> (tmac_experts_router.hip) ---------------------------------------------------------------------
+// logits = x Wr^T on the matrix cores, softmax and top-S in one launch.  One workgroup of 16 waves serves a tile of 32 tokens; its waves
+// are dealt over (column tile of 32 experts) x (K slice): wave w = slice * ctiles + column tile.  K is walked in steps of 64 values; slice i
+// owns the steps [i steps, (i + 1) steps), the last slice what is left.  ctiles, slices and steps follow from (K, E) alone -- never from
+// N: a token's bits do not depend on its batch.  LDS: the slices' partial tiles, [slices][32][e_pad] fp32.
+constexpr int ROUTER_NWV = 16, ROUTER_FT = 64 * ROUTER_NWV, ROUTER_TOKENS = 32, ROUTER_KSTEP = 64, ROUTER_MAX_E = 256;
+struct ExpertsRouterPlan {
+    const char* why;         // null: served
+    int waves;               // waves that run MFMAs: ctiles * slices <= 16 (every wave of the 16 selects)
+    int ctiles, slices;      // column tiles of 32 experts; K slices
+    int steps;               // steps of 64 values per slice (the last slice: K / 64 - (slices - 1) steps, at least one)
+    int e_pad;               // 32 ctiles
+    int gx;                  // ceil(N / 32)
+    size_t lds_bytes;
+};
+// Pure.  Returns why == null.  (x_f16 && w_f16: the f16 matrix instruction; else the fp32 one: the plan is the same.)
+bool experts_router_plan(long long K, long long E, long long S, long long N, bool x_f16, bool w_f16, ExpertsRouterPlan& p);
+
 // ---- k_decode_chain<BITS, ZP, SCF16, SM, XF, TAP, G2, GT> ---------------------------------------------------------------------------
 // The tap's instance carries the transforms too, and a gate other than silu belongs to a transform: TAP and GT imply XF.  Unified scales
 // (SM 2) have one scale per matrix: no G2 instance (two scale groups per lane and item), and no zero points.

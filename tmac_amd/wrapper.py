@@ -1057,6 +1057,44 @@ class TMACGeMMWrapper:
                                                       _dtype_code(outs[0]), _stream(stream)))
         return outs
 
+    def experts_router(self, x, Wr, S: int, renorm: bool = False, out=None, logits=None, stream=None):
+        """The router of a mixture-of-experts layer in one launch (tmac_hip_experts_router_dev): ``logits = x @ Wr.T`` on the matrix cores
+        in fp32, a softmax over all E experts and the S largest, largest first, the lower id among equal logits.  ``x``: CUDA fp16 / fp32
+        ``[K]`` or ``[N, K]``; ``Wr``: CUDA fp16 / fp32 ``[E, K]`` (bf16: widen to fp32, which is exact); S <= 8, S <= E <= 256, K a
+        multiple of 64.  Returns ``(ids, gates)``, CUDA int32 and fp32, ``[S]`` for a 1-D ``x`` and ``[N, S]`` otherwise: the tensors
+        ``experts`` / ``experts_route`` / ``experts_combine`` take as they are.  ``gates[n, s] = softmax(logits[n])[ids[n, s]]``, with
+        ``renorm`` divided by the sum over the S selected.  ``out``: the ``(ids, gates)`` pair to write instead; ``logits``: a CUDA fp32
+        ``[N, E]`` tensor that receives the logits.  The ids of a token are distinct and in [0, E) for any input bits.  Nothing is copied
+        to the host.  A layer, torch left only for the activation function::
+
+            ids, gates = wr.experts_router(x, Wr, S, renorm=True)             # x [N, K]
+            route = wr.experts_route(ids, E)
+            g, u = wr.experts_rows([gate, up], x, route, S)
+            (d,) = wr.experts_rows(down, torch.nn.functional.silu(g) * u, route, S)
+            y = wr.experts_combine(d, route, gates)                           # [N, Mw]
+
+        and for one token::
+
+            ids, gates = wr.experts_router(x, Wr, S, renorm=True)             # x [K]
+            g, u = wr.experts([gate, up], x, ids, build="kernel")
+            y = wr.experts(down, g, ids, gates=gates, glu="glu", in2=u)
+        """
+        import torch
+        if x.dim() not in (1, 2) or Wr.dim() != 2 or not x.is_contiguous() or not Wr.is_contiguous() or int(x.shape[-1]) != int(Wr.shape[1]):
+            raise TypeError("x is a contiguous [K] or [N, K] tensor and Wr a contiguous [E, K] tensor")
+        N, K, E, S = (1 if x.dim() == 1 else int(x.shape[0])), int(Wr.shape[1]), int(Wr.shape[0]), int(S)
+        shape = (S,) if x.dim() == 1 else (N, S)
+        if out is None:
+            out = (torch.empty(shape, dtype=torch.int32, device=x.device), torch.empty(shape, dtype=torch.float32, device=x.device))
+        ids, gates = out
+        if ids.dtype != torch.int32 or gates.dtype != torch.float32 or any(not t.is_cuda or not t.is_contiguous() or int(t.numel()) != N * S for t in out):
+            raise TypeError(f"out is (ids, gates): contiguous CUDA int32 and float32 tensors of {N * S} elements")
+        if logits is not None and (logits.dtype != torch.float32 or not logits.is_cuda or not logits.is_contiguous() or int(logits.numel()) != N * E):
+            raise TypeError(f"logits is a contiguous CUDA float32 tensor of {N * E} elements")
+        check(B.lib().tmac_hip_experts_router_dev(_ptr(Wr), _dtype_code(Wr), _ptr(x), _dtype_code(x), N, K, E, S, 1 if renorm else 0, _ptr(ids),
+                                                  _ptr(gates), _ptr(logits), _stream(stream)))
+        return ids, gates
+
     def record_gather(self, send_dev, recv_dev, bytes_per_rank: int, rank: int, world: int) -> None:
         """while recording a chain: the exchange step ``recv = all-gather over the ranks of send`` (what ``Comm.allgather`` records
         by itself); inside the launch it becomes part of the hand-off"""
